@@ -11,6 +11,13 @@ Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel (K2) with
 SURVEY.md section 8d's algorithmic bytes per pair against 8 TB/s; `cpu_baseline`
 times the CPU oracle (this repo's restatement -- the reference's own engine
 source is absent, so kind = "port") on the same workload on the host cores.
+
+A plain run does only what the headline needs: set-up, settling and warm-up steps, the
+--steps timed steps, --dump-outputs when given, the line.  Everything else it can
+measure or check (the per-step median and per-kernel passes, live PMC traffic, the
+other search modes, the realistic input, the other workloads, configs[3]'s strong
+shape, parity against the CPU oracle, cpu_baseline) runs behind the timed region with
+--full only.
 """
 from __future__ import annotations
 
@@ -180,10 +187,11 @@ def bench_c1(args, aof, rank, world, dist):
     flow = aof.OpticalFlowPX4(216.6677, 216.2457, 15, 64, 64)
     calls = args.pairs
     t_us = [0]
+    res = [None] * calls   # what the calls of the latest step returned
 
     def step():
         for k in range(calls):
-            flow.calcFlow(frames[k & 63], t_us[0])
+            res[k] = flow.calcFlow(frames[k & 63], t_us[0])
             t_us[0] = (t_us[0] + 13333) & 0xFFFFFFFF
 
     for _ in range(args.warmup):
@@ -199,6 +207,13 @@ def bench_c1(args, aof, rank, world, dist):
            "config": {"workload": "C1 64x64 frames, PX4Flow 5x5 sparse grid, facade OpticalFlowPX4::calcFlow, "
                                   "host buffers (PCIe-inclusive)", "calls_per_step": calls,
                       "us_per_call": round(elapsed / (args.steps * calls) * 1e6, 2)}}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"calc_flow": np.array(res, dtype=[("quality", "<i4"), ("dt_us", "<i4"),
+                                                                           ("flow_x", "<f4"), ("flow_y", "<f4")])})
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        return
     # the class mainloop.cpp:423 actually creates, at the reference's default crop (main.cpp:57-58):
     # OpticalFlowOpenCV, 128x128, two levels + mean equalisation
     frames2, _ = synth.make_sequence(128, 128, 64, 8, seed=2, max_step=6)
@@ -273,6 +288,8 @@ def bench_ingest(args, aof, device, rank, world, dist):
         t = torch.tensor([elapsed], dtype=torch.float64, device=device if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"cropped": cropped.cpu().numpy(), "hist": hist.cpu().numpy().view(np.uint32)})
     k_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))  # memset + kernel on torch's stream
     alg = 2 * crop * crop + 40
     achieved = alg * n / (k_ms * 1e-3) / 1e9
@@ -285,7 +302,7 @@ def bench_ingest(args, aof, device, rank, world, dist):
                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": pmc_traffic(f"ingest:{n}")[0],
                         "traffic_source": pmc_traffic(f"ingest:{n}")[1], "kernel": "k_ingest (K0)",
                         "kernel_ms": round(k_ms, 5), "algorithmic_bytes_per_frame": alg, "frames_per_launch": n}}
-    if rank == 0:
+    if rank == 0 and args.full:
         from oracle import pyoracle as orc
         hc = cam[:4].cpu().numpy()
         ok = True
@@ -307,6 +324,7 @@ def bench_ingest(args, aof, device, rank, world, dist):
             out["cpu_baseline"] = {"value": round(done / spent, 1), "unit": "frames/s", "cores": 1, "kind": "port",
                                    "sample": f"{done} frames, scalar C oracle restating mainloop.cpp:295-298,203-214, "
                                              f"one thread, {spent:.1f} s"}
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()
@@ -351,6 +369,14 @@ def bench_sequence(args, aof, device, rank, world, dist):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     out = eng.sequence_outputs(sp, ws, L, n)
+    if args.dump_outputs and rank == 0:
+        mav = np.zeros((len(out["mavlink"]), aof.SEQ_FRAME_BYTES), dtype=np.uint8)
+        for i, m in enumerate(out["mavlink"]):
+            mav[i, :len(m)] = np.frombuffer(m, dtype=np.uint8)
+        dump_outputs(args.dump_outputs, {
+            "records": out["records"], "frames_sent": out["frames_sent"], "status": out["status"], "cropped": out["cropped"],
+            "exposure": out["exposure"], "flows": out["flows"], "derotated": out["derotated"], "mavlink": mav,
+            "mavlink_len": np.array([len(m) for m in out["mavlink"]], dtype=np.int16)})
     step_ms = elapsed / args.steps * 1e3
     # compulsory bytes per frame: the crop region of the sensor frame read once, the cropped frame written once
     # and read twice by the flow (it is cur of one pair and prev of the next), 16 B flow record, ~56 B of frame
@@ -368,7 +394,7 @@ def bench_sequence(args, aof, device, rank, world, dist):
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None, "kernel": "whole pipeline (all kernels of one call)",
                          "kernel_ms": round(step_ms, 5), "algorithmic_bytes_per_frame": alg, "frames_per_launch": n}}
-    if rank == 0:
+    if rank == 0 and args.full:
         from oracle import pyoracle as orc
         # parity on a prefix: the oracle's calcFlow chain over the same cropped frames
         m = min(n, 600)
@@ -402,6 +428,7 @@ def bench_sequence(args, aof, device, rank, world, dist):
             line["cpu_baseline"] = {"value": round(done / spent, 1), "unit": "frames/s", "cores": 1, "kind": "port",
                                     "sample": f"{done} calcFlow calls of the oracle on the cropped frames (crop, limiter and angle "
                                               f"included; SAD via {'SSE2 psadbw' if simd else 'the byte loop'}), {spent:.1f} s"}
+    if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()
@@ -438,7 +465,7 @@ def live_traffic(args, n, search_flag):
     env = dict(os.environ, TMPDIR="/tmp")
     child = [sys.executable, os.path.abspath(__file__), "--workload", args.workload, "--pairs", str(args.pairs), "--steps", "4",
              "--warmup", "1", "--settle-steps", "0", "--cpu-seconds", "0", "--traffic", "file", "--streams", "1", "--graph", "off",
-             "--legs", "none", "--input", args.input, "--noise", str(args.noise)] + search_flag
+             "--legs", "none", "--full", "--input", args.input, "--noise", str(args.noise)] + search_flag
     if args.brightness is not None:
         child += ["--brightness", str(args.brightness)]
     if args.max_shift is not None:
@@ -473,6 +500,36 @@ def pmc_traffic(key, field="hbm_bytes_per_launch"):
     return None, f"none: profiles/pmc_traffic.json has no entry {key}"
 
 
+DUMP_BUDGET = 60_000_000   # bytes of array data in all: --dump-outputs promises at most 64 MB, .npy headers included
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: write host arrays as DIR/<name>.npy, one file per field of a structured array (<name>_<field>.npy),
+    in float32 where it holds every value exactly (8- and 16-bit integers, float32) and float64 otherwise.  When the whole
+    would exceed DUMP_BUDGET, every array keeps the same fraction of its rows (first axis), drawn by a fixed seed so that
+    two runs write the same sample, and the indices of the rows kept go to <name>_index.npy."""
+    def f_type(dt):
+        return np.float32 if (dt.kind == "f" and dt.itemsize <= 4) or (dt.kind in "iub" and dt.itemsize <= 2) else np.float64
+
+    def row_bytes(a):
+        per = [np.dtype(f_type(a.dtype[f])).itemsize for f in a.dtype.names] if a.dtype.names else [np.dtype(f_type(a.dtype)).itemsize]
+        return sum(per) * (int(np.prod(a.shape[1:])) if a.ndim else 1)
+
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    fixed = sum(row_bytes(a) for a in arrays.values() if not a.ndim)
+    rows = sum(row_bytes(a) * len(a) for a in arrays.values() if a.ndim)
+    scale = 1.0 if fixed + rows <= DUMP_BUDGET else (DUMP_BUDGET - fixed) / (rows + 8 * sum(len(a) for a in arrays.values() if a.ndim))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        if scale < 1.0 and a.ndim and len(a):
+            idx = np.sort(np.random.default_rng(0).choice(len(a), max(1, int(len(a) * scale)), replace=False))
+            a = a[idx]
+            np.save(os.path.join(dirname, f"{name}_index.npy"), idx.astype(np.float64))
+        for f in a.dtype.names or (None,):
+            v = a if f is None else a[f]
+            np.save(os.path.join(dirname, name + ("" if f is None else "_" + f) + ".npy"), v.astype(f_type(v.dtype)))
+
+
 def bench_derotate(args, aof, device, rank, world, dist):
     """Output-side row of the scope table: gyro de-rotation of a batch of flow
     records on the device.  Step = one launch over --pairs * 1024 records (default 1 Mi)."""
@@ -493,6 +550,8 @@ def bench_derotate(args, aof, device, rank, world, dist):
         b.record()
     torch.cuda.synchronize(device)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"derotated": out.cpu().numpy()})
     k_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     alg = 16 + 16 + 8   # flow record + gyro sample in, two floats out
     achieved = alg * n / (k_ms * 1e-3) / 1e9
@@ -506,15 +565,16 @@ def bench_derotate(args, aof, device, rank, world, dist):
                          "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": src,
                          "kernel": "k_derotate", "kernel_ms": round(k_ms, 5), "algorithmic_bytes_per_record": alg,
                          "records_per_launch": n}}
-    from oracle import pyoracle as orc
-    m = min(n, 2048)
-    hf = flows[:m].cpu().numpy().view(np.float32).reshape(m, 4)
-    hg = gyro[:m].cpu().numpy()
-    ref = np.array([orc.derotate(float(hf[i, 0]), float(hf[i, 1]), float(hg[i, 0]), float(hg[i, 1]), float(hg[i, 3]),
-                                 216.6677, 216.2457, 4.5, 0.01) for i in range(m)], dtype=np.float32)
-    line["parity"] = {"oracle_records_bit_exact": bool(np.array_equal(out[:m].cpu().numpy().view(np.uint32),
-                                                                      ref.view(np.uint32))),
-                      "records_checked": m}
+    if args.full:
+        from oracle import pyoracle as orc
+        m = min(n, 2048)
+        hf = flows[:m].cpu().numpy().view(np.float32).reshape(m, 4)
+        hg = gyro[:m].cpu().numpy()
+        ref = np.array([orc.derotate(float(hf[i, 0]), float(hf[i, 1]), float(hg[i, 0]), float(hg[i, 1]), float(hg[i, 3]),
+                                     216.6677, 216.2457, 4.5, 0.01) for i in range(m)], dtype=np.float32)
+        line["parity"] = {"oracle_records_bit_exact": bool(np.array_equal(out[:m].cpu().numpy().view(np.uint32),
+                                                                          ref.view(np.uint32))),
+                          "records_checked": m}
     print(json.dumps(line), flush=True)
 
 
@@ -531,7 +591,17 @@ def main():
                          "the number actually run is in the line (settle_steps)")
     ap.add_argument("--pairs", type=int, default=1024, help="frame pairs per GPU per step")
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS) + ["ingest", "c1", "derotate", "seq"])
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline budget; 0 = skip")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline budget (with --full); 0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline, behind the timed region: the per-step median and per-kernel passes, "
+                         "K2 in a second pass, live PMC traffic, the other search modes, the realistic input, the other "
+                         "workloads in child runs, configs[3]'s strong shape, parity against the CPU oracle and the CPU baseline.  "
+                         "Without it (default) a run sets up, settles, warms up, times --steps steps, writes --dump-outputs and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step as DIR/<name>.npy (float32 / float64, at "
+                         "most 64 MB in all: a fixed seeded sample of the rows of larger outputs, their indices in "
+                         "<name>_index.npy); rank 0's outputs")
     ap.add_argument("--search", default="auto", choices=["auto", "exhaustive", "pruned", "adaptive"],
                     help="auto (default): what a fresh context runs = exact-adaptive for every tile size (exact pruning where "
                          "it pays: 16x16 tiles by a probe of the pair, 8x8 tiles by what the context's previous launches "
@@ -546,7 +616,7 @@ def main():
                          "shift, and the newer frame at half the contrast (exposure drift) -- the default line times this "
                          "input too (realistic_input)")
     ap.add_argument("--legs", default="all", choices=["all", "none"],
-                    help="all (default): behind the timed region the line also times the other search modes on the same batch, "
+                    help="with --full, all (default): behind the timed region the line also times the other search modes on the same batch, "
                          "the realistic input and (workload c2, one GPU) the other BASELINE configurations in child runs; "
                          "none: the headline only")
     ap.add_argument("--max-shift", type=int, default=None,
@@ -584,11 +654,12 @@ def main():
                     help="initialise the process group and run the per-step gather even with ONE rank: rehearses the "
                          "N > 1 code path (RCCL, graph capture beside its watchdog thread) on a one-GPU box")
     ap.add_argument("--traffic", default="auto", choices=["auto", "live", "file"],
-                    help="roofline.traffic (HBM bytes per launch from the PMC counters): auto / live = measured in this run by two short "
+                    help="roofline.traffic (HBM bytes per launch from the PMC counters): with --full, auto / live = measured in this run by two short "
                          "child runs under rocprofv3 --pmc (one GPU only; falls back to the committed summary when the profiler is not "
-                         "usable or a profiler is already around this process), file = the committed summary of the same command")
+                         "usable or a profiler is already around this process), file (and any run without --full) = the committed "
+                         "summary of the same command")
     ap.add_argument("--configs3-pairs", type=int, default=1024,
-                    help="N > 1: pairs of the strong-scaling shape every multi-GPU line also times (BASELINE configs[3]: "
+                    help="N > 1 with --full: pairs of the strong-scaling shape the multi-GPU line also times (BASELINE configs[3]: "
                          "1024 pairs sharded over the GPUs, against the same pairs on one GPU); 0 = skip")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="rehearse the N>1 control flow without a GPU: rendezvous, shard, gather a batch of "
@@ -865,10 +936,16 @@ def main():
     for _ in range(args.warmup):
         step()
     elapsed = run.timed(args.steps)
+    if args.dump_outputs and rank == 0:   # the last timed step's records, before any further pass writes them again
+        ln, k = state["last"]
+        outs = {"blocks": aof.blocks_view(ln.blocks), "flows": aof.flows_view(ln.flows[k])}
+        if ln.sub is not None:
+            outs["subdirs"] = ln.sub.cpu().numpy()
+        dump_outputs(args.dump_outputs, outs)
     # Per-step times for the median: a further pass of the same K steps with one event behind every step
     # (outside the timed region, so that `value` is not taxed with the event records).
     marks = []
-    for _ in range(args.steps):
+    for _ in range(args.steps if args.full else 0):
         step()
         ln, _k = state["last"]
         ev = torch.cuda.Event(enable_timing=True)
@@ -881,7 +958,7 @@ def main():
         per_step_ms.append(marks[j - stride][1].elapsed_time(marks[j][1]) / stride)
     if multi:
         torch.cuda.set_stream(torch.cuda.default_stream(device))
-    if not events_in_timed_region:
+    if args.full and not events_in_timed_region:
         eng_set_profiling(True, kernels=[aof.K_SEARCH])
         for _ in range(args.steps):
             lanes[0].enqueue[0]()
@@ -889,35 +966,38 @@ def main():
     eng_set_profiling(False)
 
     # ---- dominant kernel against its roofline (rank 0's launches) ----
-    # (the event ring keeps the last 256 launches: whole steps only)
-    k2 = eng.profile_ms(aof.K_SEARCH)
+    # (the event ring keeps the last 256 launches: whole steps only.  Without --full K2 is known only where the timed
+    # region carried the events)
+    k2 = eng.profile_ms(aof.K_SEARCH) if args.full or events_in_timed_region else []
     k2 = k2[len(k2) - min(args.steps, len(k2) // lps) * lps:]
-    k2_ms = float(np.sum(k2)) / (len(k2) // lps) if k2 else float("nan")
+    k2_ms = float(np.sum(k2)) / (len(k2) // lps) if k2 else None
     # Every kernel of the step bracketed by events, in ONE further pass of its own (outside the timed region: an event
     # pair costs the stream a few microseconds), with that pass's own step time beside the parts -- so that the parts are
     # held against the whole they were measured in.  `ms_per_step` (wall clock over the K timed steps) stays the
     # authoritative figure `value` is computed from; roofline.kernel_ms is K2 from the timed region where it carries events.
-    kpass = max(1, min(args.steps, 64, 256 // lps))   # (the event ring keeps 256 launches per kernel)
-    eng_set_profiling(True)
-    fence()
-    t1 = time.perf_counter()
-    for _ in range(kpass):
-        lanes[0].enqueue[0]()
-    fence()
-    kpass_ms = (time.perf_counter() - t1) / kpass * 1e3
-    eng_set_profiling(False)
-    per_kernel = {}
-    for name, kid in (("pyramid", aof.K_PYRAMID), ("search_l1", aof.K_SEARCH_L1),
-                      ("reduce_l1", aof.K_REDUCE_L1), ("search", aof.K_SEARCH), ("reduce", aof.K_REDUCE)):
-        v = eng.profile_ms(kid)
-        if v:   # per step: the sum over the step's sub-batch launches
-            per_kernel[name] = round(float(np.sum(v)) / kpass, 5)
-    if "pyramid" in per_kernel and "search_l1" not in per_kernel and p.pyramid_levels == 2:
-        # the AOF_K_PYRAMID bracket timed k_coarse: sums + pyramid + level-1 search + level-1 reduction
-        per_kernel["coarse_fused"] = per_kernel.pop("pyramid")
-    per_kernel["step_in_this_pass"] = round(kpass_ms, 5)
-    per_kernel["note"] = (f"one separate pass of {kpass} steps on lane 0 with HIP events around every kernel; step_in_this_pass is "
-                          "that pass's own wall time per step: the parts add up to less than it; ms_per_step is authoritative")
+    per_kernel = None
+    if args.full:
+        kpass = max(1, min(args.steps, 64, 256 // lps))   # (the event ring keeps 256 launches per kernel)
+        eng_set_profiling(True)
+        fence()
+        t1 = time.perf_counter()
+        for _ in range(kpass):
+            lanes[0].enqueue[0]()
+        fence()
+        kpass_ms = (time.perf_counter() - t1) / kpass * 1e3
+        eng_set_profiling(False)
+        per_kernel = {}
+        for name, kid in (("pyramid", aof.K_PYRAMID), ("search_l1", aof.K_SEARCH_L1),
+                          ("reduce_l1", aof.K_REDUCE_L1), ("search", aof.K_SEARCH), ("reduce", aof.K_REDUCE)):
+            v = eng.profile_ms(kid)
+            if v:   # per step: the sum over the step's sub-batch launches
+                per_kernel[name] = round(float(np.sum(v)) / kpass, 5)
+        if "pyramid" in per_kernel and "search_l1" not in per_kernel and p.pyramid_levels == 2:
+            # the AOF_K_PYRAMID bracket timed k_coarse: sums + pyramid + level-1 search + level-1 reduction
+            per_kernel["coarse_fused"] = per_kernel.pop("pyramid")
+        per_kernel["step_in_this_pass"] = round(kpass_ms, 5)
+        per_kernel["note"] = (f"one separate pass of {kpass} steps on lane 0 with HIP events around every kernel; step_in_this_pass is "
+                              "that pass's own wall time per step: the parts add up to less than it; ms_per_step is authoritative")
     # ---- BASELINE configs[3] on every N > 1 line, whatever --scaling says: the STRONG shape ----
     # (--configs3-pairs, default 1 024, sharded over the ranks: 128 per GPU at N = 8, run as the automatic
     # choice runs it -- two lanes, graph replay, reduction in the search launch -- with the gather inside the
@@ -931,7 +1011,7 @@ def main():
         mine = f"rank {rank}: cuda:{dev_index} {props.name} ({getattr(props, 'gcnArchName', '?')}, {props.total_memory >> 30} GiB)"
         devices_seen = [None] * ranks_seen
         dist.all_gather_object(devices_seen, mine)
-    if dist is not None and args.configs3_pairs > 0:
+    if args.full and dist is not None and args.configs3_pairs > 0:
         total3 = args.configs3_pairs
         if total3 % world:
             configs3 = {"skipped": f"{total3} pairs do not divide over {world} ranks"}
@@ -993,13 +1073,13 @@ def main():
                         "note": f"{total3} pairs sharded over {world} ranks with the flow records gathered on every rank, "
                                 f"against the same {total3} pairs on rank 0's GPU alone (same job, same clock)"}
     alg_bytes = aof.algorithmic_bytes(p)
-    achieved = alg_bytes * n / (k2_ms * 1e-3) / 1e9
+    achieved = alg_bytes * n / (k2_ms * 1e-3) / 1e9 if k2_ms else None
     # `traffic` is NOT measured in this run: PMC counters need rocprofv3 around the process.  It is
     # read from the committed summary of the same command under profiles/ (tools/collect_evidence.sh);
     # `traffic_source` names the file, or says that no summary exists for this workload and size.
     traffic, traffic_source = pmc_traffic(f"{args.workload}:{n}")
     traffic_step = pmc_traffic(f"{args.workload}:{n}", "step_bytes")[0]
-    if args.traffic != "file" and rank == 0 and world == 1 and dist is None:
+    if args.full and args.traffic != "file" and rank == 0 and world == 1 and dist is None:
         # (behind the timed region) measure it here and now; the committed summary stays the fallback
         flag = ["--search", args.search]
         if args.search == "auto":
@@ -1024,8 +1104,8 @@ def main():
         "ms_per_step": round(step_ms, 4),
         "timed_region_ms": round(elapsed * 1e3, 3),
         "timing_note": "ms_per_step = wall clock of the K timed steps between barrier + synchronize, / K: AUTHORITATIVE, value = pairs / it.  "
-                       "ms_per_step_median / p10_p90 = per-step HIP-event intervals of a FURTHER pass of K steps (each event costs the stream "
-                       "a few microseconds: a little slower by construction); kernels_ms = a third pass with events around every kernel",
+                       "with --full, ms_per_step_median / p10_p90 = per-step HIP-event intervals of a FURTHER pass of K steps (each event costs the "
+                       "stream a few microseconds: a little slower by construction); kernels_ms = a third pass with events around every kernel",
         # median over per-step HIP-event intervals of a further pass of the same K steps
         "ms_per_step_median": round(float(np.median(per_step_ms)), 5) if per_step_ms else None,
         "value_median": round(world * n / (float(np.median(per_step_ms)) * 1e-3), 1) if per_step_ms else None,
@@ -1037,8 +1117,8 @@ def main():
                    "search_kernel": eng.variant, "search": args.search, "coarse": args.coarse, "reduce": reduce_mode,
                    "streams": len(lanes), "graph_replay": bool(use_graph), "k2_launches_per_step": lps, "input": args.input, "noise_lsb": args.noise, "exposure_step": brightness, "parallelism": f"pairs sharded x{world}, flows all_gather ({args.backend}) every {G} steps per lane"
                    if dist is not None else "single GPU"},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+        "roofline": {"bound": "hbm", "achieved": round(achieved, 1) if k2_ms else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": round(achieved / HBM_PEAK_GBS, 4) if k2_ms else None, "traffic": traffic,
                      "traffic_source": traffic_source,
                      # beyond-L2 bytes of ALL kernels of one step (same source): what to hold against the
                      # algorithmic bytes of a multi-kernel workload
@@ -1046,14 +1126,15 @@ def main():
                      # the same algorithmic bytes over the WHOLE step (all kernels of the workload and
                      # the gaps between them): the figure to quote for multi-kernel workloads (c3, c5p)
                      "achieved_step": round(achieved_step, 1), "frac_step": round(achieved_step / HBM_PEAK_GBS, 4),
-                     "kernel": "k_search (K2)", "kernel_ms": round(k2_ms, 5),
+                     "kernel": "k_search (K2)", "kernel_ms": round(k2_ms, 5) if k2_ms else None,
                      "kernel_ms_from": "HIP events on the launch stream inside the timed region" if events_in_timed_region
+                     else "not measured: --full times K2 in a second pass" if not args.full
                      else f"HIP events in a second pass of the same {args.steps} steps (sum of the {lps} "
                           "launches of a step, which other kernels overlap): quote frac_step for this workload",
                      "algorithmic_bytes_per_pair": alg_bytes, "pairs_per_launch": n,
                      # nominal abs-diffs of the exhaustive scan; meaningless when candidates are pruned
                      "abs_diff_per_s": round(aof.abs_diffs(p) * n / (k2_ms * 1e-3), 1)
-                     if eng.search_mode == aof.SEARCH_EXHAUSTIVE else None},
+                     if eng.search_mode == aof.SEARCH_EXHAUSTIVE and k2_ms else None},
         "kernels_ms": per_kernel,
     }
     if dist is not None:
@@ -1089,7 +1170,7 @@ def main():
         except Exception as e:
             out["config"]["adaptive_search"] = {"error": f"{type(e).__name__}: {e}"[:200]}
     pruned_available = (eng.variant == "lane8" and eng.nblocks(0) > 256) or eng.variant == "tile16_lds"
-    if args.search == "auto" and pruned_available and not args.force_generic and args.legs == "all":
+    if args.full and args.search == "auto" and pruned_available and not args.force_generic and args.legs == "all":
         others = [m for m in (aof.SEARCH_EXHAUSTIVE, aof.SEARCH_PRUNED, aof.SEARCH_ADAPTIVE) if m != head_mode]
         ref_blocks = blocks.clone()
         for mode in others:
@@ -1131,7 +1212,7 @@ def main():
     # (+-4 LSB noise, a half-pixel displacement on top of the integer shift, the newer frame at half the contrast:
     #  mainloop.cpp:197-275,295-322 feeds OV7251 frames under an auto-exposure loop.  Timed like the headline: same
     #  configuration, fresh contexts, settling steps, warm-up, K steps between synchronisations.)
-    if args.legs == "all" and args.input == "baseline" and not args.noise and world == 1 and dist is None and rank == 0:
+    if args.full and args.legs == "all" and args.input == "baseline" and not args.noise and world == 1 and dist is None and rank == 0:
         prev_r, cur_r, _ = make_batch_gpu(W, H, n, reach, 0xA0F + 7919 * rank, device, brightness=brightness, **REALISTIC)
         leg = {"input": "+-4 LSB noise + a half-pixel displacement per pair + the newer frame at contrast 0.5 (bench.py --input realistic)"}
         for key, mode in (("default_search", None), ("exhaustive_search", "exhaustive")):
@@ -1180,7 +1261,7 @@ def main():
                                 "+-4 LSB noise + half-pixel motion + half contrast.  Records are identical in every mode.")
 
     # ---- the other BASELINE configurations, driver-visible: child runs of this script (workload c2, one GPU) ----
-    if (args.legs == "all" and args.workload == "c2" and args.input == "baseline" and not args.noise and world == 1 and dist is None
+    if (args.full and args.legs == "all" and args.workload == "c2" and args.input == "baseline" and not args.noise and world == 1 and dist is None
             and rank == 0 and n == 1024 and not being_profiled()):
         import subprocess
         legs = {}
@@ -1192,7 +1273,7 @@ def main():
                            ("c5_realistic", ["--workload", "c5", "--pairs", "256", "--input", "realistic"])):
             cmd = [sys.executable, os.path.abspath(__file__)] + extra + [
                 "--steps", str(args.steps), "--warmup", str(args.warmup), "--settle-steps", str(args.settle_steps if args.settle_steps >= 0 else 300),
-                "--cpu-seconds", "0", "--traffic", "file", "--legs", "none"]
+                "--cpu-seconds", "0", "--traffic", "file", "--legs", "none", "--full"]
             try:
                 r = subprocess.run(cmd, capture_output=True, text=True, timeout=150)
                 d = json.loads(r.stdout.strip().splitlines()[-1])
@@ -1208,7 +1289,7 @@ def main():
         out["workloads"] = legs
 
     # ---- parity on a sample + CPU baseline (rank 0, N=1 only) ----
-    if rank == 0:
+    if rank == 0 and args.full:
         from oracle import pyoracle as orc
         po = orc.params_from(p)
         ln, k = state["last"]
@@ -1261,6 +1342,7 @@ def main():
                                    "sample": f"{done} pairs ({m} distinct) of the same workload, this repo's "
                                              f"C oracle (-O2, SAD via {'SSE2 psadbw' if simd else 'the byte loop'}), "
                                              f"OpenMP over pairs, {spent:.1f} s"}
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

@@ -59,7 +59,7 @@ def test_single_rank_needs_no_launcher():
 def test_plain_two_rank_bench_line_on_one_gpu():
     """The real N = 2 bench path from a plain command line: two ranks share the one GPU of the
     box (gloo for the gather of the flow records), max-over-ranks timing, one JSON line."""
-    j = run_bench("--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--settle-steps", "3",
+    j = run_bench("--full", "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--settle-steps", "3",
                   "--pairs", "8", "--cpu-seconds", "0", "--configs3-pairs", "64")
     assert j["n_gpus"] == 2 and j["config"]["global_pairs"] == 16 and j["steps"] == 2 and j["settle_steps"] == 3
     assert j["value"] > 0 and j["parity"]["oracle_pairs_bit_exact"] and j["parity"]["all_pairs_return_known_shift"]
@@ -68,7 +68,7 @@ def test_plain_two_rank_bench_line_on_one_gpu():
     c3 = j["configs3"]
     assert c3["global_pairs"] == 64 and c3["pairs_per_gpu"] == 32 and c3["scaling"] == "strong"
     assert c3["ms_per_step"] > 0 and c3["one_gpu_ms_per_step"] > 0 and c3["vs_one_gpu_1024"] > 0
-    k = run_bench("--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--settle-steps", "3",
+    k = run_bench("--full", "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--settle-steps", "3",
                   "--pairs", "16", "--scaling", "strong", "--cpu-seconds", "0", "--configs3-pairs", "16")
     assert k["scaling"] == "strong" and k["config"]["global_pairs"] == 16 and k["config"]["pairs_per_gpu"] == 8
     assert k["configs3"]["pairs_per_gpu"] == 8 and k["configs3"]["ms_per_step"] == pytest.approx(k["ms_per_step"], rel=1e-3)
@@ -79,7 +79,7 @@ def test_four_ranks_with_two_batches_in_flight_on_one_gpu():
     """configs[3]'s per-GPU share as the strong-scaling line runs it: 128 VGA pairs per rank, two batches
     in flight per rank (bench lanes on two HIP streams), the reduction inside the search launch, the
     step replayed as a hipGraph -- four ranks sharing the one GPU of the box, gloo for the gather."""
-    j = run_bench("--gpus", "4", "--backend", "gloo", "--steps", "4", "--warmup", "1", "--settle-steps", "4",
+    j = run_bench("--full", "--gpus", "4", "--backend", "gloo", "--steps", "4", "--warmup", "1", "--settle-steps", "4",
                   "--pairs", "512", "--scaling", "strong", "--cpu-seconds", "0", "--configs3-pairs", "512")
     c = j["config"]
     c3 = j["configs3"]
@@ -96,7 +96,7 @@ def test_one_rank_rccl_rehearsal_of_the_gather_path():
     the step captured into a hipGraph beside its watchdog thread, the flow records of G steps shipped by
     one all_gather_into_tensor, completion checked from the host -- for the headline step and for
     configs[3]'s per-GPU share (two lanes, reduction in the launch)."""
-    j = run_bench("--force-dist", "--steps", "40", "--warmup", "2", "--settle-steps", "20", "--cpu-seconds", "0")
+    j = run_bench("--full", "--force-dist", "--steps", "40", "--warmup", "2", "--settle-steps", "20", "--cpu-seconds", "0")
     assert j["config"]["streams"] == 1 and "every 4 steps" in j["config"]["parallelism"]
     assert j["parity"]["oracle_pairs_bit_exact"] and j["parity"]["all_pairs_return_known_shift"]
     # the keys the first real 8-GPU line will be read by: ranks and devices as the process group saw them,
@@ -105,6 +105,6 @@ def test_one_rank_rccl_rehearsal_of_the_gather_path():
     c3 = j["configs3"]
     assert c3["global_pairs"] == 1024 and c3["pairs_per_gpu"] == 1024 and c3["scaling"] == "strong"
     assert 0.8 < c3["vs_one_gpu_1024"] < 1.25, c3   # one rank: the sharded batch IS the one-GPU batch (+ the gather)
-    k = run_bench("--force-dist", "--pairs", "128", "--steps", "64", "--warmup", "2", "--settle-steps", "20", "--cpu-seconds", "0")
+    k = run_bench("--full", "--force-dist", "--pairs", "128", "--steps", "64", "--warmup", "2", "--settle-steps", "20", "--cpu-seconds", "0")
     assert k["config"]["streams"] == 2 and k["config"]["graph_replay"] and "every 16 steps" in k["config"]["parallelism"]
     assert k["parity"]["oracle_pairs_bit_exact"] and k["parity"]["all_pairs_return_known_shift"]

@@ -7,7 +7,7 @@ for round in 1 2; do
   for nz in $nzs; do
     for lib in "$@"; do
       tag=$(basename $lib .so)
-      AOF_LIB=$PWD/$lib timeout -k 10 200 python bench.py --workload $wl --noise $nz --traffic file --cpu-seconds 0 --steps 100 --warmup 20 > $out/${wl}_${tag}_${round}_n$nz.json 2> $out/err.txt || { echo "$lib failed"; tail -3 $out/err.txt; exit 1; }
+      AOF_LIB=$PWD/$lib timeout -k 10 200 python bench.py --full --workload $wl --noise $nz --traffic file --cpu-seconds 0 --steps 100 --warmup 20 > $out/${wl}_${tag}_${round}_n$nz.json 2> $out/err.txt || { echo "$lib failed"; tail -3 $out/err.txt; exit 1; }
     done
   done
 done

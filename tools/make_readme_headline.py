@@ -35,7 +35,7 @@ sx = load("share_p1024_exhaustive_two_batches")
 one = load("share_p1024")
 c3n, c3r = load("c3_noise16"), load("c3_realistic")
 c5r, c5h = load("c5_realistic"), load("c5h")
-txt = (f"Headline (`bench.py`, C2: 1 024 VGA pairs per launch, 8×8 SAD, ±4, the exact-adaptive search every context runs by default, on BASELINE's "
+txt = (f"Headline (`bench.py --full`, C2: 1 024 VGA pairs per launch, 8×8 SAD, ±4, the exact-adaptive search every context runs by default, on BASELINE's "
        f"synthetic translations): **{c2['value']/1e6:.2f} M frame-pairs/s**, "
        f"K2 {rf['kernel_ms']*1e3:.1f} µs per launch = **{rf['frac']*100:.1f} % of the 8 TB/s HBM roofline** (whole step {rf['frac_step']*100:.1f} %), "
        f"{two['value']/1e6:.2f} M with two batches in flight.  That rate depends on the input; the line carries the other two beside it: the exhaustive scan of "

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/pmc_fused; mkdir -p $O; cd /tm
 for mode in separate fused; do
   for set in "SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU" "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_SALU" "GRBM_GUI_ACTIVE SQ_WAVES SQ_INSTS_VMEM_RD SQ_INSTS_SMEM"; do
     tag=$(echo $set | cut -d" " -f1)
-    timeout -k 10 200 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $O/${mode}_$tag -- python3 $R/bench.py --reduce $mode --steps 30 --settle-steps 100 --cpu-seconds 0 > $O/${mode}_$tag.log 2>&1 || { echo "$mode $tag failed"; tail -3 $O/${mode}_$tag.log; }
+    timeout -k 10 200 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $O/${mode}_$tag -- python3 $R/bench.py --full --reduce $mode --steps 30 --settle-steps 100 --cpu-seconds 0 > $O/${mode}_$tag.log 2>&1 || { echo "$mode $tag failed"; tail -3 $O/${mode}_$tag.log; }
   done
 done
 python3 - <<'PY'

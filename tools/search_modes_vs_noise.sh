@@ -5,7 +5,7 @@ out=$1; shift
 mkdir -p $out
 for wl in "$@"; do
   for nz in ${NZS:-0 2 4 8 16 40}; do
-    timeout -k 10 300 python3 ${GRAFT_REPO_ROOT:-.}/bench.py --workload $wl --noise $nz --traffic file --cpu-seconds 0 > $out/${wl}_n$nz.json 2> $out/${wl}_n$nz.err || { tail -3 $out/${wl}_n$nz.err; exit 1; }
+    timeout -k 10 300 python3 "$(dirname "$0")"/../bench.py --full --workload $wl --noise $nz --traffic file --cpu-seconds 0 > $out/${wl}_n$nz.json 2> $out/${wl}_n$nz.err || { tail -3 $out/${wl}_n$nz.err; exit 1; }
   done
 done
 python - $out "$@" <<'PY'
