@@ -64,7 +64,7 @@ struct VoteMem {
     uint32_t deadline_ticks;   // finaliser waves give up after this many ticks of the 100 MHz counter
 };
 
-// What the pruned lane8 search tells the host about itself (the ADAPTIVE mode of 8x8 contexts, aof_capi.hip):
+// What the pruned lane8 search tells the host about itself (the ADAPTIVE mode of 8x8 contexts, aof_batch.cpp):
 // one workgroup in `stride` stores how many of its first wave's chunks left with "pruning pays" into a word of
 // pinned host memory: tag (low 16 bits of launch_no) << 16 | paying << 8 | chunks.  Plain stores, nobody waits
 // for them: the host reads whatever has arrived when it enqueues the next launch.  Speed only, never results.
@@ -261,7 +261,7 @@ int launch_sequence_output(const SequenceArgs &a, void *stream);
 // aof_last_error's text for the callers outside aof_capi.hip
 int precheck(aof_ctx *ctx);
 int ctx_fail(aof_ctx *ctx, int code, const char *what);
-// (aof_capi.hip) the flow of a frame sequence for the pipeline: does the call run K1 as a pass of its own, and the
+// (aof_batch.cpp) the flow of a frame sequence for the pipeline: does the call run K1 as a pass of its own, and the
 // call itself with K1's outputs already in the workspace
 bool sequence_runs_k1(aof_ctx *ctx, const uint8_t *d_frames, int64_t n_pairs, void *d_workspace);
 int flow_sequence(aof_ctx *ctx, const uint8_t *d_frames, int64_t n_pairs, aof_flow *d_flows, void *d_workspace,
