@@ -156,6 +156,7 @@ def _load():
         "aof_debug_resident_fault": (C.c_int, [VP, C.c_int, C.c_uint32]),
         "aof_set_vote_deadline_us": (C.c_int, [VP, C.c_uint32]),
         "aof_debug_vote_deadline_ticks": (C.c_int, [VP, C.c_uint32]),
+        "aof_debug_tile16_verdicts": (C.c_int, [VP, VP, C.c_int]),
         "aof_ingest_batch_device": (C.c_int, [P(IngestParams), VP, I64, I64, VP, I64, VP, VP]),
         "aof_sequence_layout": (C.c_int, [P(Params), P(SequenceParams), I64, P(SeqLayout)]),
         "aof_sequence_device": (C.c_int, [VP, P(SequenceParams), VP, I64, I64, VP, VP, VP, C.c_size_t, VP]),
@@ -552,6 +553,12 @@ class FlowEngine:
     def debug_vote_deadline_ticks(self, ticks):
         """Fault injection: that deadline in 10 ns ticks, unchecked (0: every finaliser gives up at once)."""
         self._check(lib.aof_debug_vote_deadline_ticks(self._ctx, int(ticks)))
+
+    def debug_tile16_verdicts(self, verdicts=()):
+        """Test hook of the 16x16 adaptive search: pair i gets verdicts[i % len(verdicts)] (0..4, as in the workspace's
+        hints) instead of the probe's; an empty sequence gives the decision back to the probe."""
+        v = [int(x) for x in verdicts]
+        self._check(lib.aof_debug_tile16_verdicts(self._ctx, (C.c_uint8 * max(len(v), 1))(*v), len(v)))
 
     def stream_graph_active(self) -> bool:
         return lib.aof_set_stream_graph(self._ctx, -1) == 1

@@ -319,7 +319,7 @@ int enqueue_level(aof_ctx *ctx, const LevelPlan &l, uint8_t *hist, int kid_searc
         int rc;
         switch (l.kind) {
         case SK_TILE16:   // (refines out of its LDS tile when directions are wanted)
-            rc = launch_search_tile16(l.a, s);
+            rc = launch_search_tile16(l.a, s, ctx->tile16_verdicts);
             if (!rc && l.refine) rc = launch_refine(l.a, s);
             break;
         case SK_LANE8_GROUP:

@@ -264,6 +264,25 @@ int aof_debug_vote_deadline_ticks(aof_ctx *ctx, uint32_t ticks)
     return 0;
 }
 
+int aof_debug_tile16_verdicts(aof_ctx *ctx, const uint8_t *verdicts, int count)
+{
+    if (!ctx) return -EINVAL;
+    if (ctx->params.tile != 16) return fail(ctx, -EINVAL, "verdicts of the 16x16 search on a %dx%d context", ctx->params.tile, ctx->params.tile);
+    if (count < 0 || count > kMaxForcedVerdicts) return fail(ctx, -EINVAL, "%d verdicts: 0 .. %d", count, kMaxForcedVerdicts);
+    if (count > 0 && !verdicts) return fail(ctx, -EINVAL, "null verdicts");
+    Tile16Verdicts f = {};
+    for (int i = 0; i < count; i++) {
+        if (verdicts[i] > 4) return fail(ctx, -EINVAL, "verdict %d of %u: 0 .. 4", i, verdicts[i]);
+        f.v[i] = verdicts[i];
+    }
+    f.count = count;
+    const bool changes = f.count != ctx->tile16_verdicts.count ||
+                         std::memcmp(f.v, ctx->tile16_verdicts.v, sizeof f.v) != 0;
+    kernel_choice_changes(ctx, changes);   // (captured per-call graphs hold the probe or the verdicts of their time)
+    ctx->tile16_verdicts = f;
+    return 0;
+}
+
 int aof_set_profiling(aof_ctx *ctx, int on)
 {
     if (!ctx) return -EINVAL;

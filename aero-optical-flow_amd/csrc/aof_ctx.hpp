@@ -136,6 +136,7 @@ struct aof_ctx {
     aof::Resident res;
     aof::InLaunchReduce votes;
     aof::AdaptiveSearch adapt;
+    aof::Tile16Verdicts tile16_verdicts;   // test hook (aof_debug_tile16_verdicts): count 0 = the probe decides
     aof::Profiling prof;
     aof_stream_stats stats;     // aof_stream_get_stats
 };

@@ -195,7 +195,14 @@ int launch_flow_lane8(const SearchArgs &a, const FlowTail &tail, void *stream);
 // LDS-tiled (block, dy)-per-lane kernel for B=16, S=8 on a dense grid (any predictor).
 bool tile16_supported(const SearchArgs &a);
 bool tile16_refines(const SearchArgs &a);   // the launch also writes the half-pixel directions (no K2b behind it)
-int launch_search_tile16(const SearchArgs &a, void *stream);
+// Test hook of the adaptive 16x16 search (aof_debug_tile16_verdicts): pair i gets v[i % count] instead of the probe's
+// verdict; count 0 = the probe decides.  Only launches with prune == 2 read it.
+constexpr int kMaxForcedVerdicts = 8;
+struct Tile16Verdicts {
+    uint8_t v[kMaxForcedVerdicts];
+    int32_t count;
+};
+int launch_search_tile16(const SearchArgs &a, void *stream, const Tile16Verdicts &forced);
 // Small pairs (frames fit LDS, grids <= 256 blocks), one or two levels, in one launch: one workgroup per pair.
 bool flow_small_supported(const SmallArgs &a);
 int launch_flow_small(const SmallArgs &a, void *stream);

@@ -613,6 +613,8 @@ __global__ __launch_bounds__(kProbeThreads) void k_tile16_probe(SearchArgs a, ui
             }
             if (blk < nsamp && part == 0) s_full[blk] = in ? (uint16_t)(row_key(acc, acc16, 0) >> 16) : (uint16_t)0xFFFFu;
         }
+        // (b) overwrites the two-row bounds that (a) picks its rows from, and the waves without work in (a) get here first
+        __syncthreads();
         // (b) the four-row bounds (tile rows 2, 6, 10, 14) and the eight-row bounds (+ rows 0, 4, 8, 12) of those blocks' items in
         //     one pass (24 loads per item)
         const int ndeep = (nsamp + 1) / 2;
@@ -663,6 +665,17 @@ __global__ __launch_bounds__(kProbeThreads) void k_tile16_probe(SearchArgs a, ui
     if (tid == 0) hints[pair] = hint | (separation << 8);   // (low byte: the verdict)
 }
 
+// The test hook aof_debug_tile16_verdicts in place of the probe: pair i gets f.v[i % f.count], under a fixed non-zero pattern
+// where the probe puts its separation figure (the search kernel reads the low byte alone).  The verdicts travel as a kernel
+// argument: no host copy, so the launch can be captured into a graph.
+constexpr uint32_t kForcedVerdictPattern = 0x5A5A00u;
+constexpr int kFillThreads = 256;
+__global__ __launch_bounds__(kFillThreads) void k_tile16_fill_verdicts(uint32_t *hints, int64_t n_pairs, Tile16Verdicts f)
+{
+    const int64_t i = (int64_t)blockIdx.x * kFillThreads + threadIdx.x;
+    if (i < n_pairs) hints[i] = (uint32_t)f.v[i % f.count] | kForcedVerdictPattern;
+}
+
 size_t tile16_lds(const SearchArgs &a)
 {
     size_t bytes = (size_t)48 * a.w + 4 * (size_t)a.grid.nx + 16;
@@ -687,12 +700,18 @@ bool tile16_supported(const SearchArgs &a)
     return tile16_lds(a) <= 156 * 1024;
 }
 
-int launch_search_tile16(const SearchArgs &a, void *stream)
+int launch_search_tile16(const SearchArgs &a, void *stream, const Tile16Verdicts &forced)
 {
     if (a.n_pairs == 0) return 0;
     const int64_t total = a.n_pairs * a.grid.ny;
     if (total > 0x7FFFFFFF) return (int)hipErrorInvalidValue;
-    if (a.prune == 2) {   // ADAPTIVE: judge every pair first (hints in the workspace), then the search decides per pair
+    if (a.prune == 2 && forced.count > 0) {   // (test hook: the verdicts are set, no probe runs)
+        if (!a.hints || forced.count > kMaxForcedVerdicts) return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_tile16_fill_verdicts, dim3((uint32_t)((a.n_pairs + kFillThreads - 1) / kFillThreads)), dim3(kFillThreads), 0,
+                           static_cast<hipStream_t>(stream), a.hints, a.n_pairs, forced);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+    } else if (a.prune == 2) {   // ADAPTIVE: judge every pair first (hints in the workspace), then the search decides per pair
         if (!a.hints) return (int)hipErrorInvalidValue;
         // every kProbeStride-th block per axis; an axis with fewer blocks than that is sampled more densely (at least one
         // block), and the strides grow -- the longer axis first -- until the sample fits the kernel's table

@@ -226,6 +226,11 @@ int aof_set_vote_deadline_us(aof_ctx *ctx, uint32_t microseconds);
 /* Fault injection for the tests of that path: the deadline in ticks of the 100 MHz counter, unchecked (0 = every
  * finaliser gives up at once -> zero records, sticky -EIO). */
 int aof_debug_vote_deadline_ticks(aof_ctx *ctx, uint32_t ticks);
+/* Test hook of the 16x16 adaptive search: no probe runs; pair i gets verdicts[i % count] (each 0..4, as in
+ * aof_ws_layout.hints), at both levels.  count = 0 gives the decision back to the probe.  Records do not depend on
+ * the verdict.  -EINVAL: NULL ctx, a context whose tile is not 16, count < 0 or > 8, NULL verdicts with count > 0,
+ * a verdict above 4. */
+int aof_debug_tile16_verdicts(aof_ctx *ctx, const uint8_t *verdicts, int count);
 
 /* ---- host-buffer conveniences (what the C++ facade calls) ----
  * Synchronous: copy in, run the kernels above, copy out.  blocks/subdirs may be NULL. */
