@@ -6,45 +6,11 @@
 #include "aof_device.hpp"
 #include "aof_internal.hpp"
 #include "aof_refine.hpp"
+#include "aof_sad.hpp"
 
 namespace aof {
 
 namespace {
-
-__device__ __forceinline__ u64 qsad(u64 window, uint32_t ref, u64 acc)
-{
-    return __builtin_amdgcn_qsad_pk_u16_u8(window, ref, acc);
-}
-__device__ __forceinline__ u64 pack64(uint32_t lo, uint32_t hi) { return ((u64)hi << 32) | lo; }
-// Dwords 1 and 2 of a window row whose dwords (0, 1) and (2, 3) sit in two aligned register pairs: ONE v_pk_mov_b32
-// (pack64(w.y, w.z) compiles to it in the exhaustive kernels, but to two v_mov_b32 in the pruned rows).
-__device__ __forceinline__ u64 middle64(u64 p01, u64 p23)
-{
-    u64 r;
-    asm("v_pk_mov_b32 %0, %1, %2 op_sel:[1,0]" : "=v"(r) : "v"(p01), "v"(p23));
-    return r;
-}
-
-typedef unsigned short ushort2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pk_min_u16(uint32_t x, uint32_t y)
-{
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(ushort2_t, x),
-                                                                  __builtin_bit_cast(ushort2_t, y)));
-}
-
-// 4x4 gradient gate on tile bytes [2..5] x rows [2..5]
-__device__ __forceinline__ uint32_t gradient_gate(const uint32_t (&ref)[8][2])
-{
-    uint32_t mid[4], diff = 0;
-#pragma unroll
-    for (int r = 0; r < 4; r++) mid[r] = __builtin_amdgcn_alignbyte(ref[r + 2][1], ref[r + 2][0], 2);
-#pragma unroll
-    for (int r = 0; r < 3; r++) diff = __builtin_amdgcn_sad_u8(mid[r], mid[r + 1], diff);
-#pragma unroll
-    for (int r = 0; r < 4; r++)  // bytes (3,4,5,5) against (2,3,4,5): the doubled byte adds 0
-        diff = __builtin_amdgcn_sad_u8(mid[r], __builtin_amdgcn_perm(0u, mid[r], 0x03030201u), diff);
-    return diff;
-}
 
 // All 81 candidates: per dy, offsets 0..3 / 4..7 as packed u16, offset 8 as (sad << 16 | idx);
 // returns the smallest packed key = first minimum in scan order.

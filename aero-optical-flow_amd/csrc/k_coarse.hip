@@ -27,6 +27,7 @@
 #include "aof_internal.hpp"
 #include "aof_lab_hooks.hpp"
 #include "aof_reduce.hpp"
+#include "aof_sad.hpp"
 
 namespace aof {
 
@@ -44,12 +45,6 @@ constexpr int kNonTemporal = 2;                // buffer-load cache policy: nt (
 constexpr int kScratch = 8;                    // words behind the histograms: pixel sums, vote sums
 constexpr int kStaggerGroups = 3;              // lab sweep (tools/coarse_lab.hip): 1: 0.215, 2: 0.206, 3: 0.203, 4: 0.212 ms
 constexpr int64_t kStaggerBytesPerUs = 75000;  // start-up spacing of the groups: ~8 us at VGA
-
-__device__ __forceinline__ u64 qsad(u64 window, uint32_t ref, u64 acc)
-{
-    return __builtin_amdgcn_qsad_pk_u16_u8(window, ref, acc);
-}
-__device__ __forceinline__ u64 pack64(uint32_t lo, uint32_t hi) { return ((u64)hi << 32) | lo; }
 
 // Workgroup barrier for data exchanged through LDS only.  __syncthreads() carries a workgroup
 // fence, for which the compiler drains EVERY outstanding vector-memory operation (s_waitcnt
@@ -216,18 +211,13 @@ __global__ __launch_bounds__(kThreads) void k_coarse(CoarseArgs a)
     for (int blk = tid; blk < nb; blk += kThreads) {
         const int by = (int)fast_div((uint32_t)blk, a.div_nx), bx = blk - by * a.grid.nx;
         const uint8_t *t = l1[0] + (y0 + 8 * by + 2) * w1 + x0 + 8 * bx;   // tile rows 2..5
-        uint32_t mid[4], diff = 0;
+        uint32_t mid[4];
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const uint32_t *q = reinterpret_cast<const uint32_t *>(t + r * w1);   // 4-byte aligned (x0 = 4)
             mid[r] = __builtin_amdgcn_alignbyte(q[1], q[0], 2);
         }
-#pragma unroll
-        for (int r = 0; r < 3; r++) diff = __builtin_amdgcn_sad_u8(mid[r], mid[r + 1], diff);
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-            diff = __builtin_amdgcn_sad_u8(mid[r], __builtin_amdgcn_perm(0u, mid[r], 0x03030201u), diff);
-        keys[blk] = diff >= (uint32_t)a.feature_threshold ? kOpen : kGated;
+        keys[blk] = gradient_gate(mid) >= (uint32_t)a.feature_threshold ? kOpen : kGated;
     }
     lds_barrier();
     AOF_LAB_STAMP(pair, 2);

@@ -23,6 +23,7 @@
 #include "aof_internal.hpp"
 #include "aof_reduce.hpp"
 #include "aof_refine.hpp"
+#include "aof_sad.hpp"
 
 namespace aof {
 
@@ -32,8 +33,6 @@ constexpr int kThreads = 256;
 constexpr int kMaxBins = 64;   // n = 2(2R+1)+1: 19 at level 1 (and for one level), 55 at level 0 of two (S = 4)
 constexpr int kLoads = 8;      // 16-byte chunks a thread has in flight in pass A
 constexpr int kPad = 16;       // bytes after each LDS frame: the dword reads of the last row may run past it
-
-__device__ __forceinline__ u64 pack64(uint32_t lo, uint32_t hi) { return ((u64)hi << 32) | lo; }
 
 // Unaligned reads from an LDS frame: aligned dwords, funnel-shifted by the byte offset's low bits.
 __device__ __forceinline__ uint4 lds_bytes16(const uint8_t *frame, int off)
@@ -60,20 +59,6 @@ __device__ __forceinline__ void lds_bytes12(const uint8_t *frame, int off, uint3
     out[0] = __builtin_amdgcn_alignbyte(q1, q0, sh);
     out[1] = __builtin_amdgcn_alignbyte(q2, q1, sh);
     out[2] = __builtin_amdgcn_alignbyte(q3, q2, sh);
-}
-
-// 4x4 gradient gate on tile bytes [2..5] x rows [2..5] (same arithmetic as aof_lane8.hpp)
-__device__ __forceinline__ uint32_t gate_4x4(const uint32_t (&ref)[8][2])
-{
-    uint32_t mid[4], diff = 0;
-#pragma unroll
-    for (int r = 0; r < 4; r++) mid[r] = __builtin_amdgcn_alignbyte(ref[r + 2][1], ref[r + 2][0], 2);
-#pragma unroll
-    for (int r = 0; r < 3; r++) diff = __builtin_amdgcn_sad_u8(mid[r], mid[r + 1], diff);
-#pragma unroll
-    for (int r = 0; r < 4; r++)
-        diff = __builtin_amdgcn_sad_u8(mid[r], __builtin_amdgcn_perm(0u, mid[r], 0x03030201u), diff);
-    return diff;
 }
 
 struct LevelMeta { int px, py, delta; };
@@ -107,7 +92,7 @@ __device__ __forceinline__ void run_level(const SearchArgs &a, const FlowTail &t
         uint32_t ref[8][2];
 #pragma unroll
         for (int r = 0; r < 8; r++) lds_bytes8(fp, (j + r) * W + i, ref[r]);
-        if (gate_4x4(ref) < (uint32_t)a.feature_threshold) continue;
+        if (gradient_gate(ref) < (uint32_t)a.feature_threshold) continue;
         u64 lo = 0, hi = 0;
         uint32_t k8 = (uint32_t)(d * 9 + 8);
 #pragma unroll
@@ -115,10 +100,10 @@ __device__ __forceinline__ void run_level(const SearchArgs &a, const FlowTail &t
             uint4 w = lds_bytes16(fc, (wy0 + d + r) * W + wx0);
             if (m.delta != 0) w = sat_add_u8x16(w, m.delta);
             const u64 p01 = pack64(w.x, w.y), p12 = pack64(w.y, w.z), p23 = pack64(w.z, w.w);
-            lo = __builtin_amdgcn_qsad_pk_u16_u8(p01, ref[r][0], lo);
-            lo = __builtin_amdgcn_qsad_pk_u16_u8(p12, ref[r][1], lo);
-            hi = __builtin_amdgcn_qsad_pk_u16_u8(p12, ref[r][0], hi);
-            hi = __builtin_amdgcn_qsad_pk_u16_u8(p23, ref[r][1], hi);
+            lo = qsad(p01, ref[r][0], lo);
+            lo = qsad(p12, ref[r][1], lo);
+            hi = qsad(p12, ref[r][0], hi);
+            hi = qsad(p23, ref[r][1], hi);
             k8 = __builtin_amdgcn_sad_hi_u8(w.z, ref[r][0], k8);
             k8 = __builtin_amdgcn_sad_hi_u8(w.w, ref[r][1], k8);
         }

@@ -17,6 +17,7 @@
 #include "aof_device.hpp"
 #include "aof_internal.hpp"
 #include "aof_refine.hpp"
+#include "aof_sad.hpp"
 
 namespace aof {
 
@@ -55,12 +56,6 @@ constexpr uint32_t kMaxFourRowSurvivorsPct = 40, kMaxEightRowSurvivorsPct = 10;
 // pay there), +-24 LSB 543, +-40 LSB 738, the realistic input 683 (no depth pays from there on).
 constexpr uint32_t kMaxSeparationForDeeperLook = 450;
 constexpr int kRefineParts = 4;  // lanes per block in the half-pixel refinement (1: 3.56, 2: 3.31, 4: 3.28 ms per 1 024 c5h pairs)
-
-__device__ __forceinline__ u64 qsad(u64 window, uint32_t ref, u64 acc)
-{
-    return __builtin_amdgcn_qsad_pk_u16_u8(window, ref, acc);
-}
-__device__ __forceinline__ u64 pack64(uint32_t lo, uint32_t hi) { return ((u64)hi << 32) | lo; }
 
 // One (dy row, block) item: the SADs of all 17 dx over the NR tile rows first, first + STEP, ...
 // (16, 1 from row 0: the whole tile; 4, 4: a quarter of it -- the lower bound of the pruned search
@@ -114,13 +109,7 @@ __device__ __forceinline__ uint32_t row_key(const u64 (&acc)[4], uint32_t acc16,
     return best;
 }
 
-// The smallest of a dy row's 17 partial sums alone (the lower bounds of the pruned search need no candidate index): packed
-// minima instead of 17 keys -- 11 instructions against row_key's 25, on every (dy, block) item of every block row.
-typedef unsigned short ushort2_t16 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pk_min_u16(uint32_t x, uint32_t y)
-{
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(ushort2_t16, x), __builtin_bit_cast(ushort2_t16, y)));
-}
+// A lower bound of the pruned search: the smallest of the item's 17 partial sums over NR tile rows (no candidate index).
 template <int NR, int STEP>
 __device__ __forceinline__ uint32_t bound_item(const uint8_t *s_prev, const uint8_t *s_cur, int W, int dyi, int bx, int xs,
                                                int first, int delta = 0)
@@ -128,10 +117,7 @@ __device__ __forceinline__ uint32_t bound_item(const uint8_t *s_prev, const uint
     u64 acc[4] = {0, 0, 0, 0};
     uint32_t acc16 = 0;   // offset 16 in the high half
     sum_item<NR, STEP>(s_prev, s_cur, W, dyi, bx, xs, first, acc, acc16, delta);
-    const uint32_t m01 = pk_min_u16(pk_min_u16((uint32_t)acc[0], (uint32_t)(acc[0] >> 32)), pk_min_u16((uint32_t)acc[1], (uint32_t)(acc[1] >> 32)));
-    const uint32_t m23 = pk_min_u16(pk_min_u16((uint32_t)acc[2], (uint32_t)(acc[2] >> 32)), pk_min_u16((uint32_t)acc[3], (uint32_t)(acc[3] >> 32)));
-    const uint32_t m = pk_min_u16(pk_min_u16(m01, m23), acc16 | 0xFFFFu);
-    return min(m & 0xFFFFu, m >> 16);
+    return row_min17(acc, acc16);
 }
 
 template <int NR, int STEP>
@@ -142,6 +128,22 @@ __device__ __forceinline__ uint32_t eval_item(const uint8_t *s_prev, const uint8
     uint32_t acc16 = (uint32_t)(dyi * kSide + 16);  // offset 16 as sad<<16 | idx
     sum_item<NR, STEP>(s_prev, s_cur, W, dyi, bx, xs, first, acc, acc16, delta);
     return row_key(acc, acc16, dyi);
+}
+
+// Adds up the sums of the four lanes of a quad that split an item's tile rows between them (sum_item<4, 4> from row
+// `part`).  u16 lanes cannot carry: a whole tile's SAD is at most 65 280.  Whole waves: shuffles.
+__device__ __forceinline__ void quad_join(u64 (&acc)[4], uint32_t &acc16)
+{
+#pragma unroll
+    for (int o = 1; o <= 2; o <<= 1) {
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            const uint32_t lo = (uint32_t)acc[g] + (uint32_t)__shfl_xor((int)(uint32_t)acc[g], o, 64);
+            const uint32_t hi = (uint32_t)(acc[g] >> 32) + (uint32_t)__shfl_xor((int)(uint32_t)(acc[g] >> 32), o, 64);
+            acc[g] = pack64(lo, hi);
+        }
+        acc16 += (uint32_t)__shfl_xor((int)acc16, o, 64);
+    }
 }
 
 // Staging of a block row: `total` 16-byte chunks, global memory -> LDS, `map(c, src, dst, is_cur)` names chunk c's addresses.
@@ -194,6 +196,22 @@ __device__ __forceinline__ void wave_append(uint16_t *list, uint32_t *count, boo
     if (lane == leader) base = atomicAdd(count, (uint32_t)__popcll(m));
     base = (uint32_t)__shfl((int)base, leader, 64);
     if (keep) list[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)item;
+}
+
+// Between B1 and B2: the items whose bound does not exceed their block's best SAD so far, compacted into s_list.
+__device__ __forceinline__ void list_survivors(const uint32_t *s_best, const uint16_t *s_pmin, uint16_t *s_list, uint32_t *s_count,
+                                               int nx, const SearchArgs &a, int items, int tid)
+{
+    for (int item0 = tid - (tid & 63); item0 < items; item0 += kThreads) {   // whole waves
+        const int item = item0 + (tid & 63);
+        bool keep = false;
+        if (item < items) {
+            const int dyi = (int)fast_div((uint32_t)item, a.div_nx), bx = item - dyi * nx;
+            const uint32_t bound = s_pmin[item];
+            keep = bound != 0xFFFFu && bound <= (s_best[bx] >> 16);
+        }
+        wave_append(s_list, s_count, keep, item);
+    }
 }
 
 // REFINE (half-pixel refinement, origin S+1): the ring of every best match lies in the staged block row
@@ -355,7 +373,8 @@ __global__ __launch_bounds__(kThreads) void k_search_tile16(SearchArgs a, uint32
             u64 acc[4] = {0, 0, 0, 0};
             uint32_t acc16 = part == 0 ? (uint32_t)(dyi * kSide + 16) : 0u;   // (the index once per quad)
             if (in) sum_item<4, 4>(s_prev, s_cur, W, dyi, bx, xf - sh, part, acc, acc16);
-            // u16 lanes cannot carry: a whole tile's SAD is at most 65 280
+            // the quad's sums joined as quad_join does (spelled out: calling it here changes the pruned kernels' code, and
+            // the half-pixel form then measured 0.7 % slower, profiles/isa_identity_sad_helpers_tile16_steps.txt)
 #pragma unroll
             for (int o = 1; o <= 2; o <<= 1) {
 #pragma unroll
@@ -372,16 +391,7 @@ __global__ __launch_bounds__(kThreads) void k_search_tile16(SearchArgs a, uint32
             }
         }
         __syncthreads();
-        for (int item0 = tid - (tid & 63); item0 < items; item0 += kThreads) {   // whole waves
-            const int item = item0 + (tid & 63);
-            bool keep = false;
-            if (item < items) {
-                const int dyi = (int)fast_div((uint32_t)item, a.div_nx), bx = item - dyi * nx;
-                const uint32_t bound = s_pmin[item];
-                keep = bound != 0xFFFFu && bound <= (s_best[bx] >> 16);
-            }
-            wave_append(s_list, s_count, keep, item);
-        }
+        list_survivors(s_best, s_pmin, s_list, s_count, nx, a, items, tid);
         __syncthreads();
         // B2: the survivors of the two-row bound get a four-row bound first (sensor noise lets half
         // of the two-row bounds through, the four-row bound stops most of those); what survives
@@ -433,12 +443,7 @@ __global__ __launch_bounds__(kThreads) void k_search_tile16(SearchArgs a, uint32
                 reinterpret_cast<const uint32_t *>(s_prev + (size_t)(6 + r) * W + 16 * bx + 4);
             mid[r] = __builtin_amdgcn_alignbyte(p[1], p[0], 2);  // tile bytes 6..9
         }
-        uint32_t diff = 0;
-#pragma unroll
-        for (int r = 0; r < 3; r++) diff = __builtin_amdgcn_sad_u8(mid[r], mid[r + 1], diff);
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-            diff = __builtin_amdgcn_sad_u8(mid[r], __builtin_amdgcn_perm(0u, mid[r], 0x03030201u), diff);
+        const uint32_t diff = gradient_gate(mid);
         aof_block rec;
         rec.dx = 0; rec.dy = 0; rec.sad = AOF_SAD_SKIPPED;
         const int xf = 16 * bx + px;
@@ -601,16 +606,7 @@ __global__ __launch_bounds__(kProbeThreads) void k_tile16_probe(SearchArgs a, ui
                 const int by = (blk / sx) * stride_y + stride_y / 2, bx = (blk % sx) * stride_x + stride_x / 2;
                 sum_item<4, 4>(prev + (int64_t)(16 * by + 8) * W + 8, cur + (int64_t)(16 * by + py) * W, W, (int)(m & 0xFFu), bx, 16 * bx + px, part, acc, acc16, delta);
             }
-#pragma unroll
-            for (int o = 1; o <= 2; o <<= 1) {
-#pragma unroll
-                for (int g = 0; g < 4; g++) {
-                    const uint32_t lo = (uint32_t)acc[g] + (uint32_t)__shfl_xor((int)(uint32_t)acc[g], o, 64);
-                    const uint32_t hi = (uint32_t)(acc[g] >> 32) + (uint32_t)__shfl_xor((int)(uint32_t)(acc[g] >> 32), o, 64);
-                    acc[g] = pack64(lo, hi);
-                }
-                acc16 += (uint32_t)__shfl_xor((int)acc16, o, 64);
-            }
+            quad_join(acc, acc16);
             if (blk < nsamp && part == 0) s_full[blk] = in ? (uint16_t)(row_key(acc, acc16, 0) >> 16) : (uint16_t)0xFFFFu;
         }
         // (b) overwrites the two-row bounds that (a) picks its rows from, and the waves without work in (a) get here first
@@ -626,17 +622,11 @@ __global__ __launch_bounds__(kProbeThreads) void k_tile16_probe(SearchArgs a, ui
             if (xf >= 0 && xf + 32 <= Wb && yc0 >= 0 && yc0 + 32 <= H) {
                 u64 acc[4] = {0, 0, 0, 0};
                 uint32_t acc16 = 0;
-                auto smallest = [](const u64 (&acc)[4], uint32_t acc16) -> uint32_t {
-                    const uint32_t m01 = pk_min_u16(pk_min_u16((uint32_t)acc[0], (uint32_t)(acc[0] >> 32)), pk_min_u16((uint32_t)acc[1], (uint32_t)(acc[1] >> 32)));
-                    const uint32_t m23 = pk_min_u16(pk_min_u16((uint32_t)acc[2], (uint32_t)(acc[2] >> 32)), pk_min_u16((uint32_t)acc[3], (uint32_t)(acc[3] >> 32)));
-                    const uint32_t m = pk_min_u16(pk_min_u16(m01, m23), acc16 | 0xFFFFu);
-                    return min(m & 0xFFFFu, m >> 16);
-                };
                 sum_item<4, 4>(prev + (int64_t)(16 * by + 8) * W + 8, cur + (int64_t)yc0 * W, W, dyi, bx, xf, 2, acc, acc16, delta);
-                b4 = smallest(acc, acc16);
+                b4 = row_min17(acc, acc16);
                 // (the same sums go on: u16 lanes, eight rows of 16 pixels stay below 65 536)
                 sum_item<4, 4>(prev + (int64_t)(16 * by + 8) * W + 8, cur + (int64_t)yc0 * W, W, dyi, bx, xf, 0, acc, acc16, delta);
-                b8 = smallest(acc, acc16);
+                b8 = row_min17(acc, acc16);
             }
             s_bound[blk][dyi] = (uint16_t)b4;
             s_bound1[blk][dyi] = (uint16_t)b8;
