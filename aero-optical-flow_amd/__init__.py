@@ -81,6 +81,25 @@ SEQ_STATUS_STALLED = 1
 assert SEQ_RECORD_DTYPE.itemsize == 32
 
 
+class BankParams(C.Structure):
+    """``aof_bank_params`` (include/aof.h)."""
+    _fields_ = [("n_streams", C.c_int32), ("frame_stride", C.c_int64), ("focal_x", C.c_float), ("focal_y", C.c_float),
+                ("output_rate", C.c_int32), ("offset_timestamp_usec", C.c_uint64),
+                ("system_id", C.c_uint8), ("component_id", C.c_uint8), ("first_seq", C.c_uint8)]
+
+
+class BankLayout(C.Structure):
+    """``struct aof_bank_layout`` (include/aof.h)."""
+    _fields_ = [(n, C.c_size_t) for n in ("total_bytes", "frames", "state", "scratch")]
+
+
+TICK_HELD, TICK_IDLE = -1, -2
+TICK_DTYPE = np.dtype([("quality", "<i4"), ("dt_us", "<i4"), ("flow_x", "<f4"), ("flow_y", "<f4"),
+                       ("gyro_x", "<f4"), ("gyro_y", "<f4"), ("gyro_z", "<f4"), ("frame", "<u4"), ("pixel", FLOW_DTYPE)])
+BANK_STATE_BYTES = 64
+assert TICK_DTYPE.itemsize == 48
+
+
 class WsLayout(C.Structure):
     _fields_ = [(n, C.c_size_t) for n in (
         "total_bytes", "sums", "l1_prev", "l1_cur", "l1_blocks", "l1_subdirs", "l1_flows",
@@ -161,6 +180,10 @@ def _load():
         "aof_sequence_layout": (C.c_int, [P(Params), P(SequenceParams), I64, P(SeqLayout)]),
         "aof_sequence_device": (C.c_int, [VP, P(SequenceParams), VP, I64, I64, VP, VP, VP, C.c_size_t, VP]),
         "aof_flow_angle": (C.c_float, [C.c_float, C.c_float]),
+        "aof_bank_layout": (C.c_int, [P(Params), P(BankParams), P(BankLayout)]),
+        "aof_bank_reset_device": (C.c_int, [VP, P(BankParams), VP, VP, C.c_size_t, VP]),
+        "aof_bank_push_device": (C.c_int, [VP, P(BankParams), VP, VP, VP, VP, VP, C.c_size_t, VP, VP, VP, VP]),
+        "aof_set_bank_path": (C.c_int, [VP, C.c_int]),
         "aof_derotate_batch_device": (C.c_int, [P(DerotateParams), VP, VP, I64, VP, VP]),
         "aof_exposure_msv": (C.c_float, [VP]),
         "aof_exposure_bin": (C.c_int, [C.c_int]),
@@ -296,6 +319,51 @@ def sequence_layout(p: Params, sp: SequenceParams, n_frames: int) -> SeqLayout:
     if rc:
         raise AofError(rc, lib.aof_strerror(rc).decode())
     return L
+
+
+def bank_params(n_streams, focal_x=216.6677, focal_y=216.2457, output_rate=15, offset_timestamp_usec=0, system_id=1,
+                component_id=100, first_seq=0, frame_stride=0) -> BankParams:
+    """``aof_bank_params`` of a bank of ``n_streams`` live streams (frame_stride 0: frames back to back)."""
+    bp = BankParams()
+    bp.n_streams, bp.frame_stride = n_streams, frame_stride
+    bp.focal_x, bp.focal_y, bp.output_rate = focal_x, focal_y, output_rate
+    bp.offset_timestamp_usec = offset_timestamp_usec
+    bp.system_id, bp.component_id, bp.first_seq = system_id, component_id, first_seq & 0xFF
+    return bp
+
+
+def bank_layout(p: Params, bp: BankParams) -> BankLayout:
+    L = BankLayout()
+    rc = lib.aof_bank_layout(C.byref(p), C.byref(bp), C.byref(L))
+    if rc:
+        raise AofError(rc, lib.aof_strerror(rc).decode())
+    return L
+
+
+def ticks_view(t) -> np.ndarray:
+    """uint8 tensor/array [S, 48] of ``aof_tick_record`` -> structured numpy view [S]."""
+    a = t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+    return np.ascontiguousarray(a).view(TICK_DTYPE).reshape(a.shape[0])
+
+
+class Bank:
+    """A stream bank in device memory (``FlowEngine.bank_create``): the buffer, its parameters and its layout."""
+
+    def __init__(self, bp: BankParams, layout: BankLayout, buffer):
+        self.bp, self.layout, self.buffer = bp, layout, buffer
+
+    @property
+    def n_streams(self) -> int:
+        return self.bp.n_streams
+
+    def frames_bytes(self) -> np.ndarray:
+        """Host copy of the bank's ``frames`` region (up to the state records)."""
+        return self.buffer[self.layout.frames:self.layout.state].cpu().numpy()
+
+    def state_bytes(self) -> np.ndarray:
+        """Host copy of the bank's ``state`` region: [S, 64] bytes."""
+        L = self.layout
+        return self.buffer[L.state:L.state + BANK_STATE_BYTES * self.n_streams].cpu().numpy().reshape(self.n_streams, BANK_STATE_BYTES)
 
 
 def exposure_msv(hist) -> float:
@@ -499,6 +567,54 @@ class FlowEngine:
         out["mavlink"] = [bytes(ws[L.frames + SEQ_FRAME_BYTES * m:L.frames + SEQ_FRAME_BYTES * m + int(lens[m])])
                           for m in range(int(count[0]))]
         return out
+
+    # -- a bank of live streams: many cameras per tick --------------------------------
+    def bank_create(self, bp: BankParams, device=None) -> "Bank":
+        """Allocates a bank for ``bp.n_streams`` streams as a (zeroed) torch buffer and resets it."""
+        import torch
+        L = bank_layout(self.params, bp)
+        dev = torch.device("cuda", self.device) if device is None else device
+        bank = Bank(bp, L, torch.zeros(L.total_bytes, dtype=torch.uint8, device=dev))
+        self.bank_reset(bank)
+        return bank
+
+    def bank_reset(self, bank: "Bank", mask=None):
+        """aof_bank_reset_device: mask uint8 CUDA tensor [S] (non-zero = reset) or None (all streams)."""
+        import torch
+        buf = bank.buffer
+        assert mask is None or (mask.dtype == torch.uint8 and mask.numel() == bank.n_streams and mask.is_contiguous())
+        self._check(lib.aof_bank_reset_device(self._ctx, C.byref(bank.bp), mask.data_ptr() if mask is not None else None,
+                                              buf.data_ptr(), buf.numel(), torch.cuda.current_stream(buf.device).cuda_stream))
+
+    def bank_push(self, bank: "Bank", frames, times, active=None, gyro=None, mavlink=False, records=None, out_frames=None,
+                  out_lengths=None):
+        """aof_bank_push_device, one tick: frames uint8 CUDA tensor [S, H, W] (stream s at s * frame_stride bytes);
+        times int64 CUDA tensor [S] (microseconds); active uint8 [S] or None (all); gyro float32 [S, 4] or None.
+        Everything is enqueued on torch's current stream.  Returns the record tensor [S, 48] (read it with
+        ticks_view()), and with mavlink=True (records, frames [S, 56], lengths [S])."""
+        import torch
+        S, buf = bank.n_streams, bank.buffer
+        dev = buf.device
+        assert frames.dtype == torch.uint8 and frames.is_contiguous()
+        assert times.dtype == torch.int64 and times.numel() == S
+        if records is None:
+            records = torch.empty((S, 48), dtype=torch.uint8, device=dev)
+        if mavlink:
+            if out_frames is None:
+                out_frames = torch.zeros((S, SEQ_FRAME_BYTES), dtype=torch.uint8, device=dev)
+            if out_lengths is None:
+                out_lengths = torch.zeros(S, dtype=torch.uint8, device=dev)
+        self._check(lib.aof_bank_push_device(
+            self._ctx, C.byref(bank.bp), frames.data_ptr(), times.data_ptr(), active.data_ptr() if active is not None else None,
+            gyro.data_ptr() if gyro is not None else None, buf.data_ptr(), buf.numel(), records.data_ptr(),
+            out_frames.data_ptr() if mavlink else None, out_lengths.data_ptr() if mavlink else None,
+            torch.cuda.current_stream(dev).cuda_stream))
+        return (records, out_frames, out_lengths) if mavlink else records
+
+    def set_bank_path(self, path=0):
+        """0: the library chooses between the one-launch tick kernel and the composed path, 1: the tick kernel where
+        the configuration allows it, 2: always the composed path.  Same bytes either way."""
+        self._check(lib.aof_set_bank_path(self._ctx, int(path)))
 
     # -- host buffers -----------------------------------------------------------
     def flow_pair_host(self, prev: np.ndarray, cur: np.ndarray):

@@ -1,0 +1,165 @@
+// The stream bank (include/aof.h, "a bank of live streams"): S live streams per tick from one device launch.  Host
+// side only: argument checks, the layout, the path choice and the launches of k_bank.hip -- the one-launch tick
+// kernel, or aof_flow_batch_device's own plan on (bank frames, tick frames) followed by the commit kernel.  Nothing
+// here allocates or synchronises.
+#include <cerrno>
+#include <cstring>
+
+#include "aof_internal.hpp"
+
+using namespace aof;
+
+namespace {
+
+size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// Largest bank the one-launch tick kernel serves under aof_set_bank_path(ctx, 0).  Measured (tools/bench_bank.py,
+// profiles/bank_tick_sweep.txt; us per tick, one-launch kernel / composed path): PX4 64x64 1 024 streams 13.0 / 17.2,
+// 1 536: 16.2 / 18.1, 2 048: 20.8 / 19.2, 4 096: 33.8 / 26.7; 128x128 on two levels 1 024: 39.9 / 48.3, 1 536: 50.1 /
+// 54.6, 2 048: 69.5 / 62.3, 4 096: 126.0 / 94.3.  A workgroup per stream wins until the grid is six rounds of the
+// device's 256 compute units; beyond that the grouped flow kernels make up for the commit kernel's second pass over
+// the new frames.  (Flow alone crosses at 128 pairs, kSmallMaxPairs of aof_batch.cpp: the tick's write-back and tail
+// ride along in the one launch and cost a launch and a pass of their own on the composed path.)
+constexpr int32_t kBankFusedMaxStreams = 1536;
+
+struct Layout {
+    struct aof_bank_layout pub;
+    size_t flow_ws_bytes, flows;   // inside the bank: the engine's workspace is at pub.scratch, the pixel records at `flows`
+    int64_t stride, frame;
+};
+
+int bank_layout(const aof_params *p, const aof_bank_params *bp, Layout *L)
+{
+    if (!p || !bp) return -EINVAL;
+    const int rc = aof_params_check(p);
+    if (rc) return rc;
+    if (bp->n_streams < 1) return -EINVAL;
+    const int64_t frame = (int64_t)p->width * p->height;
+    const int64_t stride = bp->frame_stride ? bp->frame_stride : frame;
+    if (stride < frame || (bp->frame_stride && stride % 16)) return -EINVAL;
+    if (!(bp->focal_x > 0.0f) || !(bp->focal_y > 0.0f)) return -EINVAL;
+    aof_ws_layout W;
+    const int rw = aof_workspace_layout(p, bp->n_streams, &W);
+    if (rw) return rw;
+    const size_t S = (size_t)bp->n_streams;
+    std::memset(L, 0, sizeof(*L));
+    size_t off = 0;
+    L->pub.frames = off;  off = align_up(off + S * (size_t)stride, 256);
+    L->pub.state = off;   off = align_up(off + S * sizeof(BankState), 256);
+    L->pub.scratch = off; off = align_up(off + W.total_bytes, 256);
+    L->flows = off;       off = align_up(off + S * sizeof(aof_flow), 256);
+    L->pub.total_bytes = off;
+    L->flow_ws_bytes = W.total_bytes;
+    L->stride = stride;
+    L->frame = frame;
+    return 0;
+}
+
+// Everything both entry points check about the bank itself.
+int check_bank(aof_ctx *ctx, const aof_bank_params *bp, const void *d_bank, size_t bank_bytes, Layout *L)
+{
+    if (!ctx) return -EINVAL;
+    aof_params p;
+    int rc = aof_get_params(ctx, &p);
+    if (rc) return rc;
+    if (!bp) return ctx_fail(ctx, -EINVAL, "null bank parameters");
+    rc = bank_layout(&p, bp, L);
+    if (rc) return ctx_fail(ctx, rc, "bad bank parameters (n_streams, frame_stride, focal length)");
+    if (!d_bank) return ctx_fail(ctx, -EINVAL, "null bank pointer");
+    if (reinterpret_cast<uintptr_t>(d_bank) % 256) return ctx_fail(ctx, -EINVAL, "bank must be 256-byte aligned");
+    if (bank_bytes < L->pub.total_bytes) return ctx_fail(ctx, -ENOSPC, "bank smaller than aof_bank_layout().total_bytes");
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int aof_bank_layout(const aof_params *p, const aof_bank_params *bp, struct aof_bank_layout *out)
+{
+    if (!out) return -EINVAL;
+    Layout L;
+    const int rc = bank_layout(p, bp, &L);
+    if (rc) return rc;
+    *out = L.pub;
+    return 0;
+}
+
+int aof_set_bank_path(aof_ctx *ctx, int path)
+{
+    if (!ctx || path < 0 || path > 2) return -EINVAL;
+    set_bank_path(ctx, path);
+    return 0;
+}
+
+int aof_bank_reset_device(aof_ctx *ctx, const aof_bank_params *bp, const uint8_t *d_mask, void *d_bank, size_t bank_bytes,
+                          void *stream)
+{
+    Layout L;
+    int rc = check_bank(ctx, bp, d_bank, bank_bytes, &L);
+    if (rc) return rc;
+    if ((rc = precheck(ctx))) return rc;
+    uint8_t *bank = static_cast<uint8_t *>(d_bank);
+    if (launch_bank_reset(reinterpret_cast<BankState *>(bank + L.pub.state), d_mask, bp->n_streams, stream))
+        return ctx_fail(ctx, -EIO, "bank reset launch failed");
+    return 0;
+}
+
+int aof_bank_push_device(aof_ctx *ctx, const aof_bank_params *bp, const uint8_t *d_frames, const uint64_t *d_time_us,
+                         const uint8_t *d_active, const aof_gyro *d_gyro, void *d_bank, size_t bank_bytes,
+                         aof_tick_record *d_records, uint8_t *d_mavlink, uint8_t *d_mavlink_len, void *stream)
+{
+    Layout L;
+    int rc = check_bank(ctx, bp, d_bank, bank_bytes, &L);
+    if (rc) return rc;
+    if (!d_frames || !d_time_us || !d_records) return ctx_fail(ctx, -EINVAL, "null frame, time stamp or record pointer");
+    if (d_mavlink && !d_mavlink_len) return ctx_fail(ctx, -EINVAL, "MAVLink frames need their length array");
+    if (reinterpret_cast<uintptr_t>(d_time_us) % 8 || reinterpret_cast<uintptr_t>(d_records) % 4 ||
+        reinterpret_cast<uintptr_t>(d_gyro) % 4)
+        return ctx_fail(ctx, -EINVAL, "time stamps must be 8-byte aligned, records and gyro samples 4-byte aligned");
+    // before the first launch: a faulted or wedged context, or a thread on another device, must not touch the bank
+    if ((rc = precheck(ctx))) return rc;
+
+    uint8_t *bank = static_cast<uint8_t *>(d_bank);
+    aof_flow *flows = reinterpret_cast<aof_flow *>(bank + L.flows);
+    BankArgs a;
+    a.n_streams = bp->n_streams;
+    a.frame_stride = L.stride;
+    a.frame_bytes = L.frame;
+    a.frames = d_frames;
+    a.time_us = d_time_us;
+    a.active = d_active;
+    a.gyro = d_gyro;
+    a.bank_frames = bank + L.pub.frames;
+    a.state = reinterpret_cast<BankState *>(bank + L.pub.state);
+    a.flows = flows;
+    a.output_rate = bp->output_rate;
+    a.period_us = bp->output_rate > 0 ? 1.0e6f / (float)bp->output_rate : 0.0f;   // (the facade's own division)
+    a.focal_x = bp->focal_x; a.focal_y = bp->focal_y;
+    a.offset_timestamp_usec = bp->offset_timestamp_usec;
+    a.system_id = bp->system_id; a.component_id = bp->component_id; a.first_seq = bp->first_seq;
+    a.records = d_records;
+    a.mavlink = d_mavlink;
+    a.mavlink_len = d_mavlink_len;
+
+    // which path: the one-launch kernel where the configuration (and these buffers) allow it and the bank is small
+    // enough for a workgroup per stream to pay, or because the caller asked for it
+    const int path = bank_path(ctx);
+    SmallArgs sm;
+    const bool fused = path != 2 &&
+                       plan_small_batch(ctx, a.bank_frames, d_frames, L.stride, bp->n_streams, flows, bank + L.pub.scratch, &sm) &&
+                       (path == 1 || bp->n_streams <= kBankFusedMaxStreams);
+    if (fused) {
+        if (launch_bank_tick(sm, a, stream)) return ctx_fail(ctx, -EIO, "bank tick launch failed");
+        return 0;
+    }
+    // composed: flows of (stored frame, new frame) for all S streams -- those of idle and first-frame streams are
+    // computed and ignored --, then the tails and the masked copy
+    rc = aof_flow_batch_device(ctx, a.bank_frames, d_frames, L.stride, bp->n_streams, nullptr, nullptr, flows,
+                               bank + L.pub.scratch, L.flow_ws_bytes, stream);
+    if (rc) return rc;
+    if (launch_bank_commit(a, stream)) return ctx_fail(ctx, -EIO, "bank commit launch failed");
+    return 0;
+}
+
+}  // extern "C"

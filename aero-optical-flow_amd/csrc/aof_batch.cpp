@@ -46,6 +46,7 @@ struct LevelPlan {
 // Every kernel choice of one aof_flow_batch_device call, made before the first launch.
 struct BatchPlan {
     bool small;        // k_flow_small does the whole batch in one launch, from `sm`; nothing below applies
+    bool small_class;  // ... could, were the batch not larger than kSmallMaxPairs (the stream bank's tick kernel asks)
     SmallArgs sm;
     CoarseKind coarse; // pixel sums / pyramid / level-1 search: none, fused into k_coarse, or K1 + level[1]
     bool k1_pass;      // COARSE_K1 and its outputs are not in the workspace yet: K1 runs
@@ -156,8 +157,9 @@ BatchPlan plan_batch(const aof_ctx *ctx, const BatchView &v, int64_t n, bool k1_
     // Small pairs (sparse grids, frames that fit LDS -- the reference's call shape): sums, pyramid, searches and
     // reductions of a pair in one launch, one workgroup per pair.  Large batches of such pairs keep the separate
     // kernels, whose grouped searches pack several pairs into a workgroup.
-    P.small = !ctx->force_generic && !ctx->split_coarse && n <= kSmallMaxPairs && P.level[0].kind == SK_LANE8_GROUP &&
-              (!two || plan_level(ctx, sm.l1, sm.t1).kind == SK_LANE8_GROUP) && flow_small_supported(sm);
+    P.small_class = !ctx->force_generic && !ctx->split_coarse && P.level[0].kind == SK_LANE8_GROUP &&
+                    (!two || plan_level(ctx, sm.l1, sm.t1).kind == SK_LANE8_GROUP) && flow_small_supported(sm);
+    P.small = P.small_class && n <= kSmallMaxPairs;
     if (P.small || (!two && !eq)) return P;   // (one level without equalisation: no coarse pass)
 
     // K1C: sums, pyramid, level-1 search and predictor of a pair in one workgroup, the level-1 frames never
@@ -402,6 +404,20 @@ bool plan_small_pair(const aof_ctx *ctx, const uint8_t *prev, const uint8_t *cur
     *sm = P.sm;
     return P.small;
 }
+
+bool plan_small_batch(const aof_ctx *ctx, const uint8_t *prev, const uint8_t *cur, int64_t stride, int64_t n, aof_flow *flows,
+                      void *d_workspace, SmallArgs *sm)
+{
+    aof_ws_layout L;
+    if (n < 1 || aof_workspace_layout(&ctx->params, n, &L)) return false;
+    const BatchView v = batch_view(ctx, L, prev, cur, stride, nullptr, nullptr, flows, d_workspace);
+    const BatchPlan P = plan_batch(ctx, v, n, false);
+    *sm = P.sm;
+    return P.small_class;
+}
+
+int bank_path(const aof_ctx *ctx) { return ctx->bank_path; }
+void set_bank_path(aof_ctx *ctx, int path) { ctx->bank_path = path; }
 
 // Would a sequence-view call (frames viewed twice, n_pairs = frames - 1) run K1 as a pass of its own?  The sequence
 // pipeline asks, because its ingest kernel can leave K1's outputs (pixel sums at ws + L.sums, one level-1 frame per

@@ -264,6 +264,55 @@ inline int sequence_rounds(int64_t n_frames)   // smallest R with 4^R > n_frames
     return r;
 }
 int launch_sequence_output(const SequenceArgs &a, void *stream);
+// The stream bank (aof_bank.cpp, k_bank.hip; include/aof.h "a bank of live streams").  Layout of a bank:
+//   frames   u8 [S][frame_stride]     the stored (previous) frame of every stream
+//   state    BankState [S]            what one facade object keeps between calcFlow() calls, 64 bytes per stream
+//   scratch  aof_workspace_layout(p, S) bytes (block records, sub-pixel directions, pixel sums and, on the composed
+//            path, everything the batch plan needs), then aof_flow [S]: the tick's pixel records
+// every region at a multiple of 256 bytes.
+struct BankState {
+    uint32_t has_prev;         // 0 after a reset: the next frame is the stream's first
+    uint32_t time_last_pub;    // OpticalFlow::time_last_pub
+    float sum_flow_x, sum_flow_y;   // the limiter's sums (initLimitRate)
+    int32_t sum_flow_quality, valid_frame_count;
+    double gyro_x, gyro_y, gyro_z;  // summed since the last publication (mainloop.cpp:383-405)
+    uint32_t messages;         // records published so far: the next MAVLink sequence number is first_seq + messages
+    uint32_t frames;           // frames the stream has been given
+    uint32_t pad[2];
+};
+static_assert(sizeof(BankState) == 64, "one bank state record is 64 bytes");
+struct BankArgs {
+    int32_t n_streams;
+    int64_t frame_stride, frame_bytes;
+    const uint8_t *frames;         // the tick's frames, stream s at + s * frame_stride
+    const uint64_t *time_us;       // [S]
+    const uint8_t *active;         // [S] or nullptr (= all)
+    const aof_gyro *gyro;          // [S] or nullptr (zeros)
+    uint8_t *bank_frames;          // [S][frame_stride]
+    BankState *state;              // [S]
+    const aof_flow *flows;         // [S] the tick's pixel records (composed path: written by the batch plan)
+    int32_t output_rate;
+    float period_us;               // 1e6f / output_rate, divided on the host as the facade divides
+    float focal_x, focal_y;
+    uint64_t offset_timestamp_usec;
+    uint8_t system_id, component_id, first_seq;
+    aof_tick_record *records;      // [S]
+    uint8_t *mavlink;              // [S][AOF_SEQ_FRAME_BYTES] or nullptr
+    uint8_t *mavlink_len;          // [S]
+};
+// One launch per tick: a workgroup per stream computes the pair with flow_small_pair, runs the stream's tail and
+// stores the new frame (sm: the small-pair plan of (bank frames, tick frames), flow_small_supported).
+int launch_bank_tick(const SmallArgs &sm, const BankArgs &a, void *stream);
+// Behind aof_flow_batch_device on (bank frames, tick frames): the tail of every stream and the masked copy of the
+// active streams' frames into the bank.
+int launch_bank_commit(const BankArgs &a, void *stream);
+int launch_bank_reset(BankState *state, const uint8_t *mask, int32_t n_streams, void *stream);
+// (aof_batch.cpp) the small-pair plan of n pairs, whatever n: true where one workgroup per pair can serve the
+// context's configuration and these buffers (flows: [n]; d_workspace: aof_workspace_layout(p, n))
+bool plan_small_batch(const aof_ctx *ctx, const uint8_t *prev, const uint8_t *cur, int64_t stride, int64_t n, aof_flow *flows,
+                      void *d_workspace, SmallArgs *sm);
+int bank_path(const aof_ctx *ctx);            // (aof_batch.cpp) aof_set_bank_path's value
+void set_bank_path(aof_ctx *ctx, int path);
 // (aof_capi.hip) sticky fault / wedged state and current-device check of a context, before anything is enqueued; and
 // aof_last_error's text for the callers outside aof_capi.hip
 int precheck(aof_ctx *ctx);

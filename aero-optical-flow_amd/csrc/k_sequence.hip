@@ -19,6 +19,7 @@
 // in the host's order: the frames are byte-identical to driving the C++ facade frame by frame.
 #include "aof_device.hpp"
 #include "aof_internal.hpp"
+#include "aof_mavlink.hpp"
 #include "aof_math.h"
 
 namespace aof {
@@ -83,19 +84,6 @@ __global__ __launch_bounds__(kThreads) void k_limit_double(SequenceArgs a, int r
     }
 }
 
-__device__ __forceinline__ uint16_t crc_accumulate(uint8_t byte, uint16_t crc)
-{
-    uint8_t tmp = (uint8_t)(byte ^ (uint8_t)(crc & 0xFF));
-    tmp = (uint8_t)(tmp ^ (uint8_t)(tmp << 4));
-    return (uint16_t)((crc >> 8) ^ ((uint16_t)tmp << 8) ^ ((uint16_t)tmp << 3) ^ (tmp >> 4));
-}
-
-template <typename T> __device__ __forceinline__ void put(uint8_t *&p, T v)
-{
-    __builtin_memcpy(p, &v, sizeof(T));   // little-endian wire order = the device's own
-    p += sizeof(T);
-}
-
 // One lane per frame; the lanes of published frames (frame 0, and the frames on the chain) write their message.
 __global__ __launch_bounds__(kThreads) void k_sequence_emit(SequenceArgs a)
 {
@@ -155,39 +143,10 @@ __global__ __launch_bounds__(kThreads) void k_sequence_emit(SequenceArgs a)
         a.frame_len[m] = 0;
         return;
     }
-    // field mapping of mainloop.cpp:359-371 (gyro axes switched to match pixel directions), wire order of
-    // OPTICAL_FLOW_RAD (message 106): by field size, then declaration
-    uint8_t payload[44];
-    uint8_t *p = payload;
-    put(p, (uint64_t)(a.offset_timestamp_usec + a.time_us[k]));
-    put(p, (uint32_t)dt_us);
-    put(p, ang_x);
-    put(p, ang_y);
-    put(p, (float)(-gy));
-    put(p, (float)gx);
-    put(p, (float)gz);
-    put(p, (uint32_t)0);        // time_delta_distance_us
-    put(p, -1.0f);              // distance
-    put(p, (int16_t)0);         // temperature
-    put(p, (uint8_t)0);         // sensor_id
-    put(p, (uint8_t)quality);
-    int len = 44;
-    while (len > 1 && payload[len - 1] == 0) len--;   // MAVLink 2 payload truncation
-    uint8_t head[10] = {0xFD, (uint8_t)len, 0, 0, (uint8_t)(a.first_seq + m), a.system_id, a.component_id, 106, 0, 0};
-    uint16_t crc = 0xFFFF;
-#pragma unroll
-    for (int b = 0; b < 10; b++) {
-        out[b] = head[b];
-        if (b) crc = crc_accumulate(head[b], crc);
-    }
-    for (int b = 0; b < len; b++) {
-        out[10 + b] = payload[b];
-        crc = crc_accumulate(payload[b], crc);
-    }
-    crc = crc_accumulate(138, crc);   // CRC_EXTRA of OPTICAL_FLOW_RAD
-    out[10 + len] = (uint8_t)(crc & 0xFF);
-    out[11 + len] = (uint8_t)(crc >> 8);
-    a.frame_len[m] = (uint8_t)(12 + len);
+    // field mapping, wire order and frame: aof_mavlink.hpp
+    uint8_t payload[kMavlinkPayloadBytes];
+    a.frame_len[m] = (uint8_t)pack_optical_flow_rad(out, payload, a.offset_timestamp_usec + a.time_us[k], dt_us, ang_x, ang_y, gx, gy, gz,
+                                                    quality, (uint8_t)(a.first_seq + m), a.system_id, a.component_id);
 }
 
 }  // namespace

@@ -394,6 +394,82 @@ int aof_sequence_device(aof_ctx *ctx, const aof_sequence_params *sp, const uint8
  * atan2(flow_px, focal_px) as a fixed sequence of IEEE double operations (include/aof_math.h).  Host only. */
 float aof_flow_angle(float flow_px, float focal_px);
 
+/* ---- a bank of live streams: many cameras per tick from one device launch ----
+ * A stream bank is device memory, owned by the caller, that holds for each of S independent live streams what one
+ * facade object holds on the host: the previous frame, the rate limiter's sums, the time of the last publication, the
+ * gyro sums and the MAVLink sequence number.  One aof_bank_push_device call per tick takes the newest frame of every
+ * stream that has one and leaves, per stream, exactly what OpticalFlow::calcFlow() + the reference's message code
+ * would have produced for that frame (facade/src/optical_flow.cpp integrate() / limitRate(), mainloop.cpp:322-373):
+ *   * a stream's first frame after a reset is stored; its record has quality 0, dt_us 0, flow 0, the tick's gyro
+ *     (taken and zeroed) and an all-zero pixel record; the time of the last publication stays 0 (this is what
+ *     aof_sequence_device writes for frame 0 and what mainloop.cpp sends after calcFlow() returned 0);
+ *   * otherwise: the pixel flow of (stored frame, new frame) -- the aof_flow bytes aof_flow_batch_device gives for that
+ *     pair --, then limitRate() on the stream's state, then aof_flow_angle; the new frame replaces the stored one.
+ *     Gyro increments are added as doubles every active tick, and taken (cast to float) and zeroed with every record
+ *     whose quality is >= 0;
+ *   * with d_mavlink and a non-zero offset_timestamp_usec every record with quality >= 0 gets its MAVLink 2
+ *     OPTICAL_FLOW_RAD frame (time_usec = offset + t, per-stream sequence number counting from first_seq),
+ *     byte-identical to fillOpticalFlowRad + packOpticalFlowRad;
+ *   * a stream without a frame in the tick gets AOF_TICK_IDLE and an otherwise zero record; its bank bytes (frame and
+ *     state) are not written.
+ * Both calls only enqueue: no allocation, no host synchronisation, capturable into a hipGraph.  Small configurations
+ * (8x8 tiles, +-4, grids of 8..256 blocks per level, width a multiple of 16, frames that fit LDS: the PX4 64x64 and
+ * the OpticalFlowOpenCV 128x128 two-level configurations among them) run a tick as ONE kernel, a workgroup per
+ * stream; every other configuration, and banks of more streams than that pays for, run aof_flow_batch_device's plan on
+ * (bank frames, tick frames) followed by one commit kernel.  The bytes are the same either way.
+ * Calls on one context and one bank must not overlap on the device (the bank is read and written in place, and the
+ * context's vote memory may serve the flow): keep them on one stream, or order them with events. */
+typedef struct aof_bank_params {
+    int32_t n_streams;               /* S >= 1 */
+    int64_t frame_stride;            /* bytes between the frames of consecutive streams, in the bank AND in the
+                                        caller's tick buffer; 0 = width*height; >= width*height, multiple of 16 */
+    float focal_x, focal_y;          /* px */
+    int32_t output_rate;             /* Hz; <= 0 publishes every frame */
+    uint64_t offset_timestamp_usec;  /* 0: records only, no frame is sent (mainloop.cpp:353-357) */
+    uint8_t system_id, component_id, first_seq;
+} aof_bank_params;
+
+#define AOF_TICK_HELD (-1)   /* calcFlow returned -1: still integrating */
+#define AOF_TICK_IDLE (-2)   /* the stream had no frame in this tick: nothing about it changed */
+typedef struct aof_tick_record {     /* 48 bytes, one per stream and tick */
+    int32_t quality;                 /* >= 0: published (what calcFlow returned), or AOF_TICK_HELD / AOF_TICK_IDLE */
+    int32_t dt_us;                   /* integration time of a published record, else 0 */
+    float flow_x, flow_y;            /* rad (aof_flow_angle) of a published record, else 0 */
+    float gyro_x, gyro_y, gyro_z;    /* rad, summed since the stream's previous publication, before the axis switch
+                                        (published records; else 0) */
+    uint32_t frame;                  /* frames this stream has been given, this one included (0 for idle streams) */
+    aof_flow pixel;                  /* this tick's pair record (all zero for a stream's first frame and for idle streams) */
+} aof_tick_record;
+
+/* Byte offsets of the regions of a bank.  (A struct tag only: C has one name space for typedefs and functions, and the
+ * function below carries the name.  Write `struct aof_bank_layout`.) */
+struct aof_bank_layout {
+    size_t total_bytes;
+    size_t frames;   /* u8 [S][frame_stride]: the stored frame of every stream */
+    size_t state;    /* one 64-byte record per stream (limiter, gyro sums, counters) */
+    size_t scratch;  /* the flow engine's workspace for S pairs and aof_flow [S] */
+};
+int aof_bank_layout(const aof_params *p, const aof_bank_params *bp, struct aof_bank_layout *out);   /* host only */
+/* d_mask: u8 [S] or NULL (= all).  Masked streams go back to "no previous frame", limiter and gyro sums zero,
+ * time of the last publication 0, sequence number first_seq, frame counter 0.  A new bank must be reset once.
+ * d_bank: >= aof_bank_layout().total_bytes, 256-byte aligned. */
+int aof_bank_reset_device(aof_ctx *ctx, const aof_bank_params *bp, const uint8_t *d_mask, void *d_bank,
+                          size_t bank_bytes, void *stream);
+/* d_frames: stream s at + s*frame_stride.  d_time_us: u64 [S], the limiter sees (uint32_t)t.  d_active: u8 [S] or
+ * NULL (= all).  d_gyro: aof_gyro [S] (integrated over the interval that ends at this frame) or NULL (zeros).
+ * d_records: aof_tick_record [S].  d_mavlink: u8 [S][AOF_SEQ_FRAME_BYTES] or NULL; d_mavlink_len: u8 [S]
+ * (0 = nothing sent), required with d_mavlink.
+ * -EINVAL: NULL ctx / params / bank / frames / times / records, n_streams < 1, a bad frame_stride or focal length, a
+ * bank that is not 256-byte aligned, d_mavlink without its lengths; -ENOSPC: a bank smaller than its layout; -EIO: the
+ * context's sticky fault.  A refused call leaves the bank untouched. */
+int aof_bank_push_device(aof_ctx *ctx, const aof_bank_params *bp, const uint8_t *d_frames, const uint64_t *d_time_us,
+                         const uint8_t *d_active, const aof_gyro *d_gyro, void *d_bank, size_t bank_bytes,
+                         aof_tick_record *d_records, uint8_t *d_mavlink, uint8_t *d_mavlink_len, void *stream);
+/* 0 = the library chooses (default), 1 = always the one-launch kernel where the configuration allows it (elsewhere
+ * the composed path, not an error), 2 = always the composed path.  Identical bytes either way (tests compare them).
+ * -EINVAL: NULL ctx, path outside 0..2. */
+int aof_set_bank_path(aof_ctx *ctx, int path);
+
 /* ---- measurement ----
  * With profiling on, every launch is bracketed by HIP events on the stream it
  * is launched on; the last AOF_PROFILE_RING launches of each kernel are kept.

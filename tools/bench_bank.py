@@ -1,0 +1,222 @@
+#!/usr/bin/env python3
+"""The stream bank's tick against the library's two existing ways in, one GPU, one process, legs alternated:
+  T0 / T1 / T2  aof_bank_push_device, all streams active, with MAVLink frames: as the library chooses the path (0), the
+                one-launch kernel (1), the composed path (2) -- the sweep kBankFusedMaxStreams (aof_bank.cpp) comes from;
+  B             what the library offers today for state-keeping streams: S contexts, one aof_stream_push_host each per
+                tick, in a loop on one thread (S <= 64 only);
+  C             aof_flow_batch_device on the same S pairs resident in memory: flow without state, the floor of any tick
+                that computes S flows.
+Every leg settles for about 0.2 s of untimed ticks, then times at least --ticks ticks and at least --seconds seconds
+with the host clock around ticks that end in a synchronise.  The whole sweep runs --repeats times: the difference
+between the repeats is the run-to-run spread a difference between legs has to beat.
+    python tools/bench_bank.py [--streams 1,16,...] [--configs px4-64,opencv-128] > profiles/bank_tick_sweep.txt"""
+import argparse
+import ctypes as C
+import importlib
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import __graft_entry__ as ge  # noqa: E402
+
+aof = ge.load_package()
+synth = importlib.import_module(ge.PKG_NAME + ".synth")
+FX, FY = 216.6677, 216.2457
+RING = 8          # ticks whose frames and time stamps are resident: the timed loop cycles through them
+POOL = 16         # distinct synthetic streams; stream s shows pool[s % POOL]
+
+
+def params_of(name):
+    if name == "px4-64":
+        return aof.px4flow_params(64, 64)
+    if name == "opencv-128":
+        return aof.px4flow_params(128, 128, pyramid_levels=2, mean_subtract=1)
+    raise SystemExit(f"unknown configuration {name}")
+
+
+def tick_bytes(p):
+    """Compulsory bytes per stream and tick: read the stored and the new frame, write the new one, the record and the
+    MAVLink frame; and of a stateless pair (algorithmic_bytes)."""
+    return 3 * p.width * p.height + 48 + 56, aof.algorithmic_bytes(p)
+
+
+def timed(step, sync, min_ticks, min_seconds, settle_seconds):
+    """step(i) enqueues tick i.  Returns (seconds per tick, ticks timed)."""
+    i, t0 = 0, time.perf_counter()
+    while time.perf_counter() - t0 < settle_seconds:
+        for _ in range(16):
+            step(i)
+            i += 1
+        sync()
+    done, elapsed, chunk = 0, 0.0, 256
+    while done < min_ticks or elapsed < min_seconds:
+        t0 = time.perf_counter()
+        for _ in range(chunk):
+            step(i)
+            i += 1
+        sync()
+        elapsed += time.perf_counter() - t0
+        done += chunk
+    return elapsed / done, done
+
+
+class Inputs:
+    """RING ticks of S streams on the device: frames [RING][S, h, w], times [RING][S]."""
+
+    def __init__(self, p, S, dev):
+        w, h = p.width, p.height
+        pool = np.stack([synth.make_sequence(w, h, RING + 1, 4, seed=500 + k, max_step=3)[0] for k in range(POOL)])   # [POOL, RING + 1, h, w]
+        idx = np.arange(S) % POOL
+        self.host = pool                                            # (the B leg pushes from host memory)
+        self.frames = [torch.from_numpy(pool[:, k]).to(dev)[torch.from_numpy(idx).to(dev)].contiguous() for k in range(RING + 1)]
+        # ~75 frames/s against a 15 Hz output rate: a publication every five frames (and one at the ring's wrap)
+        self.times = [torch.full((S,), 13333 * (k + 1), dtype=torch.int64, device=dev) for k in range(RING + 1)]
+        self.gyro = torch.full((S, 4), 0.001, dtype=torch.float32, device=dev)
+
+
+def leg_tick(p, S, path, inp, dev, a):
+    eng = aof.FlowEngine(p, 0)
+    eng.set_bank_path(path)
+    bp = aof.bank_params(S, FX, FY, 15, 5_000_000, 1, 100, 0)
+    bank = eng.bank_create(bp, dev)
+    recs = torch.empty((S, 48), dtype=torch.uint8, device=dev)
+    wire = torch.empty((S, 56), dtype=torch.uint8, device=dev)
+    lens = torch.empty(S, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    fn, ctx, bpp = aof.lib.aof_bank_push_device, eng._ctx, C.byref(bp)
+    calls = [(inp.frames[k].data_ptr(), inp.times[k].data_ptr()) for k in range(RING)]
+    rest = (None, inp.gyro.data_ptr(), bank.buffer.data_ptr(), bank.buffer.numel(), recs.data_ptr(), wire.data_ptr(), lens.data_ptr(), stream)
+
+    def step(i):
+        f, t = calls[i % RING]
+        rc = fn(ctx, bpp, f, t, *rest)
+        if rc:
+            raise aof.AofError(rc, aof.lib.aof_last_error(ctx).decode())
+    out = timed(step, torch.cuda.synchronize, a.ticks, a.seconds, a.settle)
+    r = aof.ticks_view(recs)
+    assert (r["quality"] >= aof.TICK_HELD).all() and (r["frame"] > a.ticks).all(), "the timed ticks were real ticks"
+    eng.close()
+    return out
+
+
+def leg_contexts(p, S, inp, a):
+    engs = [aof.FlowEngine(p, 0) for _ in range(S)]
+    flow = np.zeros(1, aof.FLOW_DTYPE)
+    frames = [[np.ascontiguousarray(inp.host[s % POOL, k]) for s in range(S)] for k in range(RING)]
+    fn = aof.lib.aof_stream_push_host
+    ctxs = [e._ctx for e in engs]
+    ptrs = [[f.ctypes.data for f in tick] for tick in frames]
+    out_ptr = flow.ctypes.data
+
+    def step(i):
+        row = ptrs[i % RING]
+        for s in range(S):
+            if fn(ctxs[s], row[s], out_ptr) < 0:
+                raise aof.AofError(-5, aof.lib.aof_last_error(ctxs[s]).decode())
+    out = timed(step, lambda: None, a.ticks, a.seconds, a.settle)   # (every call is synchronous)
+    for e in engs:
+        e.close()
+    return out
+
+
+def leg_batch(p, S, inp, dev, a):
+    eng = aof.FlowEngine(p, 0)
+    nb = eng.nblocks(0)
+    blocks = torch.empty((S, nb), dtype=torch.int32, device=dev)
+    flows = torch.empty((S, 16), dtype=torch.uint8, device=dev)
+    subdirs = torch.empty((S, nb), dtype=torch.uint8, device=dev) if p.subpixel else None
+    ws = torch.empty(aof.workspace_layout(p, S).total_bytes, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    calls = [eng.bind_batch(inp.frames[k], inp.frames[k + 1], blocks, flows, ws, subdirs=subdirs, stream=stream) for k in range(RING)]
+    out = timed(lambda i: calls[i % RING](), torch.cuda.synchronize, a.ticks, a.seconds, a.settle)
+    eng.close()
+    return out
+
+
+def class_marker(dev):
+    """K2 of the exhaustive C2 search (1 024 VGA pairs) on this GPU: the figure profiles/README.md tells boxes apart by."""
+    p = aof.default_params(640, 480)
+    base = [synth.make_pair(640, 480, reach=4, pair_index=k) for k in range(8)]
+    tp = torch.from_numpy(np.stack([b[0] for b in base])).to(dev).repeat(128, 1, 1).contiguous()
+    tc = torch.from_numpy(np.stack([b[1] for b in base])).to(dev).repeat(128, 1, 1).contiguous()
+    eng = aof.FlowEngine(p, 0)
+    eng.set_search_mode(aof.SEARCH_EXHAUSTIVE)
+    for _ in range(20):
+        eng.flow_batch(tp, tc)
+    torch.cuda.synchronize()
+    eng.set_profiling(True, kernels=[aof.K_SEARCH])
+    for _ in range(50):
+        eng.flow_batch(tp, tc)
+    torch.cuda.synchronize()
+    ms = float(np.median(eng.profile_ms(aof.K_SEARCH)))
+    eng.close()
+    return ms
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--streams", default="1,16,64,128,256,1024,4096,16384")
+    ap.add_argument("--configs", default="px4-64,opencv-128")
+    ap.add_argument("--ticks", type=int, default=2000, help="timed ticks per leg, at least")
+    ap.add_argument("--seconds", type=float, default=0.5, help="timed seconds per leg, at least")
+    ap.add_argument("--settle", type=float, default=0.2, help="untimed seconds in front of every leg")
+    ap.add_argument("--repeats", type=int, default=2)
+    ap.add_argument("--contexts-max", type=int, default=64, help="largest S of the B leg")
+    ap.add_argument("--legs", default="T0,T1,T2,C,B", help="legs to run (a kernel trace wants one at a time)")
+    ap.add_argument("--no-marker", action="store_true")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_bank.py measures on a GPU; none is visible")
+    dev = torch.device("cuda:0")
+    print(f"# tools/bench_bank.py {' '.join(sys.argv[1:])}")
+    print(f"# device: {torch.cuda.get_device_name(0)}")
+    if not a.no_marker:
+        print(f"# class marker: exhaustive C2 K2 (1 024 VGA pairs) {class_marker(dev):.4f} ms")
+    print("# legs: T0/T1/T2 bank tick on path 0/1/2 (MAVLink frames on, all streams active), B = S contexts x aof_stream_push_host, "
+          "C = aof_flow_batch_device on S pairs")
+    print("# us = microseconds per tick (host clock, ticks ending in a synchronise); Mframes/s = stream-frames per second")
+    sizes = [int(s) for s in a.streams.split(",")]
+    results = {}
+    for rep in range(a.repeats):
+        for cfg in a.configs.split(","):
+            p = params_of(cfg)
+            for S in sizes:
+                inp = Inputs(p, S, dev)
+                legs = [("T0", lambda: leg_tick(p, S, 0, inp, dev, a)), ("T1", lambda: leg_tick(p, S, 1, inp, dev, a)),
+                        ("T2", lambda: leg_tick(p, S, 2, inp, dev, a)), ("C", lambda: leg_batch(p, S, inp, dev, a))]
+                if S <= a.contexts_max:
+                    legs.append(("B", lambda: leg_contexts(p, S, inp, a)))
+                for name, fn in legs:
+                    if name not in a.legs.split(","):
+                        continue
+                    sec, n = fn()
+                    results.setdefault((cfg, S, name), []).append(sec)
+                    print(f"rep {rep} {cfg:11s} S={S:6d} {name:2s} {sec * 1e6:10.2f} us  {1 / sec:12.0f} ticks/s  {S / sec / 1e6:9.3f} Mframes/s  ({n} ticks)", flush=True)
+                del inp
+                torch.cuda.empty_cache()
+    if not all(n in a.legs.split(",") for n in ("T0", "T1", "T2", "C")):
+        return
+    print("# ---- summary (mean of the repeats; spread = |difference of the repeats| / mean) ----")
+    for cfg in a.configs.split(","):
+        tb, cb = tick_bytes(params_of(cfg))
+        print(f"# {cfg}: bytes per stream and tick {tb}, per stateless pair {cb} (ratio {tb / cb:.2f})")
+        for S in sizes:
+            m = {n: float(np.mean(results[(cfg, S, n)])) for n in ("T0", "T1", "T2", "C", "B") if (cfg, S, n) in results}
+            sp = {n: (abs(results[(cfg, S, n)][0] - results[(cfg, S, n)][-1]) / m[n]) for n in m}
+            best = "T1" if m["T1"] <= m["T2"] else "T2"
+            line = (f"{cfg:11s} S={S:6d}  T0 {m['T0'] * 1e6:9.2f} us (+-{sp['T0'] * 100:4.1f} %)  T1 {m['T1'] * 1e6:9.2f} (+-{sp['T1'] * 100:4.1f} %)  "
+                    f"T2 {m['T2'] * 1e6:9.2f} (+-{sp['T2'] * 100:4.1f} %)  C {m['C'] * 1e6:9.2f} (+-{sp['C'] * 100:4.1f} %)  "
+                    f"T0/C {m['T0'] / m['C']:5.2f}  faster path {best}  T0/best {m['T0'] / m[best]:5.3f}  "
+                    f"T0 {1 / m['T0']:9.0f} ticks/s {S / m['T0'] / 1e6:8.3f} Mframes/s")
+            if "B" in m:
+                line += f"  B {m['B'] * 1e6:9.2f} us  B/T0 {m['B'] / m['T0']:6.1f}x"
+            print(line)
+
+
+if __name__ == "__main__":
+    main()
