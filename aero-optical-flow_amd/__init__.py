@@ -93,11 +93,18 @@ class BankLayout(C.Structure):
     _fields_ = [(n, C.c_size_t) for n in ("total_bytes", "frames", "state", "scratch")]
 
 
+class BankCamera(C.Structure):
+    """``aof_bank_camera`` (include/aof.h)."""
+    _fields_ = [("ingest", IngestParams), ("camera_stride", C.c_int64), ("exposure_interval_us", C.c_uint32),
+                ("derotate", C.c_uint8), ("derotate_params", DerotateParams)]
+
+
 TICK_HELD, TICK_IDLE = -1, -2
 TICK_DTYPE = np.dtype([("quality", "<i4"), ("dt_us", "<i4"), ("flow_x", "<f4"), ("flow_y", "<f4"),
                        ("gyro_x", "<f4"), ("gyro_y", "<f4"), ("gyro_z", "<f4"), ("frame", "<u4"), ("pixel", FLOW_DTYPE)])
 BANK_STATE_BYTES = 64
-assert TICK_DTYPE.itemsize == 48
+EXPOSURE_DTYPE = np.dtype([("hist", "<u4", (10,)), ("msv", "<f4"), ("due", "<u4")])   # aof_exposure_record
+assert TICK_DTYPE.itemsize == 48 and EXPOSURE_DTYPE.itemsize == 48
 
 
 class WsLayout(C.Structure):
@@ -184,6 +191,9 @@ def _load():
         "aof_bank_reset_device": (C.c_int, [VP, P(BankParams), VP, VP, C.c_size_t, VP]),
         "aof_bank_push_device": (C.c_int, [VP, P(BankParams), VP, VP, VP, VP, VP, C.c_size_t, VP, VP, VP, VP]),
         "aof_set_bank_path": (C.c_int, [VP, C.c_int]),
+        "aof_bank_camera_layout": (C.c_int, [P(Params), P(BankParams), P(BankCamera), P(BankLayout), P(C.c_size_t)]),
+        "aof_bank_push_camera_device": (C.c_int, [VP, P(BankParams), P(BankCamera), VP, VP, VP, VP, VP, C.c_size_t, VP, VP, VP,
+                                                  VP, VP, VP]),
         "aof_derotate_batch_device": (C.c_int, [P(DerotateParams), VP, VP, I64, VP, VP]),
         "aof_exposure_msv": (C.c_float, [VP]),
         "aof_exposure_bin": (C.c_int, [C.c_int]),
@@ -340,6 +350,34 @@ def bank_layout(p: Params, bp: BankParams) -> BankLayout:
     return L
 
 
+def bank_camera_params(cam_w, cam_h, crop_w, crop_h, camera_stride=0, exposure_interval_us=200000, derotate=None,
+                       focal_x=216.6677, focal_y=216.2457) -> BankCamera:
+    """``aof_bank_camera``: sensor size -> centre crop; derotate: None or (max_flow, rate_threshold) of the gyro
+    compensation; exposure_interval_us: mainloop.cpp:274 (0 = statistics with every frame)."""
+    cam = BankCamera()
+    cam.ingest = IngestParams(cam_w, cam_h, crop_w, crop_h)
+    cam.camera_stride, cam.exposure_interval_us = camera_stride, exposure_interval_us
+    cam.derotate = 0 if derotate is None else 1
+    if derotate is not None:
+        cam.derotate_params = DerotateParams(focal_x, focal_y, derotate[0], derotate[1])
+    return cam
+
+
+def bank_camera_layout(p: Params, bp: BankParams, cam: BankCamera):
+    """(``BankLayout``, offset of the staging region) of a bank that serves ``bank_push_camera``."""
+    L, staging = BankLayout(), C.c_size_t()
+    rc = lib.aof_bank_camera_layout(C.byref(p), C.byref(bp), C.byref(cam), C.byref(L), C.byref(staging))
+    if rc:
+        raise AofError(rc, lib.aof_strerror(rc).decode())
+    return L, staging.value
+
+
+def exposure_view(t) -> np.ndarray:
+    """uint8 tensor/array [S, 48] of ``aof_exposure_record`` -> structured numpy view [S]."""
+    a = t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+    return np.ascontiguousarray(a).view(EXPOSURE_DTYPE).reshape(a.shape[0])
+
+
 def ticks_view(t) -> np.ndarray:
     """uint8 tensor/array [S, 48] of ``aof_tick_record`` -> structured numpy view [S]."""
     a = t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
@@ -349,8 +387,9 @@ def ticks_view(t) -> np.ndarray:
 class Bank:
     """A stream bank in device memory (``FlowEngine.bank_create``): the buffer, its parameters and its layout."""
 
-    def __init__(self, bp: BankParams, layout: BankLayout, buffer):
+    def __init__(self, bp: BankParams, layout: BankLayout, buffer, camera: BankCamera = None, staging: int = None):
         self.bp, self.layout, self.buffer = bp, layout, buffer
+        self.camera, self.staging = camera, staging     # (a bank made for bank_push_camera: its staging region's offset)
 
     @property
     def n_streams(self) -> int:
@@ -569,12 +608,17 @@ class FlowEngine:
         return out
 
     # -- a bank of live streams: many cameras per tick --------------------------------
-    def bank_create(self, bp: BankParams, device=None) -> "Bank":
-        """Allocates a bank for ``bp.n_streams`` streams as a (zeroed) torch buffer and resets it."""
+    def bank_create(self, bp: BankParams, device=None, camera: BankCamera = None) -> "Bank":
+        """Allocates a bank for ``bp.n_streams`` streams as a (zeroed) torch buffer and resets it.  camera: the bank is
+        sized by aof_bank_camera_layout and serves bank_push_camera (and bank_push)."""
         import torch
-        L = bank_layout(self.params, bp)
+        staging = None
+        if camera is None:
+            L = bank_layout(self.params, bp)
+        else:
+            L, staging = bank_camera_layout(self.params, bp, camera)
         dev = torch.device("cuda", self.device) if device is None else device
-        bank = Bank(bp, L, torch.zeros(L.total_bytes, dtype=torch.uint8, device=dev))
+        bank = Bank(bp, L, torch.zeros(L.total_bytes, dtype=torch.uint8, device=dev), camera, staging)
         self.bank_reset(bank)
         return bank
 
@@ -610,6 +654,38 @@ class FlowEngine:
             out_frames.data_ptr() if mavlink else None, out_lengths.data_ptr() if mavlink else None,
             torch.cuda.current_stream(dev).cuda_stream))
         return (records, out_frames, out_lengths) if mavlink else records
+
+    def bank_push_camera(self, bank: "Bank", camera, times, active=None, gyro=None, mavlink=False, records=None,
+                         exposure=None, derotated=None, out_frames=None, out_lengths=None, want_exposure=True):
+        """aof_bank_push_camera_device, one tick on raw sensor frames: camera uint8 CUDA tensor, stream s's sensor frame
+        at s * camera_stride bytes (no alignment needed); the rest as bank_push.  exposure: uint8 [S, 48] (read it with
+        exposure_view()), allocated unless want_exposure is False (then no statistics, the gate does not move);
+        derotated: float32 [S, 2], allocated when the bank's camera parameters ask for de-rotation.  Returns a dict of
+        the output tensors: records, exposure, derotated, frames, lengths (None where not written)."""
+        import torch
+        S, buf, cam = bank.n_streams, bank.buffer, bank.camera
+        assert cam is not None, "bank_create(..., camera=...) makes a bank for sensor frames"
+        dev = buf.device
+        assert camera.dtype == torch.uint8 and times.dtype == torch.int64 and times.numel() == S
+        if records is None:
+            records = torch.empty((S, 48), dtype=torch.uint8, device=dev)
+        if exposure is None and want_exposure:
+            exposure = torch.empty((S, 48), dtype=torch.uint8, device=dev)
+        if derotated is None and cam.derotate:
+            derotated = torch.empty((S, 2), dtype=torch.float32, device=dev)
+        if mavlink:
+            if out_frames is None:
+                out_frames = torch.zeros((S, SEQ_FRAME_BYTES), dtype=torch.uint8, device=dev)
+            if out_lengths is None:
+                out_lengths = torch.zeros(S, dtype=torch.uint8, device=dev)
+        self._check(lib.aof_bank_push_camera_device(
+            self._ctx, C.byref(bank.bp), C.byref(cam), camera.data_ptr(), times.data_ptr(),
+            active.data_ptr() if active is not None else None, gyro.data_ptr() if gyro is not None else None,
+            buf.data_ptr(), buf.numel(), records.data_ptr(), exposure.data_ptr() if exposure is not None else None,
+            derotated.data_ptr() if derotated is not None else None, out_frames.data_ptr() if mavlink else None,
+            out_lengths.data_ptr() if mavlink else None, torch.cuda.current_stream(dev).cuda_stream))
+        return dict(records=records, exposure=exposure, derotated=derotated, frames=out_frames if mavlink else None,
+                    lengths=out_lengths if mavlink else None)
 
     def set_bank_path(self, path=0):
         """0: the library chooses between the one-launch tick kernel and the composed path, 1: the tick kernel where

@@ -21,11 +21,21 @@ size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // the new frames.  (Flow alone crosses at 128 pairs, kSmallMaxPairs of aof_batch.cpp: the tick's write-back and tail
 // ride along in the one launch and cost a launch and a pass of their own on the composed path.)
 constexpr int32_t kBankFusedMaxStreams = 1536;
+// The same for aof_bank_push_camera_device, whose composed path carries a third launch (the ingest kernel into the
+// staging region) and a crop written and read again.  Measured (tools/bench_bank.py --camera, legs K1 / K2,
+// profiles/bank_camera_tick_sweep.txt; us per tick, one-launch kernel / composed path): 320x240 -> PX4 64x64 1 024
+// streams 16.4 / 25.8, 1 536: 19.9 / 28.7, 2 048: 25.4 / 30.5, 3 072: 32.1 / 40.5, 4 096: 40.7 / 45.0; 640x480 -> 128x128 on
+// two levels 1 024: 44.1 / 63.1, 1 536: 55.7 / 71.5, 2 048: 74.9 / 80.8, 3 072: 103.2 / 107.5, 4 096: 133.9 / 127.9.  (With the
+// plain tick's 1 536 the library's own choice lost 18 % and 7 % at 2 048 streams.)  The two-level configuration crosses
+// between 3 072 and 4 096 streams, the small frames beyond 4 096; 3 072 was measured only in the sweep that ran with this
+// constant at 2 048, which therefore stays: the largest size at which the library's own choice was measured and tested.
+constexpr int32_t kBankCameraFusedMaxStreams = 2048;
 
 struct Layout {
     struct aof_bank_layout pub;
     size_t flow_ws_bytes, flows;   // inside the bank: the engine's workspace is at pub.scratch, the pixel records at `flows`
     int64_t stride, frame;
+    size_t staging, staging_hist;  // camera layout only: the tick's cropped frames and their raw histograms
 };
 
 int bank_layout(const aof_params *p, const aof_bank_params *bp, Layout *L)
@@ -55,20 +65,82 @@ int bank_layout(const aof_params *p, const aof_bank_params *bp, Layout *L)
     return 0;
 }
 
-// Everything both entry points check about the bank itself.
-int check_bank(aof_ctx *ctx, const aof_bank_params *bp, const void *d_bank, size_t bank_bytes, Layout *L)
+// The bank layout plus the staging region of the camera push; also everything about `cam` that needs no context.
+int camera_layout(const aof_params *p, const aof_bank_params *bp, const aof_bank_camera *cam, Layout *L)
+{
+    if (!cam) return -EINVAL;
+    const int rc = bank_layout(p, bp, L);
+    if (rc) return rc;
+    const aof_ingest_params &g = cam->ingest;
+    if (g.crop_width != p->width || g.crop_height != p->height) return -EINVAL;
+    if (g.crop_width > g.camera_width || g.crop_height > g.camera_height) return -EINVAL;
+    if (cam->camera_stride && cam->camera_stride < (int64_t)g.camera_width * g.camera_height) return -EINVAL;
+    const size_t S = (size_t)bp->n_streams;
+    size_t off = L->pub.total_bytes;
+    L->staging = off;
+    L->staging_hist = align_up(off + S * (size_t)L->stride, 256);
+    L->pub.total_bytes = align_up(L->staging_hist + S * AOF_EXPOSURE_BINS * sizeof(uint32_t), 256);
+    return 0;
+}
+
+// Everything all entry points check about the bank itself (cam: the camera push, whose bank has a staging region).
+int check_bank(aof_ctx *ctx, const aof_bank_params *bp, const void *d_bank, size_t bank_bytes, Layout *L,
+               const aof_bank_camera *cam = nullptr, bool camera = false)
 {
     if (!ctx) return -EINVAL;
     aof_params p;
     int rc = aof_get_params(ctx, &p);
     if (rc) return rc;
     if (!bp) return ctx_fail(ctx, -EINVAL, "null bank parameters");
-    rc = bank_layout(&p, bp, L);
-    if (rc) return ctx_fail(ctx, rc, "bad bank parameters (n_streams, frame_stride, focal length)");
+    if (camera && !cam) return ctx_fail(ctx, -EINVAL, "null bank camera parameters");
+    rc = camera ? camera_layout(&p, bp, cam, L) : bank_layout(&p, bp, L);
+    if (rc) return ctx_fail(ctx, rc, camera ? "bad bank parameters (n_streams, frame_stride, focal length) or bank camera parameters (crop, camera_stride)"
+                                            : "bad bank parameters (n_streams, frame_stride, focal length)");
     if (!d_bank) return ctx_fail(ctx, -EINVAL, "null bank pointer");
     if (reinterpret_cast<uintptr_t>(d_bank) % 256) return ctx_fail(ctx, -EINVAL, "bank must be 256-byte aligned");
-    if (bank_bytes < L->pub.total_bytes) return ctx_fail(ctx, -ENOSPC, "bank smaller than aof_bank_layout().total_bytes");
+    if (bank_bytes < L->pub.total_bytes)
+        return ctx_fail(ctx, -ENOSPC, camera ? "bank smaller than aof_bank_camera_layout().total_bytes" : "bank smaller than aof_bank_layout().total_bytes");
     return 0;
+}
+
+// What the plain and the camera push check about their shared arguments.
+int check_tick(aof_ctx *ctx, const void *d_frames, const uint64_t *d_time_us, const aof_gyro *d_gyro, const aof_tick_record *d_records,
+               const uint8_t *d_mavlink, const uint8_t *d_mavlink_len)
+{
+    if (!d_frames || !d_time_us || !d_records) return ctx_fail(ctx, -EINVAL, "null frame, time stamp or record pointer");
+    if (d_mavlink && !d_mavlink_len) return ctx_fail(ctx, -EINVAL, "MAVLink frames need their length array");
+    if (reinterpret_cast<uintptr_t>(d_time_us) % 8 || reinterpret_cast<uintptr_t>(d_records) % 4 ||
+        reinterpret_cast<uintptr_t>(d_gyro) % 4)
+        return ctx_fail(ctx, -EINVAL, "time stamps must be 8-byte aligned, records and gyro samples 4-byte aligned");
+    return 0;
+}
+
+// The tick's arguments for the kernels of k_bank.hip (frames: the caller's tick buffer, or the staging region).
+BankArgs bank_args(const aof_bank_params *bp, const Layout &L, uint8_t *bank, const uint8_t *frames, const uint64_t *d_time_us,
+                   const uint8_t *d_active, const aof_gyro *d_gyro, aof_tick_record *d_records, uint8_t *d_mavlink,
+                   uint8_t *d_mavlink_len)
+{
+    BankArgs a;
+    std::memset(&a, 0, sizeof(a));   // (cam.camera == nullptr: a plain tick)
+    a.n_streams = bp->n_streams;
+    a.frame_stride = L.stride;
+    a.frame_bytes = L.frame;
+    a.frames = frames;
+    a.time_us = d_time_us;
+    a.active = d_active;
+    a.gyro = d_gyro;
+    a.bank_frames = bank + L.pub.frames;
+    a.state = reinterpret_cast<BankState *>(bank + L.pub.state);
+    a.flows = reinterpret_cast<aof_flow *>(bank + L.flows);
+    a.output_rate = bp->output_rate;
+    a.period_us = bp->output_rate > 0 ? 1.0e6f / (float)bp->output_rate : 0.0f;   // (the facade's own division)
+    a.focal_x = bp->focal_x; a.focal_y = bp->focal_y;
+    a.offset_timestamp_usec = bp->offset_timestamp_usec;
+    a.system_id = bp->system_id; a.component_id = bp->component_id; a.first_seq = bp->first_seq;
+    a.records = d_records;
+    a.mavlink = d_mavlink;
+    a.mavlink_len = d_mavlink_len;
+    return a;
 }
 
 }  // namespace
@@ -112,35 +184,13 @@ int aof_bank_push_device(aof_ctx *ctx, const aof_bank_params *bp, const uint8_t 
     Layout L;
     int rc = check_bank(ctx, bp, d_bank, bank_bytes, &L);
     if (rc) return rc;
-    if (!d_frames || !d_time_us || !d_records) return ctx_fail(ctx, -EINVAL, "null frame, time stamp or record pointer");
-    if (d_mavlink && !d_mavlink_len) return ctx_fail(ctx, -EINVAL, "MAVLink frames need their length array");
-    if (reinterpret_cast<uintptr_t>(d_time_us) % 8 || reinterpret_cast<uintptr_t>(d_records) % 4 ||
-        reinterpret_cast<uintptr_t>(d_gyro) % 4)
-        return ctx_fail(ctx, -EINVAL, "time stamps must be 8-byte aligned, records and gyro samples 4-byte aligned");
+    if ((rc = check_tick(ctx, d_frames, d_time_us, d_gyro, d_records, d_mavlink, d_mavlink_len))) return rc;
     // before the first launch: a faulted or wedged context, or a thread on another device, must not touch the bank
     if ((rc = precheck(ctx))) return rc;
 
     uint8_t *bank = static_cast<uint8_t *>(d_bank);
+    const BankArgs a = bank_args(bp, L, bank, d_frames, d_time_us, d_active, d_gyro, d_records, d_mavlink, d_mavlink_len);
     aof_flow *flows = reinterpret_cast<aof_flow *>(bank + L.flows);
-    BankArgs a;
-    a.n_streams = bp->n_streams;
-    a.frame_stride = L.stride;
-    a.frame_bytes = L.frame;
-    a.frames = d_frames;
-    a.time_us = d_time_us;
-    a.active = d_active;
-    a.gyro = d_gyro;
-    a.bank_frames = bank + L.pub.frames;
-    a.state = reinterpret_cast<BankState *>(bank + L.pub.state);
-    a.flows = flows;
-    a.output_rate = bp->output_rate;
-    a.period_us = bp->output_rate > 0 ? 1.0e6f / (float)bp->output_rate : 0.0f;   // (the facade's own division)
-    a.focal_x = bp->focal_x; a.focal_y = bp->focal_y;
-    a.offset_timestamp_usec = bp->offset_timestamp_usec;
-    a.system_id = bp->system_id; a.component_id = bp->component_id; a.first_seq = bp->first_seq;
-    a.records = d_records;
-    a.mavlink = d_mavlink;
-    a.mavlink_len = d_mavlink_len;
 
     // which path: the one-launch kernel where the configuration (and these buffers) allow it and the bank is small
     // enough for a workgroup per stream to pay, or because the caller asked for it
@@ -156,6 +206,74 @@ int aof_bank_push_device(aof_ctx *ctx, const aof_bank_params *bp, const uint8_t 
     // composed: flows of (stored frame, new frame) for all S streams -- those of idle and first-frame streams are
     // computed and ignored --, then the tails and the masked copy
     rc = aof_flow_batch_device(ctx, a.bank_frames, d_frames, L.stride, bp->n_streams, nullptr, nullptr, flows,
+                               bank + L.pub.scratch, L.flow_ws_bytes, stream);
+    if (rc) return rc;
+    if (launch_bank_commit(a, stream)) return ctx_fail(ctx, -EIO, "bank commit launch failed");
+    return 0;
+}
+
+int aof_bank_camera_layout(const aof_params *p, const aof_bank_params *bp, const aof_bank_camera *cam,
+                           struct aof_bank_layout *out, size_t *staging)
+{
+    if (!out || !staging) return -EINVAL;
+    Layout L;
+    const int rc = camera_layout(p, bp, cam, &L);
+    if (rc) return rc;
+    *out = L.pub;
+    *staging = L.staging;
+    return 0;
+}
+
+int aof_bank_push_camera_device(aof_ctx *ctx, const aof_bank_params *bp, const aof_bank_camera *cam, const uint8_t *d_camera,
+                                const uint64_t *d_time_us, const uint8_t *d_active, const aof_gyro *d_gyro, void *d_bank,
+                                size_t bank_bytes, aof_tick_record *d_records, aof_exposure_record *d_exposure,
+                                float *d_derotated, uint8_t *d_mavlink, uint8_t *d_mavlink_len, void *stream)
+{
+    Layout L;
+    int rc = check_bank(ctx, bp, d_bank, bank_bytes, &L, cam, true);
+    if (rc) return rc;
+    if ((rc = check_tick(ctx, d_camera, d_time_us, d_gyro, d_records, d_mavlink, d_mavlink_len))) return rc;
+    if (cam->derotate && !d_derotated) return ctx_fail(ctx, -EINVAL, "bank camera: derotate needs d_derotated");
+    if (reinterpret_cast<uintptr_t>(d_exposure) % 4 || reinterpret_cast<uintptr_t>(d_derotated) % 4)
+        return ctx_fail(ctx, -EINVAL, "bank camera: exposure records and de-rotated pairs must be 4-byte aligned");
+    if ((rc = precheck(ctx))) return rc;
+
+    uint8_t *bank = static_cast<uint8_t *>(d_bank);
+    uint8_t *staging = bank + L.staging;
+    uint32_t *hist = reinterpret_cast<uint32_t *>(bank + L.staging_hist);
+    BankArgs a = bank_args(bp, L, bank, staging, d_time_us, d_active, d_gyro, d_records, d_mavlink, d_mavlink_len);
+    aof_flow *flows = reinterpret_cast<aof_flow *>(bank + L.flows);
+    const aof_ingest_params &g = cam->ingest;
+    const int x0 = g.camera_width / 2 - g.crop_width / 2, y0 = g.camera_height / 2 - g.crop_height / 2;   // mainloop.cpp:295-296
+    a.cam.camera = d_camera;
+    a.cam.camera_stride = cam->camera_stride ? cam->camera_stride : (int64_t)g.camera_width * g.camera_height;
+    a.cam.pitch = g.camera_width;
+    a.cam.origin = y0 * g.camera_width + x0;
+    a.cam.crop_w = g.crop_width; a.cam.crop_h = g.crop_height;
+    const int mx0 = g.crop_width / 2 - AOF_EXPOSURE_MASK_SIZE / 2, my0 = g.crop_height / 2 - AOF_EXPOSURE_MASK_SIZE / 2;   // :203-206
+    a.cam.mx0 = mx0 < 0 ? 0 : mx0; a.cam.my0 = my0 < 0 ? 0 : my0;
+    a.cam.mx1 = mx0 + AOF_EXPOSURE_MASK_SIZE > g.crop_width ? g.crop_width : mx0 + AOF_EXPOSURE_MASK_SIZE;
+    a.cam.my1 = my0 + AOF_EXPOSURE_MASK_SIZE > g.crop_height ? g.crop_height : my0 + AOF_EXPOSURE_MASK_SIZE;
+    a.cam.hist = hist;
+    a.cam.exposure = d_exposure;
+    a.cam.interval_us = cam->exposure_interval_us;
+    a.cam.derotated = cam->derotate ? d_derotated : nullptr;
+    a.cam.derotate = cam->derotate_params;
+
+    const int path = bank_path(ctx);
+    SmallArgs sm;
+    const bool fused = path != 2 &&
+                       plan_small_batch(ctx, a.bank_frames, staging, L.stride, bp->n_streams, flows, bank + L.pub.scratch, &sm) &&
+                       (path == 1 || bp->n_streams <= kBankCameraFusedMaxStreams);
+    if (fused) {
+        if (launch_bank_tick(sm, a, stream)) return ctx_fail(ctx, -EIO, "bank camera tick launch failed");
+        return 0;
+    }
+    // composed: crop (and raw histograms) of all S sensor frames into the staging region -- those of idle streams are
+    // cropped and ignored, like their flows --, the batch plan on (bank frames, staging), then the commit kernel
+    if (launch_ingest(g, d_camera, a.cam.camera_stride, bp->n_streams, staging, L.stride, d_exposure ? hist : nullptr, stream))
+        return ctx_fail(ctx, -EIO, "bank camera ingest launch failed");
+    rc = aof_flow_batch_device(ctx, a.bank_frames, staging, L.stride, bp->n_streams, nullptr, nullptr, flows,
                                bank + L.pub.scratch, L.flow_ws_bytes, stream);
     if (rc) return rc;
     if (launch_bank_commit(a, stream)) return ctx_fail(ctx, -EIO, "bank commit launch failed");

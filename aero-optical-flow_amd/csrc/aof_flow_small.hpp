@@ -187,9 +187,11 @@ __device__ __forceinline__ void run_level(const SearchArgs &a, const FlowTail &t
 // `cur_buf` says which buffer holds the newer frame of the pair, and bit b of `load` says whether buffer
 // b has to be fetched (and its level-1 image and sums made) -- the resident kernel keeps the frame of its
 // previous call in LDS and fetches only the new one.
-template <bool SUBPIXEL>
+// PITCHED (the stream bank's camera tick): src1 is a window of a larger image -- its rows lie `pitch1` bytes apart
+// and may start on any byte; src0 stays a contiguous, 16-byte aligned frame.
+template <bool SUBPIXEL, bool PITCHED = false>
 __device__ __forceinline__ void flow_small_pair(const SmallArgs &a, uint32_t pair, const uint8_t *src0, const uint8_t *src1,
-                                                int cur_buf, uint32_t load, aof_flow *final_copy = nullptr)
+                                                int cur_buf, uint32_t load, aof_flow *final_copy = nullptr, int pitch1 = 0)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_mem[];
     __shared__ uint32_t s_keys[kThreads];
@@ -220,7 +222,12 @@ __device__ __forceinline__ void flow_small_pair(const SmallArgs &a, uint32_t pai
                 v[k] = make_uint4(0, 0, 0, 0);
                 if (it < items) {
                     const int buf = first + (it >= per_frame), c = it - (it >= per_frame) * per_frame;
-                    v[k] = *reinterpret_cast<const uint4 *>((buf ? src1 : src0) + c * 16);
+                    if (PITCHED && buf) {   // one 16-byte load wherever the window starts (as k_ingest fetches its crop)
+                        const int y = c / (w / 16), x = c - y * (w / 16);
+                        __builtin_memcpy(&v[k], src1 + (int64_t)y * pitch1 + x * 16, 16);
+                    } else {
+                        v[k] = *reinterpret_cast<const uint4 *>((buf ? src1 : src0) + c * 16);
+                    }
                 }
             }
 #pragma unroll

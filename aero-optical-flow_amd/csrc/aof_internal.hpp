@@ -269,6 +269,8 @@ int launch_sequence_output(const SequenceArgs &a, void *stream);
 //   state    BankState [S]            what one facade object keeps between calcFlow() calls, 64 bytes per stream
 //   scratch  aof_workspace_layout(p, S) bytes (block records, sub-pixel directions, pixel sums and, on the composed
 //            path, everything the batch plan needs), then aof_flow [S]: the tick's pixel records
+//   staging  (aof_bank_camera_layout only) u8 [S][frame_stride]: the tick's cropped frames on the composed path of
+//            aof_bank_push_camera_device, then u32 [S][10]: their raw exposure histograms
 // every region at a multiple of 256 bytes.
 struct BankState {
     uint32_t has_prev;         // 0 after a reset: the next frame is the stream's first
@@ -278,9 +280,23 @@ struct BankState {
     double gyro_x, gyro_y, gyro_z;  // summed since the last publication (mainloop.cpp:383-405)
     uint32_t messages;         // records published so far: the next MAVLink sequence number is first_seq + messages
     uint32_t frames;           // frames the stream has been given
-    uint32_t pad[2];
+    uint64_t next_exposure_us; // aof_bank_push_camera_device: the stream's exposure gate (mainloop.cpp:273-274); 0 after a
+                               // reset.  The plain push passes it through.
 };
 static_assert(sizeof(BankState) == 64, "one bank state record is 64 bytes");
+// What aof_bank_push_camera_device adds to a tick (include/aof.h, "sensor frames").  camera == nullptr: a plain tick.
+struct BankCamera {
+    const uint8_t *camera;         // [S] sensor frames, stream s at + s * camera_stride; its crop starts `origin` bytes in
+    int64_t camera_stride;
+    int32_t pitch, origin;         // bytes between sensor rows; y0 * pitch + x0 of the crop rectangle
+    int32_t crop_w, crop_h;
+    int32_t mx0, my0, mx1, my1;    // the exposure mask inside the crop (mainloop.cpp:203-206, clipped)
+    const uint32_t *hist;          // composed path: [S][10] raw histograms of the tick's crops (k_ingest)
+    aof_exposure_record *exposure; // [S] or nullptr (no statistics, the gate does not move)
+    uint32_t interval_us;
+    float *derotated;              // [S][2] or nullptr
+    aof_derotate_params derotate;
+};
 struct BankArgs {
     int32_t n_streams;
     int64_t frame_stride, frame_bytes;
@@ -299,12 +315,15 @@ struct BankArgs {
     aof_tick_record *records;      // [S]
     uint8_t *mavlink;              // [S][AOF_SEQ_FRAME_BYTES] or nullptr
     uint8_t *mavlink_len;          // [S]
+    BankCamera cam;                // (last: the plain kernels' argument offsets stay)
 };
 // One launch per tick: a workgroup per stream computes the pair with flow_small_pair, runs the stream's tail and
-// stores the new frame (sm: the small-pair plan of (bank frames, tick frames), flow_small_supported).
+// stores the new frame (sm: the small-pair plan of (bank frames, tick frames), flow_small_supported).  With
+// a.cam.camera the workgroup fetches the crop's rows from the stream's sensor frame itself (a.frames is not read).
 int launch_bank_tick(const SmallArgs &sm, const BankArgs &a, void *stream);
 // Behind aof_flow_batch_device on (bank frames, tick frames): the tail of every stream and the masked copy of the
-// active streams' frames into the bank.
+// active streams' frames into the bank.  With a.cam.camera: a.frames is the staging region, and the exposure gate,
+// the exposure record and the de-rotated pair come from here as well.
 int launch_bank_commit(const BankArgs &a, void *stream);
 int launch_bank_reset(BankState *state, const uint8_t *mask, int32_t n_streams, void *stream);
 // (aof_batch.cpp) the small-pair plan of n pairs, whatever n: true where one workgroup per pair can serve the

@@ -470,6 +470,61 @@ int aof_bank_push_device(aof_ctx *ctx, const aof_bank_params *bp, const uint8_t 
  * -EINVAL: NULL ctx, path outside 0..2. */
 int aof_set_bank_path(aof_ctx *ctx, int path);
 
+/* ---- the stream bank with sensor frames: crop, exposure statistics and de-rotation in the tick ----
+ * The reference's per-frame loop does not begin at calcFlow(): a full sensor frame arrives, is centre-cropped to the
+ * engine's size (mainloop.cpp:295-298,317-319), the crop's central 128x128 region goes into the 10-bin histogram whose
+ * mean sample value drives the auto-exposure loop at 5 Hz (mainloop.cpp:197-220,273-274), and only then comes
+ * calcFlow().  aof_bank_push_camera_device is aof_bank_push_device for S raw sensor frames:
+ *   * crop: the frame a stream is given in a tick is the centre crop of its sensor frame, the rectangle of
+ *     aof_ingest_batch_device (x0 = camera_width/2 - crop_width/2, y0 likewise).  From there on the tick is exactly
+ *     aof_bank_push_device on the cropped frames: d_records, d_mavlink, d_mavlink_len, the stored frames and the
+ *     limiter, gyro and counter fields of the state are byte-identical to that call.  Stream s's sensor frame sits at
+ *     d_camera + s*camera_stride; it needs no alignment, and its crop origin may fall on any byte;
+ *   * exposure gate, per stream (mainloop.cpp:199-201,273-274): the state record holds next_exposure_us, a u64 in the
+ *     record's last 8 bytes, 0 after a reset.  An active frame with 64-bit time t is DUE iff t >= next_exposure_us
+ *     (the untruncated time, as the reference compares it).  A due frame gets the masked histogram of
+ *     aof_ingest_batch_device and its aof_exposure_msv, and sets next_exposure_us = t + exposure_interval_us.  A frame
+ *     that is not due, and an idle stream, get an all-zero record.  A stream's first frame is always due.  With
+ *     d_exposure == NULL no statistics are computed and the gate does not move; aof_bank_push_device passes the field
+ *     through untouched;
+ *   * de-rotation, with cam->derotate and d_derotated (float [S][2]): every active frame that is not a first frame gets
+ *     the two floats aof_derotate_batch_device gives for (this tick's pixel record, d_gyro[s]); first frames and idle
+ *     streams get 0, 0; a NULL d_gyro means zeros.
+ * Small configurations (see above) run the whole tick as ONE kernel that reads the crop's rows straight out of the
+ * sensor frames; every other configuration, and large banks, crop into the bank's staging region (aof_ingest_batch_device's
+ * kernel), run aof_flow_batch_device's plan on (bank frames, staging) and finish with the commit kernel.  Same bytes
+ * either way; aof_set_bank_path applies. */
+typedef struct aof_bank_camera {
+    aof_ingest_params ingest;      /* sensor size -> crop; crop size == the context's frame size */
+    int64_t camera_stride;         /* bytes between the sensor frames of consecutive streams; 0 = camera_width*camera_height */
+    uint32_t exposure_interval_us; /* mainloop.cpp:274: 200 000; 0 = statistics with every frame */
+    uint8_t derotate;              /* 1: d_derotated is written */
+    aof_derotate_params derotate_params;
+} aof_bank_camera;
+
+typedef struct aof_exposure_record {   /* 48 bytes, one per stream and tick */
+    uint32_t hist[AOF_EXPOSURE_BINS];
+    float msv;                          /* aof_exposure_msv(hist), bit for bit */
+    uint32_t due;                       /* 1: this frame passed the stream's exposure gate; 0: hist and msv are zero */
+} aof_exposure_record;
+
+/* The regions of aof_bank_layout at the same offsets, and one region behind them at *staging: u8 [S][frame_stride]
+ * and u32 [S][10], for the composed path (out->total_bytes includes it).  A bank sized by it also serves
+ * aof_bank_push_device.  -EINVAL: what aof_bank_layout refuses, NULL cam / out / staging, a crop size that is not the
+ * frame size of `p`, a crop larger than the sensor frame, a camera_stride below one sensor frame.  Host only. */
+int aof_bank_camera_layout(const aof_params *p, const aof_bank_params *bp, const aof_bank_camera *cam,
+                           struct aof_bank_layout *out, size_t *staging);
+/* d_camera: u8, stream s's sensor frame at + s*camera_stride.  d_exposure: aof_exposure_record [S] or NULL.
+ * d_derotated: float [S][2], required with cam->derotate (else not written).  Everything else as aof_bank_push_device.
+ * -EINVAL: everything aof_bank_camera_layout and aof_bank_push_device refuse, cam->derotate without d_derotated,
+ * d_exposure or d_derotated not 4-byte aligned; -ENOSPC: a bank smaller than aof_bank_camera_layout().total_bytes;
+ * -EIO: the context's sticky fault.  A refused call leaves the bank untouched.  Only enqueues; capturable. */
+int aof_bank_push_camera_device(aof_ctx *ctx, const aof_bank_params *bp, const aof_bank_camera *cam,
+                                const uint8_t *d_camera, const uint64_t *d_time_us, const uint8_t *d_active,
+                                const aof_gyro *d_gyro, void *d_bank, size_t bank_bytes, aof_tick_record *d_records,
+                                aof_exposure_record *d_exposure, float *d_derotated,
+                                uint8_t *d_mavlink, uint8_t *d_mavlink_len, void *stream);
+
 /* ---- measurement ----
  * With profiling on, every launch is bracketed by HIP events on the stream it
  * is launched on; the last AOF_PROFILE_RING launches of each kernel are kept.

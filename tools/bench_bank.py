@@ -6,10 +6,17 @@
                 tick, in a loop on one thread (S <= 64 only);
   C             aof_flow_batch_device on the same S pairs resident in memory: flow without state, the floor of any tick
                 that computes S flows.
+With --camera, the tick on raw sensor frames (320x240 -> PX4 64x64, 640x480 -> 128x128 on two levels):
+  K0 / K1 / K2  aof_bank_push_camera_device (statistics at 200 000 us, gyro, MAVLink frames, de-rotation on) as the library
+                chooses the path, on the one-launch kernel, on the composed path (K1 / K2 from 1 024 streams on: the
+                sweep kBankCameraFusedMaxStreams comes from);
+  Y             what a caller had before: aof_ingest_batch_device into a tick buffer, then aof_bank_push_device;
+  T0            the plain tick on pre-cropped frames.
 Every leg settles for about 0.2 s of untimed ticks, then times at least --ticks ticks and at least --seconds seconds
 with the host clock around ticks that end in a synchronise.  The whole sweep runs --repeats times: the difference
 between the repeats is the run-to-run spread a difference between legs has to beat.
-    python tools/bench_bank.py [--streams 1,16,...] [--configs px4-64,opencv-128] > profiles/bank_tick_sweep.txt"""
+    python tools/bench_bank.py [--streams 1,16,...] [--configs px4-64,opencv-128] > profiles/bank_tick_sweep.txt
+    python tools/bench_bank.py --camera > profiles/bank_camera_tick_sweep.txt"""
 import argparse
 import ctypes as C
 import importlib
@@ -104,6 +111,147 @@ def leg_tick(p, S, path, inp, dev, a):
     return out
 
 
+SENSOR = {"px4-64": (320, 240), "opencv-128": (640, 480)}
+DEROTATE = (4.5, 0.05)
+
+
+def sensor_frames(p, S, inp, dev, cam_w, cam_h):
+    """RING ticks of S sensor frames on the device: inp.frames[k] at the crop origin of noise."""
+    x0, y0 = cam_w // 2 - p.width // 2, cam_h // 2 - p.height // 2
+    out = []
+    for k in range(RING):
+        cam = torch.randint(0, 256, (S, cam_h, cam_w), dtype=torch.uint8, device=dev)
+        cam[:, y0:y0 + p.height, x0:x0 + p.width] = inp.frames[k]
+        out.append(cam)
+    return out
+
+
+def leg_camera(p, S, path, inp, cams, dev, a, cam_w, cam_h):
+    eng = aof.FlowEngine(p, 0)
+    eng.set_bank_path(path)
+    bp = aof.bank_params(S, FX, FY, 15, 5_000_000, 1, 100, 0)
+    cam = aof.bank_camera_params(cam_w, cam_h, p.width, p.height, 0, 200_000, DEROTATE, FX, FY)
+    bank = eng.bank_create(bp, dev, camera=cam)
+    recs = torch.empty((S, 48), dtype=torch.uint8, device=dev)
+    expo = torch.empty((S, 48), dtype=torch.uint8, device=dev)
+    derot = torch.empty((S, 2), dtype=torch.float32, device=dev)
+    wire = torch.empty((S, 56), dtype=torch.uint8, device=dev)
+    lens = torch.empty(S, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    fn, ctx, bpp, cp = aof.lib.aof_bank_push_camera_device, eng._ctx, C.byref(bp), C.byref(cam)
+    # the clock runs on at 13 333 us per tick across the ring's wraps, so the gate opens every 15 ticks, as on a camera
+    times = torch.zeros(S, dtype=torch.int64, device=dev)
+    rest = (times.data_ptr(), None, inp.gyro.data_ptr(), bank.buffer.data_ptr(), bank.buffer.numel(), recs.data_ptr(), expo.data_ptr(),
+            derot.data_ptr(), wire.data_ptr(), lens.data_ptr(), stream)
+    ptrs = [c.data_ptr() for c in cams]
+
+    def step(i):
+        times.add_(13333)
+        rc = fn(ctx, bpp, cp, ptrs[i % RING], *rest)
+        if rc:
+            raise aof.AofError(rc, aof.lib.aof_last_error(ctx).decode())
+    out = timed(step, torch.cuda.synchronize, a.ticks, a.seconds, a.settle)
+    r = aof.ticks_view(recs)
+    assert (r["quality"] >= aof.TICK_HELD).all() and (r["frame"] > a.ticks).all(), "the timed ticks were real ticks"
+    eng.close()
+    return out
+
+
+def leg_two_calls(p, S, inp, cams, dev, a, cam_w, cam_h):
+    eng = aof.FlowEngine(p, 0)
+    bp = aof.bank_params(S, FX, FY, 15, 5_000_000, 1, 100, 0)
+    bank = eng.bank_create(bp, dev)
+    frames = torch.empty((S, p.height, p.width), dtype=torch.uint8, device=dev)
+    hist = torch.empty((S, 10), dtype=torch.int32, device=dev)
+    recs = torch.empty((S, 48), dtype=torch.uint8, device=dev)
+    wire = torch.empty((S, 56), dtype=torch.uint8, device=dev)
+    lens = torch.empty(S, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    ingest, push, ctx, bpp = aof.lib.aof_ingest_batch_device, aof.lib.aof_bank_push_device, eng._ctx, C.byref(bp)
+    ip = aof.IngestParams(cam_w, cam_h, p.width, p.height)
+    ipp = C.byref(ip)
+    times = torch.zeros(S, dtype=torch.int64, device=dev)
+    ptrs = [c.data_ptr() for c in cams]
+    ing = (cam_w * cam_h, S, frames.data_ptr(), p.width * p.height, hist.data_ptr(), stream)
+    rest = (frames.data_ptr(), times.data_ptr(), None, inp.gyro.data_ptr(), bank.buffer.data_ptr(), bank.buffer.numel(), recs.data_ptr(),
+            wire.data_ptr(), lens.data_ptr(), stream)
+
+    def step(i):
+        times.add_(13333)
+        rc = ingest(ipp, ptrs[i % RING], *ing) or push(ctx, bpp, *rest)
+        if rc:
+            raise aof.AofError(rc, aof.lib.aof_last_error(ctx).decode())
+    out = timed(step, torch.cuda.synchronize, a.ticks, a.seconds, a.settle)
+    eng.close()
+    return out
+
+
+def leg_plain(p, S, inp, dev, a):
+    """leg_tick with the camera legs' running clock (one more small kernel per tick, like theirs)."""
+    eng = aof.FlowEngine(p, 0)
+    bp = aof.bank_params(S, FX, FY, 15, 5_000_000, 1, 100, 0)
+    bank = eng.bank_create(bp, dev)
+    recs = torch.empty((S, 48), dtype=torch.uint8, device=dev)
+    wire = torch.empty((S, 56), dtype=torch.uint8, device=dev)
+    lens = torch.empty(S, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    fn, ctx, bpp = aof.lib.aof_bank_push_device, eng._ctx, C.byref(bp)
+    times = torch.zeros(S, dtype=torch.int64, device=dev)
+    ptrs = [f.data_ptr() for f in inp.frames[:RING]]
+    rest = (times.data_ptr(), None, inp.gyro.data_ptr(), bank.buffer.data_ptr(), bank.buffer.numel(), recs.data_ptr(), wire.data_ptr(),
+            lens.data_ptr(), stream)
+
+    def step(i):
+        times.add_(13333)
+        rc = fn(ctx, bpp, ptrs[i % RING], *rest)
+        if rc:
+            raise aof.AofError(rc, aof.lib.aof_last_error(ctx).decode())
+    out = timed(step, torch.cuda.synchronize, a.ticks, a.seconds, a.settle)
+    eng.close()
+    return out
+
+
+def camera_sweep(a, dev):
+    print("# legs: K0/K1/K2 camera tick on path 0/1/2 (statistics at 200 000 us, gyro, MAVLink frames, de-rotation), "
+          "Y = aof_ingest_batch_device + aof_bank_push_device, T0 = plain tick on pre-cropped frames; every leg advances its clock "
+          "on the device per tick (one small kernel more than a caller with real time stamps)")
+    print("# us = microseconds per tick (host clock, ticks ending in a synchronise)")
+    sizes = [int(s) for s in a.streams.split(",")]
+    results = {}
+    for rep in range(a.repeats):
+        for cfg in a.configs.split(","):
+            p = params_of(cfg)
+            cw, ch = SENSOR[cfg]
+            for S in sizes:
+                inp = Inputs(p, S, dev)
+                cams = sensor_frames(p, S, inp, dev, cw, ch)
+                legs = [("K0", lambda: leg_camera(p, S, 0, inp, cams, dev, a, cw, ch)), ("Y", lambda: leg_two_calls(p, S, inp, cams, dev, a, cw, ch)),
+                        ("T0", lambda: leg_plain(p, S, inp, dev, a))]
+                if S >= 1024:
+                    legs += [("K1", lambda: leg_camera(p, S, 1, inp, cams, dev, a, cw, ch)), ("K2", lambda: leg_camera(p, S, 2, inp, cams, dev, a, cw, ch))]
+                for name, fn in legs:
+                    sec, n = fn()
+                    results.setdefault((cfg, S, name), []).append(sec)
+                    print(f"rep {rep} {cfg:11s} {cw}x{ch} S={S:6d} {name:2s} {sec * 1e6:10.2f} us  {1 / sec:12.0f} ticks/s  ({n} ticks)", flush=True)
+                del inp, cams
+                torch.cuda.empty_cache()
+    print("# ---- summary (mean of the repeats; spread = |difference of the repeats| / mean) ----")
+    for cfg in a.configs.split(","):
+        p = params_of(cfg)
+        print(f"# {cfg}: frame bytes per stream and tick: camera tick on the one-launch path {3 * p.width * p.height}, two calls {5 * p.width * p.height}")
+        for S in sizes:
+            m = {n: float(np.mean(results[(cfg, S, n)])) for n in ("K0", "Y", "T0", "K1", "K2") if (cfg, S, n) in results}
+            sp = {n: (abs(results[(cfg, S, n)][0] - results[(cfg, S, n)][-1]) / m[n]) for n in m}
+            gain = (m["Y"] - m["K0"]) / m["Y"]
+            line = (f"{cfg:11s} S={S:6d}  K0 {m['K0'] * 1e6:9.2f} us (+-{sp['K0'] * 100:4.1f} %)  Y {m['Y'] * 1e6:9.2f} (+-{sp['Y'] * 100:4.1f} %)  "
+                    f"T0 {m['T0'] * 1e6:9.2f} (+-{sp['T0'] * 100:4.1f} %)  K0 below Y by {gain * 100:5.1f} % "
+                    f"({'more' if gain > sp['K0'] + sp['Y'] else 'NOT more'} than the legs' spread)  K0/T0 {m['K0'] / m['T0']:5.3f}")
+            if "K1" in m:
+                line += (f"  K1 {m['K1'] * 1e6:9.2f} (+-{sp['K1'] * 100:4.1f} %)  K2 {m['K2'] * 1e6:9.2f} (+-{sp['K2'] * 100:4.1f} %)  "
+                         f"faster path {'K1' if m['K1'] <= m['K2'] else 'K2'}")
+            print(line)
+
+
 def leg_contexts(p, S, inp, a):
     engs = [aof.FlowEngine(p, 0) for _ in range(S)]
     flow = np.zeros(1, aof.FLOW_DTYPE)
@@ -169,7 +317,10 @@ def main():
     ap.add_argument("--contexts-max", type=int, default=64, help="largest S of the B leg")
     ap.add_argument("--legs", default="T0,T1,T2,C,B", help="legs to run (a kernel trace wants one at a time)")
     ap.add_argument("--no-marker", action="store_true")
+    ap.add_argument("--camera", action="store_true", help="the sweep of the tick on raw sensor frames (legs K0, K1, K2, Y, T0)")
     a = ap.parse_args()
+    if a.camera and a.streams == ap.get_default("streams"):
+        a.streams = "1,64,1024,1536,2048,4096"
     if not torch.cuda.is_available():
         raise SystemExit("bench_bank.py measures on a GPU; none is visible")
     dev = torch.device("cuda:0")
@@ -177,6 +328,8 @@ def main():
     print(f"# device: {torch.cuda.get_device_name(0)}")
     if not a.no_marker:
         print(f"# class marker: exhaustive C2 K2 (1 024 VGA pairs) {class_marker(dev):.4f} ms")
+    if a.camera:
+        return camera_sweep(a, dev)
     print("# legs: T0/T1/T2 bank tick on path 0/1/2 (MAVLink frames on, all streams active), B = S contexts x aof_stream_push_host, "
           "C = aof_flow_batch_device on S pairs")
     print("# us = microseconds per tick (host clock, ticks ending in a synchronise); Mframes/s = stream-frames per second")
