@@ -99,6 +99,12 @@ class BankCamera(C.Structure):
                 ("derotate", C.c_uint8), ("derotate_params", DerotateParams)]
 
 
+class BankBurst(C.Structure):
+    """``aof_bank_burst`` (include/aof.h)."""
+    _fields_ = [("n_rounds", C.c_int32), ("round_stride", C.c_int64)]
+
+
+BANK_BURST_MAX = 16
 TICK_HELD, TICK_IDLE = -1, -2
 TICK_DTYPE = np.dtype([("quality", "<i4"), ("dt_us", "<i4"), ("flow_x", "<f4"), ("flow_y", "<f4"),
                        ("gyro_x", "<f4"), ("gyro_y", "<f4"), ("gyro_z", "<f4"), ("frame", "<u4"), ("pixel", FLOW_DTYPE)])
@@ -194,6 +200,9 @@ def _load():
         "aof_bank_camera_layout": (C.c_int, [P(Params), P(BankParams), P(BankCamera), P(BankLayout), P(C.c_size_t)]),
         "aof_bank_push_camera_device": (C.c_int, [VP, P(BankParams), P(BankCamera), VP, VP, VP, VP, VP, C.c_size_t, VP, VP, VP,
                                                   VP, VP, VP]),
+        "aof_bank_push_burst_device": (C.c_int, [VP, P(BankParams), P(BankBurst), VP, VP, VP, VP, VP, C.c_size_t, VP, VP, VP, VP]),
+        "aof_bank_push_camera_burst_device": (C.c_int, [VP, P(BankParams), P(BankCamera), P(BankBurst), VP, VP, VP, VP, VP,
+                                                        C.c_size_t, VP, VP, VP, VP, VP, VP]),
         "aof_derotate_batch_device": (C.c_int, [P(DerotateParams), VP, VP, I64, VP, VP]),
         "aof_exposure_msv": (C.c_float, [VP]),
         "aof_exposure_bin": (C.c_int, [C.c_int]),
@@ -361,6 +370,13 @@ def bank_camera_params(cam_w, cam_h, crop_w, crop_h, camera_stride=0, exposure_i
     if derotate is not None:
         cam.derotate_params = DerotateParams(focal_x, focal_y, derotate[0], derotate[1])
     return cam
+
+
+def bank_burst_params(n_rounds, round_stride=0) -> BankBurst:
+    """``aof_bank_burst``: K frame rounds per call; round_stride 0: the rounds lie back to back."""
+    b = BankBurst()
+    b.n_rounds, b.round_stride = int(n_rounds), int(round_stride)
+    return b
 
 
 def bank_camera_layout(p: Params, bp: BankParams, cam: BankCamera):
@@ -681,6 +697,70 @@ class FlowEngine:
         self._check(lib.aof_bank_push_camera_device(
             self._ctx, C.byref(bank.bp), C.byref(cam), camera.data_ptr(), times.data_ptr(),
             active.data_ptr() if active is not None else None, gyro.data_ptr() if gyro is not None else None,
+            buf.data_ptr(), buf.numel(), records.data_ptr(), exposure.data_ptr() if exposure is not None else None,
+            derotated.data_ptr() if derotated is not None else None, out_frames.data_ptr() if mavlink else None,
+            out_lengths.data_ptr() if mavlink else None, torch.cuda.current_stream(dev).cuda_stream))
+        return dict(records=records, exposure=exposure, derotated=derotated, frames=out_frames if mavlink else None,
+                    lengths=out_lengths if mavlink else None)
+
+    def bank_push_burst(self, bank: "Bank", n_rounds, frames, times, count=None, gyro=None, mavlink=False, records=None,
+                        out_frames=None, out_lengths=None, round_stride=0):
+        """aof_bank_push_burst_device, K = n_rounds frame rounds in one call: frames uint8 CUDA tensor, stream s's frame
+        of round k at k * round_stride + s * frame_stride bytes (round_stride 0: the rounds back to back); times int64
+        [K, S]; count uint8 [S] (stream s has frames in rounds 0..count[s]-1) or None (all K); gyro float32 [K, S, 4] or
+        None.  Returns the record tensor [K, S, 48] (ticks_view() of round k: records[k]), and with mavlink=True
+        (records, frames [K, S, 56], lengths [K, S])."""
+        import torch
+        K, S, buf = int(n_rounds), bank.n_streams, bank.buffer
+        dev = buf.device
+        assert frames.dtype == torch.uint8 and frames.is_contiguous()
+        assert times.dtype == torch.int64 and times.numel() == K * S and times.is_contiguous()
+        assert count is None or (count.dtype == torch.uint8 and count.numel() == S)
+        assert gyro is None or gyro.numel() == K * S * 4
+        if records is None:
+            records = torch.empty((K, S, 48), dtype=torch.uint8, device=dev)
+        if mavlink:
+            if out_frames is None:
+                out_frames = torch.zeros((K, S, SEQ_FRAME_BYTES), dtype=torch.uint8, device=dev)
+            if out_lengths is None:
+                out_lengths = torch.zeros((K, S), dtype=torch.uint8, device=dev)
+        burst = bank_burst_params(K, round_stride)
+        self._check(lib.aof_bank_push_burst_device(
+            self._ctx, C.byref(bank.bp), C.byref(burst), frames.data_ptr(), times.data_ptr(),
+            count.data_ptr() if count is not None else None, gyro.data_ptr() if gyro is not None else None, buf.data_ptr(),
+            buf.numel(), records.data_ptr(), out_frames.data_ptr() if mavlink else None,
+            out_lengths.data_ptr() if mavlink else None, torch.cuda.current_stream(dev).cuda_stream))
+        return (records, out_frames, out_lengths) if mavlink else records
+
+    def bank_push_camera_burst(self, bank: "Bank", n_rounds, camera, times, count=None, gyro=None, mavlink=False,
+                               records=None, exposure=None, derotated=None, out_frames=None, out_lengths=None,
+                               want_exposure=True, round_stride=0):
+        """aof_bank_push_camera_burst_device, K = n_rounds rounds of raw sensor frames in one call: camera uint8 CUDA
+        tensor, stream s's sensor frame of round k at k * round_stride + s * camera_stride bytes; the rest as
+        bank_push_burst and bank_push_camera, every output with a leading [K].  Returns a dict of the output tensors:
+        records, exposure, derotated, frames, lengths (None where not written)."""
+        import torch
+        K, S, buf, cam = int(n_rounds), bank.n_streams, bank.buffer, bank.camera
+        assert cam is not None, "bank_create(..., camera=...) makes a bank for sensor frames"
+        dev = buf.device
+        assert camera.dtype == torch.uint8 and times.dtype == torch.int64 and times.numel() == K * S and times.is_contiguous()
+        assert count is None or (count.dtype == torch.uint8 and count.numel() == S)
+        assert gyro is None or gyro.numel() == K * S * 4
+        if records is None:
+            records = torch.empty((K, S, 48), dtype=torch.uint8, device=dev)
+        if exposure is None and want_exposure:
+            exposure = torch.empty((K, S, 48), dtype=torch.uint8, device=dev)
+        if derotated is None and cam.derotate:
+            derotated = torch.empty((K, S, 2), dtype=torch.float32, device=dev)
+        if mavlink:
+            if out_frames is None:
+                out_frames = torch.zeros((K, S, SEQ_FRAME_BYTES), dtype=torch.uint8, device=dev)
+            if out_lengths is None:
+                out_lengths = torch.zeros((K, S), dtype=torch.uint8, device=dev)
+        burst = bank_burst_params(K, round_stride)
+        self._check(lib.aof_bank_push_camera_burst_device(
+            self._ctx, C.byref(bank.bp), C.byref(cam), C.byref(burst), camera.data_ptr(), times.data_ptr(),
+            count.data_ptr() if count is not None else None, gyro.data_ptr() if gyro is not None else None,
             buf.data_ptr(), buf.numel(), records.data_ptr(), exposure.data_ptr() if exposure is not None else None,
             derotated.data_ptr() if derotated is not None else None, out_frames.data_ptr() if mavlink else None,
             out_lengths.data_ptr() if mavlink else None, torch.cuda.current_stream(dev).cuda_stream))

@@ -31,6 +31,22 @@ constexpr int32_t kBankFusedMaxStreams = 1536;
 // constant at 2 048, which therefore stays: the largest size at which the library's own choice was measured and tested.
 constexpr int32_t kBankCameraFusedMaxStreams = 2048;
 
+// The same two for a burst (aof_bank_push_burst_device / aof_bank_push_camera_burst_device).  A burst workgroup lives K
+// times as long as a tick workgroup and, with the loop over the rounds, needs 128 VGPRs where the tick needs 77: four
+// workgroups per compute unit instead of six, so the one-launch burst falls off at 1 536 streams of 64x64, where the
+// tick still holds.  Measured (tools/bench_bank.py --burst 2,5,16, legs B1 / B2, profiles/bank_burst_sweep.txt; us per
+// burst of K = 5 rounds, one-launch kernel / composed path): PX4 64x64 1 024 streams 70.4 / 87.9, 1 536: 116.8 / 92.4,
+// 2 048: 135.7 / 98.6; 128x128 on two levels 1 024: 191.7 / 245.2, 1 536: 240.8 / 276.0, 2 048: 325.3 / 304.8 (K = 2 and
+// K = 16 cross at the same sizes).  1 024 is the largest swept size at which the one-launch burst wins in both
+// configurations; the two-level configuration gives up 13 % at 1 536 streams for it.
+constexpr int32_t kBankBurstFusedMaxStreams = 1024;
+// Camera form (legs B1 / B2 of the same file, K = 5): 320x240 -> PX4 64x64 1 024 streams 78.1 / 122.4, 1 536: 131.2 /
+// 136.1, 2 048: 148.8 / 145.4, 4 096: 286.8 / 211.2; 640x480 -> 128x128 on two levels 1 536: 263.8 / 343.1, 2 048: 355.9 /
+// 390.1, 4 096: 685.5 / 633.9.  (K = 2: 64x64 1 536: 53.4 / 54.6, 2 048: 62.0 / 58.1; K = 16: 1 536: 396.2 / 436.7, 2 048:
+// 503.6 / 471.5.)  The small frames cross between 1 536 and 2 048 streams at every K; the two-level configuration
+// gives up 9 % at 2 048 for it.
+constexpr int32_t kBankCameraBurstFusedMaxStreams = 1536;
+
 struct Layout {
     struct aof_bank_layout pub;
     size_t flow_ws_bytes, flows;   // inside the bank: the engine's workspace is at pub.scratch, the pixel records at `flows`
@@ -143,6 +159,59 @@ BankArgs bank_args(const aof_bank_params *bp, const Layout &L, uint8_t *bank, co
     return a;
 }
 
+// What the camera forms add to the tick's arguments: the crop rectangle, the exposure mask, the outputs.
+void camera_args(BankArgs *args, const aof_bank_camera *cam, const uint8_t *d_camera, const uint32_t *hist,
+                 aof_exposure_record *d_exposure, float *d_derotated)
+{
+    BankArgs &a = *args;
+    const aof_ingest_params &g = cam->ingest;
+    const int x0 = g.camera_width / 2 - g.crop_width / 2, y0 = g.camera_height / 2 - g.crop_height / 2;   // mainloop.cpp:295-296
+    a.cam.camera = d_camera;
+    a.cam.camera_stride = cam->camera_stride ? cam->camera_stride : (int64_t)g.camera_width * g.camera_height;
+    a.cam.pitch = g.camera_width;
+    a.cam.origin = y0 * g.camera_width + x0;
+    a.cam.crop_w = g.crop_width; a.cam.crop_h = g.crop_height;
+    const int mx0 = g.crop_width / 2 - AOF_EXPOSURE_MASK_SIZE / 2, my0 = g.crop_height / 2 - AOF_EXPOSURE_MASK_SIZE / 2;   // :203-206
+    a.cam.mx0 = mx0 < 0 ? 0 : mx0; a.cam.my0 = my0 < 0 ? 0 : my0;
+    a.cam.mx1 = mx0 + AOF_EXPOSURE_MASK_SIZE > g.crop_width ? g.crop_width : mx0 + AOF_EXPOSURE_MASK_SIZE;
+    a.cam.my1 = my0 + AOF_EXPOSURE_MASK_SIZE > g.crop_height ? g.crop_height : my0 + AOF_EXPOSURE_MASK_SIZE;
+    a.cam.hist = hist;
+    a.cam.exposure = d_exposure;
+    a.cam.interval_us = cam->exposure_interval_us;
+    a.cam.derotated = cam->derotate ? d_derotated : nullptr;
+    a.cam.derotate = cam->derotate_params;
+}
+
+// What a burst adds to the checks of a tick.  round: bytes of one round of the frame buffer.
+int check_burst(aof_ctx *ctx, const aof_bank_burst *burst, int64_t round, bool pitched, int64_t *round_stride)
+{
+    if (!burst) return ctx_fail(ctx, -EINVAL, "null bank burst parameters");
+    if (burst->n_rounds < 1 || burst->n_rounds > AOF_BANK_BURST_MAX)
+        return ctx_fail(ctx, -EINVAL, "bank burst: n_rounds outside 1..AOF_BANK_BURST_MAX");
+    const int64_t stride = burst->round_stride ? burst->round_stride : round;
+    if (stride < round || (!pitched && stride % 16))
+        return ctx_fail(ctx, -EINVAL, "bank burst: round_stride must hold one round (pre-cropped frames: and be a multiple of 16)");
+    *round_stride = stride;
+    return 0;
+}
+
+// Round k of a burst as a tick of its own (the composed path): every per-round pointer moved k rounds on.
+BankArgs round_args(const BankArgs &a, int k, const uint8_t *frames)
+{
+    BankArgs r = a;
+    const size_t o = (size_t)k * (size_t)a.n_streams;
+    r.frames = frames;
+    r.time_us = a.time_us + o;
+    r.active = nullptr;
+    if (a.gyro) r.gyro = a.gyro + o;
+    r.records = a.records + o;
+    if (a.mavlink) r.mavlink = a.mavlink + o * AOF_SEQ_FRAME_BYTES;
+    if (a.mavlink_len) r.mavlink_len = a.mavlink_len + o;
+    if (a.cam.exposure) r.cam.exposure = a.cam.exposure + o;
+    if (a.cam.derotated) r.cam.derotated = a.cam.derotated + 2 * o;
+    return r;
+}
+
 }  // namespace
 
 extern "C" {
@@ -244,21 +313,7 @@ int aof_bank_push_camera_device(aof_ctx *ctx, const aof_bank_params *bp, const a
     BankArgs a = bank_args(bp, L, bank, staging, d_time_us, d_active, d_gyro, d_records, d_mavlink, d_mavlink_len);
     aof_flow *flows = reinterpret_cast<aof_flow *>(bank + L.flows);
     const aof_ingest_params &g = cam->ingest;
-    const int x0 = g.camera_width / 2 - g.crop_width / 2, y0 = g.camera_height / 2 - g.crop_height / 2;   // mainloop.cpp:295-296
-    a.cam.camera = d_camera;
-    a.cam.camera_stride = cam->camera_stride ? cam->camera_stride : (int64_t)g.camera_width * g.camera_height;
-    a.cam.pitch = g.camera_width;
-    a.cam.origin = y0 * g.camera_width + x0;
-    a.cam.crop_w = g.crop_width; a.cam.crop_h = g.crop_height;
-    const int mx0 = g.crop_width / 2 - AOF_EXPOSURE_MASK_SIZE / 2, my0 = g.crop_height / 2 - AOF_EXPOSURE_MASK_SIZE / 2;   // :203-206
-    a.cam.mx0 = mx0 < 0 ? 0 : mx0; a.cam.my0 = my0 < 0 ? 0 : my0;
-    a.cam.mx1 = mx0 + AOF_EXPOSURE_MASK_SIZE > g.crop_width ? g.crop_width : mx0 + AOF_EXPOSURE_MASK_SIZE;
-    a.cam.my1 = my0 + AOF_EXPOSURE_MASK_SIZE > g.crop_height ? g.crop_height : my0 + AOF_EXPOSURE_MASK_SIZE;
-    a.cam.hist = hist;
-    a.cam.exposure = d_exposure;
-    a.cam.interval_us = cam->exposure_interval_us;
-    a.cam.derotated = cam->derotate ? d_derotated : nullptr;
-    a.cam.derotate = cam->derotate_params;
+    camera_args(&a, cam, d_camera, hist, d_exposure, d_derotated);
 
     const int path = bank_path(ctx);
     SmallArgs sm;
@@ -277,6 +332,97 @@ int aof_bank_push_camera_device(aof_ctx *ctx, const aof_bank_params *bp, const a
                                bank + L.pub.scratch, L.flow_ws_bytes, stream);
     if (rc) return rc;
     if (launch_bank_commit(a, stream)) return ctx_fail(ctx, -EIO, "bank commit launch failed");
+    return 0;
+}
+
+int aof_bank_push_burst_device(aof_ctx *ctx, const aof_bank_params *bp, const aof_bank_burst *burst, const uint8_t *d_frames,
+                               const uint64_t *d_time_us, const uint8_t *d_count, const aof_gyro *d_gyro, void *d_bank,
+                               size_t bank_bytes, aof_tick_record *d_records, uint8_t *d_mavlink, uint8_t *d_mavlink_len,
+                               void *stream)
+{
+    Layout L;
+    int rc = check_bank(ctx, bp, d_bank, bank_bytes, &L);
+    if (rc) return rc;
+    int64_t round_stride = 0;
+    if ((rc = check_burst(ctx, burst, (int64_t)bp->n_streams * L.stride, false, &round_stride))) return rc;
+    if ((rc = check_tick(ctx, d_frames, d_time_us, d_gyro, d_records, d_mavlink, d_mavlink_len))) return rc;
+    if ((rc = precheck(ctx))) return rc;
+
+    uint8_t *bank = static_cast<uint8_t *>(d_bank);
+    const BankArgs a = bank_args(bp, L, bank, d_frames, d_time_us, nullptr, d_gyro, d_records, d_mavlink, d_mavlink_len);
+    aof_flow *flows = reinterpret_cast<aof_flow *>(bank + L.flows);
+    const BankBurst b = {burst->n_rounds, round_stride, d_count};
+
+    const int path = bank_path(ctx);
+    SmallArgs sm;
+    const bool fused = path != 2 &&
+                       plan_small_batch(ctx, a.bank_frames, d_frames, L.stride, bp->n_streams, flows, bank + L.pub.scratch, &sm) &&
+                       (path == 1 || bp->n_streams <= kBankBurstFusedMaxStreams);
+    if (fused) {
+        if (launch_bank_burst(sm, a, b, stream)) return ctx_fail(ctx, -EIO, "bank burst launch failed");
+        return 0;
+    }
+    // composed: K rounds of the single tick's launches, in order on the one stream
+    for (int k = 0; k < b.n_rounds; k++) {
+        const uint8_t *frames = d_frames + (int64_t)k * round_stride;
+        rc = aof_flow_batch_device(ctx, a.bank_frames, frames, L.stride, bp->n_streams, nullptr, nullptr, flows,
+                                   bank + L.pub.scratch, L.flow_ws_bytes, stream);
+        if (rc) return rc;
+        if (launch_bank_commit(round_args(a, k, frames), stream, d_count, d_count ? k : 0))
+            return ctx_fail(ctx, -EIO, "bank commit launch failed");
+    }
+    return 0;
+}
+
+int aof_bank_push_camera_burst_device(aof_ctx *ctx, const aof_bank_params *bp, const aof_bank_camera *cam,
+                                      const aof_bank_burst *burst, const uint8_t *d_camera, const uint64_t *d_time_us,
+                                      const uint8_t *d_count, const aof_gyro *d_gyro, void *d_bank, size_t bank_bytes,
+                                      aof_tick_record *d_records, aof_exposure_record *d_exposure, float *d_derotated,
+                                      uint8_t *d_mavlink, uint8_t *d_mavlink_len, void *stream)
+{
+    Layout L;
+    int rc = check_bank(ctx, bp, d_bank, bank_bytes, &L, cam, true);
+    if (rc) return rc;
+    const aof_ingest_params &g = cam->ingest;
+    const int64_t camera_stride = cam->camera_stride ? cam->camera_stride : (int64_t)g.camera_width * g.camera_height;
+    int64_t round_stride = 0;
+    if ((rc = check_burst(ctx, burst, (int64_t)bp->n_streams * camera_stride, true, &round_stride))) return rc;
+    if ((rc = check_tick(ctx, d_camera, d_time_us, d_gyro, d_records, d_mavlink, d_mavlink_len))) return rc;
+    if (cam->derotate && !d_derotated) return ctx_fail(ctx, -EINVAL, "bank camera: derotate needs d_derotated");
+    if (reinterpret_cast<uintptr_t>(d_exposure) % 4 || reinterpret_cast<uintptr_t>(d_derotated) % 4)
+        return ctx_fail(ctx, -EINVAL, "bank camera: exposure records and de-rotated pairs must be 4-byte aligned");
+    if ((rc = precheck(ctx))) return rc;
+
+    uint8_t *bank = static_cast<uint8_t *>(d_bank);
+    uint8_t *staging = bank + L.staging;
+    uint32_t *hist = reinterpret_cast<uint32_t *>(bank + L.staging_hist);
+    BankArgs a = bank_args(bp, L, bank, staging, d_time_us, nullptr, d_gyro, d_records, d_mavlink, d_mavlink_len);
+    aof_flow *flows = reinterpret_cast<aof_flow *>(bank + L.flows);
+    camera_args(&a, cam, d_camera, hist, d_exposure, d_derotated);
+    const BankBurst b = {burst->n_rounds, round_stride, d_count};
+
+    const int path = bank_path(ctx);
+    SmallArgs sm;
+    const bool fused = path != 2 &&
+                       plan_small_batch(ctx, a.bank_frames, staging, L.stride, bp->n_streams, flows, bank + L.pub.scratch, &sm) &&
+                       (path == 1 || bp->n_streams <= kBankCameraBurstFusedMaxStreams);
+    if (fused) {
+        if (launch_bank_burst(sm, a, b, stream)) return ctx_fail(ctx, -EIO, "bank camera burst launch failed");
+        return 0;
+    }
+    // composed: per round the ingest launch into the staging region, the batch plan on (bank frames, staging) and the
+    // commit kernel, in order on the one stream
+    for (int k = 0; k < b.n_rounds; k++) {
+        const uint8_t *camera = d_camera + (int64_t)k * round_stride;
+        if (launch_ingest(g, camera, a.cam.camera_stride, bp->n_streams, staging, L.stride, d_exposure ? hist : nullptr, stream))
+            return ctx_fail(ctx, -EIO, "bank camera ingest launch failed");
+        rc = aof_flow_batch_device(ctx, a.bank_frames, staging, L.stride, bp->n_streams, nullptr, nullptr, flows,
+                                   bank + L.pub.scratch, L.flow_ws_bytes, stream);
+        if (rc) return rc;
+        BankArgs r = round_args(a, k, staging);
+        r.cam.camera = camera;
+        if (launch_bank_commit(r, stream, d_count, d_count ? k : 0)) return ctx_fail(ctx, -EIO, "bank commit launch failed");
+    }
     return 0;
 }
 

@@ -1,0 +1,226 @@
+// What one stream of the bank does with one frame, shared by the tick kernels (k_bank.hip) and the burst kernel
+// (k_bank_burst.hip): the idle record, the exposure gate and the MSV, the tail (rate limiter, angles, gyro sums,
+// OPTICAL_FLOW_RAD frame), the masked histogram and the frame copies.  One function each, as aof_flow_small.hpp has one
+// function for the pair: a record cannot depend on the entry point that produced it.
+// The tail is the facade's limitRate() / integrate() (facade/src/optical_flow.cpp) and mainloop.cpp:322-373 on ONE
+// stream's state: every float operation is the host's, in the host's order.
+#pragma once
+
+#include "aof_derotate.hpp"
+#include "aof_flow_small.hpp"
+#include "aof_mavlink.hpp"
+#include "aof_math.h"
+
+namespace aof {
+
+namespace {
+
+template <bool CAMERA>
+__device__ __forceinline__ void bank_idle(const BankArgs &a, size_t o)
+{
+    aof_tick_record rec = {};
+    rec.quality = AOF_TICK_IDLE;
+    a.records[o] = rec;
+    if (a.mavlink_len) a.mavlink_len[o] = 0;
+    if constexpr (CAMERA) {
+        if (a.cam.exposure) a.cam.exposure[o] = aof_exposure_record{};
+        if (a.cam.derotated) { a.cam.derotated[2 * o] = 0.0f; a.cam.derotated[2 * o + 1] = 0.0f; }
+    }
+}
+
+// Is a frame of 64-bit time t due for exposure statistics (mainloop.cpp:199-201: the untruncated time)?
+__device__ __forceinline__ bool exposure_due(const BankArgs &a, const BankState &st, uint64_t t)
+{
+    return a.cam.exposure != nullptr && t >= st.next_exposure_us;
+}
+
+// mainloop.cpp:216-220 as aof_exposure_msv computes it: the same float operations in the same order, none fused.
+__device__ __forceinline__ float exposure_msv(const uint32_t *hist)
+{
+#pragma clang fp contract(off)
+    float msv = 0.0f;
+    for (int i = 0; i < AOF_EXPOSURE_BINS; i++) msv += (i + 1) * (float)hist[i] / 16384.0f;
+    return msv;
+}
+
+// One lane: a stream has been given a frame; `st` is the stream's state record, `f` the pixel record of (older frame,
+// new frame), `first` says that there was no older frame.  `o` indexes the frame's time, gyro sample and every output:
+// the stream's number in a tick, round * S + stream in a burst.  payload: kMavlinkPayloadBytes of LDS for the packer.
+// CAMERA: `hist` holds the frame's ten raw bin totals if the frame is due (exposure_due; LDS or global memory).
+// The ONE place a record is made: a tick's (bank_tail below) and a burst round's cannot differ.
+template <bool CAMERA>
+__device__ __forceinline__ void bank_tail_step(const BankArgs &a, size_t o, BankState &st, aof_flow f, bool first,
+                                               uint8_t *payload, const uint32_t *hist = nullptr)
+{
+    const uint64_t t64 = a.time_us[o];
+    if constexpr (CAMERA) {
+        if (a.cam.exposure) {
+            aof_exposure_record e = {};
+            if (exposure_due(a, st, t64)) {
+                for (int i = 0; i < AOF_EXPOSURE_BINS; i++) e.hist[i] = hist[i];
+                e.msv = exposure_msv(e.hist);
+                e.due = 1;
+                st.next_exposure_us = t64 + a.cam.interval_us;
+            }
+            a.cam.exposure[o] = e;
+        }
+        if (a.cam.derotated) {   // of the pair's own pixel record, whatever the limiter does with it
+            float x = 0.0f, y = 0.0f;
+            if (!first) derotate_flow(a.cam.derotate, f, a.gyro ? a.gyro[o] : aof_gyro{}, &x, &y);
+            a.cam.derotated[2 * o] = x;
+            a.cam.derotated[2 * o + 1] = y;
+        }
+    }
+    const uint32_t t = (uint32_t)t64;   // calcFlow sees 32 bits (mainloop.cpp:305-315)
+    st.frames++;
+    if (a.gyro) {                       // integrated since the last message (mainloop.cpp:383-405)
+        const aof_gyro g = a.gyro[o];
+        st.gyro_x += g.integ_x; st.gyro_y += g.integ_y; st.gyro_z += g.integ_z;
+    }
+    int quality = 0, dt_us = 0;
+    float px = 0.0f, py = 0.0f;
+    if (first) {
+        // calcFlow returns 0 with its outputs untouched (integrate(): nothing to compare the frame with), and the
+        // caller sends what its zero-initialised locals hold (mainloop.cpp:280-281,322-373)
+        st.has_prev = 1;
+        f = aof_flow{};
+    } else {
+        quality = f.quality; px = f.flow_x; py = f.flow_y;
+        if (a.output_rate <= 0) {       // limitRate: no limit, the frame's own flow and quality
+            dt_us = (int)(t - st.time_last_pub);
+            st.time_last_pub = t;
+        } else {
+            if (quality > 0) {
+                st.sum_flow_x += px;
+                st.sum_flow_y += py;
+                st.sum_flow_quality += quality;
+                st.valid_frame_count++;
+            }
+            if ((float)(t - st.time_last_pub) > a.period_us) {
+                quality = 0;
+                if (st.valid_frame_count > 0) quality = (int)floorf((float)st.sum_flow_quality / (float)st.valid_frame_count);
+                px = st.sum_flow_x; py = st.sum_flow_y;
+                st.sum_flow_x = 0.0f; st.sum_flow_y = 0.0f; st.sum_flow_quality = 0; st.valid_frame_count = 0;
+                dt_us = (int)(t - st.time_last_pub);
+                st.time_last_pub = t;
+            } else {
+                quality = AOF_TICK_HELD;   // still integrating: the caller skips this frame (mainloop.cpp:327-331)
+            }
+        }
+    }
+    aof_tick_record rec = {};
+    rec.quality = quality;
+    rec.frame = st.frames;
+    rec.pixel = f;
+    uint8_t len = 0;
+    if (quality >= 0) {
+        float ang_x = 0.0f, ang_y = 0.0f;
+        if (!first) { ang_x = aof_atan2f(px, a.focal_x); ang_y = aof_atan2f(py, a.focal_y); }
+        rec.dt_us = dt_us;
+        rec.flow_x = ang_x; rec.flow_y = ang_y;
+        rec.gyro_x = (float)st.gyro_x; rec.gyro_y = (float)st.gyro_y; rec.gyro_z = (float)st.gyro_z;
+        if (a.mavlink && a.offset_timestamp_usec != 0)   // (0: vehicle time not known, nothing is sent; mainloop.cpp:353-357)
+            len = (uint8_t)pack_optical_flow_rad(a.mavlink + o * AOF_SEQ_FRAME_BYTES, payload, a.offset_timestamp_usec + t64, dt_us,
+                                                 ang_x, ang_y, st.gyro_x, st.gyro_y, st.gyro_z, quality,
+                                                 (uint8_t)(a.first_seq + st.messages), a.system_id, a.component_id);
+        st.messages++;
+        st.gyro_x = 0.0; st.gyro_y = 0.0; st.gyro_z = 0.0;   // taken with the message (mainloop.cpp:333-334)
+    }
+    a.records[o] = rec;
+    if (a.mavlink_len) a.mavlink_len[o] = len;
+}
+
+// The tail of a tick: the state record comes from the bank and goes back to it.
+template <bool CAMERA>
+__device__ __forceinline__ void bank_tail(const BankArgs &a, uint32_t s, aof_flow f, bool first, uint8_t *payload,
+                                          const uint32_t *hist = nullptr)
+{
+    BankState st = a.state[s];
+    bank_tail_step<CAMERA>(a, s, st, f, first, payload, hist);
+    a.state[s] = st;
+}
+
+// `bytes` from src to dst by the whole workgroup: 16 bytes per lane where both are aligned (dst, a bank slot, always is).
+__device__ __forceinline__ void copy_frame(uint8_t *dst, const uint8_t *src, int64_t bytes)
+{
+    const int tid = threadIdx.x;
+    int64_t done = 0;
+    if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
+        const int64_t chunks = bytes / 16;
+        for (int64_t c = tid; c < chunks; c += kThreads)
+            reinterpret_cast<uint4 *>(dst)[c] = reinterpret_cast<const uint4 *>(src)[c];
+        done = chunks * 16;
+    }
+    for (int64_t b = done + tid; b < bytes; b += kThreads) dst[b] = src[b];
+}
+
+// Is stream s's frame its first?  Asked through LDS: lane 0 rewrites the state record later, and the waves of a
+// workgroup do not run in step.
+__device__ __forceinline__ bool bank_first(const BankArgs &a, uint32_t s)
+{
+    __shared__ uint32_t s_first;
+    if (threadIdx.x == 0) s_first = a.state[s].has_prev == 0 ? 1u : 0u;
+    __syncthreads();
+    return s_first != 0;
+}
+
+// CAMERA: is stream s's frame its first (bit 0), and is it due for exposure statistics (bit 1)?  One lane reads the
+// state and the time, like bank_first.
+__device__ __forceinline__ uint32_t bank_gate(const BankArgs &a, uint32_t s)
+{
+    __shared__ uint32_t s_gate;
+    if (threadIdx.x == 0) {
+        const BankState st = a.state[s];
+        s_gate = (st.has_prev == 0 ? 1u : 0u) | (exposure_due(a, st, a.time_us[s]) ? 2u : 0u);
+    }
+    __syncthreads();
+    return s_gate;
+}
+
+// The masked 10-bin histogram (k_ingest's, mainloop.cpp:203-214) of a cropped frame in LDS, by the whole workgroup:
+// the mask has at most 128 x 128 pixels, 16 dwords per lane, so a lane's ten counters fit 12-bit fields of two
+// 64-bit registers (no table, no scratch); ten wave sums, and one lane per wave adds each to `hist`.  Needs a crop
+// width and mask origin on a dword (the one-workgroup class: widths are multiples of 16).  Ends in a barrier.
+__device__ __forceinline__ void bank_histogram(const BankCamera &c, const uint8_t *frame, uint32_t *hist)
+{
+    const int tid = threadIdx.x;
+    if (tid < AOF_EXPOSURE_BINS) hist[tid] = 0;
+    __syncthreads();
+    const int row_dwords = (c.mx1 - c.mx0) / 4, dwords = row_dwords * (c.my1 - c.my0);
+    unsigned long long lo = 0, hi = 0;   // bins 0..4, bins 5..9
+    for (int i = tid; i < dwords; i += kThreads) {
+        const int y = i / row_dwords, x = i - y * row_dwords;
+        const uint32_t v = *reinterpret_cast<const uint32_t *>(frame + (c.my0 + y) * c.crop_w + c.mx0 + 4 * x);
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const uint32_t b = (((v >> (8 * k)) & 0xFFu) * 10u) / 255u;   // 10 for v = 255: outside cv::calcHist's range
+            if (b < 5) lo += 1ull << (12 * b);
+            else if (b < 10) hi += 1ull << (12 * (b - 5));
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < AOF_EXPOSURE_BINS; b++) {
+        const uint32_t n = wave_sum_u32((uint32_t)((b < 5 ? lo >> (12 * b) : hi >> (12 * (b - 5))) & 0xFFFu));
+        if ((tid & 63) == 0 && n) atomicAdd(&hist[b], n);
+    }
+    __syncthreads();
+}
+
+// CAMERA: the crop of a stream's first frame, sensor rows -> LDS -> slot (a first frame is always due: its histogram
+// comes from the LDS copy).  Ends in a barrier.
+__device__ __forceinline__ void crop_first_frame(const BankCamera &c, const uint8_t *src, uint8_t *lds, uint8_t *slot)
+{
+    const int row_chunks = c.crop_w / 16, chunks = row_chunks * c.crop_h;
+    for (int i = threadIdx.x; i < chunks; i += kThreads) {
+        const int y = i / row_chunks, x = i - y * row_chunks;
+        uint4 v;
+        __builtin_memcpy(&v, src + (int64_t)y * c.pitch + x * 16, 16);
+        reinterpret_cast<uint4 *>(lds)[i] = v;
+        reinterpret_cast<uint4 *>(slot)[i] = v;
+    }
+    __syncthreads();
+}
+
+}  // namespace
+
+}  // namespace aof

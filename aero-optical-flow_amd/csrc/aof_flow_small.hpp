@@ -187,11 +187,15 @@ __device__ __forceinline__ void run_level(const SearchArgs &a, const FlowTail &t
 // `cur_buf` says which buffer holds the newer frame of the pair, and bit b of `load` says whether buffer
 // b has to be fetched (and its level-1 image and sums made) -- the resident kernel keeps the frame of its
 // previous call in LDS and fetches only the new one.
-// PITCHED (the stream bank's camera tick): src1 is a window of a larger image -- its rows lie `pitch1` bytes apart
-// and may start on any byte; src0 stays a contiguous, 16-byte aligned frame.
+// PITCHED (the stream bank's camera forms): bit b of `pitched` says that src[b] is a window of a larger image -- its
+// rows lie `pitch` bytes apart and may start on any byte; every other source is a contiguous, 16-byte aligned frame.
+// The camera tick fetches its new frame into buffer 1 (the default); a burst alternates the buffers.
+// `search` false: only the fetch (passes A and B) -- the buffers named by `load` then hold their frame, its level-1
+// image and its sums for a later call that names them as the older frame (a stream's first frame inside a burst).
 template <bool SUBPIXEL, bool PITCHED = false>
 __device__ __forceinline__ void flow_small_pair(const SmallArgs &a, uint32_t pair, const uint8_t *src0, const uint8_t *src1,
-                                                int cur_buf, uint32_t load, aof_flow *final_copy = nullptr, int pitch1 = 0)
+                                                int cur_buf, uint32_t load, aof_flow *final_copy = nullptr, int pitch = 0,
+                                                uint32_t pitched = 2u, bool search = true)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_mem[];
     __shared__ uint32_t s_keys[kThreads];
@@ -222,9 +226,9 @@ __device__ __forceinline__ void flow_small_pair(const SmallArgs &a, uint32_t pai
                 v[k] = make_uint4(0, 0, 0, 0);
                 if (it < items) {
                     const int buf = first + (it >= per_frame), c = it - (it >= per_frame) * per_frame;
-                    if (PITCHED && buf) {   // one 16-byte load wherever the window starts (as k_ingest fetches its crop)
+                    if (PITCHED && ((pitched >> buf) & 1u)) {   // one 16-byte load wherever the window starts (as k_ingest fetches its crop)
                         const int y = c / (w / 16), x = c - y * (w / 16);
-                        __builtin_memcpy(&v[k], src1 + (int64_t)y * pitch1 + x * 16, 16);
+                        __builtin_memcpy(&v[k], (buf ? src1 : src0) + (int64_t)y * pitch + x * 16, 16);
                     } else {
                         v[k] = *reinterpret_cast<const uint4 *>((buf ? src1 : src0) + c * 16);
                     }
@@ -279,6 +283,7 @@ __device__ __forceinline__ void flow_small_pair(const SmallArgs &a, uint32_t pai
         }
         __syncthreads();
     }
+    if (!search) return;
 
     const int pb = 1 - cur_buf;   // the buffer of the older frame
     LevelMeta m0 = {0, 0, 0}, m1 = {0, 0, 0};

@@ -324,7 +324,20 @@ int launch_bank_tick(const SmallArgs &sm, const BankArgs &a, void *stream);
 // Behind aof_flow_batch_device on (bank frames, tick frames): the tail of every stream and the masked copy of the
 // active streams' frames into the bank.  With a.cam.camera: a.frames is the staging region, and the exposure gate,
 // the exposure record and the de-rotated pair come from here as well.
-int launch_bank_commit(const BankArgs &a, void *stream);
+// A burst's composed path runs it once per round: `a` carries the round's buffers, and stream s is active iff
+// round < count[s] (count NULL: a.active decides, as in a tick).
+int launch_bank_commit(const BankArgs &a, void *stream, const uint8_t *count = nullptr, int32_t round = 0);
+// K frame rounds per stream (aof_bank_push_burst_device, k_bank_burst.hip).  Round k's frame of stream s sits
+// round_stride bytes behind round k - 1's; time_us, gyro, records, mavlink_len, mavlink, cam.exposure and
+// cam.derotated of a BankArgs are then dense [K][S] arrays, a.active is not read.
+struct BankBurst {
+    int32_t n_rounds;              // K, 1..AOF_BANK_BURST_MAX
+    int64_t round_stride;          // bytes between the rounds of a.frames (a.cam.camera for the camera form)
+    const uint8_t *count;          // [S] frames per stream (values above K count as K), or nullptr (= K)
+};
+// One launch per burst: a workgroup per stream walks its rounds with one frame resident in LDS (same configuration
+// class and same `sm` as launch_bank_tick).
+int launch_bank_burst(const SmallArgs &sm, const BankArgs &a, const BankBurst &b, void *stream);
 int launch_bank_reset(BankState *state, const uint8_t *mask, int32_t n_streams, void *stream);
 // (aof_batch.cpp) the small-pair plan of n pairs, whatever n: true where one workgroup per pair can serve the
 // context's configuration and these buffers (flows: [n]; d_workspace: aof_workspace_layout(p, n))

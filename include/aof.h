@@ -525,6 +525,52 @@ int aof_bank_push_camera_device(aof_ctx *ctx, const aof_bank_params *bp, const a
                                 aof_exposure_record *d_exposure, float *d_derotated,
                                 uint8_t *d_mavlink, uint8_t *d_mavlink_len, void *stream);
 
+/* ---- the stream bank in bursts: K frame rounds per stream from one launch ----
+ * A camera delivers about 75 frames/s and the limiter publishes at 15 Hz (mainloop.cpp:39-44,59): a service that holds
+ * many cameras, a stream that catches up after a stall and a replay of many recordings all have several frames per
+ * stream at hand.  aof_bank_push_burst_device and aof_bank_push_camera_burst_device take K rounds of frames at once.
+ * The layout is round-major, so that round k of a burst is exactly one tick buffer of the single-tick calls:
+ *   * stream s's frame of round k sits at d_frames + k*round_stride + s*frame_stride (the camera form: d_camera +
+ *     k*round_stride + s*camera_stride);
+ *   * d_time_us, d_gyro, d_records, d_mavlink_len and d_exposure are dense [K][S], d_derotated is [K][S][2], d_mavlink
+ *     is [K][S][AOF_SEQ_FRAME_BYTES];
+ *   * d_count: u8 [S] or NULL (= K everywhere).  Stream s has frames in rounds 0 .. d_count[s]-1 and is idle in the
+ *     others; a value above K counts as K (the kernel clamps it: the host cannot see device data).
+ * Contract: every output (idle records included) and the bank's frames and state regions after the call are
+ * byte-identical to K consecutive calls of the single-tick entry point on the same bank, call k with round k's buffers
+ * and d_active[s] = (k < d_count[s]).  Everything the single tick defines therefore carries over round by round: first
+ * frames, the limiter's u32 wrap, AOF_TICK_HELD / AOF_TICK_IDLE, gyro sums taken with each published record,
+ * per-stream MAVLink sequence numbers, the 64-bit exposure gate, de-rotation of every non-first active frame.  The
+ * scratch, flows and staging regions are unspecified, as they are after a tick.
+ * A bank sized by aof_bank_layout / aof_bank_camera_layout serves bursts.  Small configurations run a burst as ONE
+ * kernel, a workgroup per stream that keeps the newest frame (with its level-1 image and pixel sums) in LDS from round
+ * to round, reads the stored frame once and writes it once: (K+2) W H bytes per stream instead of 3 K W H.  Every other
+ * configuration, and large banks, run K rounds of the single tick's composed launches in order.  Same bytes either
+ * way; aof_set_bank_path applies.  Both calls only enqueue: no allocation, no host synchronisation, capturable. */
+#define AOF_BANK_BURST_MAX 16
+typedef struct aof_bank_burst {
+    int32_t n_rounds;        /* K: 1 .. AOF_BANK_BURST_MAX */
+    int64_t round_stride;    /* bytes between round k and round k+1 of the frame buffer; 0 = dense: n_streams *
+                                frame_stride (the camera form: n_streams * camera_stride).  It must hold one round
+                                (>= that product); for pre-cropped frames a multiple of 16 */
+} aof_bank_burst;
+/* -EINVAL: everything aof_bank_push_device refuses, a NULL burst, n_rounds outside 1..AOF_BANK_BURST_MAX, a bad
+ * round_stride; -ENOSPC, -EIO as there.  A call refused for its arguments or for the context's sticky fault leaves the bank
+ * untouched.  On the composed path a launch that fails in round k > 0 (-EIO, or what aof_flow_batch_device returns) comes
+ * back after rounds 0 .. k-1 have been enqueued: the bank then holds those rounds, as after k single ticks. */
+int aof_bank_push_burst_device(aof_ctx *ctx, const aof_bank_params *bp, const aof_bank_burst *burst,
+                               const uint8_t *d_frames, const uint64_t *d_time_us, const uint8_t *d_count,
+                               const aof_gyro *d_gyro, void *d_bank, size_t bank_bytes, aof_tick_record *d_records,
+                               uint8_t *d_mavlink, uint8_t *d_mavlink_len, void *stream);
+/* -EINVAL: everything aof_bank_push_camera_device refuses, a NULL burst, n_rounds outside 1..AOF_BANK_BURST_MAX, a
+ * round_stride below one round of sensor frames; -ENOSPC, -EIO as there.  What a refused or failed call leaves: as
+ * aof_bank_push_burst_device. */
+int aof_bank_push_camera_burst_device(aof_ctx *ctx, const aof_bank_params *bp, const aof_bank_camera *cam,
+                                      const aof_bank_burst *burst, const uint8_t *d_camera, const uint64_t *d_time_us,
+                                      const uint8_t *d_count, const aof_gyro *d_gyro, void *d_bank, size_t bank_bytes,
+                                      aof_tick_record *d_records, aof_exposure_record *d_exposure, float *d_derotated,
+                                      uint8_t *d_mavlink, uint8_t *d_mavlink_len, void *stream);
+
 /* ---- measurement ----
  * With profiling on, every launch is bracketed by HIP events on the stream it
  * is launched on; the last AOF_PROFILE_RING launches of each kernel are kept.

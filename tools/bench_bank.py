@@ -12,11 +12,17 @@ With --camera, the tick on raw sensor frames (320x240 -> PX4 64x64, 640x480 -> 1
                 sweep kBankCameraFusedMaxStreams comes from);
   Y             what a caller had before: aof_ingest_batch_device into a tick buffer, then aof_bank_push_device;
   T0            the plain tick on pre-cropped frames.
+With --burst K[,K...], K frame rounds per call against K calls of the single tick on the same frames, plain and camera
+form (--forms), each on path 0 / 1 / 2:
+  B0 / B1 / B2  one aof_bank_push_burst_device (aof_bank_push_camera_burst_device) of K rounds, all streams in all rounds;
+  T0 / T1 / T2  K calls of aof_bank_push_device (aof_bank_push_camera_device) on round k's buffers: the same library
+                and the entry point that existed before bursts -- the yardstick.
 Every leg settles for about 0.2 s of untimed ticks, then times at least --ticks ticks and at least --seconds seconds
 with the host clock around ticks that end in a synchronise.  The whole sweep runs --repeats times: the difference
 between the repeats is the run-to-run spread a difference between legs has to beat.
     python tools/bench_bank.py [--streams 1,16,...] [--configs px4-64,opencv-128] > profiles/bank_tick_sweep.txt
-    python tools/bench_bank.py --camera > profiles/bank_camera_tick_sweep.txt"""
+    python tools/bench_bank.py --camera > profiles/bank_camera_tick_sweep.txt
+    python tools/bench_bank.py --burst 2,5,16 > profiles/bank_burst_sweep.txt"""
 import argparse
 import ctypes as C
 import importlib
@@ -252,6 +258,146 @@ def camera_sweep(a, dev):
             print(line)
 
 
+def timed_bursts(step, sync, K, min_rounds, min_seconds, settle_seconds):
+    """step() enqueues K frame rounds (one burst, or K ticks).  Returns (seconds per K rounds, rounds timed)."""
+    chunk = max(4, 128 // K)
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < settle_seconds:
+        for _ in range(chunk):
+            step()
+        sync()
+    done, elapsed = 0, 0.0
+    while done * K < min_rounds or elapsed < min_seconds:
+        t0 = time.perf_counter()
+        for _ in range(chunk):
+            step()
+        sync()
+        elapsed += time.perf_counter() - t0
+        done += chunk
+    return elapsed / done, done * K
+
+
+class BurstInputs:
+    """K rounds of S streams on the device, round-major: frames [K, S, h, w] (camera: sensor frames [K, S, ch, cw] with
+    the frames at the crop origin of noise), times [K, S] (13 333 us per round), gyro [K, S, 4]."""
+
+    def __init__(self, p, S, K, dev, sensor=None):
+        w, h = p.width, p.height
+        pool = np.stack([synth.make_sequence(w, h, K, 4, seed=500 + k, max_step=3)[0] for k in range(POOL)])   # [POOL, K, h, w]
+        idx = torch.from_numpy(np.arange(S) % POOL).to(dev)
+        frames = torch.from_numpy(pool).to(dev)[idx].transpose(0, 1).contiguous()                               # [K, S, h, w]
+        if sensor is None:
+            self.frames = frames
+        else:
+            cw, ch = sensor
+            x0, y0 = cw // 2 - w // 2, ch // 2 - h // 2
+            self.frames = torch.randint(0, 256, (K, 1, ch, cw), dtype=torch.uint8, device=dev).repeat(1, S, 1, 1)
+            self.frames[:, :, y0:y0 + h, x0:x0 + w] = frames
+        self.round_bytes = self.frames[0].numel()
+        self.times0 = (torch.arange(K, dtype=torch.int64, device=dev).view(K, 1) + 1).repeat(1, S) * 13333
+        self.gyro = torch.full((K, S, 4), 0.001, dtype=torch.float32, device=dev)
+
+
+def leg_burst(p, S, K, path, inp, dev, a, sensor, single_ticks):
+    """One burst of K rounds per step, or (single_ticks) K calls of the single tick on the same buffers, round by round."""
+    eng = aof.FlowEngine(p, 0)
+    eng.set_bank_path(path)
+    bp = aof.bank_params(S, FX, FY, 15, 5_000_000, 1, 100, 0)
+    cam = aof.bank_camera_params(sensor[0], sensor[1], p.width, p.height, 0, 200_000, DEROTATE, FX, FY) if sensor else None
+    bank = eng.bank_create(bp, dev, camera=cam)
+    recs = torch.empty((K, S, 48), dtype=torch.uint8, device=dev)
+    expo = torch.empty((K, S, 48), dtype=torch.uint8, device=dev)
+    derot = torch.empty((K, S, 2), dtype=torch.float32, device=dev)
+    wire = torch.empty((K, S, 56), dtype=torch.uint8, device=dev)
+    lens = torch.empty((K, S), dtype=torch.uint8, device=dev)
+    times = inp.times0.clone()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    ctx, bpp, cp = eng._ctx, C.byref(bp), C.byref(cam) if cam else None
+    burst = aof.bank_burst_params(K)
+    bank_args = (bank.buffer.data_ptr(), bank.buffer.numel())
+
+    def rounds(k):   # the pointers of round k (k = 0: of the whole burst)
+        f, t, g = inp.frames.data_ptr() + k * inp.round_bytes, times.data_ptr() + k * S * 8, inp.gyro.data_ptr() + k * S * 16
+        r, w, n = recs.data_ptr() + k * S * 48, wire.data_ptr() + k * S * 56, lens.data_ptr() + k * S
+        if cam:
+            return (f, t, None, g) + bank_args + (r, expo.data_ptr() + k * S * 48, derot.data_ptr() + k * S * 8, w, n, stream)
+        return (f, t, None, g) + bank_args + (r, w, n, stream)
+    if single_ticks:
+        fn = aof.lib.aof_bank_push_camera_device if cam else aof.lib.aof_bank_push_device
+        head = (ctx, bpp, cp) if cam else (ctx, bpp)
+        calls = [head + rounds(k) for k in range(K)]
+    else:
+        fn = aof.lib.aof_bank_push_camera_burst_device if cam else aof.lib.aof_bank_push_burst_device
+        head = (ctx, bpp, cp, C.byref(burst)) if cam else (ctx, bpp, C.byref(burst))
+        calls = [head + rounds(0)]
+    step_us = 13333 * K
+
+    def step():
+        times.add_(step_us)      # the clock runs on across the bursts (one small kernel per K rounds, in every leg)
+        for c in calls:
+            rc = fn(*c)
+            if rc:
+                raise aof.AofError(rc, aof.lib.aof_last_error(ctx).decode())
+    out = timed_bursts(step, torch.cuda.synchronize, K, a.ticks, a.seconds, a.settle)
+    r = aof.ticks_view(recs[K - 1])
+    assert (r["quality"] >= aof.TICK_HELD).all() and (r["frame"] > a.ticks).all(), "the timed rounds were real rounds"
+    eng.close()
+    return out
+
+
+def burst_sweep(a, dev):
+    print("# legs: B0/B1/B2 one burst of K rounds on path 0/1/2, T0/T1/T2 K calls of the single tick on the same buffers on path 0/1/2 "
+          "(all streams in all rounds, gyro, MAVLink frames; camera form: statistics at 200 000 us, de-rotation); every leg advances "
+          "its clock on the device once per K rounds")
+    print("# us = microseconds per K rounds (host clock, chunks of steps ending in a synchronise)")
+    sizes = [int(s) for s in a.streams.split(",")]
+    forms, ks = a.forms.split(","), [int(k) for k in a.burst.split(",")]
+    legs = [("B0", 0, False), ("T0", 0, True), ("B1", 1, False), ("T1", 1, True), ("B2", 2, False), ("T2", 2, True)]
+    results, skipped = {}, set()
+    # (--legs B1,...: a subset, for comparing two builds of the library loaded through AOF_LIB; no summary then)
+    want = [n for n, _, _ in legs] if a.legs == "T0,T1,T2,C,B" else a.legs.split(",")
+    for rep in range(a.repeats):
+        for cfg in a.configs.split(","):
+            p = params_of(cfg)
+            for form in forms:
+                sensor = SENSOR[cfg] if form == "camera" else None
+                for K in ks:
+                    for S in sizes:
+                        item = sensor[0] * sensor[1] if sensor else p.width * p.height
+                        if K * S * item > a.input_bytes_max:
+                            skipped.add((cfg, form, K, S))
+                            print(f"rep {rep} {cfg:11s} {form:6s} K={K:2d} S={S:6d} skipped: {K * S * item / 2**30:.1f} GiB of input", flush=True)
+                            continue
+                        inp = BurstInputs(p, S, K, dev, sensor)
+                        for name, path, single in legs:
+                            if name not in want:
+                                continue
+                            sec, n = leg_burst(p, S, K, path, inp, dev, a, sensor, single)
+                            results.setdefault((cfg, form, K, S, name), []).append(sec)
+                            print(f"rep {rep} {cfg:11s} {form:6s} K={K:2d} S={S:6d} {name:2s} {sec * 1e6:10.2f} us  {sec / K * 1e6:9.2f} us/round  "
+                                  f"({n} rounds)", flush=True)
+                        del inp
+                        torch.cuda.empty_cache()
+    if len(want) != len(legs):
+        return
+    print("# ---- summary (mean of the repeats; spread = |difference of the repeats| / mean) ----")
+    for cfg in a.configs.split(","):
+        p = params_of(cfg)
+        for form in forms:
+            for K in ks:
+                print(f"# {cfg} {form} K={K}: frame bytes per stream, burst on the one-launch path {(K + 2) * p.width * p.height}, K ticks {3 * K * p.width * p.height}")
+                for S in sizes:
+                    if (cfg, form, K, S) in skipped:
+                        continue
+                    m = {n: float(np.mean(results[(cfg, form, K, S, n)])) for n, _, _ in legs}
+                    sp = {n: abs(results[(cfg, form, K, S, n)][0] - results[(cfg, form, K, S, n)][-1]) / m[n] for n in m}
+                    gain = (m["T0"] - m["B0"]) / m["T0"]
+                    print(f"{cfg:11s} {form:6s} K={K:2d} S={S:6d}  " + "  ".join(f"{n} {m[n] * 1e6:9.2f} (+-{sp[n] * 100:4.1f} %)" for n in m) +
+                          f"  B0 below T0 by {gain * 100:5.1f} % ({'more' if gain > sp['B0'] + sp['T0'] else 'NOT more'} than the legs' spread)  "
+                          f"T0/B0 {m['T0'] / m['B0']:5.2f}  T1/B1 {m['T1'] / m['B1']:5.2f}  faster burst path {'B1' if m['B1'] <= m['B2'] else 'B2'}  "
+                          f"B0/best {m['B0'] / min(m['B1'], m['B2']):5.3f}")
+
+
 def leg_contexts(p, S, inp, a):
     engs = [aof.FlowEngine(p, 0) for _ in range(S)]
     flow = np.zeros(1, aof.FLOW_DTYPE)
@@ -318,7 +464,12 @@ def main():
     ap.add_argument("--legs", default="T0,T1,T2,C,B", help="legs to run (a kernel trace wants one at a time)")
     ap.add_argument("--no-marker", action="store_true")
     ap.add_argument("--camera", action="store_true", help="the sweep of the tick on raw sensor frames (legs K0, K1, K2, Y, T0)")
+    ap.add_argument("--burst", default="", help="K[,K...]: the sweep of bursts of K rounds against K single ticks (legs B0-B2, T0-T2)")
+    ap.add_argument("--forms", default="plain,camera", help="--burst: entry points to sweep")
+    ap.add_argument("--input-bytes-max", type=float, default=24 * 2**30, help="--burst: sizes whose K rounds of input exceed this are skipped")
     a = ap.parse_args()
+    if a.burst and a.ticks == ap.get_default("ticks"):
+        a.ticks = 1000           # (frame rounds)
     if a.camera and a.streams == ap.get_default("streams"):
         a.streams = "1,64,1024,1536,2048,4096"
     if not torch.cuda.is_available():
@@ -328,6 +479,8 @@ def main():
     print(f"# device: {torch.cuda.get_device_name(0)}")
     if not a.no_marker:
         print(f"# class marker: exhaustive C2 K2 (1 024 VGA pairs) {class_marker(dev):.4f} ms")
+    if a.burst:
+        return burst_sweep(a, dev)
     if a.camera:
         return camera_sweep(a, dev)
     print("# legs: T0/T1/T2 bank tick on path 0/1/2 (MAVLink frames on, all streams active), B = S contexts x aof_stream_push_host, "
