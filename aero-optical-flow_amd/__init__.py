@@ -113,6 +113,21 @@ EXPOSURE_DTYPE = np.dtype([("hist", "<u4", (10,)), ("msv", "<f4"), ("due", "<u4"
 assert TICK_DTYPE.itemsize == 48 and EXPOSURE_DTYPE.itemsize == 48
 
 
+class OutboxLayout(C.Structure):
+    """``struct aof_outbox_layout`` (include/aof.h)."""
+    _fields_ = [(n, C.c_size_t) for n in ("total_bytes", "messages", "exposures")]
+
+
+OUTBOX_HEADER_DTYPE = np.dtype([("tag", "<u8"), ("n_messages", "<u4"), ("messages_found", "<u4"), ("n_exposures", "<u4"),
+                                ("exposures_found", "<u4"), ("reserved", "u1", (40,))])            # aof_outbox_header
+OUTBOX_ENTRY_DTYPE = np.dtype([("stream", "<u4"), ("round", "<u2"), ("mavlink_len", "u1"), ("reserved0", "u1"),
+                               ("mavlink", "u1", (SEQ_FRAME_BYTES,)), ("record", TICK_DTYPE), ("derotated", "<f4", (2,)),
+                               ("reserved1", "u1", (8,))])                                           # aof_outbox_entry
+OUTBOX_EXPOSURE_DTYPE = np.dtype([("stream", "<u4"), ("round", "<u2"), ("reserved0", "<u2"), ("exposure", EXPOSURE_DTYPE),
+                                  ("reserved1", "u1", (8,))])                                        # aof_outbox_exposure
+assert OUTBOX_HEADER_DTYPE.itemsize == 64 and OUTBOX_ENTRY_DTYPE.itemsize == 128 and OUTBOX_EXPOSURE_DTYPE.itemsize == 64
+
+
 class WsLayout(C.Structure):
     _fields_ = [(n, C.c_size_t) for n in (
         "total_bytes", "sums", "l1_prev", "l1_cur", "l1_blocks", "l1_subdirs", "l1_flows",
@@ -203,6 +218,11 @@ def _load():
         "aof_bank_push_burst_device": (C.c_int, [VP, P(BankParams), P(BankBurst), VP, VP, VP, VP, VP, C.c_size_t, VP, VP, VP, VP]),
         "aof_bank_push_camera_burst_device": (C.c_int, [VP, P(BankParams), P(BankCamera), P(BankBurst), VP, VP, VP, VP, VP,
                                                         C.c_size_t, VP, VP, VP, VP, VP, VP]),
+        "aof_outbox_layout": (C.c_int, [C.c_uint32, C.c_uint32, P(OutboxLayout)]),
+        "aof_bank_collect_device": (C.c_int, [VP, C.c_int32, C.c_int32, VP, VP, VP, VP, VP, C.c_uint32, C.c_uint32, VP,
+                                              C.c_size_t, C.c_uint64, VP, VP]),
+        "aof_outbox_alloc_host": (C.c_int, [C.c_size_t, P(VP)]),
+        "aof_outbox_free_host": (C.c_int, [VP]),
         "aof_derotate_batch_device": (C.c_int, [P(DerotateParams), VP, VP, I64, VP, VP]),
         "aof_exposure_msv": (C.c_float, [VP]),
         "aof_exposure_bin": (C.c_int, [C.c_int]),
@@ -386,6 +406,77 @@ def bank_camera_layout(p: Params, bp: BankParams, cam: BankCamera):
     if rc:
         raise AofError(rc, lib.aof_strerror(rc).decode())
     return L, staging.value
+
+
+def outbox_layout(capacity_messages, capacity_exposures=0) -> OutboxLayout:
+    """``aof_outbox_layout``: byte offsets of the two entry lists behind the 64-byte header, and the outbox's size."""
+    L = OutboxLayout()
+    rc = lib.aof_outbox_layout(capacity_messages, capacity_exposures, C.byref(L))
+    if rc:
+        raise AofError(rc, lib.aof_strerror(rc).decode())
+    return L
+
+
+def outbox_view(buffer, capacity_messages=None, capacity_exposures=0):
+    """(header, messages, exposures) of an outbox as structured numpy views: the header (OUTBOX_HEADER_DTYPE, a 0-d
+    array), its n_messages stored entries (OUTBOX_ENTRY_DTYPE) and its n_exposures stored exposure entries
+    (OUTBOX_EXPOSURE_DTYPE).  buffer: a uint8 tensor or array, or a HostOutbox (then a view of the pinned memory itself,
+    not a copy).  capacity_messages None: what is left of the buffer beside capacity_exposures exposure entries."""
+    if isinstance(buffer, HostOutbox):
+        capacity_messages, capacity_exposures, a = buffer.capacity_messages, buffer.capacity_exposures, buffer.array
+    else:
+        a = buffer.cpu().numpy() if hasattr(buffer, "cpu") else np.asarray(buffer)
+        a = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+    if capacity_messages is None:
+        capacity_messages = (a.size - 64 - 64 * capacity_exposures) // 128
+    L = outbox_layout(capacity_messages, capacity_exposures)
+    assert a.size >= L.total_bytes, (a.size, L.total_bytes)
+    header = a[:64].view(OUTBOX_HEADER_DTYPE).reshape(())
+    messages = a[L.messages:L.messages + 128 * capacity_messages].view(OUTBOX_ENTRY_DTYPE)[:int(header["n_messages"])]
+    exposures = a[L.exposures:L.exposures + 64 * capacity_exposures].view(OUTBOX_EXPOSURE_DTYPE)[:int(header["n_exposures"])]
+    return header, messages, exposures
+
+
+class HostOutbox:
+    """An outbox in pinned, coherent, device-mapped host memory (``aof_outbox_alloc_host``): ``bank_collect`` writes it
+    from the device and the host polls its tag, without any stream synchronisation.  ``array`` is a numpy uint8 view of
+    the memory itself; ``ptr`` is its address, valid on both sides.  Needs a current HIP device."""
+
+    def __init__(self, capacity_messages, capacity_exposures=0):
+        self.capacity_messages, self.capacity_exposures = int(capacity_messages), int(capacity_exposures)
+        self.layout = outbox_layout(self.capacity_messages, self.capacity_exposures)
+        self.nbytes = self.layout.total_bytes
+        p = C.c_void_p()
+        rc = lib.aof_outbox_alloc_host(self.nbytes, C.byref(p))
+        if rc:
+            raise AofError(rc, "aof_outbox_alloc_host failed")
+        self.ptr = p.value
+        self.array = np.frombuffer((C.c_uint8 * self.nbytes).from_address(self.ptr), dtype=np.uint8)
+        self._tag = self.array[:8].view("<u8")
+
+    @property
+    def tag(self) -> int:
+        """The header's tag as the memory holds it now."""
+        return int(self._tag[0])
+
+    def wait(self, tag, timeout_s=2.0) -> bool:
+        """Polls for ``tag`` until the deadline; False when it ran out.  Never blocks on the device."""
+        import time
+        deadline = time.perf_counter() + timeout_s
+        tagword, tag = self._tag, int(tag)
+        while int(tagword[0]) != tag:
+            if time.perf_counter() > deadline:
+                return False
+        return True
+
+    def close(self):
+        """Frees the memory: only once the work that writes it has drained.  The views die with it."""
+        if getattr(self, "ptr", None) and lib is not None:
+            self.array = self._tag = None
+            lib.aof_outbox_free_host(self.ptr)
+            self.ptr = None
+
+    __del__ = close
 
 
 def exposure_view(t) -> np.ndarray:
@@ -767,6 +858,35 @@ class FlowEngine:
         return dict(records=records, exposure=exposure, derotated=derotated, frames=out_frames if mavlink else None,
                     lengths=out_lengths if mavlink else None)
 
+    def bank_collect(self, records, mavlink=None, lengths=None, exposure=None, derotated=None, capacity_messages=None,
+                     capacity_exposures=0, outbox=None, tag=1, tag_tensor=None):
+        """aof_bank_collect_device behind a push: records uint8 CUDA tensor [S, 48] (a tick) or [K, S, 48] (a burst);
+        mavlink [.., 56] / lengths [..], exposure [.., 48], derotated float32 [.., 2] (or its 8 bytes): the push's other outputs, or None.
+        capacity_messages: entries the outbox holds (default: one per record); outbox: a uint8 CUDA tensor of at least
+        outbox_layout().total_bytes, a HostOutbox, or None (a new tensor).  tag: non-zero; tag_tensor: int64 CUDA tensor
+        [1] the kernel reads the tag from instead (a captured graph: update it between replays).  Enqueued on torch's
+        current stream.  Returns the outbox (read it with outbox_view())."""
+        import torch
+        dev = records.device
+        assert records.dtype == torch.uint8 and records.is_contiguous() and records.shape[-1] == 48 and records.dim() in (2, 3)
+        K, S = (1, records.shape[0]) if records.dim() == 2 else (records.shape[0], records.shape[1])
+        n = K * S
+        assert mavlink is None or (mavlink.is_contiguous() and mavlink.numel() == n * SEQ_FRAME_BYTES)
+        assert lengths is None or (lengths.is_contiguous() and lengths.numel() == n)
+        assert exposure is None or (exposure.is_contiguous() and exposure.numel() == n * 48)
+        assert derotated is None or (derotated.is_contiguous() and derotated.numel() * derotated.element_size() == n * 8)
+        assert tag_tensor is None or (tag_tensor.dtype == torch.int64 and tag_tensor.numel() == 1)
+        if capacity_messages is None:
+            capacity_messages = outbox.capacity_messages if isinstance(outbox, HostOutbox) else n
+        if outbox is None:
+            outbox = torch.empty(outbox_layout(capacity_messages, capacity_exposures).total_bytes, dtype=torch.uint8, device=dev)
+        ptr, size = (outbox.ptr, outbox.nbytes) if isinstance(outbox, HostOutbox) else (outbox.data_ptr(), outbox.numel())
+        opt = lambda t: t.data_ptr() if t is not None else None
+        self._check(lib.aof_bank_collect_device(
+            self._ctx, S, K, records.data_ptr(), opt(mavlink), opt(lengths), opt(exposure), opt(derotated),
+            capacity_messages, capacity_exposures, ptr, size, int(tag), opt(tag_tensor), torch.cuda.current_stream(dev).cuda_stream))
+        return outbox
+
     def set_bank_path(self, path=0):
         """0: the library chooses between the one-launch tick kernel and the composed path, 1: the tick kernel where
         the configuration allows it, 2: always the composed path.  Same bytes either way."""
@@ -883,6 +1003,18 @@ def facade_lib():
         f.aof_facade_image_height.argtypes = [C.c_void_p]
         f.aof_facade_last_error.restype = C.c_char_p
         f.aof_facade_last_error.argtypes = [C.c_void_p]
+        f.aof_facade_bank_create.restype = C.c_void_p
+        f.aof_facade_bank_create.argtypes = [C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int]
+        f.aof_facade_bank_destroy.argtypes = [C.c_void_p]
+        f.aof_facade_bank_set_timestamp_offset.argtypes = [C.c_void_p, C.c_uint64]
+        f.aof_facade_bank_push.argtypes = [C.c_void_p] * 5
+        f.aof_facade_bank_published.restype = C.c_void_p
+        f.aof_facade_bank_published.argtypes = [C.c_void_p]
+        f.aof_facade_bank_reset.argtypes = [C.c_void_p, C.c_void_p]
+        f.aof_facade_bank_pyramid_levels.argtypes = [C.c_void_p]
+        f.aof_facade_bank_ok.argtypes = [C.c_void_p]
+        f.aof_facade_bank_last_error.restype = C.c_char_p
+        f.aof_facade_bank_last_error.argtypes = [C.c_void_p]
         _facade = f
     return _facade
 
@@ -981,3 +1113,56 @@ class OpticalFlowOpenCV(_FacadeFlow):
                  img_width=DEFAULT_IMAGE_WIDTH, img_height=DEFAULT_IMAGE_HEIGHT):
         self._h = facade_lib().aof_facade_opencv_create(f_length_x, f_length_y, output_rate,
                                                          img_width, img_height)
+
+
+class OpticalFlowBank:
+    """facade/include/flow_bank.hpp -- the many-camera counterpart of OpticalFlowOpenCV: one C++ object for
+    ``n_streams`` cameras of one frame size, a push() per tick."""
+
+    def __init__(self, f_length_x, f_length_y, output_rate=DEFAULT_OUTPUT_RATE, img_width=DEFAULT_IMAGE_WIDTH,
+                 img_height=DEFAULT_IMAGE_HEIGHT, n_streams=1):
+        self.n_streams, self.width, self.height = int(n_streams), int(img_width), int(img_height)
+        self._h = facade_lib().aof_facade_bank_create(f_length_x, f_length_y, output_rate, img_width, img_height, n_streams)
+
+    def setTimestampOffset(self, offset_usec):
+        facade_lib().aof_facade_bank_set_timestamp_offset(self._h, int(offset_usec))
+
+    def getPyramidLevels(self):
+        return facade_lib().aof_facade_bank_pyramid_levels(self._h)
+
+    def engineOk(self):
+        return bool(facade_lib().aof_facade_bank_ok(self._h))
+
+    def lastError(self):
+        return facade_lib().aof_facade_bank_last_error(self._h).decode()
+
+    def push(self, frames, img_time_us, active=None, gyro=None):
+        """frames uint8 [S, h, w]; img_time_us [S]; active uint8 [S] or None (all); gyro float32 [S, 4] or None.
+        Returns (n, entries): the return value of the C++ push() and a copy of its n published entries
+        (OUTBOX_ENTRY_DTYPE; empty when n <= 0)."""
+        S = self.n_streams
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        times = np.ascontiguousarray(img_time_us, dtype=np.uint64)
+        assert frames.size == S * self.width * self.height and times.size == S
+        active = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
+        gyro = None if gyro is None else np.ascontiguousarray(gyro, dtype=np.float32)
+        assert active is None or active.size == S
+        assert gyro is None or gyro.size == 4 * S
+        n = facade_lib().aof_facade_bank_push(self._h, frames.ctypes.data, times.ctypes.data,
+                                              active.ctypes.data if active is not None else None,
+                                              gyro.ctypes.data if gyro is not None else None)
+        if n <= 0:
+            return n, np.zeros(0, OUTBOX_ENTRY_DTYPE)
+        p = facade_lib().aof_facade_bank_published(self._h)
+        return n, np.frombuffer((C.c_uint8 * (128 * n)).from_address(p), dtype=OUTBOX_ENTRY_DTYPE).copy()
+
+    def reset(self, mask=None):
+        mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        return facade_lib().aof_facade_bank_reset(self._h, mask.ctypes.data if mask is not None else None)
+
+    def close(self):
+        if self._h:
+            facade_lib().aof_facade_bank_destroy(self._h)
+            self._h = None
+
+    __del__ = close

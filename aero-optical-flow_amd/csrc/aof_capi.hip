@@ -139,6 +139,14 @@ int aof_create(const aof_params *p, int device, aof_ctx **out)
         ctx->adapt.slots = ctx->h_fault + 16;
         ctx->votes.pairs = kVotePairs;
     }
+    {   // next to the vote records: the arrival counter of the outbox kernel (aof_bank_collect_device), zero at rest
+        DeviceGuard guard(device);
+        if (hipMalloc((void **)&ctx->outbox_counter, sizeof(OutboxCounter)) != hipSuccess ||
+            hipMemset(ctx->outbox_counter, 0, sizeof(OutboxCounter)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+            aof_destroy(ctx);
+            return -EIO;
+        }
+    }
     ctx->votes.deadline_ticks = kVoteDeadlineTicks;
     ctx->res.stop_wait_s = 1.0;
     ctx->votes.separate = true;   // the in-launch reduction is opt-in (aof_set_reduce_fusion)
@@ -184,6 +192,7 @@ void aof_destroy(aof_ctx *ctx)
     if (ctx->res.k.box) (void)hipHostFree(ctx->res.k.box);
     if (ctx->votes.done) (void)hipEventDestroy(ctx->votes.done);
     if (ctx->votes.mem) (void)hipFree(ctx->votes.mem);
+    if (ctx->outbox_counter) (void)hipFree(ctx->outbox_counter);
     if (ctx->h_fault) (void)hipHostFree(ctx->h_fault);
     delete ctx;
 }

@@ -136,6 +136,7 @@ struct aof_ctx {
     aof::HostState host;
     aof::Resident res;
     aof::InLaunchReduce votes;
+    aof::OutboxCounter *outbox_counter;   // device memory, zero at rest: arrivals of aof_bank_collect_device's workgroups
     aof::AdaptiveSearch adapt;
     aof::Tile16Verdicts tile16_verdicts;   // test hook (aof_debug_tile16_verdicts): count 0 = the probe decides
     aof::Profiling prof;

@@ -339,6 +339,29 @@ struct BankBurst {
 // class and same `sm` as launch_bank_tick).
 int launch_bank_burst(const SmallArgs &sm, const BankArgs &a, const BankBurst &b, void *stream);
 int launch_bank_reset(BankState *state, const uint8_t *mask, int32_t n_streams, void *stream);
+// The outbox of a push (aof_bank_collect_device, aof_outbox.cpp, k_bank_outbox.hip): compaction of the published records
+// and the due exposure records of n = K * S records into dense lists, and the tag behind them.
+constexpr uint32_t kOutboxTile = 1024;   // consecutive records one workgroup owns
+struct OutboxCounter {             // context-owned device memory, zero at rest (the kernel's last arriver zeroes it)
+    uint32_t arrivals;             // workgroups that have finished their stores
+    uint32_t pad;
+    unsigned long long found;      // selected records of the workgroups that have arrived: messages | exposures << 32
+};
+struct OutboxArgs {
+    uint32_t n, n_streams;         // records in all (K * S, < 2^31), records per round
+    const uint8_t *records;        // aof_tick_record [n]
+    const uint8_t *mavlink;        // [n][AOF_SEQ_FRAME_BYTES] or nullptr
+    const uint8_t *mavlink_len;    // [n] or nullptr
+    const uint8_t *exposure;       // aof_exposure_record [n] or nullptr
+    const uint8_t *derotated;      // float [n][2] or nullptr
+    uint32_t cap_messages, cap_exposures;
+    uint8_t *outbox;               // header at 0
+    uint8_t *messages, *exposures; // the two entry lists inside it
+    unsigned long long tag;
+    const unsigned long long *d_tag;   // or nullptr
+    OutboxCounter *counter;
+};
+int launch_bank_outbox(const OutboxArgs &a, void *stream);
 // (aof_batch.cpp) the small-pair plan of n pairs, whatever n: true where one workgroup per pair can serve the
 // context's configuration and these buffers (flows: [n]; d_workspace: aof_workspace_layout(p, n))
 bool plan_small_batch(const aof_ctx *ctx, const uint8_t *prev, const uint8_t *cur, int64_t stride, int64_t n, aof_flow *flows,

@@ -5,6 +5,7 @@
 // a delegate needs likewise.
 #include <new>
 
+#include "flow_bank.hpp"
 #include "flow_opencv.hpp"
 #include "flow_px4.hpp"
 #include "optical_flow_rad.hpp"
@@ -70,5 +71,26 @@ int aof_facade_image_width(void *flow) { return static_cast<OpticalFlow *>(flow)
 int aof_facade_image_height(void *flow) { return static_cast<OpticalFlow *>(flow)->getImageHeight(); }
 const char *aof_facade_last_error(void *flow) { return static_cast<OpticalFlow *>(flow)->lastError(); }
 int aof_facade_default_output_rate(void) { return DEFAULT_OUTPUT_RATE; }
+
+// ---- OpticalFlowBank (flow_bank.hpp) ----
+void *aof_facade_bank_create(float fx, float fy, int output_rate, int w, int h, int n_streams)
+{
+	return new (std::nothrow) OpticalFlowBank(fx, fy, output_rate, w, h, n_streams);
+}
+void aof_facade_bank_destroy(void *bank) { delete static_cast<OpticalFlowBank *>(bank); }
+void aof_facade_bank_set_timestamp_offset(void *bank, uint64_t offset_usec)
+{
+	static_cast<OpticalFlowBank *>(bank)->setTimestampOffset(offset_usec);
+}
+int aof_facade_bank_push(void *bank, const uint8_t *frames, const uint64_t *img_time_us, const uint8_t *active,
+			 const aof_gyro *gyro)
+{
+	return static_cast<OpticalFlowBank *>(bank)->push(frames, img_time_us, active, gyro);
+}
+const void *aof_facade_bank_published(void *bank) { return static_cast<OpticalFlowBank *>(bank)->published(); }
+int aof_facade_bank_reset(void *bank, const uint8_t *mask) { return static_cast<OpticalFlowBank *>(bank)->reset(mask); }
+int aof_facade_bank_pyramid_levels(void *bank) { return static_cast<OpticalFlowBank *>(bank)->getPyramidLevels(); }
+int aof_facade_bank_ok(void *bank) { return static_cast<OpticalFlowBank *>(bank)->engineOk() ? 1 : 0; }
+const char *aof_facade_bank_last_error(void *bank) { return static_cast<OpticalFlowBank *>(bank)->lastError(); }
 
 }  // extern "C"

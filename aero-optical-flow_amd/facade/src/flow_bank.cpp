@@ -1,0 +1,218 @@
+// OpticalFlowBank (flow_bank.hpp): S cameras per push() through the stream bank of the C ABI
+// (aof_bank_push_device) and its outbox (aof_bank_collect_device) in pinned host memory.  A push is one
+// host-to-device copy of the pinned staging block (frames, times, masks, gyro), the tick, the collect
+// launch, and a bounded poll of the outbox's tag: no stream synchronisation anywhere.
+#include <cerrno>
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+#include <new>
+
+#include <hip/hip_runtime_api.h>
+
+#include "aof.h"
+#include "flow_bank.hpp"
+#include "opencv_params.hpp"
+#include "optical_flow_rad.hpp"
+
+namespace {
+
+// every host wait for the device ends after this long (a tick runs microseconds to a millisecond)
+const double kDeadlineS = 2.0;
+
+size_t alignUp(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+double secondsSince(std::chrono::steady_clock::time_point t0)
+{
+	return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+
+}  // namespace
+
+struct OpticalFlowBank::Impl {
+	aof_ctx *ctx;
+	aof_bank_params bp;
+	hipStream_t stream;
+	// one staging block, the same layout on both sides: frames, times, gyro, masks
+	uint8_t *h_stage, *d_stage;
+	size_t stage_bytes, off_times, off_gyro, off_active;
+	void *d_bank;
+	size_t bank_bytes;
+	aof_tick_record *d_records;
+	uint8_t *d_mavlink, *d_lens;
+	uint8_t *outbox;   // pinned (aof_outbox_alloc_host): header, then n_streams entries
+	size_t outbox_bytes;
+	uint64_t tag;
+};
+
+OpticalFlowBank::OpticalFlowBank(float f_length_x, float f_length_y, int output_rate, int img_width, int img_height,
+				 int streams)
+	: image_width(img_width), image_height(img_height), n_streams(streams), _m(NULL), _failed(false)
+{
+	std::snprintf(_err, sizeof(_err), "engine not opened");
+	Impl *m = new (std::nothrow) Impl();
+	if (!m) return;
+	aof_params p;
+	opencvEngineParams(img_width, img_height, DEFAULT_NUMBER_OF_FEATURES, &p);
+	int rc = streams < 1 ? -EINVAL : aof_create(&p, 0, &m->ctx);
+	if (rc) {
+		// as the single-camera classes: stay alive, never publish, say why once
+		std::snprintf(_err, sizeof(_err), "aof_create failed: %s", streams < 1 ? "n_streams < 1" : aof_strerror(rc));
+		std::fprintf(stderr, "OpticalFlowBank: %s (no CPU fallback; flow output disabled)\n", _err);
+		delete m;
+		return;
+	}
+	std::memset(&m->bp, 0, sizeof(m->bp));
+	m->bp.n_streams = streams;
+	m->bp.focal_x = f_length_x;
+	m->bp.focal_y = f_length_y;
+	m->bp.output_rate = output_rate;
+	m->bp.system_id = MAVLINK_SYSTEM_ID_DEFAULT;
+	m->bp.component_id = MAVLINK_COMPONENT_ID_CAMERA;
+	const size_t S = (size_t)streams, frame = (size_t)img_width * img_height;
+	m->off_times = alignUp(S * frame, 256);
+	m->off_gyro = alignUp(m->off_times + S * sizeof(uint64_t), 256);
+	m->off_active = alignUp(m->off_gyro + S * sizeof(aof_gyro), 256);
+	m->stage_bytes = alignUp(m->off_active + S, 256);
+	struct aof_bank_layout L;
+	struct aof_outbox_layout O;
+	bool ok = aof_bank_layout(&p, &m->bp, &L) == 0 && aof_outbox_layout((uint32_t)streams, 0, &O) == 0;
+	if (ok) {
+		m->bank_bytes = L.total_bytes;
+		m->outbox_bytes = O.total_bytes;
+		ok = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) == hipSuccess &&
+		     hipHostMalloc((void **)&m->h_stage, m->stage_bytes, hipHostMallocDefault) == hipSuccess &&
+		     hipMalloc((void **)&m->d_stage, m->stage_bytes) == hipSuccess &&
+		     hipMalloc(&m->d_bank, m->bank_bytes) == hipSuccess &&
+		     hipMalloc((void **)&m->d_records, S * sizeof(aof_tick_record)) == hipSuccess &&
+		     hipMalloc((void **)&m->d_mavlink, S * AOF_SEQ_FRAME_BYTES) == hipSuccess &&
+		     hipMalloc((void **)&m->d_lens, S) == hipSuccess &&
+		     aof_outbox_alloc_host(m->outbox_bytes, (void **)&m->outbox) == 0;
+	}
+	_m = m;
+	if (!ok) {
+		fail(-ENOMEM, "device or pinned memory for the bank could not be allocated");
+		return;
+	}
+	std::memset(m->outbox, 0, m->outbox_bytes);
+	std::snprintf(_err, sizeof(_err), "ok");
+	if (aof_bank_reset_device(m->ctx, &m->bp, NULL, m->d_bank, m->bank_bytes, m->stream)) {
+		fail(-EIO, aof_last_error(m->ctx));
+		return;
+	}
+	waitIdle();
+}
+
+OpticalFlowBank::~OpticalFlowBank()
+{
+	if (!_m) return;
+	Impl *m = _m;
+	// a bounded wait, as everywhere: memory a kernel may still write is leaked, not freed
+	const bool drained = !m->stream || waitIdle();
+	if (drained) {
+		if (m->outbox) aof_outbox_free_host(m->outbox);
+		if (m->d_lens) (void)hipFree(m->d_lens);
+		if (m->d_mavlink) (void)hipFree(m->d_mavlink);
+		if (m->d_records) (void)hipFree(m->d_records);
+		if (m->d_bank) (void)hipFree(m->d_bank);
+		if (m->d_stage) (void)hipFree(m->d_stage);
+		if (m->h_stage) (void)hipHostFree(m->h_stage);
+		if (m->stream) (void)hipStreamDestroy(m->stream);
+		if (m->ctx) aof_destroy(m->ctx);
+	} else {
+		std::fprintf(stderr, "OpticalFlowBank: the device did not drain: its memory is leaked, not freed\n");
+	}
+	delete m;
+}
+
+int OpticalFlowBank::fail(int code, const char *what)
+{
+	_failed = true;
+	std::snprintf(_err, sizeof(_err), "%s", what);
+	return code;
+}
+
+// The object's stream has nothing left to do (polled, with the deadline); false fails the object.
+bool OpticalFlowBank::waitIdle()
+{
+	const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+	for (;;) {
+		const hipError_t e = hipStreamQuery(_m->stream);
+		if (e == hipSuccess) return true;
+		if (e != hipErrorNotReady) {
+			fail(-EIO, hipGetErrorString(e));
+			return false;
+		}
+		if (secondsSince(t0) > kDeadlineS) {
+			fail(-ETIMEDOUT, "the device did not finish within the deadline");
+			return false;
+		}
+	}
+}
+
+void OpticalFlowBank::setTimestampOffset(uint64_t offset_usec)
+{
+	if (_m) _m->bp.offset_timestamp_usec = offset_usec;
+}
+
+int OpticalFlowBank::getPyramidLevels() const
+{
+	aof_params p;
+	if (!_m || !_m->ctx || aof_get_params(_m->ctx, &p)) return 0;
+	return p.pyramid_levels;
+}
+
+bool OpticalFlowBank::engineOk() const { return _m != NULL && !_failed; }
+
+const char *OpticalFlowBank::lastError() const { return _err; }
+
+const aof_outbox_entry *OpticalFlowBank::published() const
+{
+	return _m && _m->outbox ? reinterpret_cast<const aof_outbox_entry *>(_m->outbox + sizeof(aof_outbox_header)) : NULL;
+}
+
+int OpticalFlowBank::push(const uint8_t *frames, const uint64_t *img_time_us, const uint8_t *active, const aof_gyro *gyro)
+{
+	if (!engineOk()) return -1;
+	if (!frames || !img_time_us) return -EINVAL;
+	Impl *m = _m;
+	const size_t S = (size_t)n_streams, frame = (size_t)image_width * image_height;
+	std::memcpy(m->h_stage, frames, S * frame);
+	std::memcpy(m->h_stage + m->off_times, img_time_us, S * sizeof(uint64_t));
+	if (gyro) std::memcpy(m->h_stage + m->off_gyro, gyro, S * sizeof(aof_gyro));
+	if (active) std::memcpy(m->h_stage + m->off_active, active, S);
+	if (hipMemcpyAsync(m->d_stage, m->h_stage, m->stage_bytes, hipMemcpyHostToDevice, m->stream) != hipSuccess)
+		return fail(-EIO, "copy of the tick's frames failed");
+	int rc = aof_bank_push_device(m->ctx, &m->bp, m->d_stage, reinterpret_cast<const uint64_t *>(m->d_stage + m->off_times),
+				      active ? m->d_stage + m->off_active : NULL,
+				      gyro ? reinterpret_cast<const aof_gyro *>(m->d_stage + m->off_gyro) : NULL, m->d_bank,
+				      m->bank_bytes, m->d_records, m->d_mavlink, m->d_lens, m->stream);
+	if (rc) return fail(rc, aof_last_error(m->ctx));
+	const uint64_t tag = ++m->tag;
+	rc = aof_bank_collect_device(m->ctx, n_streams, 1, m->d_records, m->d_mavlink, m->d_lens, NULL, NULL, (uint32_t)n_streams,
+				     0, m->outbox, m->outbox_bytes, tag, NULL, m->stream);
+	if (rc) return fail(rc, aof_last_error(m->ctx));
+	// the tag is the kernel's last store: once it is here, so are the counts and the entries
+	const uint64_t *word = reinterpret_cast<const uint64_t *>(m->outbox);
+	const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+	while (__atomic_load_n(word, __ATOMIC_ACQUIRE) != tag) {
+		if (secondsSince(t0) > kDeadlineS) return fail(-ETIMEDOUT, "the tick did not finish within the deadline");
+	}
+	return (int)reinterpret_cast<const aof_outbox_header *>(m->outbox)->n_messages;
+}
+
+int OpticalFlowBank::reset(const uint8_t *mask)
+{
+	if (!engineOk()) return -1;
+	Impl *m = _m;
+	if (mask) {
+		std::memcpy(m->h_stage + m->off_active, mask, (size_t)n_streams);
+		if (hipMemcpyAsync(m->d_stage + m->off_active, m->h_stage + m->off_active, (size_t)n_streams, hipMemcpyHostToDevice,
+				   m->stream) != hipSuccess)
+			return fail(-EIO, "copy of the reset mask failed");
+	}
+	const int rc = aof_bank_reset_device(m->ctx, &m->bp, mask ? m->d_stage + m->off_active : NULL, m->d_bank, m->bank_bytes,
+					     m->stream);
+	if (rc) return fail(rc, aof_last_error(m->ctx));
+	return waitIdle() ? 0 : -ETIMEDOUT;
+}

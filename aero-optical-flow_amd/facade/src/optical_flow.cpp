@@ -11,6 +11,7 @@
 #include "aof_math.h"
 #include "flow_opencv.hpp"
 #include "flow_px4.hpp"
+#include "opencv_params.hpp"
 
 OpticalFlow::OpticalFlow(float f_length_x, float f_length_y, int ouput_rate, int img_width,
 			 int img_height)
@@ -241,20 +242,8 @@ OpticalFlowOpenCV::OpticalFlowOpenCV(float f_length_x, float f_length_y, int oup
 	  num_features(num_feat), confidence_multiplier(conf_multi)
 {
 	aof_params p;
-	aof_params_px4flow(&p, img_width, img_height, DEFAULT_SEARCH_SIZE,
-			   DEFAULT_FLOW_FEATURE_THRESHOLD, DEFAULT_FLOW_VALUE_THRESHOLD);
-	int per_axis = 1;
-	while (per_axis * per_axis < num_feat) per_axis++;
-	p.num_blocks = per_axis;
-	// The class mainloop.cpp:423 creates runs at 128x128 and ~75 Hz on a moving vehicle: a
-	// single +-4 search would pin fast motion at the search limit while still reporting a
-	// plausible quality.  Two levels with per-level mean equalisation reach +-9.5 px and
-	// shrug off the auto-exposure steps; geometries that cannot carry a half-resolution grid
-	// keep the single level (getPyramidLevels() says which).
-	aof_params two = p;
-	two.pyramid_levels = 2;
-	two.mean_subtract = 1;
-	openEngine(aof_params_check(&two) == 0 ? &two : &p);
+	opencvEngineParams(img_width, img_height, num_feat, &p);
+	openEngine(&p);
 }
 
 OpticalFlowOpenCV::~OpticalFlowOpenCV() {}

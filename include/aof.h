@@ -571,6 +571,78 @@ int aof_bank_push_camera_burst_device(aof_ctx *ctx, const aof_bank_params *bp, c
                                       aof_tick_record *d_records, aof_exposure_record *d_exposure, float *d_derotated,
                                       uint8_t *d_mavlink, uint8_t *d_mavlink_len, void *stream);
 
+/* ---- the stream bank's outbox: the published messages of a push as one dense, ordered, host-pollable list ----
+ * A push leaves [K][S] records of which most say "nothing to do": the limiter publishes at 15 Hz from 75 Hz cameras, the
+ * exposure gate opens at 5 Hz, idle streams get AOF_TICK_IDLE.  aof_bank_collect_device, enqueued behind any of the four
+ * push calls (a tick is K = 1), reads only the push's output arrays and writes an OUTBOX: a 64-byte header, then one
+ * 128-byte entry per published record -- what mainloop.cpp:322-373 would send: stream, round, the MAVLink frame, the
+ * tick record, the de-rotated pair --, then one 64-byte entry per exposure record that is due.
+ * Selection and order, with o = round * n_streams + stream:
+ *   * a message entry for every o with d_records[o].quality >= 0 (first frames have quality 0 and are published, as
+ *     mainloop.cpp sends them), in increasing o;
+ *   * an exposure entry for every o with d_exposure[o].due != 0, in increasing o;
+ *   * messages_found / exposures_found count all selected records, n_messages / n_exposures the stored ones: the first
+ *     capacity_messages / capacity_exposures of them.  Of the entries behind the stored ones not one byte is written;
+ *   * d_mavlink, d_mavlink_len, d_exposure, d_derotated may each be NULL: mavlink_len 0 (and an all-zero frame),
+ *     mavlink_len 0, no exposure list (both counts 0), derotated 0, 0.
+ * The outbox is a pure function of the input arrays.  It may be device memory, or memory of aof_outbox_alloc_host.
+ * Tag: the header's first 8 bytes, the kernel's LAST store (released at system scope behind every other byte of the
+ * outbox).  `tag` must be non-zero; with d_tag the kernel reads the tag from that device word (u64) instead, so that a
+ * captured graph carries a fresh tag on every replay.  A host that polls an outbox in aof_outbox_alloc_host memory and
+ * sees the tag it asked for may read the counts and the n_* entries at once, without any stream synchronisation (write
+ * a different value over the tag, or pass another tag, before the next call).
+ * One launch, no device-side waiting; only enqueues: no allocation, no host synchronisation, capturable.  Calls on one
+ * context must not overlap on the device (they share the context's arrival counter, as the pushes share its vote
+ * memory). */
+typedef struct aof_outbox_entry {            /* 128 bytes */
+    uint32_t stream;
+    uint16_t round;                          /* 0 for a tick */
+    uint8_t  mavlink_len;                    /* 0: no frame (no d_mavlink, or nothing was sent) */
+    uint8_t  reserved0;                      /* 0 */
+    uint8_t  mavlink[AOF_SEQ_FRAME_BYTES];   /* the first mavlink_len bytes of the frame, the rest 0 */
+    aof_tick_record record;                  /* the 48 bytes of d_records[round][stream] */
+    float    derotated[2];                   /* d_derotated[round][stream], or 0, 0 without it */
+    uint8_t  reserved1[8];                   /* 0 */
+} aof_outbox_entry;
+typedef struct aof_outbox_exposure {         /* 64 bytes */
+    uint32_t stream;
+    uint16_t round;
+    uint16_t reserved0;                      /* 0 */
+    aof_exposure_record exposure;            /* the 48 bytes of d_exposure[round][stream]: due == 1 */
+    uint8_t  reserved1[8];                   /* 0 */
+} aof_outbox_exposure;
+typedef struct aof_outbox_header {           /* 64 bytes, at offset 0 of the outbox */
+    uint64_t tag;                            /* written LAST */
+    uint32_t n_messages, messages_found;     /* stored (<= capacity_messages) / present in the input */
+    uint32_t n_exposures, exposures_found;
+    uint8_t  reserved[40];                   /* 0 */
+} aof_outbox_header;
+/* Byte offsets inside an outbox: the header at 0, aof_outbox_entry [capacity_messages] at `messages`,
+ * aof_outbox_exposure [capacity_exposures] at `exposures`, each a multiple of 64.  (A struct tag only, as aof_bank_layout.) */
+struct aof_outbox_layout {
+    size_t total_bytes;
+    size_t messages;
+    size_t exposures;
+};
+/* -EINVAL: NULL out, a capacity above 2^31 - 1.  Host only. */
+int aof_outbox_layout(uint32_t capacity_messages, uint32_t capacity_exposures, struct aof_outbox_layout *out);
+/* d_records: aof_tick_record [n_rounds][n_streams]; d_mavlink u8 [K][S][AOF_SEQ_FRAME_BYTES], d_mavlink_len u8 [K][S],
+ * d_exposure aof_exposure_record [K][S], d_derotated float [K][S][2]: what the push wrote, or NULL.  outbox: >=
+ * aof_outbox_layout().total_bytes, 64-byte aligned, valid on the device.  d_tag: u64 device word, or NULL.
+ * -EINVAL: NULL ctx, records or outbox; n_streams < 1; n_rounds outside 1..AOF_BANK_BURST_MAX (or more than 2^31 - 1
+ * records in all); an outbox that is not 64-byte aligned; d_mavlink without its lengths; tag 0 with no d_tag; records,
+ * exposure records or de-rotated pairs that are not 4-byte aligned; -ENOSPC: an outbox smaller than its layout; -EIO:
+ * the context's sticky fault.  A refused call writes nothing. */
+int aof_bank_collect_device(aof_ctx *ctx, int32_t n_streams, int32_t n_rounds, const aof_tick_record *d_records,
+                            const uint8_t *d_mavlink, const uint8_t *d_mavlink_len, const aof_exposure_record *d_exposure,
+                            const float *d_derotated, uint32_t capacity_messages, uint32_t capacity_exposures,
+                            void *outbox, size_t outbox_bytes, uint64_t tag, const uint64_t *d_tag, void *stream);
+/* Pinned, coherent, device-mapped host memory whose pointer is valid on both sides (what the per-call path's tagged
+ * record lives in): an outbox the host can poll.  The calling thread's current device maps it.  -EINVAL: NULL out,
+ * bytes 0; -ENOMEM.  aof_outbox_free_host(NULL) is allowed; free only once the work that writes it has drained. */
+int aof_outbox_alloc_host(size_t bytes, void **out);
+int aof_outbox_free_host(void *p);
+
 /* ---- measurement ----
  * With profiling on, every launch is bracketed by HIP events on the stream it
  * is launched on; the last AOF_PROFILE_RING launches of each kernel are kept.

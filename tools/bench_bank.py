@@ -17,12 +17,21 @@ form (--forms), each on path 0 / 1 / 2:
   B0 / B1 / B2  one aof_bank_push_burst_device (aof_bank_push_camera_burst_device) of K rounds, all streams in all rounds;
   T0 / T1 / T2  K calls of aof_bank_push_device (aof_bank_push_camera_device) on round k's buffers: the same library
                 and the entry point that existed before bursts -- the yardstick.
+With --outbox, what it costs and gains to collect the published messages of a push into one dense list
+(aof_bank_collect_device), at 15 Hz with 9-18 ms between a stream's frames and at output_rate 0 (everything publishes):
+  T             the tick alone, pipelined (as T0);
+  D             tick + collect into a device outbox, pipelined: D - T prices the extra launch in a stream that runs on;
+  H             what a host had before: tick + three asynchronous device-to-host copies (records, lengths, frames) into
+                pinned memory + stream synchronise + np.flatnonzero(quality >= 0) -- the yardstick of O;
+  O             tick + collect into a HostOutbox + polling the tag.
+H and O are timed per tick from the enqueue to the host holding the list; one line with bursts of K = 5 rounds.
 Every leg settles for about 0.2 s of untimed ticks, then times at least --ticks ticks and at least --seconds seconds
 with the host clock around ticks that end in a synchronise.  The whole sweep runs --repeats times: the difference
 between the repeats is the run-to-run spread a difference between legs has to beat.
     python tools/bench_bank.py [--streams 1,16,...] [--configs px4-64,opencv-128] > profiles/bank_tick_sweep.txt
     python tools/bench_bank.py --camera > profiles/bank_camera_tick_sweep.txt
-    python tools/bench_bank.py --burst 2,5,16 > profiles/bank_burst_sweep.txt"""
+    python tools/bench_bank.py --burst 2,5,16 > profiles/bank_burst_sweep.txt
+    python tools/bench_bank.py --outbox > profiles/bank_outbox_sweep.txt"""
 import argparse
 import ctypes as C
 import importlib
@@ -398,6 +407,152 @@ def burst_sweep(a, dev):
                           f"B0/best {m['B0'] / min(m['B1'], m['B2']):5.3f}")
 
 
+class OutboxInputs:
+    """K rounds of S streams per step on the device: RING steps of frames [K, S, h, w]; the streams' clocks run on by
+    9 000..18 000 us per frame (the test recipe's spacing), drawn once per ring slot."""
+
+    def __init__(self, p, S, K, dev):
+        w, h = p.width, p.height
+        pool = np.stack([synth.make_sequence(w, h, RING * K, 4, seed=500 + k, max_step=3)[0] for k in range(POOL)])   # [POOL, RING * K, h, w]
+        idx = torch.from_numpy(np.arange(S) % POOL).to(dev)
+        pool_d = torch.from_numpy(pool).to(dev)
+        self.frames = [pool_d[:, k * K:(k + 1) * K][idx].transpose(0, 1).contiguous() for k in range(RING)]          # [K, S, h, w] each
+        rng = np.random.default_rng(7)
+        step = rng.integers(9000, 18000, (RING, K, S)).astype(np.int64)
+        self.offsets = torch.from_numpy(np.cumsum(step, axis=1)).to(dev)       # [RING, K, S]: round k's time behind the step's start
+        self.advance = self.offsets[:, K - 1].contiguous()                      # [RING, S]
+        self.gyro = torch.full((K, S, 4), 0.001, dtype=torch.float32, device=dev)
+
+
+def hip_runtime():
+    """hipMemcpyAsync / hipStreamSynchronize of the HIP runtime torch has loaded (the H leg's copies without torch's
+    per-call overhead)."""
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    hip.hipStreamSynchronize.argtypes = [C.c_void_p]
+    return hip
+
+
+def leg_outbox(p, S, K, rate, leg, inp, dev, a):
+    """One of T / D / H / O on K rounds per step (K = 1: the tick, else the burst call).  Returns (seconds per step,
+    steps, messages per step)."""
+    eng = aof.FlowEngine(p, 0)
+    bp = aof.bank_params(S, FX, FY, rate, 5_000_000, 1, 100, 0)
+    bank = eng.bank_create(bp, dev)
+    n = K * S
+    recs = torch.empty((K, S, 48), dtype=torch.uint8, device=dev)
+    wire = torch.empty((K, S, 56), dtype=torch.uint8, device=dev)
+    lens = torch.empty((K, S), dtype=torch.uint8, device=dev)
+    clock = torch.zeros(S, dtype=torch.int64, device=dev)
+    times = torch.zeros((K, S), dtype=torch.int64, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    ctx, bpp = eng._ctx, C.byref(bp)
+    burst = aof.bank_burst_params(K)
+    tail = (times.data_ptr(), None, inp.gyro.data_ptr(), bank.buffer.data_ptr(), bank.buffer.numel(), recs.data_ptr(), wire.data_ptr(),
+            lens.data_ptr(), stream)
+    if K == 1:
+        push, head = aof.lib.aof_bank_push_device, (ctx, bpp)
+    else:
+        push, head = aof.lib.aof_bank_push_burst_device, (ctx, bpp, C.byref(burst))
+    ptrs = [f.data_ptr() for f in inp.frames]
+    collect = aof.lib.aof_bank_collect_device
+    counts = []
+
+    def tick(i):
+        torch.add(clock, inp.offsets[i % RING], out=times)      # the clocks run on across the ring's wraps (two small kernels
+        clock.add_(inp.advance[i % RING])                       # per step, in every leg)
+        rc = push(*head, ptrs[i % RING], *tail)
+        if rc:
+            raise aof.AofError(rc, aof.lib.aof_last_error(ctx).decode())
+
+    if leg == "T":
+        out = timed(tick, torch.cuda.synchronize, a.ticks, a.seconds, a.settle)
+    elif leg == "D":
+        box = torch.empty(aof.outbox_layout(n, 0).total_bytes, dtype=torch.uint8, device=dev)
+        cargs = (ctx, S, K, recs.data_ptr(), wire.data_ptr(), lens.data_ptr(), None, None, n, 0, box.data_ptr(), box.numel(), 1, None, stream)
+
+        def step(i):
+            tick(i)
+            rc = collect(*cargs)
+            if rc:
+                raise aof.AofError(rc, aof.lib.aof_last_error(ctx).decode())
+        out = timed(step, torch.cuda.synchronize, a.ticks, a.seconds, a.settle)
+        counts.append(int(aof.outbox_view(box)[0]["n_messages"]))
+    elif leg == "H":
+        hip = hip_runtime()
+        h_recs = torch.empty((n, 48), dtype=torch.uint8, pin_memory=True)
+        h_wire = torch.empty((n, 56), dtype=torch.uint8, pin_memory=True)
+        h_lens = torch.empty(n, dtype=torch.uint8, pin_memory=True)
+        quality = h_recs.numpy().view(aof.TICK_DTYPE).reshape(n)["quality"]
+        copies = [(h.data_ptr(), d.data_ptr(), d.numel()) for h, d in ((h_recs, recs), (h_lens, lens), (h_wire, wire))]
+
+        def step(i):
+            tick(i)
+            for dst, src, size in copies:
+                if hip.hipMemcpyAsync(dst, src, size, 2, stream):           # hipMemcpyDeviceToHost
+                    raise RuntimeError("hipMemcpyAsync failed")
+            if hip.hipStreamSynchronize(stream):
+                raise RuntimeError("hipStreamSynchronize failed")
+            counts.append(len(np.flatnonzero(quality >= 0)))
+        out = timed(step, lambda: None, a.ticks, a.seconds, a.settle)
+    else:
+        host = aof.HostOutbox(n)
+        tagword = host.array[:8].view("<u8")
+        n_messages = host.array[8:12].view("<u4")
+        before, after = (ctx, S, K, recs.data_ptr(), wire.data_ptr(), lens.data_ptr(), None, None, n, 0, host.ptr, host.nbytes), (None, stream)
+
+        def step(i):
+            tick(i)
+            tag = i + 1
+            rc = collect(*before, tag, *after)
+            if rc:
+                raise aof.AofError(rc, aof.lib.aof_last_error(ctx).decode())
+            deadline = time.perf_counter() + 5.0
+            while tagword[0] != tag:
+                if time.perf_counter() > deadline:
+                    raise RuntimeError("the outbox tag did not arrive within 5 s")
+            counts.append(int(n_messages[0]))
+        out = timed(step, lambda: None, a.ticks, a.seconds, a.settle)
+        torch.cuda.synchronize()
+        host.close()
+    torch.cuda.synchronize()
+    r = aof.ticks_view(recs[K - 1])
+    assert (r["quality"] >= aof.TICK_HELD).all() and (r["frame"] > a.ticks).all(), "the timed ticks were real ticks"
+    eng.close()
+    return out[0], out[1], float(np.mean(counts[-256:])) if counts else float("nan")
+
+
+def outbox_sweep(a, dev):
+    print("# legs: T tick alone (pipelined), D tick + collect into a device outbox (pipelined), H tick + 3 async D2H copies (records, "
+          "lengths, frames) into pinned memory + stream synchronise + np.flatnonzero(quality >= 0), O tick + collect into a HostOutbox "
+          "+ polling the tag; MAVLink frames on, all streams active, gyro; every leg advances its clocks on the device per step")
+    print("# us = microseconds per step (a tick, or a burst of K rounds); T and D: host clock around chunks of steps ending in a "
+          "synchronise; H and O: every step ends with the host holding the list; msgs = messages per step the leg's host saw")
+    sizes = [int(s) for s in a.streams.split(",")]
+    cases = [(cfg, 1, rate, S) for cfg in a.configs.split(",") for rate in (15, 0) for S in sizes]
+    cases += [(cfg, 5, 15, S) for cfg, S in (("px4-64", 4096),) if cfg in a.configs.split(",")]        # the one burst line
+    results, msgs = {}, {}
+    for rep in range(a.repeats):
+        for cfg, K, rate, S in cases:
+            p = params_of(cfg)
+            inp = OutboxInputs(p, S, K, dev)
+            for leg in ("T", "D", "H", "O"):
+                sec, n, m = leg_outbox(p, S, K, rate, leg, inp, dev, a)
+                results.setdefault((cfg, K, rate, S, leg), []).append(sec)
+                msgs[(cfg, K, rate, S, leg)] = m
+                print(f"rep {rep} {cfg:11s} K={K:2d} rate={rate:2d} S={S:6d} {leg} {sec * 1e6:10.2f} us  ({n} steps, msgs {m:9.1f})", flush=True)
+            del inp
+            torch.cuda.empty_cache()
+    print("# ---- summary (mean of the repeats; spread = |difference of the repeats| / mean) ----")
+    for cfg, K, rate, S in cases:
+        m = {leg: float(np.mean(results[(cfg, K, rate, S, leg)])) for leg in "TDHO"}
+        sp = {leg: abs(results[(cfg, K, rate, S, leg)][0] - results[(cfg, K, rate, S, leg)][-1]) / m[leg] for leg in "TDHO"}
+        gain = (m["H"] - m["O"]) / m["H"]
+        print(f"{cfg:11s} K={K:2d} rate={rate:2d} S={S:6d}  " + "  ".join(f"{leg} {m[leg] * 1e6:9.2f} (+-{sp[leg] * 100:4.1f} %)" for leg in "TDHO") +
+              f"  D-T {(m['D'] - m['T']) * 1e6:7.2f} us  msgs/step {msgs[(cfg, K, rate, S, 'O')]:9.1f} of {K * S}  "
+              f"O below H by {gain * 100:5.1f} % ({'more' if gain > sp['O'] + sp['H'] else 'NOT more'} than the legs' spread)  H/O {m['H'] / m['O']:5.2f}")
+
+
 def leg_contexts(p, S, inp, a):
     engs = [aof.FlowEngine(p, 0) for _ in range(S)]
     flow = np.zeros(1, aof.FLOW_DTYPE)
@@ -465,6 +620,7 @@ def main():
     ap.add_argument("--no-marker", action="store_true")
     ap.add_argument("--camera", action="store_true", help="the sweep of the tick on raw sensor frames (legs K0, K1, K2, Y, T0)")
     ap.add_argument("--burst", default="", help="K[,K...]: the sweep of bursts of K rounds against K single ticks (legs B0-B2, T0-T2)")
+    ap.add_argument("--outbox", action="store_true", help="the sweep of the outbox: legs T, D, H, O")
     ap.add_argument("--forms", default="plain,camera", help="--burst: entry points to sweep")
     ap.add_argument("--input-bytes-max", type=float, default=24 * 2**30, help="--burst: sizes whose K rounds of input exceed this are skipped")
     a = ap.parse_args()
@@ -472,6 +628,8 @@ def main():
         a.ticks = 1000           # (frame rounds)
     if a.camera and a.streams == ap.get_default("streams"):
         a.streams = "1,64,1024,1536,2048,4096"
+    if a.outbox and a.streams == ap.get_default("streams"):
+        a.streams = "64,256,1024,4096,16384"
     if not torch.cuda.is_available():
         raise SystemExit("bench_bank.py measures on a GPU; none is visible")
     dev = torch.device("cuda:0")
@@ -479,6 +637,8 @@ def main():
     print(f"# device: {torch.cuda.get_device_name(0)}")
     if not a.no_marker:
         print(f"# class marker: exhaustive C2 K2 (1 024 VGA pairs) {class_marker(dev):.4f} ms")
+    if a.outbox:
+        return outbox_sweep(a, dev)
     if a.burst:
         return burst_sweep(a, dev)
     if a.camera:
