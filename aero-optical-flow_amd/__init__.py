@@ -113,6 +113,20 @@ EXPOSURE_DTYPE = np.dtype([("hist", "<u4", (10,)), ("msv", "<f4"), ("due", "<u4"
 assert TICK_DTYPE.itemsize == 48 and EXPOSURE_DTYPE.itemsize == 48
 
 
+class ExposureControl(C.Structure):
+    """``aof_exposure_control`` (include/aof.h): the constants of the auto-exposure controller."""
+    _fields_ = [(n, C.c_float) for n in ("msv_target", "exposure_p", "exposure_i", "exposure_d", "gain_p", "gain_i", "gain_d",
+                                         "exposure_change_threshold", "exposure_max", "gain_change_threshold", "gain_max")]
+
+
+EXPOSURE_UPDATED, EXPOSURE_SET_EXPOSURE, EXPOSURE_SET_GAIN = 1, 2, 4
+EXPOSURE_STATE_DTYPE = np.dtype([("msv_error_old", "<f4"), ("msv_error_int", "<f4"), ("exposure", "<u2"), ("gain", "u1"),
+                                 ("reserved", "u1"), ("updates", "<u4")])                            # aof_exposure_state
+EXPOSURE_COMMAND_DTYPE = np.dtype([("exposure", "<u2"), ("gain", "u1"), ("flags", "u1"), ("msv_error", "<f4"),
+                                   ("msv_error_int", "<f4"), ("update", "<u4")])                     # aof_exposure_command
+assert EXPOSURE_STATE_DTYPE.itemsize == 16 and EXPOSURE_COMMAND_DTYPE.itemsize == 16
+
+
 class OutboxLayout(C.Structure):
     """``struct aof_outbox_layout`` (include/aof.h)."""
     _fields_ = [(n, C.c_size_t) for n in ("total_bytes", "messages", "exposures")]
@@ -223,6 +237,10 @@ def _load():
                                               C.c_size_t, C.c_uint64, VP, VP]),
         "aof_outbox_alloc_host": (C.c_int, [C.c_size_t, P(VP)]),
         "aof_outbox_free_host": (C.c_int, [VP]),
+        "aof_exposure_control_default": (C.c_int, [P(ExposureControl)]),
+        "aof_bank_exposure_reset_device": (C.c_int, [VP, C.c_int32, VP, C.c_uint16, C.c_uint8, VP, VP, VP, VP]),
+        "aof_bank_exposure_control_device": (C.c_int, [VP, P(ExposureControl), C.c_int32, C.c_int32, VP, VP, VP, VP]),
+        "aof_exposure_control_host": (C.c_int, [P(ExposureControl), C.c_int32, C.c_int32, VP, VP, VP]),
         "aof_derotate_batch_device": (C.c_int, [P(DerotateParams), VP, VP, I64, VP, VP]),
         "aof_exposure_msv": (C.c_float, [VP]),
         "aof_exposure_bin": (C.c_int, [C.c_int]),
@@ -477,6 +495,43 @@ class HostOutbox:
             self.ptr = None
 
     __del__ = close
+
+
+def exposure_control_default() -> ExposureControl:
+    """``aof_exposure_control_default``: the reference's constants (mainloop.cpp:53-63)."""
+    ec = ExposureControl()
+    rc = lib.aof_exposure_control_default(C.byref(ec))
+    if rc:
+        raise AofError(rc, lib.aof_strerror(rc).decode())
+    return ec
+
+
+def exposure_control_host(records, states, ec: ExposureControl = None):
+    """``aof_exposure_control_host``: the controller on host memory, no device.  records: EXPOSURE_DTYPE [S] or [K, S];
+    states: EXPOSURE_STATE_DTYPE [S], contiguous, updated IN PLACE.  Returns the commands (EXPOSURE_COMMAND_DTYPE, the
+    shape of records)."""
+    ec = exposure_control_default() if ec is None else ec
+    records = np.ascontiguousarray(records, dtype=EXPOSURE_DTYPE)
+    assert records.ndim in (1, 2)
+    K, S = (1, records.shape[0]) if records.ndim == 1 else records.shape
+    assert states.dtype == EXPOSURE_STATE_DTYPE and states.shape == (S,) and states.flags.c_contiguous and states.flags.writeable
+    commands = np.empty(records.shape, EXPOSURE_COMMAND_DTYPE)
+    rc = lib.aof_exposure_control_host(C.byref(ec), S, K, records.ctypes.data, states.ctypes.data, commands.ctypes.data)
+    if rc:
+        raise AofError(rc, lib.aof_strerror(rc).decode())
+    return commands
+
+
+def exposure_states_view(t) -> np.ndarray:
+    """uint8 tensor/array [S, 16] of ``aof_exposure_state`` -> structured numpy view [S]."""
+    a = t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+    return np.ascontiguousarray(a).view(EXPOSURE_STATE_DTYPE).reshape(a.shape[:-1])
+
+
+def exposure_commands_view(t) -> np.ndarray:
+    """uint8 tensor/array [.., 16] of ``aof_exposure_command`` -> structured numpy view [..]."""
+    a = t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+    return np.ascontiguousarray(a).view(EXPOSURE_COMMAND_DTYPE).reshape(a.shape[:-1])
 
 
 def exposure_view(t) -> np.ndarray:
@@ -887,6 +942,43 @@ class FlowEngine:
             capacity_messages, capacity_exposures, ptr, size, int(tag), opt(tag_tensor), torch.cuda.current_stream(dev).cuda_stream))
         return outbox
 
+    def bank_exposure_reset(self, state, mask=None, exposure0=1, gain0=1, exposures=None, gains=None):
+        """aof_bank_exposure_reset_device: state uint8 CUDA tensor [S, 16] (``aof_exposure_state``; read it with
+        exposure_states_view()); mask uint8 [S] (non-zero = reset) or None (all); the streams start from exposures
+        (int16/uint16 [S]) / gains (uint8 [S]) where given, else from the scalars.  Enqueued on torch's current stream."""
+        import torch
+        S = state.numel() // 16
+        assert state.dtype == torch.uint8 and state.is_contiguous() and state.numel() == 16 * S
+        assert mask is None or (mask.dtype == torch.uint8 and mask.numel() == S and mask.is_contiguous())
+        assert exposures is None or (exposures.element_size() == 2 and exposures.numel() == S and exposures.is_contiguous())
+        assert gains is None or (gains.dtype == torch.uint8 and gains.numel() == S and gains.is_contiguous())
+        opt = lambda t: t.data_ptr() if t is not None else None
+        self._check(lib.aof_bank_exposure_reset_device(self._ctx, S, opt(mask), int(exposure0), int(gain0), opt(exposures),
+                                                       opt(gains), state.data_ptr(), torch.cuda.current_stream(state.device).cuda_stream))
+
+    def bank_exposure_control(self, exposure, state, commands=None, ec: ExposureControl = None):
+        """aof_bank_exposure_control_device behind a camera push: exposure uint8 CUDA tensor [S, 48] (a tick) or
+        [K, S, 48] (a burst), what the push wrote; state uint8 [S, 16], stepped in place; commands: uint8 CUDA tensor
+        [.., 16], a numpy uint8 array over device-mapped host memory (a HostOutbox's ``array``), or None (a new tensor).
+        Enqueued on torch's current stream.  Returns the commands (read them with exposure_commands_view())."""
+        import torch
+        dev = exposure.device
+        assert exposure.dtype == torch.uint8 and exposure.is_contiguous() and exposure.shape[-1] == 48 and exposure.dim() in (2, 3)
+        K, S = (1, exposure.shape[0]) if exposure.dim() == 2 else (exposure.shape[0], exposure.shape[1])
+        assert state.dtype == torch.uint8 and state.is_contiguous() and state.numel() == 16 * S
+        if commands is None:
+            commands = torch.empty(tuple(exposure.shape[:-1]) + (16,), dtype=torch.uint8, device=dev)
+        if isinstance(commands, np.ndarray):
+            assert commands.dtype == np.uint8 and commands.size == 16 * K * S and commands.flags.c_contiguous
+            ptr = commands.ctypes.data
+        else:
+            assert commands.dtype == torch.uint8 and commands.is_contiguous() and commands.numel() == 16 * K * S
+            ptr = commands.data_ptr()
+        ec = exposure_control_default() if ec is None else ec
+        self._check(lib.aof_bank_exposure_control_device(self._ctx, C.byref(ec), S, K, exposure.data_ptr(), state.data_ptr(), ptr,
+                                                         torch.cuda.current_stream(dev).cuda_stream))
+        return commands
+
     def set_bank_path(self, path=0):
         """0: the library chooses between the one-launch tick kernel and the composed path, 1: the tick kernel where
         the configuration allows it, 2: always the composed path.  Same bytes either way."""
@@ -1008,6 +1100,10 @@ def facade_lib():
         f.aof_facade_bank_destroy.argtypes = [C.c_void_p]
         f.aof_facade_bank_set_timestamp_offset.argtypes = [C.c_void_p, C.c_uint64]
         f.aof_facade_bank_push.argtypes = [C.c_void_p] * 5
+        f.aof_facade_bank_enable_camera.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32]
+        f.aof_facade_bank_push_camera.argtypes = [C.c_void_p] * 5
+        f.aof_facade_bank_exposure_commands.restype = C.c_void_p
+        f.aof_facade_bank_exposure_commands.argtypes = [C.c_void_p]
         f.aof_facade_bank_published.restype = C.c_void_p
         f.aof_facade_bank_published.argtypes = [C.c_void_p]
         f.aof_facade_bank_reset.argtypes = [C.c_void_p, C.c_void_p]
@@ -1136,25 +1232,49 @@ class OpticalFlowBank:
     def lastError(self):
         return facade_lib().aof_facade_bank_last_error(self._h).decode()
 
-    def push(self, frames, img_time_us, active=None, gyro=None):
-        """frames uint8 [S, h, w]; img_time_us [S]; active uint8 [S] or None (all); gyro float32 [S, 4] or None.
-        Returns (n, entries): the return value of the C++ push() and a copy of its n published entries
-        (OUTBOX_ENTRY_DTYPE; empty when n <= 0)."""
+    def _push(self, call, frames, frame_bytes, img_time_us, active, gyro):
+        """One tick through `call` (the plain or the sensor-frame delegate): (n, a copy of the n published entries)."""
         S = self.n_streams
         frames = np.ascontiguousarray(frames, dtype=np.uint8)
         times = np.ascontiguousarray(img_time_us, dtype=np.uint64)
-        assert frames.size == S * self.width * self.height and times.size == S
+        assert frames.size == S * frame_bytes and times.size == S
         active = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
         gyro = None if gyro is None else np.ascontiguousarray(gyro, dtype=np.float32)
         assert active is None or active.size == S
         assert gyro is None or gyro.size == 4 * S
-        n = facade_lib().aof_facade_bank_push(self._h, frames.ctypes.data, times.ctypes.data,
-                                              active.ctypes.data if active is not None else None,
-                                              gyro.ctypes.data if gyro is not None else None)
+        n = call(self._h, frames.ctypes.data, times.ctypes.data, active.ctypes.data if active is not None else None,
+                 gyro.ctypes.data if gyro is not None else None)
         if n <= 0:
             return n, np.zeros(0, OUTBOX_ENTRY_DTYPE)
         p = facade_lib().aof_facade_bank_published(self._h)
         return n, np.frombuffer((C.c_uint8 * (128 * n)).from_address(p), dtype=OUTBOX_ENTRY_DTYPE).copy()
+
+    def push(self, frames, img_time_us, active=None, gyro=None):
+        """frames uint8 [S, h, w]; img_time_us [S]; active uint8 [S] or None (all); gyro float32 [S, 4] or None.
+        Returns (n, entries): the return value of the C++ push() and a copy of its n published entries
+        (OUTBOX_ENTRY_DTYPE; empty when n <= 0)."""
+        return self._push(facade_lib().aof_facade_bank_push, frames, self.width * self.height, img_time_us, active, gyro)
+
+    def enableCamera(self, camera_width, camera_height, exposure0=1, gain0=1, exposure_interval_us=200000):
+        """The sensor-frame form: pushCamera() takes camera_width x camera_height frames, and every stream's
+        auto-exposure controller starts from exposure0 / gain0.  Returns 0 or a negative value."""
+        rc = facade_lib().aof_facade_bank_enable_camera(self._h, int(camera_width), int(camera_height), int(exposure0), int(gain0),
+                                                        int(exposure_interval_us))
+        if rc == 0:
+            self._sensor = int(camera_width) * int(camera_height)
+        return rc
+
+    def pushCamera(self, sensor_frames, img_time_us, active=None, gyro=None):
+        """sensor_frames uint8 [S, camera_height, camera_width]; the rest and the return value as push()."""
+        assert getattr(self, "_sensor", None), "pushCamera() needs enableCamera()"
+        return self._push(facade_lib().aof_facade_bank_push_camera, sensor_frames, self._sensor, img_time_us, active, gyro)
+
+    def exposureCommands(self):
+        """A copy of the last pushCamera()'s commands (EXPOSURE_COMMAND_DTYPE [n_streams]); None without enableCamera()."""
+        p = facade_lib().aof_facade_bank_exposure_commands(self._h)
+        if not p:
+            return None
+        return np.frombuffer((C.c_uint8 * (16 * self.n_streams)).from_address(p), dtype=EXPOSURE_COMMAND_DTYPE).copy()
 
     def reset(self, mask=None):
         mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)

@@ -362,6 +362,18 @@ struct OutboxArgs {
     OutboxCounter *counter;
 };
 int launch_bank_outbox(const OutboxArgs &a, void *stream);
+// The auto-exposure controller behind a camera push (aof_bank_exposure_control_device, aof_exposure.cpp,
+// k_bank_exposure.hip): a lane per stream walks its K exposure records and steps the stream's state.
+struct ExposureArgs {
+    aof_exposure_control ec;
+    uint32_t n_streams, n_rounds;      // S, K (1..AOF_BANK_BURST_MAX)
+    const uint8_t *records;            // aof_exposure_record [K][S]
+    aof_exposure_state *state;         // [S]
+    aof_exposure_command *commands;    // [K][S]
+};
+int launch_bank_exposure(const ExposureArgs &a, void *stream);
+int launch_bank_exposure_reset(aof_exposure_state *state, const uint8_t *mask, uint32_t n_streams, uint16_t exposure0,
+                               uint8_t gain0, const uint16_t *d_exposure0, const uint8_t *d_gain0, void *stream);
 // (aof_batch.cpp) the small-pair plan of n pairs, whatever n: true where one workgroup per pair can serve the
 // context's configuration and these buffers (flows: [n]; d_workspace: aof_workspace_layout(p, n))
 bool plan_small_batch(const aof_ctx *ctx, const uint8_t *prev, const uint8_t *cur, int64_t stride, int64_t n, aof_flow *flows,

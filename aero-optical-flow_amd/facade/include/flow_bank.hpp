@@ -13,6 +13,7 @@
 
 struct aof_outbox_entry;   // include/aof.h: stream, MAVLink frame, tick record (quality, dt_us, flow_x, flow_y, gyro sums)
 struct aof_gyro;           // include/aof.h: gyro angles integrated over the interval that ends at a frame
+struct aof_exposure_command;   // include/aof.h: what the auto-exposure controller decided for a stream in a tick
 
 class OpticalFlowBank {
 public:
@@ -36,8 +37,30 @@ public:
 	int push(const uint8_t *frames, const uint64_t *img_time_us, const uint8_t *active, const aof_gyro *gyro);
 	// The entries of the last push(), in stream order; valid until the next push().
 	const aof_outbox_entry *published() const;
-	// Masked streams (mask[s] != 0; NULL = all) start over: no previous frame, limiter and gyro sums zero.
+	// Masked streams (mask[s] != 0; NULL = all) start over: no previous frame, limiter and gyro sums zero,
+	// the exposure gate open.  The auto-exposure controllers keep what they hold: the cameras keep running.
+	// This class has no call that restarts one stream's controller or overwrites its state (after a camera
+	// refused a value, say): a host that needs that drives aof_bank_exposure_reset_device and a state array
+	// of its own through include/aof.h.
 	int reset(const uint8_t *mask);
+
+	// The sensor-frame form: what mainloop.cpp's camera_callback does in front of calcFlow() (crop, exposure
+	// statistics at 5 Hz, the auto-exposure PID of mainloop.cpp:222-271) moves behind pushCamera() for every
+	// stream.  enableCamera() sizes the device memory for n_streams sensor frames of camera_width x
+	// camera_height (centre-cropped to the image size), starts every controller from exposure0 / gain0 and
+	// starts every stream over; exposure_interval_us: mainloop.cpp:274.  Returns 0, or a negative value:
+	// -EINVAL for a second call or a sensor size that cannot hold the image (refused: the object is as it
+	// was, lastError() says why), anything else for no memory or a device that did not answer (the object
+	// has failed).
+	int enableCamera(int camera_width, int camera_height, uint16_t exposure0, uint8_t gain0,
+			 uint32_t exposure_interval_us = 200000);
+	// One tick on sensor frames: stream s's frame at s * camera_width * camera_height; everything else, and
+	// the return value and published(), as push().  Runs camera push, exposure control and collect on the
+	// object's stream.  Needs enableCamera().
+	int pushCamera(const uint8_t *sensor_frames, const uint64_t *img_time_us, const uint8_t *active, const aof_gyro *gyro);
+	// The last pushCamera()'s aof_exposure_command [n_streams] in pinned memory (flags 0: the stream's frame
+	// was not due); valid until the next push.  NULL without enableCamera().
+	const aof_exposure_command *exposureCommands() const;
 
 	inline int getStreams() const { return n_streams; }
 	inline int getImageWidth() const { return image_width; }
@@ -50,7 +73,9 @@ private:
 	OpticalFlowBank(const OpticalFlowBank &);
 	OpticalFlowBank &operator=(const OpticalFlowBank &);
 	int fail(int code, const char *what);
+	int refuse(int code, const char *what);
 	bool waitIdle();
+	int collect();
 
 	int image_width, image_height, n_streams;
 	struct Impl;

@@ -87,6 +87,18 @@ int aof_facade_bank_push(void *bank, const uint8_t *frames, const uint64_t *img_
 {
 	return static_cast<OpticalFlowBank *>(bank)->push(frames, img_time_us, active, gyro);
 }
+int aof_facade_bank_enable_camera(void *bank, int camera_width, int camera_height, int exposure0, int gain0,
+				  uint32_t exposure_interval_us)
+{
+	return static_cast<OpticalFlowBank *>(bank)->enableCamera(camera_width, camera_height, (uint16_t)exposure0, (uint8_t)gain0,
+								   exposure_interval_us);
+}
+int aof_facade_bank_push_camera(void *bank, const uint8_t *sensor_frames, const uint64_t *img_time_us, const uint8_t *active,
+				const aof_gyro *gyro)
+{
+	return static_cast<OpticalFlowBank *>(bank)->pushCamera(sensor_frames, img_time_us, active, gyro);
+}
+const void *aof_facade_bank_exposure_commands(void *bank) { return static_cast<OpticalFlowBank *>(bank)->exposureCommands(); }
 const void *aof_facade_bank_published(void *bank) { return static_cast<OpticalFlowBank *>(bank)->published(); }
 int aof_facade_bank_reset(void *bank, const uint8_t *mask) { return static_cast<OpticalFlowBank *>(bank)->reset(mask); }
 int aof_facade_bank_pyramid_levels(void *bank) { return static_cast<OpticalFlowBank *>(bank)->getPyramidLevels(); }

@@ -1,7 +1,10 @@
 // OpticalFlowBank (flow_bank.hpp): S cameras per push() through the stream bank of the C ABI
 // (aof_bank_push_device) and its outbox (aof_bank_collect_device) in pinned host memory.  A push is one
 // host-to-device copy of the pinned staging block (frames, times, masks, gyro), the tick, the collect
-// launch, and a bounded poll of the outbox's tag: no stream synchronisation anywhere.
+// launch, and a bounded poll of the outbox's tag: no stream synchronisation anywhere.  pushCamera() is the same
+// on raw sensor frames (aof_bank_push_camera_device), with the auto-exposure controller
+// (aof_bank_exposure_control_device) between the tick and the collect launch: its commands land in pinned
+// memory in front of the tag.
 #include <cerrno>
 #include <chrono>
 #include <cstdio>
@@ -43,6 +46,15 @@ struct OpticalFlowBank::Impl {
 	uint8_t *outbox;   // pinned (aof_outbox_alloc_host): header, then n_streams entries
 	size_t outbox_bytes;
 	uint64_t tag;
+	// the sensor-frame form (enableCamera): sensor frames staged apart from the block above
+	bool camera;
+	aof_bank_camera cam;
+	aof_exposure_control ec;
+	size_t sensor_bytes;               // all n_streams sensor frames
+	uint8_t *h_sensor, *d_sensor;
+	aof_exposure_record *d_exposure;
+	aof_exposure_state *d_exposure_state;
+	aof_exposure_command *commands;    // pinned (aof_outbox_alloc_host): [n_streams]
 };
 
 OpticalFlowBank::OpticalFlowBank(float f_length_x, float f_length_y, int output_rate, int img_width, int img_height,
@@ -110,6 +122,11 @@ OpticalFlowBank::~OpticalFlowBank()
 	// a bounded wait, as everywhere: memory a kernel may still write is leaked, not freed
 	const bool drained = !m->stream || waitIdle();
 	if (drained) {
+		if (m->commands) aof_outbox_free_host(m->commands);
+		if (m->d_exposure_state) (void)hipFree(m->d_exposure_state);
+		if (m->d_exposure) (void)hipFree(m->d_exposure);
+		if (m->d_sensor) (void)hipFree(m->d_sensor);
+		if (m->h_sensor) (void)hipHostFree(m->h_sensor);
 		if (m->outbox) aof_outbox_free_host(m->outbox);
 		if (m->d_lens) (void)hipFree(m->d_lens);
 		if (m->d_mavlink) (void)hipFree(m->d_mavlink);
@@ -128,6 +145,13 @@ OpticalFlowBank::~OpticalFlowBank()
 int OpticalFlowBank::fail(int code, const char *what)
 {
 	_failed = true;
+	std::snprintf(_err, sizeof(_err), "%s", what);
+	return code;
+}
+
+// A refused call: lastError() says why, the object stays usable.
+int OpticalFlowBank::refuse(int code, const char *what)
+{
 	std::snprintf(_err, sizeof(_err), "%s", what);
 	return code;
 }
@@ -188,17 +212,99 @@ int OpticalFlowBank::push(const uint8_t *frames, const uint64_t *img_time_us, co
 				      gyro ? reinterpret_cast<const aof_gyro *>(m->d_stage + m->off_gyro) : NULL, m->d_bank,
 				      m->bank_bytes, m->d_records, m->d_mavlink, m->d_lens, m->stream);
 	if (rc) return fail(rc, aof_last_error(m->ctx));
+	return collect();
+}
+
+// The collect launch behind a tick and the bounded poll of its tag; returns the number of published entries.
+int OpticalFlowBank::collect()
+{
+	Impl *m = _m;
 	const uint64_t tag = ++m->tag;
-	rc = aof_bank_collect_device(m->ctx, n_streams, 1, m->d_records, m->d_mavlink, m->d_lens, NULL, NULL, (uint32_t)n_streams,
-				     0, m->outbox, m->outbox_bytes, tag, NULL, m->stream);
+	const int rc = aof_bank_collect_device(m->ctx, n_streams, 1, m->d_records, m->d_mavlink, m->d_lens, NULL, NULL,
+					       (uint32_t)n_streams, 0, m->outbox, m->outbox_bytes, tag, NULL, m->stream);
 	if (rc) return fail(rc, aof_last_error(m->ctx));
-	// the tag is the kernel's last store: once it is here, so are the counts and the entries
+	// the tag is the kernel's last store: once it is here, so are the counts and the entries (and what earlier
+	// launches on the stream released to the host: the exposure commands)
 	const uint64_t *word = reinterpret_cast<const uint64_t *>(m->outbox);
 	const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
 	while (__atomic_load_n(word, __ATOMIC_ACQUIRE) != tag) {
 		if (secondsSince(t0) > kDeadlineS) return fail(-ETIMEDOUT, "the tick did not finish within the deadline");
 	}
 	return (int)reinterpret_cast<const aof_outbox_header *>(m->outbox)->n_messages;
+}
+
+int OpticalFlowBank::enableCamera(int camera_width, int camera_height, uint16_t exposure0, uint8_t gain0,
+				  uint32_t exposure_interval_us)
+{
+	if (!engineOk()) return -1;
+	Impl *m = _m;
+	// a wrong argument is refused and leaves the object as it was
+	if (m->camera) return refuse(-EINVAL, "enableCamera() was already called");
+	if (!waitIdle()) return -ETIMEDOUT;
+	aof_params p;
+	if (aof_get_params(m->ctx, &p)) return fail(-EIO, aof_last_error(m->ctx));
+	std::memset(&m->cam, 0, sizeof(m->cam));
+	m->cam.ingest.camera_width = camera_width;
+	m->cam.ingest.camera_height = camera_height;
+	m->cam.ingest.crop_width = image_width;
+	m->cam.ingest.crop_height = image_height;
+	m->cam.exposure_interval_us = exposure_interval_us;
+	struct aof_bank_layout L;
+	size_t staging = 0;
+	if (camera_width < 1 || camera_height < 1 || aof_bank_camera_layout(&p, &m->bp, &m->cam, &L, &staging))
+		return refuse(-EINVAL, "enableCamera(): the sensor frame cannot hold the image size");
+	const size_t S = (size_t)n_streams;
+	m->sensor_bytes = S * (size_t)camera_width * (size_t)camera_height;
+	aof_exposure_control_default(&m->ec);
+	void *bank = NULL;
+	const bool ok = hipMalloc(&bank, L.total_bytes) == hipSuccess &&
+			hipHostMalloc((void **)&m->h_sensor, m->sensor_bytes, hipHostMallocDefault) == hipSuccess &&
+			hipMalloc((void **)&m->d_sensor, m->sensor_bytes) == hipSuccess &&
+			hipMalloc((void **)&m->d_exposure, S * sizeof(aof_exposure_record)) == hipSuccess &&
+			hipMalloc((void **)&m->d_exposure_state, S * sizeof(aof_exposure_state)) == hipSuccess &&
+			aof_outbox_alloc_host(S * sizeof(aof_exposure_command), (void **)&m->commands) == 0;
+	if (bank) {   // the bank grows by the staging region of the composed path; the stream is idle
+		(void)hipFree(m->d_bank);
+		m->d_bank = bank;
+		m->bank_bytes = L.total_bytes;
+	}
+	if (!ok) return fail(-ENOMEM, "device or pinned memory for the sensor frames could not be allocated");
+	std::memset(m->commands, 0, S * sizeof(aof_exposure_command));
+	if (aof_bank_reset_device(m->ctx, &m->bp, NULL, m->d_bank, m->bank_bytes, m->stream) ||
+	    aof_bank_exposure_reset_device(m->ctx, n_streams, NULL, exposure0, gain0, NULL, NULL, m->d_exposure_state, m->stream))
+		return fail(-EIO, aof_last_error(m->ctx));
+	if (!waitIdle()) return -ETIMEDOUT;
+	m->camera = true;
+	return 0;
+}
+
+const aof_exposure_command *OpticalFlowBank::exposureCommands() const { return _m && _m->camera ? _m->commands : NULL; }
+
+int OpticalFlowBank::pushCamera(const uint8_t *sensor_frames, const uint64_t *img_time_us, const uint8_t *active,
+				const aof_gyro *gyro)
+{
+	if (!engineOk()) return -1;
+	if (!sensor_frames || !img_time_us || !_m->camera) return -EINVAL;
+	Impl *m = _m;
+	const size_t S = (size_t)n_streams;
+	std::memcpy(m->h_sensor, sensor_frames, m->sensor_bytes);
+	std::memcpy(m->h_stage + m->off_times, img_time_us, S * sizeof(uint64_t));
+	if (gyro) std::memcpy(m->h_stage + m->off_gyro, gyro, S * sizeof(aof_gyro));
+	if (active) std::memcpy(m->h_stage + m->off_active, active, S);
+	if (hipMemcpyAsync(m->d_sensor, m->h_sensor, m->sensor_bytes, hipMemcpyHostToDevice, m->stream) != hipSuccess ||
+	    hipMemcpyAsync(m->d_stage + m->off_times, m->h_stage + m->off_times, m->stage_bytes - m->off_times,
+			   hipMemcpyHostToDevice, m->stream) != hipSuccess)
+		return fail(-EIO, "copy of the tick's sensor frames failed");
+	int rc = aof_bank_push_camera_device(m->ctx, &m->bp, &m->cam, m->d_sensor,
+					     reinterpret_cast<const uint64_t *>(m->d_stage + m->off_times),
+					     active ? m->d_stage + m->off_active : NULL,
+					     gyro ? reinterpret_cast<const aof_gyro *>(m->d_stage + m->off_gyro) : NULL, m->d_bank,
+					     m->bank_bytes, m->d_records, m->d_exposure, NULL, m->d_mavlink, m->d_lens, m->stream);
+	if (rc) return fail(rc, aof_last_error(m->ctx));
+	rc = aof_bank_exposure_control_device(m->ctx, &m->ec, n_streams, 1, m->d_exposure, m->d_exposure_state, m->commands,
+					      m->stream);
+	if (rc) return fail(rc, aof_last_error(m->ctx));
+	return collect();
 }
 
 int OpticalFlowBank::reset(const uint8_t *mask)

@@ -643,6 +643,80 @@ int aof_bank_collect_device(aof_ctx *ctx, int32_t n_streams, int32_t n_rounds, c
 int aof_outbox_alloc_host(size_t bytes, void **out);
 int aof_outbox_free_host(void *p);
 
+/* ---- the stream bank's auto-exposure control: the PID step per stream behind a camera push ----
+ * The second half of the reference's _exposure_update (mainloop.cpp:222-271): a PID controller turns the mean sample
+ * value of a frame that passed the exposure gate into new exposure and gain values and decides whether the camera is
+ * told about them.  aof_bank_exposure_control_device, enqueued behind a camera push (K = 1) or a camera burst, reads
+ * `due` and `msv` of the push's [K][S] exposure records, steps one aof_exposure_state per stream and writes one
+ * aof_exposure_command per stream and round.  The state array is the caller's device memory and no part of the bank.
+ * One step per record with due != 0, in increasing round, per stream; all arithmetic IEEE float32, nothing fused:
+ *     err = msv_target - msv;   d = err - msv_error_old;   msv_error_int += err
+ *     ce = (float)exposure;     cg = (float)gain
+ *     e  = ce + ((exposure_p*err + exposure_i*msv_error_int) + exposure_d*d)
+ *     if cg > 1 or (e > exposure_max-1 and ce > exposure_max-1):              the gain branch
+ *         g = cg + ((gain_p*err + gain_i*msv_error_int) + gain_d*d);  g > gain_max: g = gain_max, else g < 1: g = 1
+ *         if |g - cg| > gain_change_threshold or (g < 2 and cg > 1) or (g > gain_max-1 and cg < gain_max):
+ *             gain = (uint8_t)g;  flags |= AOF_EXPOSURE_SET_GAIN
+ *     else:                                                                   the exposure branch
+ *         e > exposure_max: e = exposure_max, else e < 1: e = 1
+ *         if |e - ce| > exposure_change_threshold or (e < 2 and ce > 1) or (e > exposure_max-1 and ce < exposure_max):
+ *             exposure = (uint16_t)e;  flags |= AOF_EXPOSURE_SET_EXPOSURE
+ *     msv_error_old = err;  updates += 1;  flags |= AOF_EXPOSURE_UPDATED
+ * This is the reference with its quirks: the integral has no anti-windup, the gain branch never touches the exposure,
+ * the controller restarts from the integer the camera holds (fractions are carried by the integral only), and a NaN
+ * sets nothing (every comparison with it is false).  The msv values are specified as finite. */
+typedef struct aof_exposure_control {   /* the constants of mainloop.cpp:53-63 */
+    float msv_target;                                   /* 5 */
+    float exposure_p, exposure_i, exposure_d;           /* 100, 0.5, 0.5 */
+    float gain_p, gain_i, gain_d;                       /* 50, 0.5, 0.5 */
+    float exposure_change_threshold, exposure_max;      /* 30, 1727 */
+    float gain_change_threshold, gain_max;              /* 15, 127 */
+} aof_exposure_control;
+/* -EINVAL: NULL ec.  Host only. */
+int aof_exposure_control_default(aof_exposure_control *ec);
+
+typedef struct aof_exposure_state {     /* 16 bytes, one per stream, caller-owned device memory */
+    float msv_error_old, msv_error_int;
+    uint16_t exposure;                  /* what the camera is running with: the last value commanded */
+    uint8_t gain, reserved;             /* likewise; reserved = 0 */
+    uint32_t updates;                   /* controller steps so far */
+} aof_exposure_state;
+
+#define AOF_EXPOSURE_UPDATED      1u    /* the record was due: the controller stepped */
+#define AOF_EXPOSURE_SET_EXPOSURE 2u    /* tell the camera `exposure` (mainloop.cpp:266) */
+#define AOF_EXPOSURE_SET_GAIN     4u    /* tell the camera `gain` (mainloop.cpp:249) */
+typedef struct aof_exposure_command {   /* 16 bytes, one per stream and round */
+    uint16_t exposure; uint8_t gain; uint8_t flags;   /* state values behind this step */
+    float msv_error, msv_error_int;                    /* behind this step */
+    uint32_t update;                                   /* the state's `updates` behind this step */
+} aof_exposure_command;                 /* all zero for a record that was not due */
+
+/* Masked streams (d_mask: u8 [S], or NULL = all) start over: both errors 0, updates 0, reserved 0, exposure and gain
+ * from d_exposure0 (u16 [S]) / d_gain0 (u8 [S]) where given, else from the scalars.  The layout of the state is
+ * public: a host whose camera refused a value may also overwrite a state record directly.
+ * -EINVAL: NULL ctx or state, n_streams < 1, a state array that is not 4-byte aligned, d_exposure0 not 2-byte aligned;
+ * -EIO: the context's sticky fault.  Only enqueues. */
+int aof_bank_exposure_reset_device(aof_ctx *ctx, int32_t n_streams, const uint8_t *d_mask, uint16_t exposure0,
+                                   uint8_t gain0, const uint16_t *d_exposure0, const uint8_t *d_gain0,
+                                   aof_exposure_state *d_state, void *stream);
+/* d_exposure: aof_exposure_record [n_rounds][n_streams], exactly what a camera push (n_rounds = 1) or a camera burst
+ * wrote; only `due` and `msv` of each record are read.  d_state: [n_streams], updated in place.  d_commands:
+ * aof_exposure_command [n_rounds][n_streams]; every element is written.  The kernel ends with a system-scope release
+ * behind its stores: a host that has seen the tag of an aof_bank_collect_device enqueued behind it on the same stream
+ * may read commands kept in aof_outbox_alloc_host memory without a synchronise.
+ * -EINVAL: NULL ctx, ec, records, state or commands; n_streams < 1; n_rounds outside 1..AOF_BANK_BURST_MAX; pointers
+ * that are not 4-byte aligned; a non-finite constant, exposure_max outside 1..65535, gain_max outside 1..255; -EIO:
+ * the context's sticky fault.  A refused call writes nothing.  One launch; only enqueues: no allocation, no host
+ * synchronisation, capturable. */
+int aof_bank_exposure_control_device(aof_ctx *ctx, const aof_exposure_control *ec, int32_t n_streams, int32_t n_rounds,
+                                     const aof_exposure_record *d_exposure, aof_exposure_state *d_state,
+                                     aof_exposure_command *d_commands, void *stream);
+/* The same function on host memory, a plain loop: no device, no context (single-camera users of OpticalFlowOpenCV,
+ * and the check of the device's bytes).  -EINVAL: a NULL pointer, the counts and constants refused above. */
+int aof_exposure_control_host(const aof_exposure_control *ec, int32_t n_streams, int32_t n_rounds,
+                              const aof_exposure_record *records, aof_exposure_state *states,
+                              aof_exposure_command *commands);
+
 /* ---- measurement ----
  * With profiling on, every launch is bracketed by HIP events on the stream it
  * is launched on; the last AOF_PROFILE_RING launches of each kernel are kept.

@@ -25,13 +25,21 @@ With --outbox, what it costs and gains to collect the published messages of a pu
                 pinned memory + stream synchronise + np.flatnonzero(quality >= 0) -- the yardstick of O;
   O             tick + collect into a HostOutbox + polling the tag.
 H and O are timed per tick from the enqueue to the host holding the list; one line with bursts of K = 5 rounds.
+With --exposure-control, the auto-exposure controller behind the camera push (320x240 -> PX4 64x64; K = 1: the camera
+tick, K = 5: the camera burst; statistics at 200 000 us, frames 13 333 us apart):
+  T             the camera push alone, pipelined;
+  C             camera push + aof_bank_exposure_control_device, pipelined: C - T prices the extra launch;
+  H             what a host did before: camera push + one asynchronous device-to-host copy of the exposure records into
+                pinned memory + stream synchronise + aof_exposure_control_host on host states: every step ends with the
+                host holding the commands.
 Every leg settles for about 0.2 s of untimed ticks, then times at least --ticks ticks and at least --seconds seconds
 with the host clock around ticks that end in a synchronise.  The whole sweep runs --repeats times: the difference
 between the repeats is the run-to-run spread a difference between legs has to beat.
     python tools/bench_bank.py [--streams 1,16,...] [--configs px4-64,opencv-128] > profiles/bank_tick_sweep.txt
     python tools/bench_bank.py --camera > profiles/bank_camera_tick_sweep.txt
     python tools/bench_bank.py --burst 2,5,16 > profiles/bank_burst_sweep.txt
-    python tools/bench_bank.py --outbox > profiles/bank_outbox_sweep.txt"""
+    python tools/bench_bank.py --outbox > profiles/bank_outbox_sweep.txt
+    python tools/bench_bank.py --exposure-control > profiles/bank_exposure_control_sweep.txt"""
 import argparse
 import ctypes as C
 import importlib
@@ -553,6 +561,107 @@ def outbox_sweep(a, dev):
               f"O below H by {gain * 100:5.1f} % ({'more' if gain > sp['O'] + sp['H'] else 'NOT more'} than the legs' spread)  H/O {m['H'] / m['O']:5.2f}")
 
 
+def leg_exposure(p, S, K, leg, inp, dev, a, sensor):
+    """One of T / C / H on K rounds of sensor frames per step.  Returns (seconds per step, rounds timed, controller
+    steps per stream at the end)."""
+    eng = aof.FlowEngine(p, 0)
+    bp = aof.bank_params(S, FX, FY, 15, 5_000_000, 1, 100, 0)
+    cam = aof.bank_camera_params(sensor[0], sensor[1], p.width, p.height, 0, 200_000, None, FX, FY)
+    bank = eng.bank_create(bp, dev, camera=cam)
+    n = K * S
+    recs = torch.empty((K, S, 48), dtype=torch.uint8, device=dev)
+    expo = torch.empty((K, S, 48), dtype=torch.uint8, device=dev)
+    wire = torch.empty((K, S, 56), dtype=torch.uint8, device=dev)
+    lens = torch.empty((K, S), dtype=torch.uint8, device=dev)
+    times = inp.times0.clone()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    ctx, burst, ec = eng._ctx, aof.bank_burst_params(K), aof.exposure_control_default()
+    tail = (inp.frames.data_ptr(), times.data_ptr(), None, inp.gyro.data_ptr(), bank.buffer.data_ptr(), bank.buffer.numel(),
+            recs.data_ptr(), expo.data_ptr(), None, wire.data_ptr(), lens.data_ptr(), stream)
+    if K == 1:
+        push, head = aof.lib.aof_bank_push_camera_device, (ctx, C.byref(bp), C.byref(cam))
+    else:
+        push, head = aof.lib.aof_bank_push_camera_burst_device, (ctx, C.byref(bp), C.byref(cam), C.byref(burst))
+
+    def tick():
+        times.add_(13333 * K)                                   # the clocks run on: the gate opens every 15 rounds
+        rc = push(*head, *tail)
+        if rc:
+            raise aof.AofError(rc, aof.lib.aof_last_error(ctx).decode())
+
+    if leg == "T":
+        out = timed_bursts(tick, torch.cuda.synchronize, K, a.ticks, a.seconds, a.settle)
+        updates = float("nan")
+    elif leg == "C":
+        state = torch.zeros((S, 16), dtype=torch.uint8, device=dev)
+        eng.bank_exposure_reset(state, exposure0=400, gain0=1)
+        commands = torch.empty((K, S, 16), dtype=torch.uint8, device=dev)
+        control = aof.lib.aof_bank_exposure_control_device
+        cargs = (ctx, C.byref(ec), S, K, expo.data_ptr(), state.data_ptr(), commands.data_ptr(), stream)
+
+        def step():
+            tick()
+            rc = control(*cargs)
+            if rc:
+                raise aof.AofError(rc, aof.lib.aof_last_error(ctx).decode())
+        out = timed_bursts(step, torch.cuda.synchronize, K, a.ticks, a.seconds, a.settle)
+        updates = float(aof.exposure_states_view(state)["updates"].mean())
+    else:
+        hip = hip_runtime()
+        h_expo = torch.empty((n, 48), dtype=torch.uint8, pin_memory=True)
+        states = np.zeros(S, aof.EXPOSURE_STATE_DTYPE)
+        states["exposure"], states["gain"] = 400, 1
+        commands = np.empty(n, aof.EXPOSURE_COMMAND_DTYPE)
+        host = aof.lib.aof_exposure_control_host
+        hargs = (C.byref(ec), S, K, h_expo.data_ptr(), states.ctypes.data, commands.ctypes.data)
+        copy = (h_expo.data_ptr(), expo.data_ptr(), expo.numel(), 2, stream)       # hipMemcpyDeviceToHost
+
+        def step():
+            tick()
+            if hip.hipMemcpyAsync(*copy):
+                raise RuntimeError("hipMemcpyAsync failed")
+            if hip.hipStreamSynchronize(stream):
+                raise RuntimeError("hipStreamSynchronize failed")
+            if host(*hargs):
+                raise RuntimeError("aof_exposure_control_host failed")
+        out = timed_bursts(step, lambda: None, K, a.ticks, a.seconds, a.settle)
+        updates = float(states["updates"].mean())
+    torch.cuda.synchronize()
+    r = aof.ticks_view(recs[K - 1])
+    assert (r["quality"] >= aof.TICK_HELD).all() and (r["frame"] > a.ticks).all(), "the timed rounds were real ticks"
+    eng.close()
+    return out[0], out[1], updates
+
+
+def exposure_sweep(a, dev):
+    print("# legs: T camera push alone (pipelined), C camera push + aof_bank_exposure_control_device (pipelined), H camera push + "
+          "async D2H copy of the exposure records into pinned memory + stream synchronise + aof_exposure_control_host")
+    print("# us = microseconds per step (a camera tick, or a camera burst of K rounds) of 320x240 -> 64x64 streams; T and C: host "
+          "clock around chunks of steps ending in a synchronise; H: every step ends with the host holding the commands; "
+          "upd = controller steps per stream when the leg ended")
+    p, sensor = params_of("px4-64"), (320, 240)
+    cases = [(K, S) for K in (1, 5) for S in (int(s) for s in a.streams.split(","))]
+    results, upd = {}, {}
+    for rep in range(a.repeats):
+        for K, S in cases:
+            inp = BurstInputs(p, S, K, dev, sensor=sensor)
+            for leg in ("T", "C", "H"):
+                sec, n, u = leg_exposure(p, S, K, leg, inp, dev, a, sensor)
+                results.setdefault((K, S, leg), []).append(sec)
+                upd[(K, S, leg)] = u
+                print(f"rep {rep} px4-64 K={K:2d} S={S:6d} {leg} {sec * 1e6:10.2f} us  ({n} rounds, upd {u:7.1f})", flush=True)
+            del inp
+            torch.cuda.empty_cache()
+    print("# ---- summary (mean of the repeats; spread = |difference of the repeats| / mean) ----")
+    for K, S in cases:
+        m = {leg: float(np.mean(results[(K, S, leg)])) for leg in "TCH"}
+        sp = {leg: abs(results[(K, S, leg)][0] - results[(K, S, leg)][-1]) / m[leg] for leg in "TCH"}
+        gain = (m["H"] - m["C"]) / m["H"]
+        print(f"px4-64 K={K:2d} S={S:6d}  " + "  ".join(f"{leg} {m[leg] * 1e6:9.2f} (+-{sp[leg] * 100:4.1f} %)" for leg in "TCH") +
+              f"  C-T {(m['C'] - m['T']) * 1e6:7.2f} us  C below H by {gain * 100:5.1f} % "
+              f"({'more' if gain > sp['C'] + sp['H'] else 'NOT more'} than the legs' spread)  H/C {m['H'] / m['C']:5.2f}")
+
+
 def leg_contexts(p, S, inp, a):
     engs = [aof.FlowEngine(p, 0) for _ in range(S)]
     flow = np.zeros(1, aof.FLOW_DTYPE)
@@ -621,6 +730,7 @@ def main():
     ap.add_argument("--camera", action="store_true", help="the sweep of the tick on raw sensor frames (legs K0, K1, K2, Y, T0)")
     ap.add_argument("--burst", default="", help="K[,K...]: the sweep of bursts of K rounds against K single ticks (legs B0-B2, T0-T2)")
     ap.add_argument("--outbox", action="store_true", help="the sweep of the outbox: legs T, D, H, O")
+    ap.add_argument("--exposure-control", action="store_true", help="the sweep of the auto-exposure controller: legs T, C, H")
     ap.add_argument("--forms", default="plain,camera", help="--burst: entry points to sweep")
     ap.add_argument("--input-bytes-max", type=float, default=24 * 2**30, help="--burst: sizes whose K rounds of input exceed this are skipped")
     a = ap.parse_args()
@@ -628,6 +738,8 @@ def main():
         a.ticks = 1000           # (frame rounds)
     if a.camera and a.streams == ap.get_default("streams"):
         a.streams = "1,64,1024,1536,2048,4096"
+    if a.exposure_control and a.streams == ap.get_default("streams"):
+        a.streams = "64,1024,4096"
     if a.outbox and a.streams == ap.get_default("streams"):
         a.streams = "64,256,1024,4096,16384"
     if not torch.cuda.is_available():
@@ -637,6 +749,8 @@ def main():
     print(f"# device: {torch.cuda.get_device_name(0)}")
     if not a.no_marker:
         print(f"# class marker: exhaustive C2 K2 (1 024 VGA pairs) {class_marker(dev):.4f} ms")
+    if a.exposure_control:
+        return exposure_sweep(a, dev)
     if a.outbox:
         return outbox_sweep(a, dev)
     if a.burst:
