@@ -792,30 +792,58 @@ class FlowEngine:
         self._check(lib.aof_bank_reset_device(self._ctx, C.byref(bank.bp), mask.data_ptr() if mask is not None else None,
                                               buf.data_ptr(), buf.numel(), torch.cuda.current_stream(buf.device).cuda_stream))
 
+    def _bank_push(self, bank, src, times, select, gyro, mavlink, records, out_frames, out_lengths, n_rounds=None,
+                   round_stride=0, camera=False, exposure=None, derotated=None, want_exposure=True):
+        """The one push behind bank_push, bank_push_camera, bank_push_burst and bank_push_camera_burst: the assertions,
+        the outputs (with a leading [K] for a burst: n_rounds is not None) and the one call into the library.  select:
+        `active` of a tick, `count` of a burst.  Returns every output tensor (None where not written)."""
+        import torch
+        S, buf, cam = bank.n_streams, bank.buffer, bank.camera
+        burst = n_rounds is not None
+        lead = (int(n_rounds), S) if burst else (S,)
+        n = int(n_rounds) * S if burst else S
+        dev = buf.device
+        if camera:
+            assert cam is not None, "bank_create(..., camera=...) makes a bank for sensor frames"
+        assert src.dtype == torch.uint8 and (camera or src.is_contiguous())
+        assert times.dtype == torch.int64 and times.numel() == n and (not burst or times.is_contiguous())
+        if burst:
+            assert select is None or (select.dtype == torch.uint8 and select.numel() == S)
+            assert gyro is None or gyro.numel() == n * 4
+        if records is None:
+            records = torch.empty(lead + (48,), dtype=torch.uint8, device=dev)
+        if camera and exposure is None and want_exposure:
+            exposure = torch.empty(lead + (48,), dtype=torch.uint8, device=dev)
+        if camera and derotated is None and cam.derotate:
+            derotated = torch.empty(lead + (2,), dtype=torch.float32, device=dev)
+        if mavlink:
+            if out_frames is None:
+                out_frames = torch.zeros(lead + (SEQ_FRAME_BYTES,), dtype=torch.uint8, device=dev)
+            if out_lengths is None:
+                out_lengths = torch.zeros(lead, dtype=torch.uint8, device=dev)
+        else:
+            out_frames = out_lengths = None
+        opt = lambda t: t.data_ptr() if t is not None else None
+        fn = getattr(lib, "aof_bank_push" + ("_camera" if camera else "") + ("_burst" if burst else "") + "_device")
+        args = [self._ctx, C.byref(bank.bp)]
+        if camera:
+            args.append(C.byref(cam))
+        if burst:
+            args.append(C.byref(bank_burst_params(int(n_rounds), round_stride)))
+        args += [src.data_ptr(), times.data_ptr(), opt(select), opt(gyro), buf.data_ptr(), buf.numel(), records.data_ptr()]
+        if camera:
+            args += [opt(exposure), opt(derotated)]
+        self._check(fn(*args, opt(out_frames), opt(out_lengths), torch.cuda.current_stream(dev).cuda_stream))
+        return dict(records=records, exposure=exposure, derotated=derotated, frames=out_frames, lengths=out_lengths)
+
     def bank_push(self, bank: "Bank", frames, times, active=None, gyro=None, mavlink=False, records=None, out_frames=None,
                   out_lengths=None):
         """aof_bank_push_device, one tick: frames uint8 CUDA tensor [S, H, W] (stream s at s * frame_stride bytes);
         times int64 CUDA tensor [S] (microseconds); active uint8 [S] or None (all); gyro float32 [S, 4] or None.
         Everything is enqueued on torch's current stream.  Returns the record tensor [S, 48] (read it with
         ticks_view()), and with mavlink=True (records, frames [S, 56], lengths [S])."""
-        import torch
-        S, buf = bank.n_streams, bank.buffer
-        dev = buf.device
-        assert frames.dtype == torch.uint8 and frames.is_contiguous()
-        assert times.dtype == torch.int64 and times.numel() == S
-        if records is None:
-            records = torch.empty((S, 48), dtype=torch.uint8, device=dev)
-        if mavlink:
-            if out_frames is None:
-                out_frames = torch.zeros((S, SEQ_FRAME_BYTES), dtype=torch.uint8, device=dev)
-            if out_lengths is None:
-                out_lengths = torch.zeros(S, dtype=torch.uint8, device=dev)
-        self._check(lib.aof_bank_push_device(
-            self._ctx, C.byref(bank.bp), frames.data_ptr(), times.data_ptr(), active.data_ptr() if active is not None else None,
-            gyro.data_ptr() if gyro is not None else None, buf.data_ptr(), buf.numel(), records.data_ptr(),
-            out_frames.data_ptr() if mavlink else None, out_lengths.data_ptr() if mavlink else None,
-            torch.cuda.current_stream(dev).cuda_stream))
-        return (records, out_frames, out_lengths) if mavlink else records
+        out = self._bank_push(bank, frames, times, active, gyro, mavlink, records, out_frames, out_lengths)
+        return (out["records"], out["frames"], out["lengths"]) if mavlink else out["records"]
 
     def bank_push_camera(self, bank: "Bank", camera, times, active=None, gyro=None, mavlink=False, records=None,
                          exposure=None, derotated=None, out_frames=None, out_lengths=None, want_exposure=True):
@@ -824,30 +852,8 @@ class FlowEngine:
         exposure_view()), allocated unless want_exposure is False (then no statistics, the gate does not move);
         derotated: float32 [S, 2], allocated when the bank's camera parameters ask for de-rotation.  Returns a dict of
         the output tensors: records, exposure, derotated, frames, lengths (None where not written)."""
-        import torch
-        S, buf, cam = bank.n_streams, bank.buffer, bank.camera
-        assert cam is not None, "bank_create(..., camera=...) makes a bank for sensor frames"
-        dev = buf.device
-        assert camera.dtype == torch.uint8 and times.dtype == torch.int64 and times.numel() == S
-        if records is None:
-            records = torch.empty((S, 48), dtype=torch.uint8, device=dev)
-        if exposure is None and want_exposure:
-            exposure = torch.empty((S, 48), dtype=torch.uint8, device=dev)
-        if derotated is None and cam.derotate:
-            derotated = torch.empty((S, 2), dtype=torch.float32, device=dev)
-        if mavlink:
-            if out_frames is None:
-                out_frames = torch.zeros((S, SEQ_FRAME_BYTES), dtype=torch.uint8, device=dev)
-            if out_lengths is None:
-                out_lengths = torch.zeros(S, dtype=torch.uint8, device=dev)
-        self._check(lib.aof_bank_push_camera_device(
-            self._ctx, C.byref(bank.bp), C.byref(cam), camera.data_ptr(), times.data_ptr(),
-            active.data_ptr() if active is not None else None, gyro.data_ptr() if gyro is not None else None,
-            buf.data_ptr(), buf.numel(), records.data_ptr(), exposure.data_ptr() if exposure is not None else None,
-            derotated.data_ptr() if derotated is not None else None, out_frames.data_ptr() if mavlink else None,
-            out_lengths.data_ptr() if mavlink else None, torch.cuda.current_stream(dev).cuda_stream))
-        return dict(records=records, exposure=exposure, derotated=derotated, frames=out_frames if mavlink else None,
-                    lengths=out_lengths if mavlink else None)
+        return self._bank_push(bank, camera, times, active, gyro, mavlink, records, out_frames, out_lengths, camera=True,
+                               exposure=exposure, derotated=derotated, want_exposure=want_exposure)
 
     def bank_push_burst(self, bank: "Bank", n_rounds, frames, times, count=None, gyro=None, mavlink=False, records=None,
                         out_frames=None, out_lengths=None, round_stride=0):
@@ -856,27 +862,8 @@ class FlowEngine:
         [K, S]; count uint8 [S] (stream s has frames in rounds 0..count[s]-1) or None (all K); gyro float32 [K, S, 4] or
         None.  Returns the record tensor [K, S, 48] (ticks_view() of round k: records[k]), and with mavlink=True
         (records, frames [K, S, 56], lengths [K, S])."""
-        import torch
-        K, S, buf = int(n_rounds), bank.n_streams, bank.buffer
-        dev = buf.device
-        assert frames.dtype == torch.uint8 and frames.is_contiguous()
-        assert times.dtype == torch.int64 and times.numel() == K * S and times.is_contiguous()
-        assert count is None or (count.dtype == torch.uint8 and count.numel() == S)
-        assert gyro is None or gyro.numel() == K * S * 4
-        if records is None:
-            records = torch.empty((K, S, 48), dtype=torch.uint8, device=dev)
-        if mavlink:
-            if out_frames is None:
-                out_frames = torch.zeros((K, S, SEQ_FRAME_BYTES), dtype=torch.uint8, device=dev)
-            if out_lengths is None:
-                out_lengths = torch.zeros((K, S), dtype=torch.uint8, device=dev)
-        burst = bank_burst_params(K, round_stride)
-        self._check(lib.aof_bank_push_burst_device(
-            self._ctx, C.byref(bank.bp), C.byref(burst), frames.data_ptr(), times.data_ptr(),
-            count.data_ptr() if count is not None else None, gyro.data_ptr() if gyro is not None else None, buf.data_ptr(),
-            buf.numel(), records.data_ptr(), out_frames.data_ptr() if mavlink else None,
-            out_lengths.data_ptr() if mavlink else None, torch.cuda.current_stream(dev).cuda_stream))
-        return (records, out_frames, out_lengths) if mavlink else records
+        out = self._bank_push(bank, frames, times, count, gyro, mavlink, records, out_frames, out_lengths, n_rounds, round_stride)
+        return (out["records"], out["frames"], out["lengths"]) if mavlink else out["records"]
 
     def bank_push_camera_burst(self, bank: "Bank", n_rounds, camera, times, count=None, gyro=None, mavlink=False,
                                records=None, exposure=None, derotated=None, out_frames=None, out_lengths=None,
@@ -885,33 +872,8 @@ class FlowEngine:
         tensor, stream s's sensor frame of round k at k * round_stride + s * camera_stride bytes; the rest as
         bank_push_burst and bank_push_camera, every output with a leading [K].  Returns a dict of the output tensors:
         records, exposure, derotated, frames, lengths (None where not written)."""
-        import torch
-        K, S, buf, cam = int(n_rounds), bank.n_streams, bank.buffer, bank.camera
-        assert cam is not None, "bank_create(..., camera=...) makes a bank for sensor frames"
-        dev = buf.device
-        assert camera.dtype == torch.uint8 and times.dtype == torch.int64 and times.numel() == K * S and times.is_contiguous()
-        assert count is None or (count.dtype == torch.uint8 and count.numel() == S)
-        assert gyro is None or gyro.numel() == K * S * 4
-        if records is None:
-            records = torch.empty((K, S, 48), dtype=torch.uint8, device=dev)
-        if exposure is None and want_exposure:
-            exposure = torch.empty((K, S, 48), dtype=torch.uint8, device=dev)
-        if derotated is None and cam.derotate:
-            derotated = torch.empty((K, S, 2), dtype=torch.float32, device=dev)
-        if mavlink:
-            if out_frames is None:
-                out_frames = torch.zeros((K, S, SEQ_FRAME_BYTES), dtype=torch.uint8, device=dev)
-            if out_lengths is None:
-                out_lengths = torch.zeros((K, S), dtype=torch.uint8, device=dev)
-        burst = bank_burst_params(K, round_stride)
-        self._check(lib.aof_bank_push_camera_burst_device(
-            self._ctx, C.byref(bank.bp), C.byref(cam), C.byref(burst), camera.data_ptr(), times.data_ptr(),
-            count.data_ptr() if count is not None else None, gyro.data_ptr() if gyro is not None else None,
-            buf.data_ptr(), buf.numel(), records.data_ptr(), exposure.data_ptr() if exposure is not None else None,
-            derotated.data_ptr() if derotated is not None else None, out_frames.data_ptr() if mavlink else None,
-            out_lengths.data_ptr() if mavlink else None, torch.cuda.current_stream(dev).cuda_stream))
-        return dict(records=records, exposure=exposure, derotated=derotated, frames=out_frames if mavlink else None,
-                    lengths=out_lengths if mavlink else None)
+        return self._bank_push(bank, camera, times, count, gyro, mavlink, records, out_frames, out_lengths, n_rounds,
+                               round_stride, camera=True, exposure=exposure, derotated=derotated, want_exposure=want_exposure)
 
     def bank_collect(self, records, mavlink=None, lengths=None, exposure=None, derotated=None, capacity_messages=None,
                      capacity_exposures=0, outbox=None, tag=1, tag_tensor=None):

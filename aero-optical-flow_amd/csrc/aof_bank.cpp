@@ -1,7 +1,9 @@
 // The stream bank (include/aof.h, "a bank of live streams"): S live streams per tick from one device launch.  Host
-// side only: argument checks, the layout, the path choice and the launches of k_bank.hip -- the one-launch tick
-// kernel, or aof_flow_batch_device's own plan on (bank frames, tick frames) followed by the commit kernel.  Nothing
-// here allocates or synchronises.
+// side only: the layout and ONE push path (bank_push) behind the four push entry points -- pre-cropped or sensor
+// frames, one tick or a burst of K rounds: the argument checks, the path choice and the launches of k_bank.hip /
+// k_bank_burst.hip -- the one-launch kernel, or per round (the ingest kernel,) aof_flow_batch_device's own plan on
+// (bank frames, new frames) and the commit kernel.  An entry point only packs its arguments.  Nothing here allocates
+// or synchronises.
 #include <cerrno>
 #include <cstring>
 
@@ -46,6 +48,9 @@ constexpr int32_t kBankBurstFusedMaxStreams = 1024;
 // 503.6 / 471.5.)  The small frames cross between 1 536 and 2 048 streams at every K; the two-level configuration
 // gives up 9 % at 2 048 for it.
 constexpr int32_t kBankCameraBurstFusedMaxStreams = 1536;
+// The four by form: [sensor frames][burst].
+constexpr int32_t kFusedMaxStreams[2][2] = {{kBankFusedMaxStreams, kBankBurstFusedMaxStreams},
+                                            {kBankCameraFusedMaxStreams, kBankCameraBurstFusedMaxStreams}};
 
 struct Layout {
     struct aof_bank_layout pub;
@@ -212,6 +217,88 @@ BankArgs round_args(const BankArgs &a, int k, const uint8_t *frames)
     return r;
 }
 
+// What the four push entry points differ in.  `camera` / `burst` name the form; the form's own parameter block may
+// still be NULL and is refused where the order of the checks has it.
+struct Push {
+    bool camera, burst;                  // sensor frames (else pre-cropped frames); K rounds (else one tick)
+    const aof_bank_camera *cam;          // camera forms
+    const aof_bank_burst *rounds;        // burst forms
+    const uint8_t *src;                  // the caller's frames: pre-cropped or sensor frames, round 0
+    const uint64_t *time_us;
+    const uint8_t *select;               // per stream: d_active of a tick, d_count of a burst (or NULL: every stream, every round)
+    const aof_gyro *gyro;
+    aof_tick_record *records;
+    aof_exposure_record *exposure;       // camera forms, optional
+    float *derotated;                    // camera forms, needed iff cam->derotate
+    uint8_t *mavlink, *mavlink_len;
+};
+
+// The one push path behind aof_bank_push_device, _camera_device, _burst_device and _camera_burst_device: the checks in
+// their order, the kernels' arguments, the path choice and the launches.  A tick is a burst of one round that keeps its
+// `active` mask and has no `count`.
+int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank_bytes, const Push &p, void *stream)
+{
+    Layout L;
+    int rc = check_bank(ctx, bp, d_bank, bank_bytes, &L, p.cam, p.camera);
+    if (rc) return rc;
+    int64_t round_stride = 0;
+    if (p.burst) {
+        // one round: S pre-cropped frames frame_stride apart (16-byte chunks), or S sensor frames camera_stride apart (any byte)
+        int64_t frame = L.stride;
+        if (p.camera) frame = p.cam->camera_stride ? p.cam->camera_stride : (int64_t)p.cam->ingest.camera_width * p.cam->ingest.camera_height;
+        if ((rc = check_burst(ctx, p.rounds, (int64_t)bp->n_streams * frame, p.camera, &round_stride))) return rc;
+    }
+    if ((rc = check_tick(ctx, p.src, p.time_us, p.gyro, p.records, p.mavlink, p.mavlink_len))) return rc;
+    if (p.camera) {
+        if (p.cam->derotate && !p.derotated) return ctx_fail(ctx, -EINVAL, "bank camera: derotate needs d_derotated");
+        if (reinterpret_cast<uintptr_t>(p.exposure) % 4 || reinterpret_cast<uintptr_t>(p.derotated) % 4)
+            return ctx_fail(ctx, -EINVAL, "bank camera: exposure records and de-rotated pairs must be 4-byte aligned");
+    }
+    // before the first launch: a faulted or wedged context, or a thread on another device, must not touch the bank
+    if ((rc = precheck(ctx))) return rc;
+
+    uint8_t *bank = static_cast<uint8_t *>(d_bank);
+    uint8_t *staging = bank + L.staging;                                     // (camera forms only)
+    uint32_t *hist = reinterpret_cast<uint32_t *>(bank + L.staging_hist);
+    // what the flow kernels pair with the stored frames: the caller's frames, or the crops in the staging region
+    const uint8_t *cur = p.camera ? staging : p.src;
+    BankArgs a = bank_args(bp, L, bank, cur, p.time_us, p.burst ? nullptr : p.select, p.gyro, p.records, p.mavlink, p.mavlink_len);
+    if (p.camera) camera_args(&a, p.cam, p.src, hist, p.exposure, p.derotated);
+    aof_flow *flows = reinterpret_cast<aof_flow *>(bank + L.flows);
+    const BankBurst b = {p.burst ? p.rounds->n_rounds : 1, round_stride, p.burst ? p.select : nullptr};
+
+    // which path: the one-launch kernel where the configuration (and these buffers) allow it and the bank is small
+    // enough for a workgroup per stream to pay, or because the caller asked for it
+    const int path = bank_path(ctx);
+    SmallArgs sm;
+    const bool fused = path != 2 &&
+                       plan_small_batch(ctx, a.bank_frames, cur, L.stride, bp->n_streams, flows, bank + L.pub.scratch, &sm) &&
+                       (path == 1 || bp->n_streams <= kFusedMaxStreams[p.camera][p.burst]);
+    if (fused) {
+        if (p.burst ? launch_bank_burst(sm, a, b, stream) : launch_bank_tick(sm, a, stream))
+            return ctx_fail(ctx, -EIO, p.burst ? "bank burst launch failed" : "bank tick launch failed");
+        return 0;
+    }
+    // composed, per round and in order on the one stream: (camera forms) the crops and raw histograms of all S sensor
+    // frames into the staging region; the flows of (stored frame, new frame) for all S streams -- those of idle and
+    // first-frame streams are cropped, computed and ignored --; then the tails and the masked copy
+    for (int k = 0; k < b.n_rounds; k++) {
+        const uint8_t *src = p.src + (int64_t)k * round_stride;
+        BankArgs r = a;   // (a tick keeps its `active` mask: round_args drops it for the burst's `count`)
+        if (p.burst) r = round_args(a, k, p.camera ? staging : src);
+        if (p.camera) {
+            r.cam.camera = src;
+            if (launch_ingest(p.cam->ingest, src, a.cam.camera_stride, bp->n_streams, staging, L.stride, p.exposure ? hist : nullptr, stream))
+                return ctx_fail(ctx, -EIO, "bank camera ingest launch failed");
+        }
+        rc = aof_flow_batch_device(ctx, a.bank_frames, r.frames, L.stride, bp->n_streams, nullptr, nullptr, flows,
+                                   bank + L.pub.scratch, L.flow_ws_bytes, stream);
+        if (rc) return rc;
+        if (launch_bank_commit(r, stream, b.count, b.count ? k : 0)) return ctx_fail(ctx, -EIO, "bank commit launch failed");
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -246,41 +333,6 @@ int aof_bank_reset_device(aof_ctx *ctx, const aof_bank_params *bp, const uint8_t
     return 0;
 }
 
-int aof_bank_push_device(aof_ctx *ctx, const aof_bank_params *bp, const uint8_t *d_frames, const uint64_t *d_time_us,
-                         const uint8_t *d_active, const aof_gyro *d_gyro, void *d_bank, size_t bank_bytes,
-                         aof_tick_record *d_records, uint8_t *d_mavlink, uint8_t *d_mavlink_len, void *stream)
-{
-    Layout L;
-    int rc = check_bank(ctx, bp, d_bank, bank_bytes, &L);
-    if (rc) return rc;
-    if ((rc = check_tick(ctx, d_frames, d_time_us, d_gyro, d_records, d_mavlink, d_mavlink_len))) return rc;
-    // before the first launch: a faulted or wedged context, or a thread on another device, must not touch the bank
-    if ((rc = precheck(ctx))) return rc;
-
-    uint8_t *bank = static_cast<uint8_t *>(d_bank);
-    const BankArgs a = bank_args(bp, L, bank, d_frames, d_time_us, d_active, d_gyro, d_records, d_mavlink, d_mavlink_len);
-    aof_flow *flows = reinterpret_cast<aof_flow *>(bank + L.flows);
-
-    // which path: the one-launch kernel where the configuration (and these buffers) allow it and the bank is small
-    // enough for a workgroup per stream to pay, or because the caller asked for it
-    const int path = bank_path(ctx);
-    SmallArgs sm;
-    const bool fused = path != 2 &&
-                       plan_small_batch(ctx, a.bank_frames, d_frames, L.stride, bp->n_streams, flows, bank + L.pub.scratch, &sm) &&
-                       (path == 1 || bp->n_streams <= kBankFusedMaxStreams);
-    if (fused) {
-        if (launch_bank_tick(sm, a, stream)) return ctx_fail(ctx, -EIO, "bank tick launch failed");
-        return 0;
-    }
-    // composed: flows of (stored frame, new frame) for all S streams -- those of idle and first-frame streams are
-    // computed and ignored --, then the tails and the masked copy
-    rc = aof_flow_batch_device(ctx, a.bank_frames, d_frames, L.stride, bp->n_streams, nullptr, nullptr, flows,
-                               bank + L.pub.scratch, L.flow_ws_bytes, stream);
-    if (rc) return rc;
-    if (launch_bank_commit(a, stream)) return ctx_fail(ctx, -EIO, "bank commit launch failed");
-    return 0;
-}
-
 int aof_bank_camera_layout(const aof_params *p, const aof_bank_params *bp, const aof_bank_camera *cam,
                            struct aof_bank_layout *out, size_t *staging)
 {
@@ -293,46 +345,21 @@ int aof_bank_camera_layout(const aof_params *p, const aof_bank_params *bp, const
     return 0;
 }
 
+int aof_bank_push_device(aof_ctx *ctx, const aof_bank_params *bp, const uint8_t *d_frames, const uint64_t *d_time_us,
+                         const uint8_t *d_active, const aof_gyro *d_gyro, void *d_bank, size_t bank_bytes,
+                         aof_tick_record *d_records, uint8_t *d_mavlink, uint8_t *d_mavlink_len, void *stream)
+{
+    const Push p = {false, false, nullptr, nullptr, d_frames, d_time_us, d_active, d_gyro, d_records, nullptr, nullptr, d_mavlink, d_mavlink_len};
+    return bank_push(ctx, bp, d_bank, bank_bytes, p, stream);
+}
+
 int aof_bank_push_camera_device(aof_ctx *ctx, const aof_bank_params *bp, const aof_bank_camera *cam, const uint8_t *d_camera,
                                 const uint64_t *d_time_us, const uint8_t *d_active, const aof_gyro *d_gyro, void *d_bank,
                                 size_t bank_bytes, aof_tick_record *d_records, aof_exposure_record *d_exposure,
                                 float *d_derotated, uint8_t *d_mavlink, uint8_t *d_mavlink_len, void *stream)
 {
-    Layout L;
-    int rc = check_bank(ctx, bp, d_bank, bank_bytes, &L, cam, true);
-    if (rc) return rc;
-    if ((rc = check_tick(ctx, d_camera, d_time_us, d_gyro, d_records, d_mavlink, d_mavlink_len))) return rc;
-    if (cam->derotate && !d_derotated) return ctx_fail(ctx, -EINVAL, "bank camera: derotate needs d_derotated");
-    if (reinterpret_cast<uintptr_t>(d_exposure) % 4 || reinterpret_cast<uintptr_t>(d_derotated) % 4)
-        return ctx_fail(ctx, -EINVAL, "bank camera: exposure records and de-rotated pairs must be 4-byte aligned");
-    if ((rc = precheck(ctx))) return rc;
-
-    uint8_t *bank = static_cast<uint8_t *>(d_bank);
-    uint8_t *staging = bank + L.staging;
-    uint32_t *hist = reinterpret_cast<uint32_t *>(bank + L.staging_hist);
-    BankArgs a = bank_args(bp, L, bank, staging, d_time_us, d_active, d_gyro, d_records, d_mavlink, d_mavlink_len);
-    aof_flow *flows = reinterpret_cast<aof_flow *>(bank + L.flows);
-    const aof_ingest_params &g = cam->ingest;
-    camera_args(&a, cam, d_camera, hist, d_exposure, d_derotated);
-
-    const int path = bank_path(ctx);
-    SmallArgs sm;
-    const bool fused = path != 2 &&
-                       plan_small_batch(ctx, a.bank_frames, staging, L.stride, bp->n_streams, flows, bank + L.pub.scratch, &sm) &&
-                       (path == 1 || bp->n_streams <= kBankCameraFusedMaxStreams);
-    if (fused) {
-        if (launch_bank_tick(sm, a, stream)) return ctx_fail(ctx, -EIO, "bank camera tick launch failed");
-        return 0;
-    }
-    // composed: crop (and raw histograms) of all S sensor frames into the staging region -- those of idle streams are
-    // cropped and ignored, like their flows --, the batch plan on (bank frames, staging), then the commit kernel
-    if (launch_ingest(g, d_camera, a.cam.camera_stride, bp->n_streams, staging, L.stride, d_exposure ? hist : nullptr, stream))
-        return ctx_fail(ctx, -EIO, "bank camera ingest launch failed");
-    rc = aof_flow_batch_device(ctx, a.bank_frames, staging, L.stride, bp->n_streams, nullptr, nullptr, flows,
-                               bank + L.pub.scratch, L.flow_ws_bytes, stream);
-    if (rc) return rc;
-    if (launch_bank_commit(a, stream)) return ctx_fail(ctx, -EIO, "bank commit launch failed");
-    return 0;
+    const Push p = {true, false, cam, nullptr, d_camera, d_time_us, d_active, d_gyro, d_records, d_exposure, d_derotated, d_mavlink, d_mavlink_len};
+    return bank_push(ctx, bp, d_bank, bank_bytes, p, stream);
 }
 
 int aof_bank_push_burst_device(aof_ctx *ctx, const aof_bank_params *bp, const aof_bank_burst *burst, const uint8_t *d_frames,
@@ -340,38 +367,8 @@ int aof_bank_push_burst_device(aof_ctx *ctx, const aof_bank_params *bp, const ao
                                size_t bank_bytes, aof_tick_record *d_records, uint8_t *d_mavlink, uint8_t *d_mavlink_len,
                                void *stream)
 {
-    Layout L;
-    int rc = check_bank(ctx, bp, d_bank, bank_bytes, &L);
-    if (rc) return rc;
-    int64_t round_stride = 0;
-    if ((rc = check_burst(ctx, burst, (int64_t)bp->n_streams * L.stride, false, &round_stride))) return rc;
-    if ((rc = check_tick(ctx, d_frames, d_time_us, d_gyro, d_records, d_mavlink, d_mavlink_len))) return rc;
-    if ((rc = precheck(ctx))) return rc;
-
-    uint8_t *bank = static_cast<uint8_t *>(d_bank);
-    const BankArgs a = bank_args(bp, L, bank, d_frames, d_time_us, nullptr, d_gyro, d_records, d_mavlink, d_mavlink_len);
-    aof_flow *flows = reinterpret_cast<aof_flow *>(bank + L.flows);
-    const BankBurst b = {burst->n_rounds, round_stride, d_count};
-
-    const int path = bank_path(ctx);
-    SmallArgs sm;
-    const bool fused = path != 2 &&
-                       plan_small_batch(ctx, a.bank_frames, d_frames, L.stride, bp->n_streams, flows, bank + L.pub.scratch, &sm) &&
-                       (path == 1 || bp->n_streams <= kBankBurstFusedMaxStreams);
-    if (fused) {
-        if (launch_bank_burst(sm, a, b, stream)) return ctx_fail(ctx, -EIO, "bank burst launch failed");
-        return 0;
-    }
-    // composed: K rounds of the single tick's launches, in order on the one stream
-    for (int k = 0; k < b.n_rounds; k++) {
-        const uint8_t *frames = d_frames + (int64_t)k * round_stride;
-        rc = aof_flow_batch_device(ctx, a.bank_frames, frames, L.stride, bp->n_streams, nullptr, nullptr, flows,
-                                   bank + L.pub.scratch, L.flow_ws_bytes, stream);
-        if (rc) return rc;
-        if (launch_bank_commit(round_args(a, k, frames), stream, d_count, d_count ? k : 0))
-            return ctx_fail(ctx, -EIO, "bank commit launch failed");
-    }
-    return 0;
+    const Push p = {false, true, nullptr, burst, d_frames, d_time_us, d_count, d_gyro, d_records, nullptr, nullptr, d_mavlink, d_mavlink_len};
+    return bank_push(ctx, bp, d_bank, bank_bytes, p, stream);
 }
 
 int aof_bank_push_camera_burst_device(aof_ctx *ctx, const aof_bank_params *bp, const aof_bank_camera *cam,
@@ -380,50 +377,8 @@ int aof_bank_push_camera_burst_device(aof_ctx *ctx, const aof_bank_params *bp, c
                                       aof_tick_record *d_records, aof_exposure_record *d_exposure, float *d_derotated,
                                       uint8_t *d_mavlink, uint8_t *d_mavlink_len, void *stream)
 {
-    Layout L;
-    int rc = check_bank(ctx, bp, d_bank, bank_bytes, &L, cam, true);
-    if (rc) return rc;
-    const aof_ingest_params &g = cam->ingest;
-    const int64_t camera_stride = cam->camera_stride ? cam->camera_stride : (int64_t)g.camera_width * g.camera_height;
-    int64_t round_stride = 0;
-    if ((rc = check_burst(ctx, burst, (int64_t)bp->n_streams * camera_stride, true, &round_stride))) return rc;
-    if ((rc = check_tick(ctx, d_camera, d_time_us, d_gyro, d_records, d_mavlink, d_mavlink_len))) return rc;
-    if (cam->derotate && !d_derotated) return ctx_fail(ctx, -EINVAL, "bank camera: derotate needs d_derotated");
-    if (reinterpret_cast<uintptr_t>(d_exposure) % 4 || reinterpret_cast<uintptr_t>(d_derotated) % 4)
-        return ctx_fail(ctx, -EINVAL, "bank camera: exposure records and de-rotated pairs must be 4-byte aligned");
-    if ((rc = precheck(ctx))) return rc;
-
-    uint8_t *bank = static_cast<uint8_t *>(d_bank);
-    uint8_t *staging = bank + L.staging;
-    uint32_t *hist = reinterpret_cast<uint32_t *>(bank + L.staging_hist);
-    BankArgs a = bank_args(bp, L, bank, staging, d_time_us, nullptr, d_gyro, d_records, d_mavlink, d_mavlink_len);
-    aof_flow *flows = reinterpret_cast<aof_flow *>(bank + L.flows);
-    camera_args(&a, cam, d_camera, hist, d_exposure, d_derotated);
-    const BankBurst b = {burst->n_rounds, round_stride, d_count};
-
-    const int path = bank_path(ctx);
-    SmallArgs sm;
-    const bool fused = path != 2 &&
-                       plan_small_batch(ctx, a.bank_frames, staging, L.stride, bp->n_streams, flows, bank + L.pub.scratch, &sm) &&
-                       (path == 1 || bp->n_streams <= kBankCameraBurstFusedMaxStreams);
-    if (fused) {
-        if (launch_bank_burst(sm, a, b, stream)) return ctx_fail(ctx, -EIO, "bank camera burst launch failed");
-        return 0;
-    }
-    // composed: per round the ingest launch into the staging region, the batch plan on (bank frames, staging) and the
-    // commit kernel, in order on the one stream
-    for (int k = 0; k < b.n_rounds; k++) {
-        const uint8_t *camera = d_camera + (int64_t)k * round_stride;
-        if (launch_ingest(g, camera, a.cam.camera_stride, bp->n_streams, staging, L.stride, d_exposure ? hist : nullptr, stream))
-            return ctx_fail(ctx, -EIO, "bank camera ingest launch failed");
-        rc = aof_flow_batch_device(ctx, a.bank_frames, staging, L.stride, bp->n_streams, nullptr, nullptr, flows,
-                                   bank + L.pub.scratch, L.flow_ws_bytes, stream);
-        if (rc) return rc;
-        BankArgs r = round_args(a, k, staging);
-        r.cam.camera = camera;
-        if (launch_bank_commit(r, stream, d_count, d_count ? k : 0)) return ctx_fail(ctx, -EIO, "bank commit launch failed");
-    }
-    return 0;
+    const Push p = {true, true, cam, burst, d_camera, d_time_us, d_count, d_gyro, d_records, d_exposure, d_derotated, d_mavlink, d_mavlink_len};
+    return bank_push(ctx, bp, d_bank, bank_bytes, p, stream);
 }
 
 }  // extern "C"

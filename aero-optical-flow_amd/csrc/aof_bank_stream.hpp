@@ -221,6 +221,30 @@ __device__ __forceinline__ void crop_first_frame(const BankCamera &c, const uint
     __syncthreads();
 }
 
+// Where stream s's new frames start: the crop rectangle inside its sensor frame, or its frame in the tick buffer.
+template <bool CAMERA>
+__device__ __forceinline__ const uint8_t *bank_source(const BankArgs &a, uint32_t s)
+{
+    return CAMERA ? a.cam.camera + (int64_t)s * a.cam.camera_stride + a.cam.origin : a.frames + (int64_t)s * a.frame_stride;
+}
+
+// The stream's newest frame out of LDS into its slot, by the whole workgroup.
+__device__ __forceinline__ void store_slot(const BankArgs &a, uint8_t *slot, const uint8_t *lds_new)
+{
+    for (int c = threadIdx.x; c < (int)(a.frame_bytes / 16); c += kThreads)
+        reinterpret_cast<uint4 *>(slot)[c] = reinterpret_cast<const uint4 *>(lds_new)[c];
+}
+
+// Host: does the small-pair plan `sm` belong to the bank `a`?  What launch_bank_tick and launch_bank_burst check before
+// they hand both to a kernel: a workgroup per stream, the plan's frame the bank's (in 16-byte chunks), and the camera
+// crop the plan's frame.
+inline bool bank_plan_fits(const SmallArgs &sm, const BankArgs &a)
+{
+    if (a.n_streams < 1 || sm.l0.n_pairs != a.n_streams) return false;
+    if (a.frame_bytes != (int64_t)sm.l0.w * sm.l0.h || a.frame_bytes % 16) return false;
+    return a.cam.camera == nullptr || (a.cam.crop_w == sm.l0.w && a.cam.crop_h == sm.l0.h);
+}
+
 }  // namespace
 
 }  // namespace aof

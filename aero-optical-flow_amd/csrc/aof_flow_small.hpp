@@ -317,6 +317,23 @@ inline size_t small_lds_bytes(const SmallArgs &a)
     return bytes;
 }
 
+// The ONE launcher of the one-workgroup class (k_flow_small.hip, k_bank.hip, k_bank_burst.hip): `grid` workgroups of
+// kThreads lanes run `fn` on the plan `sm`; `args` are the kernel's own arguments.  `fn` is the instantiation that is
+// launched: the dynamic-LDS limit above 48 KiB is an attribute of that one function.
+template <typename... Params, typename... Args>
+inline int launch_small_class(void (*fn)(Params...), uint32_t grid, const SmallArgs &sm, void *stream, const Args &...args)
+{
+    if (!flow_small_supported(sm)) return (int)hipErrorInvalidValue;
+    const size_t lds = small_lds_bytes(sm);
+    if (lds > 48 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(kThreads), lds, static_cast<hipStream_t>(stream), args...);
+    return (int)hipGetLastError();
+}
+
 }  // namespace
 
 }  // namespace aof

@@ -15,7 +15,10 @@
 // 10-bin histogram from the new frame's LDS copy; the tail lane moves the gate, writes the exposure record (the MSV in
 // aof_exposure_msv's float operations and order) and the de-rotated pair (derotate_flow, the function k_derotate
 // runs).  The commit kernel does the same from the staging region's frames and raw histograms (k_ingest).
-// What a stream does with a frame (tail, gate, histogram, copies) is aof_bank_stream.hpp, shared with k_bank_burst.hip.
+// What a stream does with a frame (tail, gate, histogram, copies) is aof_bank_stream.hpp, shared with k_bank_burst.hip,
+// as is the launchers' check of the plan against the bank (bank_plan_fits); the tick goes out through the one launcher
+// of the one-workgroup class (launch_small_class, aof_flow_small.hpp).  On the host all four push forms are one path
+// (bank_push, aof_bank.cpp).
 #include "aof_bank_stream.hpp"
 
 namespace aof {
@@ -33,7 +36,7 @@ __global__ __launch_bounds__(kThreads) void k_bank_tick(SmallArgs sm, BankArgs a
         if (threadIdx.x == 0) bank_idle<CAMERA>(a, s);
         return;
     }
-    const uint8_t *src = CAMERA ? a.cam.camera + (int64_t)s * a.cam.camera_stride + a.cam.origin : a.frames + (int64_t)s * a.frame_stride;
+    const uint8_t *src = bank_source<CAMERA>(a, s);
     uint8_t *slot = a.bank_frames + (int64_t)s * a.frame_stride;
     if constexpr (CAMERA) {
         __shared__ uint32_t s_hist[AOF_EXPOSURE_BINS];
@@ -61,9 +64,7 @@ __global__ __launch_bounds__(kThreads) void k_bank_tick(SmallArgs sm, BankArgs a
         if (threadIdx.x == 0) bank_tail<false>(a, s, s_record, false, s_payload);
     }
     // the new frame sits in LDS buffer 1 (flow_small_pair's layout: frame, kPad bytes, frame)
-    const uint8_t *lds_new = s_mem + a.frame_bytes + kPad;
-    for (int c = threadIdx.x; c < (int)(a.frame_bytes / 16); c += kThreads)
-        reinterpret_cast<uint4 *>(slot)[c] = reinterpret_cast<const uint4 *>(lds_new)[c];
+    store_slot(a, slot, s_mem + a.frame_bytes + kPad);
 }
 
 // count (a burst's composed path, round `round` of it; a's per-round pointers are the round's): the stream is active
@@ -94,20 +95,11 @@ __global__ __launch_bounds__(kThreads) void k_bank_reset(BankState *state, const
 
 int launch_bank_tick(const SmallArgs &sm, const BankArgs &a, void *stream)
 {
-    if (a.n_streams < 1 || sm.l0.n_pairs != a.n_streams || !flow_small_supported(sm)) return (int)hipErrorInvalidValue;
-    if (a.frame_bytes != (int64_t)sm.l0.w * sm.l0.h || a.frame_bytes % 16) return (int)hipErrorInvalidValue;
+    if (!bank_plan_fits(sm, a)) return (int)hipErrorInvalidValue;
     const bool camera = a.cam.camera != nullptr;
-    if (camera && (a.cam.crop_w != sm.l0.w || a.cam.crop_h != sm.l0.h)) return (int)hipErrorInvalidValue;
-    void (*fn)(SmallArgs, BankArgs) = camera ? (sm.l0.subpixel ? k_bank_tick<true, true> : k_bank_tick<false, true>)
-                                             : (sm.l0.subpixel ? k_bank_tick<true, false> : k_bank_tick<false, false>);
-    const size_t lds = small_lds_bytes(sm);
-    if (lds > 48 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(fn, dim3((uint32_t)a.n_streams), dim3(kThreads), lds, static_cast<hipStream_t>(stream), sm, a);
-    return (int)hipGetLastError();
+    return launch_small_class(camera ? (sm.l0.subpixel ? k_bank_tick<true, true> : k_bank_tick<false, true>)
+                                     : (sm.l0.subpixel ? k_bank_tick<true, false> : k_bank_tick<false, false>),
+                              (uint32_t)a.n_streams, sm, stream, sm, a);
 }
 
 int launch_bank_commit(const BankArgs &a, void *stream, const uint8_t *count, int32_t round)

@@ -46,8 +46,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
     __syncthreads();                 // (neither the state nor, behind pass A of the first pair, the slot is read again)
     uint32_t gate = s_gate;
     uint8_t *slot = a.bank_frames + (int64_t)s * a.frame_stride;
-    const uint8_t *base = CAMERA ? a.cam.camera + (int64_t)s * a.cam.camera_stride + a.cam.origin
-                                 : a.frames + (int64_t)s * a.frame_stride;
+    const uint8_t *base = bank_source<CAMERA>(a, s);
     uint8_t *const f0[2] = {s_mem, s_mem + a.frame_bytes + kPad};   // flow_small_pair's layout: frame, kPad bytes, frame
     constexpr uint32_t kWindow = CAMERA ? 1u : 0u;
     int newest = -1;                 // the LDS buffer that holds the newest frame; -1: none yet, the slot does
@@ -88,31 +87,19 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
         gate &= ~1u;
     }
     if (tid == 0) a.state[s] = s_state;
-    const uint8_t *lds_new = f0[newest];
-    for (int c = tid; c < (int)(a.frame_bytes / 16); c += kThreads)
-        reinterpret_cast<uint4 *>(slot)[c] = reinterpret_cast<const uint4 *>(lds_new)[c];
+    store_slot(a, slot, f0[newest]);
 }
 
 }  // namespace
 
 int launch_bank_burst(const SmallArgs &sm, const BankArgs &a, const BankBurst &b, void *stream)
 {
-    if (a.n_streams < 1 || sm.l0.n_pairs != a.n_streams || !flow_small_supported(sm)) return (int)hipErrorInvalidValue;
-    if (a.frame_bytes != (int64_t)sm.l0.w * sm.l0.h || a.frame_bytes % 16) return (int)hipErrorInvalidValue;
+    if (!bank_plan_fits(sm, a)) return (int)hipErrorInvalidValue;
     if (b.n_rounds < 1 || b.n_rounds > AOF_BANK_BURST_MAX) return (int)hipErrorInvalidValue;
     const bool camera = a.cam.camera != nullptr;
-    if (camera && (a.cam.crop_w != sm.l0.w || a.cam.crop_h != sm.l0.h)) return (int)hipErrorInvalidValue;
-    void (*fn)(SmallArgs, BankArgs, BankBurst) =
-        camera ? (sm.l0.subpixel ? k_bank_burst<true, true> : k_bank_burst<false, true>)
-               : (sm.l0.subpixel ? k_bank_burst<true, false> : k_bank_burst<false, false>);
-    const size_t lds = small_lds_bytes(sm);
-    if (lds > 48 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(fn, dim3((uint32_t)a.n_streams), dim3(kThreads), lds, static_cast<hipStream_t>(stream), sm, a, b);
-    return (int)hipGetLastError();
+    return launch_small_class(camera ? (sm.l0.subpixel ? k_bank_burst<true, true> : k_bank_burst<false, true>)
+                                     : (sm.l0.subpixel ? k_bank_burst<true, false> : k_bank_burst<false, false>),
+                              (uint32_t)a.n_streams, sm, stream, sm, a, b);
 }
 
 }  // namespace aof

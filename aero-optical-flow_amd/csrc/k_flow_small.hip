@@ -19,6 +19,8 @@
 // Nothing but the block records, the flow records and the sums leaves the chip (the level-1 frames of
 // the workspace stay untouched, as under the fused coarse kernel).  Results are those of the separate
 // kernels bit for bit.
+// Every kernel of this class -- the three forms here, the stream bank's tick and burst -- goes out through the one
+// launcher launch_small_class (aof_flow_small.hpp): the support check, the dynamic-LDS attribute, the launch.
 #include "aof_flow_small.hpp"
 
 namespace aof {
@@ -154,47 +156,21 @@ int launch_flow_resident(const SmallArgs &a, ResidentBox *box, aof_flow *host_re
                          const uint8_t *frame_b, uint32_t served, uint32_t launch_no, uint64_t idle_ticks,
                          uint64_t life_ticks, bool deaf, void *stream)
 {
-    if (a.l0.n_pairs != 1 || !flow_small_supported(a)) return (int)hipErrorInvalidValue;
-    void (*fn)(SmallArgs, ResidentBox *, aof_flow *, const uint8_t *, const uint8_t *, uint32_t, uint32_t, uint64_t, uint64_t, int) =
-        a.l0.subpixel ? k_flow_resident<true> : k_flow_resident<false>;
-    const size_t lds = small_lds_bytes(a);
-    if (lds > 48 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(fn, dim3(1), dim3(kThreads), lds, static_cast<hipStream_t>(stream), a, box, host_record, frame_a, frame_b,
-                       served, launch_no, idle_ticks, life_ticks, deaf ? 1 : 0);
-    return (int)hipGetLastError();
+    if (a.l0.n_pairs != 1) return (int)hipErrorInvalidValue;
+    return launch_small_class(a.l0.subpixel ? k_flow_resident<true> : k_flow_resident<false>, 1, a, stream, a, box, host_record,
+                              frame_a, frame_b, served, launch_no, idle_ticks, life_ticks, deaf ? 1 : 0);
 }
 
 int launch_flow_small_tagged(const SmallArgs &a, aof_flow *host_record, const uint32_t *tag, void *stream)
 {
-    if (a.l0.n_pairs != 1 || !flow_small_supported(a) || !host_record || !tag) return (int)hipErrorInvalidValue;
-    void (*fn)(SmallArgs, aof_flow *, const uint32_t *) = a.l0.subpixel ? k_flow_small_tagged<true> : k_flow_small_tagged<false>;
-    const size_t lds = small_lds_bytes(a);
-    if (lds > 48 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(fn, dim3(1), dim3(kThreads), lds, static_cast<hipStream_t>(stream), a, host_record, tag);
-    return (int)hipGetLastError();
+    if (a.l0.n_pairs != 1 || !host_record || !tag) return (int)hipErrorInvalidValue;
+    return launch_small_class(a.l0.subpixel ? k_flow_small_tagged<true> : k_flow_small_tagged<false>, 1, a, stream, a, host_record, tag);
 }
 
 int launch_flow_small(const SmallArgs &a, void *stream)
 {
     if (a.l0.n_pairs == 0) return 0;
-    if (!flow_small_supported(a)) return (int)hipErrorInvalidValue;
-    void (*fn)(SmallArgs) = a.l0.subpixel ? k_flow_small<true> : k_flow_small<false>;
-    const size_t lds = small_lds_bytes(a);
-    if (lds > 48 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(fn, dim3((uint32_t)a.l0.n_pairs), dim3(kThreads), lds, static_cast<hipStream_t>(stream), a);
-    return (int)hipGetLastError();
+    return launch_small_class(a.l0.subpixel ? k_flow_small<true> : k_flow_small<false>, (uint32_t)a.l0.n_pairs, a, stream, a);
 }
 
 }  // namespace aof
