@@ -19,8 +19,9 @@ class Run:
         self.T, self.S = active.shape
 
 
-def make_run(synth, w, h, S, T, case_seed, wrap=False, black=True, density=None):
-    """The recipe of the issue: stream s uses make_sequence(w, h, T, 4, seed=1000*case_seed + s, max_step=3); it joins at
+def make_run(synth, w, h, S, T, case_seed, wrap=False, black=True, density=None, source=None):
+    """The recipe of the issue: stream s uses make_sequence(w, h, T, 4, seed=1000*case_seed + s, max_step=3) -- or, with
+    `source`, the T frames [T, h, w] that source(s, T) returns --; it joins at
     tick s % 4; it is idle in tick k when (7k + 3s) % 5 == 0 (or, with `density`, with that probability); every active
     tick advances its clock by 9 000..18 000 us; streams with s % 5 == 3 see three black frames (their frames 7..9);
     with `wrap`, the 32-bit time stamp of every third stream wraps in the middle of the run."""
@@ -30,7 +31,11 @@ def make_run(synth, w, h, S, T, case_seed, wrap=False, black=True, density=None)
     gyro = rng.normal(0, 1.0, (T, S, 4)).astype(np.float32)
     active = np.zeros((T, S), np.uint8)
     for s in range(S):
-        seq, _ = synth.make_sequence(w, h, T, 4, seed=1000 * case_seed + s, max_step=3)
+        if source is None:
+            seq, _ = synth.make_sequence(w, h, T, 4, seed=1000 * case_seed + s, max_step=3)
+        else:
+            seq = np.array(source(s, T), dtype=np.uint8)
+            assert seq.shape == (T, h, w)
         if black and s % 5 == 3:
             seq[7:10] = 0
         n, clock = 0, 0
@@ -89,9 +94,9 @@ class Chain:
         return rec, wire
 
 
-def oracle_chain(aof, orc, p, rate, offset, first_seq, use_gyro=True):
+def oracle_chain(aof, orc, p, rate, offset, first_seq, use_gyro=True, fx=FX, fy=FY):
     po = orc.params_from(p)
-    o = orc.Px4(po, FX, FY, rate)
+    o = orc.Px4(po, fx, fy, rate)
     return Chain(aof.TICK_DTYPE, o.calc_flow, py_frame, offset, first_seq,
                  pixel=lambda a, b: orc.flow_pair(po, a, b)["flow"], use_gyro=use_gyro)
 

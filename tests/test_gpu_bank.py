@@ -99,23 +99,24 @@ def same_records(got, want, tick, what, pixel=True):
 
 
 def run_case(aof, orc, synth, gpu_device, cfg, S, T, seed, rate=15, offset=OFFSET, first_seq=0, wrap=False, use_gyro=True,
-             path=0, facade=0, density=None, census=None, frame_stride=0):
+             path=0, facade=0, density=None, census=None, frame_stride=0, fx=FX, fy=FY, source=None):
     """One bank over one Run against the oracle chain (all streams) and the facade (streams < facade); returns the
-    oracle's records."""
+    oracle's records.  fx, fy: the focal lengths of the bank, the chains and the facade objects; source: bank_ref.make_run's
+    per-stream sequence source."""
     p = params_of(aof, cfg)
-    run = ref.make_run(synth, p.width, p.height, S, T, seed, wrap=wrap, density=density)
-    want, wire = ref.expected(run, [ref.oracle_chain(aof, orc, p, rate, offset, first_seq, use_gyro) for _ in range(S)])
+    run = ref.make_run(synth, p.width, p.height, S, T, seed, wrap=wrap, density=density, source=source)
+    want, wire = ref.expected(run, [ref.oracle_chain(aof, orc, p, rate, offset, first_seq, use_gyro, fx=fx, fy=fy) for _ in range(S)])
     pub, held, idle = ref.census(want)
     if census is not None:          # a condition on the INPUT: a bank that never holds or never publishes cannot pass
         assert pub.min() >= census[0] and held.min() >= census[1] and idle.min() >= census[2], (pub, held, idle)
     eng = aof.FlowEngine(p, 0)
     eng.set_bank_path(path)
-    bp = aof.bank_params(S, FX, FY, rate, offset, 1, 100, first_seq, frame_stride)
+    bp = aof.bank_params(S, fx, fy, rate, offset, 1, 100, first_seq, frame_stride)
     dev = Device(aof, eng, run, bp, gpu_device, use_gyro=use_gyro)
     stride = frame_stride or p.width * p.height
     facs = []
     for s in range(min(facade, S)):
-        f = aof.OpticalFlowPX4(FX, FY, rate, p.width, p.height) if p.pyramid_levels == 1 else aof.OpticalFlowOpenCV(FX, FY, rate, p.width, p.height)
+        f = aof.OpticalFlowPX4(fx, fy, rate, p.width, p.height) if p.pyramid_levels == 1 else aof.OpticalFlowOpenCV(fx, fy, rate, p.width, p.height)
         assert f.getPyramidLevels() == p.pyramid_levels
         facs.append(f)
     chains_f = [ref.Chain(aof.TICK_DTYPE, f.calcFlow, aof.pack_optical_flow_rad, offset, first_seq, use_gyro=use_gyro) for f in facs]

@@ -191,27 +191,33 @@ class Case:
 
     def __init__(self, aof, orc, synth, cfg, K, S=24, B=6, seed=1, camera=False, overrides=None, rate=15, first_seq=0,
                  wrap=False, use_gyro=True, exposure=True, derotate=True, sensor=None, skew=0, pad=0, frame_stride=0,
-                 camera_stride=0, interval=cref.EXPOSURE_INTERVAL_US, path=0, needs=(), resets=None):
+                 camera_stride=0, interval=cref.EXPOSURE_INTERVAL_US, path=0, needs=(), resets=None, fx=FX, fy=FY, burst_run=None):
+        """fx, fy: the focal lengths of the bank, the camera's de-rotation and the oracle chains.  burst_run: (Run, counts,
+        given) in make_burst_run's form to use in its place, as they are (no saturated patches)."""
         self.aof, self.K, self.S, self.B, self.camera, self.path = aof, K, S, B, camera, path
         self.use_gyro, self.exposure, self.derotate, self.skew, self.pad = use_gyro, exposure, derotate, skew, pad
         self.p = p = params_for(aof, cfg, overrides)
-        self.run, self.counts, self.given = make_burst_run(synth, p.width, p.height, S, K, B, seed, wrap=wrap)
-        if camera:
-            cref.add_saturated_patches(self.run)
-        new = lambda s=0: ref.oracle_chain(aof, orc, p, rate, OFFSET, first_seq, use_gyro)
+        if burst_run is not None:
+            self.run, self.counts, self.given = burst_run
+            assert (self.run.T, self.run.S) == (B * K, S)
+        else:
+            self.run, self.counts, self.given = make_burst_run(synth, p.width, p.height, S, K, B, seed, wrap=wrap)
+            if camera:
+                cref.add_saturated_patches(self.run)
+        new = lambda s=0: ref.oracle_chain(aof, orc, p, rate, OFFSET, first_seq, use_gyro, fx=fx, fy=fy)
         tick_resets = {j * K: m for j, m in (resets or {}).items()}
         self.want, self.wire = ref.expected(self.run, [new() for _ in range(S)], resets=tick_resets, new_chain=new)
-        self.bp = aof.bank_params(S, FX, FY, rate, OFFSET, 1, 100, first_seq, frame_stride)
+        self.bp = aof.bank_params(S, fx, fy, rate, OFFSET, 1, 100, first_seq, frame_stride)
         self.due = self.after = self.derot = self.cam = self.cam_run = None
         if camera:
             sensor = sensor or SENSOR[cfg]
             self.cam = aof.bank_camera_params(sensor[0], sensor[1], p.width, p.height, camera_stride, interval,
-                                              cref.DEROTATE if derotate else None, FX, FY)
+                                              cref.DEROTATE if derotate else None, fx, fy)
             self.cam_run = cref.CameraRun(self.run, sensor[0], sensor[1], seed)
             self.due, self.after = cref.gate(self.run.times, self.run.active, interval, resets=tick_resets)
             if not exposure:                # no statistics: the gate does not move
                 self.due[:], self.after[:] = 0, 0
-            self.derot = np.stack([cref.expected_derotated(orc, self.want[t], self.run.gyro[t], FX, FY, use_gyro=use_gyro)
+            self.derot = np.stack([cref.expected_derotated(orc, self.want[t], self.run.gyro[t], fx, fy, use_gyro=use_gyro)
                                    for t in range(self.run.T)])
         # conditions on the INPUT, checked on the CPU chain before the device is compared
         self.seen = census(self.run, self.counts, K, self.want, self.wire, self.due if exposure else None, rate, first_seq)

@@ -96,14 +96,17 @@ def untouched(a):
 GATED = (2, 10)   # per stream, 48 ticks at 200 000 us: >= 2 due and >= 10 not-due active frames
 
 
-def prepare(aof, orc, synth, p, S, T, seed, interval, rate, wrap, use_gyro, census, gated, exposure, derotate):
+def prepare(aof, orc, synth, p, S, T, seed, interval, rate, wrap, use_gyro, census, gated, exposure, derotate, fx=FX, fy=FY,
+            source=None, patches=True):
     """The inputs and everything expected of a case, with the conditions on the INPUT asserted (no device needed)."""
-    run = cref.add_saturated_patches(ref.make_run(synth, p.width, p.height, S, T, seed, wrap=wrap))
-    want, wire = ref.expected(run, [ref.oracle_chain(aof, orc, p, rate, OFFSET, 0, use_gyro) for _ in range(S)])
+    run = ref.make_run(synth, p.width, p.height, S, T, seed, wrap=wrap, source=source)
+    if patches:
+        cref.add_saturated_patches(run)
+    want, wire = ref.expected(run, [ref.oracle_chain(aof, orc, p, rate, OFFSET, 0, use_gyro, fx=fx, fy=fy) for _ in range(S)])
     due, after = cref.gate(run.times, run.active, interval)
     if not exposure:                # no statistics: the gate does not move
         due[:], after[:] = 0, 0
-    derot = np.stack([cref.expected_derotated(orc, want[k], run.gyro[k], FX, FY, use_gyro=use_gyro) for k in range(T)])
+    derot = np.stack([cref.expected_derotated(orc, want[k], run.gyro[k], fx, fy, use_gyro=use_gyro) for k in range(T)])
     # conditions on the INPUT, before the device runs: a bank that never gates, holds or de-rotates cannot pass
     if census is not None:
         pub, held, idle = ref.census(want)
@@ -121,17 +124,19 @@ def prepare(aof, orc, synth, p, S, T, seed, interval, rate, wrap, use_gyro, cens
 
 def run_case(aof, orc, synth, gpu_device, cfg, S, T, seed, sensor=None, interval=cref.EXPOSURE_INTERVAL_US, rate=15,
              wrap=False, use_gyro=True, path=0, census=None, gated=None, frame_stride=0, camera_stride=0, exposure=True,
-             derotate=True, skew=0):
-    """One camera bank over one Run against the oracle chain, tick by tick; returns (records, due)."""
+             derotate=True, skew=0, fx=FX, fy=FY, source=None, patches=True):
+    """One camera bank over one Run against the oracle chain, tick by tick; returns (records, due).  fx, fy: the focal
+    lengths of the bank, the de-rotation and the chains; source: bank_ref.make_run's per-stream sequence source; patches:
+    the saturated patches of bank_camera_ref on the frames."""
     p = params_of(aof, cfg)
     sensor = sensor or SENSOR[cfg]
     run, want, wire, due, after, derot = prepare(aof, orc, synth, p, S, T, seed, interval, rate, wrap, use_gyro, census, gated,
-                                                 exposure, derotate)
+                                                 exposure, derotate, fx=fx, fy=fy, source=source, patches=patches)
     eng = aof.FlowEngine(p, 0)
     eng.set_bank_path(path)
-    bp = aof.bank_params(S, FX, FY, rate, OFFSET, 1, 100, 0, frame_stride)
+    bp = aof.bank_params(S, fx, fy, rate, OFFSET, 1, 100, 0, frame_stride)
     cam = aof.bank_camera_params(sensor[0], sensor[1], p.width, p.height, camera_stride, interval,
-                                 cref.DEROTATE if derotate else None, FX, FY)
+                                 cref.DEROTATE if derotate else None, fx, fy)
     cam_run = cref.CameraRun(run, sensor[0], sensor[1], seed)
     dev = CamDevice(aof, eng, run, cam_run, bp, cam, gpu_device, use_gyro=use_gyro, exposure=exposure, skew=skew)
     stride = frame_stride or p.width * p.height
