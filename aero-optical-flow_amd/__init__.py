@@ -127,6 +127,22 @@ EXPOSURE_COMMAND_DTYPE = np.dtype([("exposure", "<u2"), ("gain", "u1"), ("flags"
 assert EXPOSURE_STATE_DTYPE.itemsize == 16 and EXPOSURE_COMMAND_DTYPE.itemsize == 16
 
 
+class ImuParams(C.Structure):
+    """``aof_imu_params`` (include/aof.h)."""
+    _fields_ = [("n_streams", C.c_int32), ("n_rounds", C.c_int32), ("max_samples", C.c_int32),
+                ("system_id", C.c_uint8), ("component_id", C.c_uint8), ("first_seq", C.c_uint8)]
+
+
+IMU_SLOTS_MAX = 16
+TICK_STALE_GYRO, TICK_NO_OFFSET = -3, -4
+IMU_SAMPLE_DTYPE = np.dtype([("time_usec", "<u8"), ("xgyro", "<f4"), ("ygyro", "<f4"), ("zgyro", "<f4"),
+                             ("reserved", "<u4")])                                                   # aof_imu_sample
+IMU_STATE_DTYPE = np.dtype([("gyro_x", "<f8"), ("gyro_y", "<f8"), ("gyro_z", "<f8"), ("prev_time_usec", "<u8"),
+                            ("last_taken_time_usec", "<u8"), ("offset_timestamp_usec", "<u8"), ("messages", "<u4"),
+                            ("samples_integrated", "<u4"), ("samples_rejected", "<u4"), ("dropped", "<u4")])   # aof_imu_state
+assert IMU_SAMPLE_DTYPE.itemsize == 24 and IMU_STATE_DTYPE.itemsize == 64
+
+
 class OutboxLayout(C.Structure):
     """``struct aof_outbox_layout`` (include/aof.h)."""
     _fields_ = [(n, C.c_size_t) for n in ("total_bytes", "messages", "exposures")]
@@ -241,6 +257,9 @@ def _load():
         "aof_bank_exposure_reset_device": (C.c_int, [VP, C.c_int32, VP, C.c_uint16, C.c_uint8, VP, VP, VP, VP]),
         "aof_bank_exposure_control_device": (C.c_int, [VP, P(ExposureControl), C.c_int32, C.c_int32, VP, VP, VP, VP]),
         "aof_exposure_control_host": (C.c_int, [P(ExposureControl), C.c_int32, C.c_int32, VP, VP, VP]),
+        "aof_bank_imu_reset_device": (C.c_int, [VP, C.c_int32, VP, C.c_uint64, VP, VP]),
+        "aof_bank_imu_device": (C.c_int, [VP, P(ImuParams), VP, VP, VP, VP, VP, VP, VP, VP, VP]),
+        "aof_bank_imu_host": (C.c_int, [P(ImuParams), VP, VP, VP, VP, VP, VP, VP, VP]),
         "aof_derotate_batch_device": (C.c_int, [P(DerotateParams), VP, VP, I64, VP, VP]),
         "aof_exposure_msv": (C.c_float, [VP]),
         "aof_exposure_bin": (C.c_int, [C.c_int]),
@@ -520,6 +539,48 @@ def exposure_control_host(records, states, ec: ExposureControl = None):
     if rc:
         raise AofError(rc, lib.aof_strerror(rc).decode())
     return commands
+
+
+def imu_params(n_streams, n_rounds, max_samples, system_id=1, component_id=100, first_seq=0) -> ImuParams:
+    ip = ImuParams()
+    ip.n_streams, ip.n_rounds, ip.max_samples = int(n_streams), int(n_rounds), int(max_samples)
+    ip.system_id, ip.component_id, ip.first_seq = int(system_id), int(component_id), int(first_seq)
+    return ip
+
+
+def bank_imu_host(samples, counts, times, records, states, system_id=1, component_id=100, first_seq=0, mavlink=True,
+                  records_out=None, fill=0):
+    """``aof_bank_imu_host``: the IMU call on host memory, no device.  samples: IMU_SAMPLE_DTYPE [K, M, S]; counts:
+    uint8 [K, S] or None (M everywhere); times: uint64 [K, S]; records: TICK_DTYPE [K, S], what a push wrote; states:
+    IMU_STATE_DTYPE [S], contiguous, updated IN PLACE.  records_out: a TICK_DTYPE [K, S] array to write (`records`
+    itself for the in-place form) or None (a new one).  Returns (records_out, frames uint8 [K, S, 56] -- bytes nobody
+    wrote keep `fill` --, lengths uint8 [K, S]); frames and lengths are None with mavlink=False."""
+    samples = np.ascontiguousarray(samples, dtype=IMU_SAMPLE_DTYPE)
+    K, M, S = samples.shape
+    times = np.ascontiguousarray(times, dtype=np.uint64)
+    assert records.dtype == TICK_DTYPE and records.shape == (K, S) and records.flags.c_contiguous and times.shape == (K, S)
+    assert states.dtype == IMU_STATE_DTYPE and states.shape == (S,) and states.flags.c_contiguous and states.flags.writeable
+    if counts is not None:
+        counts = np.ascontiguousarray(counts, dtype=np.uint8)
+        assert counts.shape == (K, S)
+    if records_out is None:
+        records_out = np.empty((K, S), TICK_DTYPE)
+    assert records_out.dtype == TICK_DTYPE and records_out.shape == (K, S) and records_out.flags.c_contiguous
+    frames = np.full((K, S, SEQ_FRAME_BYTES), fill, np.uint8) if mavlink else None
+    lengths = np.full((K, S), fill, np.uint8) if mavlink else None
+    ip = imu_params(S, K, M, system_id, component_id, first_seq)
+    rc = lib.aof_bank_imu_host(C.byref(ip), samples.ctypes.data, counts.ctypes.data if counts is not None else None,
+                               times.ctypes.data, records.ctypes.data, states.ctypes.data, records_out.ctypes.data,
+                               frames.ctypes.data if mavlink else None, lengths.ctypes.data if mavlink else None)
+    if rc:
+        raise AofError(rc, lib.aof_strerror(rc).decode())
+    return records_out, frames, lengths
+
+
+def imu_states_view(t) -> np.ndarray:
+    """uint8 tensor/array [S, 64] of ``aof_imu_state`` -> structured numpy view [S]."""
+    a = t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+    return np.ascontiguousarray(a).view(IMU_STATE_DTYPE).reshape(a.shape[:-1])
 
 
 def exposure_states_view(t) -> np.ndarray:
@@ -941,6 +1002,57 @@ class FlowEngine:
                                                          torch.cuda.current_stream(dev).cuda_stream))
         return commands
 
+    def bank_imu_reset(self, state, mask=None, offset0=0):
+        """aof_bank_imu_reset_device: state uint8 CUDA tensor [S, 64] (``aof_imu_state``; read it with imu_states_view());
+        mask uint8 [S] (non-zero = reset) or None (all); offset0: the streams' vehicle-time offset, 0 = learned from the
+        first sample.  Enqueued on torch's current stream."""
+        import torch
+        S = state.numel() // 64
+        assert state.dtype == torch.uint8 and state.is_contiguous() and state.numel() == 64 * S
+        assert mask is None or (mask.dtype == torch.uint8 and mask.numel() == S and mask.is_contiguous())
+        self._check(lib.aof_bank_imu_reset_device(self._ctx, S, mask.data_ptr() if mask is not None else None, int(offset0),
+                                                  state.data_ptr(), torch.cuda.current_stream(state.device).cuda_stream))
+
+    def bank_imu(self, samples, times, records, state, counts=None, mavlink=True, records_out=None, out_frames=None,
+                 out_lengths=None, system_id=1, component_id=100, first_seq=0):
+        """aof_bank_imu_device behind a records-only push: samples uint8 CUDA tensor [K, M, S, 24] (or [M, S, 24] for a
+        tick); times int64 [K, S] / [S], what the push was given; records uint8 [K, S, 48] / [S, 48], what it wrote;
+        state uint8 [S, 64], stepped in place; counts uint8 [K, S] / [S] or None (M everywhere).  records_out: `records`
+        itself (in place), another tensor of its shape, or None (a new one); out_frames [.., 56] / out_lengths [..]:
+        tensors, numpy uint8 arrays over device-mapped host memory, or None (new tensors, zero-filled).  Enqueued on
+        torch's current stream.  Returns (records_out, frames, lengths); the last two are None with mavlink=False."""
+        import torch
+        dev = records.device
+        assert records.dtype == torch.uint8 and records.is_contiguous() and records.shape[-1] == 48 and records.dim() in (2, 3)
+        K, S = (1, records.shape[0]) if records.dim() == 2 else (records.shape[0], records.shape[1])
+        lead = tuple(records.shape[:-1])
+        assert samples.dtype == torch.uint8 and samples.is_contiguous() and samples.shape[-1] == 24 and samples.numel() % (24 * K * S) == 0
+        M = samples.numel() // (24 * K * S)
+        assert times.dtype == torch.int64 and times.is_contiguous() and times.numel() == K * S
+        assert state.dtype == torch.uint8 and state.is_contiguous() and state.numel() == 64 * S
+        assert counts is None or (counts.dtype == torch.uint8 and counts.is_contiguous() and counts.numel() == K * S)
+        if records_out is None:
+            records_out = torch.empty_like(records)
+        assert records_out.dtype == torch.uint8 and records_out.is_contiguous() and records_out.shape == records.shape
+        ptr = lambda t: None if t is None else t.ctypes.data if isinstance(t, np.ndarray) else t.data_ptr()
+        if mavlink:
+            if out_frames is None:
+                out_frames = torch.zeros(lead + (SEQ_FRAME_BYTES,), dtype=torch.uint8, device=dev)
+            if out_lengths is None:
+                out_lengths = torch.zeros(lead, dtype=torch.uint8, device=dev)
+            for t, n in ((out_frames, K * S * SEQ_FRAME_BYTES), (out_lengths, K * S)):
+                if isinstance(t, np.ndarray):
+                    assert t.dtype == np.uint8 and t.size == n and t.flags.c_contiguous
+                else:
+                    assert t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n
+        else:
+            out_frames = out_lengths = None
+        ip = imu_params(S, K, M, system_id, component_id, first_seq)
+        self._check(lib.aof_bank_imu_device(self._ctx, C.byref(ip), samples.data_ptr(), ptr(counts), times.data_ptr(),
+                                            records.data_ptr(), state.data_ptr(), records_out.data_ptr(), ptr(out_frames),
+                                            ptr(out_lengths), torch.cuda.current_stream(dev).cuda_stream))
+        return records_out, out_frames, out_lengths
+
     def set_bank_path(self, path=0):
         """0: the library chooses between the one-launch tick kernel and the composed path, 1: the tick kernel where
         the configuration allows it, 2: always the composed path.  Same bytes either way."""
@@ -1064,6 +1176,8 @@ def facade_lib():
         f.aof_facade_bank_push.argtypes = [C.c_void_p] * 5
         f.aof_facade_bank_enable_camera.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32]
         f.aof_facade_bank_push_camera.argtypes = [C.c_void_p] * 5
+        f.aof_facade_bank_enable_imu.argtypes = [C.c_void_p, C.c_int, C.c_uint64]
+        f.aof_facade_bank_push_imu.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_float, C.c_float, C.c_float]
         f.aof_facade_bank_exposure_commands.restype = C.c_void_p
         f.aof_facade_bank_exposure_commands.argtypes = [C.c_void_p]
         f.aof_facade_bank_published.restype = C.c_void_p
@@ -1230,6 +1344,16 @@ class OpticalFlowBank:
         """sensor_frames uint8 [S, camera_height, camera_width]; the rest and the return value as push()."""
         assert getattr(self, "_sensor", None), "pushCamera() needs enableCamera()"
         return self._push(facade_lib().aof_facade_bank_push_camera, sensor_frames, self._sensor, img_time_us, active, gyro)
+
+    def enableImu(self, max_samples, offset0=0):
+        """The IMU form: pushImu() queues raw gyro samples, push() / pushCamera() ignore their gyro argument, and the
+        entries are what the reference would have sent (stale-gyro and no-offset records dropped).  Returns 0 or a
+        negative value."""
+        return facade_lib().aof_facade_bank_enable_imu(self._h, int(max_samples), int(offset0))
+
+    def pushImu(self, stream, time_usec, xgyro, ygyro, zgyro):
+        """One HIGHRES_IMU sample for the stream's next tick: 0, -ENOBUFS (the stream's queue is full), -EINVAL."""
+        return facade_lib().aof_facade_bank_push_imu(self._h, int(stream), int(time_usec), float(xgyro), float(ygyro), float(zgyro))
 
     def exposureCommands(self):
         """A copy of the last pushCamera()'s commands (EXPOSURE_COMMAND_DTYPE [n_streams]); None without enableCamera()."""

@@ -374,6 +374,21 @@ struct ExposureArgs {
 int launch_bank_exposure(const ExposureArgs &a, void *stream);
 int launch_bank_exposure_reset(aof_exposure_state *state, const uint8_t *mask, uint32_t n_streams, uint16_t exposure0,
                                uint8_t gain0, const uint16_t *d_exposure0, const uint8_t *d_gain0, void *stream);
+// The IMU call behind a push (aof_bank_imu_device / aof_bank_imu_reset_device, aof_imu.cpp, k_bank_imu.hip): a lane per
+// stream takes the stream's samples and completes its K records.
+struct ImuArgs {
+    uint32_t n_streams, n_rounds, max_samples;   // S, K (1..AOF_BANK_BURST_MAX), M (1..AOF_IMU_SLOTS_MAX)
+    uint8_t system_id, component_id, first_seq;
+    const uint8_t *samples;            // aof_imu_sample [K][M][S]
+    const uint8_t *sample_count;       // u8 [K][S] or nullptr (M everywhere)
+    const uint64_t *time_us;           // [K][S]
+    const uint8_t *records_in;         // aof_tick_record [K][S]
+    uint8_t *records_out;              // [K][S]: records_in, or disjoint from it
+    aof_imu_state *state;              // [S]
+    uint8_t *mavlink, *mavlink_len;    // [K][S][AOF_SEQ_FRAME_BYTES], [K][S]; both nullptr, or neither
+};
+int launch_bank_imu(const ImuArgs &a, void *stream);
+int launch_bank_imu_reset(aof_imu_state *state, const uint8_t *mask, uint32_t n_streams, uint64_t offset0, void *stream);
 // (aof_batch.cpp) the small-pair plan of n pairs, whatever n: true where one workgroup per pair can serve the
 // context's configuration and these buffers (flows: [n]; d_workspace: aof_workspace_layout(p, n))
 bool plan_small_batch(const aof_ctx *ctx, const uint8_t *prev, const uint8_t *cur, int64_t stride, int64_t n, aof_flow *flows,

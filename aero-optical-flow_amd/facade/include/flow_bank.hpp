@@ -38,7 +38,9 @@ public:
 	// The entries of the last push(), in stream order; valid until the next push().
 	const aof_outbox_entry *published() const;
 	// Masked streams (mask[s] != 0; NULL = all) start over: no previous frame, limiter and gyro sums zero,
-	// the exposure gate open.  The auto-exposure controllers keep what they hold: the cameras keep running.
+	// the exposure gate open; with enableImu() their IMU state starts over as well, with its offset0, and the
+	// samples pushImu() queued for them are dropped.  The
+	// auto-exposure controllers keep what they hold: the cameras keep running.
 	// This class has no call that restarts one stream's controller or overwrites its state (after a camera
 	// refused a value, say): a host that needs that drives aof_bank_exposure_reset_device and a state array
 	// of its own through include/aof.h.
@@ -62,6 +64,21 @@ public:
 	// was not due); valid until the next push.  NULL without enableCamera().
 	const aof_exposure_command *exposureCommands() const;
 
+	// The IMU form: what mainloop.cpp's highres_imu_msg_callback and the gates behind calcFlow() do (the gyro
+	// integrator of :383-405, the stale-gyro drop of :336-342, "no vehicle time yet" of :353-357) moves behind
+	// push() and pushCamera() for every stream (aof_bank_imu_device, include/aof.h).  enableImu() allocates the
+	// per-stream state and a pinned staging area of max_samples (1..AOF_IMU_SLOTS_MAX) samples per stream and
+	// tick, and starts every stream over; offset0: the vehicle-time offset of every stream, 0 = each stream learns
+	// it from its first sample (setTimestampOffset() is not consulted any more).  From then on push() and
+	// pushCamera() ignore their gyro argument, and published() holds only the records the reference would have
+	// sent, their gyro sums integrated sample by sample.  Returns 0, or a negative value: -EINVAL for a second
+	// call or a bad max_samples (refused: the object is as it was), anything else as enableCamera().
+	int enableImu(int max_samples, uint64_t offset0 = 0);
+	// Queues one HIGHRES_IMU sample (time in microseconds, rates in rad/s) for the stream's next tick.  Returns
+	// 0; -ENOBUFS, the object unchanged, when the stream already holds max_samples; -EINVAL for a bad stream
+	// index or without enableImu().
+	int pushImu(int stream, uint64_t time_usec, float xgyro, float ygyro, float zgyro);
+
 	inline int getStreams() const { return n_streams; }
 	inline int getImageWidth() const { return image_width; }
 	inline int getImageHeight() const { return image_height; }
@@ -76,6 +93,7 @@ private:
 	int refuse(int code, const char *what);
 	bool waitIdle();
 	int collect();
+	int takeImu();
 
 	int image_width, image_height, n_streams;
 	struct Impl;

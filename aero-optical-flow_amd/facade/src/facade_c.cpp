@@ -98,6 +98,14 @@ int aof_facade_bank_push_camera(void *bank, const uint8_t *sensor_frames, const 
 {
 	return static_cast<OpticalFlowBank *>(bank)->pushCamera(sensor_frames, img_time_us, active, gyro);
 }
+int aof_facade_bank_enable_imu(void *bank, int max_samples, uint64_t offset0)
+{
+	return static_cast<OpticalFlowBank *>(bank)->enableImu(max_samples, offset0);
+}
+int aof_facade_bank_push_imu(void *bank, int stream, uint64_t time_usec, float xgyro, float ygyro, float zgyro)
+{
+	return static_cast<OpticalFlowBank *>(bank)->pushImu(stream, time_usec, xgyro, ygyro, zgyro);
+}
 const void *aof_facade_bank_exposure_commands(void *bank) { return static_cast<OpticalFlowBank *>(bank)->exposureCommands(); }
 const void *aof_facade_bank_published(void *bank) { return static_cast<OpticalFlowBank *>(bank)->published(); }
 int aof_facade_bank_reset(void *bank, const uint8_t *mask) { return static_cast<OpticalFlowBank *>(bank)->reset(mask); }

@@ -4,7 +4,9 @@
 // launch, and a bounded poll of the outbox's tag: no stream synchronisation anywhere.  pushCamera() is the same
 // on raw sensor frames (aof_bank_push_camera_device), with the auto-exposure controller
 // (aof_bank_exposure_control_device) between the tick and the collect launch: its commands land in pinned
-// memory in front of the tag.
+// memory in front of the tag.  With enableImu() the tick leaves records only and the IMU call
+// (aof_bank_imu_device) behind it takes the samples pushImu() queued, completes the records in place and packs the
+// frames, so that the collect launch lists only what the reference would have sent.
 #include <cerrno>
 #include <chrono>
 #include <cstdio>
@@ -55,6 +57,13 @@ struct OpticalFlowBank::Impl {
 	aof_exposure_record *d_exposure;
 	aof_exposure_state *d_exposure_state;
 	aof_exposure_command *commands;    // pinned (aof_outbox_alloc_host): [n_streams]
+	// the IMU form (enableImu): samples queued by pushImu() for the next tick, [slots][n_streams] and their counts
+	bool imu;
+	aof_imu_params ip;
+	uint64_t imu_offset0;
+	uint8_t *h_imu, *d_imu;            // one block on both sides: aof_imu_sample [slots][n_streams], then u8 [n_streams]
+	size_t imu_bytes, off_imu_counts;
+	aof_imu_state *d_imu_state;
 };
 
 OpticalFlowBank::OpticalFlowBank(float f_length_x, float f_length_y, int output_rate, int img_width, int img_height,
@@ -122,6 +131,9 @@ OpticalFlowBank::~OpticalFlowBank()
 	// a bounded wait, as everywhere: memory a kernel may still write is leaked, not freed
 	const bool drained = !m->stream || waitIdle();
 	if (drained) {
+		if (m->d_imu_state) (void)hipFree(m->d_imu_state);
+		if (m->d_imu) (void)hipFree(m->d_imu);
+		if (m->h_imu) (void)hipHostFree(m->h_imu);
 		if (m->commands) aof_outbox_free_host(m->commands);
 		if (m->d_exposure_state) (void)hipFree(m->d_exposure_state);
 		if (m->d_exposure) (void)hipFree(m->d_exposure);
@@ -207,11 +219,15 @@ int OpticalFlowBank::push(const uint8_t *frames, const uint64_t *img_time_us, co
 	if (active) std::memcpy(m->h_stage + m->off_active, active, S);
 	if (hipMemcpyAsync(m->d_stage, m->h_stage, m->stage_bytes, hipMemcpyHostToDevice, m->stream) != hipSuccess)
 		return fail(-EIO, "copy of the tick's frames failed");
-	int rc = aof_bank_push_device(m->ctx, &m->bp, m->d_stage, reinterpret_cast<const uint64_t *>(m->d_stage + m->off_times),
+	// with the IMU form the tick leaves records only: the IMU call behind it completes them and packs the frames
+	aof_bank_params bp = m->bp;
+	if (m->imu) bp.offset_timestamp_usec = 0;
+	int rc = aof_bank_push_device(m->ctx, &bp, m->d_stage, reinterpret_cast<const uint64_t *>(m->d_stage + m->off_times),
 				      active ? m->d_stage + m->off_active : NULL,
-				      gyro ? reinterpret_cast<const aof_gyro *>(m->d_stage + m->off_gyro) : NULL, m->d_bank,
-				      m->bank_bytes, m->d_records, m->d_mavlink, m->d_lens, m->stream);
+				      gyro && !m->imu ? reinterpret_cast<const aof_gyro *>(m->d_stage + m->off_gyro) : NULL, m->d_bank,
+				      m->bank_bytes, m->d_records, m->imu ? NULL : m->d_mavlink, m->imu ? NULL : m->d_lens, m->stream);
 	if (rc) return fail(rc, aof_last_error(m->ctx));
+	if (m->imu && (rc = takeImu()) != 0) return rc;
 	return collect();
 }
 
@@ -230,6 +246,7 @@ int OpticalFlowBank::collect()
 	while (__atomic_load_n(word, __ATOMIC_ACQUIRE) != tag) {
 		if (secondsSince(t0) > kDeadlineS) return fail(-ETIMEDOUT, "the tick did not finish within the deadline");
 	}
+	if (m->imu) std::memset(m->h_imu + m->off_imu_counts, 0, (size_t)n_streams);   // the tick took the queued samples
 	return (int)reinterpret_cast<const aof_outbox_header *>(m->outbox)->n_messages;
 }
 
@@ -273,6 +290,11 @@ int OpticalFlowBank::enableCamera(int camera_width, int camera_height, uint16_t 
 	if (aof_bank_reset_device(m->ctx, &m->bp, NULL, m->d_bank, m->bank_bytes, m->stream) ||
 	    aof_bank_exposure_reset_device(m->ctx, n_streams, NULL, exposure0, gain0, NULL, NULL, m->d_exposure_state, m->stream))
 		return fail(-EIO, aof_last_error(m->ctx));
+	if (m->imu) {   // every stream starts over: its IMU state and the samples queued for it as well
+		if (aof_bank_imu_reset_device(m->ctx, n_streams, NULL, m->imu_offset0, m->d_imu_state, m->stream))
+			return fail(-EIO, aof_last_error(m->ctx));
+		std::memset(m->h_imu + m->off_imu_counts, 0, (size_t)n_streams);
+	}
 	if (!waitIdle()) return -ETIMEDOUT;
 	m->camera = true;
 	return 0;
@@ -295,12 +317,16 @@ int OpticalFlowBank::pushCamera(const uint8_t *sensor_frames, const uint64_t *im
 	    hipMemcpyAsync(m->d_stage + m->off_times, m->h_stage + m->off_times, m->stage_bytes - m->off_times,
 			   hipMemcpyHostToDevice, m->stream) != hipSuccess)
 		return fail(-EIO, "copy of the tick's sensor frames failed");
-	int rc = aof_bank_push_camera_device(m->ctx, &m->bp, &m->cam, m->d_sensor,
+	aof_bank_params bp = m->bp;
+	if (m->imu) bp.offset_timestamp_usec = 0;   // (records only, as in push())
+	int rc = aof_bank_push_camera_device(m->ctx, &bp, &m->cam, m->d_sensor,
 					     reinterpret_cast<const uint64_t *>(m->d_stage + m->off_times),
 					     active ? m->d_stage + m->off_active : NULL,
-					     gyro ? reinterpret_cast<const aof_gyro *>(m->d_stage + m->off_gyro) : NULL, m->d_bank,
-					     m->bank_bytes, m->d_records, m->d_exposure, NULL, m->d_mavlink, m->d_lens, m->stream);
+					     gyro && !m->imu ? reinterpret_cast<const aof_gyro *>(m->d_stage + m->off_gyro) : NULL, m->d_bank,
+					     m->bank_bytes, m->d_records, m->d_exposure, NULL, m->imu ? NULL : m->d_mavlink,
+					     m->imu ? NULL : m->d_lens, m->stream);
 	if (rc) return fail(rc, aof_last_error(m->ctx));
+	if (m->imu && (rc = takeImu()) != 0) return rc;
 	rc = aof_bank_exposure_control_device(m->ctx, &m->ec, n_streams, 1, m->d_exposure, m->d_exposure_state, m->commands,
 					      m->stream);
 	if (rc) return fail(rc, aof_last_error(m->ctx));
@@ -317,8 +343,79 @@ int OpticalFlowBank::reset(const uint8_t *mask)
 				   m->stream) != hipSuccess)
 			return fail(-EIO, "copy of the reset mask failed");
 	}
-	const int rc = aof_bank_reset_device(m->ctx, &m->bp, mask ? m->d_stage + m->off_active : NULL, m->d_bank, m->bank_bytes,
-					     m->stream);
+	int rc = aof_bank_reset_device(m->ctx, &m->bp, mask ? m->d_stage + m->off_active : NULL, m->d_bank, m->bank_bytes,
+				       m->stream);
 	if (rc) return fail(rc, aof_last_error(m->ctx));
+	if (m->imu) {
+		rc = aof_bank_imu_reset_device(m->ctx, n_streams, mask ? m->d_stage + m->off_active : NULL, m->imu_offset0,
+					       m->d_imu_state, m->stream);
+		if (rc) return fail(rc, aof_last_error(m->ctx));
+		// samples queued for a stream that starts over belong to its past: they are dropped with it
+		uint8_t *counts = m->h_imu + m->off_imu_counts;
+		for (int s = 0; s < n_streams; s++)
+			if (!mask || mask[s]) counts[s] = 0;
+	}
 	return waitIdle() ? 0 : -ETIMEDOUT;
+}
+
+int OpticalFlowBank::enableImu(int max_samples, uint64_t offset0)
+{
+	if (!engineOk()) return -1;
+	Impl *m = _m;
+	if (m->imu) return refuse(-EINVAL, "enableImu() was already called");
+	if (max_samples < 1 || max_samples > AOF_IMU_SLOTS_MAX) return refuse(-EINVAL, "enableImu(): max_samples outside 1..AOF_IMU_SLOTS_MAX");
+	if (!waitIdle()) return -ETIMEDOUT;
+	const size_t S = (size_t)n_streams;
+	m->off_imu_counts = (size_t)max_samples * S * sizeof(aof_imu_sample);
+	m->imu_bytes = alignUp(m->off_imu_counts + S, 256);
+	const bool ok = hipHostMalloc((void **)&m->h_imu, m->imu_bytes, hipHostMallocDefault) == hipSuccess &&
+			hipMalloc((void **)&m->d_imu, m->imu_bytes) == hipSuccess &&
+			hipMalloc((void **)&m->d_imu_state, S * sizeof(aof_imu_state)) == hipSuccess;
+	if (!ok) return fail(-ENOMEM, "device or pinned memory for the IMU samples could not be allocated");
+	std::memset(m->h_imu, 0, m->imu_bytes);
+	std::memset(&m->ip, 0, sizeof(m->ip));
+	m->ip.n_streams = n_streams;
+	m->ip.n_rounds = 1;
+	m->ip.max_samples = max_samples;
+	m->ip.system_id = m->bp.system_id;
+	m->ip.component_id = m->bp.component_id;
+	m->ip.first_seq = m->bp.first_seq;
+	m->imu_offset0 = offset0;
+	if (aof_bank_reset_device(m->ctx, &m->bp, NULL, m->d_bank, m->bank_bytes, m->stream) ||
+	    aof_bank_imu_reset_device(m->ctx, n_streams, NULL, offset0, m->d_imu_state, m->stream))
+		return fail(-EIO, aof_last_error(m->ctx));
+	if (!waitIdle()) return -ETIMEDOUT;
+	m->imu = true;
+	return 0;
+}
+
+int OpticalFlowBank::pushImu(int stream, uint64_t time_usec, float xgyro, float ygyro, float zgyro)
+{
+	if (!engineOk()) return -1;
+	Impl *m = _m;
+	if (!m->imu || stream < 0 || stream >= n_streams) return -EINVAL;
+	uint8_t *count = m->h_imu + m->off_imu_counts + stream;
+	if (*count >= m->ip.max_samples) return -ENOBUFS;
+	aof_imu_sample *slot = reinterpret_cast<aof_imu_sample *>(m->h_imu) + (size_t)*count * (size_t)n_streams + stream;
+	slot->time_usec = time_usec;
+	slot->xgyro = xgyro;
+	slot->ygyro = ygyro;
+	slot->zgyro = zgyro;
+	slot->reserved = 0;
+	*count += 1;
+	return 0;
+}
+
+// Behind a records-only tick: the queued samples to the device, the IMU call in place on the tick's records, and the
+// queue is empty again (collect() waits for the tick, so the pinned block is free when push() returns).
+int OpticalFlowBank::takeImu()
+{
+	Impl *m = _m;
+	if (hipMemcpyAsync(m->d_imu, m->h_imu, m->imu_bytes, hipMemcpyHostToDevice, m->stream) != hipSuccess)
+		return fail(-EIO, "copy of the tick's IMU samples failed");
+	const int rc = aof_bank_imu_device(m->ctx, &m->ip, reinterpret_cast<const aof_imu_sample *>(m->d_imu), m->d_imu + m->off_imu_counts,
+					   reinterpret_cast<const uint64_t *>(m->d_stage + m->off_times), m->d_records, m->d_imu_state,
+					   m->d_records, m->d_mavlink, m->d_lens, m->stream);
+	if (rc) return fail(rc, aof_last_error(m->ctx));
+	return 0;
 }

@@ -717,6 +717,90 @@ int aof_exposure_control_host(const aof_exposure_control *ec, int32_t n_streams,
                               const aof_exposure_record *records, aof_exposure_state *states,
                               aof_exposure_command *commands);
 
+/* ---- the stream bank's IMU: raw HIGHRES_IMU samples in, gyro sums and the send gates behind a push ----
+ * The gyro integrator of highres_imu_msg_callback (mainloop.cpp:383-405) and the two gates behind calcFlow() that
+ * decide whether a published record is really sent: the stale-gyro drop (mainloop.cpp:336-342) and "no vehicle time
+ * yet", with a time offset the first IMU message sets (mainloop.cpp:353-357, 403-404).  aof_bank_imu_device is a launch
+ * of its own, enqueued behind any of the four pushes (a tick is K = 1).  That push is called with d_gyro = NULL and
+ * for records only (offset_timestamp_usec = 0, no d_mavlink): the IMU call completes its records with the gyro sums,
+ * turns the quality of the records the reference would not send into AOF_TICK_STALE_GYRO / AOF_TICK_NO_OFFSET and packs
+ * the frames of the others.  The state array is the caller's device memory and no part of the bank.
+ * Each stream walks rounds k = 0 .. K-1 in order; in a round it first takes the round's samples j = 0 .. n-1 in order,
+ * then the round's record.  All arithmetic is IEEE double, every operation rounded on its own, nothing fused.
+ *   sample (t, x, y, z):
+ *     dt = (double)(uint64_t)(t - prev_time_usec) / 1e6          (u64 wrap: a time that runs backwards gives a huge dt;
+ *                                                                  a true division)
+ *     accepted iff prev_time_usec != 0 and dt < 0.05 and fabsf(x) < 20 and fabsf(y) < 20 and fabsf(z) < 20, each
+ *       compared as double (NaN and infinities fail; the reference's unqualified abs is read as the float overload):
+ *         gyro_x += (double)x * dt, likewise y and z;  samples_integrated++
+ *     rejected: samples_rejected++
+ *     prev_time_usec = t in every case;  if offset_timestamp_usec == 0: offset_timestamp_usec = t
+ *     Samples are taken in rounds in which the stream is idle, too.
+ *   record with quality < 0 (AOF_TICK_HELD, AOF_TICK_IDLE): copied unchanged, mavlink_len 0, the state untouched.
+ *   record with quality >= 0 (first frames included, as mainloop.cpp sends them):
+ *     g = (gyro_x, gyro_y, gyro_z); the sums are zeroed; the out record is the in record with gyro_x/y/z = (float)g
+ *     if last_taken_time_usec == prev_time_usec: quality = AOF_TICK_STALE_GYRO, dropped++
+ *     else: last_taken_time_usec = prev_time_usec; then
+ *       if offset_timestamp_usec == 0: quality = AOF_TICK_NO_OFFSET, dropped++
+ *       else the record is sent, its quality kept: the OPTICAL_FLOW_RAD frame of the push with time_usec =
+ *         offset_timestamp_usec + d_time_us[k][s], the record's dt_us, flows and quality, the doubles g and sequence
+ *         number (uint8_t)(first_seq + messages); messages++
+ *   A dropped or unsent record has mavlink_len 0.  As with the push, the bytes of a frame behind its length are not
+ *   written, and neither are frames of length 0.  Without d_mavlink decisions and counters are the same; only the
+ *   packing is skipped.
+ * aof_bank_collect_device runs unchanged on d_records_out, d_mavlink and d_mavlink_len: it selects quality >= 0, so the
+ * outbox then holds what the reference would send.  `messages` counts packed frames, as a MAVLink channel's sequence
+ * number does (the push's own counter counts every published record). */
+#define AOF_IMU_SLOTS_MAX 16
+#define AOF_TICK_STALE_GYRO (-3)  /* published by calcFlow, dropped: no IMU sample since the previous take (mainloop.cpp:337-341) */
+#define AOF_TICK_NO_OFFSET  (-4)  /* published, dropped: the stream has no vehicle time yet (mainloop.cpp:353-357) */
+
+typedef struct aof_imu_sample {   /* 24 bytes: the fields of HIGHRES_IMU the reference reads */
+    uint64_t time_usec; float xgyro, ygyro, zgyro; uint32_t reserved;
+} aof_imu_sample;
+
+typedef struct aof_imu_state {    /* 64 bytes, one per stream, caller-owned device memory beside the bank */
+    double gyro_x, gyro_y, gyro_z;      /* _gyro_integrated */
+    uint64_t prev_time_usec;            /* _gyro_prev_timestamp */
+    uint64_t last_taken_time_usec;      /* _gyro_last_usec_timestamp */
+    uint64_t offset_timestamp_usec;     /* _offset_timestamp_usec; 0 = not known yet */
+    uint32_t messages;                  /* frames packed so far: seq = first_seq + messages */
+    uint32_t samples_integrated, samples_rejected, dropped;
+} aof_imu_state;
+
+typedef struct aof_imu_params {
+    int32_t n_streams, n_rounds /* 1..AOF_BANK_BURST_MAX */, max_samples /* M: 1..AOF_IMU_SLOTS_MAX */;
+    uint8_t system_id, component_id, first_seq;
+} aof_imu_params;
+
+/* Masked streams (d_mask: u8 [S], or NULL = all) are zeroed and get offset_timestamp_usec = offset0; offset0 == 0: the
+ * stream learns the offset from its first sample.  A new state array must be reset once.
+ * -EINVAL: NULL ctx or state, n_streams < 1, a state array that is not 8-byte aligned; -EIO: the context's sticky
+ * fault.  Only enqueues. */
+int aof_bank_imu_reset_device(aof_ctx *ctx, int32_t n_streams, const uint8_t *d_mask, uint64_t offset0,
+                              aof_imu_state *d_state, void *stream);
+/* d_samples: aof_imu_sample [K][M][S], stream fastest: sample (k, j, s) at ((k*M + j)*S + s)*24 bytes.
+ * d_sample_count: u8 [K][S], the samples that arrived for stream s since its previous round and before round k's frame;
+ * NULL = M everywhere; a value above M counts as M (the kernel clamps it: the host cannot see device data).
+ * d_time_us: the u64 [K][S] array the push was given.  d_records_in: aof_tick_record [K][S], what the push wrote.
+ * d_records_out: [K][S], d_records_in itself or disjoint from it.  d_state: [S], updated in place.  d_mavlink: u8
+ * [K][S][AOF_SEQ_FRAME_BYTES] and d_mavlink_len: u8 [K][S]; both NULL, or neither.  The kernel ends with a system-scope
+ * release behind its stores: a host that has seen the tag of an aof_bank_collect_device enqueued behind it on the same
+ * stream may read outputs kept in aof_outbox_alloc_host memory without a synchronise.
+ * -EINVAL: NULL ctx, params, samples, times, records or state; n_streams < 1; n_rounds outside 1..AOF_BANK_BURST_MAX;
+ * max_samples outside 1..AOF_IMU_SLOTS_MAX; d_mavlink without its lengths or the reverse; samples, state or times not
+ * 8-byte aligned, records not 4-byte aligned; -EIO: the context's sticky fault.  A refused call writes nothing.  One
+ * launch; only enqueues: no allocation, no host synchronisation, capturable. */
+int aof_bank_imu_device(aof_ctx *ctx, const aof_imu_params *ip, const aof_imu_sample *d_samples,
+                        const uint8_t *d_sample_count, const uint64_t *d_time_us, const aof_tick_record *d_records_in,
+                        aof_imu_state *d_state, aof_tick_record *d_records_out, uint8_t *d_mavlink,
+                        uint8_t *d_mavlink_len, void *stream);
+/* The same function on host memory, a plain loop: no device, no context (what one camera's host would call, and the
+ * check of the device's bytes).  -EINVAL as above. */
+int aof_bank_imu_host(const aof_imu_params *ip, const aof_imu_sample *samples, const uint8_t *sample_count,
+                      const uint64_t *time_us, const aof_tick_record *records_in, aof_imu_state *states,
+                      aof_tick_record *records_out, uint8_t *mavlink, uint8_t *mavlink_len);
+
 /* ---- measurement ----
  * With profiling on, every launch is bracketed by HIP events on the stream it
  * is launched on; the last AOF_PROFILE_RING launches of each kernel are kept.

@@ -39,7 +39,8 @@ between the repeats is the run-to-run spread a difference between legs has to be
     python tools/bench_bank.py --camera > profiles/bank_camera_tick_sweep.txt
     python tools/bench_bank.py --burst 2,5,16 > profiles/bank_burst_sweep.txt
     python tools/bench_bank.py --outbox > profiles/bank_outbox_sweep.txt
-    python tools/bench_bank.py --exposure-control > profiles/bank_exposure_control_sweep.txt"""
+    python tools/bench_bank.py --exposure-control > profiles/bank_exposure_control_sweep.txt
+    python tools/bench_bank.py --imu > profiles/bank_imu_sweep.txt"""
 import argparse
 import ctypes as C
 import importlib
@@ -662,6 +663,159 @@ def exposure_sweep(a, dev):
               f"({'more' if gain > sp['C'] + sp['H'] else 'NOT more'} than the legs' spread)  H/C {m['H'] / m['C']:5.2f}")
 
 
+IMU_SAMPLES = 4      # HIGHRES_IMU samples per stream and frame round
+
+# Leg G's host: what a caller of the push with d_gyro runs per step -- the reference's integrator
+# (mainloop.cpp:383-405) over [K][M][S] samples, the round's sums written as aof_gyro [K][S] -- as one plain C loop,
+# compiled when the sweep starts.  The sample times advance by step_us in the same pass.
+HOST_LOOP_C = r"""
+#include <math.h>
+#include <stddef.h>
+#include <stdint.h>
+typedef struct { uint64_t t; float x, y, z; uint32_t r; } sample;
+typedef struct { float x, y, z, dt_s; } gyro;
+void integrate(sample *m, int K, int M, int S, uint64_t *prev, uint64_t step_us, gyro *out)
+{
+    for (int k = 0; k < K; k++)
+        for (int s = 0; s < S; s++) {
+            double gx = 0.0, gy = 0.0, gz = 0.0;
+            for (int j = 0; j < M; j++) {
+                sample *p = m + ((size_t)k * M + j) * S + s;
+                p->t += step_us;
+                const double dt = (double)(uint64_t)(p->t - prev[s]) / 1e6;
+                if (prev[s] != 0 && dt < 0.05 && fabsf(p->x) < 20.0 && fabsf(p->y) < 20.0 && fabsf(p->z) < 20.0) {
+                    gx += (double)p->x * dt; gy += (double)p->y * dt; gz += (double)p->z * dt;
+                }
+                prev[s] = p->t;
+            }
+            gyro *g = out + (size_t)k * S + s;
+            g->x = (float)gx; g->y = (float)gy; g->z = (float)gz; g->dt_s = 0.013333f;
+        }
+}
+"""
+_host_loop = []
+
+
+def host_loop():
+    """The compiled HOST_LOOP_C (cc -O2, once per process)."""
+    if not _host_loop:
+        import subprocess
+        import tempfile
+        tmp = tempfile.mkdtemp(prefix="bench_bank_imu_")
+        src, lib = os.path.join(tmp, "host_loop.c"), os.path.join(tmp, "host_loop.so")
+        with open(src, "w") as f:
+            f.write(HOST_LOOP_C)
+        subprocess.run(["cc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", src, "-o", lib, "-lm"], check=True)
+        fn = C.CDLL(lib).integrate
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
+        fn.restype = None
+        _host_loop.append(fn)
+    return _host_loop[0]
+
+
+def leg_imu(p, S, K, leg, inp, dev, a):
+    """G: the host integrates the samples in a plain C loop that writes aof_gyro [K][S] (host_loop), copies them to the
+    device and pushes with frames -- the way without the IMU call.  D: the samples are copied to the device, the push
+    leaves records only, aof_bank_imu_device completes them.  Both advance the sample times in pinned memory per step (G
+    inside its loop, D with one numpy add).  Returns (seconds per step, rounds timed)."""
+    eng = aof.FlowEngine(p, 0)
+    hip = hip_runtime()
+    M = IMU_SAMPLES
+    bp = aof.bank_params(S, FX, FY, 15, 5_000_000 if leg == "G" else 0, 1, 100, 0)
+    bank = eng.bank_create(bp, dev)
+    recs = torch.empty((K, S, 48), dtype=torch.uint8, device=dev)
+    wire = torch.empty((K, S, 56), dtype=torch.uint8, device=dev)
+    lens = torch.empty((K, S), dtype=torch.uint8, device=dev)
+    times = inp.times0.clone()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    ctx, burst = eng._ctx, aof.bank_burst_params(K)
+    h_samples = torch.empty((K, M, S, 24), dtype=torch.uint8, pin_memory=True)
+    samples = h_samples.numpy().view(aof.IMU_SAMPLE_DTYPE).reshape(K, M, S)
+    step_us = 13333 * K
+    # 300 Hz gyro samples that run on from step to step
+    samples["time_usec"] = (1_000_000 + (np.arange(K)[:, None, None] * M + np.arange(M)[None, :, None]) * (13333 // M)).astype(np.uint64)
+    samples["xgyro"], samples["ygyro"], samples["zgyro"], samples["reserved"] = 0.01, -0.02, 0.005, 0
+    sample_times = samples["time_usec"]
+    ip = aof.imu_params(S, K, M)
+    # (the pinned blocks are rewritten while an earlier step's copy may still be in flight: a real host would
+    # double-buffer; the bytes moved and the work done are the same)
+    if leg == "G":
+        gyro = torch.zeros((K, S, 4), dtype=torch.float32, device=dev)
+        h_gyro = torch.zeros((K, S, 4), dtype=torch.float32, pin_memory=True)
+        prev = np.zeros(S, np.uint64)
+        integrate = host_loop()
+        hargs = (h_samples.data_ptr(), K, M, S, prev.ctypes.data, step_us, h_gyro.data_ptr())
+        copy = (gyro.data_ptr(), h_gyro.data_ptr(), gyro.numel() * 4, 1, stream)             # hipMemcpyHostToDevice
+        tail = (inp.frames.data_ptr(), times.data_ptr(), None, gyro.data_ptr(), bank.buffer.data_ptr(), bank.buffer.numel(),
+                recs.data_ptr(), wire.data_ptr(), lens.data_ptr(), stream)
+    else:
+        d_samples = torch.empty((K, M, S, 24), dtype=torch.uint8, device=dev)
+        state = torch.zeros((S, 64), dtype=torch.uint8, device=dev)
+        eng.bank_imu_reset(state, offset0=5_000_000)
+        copy = (d_samples.data_ptr(), h_samples.data_ptr(), d_samples.numel(), 1, stream)
+        imu = aof.lib.aof_bank_imu_device
+        iargs = (ctx, C.byref(ip), d_samples.data_ptr(), None, times.data_ptr(), recs.data_ptr(), state.data_ptr(), recs.data_ptr(),
+                 wire.data_ptr(), lens.data_ptr(), stream)
+        tail = (inp.frames.data_ptr(), times.data_ptr(), None, None, bank.buffer.data_ptr(), bank.buffer.numel(),
+                recs.data_ptr(), None, None, stream)
+    if K == 1:
+        push, head = aof.lib.aof_bank_push_device, (ctx, C.byref(bp))
+    else:
+        push, head = aof.lib.aof_bank_push_burst_device, (ctx, C.byref(bp), C.byref(burst))
+
+    def step():
+        times.add_(step_us)
+        if leg == "G":
+            integrate(*hargs)
+        else:
+            np.add(sample_times, step_us, out=sample_times)
+        if hip.hipMemcpyAsync(*copy):
+            raise RuntimeError("hipMemcpyAsync failed")
+        rc = push(*head, *tail)
+        if rc == 0 and leg == "D":
+            rc = imu(*iargs)
+        if rc:
+            raise aof.AofError(rc, aof.lib.aof_last_error(ctx).decode())
+    out_t = timed_bursts(step, torch.cuda.synchronize, K, a.ticks, a.seconds, a.settle)
+    torch.cuda.synchronize()
+    r = aof.ticks_view(recs[K - 1])
+    assert (r["frame"] > a.ticks).all(), "the timed rounds were real ticks"
+    if leg == "G":
+        assert (h_gyro.numpy()[..., 0] > 0).all(), "the host loop integrated"
+    else:
+        assert (aof.imu_states_view(state)["samples_integrated"] > 0).all(), "the device integrated"
+    eng.close()
+    return out_t[0], out_t[1]
+
+
+def imu_sweep(a, dev):
+    print("# legs: G host loop over the samples (a plain C loop that writes aof_gyro [K][S]) + H2D copy of aof_gyro [K][S] + push with frames "
+          "(the way without the IMU call), D H2D copy of the samples + records-only push + aof_bank_imu_device")
+    print(f"# us = microseconds per step (a tick, or a burst of K rounds) of 64x64 streams, {IMU_SAMPLES} samples per stream and round; "
+          "host clock around chunks of steps ending in a synchronise")
+    p = params_of("px4-64")
+    cases = [(K, S) for K in (1, 5) for S in (int(s) for s in a.streams.split(","))]
+    results = {}
+    for rep in range(a.repeats):
+        for K, S in cases:
+            inp = BurstInputs(p, S, K, dev)
+            for leg in ("G", "D"):
+                sec, n = leg_imu(p, S, K, leg, inp, dev, a)
+                results.setdefault((K, S, leg), []).append(sec)
+                print(f"rep {rep} px4-64 K={K:2d} S={S:6d} {leg} {sec * 1e6:10.2f} us  ({n} rounds)", flush=True)
+            del inp
+            torch.cuda.empty_cache()
+    print("# ---- summary (mean of the repeats; spread = |difference of the repeats| / mean) ----")
+    for K, S in cases:
+        m = {leg: float(np.mean(results[(K, S, leg)])) for leg in "GD"}
+        sp = {leg: abs(results[(K, S, leg)][0] - results[(K, S, leg)][-1]) / m[leg] for leg in "GD"}
+        gain = (m["G"] - m["D"]) / m["G"]
+        clear = abs(gain) > sp["G"] + sp["D"]
+        print(f"px4-64 K={K:2d} S={S:6d}  " + "  ".join(f"{leg} {m[leg] * 1e6:9.2f} (+-{sp[leg] * 100:4.1f} %)" for leg in "GD") +
+              f"  G/D {m['G'] / m['D']:5.2f}  {'D' if gain > 0 else 'G'} wins by {abs(gain) * 100:5.1f} % "
+              f"({'more' if clear else 'NOT more'} than the legs' spread)")
+
+
 def leg_contexts(p, S, inp, a):
     engs = [aof.FlowEngine(p, 0) for _ in range(S)]
     flow = np.zeros(1, aof.FLOW_DTYPE)
@@ -731,6 +885,7 @@ def main():
     ap.add_argument("--burst", default="", help="K[,K...]: the sweep of bursts of K rounds against K single ticks (legs B0-B2, T0-T2)")
     ap.add_argument("--outbox", action="store_true", help="the sweep of the outbox: legs T, D, H, O")
     ap.add_argument("--exposure-control", action="store_true", help="the sweep of the auto-exposure controller: legs T, C, H")
+    ap.add_argument("--imu", action="store_true", help="the sweep of the IMU call: legs G, D")
     ap.add_argument("--forms", default="plain,camera", help="--burst: entry points to sweep")
     ap.add_argument("--input-bytes-max", type=float, default=24 * 2**30, help="--burst: sizes whose K rounds of input exceed this are skipped")
     a = ap.parse_args()
@@ -740,6 +895,8 @@ def main():
         a.streams = "1,64,1024,1536,2048,4096"
     if a.exposure_control and a.streams == ap.get_default("streams"):
         a.streams = "64,1024,4096"
+    if a.imu and a.streams == ap.get_default("streams"):
+        a.streams = "64,256,1024,4096"
     if a.outbox and a.streams == ap.get_default("streams"):
         a.streams = "64,256,1024,4096,16384"
     if not torch.cuda.is_available():
@@ -749,6 +906,8 @@ def main():
     print(f"# device: {torch.cuda.get_device_name(0)}")
     if not a.no_marker:
         print(f"# class marker: exhaustive C2 K2 (1 024 VGA pairs) {class_marker(dev):.4f} ms")
+    if a.imu:
+        return imu_sweep(a, dev)
     if a.exposure_control:
         return exposure_sweep(a, dev)
     if a.outbox:
