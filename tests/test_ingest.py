@@ -9,17 +9,7 @@ import math
 import numpy as np
 import pytest
 
-
-def np_ingest(cam, crop_w, crop_h):
-    h, w = cam.shape
-    x0, y0 = w // 2 - crop_w // 2, h // 2 - crop_h // 2
-    crop = cam[y0:y0 + crop_h, x0:x0 + crop_w].copy()
-    mx0, my0 = max(crop_w // 2 - 64, 0), max(crop_h // 2 - 64, 0)
-    mx1, my1 = min(crop_w // 2 + 64, crop_w), min(crop_h // 2 + 64, crop_h)
-    m = crop[my0:my1, mx0:mx1].astype(np.float64)
-    idx = np.floor(m * (10 / 255.0)).astype(np.int64)
-    hist = np.bincount(idx[idx < 10].ravel(), minlength=10).astype(np.uint32)
-    return crop, hist
+from ingest_ref import ingest as np_ingest   # the numpy model (tests/ingest_ref.py)
 
 
 def test_exposure_bin_matches_calchist_formula(orc, aof):
