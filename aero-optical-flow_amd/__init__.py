@@ -143,6 +143,18 @@ IMU_STATE_DTYPE = np.dtype([("gyro_x", "<f8"), ("gyro_y", "<f8"), ("gyro_z", "<f
 assert IMU_SAMPLE_DTYPE.itemsize == 24 and IMU_STATE_DTYPE.itemsize == 64
 
 
+class MavlinkRxParams(C.Structure):
+    """``aof_mavlink_rx_params`` (include/aof.h)."""
+    _fields_ = [("n_streams", C.c_int32), ("n_rounds", C.c_int32), ("max_bytes", C.c_int32), ("max_samples", C.c_int32)]
+
+
+MAVLINK_RX_BYTES_MAX = 4096
+MAVLINK_RX_STATE_DTYPE = np.dtype([("bytes", "<u8"), ("frames", "<u4"), ("imu_samples", "<u4"), ("bad_check", "<u4"),
+                                   ("overflowed", "<u4"), ("skipped", "<u4"), ("rejected_flags", "<u4"),
+                                   ("in_progress", "u1", (96,))])                                   # aof_mavlink_rx_state
+assert MAVLINK_RX_STATE_DTYPE.itemsize == 128
+
+
 class OutboxLayout(C.Structure):
     """``struct aof_outbox_layout`` (include/aof.h)."""
     _fields_ = [(n, C.c_size_t) for n in ("total_bytes", "messages", "exposures")]
@@ -260,6 +272,9 @@ def _load():
         "aof_bank_imu_reset_device": (C.c_int, [VP, C.c_int32, VP, C.c_uint64, VP, VP]),
         "aof_bank_imu_device": (C.c_int, [VP, P(ImuParams), VP, VP, VP, VP, VP, VP, VP, VP, VP]),
         "aof_bank_imu_host": (C.c_int, [P(ImuParams), VP, VP, VP, VP, VP, VP, VP, VP]),
+        "aof_bank_mavlink_rx_reset_device": (C.c_int, [VP, C.c_int32, VP, VP, VP]),
+        "aof_bank_mavlink_rx_device": (C.c_int, [VP, P(MavlinkRxParams), VP, VP, VP, VP, VP, VP]),
+        "aof_bank_mavlink_rx_host": (C.c_int, [P(MavlinkRxParams), VP, VP, VP, VP, VP]),
         "aof_derotate_batch_device": (C.c_int, [P(DerotateParams), VP, VP, I64, VP, VP]),
         "aof_exposure_msv": (C.c_float, [VP]),
         "aof_exposure_bin": (C.c_int, [C.c_int]),
@@ -581,6 +596,56 @@ def imu_states_view(t) -> np.ndarray:
     """uint8 tensor/array [S, 64] of ``aof_imu_state`` -> structured numpy view [S]."""
     a = t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
     return np.ascontiguousarray(a).view(IMU_STATE_DTYPE).reshape(a.shape[:-1])
+
+
+def mavlink_rx_params(n_streams, n_rounds, max_bytes, max_samples) -> MavlinkRxParams:
+    rp = MavlinkRxParams()
+    rp.n_streams, rp.n_rounds, rp.max_bytes, rp.max_samples = int(n_streams), int(n_rounds), int(max_bytes), int(max_samples)
+    return rp
+
+
+def _aligned_copy(a, align=16):
+    """A C-contiguous copy of uint8 array `a` whose first byte lies at a multiple of `align`."""
+    raw = np.empty(a.size + align, np.uint8)
+    off = -raw.ctypes.data % align
+    out = raw[off:off + a.size].reshape(a.shape)
+    out[...] = a
+    return out
+
+
+def bank_mavlink_rx_host(data, lengths, states, max_samples, samples=None, counts=None):
+    """``aof_bank_mavlink_rx_host``: the MAVLink receive on host memory, no device.  data: uint8 [K, S, B], what stream
+    s received for round k in its first lengths[k, s] bytes; lengths: uint16 [K, S] or None (B everywhere); states:
+    MAVLINK_RX_STATE_DTYPE [S], contiguous, updated IN PLACE; samples: an IMU_SAMPLE_DTYPE [K, M, S] array to write
+    (slots at and behind a count keep what they hold) or None (a new one, zero-filled); counts likewise, uint8 [K, S].
+    Returns (samples, counts)."""
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    K, S, B = data.shape
+    M = int(max_samples)
+    if data.ctypes.data % 16:
+        data = _aligned_copy(data)
+    if lengths is not None:
+        lengths = np.ascontiguousarray(lengths, dtype=np.uint16)
+        assert lengths.shape == (K, S)
+    assert states.dtype == MAVLINK_RX_STATE_DTYPE and states.shape == (S,) and states.flags.c_contiguous and states.flags.writeable
+    if samples is None:
+        samples = np.zeros((K, M, S), IMU_SAMPLE_DTYPE)
+    if counts is None:
+        counts = np.zeros((K, S), np.uint8)
+    assert samples.dtype == IMU_SAMPLE_DTYPE and samples.shape == (K, M, S) and samples.flags.c_contiguous
+    assert counts.dtype == np.uint8 and counts.shape == (K, S) and counts.flags.c_contiguous
+    rp = mavlink_rx_params(S, K, B, M)
+    rc = lib.aof_bank_mavlink_rx_host(C.byref(rp), data.ctypes.data, lengths.ctypes.data if lengths is not None else None,
+                                      states.ctypes.data, samples.ctypes.data, counts.ctypes.data)
+    if rc:
+        raise AofError(rc, lib.aof_strerror(rc).decode())
+    return samples, counts
+
+
+def mavlink_rx_states_view(t) -> np.ndarray:
+    """uint8 tensor/array [S, 128] of ``aof_mavlink_rx_state`` -> structured numpy view [S]."""
+    a = t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+    return np.ascontiguousarray(a).view(MAVLINK_RX_STATE_DTYPE).reshape(a.shape[:-1])
 
 
 def exposure_states_view(t) -> np.ndarray:
@@ -1053,6 +1118,41 @@ class FlowEngine:
                                             ptr(out_lengths), torch.cuda.current_stream(dev).cuda_stream))
         return records_out, out_frames, out_lengths
 
+    def bank_mavlink_rx_reset(self, state, mask=None):
+        """aof_bank_mavlink_rx_reset_device: state uint8 CUDA tensor [S, 128] (``aof_mavlink_rx_state``; read it with
+        mavlink_rx_states_view()); mask uint8 [S] (non-zero = reset) or None (all).  Enqueued on torch's current stream."""
+        import torch
+        S = state.numel() // 128
+        assert state.dtype == torch.uint8 and state.is_contiguous() and state.numel() == 128 * S
+        assert mask is None or (mask.dtype == torch.uint8 and mask.numel() == S and mask.is_contiguous())
+        self._check(lib.aof_bank_mavlink_rx_reset_device(self._ctx, S, mask.data_ptr() if mask is not None else None,
+                                                         state.data_ptr(), torch.cuda.current_stream(state.device).cuda_stream))
+
+    def bank_mavlink_rx(self, data, state, max_samples, lengths=None, samples=None, counts=None):
+        """aof_bank_mavlink_rx_device in front of bank_imu(): data uint8 CUDA tensor [K, S, B] (or [S, B] for a tick), what
+        each stream received; lengths: a tensor of K * S 16-bit elements (the received byte counts) or None (B everywhere);
+        state uint8 [S, 128], stepped in place; samples uint8 [K, M, S, 24] / [M, S, 24] and counts uint8 [K, S] / [S]:
+        tensors to write or None (new ones, zero-filled) -- what bank_imu() takes.  Enqueued on torch's current stream.
+        Returns (samples, counts)."""
+        import torch
+        dev = data.device
+        assert data.dtype == torch.uint8 and data.is_contiguous() and data.dim() in (2, 3)
+        K, S, B = (1,) + tuple(data.shape) if data.dim() == 2 else tuple(data.shape)
+        M = int(max_samples)
+        assert state.dtype == torch.uint8 and state.is_contiguous() and state.numel() == 128 * S
+        assert lengths is None or (lengths.element_size() == 2 and lengths.is_contiguous() and lengths.numel() == K * S)
+        if samples is None:
+            samples = torch.zeros(((K,) if data.dim() == 3 else ()) + (M, S, 24), dtype=torch.uint8, device=dev)
+        if counts is None:
+            counts = torch.zeros(tuple(data.shape[:-1]), dtype=torch.uint8, device=dev)
+        assert samples.dtype == torch.uint8 and samples.is_contiguous() and samples.numel() == K * M * S * 24
+        assert counts.dtype == torch.uint8 and counts.is_contiguous() and counts.numel() == K * S
+        rp = mavlink_rx_params(S, K, B, M)
+        self._check(lib.aof_bank_mavlink_rx_device(self._ctx, C.byref(rp), data.data_ptr(),
+                                                   lengths.data_ptr() if lengths is not None else None, state.data_ptr(),
+                                                   samples.data_ptr(), counts.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        return samples, counts
+
     def set_bank_path(self, path=0):
         """0: the library chooses between the one-launch tick kernel and the composed path, 1: the tick kernel where
         the configuration allows it, 2: always the composed path.  Same bytes either way."""
@@ -1178,6 +1278,8 @@ def facade_lib():
         f.aof_facade_bank_push_camera.argtypes = [C.c_void_p] * 5
         f.aof_facade_bank_enable_imu.argtypes = [C.c_void_p, C.c_int, C.c_uint64]
         f.aof_facade_bank_push_imu.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_float, C.c_float, C.c_float]
+        f.aof_facade_bank_enable_mavlink_rx.argtypes = [C.c_void_p, C.c_int]
+        f.aof_facade_bank_push_mavlink.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         f.aof_facade_bank_exposure_commands.restype = C.c_void_p
         f.aof_facade_bank_exposure_commands.argtypes = [C.c_void_p]
         f.aof_facade_bank_published.restype = C.c_void_p
@@ -1354,6 +1456,18 @@ class OpticalFlowBank:
     def pushImu(self, stream, time_usec, xgyro, ygyro, zgyro):
         """One HIGHRES_IMU sample for the stream's next tick: 0, -ENOBUFS (the stream's queue is full), -EINVAL."""
         return facade_lib().aof_facade_bank_push_imu(self._h, int(stream), int(time_usec), float(xgyro), float(ygyro), float(zgyro))
+
+    def enableMavlinkRx(self, max_bytes):
+        """The receive path behind enableImu(): pushMavlink() queues the bytes a stream's connection received, and the
+        device parses them into the samples of the stream's next tick; pushImu() then answers -EINVAL.  max_bytes: a
+        stream's bytes per tick, 16..4096 and a multiple of 16.  Returns 0 or a negative value."""
+        return facade_lib().aof_facade_bank_enable_mavlink_rx(self._h, int(max_bytes))
+
+    def pushMavlink(self, stream, data):
+        """Appends received bytes to the stream's slot for its next tick: 0, -ENOBUFS (they do not fit: nothing is
+        taken), -EINVAL."""
+        data = np.frombuffer(bytes(data), np.uint8)
+        return facade_lib().aof_facade_bank_push_mavlink(self._h, int(stream), data.ctypes.data if data.size else None, int(data.size))
 
     def exposureCommands(self):
         """A copy of the last pushCamera()'s commands (EXPOSURE_COMMAND_DTYPE [n_streams]); None without enableCamera()."""

@@ -389,6 +389,18 @@ struct ImuArgs {
 };
 int launch_bank_imu(const ImuArgs &a, void *stream);
 int launch_bank_imu_reset(aof_imu_state *state, const uint8_t *mask, uint32_t n_streams, uint64_t offset0, void *stream);
+// The MAVLink receive in front of the IMU call (aof_bank_mavlink_rx_device / aof_bank_mavlink_rx_reset_device,
+// aof_mavlink_rx.cpp, k_bank_mavlink_rx.hip): a lane per stream takes the stream's bytes and writes its samples.
+struct MavlinkRxArgs {
+    uint32_t n_streams, n_rounds, max_bytes, max_samples;   // S, K, B (16..4096, a multiple of 16), M
+    const uint8_t *bytes;              // [K][S][B], 16-byte aligned
+    const uint16_t *len;               // [K][S] or nullptr (B everywhere)
+    aof_mavlink_rx_state *state;       // [S]
+    uint8_t *samples;                  // aof_imu_sample [K][M][S]
+    uint8_t *sample_count;             // [K][S]
+};
+int launch_bank_mavlink_rx(const MavlinkRxArgs &a, void *stream);
+int launch_bank_mavlink_rx_reset(aof_mavlink_rx_state *state, const uint8_t *mask, uint32_t n_streams, void *stream);
 // (aof_batch.cpp) the small-pair plan of n pairs, whatever n: true where one workgroup per pair can serve the
 // context's configuration and these buffers (flows: [n]; d_workspace: aof_workspace_layout(p, n))
 bool plan_small_batch(const aof_ctx *ctx, const uint8_t *prev, const uint8_t *cur, int64_t stride, int64_t n, aof_flow *flows,

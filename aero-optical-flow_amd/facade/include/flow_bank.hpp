@@ -79,6 +79,22 @@ public:
 	// index or without enableImu().
 	int pushImu(int stream, uint64_t time_usec, float xgyro, float ygyro, float zgyro);
 
+	// The receive path behind enableImu(): what mavlink_tcp.cpp:100-129 does with the autopilot's byte stream
+	// (mavlink_parse_char byte by byte, HIGHRES_IMU decoded) moves behind push() and pushCamera() for every stream
+	// (aof_bank_mavlink_rx_device, include/aof.h: the written contract of the parser).  enableMavlinkRx() allocates
+	// the per-stream receive state and a pinned staging buffer of max_bytes (16..AOF_MAVLINK_RX_BYTES_MAX, a multiple
+	// of 16) per stream and tick; samples queued by pushImu() are dropped.  From then on a push runs receive, tick,
+	// IMU call, (exposure control,) collect on the object's stream, a frame cut by the end of a tick's bytes is
+	// completed by the next tick's, and pushImu() answers -EINVAL.  A tick keeps the first max_samples samples of a
+	// stream (the receive state counts the others as overflowed).  reset() also drops a masked stream's half-received
+	// frame and queued bytes.  Returns 0, or a negative value: -EINVAL without enableImu(), for a second call or a
+	// bad max_bytes (refused: the object is as it was), anything else as enableCamera().
+	int enableMavlinkRx(int max_bytes);
+	// Appends n bytes a stream's connection received (any cut of the byte stream) to its slot for the next tick.
+	// Returns 0; -ENOBUFS, the object unchanged, when the slot cannot hold n more bytes; -EINVAL for a bad stream
+	// index, a negative n, NULL bytes or without enableMavlinkRx().
+	int pushMavlink(int stream, const uint8_t *bytes, int n);
+
 	inline int getStreams() const { return n_streams; }
 	inline int getImageWidth() const { return image_width; }
 	inline int getImageHeight() const { return image_height; }
@@ -94,6 +110,7 @@ private:
 	bool waitIdle();
 	int collect();
 	int takeImu();
+	int receive();
 
 	int image_width, image_height, n_streams;
 	struct Impl;

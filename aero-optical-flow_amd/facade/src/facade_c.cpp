@@ -106,6 +106,14 @@ int aof_facade_bank_push_imu(void *bank, int stream, uint64_t time_usec, float x
 {
 	return static_cast<OpticalFlowBank *>(bank)->pushImu(stream, time_usec, xgyro, ygyro, zgyro);
 }
+int aof_facade_bank_enable_mavlink_rx(void *bank, int max_bytes)
+{
+	return static_cast<OpticalFlowBank *>(bank)->enableMavlinkRx(max_bytes);
+}
+int aof_facade_bank_push_mavlink(void *bank, int stream, const uint8_t *bytes, int n)
+{
+	return static_cast<OpticalFlowBank *>(bank)->pushMavlink(stream, bytes, n);
+}
 const void *aof_facade_bank_exposure_commands(void *bank) { return static_cast<OpticalFlowBank *>(bank)->exposureCommands(); }
 const void *aof_facade_bank_published(void *bank) { return static_cast<OpticalFlowBank *>(bank)->published(); }
 int aof_facade_bank_reset(void *bank, const uint8_t *mask) { return static_cast<OpticalFlowBank *>(bank)->reset(mask); }

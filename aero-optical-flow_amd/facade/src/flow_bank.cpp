@@ -6,7 +6,9 @@
 // (aof_bank_exposure_control_device) between the tick and the collect launch: its commands land in pinned
 // memory in front of the tag.  With enableImu() the tick leaves records only and the IMU call
 // (aof_bank_imu_device) behind it takes the samples pushImu() queued, completes the records in place and packs the
-// frames, so that the collect launch lists only what the reference would have sent.
+// frames, so that the collect launch lists only what the reference would have sent.  With enableMavlinkRx() the
+// samples come from the device as well: the bytes pushMavlink() queued go over in one copy, and the receive launch
+// (aof_bank_mavlink_rx_device) in front of the tick parses them into the sample block the IMU call reads.
 #include <cerrno>
 #include <chrono>
 #include <cstdio>
@@ -64,6 +66,13 @@ struct OpticalFlowBank::Impl {
 	uint8_t *h_imu, *d_imu;            // one block on both sides: aof_imu_sample [slots][n_streams], then u8 [n_streams]
 	size_t imu_bytes, off_imu_counts;
 	aof_imu_state *d_imu_state;
+	// the receive path (enableMavlinkRx): bytes queued by pushMavlink() for the next tick, [n_streams][max_bytes], and
+	// their lengths
+	bool rx;
+	aof_mavlink_rx_params rp;
+	uint8_t *h_rx, *d_rx;              // one block on both sides: u8 [n_streams][max_bytes], then u16 [n_streams]
+	size_t rx_bytes, off_rx_len;
+	aof_mavlink_rx_state *d_rx_state;
 };
 
 OpticalFlowBank::OpticalFlowBank(float f_length_x, float f_length_y, int output_rate, int img_width, int img_height,
@@ -131,6 +140,9 @@ OpticalFlowBank::~OpticalFlowBank()
 	// a bounded wait, as everywhere: memory a kernel may still write is leaked, not freed
 	const bool drained = !m->stream || waitIdle();
 	if (drained) {
+		if (m->d_rx_state) (void)hipFree(m->d_rx_state);
+		if (m->d_rx) (void)hipFree(m->d_rx);
+		if (m->h_rx) (void)hipHostFree(m->h_rx);
 		if (m->d_imu_state) (void)hipFree(m->d_imu_state);
 		if (m->d_imu) (void)hipFree(m->d_imu);
 		if (m->h_imu) (void)hipHostFree(m->h_imu);
@@ -217,6 +229,10 @@ int OpticalFlowBank::push(const uint8_t *frames, const uint64_t *img_time_us, co
 	std::memcpy(m->h_stage + m->off_times, img_time_us, S * sizeof(uint64_t));
 	if (gyro) std::memcpy(m->h_stage + m->off_gyro, gyro, S * sizeof(aof_gyro));
 	if (active) std::memcpy(m->h_stage + m->off_active, active, S);
+	if (m->rx) {
+		const int rrc = receive();
+		if (rrc) return rrc;
+	}
 	if (hipMemcpyAsync(m->d_stage, m->h_stage, m->stage_bytes, hipMemcpyHostToDevice, m->stream) != hipSuccess)
 		return fail(-EIO, "copy of the tick's frames failed");
 	// with the IMU form the tick leaves records only: the IMU call behind it completes them and packs the frames
@@ -247,6 +263,7 @@ int OpticalFlowBank::collect()
 		if (secondsSince(t0) > kDeadlineS) return fail(-ETIMEDOUT, "the tick did not finish within the deadline");
 	}
 	if (m->imu) std::memset(m->h_imu + m->off_imu_counts, 0, (size_t)n_streams);   // the tick took the queued samples
+	if (m->rx) std::memset(m->h_rx + m->off_rx_len, 0, (size_t)n_streams * sizeof(uint16_t));   // and the queued bytes
 	return (int)reinterpret_cast<const aof_outbox_header *>(m->outbox)->n_messages;
 }
 
@@ -295,6 +312,11 @@ int OpticalFlowBank::enableCamera(int camera_width, int camera_height, uint16_t 
 			return fail(-EIO, aof_last_error(m->ctx));
 		std::memset(m->h_imu + m->off_imu_counts, 0, (size_t)n_streams);
 	}
+	if (m->rx) {    // and its receive state and queued bytes
+		if (aof_bank_mavlink_rx_reset_device(m->ctx, n_streams, NULL, m->d_rx_state, m->stream))
+			return fail(-EIO, aof_last_error(m->ctx));
+		std::memset(m->h_rx + m->off_rx_len, 0, (size_t)n_streams * sizeof(uint16_t));
+	}
 	if (!waitIdle()) return -ETIMEDOUT;
 	m->camera = true;
 	return 0;
@@ -313,6 +335,10 @@ int OpticalFlowBank::pushCamera(const uint8_t *sensor_frames, const uint64_t *im
 	std::memcpy(m->h_stage + m->off_times, img_time_us, S * sizeof(uint64_t));
 	if (gyro) std::memcpy(m->h_stage + m->off_gyro, gyro, S * sizeof(aof_gyro));
 	if (active) std::memcpy(m->h_stage + m->off_active, active, S);
+	if (m->rx) {
+		const int rrc = receive();
+		if (rrc) return rrc;
+	}
 	if (hipMemcpyAsync(m->d_sensor, m->h_sensor, m->sensor_bytes, hipMemcpyHostToDevice, m->stream) != hipSuccess ||
 	    hipMemcpyAsync(m->d_stage + m->off_times, m->h_stage + m->off_times, m->stage_bytes - m->off_times,
 			   hipMemcpyHostToDevice, m->stream) != hipSuccess)
@@ -355,6 +381,14 @@ int OpticalFlowBank::reset(const uint8_t *mask)
 		for (int s = 0; s < n_streams; s++)
 			if (!mask || mask[s]) counts[s] = 0;
 	}
+	if (m->rx) {   // likewise a frame half received and the bytes queued
+		rc = aof_bank_mavlink_rx_reset_device(m->ctx, n_streams, mask ? m->d_stage + m->off_active : NULL, m->d_rx_state,
+						      m->stream);
+		if (rc) return fail(rc, aof_last_error(m->ctx));
+		uint16_t *lens = reinterpret_cast<uint16_t *>(m->h_rx + m->off_rx_len);
+		for (int s = 0; s < n_streams; s++)
+			if (!mask || mask[s]) lens[s] = 0;
+	}
 	return waitIdle() ? 0 : -ETIMEDOUT;
 }
 
@@ -393,7 +427,7 @@ int OpticalFlowBank::pushImu(int stream, uint64_t time_usec, float xgyro, float 
 {
 	if (!engineOk()) return -1;
 	Impl *m = _m;
-	if (!m->imu || stream < 0 || stream >= n_streams) return -EINVAL;
+	if (!m->imu || m->rx || stream < 0 || stream >= n_streams) return -EINVAL;   // (with the receive path the device counts)
 	uint8_t *count = m->h_imu + m->off_imu_counts + stream;
 	if (*count >= m->ip.max_samples) return -ENOBUFS;
 	aof_imu_sample *slot = reinterpret_cast<aof_imu_sample *>(m->h_imu) + (size_t)*count * (size_t)n_streams + stream;
@@ -411,11 +445,68 @@ int OpticalFlowBank::pushImu(int stream, uint64_t time_usec, float xgyro, float 
 int OpticalFlowBank::takeImu()
 {
 	Impl *m = _m;
-	if (hipMemcpyAsync(m->d_imu, m->h_imu, m->imu_bytes, hipMemcpyHostToDevice, m->stream) != hipSuccess)
+	// (with the receive path the samples and their counts are on the device already: receive() wrote them)
+	if (!m->rx && hipMemcpyAsync(m->d_imu, m->h_imu, m->imu_bytes, hipMemcpyHostToDevice, m->stream) != hipSuccess)
 		return fail(-EIO, "copy of the tick's IMU samples failed");
 	const int rc = aof_bank_imu_device(m->ctx, &m->ip, reinterpret_cast<const aof_imu_sample *>(m->d_imu), m->d_imu + m->off_imu_counts,
 					   reinterpret_cast<const uint64_t *>(m->d_stage + m->off_times), m->d_records, m->d_imu_state,
 					   m->d_records, m->d_mavlink, m->d_lens, m->stream);
+	if (rc) return fail(rc, aof_last_error(m->ctx));
+	return 0;
+}
+
+int OpticalFlowBank::enableMavlinkRx(int max_bytes)
+{
+	if (!engineOk()) return -1;
+	Impl *m = _m;
+	if (!m->imu) return refuse(-EINVAL, "enableMavlinkRx() needs enableImu()");
+	if (m->rx) return refuse(-EINVAL, "enableMavlinkRx() was already called");
+	if (max_bytes < 16 || max_bytes > AOF_MAVLINK_RX_BYTES_MAX || max_bytes % 16)
+		return refuse(-EINVAL, "enableMavlinkRx(): max_bytes outside 16..AOF_MAVLINK_RX_BYTES_MAX or no multiple of 16");
+	if (!waitIdle()) return -ETIMEDOUT;
+	const size_t S = (size_t)n_streams;
+	m->off_rx_len = S * (size_t)max_bytes;
+	m->rx_bytes = alignUp(m->off_rx_len + S * sizeof(uint16_t), 256);
+	const bool ok = hipHostMalloc((void **)&m->h_rx, m->rx_bytes, hipHostMallocDefault) == hipSuccess &&
+			hipMalloc((void **)&m->d_rx, m->rx_bytes) == hipSuccess &&
+			hipMalloc((void **)&m->d_rx_state, S * sizeof(aof_mavlink_rx_state)) == hipSuccess;
+	if (!ok) return fail(-ENOMEM, "device or pinned memory for the MAVLink bytes could not be allocated");
+	std::memset(m->h_rx, 0, m->rx_bytes);
+	m->rp.n_streams = n_streams;
+	m->rp.n_rounds = 1;
+	m->rp.max_bytes = max_bytes;
+	m->rp.max_samples = m->ip.max_samples;
+	if (aof_bank_mavlink_rx_reset_device(m->ctx, n_streams, NULL, m->d_rx_state, m->stream))
+		return fail(-EIO, aof_last_error(m->ctx));
+	if (!waitIdle()) return -ETIMEDOUT;
+	// samples pushImu() queued are dropped: from here on the device writes the sample block
+	std::memset(m->h_imu + m->off_imu_counts, 0, S);
+	m->rx = true;
+	return 0;
+}
+
+int OpticalFlowBank::pushMavlink(int stream, const uint8_t *bytes, int n)
+{
+	if (!engineOk()) return -1;
+	Impl *m = _m;
+	if (!m->rx || stream < 0 || stream >= n_streams || n < 0 || (n > 0 && !bytes)) return -EINVAL;
+	uint16_t *len = reinterpret_cast<uint16_t *>(m->h_rx + m->off_rx_len) + stream;
+	if ((int)*len + n > m->rp.max_bytes) return -ENOBUFS;
+	if (n) std::memcpy(m->h_rx + (size_t)stream * (size_t)m->rp.max_bytes + *len, bytes, (size_t)n);
+	*len = (uint16_t)(*len + n);
+	return 0;
+}
+
+// In front of a tick: the queued bytes to the device and the receive launch, which leaves the samples and their counts
+// where takeImu()'s IMU call reads them (collect() empties the queue once the tick is through).
+int OpticalFlowBank::receive()
+{
+	Impl *m = _m;
+	if (hipMemcpyAsync(m->d_rx, m->h_rx, m->rx_bytes, hipMemcpyHostToDevice, m->stream) != hipSuccess)
+		return fail(-EIO, "copy of the tick's MAVLink bytes failed");
+	const int rc = aof_bank_mavlink_rx_device(m->ctx, &m->rp, m->d_rx, reinterpret_cast<const uint16_t *>(m->d_rx + m->off_rx_len),
+						  m->d_rx_state, reinterpret_cast<aof_imu_sample *>(m->d_imu), m->d_imu + m->off_imu_counts,
+						  m->stream);
 	if (rc) return fail(rc, aof_last_error(m->ctx));
 	return 0;
 }

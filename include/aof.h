@@ -801,6 +801,67 @@ int aof_bank_imu_host(const aof_imu_params *ip, const aof_imu_sample *samples, c
                       const uint64_t *time_us, const aof_tick_record *records_in, aof_imu_state *states,
                       aof_tick_record *records_out, uint8_t *mavlink, uint8_t *mavlink_len);
 
+/* ---- the stream bank's MAVLink receive: the autopilots' byte streams in, HIGHRES_IMU samples out ----
+ * What mavlink_tcp.cpp:100-129 does for one connection (recvfrom fills a buffer, mavlink_parse_char runs byte by byte,
+ * _handle decodes HIGHRES_IMU) for S connections in one launch in front of aof_bank_imu_device: the call turns the bytes
+ * each connection received into exactly the two arrays that call takes, aof_imu_sample [K][M][S] and u8 [K][S].
+ * THE CONTRACT IS THE TEXT BELOW, not the MAVLink C library: its headers were not at hand when this was written, so
+ * parity with mavlink_parse_char is not pinned by any test.  The text follows the library in what matters for a healthy
+ * stream: both wire versions are accepted, a frame is consumed whole by its declared length whether or not it is
+ * wanted, a signature is consumed and not verified, a MAVLink 2 payload is zero-extended.  HIGHRES_IMU is message 105
+ * with CRC_EXTRA 93 (MAVLink's common message set; quoted from memory of the set); its payload is 62 bytes, 63 with the
+ * `id` extension, little-endian: time_usec u64 at 0, xgyro / ygyro / zgyro f32 at 20 / 24 / 28.  Nothing else is read.
+ * Per stream the bytes are taken strictly in order by a state machine that survives the end of a call (TCP reads cut
+ * frames anywhere):
+ *   idle:      0xFD starts a MAVLink 2 frame, 0xFE a MAVLink 1 frame; any other byte: skipped++.
+ *   header:    v2: 9 bytes len, incompat, compat, seq, sysid, compid, msgid[0..2]; v1: 5 bytes len, seq, sysid, compid,
+ *              msgid.  A v2 incompat byte with any bit other than bit 0 set: rejected_flags++, the parser is idle at
+ *              once; the byte is consumed and not rescanned, what follows is scanned in idle.
+ *   payload:   len bytes (0 is allowed).     check: 2 bytes.     signature: 13 bytes, if v2 and incompat & 1.
+ *   at the frame's last byte: frames++.  If msgid == 105 the checksum (X.25 as MAVLink accumulates it: start 0xFFFF,
+ *              over the header bytes behind the start byte, the payload, then the byte 93) is compared, low byte
+ *              first, with the two check bytes.  Mismatch: bad_check++, the frame is dropped, its bytes are never
+ *              rescanned.  Match: imu_samples++; the payload's first 32 bytes, zero-extended if len < 32, give
+ *              (time_usec, xgyro, ygyro, zgyro); if the round's count for the stream is below M the sample is written
+ *              to slot `count` with reserved = 0 and the count rises, otherwise overflowed++ and the sample is lost.
+ *              Frames of any other message are consumed by their length and never checked.
+ *   bytes counts every byte taken.  No system or component filter is applied; the reference has none.
+ * A sample is delivered at its frame's last byte, signature included: a frame that ends in a later round or call
+ * delivers there. */
+#define AOF_MAVLINK_RX_BYTES_MAX 4096
+typedef struct aof_mavlink_rx_state {          /* 128 bytes per stream, caller-owned device memory */
+    uint64_t bytes;
+    uint32_t frames, imu_samples, bad_check, overflowed, skipped, rejected_flags;   /* the public 32 bytes */
+    uint8_t  in_progress[96];                  /* the frame being received; all zero when idle; layout private */
+} aof_mavlink_rx_state;
+typedef struct aof_mavlink_rx_params {
+    int32_t n_streams, n_rounds /* 1..AOF_BANK_BURST_MAX */, max_bytes /* B: 16..4096, a multiple of 16 */,
+            max_samples /* M: 1..AOF_IMU_SLOTS_MAX */;
+} aof_mavlink_rx_params;
+/* Masked streams (d_mask: u8 [S], or NULL = all) are zeroed: idle, every counter 0.  A new state array must be reset
+ * once.  -EINVAL: NULL ctx or state, n_streams < 1, a state array that is not 8-byte aligned; -EIO: the context's sticky
+ * fault.  Only enqueues. */
+int aof_bank_mavlink_rx_reset_device(aof_ctx *ctx, int32_t n_streams, const uint8_t *d_mask, aof_mavlink_rx_state *d_state,
+                                     void *stream);
+/* d_bytes: u8 [K][S][B], stream-major within a round (what S recv() calls into slots s*B produce), 16-byte aligned;
+ * bytes of a slot behind its length may be loaded and are never interpreted.  d_len: u16 [K][S], the bytes stream s
+ * received for round k; NULL = B everywhere; a value above B counts as B.  d_state: [S], updated in place.  d_samples:
+ * aof_imu_sample [K][M][S] and d_sample_count: u8 [K][S], as aof_bank_imu_device takes them: the count is written for
+ * every (k, s), sample slots at and behind the count are not written.  The kernel ends with a system-scope release
+ * behind its stores.
+ * -EINVAL: NULL ctx, params, bytes, state, samples or counts; n_streams < 1; n_rounds outside 1..AOF_BANK_BURST_MAX;
+ * max_bytes outside 16..AOF_MAVLINK_RX_BYTES_MAX or no multiple of 16; max_samples outside 1..AOF_IMU_SLOTS_MAX; bytes
+ * not 16-byte aligned, state or samples not 8-byte aligned, lengths not 2-byte aligned; -EIO: the context's sticky
+ * fault.  A refused call writes nothing.  One launch; only enqueues: no allocation, no host synchronisation,
+ * capturable. */
+int aof_bank_mavlink_rx_device(aof_ctx *ctx, const aof_mavlink_rx_params *rp, const uint8_t *d_bytes, const uint16_t *d_len,
+                               aof_mavlink_rx_state *d_state, aof_imu_sample *d_samples, uint8_t *d_sample_count,
+                               void *stream);
+/* The same function on host memory, a plain loop: no device, no context (what one camera's host would call on its
+ * receive buffer, and the check of the device's bytes).  -EINVAL as above. */
+int aof_bank_mavlink_rx_host(const aof_mavlink_rx_params *rp, const uint8_t *bytes, const uint16_t *len,
+                             aof_mavlink_rx_state *states, aof_imu_sample *samples, uint8_t *sample_count);
+
 /* ---- measurement ----
  * With profiling on, every launch is bracketed by HIP events on the stream it
  * is launched on; the last AOF_PROFILE_RING launches of each kernel are kept.

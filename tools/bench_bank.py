@@ -32,6 +32,13 @@ tick, K = 5: the camera burst; statistics at 200 000 us, frames 13 333 us apart)
   H             what a host did before: camera push + one asynchronous device-to-host copy of the exposure records into
                 pinned memory + stream synchronise + aof_exposure_control_host on host states: every step ends with the
                 host holding the commands.
+With --mavlink-rx, the MAVLink receive in front of the IMU call (64x64 ticks; 4 HIGHRES_IMU frames per stream and tick,
+alone -- mix "imu" -- and inside about 1 KB of other frames -- mix "mixed"):
+  H             aof_bank_mavlink_rx_host over the S slots of a pinned receive block + one host-to-device copy of the
+                samples and counts + records-only push + aof_bank_imu_device: the way without the receive call, and the
+                yardstick of D;
+  D             one host-to-device copy of the receive block (bytes and lengths) + aof_bank_mavlink_rx_device + the same
+                push and IMU call.
 Every leg settles for about 0.2 s of untimed ticks, then times at least --ticks ticks and at least --seconds seconds
 with the host clock around ticks that end in a synchronise.  The whole sweep runs --repeats times: the difference
 between the repeats is the run-to-run spread a difference between legs has to beat.
@@ -40,7 +47,8 @@ between the repeats is the run-to-run spread a difference between legs has to be
     python tools/bench_bank.py --burst 2,5,16 > profiles/bank_burst_sweep.txt
     python tools/bench_bank.py --outbox > profiles/bank_outbox_sweep.txt
     python tools/bench_bank.py --exposure-control > profiles/bank_exposure_control_sweep.txt
-    python tools/bench_bank.py --imu > profiles/bank_imu_sweep.txt"""
+    python tools/bench_bank.py --imu > profiles/bank_imu_sweep.txt
+    python tools/bench_bank.py --mavlink-rx > profiles/bank_mavlink_rx_sweep.txt"""
 import argparse
 import ctypes as C
 import importlib
@@ -816,6 +824,173 @@ def imu_sweep(a, dev):
               f"({'more' if clear else 'NOT more'} than the legs' spread)")
 
 
+RX_FRAMES = 4        # HIGHRES_IMU frames per stream and tick
+RX_RING = 8          # ticks of received bytes resident in pinned memory: the timed loop cycles through them
+
+
+def _crc_x25(data, crc=0xFFFF):
+    for b in data:
+        tmp = (b ^ crc) & 0xFF
+        tmp = (tmp ^ (tmp << 4)) & 0xFF
+        crc = ((crc >> 8) ^ (tmp << 8) ^ (tmp << 3) ^ (tmp >> 4)) & 0xFFFF
+    return crc
+
+
+def _mavlink2(msgid, payload, seq, extra):
+    body = bytes([len(payload), 0, 0, seq & 255, 1, 1, msgid & 255, (msgid >> 8) & 255, msgid >> 16]) + payload
+    crc = _crc_x25(body + bytes([extra]))
+    return b"\xfd" + body + bytes([crc & 255, crc >> 8])
+
+
+def rx_traffic(mix, S):
+    """RX_RING ticks of what S autopilots send per tick: mix "imu": RX_FRAMES HIGHRES_IMU frames (MAVLink 2, 74 bytes
+    each); mix "mixed": the same frames spread through about 1 KB of frames of other messages.  POOL distinct streams
+    (stream s shows pool[s % POOL]: the frames' order is rotated, so neighbouring lanes are in different places).
+    Returns (B, [RX_RING] arrays uint8 [S, B], [RX_RING] arrays uint16 [S])."""
+    import struct
+    rng = np.random.default_rng(77)
+    blob = lambda n: rng.integers(0, 250, n, dtype=np.uint8).tobytes()
+    ticks = []
+    for k in range(RX_RING):
+        pool = []
+        for v in range(POOL):
+            imu = [_mavlink2(105, struct.pack("<Q13fH", 1_000_000 + ((k * RX_FRAMES + j) * 13333) // RX_FRAMES, 0.1, 0.2, 9.8,
+                                              0.01, -0.02, 0.005, 0.3, 0.1, 0.4, 1013.0, 0.0, 120.0, 25.0, 0x1FFF), k * RX_FRAMES + j, 93)
+                   for j in range(RX_FRAMES)]
+            other = []
+            if mix == "mixed":
+                other = ([_mavlink2(30, blob(28), i, 39) for i in range(10)] + [_mavlink2(33, blob(28), i, 104) for i in range(4)] +
+                         [_mavlink2(24, blob(30), i, 24) for i in range(3)] + [_mavlink2(253, blob(51), 0, 83)])
+            n_other = len(other) // RX_FRAMES
+            parts = []
+            for j in range(RX_FRAMES):
+                parts += [imu[j]] + other[j * n_other:(j + 1) * n_other]
+            parts += other[RX_FRAMES * n_other:]
+            r = v % len(parts)
+            pool.append(b"".join(parts[r:] + parts[:r]))
+        ticks.append(pool)
+    longest = max(len(b) for pool in ticks for b in pool)
+    B = (longest + 15) // 16 * 16
+    data, lens = [], []
+    for pool in ticks:
+        a = np.zeros((POOL, B), np.uint8)
+        for v, b in enumerate(pool):
+            a[v, :len(b)] = np.frombuffer(b, np.uint8)
+        idx = np.arange(S) % POOL
+        data.append(a[idx])
+        lens.append(np.array([len(pool[v]) for v in idx], np.uint16))
+    return B, data, lens
+
+
+def leg_mavlink_rx(p, S, mix, leg, inp, dev, a):
+    """One tick per step.  H: aof_bank_mavlink_rx_host over the S slots of the tick's pinned receive block, one copy of
+    the samples (and their counts) to the device, the records-only push, the IMU call.  D: one copy of the receive
+    block (bytes and lengths), aof_bank_mavlink_rx_device, the same push and IMU call.  The receive blocks are RX_RING
+    pinned blocks the loop cycles through (the frames' times run backwards at the ring's wrap: one rejected sample per
+    stream and wrap, on both legs).  Returns (seconds per step, ticks timed, B)."""
+    eng = aof.FlowEngine(p, 0)
+    hip = hip_runtime()
+    M = IMU_SAMPLES
+    B, data, lens = rx_traffic(mix, S)
+    bp = aof.bank_params(S, FX, FY, 15, 0, 1, 100, 0)
+    bank = eng.bank_create(bp, dev)
+    recs = torch.empty((1, S, 48), dtype=torch.uint8, device=dev)
+    wire = torch.empty((1, S, 56), dtype=torch.uint8, device=dev)
+    lens_out = torch.empty((1, S), dtype=torch.uint8, device=dev)
+    times = inp.times0.clone()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    ctx = eng._ctx
+    block = S * B + 2 * S                                    # bytes [S][B], then u16 [S]
+    ring = [torch.empty(block, dtype=torch.uint8, pin_memory=True) for _ in range(RX_RING)]
+    for k in range(RX_RING):
+        ring[k].numpy()[:S * B] = data[k].ravel()
+        ring[k].numpy()[S * B:] = lens[k].view(np.uint8)
+    sample_bytes = 24 * M * S
+    d_samples = torch.zeros(sample_bytes + S, dtype=torch.uint8, device=dev)      # aof_imu_sample [M][S], then u8 [S]
+    imu_state = torch.zeros((S, 64), dtype=torch.uint8, device=dev)
+    eng.bank_imu_reset(imu_state, offset0=5_000_000)
+    rp, ip = aof.mavlink_rx_params(S, 1, B, M), aof.imu_params(S, 1, M)
+    imu = aof.lib.aof_bank_imu_device
+    iargs = (ctx, C.byref(ip), d_samples.data_ptr(), d_samples.data_ptr() + sample_bytes, times.data_ptr(), recs.data_ptr(),
+             imu_state.data_ptr(), recs.data_ptr(), wire.data_ptr(), lens_out.data_ptr(), stream)
+    pargs = (ctx, C.byref(bp), inp.frames.data_ptr(), times.data_ptr(), None, None, bank.buffer.data_ptr(), bank.buffer.numel(),
+             recs.data_ptr(), None, None, stream)
+    push = aof.lib.aof_bank_push_device
+    if leg == "H":
+        h_samples = torch.zeros(sample_bytes + S, dtype=torch.uint8, pin_memory=True)
+        states = np.zeros(S, aof.MAVLINK_RX_STATE_DTYPE)
+        parse = aof.lib.aof_bank_mavlink_rx_host
+        hargs = [(C.byref(rp), r.data_ptr(), r.data_ptr() + S * B, states.ctypes.data, h_samples.data_ptr(),
+                  h_samples.data_ptr() + sample_bytes) for r in ring]
+        copy = (d_samples.data_ptr(), h_samples.data_ptr(), sample_bytes + S, 1, stream)       # hipMemcpyHostToDevice
+    else:
+        d_block = torch.zeros(block, dtype=torch.uint8, device=dev)
+        rx_state = torch.zeros((S, 128), dtype=torch.uint8, device=dev)
+        eng.bank_mavlink_rx_reset(rx_state)
+        rx = aof.lib.aof_bank_mavlink_rx_device
+        rargs = (ctx, C.byref(rp), d_block.data_ptr(), d_block.data_ptr() + S * B, rx_state.data_ptr(), d_samples.data_ptr(),
+                 d_samples.data_ptr() + sample_bytes, stream)
+        copies = [(d_block.data_ptr(), r.data_ptr(), block, 1, stream) for r in ring]
+    count = [0]
+
+    def step():
+        i = count[0] % RX_RING
+        count[0] += 1
+        times.add_(13333)
+        if leg == "H":
+            rc = parse(*hargs[i])
+            if rc == 0 and hip.hipMemcpyAsync(*copy):
+                raise RuntimeError("hipMemcpyAsync failed")
+        else:
+            if hip.hipMemcpyAsync(*copies[i]):
+                raise RuntimeError("hipMemcpyAsync failed")
+            rc = rx(*rargs)
+        if rc == 0:
+            rc = push(*pargs)
+        if rc == 0:
+            rc = imu(*iargs)
+        if rc:
+            raise aof.AofError(rc, aof.lib.aof_last_error(ctx).decode())
+    out_t = timed_bursts(step, torch.cuda.synchronize, 1, a.ticks, a.seconds, a.settle)
+    torch.cuda.synchronize()
+    assert (aof.ticks_view(recs[0])["frame"] > a.ticks).all(), "the timed rounds were real ticks"
+    st = states if leg == "H" else aof.mavlink_rx_states_view(rx_state)
+    assert (st["imu_samples"] == RX_FRAMES * count[0]).all() and (st["bad_check"] == 0).all() and (st["overflowed"] == 0).all(), \
+        "every HIGHRES_IMU frame was decoded"
+    assert (aof.imu_states_view(imu_state)["samples_integrated"] > count[0]).all(), "the IMU call integrated them"
+    eng.close()
+    return out_t[0], out_t[1], B
+
+
+def mavlink_rx_sweep(a, dev):
+    print("# legs: H aof_bank_mavlink_rx_host over the S slots + H2D copy of the samples and counts + records-only push + "
+          "aof_bank_imu_device, D H2D copy of the bytes and lengths + aof_bank_mavlink_rx_device + the same push and IMU call")
+    print(f"# us = microseconds per tick of 64x64 streams; mixes: imu = {RX_FRAMES} HIGHRES_IMU frames per stream and tick, mixed = the "
+          "same frames inside about 1 KB of other frames; host clock around chunks of ticks ending in a synchronise")
+    p = params_of("px4-64")
+    cases = [(mix, S) for mix in ("imu", "mixed") for S in (int(s) for s in a.streams.split(","))]
+    results, slot = {}, {}
+    for rep in range(a.repeats):
+        for mix, S in cases:
+            inp = BurstInputs(p, S, 1, dev)
+            for leg in ("H", "D"):
+                sec, n, B = leg_mavlink_rx(p, S, mix, leg, inp, dev, a)
+                results.setdefault((mix, S, leg), []).append(sec)
+                slot[mix] = B
+                print(f"rep {rep} px4-64 {mix:5s} B={B:5d} S={S:6d} {leg} {sec * 1e6:10.2f} us  ({n} ticks)", flush=True)
+            del inp
+            torch.cuda.empty_cache()
+    print("# ---- summary (mean of the repeats; spread = |difference of the repeats| / mean) ----")
+    for mix, S in cases:
+        m = {leg: float(np.mean(results[(mix, S, leg)])) for leg in "HD"}
+        sp = {leg: abs(results[(mix, S, leg)][0] - results[(mix, S, leg)][-1]) / m[leg] for leg in "HD"}
+        gain = (m["H"] - m["D"]) / m["H"]
+        clear = abs(gain) > sp["H"] + sp["D"]
+        print(f"px4-64 {mix:5s} B={slot[mix]:5d} S={S:6d}  " + "  ".join(f"{leg} {m[leg] * 1e6:9.2f} (+-{sp[leg] * 100:4.1f} %)" for leg in "HD") +
+              f"  H/D {m['H'] / m['D']:5.2f}  {'D' if gain > 0 else 'H'} wins by {abs(gain) * 100:5.1f} % "
+              f"({'more' if clear else 'NOT more'} than the legs' spread)")
+
+
 def leg_contexts(p, S, inp, a):
     engs = [aof.FlowEngine(p, 0) for _ in range(S)]
     flow = np.zeros(1, aof.FLOW_DTYPE)
@@ -886,6 +1061,7 @@ def main():
     ap.add_argument("--outbox", action="store_true", help="the sweep of the outbox: legs T, D, H, O")
     ap.add_argument("--exposure-control", action="store_true", help="the sweep of the auto-exposure controller: legs T, C, H")
     ap.add_argument("--imu", action="store_true", help="the sweep of the IMU call: legs G, D")
+    ap.add_argument("--mavlink-rx", action="store_true", help="the sweep of the MAVLink receive: legs H, D on two traffic mixes")
     ap.add_argument("--forms", default="plain,camera", help="--burst: entry points to sweep")
     ap.add_argument("--input-bytes-max", type=float, default=24 * 2**30, help="--burst: sizes whose K rounds of input exceed this are skipped")
     a = ap.parse_args()
@@ -895,7 +1071,7 @@ def main():
         a.streams = "1,64,1024,1536,2048,4096"
     if a.exposure_control and a.streams == ap.get_default("streams"):
         a.streams = "64,1024,4096"
-    if a.imu and a.streams == ap.get_default("streams"):
+    if (a.imu or a.mavlink_rx) and a.streams == ap.get_default("streams"):
         a.streams = "64,256,1024,4096"
     if a.outbox and a.streams == ap.get_default("streams"):
         a.streams = "64,256,1024,4096,16384"
@@ -906,6 +1082,8 @@ def main():
     print(f"# device: {torch.cuda.get_device_name(0)}")
     if not a.no_marker:
         print(f"# class marker: exhaustive C2 K2 (1 024 VGA pairs) {class_marker(dev):.4f} ms")
+    if a.mavlink_rx:
+        return mavlink_rx_sweep(a, dev)
     if a.imu:
         return imu_sweep(a, dev)
     if a.exposure_control:
