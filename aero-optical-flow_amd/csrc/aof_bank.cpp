@@ -118,7 +118,7 @@ int check_bank(aof_ctx *ctx, const aof_bank_params *bp, const void *d_bank, size
     if (rc) return ctx_fail(ctx, rc, camera ? "bad bank parameters (n_streams, frame_stride, focal length) or bank camera parameters (crop, camera_stride)"
                                             : "bad bank parameters (n_streams, frame_stride, focal length)");
     if (!d_bank) return ctx_fail(ctx, -EINVAL, "null bank pointer");
-    if (reinterpret_cast<uintptr_t>(d_bank) % 256) return ctx_fail(ctx, -EINVAL, "bank must be 256-byte aligned");
+    if (!aligned(d_bank, 256)) return ctx_fail(ctx, -EINVAL, "bank must be 256-byte aligned");
     if (bank_bytes < L->pub.total_bytes)
         return ctx_fail(ctx, -ENOSPC, camera ? "bank smaller than aof_bank_camera_layout().total_bytes" : "bank smaller than aof_bank_layout().total_bytes");
     return 0;
@@ -130,8 +130,7 @@ int check_tick(aof_ctx *ctx, const void *d_frames, const uint64_t *d_time_us, co
 {
     if (!d_frames || !d_time_us || !d_records) return ctx_fail(ctx, -EINVAL, "null frame, time stamp or record pointer");
     if (d_mavlink && !d_mavlink_len) return ctx_fail(ctx, -EINVAL, "MAVLink frames need their length array");
-    if (reinterpret_cast<uintptr_t>(d_time_us) % 8 || reinterpret_cast<uintptr_t>(d_records) % 4 ||
-        reinterpret_cast<uintptr_t>(d_gyro) % 4)
+    if (!aligned(d_time_us, 8) || !aligned(d_records, 4) || !aligned(d_gyro, 4))
         return ctx_fail(ctx, -EINVAL, "time stamps must be 8-byte aligned, records and gyro samples 4-byte aligned");
     return 0;
 }
@@ -154,7 +153,7 @@ BankArgs bank_args(const aof_bank_params *bp, const Layout &L, uint8_t *bank, co
     a.state = reinterpret_cast<BankState *>(bank + L.pub.state);
     a.flows = reinterpret_cast<aof_flow *>(bank + L.flows);
     a.output_rate = bp->output_rate;
-    a.period_us = bp->output_rate > 0 ? 1.0e6f / (float)bp->output_rate : 0.0f;   // (the facade's own division)
+    a.period_us = limiter_period_us(bp->output_rate);
     a.focal_x = bp->focal_x; a.focal_y = bp->focal_y;
     a.offset_timestamp_usec = bp->offset_timestamp_usec;
     a.system_id = bp->system_id; a.component_id = bp->component_id; a.first_seq = bp->first_seq;
@@ -251,7 +250,7 @@ int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank
     if ((rc = check_tick(ctx, p.src, p.time_us, p.gyro, p.records, p.mavlink, p.mavlink_len))) return rc;
     if (p.camera) {
         if (p.cam->derotate && !p.derotated) return ctx_fail(ctx, -EINVAL, "bank camera: derotate needs d_derotated");
-        if (reinterpret_cast<uintptr_t>(p.exposure) % 4 || reinterpret_cast<uintptr_t>(p.derotated) % 4)
+        if (!aligned(p.exposure, 4) || !aligned(p.derotated, 4))
             return ctx_fail(ctx, -EINVAL, "bank camera: exposure records and de-rotated pairs must be 4-byte aligned");
     }
     // before the first launch: a faulted or wedged context, or a thread on another device, must not touch the bank

@@ -7,6 +7,7 @@
 #pragma once
 
 #include "aof_derotate.hpp"
+#include "aof_exposure_step.hpp"
 #include "aof_flow_small.hpp"
 #include "aof_mavlink.hpp"
 #include "aof_math.h"
@@ -32,15 +33,6 @@ __device__ __forceinline__ void bank_idle(const BankArgs &a, size_t o)
 __device__ __forceinline__ bool exposure_due(const BankArgs &a, const BankState &st, uint64_t t)
 {
     return a.cam.exposure != nullptr && t >= st.next_exposure_us;
-}
-
-// mainloop.cpp:216-220 as aof_exposure_msv computes it: the same float operations in the same order, none fused.
-__device__ __forceinline__ float exposure_msv(const uint32_t *hist)
-{
-#pragma clang fp contract(off)
-    float msv = 0.0f;
-    for (int i = 0; i < AOF_EXPOSURE_BINS; i++) msv += (i + 1) * (float)hist[i] / 16384.0f;
-    return msv;
 }
 
 // One lane: a stream has been given a frame; `st` is the stream's state record, `f` the pixel record of (older frame,

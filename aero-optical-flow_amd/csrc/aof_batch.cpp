@@ -364,9 +364,9 @@ int flow_batch(aof_ctx *ctx, const uint8_t *d_prev, const uint8_t *d_cur, int64_
     if (rc) return fail(ctx, rc, "bad workspace layout");
     if (!d_workspace || workspace_bytes < L.total_bytes)
         return fail(ctx, -ENOSPC, "workspace %zu B < required %zu B", workspace_bytes, L.total_bytes);
-    if (reinterpret_cast<uintptr_t>(d_workspace) % 256)
+    if (!aligned(d_workspace, 256))
         return fail(ctx, -EINVAL, "workspace must be 256-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_blocks) % 4 || reinterpret_cast<uintptr_t>(d_flows) % 4)
+    if (!aligned(d_blocks, 4) || !aligned(d_flows, 4))
         return fail(ctx, -EINVAL, "block and flow records must be 4-byte aligned");
     if ((rc = device_check(ctx))) return rc;
     const BatchView v = batch_view(ctx, L, d_prev, d_cur, pair_stride, d_blocks, d_subdirs, d_flows, d_workspace);

@@ -14,8 +14,6 @@ using namespace aof;
 
 namespace {
 
-bool aligned4(const void *p) { return reinterpret_cast<uintptr_t>(p) % 4 == 0; }
-
 // nullptr, or what is wrong with the constants
 const char *bad_control(const aof_exposure_control &ec)
 {
@@ -57,7 +55,7 @@ int aof_bank_exposure_reset_device(aof_ctx *ctx, int32_t n_streams, const uint8_
     if (!ctx) return -EINVAL;
     if (!d_state) return ctx_fail(ctx, -EINVAL, "exposure reset: null state pointer");
     if (n_streams < 1) return ctx_fail(ctx, -EINVAL, "exposure reset: n_streams < 1");
-    if (!aligned4(d_state) || reinterpret_cast<uintptr_t>(d_exposure0) % 2)
+    if (!aligned(d_state, 4) || !aligned(d_exposure0, 2))
         return ctx_fail(ctx, -EINVAL, "exposure reset: the state must be 4-byte aligned, the exposure values 2-byte aligned");
     if (const int rc = precheck(ctx)) return rc;
     if (launch_bank_exposure_reset(d_state, d_mask, (uint32_t)n_streams, exposure0, gain0, d_exposure0, d_gain0, stream))
@@ -75,7 +73,7 @@ int aof_bank_exposure_control_device(aof_ctx *ctx, const aof_exposure_control *e
     if (n_streams < 1) return ctx_fail(ctx, -EINVAL, "exposure control: n_streams < 1");
     if (n_rounds < 1 || n_rounds > AOF_BANK_BURST_MAX)
         return ctx_fail(ctx, -EINVAL, "exposure control: n_rounds outside 1..AOF_BANK_BURST_MAX");
-    if (!aligned4(d_exposure) || !aligned4(d_state) || !aligned4(d_commands))
+    if (!aligned(d_exposure, 4) || !aligned(d_state, 4) || !aligned(d_commands, 4))
         return ctx_fail(ctx, -EINVAL, "exposure control: records, state and commands must be 4-byte aligned");
     if (const char *what = bad_control(*ec)) return ctx_fail(ctx, -EINVAL, what);
     if (const int rc = precheck(ctx)) return rc;

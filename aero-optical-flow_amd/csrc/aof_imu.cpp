@@ -8,12 +8,11 @@
 
 #include "aof_ctx.hpp"
 #include "aof_imu_step.hpp"
+#include "aof_mavlink.hpp"
 
 using namespace aof;
 
 namespace {
-
-bool aligned(const void *p, uintptr_t n) { return reinterpret_cast<uintptr_t>(p) % n == 0; }
 
 // nullptr, or what is wrong with the arguments both forms of the call share
 const char *bad_call(const aof_imu_params *ip, const void *samples, const void *time_us, const void *records_in, const void *states,
@@ -29,55 +28,6 @@ const char *bad_call(const aof_imu_params *ip, const void *samples, const void *
         return "imu: samples, states and times must be 8-byte aligned";
     if (!aligned(records_in, 4) || !aligned(records_out, 4)) return "imu: records must be 4-byte aligned";
     return nullptr;
-}
-
-uint16_t crc_accumulate(uint8_t byte, uint16_t crc)
-{
-    uint8_t tmp = (uint8_t)(byte ^ (uint8_t)(crc & 0xFF));
-    tmp = (uint8_t)(tmp ^ (uint8_t)(tmp << 4));
-    return (uint16_t)((crc >> 8) ^ ((uint16_t)tmp << 8) ^ ((uint16_t)tmp << 3) ^ (tmp >> 4));
-}
-
-template <typename T> void put(uint8_t *&p, T v)
-{
-    std::memcpy(p, &v, sizeof(T));   // little-endian wire order: the hosts this library builds for
-    p += sizeof(T);
-}
-
-// The frame pack_optical_flow_rad (aof_mavlink.hpp) writes on the device, on the host: the field mapping of
-// mainloop.cpp:359-371 and the MAVLink 2 frame of mavlink_tcp.cpp:142-162.  Returns the frame's length.
-int pack_frame(uint8_t *out, const ImuFrame &f, const aof_tick_record &rec, uint8_t system_id, uint8_t component_id)
-{
-    uint8_t payload[44];
-    uint8_t *p = payload;
-    put(p, f.time_usec);
-    put(p, (uint32_t)rec.dt_us);
-    put(p, rec.flow_x);
-    put(p, rec.flow_y);
-    put(p, (float)(-f.gy));      // gyro axes are switched to match pixel directions
-    put(p, (float)f.gx);
-    put(p, (float)f.gz);
-    put(p, (uint32_t)0);         // time_delta_distance_us
-    put(p, -1.0f);               // distance
-    put(p, (int16_t)0);          // temperature
-    put(p, (uint8_t)0);          // sensor_id
-    put(p, (uint8_t)rec.quality);
-    int len = 44;
-    while (len > 1 && payload[len - 1] == 0) len--;   // MAVLink 2 payload truncation
-    const uint8_t head[10] = {0xFD, (uint8_t)len, 0, 0, f.seq, system_id, component_id, 106, 0, 0};
-    uint16_t crc = 0xFFFF;
-    for (int b = 0; b < 10; b++) {
-        out[b] = head[b];
-        if (b) crc = crc_accumulate(head[b], crc);
-    }
-    for (int b = 0; b < len; b++) {
-        out[10 + b] = payload[b];
-        crc = crc_accumulate(payload[b], crc);
-    }
-    crc = crc_accumulate(138, crc);   // CRC_EXTRA of OPTICAL_FLOW_RAD
-    out[10 + len] = (uint8_t)(crc & 0xFF);
-    out[11 + len] = (uint8_t)(crc >> 8);
-    return 12 + len;
 }
 
 }  // namespace
@@ -144,9 +94,10 @@ int aof_bank_imu_host(const aof_imu_params *ip, const aof_imu_sample *samples, c
             }
             aof_tick_record rec = records_in[o];
             ImuFrame f;
-            uint8_t len = 0;
+            uint8_t len = 0, payload[kMavlinkPayloadBytes];
             if (imu_take(st, rec, time_us[o], ip->first_seq, f) && mavlink)
-                len = (uint8_t)pack_frame(mavlink + o * AOF_SEQ_FRAME_BYTES, f, rec, ip->system_id, ip->component_id);
+                len = (uint8_t)pack_optical_flow_rad(mavlink + o * AOF_SEQ_FRAME_BYTES, payload, f.time_usec, rec.dt_us, rec.flow_x,
+                                                     rec.flow_y, f.gx, f.gy, f.gz, rec.quality, f.seq, ip->system_id, ip->component_id);
             records_out[o] = rec;
             if (mavlink_len) mavlink_len[o] = len;
         }

@@ -4,18 +4,12 @@
 // side, and the division by 1e6 is a division.
 #pragma once
 
-#include "aof.h"
-
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define AOF_IMU_HD __host__ __device__ __forceinline__
-#else
-#define AOF_IMU_HD inline
-#endif
+#include "aof_hd.hpp"
 
 namespace aof {
 
 // One HIGHRES_IMU sample (time in microseconds, rates in rad/s) for the stream whose state is `st`.
-AOF_IMU_HD void imu_sample(aof_imu_state &st, uint64_t t, float x, float y, float z)
+AOF_HD_INLINE void imu_sample(aof_imu_state &st, uint64_t t, float x, float y, float z)
 {
 #pragma clang fp contract(off)
     const double dt = (double)(uint64_t)(t - st.prev_time_usec) / 1e6;   // (u64 wrap: time running backwards is a huge dt)
@@ -42,7 +36,7 @@ struct ImuFrame {
 
 // The record of a frame with time `t` (what the push wrote, `rec`, completed in place).  Returns true where the record
 // is sent: `f` then says what its frame carries, and the caller packs it.  A record with quality < 0 is left as it is.
-AOF_IMU_HD bool imu_take(aof_imu_state &st, aof_tick_record &rec, uint64_t t, uint8_t first_seq, ImuFrame &f)
+AOF_HD_INLINE bool imu_take(aof_imu_state &st, aof_tick_record &rec, uint64_t t, uint8_t first_seq, ImuFrame &f)
 {
     if (rec.quality < 0) return false;   // held or idle: nothing is taken
     f.gx = st.gyro_x; f.gy = st.gyro_y; f.gz = st.gyro_z;

@@ -32,6 +32,12 @@ inline FastDiv fastdiv_make(uint32_t d)
     return f;
 }
 
+// Is p a multiple of n bytes (nullptr is)?  The host-side test of every entry point and launcher; kernels test their own.
+inline bool aligned(const void *p, uintptr_t n) { return reinterpret_cast<uintptr_t>(p) % n == 0; }
+
+// The rate limiter's period in microseconds, 0 without a limit: the facade's own division, in float.
+inline float limiter_period_us(int output_rate) { return output_rate > 0 ? 1.0e6f / (float)output_rate : 0.0f; }
+
 struct Grid {
     int32_t x0, y0, step_x, step_y, nx, ny;
     AOF_HD int32_t blocks() const { return nx * ny; }
@@ -244,7 +250,7 @@ struct SequenceArgs {
     const aof_gyro *gyro;          // [n_frames] gyro integrated over the interval that ends at frame k, or nullptr
     const aof_flow *flows;         // [n_frames - 1]: pair k = frames k, k + 1
     int32_t output_rate;
-    float period_us;               // 1e6f / output_rate, divided on the host as the facade divides
+    float period_us;               // limiter_period_us(output_rate)
     float focal_x, focal_y;
     uint64_t offset_timestamp_usec;
     uint8_t system_id, component_id, first_seq;
@@ -308,7 +314,7 @@ struct BankArgs {
     BankState *state;              // [S]
     const aof_flow *flows;         // [S] the tick's pixel records (composed path: written by the batch plan)
     int32_t output_rate;
-    float period_us;               // 1e6f / output_rate, divided on the host as the facade divides
+    float period_us;               // limiter_period_us(output_rate)
     float focal_x, focal_y;
     uint64_t offset_timestamp_usec;
     uint8_t system_id, component_id, first_seq;

@@ -12,8 +12,6 @@ using namespace aof;
 
 namespace {
 
-bool aligned(const void *p, uintptr_t n) { return reinterpret_cast<uintptr_t>(p) % n == 0; }
-
 // nullptr, or what is wrong with the arguments both forms of the call share
 const char *bad_call(const aof_mavlink_rx_params *rp, const void *bytes, const void *len, const void *states, const void *samples,
                      const void *sample_count)

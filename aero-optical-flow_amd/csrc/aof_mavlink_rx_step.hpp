@@ -4,13 +4,7 @@
 // 96 private bytes of aof_mavlink_rx_state are laid out, so both sides agree on them byte for byte.
 #pragma once
 
-#include "aof.h"
-
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define AOF_RX_HD __host__ __device__ __forceinline__
-#else
-#define AOF_RX_HD inline
-#endif
+#include "aof_mavlink.hpp"   // rx_crc: the checksum step, beside the packer's
 
 namespace aof {
 
@@ -42,7 +36,7 @@ struct MavRx {
     uint32_t gx, gy, gz, msgid, pos, crc, start, len, incompat, check;
 };
 
-AOF_RX_HD void rx_load(MavRx &r, const MavRxBytes &m)
+AOF_HD_INLINE void rx_load(MavRx &r, const MavRxBytes &m)
 {
     r.bytes = m.bytes; r.frames = m.frames; r.imu_samples = m.imu_samples; r.bad_check = m.bad_check;
     r.overflowed = m.overflowed; r.skipped = m.skipped; r.rejected_flags = m.rejected_flags;
@@ -51,7 +45,7 @@ AOF_RX_HD void rx_load(MavRx &r, const MavRxBytes &m)
 }
 
 // (the first kRxLiveBytes of `m` only)
-AOF_RX_HD void rx_store(MavRxBytes &m, const MavRx &r)
+AOF_HD_INLINE void rx_store(MavRxBytes &m, const MavRx &r)
 {
     m.bytes = r.bytes; m.frames = r.frames; m.imu_samples = r.imu_samples; m.bad_check = r.bad_check;
     m.overflowed = r.overflowed; m.skipped = r.skipped; m.rejected_flags = r.rejected_flags;
@@ -60,31 +54,23 @@ AOF_RX_HD void rx_store(MavRxBytes &m, const MavRx &r)
     m.incompat = (uint8_t)r.incompat; m.check = (uint8_t)r.check;
 }
 
-AOF_RX_HD void rx_idle(MavRx &r)
+AOF_HD_INLINE void rx_idle(MavRx &r)
 {
     r.time_usec = 0;
     r.gx = r.gy = r.gz = r.msgid = r.pos = r.crc = r.start = r.len = r.incompat = r.check = 0;
 }
 
-// the accumulate step of aof_mavlink.hpp (mavlinkCrcAccumulate), on 32-bit values
-AOF_RX_HD uint32_t rx_crc(uint32_t byte, uint32_t crc)
-{
-    uint32_t tmp = (byte ^ crc) & 0xFFu;
-    tmp = (tmp ^ (tmp << 4)) & 0xFFu;
-    return ((crc >> 8) ^ (tmp << 8) ^ (tmp << 3) ^ (tmp >> 4)) & 0xFFFFu;
-}
-
-AOF_RX_HD uint32_t rx_header_bytes(const MavRx &r) { return r.start == kRxStartV2 ? 9u : 5u; }
+AOF_HD_INLINE uint32_t rx_header_bytes(const MavRx &r) { return r.start == kRxStartV2 ? 9u : 5u; }
 
 // bytes of the frame behind its start byte; valid once the header is in (pos >= rx_header_bytes)
-AOF_RX_HD uint32_t rx_frame_bytes(const MavRx &r)
+AOF_HD_INLINE uint32_t rx_frame_bytes(const MavRx &r)
 {
     return rx_header_bytes(r) + r.len + 2u + (r.start == kRxStartV2 && (r.incompat & 1u) ? 13u : 0u);
 }
 
 // One byte.  True where it was the last byte of a HIGHRES_IMU frame whose checksum matched: (t, x, y, z) is the sample
 // (the float bits as they lay on the wire) and the caller hands it to rx_take.
-AOF_RX_HD bool rx_byte(MavRx &r, uint32_t b, uint64_t &t, uint32_t &x, uint32_t &y, uint32_t &z)
+AOF_HD_INLINE bool rx_byte(MavRx &r, uint32_t b, uint64_t &t, uint32_t &x, uint32_t &y, uint32_t &z)
 {
     r.bytes += 1u;
     if (!r.start) {
@@ -159,7 +145,7 @@ AOF_RX_HD bool rx_byte(MavRx &r, uint32_t b, uint64_t &t, uint32_t &x, uint32_t 
 
 // A sample rx_byte delivered, in a round that holds `count` samples of at most M: true where the caller writes it to
 // slot `count` and raises the count.
-AOF_RX_HD bool rx_take(MavRx &r, uint32_t count, uint32_t M)
+AOF_HD_INLINE bool rx_take(MavRx &r, uint32_t count, uint32_t M)
 {
     if (count < M) return true;
     r.overflowed += 1u;
@@ -169,13 +155,13 @@ AOF_RX_HD bool rx_take(MavRx &r, uint32_t count, uint32_t M)
 // The bulk steps.  rx_skippable: how many of the next bytes can be taken without looking at them -- what is left of a
 // frame that is not HIGHRES_IMU once its header is in (payload, check and signature: consumed by length, never
 // checked).  rx_skip takes n <= rx_skippable(r) of them.
-AOF_RX_HD uint32_t rx_skippable(const MavRx &r)
+AOF_HD_INLINE uint32_t rx_skippable(const MavRx &r)
 {
     if (!r.start || r.pos < rx_header_bytes(r) || r.msgid == kRxHighresImu) return 0u;
     return rx_frame_bytes(r) - r.pos;
 }
 
-AOF_RX_HD void rx_skip(MavRx &r, uint32_t n)
+AOF_HD_INLINE void rx_skip(MavRx &r, uint32_t n)
 {
     r.bytes += n;
     r.pos += n;
@@ -186,14 +172,14 @@ AOF_RX_HD void rx_skip(MavRx &r, uint32_t n)
 }
 
 // n bytes in idle, none of them a start byte
-AOF_RX_HD void rx_skip_idle(MavRx &r, uint32_t n)
+AOF_HD_INLINE void rx_skip_idle(MavRx &r, uint32_t n)
 {
     r.bytes += n;
     r.skipped += n;
 }
 
 // true where none of the eight bytes of `w` can be a start byte (a conservative test: 0xFC..0xFF are candidates)
-AOF_RX_HD bool rx_no_start_in(uint64_t w)
+AOF_HD_INLINE bool rx_no_start_in(uint64_t w)
 {
     const uint64_t k = 0xFCFCFCFCFCFCFCFCull, v = (w & k) ^ k;   // a zero byte where a candidate was
     return ((v - 0x0101010101010101ull) & ~v & 0x8080808080808080ull) == 0u;

@@ -44,11 +44,10 @@ int aof_bank_collect_device(aof_ctx *ctx, int32_t n_streams, int32_t n_rounds, c
         return ctx_fail(ctx, -EINVAL, "bank collect: n_rounds outside 1..AOF_BANK_BURST_MAX");
     const int64_t n = (int64_t)n_streams * n_rounds;
     if (n > 0x7FFFFFFF) return ctx_fail(ctx, -EINVAL, "bank collect: more than 2^31 - 1 records");
-    if (reinterpret_cast<uintptr_t>(outbox) % 64) return ctx_fail(ctx, -EINVAL, "bank collect: the outbox must be 64-byte aligned");
+    if (!aligned(outbox, 64)) return ctx_fail(ctx, -EINVAL, "bank collect: the outbox must be 64-byte aligned");
     if (d_mavlink && !d_mavlink_len) return ctx_fail(ctx, -EINVAL, "bank collect: MAVLink frames need their length array");
     if (!tag && !d_tag) return ctx_fail(ctx, -EINVAL, "bank collect: the tag must be non-zero");
-    if (reinterpret_cast<uintptr_t>(d_records) % 4 || reinterpret_cast<uintptr_t>(d_exposure) % 4 ||
-        reinterpret_cast<uintptr_t>(d_derotated) % 4 || reinterpret_cast<uintptr_t>(d_tag) % 8)
+    if (!aligned(d_records, 4) || !aligned(d_exposure, 4) || !aligned(d_derotated, 4) || !aligned(d_tag, 8))
         return ctx_fail(ctx, -EINVAL, "bank collect: records, exposure records and de-rotated pairs must be 4-byte aligned, the tag word 8-byte aligned");
     struct aof_outbox_layout L;
     if (outbox_layout(capacity_messages, capacity_exposures, &L))

@@ -4,6 +4,7 @@
 #include <cerrno>
 #include <cstring>
 
+#include "aof_exposure_step.hpp"
 #include "aof_internal.hpp"
 
 namespace aof {
@@ -89,16 +90,13 @@ const char *aof_strerror(int code)
 
 float aof_exposure_msv(const uint32_t hist[AOF_EXPOSURE_BINS])
 {
-    // /root/reference/src/mainloop.cpp:216-220, same float operation order
-    float msv = 0.0f;
-    for (int i = 0; i < AOF_EXPOSURE_BINS; i++) msv += (i + 1) * (float)hist[i] / 16384.0f;
-    return msv;
+    return exposure_msv(hist);
 }
 
 int aof_exposure_bin(int grey)
 {
     if (grey < 0 || grey > 255) return -1;
-    const int b = (grey * 10) / 255;  // == cvFloor(grey * (10 / 255.0)) for every 8-bit value
+    const int b = exposure_bin((uint32_t)grey);
     return b < AOF_EXPOSURE_BINS ? b : -1;
 }
 

@@ -98,7 +98,7 @@ int aof_sequence_device(aof_ctx *ctx, const aof_sequence_params *sp, const uint8
     if (n_frames == 0) return 0;
     if (!d_camera || !d_time_us || !d_workspace) return ctx_fail(ctx, -EINVAL, "null camera, time stamp or workspace pointer");
     if (workspace_bytes < L.total_bytes) return ctx_fail(ctx, -ENOSPC, "sequence workspace smaller than aof_sequence_layout().total_bytes");
-    if (reinterpret_cast<uintptr_t>(d_workspace) % 256) return ctx_fail(ctx, -EINVAL, "workspace must be 256-byte aligned");
+    if (!aligned(d_workspace, 256)) return ctx_fail(ctx, -EINVAL, "workspace must be 256-byte aligned");
     if (sp->derotate && !d_gyro) return ctx_fail(ctx, -EINVAL, "de-rotation needs the gyro samples");
     Scratch s;
     scratch_layout(&p, n_frames, &s);
@@ -141,7 +141,7 @@ int aof_sequence_device(aof_ctx *ctx, const aof_sequence_params *sp, const uint8
     a.gyro = d_gyro;
     a.flows = flows;
     a.output_rate = sp->output_rate;
-    a.period_us = sp->output_rate > 0 ? 1.0e6f / (float)sp->output_rate : 0.0f;   // (the facade's own division)
+    a.period_us = limiter_period_us(sp->output_rate);
     a.focal_x = sp->focal_x; a.focal_y = sp->focal_y;
     a.offset_timestamp_usec = sp->offset_timestamp_usec;
     a.system_id = sp->system_id; a.component_id = sp->component_id; a.first_seq = sp->first_seq;

@@ -258,10 +258,9 @@ __global__ __launch_bounds__(kThreads) void k_bank_outbox(OutboxArgs a)
 int launch_bank_outbox(const OutboxArgs &a, void *stream)
 {
     if (a.n < 1 || a.n_streams < 1 || !a.records || !a.outbox || !a.counter) return (int)hipErrorInvalidValue;
-    auto at = [](const void *p, uintptr_t n) { return reinterpret_cast<uintptr_t>(p) % n == 0; };
-    const bool aligned = at(a.records, 16) && at(a.exposure, 16) && at(a.mavlink, 8) && at(a.derotated, 8);
+    const bool wide = aligned(a.records, 16) && aligned(a.exposure, 16) && aligned(a.mavlink, 8) && aligned(a.derotated, 8);
     const uint32_t tiles = (a.n + kOutboxTile - 1) / kOutboxTile;
-    hipLaunchKernelGGL(aligned ? k_bank_outbox<true> : k_bank_outbox<false>, dim3(tiles), dim3(kThreads), 0,
+    hipLaunchKernelGGL(wide ? k_bank_outbox<true> : k_bank_outbox<false>, dim3(tiles), dim3(kThreads), 0,
                        static_cast<hipStream_t>(stream), a);
     return (int)hipGetLastError();
 }

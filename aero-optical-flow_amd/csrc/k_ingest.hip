@@ -19,6 +19,7 @@
 // (crops of up to 128 rows) stores the ten totals; taller crops take several workgroups per frame, which
 // add to a zeroed histogram with one integer global atomic per bin (order-independent).
 #include "aof_device.hpp"
+#include "aof_exposure_step.hpp"
 #include "aof_internal.hpp"
 
 namespace aof {
@@ -41,8 +42,6 @@ constexpr int kRowsPerBlock = 128;   // (64 / 32 rows per workgroup: 80 / 115 us
 constexpr int kLaneField = 6;      // bits per counter of a lane's table sums: <= 3 pieces x 16 pixels = 48 < 64
 constexpr int kLanePieces = 3;     // pieces between two widenings
 constexpr int kWavePieces = 63;    // pieces per lane between two wave sums: 63 x 16 x 64 lanes = 64 512 < 65 536
-
-__device__ __forceinline__ int exposure_bin(uint32_t v) { return (int)((v * 10u) / 255u); }  // 10 => dropped
 
 // A lane's ten counters as 16-bit fields, two per word (bins 2k and 2k+1 in word k).
 struct LaneCounts { uint32_t w[5]; };

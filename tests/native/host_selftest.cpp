@@ -1,16 +1,131 @@
 // Sanitizer self-test of the product's HOST-ONLY logic (no HIP calls): parameter checks, grids,
-// strip plans, workspace layout (aof_params.cpp) and the OPTICAL_FLOW_RAD packer.
+// strip plans, workspace layout (aof_params.cpp) and the OPTICAL_FLOW_RAD packer; and of the rules the host shares
+// with the kernels, compiled for the host: the kernels' own packer (aof_mavlink.hpp) against the facade's, the two
+// forms of the checksum step against each other, the exposure bin and mean sample value (aof_exposure_step.hpp)
+// against the public functions.
 // Built with -fsanitize=address,undefined by tests/test_host_asan.py.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
 #include "aof.h"
+#include "aof_exposure_step.hpp"
 #include "aof_internal.hpp"
+#include "aof_mavlink.hpp"
 #include "optical_flow_rad.hpp"
 
 static unsigned rng_state = 777u;
 static unsigned rnd() { rng_state = rng_state * 1664525u + 1013904223u; return rng_state >> 8; }
+
+static uint64_t rnd64() { return ((uint64_t)rnd() << 48) ^ ((uint64_t)rnd() << 24) ^ rnd(); }
+template <typename T, typename U> static T bits_as(U u) { T t; static_assert(sizeof(T) == sizeof(U), "same size"); std::memcpy(&t, &u, sizeof(T)); return t; }
+
+struct Fields {
+    uint64_t time_usec;
+    int dt_us;
+    float ang_x, ang_y;
+    double gx, gy, gz;
+    int quality;
+    uint8_t seq, system_id, component_id;
+};
+
+// The kernels' packer and the facade's on one field set, each into heap blocks of exactly the documented sizes (the
+// sanitizer sees a byte too many).  Returns the frame's length, or -1 where lengths or bytes differ.
+static int packers_agree(const Fields &f)
+{
+    uint8_t *mine = (uint8_t *)std::malloc(AOF_SEQ_FRAME_BYTES), *theirs = (uint8_t *)std::malloc(AOF_SEQ_FRAME_BYTES);
+    uint8_t *payload = (uint8_t *)std::malloc(aof::kMavlinkPayloadBytes);
+    const int n = aof::pack_optical_flow_rad(mine, payload, f.time_usec, f.dt_us, f.ang_x, f.ang_y, f.gx, f.gy, f.gz, f.quality, f.seq,
+                                             f.system_id, f.component_id);
+    OpticalFlowRad m;
+    fillOpticalFlowRad(m, 0, f.time_usec, f.dt_us, f.ang_x, f.ang_y, f.gx, f.gy, f.gz, f.quality);
+    const size_t want = packOpticalFlowRad(m, f.seq, f.system_id, f.component_id, theirs);
+    const bool same = n > 0 && (size_t)n == want && want <= AOF_SEQ_FRAME_BYTES && std::memcmp(mine, theirs, want) == 0;
+    std::free(mine); std::free(theirs); std::free(payload);
+    return same ? n : -1;
+}
+
+// (a) a few thousand random field sets and the fixed cases; both frame lengths must occur (quality 0 truncates the
+// payload to 40 bytes, anything else leaves 44).  Returns the number of frames compared, or -1.
+static int check_packer()
+{
+    int frames = 0, n52 = 0, n56 = 0;
+    auto one = [&](const Fields &f) {
+        const int n = packers_agree(f);
+        if (n == 52) n52++;
+        if (n == 56) n56++;
+        frames++;
+        return n == (f.quality & 0xFF ? 56 : 52);
+    };
+    for (int it = 0; it < 4000; it++) {
+        Fields f;
+        f.time_usec = rnd64();
+        f.dt_us = (int)rnd64();
+        // any bit pattern but a NaN's (a NaN's payload need not survive being passed by value)
+        f.ang_x = bits_as<float>((uint32_t)rnd64()); f.ang_y = bits_as<float>((uint32_t)rnd64());
+        if (f.ang_x != f.ang_x) f.ang_x = 0.25f;
+        if (f.ang_y != f.ang_y) f.ang_y = -0.0f;
+        if (it & 1) {   // sums of a plausible size, or any finite or infinite double
+            f.gx = 1e-3 * ((double)(rnd() % 20001) - 10000.0); f.gy = 1e-4 * ((double)(rnd() % 20001) - 10000.0); f.gz = 1e-5 * (double)rnd();
+        } else {
+            f.gx = bits_as<double>(rnd64()); f.gy = bits_as<double>(rnd64()); f.gz = bits_as<double>(rnd64());
+            if (f.gx != f.gx) f.gx = 1.0;
+            if (f.gy != f.gy) f.gy = -2.0;
+            if (f.gz != f.gz) f.gz = 3.0;
+        }
+        f.quality = it % 7 == 0 ? 0 : (int)(rnd() % 256);
+        f.seq = (uint8_t)rnd(); f.system_id = (uint8_t)rnd(); f.component_id = (uint8_t)rnd();
+        if (!one(f)) return -1;
+    }
+    const Fields base = {5000000123ull, 66667, 0.01f, -0.02f, 0.1, 0.2, 0.3, 200, 7, 1, 100};
+    const int ends[2] = {0, 255};
+    for (int q : ends)
+        for (int seq : ends) {
+            Fields f = base;
+            f.quality = q; f.seq = (uint8_t)seq;
+            if (!one(f)) return -1;
+            f.gx = -0.0; f.gy = 0.0; f.gz = -1e-60;              // all three convert to float -0.0 (gy through its sign switch)
+            if ((float)f.gx != 0.0f || !std::signbit((float)f.gx) || !std::signbit((float)(-f.gy)) || !std::signbit((float)f.gz)) return -1;
+            if (!one(f)) return -1;
+            f.time_usec = 0xFF00000000000000ull | (uint64_t)seq; // the top byte set
+            if (!one(f)) return -1;
+        }
+    return n52 > 0 && n56 > 0 ? frames : -1;
+}
+
+// (b) the two forms of the checksum step (aof_mavlink.hpp) on every (checksum, byte), and the facade's with them
+static bool check_crc_steps()
+{
+    for (uint32_t crc = 0; crc < 65536u; crc++)
+        for (uint32_t b = 0; b < 256u; b++) {
+            const uint8_t byte = (uint8_t)b;
+            const uint32_t narrow = aof::crc_accumulate(byte, (uint16_t)crc);
+            if (narrow != aof::rx_crc(b, crc) || narrow != mavlinkCrcAccumulate(&byte, 1, (uint16_t)crc)) return false;
+        }
+    return true;
+}
+
+// (c) the shared bin and mean sample value against the public functions.  Returns the histograms compared, or -1.
+static int check_exposure()
+{
+    for (int v = 0; v < 256; v++) {
+        const int shared = aof::exposure_bin((uint32_t)v), pub = aof_exposure_bin(v);
+        if (shared < 0 || shared > AOF_EXPOSURE_BINS || (shared == AOF_EXPOSURE_BINS ? -1 : shared) != pub) return -1;
+    }
+    if (aof::exposure_bin(255u) != AOF_EXPOSURE_BINS || aof_exposure_bin(254) != 9 || aof_exposure_bin(0) != 0) return -1;
+    int hists = 0;
+    for (int it = 0; it < 2002; it++) {
+        uint32_t hist[AOF_EXPOSURE_BINS];
+        for (uint32_t &h : hist) h = it == 0 ? 0u : it == 1 ? 16384u : (it & 1) ? rnd() % 16385u : (uint32_t)rnd64();
+        const float shared = aof::exposure_msv(hist), pub = aof_exposure_msv(hist);
+        if (std::memcmp(&shared, &pub, sizeof(float)) != 0) return -1;
+        if (it == 0 && shared != 0.0f) return -1;
+        if (it == 1 && shared != 55.0f) return -1;   // 1 + 2 + ... + 10, every term exact
+        hists++;
+    }
+    return hists;
+}
 
 int main()
 {
@@ -56,6 +171,14 @@ int main()
     }
     uint32_t hist[AOF_EXPOSURE_BINS] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10};
     if (aof_exposure_msv(hist) <= 0.0f || aof_exposure_bin(255) != -1 || aof_exposure_bin(-3) != -1) return 10;
+    const int frames = check_packer();
+    if (frames < 0) return 12;
+    std::printf("host selftest: packer: %d frames equal to the facade's, lengths 52 and 56\n", frames);
+    if (!check_crc_steps()) return 13;
+    std::printf("host selftest: checksum: both steps and the facade's agree on 65536 x 256 inputs\n");
+    const int hists = check_exposure();
+    if (hists < 0) return 14;
+    std::printf("host selftest: exposure: 256 bins and %d mean sample values equal to the public functions\n", hists);
     std::printf("host selftest: %d valid parameter sets, %d rejected\n", valid, bad);
     return valid > 1000 ? 0 : 11;
 }

@@ -1,5 +1,7 @@
 """ASan + UBSan over the product's host-only logic (parameter validation, grids, reduction chunks,
-workspace layout, MAVLink packer), 20 000 random parameter sets including invalid ones."""
+workspace layout, MAVLink packer), 20 000 random parameter sets including invalid ones; and over the rules the host
+shares with the kernels (csrc/aof_mavlink.hpp, csrc/aof_exposure_step.hpp) compiled for the host: the kernels' packer
+against the facade's, the two checksum steps on every input, the exposure bin and mean sample value."""
 import os
 import subprocess
 
@@ -18,3 +20,6 @@ def test_host_logic_is_clean_under_asan_ubsan(tmp_path):
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, f"rc={r.returncode}\n{r.stdout}{r.stderr}"
     assert "valid parameter sets" in r.stdout
+    assert "packer: 4012 frames equal to the facade's, lengths 52 and 56" in r.stdout
+    assert "checksum: both steps and the facade's agree on 65536 x 256 inputs" in r.stdout
+    assert "exposure: 256 bins and 2002 mean sample values equal to the public functions" in r.stdout
