@@ -88,6 +88,19 @@ class BankParams(C.Structure):
                 ("system_id", C.c_uint8), ("component_id", C.c_uint8), ("first_seq", C.c_uint8)]
 
 
+class BankStream(C.Structure):
+    """``aof_bank_stream`` (include/aof.h): what belongs to one camera of a bank."""
+    _fields_ = [("focal_x", C.c_float), ("focal_y", C.c_float), ("output_rate", C.c_int32),
+                ("system_id", C.c_uint8), ("component_id", C.c_uint8), ("first_seq", C.c_uint8), ("reserved0", C.c_uint8),
+                ("offset_timestamp_usec", C.c_uint64), ("reserved1", C.c_uint64)]
+
+
+BANK_STREAM_DTYPE = np.dtype([("focal_x", "<f4"), ("focal_y", "<f4"), ("output_rate", "<i4"), ("system_id", "u1"),
+                              ("component_id", "u1"), ("first_seq", "u1"), ("reserved0", "u1"),
+                              ("offset_timestamp_usec", "<u8"), ("reserved1", "<u8")])                # aof_bank_stream
+assert BANK_STREAM_DTYPE.itemsize == 32 and C.sizeof(BankStream) == 32
+
+
 class BankLayout(C.Structure):
     """``struct aof_bank_layout`` (include/aof.h)."""
     _fields_ = [(n, C.c_size_t) for n in ("total_bytes", "frames", "state", "scratch")]
@@ -254,6 +267,8 @@ def _load():
         "aof_bank_reset_device": (C.c_int, [VP, P(BankParams), VP, VP, C.c_size_t, VP]),
         "aof_bank_push_device": (C.c_int, [VP, P(BankParams), VP, VP, VP, VP, VP, C.c_size_t, VP, VP, VP, VP]),
         "aof_set_bank_path": (C.c_int, [VP, C.c_int]),
+        "aof_bank_stream_from_params": (C.c_int, [P(BankParams), P(BankStream)]),
+        "aof_set_bank_streams": (C.c_int, [VP, VP, C.c_int32]),
         "aof_bank_camera_layout": (C.c_int, [P(Params), P(BankParams), P(BankCamera), P(BankLayout), P(C.c_size_t)]),
         "aof_bank_push_camera_device": (C.c_int, [VP, P(BankParams), P(BankCamera), VP, VP, VP, VP, VP, C.c_size_t, VP, VP, VP,
                                                   VP, VP, VP]),
@@ -421,6 +436,17 @@ def bank_params(n_streams, focal_x=216.6677, focal_y=216.2457, output_rate=15, o
     bp.offset_timestamp_usec = offset_timestamp_usec
     bp.system_id, bp.component_id, bp.first_seq = system_id, component_id, first_seq & 0xFF
     return bp
+
+
+def bank_stream_from_params(bp: BankParams, n=None):
+    """aof_bank_stream_from_params: the ``aof_bank_stream`` record the scalars of ``bp`` mean, as a numpy record of
+    BANK_STREAM_DTYPE -- or, with ``n``, an array of n copies of it (the start of a per-stream table)."""
+    rec = BankStream()
+    rc = lib.aof_bank_stream_from_params(C.byref(bp), C.byref(rec))
+    if rc:
+        raise AofError(rc, lib.aof_strerror(rc).decode())
+    one = np.frombuffer(bytes(rec), dtype=BANK_STREAM_DTYPE)[0]
+    return one if n is None else np.full(int(n), one, dtype=BANK_STREAM_DTYPE)
 
 
 def bank_layout(p: Params, bp: BankParams) -> BankLayout:
@@ -1153,6 +1179,22 @@ class FlowEngine:
                                                    samples.data_ptr(), counts.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
         return samples, counts
 
+    def set_bank_streams(self, streams=None, n_streams=None):
+        """aof_set_bank_streams: binds a uint8 CUDA tensor of S * 32 bytes (``aof_bank_stream`` records, BANK_STREAM_DTYPE;
+        16-byte aligned) to the context, or with None unbinds.  n_streams: S, where the tensor holds more than S records.  While it is bound every push and IMU call of S streams
+        takes focal lengths, output rate, time offset and MAVLink identity of stream s from record s; the kernels read
+        it when they run, so the tensor must stay alive and may be rewritten between ticks.  Enqueues nothing."""
+        if streams is None:
+            self._check(lib.aof_set_bank_streams(self._ctx, None, 0))
+            self._bank_streams = None
+            return
+        import torch
+        assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.numel() % 32 == 0
+        n = streams.numel() // 32 if n_streams is None else int(n_streams)
+        assert 1 <= n <= streams.numel() // 32
+        self._check(lib.aof_set_bank_streams(self._ctx, streams.data_ptr(), n))
+        self._bank_streams = streams   # (kept alive for as long as it is bound)
+
     def set_bank_path(self, path=0):
         """0: the library chooses between the one-launch tick kernel and the composed path, 1: the tick kernel where
         the configuration allows it, 2: always the composed path.  Same bytes either way."""
@@ -1273,6 +1315,10 @@ def facade_lib():
         f.aof_facade_bank_create.argtypes = [C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int]
         f.aof_facade_bank_destroy.argtypes = [C.c_void_p]
         f.aof_facade_bank_set_timestamp_offset.argtypes = [C.c_void_p, C.c_uint64]
+        f.aof_facade_bank_set_stream_focal_length.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float]
+        f.aof_facade_bank_set_stream_output_rate.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        f.aof_facade_bank_set_stream_identity.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+        f.aof_facade_bank_set_stream_timestamp_offset.argtypes = [C.c_void_p, C.c_int, C.c_uint64]
         f.aof_facade_bank_push.argtypes = [C.c_void_p] * 5
         f.aof_facade_bank_enable_camera.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32]
         f.aof_facade_bank_push_camera.argtypes = [C.c_void_p] * 5
@@ -1400,6 +1446,23 @@ class OpticalFlowBank:
 
     def setTimestampOffset(self, offset_usec):
         facade_lib().aof_facade_bank_set_timestamp_offset(self._h, int(offset_usec))
+
+    def setStreamFocalLength(self, s, fx, fy):
+        """Stream s's own focal lengths (px), from the next push on.  0, or -EINVAL (bad index or focal length)."""
+        return facade_lib().aof_facade_bank_set_stream_focal_length(self._h, int(s), float(fx), float(fy))
+
+    def setStreamOutputRate(self, s, hz):
+        """Stream s's own output rate (<= 0: every frame), from the next push on.  0, or -EINVAL for a bad index."""
+        return facade_lib().aof_facade_bank_set_stream_output_rate(self._h, int(s), int(hz))
+
+    def setStreamIdentity(self, s, system_id, component_id, first_seq):
+        """The MAVLink system id, component id and first sequence number of stream s's frames.  0, or -EINVAL."""
+        return facade_lib().aof_facade_bank_set_stream_identity(self._h, int(s), int(system_id) & 0xFF, int(component_id) & 0xFF,
+                                                                int(first_seq) & 0xFF)
+
+    def setStreamTimestampOffset(self, s, usec):
+        """Stream s's own MAVLink time offset (0: no frame for it); ignored once enableImu() is on.  0, or -EINVAL."""
+        return facade_lib().aof_facade_bank_set_stream_timestamp_offset(self._h, int(s), int(usec))
 
     def getPyramidLevels(self):
         return facade_lib().aof_facade_bank_pyramid_levels(self._h)

@@ -138,7 +138,7 @@ int check_tick(aof_ctx *ctx, const void *d_frames, const uint64_t *d_time_us, co
 // The tick's arguments for the kernels of k_bank.hip (frames: the caller's tick buffer, or the staging region).
 BankArgs bank_args(const aof_bank_params *bp, const Layout &L, uint8_t *bank, const uint8_t *frames, const uint64_t *d_time_us,
                    const uint8_t *d_active, const aof_gyro *d_gyro, aof_tick_record *d_records, uint8_t *d_mavlink,
-                   uint8_t *d_mavlink_len)
+                   uint8_t *d_mavlink_len, const aof_bank_stream *d_streams)
 {
     BankArgs a;
     std::memset(&a, 0, sizeof(a));   // (cam.camera == nullptr: a plain tick)
@@ -157,6 +157,7 @@ BankArgs bank_args(const aof_bank_params *bp, const Layout &L, uint8_t *bank, co
     a.focal_x = bp->focal_x; a.focal_y = bp->focal_y;
     a.offset_timestamp_usec = bp->offset_timestamp_usec;
     a.system_id = bp->system_id; a.component_id = bp->component_id; a.first_seq = bp->first_seq;
+    a.streams = d_streams;           // (bound: the kernels take the six values above from record s instead)
     a.records = d_records;
     a.mavlink = d_mavlink;
     a.mavlink_len = d_mavlink_len;
@@ -253,6 +254,11 @@ int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank
         if (!aligned(p.exposure, 4) || !aligned(p.derotated, 4))
             return ctx_fail(ctx, -EINVAL, "bank camera: exposure records and de-rotated pairs must be 4-byte aligned");
     }
+    // a bound per-stream array (aof_set_bank_streams) is for one stream count: the kernels index it by the stream
+    int32_t bound = 0;
+    const aof_bank_stream *d_streams = bank_streams(ctx, &bound);
+    if (d_streams && bound != bp->n_streams)
+        return ctx_fail(ctx, -EINVAL, "bank: n_streams differs from the array bound with aof_set_bank_streams");
     // before the first launch: a faulted or wedged context, or a thread on another device, must not touch the bank
     if ((rc = precheck(ctx))) return rc;
 
@@ -261,7 +267,8 @@ int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank
     uint32_t *hist = reinterpret_cast<uint32_t *>(bank + L.staging_hist);
     // what the flow kernels pair with the stored frames: the caller's frames, or the crops in the staging region
     const uint8_t *cur = p.camera ? staging : p.src;
-    BankArgs a = bank_args(bp, L, bank, cur, p.time_us, p.burst ? nullptr : p.select, p.gyro, p.records, p.mavlink, p.mavlink_len);
+    BankArgs a = bank_args(bp, L, bank, cur, p.time_us, p.burst ? nullptr : p.select, p.gyro, p.records, p.mavlink, p.mavlink_len,
+                           d_streams);
     if (p.camera) camera_args(&a, p.cam, p.src, hist, p.exposure, p.derotated);
     aof_flow *flows = reinterpret_cast<aof_flow *>(bank + L.flows);
     const BankBurst b = {p.burst ? p.rounds->n_rounds : 1, round_stride, p.burst ? p.select : nullptr};
@@ -316,6 +323,26 @@ int aof_set_bank_path(aof_ctx *ctx, int path)
 {
     if (!ctx || path < 0 || path > 2) return -EINVAL;
     set_bank_path(ctx, path);
+    return 0;
+}
+
+int aof_bank_stream_from_params(const aof_bank_params *bp, aof_bank_stream *out)
+{
+    if (!bp || !out) return -EINVAL;
+    std::memset(out, 0, sizeof(*out));
+    out->focal_x = bp->focal_x; out->focal_y = bp->focal_y;
+    out->output_rate = bp->output_rate;
+    out->system_id = bp->system_id; out->component_id = bp->component_id; out->first_seq = bp->first_seq;
+    out->offset_timestamp_usec = bp->offset_timestamp_usec;
+    return 0;
+}
+
+int aof_set_bank_streams(aof_ctx *ctx, const aof_bank_stream *d_streams, int32_t n_streams)
+{
+    if (!ctx) return -EINVAL;
+    if (d_streams && n_streams < 1) return ctx_fail(ctx, -EINVAL, "bank streams: an array needs n_streams >= 1");
+    if (!aligned(d_streams, 16)) return ctx_fail(ctx, -EINVAL, "bank streams: the array must be 16-byte aligned");
+    set_bank_streams(ctx, d_streams, n_streams);
     return 0;
 }
 

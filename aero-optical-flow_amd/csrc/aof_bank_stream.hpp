@@ -35,16 +35,51 @@ __device__ __forceinline__ bool exposure_due(const BankArgs &a, const BankState 
     return a.cam.exposure != nullptr && t >= st.next_exposure_us;
 }
 
+// What belongs to ONE camera and its vehicle: the limiter's rate and period, the focal lengths, the vehicle-time offset and
+// the MAVLink identity.  The one place they are resolved: from the call's scalars (aof_bank_params), or, with an array
+// bound (aof_set_bank_streams), from stream s's record -- two 16-byte loads by the lane that runs the tail, made inside
+// the tail so that nothing of the record is live across a pair.  The branch is uniform, and without an array the values
+// are the kernel arguments themselves.  The period is limiter_period_us's float: one correctly rounded division.
+struct BankStream {
+    int32_t output_rate;
+    float period_us, focal_x, focal_y;
+    uint64_t offset_timestamp_usec;
+    uint8_t system_id, component_id, first_seq;
+};
+static_assert(sizeof(aof_bank_stream) == 32 && offsetof(aof_bank_stream, output_rate) == 8 && offsetof(aof_bank_stream, system_id) == 12 &&
+              offsetof(aof_bank_stream, offset_timestamp_usec) == 16, "a stream record is two 16-byte words");
+
+__device__ __forceinline__ BankStream bank_stream(const BankArgs &a, uint32_t s)
+{
+    BankStream v;
+    if (a.streams) {
+        const uint4 *rec = reinterpret_cast<const uint4 *>(a.streams + s);
+        const uint4 lo = rec[0], hi = rec[1];
+        v.focal_x = __uint_as_float(lo.x); v.focal_y = __uint_as_float(lo.y);
+        v.output_rate = (int32_t)lo.z;
+        v.period_us = v.output_rate > 0 ? 1.0e6f / (float)v.output_rate : 0.0f;
+        v.system_id = (uint8_t)lo.w; v.component_id = (uint8_t)(lo.w >> 8); v.first_seq = (uint8_t)(lo.w >> 16);
+        v.offset_timestamp_usec = (uint64_t)hi.x | (uint64_t)hi.y << 32;
+    } else {
+        v.output_rate = a.output_rate; v.period_us = a.period_us;
+        v.focal_x = a.focal_x; v.focal_y = a.focal_y;
+        v.offset_timestamp_usec = a.offset_timestamp_usec;
+        v.system_id = a.system_id; v.component_id = a.component_id; v.first_seq = a.first_seq;
+    }
+    return v;
+}
+
 // One lane: a stream has been given a frame; `st` is the stream's state record, `f` the pixel record of (older frame,
 // new frame), `first` says that there was no older frame.  `o` indexes the frame's time, gyro sample and every output:
 // the stream's number in a tick, round * S + stream in a burst.  payload: kMavlinkPayloadBytes of LDS for the packer.
 // CAMERA: `hist` holds the frame's ten raw bin totals if the frame is due (exposure_due; LDS or global memory).
 // The ONE place a record is made: a tick's (bank_tail below) and a burst round's cannot differ.
 template <bool CAMERA>
-__device__ __forceinline__ void bank_tail_step(const BankArgs &a, size_t o, BankState &st, aof_flow f, bool first,
+__device__ __forceinline__ void bank_tail_step(const BankArgs &a, size_t o, uint32_t s, BankState &st, aof_flow f, bool first,
                                                uint8_t *payload, const uint32_t *hist = nullptr)
 {
     const uint64_t t64 = a.time_us[o];
+    const BankStream c = bank_stream(a, s);   // (behind the time's load: the record's loads are in flight with it, one wait for both)
     if constexpr (CAMERA) {
         if (a.cam.exposure) {
             aof_exposure_record e = {};
@@ -78,7 +113,7 @@ __device__ __forceinline__ void bank_tail_step(const BankArgs &a, size_t o, Bank
         f = aof_flow{};
     } else {
         quality = f.quality; px = f.flow_x; py = f.flow_y;
-        if (a.output_rate <= 0) {       // limitRate: no limit, the frame's own flow and quality
+        if (c.output_rate <= 0) {       // limitRate: no limit, the frame's own flow and quality
             dt_us = (int)(t - st.time_last_pub);
             st.time_last_pub = t;
         } else {
@@ -88,7 +123,7 @@ __device__ __forceinline__ void bank_tail_step(const BankArgs &a, size_t o, Bank
                 st.sum_flow_quality += quality;
                 st.valid_frame_count++;
             }
-            if ((float)(t - st.time_last_pub) > a.period_us) {
+            if ((float)(t - st.time_last_pub) > c.period_us) {
                 quality = 0;
                 if (st.valid_frame_count > 0) quality = (int)floorf((float)st.sum_flow_quality / (float)st.valid_frame_count);
                 px = st.sum_flow_x; py = st.sum_flow_y;
@@ -107,14 +142,14 @@ __device__ __forceinline__ void bank_tail_step(const BankArgs &a, size_t o, Bank
     uint8_t len = 0;
     if (quality >= 0) {
         float ang_x = 0.0f, ang_y = 0.0f;
-        if (!first) { ang_x = aof_atan2f(px, a.focal_x); ang_y = aof_atan2f(py, a.focal_y); }
+        if (!first) { ang_x = aof_atan2f(px, c.focal_x); ang_y = aof_atan2f(py, c.focal_y); }
         rec.dt_us = dt_us;
         rec.flow_x = ang_x; rec.flow_y = ang_y;
         rec.gyro_x = (float)st.gyro_x; rec.gyro_y = (float)st.gyro_y; rec.gyro_z = (float)st.gyro_z;
-        if (a.mavlink && a.offset_timestamp_usec != 0)   // (0: vehicle time not known, nothing is sent; mainloop.cpp:353-357)
-            len = (uint8_t)pack_optical_flow_rad(a.mavlink + o * AOF_SEQ_FRAME_BYTES, payload, a.offset_timestamp_usec + t64, dt_us,
+        if (a.mavlink && c.offset_timestamp_usec != 0)   // (0: vehicle time not known, nothing is sent; mainloop.cpp:353-357)
+            len = (uint8_t)pack_optical_flow_rad(a.mavlink + o * AOF_SEQ_FRAME_BYTES, payload, c.offset_timestamp_usec + t64, dt_us,
                                                  ang_x, ang_y, st.gyro_x, st.gyro_y, st.gyro_z, quality,
-                                                 (uint8_t)(a.first_seq + st.messages), a.system_id, a.component_id);
+                                                 (uint8_t)(c.first_seq + st.messages), c.system_id, c.component_id);
         st.messages++;
         st.gyro_x = 0.0; st.gyro_y = 0.0; st.gyro_z = 0.0;   // taken with the message (mainloop.cpp:333-334)
     }
@@ -128,7 +163,7 @@ __device__ __forceinline__ void bank_tail(const BankArgs &a, uint32_t s, aof_flo
                                           const uint32_t *hist = nullptr)
 {
     BankState st = a.state[s];
-    bank_tail_step<CAMERA>(a, s, st, f, first, payload, hist);
+    bank_tail_step<CAMERA>(a, s, s, st, f, first, payload, hist);
     a.state[s] = st;
 }
 

@@ -418,6 +418,16 @@ bool plan_small_batch(const aof_ctx *ctx, const uint8_t *prev, const uint8_t *cu
 
 int bank_path(const aof_ctx *ctx) { return ctx->bank_path; }
 void set_bank_path(aof_ctx *ctx, int path) { ctx->bank_path = path; }
+const aof_bank_stream *bank_streams(const aof_ctx *ctx, int32_t *n_streams)
+{
+    *n_streams = ctx->bank_streams_n;
+    return ctx->bank_streams;
+}
+void set_bank_streams(aof_ctx *ctx, const aof_bank_stream *d_streams, int32_t n_streams)
+{
+    ctx->bank_streams = d_streams;
+    ctx->bank_streams_n = d_streams ? n_streams : 0;
+}
 
 // Would a sequence-view call (frames viewed twice, n_pairs = frames - 1) run K1 as a pass of its own?  The sequence
 // pipeline asks, because its ingest kernel can leave K1's outputs (pixel sums at ws + L.sums, one level-1 frame per

@@ -318,6 +318,10 @@ struct BankArgs {
     float focal_x, focal_y;
     uint64_t offset_timestamp_usec;
     uint8_t system_id, component_id, first_seq;
+    // [S] per-stream values in place of output_rate .. first_seq (aof_set_bank_streams), or nullptr.  Here, beside the
+    // scalars it replaces, and not behind `cam`: measured there, the UNBOUND tick lost 0.3 us (LAB_LOG.md, "Stream bank
+    // per-stream cameras")
+    const aof_bank_stream *streams;
     aof_tick_record *records;      // [S]
     uint8_t *mavlink;              // [S][AOF_SEQ_FRAME_BYTES] or nullptr
     uint8_t *mavlink_len;          // [S]
@@ -385,6 +389,7 @@ int launch_bank_exposure_reset(aof_exposure_state *state, const uint8_t *mask, u
 struct ImuArgs {
     uint32_t n_streams, n_rounds, max_samples;   // S, K (1..AOF_BANK_BURST_MAX), M (1..AOF_IMU_SLOTS_MAX)
     uint8_t system_id, component_id, first_seq;
+    const aof_bank_stream *streams;    // [S] the identity of stream s in place of the triple above (aof_set_bank_streams), or nullptr
     const uint8_t *samples;            // aof_imu_sample [K][M][S]
     const uint8_t *sample_count;       // u8 [K][S] or nullptr (M everywhere)
     const uint64_t *time_us;           // [K][S]
@@ -413,6 +418,9 @@ bool plan_small_batch(const aof_ctx *ctx, const uint8_t *prev, const uint8_t *cu
                       void *d_workspace, SmallArgs *sm);
 int bank_path(const aof_ctx *ctx);            // (aof_batch.cpp) aof_set_bank_path's value
 void set_bank_path(aof_ctx *ctx, int path);
+// (aof_batch.cpp) aof_set_bank_streams' binding: the array (nullptr: none) and its stream count
+const aof_bank_stream *bank_streams(const aof_ctx *ctx, int32_t *n_streams);
+void set_bank_streams(aof_ctx *ctx, const aof_bank_stream *d_streams, int32_t n_streams);
 // (aof_capi.hip) sticky fault / wedged state and current-device check of a context, before anything is enqueued; and
 // aof_last_error's text for the callers outside aof_capi.hip
 int precheck(aof_ctx *ctx);

@@ -80,7 +80,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
         __syncthreads();
         if (tid == 0) {
             BankState st = s_state;
-            bank_tail_step<CAMERA>(a, o, st, first ? aof_flow{} : s_record, first, s_payload, s_hist);
+            bank_tail_step<CAMERA>(a, o, s, st, first ? aof_flow{} : s_record, first, s_payload, s_hist);
             s_state = st;
         }
         newest = cur;

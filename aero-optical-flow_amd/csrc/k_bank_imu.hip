@@ -57,6 +57,11 @@ __global__ __launch_bounds__(kThreads) void k_bank_imu(ImuArgs a)
         } else {
             counts[0] = counts[1] = (uint64_t)M * 0x0101010101010101ull;
         }
+        // the stream's MAVLink identity: the call's, or with an array bound (aof_set_bank_streams) the fourth word of the
+        // stream's own record (system_id, component_id, first_seq, reserved); the branch is uniform
+        uint32_t id = (uint32_t)a.system_id | (uint32_t)a.component_id << 8 | (uint32_t)a.first_seq << 16;
+        if (a.streams) id = reinterpret_cast<const uint32_t *>(a.streams + s)[3];
+        const uint8_t system_id = (uint8_t)id, component_id = (uint8_t)(id >> 8), first_seq = (uint8_t)(id >> 16);
         uint8_t *payload = s_payload + threadIdx.x * kMavlinkPayloadBytes;
         for (uint32_t k = 0; k <= last; k++) {
             const size_t o = (size_t)k * S + s;
@@ -86,9 +91,9 @@ __global__ __launch_bounds__(kThreads) void k_bank_imu(ImuArgs a)
             __builtin_memcpy(&rec, rw, sizeof(rec));
             ImuFrame f;
             uint8_t len = 0;
-            if (imu_take(st, rec, t, a.first_seq, f) && a.mavlink)
+            if (imu_take(st, rec, t, first_seq, f) && a.mavlink)
                 len = (uint8_t)pack_optical_flow_rad(a.mavlink + o * AOF_SEQ_FRAME_BYTES, payload, f.time_usec, rec.dt_us, rec.flow_x,
-                                                     rec.flow_y, f.gx, f.gy, f.gz, rec.quality, f.seq, a.system_id, a.component_id);
+                                                     rec.flow_y, f.gx, f.gy, f.gz, rec.quality, f.seq, system_id, component_id);
             __builtin_memcpy(rw, &rec, sizeof(rec));
             uint32_t *rout = reinterpret_cast<uint32_t *>(a.records_out + o * kRecordBytes);
 #pragma unroll

@@ -6,7 +6,10 @@
 // (/root/reference/src/mainloop.cpp:322-373) come back as one dense, ordered list (the bank's outbox).
 // Per stream, the pushes in which it has an entry, with their quality, dt_us, flow_x and flow_y, are
 // exactly the calcFlow() calls of an OpticalFlowOpenCV object, fed the same frames and (uint32_t) times,
-// that return >= 0, with their outputs.  C++11, no exceptions; every host wait is bounded.
+// that return >= 0, with their outputs.  The cameras need not be alike: the constructor's focal lengths and
+// output rate are every stream's starting values, and the setStream...() calls give one stream its own --
+// stream s then equals an OpticalFlowOpenCV(fx_s, fy_s, rate_s, ...) object.  C++11, no exceptions; every
+// host wait is bounded.
 #pragma once
 
 #include <cstdint>
@@ -14,6 +17,7 @@
 struct aof_outbox_entry;   // include/aof.h: stream, MAVLink frame, tick record (quality, dt_us, flow_x, flow_y, gyro sums)
 struct aof_gyro;           // include/aof.h: gyro angles integrated over the interval that ends at a frame
 struct aof_exposure_command;   // include/aof.h: what the auto-exposure controller decided for a stream in a tick
+struct aof_bank_stream;        // include/aof.h: one stream's focal lengths, output rate, time offset and MAVLink identity
 
 class OpticalFlowBank {
 public:
@@ -25,8 +29,21 @@ public:
 	~OpticalFlowBank();
 
 	// The MAVLink time offset (vehicle time of time stamp 0, mainloop.cpp:360).  0, the initial value: the
-	// entries carry their records and no MAVLink frame (mainloop.cpp:353-357).
+	// entries carry their records and no MAVLink frame (mainloop.cpp:353-357).  Sets every stream's offset.
 	void setTimestampOffset(uint64_t offset_usec);
+
+	// What belongs to ONE camera and its vehicle (the reference takes these per process from its command line):
+	// stream s's focal lengths in pixels (> 0), its output rate (<= 0 publishes every frame; the limiter's sums
+	// stay as they stand, the new period applies from the next push on), the system id, component id and first
+	// sequence number of its MAVLink frames, and its time offset (0: records and no frame for this stream;
+	// ignored once enableImu() is on, as setTimestampOffset() is).  Each takes effect with the next push and
+	// returns 0, or -EINVAL for a bad stream index (or a focal length that is not > 0), the object unchanged.
+	// An object on which none of them was called runs exactly as one without them.  With enableImu() the frames
+	// carry each stream's identity.
+	int setStreamFocalLength(int stream, float f_length_x, float f_length_y);
+	int setStreamOutputRate(int stream, int output_rate);
+	int setStreamIdentity(int stream, uint8_t system_id, uint8_t component_id, uint8_t first_seq);
+	int setStreamTimestampOffset(int stream, uint64_t offset_usec);
 
 	// One tick.  frames: host memory, stream s's img_width x img_height grey frame at s * img_width *
 	// img_height; img_time_us: [n_streams], the limiter sees (uint32_t)t; active: [n_streams], non-zero =
@@ -111,6 +128,8 @@ private:
 	int collect();
 	int takeImu();
 	int receive();
+	int syncStreams();
+	aof_bank_stream *streamRecord(int stream);
 
 	int image_width, image_height, n_streams;
 	struct Impl;

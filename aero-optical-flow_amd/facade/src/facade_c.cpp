@@ -82,6 +82,22 @@ void aof_facade_bank_set_timestamp_offset(void *bank, uint64_t offset_usec)
 {
 	static_cast<OpticalFlowBank *>(bank)->setTimestampOffset(offset_usec);
 }
+int aof_facade_bank_set_stream_focal_length(void *bank, int stream, float fx, float fy)
+{
+	return static_cast<OpticalFlowBank *>(bank)->setStreamFocalLength(stream, fx, fy);
+}
+int aof_facade_bank_set_stream_output_rate(void *bank, int stream, int output_rate)
+{
+	return static_cast<OpticalFlowBank *>(bank)->setStreamOutputRate(stream, output_rate);
+}
+int aof_facade_bank_set_stream_identity(void *bank, int stream, int system_id, int component_id, int first_seq)
+{
+	return static_cast<OpticalFlowBank *>(bank)->setStreamIdentity(stream, (uint8_t)system_id, (uint8_t)component_id, (uint8_t)first_seq);
+}
+int aof_facade_bank_set_stream_timestamp_offset(void *bank, int stream, uint64_t offset_usec)
+{
+	return static_cast<OpticalFlowBank *>(bank)->setStreamTimestampOffset(stream, offset_usec);
+}
 int aof_facade_bank_push(void *bank, const uint8_t *frames, const uint64_t *img_time_us, const uint8_t *active,
 			 const aof_gyro *gyro)
 {

@@ -9,6 +9,8 @@
 // frames, so that the collect launch lists only what the reference would have sent.  With enableMavlinkRx() the
 // samples come from the device as well: the bytes pushMavlink() queued go over in one copy, and the receive launch
 // (aof_bank_mavlink_rx_device) in front of the tick parses them into the sample block the IMU call reads.
+// The setStream...() calls write a pinned shadow array of per-stream records (aof_bank_stream); the next push copies
+// it to the device on the object's stream and, the first time, binds it to the context (aof_set_bank_streams).
 #include <cerrno>
 #include <chrono>
 #include <cstdio>
@@ -73,6 +75,11 @@ struct OpticalFlowBank::Impl {
 	uint8_t *h_rx, *d_rx;              // one block on both sides: u8 [n_streams][max_bytes], then u16 [n_streams]
 	size_t rx_bytes, off_rx_len;
 	aof_mavlink_rx_state *d_rx_state;
+	// the per-stream form (setStream...()): the shadow records start from the constructor's values; nothing is copied or
+	// bound before the first setter
+	aof_bank_stream *h_streams, *d_streams;   // pinned, device: [n_streams]
+	bool streams_used, streams_dirty, streams_bound;
+	bool streams_copying;              // a copy of the shadow is enqueued: it is through once collect() has seen the tick's tag
 };
 
 OpticalFlowBank::OpticalFlowBank(float f_length_x, float f_length_y, int output_rate, int img_width, int img_height,
@@ -117,6 +124,8 @@ OpticalFlowBank::OpticalFlowBank(float f_length_x, float f_length_y, int output_
 		     hipMalloc((void **)&m->d_records, S * sizeof(aof_tick_record)) == hipSuccess &&
 		     hipMalloc((void **)&m->d_mavlink, S * AOF_SEQ_FRAME_BYTES) == hipSuccess &&
 		     hipMalloc((void **)&m->d_lens, S) == hipSuccess &&
+		     hipHostMalloc((void **)&m->h_streams, S * sizeof(aof_bank_stream), hipHostMallocDefault) == hipSuccess &&
+		     hipMalloc((void **)&m->d_streams, S * sizeof(aof_bank_stream)) == hipSuccess &&
 		     aof_outbox_alloc_host(m->outbox_bytes, (void **)&m->outbox) == 0;
 	}
 	_m = m;
@@ -125,6 +134,7 @@ OpticalFlowBank::OpticalFlowBank(float f_length_x, float f_length_y, int output_
 		return;
 	}
 	std::memset(m->outbox, 0, m->outbox_bytes);
+	for (size_t s = 0; s < S; s++) aof_bank_stream_from_params(&m->bp, &m->h_streams[s]);
 	std::snprintf(_err, sizeof(_err), "ok");
 	if (aof_bank_reset_device(m->ctx, &m->bp, NULL, m->d_bank, m->bank_bytes, m->stream)) {
 		fail(-EIO, aof_last_error(m->ctx));
@@ -152,6 +162,8 @@ OpticalFlowBank::~OpticalFlowBank()
 		if (m->d_sensor) (void)hipFree(m->d_sensor);
 		if (m->h_sensor) (void)hipHostFree(m->h_sensor);
 		if (m->outbox) aof_outbox_free_host(m->outbox);
+		if (m->d_streams) (void)hipFree(m->d_streams);
+		if (m->h_streams) (void)hipHostFree(m->h_streams);
 		if (m->d_lens) (void)hipFree(m->d_lens);
 		if (m->d_mavlink) (void)hipFree(m->d_mavlink);
 		if (m->d_records) (void)hipFree(m->d_records);
@@ -200,7 +212,81 @@ bool OpticalFlowBank::waitIdle()
 
 void OpticalFlowBank::setTimestampOffset(uint64_t offset_usec)
 {
-	if (_m) _m->bp.offset_timestamp_usec = offset_usec;
+	if (!_m) return;
+	_m->bp.offset_timestamp_usec = offset_usec;
+	if (!_m->h_streams) return;
+	for (int s = 0; s < n_streams; s++) _m->h_streams[s].offset_timestamp_usec = offset_usec;
+	_m->streams_dirty = true;
+}
+
+// The shadow record of stream s for a setter, or NULL (bad index, no engine); the next push copies the array.
+aof_bank_stream *OpticalFlowBank::streamRecord(int s)
+{
+	if (!_m || !_m->h_streams || s < 0 || s >= n_streams) return NULL;
+	_m->streams_used = true;
+	_m->streams_dirty = true;
+	return &_m->h_streams[s];
+}
+
+int OpticalFlowBank::setStreamFocalLength(int s, float f_length_x, float f_length_y)
+{
+	if (!(f_length_x > 0.0f) || !(f_length_y > 0.0f)) return -EINVAL;
+	aof_bank_stream *r = streamRecord(s);
+	if (!r) return -EINVAL;
+	r->focal_x = f_length_x;
+	r->focal_y = f_length_y;
+	return 0;
+}
+
+int OpticalFlowBank::setStreamOutputRate(int s, int output_rate)
+{
+	aof_bank_stream *r = streamRecord(s);
+	if (!r) return -EINVAL;
+	r->output_rate = output_rate;
+	return 0;
+}
+
+int OpticalFlowBank::setStreamIdentity(int s, uint8_t system_id, uint8_t component_id, uint8_t first_seq)
+{
+	aof_bank_stream *r = streamRecord(s);
+	if (!r) return -EINVAL;
+	r->system_id = system_id;
+	r->component_id = component_id;
+	r->first_seq = first_seq;
+	return 0;
+}
+
+int OpticalFlowBank::setStreamTimestampOffset(int s, uint64_t offset_usec)
+{
+	if (!_m || s < 0 || s >= n_streams) return -EINVAL;
+	if (_m->imu) return 0;   // (the IMU form keeps every stream's offset in its IMU state, as with setTimestampOffset())
+	aof_bank_stream *r = streamRecord(s);
+	if (!r) return -EINVAL;
+	r->offset_timestamp_usec = offset_usec;
+	return 0;
+}
+
+// In front of a tick: the shadow records to the device if a setter changed them, and bound to the context the first
+// time.  Without a setter nothing happens: the tick runs on the scalars, as it always did.  The shadow counts as copied
+// only once collect() has waited for the tick: a setter behind a push that failed in between writes an array that is
+// still marked dirty, and the object has failed for good by then.
+int OpticalFlowBank::syncStreams()
+{
+	Impl *m = _m;
+	if (!m->streams_used) return 0;
+	if (m->streams_dirty) {
+		if (hipMemcpyAsync(m->d_streams, m->h_streams, (size_t)n_streams * sizeof(aof_bank_stream), hipMemcpyHostToDevice,
+				   m->stream) != hipSuccess)
+			return fail(-EIO, "copy of the per-stream records failed");
+		// (still dirty: only collect(), which waits for the tick, knows that the copy has read the shadow; a push that
+		// fails behind this point copies again)
+		m->streams_copying = true;
+	}
+	if (!m->streams_bound) {
+		if (aof_set_bank_streams(m->ctx, m->d_streams, n_streams)) return fail(-EIO, aof_last_error(m->ctx));
+		m->streams_bound = true;
+	}
+	return 0;
 }
 
 int OpticalFlowBank::getPyramidLevels() const
@@ -235,10 +321,12 @@ int OpticalFlowBank::push(const uint8_t *frames, const uint64_t *img_time_us, co
 	}
 	if (hipMemcpyAsync(m->d_stage, m->h_stage, m->stage_bytes, hipMemcpyHostToDevice, m->stream) != hipSuccess)
 		return fail(-EIO, "copy of the tick's frames failed");
+	int rc = syncStreams();
+	if (rc) return rc;
 	// with the IMU form the tick leaves records only: the IMU call behind it completes them and packs the frames
 	aof_bank_params bp = m->bp;
 	if (m->imu) bp.offset_timestamp_usec = 0;
-	int rc = aof_bank_push_device(m->ctx, &bp, m->d_stage, reinterpret_cast<const uint64_t *>(m->d_stage + m->off_times),
+	rc = aof_bank_push_device(m->ctx, &bp, m->d_stage, reinterpret_cast<const uint64_t *>(m->d_stage + m->off_times),
 				      active ? m->d_stage + m->off_active : NULL,
 				      gyro && !m->imu ? reinterpret_cast<const aof_gyro *>(m->d_stage + m->off_gyro) : NULL, m->d_bank,
 				      m->bank_bytes, m->d_records, m->imu ? NULL : m->d_mavlink, m->imu ? NULL : m->d_lens, m->stream);
@@ -261,6 +349,10 @@ int OpticalFlowBank::collect()
 	const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
 	while (__atomic_load_n(word, __ATOMIC_ACQUIRE) != tag) {
 		if (secondsSince(t0) > kDeadlineS) return fail(-ETIMEDOUT, "the tick did not finish within the deadline");
+	}
+	if (m->streams_copying) {   // the copy of the per-stream records in front of the tick is through as well
+		m->streams_copying = false;
+		m->streams_dirty = false;
 	}
 	if (m->imu) std::memset(m->h_imu + m->off_imu_counts, 0, (size_t)n_streams);   // the tick took the queued samples
 	if (m->rx) std::memset(m->h_rx + m->off_rx_len, 0, (size_t)n_streams * sizeof(uint16_t));   // and the queued bytes
@@ -343,9 +435,11 @@ int OpticalFlowBank::pushCamera(const uint8_t *sensor_frames, const uint64_t *im
 	    hipMemcpyAsync(m->d_stage + m->off_times, m->h_stage + m->off_times, m->stage_bytes - m->off_times,
 			   hipMemcpyHostToDevice, m->stream) != hipSuccess)
 		return fail(-EIO, "copy of the tick's sensor frames failed");
+	int rc = syncStreams();
+	if (rc) return rc;
 	aof_bank_params bp = m->bp;
 	if (m->imu) bp.offset_timestamp_usec = 0;   // (records only, as in push())
-	int rc = aof_bank_push_camera_device(m->ctx, &bp, &m->cam, m->d_sensor,
+	rc = aof_bank_push_camera_device(m->ctx, &bp, &m->cam, m->d_sensor,
 					     reinterpret_cast<const uint64_t *>(m->d_stage + m->off_times),
 					     active ? m->d_stage + m->off_active : NULL,
 					     gyro && !m->imu ? reinterpret_cast<const aof_gyro *>(m->d_stage + m->off_gyro) : NULL, m->d_bank,

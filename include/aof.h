@@ -470,6 +470,46 @@ int aof_bank_push_device(aof_ctx *ctx, const aof_bank_params *bp, const uint8_t 
  * -EINVAL: NULL ctx, path outside 0..2. */
 int aof_set_bank_path(aof_ctx *ctx, int path);
 
+/* ---- the stream bank with per-stream cameras: focal lengths, output rate, vehicle time and MAVLink identity ----
+ * aof_bank_params carries ONE focal length pair, output rate, time offset and MAVLink identity for all S streams: S
+ * cameras built with identical arguments.  Real cameras differ in exactly these (the reference takes them per process
+ * from its command line), so a caller may bind an array of S records in device memory to the context; while it is
+ * bound, stream s of every push takes these six values from record s instead of from aof_bank_params:
+ *   * period of the rate limiter: 1.0e6f / (float)output_rate, one correctly rounded float division -- the float the
+ *     host computes for aof_bank_params.output_rate; output_rate <= 0 publishes every frame;
+ *   * angles: aof_flow_angle(pixel flow, the stream's focal length);
+ *   * a frame is packed iff d_mavlink is given and the stream's offset_timestamp_usec is non-zero, with the stream's
+ *     system_id and component_id and the sequence number (uint8_t)(first_seq + messages);
+ *   * a changed output_rate leaves the limiter's sums as they stand: the new period applies from that tick on.
+ * The four pushes (aof_bank_push_device, _camera_device, _burst_device, _camera_burst_device) use the array when
+ * bp->n_streams equals the bound count; aof_bank_imu_device with ip->n_streams equal to it takes system_id,
+ * component_id and first_seq of stream s from the array (its time offsets are per stream already, in aof_imu_state).
+ * The scalars of bp / ip are still checked as without a binding and are otherwise ignored.  A push or IMU call whose
+ * stream count differs from the bound one returns -EINVAL and writes nothing.
+ * The KERNELS read the array, when they run: the caller may rewrite records between ticks in stream order, and a
+ * captured graph replays against whatever the array holds at replay.  The host cannot see device data: the values are
+ * used as they are (a focal length that is not > 0 gives whatever aof_flow_angle gives for it).  A burst indexes the
+ * array by the stream's number alone, in every round.
+ * Contract: stream s's records, frames, lengths, stored frame and state are byte-identical to what a bank of ONE stream
+ * produces for the same inputs when its aof_bank_params carries record s's values; and if all S records equal
+ * aof_bank_stream_from_params(bp), every output and the whole bank are byte-identical to the unbound call.
+ * Not per stream, and as they were: the exposure interval and the exposure-control constants, the frame size, the
+ * sequence pipeline (aof_sequence_device) and the per-call facade classes. */
+typedef struct aof_bank_stream {     /* 32 bytes, 16-byte aligned, one per stream */
+    float    focal_x, focal_y;        /* px */
+    int32_t  output_rate;             /* Hz; <= 0 publishes every frame */
+    uint8_t  system_id, component_id, first_seq, reserved0;
+    uint64_t offset_timestamp_usec;   /* 0: records only for THIS stream (mainloop.cpp:353-357) */
+    uint64_t reserved1;               /* 0 */
+} aof_bank_stream;
+/* Host only: the record the scalars of bp mean (reserved fields zero).  -EINVAL: NULL bp or out. */
+int aof_bank_stream_from_params(const aof_bank_params *bp, aof_bank_stream *out);
+/* Stores the pointer on the context, like aof_set_bank_path: enqueues nothing, allocates nothing, reads nothing.
+ * d_streams: aof_bank_stream [n_streams] in device memory owned by the caller, alive and 16-byte aligned for as long
+ * as it is bound; NULL (with n_streams 0) unbinds.  -EINVAL: NULL ctx, a non-NULL array with n_streams < 1, an array
+ * that is not 16-byte aligned (the binding stays as it was). */
+int aof_set_bank_streams(aof_ctx *ctx, const aof_bank_stream *d_streams, int32_t n_streams);
+
 /* ---- the stream bank with sensor frames: crop, exposure statistics and de-rotation in the tick ----
  * The reference's per-frame loop does not begin at calcFlow(): a full sensor frame arrives, is centre-cropped to the
  * engine's size (mainloop.cpp:295-298,317-319), the crop's central 128x128 region goes into the 10-bin histogram whose

@@ -39,6 +39,11 @@ alone -- mix "imu" -- and inside about 1 KB of other frames -- mix "mixed"):
                 yardstick of D;
   D             one host-to-device copy of the receive block (bytes and lengths) + aof_bank_mavlink_rx_device + the same
                 push and IMU call.
+With --per-stream, the plain tick with an array of per-stream records bound (aof_set_bank_streams: every stream its own
+focal lengths, output rate, offset and MAVLink identity) against the tick on the scalars of aof_bank_params:
+  U1 / U2       aof_bank_push_device, nothing bound, on the one-launch kernel (1) and the composed path (2) -- also what a
+                build without the call runs (AOF_LIB: the yardstick of U on this build);
+  P1 / P2       the same tick with S distinct records bound.
 Every leg settles for about 0.2 s of untimed ticks, then times at least --ticks ticks and at least --seconds seconds
 with the host clock around ticks that end in a synchronise.  The whole sweep runs --repeats times: the difference
 between the repeats is the run-to-run spread a difference between legs has to beat.
@@ -48,7 +53,8 @@ between the repeats is the run-to-run spread a difference between legs has to be
     python tools/bench_bank.py --outbox > profiles/bank_outbox_sweep.txt
     python tools/bench_bank.py --exposure-control > profiles/bank_exposure_control_sweep.txt
     python tools/bench_bank.py --imu > profiles/bank_imu_sweep.txt
-    python tools/bench_bank.py --mavlink-rx > profiles/bank_mavlink_rx_sweep.txt"""
+    python tools/bench_bank.py --mavlink-rx > profiles/bank_mavlink_rx_sweep.txt
+    python tools/bench_bank.py --per-stream --streams 64,1024 > profiles/bank_per_stream_ab.txt"""
 import argparse
 import ctypes as C
 import importlib
@@ -118,11 +124,26 @@ class Inputs:
         self.gyro = torch.full((S, 4), 0.001, dtype=torch.float32, device=dev)
 
 
-def leg_tick(p, S, path, inp, dev, a):
+def distinct_streams(S):
+    """BANK_STREAM_DTYPE [S]: no two neighbours alike in focal lengths, identity and offset.  The rate is the unbound
+    leg's 15 Hz in every record: streams with other rates publish in other ticks, and a tick in which any stream publishes
+    pays for a frame being packed -- that would time another workload, not the array."""
+    s = np.arange(S)
+    recs = np.zeros(S, aof.BANK_STREAM_DTYPE)
+    recs["focal_x"], recs["focal_y"] = 150.0 + (s % 97) * 1.25, 160.0 + (s % 89) * 1.5
+    recs["output_rate"] = 15
+    recs["system_id"], recs["component_id"], recs["first_seq"] = s % 255 + 1, 100 + s % 3, s % 256
+    recs["offset_timestamp_usec"] = 5_000_000 + s
+    return recs
+
+
+def leg_tick(p, S, path, inp, dev, a, per_stream=False):
     eng = aof.FlowEngine(p, 0)
     eng.set_bank_path(path)
     bp = aof.bank_params(S, FX, FY, 15, 5_000_000, 1, 100, 0)
     bank = eng.bank_create(bp, dev)
+    if per_stream:
+        eng.set_bank_streams(torch.from_numpy(distinct_streams(S).view(np.uint8).reshape(S, 32)).to(dev))
     recs = torch.empty((S, 48), dtype=torch.uint8, device=dev)
     wire = torch.empty((S, 56), dtype=torch.uint8, device=dev)
     lens = torch.empty(S, dtype=torch.uint8, device=dev)
@@ -1045,6 +1066,36 @@ def class_marker(dev):
     return ms
 
 
+def per_stream_sweep(a, dev):
+    print("# legs: U1/U2 plain tick on the scalars of aof_bank_params on path 1/2, P1/P2 the same tick with S distinct aof_bank_stream "
+          "records bound (MAVLink frames on, all streams active, gyro)")
+    print("# us = microseconds per tick (host clock, ticks ending in a synchronise)")
+    bound = hasattr(aof.lib, "aof_set_bank_streams")      # (AOF_LIB may name a build without the call: U legs only)
+    legs = [("U1", 1, False), ("U2", 2, False)] + ([("P1", 1, True), ("P2", 2, True)] if bound else [])
+    sizes = [int(s) for s in a.streams.split(",")]
+    results = {}
+    for rep in range(a.repeats):
+        for cfg in a.configs.split(","):
+            p = params_of(cfg)
+            for S in sizes:
+                inp = Inputs(p, S, dev)
+                for name, path, per_stream in legs:
+                    sec, n = leg_tick(p, S, path, inp, dev, a, per_stream)
+                    results.setdefault((cfg, S, name), []).append(sec)
+                    print(f"rep {rep} {cfg:11s} S={S:6d} {name:2s} {sec * 1e6:10.2f} us  ({n} ticks)", flush=True)
+                del inp
+                torch.cuda.empty_cache()
+    print("# ---- summary (mean of the repeats; spread = |difference of the repeats| / mean) ----")
+    for cfg in a.configs.split(","):
+        for S in sizes:
+            m = {n: float(np.mean(results[(cfg, S, n)])) for n, _, _ in legs}
+            sp = {n: abs(results[(cfg, S, n)][0] - results[(cfg, S, n)][-1]) / m[n] for n in m}
+            line = f"{cfg:11s} S={S:6d}  " + "  ".join(f"{n} {m[n] * 1e6:9.2f} us (+-{sp[n] * 100:4.1f} %)" for n in m)
+            if bound:
+                line += f"  P1/U1 {m['P1'] / m['U1']:5.3f}  P2/U2 {m['P2'] / m['U2']:5.3f}"
+            print(line)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--streams", default="1,16,64,128,256,1024,4096,16384")
@@ -1062,6 +1113,7 @@ def main():
     ap.add_argument("--exposure-control", action="store_true", help="the sweep of the auto-exposure controller: legs T, C, H")
     ap.add_argument("--imu", action="store_true", help="the sweep of the IMU call: legs G, D")
     ap.add_argument("--mavlink-rx", action="store_true", help="the sweep of the MAVLink receive: legs H, D on two traffic mixes")
+    ap.add_argument("--per-stream", action="store_true", help="the plain tick with per-stream records bound against the unbound tick: legs U1, U2, P1, P2")
     ap.add_argument("--forms", default="plain,camera", help="--burst: entry points to sweep")
     ap.add_argument("--input-bytes-max", type=float, default=24 * 2**30, help="--burst: sizes whose K rounds of input exceed this are skipped")
     a = ap.parse_args()
@@ -1082,6 +1134,8 @@ def main():
     print(f"# device: {torch.cuda.get_device_name(0)}")
     if not a.no_marker:
         print(f"# class marker: exhaustive C2 K2 (1 024 VGA pairs) {class_marker(dev):.4f} ms")
+    if a.per_stream:
+        return per_stream_sweep(a, dev)
     if a.mavlink_rx:
         return mavlink_rx_sweep(a, dev)
     if a.imu:
