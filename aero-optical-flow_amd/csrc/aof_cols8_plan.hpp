@@ -40,5 +40,52 @@ constexpr int kColsThreads = 256;
 constexpr int kColsMaxRows = 8, kColsMinRows = 2;
 constexpr int64_t kColsWavesWanted = 3072;
 constexpr int64_t kWaveSlots = 4096;   // 256 CUs x 4 SIMDs x 4 waves of this kernel
+constexpr int64_t kColsMaxUnits = 0x7FFF0000ll;   // units are indexed with 31 bits
+
+// One launch of the walk as the host plans it: the plan the kernel decodes its units with, and the launch's geometry.
+// Host only, no HIP: tests/native/host_selftest.cpp holds it to the model of tests/cols_plan_ref.py.
+struct ColsLaunch {
+    ColsPlan plan;
+    int64_t per;          // pairs one launch can hold (a call of more pairs is cut into several launches)
+    int64_t pairs;        // pairs of this launch
+    int64_t tail_pairs;   // of which the last ones get the short segments
+    int64_t units, wgs;   // units (threads that decode one) and workgroups of kColsThreads
+};
+
+inline ColsSegments cols_segments(const Grid &g, int len)
+{
+    ColsSegments s;
+    s.len = len > g.ny ? g.ny : len;
+    s.segs = (g.ny + s.len - 1) / s.len;
+    s.units_per_pair = (uint32_t)((s.segs * g.nx + 63) / 64 * 64);
+    s.div_units = fastdiv_make(s.units_per_pair);
+    return s;
+}
+
+// The launch that starts at pair `done` of a call of n_pairs pairs (w, h, pair_stride, cur: what `aligned` depends on).
+inline ColsLaunch cols_plan_make(const Grid &g, int w, int h, int64_t pair_stride, uintptr_t cur, int64_t n_pairs, int64_t done = 0)
+{
+    auto waves = [&](int len) { return n_pairs * (int64_t)(cols_segments(g, len).units_per_pair / 64); };
+    int len = kColsMaxRows;
+    while (len > kColsMinRows && waves(len) < kColsWavesWanted) len--;
+    ColsLaunch l;
+    ColsPlan &plan = l.plan;
+    plan.head = cols_segments(g, len);
+    plan.tail = cols_segments(g, len / 2 < kColsMinRows ? kColsMinRows : len / 2);
+    plan.div_nx = fastdiv_make((uint32_t)g.nx);
+    // (columns eight bytes apart: every lane of a pair is misaligned alike and finds its last bytes in the next column's load)
+    plan.aligned = (g.step_x == 8 && w % 4 == 0 && pair_stride % 4 == 0 && cur % 4 == 0 && ((int64_t)w * h) % 4 == 0) ? 1u : 0u;
+    l.per = kColsMaxUnits / plan.tail.units_per_pair;   // (the tail's units per pair are the larger)
+    l.pairs = n_pairs - done < l.per ? n_pairs - done : l.per;
+    // pairs beyond the last full generation of wave slots (256 CUs x 16 waves) get the short segments
+    const int64_t wpp = plan.head.units_per_pair / 64, all = l.pairs * wpp, rest = all % kWaveSlots;
+    l.tail_pairs = 0;
+    if (rest != 0 && rest * 5 < kWaveSlots * 4 && plan.tail.len < plan.head.len && all > kWaveSlots) l.tail_pairs = (rest + wpp - 1) / wpp;
+    plan.head_pairs = (uint32_t)(l.pairs - l.tail_pairs);
+    plan.head_units = plan.head_pairs * plan.head.units_per_pair;
+    l.units = (int64_t)plan.head_units + l.tail_pairs * plan.tail.units_per_pair;
+    l.wgs = (l.units + kColsThreads - 1) / kColsThreads;
+    return l;
+}
 
 }  // namespace aof

@@ -26,47 +26,25 @@ int launch_search_lane8_cols(const SearchArgs &a, void *stream, PruneReport *rep
     if (report) report->expected = 0;
     if (a.n_pairs == 0) return 0;
     if (!lane8_cols_supported(a) || (a.subpixel && !a.subdirs)) return (int)hipErrorInvalidValue;
-    auto segments = [&](int len) {
-        ColsSegments g;
-        g.len = len > a.grid.ny ? a.grid.ny : len;
-        g.segs = (a.grid.ny + g.len - 1) / g.len;
-        g.units_per_pair = (uint32_t)((g.segs * a.grid.nx + 63) / 64 * 64);
-        g.div_units = fastdiv_make(g.units_per_pair);
-        return g;
-    };
-    auto waves = [&](int len) { return a.n_pairs * (int64_t)(segments(len).units_per_pair / 64); };
-    int len = kColsMaxRows;
-    while (len > kColsMinRows && waves(len) < kColsWavesWanted) len--;
-    ColsPlan plan;
-    plan.head = segments(len);
-    plan.tail = segments(len / 2 < kColsMinRows ? kColsMinRows : len / 2);
-    plan.div_nx = fastdiv_make((uint32_t)a.grid.nx);
-    // (columns eight bytes apart: every lane of a pair is misaligned alike and finds its last bytes in the next column's load)
-    plan.aligned = (a.grid.step_x == 8 && a.w % 4 == 0 && a.pair_stride % 4 == 0 && reinterpret_cast<uintptr_t>(a.cur) % 4 == 0 &&
-                    ((int64_t)a.w * a.h) % 4 == 0) ? 1u : 0u;
-    const int64_t per = 0x7FFF0000ll / plan.tail.units_per_pair;   // pairs per launch: units are indexed with 31 bits
+    const int64_t per = cols_plan_make(a.grid, a.w, a.h, a.pair_stride, reinterpret_cast<uintptr_t>(a.cur), a.n_pairs).per;
     for (int64_t done = 0; done < a.n_pairs; done += per) {
+        // (segments, short segments for the pairs behind the last full generation of waves, alignment: aof_cols8_plan.hpp)
+        const ColsLaunch l = cols_plan_make(a.grid, a.w, a.h, a.pair_stride, reinterpret_cast<uintptr_t>(a.cur), a.n_pairs, done);
+        const ColsPlan &plan = l.plan;
         SearchArgs s = a;
-        s.n_pairs = a.n_pairs - done < per ? a.n_pairs - done : per;
+        s.n_pairs = l.pairs;
         s.prev += done * a.pair_stride;
         s.cur += done * a.pair_stride;
         s.blocks += done * a.grid.blocks();
         if (s.subdirs) s.subdirs += done * a.grid.blocks();
         if (s.pred) s.pred += done;
         if (s.sums) s.sums += done * 4;
-        // pairs beyond the last full generation of wave slots (256 CUs x 16 waves) get the short segments
-        const int64_t wpp = plan.head.units_per_pair / 64, all = s.n_pairs * wpp, rest = all % kWaveSlots;
-        int64_t tail_pairs = 0;
-        if (rest != 0 && rest * 5 < kWaveSlots * 4 && plan.tail.len < plan.head.len && all > kWaveSlots) tail_pairs = (rest + wpp - 1) / wpp;
-        plan.head_pairs = (uint32_t)(s.n_pairs - tail_pairs);
-        plan.head_units = plan.head_pairs * plan.head.units_per_pair;
-        const int64_t units = (int64_t)plan.head_units + tail_pairs * plan.tail.units_per_pair;
         // a launch of one or two generations of waves ends sooner with one-wave workgroups, whose slots free up wave by
         // wave for the other batch in flight (as flat_threads does for the exhaustive kernel, k_search_lane8.hip)
         // (one-wave workgroups for launches of one or two generations of waves, as the exhaustive kernel has them, measure
         //  the same within the spread of 200-step runs: profiles/r05_small_launch_shape.txt)
         const int threads = kColsThreads;
-        const int64_t wgs = (units + threads - 1) / threads;
+        const int64_t wgs = l.wgs;
         PruneReport rep = {nullptr, 0, 1, 0};
         if (report && report->slots && done == 0) {
             rep = *report;

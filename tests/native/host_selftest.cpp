@@ -2,7 +2,9 @@
 // strip plans, workspace layout (aof_params.cpp) and the OPTICAL_FLOW_RAD packer; and of the rules the host shares
 // with the kernels, compiled for the host: the kernels' own packer (aof_mavlink.hpp) against the facade's, the two
 // forms of the checksum step against each other, the exposure bin and mean sample value (aof_exposure_step.hpp)
-// against the public functions.
+// against the public functions; the column walk's segment plan (aof_cols8_plan.hpp: cols_plan_make) on the cases of
+// tests/cols_plan_ref.py, printed field by field for tests/test_host_asan.py to hold to the Python model; and
+// fastdiv_make against the division it replaces, with the kernels' fast_div restated in 32-bit arithmetic.
 // Built with -fsanitize=address,undefined by tests/test_host_asan.py.
 #include <cmath>
 #include <cstdio>
@@ -10,6 +12,7 @@
 #include <cstring>
 
 #include "aof.h"
+#include "aof_cols8_plan.hpp"
 #include "aof_exposure_step.hpp"
 #include "aof_internal.hpp"
 #include "aof_mavlink.hpp"
@@ -127,7 +130,73 @@ static int check_exposure()
     return hists;
 }
 
-int main()
+// (d) cols_plan_make on the case file of tests/test_host_asan.py, one case per line: nx ny step_x w h pair_stride cur n_pairs
+// done.  One line of fields per case, in the order of cols_plan_ref.PLAN_FIELDS.  Returns the cases read, or -1.
+static int print_cols_plans(const char *path)
+{
+    std::FILE *f = std::fopen(path, "r");
+    if (!f) return -1;
+    int cases = 0;
+    long long nx, ny, step_x, w, h, stride, n_pairs, done;
+    unsigned long long cur;
+    while (std::fscanf(f, "%lld %lld %lld %lld %lld %lld %llu %lld %lld", &nx, &ny, &step_x, &w, &h, &stride, &cur, &n_pairs, &done) == 9) {
+        aof::Grid g = {4, 4, (int32_t)step_x, 8, (int32_t)nx, (int32_t)ny};
+        const aof::ColsLaunch l = aof::cols_plan_make(g, (int)w, (int)h, (int64_t)stride, (uintptr_t)cur, (int64_t)n_pairs, (int64_t)done);
+        const aof::ColsSegments *cls[2] = {&l.plan.head, &l.plan.tail};
+        std::printf("cols plan:");
+        for (const aof::ColsSegments *s : cls) std::printf(" %d %d %u %u %u", s->len, s->segs, s->units_per_pair, s->div_units.mul, s->div_units.shift);
+        std::printf(" %u %u %u %u %u %lld %lld %lld %lld %lld\n", l.plan.head_pairs, l.plan.head_units, l.plan.div_nx.mul, l.plan.div_nx.shift,
+                    l.plan.aligned, (long long)l.per, (long long)l.pairs, (long long)l.tail_pairs, (long long)l.units, (long long)l.wgs);
+        cases++;
+    }
+    std::fclose(f);
+    return cases;
+}
+
+// (e) fastdiv_make: the kernels' fast_div (aof_device.hpp) restated -- the high half of the product, the sum and the shift
+// in 32 bits -- against n / d.  Divisors: every d up to 4096 (grid widths, blocks per pair) and every multiple of 64 up to
+// 2^20 (units per pair); numerators: all below 2^16, and around 65 multiples of d spread up to the top of the 31 bits
+// the launchers keep to.  Returns the numerators per divisor beyond the first 2^16, or -1.
+static uint32_t fast_div_host(uint32_t n, aof::FastDiv d) { return ((uint32_t)(((uint64_t)n * d.mul) >> 32) + n) >> d.shift; }
+
+static int check_fastdiv(int *divisors)
+{
+    int extra = 0;
+    *divisors = 0;
+    for (uint32_t i = 1; i <= 4096u + (1u << 20) / 64u; i++) {
+        const uint32_t d = i <= 4096u ? i : (i - 4096u) * 64u;
+        if (i > 4096u && d <= 4096u) continue;   // (already seen)
+        const aof::FastDiv fd = aof::fastdiv_make(d);
+        if (fd.shift > 31u) return -1;
+        uint32_t q = 0, r = 0;
+        for (uint32_t n = 0; n < 65536u; n++) {
+            if (fast_div_host(n, fd) != q) return -1;
+            if (++r == d) { r = 0; q++; }
+        }
+        const uint32_t top = 0x7FFFFFFFu / d;
+        int count = 0;
+        for (uint32_t step = 0; step <= 64u; step++) {
+            const uint32_t k = (uint32_t)((uint64_t)top * step / 64u);
+            const uint64_t around[3] = {(uint64_t)k * d - 1u, (uint64_t)k * d, (uint64_t)k * d + 1u};
+            for (uint64_t n : around) {
+                if (n > 0x7FFFFFFFull) continue;   // (k = 0: -1 wraps; the top multiple + 1 may pass 2^31)
+                if (fast_div_host((uint32_t)n, fd) != (uint32_t)(n / d)) return -1;
+                count++;
+            }
+        }
+        const uint32_t ends[2] = {0x7FFEFFFFu, 0x7FFFFFFFu};
+        for (uint32_t n : ends) {
+            if (fast_div_host(n, fd) != n / d) return -1;
+            count++;
+        }
+        if (count < 190) return -1;
+        extra = count > extra ? count : extra;
+        (*divisors)++;
+    }
+    return extra;
+}
+
+int main(int argc, char **argv)
 {
     int bad = 0, valid = 0;
     for (int it = 0; it < 20000; it++) {
@@ -179,6 +248,16 @@ int main()
     const int hists = check_exposure();
     if (hists < 0) return 14;
     std::printf("host selftest: exposure: 256 bins and %d mean sample values equal to the public functions\n", hists);
+    int divisors = 0;
+    const int numerators = check_fastdiv(&divisors);
+    if (numerators < 0) return 15;
+    std::printf("host selftest: fast_div: %d divisors, all numerators below 65536 and up to %d around multiples up to 2^31 equal to n / d\n",
+                divisors, numerators);
+    if (argc > 1) {
+        const int plans = print_cols_plans(argv[1]);
+        if (plans < 0) return 16;
+        std::printf("host selftest: cols plan: %d cases\n", plans);
+    }
     std::printf("host selftest: %d valid parameter sets, %d rejected\n", valid, bad);
     return valid > 1000 ? 0 : 11;
 }

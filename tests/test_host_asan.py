@@ -1,9 +1,13 @@
 """ASan + UBSan over the product's host-only logic (parameter validation, grids, reduction chunks,
 workspace layout, MAVLink packer), 20 000 random parameter sets including invalid ones; and over the rules the host
 shares with the kernels (csrc/aof_mavlink.hpp, csrc/aof_exposure_step.hpp) compiled for the host: the kernels' packer
-against the facade's, the two checksum steps on every input, the exposure bin and mean sample value."""
+against the facade's, the two checksum steps on every input, the exposure bin and mean sample value; the column walk's
+segment plan (csrc/aof_cols8_plan.hpp: cols_plan_make) on every case of tests/cols_plan_ref.py, field by field against
+the Python model; fastdiv_make against the division it replaces."""
 import os
 import subprocess
+
+import cols_plan_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -17,9 +21,22 @@ def test_host_logic_is_clean_under_asan_ubsan(tmp_path):
            os.path.join(ROOT, "tests", "native", "host_selftest.cpp"), os.path.join(pkg, "csrc", "aof_params.cpp"),
            os.path.join(pkg, "facade", "src", "optical_flow_rad.cpp"), "-o", str(exe)]
     subprocess.run(cmd, check=True, timeout=300)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    cases = ref.CPU_CASES + ref.GPU_CASES + ref.PLAN_ONLY
+    listing = tmp_path / "cols_plan_cases.txt"
+    listing.write_text("".join(ref.selftest_line(c) + "\n" for c in cases))
+    r = subprocess.run([str(exe), str(listing)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, f"rc={r.returncode}\n{r.stdout}{r.stderr}"
     assert "valid parameter sets" in r.stdout
     assert "packer: 4012 frames equal to the facade's, lengths 52 and 56" in r.stdout
     assert "checksum: both steps and the facade's agree on 65536 x 256 inputs" in r.stdout
     assert "exposure: 256 bins and 2002 mean sample values equal to the public functions" in r.stdout
+    assert "fast_div: 20416 divisors, all numerators below 65536 and up to 196 around multiples up to 2^31 equal to n / d" in r.stdout
+    # cols_plan_make == the model, on every case of every list
+    assert f"cols plan: {len(cases)} cases" in r.stdout and len(cases) >= 60
+    plans = [line.split()[2:] for line in r.stdout.splitlines() if line.startswith("cols plan: ")]
+    assert len(plans) == len(cases)
+    for c, got in zip(cases, plans):
+        want = ref.plan_fields(ref.plan_of(c))
+        assert len(got) == len(want) == len(ref.PLAN_FIELDS)
+        diff = {name: (int(g), w) for name, g, w in zip(ref.PLAN_FIELDS, got, want) if int(g) != w}
+        assert not diff, (c["id"], diff)
