@@ -1,10 +1,10 @@
 """Inputs and the expected outputs of the stream bank tests (tests/test_gpu_bank.py): S independent live streams over T
 ticks, and for each stream what the reference's per-frame loop (mainloop.cpp:322-373) around a calcFlow implementation
 leaves for every frame it is given -- the CPU oracle's calcFlow chain with the independent serializer of
-tests/test_mavlink.py, or the C++ facade with its own packer.  Nothing here touches the GPU."""
+tests/mavlink_model.py, or the C++ facade with its own packer.  Nothing here touches the GPU."""
 import numpy as np
 
-from test_mavlink import py_frame
+from mavlink_model import py_frame
 
 FX, FY = 216.6677, 216.2457
 TICK_HELD, TICK_IDLE = -1, -2

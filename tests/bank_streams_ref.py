@@ -1,15 +1,14 @@
 """Inputs and expected outputs of the per-stream bank tests (tests/test_gpu_bank_streams.py): a bank whose S streams are
 S different cameras -- own focal lengths, output rate, vehicle-time offset and MAVLink identity (aof_bank_stream,
 include/aof.h).  The expected values are bank_ref's: one oracle chain per stream, built with that stream's values, and a
-packer that writes the stream's system and component id into the frame header.  Nothing here touches the GPU."""
-import struct
+packer that writes the stream's system and component id into the frame header (tests/mavlink_model.py).  Nothing here touches the GPU."""
 from functools import partial
 
 import numpy as np
 
 import bank_ref as ref
 from bank_ref import FX, FY
-from test_mavlink import x25
+from mavlink_model import py_frame_id
 
 # focal_x, focal_y, output_rate, offset_timestamp_usec, system_id, component_id, first_seq.  Stream 1: a sequence number
 # that wraps, an offset beyond 32 bits; 2: no limiter; 3: offset 0, no frame is ever sent; 4: focal lengths below the
@@ -38,18 +37,6 @@ def records(aof, S, rows=None):
         fx, fy, rate, offset, sysid, compid, seq = rows[s] if rows is not None else row(s)
         out[s] = (fx, fy, rate, sysid, compid, seq, 0, offset, 0)
     return out
-
-
-def py_frame_id(offset_ts, img_time_us, dt_us, fx, fy, gyro, quality, seq, system_id=1, component_id=100):
-    """tests/test_mavlink.py's independent serializer with the sender's identity in the header."""
-    payload = struct.pack("<QIfffffIfhBB", offset_ts + img_time_us, dt_us & 0xFFFFFFFF, fx, fy,
-                          np.float32(-gyro[1]), np.float32(gyro[0]), np.float32(gyro[2]), 0, -1.0, 0, 0, quality & 0xFF)
-    assert len(payload) == 44
-    while len(payload) > 1 and payload[-1] == 0:
-        payload = payload[:-1]
-    hdr = bytes([len(payload), 0, 0, seq, system_id, component_id, 106, 0, 0])
-    crc = x25(bytes([138]), x25(hdr + payload))
-    return b"\xfd" + hdr + payload + struct.pack("<H", crc)
 
 
 def chain(aof, orc, p, r, use_gyro=True):

@@ -11,6 +11,8 @@ import struct
 
 import numpy as np
 
+from mavlink_model import x25
+
 SLOTS_MAX, BURST_MAX, FRAME_BYTES = 16, 16, 56
 HELD, IDLE, STALE_GYRO, NO_OFFSET = -1, -2, -3, -4
 SENTINEL = 0xA5                      # fill of frame bytes nobody may write
@@ -33,15 +35,6 @@ OUTCOMES = ("accepted", "rejected_prev_zero", "rejected_dt", "rejected_rate", "d
             "stale_no_sample_between_takes", "sent_after_stale", "no_offset", "sent", "sent_first_frame", "held", "idle",
             "seq_wrapped", "count_zero", "count_full", "count_above_max", "idle_round_with_samples")
 BELOW_20 = float(np.nextafter(np.float32(20), np.float32(0)))
-
-
-def x25(data, crc=0xFFFF):
-    """CRC-16/MCRF4XX, as MAVLink accumulates it."""
-    for b in data:
-        tmp = (b ^ (crc & 0xFF)) & 0xFF
-        tmp = (tmp ^ (tmp << 4)) & 0xFF
-        crc = ((crc >> 8) ^ (tmp << 8) ^ (tmp << 3) ^ (tmp >> 4)) & 0xFFFF
-    return crc
 
 
 def frame(time_usec, dt_us, flow_x, flow_y, g, quality, seq, system_id, component_id):

@@ -6,6 +6,8 @@ import struct
 
 import numpy as np
 
+from mavlink_model import x25
+
 HIGHRES_IMU, HIGHRES_IMU_EXTRA = 105, 93
 PIECE = 128          # what the kernel stages per stream at a time: lengths around its multiples are edges
 SENTINEL = 0xA5
@@ -18,15 +20,6 @@ assert SAMPLE_DTYPE.itemsize == 24 and PUBLIC_DTYPE.itemsize == 32 and STATE_DTY
 COUNTERS = PUBLIC_DTYPE.names
 
 
-def crc_x25(data, crc=0xFFFF):
-    """MAVLink's checksum (crc_accumulate over `data`); 0x6F91 on b"123456789"."""
-    for b in bytes(data):
-        tmp = (b ^ crc) & 0xFF
-        tmp = (tmp ^ (tmp << 4)) & 0xFF
-        crc = ((crc >> 8) ^ (tmp << 8) ^ (tmp << 3) ^ (tmp >> 4)) & 0xFFFF
-    return crc
-
-
 # ---- generators ----------------------------------------------------------------------------------------------------
 def imu_payload(t, x, y, z, rest=0.0, ext=None):
     """HIGHRES_IMU's 62 bytes (63 with the `id` extension): time, acc x/y/z, gyro x/y/z, mag x/y/z, abs and diff
@@ -37,7 +30,7 @@ def imu_payload(t, x, y, z, rest=0.0, ext=None):
 
 def frame_v1(msgid, payload, seq=0, sysid=1, compid=1, extra=HIGHRES_IMU_EXTRA, bad=False):
     body = bytes([len(payload), seq, sysid, compid, msgid]) + bytes(payload)
-    crc = crc_x25(body + bytes([extra])) ^ (0x0100 if bad else 0)
+    crc = x25(body + bytes([extra])) ^ (0x0100 if bad else 0)
     return b"\xfe" + body + bytes([crc & 0xFF, crc >> 8])
 
 
@@ -52,7 +45,7 @@ def frame_v2(msgid, payload, seq=0, sysid=1, compid=1, extra=HIGHRES_IMU_EXTRA, 
     if signature is not None:
         incompat |= 1
     body = bytes([len(payload), incompat, compat, seq, sysid, compid, msgid & 0xFF, (msgid >> 8) & 0xFF, msgid >> 16]) + payload
-    crc = crc_x25(body + bytes([extra])) ^ (0x0001 if bad else 0)
+    crc = x25(body + bytes([extra])) ^ (0x0001 if bad else 0)
     out = b"\xfd" + body + bytes([crc & 0xFF, crc >> 8])
     return out + (bytes(signature) if signature is not None else b"")
 
@@ -136,7 +129,7 @@ class Parser:
             if self.msgid != HIGHRES_IMU:
                 self.events.add("other message")
                 continue
-            crc = crc_x25(bytes(self.head) + bytes(self.payload) + bytes([HIGHRES_IMU_EXTRA]))
+            crc = x25(bytes(self.head) + bytes(self.payload) + bytes([HIGHRES_IMU_EXTRA]))
             if [crc & 0xFF, crc >> 8] != self.check:
                 self.c["bad_check"] += 1
                 self.events.add("bad check")

@@ -8,6 +8,15 @@ import numpy as np
 SKIPPED = 0xFFFF
 
 
+def ulp_distance(a, b):
+    """Float32 values between a and b on the ordered number line (+0 and -0 coincide)."""
+    ia = np.float32(a).view(np.int32).astype(np.int64)
+    ib = np.float32(b).view(np.int32).astype(np.int64)
+    ia = np.where(ia < 0, np.int64(-2 ** 31) - ia, ia)
+    ib = np.where(ib < 0, np.int64(-2 ** 31) - ib, ib)
+    return int(abs(int(ia) - int(ib)))
+
+
 def grid(p, level):
     w, h = p["width"] >> level, p["height"] >> level
     B, S = p["tile"], p["search"]

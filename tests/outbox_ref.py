@@ -3,6 +3,8 @@ leave, byte for byte, written in plain numpy from the header's rules -- independ
 here touches the GPU."""
 import numpy as np
 
+from bank_rig import OFFSET
+
 FILL = 0xEE
 FRAME = 56
 HEADER, ENTRY, EXPOSURE_ENTRY = 64, 128, 64
@@ -88,7 +90,6 @@ def compact(records, mavlink, lengths, exposure, derotated, cap_m, cap_e, tag=1,
 RECIPE = dict(w=64, h=64, S=37, T=24, case_seed=11, wrap=True)
 CENSUS_15HZ = [8, 9, 9, 9, 2, 3, 9, 9, 11, 5, 0, 1, 11, 7, 7, 7, 3, 2, 5, 6, 9, 5, 6, 4]
 PUBLISHED_15HZ, PUBLISHED_RATE0, RECORDS = 147, 668, 888
-OFFSET = 5_000_000
 
 
 def recipe_run(aof, orc, synth, rate=15, offset=OFFSET):

@@ -9,10 +9,12 @@ from collections import Counter
 import numpy as np
 
 import bank_ref as ref
+from bank_rig import OFFSET, params_of
+from mavlink_model import py_frame
+from sequence_ref import crop_of, replay
 
 TAN_PI_8 = 0.41421356237309504880            # aof_math.h's constant: the same double
 CLASSES = ("direct", "reduced", "equal", "swapped_reduced", "swapped_direct")
-OFFSET = 5_000_000
 K_BURST = 5
 
 
@@ -65,14 +67,6 @@ CASES = [
 ]
 BY_ID = {c["id"]: c for c in CASES}
 LONG_WINDOW = 75            # summed frames behind a slow-rate publication
-
-
-def params_of(aof, cfg):
-    if cfg == "px4-64":
-        return aof.px4flow_params(64, 64)
-    if cfg == "opencv-128":      # two levels + equalisation: what OpticalFlowOpenCV's constructor selects at this size
-        return aof.px4flow_params(128, 128, pyramid_levels=2, mean_subtract=1)
-    raise KeyError(cfg)
 
 
 def sensor_of(cfg):
@@ -211,11 +205,9 @@ _cache = {}
 
 def oracle_of_sequence(aof, orc, synth, case):
     """The sequence pipeline's recording of a case and what the oracle chain leaves of it, made once: dict(frames, times,
-    gyro, cropped, recs, wire, counts, sums) -- recs and wire as test_gpu_sequence.replay returns them."""
+    gyro, cropped, recs, wire, counts, sums) -- recs and wire as sequence_ref.replay returns them."""
     key = ("sequence", case["id"])
     if key not in _cache:
-        from test_gpu_sequence import crop_of, replay
-        from test_mavlink import py_frame
         p = params_of(aof, case["cfg"])
         frames, times, gyro = sequence_inputs(synth, aof, case)
         cropped = crop_of(frames, p.width, p.height)

@@ -1,153 +1,20 @@
 """The stream bank (aof_bank_push_device / aof_bank_reset_device, include/aof.h): S live streams per tick from one
 device launch, against what the reference's per-frame loop leaves for each stream on its own -- the CPU oracle's
 calcFlow chain, one orc.Px4 per stream fed only that stream's active frames, with the independent MAVLink serializer of
-tests/test_mavlink.py; for streams 0..5 also the C++ facade driven frame by frame with its own packer.  Every record of
-every tick and every wire frame is compared by bytes, never by tolerance.  Inputs: tests/bank_ref.py."""
+tests/mavlink_model.py; for streams 0..5 also the C++ facade driven frame by frame with its own packer.  Every record of
+every tick and every wire frame is compared by bytes, never by tolerance.  Inputs: tests/bank_ref.py; the rig: tests/bank_rig.py."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import bank_ref as ref
+from bank_cases import run_case
 from bank_ref import FX, FY
+from bank_rig import EINVAL, ENOSPC, LIMITED, OFFSET, BankRig, params_of, same_records
+from bank_rig import time_limit   # (this module's fixture too: every test under a limit of its own)
 
 pytestmark = pytest.mark.gpu
-
-OFFSET = 5_000_000
-EINVAL, ENOSPC = -22, -28
-
-
-def params_of(aof, cfg):
-    if cfg == "px4-64":          # OpticalFlowPX4 at its default size
-        return aof.px4flow_params(64, 64)
-    if cfg == "opencv-128":      # what OpticalFlowOpenCV's constructor selects: two levels + equalisation
-        return aof.px4flow_params(128, 128, pyramid_levels=2, mean_subtract=1)
-    if cfg == "px4-96x80":
-        return aof.px4flow_params(96, 80)
-    if cfg == "px4-96x80-2":
-        return aof.px4flow_params(96, 80, pyramid_levels=2, mean_subtract=1)
-    if cfg == "opencv-64":
-        return aof.px4flow_params(64, 64, pyramid_levels=2, mean_subtract=1)
-    if cfg == "px4-128":
-        return aof.px4flow_params(128, 128)
-    if cfg == "dense-192x160":   # 22 x 18 = 396 blocks: outside the one-workgroup class
-        return aof.default_params(192, 160, subpixel=1)
-    if cfg == "tile16-160x128":  # 16x16 tiles, +-8 (the thresholds smoke() uses)
-        return aof.default_params(160, 128, tile=16, search=8, value_threshold=12000, min_valid=0)
-    raise KeyError(cfg)
-
-
-class Device:
-    """One bank and its tick buffers on the device; push(k) runs tick k of a Run and returns host copies."""
-
-    def __init__(self, aof, eng, run, bp, gpu_device, use_gyro=True, mavlink=True):
-        import torch
-        self.aof, self.eng, self.run, self.torch = aof, eng, run, torch
-        self.bank = eng.bank_create(bp, gpu_device)
-        S = run.S
-        self.pixels = run.frames.shape[2] * run.frames.shape[3]
-        self.frames = torch.zeros((S, bp.frame_stride or self.pixels), dtype=torch.uint8, device=gpu_device)   # stream s at s * frame_stride
-        self.times = torch.zeros(S, dtype=torch.int64, device=gpu_device)
-        self.active = torch.zeros(S, dtype=torch.uint8, device=gpu_device)
-        self.gyro = torch.zeros((S, 4), dtype=torch.float32, device=gpu_device) if use_gyro else None
-        self.records = torch.zeros((S, 48), dtype=torch.uint8, device=gpu_device)
-        self.wire = torch.zeros((S, 56), dtype=torch.uint8, device=gpu_device) if mavlink else None
-        self.lens = torch.zeros(S, dtype=torch.uint8, device=gpu_device) if mavlink else None
-
-    def load(self, k):
-        t, run = self.torch, self.run
-        self.frames[:, :self.pixels].copy_(t.from_numpy(run.frames[k].reshape(run.S, -1)))
-        self.times.copy_(t.from_numpy(run.times[k]))
-        self.active.copy_(t.from_numpy(run.active[k]))
-        if self.gyro is not None:
-            self.gyro.copy_(t.from_numpy(run.gyro[k]))
-        self.records.fill_(0xEE)              # (every record of the tick must be written)
-        if self.wire is not None:
-            self.wire.zero_()
-            self.lens.fill_(0xEE)
-
-    def enqueue(self):
-        self.eng.bank_push(self.bank, self.frames, self.times, self.active, self.gyro,
-                           mavlink=self.wire is not None, records=self.records, out_frames=self.wire, out_lengths=self.lens)
-
-    def read(self):
-        self.torch.cuda.synchronize()
-        recs = self.aof.ticks_view(self.records)
-        if self.wire is None:
-            return recs, None
-        w, n = self.wire.cpu().numpy(), self.lens.cpu().numpy()
-        return recs, [bytes(w[s, :n[s]]) for s in range(len(n))]
-
-    def push(self, k):
-        self.load(k)
-        self.enqueue()
-        return self.read()
-
-
-def same_records(got, want, tick, what, pixel=True):
-    if pixel:
-        if got.tobytes() == want.tobytes():
-            return
-        names = got.dtype.names
-    else:
-        names = [n for n in got.dtype.names if n != "pixel"]
-        if all(got[n].tobytes() == want[n].tobytes() for n in names):
-            return
-    for s in range(len(got)):
-        for n in names:
-            assert got[s][n].tobytes() == want[s][n].tobytes(), (what, "tick", tick, "stream", s, n, got[s], want[s])
-
-
-def run_case(aof, orc, synth, gpu_device, cfg, S, T, seed, rate=15, offset=OFFSET, first_seq=0, wrap=False, use_gyro=True,
-             path=0, facade=0, density=None, census=None, frame_stride=0, fx=FX, fy=FY, source=None):
-    """One bank over one Run against the oracle chain (all streams) and the facade (streams < facade); returns the
-    oracle's records.  fx, fy: the focal lengths of the bank, the chains and the facade objects; source: bank_ref.make_run's
-    per-stream sequence source."""
-    p = params_of(aof, cfg)
-    run = ref.make_run(synth, p.width, p.height, S, T, seed, wrap=wrap, density=density, source=source)
-    want, wire = ref.expected(run, [ref.oracle_chain(aof, orc, p, rate, offset, first_seq, use_gyro, fx=fx, fy=fy) for _ in range(S)])
-    pub, held, idle = ref.census(want)
-    if census is not None:          # a condition on the INPUT: a bank that never holds or never publishes cannot pass
-        assert pub.min() >= census[0] and held.min() >= census[1] and idle.min() >= census[2], (pub, held, idle)
-    eng = aof.FlowEngine(p, 0)
-    eng.set_bank_path(path)
-    bp = aof.bank_params(S, fx, fy, rate, offset, 1, 100, first_seq, frame_stride)
-    dev = Device(aof, eng, run, bp, gpu_device, use_gyro=use_gyro)
-    stride = frame_stride or p.width * p.height
-    facs = []
-    for s in range(min(facade, S)):
-        f = aof.OpticalFlowPX4(fx, fy, rate, p.width, p.height) if p.pyramid_levels == 1 else aof.OpticalFlowOpenCV(fx, fy, rate, p.width, p.height)
-        assert f.getPyramidLevels() == p.pyramid_levels
-        facs.append(f)
-    chains_f = [ref.Chain(aof.TICK_DTYPE, f.calcFlow, aof.pack_optical_flow_rad, offset, first_seq, use_gyro=use_gyro) for f in facs]
-    for k in range(T):
-        before_frames, before_state = dev.bank.frames_bytes(), dev.bank.state_bytes()
-        got, sent = dev.push(k)
-        same_records(got, want[k], k, "oracle")
-        assert sent == wire[k], ("oracle wire", k, [s for s in range(S) if sent[s] != wire[k][s]][:4])
-        if offset == 0:
-            assert all(len(f) == 0 for f in sent)
-        for s, ch in enumerate(chains_f):
-            if run.active[k, s]:
-                r, w = ch.push(run.frames[k, s], run.times[k, s], run.gyro[k, s])
-                same_records(got[s:s + 1], np.array([r]), k, f"facade stream {s}", pixel=False)
-                assert sent[s] == w, ("facade wire", k, s)
-        # idle streams: nothing about them changed; active streams: the bank holds their new frame
-        after_frames, after_state = dev.bank.frames_bytes(), dev.bank.state_bytes()
-        for s in range(S):
-            slot = slice(s * stride, s * stride + p.width * p.height)
-            if run.active[k, s]:
-                assert after_frames[slot].tobytes() == run.frames[k, s].tobytes(), ("stored frame", k, s)
-            else:
-                assert after_frames[slot].tobytes() == before_frames[slot].tobytes(), ("idle frame", k, s)
-                assert after_state[s].tobytes() == before_state[s].tobytes(), ("idle state", k, s)
-    for f in facs:
-        f.close()
-    eng.close()
-    return want
-
-
-LIMITED = (3, 10, 5)   # per stream, 48 ticks at a limited rate: >= 3 published, >= 10 held, >= 5 idle
 
 PARITY = [
     dict(id="px4-64-15Hz", cfg="px4-64", S=24, T=48, seed=1, census=LIMITED, facade=6),
@@ -193,10 +60,10 @@ def test_both_paths_leave_identical_bytes_after_every_tick(aof, synth, gpu_devic
         eng = aof.FlowEngine(p, 0)
         eng.set_bank_path(path)
         engs.append(eng)
-        devs.append(Device(aof, eng, run, bp, gpu_device))
+        devs.append(BankRig(aof, eng, run, bp, gpu_device))
     held = published = 0
     for k in range(T):
-        (ra, wa), (rb, wb) = devs[0].push(k), devs[1].push(k)
+        (ra, wa, _, _), (rb, wb, _, _) = devs[0].push(k), devs[1].push(k)
         assert ra.tobytes() == rb.tobytes(), k
         assert wa == wb, k
         assert devs[0].bank.frames_bytes().tobytes() == devs[1].bank.frames_bytes().tobytes(), k
@@ -227,14 +94,14 @@ def test_reset_with_a_mask_mid_run(aof, orc, synth, gpu_device):
     for path in (1, 2):
         eng = aof.FlowEngine(p, 0)
         eng.set_bank_path(path)
-        dev = Device(aof, eng, run, aof.bank_params(S, FX, FY, 15, OFFSET, 1, 100, first_seq), gpu_device)
+        dev = BankRig(aof, eng, run, aof.bank_params(S, FX, FY, 15, OFFSET, 1, 100, first_seq), gpu_device)
         for k in range(T):
             if k == 20:
                 before = dev.bank.state_bytes()
                 eng.bank_reset(dev.bank, torch.from_numpy(mask).to(gpu_device))
                 after = dev.bank.state_bytes()
                 assert not after[mask == 1].any() and after[mask == 0].tobytes() == before[mask == 0].tobytes()
-            got, sent = dev.push(k)
+            got, sent, _, _ = dev.push(k)
             same_records(got, want[k], k, f"path {path}")
             assert sent == wire[k], (path, k)
         # the masked streams' first frame after the reset is a first frame again
@@ -254,9 +121,9 @@ def test_a_captured_tick_replays_on_new_inputs(aof, synth, gpu_device, path):
     bp = aof.bank_params(S, FX, FY, 15, OFFSET, 1, 100, 0)
     eng = aof.FlowEngine(p, 0)
     eng.set_bank_path(path)
-    eager = Device(aof, eng, run, bp, gpu_device)
+    eager = BankRig(aof, eng, run, bp, gpu_device)
     outs = [eager.push(k) for k in range(T)]
-    dev = Device(aof, eng, run, bp, gpu_device)
+    dev = BankRig(aof, eng, run, bp, gpu_device)
     dev.push(0)                                  # (every kernel of the tick has run once before the capture)
     eng.bank_reset(dev.bank)
     torch.cuda.synchronize()
@@ -266,12 +133,12 @@ def test_a_captured_tick_replays_on_new_inputs(aof, synth, gpu_device, path):
     for k in range(T):
         dev.load(k)
         g.replay()
-        recs, sent = dev.read()
-        assert recs.tobytes() == outs[k][0].tobytes(), k
-        assert sent == outs[k][1], k
+        got = dev.read()
+        assert got.recs.tobytes() == outs[k].recs.tobytes(), k
+        assert got.wire == outs[k].wire, k
     assert dev.bank.frames_bytes().tobytes() == eager.bank.frames_bytes().tobytes()
     assert dev.bank.state_bytes().tobytes() == eager.bank.state_bytes().tobytes()
-    q = np.stack([o[0]["quality"] for o in outs])
+    q = np.stack([o.recs["quality"] for o in outs])
     assert (q == aof.TICK_HELD).any() and (q == aof.TICK_IDLE).any() and (q[4:] >= 0).any()
     eng.close()
 

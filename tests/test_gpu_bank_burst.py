@@ -4,7 +4,8 @@ bank -- call k with round k's buffers and d_active[s] = (k < count[s]) -- and wh
 leaves (tests/bank_ref.py, tests/bank_camera_ref.py driven round by round with the same activity rule), so that the
 feature is not held to the library's own tick alone.  Every case first asserts, on the oracle chain and before the
 device is compared, that its input meets the situations it is there for (census()).  Every comparison is on raw
-bytes; every output buffer is pre-filled with 0xEE (wire frames with 0)."""
+bytes; every output buffer is pre-filled with 0xEE (wire frames with 0).  The rig: tests/bank_rig.py; the cases:
+tests/bank_cases.py."""
 import ctypes as C
 
 import numpy as np
@@ -12,274 +13,12 @@ import pytest
 
 import bank_camera_ref as cref
 import bank_ref as ref
+from bank_cases import Case
 from bank_ref import FX, FY
-from test_gpu_bank import OFFSET, Device, params_of, same_records
-from test_gpu_bank_camera import SENSOR, CamDevice, same_exposure, untouched
+from bank_rig import EINVAL, EIO, ENOSPC, OFFSET, BankRig, params_of, untouched
+from bank_rig import time_limit   # (this module's fixture too: every test under a limit of its own)
 
 pytestmark = pytest.mark.gpu
-
-EINVAL, ENOSPC, EIO = -22, -28, -5
-
-
-def params_for(aof, cfg, overrides=None):
-    p = params_of(aof, cfg)
-    for k, v in (overrides or {}).items():
-        setattr(p, k, int(v))
-    return p
-
-
-def make_burst_run(synth, w, h, S, K, B, seed, wrap=False):
-    """B bursts of K rounds as a bank_ref.Run of T = B*K ticks (tick j*K + k is round k of burst j), with bank_ref's
-    recipe for the streams (make_sequence per stream, 9 000..18 000 us per active frame, three black frames for streams
-    with s % 5 == 3, the u32 time wrap of every third stream behind its fourth frame) and the activity of a burst:
-    counts [B, S] drawn from 0..K, stream s active in rounds 0..counts[j, s]-1 of burst j.  Stream 0 has all K frames
-    in burst 0 (a first frame with frames behind it), stream 1 % S none in burst 1 % B.  `given` is what the device is
-    told: counts with one value above K (which counts as K).  Entries of idle rounds hold noise."""
-    rng = np.random.default_rng(seed)
-    T = B * K
-    frames = rng.integers(0, 256, (T, S, h, w), dtype=np.uint8)
-    times = rng.integers(0, 1 << 40, (T, S)).astype(np.int64)
-    gyro = rng.normal(0, 1.0, (T, S, 4)).astype(np.float32)
-    active = np.zeros((T, S), np.uint8)
-    counts = rng.integers(0, K + 1, (B, S)).astype(np.uint8)
-    counts[0, 0] = K
-    counts[1 % B, 1 % S] = 0
-    if S == 1:
-        counts[0, 0] = K
-    counts[B - 1, S - 1] = K
-    given = counts.copy()
-    given[B - 1, S - 1] = 200                          # clamped by the kernel: the host cannot see it
-    for s in range(S):
-        seq, _ = synth.make_sequence(w, h, T, 4, seed=1000 * seed + s, max_step=3)
-        if s % 5 == 3:
-            seq[7:10] = 0
-        n, clock = 0, 0
-        for t in range(T):
-            j, k = divmod(t, K)
-            if k >= counts[j, s]:
-                continue
-            clock += int(rng.integers(9000, 18000))
-            if wrap and s % 3 == 0 and n == 3:
-                clock += (1 << 32) - clock - 20000       # the 32-bit time stamp wraps shortly behind this frame
-            active[t, s] = 1
-            frames[t, s] = seq[n]
-            times[t, s] = clock
-            gyro[t, s, :3] = rng.normal(0, 0.004, 3).astype(np.float32)
-            gyro[t, s, 3] = 0.013
-            n += 1
-    return ref.Run(frames, times, gyro, active), counts, given
-
-
-def census(run, counts, K, want, wire, due, rate, first_seq):
-    """Which of the situations a burst has to get right this input shows, on the oracle chain alone."""
-    T, S = run.T, run.S
-    q, frame = want["quality"], want["frame"]
-    out = set()
-    for t in range(T):
-        j, k = divmod(t, K)
-        for s in range(S):
-            c = int(counts[j, s])
-            if k == 0 and c == 0:
-                out.add("count0")
-            if not run.active[t, s]:
-                continue
-            if k == 0 and frame[t, s] == 1 and c >= 2:
-                out.add("first-frame-then-more")
-            if q[t, s] >= 0 and frame[t, s] > 1 and k < c - 1:
-                out.add("publication-before-the-last-round")
-            if q[t, s] == ref.TICK_HELD:
-                out.add("held")
-            if rate > 0 and frame[t, s] > 1 and want[t, s]["pixel"]["quality"] == 0:
-                out.add("zero-quality-frame-skipped")
-            if k >= 1 and (int(run.times[t, s]) >> 32) != (int(run.times[t - 1, s]) >> 32):
-                out.add("u32-wrap-inside-a-burst")
-            if due is not None and k >= 1 and due[t, s] and k < c - 1 and not due[t + 1:j * K + c, s].any():
-                out.add("gate-opens-in-a-later-round-and-stays-shut")
-    for s in range(S):
-        seqs = [w[s][4] for w in wire if w[s]]           # MAVLink 2: the sequence number is byte 4
-        if any(a == 255 and b == 0 for a, b in zip(seqs, seqs[1:])):
-            out.add("sequence-255-to-0")
-    if rate <= 0:
-        out.add("rate0")
-    return out
-
-
-class BurstDevice:
-    """One bank and the buffers of a burst of K rounds on the device.  camera: (aof_bank_camera, CameraRun) for the
-    sensor-frame form.  pad: bytes added to the dense round_stride (0: round_stride is passed as 0)."""
-
-    def __init__(self, aof, eng, run, K, bp, gpu_device, camera=None, use_gyro=True, exposure=True, skew=0, pad=0):
-        import torch
-        self.aof, self.eng, self.run, self.K, self.torch = aof, eng, run, K, torch
-        self.cam, self.cam_run = camera if camera else (None, None)
-        self.bank = eng.bank_create(bp, gpu_device, camera=self.cam)
-        S = run.S
-        self.pixels = run.frames.shape[2] * run.frames.shape[3]
-        if self.cam is None:
-            self.item, self.stride = self.pixels, bp.frame_stride or self.pixels
-        else:
-            self.item = self.cam_run.cam_w * self.cam_run.cam_h
-            self.stride = self.cam.camera_stride or self.item
-        self.round = S * self.stride + pad
-        self.round_stride = self.round if pad else 0
-        self.alloc = torch.zeros(K * self.round + 64, dtype=torch.uint8, device=gpu_device)
-        self.frames = self.alloc[skew:skew + K * self.round]
-        z = lambda *shape, dtype=torch.uint8: torch.zeros(shape, dtype=dtype, device=gpu_device)
-        self.times, self.count = z(K, S, dtype=torch.int64), z(S)
-        self.gyro = z(K, S, 4, dtype=torch.float32) if use_gyro else None
-        self.records, self.wire, self.lens = z(K, S, 48), z(K, S, 56), z(K, S)
-        self.exposure, self.derotated, self.want_exposure = z(K, S, 48), z(K, S, 8), exposure
-
-    def load(self, j, given, sensors=None):
-        t, run, K, S = self.torch, self.run, self.K, self.run.S
-        for k in range(K):
-            tick = j * K + k
-            if self.cam is None:
-                data = run.frames[tick].reshape(S, -1)
-            else:
-                data = (sensors[k] if sensors is not None else self.cam_run.sensor(tick)).reshape(S, -1)
-            dst = self.frames[k * self.round:k * self.round + S * self.stride].view(S, self.stride)
-            dst[:, :self.item].copy_(t.from_numpy(np.ascontiguousarray(data)))
-        self.times.copy_(t.from_numpy(run.times[j * K:(j + 1) * K]))
-        self.count.copy_(t.from_numpy(given[j]))
-        if self.gyro is not None:
-            self.gyro.copy_(t.from_numpy(run.gyro[j * K:(j + 1) * K]))
-        for buf in (self.records, self.lens, self.exposure, self.derotated):   # (every output of every round must be written)
-            buf.fill_(0xEE)
-        self.wire.zero_()
-
-    def enqueue(self, all_rounds=False):
-        count = None if all_rounds else self.count
-        if self.cam is None:
-            self.eng.bank_push_burst(self.bank, self.K, self.frames, self.times, count, self.gyro, mavlink=True,
-                                     records=self.records, out_frames=self.wire, out_lengths=self.lens,
-                                     round_stride=self.round_stride)
-        else:
-            self.eng.bank_push_camera_burst(self.bank, self.K, self.frames, self.times, count, self.gyro, mavlink=True,
-                                            records=self.records, exposure=self.exposure if self.want_exposure else None,
-                                            derotated=self.derotated, out_frames=self.wire, out_lengths=self.lens,
-                                            want_exposure=self.want_exposure, round_stride=self.round_stride)
-
-    def read(self):
-        """Per round: (records, wire frames, exposure records, de-rotated floats)."""
-        self.torch.cuda.synchronize()
-        w, n = self.wire.cpu().numpy(), self.lens.cpu().numpy()
-        e, d = self.exposure.cpu().numpy(), self.derotated.cpu().numpy()
-        S = self.run.S
-        return [(self.aof.ticks_view(self.records[k]), [bytes(w[k, s, :n[k, s]]) for s in range(S)],
-                 e[k].view(self.aof.EXPOSURE_DTYPE).reshape(S), d[k].view(np.float32)) for k in range(self.K)]
-
-    def push(self, j, given, sensors=None):
-        self.load(j, given, sensors)
-        self.enqueue()
-        return self.read()
-
-    def raw(self):
-        """Every output buffer as bytes (for comparisons between two devices)."""
-        self.torch.cuda.synchronize()
-        return b"".join(b.cpu().numpy().tobytes() for b in (self.records, self.wire, self.lens, self.exposure, self.derotated))
-
-    def bank_bytes(self):
-        return self.bank.frames_bytes().tobytes() + self.bank.state_bytes().tobytes()
-
-    def gate_bytes(self):
-        return np.ascontiguousarray(self.bank.state_bytes()[:, 56:64]).view("<u8").reshape(-1)
-
-
-class Case:
-    """The inputs of one case and everything the oracle chain expects of it, made on the CPU."""
-
-    def __init__(self, aof, orc, synth, cfg, K, S=24, B=6, seed=1, camera=False, overrides=None, rate=15, first_seq=0,
-                 wrap=False, use_gyro=True, exposure=True, derotate=True, sensor=None, skew=0, pad=0, frame_stride=0,
-                 camera_stride=0, interval=cref.EXPOSURE_INTERVAL_US, path=0, needs=(), resets=None, fx=FX, fy=FY, burst_run=None):
-        """fx, fy: the focal lengths of the bank, the camera's de-rotation and the oracle chains.  burst_run: (Run, counts,
-        given) in make_burst_run's form to use in its place, as they are (no saturated patches)."""
-        self.aof, self.K, self.S, self.B, self.camera, self.path = aof, K, S, B, camera, path
-        self.use_gyro, self.exposure, self.derotate, self.skew, self.pad = use_gyro, exposure, derotate, skew, pad
-        self.p = p = params_for(aof, cfg, overrides)
-        if burst_run is not None:
-            self.run, self.counts, self.given = burst_run
-            assert (self.run.T, self.run.S) == (B * K, S)
-        else:
-            self.run, self.counts, self.given = make_burst_run(synth, p.width, p.height, S, K, B, seed, wrap=wrap)
-            if camera:
-                cref.add_saturated_patches(self.run)
-        new = lambda s=0: ref.oracle_chain(aof, orc, p, rate, OFFSET, first_seq, use_gyro, fx=fx, fy=fy)
-        tick_resets = {j * K: m for j, m in (resets or {}).items()}
-        self.want, self.wire = ref.expected(self.run, [new() for _ in range(S)], resets=tick_resets, new_chain=new)
-        self.bp = aof.bank_params(S, fx, fy, rate, OFFSET, 1, 100, first_seq, frame_stride)
-        self.due = self.after = self.derot = self.cam = self.cam_run = None
-        if camera:
-            sensor = sensor or SENSOR[cfg]
-            self.cam = aof.bank_camera_params(sensor[0], sensor[1], p.width, p.height, camera_stride, interval,
-                                              cref.DEROTATE if derotate else None, fx, fy)
-            self.cam_run = cref.CameraRun(self.run, sensor[0], sensor[1], seed)
-            self.due, self.after = cref.gate(self.run.times, self.run.active, interval, resets=tick_resets)
-            if not exposure:                # no statistics: the gate does not move
-                self.due[:], self.after[:] = 0, 0
-            self.derot = np.stack([cref.expected_derotated(orc, self.want[t], self.run.gyro[t], fx, fy, use_gyro=use_gyro)
-                                   for t in range(self.run.T)])
-        # conditions on the INPUT, checked on the CPU chain before the device is compared
-        self.seen = census(self.run, self.counts, K, self.want, self.wire, self.due if exposure else None, rate, first_seq)
-        if camera and not exposure:
-            self.seen.add("no-exposure-records")
-        if camera and (self.cam_run.y0 * self.cam_run.cam_w + self.cam_run.x0 + skew) % 2 == 1:
-            self.seen.add("crop-origin-on-an-odd-byte")
-        assert (self.given > K).any(), "one count above K"
-        missing = set(needs) - self.seen
-        assert not missing, ("the oracle chain of this input does not show", missing, "only", self.seen)
-
-    def engine(self, path=None):
-        eng = self.aof.FlowEngine(self.p, 0)
-        eng.set_bank_path(self.path if path is None else path)
-        return eng
-
-    def burst_device(self, eng, gpu_device):
-        return BurstDevice(self.aof, eng, self.run, self.K, self.bp, gpu_device, camera=(self.cam, self.cam_run) if self.camera else None,
-                           use_gyro=self.use_gyro, exposure=self.exposure, skew=self.skew, pad=self.pad)
-
-    def tick_device(self, eng, gpu_device):
-        if self.camera:
-            return CamDevice(self.aof, eng, self.run, self.cam_run, self.bp, self.cam, gpu_device, use_gyro=self.use_gyro,
-                             exposure=self.exposure, skew=self.skew)
-        return Device(self.aof, eng, self.run, self.bp, gpu_device, use_gyro=self.use_gyro)
-
-    def sensors(self, j):
-        return [self.cam_run.sensor(j * self.K + k) for k in range(self.K)] if self.camera else None
-
-    def check_against_oracle(self, j, got, orc):
-        """Burst j's outputs against the oracle chain, round by round."""
-        for k, (recs, sent, expo, derot) in enumerate(got):
-            t = j * self.K + k
-            same_records(recs, self.want[t], t, "oracle")
-            assert sent == self.wire[t], ("oracle wire", j, k, [s for s in range(self.S) if sent[s] != self.wire[t][s]][:4])
-            if not self.camera:
-                continue
-            if self.exposure:
-                want_e = cref.expected_exposure(self.aof, orc, self.cam_run.sensor(t), self.run, t, self.due[t])
-                same_exposure(expo, want_e, t, "oracle exposure")
-            else:
-                assert untouched(expo), (j, k)
-            if self.derotate:
-                assert derot.tobytes() == self.derot[t].tobytes(), ("de-rotated", j, k)
-            else:
-                assert untouched(derot), (j, k)
-
-    def check_against_ticks(self, j, got, twin):
-        """Burst j's outputs against K single ticks on the twin bank (call k: round k's buffers, active = k < count)."""
-        sensors = self.sensors(j)
-        for k, (recs, sent, expo, derot) in enumerate(got):
-            t = j * self.K + k
-            assert (self.run.active[t] == (k < np.minimum(self.counts[j], self.K))).all()
-            if self.camera:
-                tick = twin.push(t, sensors[k])
-                assert recs.tobytes() == tick.recs.tobytes() and sent == tick.wire, ("records of K ticks", j, k)
-                assert expo.tobytes() == tick.exposure.tobytes(), ("exposure of K ticks", j, k)
-                assert derot.tobytes() == tick.derotated.tobytes(), ("de-rotated of K ticks", j, k)
-            else:
-                trecs, twire = twin.push(t)
-                assert recs.tobytes() == trecs.tobytes() and sent == twire, ("records of K ticks", j, k)
-
 
 BASIC = ("first-frame-then-more", "count0", "publication-before-the-last-round", "held")
 GATE = ("gate-opens-in-a-later-round-and-stays-shut",)
@@ -356,18 +95,17 @@ def test_a_null_count_means_every_round(aof, orc, synth, gpu_device):
         run.times[:, s] = 11000 * (np.arange(K * B) + 1) + 7 * s
     bp = aof.bank_params(S, FX, FY, 15, OFFSET, 1, 100, 0)
     eng, eng_t = aof.FlowEngine(p, 0), aof.FlowEngine(p, 0)
-    dev, twin = BurstDevice(aof, eng, run, K, bp, gpu_device), Device(aof, eng_t, run, bp, gpu_device)
+    dev, twin = BankRig(aof, eng, run, bp, gpu_device, K=K), BankRig(aof, eng_t, run, bp, gpu_device)
     full = np.full((B, S), K, np.uint8)
     for j in range(B):
         dev.load(j, full)
         dev.enqueue(all_rounds=True)
         for k, (recs, sent, _, _) in enumerate(dev.read()):
             twin.load(j * K + k)
-            eng_t.bank_push(twin.bank, twin.frames, twin.times, None, twin.gyro, mavlink=True, records=twin.records,
-                            out_frames=twin.wire, out_lengths=twin.lens)
-            trecs, twire = twin.read()
-            assert recs.tobytes() == trecs.tobytes() and sent == twire, (j, k)
-        assert dev.bank_bytes() == twin.bank.frames_bytes().tobytes() + twin.bank.state_bytes().tobytes(), j
+            twin.enqueue(all_rounds=True)
+            tick = twin.read()
+            assert recs.tobytes() == tick.recs.tobytes() and sent == tick.wire, (j, k)
+        assert dev.bank_bytes() == twin.bank_bytes(), j
     eng.close(), eng_t.close()
 
 

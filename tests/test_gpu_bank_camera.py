@@ -3,7 +3,8 @@ frames and leaves what mainloop.cpp:295-373 produces per camera -- against the C
 masked histogram: orc.ingest, MSV: orc.exposure_msv, calcFlow chain: tests/bank_ref.py, gyro compensation: orc.derotate,
 the exposure gate restated in integers), against the two calls it replaces (aof_ingest_batch_device + aof_bank_push_device),
 against the sequence pipeline, on both of its paths, from a captured graph, and through its argument checks.  Every
-comparison is on raw bytes; every output buffer is pre-filled with 0xEE.  Inputs: tests/bank_camera_ref.py."""
+comparison is on raw bytes; every output buffer is pre-filled with 0xEE.  Inputs: tests/bank_camera_ref.py; the rig:
+tests/bank_rig.py."""
 import ctypes as C
 
 import numpy as np
@@ -11,164 +12,12 @@ import pytest
 
 import bank_camera_ref as cref
 import bank_ref as ref
+from bank_cases import run_camera_case
 from bank_ref import FX, FY
-from test_gpu_bank import OFFSET, params_of, same_records
+from bank_rig import EINVAL, ENOSPC, GATED, LIMITED, OFFSET, SENSOR, BankRig, params_of, same_exposure, same_records, untouched
+from bank_rig import time_limit   # (this module's fixture too: every test under a limit of its own)
 
 pytestmark = pytest.mark.gpu
-
-EINVAL, ENOSPC = -22, -28
-SENSOR = {"px4-64": (320, 240), "opencv-128": (640, 480), "dense-192x160": (256, 224), "tile16-160x128": (224, 192)}
-
-
-class Tick:
-    def __init__(self, recs, wire, exposure, derotated):
-        self.recs, self.wire, self.exposure, self.derotated = recs, wire, exposure, derotated
-
-
-class CamDevice:
-    """One camera bank and its tick buffers on the device; push(k) runs tick k and returns host copies.  skew: the
-    sensor frames start that many bytes into their allocation (they need no alignment)."""
-
-    def __init__(self, aof, eng, run, cam_run, bp, cam, gpu_device, use_gyro=True, exposure=True, skew=0):
-        import torch
-        self.aof, self.eng, self.run, self.cam_run, self.torch = aof, eng, run, cam_run, torch
-        self.bank = eng.bank_create(bp, gpu_device, camera=cam)
-        S = run.S
-        self.sensor_bytes = cam_run.cam_w * cam_run.cam_h
-        self.stride = cam.camera_stride or self.sensor_bytes
-        self.alloc = torch.zeros(S * self.stride + 64, dtype=torch.uint8, device=gpu_device)
-        self.camera = self.alloc[skew:skew + S * self.stride]              # stream s at s * camera_stride
-        self.times = torch.zeros(S, dtype=torch.int64, device=gpu_device)
-        self.active = torch.zeros(S, dtype=torch.uint8, device=gpu_device)
-        self.gyro = torch.zeros((S, 4), dtype=torch.float32, device=gpu_device) if use_gyro else None
-        self.records = torch.zeros((S, 48), dtype=torch.uint8, device=gpu_device)
-        self.exposure = torch.zeros((S, 48), dtype=torch.uint8, device=gpu_device)
-        self.want_exposure = exposure
-        self.derotated = torch.zeros((S, 8), dtype=torch.uint8, device=gpu_device)    # float [S][2], compared as bytes
-        self.wire = torch.zeros((S, 56), dtype=torch.uint8, device=gpu_device)
-        self.lens = torch.zeros(S, dtype=torch.uint8, device=gpu_device)
-
-    def load(self, k, sensor=None):
-        t, run = self.torch, self.run
-        sensor = self.cam_run.sensor(k) if sensor is None else sensor
-        self.camera.view(run.S, self.stride)[:, :self.sensor_bytes].copy_(t.from_numpy(sensor.reshape(run.S, -1)))
-        self.times.copy_(t.from_numpy(run.times[k]))
-        self.active.copy_(t.from_numpy(run.active[k]))
-        if self.gyro is not None:
-            self.gyro.copy_(t.from_numpy(run.gyro[k]))
-        for buf in (self.records, self.exposure, self.derotated, self.lens):   # (every output of the tick must be written)
-            buf.fill_(0xEE)
-        self.wire.zero_()
-
-    def enqueue(self):
-        self.eng.bank_push_camera(self.bank, self.camera, self.times, self.active, self.gyro, mavlink=True, records=self.records,
-                                  exposure=self.exposure if self.want_exposure else None, derotated=self.derotated,
-                                  out_frames=self.wire, out_lengths=self.lens, want_exposure=self.want_exposure)
-
-    def read(self):
-        self.torch.cuda.synchronize()
-        w, n = self.wire.cpu().numpy(), self.lens.cpu().numpy()
-        return Tick(self.aof.ticks_view(self.records), [bytes(w[s, :n[s]]) for s in range(len(n))],
-                    self.aof.exposure_view(self.exposure), self.derotated.cpu().numpy().view(np.float32))
-
-    def push(self, k, sensor=None):
-        self.load(k, sensor)
-        self.enqueue()
-        return self.read()
-
-    def gate_bytes(self):
-        """next_exposure_us of every stream: the last 8 bytes of its state record."""
-        return np.ascontiguousarray(self.bank.state_bytes()[:, 56:64]).view("<u8").reshape(-1)
-
-
-def same_exposure(got, want, tick, what):
-    if got.tobytes() == want.tobytes():
-        return
-    for s in range(len(got)):
-        for n in got.dtype.names:
-            assert got[s][n].tobytes() == want[s][n].tobytes(), (what, "tick", tick, "stream", s, n, got[s], want[s])
-
-
-def untouched(a):
-    return (np.asarray(a).view(np.uint8) == 0xEE).all()
-
-
-GATED = (2, 10)   # per stream, 48 ticks at 200 000 us: >= 2 due and >= 10 not-due active frames
-
-
-def prepare(aof, orc, synth, p, S, T, seed, interval, rate, wrap, use_gyro, census, gated, exposure, derotate, fx=FX, fy=FY,
-            source=None, patches=True):
-    """The inputs and everything expected of a case, with the conditions on the INPUT asserted (no device needed)."""
-    run = ref.make_run(synth, p.width, p.height, S, T, seed, wrap=wrap, source=source)
-    if patches:
-        cref.add_saturated_patches(run)
-    want, wire = ref.expected(run, [ref.oracle_chain(aof, orc, p, rate, OFFSET, 0, use_gyro, fx=fx, fy=fy) for _ in range(S)])
-    due, after = cref.gate(run.times, run.active, interval)
-    if not exposure:                # no statistics: the gate does not move
-        due[:], after[:] = 0, 0
-    derot = np.stack([cref.expected_derotated(orc, want[k], run.gyro[k], fx, fy, use_gyro=use_gyro) for k in range(T)])
-    # conditions on the INPUT, before the device runs: a bank that never gates, holds or de-rotates cannot pass
-    if census is not None:
-        pub, held, idle = ref.census(want)
-        assert pub.min() >= census[0] and held.min() >= census[1] and idle.min() >= census[2], (pub, held, idle)
-    if gated is not None:
-        n_due, n_not = due.sum(0), ((run.active == 1) & (due == 0)).sum(0)
-        assert n_due.min() >= gated[0] and n_not.min() >= gated[1], (n_due, n_not)
-    if derotate and use_gyro:
-        pairs = (want["quality"] != ref.TICK_IDLE) & (want["frame"] > 1)
-        raw = np.stack([want["pixel"]["flow_x"], want["pixel"]["flow_y"]], -1)
-        moved = (derot != raw).any(-1)
-        assert (pairs & moved).any() and (pairs & ~moved & (raw != 0).any(-1)).any(), "some pair is compensated, some is left alone"
-    return run, want, wire, due, after, derot
-
-
-def run_case(aof, orc, synth, gpu_device, cfg, S, T, seed, sensor=None, interval=cref.EXPOSURE_INTERVAL_US, rate=15,
-             wrap=False, use_gyro=True, path=0, census=None, gated=None, frame_stride=0, camera_stride=0, exposure=True,
-             derotate=True, skew=0, fx=FX, fy=FY, source=None, patches=True):
-    """One camera bank over one Run against the oracle chain, tick by tick; returns (records, due).  fx, fy: the focal
-    lengths of the bank, the de-rotation and the chains; source: bank_ref.make_run's per-stream sequence source; patches:
-    the saturated patches of bank_camera_ref on the frames."""
-    p = params_of(aof, cfg)
-    sensor = sensor or SENSOR[cfg]
-    run, want, wire, due, after, derot = prepare(aof, orc, synth, p, S, T, seed, interval, rate, wrap, use_gyro, census, gated,
-                                                 exposure, derotate, fx=fx, fy=fy, source=source, patches=patches)
-    eng = aof.FlowEngine(p, 0)
-    eng.set_bank_path(path)
-    bp = aof.bank_params(S, fx, fy, rate, OFFSET, 1, 100, 0, frame_stride)
-    cam = aof.bank_camera_params(sensor[0], sensor[1], p.width, p.height, camera_stride, interval,
-                                 cref.DEROTATE if derotate else None, fx, fy)
-    cam_run = cref.CameraRun(run, sensor[0], sensor[1], seed)
-    dev = CamDevice(aof, eng, run, cam_run, bp, cam, gpu_device, use_gyro=use_gyro, exposure=exposure, skew=skew)
-    stride = frame_stride or p.width * p.height
-    for k in range(T):
-        frames_img = cam_run.sensor(k)
-        want_e = cref.expected_exposure(aof, orc, frames_img, run, k, due[k])   # (asserts: the oracle's crop is the run's frame)
-        before_frames, before_state = dev.bank.frames_bytes(), dev.bank.state_bytes()
-        got = dev.push(k, frames_img)
-        same_records(got.recs, want[k], k, "oracle")
-        assert got.wire == wire[k], ("oracle wire", k, [s for s in range(S) if got.wire[s] != wire[k][s]][:4])
-        if exposure:
-            same_exposure(got.exposure, want_e, k, "oracle exposure")
-        else:
-            assert untouched(got.exposure), k
-        if derotate:
-            assert got.derotated.tobytes() == derot[k].tobytes(), ("de-rotated", k, got.derotated, derot[k])
-        else:
-            assert untouched(got.derotated), k
-        after_frames, after_state = dev.bank.frames_bytes(), dev.bank.state_bytes()
-        for s in range(S):
-            slot = slice(s * stride, s * stride + p.width * p.height)
-            if run.active[k, s]:
-                assert after_frames[slot].tobytes() == run.frames[k, s].tobytes(), ("stored frame = the oracle's crop", k, s)
-            else:
-                assert after_frames[slot].tobytes() == before_frames[slot].tobytes(), ("idle frame", k, s)
-                assert after_state[s].tobytes() == before_state[s].tobytes(), ("idle state and gate", k, s)
-        assert dev.gate_bytes().tolist() == after[k].tolist(), ("gate", k)
-    eng.close()
-    return want, due
-
-
-LIMITED = (3, 10, 5)   # bank_ref's census per stream over 48 ticks at a limited rate: published, held, idle
 
 CASES = [
     dict(id="px4-64-from-320x240", cfg="px4-64", S=24, T=48, seed=1, census=LIMITED, gated=GATED),
@@ -195,7 +44,7 @@ CASES = [
 @pytest.mark.parametrize("case", CASES, ids=lambda c: c["id"])
 def test_camera_bank_equals_the_oracle_chain_per_stream_and_tick(aof, orc, synth, gpu_device, case):
     kw = {k: v for k, v in case.items() if k != "id"}
-    want, due = run_case(aof, orc, synth, gpu_device, **kw)
+    want, due = run_camera_case(aof, orc, synth, gpu_device, **kw)
     if case["id"].startswith("S300"):
         # 8 ticks: over all streams some frame was gated and some beyond a first frame was due
         assert ((want["quality"] != ref.TICK_IDLE) & (due == 0)).any() and (due[want["frame"] > 1] == 1).any()
@@ -217,7 +66,7 @@ def test_camera_push_equals_ingest_batch_followed_by_the_plain_push(aof, synth, 
     bp = aof.bank_params(S, FX, FY, 15, OFFSET, 1, 100, 3)
     cam = aof.bank_camera_params(sensor[0], sensor[1], p.width, p.height, 0, cref.EXPOSURE_INTERVAL_US, cref.DEROTATE, FX, FY)
     eng_a, eng_b = aof.FlowEngine(p, 0), aof.FlowEngine(p, 0)
-    dev = CamDevice(aof, eng_a, run, cam_run, bp, cam, gpu_device)
+    dev = BankRig(aof, eng_a, run, bp, gpu_device, camera=(cam, cam_run))
     plain = eng_b.bank_create(bp, gpu_device)
     frames = torch.zeros((S, p.height, p.width), dtype=torch.uint8, device=gpu_device)
     recs = torch.zeros((S, 48), dtype=torch.uint8, device=gpu_device)
@@ -228,8 +77,8 @@ def test_camera_push_equals_ingest_batch_followed_by_the_plain_push(aof, synth, 
     for k in range(T):
         got = dev.push(k)
         recs.fill_(0xEE), wire.zero_(), lens.fill_(0xEE)
-        aof.ingest_batch(dev.camera.view(S, sensor[1], sensor[0]), p.width, p.height, cropped=frames, hist=hist)
-        eng_b.bank_push(plain, frames, dev.times, dev.active, dev.gyro, mavlink=True, records=recs, out_frames=wire, out_lengths=lens)
+        aof.ingest_batch(dev.frames.view(S, sensor[1], sensor[0]), p.width, p.height, cropped=frames, hist=hist)
+        eng_b.bank_push(plain, frames, dev.times, dev.select, dev.gyro, mavlink=True, records=recs, out_frames=wire, out_lengths=lens)
         torch.cuda.synchronize()
         assert got.recs.tobytes() == aof.ticks_view(recs).tobytes(), k
         w, n = wire.cpu().numpy(), lens.cpu().numpy()
@@ -266,11 +115,11 @@ def test_both_camera_paths_leave_identical_bytes_after_every_tick(aof, synth, gp
         eng = aof.FlowEngine(p, 0)
         eng.set_bank_path(path)
         engs.append(eng)
-        devs.append(CamDevice(aof, eng, run, cam_run, bp, cam, gpu_device))
+        devs.append(BankRig(aof, eng, run, bp, gpu_device, camera=(cam, cam_run)))
     held = published = n_due = n_gated = 0
     for k in range(T):
         frames_img = cam_run.sensor(k)
-        a, b = devs[0].push(k, frames_img), devs[1].push(k, frames_img)
+        a, b = devs[0].push(k, sensors=frames_img), devs[1].push(k, sensors=frames_img)
         assert a.recs.tobytes() == b.recs.tobytes(), k
         assert a.wire == b.wire, k
         assert a.exposure.tobytes() == b.exposure.tobytes(), k
@@ -314,10 +163,10 @@ def test_one_stream_through_the_bank_equals_the_sequence_pipeline(aof, synth, gp
     cam = aof.bank_camera_params(cam_w, cam_h, w, h, 0, 0, cref.DEROTATE, FX, FY)
     for path in (1, 2):
         eng.set_bank_path(path)
-        dev = CamDevice(aof, eng, run, cam_run, bp, cam, gpu_device)
+        dev = BankRig(aof, eng, run, bp, gpu_device, camera=(cam, cam_run))
         m = 0
         for k in range(n):
-            got = dev.push(k, frames[k:k + 1])
+            got = dev.push(k, sensors=frames[k:k + 1])
             r, e = got.recs[0], got.exposure[0]
             assert e["due"] == 1 and e["hist"].tolist() == out["exposure"][k].tolist(), (path, k)
             if k == 0:
@@ -349,9 +198,9 @@ def test_a_captured_camera_tick_replays_on_new_inputs(aof, synth, gpu_device, pa
     cam = aof.bank_camera_params(sensor[0], sensor[1], 128, 128, 0, 50_000, cref.DEROTATE, FX, FY)
     eng = aof.FlowEngine(p, 0)
     eng.set_bank_path(path)
-    eager = CamDevice(aof, eng, run, cam_run, bp, cam, gpu_device)
+    eager = BankRig(aof, eng, run, bp, gpu_device, camera=(cam, cam_run))
     outs = [eager.push(k) for k in range(T)]
-    dev = CamDevice(aof, eng, run, cam_run, bp, cam, gpu_device)
+    dev = BankRig(aof, eng, run, bp, gpu_device, camera=(cam, cam_run))
     dev.push(0)                                  # (every kernel of the tick has run once before the capture)
     eng.bank_reset(dev.bank)
     torch.cuda.synchronize()
@@ -472,7 +321,7 @@ def test_a_masked_reset_mid_run_opens_the_gate_of_the_reset_streams(aof, orc, sy
     for path in (1, 2):
         eng = aof.FlowEngine(p, 0)
         eng.set_bank_path(path)
-        dev = CamDevice(aof, eng, run, cam_run, bp, cam, gpu_device)
+        dev = BankRig(aof, eng, run, bp, gpu_device, camera=(cam, cam_run))
         for k in range(T):
             if k == at:
                 before = dev.gate_bytes()
@@ -481,7 +330,7 @@ def test_a_masked_reset_mid_run_opens_the_gate_of_the_reset_streams(aof, orc, sy
                 now = dev.gate_bytes()
                 assert not now[mask == 1].any() and now[mask == 0].tolist() == before[mask == 0].tolist()
             frames_img = cam_run.sensor(k)
-            got = dev.push(k, frames_img)
+            got = dev.push(k, sensors=frames_img)
             same_records(got.recs, want[k], k, f"path {path}")
             assert got.wire == wire[k], (path, k)
             same_exposure(got.exposure, cref.expected_exposure(aof, orc, frames_img, run, k, due[k]), k, f"path {path}")

@@ -11,25 +11,14 @@ import pytest
 
 import bank_camera_ref as cref
 import exposure_control_ref as xref
+from bank_cases import make_burst_run
 from bank_ref import FX, FY
-from test_gpu_bank import OFFSET, params_of
-from test_gpu_bank_burst import BurstDevice, make_burst_run
-from test_gpu_bank_camera import CamDevice, same_exposure
+from bank_rig import EINVAL, EIO, FILL, OFFSET, BankRig, Guarded, params_of, same, same_exposure
+from bank_rig import engine, time_limit   # (this module's fixtures too: every test under a limit of its own)
 
 pytestmark = pytest.mark.gpu
 
-EINVAL, EIO = -22, -5
-FILL, GUARD = 0xEE, 64
 UPDATES = 32          # updates per stream of the synthetic runs: two calls of K = 16
-
-
-def same(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    if got.tobytes() == want.tobytes():
-        return
-    g, w = got.reshape(-1), want.reshape(-1)
-    bad = [i for i in range(len(w)) if g[i].tobytes() != w[i].tobytes()]
-    raise AssertionError((what, "first of", len(bad), "at", bad[0], g[bad[0]], w[bad[0]]))
 
 
 class Controller:
@@ -39,13 +28,9 @@ class Controller:
     def __init__(self, aof, eng, gpu_device, S, K, states, skew=0):
         import torch
         self.aof, self.eng, self.torch, self.S, self.K, self.dev = aof, eng, torch, S, K, gpu_device
-        self.state_alloc = torch.full((16 * S + GUARD,), FILL, dtype=torch.uint8, device=gpu_device)
-        self.state = self.state_alloc[skew:skew + 16 * S].view(S, 16)
-        self.cmd_alloc = torch.full((16 * K * S + GUARD,), FILL, dtype=torch.uint8, device=gpu_device)
-        self.commands = self.cmd_alloc[skew:skew + 16 * K * S].view(K, S, 16)
-        self.rec_alloc = torch.zeros(48 * K * S + GUARD, dtype=torch.uint8, device=gpu_device)
-        self.records = self.rec_alloc[skew:skew + 48 * K * S].view(K, S, 48)
-        self.skew = skew
+        self.state_buf, self.cmd_buf = Guarded(gpu_device, (S, 16), skew=skew), Guarded(gpu_device, (K, S, 16), skew=skew)
+        self.state, self.commands = self.state_buf.tensor, self.cmd_buf.tensor
+        self.records = torch.zeros(48 * K * S + 64, dtype=torch.uint8, device=gpu_device)[skew:skew + 48 * K * S].view(K, S, 48)
         eng.bank_exposure_reset(self.state, exposures=torch.from_numpy(states["exposure"].astype(np.int16)).to(gpu_device),
                                 gains=torch.from_numpy(np.ascontiguousarray(states["gain"])).to(gpu_device))
 
@@ -53,7 +38,7 @@ class Controller:
         """records: RECORD_DTYPE [k, S], k <= K."""
         k = len(records)
         self.records[:k].copy_(self.torch.from_numpy(np.ascontiguousarray(records).view(np.uint8).reshape(k, self.S, 48)))
-        self.cmd_alloc.fill_(FILL)
+        self.cmd_buf.refill()
         return k
 
     def run(self, records):
@@ -64,12 +49,8 @@ class Controller:
     def read(self, k):
         """(states, commands of the first k rounds); the bytes around both must be untouched."""
         self.torch.cuda.synchronize()
-        st, cm = self.state_alloc.cpu().numpy(), self.cmd_alloc.cpu().numpy()
-        a, b = self.skew + 16 * self.S, self.skew + 16 * k * self.S
-        assert (st[:self.skew] == FILL).all() and (st[a:] == FILL).all(), "bytes around the states were written"
-        assert (cm[:self.skew] == FILL).all() and (cm[b:] == FILL).all(), "bytes behind the commands were written"
-        return (st[self.skew:a].view(self.aof.EXPOSURE_STATE_DTYPE).copy(),
-                cm[self.skew:b].view(self.aof.EXPOSURE_COMMAND_DTYPE).reshape(k, self.S).copy())
+        return (self.state_buf.read().reshape(-1).view(self.aof.EXPOSURE_STATE_DTYPE),
+                self.cmd_buf.read(16 * k * self.S).view(self.aof.EXPOSURE_COMMAND_DTYPE).reshape(k, self.S))
 
 
 _synthetic = {}
@@ -95,13 +76,6 @@ def synthetic(S):
         tally = xref.control(records[:24], states0)[2] if S == 48 else None
         _synthetic[S] = (states0, records, half, full, np.concatenate([first, second]), tally)
     return _synthetic[S]
-
-
-@pytest.fixture(scope="module")
-def engine(aof, gpu_device):
-    eng = aof.FlowEngine(aof.px4flow_params(64, 64), 0)
-    yield eng
-    eng.close()
 
 
 @pytest.mark.parametrize("S", [1, 48, 63, 257, 300])
@@ -156,7 +130,7 @@ def test_a_masked_reset_restarts_only_the_masked_streams(aof, engine, gpu_device
     ctl = Controller(aof, engine, gpu_device, S, 16, states0)
     got_states, _ = ctl.run(records[:16])
     same(got_states, half, "before the reset")
-    ctl.cmd_alloc.fill_(FILL)                           # (a reset writes no command either: read(0) looks)
+    ctl.cmd_buf.refill()                                # (a reset writes no command either: read(0) looks)
     mask =(np.arange(S) % 3 == 1).astype(np.uint8)
     assert (half["updates"][mask == 1] > 0).any()
     # scalars for the masked streams ...
@@ -275,7 +249,7 @@ def test_refused_calls_write_nothing(aof, engine, gpu_device):
     assert b"exposure" in aof.lib.aof_last_error(engine._ctx)
     got_states, got_commands = ctl.read(0)
     same(got_states, before, "a refused call must leave the states untouched")
-    assert (ctl.cmd_alloc.cpu().numpy() == FILL).all(), "a refused call must write no command"
+    assert (ctl.cmd_buf.alloc.cpu().numpy() == FILL).all(), "a refused call must write no command"
     # the context is still usable, with the widest constants allowed
     assert call(*args(ec=control(exposure_max=65535.0, gain_max=255.0))) == 0
     wide = xref.control(records[:K], states0, xref.Constants(exposure_max=65535.0, gain_max=255.0))
@@ -308,7 +282,7 @@ def test_a_faulted_context_controls_nothing(aof, synth, gpu_device):
         eng.bank_exposure_reset(ctl.state)
     assert e.value.code == EIO
     same(ctl.read(0)[0], states0, "states")
-    assert (ctl.cmd_alloc.cpu().numpy() == FILL).all()
+    assert (ctl.cmd_buf.alloc.cpu().numpy() == FILL).all()
     eng.close()
 
 
@@ -382,12 +356,12 @@ def e2e(aof, orc, synth, request):
 def test_camera_push_then_control_equals_the_model_fed_the_oracles_msv(aof, gpu_device, e2e):
     import torch
     eng = aof.FlowEngine(e2e.p, 0)
-    dev = CamDevice(aof, eng, e2e.run, e2e.cam_run, e2e.bp(aof), e2e.cam, gpu_device)
+    dev = BankRig(aof, eng, e2e.run, e2e.bp(aof), gpu_device, camera=(e2e.cam, e2e.cam_run))
     state = e2e.new_controller_state(aof, eng, gpu_device)
     commands = torch.zeros((e2e.S, 16), dtype=torch.uint8, device=gpu_device)
     host = e2e.states0.copy()
     for k in range(e2e.T):
-        dev.load(k, e2e.sensors[k])
+        dev.load(k, sensors=e2e.sensors[k])
         commands.fill_(FILL)
         dev.enqueue()
         eng.bank_exposure_control(dev.exposure, state, commands)
@@ -407,15 +381,14 @@ def test_the_same_run_as_camera_bursts(aof, gpu_device, e2e):
     """6 camera bursts of 4 rounds, one control call of 4 rounds behind each: the commands and states of the 24 ticks."""
     import torch
     eng = aof.FlowEngine(e2e.p, 0)
-    dev = BurstDevice(aof, eng, e2e.run, K_BURST, e2e.bp(aof), gpu_device, camera=(e2e.cam, e2e.cam_run))
+    dev = BankRig(aof, eng, e2e.run, e2e.bp(aof), gpu_device, K=K_BURST, camera=(e2e.cam, e2e.cam_run))
     state = e2e.new_controller_state(aof, eng, gpu_device)
     commands = torch.zeros((K_BURST, e2e.S, 16), dtype=torch.uint8, device=gpu_device)
     for j in range(BURSTS):
         ticks = slice(j * K_BURST, (j + 1) * K_BURST)
         dev.load(j, e2e.given, e2e.sensors[ticks])
         commands.fill_(FILL)
-        eng.bank_push_camera_burst(dev.bank, K_BURST, dev.frames, dev.times, dev.count, dev.gyro, mavlink=True, records=dev.records,
-                                   exposure=dev.exposure, out_frames=dev.wire, out_lengths=dev.lens)
+        dev.enqueue()
         eng.bank_exposure_control(dev.exposure, state, commands)
         torch.cuda.synchronize()
         got_records = dev.exposure.cpu().numpy().view(aof.EXPOSURE_DTYPE).reshape(K_BURST, e2e.S)

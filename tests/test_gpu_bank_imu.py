@@ -4,50 +4,22 @@ states must equal, byte for byte, the plain-Python model of tests/imu_ref.py -- 
 the coverage family and random families at the wave and workgroup edges) and behind real pushes on every bank path.
 Frame buffers are pre-filled with the model's sentinel, so bytes behind a frame's length are compared as well; every
 buffer has guard bytes behind it.  No tolerance anywhere."""
-import faulthandler
-
 import numpy as np
 import pytest
 
 import imu_ref as ref
 import outbox_ref as ob
 from bank_ref import FX, FY, make_run
+from bank_rig import EINVAL, ENOBUFS, Guarded, engine, time_limit   # (engine, time_limit: this module's fixtures too)
+from bank_rig import same as same_bytes
 
 pytestmark = pytest.mark.gpu
-
-EINVAL, ENOBUFS = -22, -105
-GUARD, LIMIT_S = 64, 120
-
-
-@pytest.fixture(autouse=True)
-def time_limit():
-    """Every test's device work under a limit of its own.  The exit is deliberate: a step that hangs on the device ends
-    the whole process at once (os._exit behind a traceback), so that nothing more is started on a card that hung -- the
-    tests behind it go without a report, which is the lesser evil.  Each test runs a few seconds; the limit is far above
-    that and only a hang reaches it."""
-    faulthandler.dump_traceback_later(LIMIT_S, exit=True)
-    yield
-    faulthandler.cancel_dump_traceback_later()
-
-
-@pytest.fixture(scope="module")
-def engine(aof, gpu_device):
-    eng = aof.FlowEngine(aof.px4flow_params(64, 64), 0)
-    yield eng
-    eng.close()
 
 
 def same(got, want, what):
     for name in ("records", "lengths", "frames", "states"):
-        if got.get(name) is None or want.get(name) is None:
-            continue
-        g, w = np.ascontiguousarray(got[name]), np.ascontiguousarray(want[name])
-        assert g.shape == w.shape, (what, name, g.shape, w.shape)
-        if g.tobytes() != w.tobytes():
-            bad = np.flatnonzero((g.view(np.uint8).reshape(-1) != w.view(np.uint8).reshape(-1)))
-            item = g.dtype.itemsize
-            raise AssertionError((what, name, "first of", len(bad), "bytes at", int(bad[0]), "element", int(bad[0]) // item,
-                                  g.reshape(-1)[bad[0] // item], w.reshape(-1)[bad[0] // item]))
+        if got.get(name) is not None and want.get(name) is not None:
+            same_bytes(got[name], want[name], (what, name))
 
 
 def model(f, k0=0, k1=None, states=None, pack=True):
@@ -70,11 +42,9 @@ class Imu:
         self.counts = None if f["counts"] is None else up(f["counts"]).view(K, S)
         self.times = torch.from_numpy(np.ascontiguousarray(f["times"]).view(np.int64)).to(gpu_device)
         self.records_in = up(f["records"]).view(K, S, 48)
-        self.state_alloc = torch.full((64 * S + GUARD,), 0xEE, dtype=torch.uint8, device=gpu_device)
-        self.state = self.state_alloc[:64 * S].view(S, 64)
-        self.out_alloc = torch.zeros(48 * K * S + GUARD, dtype=torch.uint8, device=gpu_device)
-        self.wire_alloc = torch.zeros(56 * K * S + GUARD, dtype=torch.uint8, device=gpu_device)
-        self.lens_alloc = torch.zeros(K * S + GUARD, dtype=torch.uint8, device=gpu_device)
+        self.state_buf, self.out_buf = Guarded(gpu_device, (S, 64)), Guarded(gpu_device, (48 * K * S,))
+        self.wire_buf, self.lens_buf = Guarded(gpu_device, (56 * K * S,), fill=ref.SENTINEL), Guarded(gpu_device, (K * S,))
+        self.state = self.state_buf.tensor
         self.set_states(f["states"])
 
     def set_states(self, states):
@@ -84,12 +54,11 @@ class Imu:
         """Rounds k0 .. k1-1 in one call -> dict(records, frames, lengths, states) on the host."""
         k1 = self.K if k1 is None else k1
         n, S = k1 - k0, self.S
-        self.out_alloc.fill_(0xEE)
-        self.wire_alloc.fill_(ref.SENTINEL)
-        self.lens_alloc.fill_(0xEE)
-        out = self.out_alloc[:48 * n * S].view(n, S, 48)
-        wire = self.wire_alloc[:56 * n * S].view(n, S, 56)
-        lens = self.lens_alloc[:n * S].view(n, S)
+        for b in (self.out_buf, self.wire_buf, self.lens_buf):
+            b.refill()
+        out = self.out_buf.tensor[:48 * n * S].view(n, S, 48)
+        wire = self.wire_buf.tensor[:56 * n * S].view(n, S, 56)
+        lens = self.lens_buf.tensor[:n * S].view(n, S)
         rin = self.records_in[k0:k1]
         if in_place:
             out.copy_(rin)
@@ -98,15 +67,12 @@ class Imu:
                           mavlink=mavlink, records_out=out, out_frames=wire if mavlink else None,
                           out_lengths=lens if mavlink else None, first_seq=self.f["first_seq"])
         self.torch.cuda.synchronize()
-        o, w, l, st = (t.cpu().numpy() for t in (self.out_alloc, self.wire_alloc, self.lens_alloc, self.state_alloc))
-        assert (o[48 * n * S:] == 0xEE).all() and (st[64 * S:] == 0xEE).all(), "bytes behind the records or the states were written"
-        assert (w[56 * n * S:] == ref.SENTINEL).all() and (l[n * S:] == 0xEE).all(), "bytes behind the frames or the lengths were written"
-        got = dict(records=o[:48 * n * S].view(self.aof.TICK_DTYPE).reshape(n, S).copy(),
-                   states=st[:64 * S].view(self.aof.IMU_STATE_DTYPE).copy())
+        got = dict(records=self.out_buf.read(48 * n * S).view(self.aof.TICK_DTYPE).reshape(n, S),
+                   states=self.state_buf.read().reshape(-1).view(self.aof.IMU_STATE_DTYPE))
         if mavlink:
-            got.update(frames=w[:56 * n * S].reshape(n, S, 56).copy(), lengths=l[:n * S].reshape(n, S).copy())
-        else:
-            assert (w == ref.SENTINEL).all() and (l == 0xEE).all(), "without d_mavlink no frame byte and no length is written"
+            got.update(frames=self.wire_buf.read(56 * n * S).reshape(n, S, 56), lengths=self.lens_buf.read(n * S).reshape(n, S))
+        else:       # without d_mavlink no frame byte and no length is written
+            self.wire_buf.read(0), self.lens_buf.read(0)
         return got
 
 
@@ -180,8 +146,7 @@ def test_a_masked_reset_restarts_the_masked_streams_and_keeps_the_others(aof, en
     want[mask == 1] = fresh[mask == 1]
     assert (f["want"]["states"]["samples_integrated"][mask == 1] > 0).any()
     torch.cuda.synchronize()
-    st = imu.state_alloc.cpu().numpy()
-    assert st[:64 * 257].tobytes() == want.tobytes() and (st[64 * 257:] == 0xEE).all(), "masked reset"
+    assert imu.state_buf.read().tobytes() == want.tobytes(), "masked reset"
     # the streams go on from there
     same(imu.run(), model(f, states=want), "behind the reset")
 

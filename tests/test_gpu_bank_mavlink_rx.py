@@ -3,46 +3,16 @@ include/aof.h) and the facade's receive path (OpticalFlowBank::enableMavlinkRx /
 counts, the counts and all 128 state bytes must equal aof_bank_mavlink_rx_host byte for byte, the public 32 bytes the
 plain-Python model of tests/mavlink_rx_ref.py.  Sample buffers are pre-filled with the model's sentinel, so slots at
 and behind a count are compared as well; every buffer has guard bytes behind it.  No tolerance anywhere."""
-import faulthandler
-
 import numpy as np
 import pytest
 
 import mavlink_rx_ref as ref
 import outbox_ref as ob
 from bank_ref import FX, FY, make_run
+from bank_rig import EINVAL, ENOBUFS, Guarded, engine, same, time_limit   # (engine, time_limit: this module's fixtures too)
 
 pytestmark = pytest.mark.gpu
 
-EINVAL, ENOBUFS = -22, -105
-GUARD, LIMIT_S = 64, 120
-
-
-@pytest.fixture(autouse=True)
-def time_limit():
-    """Every test's device work under a limit of its own.  The exit is deliberate: a step that hangs on the device ends
-    the whole process at once (os._exit behind a traceback), so that nothing more is started on a card that hung.  Each
-    test runs a few seconds; the limit is far above that and only a hang reaches it."""
-    faulthandler.dump_traceback_later(LIMIT_S, exit=True)
-    yield
-    faulthandler.cancel_dump_traceback_later()
-
-
-@pytest.fixture(scope="module")
-def engine(aof, gpu_device):
-    eng = aof.FlowEngine(aof.px4flow_params(64, 64), 0)
-    yield eng
-    eng.close()
-
-
-def same_bytes(got, want, what):
-    g, w = np.ascontiguousarray(got), np.ascontiguousarray(want)
-    assert g.shape == w.shape, (what, g.shape, w.shape)
-    if g.tobytes() != w.tobytes():
-        bad = np.flatnonzero(g.view(np.uint8).reshape(-1) != w.view(np.uint8).reshape(-1))
-        item = g.dtype.itemsize
-        raise AssertionError((what, "first of", len(bad), "bytes at", int(bad[0]), "element", int(bad[0]) // item,
-                              g.reshape(-1)[bad[0] // item], w.reshape(-1)[bad[0] // item]))
 
 
 class Rx:
@@ -52,27 +22,24 @@ class Rx:
         import torch
         self.aof, self.eng, self.torch, self.dev = aof, eng, torch, gpu_device
         self.S, self.K, self.B, self.M = S, K, B, M
-        full = lambda n, v: torch.full((n + GUARD,), v, dtype=torch.uint8, device=gpu_device)
-        self.state_alloc = full(128 * S, 0xEE)
-        self.state = self.state_alloc[:128 * S].view(S, 128)
-        self.samples_alloc = full(24 * K * M * S, ref.SENTINEL)
-        self.counts_alloc = full(K * S, 0xEE)
+        self.state_buf, self.counts_buf = Guarded(gpu_device, (S, 128)), Guarded(gpu_device, (K * S,))
+        self.samples_buf = Guarded(gpu_device, (24 * K * M * S,), fill=ref.SENTINEL)
+        self.state = self.state_buf.tensor
         eng.bank_mavlink_rx_reset(self.state)
 
     def run(self, data, lengths):
         """One call -> (samples [K, M, S], counts [K, S]) on the host; slots nobody wrote hold the sentinel."""
         torch, S, M = self.torch, self.S, self.M
         K = data.shape[0]
-        self.samples_alloc.fill_(ref.SENTINEL)
-        self.counts_alloc.fill_(0xEE)
+        self.samples_buf.refill(), self.counts_buf.refill()
         d = torch.from_numpy(np.ascontiguousarray(data)).to(self.dev)
         ln = None if lengths is None else torch.from_numpy(np.ascontiguousarray(lengths).view(np.int16)).to(self.dev)
-        self.eng.bank_mavlink_rx(d, self.state, M, ln, self.samples_alloc[:24 * K * M * S].view(K, M, S, 24), self.counts_alloc[:K * S].view(K, S))
+        self.eng.bank_mavlink_rx(d, self.state, M, ln, self.samples_buf.tensor[:24 * K * M * S].view(K, M, S, 24),
+                                 self.counts_buf.tensor[:K * S].view(K, S))
         torch.cuda.synchronize()
-        sm, ct, st = (t.cpu().numpy() for t in (self.samples_alloc, self.counts_alloc, self.state_alloc))
-        assert (sm[24 * K * M * S:] == ref.SENTINEL).all() and (ct[K * S:] == 0xEE).all() and (st[128 * S:] == 0xEE).all(), \
-            "bytes behind the samples, the counts or the states were written"
-        return sm[:24 * K * M * S].view(self.aof.IMU_SAMPLE_DTYPE).reshape(K, M, S).copy(), ct[:K * S].reshape(K, S).copy()
+        self.state_buf.read()       # (the guard behind the states)
+        return (self.samples_buf.read(24 * K * M * S).view(self.aof.IMU_SAMPLE_DTYPE).reshape(K, M, S),
+                self.counts_buf.read(K * S).reshape(K, S))
 
     def states(self):
         return self.aof.mavlink_rx_states_view(self.state)
@@ -112,10 +79,10 @@ def check_family(aof, engine, gpu_device, S, K, B, M, calls):
     rx = Rx(aof, engine, gpu_device, S, K, B, M)
     for c, (data, lengths) in enumerate(f["calls"]):
         samples, counts = rx.run(data, lengths)
-        same_bytes(counts, f["want"][c][1], ("counts", c))
-        same_bytes(samples, f["want"][c][0], ("samples up to the counts, the sentinel behind them", c))
+        same(counts, f["want"][c][1], ("counts", c))
+        same(samples, f["want"][c][0], ("samples up to the counts, the sentinel behind them", c))
     st = rx.states()
-    same_bytes(st, f["states"], "all 128 state bytes against the host function")
+    same(st, f["states"], "all 128 state bytes against the host function")
     for n in ref.COUNTERS:
         assert np.array_equal(st[n], f["public"][n]), ("the public bytes against the model", n)
     return f, st
@@ -139,9 +106,9 @@ def test_null_lengths_mean_every_byte_of_the_slot(aof, engine, gpu_device):
     want, states = host_run(aof, calls, M, S)
     rx = Rx(aof, engine, gpu_device, S, K, B, M)
     samples, counts = rx.run(*calls[0])
-    same_bytes(counts, want[0][1], "counts")
-    same_bytes(samples, want[0][0], "samples")
-    same_bytes(rx.states(), states, "states")
+    same(counts, want[0][1], "counts")
+    same(samples, want[0][0], "samples")
+    same(rx.states(), states, "states")
     assert (states["bytes"] == K * B).all()
 
 
@@ -152,10 +119,10 @@ def test_one_call_of_k_rounds_equals_k_calls_of_one(aof, engine, gpu_device):
     rx = Rx(aof, engine, gpu_device, S, K, B, M)
     for k in range(K):
         samples, counts = rx.run(data[k:k + 1], lengths[k:k + 1])
-        same_bytes(counts[0], f["want"][0][1][k], ("counts", k))
-        same_bytes(samples[0], f["want"][0][0][k], ("samples", k))
+        same(counts[0], f["want"][0][1][k], ("counts", k))
+        same(samples[0], f["want"][0][0][k], ("samples", k))
     want_states = host_run(aof, f["calls"][:1], M, S)[1]
-    same_bytes(rx.states(), want_states, "states behind K calls of one round")
+    same(rx.states(), want_states, "states behind K calls of one round")
 
 
 def test_a_masked_reset_in_mid_frame_restarts_the_masked_streams_and_keeps_the_others(aof, engine, gpu_device):
@@ -174,13 +141,13 @@ def test_a_masked_reset_in_mid_frame_restarts_the_masked_streams_and_keeps_the_o
     torch.cuda.synchronize()
     after = rx.states().copy()
     assert not after[mask == 1].view(np.uint8).any(), "a reset stream is idle with every counter 0"
-    same_bytes(after[mask == 0], before[mask == 0], "the others")
-    assert (rx.state_alloc.cpu().numpy()[128 * S:] == 0xEE).all()
+    same(after[mask == 0], before[mask == 0], "the others")
+    rx.state_buf.read()         # (the guard behind the states)
     want, states = host_run(aof, f["calls"][1:], M, S, after)
     samples, counts = rx.run(*f["calls"][1])
-    same_bytes(counts, want[0][1], "counts behind the reset")
-    same_bytes(samples, want[0][0], "samples behind the reset")
-    same_bytes(rx.states(), states, "states behind the reset")
+    same(counts, want[0][1], "counts behind the reset")
+    same(samples, want[0][0], "samples behind the reset")
+    same(rx.states(), states, "states behind the reset")
 
 
 def test_refused_calls_write_nothing(aof, engine, gpu_device):
@@ -219,7 +186,7 @@ def test_refused_calls_write_nothing(aof, engine, gpu_device):
         assert (t.cpu().numpy() == 0xEE).all(), "a refused call must write nothing"
     assert call(*args()) == 0, "the context is still usable"
     torch.cuda.synchronize()
-    same_bytes(counts.cpu().numpy(), f["want"][0][1], "counts")
+    same(counts.cpu().numpy(), f["want"][0][1], "counts")
 
 
 # ---- in front of real pushes -----------------------------------------------------------------------------------------

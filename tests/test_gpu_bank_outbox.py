@@ -3,57 +3,34 @@ host-pollable list of what a push published must equal, byte for byte, the host-
 -- of the device's own outputs, of the oracle chain's records and wire frames, of K single ticks on a twin bank.
 Every outbox is pre-filled with 0xEE, and every byte behind the stored entries (guard bytes behind the outbox included)
 must still be 0xEE."""
-import ctypes as C
-import time
-
 import numpy as np
 import pytest
 
 import bank_ref as ref
 import outbox_ref as ob
+from bank_cases import Case
 from bank_ref import FX, FY
-from test_gpu_bank import Device, params_of
-from test_gpu_bank_burst import Case
+from bank_rig import EINVAL, EIO, ENOSPC, OFFSET, BankRig, Guarded, params_of, same
+from bank_rig import time_limit   # (this module's fixture too: every test under a limit of its own)
 
 pytestmark = pytest.mark.gpu
 
-OFFSET = ob.OFFSET
-EINVAL, ENOSPC, EIO = -22, -28, -5
-GUARD = 256
 
 
-class Box:
+class Box(Guarded):
     """A device outbox of the given capacities, 0xEE-filled, with guard bytes behind it."""
 
     def __init__(self, aof, gpu_device, cap_m, cap_e=0):
-        import torch
         self.total = aof.outbox_layout(cap_m, cap_e).total_bytes
-        self.cap_m, self.cap_e = cap_m, cap_e
-        self.alloc = torch.full((self.total + GUARD,), ob.FILL, dtype=torch.uint8, device=gpu_device)
-        self.tensor = self.alloc[:self.total]
+        super().__init__(gpu_device, (self.total,), fill=ob.FILL)
 
-    def refill(self):
-        self.alloc.fill_(ob.FILL)
-
-    def bytes(self):
-        """Host copy of the outbox (synchronises); the guard must be untouched."""
-        a = self.alloc.cpu().numpy()
-        assert (a[self.total:] == ob.FILL).all(), "bytes behind the outbox were written"
-        return a[:self.total]
+    bytes = Guarded.read      # host copy of the outbox (synchronises); the guard must be untouched
 
 
 def collect(aof, eng, gpu_device, records, wire, lens, exposure, derotated, cap_m, cap_e=0, tag=1):
     box = Box(aof, gpu_device, cap_m, cap_e)
     eng.bank_collect(records, wire, lens, exposure, derotated, cap_m, cap_e, outbox=box.tensor, tag=tag)
     return box.bytes()
-
-
-def same(got, want, what):
-    if got.tobytes() == want.tobytes():
-        return
-    bad = np.flatnonzero(got != want)
-    raise AssertionError((what, "first differing byte", int(bad[0]), "of", len(bad), got[bad[0]], want[bad[0]],
-                          "header", got[:24].tolist(), want[:24].tolist()))
 
 
 @pytest.fixture(scope="module")
@@ -67,7 +44,7 @@ def test_every_tick_of_the_recipe_equals_the_compaction_of_the_oracle_chain(aof,
     S = run.S
     eng = aof.FlowEngine(aof.px4flow_params(64, 64), 0)
     eng.set_bank_path(path)
-    dev = Device(aof, eng, run, aof.bank_params(S, FX, FY, 15, OFFSET, 1, 100, 0), gpu_device)
+    dev = BankRig(aof, eng, run, aof.bank_params(S, FX, FY, 15, OFFSET, 1, 100, 0), gpu_device)
     census = []
     for k in range(run.T):
         dev.load(k)
@@ -87,7 +64,7 @@ def test_overflow_stores_the_first_entries_and_counts_all(aof, recipe, gpu_devic
     run, recs, wire, lens, frames = recipe
     S, cap = run.S, 8
     eng = aof.FlowEngine(aof.px4flow_params(64, 64), 0)
-    dev = Device(aof, eng, run, aof.bank_params(S, FX, FY, 15, OFFSET, 1, 100, 0), gpu_device)
+    dev = BankRig(aof, eng, run, aof.bank_params(S, FX, FY, 15, OFFSET, 1, 100, 0), gpu_device)
     over = 0
     for k in range(run.T):
         dev.load(k)
@@ -120,11 +97,10 @@ def test_a_burst_collects_what_k_single_ticks_on_a_twin_bank_leave(aof, orc, syn
         got = collect(aof, eng, gpu_device, dev.records, dev.wire, dev.lens, expo, derot, n, n, tag=j + 7)
         tick = dict(records=[], wire=[], lens=[], exposure=[], derotated=[])
         for k in range(K):
-            twin.push(j * K + k, sensors[k]) if camera else twin.push(j * K + k)
+            twin.push(j * K + k, sensors=sensors[k] if camera else None)
             for name in tick:
-                if hasattr(twin, name):
-                    tick[name].append(getattr(twin, name).cpu().numpy())
-        t = {name: np.stack(v) for name, v in tick.items() if v}
+                tick[name].append(getattr(twin, name).cpu().numpy())
+        t = {name: np.stack(v) for name, v in tick.items()}
         want = ob.compact(t["records"], t["wire"], t["lens"], t.get("exposure") if camera else None,
                           t.get("derotated") if camera else None, n, n, tag=j + 7)
         same(got, want, ("K single ticks", j))
@@ -255,13 +231,13 @@ def test_a_captured_tick_and_collect_carry_a_fresh_tag_on_every_replay(aof, reci
     S = run.S
     eng = aof.FlowEngine(aof.px4flow_params(64, 64), 0)
     bp = aof.bank_params(S, FX, FY, 15, OFFSET, 1, 100, 0)
-    eager = Device(aof, eng, run, bp, gpu_device)
+    eager = BankRig(aof, eng, run, bp, gpu_device)
     outs = []
     for k in range(run.T):
         eager.load(k)
         eager.enqueue()
         outs.append(collect(aof, eng, gpu_device, eager.records, eager.wire, eager.lens, None, None, S, tag=500 + k))
-    dev = Device(aof, eng, run, bp, gpu_device)
+    dev = BankRig(aof, eng, run, bp, gpu_device)
     box = Box(aof, gpu_device, S)
     tag = torch.zeros(1, dtype=torch.int64, device=gpu_device)
     dev.push(0)                                   # (every kernel has run once before the capture)
@@ -355,7 +331,7 @@ def test_the_facade_bank_equals_one_opencv_object_per_stream(aof, synth, gpu_dev
     # the engine's own bank with the same configuration, for the wire frames
     p = params_of(aof, "opencv-128")
     eng = aof.FlowEngine(p, 0)
-    dev = Device(aof, eng, run, aof.bank_params(S, FX, FY, 15, OFFSET, 1, 100, 0), gpu_device)
+    dev = BankRig(aof, eng, run, aof.bank_params(S, FX, FY, 15, OFFSET, 1, 100, 0), gpu_device)
     got, want = [[] for _ in range(S)], [[] for _ in range(S)]
     empty = published = 0
     n, entries = bank.push(run.frames[0], run.times[0], run.active[0], run.gyro[0])
@@ -365,7 +341,7 @@ def test_the_facade_bank_equals_one_opencv_object_per_stream(aof, synth, gpu_dev
     for k in range(T):
         n, entries = bank.push(run.frames[k], run.times[k], run.active[k], run.gyro[k])
         assert n == len(entries) >= 0, (n, bank.lastError())
-        drecs, dwire = dev.push(k)
+        drecs, dwire, _, _ = dev.push(k)
         assert list(entries["stream"]) == sorted(entries["stream"]) and not entries["round"].any()
         for e in entries:
             s, r = int(e["stream"]), e["record"]

@@ -1,7 +1,7 @@
 """The stream bank with per-stream cameras (aof_bank_stream / aof_set_bank_streams, include/aof.h): S streams with their
 own focal lengths, output rate, vehicle-time offset and MAVLink identity, against one oracle chain per stream built with
 that stream's values (tests/bank_streams_ref.py) -- records and wire frames by bytes, never by tolerance.  The scalars of
-aof_bank_params hold values no stream has: a kernel that still reads them cannot pass."""
+aof_bank_params hold values no stream has: a kernel that still reads them cannot pass.  The rig: tests/bank_rig.py."""
 import ctypes as C
 from functools import partial
 
@@ -11,11 +11,11 @@ import pytest
 import bank_ref as ref
 import bank_streams_ref as sref
 from bank_ref import FX, FY
-from test_gpu_bank import params_of, same_records
+from bank_rig import EINVAL, BankRig, params_of, same_records, untouched
+from bank_rig import time_limit   # (this module's fixture too: every test under a limit of its own)
 
 pytestmark = pytest.mark.gpu
 
-EINVAL = -22
 # what bp carries while an array is bound: checked as ever (focal lengths > 0), used by nobody
 UNUSED = dict(focal_x=51.5, focal_y=49.25, output_rate=7, offset_timestamp_usec=31337, system_id=77, component_id=78, first_seq=79)
 SENSOR = (96, 80)   # sensor frames of the camera forms: centre-cropped to 64 x 64
@@ -39,11 +39,6 @@ def put(t, s, rec):
     t[s].copy_(up(t.device, np.frombuffer(np.asarray(rec).tobytes(), np.uint8)))
 
 
-def wires(frames, lens):
-    w, n = frames.cpu().numpy().reshape(-1, 56), lens.cpu().numpy().reshape(-1)
-    return [bytes(w[i, :n[i]]) for i in range(len(n))]
-
-
 def sensors_of(frames, seed):
     """Sensor frames [.., 80, 96] of noise whose centre crop is frames [.., 64, 64]."""
     cw, ch = SENSOR
@@ -54,50 +49,22 @@ def sensors_of(frames, seed):
     return out
 
 
-class Rig:
-    """One bank on an engine; tick() / burst() push rounds of a Run and return host copies of every output."""
+class NoiseSensors:
+    """The sensor frames of a run for BankRig: tick k's are sensors_of(run.frames[k], seed + k)."""
+    cam_w, cam_h = SENSOR
 
-    def __init__(self, aof, eng, bp, dev, camera=False):
-        self.aof, self.eng, self.dev, self.camera = aof, eng, dev, camera
-        cam = aof.bank_camera_params(SENSOR[0], SENSOR[1], 64, 64, exposure_interval_us=30000) if camera else None
-        self.bank = eng.bank_create(bp, dev, camera=cam)
+    def __init__(self, run, seed):
+        self.run, self.seed = run, seed
 
-    def _out(self, out, K):
-        import torch
-        torch.cuda.synchronize()
-        S = self.bank.n_streams
-        recs = out["records"].cpu().numpy().view(self.aof.TICK_DTYPE).reshape(K, S)
-        d = dict(records=recs, wire=wires(out["frames"], out["lengths"]), lens=out["lengths"].cpu().numpy().reshape(K, S))
-        if out.get("exposure") is not None:
-            d["exposure"] = out["exposure"].cpu().numpy().tobytes()
-        return d
+    def sensor(self, k):
+        return sensors_of(self.run.frames[k], self.seed + k)
 
-    def tick(self, run, k, seed=0):
-        dev, e = self.dev, self.eng
-        args = (up(dev, run.times[k]), up(dev, run.active[k]), up(dev, run.gyro[k]))
-        if self.camera:
-            out = e.bank_push_camera(self.bank, up(dev, sensors_of(run.frames[k], seed + k)), *args, mavlink=True)
-        else:
-            r, f, n = e.bank_push(self.bank, up(dev, run.frames[k]), *args, mavlink=True)
-            out = dict(records=r, frames=f, lengths=n)
-        return self._out(out, 1)
 
-    def burst(self, run, k0, K, seed=0):
-        dev, e = self.dev, self.eng
-        rounds = slice(k0, k0 + K)
-        count = run.active[rounds].sum(axis=0).astype(np.uint8)
-        assert (run.active[rounds].cumprod(axis=0).sum(axis=0) == count).all(), "a burst's frames are a stream's first rounds"
-        args = (up(dev, run.times[rounds]), up(dev, count), up(dev, run.gyro[rounds]))
-        if self.camera:
-            sens = np.stack([sensors_of(run.frames[k], seed + k) for k in range(k0, k0 + K)])
-            out = e.bank_push_camera_burst(self.bank, K, up(dev, sens), *args, mavlink=True)
-        else:
-            r, f, n = e.bank_push_burst(self.bank, K, up(dev, run.frames[rounds]), *args, mavlink=True)
-            out = dict(records=r, frames=f, lengths=n)
-        return self._out(out, K)
-
-    def bank_bytes(self):
-        return self.bank.frames_bytes().tobytes(), self.bank.state_bytes().tobytes()
+def counts_of(run, K):
+    """count [T // K, S] of a burstable run's bursts of K rounds."""
+    a = run.active[:run.T - run.T % K].reshape(-1, K, run.S)
+    assert (a.cumprod(axis=1).sum(axis=1) == a.sum(axis=1)).all(), "a burst's frames are a stream's first rounds"
+    return a.sum(axis=1).astype(np.uint8)
 
 
 def burstable(run, K):
@@ -124,8 +91,8 @@ def expected(aof, orc, synth, cfg, S, T, seed, K=None, rows=None):
 
 
 def check_tick(got, want, wire, k, what):
-    same_records(got["records"][0], want[k], k, what)
-    assert got["wire"] == wire[k], (what, "wire", k, [s for s in range(len(wire[k])) if got["wire"][s] != wire[k][s]][:4])
+    same_records(got.recs, want[k], k, what)
+    assert got.wire == wire[k], (what, "wire", k, [s for s in range(len(wire[k])) if got.wire[s] != wire[k][s]][:4])
 
 
 # ---- 1. oracle parity ----
@@ -139,12 +106,12 @@ def test_six_different_cameras_equal_one_oracle_chain_each(aof, orc, synth, gpu_
     p, run, want, wire = expected(aof, orc, synth, cfg, S, T, seed)
     eng = aof.FlowEngine(p, 0)
     eng.set_bank_path(path)
-    rig = Rig(aof, eng, aof.bank_params(S, **UNUSED), gpu_device)
+    rig = BankRig(aof, eng, run, aof.bank_params(S, **UNUSED), gpu_device)
     bind(aof, eng, gpu_device, sref.records(aof, S))
     px = p.width * p.height
     for k in range(T):
         before_frames, before_state = rig.bank.frames_bytes(), rig.bank.state_bytes()
-        check_tick(rig.tick(run, k), want, wire, k, "oracle")
+        check_tick(rig.push(k), want, wire, k, "oracle")
         after_frames, after_state = rig.bank.frames_bytes(), rig.bank.state_bytes()
         for s in range(S):
             slot = slice(s * px, (s + 1) * px)
@@ -170,22 +137,28 @@ def test_an_array_of_from_params_records_changes_no_byte(aof, synth, gpu_device,
     bp = aof.bank_params(S, 180.5, 222.25, 15, 5_000_000, 3, 42, 251)
     eng = aof.FlowEngine(p, 0)
     eng.set_bank_path(path)
-    a, b = Rig(aof, eng, bp, gpu_device, camera), Rig(aof, eng, bp, gpu_device, camera)
+    cam = (aof.bank_camera_params(SENSOR[0], SENSOR[1], 64, 64, exposure_interval_us=30000), NoiseSensors(run, 7)) if camera else None
+    a, b = BankRig(aof, eng, run, bp, gpu_device, camera=cam), BankRig(aof, eng, run, bp, gpu_device, camera=cam)
+    bursts = {rig: BankRig(aof, eng, run, bp, gpu_device, K=K, camera=cam, bank=rig.bank) for rig in (a, b)}
+    given = counts_of(run, K)
     table = up(gpu_device, aof.bank_stream_from_params(bp, S).view(np.uint8).reshape(S, 32))
     published = held = 0
     for step in [("tick", k) for k in range(6)] + [("burst", 6), ("burst", 9)]:
         outs = []
         for rig, bound in ((a, True), (b, False)):
             eng.set_bank_streams(table if bound else None)
-            outs.append(rig.tick(run, step[1], 7) if step[0] == "tick" else rig.burst(run, step[1], K, 7))
-        ga, gb = outs
-        assert ga["records"].tobytes() == gb["records"].tobytes(), step
-        assert ga["wire"] == gb["wire"] and ga["lens"].tobytes() == gb["lens"].tobytes(), step
-        assert ga.get("exposure") == gb.get("exposure") and (ga.get("exposure") is not None) == camera, step
+            used = rig if step[0] == "tick" else bursts[rig]
+            ticks = [used.push(step[1])] if step[0] == "tick" else used.push(step[1] // K, given)
+            outs.append((ticks, used.raw()))                  # (raw: the lengths and the exposure records among them)
+        (ga, raw_a), (gb, raw_b) = outs
+        recs = np.stack([t.recs for t in ga])
+        assert recs.tobytes() == np.stack([t.recs for t in gb]).tobytes(), step
+        assert [t.wire for t in ga] == [t.wire for t in gb] and raw_a == raw_b, step
+        assert all(untouched(t.exposure) != camera for t in ga), step
         assert a.bank_bytes() == b.bank_bytes(), step
-        published += int((ga["records"]["quality"] >= 0).sum())
-        held += int((ga["records"]["quality"] == aof.TICK_HELD).sum())
-        assert sum(1 for w in ga["wire"] if w) == int((ga["records"]["quality"] >= 0).sum()), "every published record is sent"
+        published += int((recs["quality"] >= 0).sum())
+        held += int((recs["quality"] == aof.TICK_HELD).sum())
+        assert sum(1 for t in ga for w in t.wire if w) == int((recs["quality"] >= 0).sum()), "every published record is sent"
     assert published > S and held > S, (published, held)
     eng.close()
 
@@ -201,20 +174,21 @@ def test_a_burst_reads_the_record_of_the_stream_not_of_the_round(aof, orc, synth
     p, run, want, wire = expected(aof, orc, synth, "px4-64", S, T, 91, K=K)
     eng = aof.FlowEngine(p, 0)
     eng.set_bank_path(path)
-    a, b = Rig(aof, eng, aof.bank_params(S, **UNUSED), gpu_device), Rig(aof, eng, aof.bank_params(S, **UNUSED), gpu_device)
+    a, b = BankRig(aof, eng, run, aof.bank_params(S, **UNUSED), gpu_device, K=K), BankRig(aof, eng, run, aof.bank_params(S, **UNUSED), gpu_device)
+    given = counts_of(run, K)
     recs = sref.records(aof, K * S, [sref.TABLE[s] for s in range(S)] + [sref.DECOY] * ((K - 1) * S))
     bind(aof, eng, gpu_device, recs, n_streams=S)
     later = 0
     for k0 in range(0, T, K):
-        got = a.burst(run, k0, K)
+        got = a.push(k0 // K, given)
         for j in range(K):
-            one = b.tick(run, k0 + j)
-            assert got["records"][j].tobytes() == one["records"][0].tobytes(), ("twin", k0, j)
-            assert got["wire"][j * S:(j + 1) * S] == one["wire"], ("twin wire", k0, j)
-            same_records(got["records"][j], want[k0 + j], k0 + j, "oracle")
-            assert got["wire"][j * S:(j + 1) * S] == wire[k0 + j], ("oracle wire", k0, j)
+            one = b.push(k0 + j)
+            assert got[j].recs.tobytes() == one.recs.tobytes(), ("twin", k0, j)
+            assert got[j].wire == one.wire, ("twin wire", k0, j)
+            same_records(got[j].recs, want[k0 + j], k0 + j, "oracle")
+            assert got[j].wire == wire[k0 + j], ("oracle wire", k0, j)
             if j:
-                later += int((got["records"][j]["quality"] >= 0).sum())
+                later += int((got[j].recs["quality"] >= 0).sum())
         assert a.bank_bytes() == b.bank_bytes(), k0
     assert later > S, "records published in rounds behind the first: where a round-indexed read would go wrong"
     eng.close()
@@ -228,10 +202,10 @@ def test_seventy_streams_cycle_through_the_table(aof, orc, synth, gpu_device, pa
     p, run, want, wire = expected(aof, orc, synth, "px4-64", S, T, 101)
     eng = aof.FlowEngine(p, 0)
     eng.set_bank_path(path)
-    rig = Rig(aof, eng, aof.bank_params(S, **UNUSED), gpu_device)
+    rig = BankRig(aof, eng, run, aof.bank_params(S, **UNUSED), gpu_device)
     bind(aof, eng, gpu_device, sref.records(aof, S))
     for k in range(T):
-        check_tick(rig.tick(run, k), want, wire, k, "oracle")
+        check_tick(rig.push(k), want, wire, k, "oracle")
     pub, held, _ = ref.census(want)
     assert held.sum() > 0 and (pub > 1).any() and sum(1 for w in wire[T - 1] if w) > 6
     eng.close()
@@ -254,7 +228,7 @@ def test_a_record_rewritten_between_ticks_applies_from_that_tick(aof, orc, synth
     want_b, wire_b = ref.expected(ref.Run(run.frames[:, 2:3], run.times[:, 2:3], run.gyro[:, 2:3], run.active[:, 2:3]), [chain_b])
     eng = aof.FlowEngine(p, 0)
     eng.set_bank_path(path)
-    rig = Rig(aof, eng, aof.bank_params(S, **UNUSED), gpu_device)
+    rig = BankRig(aof, eng, run, aof.bank_params(S, **UNUSED), gpu_device)
     table = bind(aof, eng, gpu_device, sref.records(aof, S))
     seqs = []
     for k in range(T):
@@ -263,12 +237,12 @@ def test_a_record_rewritten_between_ticks_applies_from_that_tick(aof, orc, synth
         w_k, x_k = want[k].copy(), list(wire[k])
         if k >= CHANGE:
             w_k[2], x_k[2] = want_b[k, 0], wire_b[k][0]
-        got = rig.tick(run, k)
-        same_records(got["records"][0], w_k, k, "oracle")
-        assert got["wire"] == x_k, (k, [s for s in range(S) if got["wire"][s] != x_k[s]])
-        if k >= CHANGE and got["wire"][2]:
-            assert got["wire"][2][5:7] == bytes([42, 7])
-            seqs.append(got["wire"][2][4])
+        got = rig.push(k)
+        same_records(got.recs, w_k, k, "oracle")
+        assert got.wire == x_k, (k, [s for s in range(S) if got.wire[s] != x_k[s]])
+        if k >= CHANGE and got.wire[2]:
+            assert got.wire[2][5:7] == bytes([42, 7])
+            seqs.append(got.wire[2][4])
     assert (want[CHANGE:, 2]["flow_x"] != want_b[CHANGE:, 0]["flow_x"]).any(), "the two focal lengths give other angles"
     assert before > 0 and len(seqs) > 8 and seqs[:8] == [250, 251, 252, 253, 254, 255, 0, 1]
     assert 255 in seqs and 0 in seqs, seqs
@@ -290,38 +264,30 @@ def test_a_captured_tick_uses_what_the_array_holds_at_replay(aof, synth, gpu_dev
     eng.set_bank_path(1)
     table = bind(aof, eng, gpu_device, first)
     rewrite = lambda recs: table.copy_(up(gpu_device, recs.view(np.uint8).reshape(S, 32)))
-    eager = Rig(aof, eng, aof.bank_params(S, **UNUSED), gpu_device)
+    eager = BankRig(aof, eng, run, aof.bank_params(S, **UNUSED), gpu_device)
     outs = []
     for k in range(T):
         if k == CHANGE:
             rewrite(second)
-        outs.append(eager.tick(run, k))
+        outs.append(eager.push(k))
     rewrite(first)
-    rig = Rig(aof, eng, aof.bank_params(S, **UNUSED), gpu_device)
-    dev = gpu_device
-    frames, times = torch.zeros((S, 64, 64), dtype=torch.uint8, device=dev), torch.zeros(S, dtype=torch.int64, device=dev)
-    active, gyro = torch.zeros(S, dtype=torch.uint8, device=dev), torch.zeros((S, 4), dtype=torch.float32, device=dev)
-    records, wire = torch.zeros((S, 48), dtype=torch.uint8, device=dev), torch.zeros((S, 56), dtype=torch.uint8, device=dev)
-    lens = torch.zeros(S, dtype=torch.uint8, device=dev)
-    enqueue = lambda: eng.bank_push(rig.bank, frames, times, active, gyro, mavlink=True, records=records, out_frames=wire, out_lengths=lens)
-    enqueue()                                    # (the tick kernel has run once before the capture)
+    rig = BankRig(aof, eng, run, aof.bank_params(S, **UNUSED), gpu_device)
+    rig.push(0)                                  # (the tick kernel has run once before the capture)
     eng.bank_reset(rig.bank)
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
-        enqueue()
+        rig.enqueue()
     new_ids = 0
     for k in range(T):
         if k == CHANGE:
             rewrite(second)
-        for t, a in ((frames, run.frames[k]), (times, run.times[k]), (active, run.active[k]), (gyro, run.gyro[k])):
-            t.copy_(up(dev, a))
-        wire.zero_()
+        rig.load(k)
         g.replay()
-        torch.cuda.synchronize()
-        assert records.cpu().numpy().tobytes() == outs[k]["records"].tobytes(), k
-        sent = wires(wire, lens)
-        assert sent == outs[k]["wire"], k
+        got = rig.read()
+        assert got.recs.tobytes() == outs[k].recs.tobytes(), k
+        sent = got.wire
+        assert sent == outs[k].wire, k
         for s, f in enumerate(sent):
             if f:
                 want_id = bytes((second if k >= CHANGE else first)[s].tobytes()[12:14])
@@ -397,9 +363,9 @@ def test_a_binding_of_another_stream_count_is_refused_and_unbinding_restores_the
     run = ref.make_run(synth, 64, 64, S, 6, 141)
     bp = aof.bank_params(S, FX, FY, 15, 5_000_000, 1, 100, 3)
     eng = aof.FlowEngine(p, 0)
-    a, b = Rig(aof, eng, bp, gpu_device), Rig(aof, eng, bp, gpu_device)     # b: never sees a binding
+    a, b = BankRig(aof, eng, run, bp, gpu_device), BankRig(aof, eng, run, bp, gpu_device)     # b: never sees a binding
     for k in range(3):
-        a.tick(run, k), b.tick(run, k)
+        a.push(k), b.push(k)
     big = torch.zeros((S + 2) * 32 + 16, dtype=torch.uint8, device=gpu_device)
     base = big.data_ptr()
     assert base % 16 == 0
@@ -407,7 +373,7 @@ def test_a_binding_of_another_stream_count_is_refused_and_unbinding_restores_the
     assert set_streams(eng._ctx, base + 8, S) == EINVAL and b"16-byte" in aof.lib.aof_last_error(eng._ctx), "a misaligned array"
     assert set_streams(eng._ctx, base, 0) == EINVAL and set_streams(eng._ctx, base, -1) == EINVAL
     # (nothing is bound yet: the refused calls left the context as it was)
-    assert a.tick(run, 3)["records"].tobytes() == b.tick(run, 3)["records"].tobytes()
+    assert a.push(3).recs.tobytes() == b.push(3).recs.tobytes()
     assert set_streams(eng._ctx, base, S + 1) == 0                          # an array for six streams
     snapshot = a.bank.buffer.clone()
     stream = torch.cuda.current_stream().cuda_stream
@@ -434,18 +400,18 @@ def test_a_binding_of_another_stream_count_is_refused_and_unbinding_restores_the
     for t in (recs, wire, lens, state):
         assert bool((t == 0xEE).all()), "a refused call writes nothing"
     # an array of the right count is accepted: one heterogeneous tick on a bank of its own carries the table's identities
-    c = Rig(aof, eng, bp, gpu_device)
+    c = BankRig(aof, eng, run, bp, gpu_device)
     bind(aof, eng, gpu_device, sref.records(aof, S))
-    first = c.tick(run, 4)                                                  # (every stream's first frame: published)
+    first = c.push(4)                                                       # (every stream's first frame: published)
     for s in range(S):
         if run.active[4, s]:
-            assert (first["wire"][s][5:7] == bytes(sref.TABLE[s][4:6])) if sref.TABLE[s][3] else first["wire"][s] == b"", s
-    assert sum(1 for w in first["wire"] if w) >= 2
+            assert (first.wire[s][5:7] == bytes(sref.TABLE[s][4:6])) if sref.TABLE[s][3] else first.wire[s] == b"", s
+    assert sum(1 for w in first.wire if w) >= 2
     # unbound again: the scalars, byte for byte what the bank without a binding gives
     eng.set_bank_streams(None)
     for k in (4, 5):
-        ga, gb = a.tick(run, k), b.tick(run, k)
-        assert ga["records"].tobytes() == gb["records"].tobytes() and ga["wire"] == gb["wire"], k
+        ga, gb = a.push(k), b.push(k)
+        assert ga.recs.tobytes() == gb.recs.tobytes() and ga.wire == gb.wire, k
     assert a.bank_bytes() == b.bank_bytes()
     eng.close()
 

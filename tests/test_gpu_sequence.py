@@ -4,13 +4,14 @@ de-rotation -> OPTICAL_FLOW_RAD frames in ONE enqueue, against the reference's o
   A  the C++ facade driven frame by frame (crop on the host, OpticalFlowPX4 / OpticalFlowOpenCV::calcFlow with
      the 32-bit time stamp, the negative-return gate, fillOpticalFlowRad + packOpticalFlowRad) -- the GPU's
      per-call path;
-  B  the CPU oracle's calcFlow chain and the independent MAVLink serializer of tests/test_mavlink.py.
+  B  the CPU oracle's calcFlow chain and the independent MAVLink serializer of tests/mavlink_model.py.
 The bar: records and wire frames byte-identical to both ("parity unpinned": the oracle is this repo's
 restatement; upstream PX4 / mavlink_c sources are absent from the reference mount)."""
 import numpy as np
 import pytest
 
-from test_mavlink import py_frame
+from mavlink_model import py_frame
+from sequence_ref import crop_of, replay
 
 pytestmark = pytest.mark.gpu
 
@@ -25,32 +26,6 @@ def make_inputs(synth, cam_w, cam_h, n, seed, times):
     dt = np.diff(np.concatenate([[0], times])).astype(np.float64) * 1e-6
     gyro[:, 3] = np.clip(dt, 0, 1).astype(np.float32)
     return frames, gyro
-
-
-def crop_of(frames, cw, ch):
-    n, H, W = frames.shape
-    x0, y0 = W // 2 - cw // 2, H // 2 - ch // 2            # mainloop.cpp:295-297
-    return np.ascontiguousarray(frames[:, y0:y0 + ch, x0:x0 + cw])
-
-
-def replay(calc_flow, cropped, times, gyro, offset, first_seq, pack):
-    """mainloop.cpp:322-373 around a calcFlow implementation: the negative-return gate, the gyro taken and
-    zeroed with every published flow, the field mapping and the frame."""
-    recs, wire = [], []
-    g = np.zeros(3, np.float64)
-    seq = first_seq
-    for k in range(len(times)):
-        g += gyro[k, :3].astype(np.float64)                 # integrated since the last message (:383-405)
-        q, dt, ax, ay = calc_flow(cropped[k], int(times[k]) & 0xFFFFFFFF)
-        if q < 0:                                           # :327-331
-            continue
-        taken, g = g.copy(), np.zeros(3, np.float64)        # :333-334
-        recs.append((k, q, dt, np.float32(ax), np.float32(ay), np.float32(taken[0]), np.float32(taken[1]), np.float32(taken[2])))
-        if offset:                                          # :353-357
-            wire.append(pack(offset, int(times[k]), dt, float(np.float32(ax)), float(np.float32(ay)),
-                             tuple(float(v) for v in taken), q, seq & 0xFF))
-            seq += 1
-    return recs, wire
 
 
 CASES = [

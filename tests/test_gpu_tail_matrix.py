@@ -2,18 +2,17 @@
 forms, one-launch and composed -- on the cases of tests/tail_ref.py: focal lengths, output rates and motions that take
 aof_atan2f (include/aof_math.h) through its argument reduction, its lo == hi case and its swap with both signs, and the
 limiter through windows of 75 frames and more.  Records and MAVLink frames byte for byte against the CPU oracle's chain
-with the independent serializer of tests/test_mavlink.py, for two cases also against the C++ facade driven frame by frame;
+with the independent serializer of tests/mavlink_model.py, for two cases also against the C++ facade driven frame by frame;
 the de-rotated flows against orc.derotate at the case's focal lengths.  Every case first asserts, on the oracle's
 records and before the device runs, that its input reaches the branches it is there for."""
 import numpy as np
 import pytest
 
-import bank_ref as ref
+import bank_camera_ref as cref
 import tail_ref as tr
-import test_gpu_bank as tb
-import test_gpu_bank_burst as tbb
-import test_gpu_bank_camera as tbc
-from test_gpu_sequence import replay
+from bank_cases import Case, run_camera_case, run_case
+from bank_rig import time_limit   # (this module's fixture too: every test under a limit of its own)
+from sequence_ref import replay
 
 pytestmark = pytest.mark.gpu
 
@@ -86,19 +85,19 @@ def test_bank_tick(aof, orc, synth, gpu_device, case, path):
     once per tick; on path 1 the facade cases also against one facade object per stream."""
     o = bank_oracle(aof, orc, synth, case)
     p = tr.params_of(aof, case["cfg"])
-    want = tb.run_case(aof, orc, synth, gpu_device, case["cfg"], case["S"], case["T"], case["seed"], rate=case["rate"], path=path,
-                       facade=case["S"] if case.get("facade") and path == 1 else 0, fx=case["fx"], fy=case["fy"],
-                       source=tr.stream_source(case, p.width, p.height))
+    want = run_case(aof, orc, synth, gpu_device, case["cfg"], case["S"], case["T"], case["seed"], rate=case["rate"], path=path,
+                    facade=case["S"] if case.get("facade") and path == 1 else 0, fx=case["fx"], fy=case["fy"],
+                    source=tr.stream_source(case, p.width, p.height))
     assert want.tobytes() == o["want"].tobytes(), "the run that was compared is the run of the census"
 
 
 def burst_case(aof, orc, synth, case, o, path, camera):
     run = o["run"]
     b, counts, given = tr.burst_run(run)
-    c = tbb.Case(aof, orc, synth, case["cfg"], tr.K_BURST, S=run.S, B=b.T // tr.K_BURST, seed=case["seed"], camera=camera,
-                 rate=case["rate"], path=path, fx=case["fx"], fy=case["fy"], burst_run=(b, counts, given),
-                 sensor=SENSOR if camera else None, skew=SKEW if camera else 0,
-                 needs=("first-frame-then-more", "count0") + (("crop-origin-on-an-odd-byte",) if camera else ()))
+    c = Case(aof, orc, synth, case["cfg"], tr.K_BURST, S=run.S, B=b.T // tr.K_BURST, seed=case["seed"], camera=camera,
+             rate=case["rate"], path=path, fx=case["fx"], fy=case["fy"], burst_run=(b, counts, given),
+             sensor=SENSOR if camera else None, skew=SKEW if camera else 0,
+             needs=("first-frame-then-more", "count0") + (("crop-origin-on-an-odd-byte",) if camera else ()))
     for s in range(run.S):      # stream by stream the chain saw what the census saw, and left the same records
         assert c.want[b.active[:, s] == 1, s].tobytes() == o["want"][run.active[:, s] == 1, s].tobytes(), s
     return c
@@ -130,11 +129,11 @@ def test_camera_tick(aof, orc, synth, gpu_device, case, path):
     (orc.derotate at the case's focal lengths) against the oracle chain, tick by tick."""
     o = bank_oracle(aof, orc, synth, case)
     p = tr.params_of(aof, case["cfg"])
-    x0, y0 = tbc.cref.crop_origin(SENSOR[0], SENSOR[1], p.width, p.height)
+    x0, y0 = cref.crop_origin(SENSOR[0], SENSOR[1], p.width, p.height)
     assert (y0 * SENSOR[0] + x0 + SKEW) % 2 == 1
-    want, _ = tbc.run_case(aof, orc, synth, gpu_device, case["cfg"], case["S"], case["T"], case["seed"], sensor=SENSOR,
-                           rate=case["rate"], path=path, skew=SKEW, fx=case["fx"], fy=case["fy"],
-                           source=tr.stream_source(case, p.width, p.height), patches=False)
+    want, _ = run_camera_case(aof, orc, synth, gpu_device, case["cfg"], case["S"], case["T"], case["seed"], sensor=SENSOR,
+                              rate=case["rate"], path=path, skew=SKEW, fx=case["fx"], fy=case["fy"],
+                              source=tr.stream_source(case, p.width, p.height), patches=False)
     assert want.tobytes() == o["want"].tobytes(), "the run that was compared is the run of the census"
 
 

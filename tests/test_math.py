@@ -6,13 +6,7 @@ import math
 
 import numpy as np
 
-
-def ulp_distance(a, b):
-    ia = np.float32(a).view(np.int32).astype(np.int64)
-    ib = np.float32(b).view(np.int32).astype(np.int64)
-    ia = np.where(ia < 0, np.int64(-2 ** 31) - ia, ia)
-    ib = np.where(ib < 0, np.int64(-2 ** 31) - ib, ib)
-    return int(abs(int(ia) - int(ib)))
+from npref import ulp_distance
 
 
 def test_angle_matches_the_oracle_restatement_and_libm_within_one_ulp(aof, orc):

@@ -2,7 +2,7 @@
 /root/reference/src/mainloop.cpp:359-371 and the MAVLink 2 frame of
 src/mavlink_tcp.cpp:142-162.  modules/mavlink_c is absent from the reference mount, so
 the wire format is checked against an independent restatement of the public MAVLink 2
-serialization rules written here (struct packing + CRC-16/MCRF4XX), not against
+serialization rules in tests/mavlink_model.py (struct packing + CRC-16/MCRF4XX), not against
 reference bytes."""
 import os
 import struct
@@ -10,25 +10,7 @@ import struct
 import numpy as np
 import pytest
 
-
-def x25(data, crc=0xFFFF):
-    for b in data:
-        tmp = (b ^ (crc & 0xFF)) & 0xFF
-        tmp = (tmp ^ (tmp << 4)) & 0xFF
-        crc = ((crc >> 8) ^ (tmp << 8) ^ (tmp << 3) ^ (tmp >> 4)) & 0xFFFF
-    return crc
-
-
-def py_frame(offset_ts, img_time_us, dt_us, fx, fy, gyro, quality, seq):
-    payload = struct.pack("<QIfffffIfhBB", offset_ts + img_time_us, dt_us & 0xFFFFFFFF, fx, fy,
-                          np.float32(-gyro[1]), np.float32(gyro[0]), np.float32(gyro[2]), 0, -1.0, 0, 0,
-                          quality & 0xFF)
-    assert len(payload) == 44
-    while len(payload) > 1 and payload[-1] == 0:
-        payload = payload[:-1]
-    hdr = bytes([len(payload), 0, 0, seq, 1, 100, 106, 0, 0])
-    crc = x25(bytes([138]), x25(hdr + payload))
-    return b"\xfd" + hdr + payload + struct.pack("<H", crc)
+from mavlink_model import py_frame, x25
 
 
 @pytest.fixture(scope="module")

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import tail_ref as tr
-from test_math import ulp_distance
+from npref import ulp_distance
 
 F32 = np.float32
 

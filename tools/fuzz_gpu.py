@@ -201,9 +201,9 @@ def sequence(n_cases, seed0):
     """aof_sequence_device over random recordings: random small configurations (one and two levels, sparse and
     dense grids), output rates from "every frame" to slower than the recording, time stamps with jitter, stalls
     and 32-bit wrap-arounds, dark stretches, gyro increments -- records and MAVLink frames against the oracle's
-    calcFlow chain and the independent serializer of tests/test_mavlink.py."""
+    calcFlow chain and the independent serializer of tests/mavlink_model.py."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from test_mavlink import py_frame
+    from mavlink_model import py_frame, x25
     dev = torch.device("cuda:0")
     t0 = time.time()
     done = 0
@@ -279,7 +279,6 @@ def sequence(n_cases, seed0):
                                        tuple(float(v) for v in taken), q, (first_seq + m) & 0xFF))
                 # (py_frame writes the reference's ids 1 / 100: patch ours in and redo the checksum)
                 f[5], f[6] = sid, cid
-                from test_mavlink import x25
                 crc = x25(bytes([138]), x25(bytes(f[1:-2])))
                 f[-2], f[-1] = crc & 0xFF, crc >> 8
                 if out["mavlink"][m] != bytes(f):
