@@ -124,12 +124,6 @@ private:
 	OpticalFlowBank &operator=(const OpticalFlowBank &);
 	int fail(int code, const char *what);
 	int refuse(int code, const char *what);
-	bool waitIdle();
-	int collect();
-	int takeImu();
-	int receive();
-	int syncStreams();
-	aof_bank_stream *streamRecord(int stream);
 
 	int image_width, image_height, n_streams;
 	struct Impl;

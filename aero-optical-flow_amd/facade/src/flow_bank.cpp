@@ -1,16 +1,8 @@
-// OpticalFlowBank (flow_bank.hpp): S cameras per push() through the stream bank of the C ABI
-// (aof_bank_push_device) and its outbox (aof_bank_collect_device) in pinned host memory.  A push is one
-// host-to-device copy of the pinned staging block (frames, times, masks, gyro), the tick, the collect
-// launch, and a bounded poll of the outbox's tag: no stream synchronisation anywhere.  pushCamera() is the same
-// on raw sensor frames (aof_bank_push_camera_device), with the auto-exposure controller
-// (aof_bank_exposure_control_device) between the tick and the collect launch: its commands land in pinned
-// memory in front of the tag.  With enableImu() the tick leaves records only and the IMU call
-// (aof_bank_imu_device) behind it takes the samples pushImu() queued, completes the records in place and packs the
-// frames, so that the collect launch lists only what the reference would have sent.  With enableMavlinkRx() the
-// samples come from the device as well: the bytes pushMavlink() queued go over in one copy, and the receive launch
-// (aof_bank_mavlink_rx_device) in front of the tick parses them into the sample block the IMU call reads.
-// The setStream...() calls write a pinned shadow array of per-stream records (aof_bank_stream); the next push copies
-// it to the device on the object's stream and, the first time, binds it to the context (aof_set_bank_streams).
+// OpticalFlowBank (flow_bank.hpp): S cameras per push() through the stream bank of the C ABI and its outbox
+// (aof_bank_collect_device) in pinned host memory.  Impl::tick() is one push, plain or on sensor frames, in every form:
+// its body is the order of the copies and launches on the object's stream, closed by a bounded poll of the outbox's tag
+// -- no stream synchronisation anywhere.  Impl::startOver() is the one way streams start over.  Every byte of device and
+// pinned memory is taken through Impl::mem, which the destructor releases in one loop.
 #include <cerrno>
 #include <chrono>
 #include <cstdio>
@@ -36,50 +28,121 @@ double secondsSince(std::chrono::steady_clock::time_point t0)
 	return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
+// Every allocation of one object, recorded where it is made: release() frees them all, the newest first.
+struct Allocations {
+	enum Kind { kDevice, kPinned, kOutbox };   // hipMalloc, hipHostMalloc, aof_outbox_alloc_host: each has its own free
+	struct { void *p; Kind kind; } list[24];   // (20 with every form on, 21 inside enableCamera())
+	int n;
+
+	bool get(void **p, size_t bytes, Kind kind)
+	{
+		*p = NULL;
+		const bool ok = n < (int)(sizeof(list) / sizeof(list[0])) &&
+				(kind == kDevice   ? hipMalloc(p, bytes) == hipSuccess
+				 : kind == kPinned ? hipHostMalloc(p, bytes, hipHostMallocDefault) == hipSuccess
+						   : aof_outbox_alloc_host(bytes, p) == 0);
+		if (!ok) return false;
+		list[n].p = *p;
+		list[n++].kind = kind;
+		return true;
+	}
+	void freeAt(int i)
+	{
+		if (list[i].kind == kOutbox) aof_outbox_free_host(list[i].p);
+		else if (list[i].kind == kPinned) (void)hipHostFree(list[i].p);
+		else (void)hipFree(list[i].p);
+	}
+	void drop(void *p)   // one of them ahead of the others
+	{
+		for (int i = 0; i < n; i++) {
+			if (list[i].p != p) continue;
+			freeAt(i);
+			list[i] = list[--n];
+			return;
+		}
+	}
+	void release()
+	{
+		while (n > 0) freeAt(--n);
+	}
+};
+
+// A staging block: the same layout in pinned host memory (zeroed) and on the device.
+struct Staged {
+	uint8_t *h, *d;
+	size_t bytes;
+
+	bool alloc(Allocations &mem, size_t n)
+	{
+		bytes = n;
+		if (!mem.get((void **)&h, n, Allocations::kPinned) || !mem.get((void **)&d, n, Allocations::kDevice)) return false;
+		std::memset(h, 0, n);
+		return true;
+	}
+	bool upload(hipStream_t stream, size_t offset, size_t n) const
+	{
+		return hipMemcpyAsync(d + offset, h + offset, n, hipMemcpyHostToDevice, stream) == hipSuccess;
+	}
+};
+
 }  // namespace
 
 struct OpticalFlowBank::Impl {
+	OpticalFlowBank *self;   // (for fail())
+	size_t S;                // n_streams
 	aof_ctx *ctx;
 	aof_bank_params bp;
 	hipStream_t stream;
-	// one staging block, the same layout on both sides: frames, times, gyro, masks
-	uint8_t *h_stage, *d_stage;
-	size_t stage_bytes, off_times, off_gyro, off_active;
+	Allocations mem;
+	Staged stage;            // frames, times, gyro, masks
+	size_t off_times, off_gyro, off_active;
 	void *d_bank;
 	size_t bank_bytes;
 	aof_tick_record *d_records;
 	uint8_t *d_mavlink, *d_lens;
-	uint8_t *outbox;   // pinned (aof_outbox_alloc_host): header, then n_streams entries
+	uint8_t *outbox;         // pinned (aof_outbox_alloc_host): header, then n_streams entries
 	size_t outbox_bytes;
 	uint64_t tag;
 	// the sensor-frame form (enableCamera): sensor frames staged apart from the block above
 	bool camera;
 	aof_bank_camera cam;
 	aof_exposure_control ec;
-	size_t sensor_bytes;               // all n_streams sensor frames
-	uint8_t *h_sensor, *d_sensor;
+	Staged sensor;           // all n_streams sensor frames
 	aof_exposure_record *d_exposure;
 	aof_exposure_state *d_exposure_state;
 	aof_exposure_command *commands;    // pinned (aof_outbox_alloc_host): [n_streams]
-	// the IMU form (enableImu): samples queued by pushImu() for the next tick, [slots][n_streams] and their counts
+	// the IMU form (enableImu): samples queued by pushImu() for the next tick
 	bool imu;
 	aof_imu_params ip;
 	uint64_t imu_offset0;
-	uint8_t *h_imu, *d_imu;            // one block on both sides: aof_imu_sample [slots][n_streams], then u8 [n_streams]
-	size_t imu_bytes, off_imu_counts;
+	Staged samples;          // aof_imu_sample [slots][n_streams], then their counts u8 [n_streams]
+	size_t off_imu_counts;
 	aof_imu_state *d_imu_state;
-	// the receive path (enableMavlinkRx): bytes queued by pushMavlink() for the next tick, [n_streams][max_bytes], and
-	// their lengths
+	// the receive path (enableMavlinkRx): bytes queued by pushMavlink() for the next tick
 	bool rx;
 	aof_mavlink_rx_params rp;
-	uint8_t *h_rx, *d_rx;              // one block on both sides: u8 [n_streams][max_bytes], then u16 [n_streams]
-	size_t rx_bytes, off_rx_len;
+	Staged bytes;            // u8 [n_streams][max_bytes], then their lengths u16 [n_streams]
+	size_t off_rx_len;
 	aof_mavlink_rx_state *d_rx_state;
 	// the per-stream form (setStream...()): the shadow records start from the constructor's values; nothing is copied or
 	// bound before the first setter
-	aof_bank_stream *h_streams, *d_streams;   // pinned, device: [n_streams]
+	Staged streams;          // aof_bank_stream [n_streams]
 	bool streams_used, streams_dirty, streams_bound;
-	bool streams_copying;              // a copy of the shadow is enqueued: it is through once collect() has seen the tick's tag
+	bool streams_copying;    // a copy of the shadow is enqueued: it is through once collect() has seen the tick's tag
+
+	int fail(int code, const char *what) { return self->fail(code, what); }
+	int failed(int rc) { return rc ? fail(rc, aof_last_error(ctx)) : 0; }   // of a call of the C ABI
+	uint8_t *imuCounts() { return samples.h + off_imu_counts; }
+	uint16_t *rxLengths() { return reinterpret_cast<uint16_t *>(bytes.h + off_rx_len); }
+	aof_bank_stream *shadow() { return reinterpret_cast<aof_bank_stream *>(streams.h); }
+	static aof_bank_stream *record(Impl *m, int s);
+	bool waitIdle();
+	int startOver(const uint8_t *mask, bool imu_too);
+	int tick(bool sensor_frames, const uint64_t *img_time_us, const uint8_t *active, const aof_gyro *gyro);
+	int receive();
+	int syncStreams();
+	int takeImu();
+	int collect();
 };
 
 OpticalFlowBank::OpticalFlowBank(float f_length_x, float f_length_y, int output_rate, int img_width, int img_height,
@@ -99,6 +162,7 @@ OpticalFlowBank::OpticalFlowBank(float f_length_x, float f_length_y, int output_
 		delete m;
 		return;
 	}
+	m->self = this;
 	std::memset(&m->bp, 0, sizeof(m->bp));
 	m->bp.n_streams = streams;
 	m->bp.focal_x = f_length_x;
@@ -106,11 +170,10 @@ OpticalFlowBank::OpticalFlowBank(float f_length_x, float f_length_y, int output_
 	m->bp.output_rate = output_rate;
 	m->bp.system_id = MAVLINK_SYSTEM_ID_DEFAULT;
 	m->bp.component_id = MAVLINK_COMPONENT_ID_CAMERA;
-	const size_t S = (size_t)streams, frame = (size_t)img_width * img_height;
+	const size_t S = m->S = (size_t)streams, frame = (size_t)img_width * img_height;
 	m->off_times = alignUp(S * frame, 256);
 	m->off_gyro = alignUp(m->off_times + S * sizeof(uint64_t), 256);
 	m->off_active = alignUp(m->off_gyro + S * sizeof(aof_gyro), 256);
-	m->stage_bytes = alignUp(m->off_active + S, 256);
 	struct aof_bank_layout L;
 	struct aof_outbox_layout O;
 	bool ok = aof_bank_layout(&p, &m->bp, &L) == 0 && aof_outbox_layout((uint32_t)streams, 0, &O) == 0;
@@ -118,15 +181,13 @@ OpticalFlowBank::OpticalFlowBank(float f_length_x, float f_length_y, int output_
 		m->bank_bytes = L.total_bytes;
 		m->outbox_bytes = O.total_bytes;
 		ok = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) == hipSuccess &&
-		     hipHostMalloc((void **)&m->h_stage, m->stage_bytes, hipHostMallocDefault) == hipSuccess &&
-		     hipMalloc((void **)&m->d_stage, m->stage_bytes) == hipSuccess &&
-		     hipMalloc(&m->d_bank, m->bank_bytes) == hipSuccess &&
-		     hipMalloc((void **)&m->d_records, S * sizeof(aof_tick_record)) == hipSuccess &&
-		     hipMalloc((void **)&m->d_mavlink, S * AOF_SEQ_FRAME_BYTES) == hipSuccess &&
-		     hipMalloc((void **)&m->d_lens, S) == hipSuccess &&
-		     hipHostMalloc((void **)&m->h_streams, S * sizeof(aof_bank_stream), hipHostMallocDefault) == hipSuccess &&
-		     hipMalloc((void **)&m->d_streams, S * sizeof(aof_bank_stream)) == hipSuccess &&
-		     aof_outbox_alloc_host(m->outbox_bytes, (void **)&m->outbox) == 0;
+		     m->stage.alloc(m->mem, alignUp(m->off_active + S, 256)) &&
+		     m->mem.get(&m->d_bank, m->bank_bytes, Allocations::kDevice) &&
+		     m->mem.get((void **)&m->d_records, S * sizeof(aof_tick_record), Allocations::kDevice) &&
+		     m->mem.get((void **)&m->d_mavlink, S * AOF_SEQ_FRAME_BYTES, Allocations::kDevice) &&
+		     m->mem.get((void **)&m->d_lens, S, Allocations::kDevice) &&
+		     m->streams.alloc(m->mem, S * sizeof(aof_bank_stream)) &&
+		     m->mem.get((void **)&m->outbox, m->outbox_bytes, Allocations::kOutbox);
 	}
 	_m = m;
 	if (!ok) {
@@ -134,13 +195,10 @@ OpticalFlowBank::OpticalFlowBank(float f_length_x, float f_length_y, int output_
 		return;
 	}
 	std::memset(m->outbox, 0, m->outbox_bytes);
-	for (size_t s = 0; s < S; s++) aof_bank_stream_from_params(&m->bp, &m->h_streams[s]);
+	for (size_t s = 0; s < S; s++) aof_bank_stream_from_params(&m->bp, &m->shadow()[s]);
 	std::snprintf(_err, sizeof(_err), "ok");
-	if (aof_bank_reset_device(m->ctx, &m->bp, NULL, m->d_bank, m->bank_bytes, m->stream)) {
-		fail(-EIO, aof_last_error(m->ctx));
-		return;
-	}
-	waitIdle();
+	if (m->startOver(NULL, false)) return;
+	m->waitIdle();
 }
 
 OpticalFlowBank::~OpticalFlowBank()
@@ -148,28 +206,8 @@ OpticalFlowBank::~OpticalFlowBank()
 	if (!_m) return;
 	Impl *m = _m;
 	// a bounded wait, as everywhere: memory a kernel may still write is leaked, not freed
-	const bool drained = !m->stream || waitIdle();
-	if (drained) {
-		if (m->d_rx_state) (void)hipFree(m->d_rx_state);
-		if (m->d_rx) (void)hipFree(m->d_rx);
-		if (m->h_rx) (void)hipHostFree(m->h_rx);
-		if (m->d_imu_state) (void)hipFree(m->d_imu_state);
-		if (m->d_imu) (void)hipFree(m->d_imu);
-		if (m->h_imu) (void)hipHostFree(m->h_imu);
-		if (m->commands) aof_outbox_free_host(m->commands);
-		if (m->d_exposure_state) (void)hipFree(m->d_exposure_state);
-		if (m->d_exposure) (void)hipFree(m->d_exposure);
-		if (m->d_sensor) (void)hipFree(m->d_sensor);
-		if (m->h_sensor) (void)hipHostFree(m->h_sensor);
-		if (m->outbox) aof_outbox_free_host(m->outbox);
-		if (m->d_streams) (void)hipFree(m->d_streams);
-		if (m->h_streams) (void)hipHostFree(m->h_streams);
-		if (m->d_lens) (void)hipFree(m->d_lens);
-		if (m->d_mavlink) (void)hipFree(m->d_mavlink);
-		if (m->d_records) (void)hipFree(m->d_records);
-		if (m->d_bank) (void)hipFree(m->d_bank);
-		if (m->d_stage) (void)hipFree(m->d_stage);
-		if (m->h_stage) (void)hipHostFree(m->h_stage);
+	if (!m->stream || m->waitIdle()) {
+		m->mem.release();
 		if (m->stream) (void)hipStreamDestroy(m->stream);
 		if (m->ctx) aof_destroy(m->ctx);
 	} else {
@@ -193,11 +231,11 @@ int OpticalFlowBank::refuse(int code, const char *what)
 }
 
 // The object's stream has nothing left to do (polled, with the deadline); false fails the object.
-bool OpticalFlowBank::waitIdle()
+bool OpticalFlowBank::Impl::waitIdle()
 {
 	const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
 	for (;;) {
-		const hipError_t e = hipStreamQuery(_m->stream);
+		const hipError_t e = hipStreamQuery(stream);
 		if (e == hipSuccess) return true;
 		if (e != hipErrorNotReady) {
 			fail(-EIO, hipGetErrorString(e));
@@ -210,28 +248,51 @@ bool OpticalFlowBank::waitIdle()
 	}
 }
 
+// Masked streams (mask[s] != 0; NULL: all) start over, enqueued on the object's stream: their part of the bank, their
+// IMU state if the form is on (imu_too: or is being turned on) and their receive state if that is on.  What the pinned
+// queues hold for them belongs to their past and is dropped with it.  The caller waits (waitIdle()).
+int OpticalFlowBank::Impl::startOver(const uint8_t *mask, bool imu_too)
+{
+	const uint8_t *d_mask = NULL;
+	if (mask) {
+		std::memcpy(stage.h + off_active, mask, S);
+		if (!stage.upload(stream, off_active, S)) return fail(-EIO, "copy of the reset mask failed");
+		d_mask = stage.d + off_active;
+	}
+	int rc = failed(aof_bank_reset_device(ctx, &bp, d_mask, d_bank, bank_bytes, stream));
+	if (!rc && imu_too) rc = failed(aof_bank_imu_reset_device(ctx, (int)S, d_mask, imu_offset0, d_imu_state, stream));
+	if (!rc && rx) rc = failed(aof_bank_mavlink_rx_reset_device(ctx, (int)S, d_mask, d_rx_state, stream));
+	if (rc) return rc;
+	for (size_t s = 0; s < S; s++) {
+		if (mask && !mask[s]) continue;
+		if (imu_too) imuCounts()[s] = 0;
+		if (rx) rxLengths()[s] = 0;   // (the frame half received went with the receive state)
+	}
+	return 0;
+}
+
 void OpticalFlowBank::setTimestampOffset(uint64_t offset_usec)
 {
 	if (!_m) return;
 	_m->bp.offset_timestamp_usec = offset_usec;
-	if (!_m->h_streams) return;
-	for (int s = 0; s < n_streams; s++) _m->h_streams[s].offset_timestamp_usec = offset_usec;
+	if (!_m->streams.h) return;
+	for (int s = 0; s < n_streams; s++) _m->shadow()[s].offset_timestamp_usec = offset_usec;
 	_m->streams_dirty = true;
 }
 
-// The shadow record of stream s for a setter, or NULL (bad index, no engine); the next push copies the array.
-aof_bank_stream *OpticalFlowBank::streamRecord(int s)
+// The shadow record of stream s for a setter, or NULL (no engine, no memory, bad index); the next push copies the array.
+aof_bank_stream *OpticalFlowBank::Impl::record(Impl *m, int s)
 {
-	if (!_m || !_m->h_streams || s < 0 || s >= n_streams) return NULL;
-	_m->streams_used = true;
-	_m->streams_dirty = true;
-	return &_m->h_streams[s];
+	if (!m || !m->streams.h || s < 0 || (size_t)s >= m->S) return NULL;
+	m->streams_used = true;
+	m->streams_dirty = true;
+	return &m->shadow()[s];
 }
 
 int OpticalFlowBank::setStreamFocalLength(int s, float f_length_x, float f_length_y)
 {
 	if (!(f_length_x > 0.0f) || !(f_length_y > 0.0f)) return -EINVAL;
-	aof_bank_stream *r = streamRecord(s);
+	aof_bank_stream *r = Impl::record(_m, s);
 	if (!r) return -EINVAL;
 	r->focal_x = f_length_x;
 	r->focal_y = f_length_y;
@@ -240,7 +301,7 @@ int OpticalFlowBank::setStreamFocalLength(int s, float f_length_x, float f_lengt
 
 int OpticalFlowBank::setStreamOutputRate(int s, int output_rate)
 {
-	aof_bank_stream *r = streamRecord(s);
+	aof_bank_stream *r = Impl::record(_m, s);
 	if (!r) return -EINVAL;
 	r->output_rate = output_rate;
 	return 0;
@@ -248,7 +309,7 @@ int OpticalFlowBank::setStreamOutputRate(int s, int output_rate)
 
 int OpticalFlowBank::setStreamIdentity(int s, uint8_t system_id, uint8_t component_id, uint8_t first_seq)
 {
-	aof_bank_stream *r = streamRecord(s);
+	aof_bank_stream *r = Impl::record(_m, s);
 	if (!r) return -EINVAL;
 	r->system_id = system_id;
 	r->component_id = component_id;
@@ -260,32 +321,9 @@ int OpticalFlowBank::setStreamTimestampOffset(int s, uint64_t offset_usec)
 {
 	if (!_m || s < 0 || s >= n_streams) return -EINVAL;
 	if (_m->imu) return 0;   // (the IMU form keeps every stream's offset in its IMU state, as with setTimestampOffset())
-	aof_bank_stream *r = streamRecord(s);
+	aof_bank_stream *r = Impl::record(_m, s);
 	if (!r) return -EINVAL;
 	r->offset_timestamp_usec = offset_usec;
-	return 0;
-}
-
-// In front of a tick: the shadow records to the device if a setter changed them, and bound to the context the first
-// time.  Without a setter nothing happens: the tick runs on the scalars, as it always did.  The shadow counts as copied
-// only once collect() has waited for the tick: a setter behind a push that failed in between writes an array that is
-// still marked dirty, and the object has failed for good by then.
-int OpticalFlowBank::syncStreams()
-{
-	Impl *m = _m;
-	if (!m->streams_used) return 0;
-	if (m->streams_dirty) {
-		if (hipMemcpyAsync(m->d_streams, m->h_streams, (size_t)n_streams * sizeof(aof_bank_stream), hipMemcpyHostToDevice,
-				   m->stream) != hipSuccess)
-			return fail(-EIO, "copy of the per-stream records failed");
-		// (still dirty: only collect(), which waits for the tick, knows that the copy has read the shadow; a push that
-		// fails behind this point copies again)
-		m->streams_copying = true;
-	}
-	if (!m->streams_bound) {
-		if (aof_set_bank_streams(m->ctx, m->d_streams, n_streams)) return fail(-EIO, aof_last_error(m->ctx));
-		m->streams_bound = true;
-	}
 	return 0;
 }
 
@@ -305,58 +343,133 @@ const aof_outbox_entry *OpticalFlowBank::published() const
 	return _m && _m->outbox ? reinterpret_cast<const aof_outbox_entry *>(_m->outbox + sizeof(aof_outbox_header)) : NULL;
 }
 
+const aof_exposure_command *OpticalFlowBank::exposureCommands() const { return _m && _m->camera ? _m->commands : NULL; }
+
 int OpticalFlowBank::push(const uint8_t *frames, const uint64_t *img_time_us, const uint8_t *active, const aof_gyro *gyro)
 {
 	if (!engineOk()) return -1;
 	if (!frames || !img_time_us) return -EINVAL;
-	Impl *m = _m;
-	const size_t S = (size_t)n_streams, frame = (size_t)image_width * image_height;
-	std::memcpy(m->h_stage, frames, S * frame);
-	std::memcpy(m->h_stage + m->off_times, img_time_us, S * sizeof(uint64_t));
-	if (gyro) std::memcpy(m->h_stage + m->off_gyro, gyro, S * sizeof(aof_gyro));
-	if (active) std::memcpy(m->h_stage + m->off_active, active, S);
-	if (m->rx) {
-		const int rrc = receive();
-		if (rrc) return rrc;
+	std::memcpy(_m->stage.h, frames, _m->S * (size_t)image_width * image_height);
+	return _m->tick(false, img_time_us, active, gyro);
+}
+
+int OpticalFlowBank::pushCamera(const uint8_t *sensor_frames, const uint64_t *img_time_us, const uint8_t *active,
+				const aof_gyro *gyro)
+{
+	if (!engineOk()) return -1;
+	if (!sensor_frames || !img_time_us || !_m->camera) return -EINVAL;
+	std::memcpy(_m->sensor.h, sensor_frames, _m->sensor.bytes);
+	return _m->tick(true, img_time_us, active, gyro);
+}
+
+// One tick on the frames push() staged in `stage`, or (sensor_frames) on those pushCamera() staged in `sensor`.  The
+// body is the order of the copies and launches on the object's stream; returns the number of published entries.
+int OpticalFlowBank::Impl::tick(bool sensor_frames, const uint64_t *img_time_us, const uint8_t *active, const aof_gyro *gyro)
+{
+	std::memcpy(stage.h + off_times, img_time_us, S * sizeof(uint64_t));
+	if (gyro) std::memcpy(stage.h + off_gyro, gyro, S * sizeof(aof_gyro));
+	if (active) std::memcpy(stage.h + off_active, active, S);
+	// What the form decides, here and nowhere else.  With the IMU form the push leaves records only (no time offset: no
+	// frames) and ignores the caller's gyro: the IMU call behind it completes the records and packs the frames.
+	aof_bank_params push_bp = bp;
+	if (imu) push_bp.offset_timestamp_usec = 0;
+	const uint64_t *d_times = reinterpret_cast<const uint64_t *>(stage.d + off_times);
+	const uint8_t *d_active = active ? stage.d + off_active : NULL;
+	const aof_gyro *d_gyro = gyro && !imu ? reinterpret_cast<const aof_gyro *>(stage.d + off_gyro) : NULL;
+	uint8_t *push_mavlink = imu ? NULL : d_mavlink, *push_lens = imu ? NULL : d_lens;
+	int rc;
+	// 1. receive: the queued bytes become the samples the IMU call reads
+	if (rx && (rc = receive()) != 0) return rc;
+	// 2. uploads: the plain form in one copy of the whole block; sensor frames apart from the block's tail
+	if (!sensor_frames) {
+		if (!stage.upload(stream, 0, stage.bytes)) return fail(-EIO, "copy of the tick's frames failed");
+	} else if (!sensor.upload(stream, 0, sensor.bytes) || !stage.upload(stream, off_times, stage.bytes - off_times)) {
+		return fail(-EIO, "copy of the tick's sensor frames failed");
 	}
-	if (hipMemcpyAsync(m->d_stage, m->h_stage, m->stage_bytes, hipMemcpyHostToDevice, m->stream) != hipSuccess)
-		return fail(-EIO, "copy of the tick's frames failed");
-	int rc = syncStreams();
-	if (rc) return rc;
-	// with the IMU form the tick leaves records only: the IMU call behind it completes them and packs the frames
-	aof_bank_params bp = m->bp;
-	if (m->imu) bp.offset_timestamp_usec = 0;
-	rc = aof_bank_push_device(m->ctx, &bp, m->d_stage, reinterpret_cast<const uint64_t *>(m->d_stage + m->off_times),
-				      active ? m->d_stage + m->off_active : NULL,
-				      gyro && !m->imu ? reinterpret_cast<const aof_gyro *>(m->d_stage + m->off_gyro) : NULL, m->d_bank,
-				      m->bank_bytes, m->d_records, m->imu ? NULL : m->d_mavlink, m->imu ? NULL : m->d_lens, m->stream);
-	if (rc) return fail(rc, aof_last_error(m->ctx));
-	if (m->imu && (rc = takeImu()) != 0) return rc;
+	// 3. the per-stream records, if a setter changed them
+	if ((rc = syncStreams()) != 0) return rc;
+	// 4. the push
+	rc = sensor_frames ? aof_bank_push_camera_device(ctx, &push_bp, &cam, sensor.d, d_times, d_active, d_gyro, d_bank, bank_bytes,
+							 d_records, d_exposure, NULL, push_mavlink, push_lens, stream)
+			   : aof_bank_push_device(ctx, &push_bp, stage.d, d_times, d_active, d_gyro, d_bank, bank_bytes, d_records,
+						  push_mavlink, push_lens, stream);
+	if (failed(rc)) return rc;
+	// 5. the IMU call, in place on the push's records
+	if (imu && (rc = takeImu()) != 0) return rc;
+	// 6. the exposure control: its commands land in pinned memory in front of the collect's tag
+	if (sensor_frames && (rc = failed(aof_bank_exposure_control_device(ctx, &ec, (int)S, 1, d_exposure, d_exposure_state,
+									    commands, stream))) != 0)
+		return rc;
+	// 7. collect, and the bounded wait for it
 	return collect();
 }
 
-// The collect launch behind a tick and the bounded poll of its tag; returns the number of published entries.
-int OpticalFlowBank::collect()
+// In front of a tick: the queued bytes to the device and the receive launch, which leaves the samples and their counts
+// where takeImu()'s IMU call reads them (collect() empties the queue once the tick is through).
+int OpticalFlowBank::Impl::receive()
 {
-	Impl *m = _m;
-	const uint64_t tag = ++m->tag;
-	const int rc = aof_bank_collect_device(m->ctx, n_streams, 1, m->d_records, m->d_mavlink, m->d_lens, NULL, NULL,
-					       (uint32_t)n_streams, 0, m->outbox, m->outbox_bytes, tag, NULL, m->stream);
-	if (rc) return fail(rc, aof_last_error(m->ctx));
+	if (!bytes.upload(stream, 0, bytes.bytes)) return fail(-EIO, "copy of the tick's MAVLink bytes failed");
+	return failed(aof_bank_mavlink_rx_device(ctx, &rp, bytes.d, reinterpret_cast<const uint16_t *>(bytes.d + off_rx_len), d_rx_state,
+						 reinterpret_cast<aof_imu_sample *>(samples.d), samples.d + off_imu_counts, stream));
+}
+
+// In front of a tick: the shadow records to the device if a setter changed them, and bound to the context the first
+// time.  Without a setter nothing happens: the tick runs on the scalars, as it always did.  The shadow counts as copied
+// only once collect() has waited for the tick: a setter behind a push that failed in between writes an array that is
+// still marked dirty, and the object has failed for good by then.
+int OpticalFlowBank::Impl::syncStreams()
+{
+	if (!streams_used) return 0;
+	if (streams_dirty) {
+		if (!streams.upload(stream, 0, streams.bytes)) return fail(-EIO, "copy of the per-stream records failed");
+		streams_copying = true;   // (still dirty: a push that fails behind this point copies again)
+	}
+	if (!streams_bound) {
+		if (failed(aof_set_bank_streams(ctx, reinterpret_cast<aof_bank_stream *>(streams.d), (int)S))) return -EIO;
+		streams_bound = true;
+	}
+	return 0;
+}
+
+// Behind a records-only push: the queued samples to the device and the IMU call in place on the push's records.
+int OpticalFlowBank::Impl::takeImu()
+{
+	// (with the receive path the samples and their counts are on the device already: receive() wrote them)
+	if (!rx && !samples.upload(stream, 0, samples.bytes)) return fail(-EIO, "copy of the tick's IMU samples failed");
+	return failed(aof_bank_imu_device(ctx, &ip, reinterpret_cast<const aof_imu_sample *>(samples.d), samples.d + off_imu_counts,
+					  reinterpret_cast<const uint64_t *>(stage.d + off_times), d_records, d_imu_state, d_records,
+					  d_mavlink, d_lens, stream));
+}
+
+// The collect launch behind a tick and the bounded poll of its tag; returns the number of published entries.
+int OpticalFlowBank::Impl::collect()
+{
+	const uint64_t want = ++tag;
+	const int rc = failed(aof_bank_collect_device(ctx, (int)S, 1, d_records, d_mavlink, d_lens, NULL, NULL, (uint32_t)S, 0, outbox,
+						      outbox_bytes, want, NULL, stream));
+	if (rc) return rc;
 	// the tag is the kernel's last store: once it is here, so are the counts and the entries (and what earlier
 	// launches on the stream released to the host: the exposure commands)
-	const uint64_t *word = reinterpret_cast<const uint64_t *>(m->outbox);
+	const uint64_t *word = reinterpret_cast<const uint64_t *>(outbox);
 	const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-	while (__atomic_load_n(word, __ATOMIC_ACQUIRE) != tag) {
+	while (__atomic_load_n(word, __ATOMIC_ACQUIRE) != want) {
 		if (secondsSince(t0) > kDeadlineS) return fail(-ETIMEDOUT, "the tick did not finish within the deadline");
 	}
-	if (m->streams_copying) {   // the copy of the per-stream records in front of the tick is through as well
-		m->streams_copying = false;
-		m->streams_dirty = false;
+	if (streams_copying) {   // the copy of the per-stream records in front of the tick is through as well
+		streams_copying = false;
+		streams_dirty = false;
 	}
-	if (m->imu) std::memset(m->h_imu + m->off_imu_counts, 0, (size_t)n_streams);   // the tick took the queued samples
-	if (m->rx) std::memset(m->h_rx + m->off_rx_len, 0, (size_t)n_streams * sizeof(uint16_t));   // and the queued bytes
-	return (int)reinterpret_cast<const aof_outbox_header *>(m->outbox)->n_messages;
+	if (imu) std::memset(imuCounts(), 0, S);                      // the tick took the queued samples
+	if (rx) std::memset(rxLengths(), 0, S * sizeof(uint16_t));    // and the queued bytes
+	return (int)reinterpret_cast<const aof_outbox_header *>(outbox)->n_messages;
+}
+
+int OpticalFlowBank::reset(const uint8_t *mask)
+{
+	if (!engineOk()) return -1;
+	const int rc = _m->startOver(mask, _m->imu);   // (the auto-exposure controllers keep what they hold)
+	if (rc) return rc;
+	return _m->waitIdle() ? 0 : -ETIMEDOUT;
 }
 
 int OpticalFlowBank::enableCamera(int camera_width, int camera_height, uint16_t exposure0, uint8_t gain0,
@@ -364,126 +477,44 @@ int OpticalFlowBank::enableCamera(int camera_width, int camera_height, uint16_t 
 {
 	if (!engineOk()) return -1;
 	Impl *m = _m;
-	// a wrong argument is refused and leaves the object as it was
+	// a refused call leaves the object as it was: nothing of the object is written before the arguments are accepted
 	if (m->camera) return refuse(-EINVAL, "enableCamera() was already called");
-	if (!waitIdle()) return -ETIMEDOUT;
+	if (!m->waitIdle()) return -ETIMEDOUT;
 	aof_params p;
 	if (aof_get_params(m->ctx, &p)) return fail(-EIO, aof_last_error(m->ctx));
-	std::memset(&m->cam, 0, sizeof(m->cam));
-	m->cam.ingest.camera_width = camera_width;
-	m->cam.ingest.camera_height = camera_height;
-	m->cam.ingest.crop_width = image_width;
-	m->cam.ingest.crop_height = image_height;
-	m->cam.exposure_interval_us = exposure_interval_us;
+	aof_bank_camera cam;
+	std::memset(&cam, 0, sizeof(cam));
+	cam.ingest.camera_width = camera_width;
+	cam.ingest.camera_height = camera_height;
+	cam.ingest.crop_width = image_width;
+	cam.ingest.crop_height = image_height;
+	cam.exposure_interval_us = exposure_interval_us;
 	struct aof_bank_layout L;
 	size_t staging = 0;
-	if (camera_width < 1 || camera_height < 1 || aof_bank_camera_layout(&p, &m->bp, &m->cam, &L, &staging))
+	if (camera_width < 1 || camera_height < 1 || aof_bank_camera_layout(&p, &m->bp, &cam, &L, &staging))
 		return refuse(-EINVAL, "enableCamera(): the sensor frame cannot hold the image size");
-	const size_t S = (size_t)n_streams;
-	m->sensor_bytes = S * (size_t)camera_width * (size_t)camera_height;
-	aof_exposure_control_default(&m->ec);
+	const size_t S = m->S;
 	void *bank = NULL;
-	const bool ok = hipMalloc(&bank, L.total_bytes) == hipSuccess &&
-			hipHostMalloc((void **)&m->h_sensor, m->sensor_bytes, hipHostMallocDefault) == hipSuccess &&
-			hipMalloc((void **)&m->d_sensor, m->sensor_bytes) == hipSuccess &&
-			hipMalloc((void **)&m->d_exposure, S * sizeof(aof_exposure_record)) == hipSuccess &&
-			hipMalloc((void **)&m->d_exposure_state, S * sizeof(aof_exposure_state)) == hipSuccess &&
-			aof_outbox_alloc_host(S * sizeof(aof_exposure_command), (void **)&m->commands) == 0;
-	if (bank) {   // the bank grows by the staging region of the composed path; the stream is idle
-		(void)hipFree(m->d_bank);
-		m->d_bank = bank;
-		m->bank_bytes = L.total_bytes;
-	}
-	if (!ok) return fail(-ENOMEM, "device or pinned memory for the sensor frames could not be allocated");
+	if (!m->mem.get(&bank, L.total_bytes, Allocations::kDevice) ||
+	    !m->sensor.alloc(m->mem, S * (size_t)camera_width * (size_t)camera_height) ||
+	    !m->mem.get((void **)&m->d_exposure, S * sizeof(aof_exposure_record), Allocations::kDevice) ||
+	    !m->mem.get((void **)&m->d_exposure_state, S * sizeof(aof_exposure_state), Allocations::kDevice) ||
+	    !m->mem.get((void **)&m->commands, S * sizeof(aof_exposure_command), Allocations::kOutbox))
+		return fail(-ENOMEM, "device or pinned memory for the sensor frames could not be allocated");
+	// the bank grows by the staging region of the composed path; the stream is idle
+	m->mem.drop(m->d_bank);
+	m->d_bank = bank;
+	m->bank_bytes = L.total_bytes;
+	m->cam = cam;
+	aof_exposure_control_default(&m->ec);
 	std::memset(m->commands, 0, S * sizeof(aof_exposure_command));
-	if (aof_bank_reset_device(m->ctx, &m->bp, NULL, m->d_bank, m->bank_bytes, m->stream) ||
-	    aof_bank_exposure_reset_device(m->ctx, n_streams, NULL, exposure0, gain0, NULL, NULL, m->d_exposure_state, m->stream))
-		return fail(-EIO, aof_last_error(m->ctx));
-	if (m->imu) {   // every stream starts over: its IMU state and the samples queued for it as well
-		if (aof_bank_imu_reset_device(m->ctx, n_streams, NULL, m->imu_offset0, m->d_imu_state, m->stream))
-			return fail(-EIO, aof_last_error(m->ctx));
-		std::memset(m->h_imu + m->off_imu_counts, 0, (size_t)n_streams);
-	}
-	if (m->rx) {    // and its receive state and queued bytes
-		if (aof_bank_mavlink_rx_reset_device(m->ctx, n_streams, NULL, m->d_rx_state, m->stream))
-			return fail(-EIO, aof_last_error(m->ctx));
-		std::memset(m->h_rx + m->off_rx_len, 0, (size_t)n_streams * sizeof(uint16_t));
-	}
-	if (!waitIdle()) return -ETIMEDOUT;
+	// every stream starts over, and every controller from exposure0 / gain0
+	if (m->startOver(NULL, m->imu)) return -EIO;
+	if (m->failed(aof_bank_exposure_reset_device(m->ctx, n_streams, NULL, exposure0, gain0, NULL, NULL, m->d_exposure_state, m->stream)))
+		return -EIO;
+	if (!m->waitIdle()) return -ETIMEDOUT;
 	m->camera = true;
 	return 0;
-}
-
-const aof_exposure_command *OpticalFlowBank::exposureCommands() const { return _m && _m->camera ? _m->commands : NULL; }
-
-int OpticalFlowBank::pushCamera(const uint8_t *sensor_frames, const uint64_t *img_time_us, const uint8_t *active,
-				const aof_gyro *gyro)
-{
-	if (!engineOk()) return -1;
-	if (!sensor_frames || !img_time_us || !_m->camera) return -EINVAL;
-	Impl *m = _m;
-	const size_t S = (size_t)n_streams;
-	std::memcpy(m->h_sensor, sensor_frames, m->sensor_bytes);
-	std::memcpy(m->h_stage + m->off_times, img_time_us, S * sizeof(uint64_t));
-	if (gyro) std::memcpy(m->h_stage + m->off_gyro, gyro, S * sizeof(aof_gyro));
-	if (active) std::memcpy(m->h_stage + m->off_active, active, S);
-	if (m->rx) {
-		const int rrc = receive();
-		if (rrc) return rrc;
-	}
-	if (hipMemcpyAsync(m->d_sensor, m->h_sensor, m->sensor_bytes, hipMemcpyHostToDevice, m->stream) != hipSuccess ||
-	    hipMemcpyAsync(m->d_stage + m->off_times, m->h_stage + m->off_times, m->stage_bytes - m->off_times,
-			   hipMemcpyHostToDevice, m->stream) != hipSuccess)
-		return fail(-EIO, "copy of the tick's sensor frames failed");
-	int rc = syncStreams();
-	if (rc) return rc;
-	aof_bank_params bp = m->bp;
-	if (m->imu) bp.offset_timestamp_usec = 0;   // (records only, as in push())
-	rc = aof_bank_push_camera_device(m->ctx, &bp, &m->cam, m->d_sensor,
-					     reinterpret_cast<const uint64_t *>(m->d_stage + m->off_times),
-					     active ? m->d_stage + m->off_active : NULL,
-					     gyro && !m->imu ? reinterpret_cast<const aof_gyro *>(m->d_stage + m->off_gyro) : NULL, m->d_bank,
-					     m->bank_bytes, m->d_records, m->d_exposure, NULL, m->imu ? NULL : m->d_mavlink,
-					     m->imu ? NULL : m->d_lens, m->stream);
-	if (rc) return fail(rc, aof_last_error(m->ctx));
-	if (m->imu && (rc = takeImu()) != 0) return rc;
-	rc = aof_bank_exposure_control_device(m->ctx, &m->ec, n_streams, 1, m->d_exposure, m->d_exposure_state, m->commands,
-					      m->stream);
-	if (rc) return fail(rc, aof_last_error(m->ctx));
-	return collect();
-}
-
-int OpticalFlowBank::reset(const uint8_t *mask)
-{
-	if (!engineOk()) return -1;
-	Impl *m = _m;
-	if (mask) {
-		std::memcpy(m->h_stage + m->off_active, mask, (size_t)n_streams);
-		if (hipMemcpyAsync(m->d_stage + m->off_active, m->h_stage + m->off_active, (size_t)n_streams, hipMemcpyHostToDevice,
-				   m->stream) != hipSuccess)
-			return fail(-EIO, "copy of the reset mask failed");
-	}
-	int rc = aof_bank_reset_device(m->ctx, &m->bp, mask ? m->d_stage + m->off_active : NULL, m->d_bank, m->bank_bytes,
-				       m->stream);
-	if (rc) return fail(rc, aof_last_error(m->ctx));
-	if (m->imu) {
-		rc = aof_bank_imu_reset_device(m->ctx, n_streams, mask ? m->d_stage + m->off_active : NULL, m->imu_offset0,
-					       m->d_imu_state, m->stream);
-		if (rc) return fail(rc, aof_last_error(m->ctx));
-		// samples queued for a stream that starts over belong to its past: they are dropped with it
-		uint8_t *counts = m->h_imu + m->off_imu_counts;
-		for (int s = 0; s < n_streams; s++)
-			if (!mask || mask[s]) counts[s] = 0;
-	}
-	if (m->rx) {   // likewise a frame half received and the bytes queued
-		rc = aof_bank_mavlink_rx_reset_device(m->ctx, n_streams, mask ? m->d_stage + m->off_active : NULL, m->d_rx_state,
-						      m->stream);
-		if (rc) return fail(rc, aof_last_error(m->ctx));
-		uint16_t *lens = reinterpret_cast<uint16_t *>(m->h_rx + m->off_rx_len);
-		for (int s = 0; s < n_streams; s++)
-			if (!mask || mask[s]) lens[s] = 0;
-	}
-	return waitIdle() ? 0 : -ETIMEDOUT;
 }
 
 int OpticalFlowBank::enableImu(int max_samples, uint64_t offset0)
@@ -492,15 +523,12 @@ int OpticalFlowBank::enableImu(int max_samples, uint64_t offset0)
 	Impl *m = _m;
 	if (m->imu) return refuse(-EINVAL, "enableImu() was already called");
 	if (max_samples < 1 || max_samples > AOF_IMU_SLOTS_MAX) return refuse(-EINVAL, "enableImu(): max_samples outside 1..AOF_IMU_SLOTS_MAX");
-	if (!waitIdle()) return -ETIMEDOUT;
-	const size_t S = (size_t)n_streams;
+	if (!m->waitIdle()) return -ETIMEDOUT;
+	const size_t S = m->S;
 	m->off_imu_counts = (size_t)max_samples * S * sizeof(aof_imu_sample);
-	m->imu_bytes = alignUp(m->off_imu_counts + S, 256);
-	const bool ok = hipHostMalloc((void **)&m->h_imu, m->imu_bytes, hipHostMallocDefault) == hipSuccess &&
-			hipMalloc((void **)&m->d_imu, m->imu_bytes) == hipSuccess &&
-			hipMalloc((void **)&m->d_imu_state, S * sizeof(aof_imu_state)) == hipSuccess;
-	if (!ok) return fail(-ENOMEM, "device or pinned memory for the IMU samples could not be allocated");
-	std::memset(m->h_imu, 0, m->imu_bytes);
+	if (!m->samples.alloc(m->mem, alignUp(m->off_imu_counts + S, 256)) ||
+	    !m->mem.get((void **)&m->d_imu_state, S * sizeof(aof_imu_state), Allocations::kDevice))
+		return fail(-ENOMEM, "device or pinned memory for the IMU samples could not be allocated");
 	std::memset(&m->ip, 0, sizeof(m->ip));
 	m->ip.n_streams = n_streams;
 	m->ip.n_rounds = 1;
@@ -509,10 +537,8 @@ int OpticalFlowBank::enableImu(int max_samples, uint64_t offset0)
 	m->ip.component_id = m->bp.component_id;
 	m->ip.first_seq = m->bp.first_seq;
 	m->imu_offset0 = offset0;
-	if (aof_bank_reset_device(m->ctx, &m->bp, NULL, m->d_bank, m->bank_bytes, m->stream) ||
-	    aof_bank_imu_reset_device(m->ctx, n_streams, NULL, offset0, m->d_imu_state, m->stream))
-		return fail(-EIO, aof_last_error(m->ctx));
-	if (!waitIdle()) return -ETIMEDOUT;
+	if (m->startOver(NULL, true)) return -EIO;
+	if (!m->waitIdle()) return -ETIMEDOUT;
 	m->imu = true;
 	return 0;
 }
@@ -522,9 +548,9 @@ int OpticalFlowBank::pushImu(int stream, uint64_t time_usec, float xgyro, float 
 	if (!engineOk()) return -1;
 	Impl *m = _m;
 	if (!m->imu || m->rx || stream < 0 || stream >= n_streams) return -EINVAL;   // (with the receive path the device counts)
-	uint8_t *count = m->h_imu + m->off_imu_counts + stream;
+	uint8_t *count = m->imuCounts() + stream;
 	if (*count >= m->ip.max_samples) return -ENOBUFS;
-	aof_imu_sample *slot = reinterpret_cast<aof_imu_sample *>(m->h_imu) + (size_t)*count * (size_t)n_streams + stream;
+	aof_imu_sample *slot = reinterpret_cast<aof_imu_sample *>(m->samples.h) + (size_t)*count * m->S + stream;
 	slot->time_usec = time_usec;
 	slot->xgyro = xgyro;
 	slot->ygyro = ygyro;
@@ -534,21 +560,7 @@ int OpticalFlowBank::pushImu(int stream, uint64_t time_usec, float xgyro, float 
 	return 0;
 }
 
-// Behind a records-only tick: the queued samples to the device, the IMU call in place on the tick's records, and the
-// queue is empty again (collect() waits for the tick, so the pinned block is free when push() returns).
-int OpticalFlowBank::takeImu()
-{
-	Impl *m = _m;
-	// (with the receive path the samples and their counts are on the device already: receive() wrote them)
-	if (!m->rx && hipMemcpyAsync(m->d_imu, m->h_imu, m->imu_bytes, hipMemcpyHostToDevice, m->stream) != hipSuccess)
-		return fail(-EIO, "copy of the tick's IMU samples failed");
-	const int rc = aof_bank_imu_device(m->ctx, &m->ip, reinterpret_cast<const aof_imu_sample *>(m->d_imu), m->d_imu + m->off_imu_counts,
-					   reinterpret_cast<const uint64_t *>(m->d_stage + m->off_times), m->d_records, m->d_imu_state,
-					   m->d_records, m->d_mavlink, m->d_lens, m->stream);
-	if (rc) return fail(rc, aof_last_error(m->ctx));
-	return 0;
-}
-
+// Narrower than startOver() on purpose: the bank and the IMU state go on as they are.
 int OpticalFlowBank::enableMavlinkRx(int max_bytes)
 {
 	if (!engineOk()) return -1;
@@ -557,24 +569,20 @@ int OpticalFlowBank::enableMavlinkRx(int max_bytes)
 	if (m->rx) return refuse(-EINVAL, "enableMavlinkRx() was already called");
 	if (max_bytes < 16 || max_bytes > AOF_MAVLINK_RX_BYTES_MAX || max_bytes % 16)
 		return refuse(-EINVAL, "enableMavlinkRx(): max_bytes outside 16..AOF_MAVLINK_RX_BYTES_MAX or no multiple of 16");
-	if (!waitIdle()) return -ETIMEDOUT;
-	const size_t S = (size_t)n_streams;
+	if (!m->waitIdle()) return -ETIMEDOUT;
+	const size_t S = m->S;
 	m->off_rx_len = S * (size_t)max_bytes;
-	m->rx_bytes = alignUp(m->off_rx_len + S * sizeof(uint16_t), 256);
-	const bool ok = hipHostMalloc((void **)&m->h_rx, m->rx_bytes, hipHostMallocDefault) == hipSuccess &&
-			hipMalloc((void **)&m->d_rx, m->rx_bytes) == hipSuccess &&
-			hipMalloc((void **)&m->d_rx_state, S * sizeof(aof_mavlink_rx_state)) == hipSuccess;
-	if (!ok) return fail(-ENOMEM, "device or pinned memory for the MAVLink bytes could not be allocated");
-	std::memset(m->h_rx, 0, m->rx_bytes);
+	if (!m->bytes.alloc(m->mem, alignUp(m->off_rx_len + S * sizeof(uint16_t), 256)) ||
+	    !m->mem.get((void **)&m->d_rx_state, S * sizeof(aof_mavlink_rx_state), Allocations::kDevice))
+		return fail(-ENOMEM, "device or pinned memory for the MAVLink bytes could not be allocated");
 	m->rp.n_streams = n_streams;
 	m->rp.n_rounds = 1;
 	m->rp.max_bytes = max_bytes;
 	m->rp.max_samples = m->ip.max_samples;
-	if (aof_bank_mavlink_rx_reset_device(m->ctx, n_streams, NULL, m->d_rx_state, m->stream))
-		return fail(-EIO, aof_last_error(m->ctx));
-	if (!waitIdle()) return -ETIMEDOUT;
+	if (m->failed(aof_bank_mavlink_rx_reset_device(m->ctx, n_streams, NULL, m->d_rx_state, m->stream))) return -EIO;
+	if (!m->waitIdle()) return -ETIMEDOUT;
 	// samples pushImu() queued are dropped: from here on the device writes the sample block
-	std::memset(m->h_imu + m->off_imu_counts, 0, S);
+	std::memset(m->imuCounts(), 0, S);
 	m->rx = true;
 	return 0;
 }
@@ -584,23 +592,9 @@ int OpticalFlowBank::pushMavlink(int stream, const uint8_t *bytes, int n)
 	if (!engineOk()) return -1;
 	Impl *m = _m;
 	if (!m->rx || stream < 0 || stream >= n_streams || n < 0 || (n > 0 && !bytes)) return -EINVAL;
-	uint16_t *len = reinterpret_cast<uint16_t *>(m->h_rx + m->off_rx_len) + stream;
+	uint16_t *len = m->rxLengths() + stream;
 	if ((int)*len + n > m->rp.max_bytes) return -ENOBUFS;
-	if (n) std::memcpy(m->h_rx + (size_t)stream * (size_t)m->rp.max_bytes + *len, bytes, (size_t)n);
+	if (n) std::memcpy(m->bytes.h + (size_t)stream * (size_t)m->rp.max_bytes + *len, bytes, (size_t)n);
 	*len = (uint16_t)(*len + n);
-	return 0;
-}
-
-// In front of a tick: the queued bytes to the device and the receive launch, which leaves the samples and their counts
-// where takeImu()'s IMU call reads them (collect() empties the queue once the tick is through).
-int OpticalFlowBank::receive()
-{
-	Impl *m = _m;
-	if (hipMemcpyAsync(m->d_rx, m->h_rx, m->rx_bytes, hipMemcpyHostToDevice, m->stream) != hipSuccess)
-		return fail(-EIO, "copy of the tick's MAVLink bytes failed");
-	const int rc = aof_bank_mavlink_rx_device(m->ctx, &m->rp, m->d_rx, reinterpret_cast<const uint16_t *>(m->d_rx + m->off_rx_len),
-						  m->d_rx_state, reinterpret_cast<aof_imu_sample *>(m->d_imu), m->d_imu + m->off_imu_counts,
-						  m->stream);
-	if (rc) return fail(rc, aof_last_error(m->ctx));
 	return 0;
 }
