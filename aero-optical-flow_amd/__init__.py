@@ -101,6 +101,17 @@ BANK_STREAM_DTYPE = np.dtype([("focal_x", "<f4"), ("focal_y", "<f4"), ("output_r
 assert BANK_STREAM_DTYPE.itemsize == 32 and C.sizeof(BankStream) == 32
 
 
+class BankSensor(C.Structure):
+    """``aof_bank_sensor`` (include/aof.h): where one camera's frame lies in the camera buffer, and its crop."""
+    _fields_ = [("offset", C.c_uint64), ("pitch", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("x0", C.c_int32), ("y0", C.c_int32), ("reserved", C.c_uint32)]
+
+
+BANK_SENSOR_DTYPE = np.dtype([("offset", "<u8"), ("pitch", "<i4"), ("width", "<i4"), ("height", "<i4"), ("x0", "<i4"),
+                              ("y0", "<i4"), ("reserved", "<u4")])                                   # aof_bank_sensor
+assert BANK_SENSOR_DTYPE.itemsize == 32 and C.sizeof(BankSensor) == 32
+
+
 class BankLayout(C.Structure):
     """``struct aof_bank_layout`` (include/aof.h)."""
     _fields_ = [(n, C.c_size_t) for n in ("total_bytes", "frames", "state", "scratch")]
@@ -119,6 +130,7 @@ class BankBurst(C.Structure):
 
 BANK_BURST_MAX = 16
 TICK_HELD, TICK_IDLE = -1, -2
+TICK_BAD_SENSOR = -5   # the stream's sensor record (aof_bank_sensor) does not describe memory inside the camera buffer
 TICK_DTYPE = np.dtype([("quality", "<i4"), ("dt_us", "<i4"), ("flow_x", "<f4"), ("flow_y", "<f4"),
                        ("gyro_x", "<f4"), ("gyro_y", "<f4"), ("gyro_z", "<f4"), ("frame", "<u4"), ("pixel", FLOW_DTYPE)])
 BANK_STATE_BYTES = 64
@@ -269,6 +281,11 @@ def _load():
         "aof_set_bank_path": (C.c_int, [VP, C.c_int]),
         "aof_bank_stream_from_params": (C.c_int, [P(BankParams), P(BankStream)]),
         "aof_set_bank_streams": (C.c_int, [VP, VP, C.c_int32]),
+        "aof_set_bank_sensors": (C.c_int, [VP, VP, C.c_int32, C.c_uint64]),
+        "aof_bank_sensor_from_camera": (C.c_int, [P(Params), P(BankCamera), C.c_int32, P(BankSensor)]),
+        "aof_bank_sensor_centred": (C.c_int, [P(Params), C.c_uint64, C.c_int32, C.c_int32, C.c_int32, P(BankSensor)]),
+        "aof_bank_sensor_valid": (C.c_int, [P(BankSensor), C.c_int32, C.c_int32, C.c_uint64, C.c_uint64]),
+        "aof_ingest_sensors_device": (C.c_int, [C.c_int32, C.c_int32, VP, C.c_uint64, VP, I64, VP, I64, VP, VP, VP]),
         "aof_bank_camera_layout": (C.c_int, [P(Params), P(BankParams), P(BankCamera), P(BankLayout), P(C.c_size_t)]),
         "aof_bank_push_camera_device": (C.c_int, [VP, P(BankParams), P(BankCamera), VP, VP, VP, VP, VP, C.c_size_t, VP, VP, VP,
                                                   VP, VP, VP]),
@@ -447,6 +464,70 @@ def bank_stream_from_params(bp: BankParams, n=None):
         raise AofError(rc, lib.aof_strerror(rc).decode())
     one = np.frombuffer(bytes(rec), dtype=BANK_STREAM_DTYPE)[0]
     return one if n is None else np.full(int(n), one, dtype=BANK_STREAM_DTYPE)
+
+
+def _sensor_record(rec: BankSensor):
+    return np.frombuffer(bytes(rec), dtype=BANK_SENSOR_DTYPE)[0]
+
+
+def bank_sensor_from_camera(p: Params, cam: BankCamera, stream=None, n=None):
+    """aof_bank_sensor_from_camera: the ``aof_bank_sensor`` record the scalars of ``cam`` mean for stream ``stream``, as a
+    numpy record of BANK_SENSOR_DTYPE -- or, with ``n``, the array of the records of streams 0..n-1 (binding it changes
+    no byte of a camera push)."""
+    def one(s):
+        rec = BankSensor()
+        rc = lib.aof_bank_sensor_from_camera(C.byref(p), C.byref(cam), int(s), C.byref(rec))
+        if rc:
+            raise AofError(rc, lib.aof_strerror(rc).decode())
+        return _sensor_record(rec)
+    if n is None:
+        return one(stream or 0)
+    return np.array([one(s) for s in range(int(n))], dtype=BANK_SENSOR_DTYPE)
+
+
+def bank_sensor_centred(p: Params, offset, pitch, width, height):
+    """aof_bank_sensor_centred: the record of a frame of width x height, rows ``pitch`` bytes apart, ``offset`` bytes into
+    the camera buffer, with the crop at the centre (the reference's rule)."""
+    rec = BankSensor()
+    rc = lib.aof_bank_sensor_centred(C.byref(p), int(offset), int(pitch), int(width), int(height), C.byref(rec))
+    if rc:
+        raise AofError(rc, lib.aof_strerror(rc).decode())
+    return _sensor_record(rec)
+
+
+def bank_sensor_valid(rec, crop_w, crop_h, camera_bytes, base=0) -> bool:
+    """aof_bank_sensor_valid: the kernels' validity rule on one BANK_SENSOR_DTYPE record, compiled for the host."""
+    r = BankSensor.from_buffer_copy(np.asarray(rec, dtype=BANK_SENSOR_DTYPE).tobytes())
+    rc = lib.aof_bank_sensor_valid(C.byref(r), int(crop_w), int(crop_h), int(base), int(camera_bytes))
+    if rc < 0:
+        raise AofError(rc, lib.aof_strerror(rc).decode())
+    return bool(rc)
+
+
+def ingest_sensors(camera, sensors, crop_w, crop_h, camera_bytes=None, cropped=None, hist=None, ok=None, want_cropped=True,
+                   want_hist=True, want_ok=True):
+    """aof_ingest_sensors_device: frame ingest on the device for frames that sensor records describe.  camera: uint8 CUDA
+    tensor (any shape; the records' offsets count from its first byte); sensors: uint8 CUDA tensor of n * 32 bytes
+    (BANK_SENSOR_DTYPE, 16-byte aligned); camera_bytes: bytes of ``camera`` the kernel may read (default: all).  Returns
+    (cropped [n, crop_h, crop_w], hist [n, 10] int32, ok [n] uint8), None where not wanted."""
+    import torch
+    assert camera.dtype == torch.uint8 and sensors.dtype == torch.uint8 and sensors.is_contiguous() and sensors.numel() % 32 == 0
+    n = sensors.numel() // 32
+    dev = camera.device
+    if cropped is None and want_cropped:
+        cropped = torch.empty((n, crop_h, crop_w), dtype=torch.uint8, device=dev)
+    if hist is None and want_hist:
+        hist = torch.empty((n, 10), dtype=torch.int32, device=dev)
+    if ok is None and want_ok:
+        ok = torch.empty((n,), dtype=torch.uint8, device=dev)
+    opt = lambda t: t.data_ptr() if t is not None else None
+    rc = lib.aof_ingest_sensors_device(int(crop_w), int(crop_h), camera.data_ptr(),
+                                       camera.numel() if camera_bytes is None else int(camera_bytes), sensors.data_ptr(), n,
+                                       opt(cropped), cropped.stride(0) if cropped is not None and n else crop_w * crop_h,
+                                       opt(hist), opt(ok), torch.cuda.current_stream(dev).cuda_stream)
+    if rc:
+        raise AofError(rc, lib.aof_strerror(rc).decode())
+    return cropped, hist, ok
 
 
 def bank_layout(p: Params, bp: BankParams) -> BankLayout:
@@ -1195,6 +1276,23 @@ class FlowEngine:
         self._check(lib.aof_set_bank_streams(self._ctx, streams.data_ptr(), n))
         self._bank_streams = streams   # (kept alive for as long as it is bound)
 
+    def set_bank_sensors(self, sensors=None, n_streams=None, camera_bytes=0):
+        """aof_set_bank_sensors: binds a uint8 CUDA tensor of S * 32 bytes (``aof_bank_sensor`` records, BANK_SENSOR_DTYPE;
+        16-byte aligned) to the context, or with None unbinds.  n_streams: S, where the tensor holds more than S records;
+        camera_bytes: the bytes readable from the camera tensor of the pushes.  While it is bound every camera push of S
+        streams takes the place, row pitch, size and crop origin of stream s's sensor frame from record s; the kernels
+        read it when they run, so the tensor must stay alive and may be rewritten between ticks.  Enqueues nothing."""
+        if sensors is None:
+            self._check(lib.aof_set_bank_sensors(self._ctx, None, 0, 0))
+            self._bank_sensors = None
+            return
+        import torch
+        assert sensors.dtype == torch.uint8 and sensors.is_contiguous() and sensors.numel() % 32 == 0
+        n = sensors.numel() // 32 if n_streams is None else int(n_streams)
+        assert 1 <= n <= sensors.numel() // 32
+        self._check(lib.aof_set_bank_sensors(self._ctx, sensors.data_ptr(), n, int(camera_bytes)))
+        self._bank_sensors = sensors   # (kept alive for as long as it is bound)
+
     def set_bank_path(self, path=0):
         """0: the library chooses between the one-launch tick kernel and the composed path, 1: the tick kernel where
         the configuration allows it, 2: always the composed path.  Same bytes either way."""
@@ -1319,6 +1417,7 @@ def facade_lib():
         f.aof_facade_bank_set_stream_output_rate.argtypes = [C.c_void_p, C.c_int, C.c_int]
         f.aof_facade_bank_set_stream_identity.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
         f.aof_facade_bank_set_stream_timestamp_offset.argtypes = [C.c_void_p, C.c_int, C.c_uint64]
+        f.aof_facade_bank_set_stream_sensor.argtypes = [C.c_void_p, C.c_int, C.c_uint64] + [C.c_int] * 5
         f.aof_facade_bank_push.argtypes = [C.c_void_p] * 5
         f.aof_facade_bank_enable_camera.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32]
         f.aof_facade_bank_push_camera.argtypes = [C.c_void_p] * 5
@@ -1463,6 +1562,13 @@ class OpticalFlowBank:
     def setStreamTimestampOffset(self, s, usec):
         """Stream s's own MAVLink time offset (0: no frame for it); ignored once enableImu() is on.  0, or -EINVAL."""
         return facade_lib().aof_facade_bank_set_stream_timestamp_offset(self._h, int(s), int(usec))
+
+    def setStreamSensor(self, s, offset, pitch, width, height, x0, y0):
+        """Stream s's own sensor layout inside the bytes pushCamera() takes: the frame's offset, row pitch, size and the
+        crop's origin.  After enableCamera(), from the next pushCamera() on.  0, or -EINVAL (bad index, no
+        enableCamera(), a record outside the staging buffer)."""
+        return facade_lib().aof_facade_bank_set_stream_sensor(self._h, int(s), int(offset), int(pitch), int(width), int(height),
+                                                              int(x0), int(y0))
 
     def getPyramidLevels(self):
         return facade_lib().aof_facade_bank_pyramid_levels(self._h)

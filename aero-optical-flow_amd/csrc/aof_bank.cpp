@@ -5,8 +5,10 @@
 // (bank frames, new frames) and the commit kernel.  An entry point only packs its arguments.  Nothing here allocates
 // or synchronises.
 #include <cerrno>
+#include <cstdint>
 #include <cstring>
 
+#include "aof_bank_sensor_rule.hpp"
 #include "aof_internal.hpp"
 
 using namespace aof;
@@ -259,6 +261,15 @@ int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank
     const aof_bank_stream *d_streams = bank_streams(ctx, &bound);
     if (d_streams && bound != bp->n_streams)
         return ctx_fail(ctx, -EINVAL, "bank: n_streams differs from the array bound with aof_set_bank_streams");
+    // likewise the sensor records of the camera forms (aof_set_bank_sensors); a round's base, k * round_stride, must be
+    // a number the kernels can form
+    int32_t bound_sensors = 0;
+    uint64_t camera_bytes = 0;
+    const aof_bank_sensor *d_sensors = p.camera ? bank_sensors(ctx, &bound_sensors, &camera_bytes) : nullptr;
+    if (d_sensors && bound_sensors != bp->n_streams)
+        return ctx_fail(ctx, -EINVAL, "bank: n_streams differs from the array bound with aof_set_bank_sensors");
+    if (d_sensors && round_stride > INT64_MAX / AOF_BANK_BURST_MAX)
+        return ctx_fail(ctx, -EINVAL, "bank burst: round_stride too large for sensor records");
     // before the first launch: a faulted or wedged context, or a thread on another device, must not touch the bank
     if ((rc = precheck(ctx))) return rc;
 
@@ -270,6 +281,8 @@ int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank
     BankArgs a = bank_args(bp, L, bank, cur, p.time_us, p.burst ? nullptr : p.select, p.gyro, p.records, p.mavlink, p.mavlink_len,
                            d_streams);
     if (p.camera) camera_args(&a, p.cam, p.src, hist, p.exposure, p.derotated);
+    // (bound: the kernels that take this argument read the crop's place, pitch and origin from record s instead)
+    const BankSensors sen = {d_sensors, camera_bytes, 0};
     aof_flow *flows = reinterpret_cast<aof_flow *>(bank + L.flows);
     const BankBurst b = {p.burst ? p.rounds->n_rounds : 1, round_stride, p.burst ? p.select : nullptr};
 
@@ -281,7 +294,7 @@ int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank
                        plan_small_batch(ctx, a.bank_frames, cur, L.stride, bp->n_streams, flows, bank + L.pub.scratch, &sm) &&
                        (path == 1 || bp->n_streams <= kFusedMaxStreams[p.camera][p.burst]);
     if (fused) {
-        if (p.burst ? launch_bank_burst(sm, a, b, stream) : launch_bank_tick(sm, a, stream))
+        if (p.burst ? launch_bank_burst(sm, a, b, stream, sen) : launch_bank_tick(sm, a, stream, sen))
             return ctx_fail(ctx, -EIO, p.burst ? "bank burst launch failed" : "bank tick launch failed");
         return 0;
     }
@@ -294,13 +307,15 @@ int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank
         if (p.burst) r = round_args(a, k, p.camera ? staging : src);
         if (p.camera) {
             r.cam.camera = src;
-            if (launch_ingest(p.cam->ingest, src, a.cam.camera_stride, bp->n_streams, staging, L.stride, p.exposure ? hist : nullptr, stream))
+            const IngestSensors crop = {d_sensors, (uint64_t)k * (uint64_t)round_stride, camera_bytes, nullptr};
+            if (launch_ingest(p.cam->ingest, src, a.cam.camera_stride, bp->n_streams, staging, L.stride, p.exposure ? hist : nullptr, stream, crop))
                 return ctx_fail(ctx, -EIO, "bank camera ingest launch failed");
         }
         rc = aof_flow_batch_device(ctx, a.bank_frames, r.frames, L.stride, bp->n_streams, nullptr, nullptr, flows,
                                    bank + L.pub.scratch, L.flow_ws_bytes, stream);
         if (rc) return rc;
-        if (launch_bank_commit(r, stream, b.count, b.count ? k : 0)) return ctx_fail(ctx, -EIO, "bank commit launch failed");
+        const BankSensors round_sen = {d_sensors, camera_bytes, (uint64_t)k * (uint64_t)round_stride};
+        if (launch_bank_commit(r, stream, b.count, b.count ? k : 0, round_sen)) return ctx_fail(ctx, -EIO, "bank commit launch failed");
     }
     return 0;
 }
@@ -344,6 +359,58 @@ int aof_set_bank_streams(aof_ctx *ctx, const aof_bank_stream *d_streams, int32_t
     if (!aligned(d_streams, 16)) return ctx_fail(ctx, -EINVAL, "bank streams: the array must be 16-byte aligned");
     set_bank_streams(ctx, d_streams, n_streams);
     return 0;
+}
+
+int aof_set_bank_sensors(aof_ctx *ctx, const aof_bank_sensor *d_sensors, int32_t n_streams, uint64_t camera_bytes)
+{
+    if (!ctx) return -EINVAL;
+    if (d_sensors && n_streams < 1) return ctx_fail(ctx, -EINVAL, "bank sensors: an array needs n_streams >= 1");
+    if (!aligned(d_sensors, 16)) return ctx_fail(ctx, -EINVAL, "bank sensors: the array must be 16-byte aligned");
+    if (d_sensors && camera_bytes == 0) return ctx_fail(ctx, -EINVAL, "bank sensors: an array needs camera_bytes > 0");
+    set_bank_sensors(ctx, d_sensors, n_streams, camera_bytes);
+    return 0;
+}
+
+int aof_bank_sensor_centred(const aof_params *p, uint64_t offset, int32_t pitch, int32_t width, int32_t height, aof_bank_sensor *out)
+{
+    if (!p || !out) return -EINVAL;
+    if (p->width < 1 || p->height < 1 || pitch < width || p->width > width || p->height > height) return -EINVAL;
+    std::memset(out, 0, sizeof(*out));
+    out->offset = offset;
+    out->pitch = pitch;
+    out->width = width; out->height = height;
+    out->x0 = width / 2 - p->width / 2; out->y0 = height / 2 - p->height / 2;   // mainloop.cpp:295-296
+    return 0;
+}
+
+int aof_bank_sensor_from_camera(const aof_params *p, const aof_bank_camera *cam, int32_t stream, aof_bank_sensor *out)
+{
+    if (!p || !cam || !out || stream < 0) return -EINVAL;
+    const aof_ingest_params &g = cam->ingest;
+    if (g.camera_width < 1 || g.camera_height < 1 || cam->camera_stride < 0) return -EINVAL;
+    const uint64_t stride = cam->camera_stride ? (uint64_t)cam->camera_stride : (uint64_t)g.camera_width * (uint64_t)g.camera_height;
+    return aof_bank_sensor_centred(p, (uint64_t)stream * stride, g.camera_width, g.camera_width, g.camera_height, out);
+}
+
+int aof_bank_sensor_valid(const aof_bank_sensor *rec, int32_t crop_width, int32_t crop_height, uint64_t base, uint64_t camera_bytes)
+{
+    if (!rec) return -EINVAL;
+    return bank_sensor_valid(rec->offset, rec->pitch, rec->width, rec->height, rec->x0, rec->y0, crop_width, crop_height, base,
+                             camera_bytes) ? 1 : 0;
+}
+
+int aof_ingest_sensors_device(int32_t crop_width, int32_t crop_height, const uint8_t *d_camera, uint64_t camera_bytes,
+                              const aof_bank_sensor *d_sensors, int64_t n_frames, uint8_t *d_cropped, int64_t cropped_stride,
+                              uint32_t *d_hist, uint8_t *d_ok, void *stream)
+{
+    if (crop_width < 1 || crop_height < 1 || n_frames < 0) return -EINVAL;
+    if (n_frames == 0) return 0;
+    if (!d_camera || !d_sensors || !aligned(d_sensors, 16) || camera_bytes == 0 || (!d_cropped && !d_hist)) return -EINVAL;
+    if (d_cropped && cropped_stride < (int64_t)crop_width * crop_height && n_frames > 1) return -EINVAL;
+    if (n_frames * ((crop_height + 15) / 16) > 0x7FFFFFFF) return -EINVAL;
+    const aof_ingest_params g = {crop_width, crop_height, crop_width, crop_height};   // (the sensor size: the records')
+    const IngestSensors sen = {d_sensors, 0, camera_bytes, d_ok};
+    return launch_ingest(g, d_camera, 0, n_frames, d_cropped, cropped_stride, d_hist, stream, sen) ? -EIO : 0;
 }
 
 int aof_bank_reset_device(aof_ctx *ctx, const aof_bank_params *bp, const uint8_t *d_mask, void *d_bank, size_t bank_bytes,

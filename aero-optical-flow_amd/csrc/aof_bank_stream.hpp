@@ -9,6 +9,7 @@
 #include "aof_derotate.hpp"
 #include "aof_exposure_step.hpp"
 #include "aof_flow_small.hpp"
+#include "aof_bank_sensor_rule.hpp"   // (behind the HIP runtime's qualifiers)
 #include "aof_mavlink.hpp"
 #include "aof_math.h"
 
@@ -16,11 +17,13 @@ namespace aof {
 
 namespace {
 
+// The record of a stream without a frame in round o: idle, or (quality AOF_TICK_BAD_SENSOR) given one its sensor record
+// does not let the kernels read.  Nothing else differs.
 template <bool CAMERA>
-__device__ __forceinline__ void bank_idle(const BankArgs &a, size_t o)
+__device__ __forceinline__ void bank_idle(const BankArgs &a, size_t o, int32_t quality = AOF_TICK_IDLE)
 {
     aof_tick_record rec = {};
-    rec.quality = AOF_TICK_IDLE;
+    rec.quality = quality;
     a.records[o] = rec;
     if (a.mavlink_len) a.mavlink_len[o] = 0;
     if constexpr (CAMERA) {
@@ -66,6 +69,40 @@ __device__ __forceinline__ BankStream bank_stream(const BankArgs &a, uint32_t s)
         v.offset_timestamp_usec = a.offset_timestamp_usec;
         v.system_id = a.system_id; v.component_id = a.component_id; v.first_seq = a.first_seq;
     }
+    return v;
+}
+
+// What stream s's sensor record (aof_set_bank_sensors) means for a crop of w x h in the round whose frames start `base`
+// bytes into the camera buffer: where the crop starts behind the round's first byte, how far apart its rows lie, and
+// whether one byte of it may be read.  The ONE place that is decided: tick, burst, commit and ingest cannot disagree
+// (the rule itself: aof_bank_sensor_rule.hpp, which the host compiles too).  The record is the same for every lane of a
+// workgroup (a workgroup serves one stream, or one strip of one frame): its 32 bytes are read through the scalar path
+// (the constant address space, from an address made of kernel arguments and blockIdx), so the values arrive in scalar
+// registers and the arithmetic below costs no lane anything.  Records rewritten between launches are seen -- the scalar
+// cache does not outlive a launch --, which tests/test_gpu_bank_sensors.py holds with offsets rewritten before every
+// tick, eagerly and through a replayed graph (test_offsets_rewritten_every_tick_eager_and_through_a_replayed_graph).
+struct BankSensor {
+    int64_t origin;    // offset + y0 * pitch + x0 (0 for an invalid record)
+    int32_t pitch;
+    bool ok;
+};
+static_assert(sizeof(aof_bank_sensor) == 32 && offsetof(aof_bank_sensor, pitch) == 8 && offsetof(aof_bank_sensor, width) == 12 &&
+              offsetof(aof_bank_sensor, height) == 16 && offsetof(aof_bank_sensor, x0) == 20 && offsetof(aof_bank_sensor, y0) == 24,
+              "a sensor record is two 16-byte words");
+
+__device__ __forceinline__ BankSensor bank_sensor(const aof_bank_sensor *sensors, size_t s, int32_t w, int32_t h, uint64_t base,
+                                                  uint64_t camera_bytes)
+{
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef const u32x4 __attribute__((address_space(4))) *const_words;
+    const const_words rec = reinterpret_cast<const_words>(reinterpret_cast<uintptr_t>(sensors + s));
+    const u32x4 lo = rec[0], hi = rec[1];
+    const uint64_t offset = (uint64_t)lo.x | (uint64_t)lo.y << 32;
+    const int32_t pitch = (int32_t)lo.z, width = (int32_t)lo.w, height = (int32_t)hi.x, x0 = (int32_t)hi.y, y0 = (int32_t)hi.z;
+    BankSensor v;
+    v.ok = bank_sensor_valid(offset, pitch, width, height, x0, y0, w, h, base, camera_bytes);
+    v.pitch = pitch;
+    v.origin = v.ok ? (int64_t)offset + (int64_t)y0 * pitch + x0 : 0;
     return v;
 }
 
@@ -191,14 +228,17 @@ __device__ __forceinline__ bool bank_first(const BankArgs &a, uint32_t s)
     return s_first != 0;
 }
 
-// CAMERA: is stream s's frame its first (bit 0), and is it due for exposure statistics (bit 1)?  One lane reads the
-// state and the time, like bank_first.
-__device__ __forceinline__ uint32_t bank_gate(const BankArgs &a, uint32_t s)
+// CAMERA: is stream s's frame its first (bit 0), is it due for exposure statistics (bit 1), and does the stream's
+// sensor record keep the kernels from reading it (bit 2: sensor_ok false)?  One lane reads the state and the time, like
+// bank_first.
+constexpr uint32_t kGateFirst = 1u, kGateDue = 2u, kGateBadSensor = 4u;
+__device__ __forceinline__ uint32_t bank_gate(const BankArgs &a, uint32_t s, bool sensor_ok = true)
 {
     __shared__ uint32_t s_gate;
     if (threadIdx.x == 0) {
         const BankState st = a.state[s];
-        s_gate = (st.has_prev == 0 ? 1u : 0u) | (exposure_due(a, st, a.time_us[s]) ? 2u : 0u);
+        s_gate = (st.has_prev == 0 ? kGateFirst : 0u) | (exposure_due(a, st, a.time_us[s]) ? kGateDue : 0u) |
+                 (sensor_ok ? 0u : kGateBadSensor);
     }
     __syncthreads();
     return s_gate;
@@ -235,24 +275,41 @@ __device__ __forceinline__ void bank_histogram(const BankCamera &c, const uint8_
 
 // CAMERA: the crop of a stream's first frame, sensor rows -> LDS -> slot (a first frame is always due: its histogram
 // comes from the LDS copy).  Ends in a barrier.
-__device__ __forceinline__ void crop_first_frame(const BankCamera &c, const uint8_t *src, uint8_t *lds, uint8_t *slot)
+__device__ __forceinline__ void crop_first_frame(const BankCamera &c, const uint8_t *src, int32_t pitch, uint8_t *lds, uint8_t *slot)
 {
     const int row_chunks = c.crop_w / 16, chunks = row_chunks * c.crop_h;
     for (int i = threadIdx.x; i < chunks; i += kThreads) {
         const int y = i / row_chunks, x = i - y * row_chunks;
         uint4 v;
-        __builtin_memcpy(&v, src + (int64_t)y * c.pitch + x * 16, 16);
+        __builtin_memcpy(&v, src + (int64_t)y * pitch + x * 16, 16);
         reinterpret_cast<uint4 *>(lds)[i] = v;
         reinterpret_cast<uint4 *>(slot)[i] = v;
     }
     __syncthreads();
 }
 
-// Where stream s's new frames start: the crop rectangle inside its sensor frame, or its frame in the tick buffer.
+// Where stream s's new frames start and how far apart their rows lie: the crop rectangle inside its sensor frame, or
+// its frame in the tick buffer.  With a BankSensors argument (the instantiations for a bound array): by the stream's
+// record, for the round whose frames start `base` bytes into the camera buffer (a.cam.camera is round 0's first byte);
+// ok false: the record forbids the read (src is then the buffer's first byte and must not be used).  Without one:
+// by the call's scalars, and ok is the constant true -- everything that asks for it folds away.
+struct BankSource {
+    const uint8_t *src;
+    int32_t pitch;
+    bool ok;
+};
 template <bool CAMERA>
-__device__ __forceinline__ const uint8_t *bank_source(const BankArgs &a, uint32_t s)
+__device__ __forceinline__ BankSource bank_source(const BankArgs &a, uint32_t s, uint64_t base = 0)
 {
-    return CAMERA ? a.cam.camera + (int64_t)s * a.cam.camera_stride + a.cam.origin : a.frames + (int64_t)s * a.frame_stride;
+    if constexpr (CAMERA) return BankSource{a.cam.camera + (int64_t)s * a.cam.camera_stride + a.cam.origin, a.cam.pitch, true};
+    else return BankSource{a.frames + (int64_t)s * a.frame_stride, 0, true};
+}
+template <bool CAMERA>
+__device__ __forceinline__ BankSource bank_source(const BankArgs &a, uint32_t s, uint64_t base, const BankSensors &sen)
+{
+    static_assert(CAMERA, "sensor records belong to the camera forms");
+    const BankSensor r = bank_sensor(sen.recs, s, a.cam.crop_w, a.cam.crop_h, sen.camera_base + base, sen.camera_bytes);
+    return BankSource{a.cam.camera + r.origin, r.pitch, r.ok};
 }
 
 // The stream's newest frame out of LDS into its slot, by the whole workgroup.

@@ -428,6 +428,18 @@ void set_bank_streams(aof_ctx *ctx, const aof_bank_stream *d_streams, int32_t n_
     ctx->bank_streams = d_streams;
     ctx->bank_streams_n = d_streams ? n_streams : 0;
 }
+const aof_bank_sensor *bank_sensors(const aof_ctx *ctx, int32_t *n_streams, uint64_t *camera_bytes)
+{
+    *n_streams = ctx->bank_sensors_n;
+    *camera_bytes = ctx->bank_camera_bytes;
+    return ctx->bank_sensors;
+}
+void set_bank_sensors(aof_ctx *ctx, const aof_bank_sensor *d_sensors, int32_t n_streams, uint64_t camera_bytes)
+{
+    ctx->bank_sensors = d_sensors;
+    ctx->bank_sensors_n = d_sensors ? n_streams : 0;
+    ctx->bank_camera_bytes = d_sensors ? camera_bytes : 0;
+}
 
 // Would a sequence-view call (frames viewed twice, n_pairs = frames - 1) run K1 as a pass of its own?  The sequence
 // pipeline asks, because its ingest kernel can leave K1's outputs (pixel sums at ws + L.sums, one level-1 frame per

@@ -129,6 +129,9 @@ struct aof_ctx {
     int bank_path;              // aof_set_bank_path: 0 the library chooses, 1 the one-launch tick kernel, 2 the composed path
     const aof_bank_stream *bank_streams;   // aof_set_bank_streams: the caller's per-stream records (device memory), or nullptr
     int32_t bank_streams_n;     // how many streams they are for
+    const aof_bank_sensor *bank_sensors;   // aof_set_bank_sensors: the caller's per-stream sensor records (device memory), or nullptr
+    int32_t bank_sensors_n;     // how many streams they are for
+    uint64_t bank_camera_bytes; // bytes the caller guarantees readable from the d_camera of its pushes
     bool graph_disabled;        // per-call graphs switched off, or a capture failed once: stay on the plain path
     bool capturing;             // a per-call graph is being captured (no event timing)
     bool wedged;                // a bounded wait for the device ran out: every later call fails, destroy frees nothing

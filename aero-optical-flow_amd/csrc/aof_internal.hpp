@@ -327,16 +327,26 @@ struct BankArgs {
     uint8_t *mavlink_len;          // [S]
     BankCamera cam;                // (last: the plain kernels' argument offsets stay)
 };
+// Per-stream sensor records in place of cam.camera_stride, cam.pitch and cam.origin (aof_set_bank_sensors): a kernel
+// argument of its own that only the instantiations for a bound array have -- with nothing bound the launched kernels
+// and their BankArgs are the ones without it, argument for argument.  recs: [S]; camera_bytes: what the records are
+// valid against; camera_base: bytes between the caller's d_camera and cam.camera (a burst's composed path: round k's
+// launches see cam.camera = d_camera + k * round_stride).  recs == nullptr: nothing bound.
+struct BankSensors {
+    const aof_bank_sensor *recs;
+    uint64_t camera_bytes, camera_base;
+};
 // One launch per tick: a workgroup per stream computes the pair with flow_small_pair, runs the stream's tail and
 // stores the new frame (sm: the small-pair plan of (bank frames, tick frames), flow_small_supported).  With
 // a.cam.camera the workgroup fetches the crop's rows from the stream's sensor frame itself (a.frames is not read).
-int launch_bank_tick(const SmallArgs &sm, const BankArgs &a, void *stream);
+int launch_bank_tick(const SmallArgs &sm, const BankArgs &a, void *stream, const BankSensors &sen = BankSensors{nullptr, 0, 0});
 // Behind aof_flow_batch_device on (bank frames, tick frames): the tail of every stream and the masked copy of the
 // active streams' frames into the bank.  With a.cam.camera: a.frames is the staging region, and the exposure gate,
 // the exposure record and the de-rotated pair come from here as well.
 // A burst's composed path runs it once per round: `a` carries the round's buffers, and stream s is active iff
 // round < count[s] (count NULL: a.active decides, as in a tick).
-int launch_bank_commit(const BankArgs &a, void *stream, const uint8_t *count = nullptr, int32_t round = 0);
+int launch_bank_commit(const BankArgs &a, void *stream, const uint8_t *count = nullptr, int32_t round = 0,
+                       const BankSensors &sen = BankSensors{nullptr, 0, 0});
 // K frame rounds per stream (aof_bank_push_burst_device, k_bank_burst.hip).  Round k's frame of stream s sits
 // round_stride bytes behind round k - 1's; time_us, gyro, records, mavlink_len, mavlink, cam.exposure and
 // cam.derotated of a BankArgs are then dense [K][S] arrays, a.active is not read.
@@ -347,7 +357,8 @@ struct BankBurst {
 };
 // One launch per burst: a workgroup per stream walks its rounds with one frame resident in LDS (same configuration
 // class and same `sm` as launch_bank_tick).
-int launch_bank_burst(const SmallArgs &sm, const BankArgs &a, const BankBurst &b, void *stream);
+int launch_bank_burst(const SmallArgs &sm, const BankArgs &a, const BankBurst &b, void *stream,
+                      const BankSensors &sen = BankSensors{nullptr, 0, 0});
 int launch_bank_reset(BankState *state, const uint8_t *mask, int32_t n_streams, void *stream);
 // The outbox of a push (aof_bank_collect_device, aof_outbox.cpp, k_bank_outbox.hip): compaction of the published records
 // and the due exposure records of n = K * S records into dense lists, and the tag behind them.
@@ -421,6 +432,9 @@ void set_bank_path(aof_ctx *ctx, int path);
 // (aof_batch.cpp) aof_set_bank_streams' binding: the array (nullptr: none) and its stream count
 const aof_bank_stream *bank_streams(const aof_ctx *ctx, int32_t *n_streams);
 void set_bank_streams(aof_ctx *ctx, const aof_bank_stream *d_streams, int32_t n_streams);
+// (aof_batch.cpp) aof_set_bank_sensors' binding: the array (nullptr: none), its stream count and its camera_bytes
+const aof_bank_sensor *bank_sensors(const aof_ctx *ctx, int32_t *n_streams, uint64_t *camera_bytes);
+void set_bank_sensors(aof_ctx *ctx, const aof_bank_sensor *d_sensors, int32_t n_streams, uint64_t camera_bytes);
 // (aof_capi.hip) sticky fault / wedged state and current-device check of a context, before anything is enqueued; and
 // aof_last_error's text for the callers outside aof_capi.hip
 int precheck(aof_ctx *ctx);
@@ -433,9 +447,17 @@ int flow_sequence(aof_ctx *ctx, const uint8_t *d_frames, int64_t n_pairs, aof_fl
 int launch_reduce(const ReduceArgs &a, void *stream);
 int launch_derotate(const aof_derotate_params &p, const aof_flow *flows, const aof_gyro *gyro,
                     int64_t n, float *out, void *stream);
+// sensors.recs (or nullptr: the kernel without the argument): frame i's place, pitch and crop origin come from record i, valid against camera_bytes with
+// `camera` `base` bytes into the caller's buffer (bank_sensor, aof_bank_stream.hpp); p.camera_width / camera_height and
+// camera_stride are then not used.  ok: u8 [n_frames] or nullptr, 1 where the record let the frame be read.
+struct IngestSensors {
+    const aof_bank_sensor *recs;
+    uint64_t base, camera_bytes;
+    uint8_t *ok;
+};
 int launch_ingest(const aof_ingest_params &p, const uint8_t *camera, int64_t camera_stride,
                   int64_t n_frames, uint8_t *cropped, int64_t cropped_stride, uint32_t *hist,
-                  void *stream);
+                  void *stream, const IngestSensors &sensors = IngestSensors{nullptr, 0, 0, nullptr});
 // The sequence pipeline's ingest: the same pass also leaves every frame's level-1 image (l1: [n_frames] frames, or
 // nullptr) and adds its byte sums to the pixel-sum records of the pairs it belongs to (sums: [n_frames - 1][2][2],
 // zeroed here; or nullptr) -- what K1 would otherwise compute in a second pass over the cropped frames.

@@ -20,8 +20,10 @@ namespace {
 
 // (four waves per SIMD: the loop over the rounds costs registers the tick does not need, and 1 024 streams are four
 // workgroups per compute unit -- one VGPR over 128 would leave the fourth one waiting for a whole burst)
-template <bool SUBPIXEL, bool CAMERA>
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_bank_burst(SmallArgs sm, BankArgs a, BankBurst b)
+// Sen: nothing, or one BankSensors (aof_set_bank_sensors; the camera form only): the body of k_bank_burst and of
+// k_bank_burst_sensors below.
+template <bool SUBPIXEL, bool CAMERA, typename... Sen>
+__device__ __forceinline__ void bank_burst_rounds(SmallArgs sm, BankArgs a, BankBurst b, Sen... sen)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_mem[];
     __shared__ aof_flow s_record;
@@ -35,7 +37,16 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
     const int K = b.n_rounds;        // (the launcher: 1..AOF_BANK_BURST_MAX)
     int n = K;                       // the stream has frames in rounds 0..n-1 (uniform)
     if (b.count) n = min((int)b.count[s], K);
-    if (tid < K - n) bank_idle<CAMERA>(a, (size_t)(n + tid) * S + s);
+    if constexpr (sizeof...(Sen) > 0) {
+        // a round's frame lies round_stride bytes behind the previous one's, so the rounds whose record forbids the read
+        // are the stream's last ones -- they get AOF_TICK_BAD_SENSOR and are otherwise idle rounds
+        const int given = n;
+        n = 0;
+        while (n < given && bank_source<true>(a, s, (uint64_t)n * (uint64_t)b.round_stride, sen...).ok) n++;
+        if (tid < K - n) bank_idle<true>(a, (size_t)(n + tid) * S + s, n + tid < given ? AOF_TICK_BAD_SENSOR : AOF_TICK_IDLE);
+    } else {
+        if (tid < K - n) bank_idle<CAMERA>(a, (size_t)(n + tid) * S + s);
+    }
     if (n == 0) return;
 
     if (tid == 0) {
@@ -46,7 +57,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
     __syncthreads();                 // (neither the state nor, behind pass A of the first pair, the slot is read again)
     uint32_t gate = s_gate;
     uint8_t *slot = a.bank_frames + (int64_t)s * a.frame_stride;
-    const uint8_t *base = bank_source<CAMERA>(a, s);
+    const BankSource from = bank_source<CAMERA>(a, s, 0, sen...);
+    const uint8_t *base = from.src;
     uint8_t *const f0[2] = {s_mem, s_mem + a.frame_bytes + kPad};   // flow_small_pair's layout: frame, kPad bytes, frame
     constexpr uint32_t kWindow = CAMERA ? 1u : 0u;
     int newest = -1;                 // the LDS buffer that holds the newest frame; -1: none yet, the slot does
@@ -71,7 +83,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
         const int cur = newest < 0 ? (first ? 0 : 1) : 1 - newest;
         const uint32_t load = first ? 1u : newest < 0 ? 3u : 1u << cur;
         const uint8_t *src = base + (int64_t)k * b.round_stride;
-        flow_small_pair<SUBPIXEL, CAMERA>(r, s, cur ? slot : src, cur ? src : slot, cur, load, &s_record, a.cam.pitch,
+        flow_small_pair<SUBPIXEL, CAMERA>(r, s, cur ? slot : src, cur ? src : slot, cur, load, &s_record, from.pitch,
                                           kWindow << cur, !first);
         // (run_level's last barrier is behind every read of the frames; s_hist is nobody else's)
         if constexpr (CAMERA) {
@@ -90,13 +102,33 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
     store_slot(a, slot, f0[newest]);
 }
 
+template <bool SUBPIXEL, bool CAMERA>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_bank_burst(SmallArgs sm, BankArgs a, BankBurst b)
+{
+    bank_burst_rounds<SUBPIXEL, CAMERA>(sm, a, b);
+}
+
+// The camera burst with a sensor array bound: the same rounds, every round's source from the stream's record.  A kernel
+// of its own name and argument list: with nothing bound the four instantiations above are launched as they always were.
+template <bool SUBPIXEL>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_bank_burst_sensors(SmallArgs sm, BankArgs a, BankBurst b,
+                                                                                                       BankSensors sen)
+{
+    bank_burst_rounds<SUBPIXEL, true>(sm, a, b, sen);
+}
+
 }  // namespace
 
-int launch_bank_burst(const SmallArgs &sm, const BankArgs &a, const BankBurst &b, void *stream)
+int launch_bank_burst(const SmallArgs &sm, const BankArgs &a, const BankBurst &b, void *stream, const BankSensors &sen)
 {
     if (!bank_plan_fits(sm, a)) return (int)hipErrorInvalidValue;
     if (b.n_rounds < 1 || b.n_rounds > AOF_BANK_BURST_MAX) return (int)hipErrorInvalidValue;
     const bool camera = a.cam.camera != nullptr;
+    if (sen.recs) {
+        if (!camera) return (int)hipErrorInvalidValue;
+        return launch_small_class(sm.l0.subpixel ? k_bank_burst_sensors<true> : k_bank_burst_sensors<false>, (uint32_t)a.n_streams, sm,
+                                  stream, sm, a, b, sen);
+    }
     return launch_small_class(camera ? (sm.l0.subpixel ? k_bank_burst<true, true> : k_bank_burst<false, true>)
                                      : (sm.l0.subpixel ? k_bank_burst<true, false> : k_bank_burst<false, false>),
                               (uint32_t)a.n_streams, sm, stream, sm, a, b);

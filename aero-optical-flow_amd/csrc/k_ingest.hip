@@ -18,9 +18,10 @@
 // with ONE butterfly of shuffles and lanes 0..9 add a bin each to the workgroup's LDS histogram.  A workgroup that owns its frame's whole crop
 // (crops of up to 128 rows) stores the ten totals; taller crops take several workgroups per frame, which
 // add to a zeroed histogram with one integer global atomic per bin (order-independent).
-#include "aof_device.hpp"
-#include "aof_exposure_step.hpp"
-#include "aof_internal.hpp"
+// With sensor records (aof_ingest_sensors_device, and the composed path of a camera push with aof_set_bank_sensors) the
+// window's place, row pitch and origin are the frame's own: bank_sensor (aof_bank_stream.hpp), the function the bank's
+// kernels decide with.  A workgroup whose frame's record forbids the read leaves before its first load.
+#include "aof_bank_stream.hpp"   // (kThreads = 256 is the one-workgroup class's: one table entry per lane below)
 
 namespace aof {
 
@@ -37,7 +38,6 @@ struct IngestPyramid {
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kRowsPerBlock = 128;   // (64 / 32 rows per workgroup: 80 / 115 us instead of 68 -- the table and the flush do not amortise)
 constexpr int kLaneField = 6;      // bits per counter of a lane's table sums: <= 3 pieces x 16 pixels = 48 < 64
 constexpr int kLanePieces = 3;     // pieces between two widenings
@@ -79,11 +79,12 @@ __device__ __forceinline__ void flush_counts(uint32_t *s_hist, LaneCounts &n)
     for (int k = 0; k < 5; k++) n.w[k] = 0;
 }
 
-template <bool PYRAMID>
+// Sen: nothing, or one IngestSensors (not with PYRAMID): without records the launched kernel has no such argument.
+template <bool PYRAMID, typename... Sen>
 __global__ __launch_bounds__(kThreads) void k_ingest(aof_ingest_params p, const uint8_t *camera,
                                                      int64_t camera_stride, uint8_t *cropped,
                                                      int64_t cropped_stride, uint32_t *hist, int nstrips,
-                                                     int vec, IngestPyramid pyr)
+                                                     int vec, IngestPyramid pyr, Sen... sensors)
 {
     __shared__ uint32_t s_hist[AOF_EXPOSURE_BINS];
     __shared__ uint2 s_onehot[256];   // grey value -> one-hot increment of a lane's table sums (bins 0..4, bins 5..9)
@@ -107,6 +108,16 @@ __global__ __launch_bounds__(kThreads) void k_ingest(aof_ingest_params p, const 
     mx0 = max(mx0, 0); my0 = max(my0, 0); mx1 = min(mx1, p.crop_width); my1 = min(my1, p.crop_height);
 
     const uint8_t *src = camera + frame * camera_stride + (int64_t)y0 * p.camera_width + x0;
+    int pitch = p.camera_width;
+    if constexpr (sizeof...(Sen) > 0) {   // (uniform, as is the record: one frame per workgroup)
+        static_assert(!PYRAMID, "the sequence pipeline has no records");
+        const IngestSensors &sen = (sensors, ...);
+        const BankSensor r = bank_sensor(sen.recs, (size_t)frame, p.crop_width, p.crop_height, sen.base, sen.camera_bytes);
+        if (sen.ok && strip == 0 && tid == 0) sen.ok[frame] = r.ok ? 1 : 0;
+        if (!r.ok) return;
+        src = camera + r.origin;
+        pitch = r.pitch;
+    }
     uint8_t *dst = cropped ? cropped + frame * cropped_stride : nullptr;
     const int row_begin = strip * kRowsPerBlock, row_end = min(p.crop_height, row_begin + kRowsPerBlock);
 
@@ -133,7 +144,7 @@ __global__ __launch_bounds__(kThreads) void k_ingest(aof_ingest_params p, const 
                 ys[u] = row_begin + (act[u] ? it / pieces : 0);
                 xs[u] = act[u] ? (it % pieces) * 16 : 0;
                 v[u] = make_uint4(0, 0, 0, 0);
-                if (act[u]) __builtin_memcpy(&v[u], src + (int64_t)ys[u] * p.camera_width + xs[u], 16);  // window start may be unaligned
+                if (act[u]) __builtin_memcpy(&v[u], src + (int64_t)ys[u] * pitch + xs[u], 16);  // window start may be unaligned
             }
 #pragma unroll
             for (int u = 0; u < kUnroll; u++, round++) {
@@ -199,7 +210,7 @@ __global__ __launch_bounds__(kThreads) void k_ingest(aof_ingest_params p, const 
         const int items = (row_end - row_begin) * p.crop_width;
         for (int it = tid; it < items; it += kThreads) {
             const int y = row_begin + it / p.crop_width, x = it % p.crop_width;
-            const uint32_t v = src[(int64_t)y * p.camera_width + x];
+            const uint32_t v = src[(int64_t)y * pitch + x];
             if (dst) dst[(int64_t)y * p.crop_width + x] = (uint8_t)v;
             if (hist && y >= my0 && y < my1 && x >= mx0 && x < mx1) {
                 const int b = exposure_bin(v);
@@ -218,7 +229,8 @@ __global__ __launch_bounds__(kThreads) void k_ingest(aof_ingest_params p, const 
 }  // namespace
 
 int launch_ingest(const aof_ingest_params &p, const uint8_t *camera, int64_t camera_stride,
-                  int64_t n_frames, uint8_t *cropped, int64_t cropped_stride, uint32_t *hist, void *stream)
+                  int64_t n_frames, uint8_t *cropped, int64_t cropped_stride, uint32_t *hist, void *stream,
+                  const IngestSensors &sensors)
 {
     if (n_frames == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -229,8 +241,12 @@ int launch_ingest(const aof_ingest_params &p, const uint8_t *camera, int64_t cam
     }
     const int vec = (p.crop_width % 16 == 0) && (!cropped || (reinterpret_cast<uintptr_t>(cropped) % 16 == 0 &&
                                                                 cropped_stride % 16 == 0));
-    hipLaunchKernelGGL(k_ingest<false>, dim3((uint32_t)(n_frames * nstrips)), dim3(kThreads), 0, s, p, camera,
-                       camera_stride, cropped, cropped_stride, hist, nstrips, vec, IngestPyramid{nullptr, nullptr, 0});
+    if (sensors.recs)
+        hipLaunchKernelGGL((k_ingest<false, IngestSensors>), dim3((uint32_t)(n_frames * nstrips)), dim3(kThreads), 0, s, p, camera,
+                           camera_stride, cropped, cropped_stride, hist, nstrips, vec, IngestPyramid{nullptr, nullptr, 0}, sensors);
+    else
+        hipLaunchKernelGGL(k_ingest<false>, dim3((uint32_t)(n_frames * nstrips)), dim3(kThreads), 0, s, p, camera,
+                           camera_stride, cropped, cropped_stride, hist, nstrips, vec, IngestPyramid{nullptr, nullptr, 0});
     return (int)hipGetLastError();
 }
 

@@ -77,6 +77,15 @@ public:
 	// the return value and published(), as push().  Runs camera push, exposure control and collect on the
 	// object's stream.  Needs enableCamera().
 	int pushCamera(const uint8_t *sensor_frames, const uint64_t *img_time_us, const uint8_t *active, const aof_gyro *gyro);
+	// What belongs to ONE camera in front of the crop (include/aof.h, "per-stream sensors"): where stream s's frame lies
+	// in the bytes pushCamera() takes (offset), how far apart its rows are (pitch, >= width: a V4L2 bytesperline), the
+	// size of its grey plane and the origin of the image-sized crop inside it -- cameras of different resolutions, padded
+	// rows, a crop around the principal point, the Y plane of a YUV420 buffer.  pushCamera() keeps taking n_streams *
+	// camera_width * camera_height bytes, laid out as the records say; streams without a call keep enableCamera()'s
+	// layout.  Valid after enableCamera(), from the next pushCamera() on.  Returns 0, or -EINVAL for a bad stream
+	// index, without enableCamera(), or for a record that does not lie inside those bytes (the object unchanged).  An
+	// object on which it was never called runs exactly as one without it.
+	int setStreamSensor(int stream, uint64_t offset, int pitch, int width, int height, int x0, int y0);
 	// The last pushCamera()'s aof_exposure_command [n_streams] in pinned memory (flags 0: the stream's frame
 	// was not due); valid until the next push.  NULL without enableCamera().
 	const aof_exposure_command *exposureCommands() const;

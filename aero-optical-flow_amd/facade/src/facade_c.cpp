@@ -98,6 +98,10 @@ int aof_facade_bank_set_stream_timestamp_offset(void *bank, int stream, uint64_t
 {
 	return static_cast<OpticalFlowBank *>(bank)->setStreamTimestampOffset(stream, offset_usec);
 }
+int aof_facade_bank_set_stream_sensor(void *bank, int stream, uint64_t offset, int pitch, int width, int height, int x0, int y0)
+{
+	return static_cast<OpticalFlowBank *>(bank)->setStreamSensor(stream, offset, pitch, width, height, x0, y0);
+}
 int aof_facade_bank_push(void *bank, const uint8_t *frames, const uint64_t *img_time_us, const uint8_t *active,
 			 const aof_gyro *gyro)
 {

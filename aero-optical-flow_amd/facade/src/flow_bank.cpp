@@ -31,7 +31,7 @@ double secondsSince(std::chrono::steady_clock::time_point t0)
 // Every allocation of one object, recorded where it is made: release() frees them all, the newest first.
 struct Allocations {
 	enum Kind { kDevice, kPinned, kOutbox };   // hipMalloc, hipHostMalloc, aof_outbox_alloc_host: each has its own free
-	struct { void *p; Kind kind; } list[24];   // (20 with every form on, 21 inside enableCamera())
+	struct { void *p; Kind kind; } list[24];   // (22 with every form on, 23 inside enableCamera())
 	int n;
 
 	bool get(void **p, size_t bytes, Kind kind)
@@ -129,6 +129,10 @@ struct OpticalFlowBank::Impl {
 	Staged streams;          // aof_bank_stream [n_streams]
 	bool streams_used, streams_dirty, streams_bound;
 	bool streams_copying;    // a copy of the shadow is enqueued: it is through once collect() has seen the tick's tag
+	// the per-sensor form (setStreamSensor()): allocated by enableCamera(), the shadow records start from what its sensor
+	// size means (aof_bank_sensor_from_camera); nothing is copied or bound before the first call
+	Staged sensors;          // aof_bank_sensor [n_streams]
+	bool sensors_used, sensors_dirty, sensors_bound, sensors_copying;
 
 	int fail(int code, const char *what) { return self->fail(code, what); }
 	int failed(int rc) { return rc ? fail(rc, aof_last_error(ctx)) : 0; }   // of a call of the C ABI
@@ -327,6 +331,27 @@ int OpticalFlowBank::setStreamTimestampOffset(int s, uint64_t offset_usec)
 	return 0;
 }
 
+int OpticalFlowBank::setStreamSensor(int s, uint64_t offset, int pitch, int width, int height, int x0, int y0)
+{
+	Impl *m = _m;
+	if (!m || !m->camera || !m->sensors.h || s < 0 || s >= n_streams) return -EINVAL;
+	aof_bank_sensor rec;
+	std::memset(&rec, 0, sizeof(rec));
+	rec.offset = offset;
+	rec.pitch = pitch;
+	rec.width = width;
+	rec.height = height;
+	rec.x0 = x0;
+	rec.y0 = y0;
+	// the kernels' own rule, against the staging buffer pushCamera() fills: here the host can see the record
+	if (aof_bank_sensor_valid(&rec, image_width, image_height, 0, m->sensor.bytes) != 1)
+		return refuse(-EINVAL, "setStreamSensor(): the record does not describe memory inside the staging buffer");
+	reinterpret_cast<aof_bank_sensor *>(m->sensors.h)[s] = rec;
+	m->sensors_used = true;
+	m->sensors_dirty = true;
+	return 0;
+}
+
 int OpticalFlowBank::getPyramidLevels() const
 {
 	aof_params p;
@@ -419,6 +444,16 @@ int OpticalFlowBank::Impl::receive()
 // still marked dirty, and the object has failed for good by then.
 int OpticalFlowBank::Impl::syncStreams()
 {
+	if (sensors_used) {   // (the same scheme for the sensor records of setStreamSensor())
+		if (sensors_dirty) {
+			if (!sensors.upload(stream, 0, sensors.bytes)) return fail(-EIO, "copy of the per-stream sensor records failed");
+			sensors_copying = true;
+		}
+		if (!sensors_bound) {
+			if (failed(aof_set_bank_sensors(ctx, reinterpret_cast<aof_bank_sensor *>(sensors.d), (int)S, sensor.bytes))) return -EIO;
+			sensors_bound = true;
+		}
+	}
 	if (!streams_used) return 0;
 	if (streams_dirty) {
 		if (!streams.upload(stream, 0, streams.bytes)) return fail(-EIO, "copy of the per-stream records failed");
@@ -459,6 +494,10 @@ int OpticalFlowBank::Impl::collect()
 		streams_copying = false;
 		streams_dirty = false;
 	}
+	if (sensors_copying) {
+		sensors_copying = false;
+		sensors_dirty = false;
+	}
 	if (imu) std::memset(imuCounts(), 0, S);                      // the tick took the queued samples
 	if (rx) std::memset(rxLengths(), 0, S * sizeof(uint16_t));    // and the queued bytes
 	return (int)reinterpret_cast<const aof_outbox_header *>(outbox)->n_messages;
@@ -497,6 +536,7 @@ int OpticalFlowBank::enableCamera(int camera_width, int camera_height, uint16_t 
 	void *bank = NULL;
 	if (!m->mem.get(&bank, L.total_bytes, Allocations::kDevice) ||
 	    !m->sensor.alloc(m->mem, S * (size_t)camera_width * (size_t)camera_height) ||
+	    !m->sensors.alloc(m->mem, S * sizeof(aof_bank_sensor)) ||
 	    !m->mem.get((void **)&m->d_exposure, S * sizeof(aof_exposure_record), Allocations::kDevice) ||
 	    !m->mem.get((void **)&m->d_exposure_state, S * sizeof(aof_exposure_state), Allocations::kDevice) ||
 	    !m->mem.get((void **)&m->commands, S * sizeof(aof_exposure_command), Allocations::kOutbox))
@@ -506,6 +546,7 @@ int OpticalFlowBank::enableCamera(int camera_width, int camera_height, uint16_t 
 	m->d_bank = bank;
 	m->bank_bytes = L.total_bytes;
 	m->cam = cam;
+	for (size_t s = 0; s < S; s++) aof_bank_sensor_from_camera(&p, &cam, (int32_t)s, reinterpret_cast<aof_bank_sensor *>(m->sensors.h) + s);
 	aof_exposure_control_default(&m->ec);
 	std::memset(m->commands, 0, S * sizeof(aof_exposure_command));
 	// every stream starts over, and every controller from exposure0 / gain0

@@ -493,8 +493,9 @@ int aof_set_bank_path(aof_ctx *ctx, int path);
  * Contract: stream s's records, frames, lengths, stored frame and state are byte-identical to what a bank of ONE stream
  * produces for the same inputs when its aof_bank_params carries record s's values; and if all S records equal
  * aof_bank_stream_from_params(bp), every output and the whole bank are byte-identical to the unbound call.
- * Not per stream, and as they were: the exposure interval and the exposure-control constants, the frame size, the
- * sequence pipeline (aof_sequence_device) and the per-call facade classes. */
+ * Not per stream, and as they were: the exposure interval and the exposure-control constants, the engine's frame size
+ * (the crop; the sensor's size is per stream through aof_set_bank_sensors, below), the sequence pipeline
+ * (aof_sequence_device) and the per-call facade classes. */
 typedef struct aof_bank_stream {     /* 32 bytes, 16-byte aligned, one per stream */
     float    focal_x, focal_y;        /* px */
     int32_t  output_rate;             /* Hz; <= 0 publishes every frame */
@@ -610,6 +611,69 @@ int aof_bank_push_camera_burst_device(aof_ctx *ctx, const aof_bank_params *bp, c
                                       const uint8_t *d_count, const aof_gyro *d_gyro, void *d_bank, size_t bank_bytes,
                                       aof_tick_record *d_records, aof_exposure_record *d_exposure, float *d_derotated,
                                       uint8_t *d_mavlink, uint8_t *d_mavlink_len, void *stream);
+
+/* ---- the stream bank with per-stream sensors: size, row pitch, crop origin and place of every camera's frame ----
+ * aof_bank_camera carries ONE sensor size for all S streams, rows exactly camera_width bytes apart, frames camera_stride
+ * apart and the reference's centre crop.  Real fleets mix resolutions, drivers pad rows (V4L2 bytesperline), a
+ * calibrated camera is cropped around its principal point, and a frame sits wherever its capture buffer is.  A caller
+ * may therefore bind an array of S sensor records in device memory to the context; while it is bound, stream s of the
+ * camera pushes (aof_bank_push_camera_device, aof_bank_push_camera_burst_device) takes its new frame from
+ *     d_camera + k*round_stride + offset + (y0 + y)*pitch + x0 + x,   0 <= y < crop_height, 0 <= x < crop_width
+ * (k: the round of a burst, 0 for a tick).  From the cropped frame on nothing changes.
+ * Validity is decided on the device, per stream and round (the host cannot see device data).  A record is valid iff
+ *     width >= 1, height >= 1, pitch >= width;  x0 >= 0, y0 >= 0, x0 + crop_width <= width, y0 + crop_height <= height;
+ *     k*round_stride + offset + (height-1)*pitch + width <= camera_bytes     (in 64 bits, nothing wraps),
+ * camera_bytes being the number of bytes the caller guarantees readable from the d_camera of the pushes.  A stream with
+ * an invalid record is treated exactly as an idle stream in that round: not one byte of its sensor frame is read, its
+ * bank bytes are not written, its exposure record, de-rotated pair and MAVLink length are the idle ones -- only the tick
+ * record's quality is AOF_TICK_BAD_SENSOR instead of AOF_TICK_IDLE.  aof_bank_collect_device and aof_bank_imu_device need
+ * no change: they pass or skip every record with quality < 0.
+ * Contract (a bank of one): stream s's records, wire frames, exposure records, de-rotated pairs, stored frame and state
+ * (exposure gate included) are byte-identical to those of a one-stream camera bank whose aof_bank_camera has
+ * camera_width = pitch_s, camera_height = height_s, whose d_camera points at offset_s and whose crop sits at (x0_s, y0_s)
+ * where the unbound form would have centred it.  S records equal to aof_bank_sensor_from_camera(p, cam, s) change no byte
+ * of any output or of the bank.  With an array bound, cam->ingest.camera_width / camera_height and cam->camera_stride
+ * are checked exactly as without one and used by no kernel (a burst's round_stride 0 still means n_streams *
+ * camera_stride); the exposure mask depends on the crop size only.  With nothing bound every kernel runs on its
+ * arguments as before.  A burst indexes the array by the stream alone, its outputs by round * S + stream.
+ * The KERNELS read the array when they run: records may be rewritten between ticks in stream order (a ring of capture
+ * buffers: a new offset every tick), and a captured graph replays against the current contents.
+ * Still not per stream: the ENGINE's frame size (the crop) is the context's. */
+#define AOF_TICK_BAD_SENSOR (-5)     /* the stream's sensor record does not describe memory inside the camera buffer */
+typedef struct aof_bank_sensor {     /* 32 bytes, 16-byte aligned, one per stream */
+    uint64_t offset;                 /* bytes from d_camera (round k of a burst: + k*round_stride) to the frame's first byte */
+    int32_t  pitch;                  /* bytes between rows, >= width */
+    int32_t  width, height;          /* the grey (Y) plane, pixels */
+    int32_t  x0, y0;                 /* crop origin inside it; the crop is the context's width x height */
+    uint32_t reserved;               /* 0 */
+} aof_bank_sensor;
+/* Stores the pointer and camera_bytes on the context, like aof_set_bank_streams: enqueues nothing, allocates nothing,
+ * reads nothing.  d_sensors: aof_bank_sensor [n_streams] in device memory owned by the caller, alive and 16-byte aligned
+ * for as long as it is bound; NULL (with n_streams 0) unbinds.  A camera push whose bp->n_streams differs from the bound
+ * count returns -EINVAL and writes nothing; the pushes of pre-cropped frames do not look at the binding.
+ * -EINVAL: NULL ctx, a non-NULL array with n_streams < 1, an array that is not 16-byte aligned, camera_bytes == 0 with
+ * an array (the binding stays as it was). */
+int aof_set_bank_sensors(aof_ctx *ctx, const aof_bank_sensor *d_sensors, int32_t n_streams, uint64_t camera_bytes);
+/* Host only: the record the scalars of cam mean for stream `stream`: offset = stream * camera_stride (camera_width *
+ * camera_height where camera_stride is 0), pitch = width = camera_width, height = camera_height, the centre crop of
+ * p->width x p->height.  -EINVAL: NULL p / cam / out, stream < 0, a crop that is not inside the sensor frame. */
+int aof_bank_sensor_from_camera(const aof_params *p, const aof_bank_camera *cam, int32_t stream, aof_bank_sensor *out);
+/* Host only: the same centre rule (x0 = width/2 - p->width/2, y0 likewise) for a caller's own place, pitch and size.
+ * -EINVAL: NULL p / out, pitch < width, a crop that is not inside width x height. */
+int aof_bank_sensor_centred(const aof_params *p, uint64_t offset, int32_t pitch, int32_t width, int32_t height, aof_bank_sensor *out);
+/* Host only: the kernels' validity rule (the same function, compiled for the host) on one record: 1 valid, 0 not, for a
+ * crop of crop_width x crop_height, the round's base = k*round_stride and camera_bytes.  -EINVAL: NULL rec. */
+int aof_bank_sensor_valid(const aof_bank_sensor *rec, int32_t crop_width, int32_t crop_height, uint64_t base, uint64_t camera_bytes);
+/* aof_ingest_batch_device for frames that sensor records describe: frame i is the crop_width x crop_height rectangle at
+ * (x0_i, y0_i) of the frame at d_camera + offset_i with rows pitch_i apart; d_cropped, cropped_stride and d_hist as
+ * there (either output may be NULL).  A frame whose record is not valid against camera_bytes (base 0) is not read;
+ * d_ok: u8 [n_frames] or NULL: 1 for a valid record, 0 for an invalid one, whose cropped frame and histogram are then
+ * unspecified (with crops of more than 128 rows its histogram is zero).  Stateless, asynchronous on `stream`.
+ * -EINVAL: crop_width or crop_height < 1, n_frames < 0, NULL d_camera or d_sensors, d_sensors not 16-byte aligned,
+ * camera_bytes 0, both outputs NULL, a cropped_stride below one crop. */
+int aof_ingest_sensors_device(int32_t crop_width, int32_t crop_height, const uint8_t *d_camera, uint64_t camera_bytes,
+                              const aof_bank_sensor *d_sensors, int64_t n_frames, uint8_t *d_cropped, int64_t cropped_stride,
+                              uint32_t *d_hist, uint8_t *d_ok, void *stream);
 
 /* ---- the stream bank's outbox: the published messages of a push as one dense, ordered, host-pollable list ----
  * A push leaves [K][S] records of which most say "nothing to do": the limiter publishes at 15 Hz from 75 Hz cameras, the

@@ -44,6 +44,14 @@ focal lengths, output rate, offset and MAVLink identity) against the tick on the
   U1 / U2       aof_bank_push_device, nothing bound, on the one-launch kernel (1) and the composed path (2) -- also what a
                 build without the call runs (AOF_LIB: the yardstick of U on this build);
   P1 / P2       the same tick with S distinct records bound.
+With --per-sensor, the camera tick with an array of per-stream sensor records bound (aof_set_bank_sensors: S records equal
+to aof_bank_sensor_from_camera, so both legs move the same bytes and the difference is the record's load and check)
+against the camera tick on the scalars of aof_bank_camera, 64x64 from 320x240 and 128x128 from 640x480:
+  K1 / K2       aof_bank_push_camera_device, nothing bound, on the one-launch kernel (1) and the composed path (2) -- also
+                what a build without the call runs (AOF_LIB: the yardstick of K on this build);
+  S1 / S2       the same tick with the S records bound.
+K1 / K2 are the legs --camera runs under those names (leg_camera); --per-sensor --legs K1,K2 runs them alone, which is how
+two builds of the library are compared in turn in one session.
 Every leg settles for about 0.2 s of untimed ticks, then times at least --ticks ticks and at least --seconds seconds
 with the host clock around ticks that end in a synchronise.  The whole sweep runs --repeats times: the difference
 between the repeats is the run-to-run spread a difference between legs has to beat.
@@ -54,7 +62,8 @@ between the repeats is the run-to-run spread a difference between legs has to be
     python tools/bench_bank.py --exposure-control > profiles/bank_exposure_control_sweep.txt
     python tools/bench_bank.py --imu > profiles/bank_imu_sweep.txt
     python tools/bench_bank.py --mavlink-rx > profiles/bank_mavlink_rx_sweep.txt
-    python tools/bench_bank.py --per-stream --streams 64,1024 > profiles/bank_per_stream_ab.txt"""
+    python tools/bench_bank.py --per-stream --streams 64,1024 > profiles/bank_per_stream_ab.txt
+    python tools/bench_bank.py --per-sensor --streams 64,1024 > profiles/bank_per_sensor_ab.txt"""
 import argparse
 import ctypes as C
 import importlib
@@ -179,12 +188,15 @@ def sensor_frames(p, S, inp, dev, cam_w, cam_h):
     return out
 
 
-def leg_camera(p, S, path, inp, cams, dev, a, cam_w, cam_h):
+def leg_camera(p, S, path, inp, cams, dev, a, cam_w, cam_h, per_sensor=False):
     eng = aof.FlowEngine(p, 0)
     eng.set_bank_path(path)
     bp = aof.bank_params(S, FX, FY, 15, 5_000_000, 1, 100, 0)
     cam = aof.bank_camera_params(cam_w, cam_h, p.width, p.height, 0, 200_000, DEROTATE, FX, FY)
     bank = eng.bank_create(bp, dev, camera=cam)
+    if per_sensor:
+        table = aof.bank_sensor_from_camera(p, cam, n=S)
+        eng.set_bank_sensors(torch.from_numpy(table.view(np.uint8).reshape(S, 32)).to(dev), S, S * cam_w * cam_h)
     recs = torch.empty((S, 48), dtype=torch.uint8, device=dev)
     expo = torch.empty((S, 48), dtype=torch.uint8, device=dev)
     derot = torch.empty((S, 2), dtype=torch.float32, device=dev)
@@ -1096,6 +1108,41 @@ def per_stream_sweep(a, dev):
             print(line)
 
 
+def per_sensor_sweep(a, dev):
+    print("# legs: K1/K2 camera tick on the scalars of aof_bank_camera on path 1/2, S1/S2 the same tick with S aof_bank_sensor "
+          "records equal to aof_bank_sensor_from_camera bound (exposure records, de-rotation, MAVLink frames on, all streams active)")
+    print("# us = microseconds per tick (host clock, ticks ending in a synchronise)")
+    bound = hasattr(aof.lib, "aof_set_bank_sensors")      # (AOF_LIB may name a build without the call: K legs only)
+    legs = [("K1", 1, False), ("K2", 2, False)] + ([("S1", 1, True), ("S2", 2, True)] if bound else [])
+    if a.legs is not None:                                # (--legs K1,K2: the same legs from two builds, alternating)
+        legs = [leg for leg in legs if leg[0] in a.legs.split(",")]
+        bound = bound and len(legs) == 4
+    sizes = [int(s) for s in a.streams.split(",")]
+    results = {}
+    for rep in range(a.repeats):
+        for cfg in a.configs.split(","):
+            p = params_of(cfg)
+            cam_w, cam_h = SENSOR[cfg]
+            for S in sizes:
+                inp = Inputs(p, S, dev)
+                cams = sensor_frames(p, S, inp, dev, cam_w, cam_h)
+                for name, path, per_sensor in legs:
+                    sec, n = leg_camera(p, S, path, inp, cams, dev, a, cam_w, cam_h, per_sensor)
+                    results.setdefault((cfg, S, name), []).append(sec)
+                    print(f"rep {rep} {cfg:11s} S={S:6d} {name:2s} {sec * 1e6:10.2f} us  ({n} ticks)", flush=True)
+                del inp, cams
+                torch.cuda.empty_cache()
+    print("# ---- summary (median of the repeats; spread = (max - min) of the repeats / median) ----")
+    for cfg in a.configs.split(","):
+        for S in sizes:
+            m = {n: float(np.median(results[(cfg, S, n)])) for n, _, _ in legs}
+            sp = {n: (max(results[(cfg, S, n)]) - min(results[(cfg, S, n)])) / m[n] for n in m}
+            line = f"{cfg:11s} S={S:6d}  " + "  ".join(f"{n} {m[n] * 1e6:9.2f} us (+-{sp[n] * 100:4.1f} %)" for n in m)
+            if bound:
+                line += f"  S1/K1 {m['S1'] / m['K1']:5.3f}  S2/K2 {m['S2'] / m['K2']:5.3f}"
+            print(line)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--streams", default="1,16,64,128,256,1024,4096,16384")
@@ -1105,7 +1152,8 @@ def main():
     ap.add_argument("--settle", type=float, default=0.2, help="untimed seconds in front of every leg")
     ap.add_argument("--repeats", type=int, default=2)
     ap.add_argument("--contexts-max", type=int, default=64, help="largest S of the B leg")
-    ap.add_argument("--legs", default="T0,T1,T2,C,B", help="legs to run (a kernel trace wants one at a time)")
+    ap.add_argument("--legs", default=None, help="legs to run (a kernel trace wants one at a time); default: T0,T1,T2,C,B, with "
+                    "--per-sensor K1,K2,S1,S2")
     ap.add_argument("--no-marker", action="store_true")
     ap.add_argument("--camera", action="store_true", help="the sweep of the tick on raw sensor frames (legs K0, K1, K2, Y, T0)")
     ap.add_argument("--burst", default="", help="K[,K...]: the sweep of bursts of K rounds against K single ticks (legs B0-B2, T0-T2)")
@@ -1114,9 +1162,13 @@ def main():
     ap.add_argument("--imu", action="store_true", help="the sweep of the IMU call: legs G, D")
     ap.add_argument("--mavlink-rx", action="store_true", help="the sweep of the MAVLink receive: legs H, D on two traffic mixes")
     ap.add_argument("--per-stream", action="store_true", help="the plain tick with per-stream records bound against the unbound tick: legs U1, U2, P1, P2")
+    ap.add_argument("--per-sensor", action="store_true", help="the camera tick with per-stream sensor records bound against the unbound camera tick: legs K1, K2, S1, S2 "
+                    "(K1 / K2 are --camera's legs of those names, the same leg_camera; --legs K1,K2 runs them alone, for two builds in turn)")
     ap.add_argument("--forms", default="plain,camera", help="--burst: entry points to sweep")
     ap.add_argument("--input-bytes-max", type=float, default=24 * 2**30, help="--burst: sizes whose K rounds of input exceed this are skipped")
     a = ap.parse_args()
+    if a.legs is None and not a.per_sensor:
+        a.legs = "T0,T1,T2,C,B"
     if a.burst and a.ticks == ap.get_default("ticks"):
         a.ticks = 1000           # (frame rounds)
     if a.camera and a.streams == ap.get_default("streams"):
@@ -1136,6 +1188,8 @@ def main():
         print(f"# class marker: exhaustive C2 K2 (1 024 VGA pairs) {class_marker(dev):.4f} ms")
     if a.per_stream:
         return per_stream_sweep(a, dev)
+    if a.per_sensor:
+        return per_sensor_sweep(a, dev)
     if a.mavlink_rx:
         return mavlink_rx_sweep(a, dev)
     if a.imu:
