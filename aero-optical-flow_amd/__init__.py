@@ -130,6 +130,7 @@ class BankBurst(C.Structure):
 
 BANK_BURST_MAX = 16
 TICK_HELD, TICK_IDLE = -1, -2
+PIXEL_GREY8, PIXEL_LUMA16_LO, PIXEL_LUMA16_HI = 0, 1, 2   # AOF_PIXEL_*: a stream's pixel format (aof_set_bank_pixel_formats)
 TICK_BAD_SENSOR = -5   # the stream's sensor record (aof_bank_sensor) does not describe memory inside the camera buffer
 TICK_DTYPE = np.dtype([("quality", "<i4"), ("dt_us", "<i4"), ("flow_x", "<f4"), ("flow_y", "<f4"),
                        ("gyro_x", "<f4"), ("gyro_y", "<f4"), ("gyro_z", "<f4"), ("frame", "<u4"), ("pixel", FLOW_DTYPE)])
@@ -286,6 +287,9 @@ def _load():
         "aof_bank_sensor_centred": (C.c_int, [P(Params), C.c_uint64, C.c_int32, C.c_int32, C.c_int32, P(BankSensor)]),
         "aof_bank_sensor_valid": (C.c_int, [P(BankSensor), C.c_int32, C.c_int32, C.c_uint64, C.c_uint64]),
         "aof_ingest_sensors_device": (C.c_int, [C.c_int32, C.c_int32, VP, C.c_uint64, VP, I64, VP, I64, VP, VP, VP]),
+        "aof_set_bank_pixel_formats": (C.c_int, [VP, VP, C.c_int32]),
+        "aof_bank_sensor_valid_format": (C.c_int, [P(BankSensor), C.c_uint8, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64]),
+        "aof_ingest_sensor_formats_device": (C.c_int, [C.c_int32, C.c_int32, VP, C.c_uint64, VP, VP, I64, VP, I64, VP, VP, VP]),
         "aof_bank_camera_layout": (C.c_int, [P(Params), P(BankParams), P(BankCamera), P(BankLayout), P(C.c_size_t)]),
         "aof_bank_push_camera_device": (C.c_int, [VP, P(BankParams), P(BankCamera), VP, VP, VP, VP, VP, C.c_size_t, VP, VP, VP,
                                                   VP, VP, VP]),
@@ -495,24 +499,30 @@ def bank_sensor_centred(p: Params, offset, pitch, width, height):
     return _sensor_record(rec)
 
 
-def bank_sensor_valid(rec, crop_w, crop_h, camera_bytes, base=0) -> bool:
-    """aof_bank_sensor_valid: the kernels' validity rule on one BANK_SENSOR_DTYPE record, compiled for the host."""
+def bank_sensor_valid(rec, crop_w, crop_h, camera_bytes, base=0, format=0) -> bool:
+    """aof_bank_sensor_valid / aof_bank_sensor_valid_format: the kernels' validity rule on one BANK_SENSOR_DTYPE record of
+    pixel format ``format`` (PIXEL_*), compiled for the host."""
     r = BankSensor.from_buffer_copy(np.asarray(rec, dtype=BANK_SENSOR_DTYPE).tobytes())
-    rc = lib.aof_bank_sensor_valid(C.byref(r), int(crop_w), int(crop_h), int(base), int(camera_bytes))
+    if format == 0:
+        rc = lib.aof_bank_sensor_valid(C.byref(r), int(crop_w), int(crop_h), int(base), int(camera_bytes))
+    else:
+        rc = lib.aof_bank_sensor_valid_format(C.byref(r), int(format) & 0xFF, int(crop_w), int(crop_h), int(base), int(camera_bytes))
     if rc < 0:
         raise AofError(rc, lib.aof_strerror(rc).decode())
     return bool(rc)
 
 
 def ingest_sensors(camera, sensors, crop_w, crop_h, camera_bytes=None, cropped=None, hist=None, ok=None, want_cropped=True,
-                   want_hist=True, want_ok=True):
+                   want_hist=True, want_ok=True, formats=None):
     """aof_ingest_sensors_device: frame ingest on the device for frames that sensor records describe.  camera: uint8 CUDA
     tensor (any shape; the records' offsets count from its first byte); sensors: uint8 CUDA tensor of n * 32 bytes
-    (BANK_SENSOR_DTYPE, 16-byte aligned); camera_bytes: bytes of ``camera`` the kernel may read (default: all).  Returns
+    (BANK_SENSOR_DTYPE, 16-byte aligned); camera_bytes: bytes of ``camera`` the kernel may read (default: all).
+    formats: None, or a uint8 CUDA tensor of n pixel formats (PIXEL_*; aof_ingest_sensor_formats_device).  Returns
     (cropped [n, crop_h, crop_w], hist [n, 10] int32, ok [n] uint8), None where not wanted."""
     import torch
     assert camera.dtype == torch.uint8 and sensors.dtype == torch.uint8 and sensors.is_contiguous() and sensors.numel() % 32 == 0
     n = sensors.numel() // 32
+    assert formats is None or (formats.dtype == torch.uint8 and formats.is_contiguous() and formats.numel() == n)
     dev = camera.device
     if cropped is None and want_cropped:
         cropped = torch.empty((n, crop_h, crop_w), dtype=torch.uint8, device=dev)
@@ -521,10 +531,13 @@ def ingest_sensors(camera, sensors, crop_w, crop_h, camera_bytes=None, cropped=N
     if ok is None and want_ok:
         ok = torch.empty((n,), dtype=torch.uint8, device=dev)
     opt = lambda t: t.data_ptr() if t is not None else None
-    rc = lib.aof_ingest_sensors_device(int(crop_w), int(crop_h), camera.data_ptr(),
-                                       camera.numel() if camera_bytes is None else int(camera_bytes), sensors.data_ptr(), n,
-                                       opt(cropped), cropped.stride(0) if cropped is not None and n else crop_w * crop_h,
-                                       opt(hist), opt(ok), torch.cuda.current_stream(dev).cuda_stream)
+    tail = (n, opt(cropped), cropped.stride(0) if cropped is not None and n else crop_w * crop_h, opt(hist), opt(ok),
+            torch.cuda.current_stream(dev).cuda_stream)
+    head = (int(crop_w), int(crop_h), camera.data_ptr(), camera.numel() if camera_bytes is None else int(camera_bytes), sensors.data_ptr())
+    if formats is None:
+        rc = lib.aof_ingest_sensors_device(*head, *tail)
+    else:
+        rc = lib.aof_ingest_sensor_formats_device(*head, formats.data_ptr(), *tail)
     if rc:
         raise AofError(rc, lib.aof_strerror(rc).decode())
     return cropped, hist, ok
@@ -1293,6 +1306,22 @@ class FlowEngine:
         self._check(lib.aof_set_bank_sensors(self._ctx, sensors.data_ptr(), n, int(camera_bytes)))
         self._bank_sensors = sensors   # (kept alive for as long as it is bound)
 
+    def set_bank_pixel_formats(self, formats=None, n_streams=None):
+        """aof_set_bank_pixel_formats: binds a uint8 CUDA tensor of S pixel formats (PIXEL_GREY8, PIXEL_LUMA16_LO,
+        PIXEL_LUMA16_HI; any alignment) to the context, or with None unbinds.  n_streams: S, where the tensor holds more.
+        Used by the camera pushes next to bound sensor records (set_bank_sensors): stream s's crop then comes from pixels
+        of one or two bytes.  The kernels read it when they run: keep it alive; it may be rewritten between ticks."""
+        if formats is None:
+            self._check(lib.aof_set_bank_pixel_formats(self._ctx, None, 0))
+            self._bank_formats = None
+            return
+        import torch
+        assert formats.dtype == torch.uint8 and formats.is_contiguous()
+        n = formats.numel() if n_streams is None else int(n_streams)
+        assert n <= formats.numel()
+        self._check(lib.aof_set_bank_pixel_formats(self._ctx, formats.data_ptr(), n))
+        self._bank_formats = formats   # (kept alive for as long as it is bound)
+
     def set_bank_path(self, path=0):
         """0: the library chooses between the one-launch tick kernel and the composed path, 1: the tick kernel where
         the configuration allows it, 2: always the composed path.  Same bytes either way."""
@@ -1418,6 +1447,8 @@ def facade_lib():
         f.aof_facade_bank_set_stream_identity.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
         f.aof_facade_bank_set_stream_timestamp_offset.argtypes = [C.c_void_p, C.c_int, C.c_uint64]
         f.aof_facade_bank_set_stream_sensor.argtypes = [C.c_void_p, C.c_int, C.c_uint64] + [C.c_int] * 5
+        f.aof_facade_bank_set_stream_pixel_format.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        f.aof_facade_bank_enable_camera_packed.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32]
         f.aof_facade_bank_push.argtypes = [C.c_void_p] * 5
         f.aof_facade_bank_enable_camera.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32]
         f.aof_facade_bank_push_camera.argtypes = [C.c_void_p] * 5
@@ -1611,8 +1642,23 @@ class OpticalFlowBank:
             self._sensor = int(camera_width) * int(camera_height)
         return rc
 
+    def enableCameraPacked(self, camera_width, camera_height, format, exposure0=1, gain0=1, exposure_interval_us=200000):
+        """enableCamera() for cameras that all deliver pixel format ``format`` (PIXEL_*): pushCamera() then takes
+        camera_width x camera_height pixels of one or two bytes per stream.  Returns 0 or a negative value."""
+        rc = facade_lib().aof_facade_bank_enable_camera_packed(self._h, int(camera_width), int(camera_height), int(format),
+                                                               int(exposure0), int(gain0), int(exposure_interval_us))
+        if rc == 0:
+            self._sensor = int(camera_width) * int(camera_height) * (1 if int(format) == PIXEL_GREY8 else 2)
+        return rc
+
+    def setStreamPixelFormat(self, s, format):
+        """Stream s's own pixel format (PIXEL_*) inside the bytes pushCamera() takes, from the next pushCamera() on.  0, or
+        -EINVAL (bad index, a format above 2, before enableCamera(), a record that no longer fits those bytes)."""
+        return facade_lib().aof_facade_bank_set_stream_pixel_format(self._h, int(s), int(format))
+
     def pushCamera(self, sensor_frames, img_time_us, active=None, gyro=None):
-        """sensor_frames uint8 [S, camera_height, camera_width]; the rest and the return value as push()."""
+        """sensor_frames uint8 [S, camera_height, camera_width] (enableCameraPacked(): [S, camera_height, camera_width *
+        bpp]); the rest and the return value as push()."""
         assert getattr(self, "_sensor", None), "pushCamera() needs enableCamera()"
         return self._push(facade_lib().aof_facade_bank_push_camera, sensor_frames, self._sensor, img_time_us, active, gyro)
 

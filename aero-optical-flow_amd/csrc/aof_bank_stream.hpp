@@ -81,9 +81,13 @@ __device__ __forceinline__ BankStream bank_stream(const BankArgs &a, uint32_t s)
 // registers and the arithmetic below costs no lane anything.  Records rewritten between launches are seen -- the scalar
 // cache does not outlive a launch --, which tests/test_gpu_bank_sensors.py holds with offsets rewritten before every
 // tick, eagerly and through a replayed graph (test_offsets_rewritten_every_tick_eager_and_through_a_replayed_graph).
+// With a format array bound as well (aof_set_bank_pixel_formats) stream s's format byte decides bpp and phase; it is
+// read by the lanes (one byte, no alignment, nothing outside formats[0..S)) and made uniform, so every branch on it is
+// a scalar one.  A value that is no format makes the record invalid (bank_sensor_valid's bpp 0).
 struct BankSensor {
-    int64_t origin;    // offset + y0 * pitch + x0 (0 for an invalid record)
+    int64_t origin;    // offset + y0 * pitch + x0 * bpp + phase (0 for an invalid record)
     int32_t pitch;
+    int32_t bpp, phase;   // bytes per pixel (1, 2); which of a pixel's bytes is its grey value
     bool ok;
 };
 static_assert(sizeof(aof_bank_sensor) == 32 && offsetof(aof_bank_sensor, pitch) == 8 && offsetof(aof_bank_sensor, width) == 12 &&
@@ -91,7 +95,7 @@ static_assert(sizeof(aof_bank_sensor) == 32 && offsetof(aof_bank_sensor, pitch) 
               "a sensor record is two 16-byte words");
 
 __device__ __forceinline__ BankSensor bank_sensor(const aof_bank_sensor *sensors, size_t s, int32_t w, int32_t h, uint64_t base,
-                                                  uint64_t camera_bytes)
+                                                  uint64_t camera_bytes, const uint8_t *formats = nullptr)
 {
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     typedef const u32x4 __attribute__((address_space(4))) *const_words;
@@ -100,9 +104,14 @@ __device__ __forceinline__ BankSensor bank_sensor(const aof_bank_sensor *sensors
     const uint64_t offset = (uint64_t)lo.x | (uint64_t)lo.y << 32;
     const int32_t pitch = (int32_t)lo.z, width = (int32_t)lo.w, height = (int32_t)hi.x, x0 = (int32_t)hi.y, y0 = (int32_t)hi.z;
     BankSensor v;
-    v.ok = bank_sensor_valid(offset, pitch, width, height, x0, y0, w, h, base, camera_bytes);
+    v.bpp = 1; v.phase = 0;
+    if (formats) {
+        const uint32_t format = (uint32_t)__builtin_amdgcn_readfirstlane((int)formats[s]);
+        v.bpp = bank_pixel_bpp(format); v.phase = bank_pixel_phase(format);
+    }
+    v.ok = bank_sensor_valid(offset, pitch, width, height, x0, y0, w, h, base, camera_bytes, v.bpp);
     v.pitch = pitch;
-    v.origin = v.ok ? (int64_t)offset + (int64_t)y0 * pitch + x0 : 0;
+    v.origin = v.ok ? (int64_t)offset + (int64_t)y0 * pitch + (int64_t)x0 * v.bpp + v.phase : 0;
     return v;
 }
 
@@ -273,15 +282,41 @@ __device__ __forceinline__ void bank_histogram(const BankCamera &c, const uint8_
     __syncthreads();
 }
 
+// The ONE fetch of a crop: pixels 16 x .. 16 x + 15 of the crop row whose pixel 0 has its grey byte at `row`, as 16
+// grey bytes.  bpp 1: one 16-byte load wherever the row starts.  bpp 2 (packed 16-bit pixels, the grey value in byte
+// `phase` of each): the 32 source bytes from row - phase + 32 x on in two 16-byte loads, and v_perm_b32 takes the even
+// (phase 0) or the odd bytes of each pair of dwords.  Those 32 bytes are pixels x0 + 16 x .. x0 + 16 x + 15 of the
+// sensor row, whole: inside the row's width * bpp bytes whenever the crop lies inside `width`, so bank_sensor_valid is
+// the bounds proof for either form.  bpp and phase are workgroup-uniform; as the constants 1, 0 (every kernel without
+// a sensor argument) the function is the single load it always was.
+__device__ __forceinline__ void crop_piece16(uint4 &v, const uint8_t *src, int y, int pitch, int x, int bpp, int phase)
+{
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    u32x4 r;
+    if (bpp == 1) {
+        __builtin_memcpy(&r, src + (int64_t)y * pitch + x * 16, 16);
+    } else {
+        u32x4 a, b;
+        const uint8_t *p = src + (int64_t)y * pitch - phase + x * 32;
+        __builtin_memcpy(&a, p, 16);
+        __builtin_memcpy(&b, p + 16, 16);
+        const uint32_t sel = phase ? 0x07050301u : 0x06040200u;
+        r = u32x4{__builtin_amdgcn_perm(a.y, a.x, sel), __builtin_amdgcn_perm(a.w, a.z, sel),
+                  __builtin_amdgcn_perm(b.y, b.x, sel), __builtin_amdgcn_perm(b.w, b.z, sel)};
+    }
+    __builtin_memcpy(&v, &r, 16);   // (one whole 16-byte value for either form)
+}
+
 // CAMERA: the crop of a stream's first frame, sensor rows -> LDS -> slot (a first frame is always due: its histogram
 // comes from the LDS copy).  Ends in a barrier.
-__device__ __forceinline__ void crop_first_frame(const BankCamera &c, const uint8_t *src, int32_t pitch, uint8_t *lds, uint8_t *slot)
+__device__ __forceinline__ void crop_first_frame(const BankCamera &c, const uint8_t *src, int32_t pitch, uint8_t *lds, uint8_t *slot,
+                                                 int bpp = 1, int phase = 0)
 {
     const int row_chunks = c.crop_w / 16, chunks = row_chunks * c.crop_h;
     for (int i = threadIdx.x; i < chunks; i += kThreads) {
         const int y = i / row_chunks, x = i - y * row_chunks;
         uint4 v;
-        __builtin_memcpy(&v, src + (int64_t)y * pitch + x * 16, 16);
+        crop_piece16(v, src, y, pitch, x, bpp, phase);
         reinterpret_cast<uint4 *>(lds)[i] = v;
         reinterpret_cast<uint4 *>(slot)[i] = v;
     }
@@ -297,19 +332,20 @@ struct BankSource {
     const uint8_t *src;
     int32_t pitch;
     bool ok;
+    int32_t bpp, phase;   // the source's pixel format (crop_piece16); 1, 0 -- constants -- without a sensor argument
 };
 template <bool CAMERA>
 __device__ __forceinline__ BankSource bank_source(const BankArgs &a, uint32_t s, uint64_t base = 0)
 {
-    if constexpr (CAMERA) return BankSource{a.cam.camera + (int64_t)s * a.cam.camera_stride + a.cam.origin, a.cam.pitch, true};
-    else return BankSource{a.frames + (int64_t)s * a.frame_stride, 0, true};
+    if constexpr (CAMERA) return BankSource{a.cam.camera + (int64_t)s * a.cam.camera_stride + a.cam.origin, a.cam.pitch, true, 1, 0};
+    else return BankSource{a.frames + (int64_t)s * a.frame_stride, 0, true, 1, 0};
 }
 template <bool CAMERA>
 __device__ __forceinline__ BankSource bank_source(const BankArgs &a, uint32_t s, uint64_t base, const BankSensors &sen)
 {
     static_assert(CAMERA, "sensor records belong to the camera forms");
-    const BankSensor r = bank_sensor(sen.recs, s, a.cam.crop_w, a.cam.crop_h, sen.camera_base + base, sen.camera_bytes);
-    return BankSource{a.cam.camera + r.origin, r.pitch, r.ok};
+    const BankSensor r = bank_sensor(sen.recs, s, a.cam.crop_w, a.cam.crop_h, sen.camera_base + base, sen.camera_bytes, sen.formats);
+    return BankSource{a.cam.camera + r.origin, r.pitch, r.ok, r.bpp, r.phase};
 }
 
 // The stream's newest frame out of LDS into its slot, by the whole workgroup.

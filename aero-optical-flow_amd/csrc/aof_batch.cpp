@@ -440,6 +440,16 @@ void set_bank_sensors(aof_ctx *ctx, const aof_bank_sensor *d_sensors, int32_t n_
     ctx->bank_sensors_n = d_sensors ? n_streams : 0;
     ctx->bank_camera_bytes = d_sensors ? camera_bytes : 0;
 }
+const uint8_t *bank_pixel_formats(const aof_ctx *ctx, int32_t *n_streams)
+{
+    *n_streams = ctx->bank_formats_n;
+    return ctx->bank_formats;
+}
+void set_bank_pixel_formats(aof_ctx *ctx, const uint8_t *d_formats, int32_t n_streams)
+{
+    ctx->bank_formats = d_formats;
+    ctx->bank_formats_n = d_formats ? n_streams : 0;
+}
 
 // Would a sequence-view call (frames viewed twice, n_pairs = frames - 1) run K1 as a pass of its own?  The sequence
 // pipeline asks, because its ingest kernel can leave K1's outputs (pixel sums at ws + L.sums, one level-1 frame per

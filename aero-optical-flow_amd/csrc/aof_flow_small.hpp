@@ -48,6 +48,10 @@ __device__ __forceinline__ void lds_bytes12(const uint8_t *frame, int off, uint3
 
 struct LevelMeta { int px, py, delta; };
 
+// One 16-byte piece of a crop row out of a sensor frame (defined in aof_bank_stream.hpp, the one place a crop is
+// fetched; used below by the PITCHED instantiations only, which that header's kernels make).
+__device__ __forceinline__ void crop_piece16(uint4 &v, const uint8_t *src, int y, int pitch, int x, int bpp, int phase);
+
 // One level of one pair out of LDS: search, records, refinement, votes, flow record.
 // `keys`: one packed key per block; `record_out`: LDS copy of the flow record (level 1: it carries the
 // predictor); `pred_rec`: the level-1 record whose predictor fields level 0 copies into its own.
@@ -189,13 +193,15 @@ __device__ __forceinline__ void run_level(const SearchArgs &a, const FlowTail &t
 // previous call in LDS and fetches only the new one.
 // PITCHED (the stream bank's camera forms): bit b of `pitched` says that src[b] is a window of a larger image -- its
 // rows lie `pitch` bytes apart and may start on any byte; every other source is a contiguous, 16-byte aligned frame.
-// The camera tick fetches its new frame into buffer 1 (the default); a burst alternates the buffers.
+// The camera tick fetches its new frame into buffer 1 (the default); a burst alternates the buffers.  bpp, phase: the
+// windows' pixel format (crop_piece16), looked at by the PACKED instantiations only (the kernels with a sensor argument):
+// 1, 0 is one grey byte per pixel, bpp 2 packed 16-bit pixels whose grey value is byte `phase`.
 // `search` false: only the fetch (passes A and B) -- the buffers named by `load` then hold their frame, its level-1
 // image and its sums for a later call that names them as the older frame (a stream's first frame inside a burst).
-template <bool SUBPIXEL, bool PITCHED = false>
+template <bool SUBPIXEL, bool PITCHED = false, bool PACKED = false>
 __device__ __forceinline__ void flow_small_pair(const SmallArgs &a, uint32_t pair, const uint8_t *src0, const uint8_t *src1,
                                                 int cur_buf, uint32_t load, aof_flow *final_copy = nullptr, int pitch = 0,
-                                                uint32_t pitched = 2u, bool search = true)
+                                                uint32_t pitched = 2u, bool search = true, int bpp = 1, int phase = 0)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_mem[];
     __shared__ uint32_t s_keys[kThreads];
@@ -216,8 +222,46 @@ __device__ __forceinline__ void flow_small_pair(const SmallArgs &a, uint32_t pai
 
     // ---- A: level-0 frames -> LDS (a frame is contiguous: row stride == w) ----
     {
-        const int per_frame = frame0 / 16, items = count * per_frame;
+        const int per_frame = frame0 / 16;
         uint32_t sum[2] = {0, 0};
+        uint32_t rest = load;   // the buffers the loop of 16-byte pieces below fetches: all, but for windows of packed pixels
+        if constexpr (PITCHED && PACKED) {
+            if (bpp != 1) {   // (uniform) two source bytes per pixel: the windows come first, in trips of half as many
+                              // pieces -- as many 16-byte loads in flight as below, not twice the registers
+                constexpr int kHalf = kLoads / 2;
+                const int row_chunks = w / 16;
+#pragma unroll
+                for (int buf = 0; buf < 2; buf++) {
+                    if (!(((load & pitched) >> buf) & 1u)) continue;
+                    const uint8_t *src = buf ? src1 : src0;
+                    for (int base = 0; base < per_frame; base += kHalf * kThreads) {
+                        uint4 v[kHalf];
+#pragma unroll
+                        for (int k = 0; k < kHalf; k++) {
+                            const int c = base + k * kThreads + tid;
+                            v[k] = make_uint4(0, 0, 0, 0);
+                            if (c < per_frame) {
+                                const int y = c / row_chunks, x = c - y * row_chunks;
+                                crop_piece16(v[k], src, y, pitch, x, 2, phase);
+                            }
+                        }
+#pragma unroll
+                        for (int k = 0; k < kHalf; k++) {
+                            const int c = base + k * kThreads + tid;
+                            if (c >= per_frame) continue;
+                            uint32_t s = 0;
+                            s = byte_sum(v[k].x, s); s = byte_sum(v[k].y, s);
+                            s = byte_sum(v[k].z, s); s = byte_sum(v[k].w, s);
+                            sum[buf] += s;
+                            *reinterpret_cast<uint4 *>(f0[buf] + c * 16) = v[k];
+                        }
+                    }
+                }
+                rest = load & ~pitched;
+            }
+        }
+        const int first_a = (rest & 1u) ? 0 : 1, count_a = (rest == 3u) ? 2 : (rest ? 1 : 0);   // (first, count of `rest`)
+        const int items = count_a * per_frame;
         for (int base = 0; base < items; base += kLoads * kThreads) {
             uint4 v[kLoads];
 #pragma unroll
@@ -225,10 +269,12 @@ __device__ __forceinline__ void flow_small_pair(const SmallArgs &a, uint32_t pai
                 const int it = base + k * kThreads + tid;
                 v[k] = make_uint4(0, 0, 0, 0);
                 if (it < items) {
-                    const int buf = first + (it >= per_frame), c = it - (it >= per_frame) * per_frame;
+                    const int buf = first_a + (it >= per_frame), c = it - (it >= per_frame) * per_frame;
                     if (PITCHED && ((pitched >> buf) & 1u)) {   // one 16-byte load wherever the window starts (as k_ingest fetches its crop)
-                        const int y = c / (w / 16), x = c - y * (w / 16);
-                        __builtin_memcpy(&v[k], (buf ? src1 : src0) + (int64_t)y * pitch + x * 16, 16);
+                        if constexpr (PITCHED) {
+                            const int y = c / (w / 16), x = c - y * (w / 16);
+                            crop_piece16(v[k], buf ? src1 : src0, y, pitch, x, 1, 0);
+                        }
                     } else {
                         v[k] = *reinterpret_cast<const uint4 *>((buf ? src1 : src0) + c * 16);
                     }
@@ -238,7 +284,7 @@ __device__ __forceinline__ void flow_small_pair(const SmallArgs &a, uint32_t pai
             for (int k = 0; k < kLoads; k++) {
                 const int it = base + k * kThreads + tid;
                 if (it >= items) continue;
-                const int buf = first + (it >= per_frame), c = it - (it >= per_frame) * per_frame;
+                const int buf = first_a + (it >= per_frame), c = it - (it >= per_frame) * per_frame;
                 uint32_t s = 0;
                 s = byte_sum(v[k].x, s); s = byte_sum(v[k].y, s);
                 s = byte_sum(v[k].z, s); s = byte_sum(v[k].w, s);

@@ -108,15 +108,16 @@ __global__ __launch_bounds__(kThreads) void k_ingest(aof_ingest_params p, const 
     mx0 = max(mx0, 0); my0 = max(my0, 0); mx1 = min(mx1, p.crop_width); my1 = min(my1, p.crop_height);
 
     const uint8_t *src = camera + frame * camera_stride + (int64_t)y0 * p.camera_width + x0;
-    int pitch = p.camera_width;
+    int pitch = p.camera_width, bpp = 1, phase = 0;   // (the pixel format: the record's, with a format array; else grey)
     if constexpr (sizeof...(Sen) > 0) {   // (uniform, as is the record: one frame per workgroup)
         static_assert(!PYRAMID, "the sequence pipeline has no records");
         const IngestSensors &sen = (sensors, ...);
-        const BankSensor r = bank_sensor(sen.recs, (size_t)frame, p.crop_width, p.crop_height, sen.base, sen.camera_bytes);
+        const BankSensor r = bank_sensor(sen.recs, (size_t)frame, p.crop_width, p.crop_height, sen.base, sen.camera_bytes, sen.formats);
         if (sen.ok && strip == 0 && tid == 0) sen.ok[frame] = r.ok ? 1 : 0;
         if (!r.ok) return;
         src = camera + r.origin;
         pitch = r.pitch;
+        bpp = r.bpp; phase = r.phase;
     }
     uint8_t *dst = cropped ? cropped + frame * cropped_stride : nullptr;
     const int row_begin = strip * kRowsPerBlock, row_end = min(p.crop_height, row_begin + kRowsPerBlock);
@@ -144,7 +145,14 @@ __global__ __launch_bounds__(kThreads) void k_ingest(aof_ingest_params p, const 
                 ys[u] = row_begin + (act[u] ? it / pieces : 0);
                 xs[u] = act[u] ? (it % pieces) * 16 : 0;
                 v[u] = make_uint4(0, 0, 0, 0);
-                if (act[u]) __builtin_memcpy(&v[u], src + (int64_t)ys[u] * pitch + xs[u], 16);  // window start may be unaligned
+                if (act[u] && bpp == 1) crop_piece16(v[u], src, ys[u], pitch, xs[u] / 16, 1, 0);  // window start may be unaligned
+            }
+            if constexpr (sizeof...(Sen) > 0) {
+                if (bpp != 1) {   // (uniform, decided per trip: packed 16-bit pixels, eight loads in flight)
+#pragma unroll
+                    for (int u = 0; u < kUnroll; u++)
+                        if (act[u]) crop_piece16(v[u], src, ys[u], pitch, xs[u] / 16, 2, phase);
+                }
             }
 #pragma unroll
             for (int u = 0; u < kUnroll; u++, round++) {
@@ -210,7 +218,7 @@ __global__ __launch_bounds__(kThreads) void k_ingest(aof_ingest_params p, const 
         const int items = (row_end - row_begin) * p.crop_width;
         for (int it = tid; it < items; it += kThreads) {
             const int y = row_begin + it / p.crop_width, x = it % p.crop_width;
-            const uint32_t v = src[(int64_t)y * pitch + x];
+            const uint32_t v = src[(int64_t)y * pitch + x * bpp];   // (src: the grey byte of the crop's first pixel)
             if (dst) dst[(int64_t)y * p.crop_width + x] = (uint8_t)v;
             if (hist && y >= my0 && y < my1 && x >= mx0 && x < mx1) {
                 const int b = exposure_bin(v);

@@ -102,6 +102,16 @@ int aof_facade_bank_set_stream_sensor(void *bank, int stream, uint64_t offset, i
 {
 	return static_cast<OpticalFlowBank *>(bank)->setStreamSensor(stream, offset, pitch, width, height, x0, y0);
 }
+int aof_facade_bank_set_stream_pixel_format(void *bank, int stream, int format)
+{
+	return static_cast<OpticalFlowBank *>(bank)->setStreamPixelFormat(stream, format);
+}
+int aof_facade_bank_enable_camera_packed(void *bank, int camera_width, int camera_height, int format, int exposure0, int gain0,
+					 uint32_t exposure_interval_us)
+{
+	return static_cast<OpticalFlowBank *>(bank)->enableCameraPacked(camera_width, camera_height, format, (uint16_t)exposure0,
+									 (uint8_t)gain0, exposure_interval_us);
+}
 int aof_facade_bank_push(void *bank, const uint8_t *frames, const uint64_t *img_time_us, const uint8_t *active,
 			 const aof_gyro *gyro)
 {

@@ -31,7 +31,7 @@ double secondsSince(std::chrono::steady_clock::time_point t0)
 // Every allocation of one object, recorded where it is made: release() frees them all, the newest first.
 struct Allocations {
 	enum Kind { kDevice, kPinned, kOutbox };   // hipMalloc, hipHostMalloc, aof_outbox_alloc_host: each has its own free
-	struct { void *p; Kind kind; } list[24];   // (22 with every form on, 23 inside enableCamera())
+	struct { void *p; Kind kind; } list[26];   // (24 with every form on, 25 inside enableCamera())
 	int n;
 
 	bool get(void **p, size_t bytes, Kind kind)
@@ -133,6 +133,10 @@ struct OpticalFlowBank::Impl {
 	// size means (aof_bank_sensor_from_camera); nothing is copied or bound before the first call
 	Staged sensors;          // aof_bank_sensor [n_streams]
 	bool sensors_used, sensors_dirty, sensors_bound, sensors_copying;
+	// the pixel formats beside them (enableCameraPacked(), setStreamPixelFormat()): u8 [n_streams], the same scheme; they
+	// travel with the sensor records (formats_used implies sensors_used)
+	Staged formats;
+	bool formats_used, formats_dirty, formats_bound, formats_copying;
 
 	int fail(int code, const char *what) { return self->fail(code, what); }
 	int failed(int rc) { return rc ? fail(rc, aof_last_error(ctx)) : 0; }   // of a call of the C ABI
@@ -142,6 +146,7 @@ struct OpticalFlowBank::Impl {
 	static aof_bank_stream *record(Impl *m, int s);
 	bool waitIdle();
 	int startOver(const uint8_t *mask, bool imu_too);
+	int enableSensorFrames(int camera_width, int camera_height, int format, uint16_t exposure0, uint8_t gain0, uint32_t interval_us);
 	int tick(bool sensor_frames, const uint64_t *img_time_us, const uint8_t *active, const aof_gyro *gyro);
 	int receive();
 	int syncStreams();
@@ -344,11 +349,29 @@ int OpticalFlowBank::setStreamSensor(int s, uint64_t offset, int pitch, int widt
 	rec.x0 = x0;
 	rec.y0 = y0;
 	// the kernels' own rule, against the staging buffer pushCamera() fills: here the host can see the record
-	if (aof_bank_sensor_valid(&rec, image_width, image_height, 0, m->sensor.bytes) != 1)
+	// (with the stream's current pixel format)
+	if (aof_bank_sensor_valid_format(&rec, m->formats.h[s], image_width, image_height, 0, m->sensor.bytes) != 1)
 		return refuse(-EINVAL, "setStreamSensor(): the record does not describe memory inside the staging buffer");
 	reinterpret_cast<aof_bank_sensor *>(m->sensors.h)[s] = rec;
 	m->sensors_used = true;
 	m->sensors_dirty = true;
+	return 0;
+}
+
+int OpticalFlowBank::setStreamPixelFormat(int s, int format)
+{
+	Impl *m = _m;
+	if (!m || !m->camera || !m->sensors.h || !m->formats.h || s < 0 || s >= n_streams) return -EINVAL;
+	if (format < AOF_PIXEL_GREY8 || format > AOF_PIXEL_LUMA16_HI)
+		return refuse(-EINVAL, "setStreamPixelFormat(): no such format");
+	// the stream's current record, by the kernels' own rule, with the new format
+	if (aof_bank_sensor_valid_format(reinterpret_cast<aof_bank_sensor *>(m->sensors.h) + s, (uint8_t)format, image_width, image_height, 0,
+					 m->sensor.bytes) != 1)
+		return refuse(-EINVAL, "setStreamPixelFormat(): the stream's record no longer lies inside the staging buffer");
+	m->formats.h[s] = (uint8_t)format;
+	m->formats_used = m->formats_dirty = true;
+	m->sensors_used = true;   // (formats are bound next to the records only)
+	if (!m->sensors_bound) m->sensors_dirty = true;
 	return 0;
 }
 
@@ -454,6 +477,16 @@ int OpticalFlowBank::Impl::syncStreams()
 			sensors_bound = true;
 		}
 	}
+	if (formats_used) {
+		if (formats_dirty) {
+			if (!formats.upload(stream, 0, formats.bytes)) return fail(-EIO, "copy of the per-stream pixel formats failed");
+			formats_copying = true;
+		}
+		if (!formats_bound) {
+			if (failed(aof_set_bank_pixel_formats(ctx, formats.d, (int)S))) return -EIO;
+			formats_bound = true;
+		}
+	}
 	if (!streams_used) return 0;
 	if (streams_dirty) {
 		if (!streams.upload(stream, 0, streams.bytes)) return fail(-EIO, "copy of the per-stream records failed");
@@ -498,6 +531,10 @@ int OpticalFlowBank::Impl::collect()
 		sensors_copying = false;
 		sensors_dirty = false;
 	}
+	if (formats_copying) {
+		formats_copying = false;
+		formats_dirty = false;
+	}
 	if (imu) std::memset(imuCounts(), 0, S);                      // the tick took the queued samples
 	if (rx) std::memset(rxLengths(), 0, S * sizeof(uint16_t));    // and the queued bytes
 	return (int)reinterpret_cast<const aof_outbox_header *>(outbox)->n_messages;
@@ -515,9 +552,27 @@ int OpticalFlowBank::enableCamera(int camera_width, int camera_height, uint16_t 
 				  uint32_t exposure_interval_us)
 {
 	if (!engineOk()) return -1;
-	Impl *m = _m;
+	return _m->enableSensorFrames(camera_width, camera_height, AOF_PIXEL_GREY8, exposure0, gain0, exposure_interval_us);
+}
+
+int OpticalFlowBank::enableCameraPacked(int camera_width, int camera_height, int format, uint16_t exposure0, uint8_t gain0,
+					uint32_t exposure_interval_us)
+{
+	if (!engineOk()) return -1;
+	if (format < AOF_PIXEL_GREY8 || format > AOF_PIXEL_LUMA16_HI) return refuse(-EINVAL, "enableCameraPacked(): no such format");
+	return _m->enableSensorFrames(camera_width, camera_height, format, exposure0, gain0, exposure_interval_us);
+}
+
+// enableCamera() and enableCameraPacked(): sensor frames of camera_width x camera_height pixels of `format`.  With
+// AOF_PIXEL_GREY8 nothing of the packed form is used or bound: the object runs as it always did.
+int OpticalFlowBank::Impl::enableSensorFrames(int camera_width, int camera_height, int format, uint16_t exposure0, uint8_t gain0,
+					      uint32_t exposure_interval_us)
+{
+	Impl *m = this;
+	const int image_width = self->image_width, image_height = self->image_height, n_streams = self->n_streams;
+	const size_t bpp = format == AOF_PIXEL_GREY8 ? 1 : 2;
 	// a refused call leaves the object as it was: nothing of the object is written before the arguments are accepted
-	if (m->camera) return refuse(-EINVAL, "enableCamera() was already called");
+	if (m->camera) return self->refuse(-EINVAL, "enableCamera() was already called");
 	if (!m->waitIdle()) return -ETIMEDOUT;
 	aof_params p;
 	if (aof_get_params(m->ctx, &p)) return fail(-EIO, aof_last_error(m->ctx));
@@ -531,12 +586,13 @@ int OpticalFlowBank::enableCamera(int camera_width, int camera_height, uint16_t 
 	struct aof_bank_layout L;
 	size_t staging = 0;
 	if (camera_width < 1 || camera_height < 1 || aof_bank_camera_layout(&p, &m->bp, &cam, &L, &staging))
-		return refuse(-EINVAL, "enableCamera(): the sensor frame cannot hold the image size");
+		return self->refuse(-EINVAL, "enableCamera(): the sensor frame cannot hold the image size");
 	const size_t S = m->S;
 	void *bank = NULL;
 	if (!m->mem.get(&bank, L.total_bytes, Allocations::kDevice) ||
-	    !m->sensor.alloc(m->mem, S * (size_t)camera_width * (size_t)camera_height) ||
+	    !m->sensor.alloc(m->mem, S * (size_t)camera_width * (size_t)camera_height * bpp) ||
 	    !m->sensors.alloc(m->mem, S * sizeof(aof_bank_sensor)) ||
+	    !m->formats.alloc(m->mem, alignUp(S, 16)) ||
 	    !m->mem.get((void **)&m->d_exposure, S * sizeof(aof_exposure_record), Allocations::kDevice) ||
 	    !m->mem.get((void **)&m->d_exposure_state, S * sizeof(aof_exposure_state), Allocations::kDevice) ||
 	    !m->mem.get((void **)&m->commands, S * sizeof(aof_exposure_command), Allocations::kOutbox))
@@ -546,7 +602,18 @@ int OpticalFlowBank::enableCamera(int camera_width, int camera_height, uint16_t 
 	m->d_bank = bank;
 	m->bank_bytes = L.total_bytes;
 	m->cam = cam;
-	for (size_t s = 0; s < S; s++) aof_bank_sensor_from_camera(&p, &cam, (int32_t)s, reinterpret_cast<aof_bank_sensor *>(m->sensors.h) + s);
+	for (size_t s = 0; s < S; s++) {
+		// the centred record; packed pixels: rows and frames of bpp bytes per pixel, and the stream's format beside it
+		aof_bank_sensor *rec = reinterpret_cast<aof_bank_sensor *>(m->sensors.h) + s;
+		aof_bank_sensor_from_camera(&p, &cam, (int32_t)s, rec);
+		rec->offset *= bpp;
+		rec->pitch *= (int32_t)bpp;
+		m->formats.h[s] = (uint8_t)format;
+	}
+	if (format != AOF_PIXEL_GREY8) {
+		m->sensors_used = m->sensors_dirty = true;
+		m->formats_used = m->formats_dirty = true;
+	}
 	aof_exposure_control_default(&m->ec);
 	std::memset(m->commands, 0, S * sizeof(aof_exposure_command));
 	// every stream starts over, and every controller from exposure0 / gain0

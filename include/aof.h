@@ -675,6 +675,53 @@ int aof_ingest_sensors_device(int32_t crop_width, int32_t crop_height, const uin
                               const aof_bank_sensor *d_sensors, int64_t n_frames, uint8_t *d_cropped, int64_t cropped_stride,
                               uint32_t *d_hist, uint8_t *d_ok, void *stream);
 
+/* ---- the stream bank with packed sensor pixels: YUYV, UYVY and Y16 buffers as the driver filled them ----
+ * The sensor records above describe one byte per pixel.  Most UVC cameras deliver YUYV (packed 4:2:2, the luma in the
+ * even bytes), many CSI bridges UYVY (the luma in the odd bytes), mono global-shutter sensors Y16 (the grey value the
+ * engine wants is the high byte of each little-endian 16-bit pixel).  A caller may therefore bind, next to the sensor
+ * records, an array of S pixel formats in device memory; stream s's crop is then fetched from pixels of bpp bytes whose
+ * grey value is byte `phase`:
+ *     format               bpp  phase
+ *     AOF_PIXEL_GREY8       1     0      exactly the records alone
+ *     AOF_PIXEL_LUMA16_LO   2     0      YUYV, YVYU, Y16_BE
+ *     AOF_PIXEL_LUMA16_HI   2     1      UYVY, VYUY, Y16 (little endian: its high byte)
+ * Pixel (x, y) of the crop is the byte at
+ *     d_camera + k*round_stride + offset + (y0 + y)*pitch + (x0 + x)*bpp + phase.
+ * width, x0 and the crop size stay in pixels, offset and pitch in bytes.  From the cropped frame on nothing changes
+ * (exposure mask, histogram, MSV, flow, limiter, wire frame, de-rotation).  The kernels fetch the 32 source bytes of a
+ * 16-pixel piece and pack the even or the odd ones (v_perm_b32): no de-interleave pass, no second buffer.
+ * A record with its format is valid iff, in 64 bits so that nothing wraps,
+ *     format <= 2;  width >= 1, height >= 1, pitch >= width*bpp;  the crop inside width x height;
+ *     k*round_stride + offset + (height-1)*pitch + width*bpp <= camera_bytes.
+ * An invalid record or format is treated as an invalid record is today: AOF_TICK_BAD_SENSOR for that round, not one byte
+ * of the stream's frame read, its bank bytes untouched.
+ * Binding: the formats are used by the two camera pushes, and only with a sensor array bound as well -- formats bound
+ * without sensors make those pushes return -EINVAL; bp->n_streams must equal the bound format count (else -EINVAL, and
+ * nothing is written); the pushes of pre-cropped frames ignore the binding; a burst indexes the array by the stream
+ * alone.  The KERNELS read the array when they run: it may be rewritten between ticks, and a replayed graph sees the
+ * current contents.
+ * Contracts: (a) stream s's outputs and bank bytes equal those of the grey sensor path fed the de-interleaved plane
+ * (a grey record of the same width, height, x0, y0 and the grey buffer's own pitch); (b) an array of all
+ * AOF_PIXEL_GREY8 changes no byte against sensors bound alone. */
+#define AOF_PIXEL_GREY8     0   /* one byte per pixel: exactly the behaviour without formats */
+#define AOF_PIXEL_LUMA16_LO 1   /* two bytes per pixel, grey value = first byte: YUYV, YVYU, Y16_BE */
+#define AOF_PIXEL_LUMA16_HI 2   /* two bytes per pixel, grey value = second byte: UYVY, VYUY, Y16 (LE: its high byte) */
+/* Stores the pointer on the context, like aof_set_bank_streams: enqueues nothing, allocates nothing, reads nothing.
+ * d_formats: u8 [n_streams] in device memory owned by the caller, alive for as long as it is bound; any alignment; the
+ * kernels read nothing outside d_formats[0..n_streams).  NULL (with n_streams 0) unbinds.
+ * -EINVAL: NULL ctx, a non-NULL array with n_streams < 1 (the binding stays as it was). */
+int aof_set_bank_pixel_formats(aof_ctx *ctx, const uint8_t *d_formats, int32_t n_streams);
+/* Host only: aof_bank_sensor_valid for a record of pixel format `format` (the same function the kernels decide with,
+ * compiled for the host): 1 valid, 0 not (a format above 2 included).  -EINVAL: NULL rec. */
+int aof_bank_sensor_valid_format(const aof_bank_sensor *rec, uint8_t format, int32_t crop_width, int32_t crop_height,
+                                 uint64_t base, uint64_t camera_bytes);
+/* aof_ingest_sensors_device with frame i's pixel format d_formats[i] (u8 [n_frames], device memory, any alignment);
+ * d_formats NULL: every frame AOF_PIXEL_GREY8 -- aof_ingest_sensors_device is this call with NULL.  A frame whose record
+ * or format is not valid is not read (d_ok 0).  -EINVAL as there. */
+int aof_ingest_sensor_formats_device(int32_t crop_width, int32_t crop_height, const uint8_t *d_camera, uint64_t camera_bytes,
+                                     const aof_bank_sensor *d_sensors, const uint8_t *d_formats, int64_t n_frames,
+                                     uint8_t *d_cropped, int64_t cropped_stride, uint32_t *d_hist, uint8_t *d_ok, void *stream);
+
 /* ---- the stream bank's outbox: the published messages of a push as one dense, ordered, host-pollable list ----
  * A push leaves [K][S] records of which most say "nothing to do": the limiter publishes at 15 Hz from 75 Hz cameras, the
  * exposure gate opens at 5 Hz, idle streams get AOF_TICK_IDLE.  aof_bank_collect_device, enqueued behind any of the four

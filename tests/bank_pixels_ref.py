@@ -1,0 +1,108 @@
+"""Inputs and expected values of the packed-pixel tests (tests/test_bank_pixels_ref.py, tests/test_bank_pixels_abi.py,
+tests/test_gpu_bank_pixels.py): the pixel formats of include/aof.h (AOF_PIXEL_*, aof_set_bank_pixel_formats), the validity
+rule with a format restated in Python integers, the crop a record and its format mean by numpy slicing, the layout tables
+of bank_sensors_ref with a format column, and a packer that lays S frames into packed buffers whose other byte per pixel is
+seeded noise independent of the luma.  Nothing here touches the GPU or the library under test."""
+import numpy as np
+
+import bank_sensors_ref as sref
+from bank_sensors_ref import SENSOR_DTYPE, record
+
+GREY8, LUMA16_LO, LUMA16_HI = 0, 1, 2
+FORMATS = (GREY8, LUMA16_LO, LUMA16_HI)
+
+# bank_sensors_ref.TABLES (the same sensors, residues mod 16, crop origins and order in the buffer) with the pitch in BYTES
+# of the stream's format and the format as a last column.  Each configuration carries all three formats, a padded and an
+# odd packed pitch, offsets with residues 0, 1, 7 and 8 mod 16, a crop that touches the right and bottom edges of a packed
+# sensor, and as the buffer's last frame a LUMA16_HI one whose crop is the sensor: the buffer's last byte is a grey byte.
+PITCH_AND_FORMAT = {
+    "px4-64": [(192, LUMA16_LO), (176, LUMA16_HI), (128, LUMA16_HI), (263, LUMA16_LO), (320, GREY8)],
+    "opencv-128": [(320, LUMA16_HI), (152, GREY8), (395, LUMA16_LO)],
+}
+ORDER = {"px4-64": [0, 1, 4, 3, 2], "opencv-128": [1, 0, 2]}     # (each ends with a packed frame)
+TABLES = {cfg: ([(w, h, pitch, mod, origin, fmt) for (w, h, _, mod, origin), (pitch, fmt) in zip(sref.TABLES[cfg][0], PITCH_AND_FORMAT[cfg])],
+                ORDER[cfg]) for cfg in sref.TABLES}
+
+
+def bpp_of(fmt):
+    return 1 if fmt == GREY8 else 2
+
+
+def phase_of(fmt):
+    return 1 if fmt == LUMA16_HI else 0
+
+
+def valid(rec, fmt, w, h, camera_bytes, base=0):
+    """The rule of include/aof.h ("packed sensor pixels") in Python integers, which do not wrap."""
+    if fmt not in FORMATS:
+        return False
+    bpp = bpp_of(fmt)
+    off, pitch, width, height, x0, y0 = (int(rec[n]) for n in ("offset", "pitch", "width", "height", "x0", "y0"))
+    if width < 1 or height < 1 or pitch < width * bpp:
+        return False
+    if x0 < 0 or y0 < 0 or x0 + w > width or y0 + h > height:
+        return False
+    return base + off + (height - 1) * pitch + width * bpp <= camera_bytes
+
+
+def extent(rec, fmt):
+    """Bytes from the frame's first to behind its last."""
+    return (int(rec["height"]) - 1) * int(rec["pitch"]) + int(rec["width"]) * bpp_of(fmt)
+
+
+def crop(buffer, rec, fmt, w, h, base=0):
+    """The w x h crop the record and its format mean, out of the flat uint8 buffer: byte by byte, the header's formula."""
+    bpp, phase = bpp_of(fmt), phase_of(fmt)
+    start = base + int(rec["offset"])
+    pitch, x0, y0 = int(rec["pitch"]), int(rec["x0"]), int(rec["y0"])
+    out = np.empty((h, w), np.uint8)
+    for y in range(h):
+        for x in range(w):
+            out[y, x] = buffer[start + (y0 + y) * pitch + (x0 + x) * bpp + phase]
+    return out
+
+
+def layout(table, order, w, h, start=0):
+    """(records [S], formats [S] uint8, bytes): a table's sensors laid one behind the other in `order`, each at the next
+    offset with the table's residue mod 16; the last frame's last byte is the buffer's last."""
+    recs, fmts = np.zeros(len(table), SENSOR_DTYPE), np.zeros(len(table), np.uint8)
+    cursor = start
+    for s in order:
+        width, height, pitch, mod, origin, fmt = table[s]
+        off = cursor + (mod - cursor) % 16
+        x0, y0 = origin if origin is not None else (width // 2 - w // 2, height // 2 - h // 2)
+        recs[s], fmts[s] = record(off, pitch, width, height, x0, y0), fmt
+        cursor = off + extent(recs[s], fmt)
+    return recs, fmts, cursor
+
+
+def pack(recs, fmts, frames, nbytes, seed):
+    """A noise buffer of nbytes in which every record's crop, read in its format, holds frames[s] ([S, h, w]).  Every other
+    byte -- the chroma or low byte of each pixel included -- keeps the seeded noise, which does not depend on the frames."""
+    buf = np.random.default_rng(seed).integers(0, 256, nbytes, dtype=np.uint8)
+    h, w = frames.shape[1:]
+    for s, rec in enumerate(recs):
+        bpp, phase = bpp_of(int(fmts[s])), phase_of(int(fmts[s]))
+        pitch = int(rec["pitch"])
+        start = int(rec["offset"]) + int(rec["y0"]) * pitch + int(rec["x0"]) * bpp + phase
+        for y in range(h):
+            buf[start + y * pitch:start + y * pitch + w * bpp:bpp] = frames[s, y]
+    return buf
+
+
+def retable(cfg, fmts):
+    """TABLES[cfg]'s cameras with other formats: the grey pitch of bank_sensors_ref times the format's bytes per pixel."""
+    table, order = TABLES[cfg]
+    return [t[:2] + (g[2] * bpp_of(f),) + t[3:5] + (f,) for t, g, f in zip(table, sref.TABLES[cfg][0], fmts)], order
+
+
+def grey_twin(table, order, w, h):
+    """The grey sensor path's records for the same cameras: bank_sensors_ref's layout of the de-interleaved planes -- the
+    same width, height, x0 and y0, the grey buffer's own pitch and offsets."""
+    return sref.layout([t[:2] + (sref_pitch,) + t[3:5] for t, sref_pitch in zip(table, _grey_pitches(table))], order, w, h)
+
+
+def _grey_pitches(table):
+    # a grey plane's rows: the sensor's width, padded as bank_sensors_ref pads them (whatever the packed pitch is)
+    by_size = {(t[0], t[1]): t[2] for cfg in sref.TABLES for t in sref.TABLES[cfg][0]}
+    return [by_size[(t[0], t[1])] for t in table]

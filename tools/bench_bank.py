@@ -50,6 +50,14 @@ against the camera tick on the scalars of aof_bank_camera, 64x64 from 320x240 an
   K1 / K2       aof_bank_push_camera_device, nothing bound, on the one-launch kernel (1) and the composed path (2) -- also
                 what a build without the call runs (AOF_LIB: the yardstick of K on this build);
   S1 / S2       the same tick with the S records bound.
+With --pixel-formats, the camera tick with packed 16-bit sensor pixels (aof_set_bank_pixel_formats), on both bank paths
+(leg names end in the path, 1 or 2):
+    G   sensors bound, no formats: grey frames (with AOF_LIB, on a build without the call: the yardstick of P0 on this build);
+    P0  formats bound, all AOF_PIXEL_GREY8: the same frames, the same bytes;
+    Y   all AOF_PIXEL_LUMA16_LO (YUYV): cam_w x cam_h pixels of two bytes, the crop fetched out of the packed frames;
+    M   formats mixed per stream (s % 3): every stream in a slot of 2 cam_w cam_h bytes;
+    D   what a caller does without the call: a device de-interleave of the whole packed buffer (one strided copy kernel,
+        2 + 1 bytes moved per sensor pixel) into a grey buffer, then leg G on that.
 K1 / K2 are the legs --camera runs under those names (leg_camera); --per-sensor --legs K1,K2 runs them alone, which is how
 two builds of the library are compared in turn in one session.
 Every leg settles for about 0.2 s of untimed ticks, then times at least --ticks ticks and at least --seconds seconds
@@ -220,6 +228,109 @@ def leg_camera(p, S, path, inp, cams, dev, a, cam_w, cam_h, per_sensor=False):
     assert (r["quality"] >= aof.TICK_HELD).all() and (r["frame"] > a.ticks).all(), "the timed ticks were real ticks"
     eng.close()
     return out
+
+
+def leg_pixels(p, S, path, inp, dev, a, cam_w, cam_h, leg):
+    """One of G / P0 / Y / M / D of --pixel-formats on `path`: the camera tick with sensor records bound.  Stream s's frame
+    lies in a slot of its own (cam_w cam_h bytes for G and P0, twice that for the packed legs), its rows cam_w * bpp bytes
+    apart; inp.frames[k] sits at the centre crop, in the grey byte of each pixel; everything else is noise."""
+    eng = aof.FlowEngine(p, 0)
+    eng.set_bank_path(path)
+    bp = aof.bank_params(S, FX, FY, 15, 5_000_000, 1, 100, 0)
+    cam = aof.bank_camera_params(cam_w, cam_h, p.width, p.height, 0, 200_000, DEROTATE, FX, FY)
+    bank = eng.bank_create(bp, dev, camera=cam)
+    fmts = {"G": None, "P0": np.zeros(S, np.uint8), "Y": np.ones(S, np.uint8), "M": (np.arange(S) % 3).astype(np.uint8),
+            "D": np.ones(S, np.uint8)}[leg]
+    packed = leg in ("Y", "M", "D")
+    slot = cam_w * cam_h * (2 if packed else 1)
+    x0, y0 = cam_w // 2 - p.width // 2, cam_h // 2 - p.height // 2
+    src_fmts = fmts if packed else np.zeros(S, np.uint8)
+    bpps = np.where(src_fmts == 0, 1, 2)
+    cams = []
+    for k in range(RING):
+        buf = torch.randint(0, 256, (S, slot), dtype=torch.uint8, device=dev)
+        for f in sorted(set(src_fmts.tolist())):
+            idx = torch.from_numpy(np.nonzero(src_fmts == f)[0]).to(dev)
+            bpp, phase = (1, 0) if f == 0 else (2, f - 1)
+            view = buf[:, :cam_w * cam_h * bpp].view(S, cam_h, cam_w, bpp)
+            sub = view[idx]
+            sub[:, y0:y0 + p.height, x0:x0 + p.width, phase] = inp.frames[k][idx]
+            view[idx] = sub
+        cams.append(buf)
+    grey = torch.empty((S, cam_w * cam_h), dtype=torch.uint8, device=dev) if leg == "D" else None
+    table = aof.bank_sensor_from_camera(p, cam, n=S)
+    if leg != "D":
+        table["offset"] = np.arange(S, dtype=np.uint64) * np.uint64(slot)
+        table["pitch"] = cam_w * bpps
+    d_table = torch.from_numpy(table.view(np.uint8).reshape(S, 32)).to(dev)
+    eng.set_bank_sensors(d_table, S, S * (cam_w * cam_h if leg == "D" else slot))
+    if fmts is not None and leg != "D":
+        d_fmts = torch.from_numpy(fmts).to(dev)
+        eng.set_bank_pixel_formats(d_fmts, S)
+    recs = torch.empty((S, 48), dtype=torch.uint8, device=dev)
+    expo = torch.empty((S, 48), dtype=torch.uint8, device=dev)
+    derot = torch.empty((S, 2), dtype=torch.float32, device=dev)
+    wire = torch.empty((S, 56), dtype=torch.uint8, device=dev)
+    lens = torch.empty(S, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    fn, ctx, bpp_, cp = aof.lib.aof_bank_push_camera_device, eng._ctx, C.byref(bp), C.byref(cam)
+    times = torch.zeros(S, dtype=torch.int64, device=dev)
+    rest = (times.data_ptr(), None, inp.gyro.data_ptr(), bank.buffer.data_ptr(), bank.buffer.numel(), recs.data_ptr(), expo.data_ptr(),
+            derot.data_ptr(), wire.data_ptr(), lens.data_ptr(), stream)
+    ptrs = [c.data_ptr() for c in cams]
+    lumas = [c.view(S, cam_w * cam_h, 2)[:, :, 0] for c in cams] if leg == "D" else None
+
+    def step(i):
+        times.add_(13333)
+        if leg == "D":
+            grey.copy_(lumas[i % RING])
+            rc = fn(ctx, bpp_, cp, grey.data_ptr(), *rest)
+        else:
+            rc = fn(ctx, bpp_, cp, ptrs[i % RING], *rest)
+        if rc:
+            raise aof.AofError(rc, aof.lib.aof_last_error(ctx).decode())
+    out = timed(step, torch.cuda.synchronize, a.ticks, a.seconds, a.settle)
+    r = aof.ticks_view(recs)
+    assert (r["quality"] >= aof.TICK_HELD).all() and (r["frame"] > a.ticks).all(), "the timed ticks were real ticks"
+    eng.close()
+    return out
+
+
+def pixel_formats_sweep(a, dev):
+    print("# legs (the digit: bank path 1 / 2): G sensors bound, grey frames; P0 formats bound, all GREY8; Y all LUMA16_LO; M formats s % 3; "
+          "D device de-interleave of the packed buffer, then G (exposure records, de-rotation, MAVLink frames on, all streams active)")
+    print("# us = microseconds per tick (host clock, ticks ending in a synchronise)")
+    bound = hasattr(aof.lib, "aof_set_bank_pixel_formats")      # (AOF_LIB may name a build without the call: G legs only)
+    kinds = ["G", "P0", "Y", "M", "D"] if bound else ["G"]
+    legs = [(k + str(path), k, path) for path in (1, 2) for k in kinds]
+    if a.legs is not None:
+        legs = [leg for leg in legs if leg[0] in a.legs.split(",")]
+    sizes = [int(s) for s in a.streams.split(",")]
+    results = {}
+    for rep in range(a.repeats):
+        for cfg in a.configs.split(","):
+            p = params_of(cfg)
+            cam_w, cam_h = SENSOR[cfg]
+            for S in sizes:
+                inp = Inputs(p, S, dev)
+                for name, kind, path in legs:
+                    sec, n = leg_pixels(p, S, path, inp, dev, a, cam_w, cam_h, kind)
+                    results.setdefault((cfg, S, name), []).append(sec)
+                    print(f"rep {rep} {cfg:11s} S={S:6d} {name:3s} {sec * 1e6:10.2f} us  ({n} ticks)", flush=True)
+                    torch.cuda.empty_cache()
+                del inp
+    print("# ---- summary (median of the repeats; p10..p90 of the repeats in us) ----")
+    for cfg in a.configs.split(","):
+        for S in sizes:
+            m = {n: float(np.median(results[(cfg, S, n)])) for n, _, _ in legs}
+            line = f"{cfg:11s} S={S:6d}  " + "  ".join(
+                f"{n} {m[n] * 1e6:9.2f} us ({np.percentile(results[(cfg, S, n)], 10) * 1e6:.2f}..{np.percentile(results[(cfg, S, n)], 90) * 1e6:.2f})"
+                for n in m)
+            for path in (1, 2):
+                if all(k + str(path) in m for k in ("G", "P0", "Y", "M", "D")):
+                    g, q, y, mm, d = (m[k + str(path)] for k in ("G", "P0", "Y", "M", "D"))
+                    line += f"  P0{path}/G{path} {q / g:5.3f}  Y{path}/D{path} {y / d:5.3f}  M{path}/D{path} {mm / d:5.3f}"
+            print(line)
 
 
 def leg_two_calls(p, S, inp, cams, dev, a, cam_w, cam_h):
@@ -1164,15 +1275,19 @@ def main():
     ap.add_argument("--per-stream", action="store_true", help="the plain tick with per-stream records bound against the unbound tick: legs U1, U2, P1, P2")
     ap.add_argument("--per-sensor", action="store_true", help="the camera tick with per-stream sensor records bound against the unbound camera tick: legs K1, K2, S1, S2 "
                     "(K1 / K2 are --camera's legs of those names, the same leg_camera; --legs K1,K2 runs them alone, for two builds in turn)")
+    ap.add_argument("--pixel-formats", action="store_true", help="the camera tick with packed 16-bit sensor pixels: legs G, P0, Y, M, D on both "
+                    "bank paths (G1, ..., D2; --legs G1,G2 runs the yardstick alone, for a build without the call through AOF_LIB)")
     ap.add_argument("--forms", default="plain,camera", help="--burst: entry points to sweep")
     ap.add_argument("--input-bytes-max", type=float, default=24 * 2**30, help="--burst: sizes whose K rounds of input exceed this are skipped")
     a = ap.parse_args()
-    if a.legs is None and not a.per_sensor:
+    if a.legs is None and not a.per_sensor and not a.pixel_formats:
         a.legs = "T0,T1,T2,C,B"
     if a.burst and a.ticks == ap.get_default("ticks"):
         a.ticks = 1000           # (frame rounds)
     if a.camera and a.streams == ap.get_default("streams"):
         a.streams = "1,64,1024,1536,2048,4096"
+    if a.pixel_formats and a.streams == ap.get_default("streams"):
+        a.streams = "64,256,1024,2048"
     if a.exposure_control and a.streams == ap.get_default("streams"):
         a.streams = "64,1024,4096"
     if (a.imu or a.mavlink_rx) and a.streams == ap.get_default("streams"):
@@ -1190,6 +1305,8 @@ def main():
         return per_stream_sweep(a, dev)
     if a.per_sensor:
         return per_sensor_sweep(a, dev)
+    if a.pixel_formats:
+        return pixel_formats_sweep(a, dev)
     if a.mavlink_rx:
         return mavlink_rx_sweep(a, dev)
     if a.imu:
