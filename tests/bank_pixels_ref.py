@@ -1,12 +1,11 @@
 """Inputs and expected values of the packed-pixel tests (tests/test_bank_pixels_ref.py, tests/test_bank_pixels_abi.py,
-tests/test_gpu_bank_pixels.py): the pixel formats of include/aof.h (AOF_PIXEL_*, aof_set_bank_pixel_formats), the validity
-rule with a format restated in Python integers, the crop a record and its format mean by numpy slicing, the layout tables
-of bank_sensors_ref with a format column, and a packer that lays S frames into packed buffers whose other byte per pixel is
-seeded noise independent of the luma.  Nothing here touches the GPU or the library under test."""
+tests/test_gpu_bank_pixels.py): the pixel formats of include/aof.h (AOF_PIXEL_*, aof_set_bank_pixel_formats), the crop a
+record and its format mean, byte by byte, and the layout tables of bank_sensors_ref with a format column.  The validity
+rule, the layouts and the packer (whose other byte per packed pixel is seeded noise independent of the luma) are
+bank_sensors_ref's.  Nothing here touches the GPU or the library under test."""
 import numpy as np
 
 import bank_sensors_ref as sref
-from bank_sensors_ref import SENSOR_DTYPE, record
 
 GREY8, LUMA16_LO, LUMA16_HI = 0, 1, 2
 FORMATS = (GREY8, LUMA16_LO, LUMA16_HI)
@@ -32,22 +31,14 @@ def phase_of(fmt):
     return 1 if fmt == LUMA16_HI else 0
 
 
+# The rule, the extent, the layouts and the packer are bank_sensors_ref's, which take the format as their last argument (the
+# layout: as the table's last column) and know grey as format 0.
+extent, layout, pack = sref.extent, sref.layout, sref.pack
+
+
 def valid(rec, fmt, w, h, camera_bytes, base=0):
-    """The rule of include/aof.h ("packed sensor pixels") in Python integers, which do not wrap."""
-    if fmt not in FORMATS:
-        return False
-    bpp = bpp_of(fmt)
-    off, pitch, width, height, x0, y0 = (int(rec[n]) for n in ("offset", "pitch", "width", "height", "x0", "y0"))
-    if width < 1 or height < 1 or pitch < width * bpp:
-        return False
-    if x0 < 0 or y0 < 0 or x0 + w > width or y0 + h > height:
-        return False
-    return base + off + (height - 1) * pitch + width * bpp <= camera_bytes
-
-
-def extent(rec, fmt):
-    """Bytes from the frame's first to behind its last."""
-    return (int(rec["height"]) - 1) * int(rec["pitch"]) + int(rec["width"]) * bpp_of(fmt)
+    """bank_sensors_ref.valid with the format where the packed tests write it: behind the record."""
+    return sref.valid(rec, w, h, camera_bytes, base, fmt)
 
 
 def crop(buffer, rec, fmt, w, h, base=0):
@@ -60,34 +51,6 @@ def crop(buffer, rec, fmt, w, h, base=0):
         for x in range(w):
             out[y, x] = buffer[start + (y0 + y) * pitch + (x0 + x) * bpp + phase]
     return out
-
-
-def layout(table, order, w, h, start=0):
-    """(records [S], formats [S] uint8, bytes): a table's sensors laid one behind the other in `order`, each at the next
-    offset with the table's residue mod 16; the last frame's last byte is the buffer's last."""
-    recs, fmts = np.zeros(len(table), SENSOR_DTYPE), np.zeros(len(table), np.uint8)
-    cursor = start
-    for s in order:
-        width, height, pitch, mod, origin, fmt = table[s]
-        off = cursor + (mod - cursor) % 16
-        x0, y0 = origin if origin is not None else (width // 2 - w // 2, height // 2 - h // 2)
-        recs[s], fmts[s] = record(off, pitch, width, height, x0, y0), fmt
-        cursor = off + extent(recs[s], fmt)
-    return recs, fmts, cursor
-
-
-def pack(recs, fmts, frames, nbytes, seed):
-    """A noise buffer of nbytes in which every record's crop, read in its format, holds frames[s] ([S, h, w]).  Every other
-    byte -- the chroma or low byte of each pixel included -- keeps the seeded noise, which does not depend on the frames."""
-    buf = np.random.default_rng(seed).integers(0, 256, nbytes, dtype=np.uint8)
-    h, w = frames.shape[1:]
-    for s, rec in enumerate(recs):
-        bpp, phase = bpp_of(int(fmts[s])), phase_of(int(fmts[s]))
-        pitch = int(rec["pitch"])
-        start = int(rec["offset"]) + int(rec["y0"]) * pitch + int(rec["x0"]) * bpp + phase
-        for y in range(h):
-            buf[start + y * pitch:start + y * pitch + w * bpp:bpp] = frames[s, y]
-    return buf
 
 
 def retable(cfg, fmts):

@@ -1,7 +1,8 @@
 """What the stream bank's device tests (tests/test_gpu_bank*.py, tests/test_gpu_tail_matrix.py) share: the constants, the
-byte comparer, guarded output buffers, the fixtures and BankRig, the one device rig behind the four push entry points
-(aof_bank_push_device, aof_bank_push_camera_device and their burst forms, include/aof.h).  A test file that wants a
-fixture imports its name.  The cases built on the rig: tests/bank_cases.py."""
+byte comparer, guarded output buffers, the fixtures, the helpers for burstable runs and bound device arrays, and BankRig,
+the one device rig behind the four push entry points (aof_bank_push_device, aof_bank_push_camera_device and their burst
+forms, include/aof.h).  A test file that wants a fixture imports its name.  The cases built on the rig:
+tests/bank_cases.py; the rig whose camera buffer holds per-stream sensor layouts: tests/bank_sensor_rig.py."""
 import faulthandler
 from collections import namedtuple
 
@@ -121,6 +122,34 @@ def engine(aof, gpu_device):
     eng.close()
 
 
+# ---- runs and device arrays ------------------------------------------------------------------------------------------
+
+def up(dev, a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def put(t, s, rec):
+    """Record s of a bound array, rewritten on the current stream: in order with the ticks around it."""
+    t[s].copy_(up(t.device, np.frombuffer(np.asarray(rec).tobytes(), np.uint8).copy()))
+
+
+def burstable(run, K):
+    """The run with every stream's frames of a burst of K rounds moved to nobody: inside rounds [jK, jK + K) a stream
+    keeps its leading frames only (aof_bank_burst's count).  The dropped frames are never given to anyone."""
+    for k0 in range(0, run.T - run.T % K, K):
+        run.active[k0:k0 + K] = run.active[k0:k0 + K].cumprod(axis=0)
+    return run
+
+
+def counts_of(run, K, T=None):
+    """count [T // K, S] of a burstable run's bursts of K rounds (T None: the run's ticks)."""
+    T = run.T if T is None else T
+    a = run.active[:T - T % K].reshape(-1, K, run.S)
+    assert (a.cumprod(axis=1).sum(axis=1) == a.sum(axis=1)).all(), "a burst's frames are a stream's first rounds"
+    return a.sum(axis=1).astype(np.uint8)
+
+
 # ---- the rig --------------------------------------------------------------------------------------------------------
 
 Tick = namedtuple("Tick", "recs wire exposure derotated")   # records [S], frames [S] of bytes, exposure records [S], float [S, 2]
@@ -160,10 +189,23 @@ class BankRig:
         self.records, self.wire, self.lens, self.exposure, self.derotated = (g.tensor for g in self.outputs)
         self.want_exposure = exposure
 
-    def load(self, k, given=None, sensors=None):
+    def load(self, k, given=None, sensors=None, **fill):
         """A tick: tick k of the run; sensors: its sensor frames [S, cam_h, cam_w], else the camera run's.  A burst:
         burst k, the run's ticks k * K .. k * K + K - 1; given [B, S]: the counts the device is told; sensors: a list
-        of K.  Every output is refilled (every record of every round must be written)."""
+        of K.  Every output is refilled (every record of every round must be written).  fill: what a subclass's
+        fill_frames takes."""
+        t, run, R = self.torch, self.run, self.K or 1
+        self.fill_frames(k, sensors, **fill)
+        ticks = slice(k * R, (k + 1) * R)
+        self.times.copy_(t.from_numpy(run.times[ticks]).view(self.times.shape))
+        self.select.copy_(t.from_numpy(run.active[k] if self.K is None else given[k]))
+        if self.gyro is not None:
+            self.gyro.copy_(t.from_numpy(run.gyro[ticks]).view(self.gyro.shape))
+        for g in self.outputs:
+            g.refill()
+
+    def fill_frames(self, k, sensors=None):
+        """The frame buffer of tick or burst k: every round's S frames, dense at the rig's strides."""
         t, run, S, R = self.torch, self.run, self.run.S, self.K or 1
         if self.K is None and sensors is not None:
             sensors = [sensors]
@@ -175,13 +217,6 @@ class BankRig:
                 data = sensors[r] if sensors is not None else self.cam_run.sensor(tick)
             dst = self.frames[r * self.round:r * self.round + S * self.stride].view(S, self.stride)
             dst[:, :self.item].copy_(t.from_numpy(np.ascontiguousarray(data.reshape(S, -1))))
-        ticks = slice(k * R, (k + 1) * R)
-        self.times.copy_(t.from_numpy(run.times[ticks]).view(self.times.shape))
-        self.select.copy_(t.from_numpy(run.active[k] if self.K is None else given[k]))
-        if self.gyro is not None:
-            self.gyro.copy_(t.from_numpy(run.gyro[ticks]).view(self.gyro.shape))
-        for g in self.outputs:
-            g.refill()
 
     def enqueue(self, all_rounds=False):
         """The push of what load() left; all_rounds: d_active / d_count is NULL."""

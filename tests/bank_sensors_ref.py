@@ -36,19 +36,29 @@ UNIFORM = {"px4-64": (96, 80), "opencv-128": (160, 144)}      # rig B: every str
 SCALARS = {"px4-64": (72, 66), "opencv-128": (136, 130)}      # what aof_bank_camera holds while records are bound: no stream's
 
 
-def valid(rec, w, h, camera_bytes, base=0):
-    """The rule of include/aof.h in Python integers (which do not wrap)."""
+def _format(fmt):
+    """(bytes per pixel, the luma's byte in the pixel) of a pixel format, None of a value that is none.  The formats are
+    bank_pixels_ref's, imported late: that module builds its tables on this one's."""
+    import bank_pixels_ref as pref
+    return (pref.bpp_of(fmt), pref.phase_of(fmt)) if fmt in pref.FORMATS else None
+
+
+def valid(rec, w, h, camera_bytes, base=0, fmt=0):
+    """The rule of include/aof.h in Python integers (which do not wrap); fmt: the stream's pixel format, 0 is grey."""
+    if _format(fmt) is None:
+        return False
+    bpp = _format(fmt)[0]
     off, pitch, width, height, x0, y0 = (int(rec[n]) for n in ("offset", "pitch", "width", "height", "x0", "y0"))
-    if width < 1 or height < 1 or pitch < width:
+    if width < 1 or height < 1 or pitch < width * bpp:
         return False
     if x0 < 0 or y0 < 0 or x0 + w > width or y0 + h > height:
         return False
-    return base + off + (height - 1) * pitch + width <= camera_bytes
+    return base + off + (height - 1) * pitch + width * bpp <= camera_bytes
 
 
-def extent(rec):
+def extent(rec, fmt=0):
     """Bytes from the frame's first to behind its last."""
-    return (int(rec["height"]) - 1) * int(rec["pitch"]) + int(rec["width"])
+    return (int(rec["height"]) - 1) * int(rec["pitch"]) + int(rec["width"]) * _format(fmt)[0]
 
 
 def crop(buffer, rec, w, h, base=0):
@@ -67,26 +77,33 @@ def record(offset, pitch, width, height, x0, y0):
 
 def layout(table, order, w, h, start=0):
     """The records [S] of a table's sensors laid one behind the other in `order`, each at the next offset with the
-    table's residue mod 16, and the bytes the buffer needs: the last frame's last byte is the buffer's last."""
-    recs = np.zeros(len(table), SENSOR_DTYPE)
+    table's residue mod 16, and the bytes the buffer needs: the last frame's last byte is the buffer's last.  A table with
+    a format as its rows' last column (bank_pixels_ref.TABLES, the pitch in bytes of that format) gives (records,
+    formats [S] uint8, bytes)."""
+    recs, fmts = np.zeros(len(table), SENSOR_DTYPE), np.zeros(len(table), np.uint8)
     cursor = start
     for s in order:
-        width, height, pitch, mod, origin = table[s]
+        width, height, pitch, mod, origin = table[s][:5]
+        fmts[s] = table[s][5] if len(table[s]) > 5 else 0
         off = cursor + (mod - cursor) % 16
         x0, y0 = origin if origin is not None else (width // 2 - w // 2, height // 2 - h // 2)
         recs[s] = record(off, pitch, width, height, x0, y0)
-        cursor = off + extent(recs[s])
-    return recs, cursor
+        cursor = off + extent(recs[s], int(fmts[s]))
+    return (recs, fmts, cursor) if len(table[0]) > 5 else (recs, cursor)
 
 
-def pack(recs, frames, nbytes, seed):
-    """A noise buffer of nbytes in which every record's crop holds frames[s] ([S, h, w])."""
+def pack(recs, frames, nbytes, seed, fmts=None):
+    """A noise buffer of nbytes in which every record's crop, read in its format (fmts None: all grey), holds frames[s]
+    ([S, h, w]).  Every other byte -- the chroma or low byte of each packed pixel included -- keeps the seeded noise, which
+    does not depend on the frames."""
     buf = np.random.default_rng(seed).integers(0, 256, nbytes, dtype=np.uint8)
     h, w = frames.shape[1:]
     for s, rec in enumerate(recs):
-        start = int(rec["offset"]) + int(rec["y0"]) * int(rec["pitch"]) + int(rec["x0"])
+        bpp, phase = _format(0 if fmts is None else int(fmts[s]))
+        pitch = int(rec["pitch"])
+        start = int(rec["offset"]) + int(rec["y0"]) * pitch + int(rec["x0"]) * bpp + phase
         for y in range(h):
-            buf[start + y * int(rec["pitch"]):start + y * int(rec["pitch"]) + w] = frames[s, y]
+            buf[start + y * pitch:start + y * pitch + w * bpp:bpp] = frames[s, y]
     return buf
 
 
@@ -107,7 +124,5 @@ def case(aof, orc, synth, cfg, K=None):
             import bank_camera_ref as cref
             import bank_ref as ref
             run = cref.add_saturated_patches(ref.make_run(synth, p.width, p.height, S, T, seed))
-            for k0 in range(0, T - T % K, K):
-                run.active[k0:k0 + K] = run.active[k0:k0 + K].cumprod(axis=0)
-            _cases[(cfg, K)] = (p, run)
+            _cases[(cfg, K)] = (p, bank_rig.burstable(run, K))
     return _cases[(cfg, K)]

@@ -1,7 +1,10 @@
 """The reference side of the packed-pixel tests (tests/bank_pixels_ref.py), checked on the CPU: the byte-by-byte crop is
 plain numpy slicing, the packer's crops are the run's frames, the inputs can tell a wrong phase and a forgotten bpp from
-the right crop, the tables carry the layouts the GPU tests rely on, and the library's aof_bank_sensor_valid_format -- the
-kernels' rule compiled for the host -- is the Python rule at every edge."""
+the right crop, the tables carry the layouts the GPU tests rely on, the library's aof_bank_sensor_valid_format -- the
+kernels' rule compiled for the host -- is the Python rule at every edge, and the packed layouts and buffers are pinned by
+sha256."""
+import hashlib
+
 import numpy as np
 import pytest
 
@@ -28,7 +31,7 @@ def test_the_model_is_numpy_slicing_and_the_packers_crops_are_the_runs_frames(sy
     recs, fmts, nbytes = pref.layout(table, order, w, w)
     run = ref.make_run(synth, w, w, S, 2, seed)
     for k in range(2):
-        buf = pref.pack(recs, fmts, run.frames[k], nbytes, [seed, k])
+        buf = pref.pack(recs, run.frames[k], nbytes, [seed, k], fmts)
         noise = np.random.default_rng([seed, k]).integers(0, 256, nbytes, dtype=np.uint8)
         for s in range(S):
             fmt = int(fmts[s])
@@ -47,7 +50,7 @@ def test_the_inputs_tell_a_wrong_phase_and_a_forgotten_bpp_from_the_right_crop(s
     w = SIZE[cfg]
     recs, fmts, nbytes = pref.layout(*pref.TABLES[cfg], w, w)
     run = ref.make_run(synth, w, w, S, 1, seed)
-    buf = np.concatenate([pref.pack(recs, fmts, run.frames[0], nbytes, seed), np.zeros(2 * w * w, np.uint8)])   # (room for the wrong reads)
+    buf = np.concatenate([pref.pack(recs, run.frames[0], nbytes, seed, fmts), np.zeros(2 * w * w, np.uint8)])   # (room for the wrong reads)
     for s in range(S):
         fmt = int(fmts[s])
         right = pref.crop(buf, recs[s], fmt, w, w)
@@ -125,3 +128,24 @@ def test_the_librarys_rule_with_a_format_is_the_python_rule_at_every_edge(aof):
         assert not pref.valid(sref.record(100, 159, 80, 72, 16, 8), fmt, 64, 64, 1 << 40)
     assert not pref.valid(good, 3, 64, 64, 1 << 40) and pref.valid(good, 0, 64, 64, 1 << 40)
     assert aof.lib.aof_bank_sensor_valid_format(None, 1, 64, 64, 0, 1) == EINVAL
+
+
+PINS = {
+    # cfg: (bytes, sha256 of the records and the formats, sha256 of the packed buffer), recorded from bank_pixels_ref's own
+    # layout() and pack() in front of their merge into bank_sensors_ref's
+    "px4-64": (131441, "8a4bedbdba5247aa7db2d6e2da62c64d7b32f1d6cbf1a374548c3de83a4878a1",
+               "fb2cc0069eebb6e409c7e10b39cfb63aa31f848f8c328f3324d28ae307f8516d"),
+    "opencv-128": (119688, "66d3382ceb2f434bb4d045a9db8a08aa78cf9933d9f80078820c41045b1716f6",
+                   "392ea56223742d73048b06af1e8e5b27be99aadf46f86ede820489f556915a5f"),
+}
+
+
+@pytest.mark.parametrize("cfg", sorted(PINS))
+def test_the_packed_layout_and_the_packed_buffer_are_pinned(cfg):
+    w = SIZE[cfg]
+    want_bytes, want_layout, want_buffer = PINS[cfg]
+    recs, fmts, nbytes = pref.layout(*pref.TABLES[cfg], w, w)
+    assert fmts.dtype == np.uint8 and nbytes == want_bytes
+    assert hashlib.sha256(recs.tobytes() + fmts.tobytes()).hexdigest() == want_layout
+    frames = np.random.default_rng(1).integers(0, 256, (len(recs), w, w), dtype=np.uint8)
+    assert hashlib.sha256(pref.pack(recs, frames, nbytes, [5, 0], fmts).tobytes()).hexdigest() == want_buffer

@@ -1,6 +1,9 @@
 """The reference side of the per-stream sensor tests (tests/bank_sensors_ref.py), checked on the CPU: the packer's crops
 are the run's frames, the validity rule holds at every edge, and the inputs of the GPU tests meet the census on the
-ORACLE's records (bank_rig.LIMITED, bank_rig.GATED) -- a bank that never publishes, holds, idles or gates cannot pass."""
+ORACLE's records (bank_rig.LIMITED, bank_rig.GATED) -- a bank that never publishes, holds, idles or gates cannot pass.
+The grey layouts and buffers are pinned by sha256."""
+import hashlib
+
 import numpy as np
 import pytest
 
@@ -72,3 +75,23 @@ def test_the_chosen_seeds_meet_the_census_on_the_oracle(aof, orc, synth, cfg):
     n_due, n_not = due.sum(0), ((run.active == 1) & (due == 0)).sum(0)
     assert n_due.min() >= GATED[0] and n_not.min() >= GATED[1], (n_due, n_not)
     assert run.T == 48 and any(any(w) for w in wire)
+
+
+PINS = {
+    # cfg: (bytes, sha256 of the records, sha256 of the packed buffer), recorded in front of the pixel format becoming an
+    # argument of layout() and pack(): grey is what it was
+    "px4-64": (104097, "ae0c9abd7440eebe5da015a39464aa483553098214b5dac60c38da23a5e43fa4",
+               "dfe52d0826061f3be7cea473591e1d4cb5c49c9e799c5dfc69384a0a503ae43d"),
+    "opencv-128": (70117, "32fb756cb5ac414093dec22e6b189405848803143b629e7198909d8578df06ea",
+                   "c98e77ff909401b99360380ee0944340a72fbb660b77038b33aaee081ab736bc"),
+}
+
+
+@pytest.mark.parametrize("cfg", sorted(PINS))
+def test_the_grey_layout_and_the_grey_buffer_are_pinned(cfg):
+    w = 64 if cfg == "px4-64" else 128
+    want_bytes, want_layout, want_buffer = PINS[cfg]
+    recs, nbytes = sref.layout(*sref.TABLES[cfg], w, w)
+    assert nbytes == want_bytes and hashlib.sha256(recs.tobytes()).hexdigest() == want_layout
+    frames = np.random.default_rng(1).integers(0, 256, (len(recs), w, w), dtype=np.uint8)
+    assert hashlib.sha256(sref.pack(recs, frames, nbytes, [5, 0]).tobytes()).hexdigest() == want_buffer

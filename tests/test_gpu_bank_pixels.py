@@ -2,7 +2,7 @@
 Y16-like buffers whose other byte per pixel is noise, against the grey sensor path fed the de-interleaved planes -- the
 form tests/test_gpu_bank_sensors.py holds to the oracle -- and against the oracle itself, by bytes, never by tolerance.
 The layouts, the packer and the rule in Python: tests/bank_pixels_ref.py (checked on the CPU: tests/test_bank_pixels_ref.py);
-the rigs: tests/bank_rig.py and tests/bank_pixels_rig.py."""
+the rigs: tests/bank_rig.py and tests/bank_sensor_rig.py."""
 
 import numpy as np
 import pytest
@@ -11,21 +11,19 @@ import bank_camera_ref as cref
 import bank_pixels_ref as pref
 import bank_sensors_ref as sref
 import ingest_ref
-import bank_pixels_rig as gs
 from bank_ref import FX, FY
-from bank_rig import EINVAL, OFFSET, Guarded, same, same_exposure, same_records, untouched
+from bank_rig import EINVAL, OFFSET, Guarded, counts_of, put, same, same_exposure, same_records, untouched, up
+from bank_sensor_rig import SLACK, SensorRig, cameras, same_rigs, table_tensor
 from bank_rig import time_limit   # (this module's fixture too: every test under a limit of its own)
 
 pytestmark = pytest.mark.gpu
 
-SLACK = gs.SLACK
 INTERVAL = sref.INTERVAL
-up, table_tensor, put, counts_of, same_rigs = gs.up, gs.table_tensor, gs.put, gs.counts_of, gs.same_rigs
 
 
 def engines_and_cam(aof, synth, orc, cfg, path, n=2, K=None):
     p, run = sref.case(aof, orc, synth, cfg, K=K)[:2]
-    cam = gs.cameras(aof, cfg, p)[0]
+    cam = cameras(aof, cfg, p)[0]
     bp = aof.bank_params(run.S, FX, FY, 15, OFFSET, 1, 100, 0)
     engs = [aof.FlowEngine(p, 0) for _ in range(n)]
     for e in engs:
@@ -41,7 +39,7 @@ def test_mixed_formats_leave_the_bytes_of_the_grey_sensor_path(aof, orc, synth, 
     """48 ticks (first frames, due and not-due exposure ticks, idle streams: the census of bank_sensors_ref.case): every
     output buffer, the banks' frames and state and the gates equal after every tick."""
     p, run, cam, bp, (ea, eb) = engines_and_cam(aof, synth, orc, cfg, path)
-    a, b = gs.PixelRig(aof, ea, run, bp, gpu_device, cam, cfg), gs.SensorRig(aof, eb, run, bp, gpu_device, cam, cfg)
+    a, b = SensorRig(aof, ea, run, bp, gpu_device, cam, cfg, formats=True), SensorRig(aof, eb, run, bp, gpu_device, cam, cfg)
     a.bind(), b.bind()
     assert set(a.layout_formats[0].tolist()) == {0, 1, 2}
     for k in range(sref.T):
@@ -59,7 +57,7 @@ def test_mixed_formats_equal_the_oracle_chain_per_stream(aof, orc, synth, gpu_de
     p, run, want, wire, due, after, derot = sref.case(aof, orc, synth, cfg)
     S = run.S
     _, _, cam, bp, (eng,) = engines_and_cam(aof, synth, orc, cfg, path, n=1)
-    a = gs.PixelRig(aof, eng, run, bp, gpu_device, cam, cfg)
+    a = SensorRig(aof, eng, run, bp, gpu_device, cam, cfg, formats=True)
     a.bind()
     uniform = cref.CameraRun(run, *sref.UNIFORM[cfg], 9)     # (the oracle crops at the centre: the same crops)
     for k in range(sref.T):
@@ -81,8 +79,8 @@ def test_formats_that_are_all_grey_change_no_byte_against_sensors_bound_alone(ao
     cfg, K = "px4-64", 3
     p, run, cam, bp, (ea, eb) = engines_and_cam(aof, synth, orc, cfg, path, K=K)
     S = run.S
-    a, b = (gs.SensorRig(aof, e, run, bp, gpu_device, cam, cfg) for e in (ea, eb))
-    ka, kb = (gs.SensorRig(aof, r.eng, run, bp, gpu_device, cam, cfg, K=K, pad=5, bank=r.bank) for r in (a, b))
+    a, b = (SensorRig(aof, e, run, bp, gpu_device, cam, cfg) for e in (ea, eb))
+    ka, kb = (SensorRig(aof, r.eng, run, bp, gpu_device, cam, cfg, K=K, pad=5, bank=r.bank) for r in (a, b))
     grey = torch.zeros(S + 1, dtype=torch.uint8, device=gpu_device)[1:]
     ea.set_bank_pixel_formats(grey, S)
     given = counts_of(run, K, sref.T)
@@ -108,8 +106,8 @@ def test_a_burst_equals_single_ticks_with_the_same_formats(aof, orc, synth, gpu_
     T = sref.T - sref.T % K      # (every whole burst of the run: 9 of K = 5, 3 of K = 16)
     p, run, cam, bp, (ea, eb) = engines_and_cam(aof, synth, orc, cfg, path, K=K)
     S = run.S
-    a = gs.PixelRig(aof, ea, run, bp, gpu_device, cam, cfg, K=K, pad=37)
-    b = gs.PixelRig(aof, eb, run, bp, gpu_device, cam, cfg)
+    a = SensorRig(aof, ea, run, bp, gpu_device, cam, cfg, K=K, pad=37, formats=True)
+    b = SensorRig(aof, eb, run, bp, gpu_device, cam, cfg, formats=True)
     a.bind(), b.bind()
     given = counts_of(run, K, sref.T)
     later = 0
@@ -137,8 +135,8 @@ def test_formats_and_offsets_rewritten_every_tick_eager_and_through_a_replayed_g
     p, run, cam, bp, (ea, eb) = engines_and_cam(aof, synth, orc, cfg, path)
     S = run.S
     other = [(int(f) + 1) % 3 for f in pref.layout(*pref.TABLES[cfg], 64, 64)[1]]
-    a = gs.PixelRig(aof, ea, run, bp, gpu_device, cam, cfg, tables=[pref.TABLES[cfg], pref.retable(cfg, other)])
-    b = gs.SensorRig(aof, eb, run, bp, gpu_device, cam, cfg)
+    a = SensorRig(aof, ea, run, bp, gpu_device, cam, cfg, tables=[pref.TABLES[cfg], pref.retable(cfg, other)], formats=True)
+    b = SensorRig(aof, eb, run, bp, gpu_device, cam, cfg)
     a.bind(), b.bind()
     assert all(a.layout_formats[0][s] != a.layout_formats[1][s] and int(a.layouts[0][s]["offset"]) != int(a.layouts[1][s]["offset"])
                for s in range(S))
@@ -189,7 +187,7 @@ def test_an_invalid_record_or_format_makes_the_stream_idle_with_its_own_quality(
     cfg, T = "px4-64", 12
     p, run, cam, bp, (ea, ec) = engines_and_cam(aof, synth, orc, cfg, path)
     S = run.S
-    a, c = (gs.PixelRig(aof, e, run, bp, gpu_device, cam, cfg) for e in (ea, ec))
+    a, c = (SensorRig(aof, e, run, bp, gpu_device, cam, cfg, formats=True) for e in (ea, ec))
     a.bind(), c.bind()
     packed = [s for s in range(S) if a.layout_formats[0][s] != pref.GREY8]
     for i in range(3):
@@ -229,7 +227,7 @@ def test_a_burst_whose_last_round_falls_outside_serves_the_rounds_before_it(aof,
     cfg, K = "px4-64", 3
     p, run, cam, bp, (ea, ec) = engines_and_cam(aof, synth, orc, cfg, path, K=K)
     last = pref.TABLES[cfg][1][-1]
-    a, c = (gs.PixelRig(aof, e, run, bp, gpu_device, cam, cfg, K=K, pad=16) for e in (ea, ec))
+    a, c = (SensorRig(aof, e, run, bp, gpu_device, cam, cfg, K=K, pad=16, formats=True) for e in (ea, ec))
     a.bind(), c.bind()
     assert a.layout_formats[0][last] == pref.LUMA16_HI
     given = counts_of(run, K, sref.T)
@@ -383,7 +381,7 @@ def test_bindings_and_refusals(aof, orc, synth, gpu_device):
     cfg = "px4-64"
     p, run, cam, bp, (ea, eb) = engines_and_cam(aof, synth, orc, cfg, 0)
     S = run.S
-    a, b = gs.PixelRig(aof, ea, run, bp, gpu_device, cam, cfg), gs.SensorRig(aof, eb, run, bp, gpu_device, cam, cfg)
+    a, b = SensorRig(aof, ea, run, bp, gpu_device, cam, cfg, formats=True), SensorRig(aof, eb, run, bp, gpu_device, cam, cfg)
     a.bind(), b.bind()
     setter = aof.lib.aof_set_bank_pixel_formats
     base = a.formats.data_ptr()
@@ -415,7 +413,7 @@ def test_bindings_and_refusals(aof, orc, synth, gpu_device):
     assert (q == np.where(run.active[3] != 0, 0, aof.TICK_IDLE)).all(), "the plain push on pre-cropped frames, whatever is bound"
     # formats unbound, sensors bound alone: the grey layouts on the same engine and bank
     ea.set_bank_pixel_formats(None)
-    g = gs.SensorRig(aof, ea, run, bp, gpu_device, cam, cfg, bank=a.bank)
+    g = SensorRig(aof, ea, run, bp, gpu_device, cam, cfg, bank=a.bank)
     g.bind()
     for k in (3, 4, 5):
         g.load(k), g.enqueue()

@@ -3,7 +3,7 @@ sizes, row pitches, alignments and crop origins in one camera buffer, against th
 oracle (uniform sensor frames, nothing bound) and against the oracle itself -- by bytes, never by tolerance.  The scalars
 of aof_bank_camera hold a sensor size no stream has: a kernel that still reads them cannot pass.  The layouts, the packer
 and the validity rule in Python: tests/bank_sensors_ref.py (its census: tests/test_bank_sensors_ref.py); the rig:
-tests/bank_rig.py."""
+tests/bank_rig.py and tests/bank_sensor_rig.py."""
 
 import numpy as np
 import pytest
@@ -12,82 +12,13 @@ import bank_camera_ref as cref
 import bank_sensors_ref as sref
 import ingest_ref
 from bank_ref import FX, FY
-from bank_rig import EINVAL, OFFSET, BankRig, Guarded, same, same_exposure, same_records, untouched
+from bank_rig import EINVAL, OFFSET, BankRig, Guarded, counts_of, put, same, same_exposure, same_records, untouched, up
+from bank_sensor_rig import SLACK, SensorRig, cameras, same_rigs, table_tensor
 from bank_rig import time_limit   # (this module's fixture too: every test under a limit of its own)
 
 pytestmark = pytest.mark.gpu
 
-SLACK = 4096      # bytes allocated (with BankRig's 64) behind what the library is told: a kernel without the guard would still read memory of the test's
 INTERVAL = sref.INTERVAL
-
-
-def up(dev, a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def table_tensor(dev, recs):
-    t = up(dev, np.ascontiguousarray(recs).view(np.uint8).reshape(len(recs), 32))
-    assert t.data_ptr() % 16 == 0
-    return t
-
-
-def put(t, s, rec):
-    """Record s of a bound array, rewritten on the current stream: in order with the ticks around it."""
-    t[s].copy_(up(t.device, np.frombuffer(np.asarray(rec).tobytes(), np.uint8).copy()))
-
-
-def counts_of(run, K, T):
-    a = run.active[:T - T % K].reshape(-1, K, run.S)
-    assert (a.cumprod(axis=1).sum(axis=1) == a.sum(axis=1)).all(), "a burst's frames are a stream's first rounds"
-    return a.sum(axis=1).astype(np.uint8)
-
-
-def cameras(aof, cfg, p):
-    """(A's aof_bank_camera: scalars no stream has; B's: the uniform sensor) with the same interval and de-rotation."""
-    mk = lambda size: aof.bank_camera_params(size[0], size[1], p.width, p.height, 0, INTERVAL, cref.DEROTATE, FX, FY)
-    return mk(sref.SCALARS[cfg]), mk(sref.UNIFORM[cfg])
-
-
-class SensorRig(BankRig):
-    """BankRig whose camera buffer holds the mixed layouts of bank_sensors_ref.TABLES[cfg]: `copies` layouts one behind the
-    other per round (the rotating-buffer test uses two), the buffer one byte into its allocation, SLACK bytes allocated
-    behind what the library is told (camera_bytes).  round_stride is always passed: 0 would mean the scalars' size.
-    bind() binds the records of layout 0 (self.table: rewrite it with put())."""
-
-    def __init__(self, aof, eng, run, bp, dev, cam, cfg, K=None, pad=0, bank=None, copies=1, seed=5):
-        import torch
-        scalars = type("Scalars", (), dict(cam_w=cam.ingest.camera_width, cam_h=cam.ingest.camera_height))
-        super().__init__(aof, eng, run, bp, dev, K=K, camera=(cam, scalars), bank=bank)
-        table, order = sref.TABLES[cfg]
-        self.layouts, end = [], 0
-        for _ in range(copies):
-            recs, end = sref.layout(table, order, cam.ingest.crop_width, cam.ingest.crop_height, start=end)
-            self.layouts.append(recs)
-        R = K or 1
-        self.recs, self.layout_bytes, self.seed = self.layouts[0], end, seed
-        self.round = end + pad
-        self.round_stride = self.round
-        self.camera_bytes = (R - 1) * self.round + end
-        self.alloc = torch.zeros(1 + R * self.round + SLACK + 64, dtype=torch.uint8, device=dev)
-        self.frames = self.alloc[1:1 + R * self.round]
-        self.table = table_tensor(dev, self.recs)
-
-    def bind(self, camera_bytes=None):
-        self.eng.set_bank_sensors(self.table, self.run.S, self.camera_bytes if camera_bytes is None else camera_bytes)
-
-    def load(self, k, given=None, sensors=None, which=0):
-        """As BankRig.load; the frames of every round packed by layout `which` into a buffer of noise."""
-        t, run, R = self.torch, self.run, self.K or 1
-        for r in range(R):
-            buf = sref.pack(self.layouts[which], run.frames[k * R + r], self.layout_bytes, [self.seed, k * R + r])
-            self.frames[r * self.round:r * self.round + self.layout_bytes].copy_(t.from_numpy(buf))
-        ticks = slice(k * R, (k + 1) * R)
-        self.times.copy_(t.from_numpy(run.times[ticks]).view(self.times.shape))
-        self.select.copy_(t.from_numpy(run.active[k] if self.K is None else given[k]))
-        self.gyro.copy_(t.from_numpy(run.gyro[ticks]).view(self.gyro.shape))
-        for g in self.outputs:
-            g.refill()
 
 
 def pair_of_rigs(aof, synth, orc, gpu_device, cfg, path, **kw):
@@ -102,12 +33,6 @@ def pair_of_rigs(aof, synth, orc, gpu_device, cfg, path, **kw):
     a.bind()
     b = BankRig(aof, eb, run, bp, gpu_device, camera=(cam_b, cref.CameraRun(run, *sref.UNIFORM[cfg], 9)))
     return (ea, eb), a, b
-
-
-def same_rigs(a, b, what):
-    assert a.raw() == b.raw(), (what, "outputs")
-    assert a.bank_bytes() == b.bank_bytes(), (what, "bank frames and state")
-    assert a.gate_bytes().tolist() == b.gate_bytes().tolist(), (what, "gates")
 
 
 # ---- 1. a bank of one, against the form that is held to the oracle ----

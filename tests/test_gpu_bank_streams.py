@@ -11,7 +11,7 @@ import pytest
 import bank_ref as ref
 import bank_streams_ref as sref
 from bank_ref import FX, FY
-from bank_rig import EINVAL, BankRig, params_of, same_records, untouched
+from bank_rig import EINVAL, BankRig, burstable, counts_of, params_of, put, same_records, untouched, up
 from bank_rig import time_limit   # (this module's fixture too: every test under a limit of its own)
 
 pytestmark = pytest.mark.gpu
@@ -21,22 +21,12 @@ UNUSED = dict(focal_x=51.5, focal_y=49.25, output_rate=7, offset_timestamp_usec=
 SENSOR = (96, 80)   # sensor frames of the camera forms: centre-cropped to 64 x 64
 
 
-def up(dev, a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
 def bind(aof, eng, dev, recs, n_streams=None):
     """Binds the BANK_STREAM_DTYPE array `recs`; returns the device tensor [n, 32] (rewrite it with put())."""
     t = up(dev, recs.view(np.uint8).reshape(len(recs), 32))
     assert t.data_ptr() % 16 == 0
     eng.set_bank_streams(t, n_streams)
     return t
-
-
-def put(t, s, rec):
-    """Record s of a bound array, rewritten on the current stream: in order with the ticks around it."""
-    t[s].copy_(up(t.device, np.frombuffer(np.asarray(rec).tobytes(), np.uint8)))
 
 
 def sensors_of(frames, seed):
@@ -58,21 +48,6 @@ class NoiseSensors:
 
     def sensor(self, k):
         return sensors_of(self.run.frames[k], self.seed + k)
-
-
-def counts_of(run, K):
-    """count [T // K, S] of a burstable run's bursts of K rounds."""
-    a = run.active[:run.T - run.T % K].reshape(-1, K, run.S)
-    assert (a.cumprod(axis=1).sum(axis=1) == a.sum(axis=1)).all(), "a burst's frames are a stream's first rounds"
-    return a.sum(axis=1).astype(np.uint8)
-
-
-def burstable(run, K):
-    """The run with every stream's frames of a burst of K rounds moved to nobody: inside rounds [jK, jK + K) a stream
-    keeps its leading frames only (aof_bank_burst's count).  The dropped frames are never given to anyone."""
-    for k0 in range(0, run.T - run.T % K, K):
-        run.active[k0:k0 + K] = run.active[k0:k0 + K].cumprod(axis=0)
-    return run
 
 
 _expected = {}

@@ -3,17 +3,13 @@ depended on which other kernels of its translation unit shared its instantiation
 each compiles to are pinned here: a change that moves a kernel's ISA fails this test until tests/golden/isa_hashes.txt
 is regenerated (tools/isa_hashes.py --update) in the same commit -- so no kernel's code moves unnoticed.  CPU-side:
 hipcc cross-compiles gfx950 without a GPU."""
-import importlib.util
 import os
 import shutil
 import tempfile
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-spec = importlib.util.spec_from_file_location("isa_hashes", os.path.join(ROOT, "tools", "isa_hashes.py"))
-isa = importlib.util.module_from_spec(spec)
-spec.loader.exec_module(isa)
+from kernel_census import tool as isa
 
 pytestmark = pytest.mark.skipif(not os.path.exists(isa.HIPCC), reason="hipcc not installed")
 
