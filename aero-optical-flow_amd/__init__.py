@@ -130,6 +130,7 @@ class BankBurst(C.Structure):
 
 BANK_BURST_MAX = 16
 TICK_HELD, TICK_IDLE = -1, -2
+BANK_BIN_MAX = 4   # AOF_BANK_BIN_MAX: a stream's binning is 1, 2 or 4 (aof_set_bank_binning)
 PIXEL_GREY8, PIXEL_LUMA16_LO, PIXEL_LUMA16_HI = 0, 1, 2   # AOF_PIXEL_*: a stream's pixel format (aof_set_bank_pixel_formats)
 TICK_BAD_SENSOR = -5   # the stream's sensor record (aof_bank_sensor) does not describe memory inside the camera buffer
 TICK_DTYPE = np.dtype([("quality", "<i4"), ("dt_us", "<i4"), ("flow_x", "<f4"), ("flow_y", "<f4"),
@@ -290,6 +291,11 @@ def _load():
         "aof_set_bank_pixel_formats": (C.c_int, [VP, VP, C.c_int32]),
         "aof_bank_sensor_valid_format": (C.c_int, [P(BankSensor), C.c_uint8, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64]),
         "aof_ingest_sensor_formats_device": (C.c_int, [C.c_int32, C.c_int32, VP, C.c_uint64, VP, VP, I64, VP, I64, VP, VP, VP]),
+        "aof_set_bank_binning": (C.c_int, [VP, VP, C.c_int32]),
+        "aof_bank_sensor_valid_binned": (C.c_int, [P(BankSensor), C.c_uint8, C.c_uint8, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64]),
+        "aof_bank_sensor_centred_binned": (C.c_int, [P(Params), C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_uint8, C.c_uint8,
+                                                     P(BankSensor)]),
+        "aof_ingest_sensors_binned_device": (C.c_int, [C.c_int32, C.c_int32, VP, C.c_uint64, VP, VP, VP, I64, VP, I64, VP, VP, VP]),
         "aof_bank_camera_layout": (C.c_int, [P(Params), P(BankParams), P(BankCamera), P(BankLayout), P(C.c_size_t)]),
         "aof_bank_push_camera_device": (C.c_int, [VP, P(BankParams), P(BankCamera), VP, VP, VP, VP, VP, C.c_size_t, VP, VP, VP,
                                                   VP, VP, VP]),
@@ -489,21 +495,29 @@ def bank_sensor_from_camera(p: Params, cam: BankCamera, stream=None, n=None):
     return np.array([one(s) for s in range(int(n))], dtype=BANK_SENSOR_DTYPE)
 
 
-def bank_sensor_centred(p: Params, offset, pitch, width, height):
-    """aof_bank_sensor_centred: the record of a frame of width x height, rows ``pitch`` bytes apart, ``offset`` bytes into
-    the camera buffer, with the crop at the centre (the reference's rule)."""
+def bank_sensor_centred(p: Params, offset, pitch, width, height, format=0, bin=1):
+    """aof_bank_sensor_centred / aof_bank_sensor_centred_binned: the record of a frame of width x height, rows ``pitch``
+    bytes apart, ``offset`` bytes into the camera buffer, with the crop at the centre (the reference's rule); with a pixel
+    format (PIXEL_*) or a bin (1, 2, 4): the footprint of the binned crop at the centre, checked by the kernels' rule."""
     rec = BankSensor()
-    rc = lib.aof_bank_sensor_centred(C.byref(p), int(offset), int(pitch), int(width), int(height), C.byref(rec))
+    if format == 0 and bin == 1:
+        rc = lib.aof_bank_sensor_centred(C.byref(p), int(offset), int(pitch), int(width), int(height), C.byref(rec))
+    else:
+        rc = lib.aof_bank_sensor_centred_binned(C.byref(p), int(offset), int(pitch), int(width), int(height), int(format) & 0xFF,
+                                                int(bin) & 0xFF, C.byref(rec))
     if rc:
         raise AofError(rc, lib.aof_strerror(rc).decode())
     return _sensor_record(rec)
 
 
-def bank_sensor_valid(rec, crop_w, crop_h, camera_bytes, base=0, format=0) -> bool:
-    """aof_bank_sensor_valid / aof_bank_sensor_valid_format: the kernels' validity rule on one BANK_SENSOR_DTYPE record of
-    pixel format ``format`` (PIXEL_*), compiled for the host."""
+def bank_sensor_valid(rec, crop_w, crop_h, camera_bytes, base=0, format=0, bin=1) -> bool:
+    """aof_bank_sensor_valid / _valid_format / _valid_binned: the kernels' validity rule on one BANK_SENSOR_DTYPE record of
+    pixel format ``format`` (PIXEL_*) and binning ``bin`` (a byte: 1, 2, 4 are bins), compiled for the host."""
     r = BankSensor.from_buffer_copy(np.asarray(rec, dtype=BANK_SENSOR_DTYPE).tobytes())
-    if format == 0:
+    if bin != 1:
+        rc = lib.aof_bank_sensor_valid_binned(C.byref(r), int(format) & 0xFF, int(bin) & 0xFF, int(crop_w), int(crop_h), int(base),
+                                              int(camera_bytes))
+    elif format == 0:
         rc = lib.aof_bank_sensor_valid(C.byref(r), int(crop_w), int(crop_h), int(base), int(camera_bytes))
     else:
         rc = lib.aof_bank_sensor_valid_format(C.byref(r), int(format) & 0xFF, int(crop_w), int(crop_h), int(base), int(camera_bytes))
@@ -513,16 +527,18 @@ def bank_sensor_valid(rec, crop_w, crop_h, camera_bytes, base=0, format=0) -> bo
 
 
 def ingest_sensors(camera, sensors, crop_w, crop_h, camera_bytes=None, cropped=None, hist=None, ok=None, want_cropped=True,
-                   want_hist=True, want_ok=True, formats=None):
+                   want_hist=True, want_ok=True, formats=None, bins=None):
     """aof_ingest_sensors_device: frame ingest on the device for frames that sensor records describe.  camera: uint8 CUDA
     tensor (any shape; the records' offsets count from its first byte); sensors: uint8 CUDA tensor of n * 32 bytes
     (BANK_SENSOR_DTYPE, 16-byte aligned); camera_bytes: bytes of ``camera`` the kernel may read (default: all).
-    formats: None, or a uint8 CUDA tensor of n pixel formats (PIXEL_*; aof_ingest_sensor_formats_device).  Returns
+    formats: None, or a uint8 CUDA tensor of n pixel formats (PIXEL_*; aof_ingest_sensor_formats_device).  bins: None, or
+    a uint8 CUDA tensor of n bins (1, 2, 4; aof_ingest_sensors_binned_device): crop_w x crop_h is the binned crop.  Returns
     (cropped [n, crop_h, crop_w], hist [n, 10] int32, ok [n] uint8), None where not wanted."""
     import torch
     assert camera.dtype == torch.uint8 and sensors.dtype == torch.uint8 and sensors.is_contiguous() and sensors.numel() % 32 == 0
     n = sensors.numel() // 32
     assert formats is None or (formats.dtype == torch.uint8 and formats.is_contiguous() and formats.numel() == n)
+    assert bins is None or (bins.dtype == torch.uint8 and bins.is_contiguous() and bins.numel() == n)
     dev = camera.device
     if cropped is None and want_cropped:
         cropped = torch.empty((n, crop_h, crop_w), dtype=torch.uint8, device=dev)
@@ -534,7 +550,9 @@ def ingest_sensors(camera, sensors, crop_w, crop_h, camera_bytes=None, cropped=N
     tail = (n, opt(cropped), cropped.stride(0) if cropped is not None and n else crop_w * crop_h, opt(hist), opt(ok),
             torch.cuda.current_stream(dev).cuda_stream)
     head = (int(crop_w), int(crop_h), camera.data_ptr(), camera.numel() if camera_bytes is None else int(camera_bytes), sensors.data_ptr())
-    if formats is None:
+    if bins is not None:
+        rc = lib.aof_ingest_sensors_binned_device(*head, opt(formats), bins.data_ptr(), *tail)
+    elif formats is None:
         rc = lib.aof_ingest_sensors_device(*head, *tail)
     else:
         rc = lib.aof_ingest_sensor_formats_device(*head, formats.data_ptr(), *tail)
@@ -1322,6 +1340,23 @@ class FlowEngine:
         self._check(lib.aof_set_bank_pixel_formats(self._ctx, formats.data_ptr(), n))
         self._bank_formats = formats   # (kept alive for as long as it is bound)
 
+    def set_bank_binning(self, bins=None, n_streams=None):
+        """aof_set_bank_binning: binds a uint8 CUDA tensor of S bins (1, 2 or 4; any alignment) to the context, or with None
+        unbinds.  n_streams: S, where the tensor holds more.  Used by the camera pushes next to bound sensor records
+        (set_bank_sensors): a pixel of stream s's crop is then the rounded mean of bin x bin sensor pixels.  The focal
+        length stays the caller's (focal / bin through set_bank_streams).  The kernels read it when they run: keep it alive;
+        it may be rewritten between ticks."""
+        if bins is None:
+            self._check(lib.aof_set_bank_binning(self._ctx, None, 0))
+            self._bank_bins = None
+            return
+        import torch
+        assert bins.dtype == torch.uint8 and bins.is_contiguous()
+        n = bins.numel() if n_streams is None else int(n_streams)
+        assert n <= bins.numel()
+        self._check(lib.aof_set_bank_binning(self._ctx, bins.data_ptr(), n))
+        self._bank_bins = bins   # (kept alive for as long as it is bound)
+
     def set_bank_path(self, path=0):
         """0: the library chooses between the one-launch tick kernel and the composed path, 1: the tick kernel where
         the configuration allows it, 2: always the composed path.  Same bytes either way."""
@@ -1448,6 +1483,7 @@ def facade_lib():
         f.aof_facade_bank_set_stream_timestamp_offset.argtypes = [C.c_void_p, C.c_int, C.c_uint64]
         f.aof_facade_bank_set_stream_sensor.argtypes = [C.c_void_p, C.c_int, C.c_uint64] + [C.c_int] * 5
         f.aof_facade_bank_set_stream_pixel_format.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        f.aof_facade_bank_set_stream_binning.argtypes = [C.c_void_p, C.c_int, C.c_int]
         f.aof_facade_bank_enable_camera_packed.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32]
         f.aof_facade_bank_push.argtypes = [C.c_void_p] * 5
         f.aof_facade_bank_enable_camera.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32]
@@ -1655,6 +1691,11 @@ class OpticalFlowBank:
         """Stream s's own pixel format (PIXEL_*) inside the bytes pushCamera() takes, from the next pushCamera() on.  0, or
         -EINVAL (bad index, a format above 2, before enableCamera(), a record that no longer fits those bytes)."""
         return facade_lib().aof_facade_bank_set_stream_pixel_format(self._h, int(s), int(format))
+
+    def setStreamBinning(self, s, bin):
+        """Stream s's binning (1, 2 or 4) inside the bytes pushCamera() takes, from the next pushCamera() on.  0, or -EINVAL
+        (bad index, another bin, before enableCamera(), a footprint that no longer fits the stream's sensor frame)."""
+        return facade_lib().aof_facade_bank_set_stream_binning(self._h, int(s), int(bin))
 
     def pushCamera(self, sensor_frames, img_time_us, active=None, gyro=None):
         """sensor_frames uint8 [S, camera_height, camera_width] (enableCameraPacked(): [S, camera_height, camera_width *

@@ -277,6 +277,13 @@ int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank
         return ctx_fail(ctx, -EINVAL, "bank: pixel formats are bound (aof_set_bank_pixel_formats) without sensor records");
     if (d_formats && bound_formats != bp->n_streams)
         return ctx_fail(ctx, -EINVAL, "bank: n_streams differs from the array bound with aof_set_bank_pixel_formats");
+    // and the binning (aof_set_bank_binning): likewise, with any format or none
+    int32_t bound_bins = 0;
+    const uint8_t *d_bins = p.camera ? bank_binning(ctx, &bound_bins) : nullptr;
+    if (d_bins && !d_sensors)
+        return ctx_fail(ctx, -EINVAL, "bank: a binning is bound (aof_set_bank_binning) without sensor records");
+    if (d_bins && bound_bins != bp->n_streams)
+        return ctx_fail(ctx, -EINVAL, "bank: n_streams differs from the array bound with aof_set_bank_binning");
     // before the first launch: a faulted or wedged context, or a thread on another device, must not touch the bank
     if ((rc = precheck(ctx))) return rc;
 
@@ -289,7 +296,7 @@ int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank
                            d_streams);
     if (p.camera) camera_args(&a, p.cam, p.src, hist, p.exposure, p.derotated);
     // (bound: the kernels that take this argument read the crop's place, pitch and origin from record s instead)
-    const BankSensors sen = {d_sensors, camera_bytes, 0, d_formats};
+    const BankSensors sen = {d_sensors, camera_bytes, 0, d_formats, d_bins};
     aof_flow *flows = reinterpret_cast<aof_flow *>(bank + L.flows);
     const BankBurst b = {p.burst ? p.rounds->n_rounds : 1, round_stride, p.burst ? p.select : nullptr};
 
@@ -314,14 +321,14 @@ int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank
         if (p.burst) r = round_args(a, k, p.camera ? staging : src);
         if (p.camera) {
             r.cam.camera = src;
-            const IngestSensors crop = {d_sensors, (uint64_t)k * (uint64_t)round_stride, camera_bytes, nullptr, d_formats};
+            const IngestSensors crop = {d_sensors, (uint64_t)k * (uint64_t)round_stride, camera_bytes, nullptr, d_formats, d_bins};
             if (launch_ingest(p.cam->ingest, src, a.cam.camera_stride, bp->n_streams, staging, L.stride, p.exposure ? hist : nullptr, stream, crop))
                 return ctx_fail(ctx, -EIO, "bank camera ingest launch failed");
         }
         rc = aof_flow_batch_device(ctx, a.bank_frames, r.frames, L.stride, bp->n_streams, nullptr, nullptr, flows,
                                    bank + L.pub.scratch, L.flow_ws_bytes, stream);
         if (rc) return rc;
-        const BankSensors round_sen = {d_sensors, camera_bytes, (uint64_t)k * (uint64_t)round_stride, d_formats};
+        const BankSensors round_sen = {d_sensors, camera_bytes, (uint64_t)k * (uint64_t)round_stride, d_formats, d_bins};
         if (launch_bank_commit(r, stream, b.count, b.count ? k : 0, round_sen)) return ctx_fail(ctx, -EIO, "bank commit launch failed");
     }
     return 0;
@@ -386,6 +393,32 @@ int aof_set_bank_pixel_formats(aof_ctx *ctx, const uint8_t *d_formats, int32_t n
     return 0;
 }
 
+int aof_set_bank_binning(aof_ctx *ctx, const uint8_t *d_bins, int32_t n_streams)
+{
+    if (!ctx) return -EINVAL;
+    if (d_bins && n_streams < 1) return ctx_fail(ctx, -EINVAL, "bank binning: an array needs n_streams >= 1");
+    set_bank_binning(ctx, d_bins, n_streams);
+    return 0;
+}
+
+int aof_bank_sensor_centred_binned(const aof_params *p, uint64_t offset, int32_t pitch, int32_t width, int32_t height, uint8_t format,
+                                   uint8_t bin, aof_bank_sensor *out)
+{
+    if (!p || !out) return -EINVAL;
+    if (bin != 1 && bin != 2 && bin != 4) return -EINVAL;
+    aof_bank_sensor rec = {};
+    rec.offset = offset;
+    rec.pitch = pitch;
+    rec.width = width; rec.height = height;
+    rec.x0 = width / 2 - (int32_t)((int64_t)bin * p->width / 2); rec.y0 = height / 2 - (int32_t)((int64_t)bin * p->height / 2);
+    // (the rule against a buffer that ends with the frame: everything but the place in a camera buffer)
+    if (p->width < 1 || p->height < 1 || width < 1 || height < 1 ||
+        !bank_sensor_valid(0, pitch, width, height, rec.x0, rec.y0, p->width, p->height, 0, UINT64_MAX, bank_pixel_bpp(format), bin))
+        return -EINVAL;
+    *out = rec;
+    return 0;
+}
+
 int aof_bank_sensor_centred(const aof_params *p, uint64_t offset, int32_t pitch, int32_t width, int32_t height, aof_bank_sensor *out)
 {
     if (!p || !out) return -EINVAL;
@@ -407,12 +440,18 @@ int aof_bank_sensor_from_camera(const aof_params *p, const aof_bank_camera *cam,
     return aof_bank_sensor_centred(p, (uint64_t)stream * stride, g.camera_width, g.camera_width, g.camera_height, out);
 }
 
-int aof_bank_sensor_valid_format(const aof_bank_sensor *rec, uint8_t format, int32_t crop_width, int32_t crop_height, uint64_t base,
-                                 uint64_t camera_bytes)
+int aof_bank_sensor_valid_binned(const aof_bank_sensor *rec, uint8_t format, uint8_t bin, int32_t crop_width, int32_t crop_height,
+                                 uint64_t base, uint64_t camera_bytes)
 {
     if (!rec) return -EINVAL;
     return bank_sensor_valid(rec->offset, rec->pitch, rec->width, rec->height, rec->x0, rec->y0, crop_width, crop_height, base,
-                             camera_bytes, bank_pixel_bpp(format)) ? 1 : 0;
+                             camera_bytes, bank_pixel_bpp(format), bin) ? 1 : 0;
+}
+
+int aof_bank_sensor_valid_format(const aof_bank_sensor *rec, uint8_t format, int32_t crop_width, int32_t crop_height, uint64_t base,
+                                 uint64_t camera_bytes)
+{
+    return aof_bank_sensor_valid_binned(rec, format, 1, crop_width, crop_height, base, camera_bytes);
 }
 
 int aof_bank_sensor_valid(const aof_bank_sensor *rec, int32_t crop_width, int32_t crop_height, uint64_t base, uint64_t camera_bytes)
@@ -420,9 +459,9 @@ int aof_bank_sensor_valid(const aof_bank_sensor *rec, int32_t crop_width, int32_
     return aof_bank_sensor_valid_format(rec, AOF_PIXEL_GREY8, crop_width, crop_height, base, camera_bytes);
 }
 
-int aof_ingest_sensor_formats_device(int32_t crop_width, int32_t crop_height, const uint8_t *d_camera, uint64_t camera_bytes,
-                                     const aof_bank_sensor *d_sensors, const uint8_t *d_formats, int64_t n_frames, uint8_t *d_cropped,
-                                     int64_t cropped_stride, uint32_t *d_hist, uint8_t *d_ok, void *stream)
+int aof_ingest_sensors_binned_device(int32_t crop_width, int32_t crop_height, const uint8_t *d_camera, uint64_t camera_bytes,
+                                     const aof_bank_sensor *d_sensors, const uint8_t *d_formats, const uint8_t *d_bins, int64_t n_frames,
+                                     uint8_t *d_cropped, int64_t cropped_stride, uint32_t *d_hist, uint8_t *d_ok, void *stream)
 {
     if (crop_width < 1 || crop_height < 1 || n_frames < 0) return -EINVAL;
     if (n_frames == 0) return 0;
@@ -430,8 +469,16 @@ int aof_ingest_sensor_formats_device(int32_t crop_width, int32_t crop_height, co
     if (d_cropped && cropped_stride < (int64_t)crop_width * crop_height && n_frames > 1) return -EINVAL;
     if (n_frames * ((crop_height + 15) / 16) > 0x7FFFFFFF) return -EINVAL;
     const aof_ingest_params g = {crop_width, crop_height, crop_width, crop_height};   // (the sensor size: the records')
-    const IngestSensors sen = {d_sensors, 0, camera_bytes, d_ok, d_formats};
+    const IngestSensors sen = {d_sensors, 0, camera_bytes, d_ok, d_formats, d_bins};
     return launch_ingest(g, d_camera, 0, n_frames, d_cropped, cropped_stride, d_hist, stream, sen) ? -EIO : 0;
+}
+
+int aof_ingest_sensor_formats_device(int32_t crop_width, int32_t crop_height, const uint8_t *d_camera, uint64_t camera_bytes,
+                                     const aof_bank_sensor *d_sensors, const uint8_t *d_formats, int64_t n_frames, uint8_t *d_cropped,
+                                     int64_t cropped_stride, uint32_t *d_hist, uint8_t *d_ok, void *stream)
+{
+    return aof_ingest_sensors_binned_device(crop_width, crop_height, d_camera, camera_bytes, d_sensors, d_formats, nullptr, n_frames,
+                                            d_cropped, cropped_stride, d_hist, d_ok, stream);
 }
 
 int aof_ingest_sensors_device(int32_t crop_width, int32_t crop_height, const uint8_t *d_camera, uint64_t camera_bytes,

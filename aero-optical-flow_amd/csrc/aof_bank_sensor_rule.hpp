@@ -17,12 +17,15 @@ AOF_HD_INLINE int32_t bank_pixel_phase(uint32_t format) { return format == 2 ? 1
 // the camera buffer, the round's frames starting `base` bytes in?  bpp is 1 or 2 (anything else: no); width, x0, w in
 // pixels, pitch in bytes.  pitch >= width * bpp >= 1 and height >= 1 make (height - 1) * pitch + width * bpp a sum of
 // non-negative terms below 2^62 + 2^32; base, then offset, are taken off camera_bytes only after each was seen to fit.
+// bin ("binned sensor pixels"): 1, 2 or 4 (anything else: no) -- a crop pixel is the rounded mean of bin x bin sensor
+// pixels, so the crop's footprint is bin * w x bin * h sensor pixels at (x0, y0); bin * w stays below 2^34.
 AOF_HD_INLINE bool bank_sensor_valid(uint64_t offset, int32_t pitch, int32_t width, int32_t height, int32_t x0, int32_t y0,
-                                     int32_t w, int32_t h, uint64_t base, uint64_t camera_bytes, int32_t bpp = 1)
+                                     int32_t w, int32_t h, uint64_t base, uint64_t camera_bytes, int32_t bpp = 1, int32_t bin = 1)
 {
     if (bpp < 1 || bpp > 2) return false;
+    if (bin != 1 && bin != 2 && bin != 4) return false;
     if (width < 1 || height < 1 || (int64_t)pitch < (int64_t)width * bpp) return false;
-    if (x0 < 0 || y0 < 0 || (int64_t)x0 + w > width || (int64_t)y0 + h > height) return false;
+    if (x0 < 0 || y0 < 0 || (int64_t)x0 + (int64_t)bin * w > width || (int64_t)y0 + (int64_t)bin * h > height) return false;
     if (base > camera_bytes || offset > camera_bytes - base) return false;
     const uint64_t extent = (uint64_t)(height - 1) * (uint64_t)pitch + (uint64_t)width * (uint64_t)bpp;
     return extent <= camera_bytes - base - offset;

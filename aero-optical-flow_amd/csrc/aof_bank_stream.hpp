@@ -84,10 +84,13 @@ __device__ __forceinline__ BankStream bank_stream(const BankArgs &a, uint32_t s)
 // With a format array bound as well (aof_set_bank_pixel_formats) stream s's format byte decides bpp and phase; it is
 // read by the lanes (one byte, no alignment, nothing outside formats[0..S)) and made uniform, so every branch on it is
 // a scalar one.  A value that is no format makes the record invalid (bank_sensor_valid's bpp 0).
+// With a binning array bound (aof_set_bank_binning) stream s's byte is read the same way and decides `bin`: the crop's
+// footprint is bin * w x bin * h sensor pixels at (x0, y0); a value that is none of 1, 2, 4 makes the record invalid.
 struct BankSensor {
     int64_t origin;    // offset + y0 * pitch + x0 * bpp + phase (0 for an invalid record)
     int32_t pitch;
     int32_t bpp, phase;   // bytes per pixel (1, 2); which of a pixel's bytes is its grey value
+    int32_t bin;          // sensor pixels per crop pixel and axis (1, 2, 4)
     bool ok;
 };
 static_assert(sizeof(aof_bank_sensor) == 32 && offsetof(aof_bank_sensor, pitch) == 8 && offsetof(aof_bank_sensor, width) == 12 &&
@@ -95,7 +98,7 @@ static_assert(sizeof(aof_bank_sensor) == 32 && offsetof(aof_bank_sensor, pitch) 
               "a sensor record is two 16-byte words");
 
 __device__ __forceinline__ BankSensor bank_sensor(const aof_bank_sensor *sensors, size_t s, int32_t w, int32_t h, uint64_t base,
-                                                  uint64_t camera_bytes, const uint8_t *formats = nullptr)
+                                                  uint64_t camera_bytes, const uint8_t *formats = nullptr, const uint8_t *bins = nullptr)
 {
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     typedef const u32x4 __attribute__((address_space(4))) *const_words;
@@ -109,7 +112,9 @@ __device__ __forceinline__ BankSensor bank_sensor(const aof_bank_sensor *sensors
         const uint32_t format = (uint32_t)__builtin_amdgcn_readfirstlane((int)formats[s]);
         v.bpp = bank_pixel_bpp(format); v.phase = bank_pixel_phase(format);
     }
-    v.ok = bank_sensor_valid(offset, pitch, width, height, x0, y0, w, h, base, camera_bytes, v.bpp);
+    v.bin = 1;
+    if (bins) v.bin = __builtin_amdgcn_readfirstlane((int)bins[s]);
+    v.ok = bank_sensor_valid(offset, pitch, width, height, x0, y0, w, h, base, camera_bytes, v.bpp, v.bin);
     v.pitch = pitch;
     v.origin = v.ok ? (int64_t)offset + (int64_t)y0 * pitch + (int64_t)x0 * v.bpp + v.phase : 0;
     return v;
@@ -307,16 +312,64 @@ __device__ __forceinline__ void crop_piece16(uint4 &v, const uint8_t *src, int y
     __builtin_memcpy(&v, &r, 16);   // (one whole 16-byte value for either form)
 }
 
+// B rows of a binned piece: sensor rows B y .. B y + B - 1 of the 16 B pixels behind `row` (the grey byte of the first),
+// added into eight registers of two 16-bit sums each -- crop pixel 2 i in the low half of acc[i], 2 i + 1 in the high
+// half.  A row is B grey pieces of crop_piece16 (16 B bpp source bytes, the same unaligned loads and v_perm_b32
+// selection).  B = 2: a grey dword gives two horizontal pair sums, the halves box2 adds; B = 4: a grey dword is one crop
+// pixel's four bytes of the row, v_sad_u8 against zero adds them to the low half, v_sad_hi_u8 to the high half.  The rows
+// go one behind the other (not unrolled): a row's loads are all that is in flight, eight at the most (bpp 2, B = 4).
+template <int B>
+__device__ __forceinline__ void binned_rows(uint32_t (&acc)[8], const uint8_t *row, int pitch, int bpp, int phase)
+{
+    constexpr uint32_t m = 0x00FF00FFu;
+#pragma unroll 1
+    for (int j = 0; j < B; j++, row += pitch) {
+#pragma unroll
+        for (int q = 0; q < B; q++) {
+            uint4 g;
+            crop_piece16(g, row, 0, 0, q, bpp, phase);
+            if constexpr (B == 2) {
+                acc[4 * q + 0] += (g.x & m) + ((g.x >> 8) & m);
+                acc[4 * q + 1] += (g.y & m) + ((g.y >> 8) & m);
+                acc[4 * q + 2] += (g.z & m) + ((g.z >> 8) & m);
+                acc[4 * q + 3] += (g.w & m) + ((g.w >> 8) & m);
+            } else {
+                acc[2 * q] = __builtin_amdgcn_sad_hi_u8(g.y, 0u, byte_sum(g.x, acc[2 * q]));
+                acc[2 * q + 1] = __builtin_amdgcn_sad_hi_u8(g.w, 0u, byte_sum(g.z, acc[2 * q + 1]));
+            }
+        }
+    }
+}
+
+// crop_piece16 for a binned stream (bin 2 or 4, workgroup-uniform): pixels 16 x .. 16 x + 15 of row y of the BINNED crop,
+// each (the sum of its bin x bin sensor pixels + bin^2 / 2) >> (2 log2 bin) -- one rounding of the whole sum, box2's for
+// bin 2.  `src` is the grey byte of sensor pixel (x0, y0).  The piece reads whole pixels x0 + 16 bin x .. x0 + 16 bin
+// (x + 1) - 1 of rows y0 + bin y .. y0 + bin y + bin - 1: inside width and height whenever the footprint is, so
+// bank_sensor_valid (with its bin) is the bounds proof here too.
+__device__ __forceinline__ void crop_piece16_binned(uint4 &v, const uint8_t *src, int y, int pitch, int x, int bpp, int phase, int bin)
+{
+    uint32_t acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const uint8_t *row = src + (int64_t)y * bin * pitch + (int64_t)x * (16 * bin * bpp);
+    uint32_t half, shift;
+    if (bin == 2) { binned_rows<2>(acc, row, pitch, bpp, phase); half = 0x00020002u; shift = 2; }
+    else { binned_rows<4>(acc, row, pitch, bpp, phase); half = 0x00080008u; shift = 4; }
+#pragma unroll
+    for (int i = 0; i < 8; i++) acc[i] = (acc[i] + half) >> shift;   // (bytes 0 and 2 are the two pixels; bytes 1, 3 are not looked at)
+    v = make_uint4(__builtin_amdgcn_perm(acc[1], acc[0], 0x06040200u), __builtin_amdgcn_perm(acc[3], acc[2], 0x06040200u),
+                   __builtin_amdgcn_perm(acc[5], acc[4], 0x06040200u), __builtin_amdgcn_perm(acc[7], acc[6], 0x06040200u));
+}
+
 // CAMERA: the crop of a stream's first frame, sensor rows -> LDS -> slot (a first frame is always due: its histogram
 // comes from the LDS copy).  Ends in a barrier.
 __device__ __forceinline__ void crop_first_frame(const BankCamera &c, const uint8_t *src, int32_t pitch, uint8_t *lds, uint8_t *slot,
-                                                 int bpp = 1, int phase = 0)
+                                                 int bpp = 1, int phase = 0, int bin = 1)
 {
     const int row_chunks = c.crop_w / 16, chunks = row_chunks * c.crop_h;
     for (int i = threadIdx.x; i < chunks; i += kThreads) {
         const int y = i / row_chunks, x = i - y * row_chunks;
         uint4 v;
-        crop_piece16(v, src, y, pitch, x, bpp, phase);
+        if (bin != 1) crop_piece16_binned(v, src, y, pitch, x, bpp, phase, bin);   // (uniform)
+        else crop_piece16(v, src, y, pitch, x, bpp, phase);
         reinterpret_cast<uint4 *>(lds)[i] = v;
         reinterpret_cast<uint4 *>(slot)[i] = v;
     }
@@ -333,19 +386,21 @@ struct BankSource {
     int32_t pitch;
     bool ok;
     int32_t bpp, phase;   // the source's pixel format (crop_piece16); 1, 0 -- constants -- without a sensor argument
+    int32_t bin;          // sensor pixels per crop pixel and axis (crop_piece16_binned); the constant 1 without one
 };
 template <bool CAMERA>
 __device__ __forceinline__ BankSource bank_source(const BankArgs &a, uint32_t s, uint64_t base = 0)
 {
-    if constexpr (CAMERA) return BankSource{a.cam.camera + (int64_t)s * a.cam.camera_stride + a.cam.origin, a.cam.pitch, true, 1, 0};
-    else return BankSource{a.frames + (int64_t)s * a.frame_stride, 0, true, 1, 0};
+    if constexpr (CAMERA) return BankSource{a.cam.camera + (int64_t)s * a.cam.camera_stride + a.cam.origin, a.cam.pitch, true, 1, 0, 1};
+    else return BankSource{a.frames + (int64_t)s * a.frame_stride, 0, true, 1, 0, 1};
 }
 template <bool CAMERA>
 __device__ __forceinline__ BankSource bank_source(const BankArgs &a, uint32_t s, uint64_t base, const BankSensors &sen)
 {
     static_assert(CAMERA, "sensor records belong to the camera forms");
-    const BankSensor r = bank_sensor(sen.recs, s, a.cam.crop_w, a.cam.crop_h, sen.camera_base + base, sen.camera_bytes, sen.formats);
-    return BankSource{a.cam.camera + r.origin, r.pitch, r.ok, r.bpp, r.phase};
+    const BankSensor r = bank_sensor(sen.recs, s, a.cam.crop_w, a.cam.crop_h, sen.camera_base + base, sen.camera_bytes, sen.formats,
+                                     sen.bins);
+    return BankSource{a.cam.camera + r.origin, r.pitch, r.ok, r.bpp, r.phase, r.bin};
 }
 
 // The stream's newest frame out of LDS into its slot, by the whole workgroup.

@@ -450,6 +450,16 @@ void set_bank_pixel_formats(aof_ctx *ctx, const uint8_t *d_formats, int32_t n_st
     ctx->bank_formats = d_formats;
     ctx->bank_formats_n = d_formats ? n_streams : 0;
 }
+const uint8_t *bank_binning(const aof_ctx *ctx, int32_t *n_streams)
+{
+    *n_streams = ctx->bank_bins_n;
+    return ctx->bank_bins;
+}
+void set_bank_binning(aof_ctx *ctx, const uint8_t *d_bins, int32_t n_streams)
+{
+    ctx->bank_bins = d_bins;
+    ctx->bank_bins_n = d_bins ? n_streams : 0;
+}
 
 // Would a sequence-view call (frames viewed twice, n_pairs = frames - 1) run K1 as a pass of its own?  The sequence
 // pipeline asks, because its ingest kernel can leave K1's outputs (pixel sums at ws + L.sums, one level-1 frame per

@@ -134,6 +134,8 @@ struct aof_ctx {
     uint64_t bank_camera_bytes; // bytes the caller guarantees readable from the d_camera of its pushes
     const uint8_t *bank_formats;   // aof_set_bank_pixel_formats: the caller's per-stream pixel formats (device memory), or nullptr
     int32_t bank_formats_n;     // how many streams they are for
+    const uint8_t *bank_bins;   // aof_set_bank_binning: the caller's per-stream binning (device memory), or nullptr
+    int32_t bank_bins_n;        // how many streams it is for
     bool graph_disabled;        // per-call graphs switched off, or a capture failed once: stay on the plain path
     bool capturing;             // a per-call graph is being captured (no event timing)
     bool wedged;                // a bounded wait for the device ran out: every later call fails, destroy frees nothing

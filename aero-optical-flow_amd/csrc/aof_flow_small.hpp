@@ -51,6 +51,7 @@ struct LevelMeta { int px, py, delta; };
 // One 16-byte piece of a crop row out of a sensor frame (defined in aof_bank_stream.hpp, the one place a crop is
 // fetched; used below by the PITCHED instantiations only, which that header's kernels make).
 __device__ __forceinline__ void crop_piece16(uint4 &v, const uint8_t *src, int y, int pitch, int x, int bpp, int phase);
+__device__ __forceinline__ void crop_piece16_binned(uint4 &v, const uint8_t *src, int y, int pitch, int x, int bpp, int phase, int bin);
 
 // One level of one pair out of LDS: search, records, refinement, votes, flow record.
 // `keys`: one packed key per block; `record_out`: LDS copy of the flow record (level 1: it carries the
@@ -195,13 +196,14 @@ __device__ __forceinline__ void run_level(const SearchArgs &a, const FlowTail &t
 // rows lie `pitch` bytes apart and may start on any byte; every other source is a contiguous, 16-byte aligned frame.
 // The camera tick fetches its new frame into buffer 1 (the default); a burst alternates the buffers.  bpp, phase: the
 // windows' pixel format (crop_piece16), looked at by the PACKED instantiations only (the kernels with a sensor argument):
-// 1, 0 is one grey byte per pixel, bpp 2 packed 16-bit pixels whose grey value is byte `phase`.
+// 1, 0 is one grey byte per pixel, bpp 2 packed 16-bit pixels whose grey value is byte `phase`; bin 2 or 4: a pixel of
+// the window is the rounded mean of bin x bin sensor pixels (crop_piece16_binned).
 // `search` false: only the fetch (passes A and B) -- the buffers named by `load` then hold their frame, its level-1
 // image and its sums for a later call that names them as the older frame (a stream's first frame inside a burst).
 template <bool SUBPIXEL, bool PITCHED = false, bool PACKED = false>
 __device__ __forceinline__ void flow_small_pair(const SmallArgs &a, uint32_t pair, const uint8_t *src0, const uint8_t *src1,
                                                 int cur_buf, uint32_t load, aof_flow *final_copy = nullptr, int pitch = 0,
-                                                uint32_t pitched = 2u, bool search = true, int bpp = 1, int phase = 0)
+                                                uint32_t pitched = 2u, bool search = true, int bpp = 1, int phase = 0, int bin = 1)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_mem[];
     __shared__ uint32_t s_keys[kThreads];
@@ -226,7 +228,27 @@ __device__ __forceinline__ void flow_small_pair(const SmallArgs &a, uint32_t pai
         uint32_t sum[2] = {0, 0};
         uint32_t rest = load;   // the buffers the loop of 16-byte pieces below fetches: all, but for windows of packed pixels
         if constexpr (PITCHED && PACKED) {
-            if (bpp != 1) {   // (uniform) two source bytes per pixel: the windows come first, in trips of half as many
+            if (bin != 1) {   // (uniform) binned windows come first as well: one piece per lane and trip -- a piece is bin
+                              // rows of up to eight loads, and its eight sums are all it keeps
+                const int row_chunks = w / 16;
+#pragma unroll
+                for (int buf = 0; buf < 2; buf++) {
+                    if (!(((load & pitched) >> buf) & 1u)) continue;
+                    const uint8_t *src = buf ? src1 : src0;
+#pragma unroll 1
+                    for (int c = tid; c < per_frame; c += kThreads) {
+                        const int y = c / row_chunks, x = c - y * row_chunks;
+                        uint4 v;
+                        crop_piece16_binned(v, src, y, pitch, x, bpp, phase, bin);
+                        uint32_t s = 0;
+                        s = byte_sum(v.x, s); s = byte_sum(v.y, s);
+                        s = byte_sum(v.z, s); s = byte_sum(v.w, s);
+                        sum[buf] += s;
+                        *reinterpret_cast<uint4 *>(f0[buf] + c * 16) = v;
+                    }
+                }
+                rest = load & ~pitched;
+            } else if (bpp != 1) {   // (uniform) two source bytes per pixel: the windows come first, in trips of half as many
                               // pieces -- as many 16-byte loads in flight as below, not twice the registers
                 constexpr int kHalf = kLoads / 2;
                 const int row_chunks = w / 16;

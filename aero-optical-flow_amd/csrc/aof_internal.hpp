@@ -333,22 +333,24 @@ struct BankArgs {
 // valid against; camera_base: bytes between the caller's d_camera and cam.camera (a burst's composed path: round k's
 // launches see cam.camera = d_camera + k * round_stride).  recs == nullptr: nothing bound.
 // formats: [S] the streams' pixel formats (aof_set_bank_pixel_formats), or nullptr: one grey byte per pixel.
+// bins: [S] the streams' binning (aof_set_bank_binning), or nullptr: 1 everywhere.
 struct BankSensors {
     const aof_bank_sensor *recs;
     uint64_t camera_bytes, camera_base;
     const uint8_t *formats;
+    const uint8_t *bins;
 };
 // One launch per tick: a workgroup per stream computes the pair with flow_small_pair, runs the stream's tail and
 // stores the new frame (sm: the small-pair plan of (bank frames, tick frames), flow_small_supported).  With
 // a.cam.camera the workgroup fetches the crop's rows from the stream's sensor frame itself (a.frames is not read).
-int launch_bank_tick(const SmallArgs &sm, const BankArgs &a, void *stream, const BankSensors &sen = BankSensors{nullptr, 0, 0, nullptr});
+int launch_bank_tick(const SmallArgs &sm, const BankArgs &a, void *stream, const BankSensors &sen = BankSensors{nullptr, 0, 0, nullptr, nullptr});
 // Behind aof_flow_batch_device on (bank frames, tick frames): the tail of every stream and the masked copy of the
 // active streams' frames into the bank.  With a.cam.camera: a.frames is the staging region, and the exposure gate,
 // the exposure record and the de-rotated pair come from here as well.
 // A burst's composed path runs it once per round: `a` carries the round's buffers, and stream s is active iff
 // round < count[s] (count NULL: a.active decides, as in a tick).
 int launch_bank_commit(const BankArgs &a, void *stream, const uint8_t *count = nullptr, int32_t round = 0,
-                       const BankSensors &sen = BankSensors{nullptr, 0, 0, nullptr});
+                       const BankSensors &sen = BankSensors{nullptr, 0, 0, nullptr, nullptr});
 // K frame rounds per stream (aof_bank_push_burst_device, k_bank_burst.hip).  Round k's frame of stream s sits
 // round_stride bytes behind round k - 1's; time_us, gyro, records, mavlink_len, mavlink, cam.exposure and
 // cam.derotated of a BankArgs are then dense [K][S] arrays, a.active is not read.
@@ -360,7 +362,7 @@ struct BankBurst {
 // One launch per burst: a workgroup per stream walks its rounds with one frame resident in LDS (same configuration
 // class and same `sm` as launch_bank_tick).
 int launch_bank_burst(const SmallArgs &sm, const BankArgs &a, const BankBurst &b, void *stream,
-                      const BankSensors &sen = BankSensors{nullptr, 0, 0, nullptr});
+                      const BankSensors &sen = BankSensors{nullptr, 0, 0, nullptr, nullptr});
 int launch_bank_reset(BankState *state, const uint8_t *mask, int32_t n_streams, void *stream);
 // The outbox of a push (aof_bank_collect_device, aof_outbox.cpp, k_bank_outbox.hip): compaction of the published records
 // and the due exposure records of n = K * S records into dense lists, and the tag behind them.
@@ -440,6 +442,9 @@ void set_bank_sensors(aof_ctx *ctx, const aof_bank_sensor *d_sensors, int32_t n_
 // (aof_batch.cpp) aof_set_bank_pixel_formats' binding: the array (nullptr: none) and its stream count
 const uint8_t *bank_pixel_formats(const aof_ctx *ctx, int32_t *n_streams);
 void set_bank_pixel_formats(aof_ctx *ctx, const uint8_t *d_formats, int32_t n_streams);
+// (aof_batch.cpp) aof_set_bank_binning's binding: the array (nullptr: none) and its stream count
+const uint8_t *bank_binning(const aof_ctx *ctx, int32_t *n_streams);
+void set_bank_binning(aof_ctx *ctx, const uint8_t *d_bins, int32_t n_streams);
 // (aof_capi.hip) sticky fault / wedged state and current-device check of a context, before anything is enqueued; and
 // aof_last_error's text for the callers outside aof_capi.hip
 int precheck(aof_ctx *ctx);
@@ -460,10 +465,11 @@ struct IngestSensors {
     uint64_t base, camera_bytes;
     uint8_t *ok;
     const uint8_t *formats;   // [n_frames] AOF_PIXEL_* of frame i, or nullptr: one grey byte per pixel
+    const uint8_t *bins;      // [n_frames] binning of frame i (1, 2, 4), or nullptr: 1
 };
 int launch_ingest(const aof_ingest_params &p, const uint8_t *camera, int64_t camera_stride,
                   int64_t n_frames, uint8_t *cropped, int64_t cropped_stride, uint32_t *hist,
-                  void *stream, const IngestSensors &sensors = IngestSensors{nullptr, 0, 0, nullptr, nullptr});
+                  void *stream, const IngestSensors &sensors = IngestSensors{nullptr, 0, 0, nullptr, nullptr, nullptr});
 // The sequence pipeline's ingest: the same pass also leaves every frame's level-1 image (l1: [n_frames] frames, or
 // nullptr) and adds its byte sums to the pixel-sum records of the pairs it belongs to (sums: [n_frames - 1][2][2],
 // zeroed here; or nullptr) -- what K1 would otherwise compute in a second pass over the cropped frames.

@@ -109,15 +109,18 @@ __global__ __launch_bounds__(kThreads) void k_ingest(aof_ingest_params p, const 
 
     const uint8_t *src = camera + frame * camera_stride + (int64_t)y0 * p.camera_width + x0;
     int pitch = p.camera_width, bpp = 1, phase = 0;   // (the pixel format: the record's, with a format array; else grey)
+    int bin = 1;                                      // (the binning: the record's, with a binning array)
     if constexpr (sizeof...(Sen) > 0) {   // (uniform, as is the record: one frame per workgroup)
         static_assert(!PYRAMID, "the sequence pipeline has no records");
         const IngestSensors &sen = (sensors, ...);
-        const BankSensor r = bank_sensor(sen.recs, (size_t)frame, p.crop_width, p.crop_height, sen.base, sen.camera_bytes, sen.formats);
+        const BankSensor r = bank_sensor(sen.recs, (size_t)frame, p.crop_width, p.crop_height, sen.base, sen.camera_bytes, sen.formats,
+                                          sen.bins);
         if (sen.ok && strip == 0 && tid == 0) sen.ok[frame] = r.ok ? 1 : 0;
         if (!r.ok) return;
         src = camera + r.origin;
         pitch = r.pitch;
         bpp = r.bpp; phase = r.phase;
+        bin = r.bin;
     }
     uint8_t *dst = cropped ? cropped + frame * cropped_stride : nullptr;
     const int row_begin = strip * kRowsPerBlock, row_end = min(p.crop_height, row_begin + kRowsPerBlock);
@@ -129,6 +132,39 @@ __global__ __launch_bounds__(kThreads) void k_ingest(aof_ingest_params p, const 
         constexpr int kUnroll = 4;
         int round = 0;
         for (int base = 0; base < items; base += kUnroll * kThreads) {  // uniform trip count
+            if constexpr (sizeof...(Sen) > 0) {
+                if (bin != 1) {   // (uniform, decided per trip: binned pixels) the trip's pieces one behind the other, each used
+                                  // before the next is fetched: a piece is bin rows of loads and eight sums of its own, and with
+                                  // four of them in flight the kernel took 112 registers and ran half its waves for EVERY frame,
+                                  // binned or not (LAB_LOG.md, "Stream bank binned sensor pixels")
+                    // (what the loop at the end of a trip does with a piece, for one piece)
+                    auto consume = [&](const uint4 &val, int y, int x, bool active) __attribute__((always_inline)) {
+                        if (active && dst) *reinterpret_cast<uint4 *>(dst + (int64_t)y * p.crop_width + x) = val;
+                        if (active && hist && y >= my0 && y < my1 && x + 16 > mx0 && x < mx1) {
+                            const uint32_t w[4] = {val.x, val.y, val.z, val.w};
+#pragma unroll
+                            for (int k = 0; k < 16; k++) {
+                                if (x + k < mx0 || x + k >= mx1) continue;
+                                const uint2 e = s_onehot[(w[k >> 2] >> (8 * (k & 3))) & 0xFFu];
+                                sum_lo += e.x; sum_hi += e.y;
+                            }
+                        }
+                        if (hist && round % kLanePieces == kLanePieces - 1) { widen_add(cnt, sum_lo, sum_hi); sum_lo = sum_hi = 0; }
+                        if (hist && round % kWavePieces == kWavePieces - 1) flush_counts(s_hist, cnt);
+                        round++;
+                    };
+#pragma unroll 1
+                    for (int u = 0; u < kUnroll; u++) {
+                        const int it = base + u * kThreads + tid;
+                        const bool active = it < items;
+                        const int y = row_begin + (active ? it / pieces : 0), x = active ? (it % pieces) * 16 : 0;
+                        uint4 val = make_uint4(0, 0, 0, 0);
+                        if (active) crop_piece16_binned(val, src, y, pitch, x / 16, bpp, phase, bin);
+                        consume(val, y, x, active);
+                    }
+                    continue;
+                }
+            }
             uint4 v[kUnroll];
             int ys[kUnroll], xs[kUnroll];
             bool act[kUnroll];
@@ -218,7 +254,15 @@ __global__ __launch_bounds__(kThreads) void k_ingest(aof_ingest_params p, const 
         const int items = (row_end - row_begin) * p.crop_width;
         for (int it = tid; it < items; it += kThreads) {
             const int y = row_begin + it / p.crop_width, x = it % p.crop_width;
-            const uint32_t v = src[(int64_t)y * pitch + x * bpp];   // (src: the grey byte of the crop's first pixel)
+            uint32_t v = src[(int64_t)y * bin * pitch + x * bin * bpp];   // (src: the grey byte of the crop's first pixel)
+            if constexpr (sizeof...(Sen) > 0) {
+                if (bin != 1) {   // (uniform) the pixel's bin x bin sensor pixels, rounded once
+                    v = 0;
+                    for (int j = 0; j < bin; j++)
+                        for (int i = 0; i < bin; i++) v += src[(int64_t)(y * bin + j) * pitch + (x * bin + i) * bpp];
+                    v = (v + bin * bin / 2) >> (bin == 2 ? 2 : 4);
+                }
+            }
             if (dst) dst[(int64_t)y * p.crop_width + x] = (uint8_t)v;
             if (hist && y >= my0 && y < my1 && x >= mx0 && x < mx1) {
                 const int b = exposure_bin(v);

@@ -99,6 +99,15 @@ public:
 	// above 2, a record that no longer fits, a call before enabling.  An object on which neither call was made runs exactly
 	// as before.
 	int setStreamPixelFormat(int stream, int format);
+	// One stream's binning (include/aof.h, "binned sensor pixels"; bin: 1, 2 or 4), after either enable call, from the next
+	// pushCamera() on: a pixel of the stream's image is the rounded mean of bin x bin sensor pixels, and the crop's
+	// footprint is bin * image size at the record's (x0, y0).  The stream keeps its layout, record and format; the record is
+	// checked again, with the new bin, against the bytes pushCamera() takes, and setStreamSensor() and
+	// setStreamPixelFormat() check with the stream's current bin.  A binned pixel subtends bin sensor pixels: the caller
+	// sets focal / bin with setStreamFocalLength().  Returns 0, or -EINVAL, the object unchanged: a bad stream index, a
+	// bin that is none of 1, 2, 4, a footprint that no longer fits, a call before enabling.  An object on which it was never
+	// called binds nothing.
+	int setStreamBinning(int stream, int bin);
 	// The last pushCamera()'s aof_exposure_command [n_streams] in pinned memory (flags 0: the stream's frame
 	// was not due); valid until the next push.  NULL without enableCamera().
 	const aof_exposure_command *exposureCommands() const;

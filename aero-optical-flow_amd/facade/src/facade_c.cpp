@@ -106,6 +106,10 @@ int aof_facade_bank_set_stream_pixel_format(void *bank, int stream, int format)
 {
 	return static_cast<OpticalFlowBank *>(bank)->setStreamPixelFormat(stream, format);
 }
+int aof_facade_bank_set_stream_binning(void *bank, int stream, int bin)
+{
+	return static_cast<OpticalFlowBank *>(bank)->setStreamBinning(stream, bin);
+}
 int aof_facade_bank_enable_camera_packed(void *bank, int camera_width, int camera_height, int format, int exposure0, int gain0,
 					 uint32_t exposure_interval_us)
 {

@@ -31,7 +31,7 @@ double secondsSince(std::chrono::steady_clock::time_point t0)
 // Every allocation of one object, recorded where it is made: release() frees them all, the newest first.
 struct Allocations {
 	enum Kind { kDevice, kPinned, kOutbox };   // hipMalloc, hipHostMalloc, aof_outbox_alloc_host: each has its own free
-	struct { void *p; Kind kind; } list[26];   // (24 with every form on, 25 inside enableCamera())
+	struct { void *p; Kind kind; } list[28];   // (26 with every form on, 27 inside enableCamera())
 	int n;
 
 	bool get(void **p, size_t bytes, Kind kind)
@@ -137,6 +137,9 @@ struct OpticalFlowBank::Impl {
 	// travel with the sensor records (formats_used implies sensors_used)
 	Staged formats;
 	bool formats_used, formats_dirty, formats_bound, formats_copying;
+	// and the binning (setStreamBinning()): u8 [n_streams], ones until a call; the same scheme, beside the records
+	Staged bins;
+	bool bins_used, bins_dirty, bins_bound, bins_copying;
 
 	int fail(int code, const char *what) { return self->fail(code, what); }
 	int failed(int rc) { return rc ? fail(rc, aof_last_error(ctx)) : 0; }   // of a call of the C ABI
@@ -349,8 +352,8 @@ int OpticalFlowBank::setStreamSensor(int s, uint64_t offset, int pitch, int widt
 	rec.x0 = x0;
 	rec.y0 = y0;
 	// the kernels' own rule, against the staging buffer pushCamera() fills: here the host can see the record
-	// (with the stream's current pixel format)
-	if (aof_bank_sensor_valid_format(&rec, m->formats.h[s], image_width, image_height, 0, m->sensor.bytes) != 1)
+	// (with the stream's current pixel format and binning)
+	if (aof_bank_sensor_valid_binned(&rec, m->formats.h[s], m->bins.h[s], image_width, image_height, 0, m->sensor.bytes) != 1)
 		return refuse(-EINVAL, "setStreamSensor(): the record does not describe memory inside the staging buffer");
 	reinterpret_cast<aof_bank_sensor *>(m->sensors.h)[s] = rec;
 	m->sensors_used = true;
@@ -365,12 +368,28 @@ int OpticalFlowBank::setStreamPixelFormat(int s, int format)
 	if (format < AOF_PIXEL_GREY8 || format > AOF_PIXEL_LUMA16_HI)
 		return refuse(-EINVAL, "setStreamPixelFormat(): no such format");
 	// the stream's current record, by the kernels' own rule, with the new format
-	if (aof_bank_sensor_valid_format(reinterpret_cast<aof_bank_sensor *>(m->sensors.h) + s, (uint8_t)format, image_width, image_height, 0,
-					 m->sensor.bytes) != 1)
+	if (aof_bank_sensor_valid_binned(reinterpret_cast<aof_bank_sensor *>(m->sensors.h) + s, (uint8_t)format, m->bins.h[s], image_width,
+					 image_height, 0, m->sensor.bytes) != 1)
 		return refuse(-EINVAL, "setStreamPixelFormat(): the stream's record no longer lies inside the staging buffer");
 	m->formats.h[s] = (uint8_t)format;
 	m->formats_used = m->formats_dirty = true;
 	m->sensors_used = true;   // (formats are bound next to the records only)
+	if (!m->sensors_bound) m->sensors_dirty = true;
+	return 0;
+}
+
+int OpticalFlowBank::setStreamBinning(int s, int bin)
+{
+	Impl *m = _m;
+	if (!m || !m->camera || !m->sensors.h || !m->formats.h || !m->bins.h || s < 0 || s >= n_streams) return -EINVAL;
+	if (bin != 1 && bin != 2 && bin != 4) return refuse(-EINVAL, "setStreamBinning(): the bin is 1, 2 or 4");
+	// the stream's current record and format, by the kernels' own rule, with the new footprint
+	if (aof_bank_sensor_valid_binned(reinterpret_cast<aof_bank_sensor *>(m->sensors.h) + s, m->formats.h[s], (uint8_t)bin, image_width,
+					 image_height, 0, m->sensor.bytes) != 1)
+		return refuse(-EINVAL, "setStreamBinning(): the binned crop no longer lies inside the stream's sensor frame");
+	m->bins.h[s] = (uint8_t)bin;
+	m->bins_used = m->bins_dirty = true;
+	m->sensors_used = true;   // (the binning is bound next to the records only)
 	if (!m->sensors_bound) m->sensors_dirty = true;
 	return 0;
 }
@@ -487,6 +506,16 @@ int OpticalFlowBank::Impl::syncStreams()
 			formats_bound = true;
 		}
 	}
+	if (bins_used) {
+		if (bins_dirty) {
+			if (!bins.upload(stream, 0, bins.bytes)) return fail(-EIO, "copy of the per-stream binning failed");
+			bins_copying = true;
+		}
+		if (!bins_bound) {
+			if (failed(aof_set_bank_binning(ctx, bins.d, (int)S))) return -EIO;
+			bins_bound = true;
+		}
+	}
 	if (!streams_used) return 0;
 	if (streams_dirty) {
 		if (!streams.upload(stream, 0, streams.bytes)) return fail(-EIO, "copy of the per-stream records failed");
@@ -534,6 +563,10 @@ int OpticalFlowBank::Impl::collect()
 	if (formats_copying) {
 		formats_copying = false;
 		formats_dirty = false;
+	}
+	if (bins_copying) {
+		bins_copying = false;
+		bins_dirty = false;
 	}
 	if (imu) std::memset(imuCounts(), 0, S);                      // the tick took the queued samples
 	if (rx) std::memset(rxLengths(), 0, S * sizeof(uint16_t));    // and the queued bytes
@@ -593,6 +626,7 @@ int OpticalFlowBank::Impl::enableSensorFrames(int camera_width, int camera_heigh
 	    !m->sensor.alloc(m->mem, S * (size_t)camera_width * (size_t)camera_height * bpp) ||
 	    !m->sensors.alloc(m->mem, S * sizeof(aof_bank_sensor)) ||
 	    !m->formats.alloc(m->mem, alignUp(S, 16)) ||
+	    !m->bins.alloc(m->mem, alignUp(S, 16)) ||
 	    !m->mem.get((void **)&m->d_exposure, S * sizeof(aof_exposure_record), Allocations::kDevice) ||
 	    !m->mem.get((void **)&m->d_exposure_state, S * sizeof(aof_exposure_state), Allocations::kDevice) ||
 	    !m->mem.get((void **)&m->commands, S * sizeof(aof_exposure_command), Allocations::kOutbox))
@@ -610,6 +644,7 @@ int OpticalFlowBank::Impl::enableSensorFrames(int camera_width, int camera_heigh
 		rec->pitch *= (int32_t)bpp;
 		m->formats.h[s] = (uint8_t)format;
 	}
+	std::memset(m->bins.h, 1, m->bins.bytes);
 	if (format != AOF_PIXEL_GREY8) {
 		m->sensors_used = m->sensors_dirty = true;
 		m->formats_used = m->formats_dirty = true;

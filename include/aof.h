@@ -722,6 +722,56 @@ int aof_ingest_sensor_formats_device(int32_t crop_width, int32_t crop_height, co
                                      const aof_bank_sensor *d_sensors, const uint8_t *d_formats, int64_t n_frames,
                                      uint8_t *d_cropped, int64_t cropped_stride, uint32_t *d_hist, uint8_t *d_ok, void *stream);
 
+/* ---- the stream bank with binned sensor pixels: 2x2 and 4x4 binning per stream, inside the crop ----
+ * An 8x8 / +-4 search measures at most +-4 pixels per frame pair (+-9 on two levels).  A faster vehicle or a wider lens
+ * bins its sensor, as the published PX4Flow pipeline does (4x, in front of its 64x64 window).  A caller may bind, next
+ * to the sensor records and the formats, an array of S bins in device memory: b = d_bins[s] is 1, 2 or 4
+ * (AOF_BANK_BIN_MAX); any other value makes the stream's record invalid.  With g(X, Y) the grey byte of sensor pixel
+ * (X, Y) -- the byte at d_camera + k*round_stride + offset + Y*pitch + X*bpp + phase, as above -- pixel (x, y) of the
+ * crop is
+ *     (sum over j < b, i < b of g(x0 + b*x + i, y0 + b*y + j) + b*b/2) >> (2*log2 b).
+ * b = 2 is the pyramid's box (a+b+c+d+2)>>2; b = 4 is ONE rounding of the sixteen-pixel sum, (sum + 8) >> 4, not the
+ * box applied twice (quadrant sums 2, 2, 2, 1 give 0 here, 1 there); b = 1 is the crop as it was.
+ * Units: width, height, x0, y0 stay in SENSOR pixels, pitch and offset in bytes; the context's width x height is the
+ * size of the BINNED crop, whose footprint is b*width x b*height sensor pixels at (x0, y0).
+ * A record with its format and bin is valid iff, in 64 bits so that nothing wraps,
+ *     b in {1, 2, 4};  x0 >= 0, y0 >= 0, x0 + b*crop_width <= width, y0 + b*crop_height <= height;
+ * and everything else as above (pitch >= width*bpp, the extent against camera_bytes).  An invalid record or bin is
+ * treated as an invalid record is: AOF_TICK_BAD_SENSOR for that round, not one byte of the stream's frame read.
+ * Contract (a bank of one): stream s's records, wire frames, exposure records (histogram and MSV: those of the binned
+ * crop), de-rotated pairs, stored frame and state, exposure gate included, equal byte for byte those of a grey stream
+ * (AOF_PIXEL_GREY8, bin 1) whose sensor frame is the binned crop computed on the host.  The exposure mask depends on
+ * the crop size only.  An array of all ones changes no byte against sensors (and formats) bound alone; with nothing
+ * bound every kernel runs as before.
+ * Binding: used by the two camera pushes, with sensor records bound -- a binning bound without records, or a bound
+ * count that differs from bp->n_streams, makes those pushes return -EINVAL before anything is enqueued.  It combines
+ * with every format, bound or not.  The KERNELS read the array when they run: values may be rewritten between ticks, a
+ * captured graph replays against the current contents, a burst indexes the array by the stream alone.
+ * The focal length is the caller's: a binned pixel subtends b sensor pixels, so a caller binds focal / b through
+ * aof_bank_stream (aof_set_bank_streams).  The library does not scale it. */
+#define AOF_BANK_BIN_MAX 4
+/* Stores the pointer on the context, like aof_set_bank_pixel_formats: enqueues nothing, allocates nothing, reads
+ * nothing.  d_bins: u8 [n_streams] in device memory owned by the caller, alive for as long as it is bound; any
+ * alignment; the kernels read nothing outside d_bins[0..n_streams).  NULL (with n_streams 0) unbinds.
+ * -EINVAL: NULL ctx, a non-NULL array with n_streams < 1 (the binding stays as it was). */
+int aof_set_bank_binning(aof_ctx *ctx, const uint8_t *d_bins, int32_t n_streams);
+/* Host only: aof_bank_sensor_valid_format for a record binned `bin` times (the same function the kernels decide with,
+ * compiled for the host): 1 valid, 0 not (a bin that is none of 1, 2, 4 included).  -EINVAL: NULL rec. */
+int aof_bank_sensor_valid_binned(const aof_bank_sensor *rec, uint8_t format, uint8_t bin, int32_t crop_width, int32_t crop_height,
+                                 uint64_t base, uint64_t camera_bytes);
+/* Host only: aof_bank_sensor_centred for a binned stream: x0 = width/2 - (bin*p->width)/2, y0 likewise.
+ * -EINVAL: NULL p / out, and wherever the record would be invalid (a format above 2, a bin that is none of 1, 2, 4,
+ * pitch < width*bpp, a footprint that is not inside width x height); *out is then not written. */
+int aof_bank_sensor_centred_binned(const aof_params *p, uint64_t offset, int32_t pitch, int32_t width, int32_t height,
+                                   uint8_t format, uint8_t bin, aof_bank_sensor *out);
+/* aof_ingest_sensor_formats_device with frame i binned d_bins[i] times (u8 [n_frames], device memory, any alignment);
+ * d_bins NULL: 1 everywhere -- aof_ingest_sensor_formats_device is this call with NULL.  crop_width x crop_height is
+ * the size of the binned crop.  A frame whose record, format or bin is not valid is not read (d_ok 0).  -EINVAL as there. */
+int aof_ingest_sensors_binned_device(int32_t crop_width, int32_t crop_height, const uint8_t *d_camera, uint64_t camera_bytes,
+                                     const aof_bank_sensor *d_sensors, const uint8_t *d_formats, const uint8_t *d_bins,
+                                     int64_t n_frames, uint8_t *d_cropped, int64_t cropped_stride, uint32_t *d_hist, uint8_t *d_ok,
+                                     void *stream);
+
 /* ---- the stream bank's outbox: the published messages of a push as one dense, ordered, host-pollable list ----
  * A push leaves [K][S] records of which most say "nothing to do": the limiter publishes at 15 Hz from 75 Hz cameras, the
  * exposure gate opens at 5 Hz, idle streams get AOF_TICK_IDLE.  aof_bank_collect_device, enqueued behind any of the four

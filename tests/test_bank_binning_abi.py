@@ -1,0 +1,139 @@
+"""The host-only side of the binning (include/aof.h, "the stream bank with binned sensor pixels"): the entry points exist in
+header, library and binding, the macro has the header's value, aof_bank_sensor_valid_binned decides as the rule in Python
+integers (tests/bank_binning_ref.py) at the edges it is held at, aof_bank_sensor_centred_binned centres the footprint, and the
+calls refuse what they can refuse without a device.  The rule itself runs under UBSan and ASan in a stand-alone program
+with its own main against a 128-bit restatement (tests/native/bank_binning_rule_selftest.cpp); nothing sanitised is loaded
+into Python.  (A binning bound without sensors and a count mismatch need a context: tests/test_gpu_bank_binning.py.)"""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import bank_binning_ref as bref
+import bank_pixels_ref as pref
+import bank_sensors_ref as sref
+
+EINVAL = -22
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CXX = os.environ.get("CXX", "c++")
+NAMES = ("aof_set_bank_binning", "aof_bank_sensor_valid_binned", "aof_bank_sensor_centred_binned", "aof_ingest_sensors_binned_device")
+BIN_BYTES = (0, 1, 2, 3, 4, 8, 255)
+
+
+def test_library_header_and_binding_have_the_entry_points_and_the_macro(aof):
+    text = open(os.path.join(ROOT, "include", "aof.h")).read()
+    for name in NAMES:
+        assert re.search(r"\bint " + name + r"\(", text), name
+        assert name in aof.EXPORTS and getattr(aof.lib, name).restype is C.c_int
+    assert re.search(r"#define AOF_BANK_BIN_MAX\s+4\b", text) and aof.BANK_BIN_MAX == 4 == bref.BIN_MAX
+    assert callable(aof.FlowEngine.set_bank_binning) and callable(aof.OpticalFlowBank.setStreamBinning)
+    facade = open(os.path.join(ROOT, "aero-optical-flow_amd", "facade", "include", "flow_bank.hpp")).read()
+    assert "int setStreamBinning(" in facade
+    assert aof.BANK_SENSOR_DTYPE.itemsize == 32, "the record keeps its 32 bytes: the bins are a parallel array"
+    assert aof.lib.aof_version() == 102
+
+
+def agree(aof, rec, fmt, b, w, h, nbytes, base=0):
+    want = bref.valid(rec, fmt, b, w, h, nbytes, base)
+    got = aof.bank_sensor_valid(rec, w, h, nbytes, base, format=fmt, bin=b)
+    assert got == want, (rec, fmt, b, w, h, nbytes, base, got, want)
+    if b == 1:
+        assert got == aof.bank_sensor_valid(rec, w, h, nbytes, base, format=fmt), "bin 1 decides as the call without a bin"
+    return want
+
+
+@pytest.mark.parametrize("fmt", pref.FORMATS)
+def test_valid_binned_is_the_rule_for_every_layout_and_bin_byte(aof, fmt):
+    w = h = 64
+    bpp = pref.bpp_of(fmt)
+    for b in BIN_BYTES:
+        foot = max(b, 1) * w
+        rec = sref.record(48, (foot + 9) * bpp + 1, foot + 9, max(b, 1) * h + 5, 9, 5)
+        n = 48 + sref.extent(rec, fmt)
+        assert agree(aof, rec, fmt, b, w, h, n) == (b in bref.BINS)
+        # the footprint fits exactly; one sensor pixel over on each axis
+        for name, over in (("x0", 10), ("y0", 6)):
+            edge = rec.copy()
+            edge[name] = over
+            assert not agree(aof, edge, fmt, b, w, h, n), (b, name)
+        # the extent equal to camera_bytes, and one byte short; the same with a base
+        assert not agree(aof, rec, fmt, b, w, h, n - 1)
+        assert agree(aof, rec, fmt, b, w, h, n + 4096, base=4096) == (b in bref.BINS) and not agree(aof, rec, fmt, b, w, h, n + 4095, base=4096)
+    # a larger bin than the sensor was laid out for does not fit; a smaller one does
+    rec = sref.record(0, 137 * bpp, 137, 133, 9, 5)
+    n = sref.extent(rec, fmt)
+    assert agree(aof, rec, fmt, 1, w, h, n) and agree(aof, rec, fmt, 2, w, h, n) and not agree(aof, rec, fmt, 4, w, h, n)
+
+
+def test_valid_binned_around_two_to_the_31(aof):
+    top = 2 ** 31 - 1
+    for b in bref.BINS:
+        w = (top - 7) // b
+        for width, x0, crop_w in ((top, top - b * w, w), (top, top - b * w + 1, w), (top, 7, w + 1), (top, 0, top), (top - 1, 0, (top - 1) // b + 1)):
+            rec = sref.record(0, top, width, 64 * b, x0, 0)
+            got = agree(aof, rec, 0, b, crop_w, 64, 2 ** 63)
+            assert got == (x0 + b * crop_w <= width), (b, width, x0, crop_w)
+        rec = sref.record(0, 64 * b, 64 * b, top, 0, top - b * w)
+        assert agree(aof, rec, 0, b, 64, w, 2 ** 63) and not agree(aof, rec, 0, b, 64, w + 1, 2 ** 63)
+
+
+def test_centred_binned(aof):
+    p = aof.px4flow_params(64, 64)
+    for fmt in pref.FORMATS:
+        bpp = pref.bpp_of(fmt)
+        for b in bref.BINS:
+            rec = aof.bank_sensor_centred(p, 4096, 331 * bpp + 3, 331, 267, format=fmt, bin=b)
+            assert (int(rec["x0"]), int(rec["y0"])) == (331 // 2 - (b * 64) // 2, 267 // 2 - (b * 64) // 2)
+            assert (int(rec["offset"]), int(rec["pitch"]), int(rec["width"]), int(rec["height"])) == (4096, 331 * bpp + 3, 331, 267)
+            assert bref.valid(rec, fmt, b, 64, 64, 4096 + sref.extent(rec, fmt))
+            if b == 1 and fmt == 0:
+                assert rec.tobytes() == aof.bank_sensor_centred(p, 4096, 334, 331, 267).tobytes()
+            exact = aof.bank_sensor_centred(p, 0, b * 64 * bpp, b * 64, b * 64, format=fmt, bin=b)     # the footprint is the sensor
+            assert (int(exact["x0"]), int(exact["y0"])) == (0, 0)
+    out = aof.BankSensor()
+    fn = aof.lib.aof_bank_sensor_centred_binned
+    bad = [(0, 127, 127, 255, 0, 2), (0, 320, 320, 255, 0, 4), (0, 320, 320, 240, 0, 3), (0, 320, 320, 240, 0, 0), (0, 320, 320, 240, 3, 1),
+           (0, 639, 320, 240, 1, 1), (0, 320, 320, 240, 0, 8), (0, 320, 320, 240, 0, 255)]
+    for args in bad:
+        C.memset(C.byref(out), 0xEE, C.sizeof(out))
+        assert fn(C.byref(p), *args, C.byref(out)) == EINVAL, args
+        assert bytes(out) == b"\xee" * 32, "a refused call writes nothing"
+    assert fn(None, 0, 320, 320, 240, 0, 1, C.byref(out)) == EINVAL and fn(C.byref(p), 0, 320, 320, 240, 0, 1, None) == EINVAL
+    assert aof.lib.aof_bank_sensor_valid_binned(None, 0, 1, 64, 64, 0, 1 << 20) == EINVAL
+
+
+def test_calls_refuse_what_they_can_without_a_device(aof):
+    buf = np.full(1 << 14, 0xEE, np.uint8)
+    d = buf.ctypes.data
+    base = d + (-d) % 16
+    setter, ingest = aof.lib.aof_set_bank_binning, aof.lib.aof_ingest_sensors_binned_device
+    for args in ((d, 4), (None, 0), (d + 1, 4), (d, 0), (d, -1)):
+        assert setter(None, *args) == EINVAL
+    ok = (64, 64, d, 1 << 14, base, d, d, 2, d, 4096, d, d, None)
+    bad = [{0: 0}, {1: 0}, {2: None}, {3: 0}, {4: None}, {4: base + 8}, {7: -1}, {8: None, 10: None}, {9: 4095}]
+    for change in bad:
+        for bins in (d, d + 3, None):             # (any alignment, or all ones: the refusals do not depend on it)
+            args = list(ok)
+            args[6] = bins
+            for i, v in change.items():
+                args[i] = v
+            assert ingest(*args) == EINVAL, change
+    args = list(ok)
+    args[7] = 0
+    assert ingest(*args) == 0, "no frames: nothing to do, nothing launched"
+    assert (buf == 0xEE).all(), "a refused call writes nothing"
+
+
+def test_the_rule_with_a_bin_neither_wraps_nor_overflows(tmp_path):
+    csrc = os.path.join(ROOT, "aero-optical-flow_amd", "csrc")
+    exe = tmp_path / "bank_binning_rule_selftest"
+    cmd = [CXX, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+           "-I" + os.path.join(ROOT, "include"), "-I" + csrc, os.path.join(ROOT, "tests", "native", "bank_binning_rule_selftest.cpp"),
+           "-o", str(exe)]
+    subprocess.run(cmd, check=True, timeout=300)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, f"rc={r.returncode}\n{r.stdout}{r.stderr}"
+    assert "agree" in r.stdout

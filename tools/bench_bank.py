@@ -58,6 +58,15 @@ With --pixel-formats, the camera tick with packed 16-bit sensor pixels (aof_set_
     M   formats mixed per stream (s % 3): every stream in a slot of 2 cam_w cam_h bytes;
     D   what a caller does without the call: a device de-interleave of the whole packed buffer (one strided copy kernel,
         2 + 1 bytes moved per sensor pixel) into a grey buffer, then leg G on that.
+With --binning, the camera tick with binned sensor pixels (aof_set_bank_binning), on both bank paths (leg names end in the
+path, 1 or 2).  A binned stream's sensor is bin * (crop + 16) pixels a side with the footprint at its centre, every crop
+pixel of the synthetic frame repeated bin x bin times, so every leg searches the same frames:
+    G   sensors and formats (all grey) bound, no bins (with AOF_LIB, on a build without the call: the yardstick of B0);
+    B0  bins bound, all ones: the same frames, the same bytes;
+    B2 / B4   every stream binned 2x / 4x, grey sensors;
+    Y4  AOF_PIXEL_LUMA16_LO sensors binned 4x;
+    D2 / D4   what a caller does without the call: aof_ingest_sensors_binned_device of the B2 / B4 sensors into a dense
+        grey buffer, then the camera tick on that buffer (sensors and formats bound, as G).
 K1 / K2 are the legs --camera runs under those names (leg_camera); --per-sensor --legs K1,K2 runs them alone, which is how
 two builds of the library are compared in turn in one session.
 Every leg settles for about 0.2 s of untimed ticks, then times at least --ticks ticks and at least --seconds seconds
@@ -71,7 +80,8 @@ between the repeats is the run-to-run spread a difference between legs has to be
     python tools/bench_bank.py --imu > profiles/bank_imu_sweep.txt
     python tools/bench_bank.py --mavlink-rx > profiles/bank_mavlink_rx_sweep.txt
     python tools/bench_bank.py --per-stream --streams 64,1024 > profiles/bank_per_stream_ab.txt
-    python tools/bench_bank.py --per-sensor --streams 64,1024 > profiles/bank_per_sensor_ab.txt"""
+    python tools/bench_bank.py --per-sensor --streams 64,1024 > profiles/bank_per_sensor_ab.txt
+    python tools/bench_bank.py --binning --repeats 3 > profiles/bank_binning_ab.txt"""
 import argparse
 import ctypes as C
 import importlib
@@ -330,6 +340,117 @@ def pixel_formats_sweep(a, dev):
                 if all(k + str(path) in m for k in ("G", "P0", "Y", "M", "D")):
                     g, q, y, mm, d = (m[k + str(path)] for k in ("G", "P0", "Y", "M", "D"))
                     line += f"  P0{path}/G{path} {q / g:5.3f}  Y{path}/D{path} {y / d:5.3f}  M{path}/D{path} {mm / d:5.3f}"
+            print(line)
+
+
+BIN_RING = 4      # resident ticks of the --binning legs (a 4x binned 128 x 128 stream reads 576 x 576 sensor pixels)
+
+
+def leg_binning(p, S, path, inp, dev, a, leg):
+    """One of G / B0 / B2 / B4 / Y4 / D2 / D4 of --binning on `path` (see the module's text)."""
+    eng = aof.FlowEngine(p, 0)
+    eng.set_bank_path(path)
+    w, h = p.width, p.height
+    b = {"G": 1, "B0": 1, "B2": 2, "B4": 4, "Y4": 4, "D2": 2, "D4": 4}[leg]
+    bpp = 2 if leg == "Y4" else 1
+    two_calls = leg in ("D2", "D4")
+    cam_w, cam_h = b * (w + 16), b * (h + 16)
+    slot = cam_w * cam_h * bpp
+    bp = aof.bank_params(S, FX, FY, 15, 5_000_000, 1, 100, 0)
+    cam = aof.bank_camera_params(w + 16, h + 16, w, h, 0, 200_000, DEROTATE, FX, FY)
+    bank = eng.bank_create(bp, dev, camera=cam)
+    x0, y0 = cam_w // 2 - b * w // 2, cam_h // 2 - b * h // 2
+    cams = []
+    for k in range(BIN_RING):
+        buf = torch.randint(0, 256, (S, cam_h, cam_w, bpp), dtype=torch.uint8, device=dev)
+        buf[:, y0:y0 + b * h, x0:x0 + b * w, 0] = inp.frames[k].repeat_interleave(b, 1).repeat_interleave(b, 2)
+        cams.append(buf)
+    table = np.zeros(S, aof.BANK_SENSOR_DTYPE)
+    table["offset"] = np.arange(S, dtype=np.uint64) * np.uint64(slot)
+    table["pitch"], table["width"], table["height"], table["x0"], table["y0"] = cam_w * bpp, cam_w, cam_h, x0, y0
+    d_table = torch.from_numpy(table.view(np.uint8).reshape(S, 32)).to(dev)
+    d_fmts = torch.full((S,), bpp - 1, dtype=torch.uint8, device=dev)
+    d_bins = torch.full((S,), b, dtype=torch.uint8, device=dev)
+    grey = None
+    if two_calls:      # the tick runs on the dense crops: records of w x h frames, the crop the frame
+        grey = torch.empty((S, h, w), dtype=torch.uint8, device=dev)
+        dense = np.zeros(S, aof.BANK_SENSOR_DTYPE)
+        dense["offset"] = np.arange(S, dtype=np.uint64) * np.uint64(w * h)
+        dense["pitch"], dense["width"], dense["height"] = w, w, h
+        d_dense = torch.from_numpy(dense.view(np.uint8).reshape(S, 32)).to(dev)
+        eng.set_bank_sensors(d_dense, S, S * w * h)
+        d_grey = torch.zeros(S, dtype=torch.uint8, device=dev)
+        eng.set_bank_pixel_formats(d_grey, S)
+    else:
+        eng.set_bank_sensors(d_table, S, S * slot)
+        eng.set_bank_pixel_formats(d_fmts, S)
+        if leg != "G":
+            eng.set_bank_binning(d_bins, S)
+    recs = torch.empty((S, 48), dtype=torch.uint8, device=dev)
+    expo = torch.empty((S, 48), dtype=torch.uint8, device=dev)
+    derot = torch.empty((S, 2), dtype=torch.float32, device=dev)
+    wire = torch.empty((S, 56), dtype=torch.uint8, device=dev)
+    lens = torch.empty(S, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    fn, ctx, bpp_, cp = aof.lib.aof_bank_push_camera_device, eng._ctx, C.byref(bp), C.byref(cam)
+    times = torch.zeros(S, dtype=torch.int64, device=dev)
+    rest = (times.data_ptr(), None, inp.gyro.data_ptr(), bank.buffer.data_ptr(), bank.buffer.numel(), recs.data_ptr(), expo.data_ptr(),
+            derot.data_ptr(), wire.data_ptr(), lens.data_ptr(), stream)
+    ptrs = [c.data_ptr() for c in cams]
+    ingest = aof.lib.aof_ingest_sensors_binned_device if two_calls else None
+
+    def step(i):
+        times.add_(13333)
+        if two_calls:
+            rc = ingest(w, h, ptrs[i % BIN_RING], S * slot, d_table.data_ptr(), d_fmts.data_ptr(), d_bins.data_ptr(), S, grey.data_ptr(),
+                        w * h, None, None, stream)
+            rc = rc or fn(ctx, bpp_, cp, grey.data_ptr(), *rest)
+        else:
+            rc = fn(ctx, bpp_, cp, ptrs[i % BIN_RING], *rest)
+        if rc:
+            raise aof.AofError(rc, aof.lib.aof_last_error(ctx).decode())
+    out = timed(step, torch.cuda.synchronize, a.ticks, a.seconds, a.settle)
+    r = aof.ticks_view(recs)
+    assert (r["quality"] >= aof.TICK_HELD).all() and (r["frame"] > a.ticks).all(), "the timed ticks were real ticks"
+    eng.close()
+    return out
+
+
+def binning_sweep(a, dev):
+    print("# legs (the digit: bank path 1 / 2): G sensors and formats bound, no bins; B0 bins bound, all ones; B2 / B4 every stream binned; "
+          "Y4 LUMA16_LO binned 4x; D2 / D4 aof_ingest_sensors_binned_device into a grey buffer, then G on it "
+          "(exposure records, de-rotation, MAVLink frames on, all streams active)")
+    print("# us = microseconds per tick (host clock, ticks ending in a synchronise)")
+    bound = hasattr(aof.lib, "aof_set_bank_binning")      # (AOF_LIB may name a build without the call: G legs only)
+    kinds = ["G", "B0", "B2", "B4", "Y4", "D2", "D4"] if bound else ["G"]
+    legs = [(k + str(path), k, path) for path in (1, 2) for k in kinds]
+    if a.legs is not None:
+        legs = [leg for leg in legs if leg[0] in a.legs.split(",")]
+    sizes = [int(s) for s in a.streams.split(",")]
+    results = {}
+    for rep in range(a.repeats):
+        for cfg in a.configs.split(","):
+            p = params_of(cfg)
+            for S in sizes:
+                inp = Inputs(p, S, dev)
+                for name, kind, path in legs:
+                    sec, n = leg_binning(p, S, path, inp, dev, a, kind)
+                    results.setdefault((cfg, S, name), []).append(sec)
+                    print(f"rep {rep} {cfg:11s} S={S:6d} {name:3s} {sec * 1e6:10.2f} us  ({n} ticks)", flush=True)
+                    torch.cuda.empty_cache()
+                del inp
+    print("# ---- summary (median of the repeats; p10..p90 of the repeats in us) ----")
+    for cfg in a.configs.split(","):
+        for S in sizes:
+            m = {n: float(np.median(results[(cfg, S, n)])) for n, _, _ in legs}
+            line = f"{cfg:11s} S={S:6d}  " + "  ".join(
+                f"{n} {m[n] * 1e6:9.2f} us ({np.percentile(results[(cfg, S, n)], 10) * 1e6:.2f}..{np.percentile(results[(cfg, S, n)], 90) * 1e6:.2f})"
+                for n in m)
+            for path in (1, 2):
+                if all(k + str(path) in m for k in kinds) and bound:
+                    g, b0, b2, b4, y4, d2, d4 = (m[k + str(path)] for k in ("G", "B0", "B2", "B4", "Y4", "D2", "D4"))
+                    line += (f"  B0{path}/G{path} {b0 / g:5.3f}  B2{path}/G{path} {b2 / g:5.3f}  B4{path}/G{path} {b4 / g:5.3f}  Y4{path}/G{path} {y4 / g:5.3f}"
+                             f"  B2{path}/D2{path} {b2 / d2:5.3f}  B4{path}/D4{path} {b4 / d4:5.3f}")
             print(line)
 
 
@@ -1277,16 +1398,18 @@ def main():
                     "(K1 / K2 are --camera's legs of those names, the same leg_camera; --legs K1,K2 runs them alone, for two builds in turn)")
     ap.add_argument("--pixel-formats", action="store_true", help="the camera tick with packed 16-bit sensor pixels: legs G, P0, Y, M, D on both "
                     "bank paths (G1, ..., D2; --legs G1,G2 runs the yardstick alone, for a build without the call through AOF_LIB)")
+    ap.add_argument("--binning", action="store_true", help="the camera tick with binned sensor pixels: legs G, B0, B2, B4, Y4, D2, D4 on both "
+                    "bank paths (G1, ..., D42; --legs G1,G2 runs the yardstick alone, for a build without the call through AOF_LIB)")
     ap.add_argument("--forms", default="plain,camera", help="--burst: entry points to sweep")
     ap.add_argument("--input-bytes-max", type=float, default=24 * 2**30, help="--burst: sizes whose K rounds of input exceed this are skipped")
     a = ap.parse_args()
-    if a.legs is None and not a.per_sensor and not a.pixel_formats:
+    if a.legs is None and not a.per_sensor and not a.pixel_formats and not a.binning:
         a.legs = "T0,T1,T2,C,B"
     if a.burst and a.ticks == ap.get_default("ticks"):
         a.ticks = 1000           # (frame rounds)
     if a.camera and a.streams == ap.get_default("streams"):
         a.streams = "1,64,1024,1536,2048,4096"
-    if a.pixel_formats and a.streams == ap.get_default("streams"):
+    if (a.pixel_formats or a.binning) and a.streams == ap.get_default("streams"):
         a.streams = "64,256,1024,2048"
     if a.exposure_control and a.streams == ap.get_default("streams"):
         a.streams = "64,1024,4096"
@@ -1307,6 +1430,8 @@ def main():
         return per_sensor_sweep(a, dev)
     if a.pixel_formats:
         return pixel_formats_sweep(a, dev)
+    if a.binning:
+        return binning_sweep(a, dev)
     if a.mavlink_rx:
         return mavlink_rx_sweep(a, dev)
     if a.imu:
