@@ -51,8 +51,8 @@ __global__ __launch_bounds__(kThreads) void k_limit_next(SequenceArgs a)
         int64_t j = i + 1;
         for (; j < stop; j++)
             if ((float)((uint32_t)a.time_us[j] - base) > a.period_us) break;
-        if (j < stop) nxt = (uint32_t)j;
-        else if (stop < n) atomicOr(a.status, 1u);   // the time stamps do not advance: this chain ends here
+        if (j < stop) nxt = (uint32_t)j;   // (else END, also where the window ends before the recording does: whether
+                                           //  that is a STALL depends on the node being on the chain -- k_sequence_emit)
     }
     a.jump[0][i] = nxt;
     a.hops[0][i] = 1;
@@ -85,6 +85,9 @@ __global__ __launch_bounds__(kThreads) void k_limit_double(SequenceArgs a, int r
 }
 
 // One lane per frame; the lanes of published frames (frame 0, and the frames on the chain) write their message.
+// The lane of the chain's LAST node (the start where nothing publishes) raises AOF_SEQ_STATUS_STALLED if the node's scan
+// window ended before the recording did: the chain ends there with frames behind it.  A frame that is not on the chain
+// and finds no successor in its own window says nothing about the chain.
 __global__ __launch_bounds__(kThreads) void k_sequence_emit(SequenceArgs a)
 {
     const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
@@ -98,6 +101,8 @@ __global__ __launch_bounds__(kThreads) void k_sequence_emit(SequenceArgs a)
     float px = 0.0f, py = 0.0f;
     double gx = 0.0, gy = 0.0, gz = 0.0;
     uint32_t m = 0;
+    if (a.reached[k] != 0 && a.rank[k] + 1 == a.rank[n] && k + 1 + kLimitScanFrames < n && a.output_rate > 0)
+        atomicOr(a.status, AOF_SEQ_STATUS_STALLED);         // (the start is node 0: reached from the beginning, rank 0)
     if (k == 0) {
         // the first frame: calcFlow returns 0 with its outputs untouched (integrate(): nothing to compare it
         // with), and the caller sends what its zero-initialised locals hold (mainloop.cpp:280-281,322-373)

@@ -366,8 +366,11 @@ typedef struct aof_seq_record {
 } aof_seq_record;
 
 #define AOF_SEQ_FRAME_BYTES 56     /* room per MAVLink 2 frame: 10 + 44 + 2 */
-#define AOF_SEQ_STATUS_STALLED 1u  /* more than 4096 frames in a row without reaching the output period: the
-                                      time stamps do not advance; nothing is published behind that point */
+#define AOF_SEQ_STATUS_STALLED 1u  /* the CHAIN of publications ended with frames left: none of the 4096 frames behind its
+                                      last publication (behind the start, where nothing was published) reaches the
+                                      output period and the recording goes on beyond them -- the time stamps do not
+                                      advance; nothing is published behind that point.  Frames that are not published
+                                      never raise it, whatever lies behind them */
 
 /* Byte offsets of the pipeline's outputs and intermediates inside the caller's workspace. */
 typedef struct aof_seq_layout {
