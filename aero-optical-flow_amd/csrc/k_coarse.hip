@@ -20,9 +20,9 @@
 //
 // Bound: phase 1 by HBM (2 * W * H bytes per pair), phase 3 by the SAD issue rate; workgroups
 // on different CUs drift out of phase, so the chip overlaps the two.
-#include <climits>
 #include <cstdint>
 
+#include "aof_coarse_plan.hpp"
 #include "aof_device.hpp"
 #include "aof_internal.hpp"
 #include "aof_lab_hooks.hpp"
@@ -43,8 +43,9 @@ constexpr uint32_t kOpen = 0xFFFFFFFFu;    // key of a block still waiting for i
 constexpr int kMaxBins = 64;
 constexpr int kNonTemporal = 2;                // buffer-load cache policy: nt (the frames are streamed once)
 constexpr int kScratch = 8;                    // words behind the histograms: pixel sums, vote sums
-constexpr int kStaggerGroups = 3;              // lab sweep (tools/coarse_lab.hip): 1: 0.215, 2: 0.206, 3: 0.203, 4: 0.212 ms
-constexpr int64_t kStaggerBytesPerUs = 75000;  // start-up spacing of the groups: ~8 us at VGA
+// (the launch plan built on these lives in aof_coarse_plan.hpp; start-up stagger: there)
+static_assert(kThreads == kCoarseThreads && kUnroll == kCoarseUnroll && kMaxBins == kCoarseMaxBins && kScratch == kCoarseScratch,
+              "the kernel and its plan agree on the workgroup, the batches and the histograms");
 
 // Workgroup barrier for data exchanged through LDS only.  __syncthreads() carries a workgroup
 // fence, for which the compiler drains EVERY outstanding vector-memory operation (s_waitcnt
@@ -329,57 +330,39 @@ __global__ __launch_bounds__(kThreads) void k_coarse(CoarseArgs a)
 
 }  // namespace
 
-size_t coarse_lds_bytes(const CoarseArgs &a)
+namespace {
+
+CoarsePlan plan_of(const CoarseArgs &a)
 {
-    return (size_t)2 * (a.w / 2) * (a.h / 2) + (size_t)a.grid.blocks() * 4 + 2 * (2 * kMaxBins + kScratch) * 4;
+    return coarse_plan_make(a.w, a.h, a.pair_stride, reinterpret_cast<uintptr_t>(a.prev), reinterpret_cast<uintptr_t>(a.cur), a.grid,
+                            a.tail.range, a.tile, a.search, a.subpixel, a.n_pairs, a.first_generation);
 }
 
-// One workgroup must hold both level-1 frames, and the windows must sit on 8-byte columns.
-bool coarse_fused_supported(const CoarseArgs &a)
-{
-    if (a.tile != 8 || a.search != 4 || a.subpixel) return false;
-    if (a.w % 16 || a.h % 2 || a.pair_stride % 16 || a.w / 16 > kThreads) return false;
-    if (reinterpret_cast<uintptr_t>(a.prev) % 16 || reinterpret_cast<uintptr_t>(a.cur) % 16) return false;
-    const Grid &g = a.grid;
-    if (g.x0 != 4 || g.y0 != 4 || g.step_x != 8 || g.step_y != 8 || g.nx < 1 || g.ny < 1) return false;
-    if ((a.w / 2) % 8) return false;   // level-1 rows a multiple of 8 bytes: aligned 8-byte LDS reads
-    if (2 * (2 * a.tail.range + 1) + 1 > kMaxBins) return false;
-    if (a.n_pairs > 0x7FFFFFFF) return false;
-    return coarse_lds_bytes(a) <= 160 * 1024;
-}
+}  // namespace
+
+// The plan (rows per sweep, fast-div constants, LDS, stagger, workgroups) and the verdict: aof_coarse_plan.hpp.
+size_t coarse_lds_bytes(const CoarseArgs &a) { return coarse_plan_lds(a.w, a.h, a.grid); }
+
+bool coarse_fused_supported(const CoarseArgs &a) { return plan_of(a).verdict == COARSE_OK; }
 
 int launch_coarse_fused(const CoarseArgs &a, void *stream)
 {
     if (a.n_pairs == 0) return 0;
-    CoarseArgs k = a;
-    k.div_nb = fastdiv_make((uint32_t)a.grid.blocks());
-    k.div_nx = fastdiv_make((uint32_t)a.grid.nx);
-    k.div_chunks = fastdiv_make((uint32_t)(a.w / 16));
-    {   // Rows per sweep: as many as the workgroup has lanes for, but such that the two frames take a
-        // whole number of rounds of two batches -- padding sweeps would be loaded for nothing
-        // (VGA: 20 rows = 800 lanes, 24 sweeps, no padding; 25 rows would pad 20 sweeps to 24).
-        const int chunks = a.w / 16, h1 = a.h / 2, rmax = kThreads / chunks;
-        int best = rmax;
-        int64_t best_rows = LLONG_MAX;
-        for (int r = rmax; r >= 1 && r >= rmax / 2; r--) {
-            const int nk = 2 * ((h1 + r - 1) / r);
-            const int nk_pad = (nk + 2 * kUnroll - 1) / (2 * kUnroll) * (2 * kUnroll);
-            const int64_t loaded = (int64_t)nk_pad * r;
-            if (loaded < best_rows) { best_rows = loaded; best = r; }
-        }
-        k.rows_per_sweep = best;
-    }
     // first_generation: the CU count of the context's device, set by the caller
-    if (k.first_generation <= 0) return (int)hipErrorInvalidValue;
+    if (a.first_generation <= 0) return (int)hipErrorInvalidValue;
+    const CoarsePlan plan = plan_of(a);
+    if (plan.verdict != COARSE_OK) return (int)hipErrorInvalidValue;
+    CoarseArgs k = a;
+    k.div_nb = plan.div_nb;
+    k.div_nx = plan.div_nx;
+    k.div_chunks = plan.div_chunks;
+    k.rows_per_sweep = plan.rows_per_sweep;
     if (k.stagger_groups == 0) {   // (the lab tool sets its own)
-        k.stagger_groups = a.n_pairs >= 2 * (int64_t)k.first_generation ? kStaggerGroups : 1;
-        // one group's share of the stream phase: the pair's bytes at the rate a CU reaches when
-        // only 1/groups of the chip streams
-        k.stagger_ticks = (int32_t)((int64_t)2 * a.w * a.h * 100 / kStaggerBytesPerUs);
+        k.stagger_groups = plan.stagger_groups;
+        k.stagger_ticks = plan.stagger_ticks;
     }
-    const size_t lds = coarse_lds_bytes(a);
-    // one workgroup per CU (LDS); each walks pairs blockIdx.x, blockIdx.x + gridDim.x, ...
-    const int64_t wgs = a.n_pairs < k.first_generation ? a.n_pairs : k.first_generation;
+    const size_t lds = plan.lds;
+    const int64_t wgs = plan.wgs;
 #ifdef AOF_LAB_COARSE_WS
     {
         int rc = 0;
@@ -388,7 +371,7 @@ int launch_coarse_fused(const CoarseArgs &a, void *stream)
 #endif
     {   // (per launch, like the 16x16 kernel: the attribute belongs to the current device's code object)
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_coarse),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCoarseLdsLimit);
         if (e != hipSuccess) return (int)e;
     }
     hipLaunchKernelGGL(k_coarse, dim3((uint32_t)wgs), dim3(kThreads), lds, static_cast<hipStream_t>(stream), k);

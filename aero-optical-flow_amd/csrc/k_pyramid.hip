@@ -6,6 +6,7 @@
 // v_sad_u8 against zero; a wave reduction and one integer atomic per wave
 // publish the sums (integer atomics: order-independent, bit-exact).
 // HBM-bound: reads W*H, writes W*H/4 per frame.
+#include "aof_coarse_plan.hpp"
 #include "aof_device.hpp"
 #include "aof_internal.hpp"
 
@@ -13,8 +14,8 @@ namespace aof {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kItemsPerBlock = 1024;  // 16-px x 2-row items per workgroup
+constexpr int kThreads = 256;   // (kPyramidItemsPerBlock, the 16-px x 2-row items per workgroup: aof_coarse_plan.hpp)
+static_assert(kThreads == kPyramidThreads, "the kernels and their plan agree on the workgroup");
 
 // One wave's share of a frame's byte sums into the pairs' records [pair][prev, cur][level 0, level 1].  In a
 // sequence frame f is prev of pair f and cur of pair f - 1: both records get it (a.n_pairs counts FRAMES then).
@@ -142,37 +143,23 @@ int launch_zero_words(uint32_t *words, int64_t count, void *stream)
     return (int)hipGetLastError();
 }
 
+// The strip plan (which kernel, rows per strip, strips, workgroups, words to zero): aof_coarse_plan.hpp.
 int launch_pyramid(const PyramidArgs &a, void *stream)
 {
     if (a.n_pairs == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // (a.sequence: n_pairs counts the FRAMES of the sequence, one unit each; n_pairs - 1 pairs of sums)
-    const int64_t units = a.sequence ? a.n_pairs : a.n_pairs * 2;
+    const PyramidPlan plan = pyramid_plan_make(a.w, a.h, a.pair_stride, reinterpret_cast<uintptr_t>(a.prev), reinterpret_cast<uintptr_t>(a.cur),
+                                               a.sequence, a.n_pairs, a.sums != nullptr);
     if (a.sums) {
-        const int rc = launch_zero_words(a.sums, (a.sequence ? a.n_pairs - 1 : a.n_pairs) * 4, stream);
+        const int rc = launch_zero_words(a.sums, plan.zero_words, stream);
         if (rc) return rc;
     }
-    const bool vec = (a.w % 16 == 0) && (a.h % 2 == 0) && (a.pair_stride % 16 == 0) &&
-                     (reinterpret_cast<uintptr_t>(a.prev) % 16 == 0) &&
-                     (a.sequence || reinterpret_cast<uintptr_t>(a.cur) % 16 == 0);
-    if (vec) {
-        const int chunks = a.w / 16, h1 = a.h / 2;
-        int rows = kItemsPerBlock / chunks;
-        if (rows < 1) rows = 1;
-        const int nstrips = (h1 + rows - 1) / rows;
-        const int64_t total = units * nstrips;
-        if (total > 0x7FFFFFFF) return (int)hipErrorInvalidValue;
-        hipLaunchKernelGGL(k_pyramid_vec, dim3((uint32_t)total), dim3(kThreads), 0, s, a, rows,
-                           nstrips);
-    } else {
-        const int64_t cells = (int64_t)((a.w + 1) / 2) * ((a.h + 1) / 2);
-        int nstrips = (int)((cells + kItemsPerBlock - 1) / kItemsPerBlock);
-        if (nstrips < 1) nstrips = 1;
-        const int64_t total = units * nstrips;
-        if (total > 0x7FFFFFFF) return (int)hipErrorInvalidValue;
-        hipLaunchKernelGGL(k_pyramid_scalar, dim3((uint32_t)total), dim3(kThreads), 0, s, a,
-                           nstrips);
-    }
+    if (plan.total > 0x7FFFFFFF) return (int)hipErrorInvalidValue;
+    if (plan.vec)
+        hipLaunchKernelGGL(k_pyramid_vec, dim3((uint32_t)plan.total), dim3(kThreads), 0, s, a, plan.rows_per_strip, plan.nstrips);
+    else
+        hipLaunchKernelGGL(k_pyramid_scalar, dim3((uint32_t)plan.total), dim3(kThreads), 0, s, a, plan.nstrips);
     return (int)hipGetLastError();
 }
 

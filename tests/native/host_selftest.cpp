@@ -3,8 +3,10 @@
 // with the kernels, compiled for the host: the kernels' own packer (aof_mavlink.hpp) against the facade's, the two
 // forms of the checksum step against each other, the exposure bin and mean sample value (aof_exposure_step.hpp)
 // against the public functions; the column walk's segment plan (aof_cols8_plan.hpp: cols_plan_make) on the cases of
-// tests/cols_plan_ref.py, printed field by field for tests/test_host_asan.py to hold to the Python model; and
-// fastdiv_make against the division it replaces, with the kernels' fast_div restated in 32-bit arithmetic.
+// tests/cols_plan_ref.py, printed field by field for tests/test_host_asan.py to hold to the Python model; the plans of the
+// two coarse passes (aof_coarse_plan.hpp: coarse_plan_make, pyramid_plan_make) on the cases of tests/coarse_plan_ref.py,
+// printed the same way; and fastdiv_make against the division it replaces, with the kernels' fast_div restated in 32-bit
+// arithmetic.
 // Built with -fsanitize=address,undefined by tests/test_host_asan.py.
 #include <cmath>
 #include <cstdio>
@@ -12,6 +14,7 @@
 #include <cstring>
 
 #include "aof.h"
+#include "aof_coarse_plan.hpp"
 #include "aof_cols8_plan.hpp"
 #include "aof_exposure_step.hpp"
 #include "aof_internal.hpp"
@@ -153,6 +156,49 @@ static int print_cols_plans(const char *path)
     return cases;
 }
 
+// (d2) coarse_plan_make on a case file, one case per line: w h pair_stride prev cur x0 y0 step_x step_y nx ny range tile
+// search subpixel n_pairs cus.  One line of fields per case, in the order of coarse_plan_ref.COARSE_FIELDS.
+static int print_coarse_plans(const char *path)
+{
+    std::FILE *f = std::fopen(path, "r");
+    if (!f) return -1;
+    int cases = 0;
+    long long w, h, stride, g[6], range, tile, search, subpixel, n_pairs, cus;
+    unsigned long long prev, cur;
+    while (std::fscanf(f, "%lld %lld %lld %llu %llu %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld", &w, &h, &stride, &prev, &cur,
+                       &g[0], &g[1], &g[2], &g[3], &g[4], &g[5], &range, &tile, &search, &subpixel, &n_pairs, &cus) == 17) {
+        const aof::Grid grid = {(int32_t)g[0], (int32_t)g[1], (int32_t)g[2], (int32_t)g[3], (int32_t)g[4], (int32_t)g[5]};
+        const aof::CoarsePlan p = aof::coarse_plan_make((int)w, (int)h, (int64_t)stride, (uintptr_t)prev, (uintptr_t)cur, grid, (int)range,
+                                                        (int)tile, (int)search, (int)subpixel, (int64_t)n_pairs, (int)cus);
+        std::printf("coarse plan: %d %d %d %d %d %u %u %u %u %u %u %zu %d %d %lld\n", (int)p.verdict, p.rows_per_sweep, p.nkf, p.nk, p.nk_pad,
+                    p.div_nb.mul, p.div_nb.shift, p.div_nx.mul, p.div_nx.shift, p.div_chunks.mul, p.div_chunks.shift, p.lds, p.stagger_groups,
+                    p.stagger_ticks, (long long)p.wgs);
+        cases++;
+    }
+    std::fclose(f);
+    return cases;
+}
+
+// (d3) pyramid_plan_make on a case file, one case per line: w h pair_stride prev cur sequence n_pairs sums.  One line of
+// fields per case, in the order of coarse_plan_ref.PYRAMID_FIELDS.
+static int print_pyramid_plans(const char *path)
+{
+    std::FILE *f = std::fopen(path, "r");
+    if (!f) return -1;
+    int cases = 0;
+    long long w, h, stride, sequence, n_pairs, sums;
+    unsigned long long prev, cur;
+    while (std::fscanf(f, "%lld %lld %lld %llu %llu %lld %lld %lld", &w, &h, &stride, &prev, &cur, &sequence, &n_pairs, &sums) == 8) {
+        const aof::PyramidPlan p = aof::pyramid_plan_make((int)w, (int)h, (int64_t)stride, (uintptr_t)prev, (uintptr_t)cur, (int)sequence,
+                                                          (int64_t)n_pairs, sums != 0);
+        std::printf("pyramid plan: %d %d %d %lld %lld %lld\n", p.vec, p.rows_per_strip, p.nstrips, (long long)p.units, (long long)p.total,
+                    (long long)p.zero_words);
+        cases++;
+    }
+    std::fclose(f);
+    return cases;
+}
+
 // (e) fastdiv_make: the kernels' fast_div (aof_device.hpp) restated -- the high half of the product, the sum and the shift
 // in 32 bits -- against n / d.  Divisors: every d up to 4096 (grid widths, blocks per pair) and every multiple of 64 up to
 // 2^20 (units per pair); numerators: all below 2^16, and around 65 multiples of d spread up to the top of the 31 bits
@@ -257,6 +303,11 @@ int main(int argc, char **argv)
         const int plans = print_cols_plans(argv[1]);
         if (plans < 0) return 16;
         std::printf("host selftest: cols plan: %d cases\n", plans);
+    }
+    if (argc > 3) {
+        const int coarse = print_coarse_plans(argv[2]), pyramid = print_pyramid_plans(argv[3]);
+        if (coarse < 0 || pyramid < 0) return 17;
+        std::printf("host selftest: coarse plan: %d cases\nhost selftest: pyramid plan: %d cases\n", coarse, pyramid);
     }
     std::printf("host selftest: %d valid parameter sets, %d rejected\n", valid, bad);
     return valid > 1000 ? 0 : 11;

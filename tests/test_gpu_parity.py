@@ -10,9 +10,11 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def run_gpu(aof, p, prevs, curs, device, force_generic=False, want_ws=False, fused_reduce=False, split_coarse=False):
+def run_gpu(aof, p, prevs, curs, device, force_generic=False, want_ws=False, fused_reduce=False, split_coarse=False, profile=False):
     import torch
     eng = aof.FlowEngine(p, 0)
+    if profile:   # out["launches"]: launches per profiling counter
+        eng.set_profiling(True)
     if force_generic:
         eng.force_generic(True)
     if split_coarse:
@@ -24,6 +26,9 @@ def run_gpu(aof, p, prevs, curs, device, force_generic=False, want_ws=False, fus
     blocks, flows, ws = eng.flow_batch(tp, tc)
     torch.cuda.synchronize()
     out = dict(blocks=aof.blocks_view(blocks), flows=aof.flows_view(flows), variant=eng.variant, eng=eng)
+    if profile:
+        out["launches"] = {k: len(eng.profile_ms(getattr(aof, k))) for k in ("K_PYRAMID", "K_SEARCH_L1", "K_REDUCE_L1", "K_SEARCH", "K_REDUCE")}
+        eng.set_profiling(False)
     if want_ws:
         out["ws"] = ws.cpu().numpy()
     return out
@@ -371,16 +376,22 @@ def test_two_level_batch_replays_from_a_graph(aof, orc, synth, gpu_device, kw):
         check_against_oracle(aof, orc, p, hp, hc, dict(blocks=aof.blocks_view(blocks), flows=aof.flows_view(flows)))
 
 
-@pytest.mark.parametrize("shape", [(160, 128), (640, 480), (320, 66), (96, 96), (672, 464), (48, 32)])
+# (w, h) at seven pairs, or (w, h, pairs).  96 x 96 at seven pairs (121 and 25 blocks) is a small-class batch: that row is
+# k_flow_small against the split kernels, and k_coarse takes the shape from 129 pairs on.  48 x 32 has two level-1 blocks,
+# too few for the grouped search, so it is no small-class batch at any pair count and runs k_coarse at seven pairs as well.
+@pytest.mark.parametrize("shape", [(160, 128), (640, 480), (320, 66), (96, 96), (672, 464), (48, 32), (96, 96, 129), (48, 32, 129)])
 @pytest.mark.parametrize("kw", [dict(), dict(mean_subtract=1), dict(mean_subtract=1, hist_filter=0, min_valid=0)])
 def test_fused_coarse_kernel_equals_the_split_kernels(aof, orc, synth, gpu_device, shape, kw):
     """k_coarse (sums + pyramid + level-1 search + predictor in one workgroup per pair, level-1
     frames in LDS) against the separate K1 / K2 / K3 kernels and the oracle: level-1 records,
-    predictors, pixel sums and the final records, on textured, flat, saturated and noisy pairs."""
-    W, H = shape
+    predictors, pixel sums and the final records, on textured, flat, saturated and noisy pairs.
+    The launch counters say which kernel made the coarse pass: the one the plan model
+    (tests/coarse_plan_ref.py: coarse_kind) names for the shape and the pair count."""
+    import coarse_plan_ref
+    W, H = shape[:2]
+    n = shape[2] if len(shape) > 2 else 7
     p = aof.default_params(W, H, pyramid_levels=2, **kw)
-    n = 7
-    prevs, curs, _ = synth.make_batch(W, H, n, 9, 8100 + W, noise=4, brightness=11 if kw else 0)
+    prevs, curs, _ = synth.make_batch(W, H, 7, 9, 8100 + W, noise=4, brightness=11 if kw else 0)
     prevs[1, : H // 2] = 7                      # flat upper half: gated blocks
     curs[1, : H // 2] = 7
     curs[2] = np.minimum(curs[2].astype(np.int32) * 2, 255).astype(np.uint8)   # saturated: the clamp bites
@@ -388,9 +399,19 @@ def test_fused_coarse_kernel_equals_the_split_kernels(aof, orc, synth, gpu_devic
     curs[3] = 255 - curs[3]
     curs[4] = prevs[4]                          # identical frames
     prevs[5] = 0                                # black previous frame: everything gated
+    prevs, curs = prevs[np.arange(n) % 7], curs[np.arange(n) % 7]   # (more than seven pairs: replicas)
+    kind = coarse_plan_ref.coarse_kind(coarse_plan_ref.case("parity", W, H, n, mean_subtract=1 if kw else 0))
+    assert kind == ("small" if (W, H, n) == (96, 96, 7) else "fused")
     outs = {}
     for split in (False, True):
-        got = run_gpu(aof, p, prevs, curs, gpu_device, want_ws=True, split_coarse=split)
+        got = run_gpu(aof, p, prevs, curs, gpu_device, want_ws=True, split_coarse=split, profile=True)
+        made = {k: got["launches"][k] for k in ("K_PYRAMID", "K_SEARCH_L1", "K_REDUCE_L1")}
+        if split:
+            assert made["K_PYRAMID"] == 1 and made["K_SEARCH_L1"] == 1, (shape, made)
+        elif kind == "small":   # k_flow_small: one launch, counted as the level-0 search
+            assert made == dict(K_PYRAMID=0, K_SEARCH_L1=0, K_REDUCE_L1=0) and got["launches"]["K_SEARCH"] == 1, (shape, got["launches"])
+        else:                   # k_coarse: one launch, counted as K1
+            assert made == dict(K_PYRAMID=1, K_SEARCH_L1=0, K_REDUCE_L1=0), (shape, made)
         L = aof.workspace_layout(p, n)
         nb1 = got["eng"].nblocks(1)
         ws = got["ws"]
@@ -399,7 +420,9 @@ def test_fused_coarse_kernel_equals_the_split_kernels(aof, orc, synth, gpu_devic
                            f1=ws[L.l1_flows:L.l1_flows + n * 16].tobytes(),
                            sums=ws[L.sums:L.sums + n * 16].tobytes() if kw else b"")
         if not split:
-            check_against_oracle(aof, orc, p, prevs, curs, got)
+            check_against_oracle(aof, orc, p, prevs[:7], curs[:7], got)
+            for i in range(7, n):   # the replicas against their originals
+                assert got["blocks"][i].tobytes() == got["blocks"][i % 7].tobytes() and got["flows"][i].tobytes() == got["flows"][i % 7].tobytes(), i
     for k in outs[False]:
         assert outs[False][k] == outs[True][k], f"{k} differs between the fused and the split coarse passes"
 

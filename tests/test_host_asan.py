@@ -3,10 +3,13 @@ workspace layout, MAVLink packer), 20 000 random parameter sets including invali
 shares with the kernels (csrc/aof_mavlink.hpp, csrc/aof_exposure_step.hpp) compiled for the host: the kernels' packer
 against the facade's, the two checksum steps on every input, the exposure bin and mean sample value; the column walk's
 segment plan (csrc/aof_cols8_plan.hpp: cols_plan_make) on every case of tests/cols_plan_ref.py, field by field against
-the Python model; fastdiv_make against the division it replaces."""
+the Python model; the plans of the two coarse passes (csrc/aof_coarse_plan.hpp: coarse_plan_make, pyramid_plan_make) on
+every case of tests/coarse_plan_ref.py and a list of extreme shapes, the same way; fastdiv_make against the division it
+replaces."""
 import os
 import subprocess
 
+import coarse_plan_ref as coarse
 import cols_plan_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,7 +27,12 @@ def test_host_logic_is_clean_under_asan_ubsan(tmp_path):
     cases = ref.CPU_CASES + ref.GPU_CASES + ref.PLAN_ONLY
     listing = tmp_path / "cols_plan_cases.txt"
     listing.write_text("".join(ref.selftest_line(c) + "\n" for c in cases))
-    r = subprocess.run([str(exe), str(listing)], capture_output=True, text=True, timeout=300)
+    coarse_cases = coarse.CPU_CASES + coarse.GPU_CASES + coarse.PLAN_ONLY
+    lines = [coarse.selftest_lines(c) for c in coarse_cases]
+    coarse_listing, pyramid_listing = tmp_path / "coarse_plan_cases.txt", tmp_path / "pyramid_plan_cases.txt"
+    coarse_listing.write_text("".join(a + "\n" for a, _ in lines))
+    pyramid_listing.write_text("".join(b + "\n" for _, b in lines))
+    r = subprocess.run([str(exe), str(listing), str(coarse_listing), str(pyramid_listing)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, f"rc={r.returncode}\n{r.stdout}{r.stderr}"
     assert "valid parameter sets" in r.stdout
     assert "packer: 4012 frames equal to the facade's, lengths 52 and 56" in r.stdout
@@ -40,3 +48,17 @@ def test_host_logic_is_clean_under_asan_ubsan(tmp_path):
         assert len(got) == len(want) == len(ref.PLAN_FIELDS)
         diff = {name: (int(g), w) for name, g, w in zip(ref.PLAN_FIELDS, got, want) if int(g) != w}
         assert not diff, (c["id"], diff)
+    # coarse_plan_make and pyramid_plan_make == the model, on every case of every list
+    assert f"coarse plan: {len(coarse_cases)} cases" in r.stdout and f"pyramid plan: {len(coarse_cases)} cases" in r.stdout
+    assert len(coarse_cases) >= 90 and len(coarse.PLAN_ONLY) >= 20
+    for tag, fields, names, which in (("coarse plan: ", coarse.coarse_fields, coarse.COARSE_FIELDS, 0),
+                                      ("pyramid plan: ", coarse.pyramid_fields, coarse.PYRAMID_FIELDS, 1)):
+        plans = [line.split()[2:] for line in r.stdout.splitlines() if line.startswith(tag)]
+        assert len(plans) == len(coarse_cases)
+        for c, got in zip(coarse_cases, plans):
+            want = fields(coarse.plans_of(c)[which])
+            assert len(got) == len(want) == len(names)
+            diff = {name: (int(g), w) for name, g, w in zip(names, got, want) if int(g) != w}
+            assert not diff, (tag, c["id"], diff)
+    verdicts = {coarse.plans_of(c)[0]["verdict"] for c in coarse_cases}
+    assert verdicts == set(coarse.VERDICTS), set(coarse.VERDICTS) - verdicts
