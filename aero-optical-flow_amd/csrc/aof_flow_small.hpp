@@ -9,15 +9,11 @@
 #include "aof_reduce.hpp"
 #include "aof_refine.hpp"
 #include "aof_sad.hpp"
+#include "aof_small_plan.hpp"   // kThreads, kMaxBins, kLoads, kPad; the launch plan
 
 namespace aof {
 
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kMaxBins = 64;   // n = 2(2R+1)+1: 19 at level 1 (and for one level), 55 at level 0 of two (S = 4)
-constexpr int kLoads = 8;      // 16-byte chunks a thread has in flight in pass A
-constexpr int kPad = 16;       // bytes after each LDS frame: the dword reads of the last row may run past it
 
 // Unaligned reads from an LDS frame: aligned dwords, funnel-shifted by the byte offset's low bits.
 __device__ __forceinline__ uint4 lds_bytes16(const uint8_t *frame, int off)
@@ -376,14 +372,9 @@ __device__ __forceinline__ void flow_small_pair(const SmallArgs &a, uint32_t pai
     run_level<SUBPIXEL>(a.l0, a.t0, pair, f0[pb], f0[cur_buf], m0, s_keys, s_votes, s_tot, final_copy, two ? &s_flow1 : nullptr);
 }
 
-// Dynamic LDS of a workgroup that runs flow_small_pair: both level-0 frames and, with two levels, their level-1 images.
-inline size_t small_lds_bytes(const SmallArgs &a)
-{
-    const size_t frame0 = (size_t)a.l0.w * a.l0.h, frame1 = (size_t)(a.l0.w / 2) * (a.l0.h / 2);
-    size_t bytes = 2 * (frame0 + kPad);
-    if (a.levels == 2) bytes += 2 * ((frame1 + kPad + 15) & ~(size_t)15);
-    return bytes;
-}
+// Dynamic LDS of a workgroup that runs flow_small_pair: both level-0 frames and, with two levels, their level-1 images
+// (small_plan_make, aof_small_plan.hpp).
+inline size_t small_lds_bytes(const SmallArgs &a) { return small_plan_make(a).lds; }
 
 // The ONE launcher of the one-workgroup class (k_flow_small.hip, k_bank.hip, k_bank_burst.hip): `grid` workgroups of
 // kThreads lanes run `fn` on the plan `sm`; `args` are the kernel's own arguments.  `fn` is the instantiation that is
@@ -391,11 +382,12 @@ inline size_t small_lds_bytes(const SmallArgs &a)
 template <typename... Params, typename... Args>
 inline int launch_small_class(void (*fn)(Params...), uint32_t grid, const SmallArgs &sm, void *stream, const Args &...args)
 {
-    if (!flow_small_supported(sm)) return (int)hipErrorInvalidValue;
-    const size_t lds = small_lds_bytes(sm);
-    if (lds > 48 * 1024) {
+    const SmallPlan plan = small_plan_make(sm);
+    if (plan.verdict != SMALL_OK) return (int)hipErrorInvalidValue;
+    const size_t lds = plan.lds;
+    if (plan.attr) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kSmallLdsLimit - kSmallStaticLds));
         if (e != hipSuccess) return (int)e;
     }
     hipLaunchKernelGGL(fn, dim3(grid), dim3(kThreads), lds, static_cast<hipStream_t>(stream), args...);

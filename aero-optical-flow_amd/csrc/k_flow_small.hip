@@ -131,26 +131,8 @@ __global__ __launch_bounds__(kThreads) void k_flow_resident(SmallArgs a, Residen
 
 }  // namespace
 
-bool flow_small_supported(const SmallArgs &a)
-{
-    const SearchArgs &l0 = a.l0, &l1 = a.l1;
-    if (a.levels != 1 && a.levels != 2) return false;
-    if (l0.tile != 8 || l0.search != 4) return false;
-    if (l0.n_pairs < 1 || l0.n_pairs > 0x7FFFFFFF / kThreads) return false;
-    if (l0.grid.blocks() < 1 || l0.grid.blocks() > kThreads) return false;
-    if (2 * (2 * a.t0.range + 1) + 1 > kMaxBins) return false;
-    // 16-byte chunks of a contiguous frame
-    if (l0.w % 16 || (l0.n_pairs > 1 && l0.pair_stride % 16)) return false;
-    if (reinterpret_cast<uintptr_t>(l0.prev) % 16 || reinterpret_cast<uintptr_t>(l0.cur) % 16) return false;
-    if (l0.subpixel && !l0.subdirs) return false;
-    if (a.levels == 2) {
-        if (l0.h % 2 || l1.w != l0.w / 2 || l1.h != l0.h / 2) return false;
-        if (l1.grid.blocks() < 1 || l1.grid.blocks() > kThreads) return false;
-        if (2 * (2 * a.t1.range + 1) + 1 > kMaxBins) return false;
-        if (l0.subpixel && !l1.subdirs) return false;
-    }
-    return small_lds_bytes(a) + 4096 <= 160 * 1024;   // frames + the kernel's static arrays
-}
+// (the conditions, in order: small_plan_make, aof_small_plan.hpp)
+bool flow_small_supported(const SmallArgs &a) { return small_plan_make(a).verdict == SMALL_OK; }
 
 int launch_flow_resident(const SmallArgs &a, ResidentBox *box, aof_flow *host_record, const uint8_t *frame_a,
                          const uint8_t *frame_b, uint32_t served, uint32_t launch_no, uint64_t idle_ticks,

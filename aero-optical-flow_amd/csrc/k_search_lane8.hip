@@ -5,27 +5,14 @@
 
 #include "aof_internal.hpp"
 #include "aof_lane8_launch.hpp"
+#include "aof_small_plan.hpp"   // kThreads: block size of the pruned and grouped kernels (aof_lane8_kernels.hpp); the grouped plan
 
 namespace aof {
-
-namespace {
-constexpr int kThreads = 256;   // block size of the pruned and grouped kernels (aof_lane8_kernels.hpp)
-}
 
 // One launch indexes its (pair, block) items with 31 bits; larger batches are cut into several.
 constexpr int64_t kMaxItems = 0x7FFF0000ll;
 
-bool lane8_supported(const SearchArgs &a)
-{
-    if (a.tile != 8 || a.search != 4) return false;
-    const int64_t frame = (int64_t)a.w * a.h;
-    const int nb = a.grid.blocks();
-    if (frame > (1 << 24) || nb < 1 || nb >= (1 << 24)) return false;   // 24-bit multiplies in the kernels
-    // a wave's lanes address their frames with 32-bit offsets from the wave's first pair
-    const int64_t span = 64 / nb + 2;
-    if (a.n_pairs > 1 && (a.pair_stride < 0 || span * a.pair_stride + frame > 0xFFFFFFFFll)) return false;
-    return true;
-}
+bool lane8_supported(const SearchArgs &a) { return lane8_plan_supported(a); }   // (aof_small_plan.hpp)
 
 namespace {
 
@@ -122,27 +109,20 @@ int launch_search_lane8(const SearchArgs &a, void *stream, const FlowTail *tail,
     });
 }
 
-// Pairs per workgroup of the grouped kernel; 0 = the grid does not qualify.
-int lane8_group(const SearchArgs &a)
-{
-    const int nb = a.grid.blocks();
-    if (!lane8_supported(a) || nb < 8 || nb > kThreads) return 0;  // 1 .. 32 pairs per workgroup
-    return kThreads / nb;
-}
+// Pairs per workgroup of the grouped kernel; 0 = the grid does not qualify (lane8_group_plan, aof_small_plan.hpp).
+int lane8_group(const SearchArgs &a) { return lane8_group_plan(a).ppw; }
 
 int launch_flow_lane8(const SearchArgs &a, const FlowTail &tail, void *stream)
 {
     if (a.n_pairs == 0) return 0;
-    const int ppw = lane8_group(a);
-    if (ppw == 0) return (int)hipErrorInvalidValue;
-    const int n = 2 * (2 * a.hist_range + 1) + 1;
+    if (lane8_group_plan(a).ppw == 0) return (int)hipErrorInvalidValue;
     if (a.subpixel && !a.subdirs) return (int)hipErrorInvalidValue;
     return for_slices(a, [&](const SearchArgs &s, int64_t done) {
         FlowTail t = tail;
         t.flows += done;
         if (t.pred) t.pred += done;
-        const int64_t wgs = (s.n_pairs + ppw - 1) / ppw;
-        return (s.subpixel ? launch_k_flow_lane8_t : launch_k_flow_lane8_f)(s, t, ppw, (uint32_t)wgs, (size_t)ppw * 2 * n * sizeof(uint32_t), stream);
+        const Lane8GroupPlan g = lane8_group_plan(s);   // (of the slice: its pairs)
+        return (s.subpixel ? launch_k_flow_lane8_t : launch_k_flow_lane8_f)(s, t, g.ppw, (uint32_t)g.wgs, g.lds, stream);
     });
 }
 

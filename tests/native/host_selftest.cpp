@@ -5,7 +5,8 @@
 // against the public functions; the column walk's segment plan (aof_cols8_plan.hpp: cols_plan_make) on the cases of
 // tests/cols_plan_ref.py, printed field by field for tests/test_host_asan.py to hold to the Python model; the plans of the
 // two coarse passes (aof_coarse_plan.hpp: coarse_plan_make, pyramid_plan_make) on the cases of tests/coarse_plan_ref.py,
-// printed the same way; and fastdiv_make against the division it replaces, with the kernels' fast_div restated in 32-bit
+// printed the same way; the plans of the small-pair kernels (aof_small_plan.hpp: small_plan_make, lane8_group_plan) on the
+// cases of tests/small_plan_ref.py, likewise; and fastdiv_make against the division it replaces, with the kernels' fast_div restated in 32-bit
 // arithmetic.
 // Built with -fsanitize=address,undefined by tests/test_host_asan.py.
 #include <cmath>
@@ -19,6 +20,7 @@
 #include "aof_exposure_step.hpp"
 #include "aof_internal.hpp"
 #include "aof_mavlink.hpp"
+#include "aof_small_plan.hpp"
 #include "optical_flow_rad.hpp"
 
 static unsigned rng_state = 777u;
@@ -199,6 +201,51 @@ static int print_pyramid_plans(const char *path)
     return cases;
 }
 
+// (d4) small_plan_make and lane8_group_plan on a case file, one case per line: w h levels, the level-0 and the level-1 grid
+// (x0 y0 step_x step_y nx ny each), n_pairs pair_stride prev cur subpixel tile search, the histogram ranges of level 0 and 1,
+// whether levels 0 and 1 have a place for their half-pixel directions, and level 1's size as the caller states it.  Two
+// lines of fields per case, in the order of small_plan_ref.PLAN_FIELDS and GROUP_FIELDS.
+static int print_small_plans(const char *path)
+{
+    std::FILE *f = std::fopen(path, "r");
+    if (!f) return -1;
+    int cases = 0;
+    long long w, h, levels, g0[6], g1[6], n_pairs, stride, subpixel, tile, search, rng0, rng1, sub0, sub1, l1_w, l1_h;
+    unsigned long long prev, cur;
+    static uint8_t somewhere[1];   // (a place for directions: only looked at for being there)
+    while (std::fscanf(f, "%lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %llu %llu %lld %lld %lld %lld %lld %lld %lld %lld %lld",
+                       &w, &h, &levels, &g0[0], &g0[1], &g0[2], &g0[3], &g0[4], &g0[5], &g1[0], &g1[1], &g1[2], &g1[3], &g1[4], &g1[5], &n_pairs,
+                       &stride, &prev, &cur, &subpixel, &tile, &search, &rng0, &rng1, &sub0, &sub1, &l1_w, &l1_h) == 28) {
+        aof::SmallArgs a = {};
+        aof::SearchArgs *lv[2] = {&a.l0, &a.l1};
+        const long long *g[2] = {g0, g1};
+        for (int l = 0; l < 2; l++) {
+            aof::SearchArgs &s = *lv[l];
+            s.prev = reinterpret_cast<const uint8_t *>((uintptr_t)prev);
+            s.cur = reinterpret_cast<const uint8_t *>((uintptr_t)cur);
+            s.pair_stride = (int64_t)stride;
+            s.w = (int32_t)(l ? l1_w : w); s.h = (int32_t)(l ? l1_h : h);
+            s.tile = (int32_t)tile; s.search = (int32_t)search;
+            s.grid = {(int32_t)g[l][0], (int32_t)g[l][1], (int32_t)g[l][2], (int32_t)g[l][3], (int32_t)g[l][4], (int32_t)g[l][5]};
+            s.subpixel = (int32_t)subpixel;
+            s.subdirs = (l ? sub1 : sub0) ? somewhere : nullptr;
+            s.n_pairs = (int64_t)n_pairs;
+            s.hist_range = (int32_t)(l ? rng1 : rng0);
+            s.level = l;
+        }
+        a.t0.range = (int32_t)rng0; a.t1.range = (int32_t)rng1;
+        a.levels = (int32_t)levels;
+        const aof::SmallPlan p = aof::small_plan_make(a);
+        std::printf("small plan: %d %zu %zu %zu %zu %zu %d %d %d %d %d %d %d %d %d %d\n", (int)p.verdict, p.lds, p.f0[0], p.f0[1], p.f1[0], p.f1[1], p.attr,
+                    p.trips_a[0], p.trips_a[1], p.trips_a[2], p.trips_b[0], p.trips_b[1], p.trips_c[0], p.trips_c[1], p.trips_d1[0], p.trips_d1[1]);
+        const aof::Lane8GroupPlan gp = aof::lane8_group_plan(a.l0);
+        std::printf("group plan: %d %lld %d %zu\n", gp.ppw, (long long)gp.wgs, gp.last_live, gp.lds);
+        cases++;
+    }
+    std::fclose(f);
+    return cases;
+}
+
 // (e) fastdiv_make: the kernels' fast_div (aof_device.hpp) restated -- the high half of the product, the sum and the shift
 // in 32 bits -- against n / d.  Divisors: every d up to 4096 (grid widths, blocks per pair) and every multiple of 64 up to
 // 2^20 (units per pair); numerators: all below 2^16, and around 65 multiples of d spread up to the top of the 31 bits
@@ -308,6 +355,11 @@ int main(int argc, char **argv)
         const int coarse = print_coarse_plans(argv[2]), pyramid = print_pyramid_plans(argv[3]);
         if (coarse < 0 || pyramid < 0) return 17;
         std::printf("host selftest: coarse plan: %d cases\nhost selftest: pyramid plan: %d cases\n", coarse, pyramid);
+    }
+    if (argc > 4) {
+        const int small = print_small_plans(argv[4]);
+        if (small < 0) return 18;
+        std::printf("host selftest: small plan: %d cases\n", small);
     }
     std::printf("host selftest: %d valid parameter sets, %d rejected\n", valid, bad);
     return valid > 1000 ? 0 : 11;

@@ -4,13 +4,15 @@ shares with the kernels (csrc/aof_mavlink.hpp, csrc/aof_exposure_step.hpp) compi
 against the facade's, the two checksum steps on every input, the exposure bin and mean sample value; the column walk's
 segment plan (csrc/aof_cols8_plan.hpp: cols_plan_make) on every case of tests/cols_plan_ref.py, field by field against
 the Python model; the plans of the two coarse passes (csrc/aof_coarse_plan.hpp: coarse_plan_make, pyramid_plan_make) on
-every case of tests/coarse_plan_ref.py and a list of extreme shapes, the same way; fastdiv_make against the division it
-replaces."""
+every case of tests/coarse_plan_ref.py and a list of extreme shapes, the same way; the plans of the small-pair kernels
+(csrc/aof_small_plan.hpp: small_plan_make, lane8_group_plan) on every case of tests/small_plan_ref.py and its list of
+extreme shapes, likewise; fastdiv_make against the division it replaces."""
 import os
 import subprocess
 
 import coarse_plan_ref as coarse
 import cols_plan_ref as ref
+import small_plan_ref as small
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -32,7 +34,11 @@ def test_host_logic_is_clean_under_asan_ubsan(tmp_path):
     coarse_listing, pyramid_listing = tmp_path / "coarse_plan_cases.txt", tmp_path / "pyramid_plan_cases.txt"
     coarse_listing.write_text("".join(a + "\n" for a, _ in lines))
     pyramid_listing.write_text("".join(b + "\n" for _, b in lines))
-    r = subprocess.run([str(exe), str(listing), str(coarse_listing), str(pyramid_listing)], capture_output=True, text=True, timeout=300)
+    small_cases = small.CPU_CASES + small.GPU_CASES + small.PLAN_ONLY
+    small_listing = tmp_path / "small_plan_cases.txt"
+    small_listing.write_text("".join(small.selftest_line(c) + "\n" for c in small_cases))
+    r = subprocess.run([str(exe), str(listing), str(coarse_listing), str(pyramid_listing), str(small_listing)], capture_output=True, text=True,
+                       timeout=300)
     assert r.returncode == 0, f"rc={r.returncode}\n{r.stdout}{r.stderr}"
     assert "valid parameter sets" in r.stdout
     assert "packer: 4012 frames equal to the facade's, lengths 52 and 56" in r.stdout
@@ -62,3 +68,16 @@ def test_host_logic_is_clean_under_asan_ubsan(tmp_path):
             assert not diff, (tag, c["id"], diff)
     verdicts = {coarse.plans_of(c)[0]["verdict"] for c in coarse_cases}
     assert verdicts == set(coarse.VERDICTS), set(coarse.VERDICTS) - verdicts
+    # small_plan_make and lane8_group_plan == the model, on every case of every list
+    assert f"small plan: {len(small_cases)} cases" in r.stdout and len(small_cases) >= 70 and len(small.PLAN_ONLY) >= 30
+    for tag, fields, names, which in (("small plan: ", small.plan_fields, small.PLAN_FIELDS, 0), ("group plan: ", small.group_fields, small.GROUP_FIELDS, 1)):
+        plans = [line.split()[2:] for line in r.stdout.splitlines() if line.startswith(tag)]
+        assert len(plans) == len(small_cases)
+        for c, got in zip(small_cases, plans):
+            want = fields(small.plans_of(c)[which])
+            assert len(got) == len(want) == len(names)
+            diff = {name: (int(g), w) for name, g, w in zip(names, got, want) if int(g) != w}
+            assert not diff, (tag, c["id"], diff)
+    # every verdict occurs, and the grouped plan both applies and does not
+    assert {small.plans_of(c)[0]["verdict"] for c in small_cases} == set(small.VERDICTS)
+    assert {small.plans_of(c)[1]["ppw"] > 0 for c in small_cases} == {True, False}
