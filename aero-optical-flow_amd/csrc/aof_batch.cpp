@@ -206,7 +206,7 @@ constexpr int kProbeEvery = 16;
 bool adaptive_lane8_prunes(AdaptiveSearch &st, const SearchArgs &a)
 {
     // level-1 searches and small launches: too few blocks per wave to carry a hint along
-    if (a.level != 0 || !st.slots || lane8_chunks(a) < kPruneMinChunks) return false;
+    if (a.level != 0 || !st.slots || !lane8_prune_large(a)) return false;
     if (st.expected) {
         const uint32_t tag = st.launch_no & 0xFFFFu;
         uint32_t arrived = 0, paying = 0, seen = 0;

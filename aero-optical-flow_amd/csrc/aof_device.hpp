@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "aof_internal.hpp"
+#include "aof_xcd_remap.hpp"
 
 namespace aof {
 
@@ -187,15 +188,6 @@ __device__ __forceinline__ void wave_vote2_weighted(uint32_t *hist_x, uint32_t *
     wave_vote_weighted(hist_y, key >> 16, weight, m1, m2, m3, m4);
 }
 
-// Bijective XCD-aware remap of a 1-D grid (workgroups b and b+8 share an XCD's
-// L2 under round-robin placement): XCD k gets one contiguous chunk of logical
-// ids, so consecutive block rows of one frame pair are served by the same L2.
-// Placement only affects speed, never results.
-__device__ __forceinline__ uint32_t xcd_remap(uint32_t b, uint32_t total)
-{
-    const uint32_t q = total / 8, r = total % 8, xcd = b % 8, slot = b / 8;
-    const uint32_t base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + slot;
-}
+// (xcd_remap, the XCD-aware placement of a 1-D grid: aof_xcd_remap.hpp, one text for the kernels and the host)
 
 }  // namespace aof

@@ -179,9 +179,9 @@ bool lane8_supported(const SearchArgs &a);
 bool lane8_votes_supported(const SearchArgs &a, const VoteMem &votes, int64_t capacity_pairs);
 int launch_search_lane8(const SearchArgs &a, void *stream, const FlowTail *tail = nullptr,
                         const VoteMem *votes = nullptr, PruneReport *report = nullptr);
-// 256-block chunks of the launch: the pruned kernels carry their hints from block to block of a wave and need a
-// launch large enough for walks of three blocks before that pays (kPruneMinChunks below).
-int64_t lane8_chunks(const SearchArgs &a);
+// The pruned kernels carry their hints from block to block of a wave and need a launch large enough for walks of three
+// blocks before that pays: at least kPruneMinChunks (below) 256-block chunks (lane8_flat_plan, aof_lane8_plan.hpp).
+bool lane8_prune_large(const SearchArgs &a);
 // The pruned search on dense grids as a column walk (k_search_cols8.hip): a lane keeps the lower half of its window for
 // the block below.  Same modes (a.prune 1 / 2), same report.
 bool lane8_cols_supported(const SearchArgs &a);

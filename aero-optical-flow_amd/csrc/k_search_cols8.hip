@@ -40,7 +40,7 @@ int launch_search_lane8_cols(const SearchArgs &a, void *stream, PruneReport *rep
         if (s.pred) s.pred += done;
         if (s.sums) s.sums += done * 4;
         // a launch of one or two generations of waves ends sooner with one-wave workgroups, whose slots free up wave by
-        // wave for the other batch in flight (as flat_threads does for the exhaustive kernel, k_search_lane8.hip)
+        // wave for the other batch in flight (as lane8_flat_threads does for the exhaustive kernel, aof_lane8_plan.hpp)
         // (one-wave workgroups for launches of one or two generations of waves, as the exhaustive kernel has them, measure
         //  the same within the spread of 200-step runs: profiles/r05_small_launch_shape.txt)
         const int threads = kColsThreads;

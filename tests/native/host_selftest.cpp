@@ -6,7 +6,9 @@
 // tests/cols_plan_ref.py, printed field by field for tests/test_host_asan.py to hold to the Python model; the plans of the
 // two coarse passes (aof_coarse_plan.hpp: coarse_plan_make, pyramid_plan_make) on the cases of tests/coarse_plan_ref.py,
 // printed the same way; the plans of the small-pair kernels (aof_small_plan.hpp: small_plan_make, lane8_group_plan) on the
-// cases of tests/small_plan_ref.py, likewise; and fastdiv_make against the division it replaces, with the kernels' fast_div restated in 32-bit
+// cases of tests/small_plan_ref.py, likewise; the plan of the flat lane-per-block launches (aof_lane8_plan.hpp: lane8_flat_plan)
+// on the cases of tests/lane8_plan_ref.py, likewise, and xcd_remap (aof_xcd_remap.hpp, the text the kernels run) printed value by
+// value for the test to hold to the model's; and fastdiv_make against the division it replaces, with the kernels' fast_div restated in 32-bit
 // arithmetic.
 // Built with -fsanitize=address,undefined by tests/test_host_asan.py.
 #include <cmath>
@@ -19,8 +21,10 @@
 #include "aof_cols8_plan.hpp"
 #include "aof_exposure_step.hpp"
 #include "aof_internal.hpp"
+#include "aof_lane8_plan.hpp"
 #include "aof_mavlink.hpp"
 #include "aof_small_plan.hpp"
+#include "aof_xcd_remap.hpp"
 #include "optical_flow_rad.hpp"
 
 static unsigned rng_state = 777u;
@@ -246,6 +250,69 @@ static int print_small_plans(const char *path)
     return cases;
 }
 
+// (d5) lane8_flat_plan on a case file, one case per line: nb n_pairs pair_stride w h prune fused rng votes_memory votes_fault
+// votes_stride (votes_memory -1: no VoteMem at all) capacity slice tile search.  One line of fields per case, in the order of
+// lane8_plan_ref.PLAN_FIELDS.
+static int print_lane8_plans(const char *path)
+{
+    std::FILE *f = std::fopen(path, "r");
+    if (!f) return -1;
+    int cases = 0;
+    long long nb, n_pairs, stride, w, h, prune, fused, rng, mem, fault, vstride, capacity, slice, tile, search;
+    static uint32_t somewhere[1];   // (vote memory and fault word: only looked at for being there)
+    while (std::fscanf(f, "%lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld", &nb, &n_pairs, &stride, &w, &h, &prune, &fused,
+                       &rng, &mem, &fault, &vstride, &capacity, &slice, &tile, &search) == 15) {
+        aof::SearchArgs a = {};
+        a.pair_stride = (int64_t)stride;
+        a.w = (int32_t)w; a.h = (int32_t)h;
+        a.tile = (int32_t)tile; a.search = (int32_t)search;
+        a.grid = {4, 4, 8, 8, (int32_t)nb, nb > 0 ? 1 : 0};
+        a.n_pairs = (int64_t)n_pairs;
+        a.hist_range = (int32_t)rng;
+        a.prune = (int32_t)prune;
+        aof::VoteMem vm = {mem > 0 ? somewhere : nullptr, (uint32_t)vstride, fault > 0 ? somewhere : nullptr, 0};
+        const aof::Lane8FlatPlan p = aof::lane8_flat_plan(a, fused != 0, mem < 0 ? nullptr : &vm, (int64_t)capacity, (int64_t)slice);
+        std::printf("lane8 plan: %d %d %d %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %d %d %lld %lld %lld %d %lld %d %d %u %u\n", p.supported, p.votes,
+                    p.prune_large, (long long)p.chunks_all, (long long)p.per, (long long)p.slices, (long long)p.done, (long long)p.pairs,
+                    (long long)p.frame_off, (long long)p.block_off, (long long)p.pred_off, (long long)p.sums_off, (long long)p.items, p.kind,
+                    p.threads, (long long)p.wgs, (long long)p.finalisers, (long long)p.grid, p.last_live, (long long)p.chunks, p.spw, p.last_chunks,
+                    p.stride, p.expected);
+        cases++;
+    }
+    std::fclose(f);
+    return cases;
+}
+
+// (d6) xcd_remap, the function the kernels run: a permutation of [0, total) for every total up to 4096 (every logical id hit
+// once), and printed at the probes of the case file's second kind of line for the test to hold to the model: "total b".
+static int check_xcd_remap()
+{
+    static uint8_t hit[4096];
+    for (uint32_t total = 1; total <= 4096u; total++) {
+        std::memset(hit, 0, total);
+        for (uint32_t b = 0; b < total; b++) {
+            const uint32_t wg = aof::xcd_remap(b, total);
+            if (wg >= total || hit[wg]++) return -1;
+            if (b >= 8 && wg != aof::xcd_remap(b - 8, total) + 1) return -1;   // an XCD's logical ids are contiguous
+        }
+    }
+    return 4096;
+}
+
+static int print_xcd_probes(const char *path)
+{
+    std::FILE *f = std::fopen(path, "r");
+    if (!f) return -1;
+    int probes = 0;
+    unsigned long long total, b;
+    while (std::fscanf(f, "%llu %llu", &total, &b) == 2) {
+        std::printf("xcd remap: %u\n", aof::xcd_remap((uint32_t)b, (uint32_t)total));
+        probes++;
+    }
+    std::fclose(f);
+    return probes;
+}
+
 // (e) fastdiv_make: the kernels' fast_div (aof_device.hpp) restated -- the high half of the product, the sum and the shift
 // in 32 bits -- against n / d.  Divisors: every d up to 4096 (grid widths, blocks per pair) and every multiple of 64 up to
 // 2^20 (units per pair); numerators: all below 2^16, and around 65 multiples of d spread up to the top of the 31 bits
@@ -360,6 +427,12 @@ int main(int argc, char **argv)
         const int small = print_small_plans(argv[4]);
         if (small < 0) return 18;
         std::printf("host selftest: small plan: %d cases\n", small);
+    }
+    if (argc > 6) {
+        const int lane8 = print_lane8_plans(argv[5]), totals = check_xcd_remap(), probes = print_xcd_probes(argv[6]);
+        if (lane8 < 0 || totals < 0 || probes < 0) return 19;
+        std::printf("host selftest: lane8 plan: %d cases\nhost selftest: xcd_remap: a permutation for every total up to %d, %d probes\n", lane8,
+                    totals, probes);
     }
     std::printf("host selftest: %d valid parameter sets, %d rejected\n", valid, bad);
     return valid > 1000 ? 0 : 11;

@@ -6,12 +6,15 @@ segment plan (csrc/aof_cols8_plan.hpp: cols_plan_make) on every case of tests/co
 the Python model; the plans of the two coarse passes (csrc/aof_coarse_plan.hpp: coarse_plan_make, pyramid_plan_make) on
 every case of tests/coarse_plan_ref.py and a list of extreme shapes, the same way; the plans of the small-pair kernels
 (csrc/aof_small_plan.hpp: small_plan_make, lane8_group_plan) on every case of tests/small_plan_ref.py and its list of
-extreme shapes, likewise; fastdiv_make against the division it replaces."""
+extreme shapes, likewise; the plan of the flat lane-per-block launches (csrc/aof_lane8_plan.hpp: lane8_flat_plan) on every case of
+tests/lane8_plan_ref.py, likewise, with xcd_remap (csrc/aof_xcd_remap.hpp, the text the kernels run) a permutation for every
+total up to 4 096 and equal to the model's at every probe; fastdiv_make against the division it replaces."""
 import os
 import subprocess
 
 import coarse_plan_ref as coarse
 import cols_plan_ref as ref
+import lane8_plan_ref as lane8
 import small_plan_ref as small
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,8 +40,12 @@ def test_host_logic_is_clean_under_asan_ubsan(tmp_path):
     small_cases = small.CPU_CASES + small.GPU_CASES + small.PLAN_ONLY
     small_listing = tmp_path / "small_plan_cases.txt"
     small_listing.write_text("".join(small.selftest_line(c) + "\n" for c in small_cases))
-    r = subprocess.run([str(exe), str(listing), str(coarse_listing), str(pyramid_listing), str(small_listing)], capture_output=True, text=True,
-                       timeout=300)
+    lane8_listing, xcd_listing = tmp_path / "lane8_plan_cases.txt", tmp_path / "xcd_probes.txt"
+    lane8_listing.write_text("".join(lane8.selftest_line(c) + "\n" for c in lane8.CASES))
+    xcd_probes = lane8.xcd_probes()
+    xcd_listing.write_text("".join(f"{total} {b}\n" for total, b in xcd_probes))
+    r = subprocess.run([str(exe), str(listing), str(coarse_listing), str(pyramid_listing), str(small_listing), str(lane8_listing),
+                        str(xcd_listing)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, f"rc={r.returncode}\n{r.stdout}{r.stderr}"
     assert "valid parameter sets" in r.stdout
     assert "packer: 4012 frames equal to the facade's, lengths 52 and 56" in r.stdout
@@ -81,3 +88,15 @@ def test_host_logic_is_clean_under_asan_ubsan(tmp_path):
     # every verdict occurs, and the grouped plan both applies and does not
     assert {small.plans_of(c)[0]["verdict"] for c in small_cases} == set(small.VERDICTS)
     assert {small.plans_of(c)[1]["ppw"] > 0 for c in small_cases} == {True, False}
+    # lane8_flat_plan == the model, on every case of every list; xcd_remap == the model's at every probe
+    assert f"lane8 plan: {len(lane8.CASES)} cases" in r.stdout and len(lane8.CASES) >= 85 and len(lane8.PLAN_ONLY) >= 35
+    plans = [line.split()[2:] for line in r.stdout.splitlines() if line.startswith("lane8 plan: ")]
+    assert len(plans) == len(lane8.CASES)
+    for c, got in zip(lane8.CASES, plans):
+        want = lane8.plan_fields(lane8.plan_of(c))
+        assert len(got) == len(want) == len(lane8.PLAN_FIELDS)
+        diff = {name: (int(g), w) for name, g, w in zip(lane8.PLAN_FIELDS, got, want) if int(g) != w}
+        assert not diff, (c["id"], diff)
+    assert f"xcd_remap: a permutation for every total up to 4096, {len(xcd_probes)} probes" in r.stdout and len(xcd_probes) >= 1000
+    remapped = [int(line.split()[2]) for line in r.stdout.splitlines() if line.startswith("xcd remap: ")]
+    assert remapped == [int(lane8.xcd_remap(b, total)) for total, b in xcd_probes]
