@@ -1291,21 +1291,28 @@ class FlowEngine:
                                                    samples.data_ptr(), counts.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
         return samples, counts
 
+    def _bind_bank_table(self, setter, keep, tensor, n_streams, item, *extra):
+        """The one body of the four set_bank_* methods: `setter` of the library on `tensor` (None: unbind) for n_streams
+        streams (None: as many as the tensor holds), `item` bytes per stream -- records (item > 1) come in whole records and
+        for at least one stream, byte arrays only have to hold n_streams --; `extra`: further arguments of the setter (zeros
+        when unbinding).  The tensor is kept alive in attribute `keep` for as long as it is bound."""
+        if tensor is None:
+            self._check(setter(self._ctx, None, 0, *(0 for _ in extra)))
+            setattr(self, keep, None)
+            return
+        import torch
+        assert tensor.dtype == torch.uint8 and tensor.is_contiguous() and tensor.numel() % item == 0
+        n = tensor.numel() // item if n_streams is None else int(n_streams)
+        assert (item == 1 or 1 <= n) and n <= tensor.numel() // item
+        self._check(setter(self._ctx, tensor.data_ptr(), n, *extra))
+        setattr(self, keep, tensor)
+
     def set_bank_streams(self, streams=None, n_streams=None):
         """aof_set_bank_streams: binds a uint8 CUDA tensor of S * 32 bytes (``aof_bank_stream`` records, BANK_STREAM_DTYPE;
         16-byte aligned) to the context, or with None unbinds.  n_streams: S, where the tensor holds more than S records.  While it is bound every push and IMU call of S streams
         takes focal lengths, output rate, time offset and MAVLink identity of stream s from record s; the kernels read
         it when they run, so the tensor must stay alive and may be rewritten between ticks.  Enqueues nothing."""
-        if streams is None:
-            self._check(lib.aof_set_bank_streams(self._ctx, None, 0))
-            self._bank_streams = None
-            return
-        import torch
-        assert streams.dtype == torch.uint8 and streams.is_contiguous() and streams.numel() % 32 == 0
-        n = streams.numel() // 32 if n_streams is None else int(n_streams)
-        assert 1 <= n <= streams.numel() // 32
-        self._check(lib.aof_set_bank_streams(self._ctx, streams.data_ptr(), n))
-        self._bank_streams = streams   # (kept alive for as long as it is bound)
+        self._bind_bank_table(lib.aof_set_bank_streams, "_bank_streams", streams, n_streams, 32)
 
     def set_bank_sensors(self, sensors=None, n_streams=None, camera_bytes=0):
         """aof_set_bank_sensors: binds a uint8 CUDA tensor of S * 32 bytes (``aof_bank_sensor`` records, BANK_SENSOR_DTYPE;
@@ -1313,32 +1320,14 @@ class FlowEngine:
         camera_bytes: the bytes readable from the camera tensor of the pushes.  While it is bound every camera push of S
         streams takes the place, row pitch, size and crop origin of stream s's sensor frame from record s; the kernels
         read it when they run, so the tensor must stay alive and may be rewritten between ticks.  Enqueues nothing."""
-        if sensors is None:
-            self._check(lib.aof_set_bank_sensors(self._ctx, None, 0, 0))
-            self._bank_sensors = None
-            return
-        import torch
-        assert sensors.dtype == torch.uint8 and sensors.is_contiguous() and sensors.numel() % 32 == 0
-        n = sensors.numel() // 32 if n_streams is None else int(n_streams)
-        assert 1 <= n <= sensors.numel() // 32
-        self._check(lib.aof_set_bank_sensors(self._ctx, sensors.data_ptr(), n, int(camera_bytes)))
-        self._bank_sensors = sensors   # (kept alive for as long as it is bound)
+        self._bind_bank_table(lib.aof_set_bank_sensors, "_bank_sensors", sensors, n_streams, 32, int(camera_bytes))
 
     def set_bank_pixel_formats(self, formats=None, n_streams=None):
         """aof_set_bank_pixel_formats: binds a uint8 CUDA tensor of S pixel formats (PIXEL_GREY8, PIXEL_LUMA16_LO,
         PIXEL_LUMA16_HI; any alignment) to the context, or with None unbinds.  n_streams: S, where the tensor holds more.
         Used by the camera pushes next to bound sensor records (set_bank_sensors): stream s's crop then comes from pixels
         of one or two bytes.  The kernels read it when they run: keep it alive; it may be rewritten between ticks."""
-        if formats is None:
-            self._check(lib.aof_set_bank_pixel_formats(self._ctx, None, 0))
-            self._bank_formats = None
-            return
-        import torch
-        assert formats.dtype == torch.uint8 and formats.is_contiguous()
-        n = formats.numel() if n_streams is None else int(n_streams)
-        assert n <= formats.numel()
-        self._check(lib.aof_set_bank_pixel_formats(self._ctx, formats.data_ptr(), n))
-        self._bank_formats = formats   # (kept alive for as long as it is bound)
+        self._bind_bank_table(lib.aof_set_bank_pixel_formats, "_bank_formats", formats, n_streams, 1)
 
     def set_bank_binning(self, bins=None, n_streams=None):
         """aof_set_bank_binning: binds a uint8 CUDA tensor of S bins (1, 2 or 4; any alignment) to the context, or with None
@@ -1346,16 +1335,7 @@ class FlowEngine:
         (set_bank_sensors): a pixel of stream s's crop is then the rounded mean of bin x bin sensor pixels.  The focal
         length stays the caller's (focal / bin through set_bank_streams).  The kernels read it when they run: keep it alive;
         it may be rewritten between ticks."""
-        if bins is None:
-            self._check(lib.aof_set_bank_binning(self._ctx, None, 0))
-            self._bank_bins = None
-            return
-        import torch
-        assert bins.dtype == torch.uint8 and bins.is_contiguous()
-        n = bins.numel() if n_streams is None else int(n_streams)
-        assert n <= bins.numel()
-        self._check(lib.aof_set_bank_binning(self._ctx, bins.data_ptr(), n))
-        self._bank_bins = bins   # (kept alive for as long as it is bound)
+        self._bind_bank_table(lib.aof_set_bank_binning, "_bank_bins", bins, n_streams, 1)
 
     def set_bank_path(self, path=0):
         """0: the library chooses between the one-launch tick kernel and the composed path, 1: the tick kernel where

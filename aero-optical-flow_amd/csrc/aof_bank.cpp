@@ -9,6 +9,7 @@
 #include <cstring>
 
 #include "aof_bank_sensor_rule.hpp"
+#include "aof_bank_tables.hpp"
 #include "aof_internal.hpp"
 
 using namespace aof;
@@ -256,34 +257,10 @@ int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank
         if (!aligned(p.exposure, 4) || !aligned(p.derotated, 4))
             return ctx_fail(ctx, -EINVAL, "bank camera: exposure records and de-rotated pairs must be 4-byte aligned");
     }
-    // a bound per-stream array (aof_set_bank_streams) is for one stream count: the kernels index it by the stream
-    int32_t bound = 0;
-    const aof_bank_stream *d_streams = bank_streams(ctx, &bound);
-    if (d_streams && bound != bp->n_streams)
-        return ctx_fail(ctx, -EINVAL, "bank: n_streams differs from the array bound with aof_set_bank_streams");
-    // likewise the sensor records of the camera forms (aof_set_bank_sensors); a round's base, k * round_stride, must be
-    // a number the kernels can form
-    int32_t bound_sensors = 0;
-    uint64_t camera_bytes = 0;
-    const aof_bank_sensor *d_sensors = p.camera ? bank_sensors(ctx, &bound_sensors, &camera_bytes) : nullptr;
-    if (d_sensors && bound_sensors != bp->n_streams)
-        return ctx_fail(ctx, -EINVAL, "bank: n_streams differs from the array bound with aof_set_bank_sensors");
-    if (d_sensors && round_stride > INT64_MAX / AOF_BANK_BURST_MAX)
-        return ctx_fail(ctx, -EINVAL, "bank burst: round_stride too large for sensor records");
-    // and the pixel formats that go with the records (aof_set_bank_pixel_formats): of the camera forms, with records only
-    int32_t bound_formats = 0;
-    const uint8_t *d_formats = p.camera ? bank_pixel_formats(ctx, &bound_formats) : nullptr;
-    if (d_formats && !d_sensors)
-        return ctx_fail(ctx, -EINVAL, "bank: pixel formats are bound (aof_set_bank_pixel_formats) without sensor records");
-    if (d_formats && bound_formats != bp->n_streams)
-        return ctx_fail(ctx, -EINVAL, "bank: n_streams differs from the array bound with aof_set_bank_pixel_formats");
-    // and the binning (aof_set_bank_binning): likewise, with any format or none
-    int32_t bound_bins = 0;
-    const uint8_t *d_bins = p.camera ? bank_binning(ctx, &bound_bins) : nullptr;
-    if (d_bins && !d_sensors)
-        return ctx_fail(ctx, -EINVAL, "bank: a binning is bound (aof_set_bank_binning) without sensor records");
-    if (d_bins && bound_bins != bp->n_streams)
-        return ctx_fail(ctx, -EINVAL, "bank: n_streams differs from the array bound with aof_set_bank_binning");
+    // the bound per-stream arrays this push uses (aof_bank_tables.hpp)
+    BankTablesUsed tables;
+    if (const char *what = bank_tables_for_push(bank_tables(ctx), bp->n_streams, p.camera, round_stride, &tables))
+        return ctx_fail(ctx, -EINVAL, what);
     // before the first launch: a faulted or wedged context, or a thread on another device, must not touch the bank
     if ((rc = precheck(ctx))) return rc;
 
@@ -293,10 +270,10 @@ int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank
     // what the flow kernels pair with the stored frames: the caller's frames, or the crops in the staging region
     const uint8_t *cur = p.camera ? staging : p.src;
     BankArgs a = bank_args(bp, L, bank, cur, p.time_us, p.burst ? nullptr : p.select, p.gyro, p.records, p.mavlink, p.mavlink_len,
-                           d_streams);
+                           tables.streams);
     if (p.camera) camera_args(&a, p.cam, p.src, hist, p.exposure, p.derotated);
     // (bound: the kernels that take this argument read the crop's place, pitch and origin from record s instead)
-    const BankSensors sen = {d_sensors, camera_bytes, 0, d_formats, d_bins};
+    const BankSensors sen = bank_sensors_of_round(tables, 0);
     aof_flow *flows = reinterpret_cast<aof_flow *>(bank + L.flows);
     const BankBurst b = {p.burst ? p.rounds->n_rounds : 1, round_stride, p.burst ? p.select : nullptr};
 
@@ -317,20 +294,28 @@ int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank
     // first-frame streams are cropped, computed and ignored --; then the tails and the masked copy
     for (int k = 0; k < b.n_rounds; k++) {
         const uint8_t *src = p.src + (int64_t)k * round_stride;
+        const uint64_t base = (uint64_t)k * (uint64_t)round_stride;
         BankArgs r = a;   // (a tick keeps its `active` mask: round_args drops it for the burst's `count`)
         if (p.burst) r = round_args(a, k, p.camera ? staging : src);
         if (p.camera) {
             r.cam.camera = src;
-            const IngestSensors crop = {d_sensors, (uint64_t)k * (uint64_t)round_stride, camera_bytes, nullptr, d_formats, d_bins};
-            if (launch_ingest(p.cam->ingest, src, a.cam.camera_stride, bp->n_streams, staging, L.stride, p.exposure ? hist : nullptr, stream, crop))
+            if (launch_ingest(p.cam->ingest, src, a.cam.camera_stride, bp->n_streams, staging, L.stride, p.exposure ? hist : nullptr, stream,
+                              ingest_sensors_of_round(tables, base)))
                 return ctx_fail(ctx, -EIO, "bank camera ingest launch failed");
         }
         rc = aof_flow_batch_device(ctx, a.bank_frames, r.frames, L.stride, bp->n_streams, nullptr, nullptr, flows,
                                    bank + L.pub.scratch, L.flow_ws_bytes, stream);
         if (rc) return rc;
-        const BankSensors round_sen = {d_sensors, camera_bytes, (uint64_t)k * (uint64_t)round_stride, d_formats, d_bins};
-        if (launch_bank_commit(r, stream, b.count, b.count ? k : 0, round_sen)) return ctx_fail(ctx, -EIO, "bank commit launch failed");
+        if (launch_bank_commit(r, stream, b.count, b.count ? k : 0, bank_sensors_of_round(tables, base))) return ctx_fail(ctx, -EIO, "bank commit launch failed");
     }
+    return 0;
+}
+
+// The four binding calls: the rules are bank_tables_bind's (aof_bank_tables.hpp); a refused call leaves the binding as it was.
+int bind_table(aof_ctx *ctx, BankTable which, const void *array, int32_t n_streams, uint64_t camera_bytes = 0)
+{
+    if (!ctx) return -EINVAL;
+    if (const char *what = bank_tables_bind(&bank_tables(ctx), which, array, n_streams, camera_bytes)) return ctx_fail(ctx, -EINVAL, what);
     return 0;
 }
 
@@ -368,37 +353,22 @@ int aof_bank_stream_from_params(const aof_bank_params *bp, aof_bank_stream *out)
 
 int aof_set_bank_streams(aof_ctx *ctx, const aof_bank_stream *d_streams, int32_t n_streams)
 {
-    if (!ctx) return -EINVAL;
-    if (d_streams && n_streams < 1) return ctx_fail(ctx, -EINVAL, "bank streams: an array needs n_streams >= 1");
-    if (!aligned(d_streams, 16)) return ctx_fail(ctx, -EINVAL, "bank streams: the array must be 16-byte aligned");
-    set_bank_streams(ctx, d_streams, n_streams);
-    return 0;
+    return bind_table(ctx, kBankStreams, d_streams, n_streams);
 }
 
 int aof_set_bank_sensors(aof_ctx *ctx, const aof_bank_sensor *d_sensors, int32_t n_streams, uint64_t camera_bytes)
 {
-    if (!ctx) return -EINVAL;
-    if (d_sensors && n_streams < 1) return ctx_fail(ctx, -EINVAL, "bank sensors: an array needs n_streams >= 1");
-    if (!aligned(d_sensors, 16)) return ctx_fail(ctx, -EINVAL, "bank sensors: the array must be 16-byte aligned");
-    if (d_sensors && camera_bytes == 0) return ctx_fail(ctx, -EINVAL, "bank sensors: an array needs camera_bytes > 0");
-    set_bank_sensors(ctx, d_sensors, n_streams, camera_bytes);
-    return 0;
+    return bind_table(ctx, kBankSensors, d_sensors, n_streams, camera_bytes);
 }
 
 int aof_set_bank_pixel_formats(aof_ctx *ctx, const uint8_t *d_formats, int32_t n_streams)
 {
-    if (!ctx) return -EINVAL;
-    if (d_formats && n_streams < 1) return ctx_fail(ctx, -EINVAL, "bank pixel formats: an array needs n_streams >= 1");
-    set_bank_pixel_formats(ctx, d_formats, n_streams);
-    return 0;
+    return bind_table(ctx, kBankFormats, d_formats, n_streams);
 }
 
 int aof_set_bank_binning(aof_ctx *ctx, const uint8_t *d_bins, int32_t n_streams)
 {
-    if (!ctx) return -EINVAL;
-    if (d_bins && n_streams < 1) return ctx_fail(ctx, -EINVAL, "bank binning: an array needs n_streams >= 1");
-    set_bank_binning(ctx, d_bins, n_streams);
-    return 0;
+    return bind_table(ctx, kBankBins, d_bins, n_streams);
 }
 
 int aof_bank_sensor_centred_binned(const aof_params *p, uint64_t offset, int32_t pitch, int32_t width, int32_t height, uint8_t format,
@@ -469,8 +439,8 @@ int aof_ingest_sensors_binned_device(int32_t crop_width, int32_t crop_height, co
     if (d_cropped && cropped_stride < (int64_t)crop_width * crop_height && n_frames > 1) return -EINVAL;
     if (n_frames * ((crop_height + 15) / 16) > 0x7FFFFFFF) return -EINVAL;
     const aof_ingest_params g = {crop_width, crop_height, crop_width, crop_height};   // (the sensor size: the records')
-    const IngestSensors sen = {d_sensors, 0, camera_bytes, d_ok, d_formats, d_bins};
-    return launch_ingest(g, d_camera, 0, n_frames, d_cropped, cropped_stride, d_hist, stream, sen) ? -EIO : 0;
+    const BankTablesUsed tables = {nullptr, d_sensors, camera_bytes, d_formats, d_bins};
+    return launch_ingest(g, d_camera, 0, n_frames, d_cropped, cropped_stride, d_hist, stream, ingest_sensors_of_round(tables, 0, d_ok)) ? -EIO : 0;
 }
 
 int aof_ingest_sensor_formats_device(int32_t crop_width, int32_t crop_height, const uint8_t *d_camera, uint64_t camera_bytes,

@@ -1,0 +1,114 @@
+// The stream bank's bound per-stream tables (include/aof.h: aof_set_bank_streams, aof_set_bank_sensors,
+// aof_set_bank_pixel_formats, aof_set_bank_binning): each a caller-owned device array for S streams, bound to the context
+// and read by the kernels when they run.  One record of what is bound (BankTables, a member of aof_ctx), and the rules
+// over it as plain functions that know no context: what a binding call accepts, which tables a push or an IMU call of
+// n_streams uses and why it is refused, and the kernels' sensor arguments of one round.  Host only: a CPU program can
+// call all of it (tests/native/host_selftest.cpp).  A further per-stream array is one more BankTable and one more line
+// in each rule.
+#pragma once
+
+#include <cstdint>
+
+#include "aof_internal.hpp"
+
+namespace aof {
+
+enum BankTable { kBankStreams, kBankSensors, kBankFormats, kBankBins, kBankTableCount };
+
+struct BankTables {
+    struct Bound {
+        const void *array;     // device memory of the caller's, or nullptr: nothing bound
+        int32_t n_streams;     // how many streams it is for (0 with nothing bound)
+    } table[kBankTableCount];
+    uint64_t camera_bytes;     // with sensor records: bytes the caller guarantees readable from the d_camera of its pushes
+};
+
+inline bool operator==(const BankTables &a, const BankTables &b)
+{
+    for (int t = 0; t < kBankTableCount; t++)
+        if (a.table[t].array != b.table[t].array || a.table[t].n_streams != b.table[t].n_streams) return false;
+    return a.camera_bytes == b.camera_bytes;
+}
+
+// The binding calls: nullptr, or why the call is refused -- the binding is then as it was.  A null array unbinds.
+// camera_bytes: of the sensor records, not looked at otherwise.
+inline const char *bank_tables_bind(BankTables *b, BankTable which, const void *array, int32_t n_streams, uint64_t camera_bytes = 0)
+{
+    static const struct { const char *no_streams, *misaligned; } kRefusal[kBankTableCount] = {
+        {"bank streams: an array needs n_streams >= 1", "bank streams: the array must be 16-byte aligned"},
+        {"bank sensors: an array needs n_streams >= 1", "bank sensors: the array must be 16-byte aligned"},
+        {"bank pixel formats: an array needs n_streams >= 1", nullptr},   // (bytes: any alignment)
+        {"bank binning: an array needs n_streams >= 1", nullptr},
+    };
+    if (array && n_streams < 1) return kRefusal[which].no_streams;
+    if (kRefusal[which].misaligned && !aligned(array, 16)) return kRefusal[which].misaligned;
+    if (which == kBankSensors) {
+        if (array && camera_bytes == 0) return "bank sensors: an array needs camera_bytes > 0";
+        b->camera_bytes = array ? camera_bytes : 0;
+    }
+    b->table[which].array = array;
+    b->table[which].n_streams = array ? n_streams : 0;
+    return nullptr;
+}
+
+// The tables one call uses: what is bound, for the call's stream count.
+struct BankTablesUsed {
+    const aof_bank_stream *streams;
+    const aof_bank_sensor *sensors;
+    uint64_t camera_bytes;
+    const uint8_t *formats, *bins;
+};
+
+// A bound array is for one stream count: the kernels index it by the stream.
+inline bool bank_table_differs(const BankTables &b, BankTable which, int32_t n_streams)
+{
+    return b.table[which].array && b.table[which].n_streams != n_streams;
+}
+
+// A push of n_streams (camera: on sensor frames; round_stride: of a burst, else 0): nullptr and the tables it uses, or
+// why it is refused.  The sensor records, the pixel formats and the binning belong to the camera forms alone: a push
+// of pre-cropped frames does not look at them.  The formats and the binning go with sensor records only, and a round's
+// base, k * round_stride, must be a number the kernels can form.
+inline const char *bank_tables_for_push(const BankTables &b, int32_t n_streams, bool camera, int64_t round_stride, BankTablesUsed *out)
+{
+    BankTablesUsed u = {};
+    if (bank_table_differs(b, kBankStreams, n_streams)) return "bank: n_streams differs from the array bound with aof_set_bank_streams";
+    u.streams = static_cast<const aof_bank_stream *>(b.table[kBankStreams].array);
+    if (camera) {
+        if (bank_table_differs(b, kBankSensors, n_streams)) return "bank: n_streams differs from the array bound with aof_set_bank_sensors";
+        u.sensors = static_cast<const aof_bank_sensor *>(b.table[kBankSensors].array);
+        u.camera_bytes = b.camera_bytes;
+        if (u.sensors && round_stride > INT64_MAX / AOF_BANK_BURST_MAX) return "bank burst: round_stride too large for sensor records";
+        u.formats = static_cast<const uint8_t *>(b.table[kBankFormats].array);
+        if (u.formats && !u.sensors) return "bank: pixel formats are bound (aof_set_bank_pixel_formats) without sensor records";
+        if (bank_table_differs(b, kBankFormats, n_streams)) return "bank: n_streams differs from the array bound with aof_set_bank_pixel_formats";
+        u.bins = static_cast<const uint8_t *>(b.table[kBankBins].array);
+        if (u.bins && !u.sensors) return "bank: a binning is bound (aof_set_bank_binning) without sensor records";
+        if (bank_table_differs(b, kBankBins, n_streams)) return "bank: n_streams differs from the array bound with aof_set_bank_binning";
+    }
+    *out = u;
+    return nullptr;
+}
+
+// The IMU call of n_streams: the per-stream records give every stream its own identity; nothing else is looked at.
+inline const char *bank_tables_for_imu(const BankTables &b, int32_t n_streams, const aof_bank_stream **streams)
+{
+    if (bank_table_differs(b, kBankStreams, n_streams)) return "imu: n_streams differs from the array bound with aof_set_bank_streams";
+    *streams = static_cast<const aof_bank_stream *>(b.table[kBankStreams].array);
+    return nullptr;
+}
+
+// The kernels' sensor arguments of one round (base: bytes between the caller's d_camera and the round's first frame;
+// sensors == nullptr: the kernels without the argument).
+inline BankSensors bank_sensors_of_round(const BankTablesUsed &u, uint64_t base)
+{
+    return BankSensors{u.sensors, u.camera_bytes, base, u.formats, u.bins};
+}
+
+// ok: u8 per frame or nullptr, 1 where the record let the frame be read
+inline IngestSensors ingest_sensors_of_round(const BankTablesUsed &u, uint64_t base, uint8_t *ok = nullptr)
+{
+    return IngestSensors{u.sensors, base, u.camera_bytes, ok, u.formats, u.bins};
+}
+
+}  // namespace aof

@@ -418,48 +418,7 @@ bool plan_small_batch(const aof_ctx *ctx, const uint8_t *prev, const uint8_t *cu
 
 int bank_path(const aof_ctx *ctx) { return ctx->bank_path; }
 void set_bank_path(aof_ctx *ctx, int path) { ctx->bank_path = path; }
-const aof_bank_stream *bank_streams(const aof_ctx *ctx, int32_t *n_streams)
-{
-    *n_streams = ctx->bank_streams_n;
-    return ctx->bank_streams;
-}
-void set_bank_streams(aof_ctx *ctx, const aof_bank_stream *d_streams, int32_t n_streams)
-{
-    ctx->bank_streams = d_streams;
-    ctx->bank_streams_n = d_streams ? n_streams : 0;
-}
-const aof_bank_sensor *bank_sensors(const aof_ctx *ctx, int32_t *n_streams, uint64_t *camera_bytes)
-{
-    *n_streams = ctx->bank_sensors_n;
-    *camera_bytes = ctx->bank_camera_bytes;
-    return ctx->bank_sensors;
-}
-void set_bank_sensors(aof_ctx *ctx, const aof_bank_sensor *d_sensors, int32_t n_streams, uint64_t camera_bytes)
-{
-    ctx->bank_sensors = d_sensors;
-    ctx->bank_sensors_n = d_sensors ? n_streams : 0;
-    ctx->bank_camera_bytes = d_sensors ? camera_bytes : 0;
-}
-const uint8_t *bank_pixel_formats(const aof_ctx *ctx, int32_t *n_streams)
-{
-    *n_streams = ctx->bank_formats_n;
-    return ctx->bank_formats;
-}
-void set_bank_pixel_formats(aof_ctx *ctx, const uint8_t *d_formats, int32_t n_streams)
-{
-    ctx->bank_formats = d_formats;
-    ctx->bank_formats_n = d_formats ? n_streams : 0;
-}
-const uint8_t *bank_binning(const aof_ctx *ctx, int32_t *n_streams)
-{
-    *n_streams = ctx->bank_bins_n;
-    return ctx->bank_bins;
-}
-void set_bank_binning(aof_ctx *ctx, const uint8_t *d_bins, int32_t n_streams)
-{
-    ctx->bank_bins = d_bins;
-    ctx->bank_bins_n = d_bins ? n_streams : 0;
-}
+BankTables &bank_tables(aof_ctx *ctx) { return ctx->bank; }
 
 // Would a sequence-view call (frames viewed twice, n_pairs = frames - 1) run K1 as a pass of its own?  The sequence
 // pipeline asks, because its ingest kernel can leave K1's outputs (pixel sums at ws + L.sums, one level-1 frame per

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 #include <chrono>
+#include "aof_bank_tables.hpp"
 #include "aof_internal.hpp"
 
 namespace aof {
@@ -127,15 +128,7 @@ struct aof_ctx {
     bool force_generic;
     bool split_coarse;          // run K1 / level-1 search / level-1 reduce as separate kernels
     int bank_path;              // aof_set_bank_path: 0 the library chooses, 1 the one-launch tick kernel, 2 the composed path
-    const aof_bank_stream *bank_streams;   // aof_set_bank_streams: the caller's per-stream records (device memory), or nullptr
-    int32_t bank_streams_n;     // how many streams they are for
-    const aof_bank_sensor *bank_sensors;   // aof_set_bank_sensors: the caller's per-stream sensor records (device memory), or nullptr
-    int32_t bank_sensors_n;     // how many streams they are for
-    uint64_t bank_camera_bytes; // bytes the caller guarantees readable from the d_camera of its pushes
-    const uint8_t *bank_formats;   // aof_set_bank_pixel_formats: the caller's per-stream pixel formats (device memory), or nullptr
-    int32_t bank_formats_n;     // how many streams they are for
-    const uint8_t *bank_bins;   // aof_set_bank_binning: the caller's per-stream binning (device memory), or nullptr
-    int32_t bank_bins_n;        // how many streams it is for
+    aof::BankTables bank;       // aof_set_bank_streams / _sensors / _pixel_formats / _binning: the caller's per-stream arrays (aof_bank_tables.hpp)
     bool graph_disabled;        // per-call graphs switched off, or a capture failed once: stay on the plain path
     bool capturing;             // a per-call graph is being captured (no event timing)
     bool wedged;                // a bounded wait for the device ran out: every later call fails, destroy frees nothing

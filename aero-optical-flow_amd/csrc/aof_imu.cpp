@@ -55,10 +55,8 @@ int aof_bank_imu_device(aof_ctx *ctx, const aof_imu_params *ip, const aof_imu_sa
     if (const char *what = bad_call(ip, d_samples, d_time_us, d_records_in, d_state, d_records_out, d_mavlink, d_mavlink_len))
         return ctx_fail(ctx, -EINVAL, what);
     // a bound per-stream array (aof_set_bank_streams) gives every stream its own identity; it is for one stream count
-    int32_t bound = 0;
-    const aof_bank_stream *d_streams = bank_streams(ctx, &bound);
-    if (d_streams && bound != ip->n_streams)
-        return ctx_fail(ctx, -EINVAL, "imu: n_streams differs from the array bound with aof_set_bank_streams");
+    const aof_bank_stream *d_streams = nullptr;
+    if (const char *what = bank_tables_for_imu(ctx->bank, ip->n_streams, &d_streams)) return ctx_fail(ctx, -EINVAL, what);
     if (const int rc = precheck(ctx)) return rc;
 
     ImuArgs a;

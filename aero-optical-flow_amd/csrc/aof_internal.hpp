@@ -433,18 +433,8 @@ bool plan_small_batch(const aof_ctx *ctx, const uint8_t *prev, const uint8_t *cu
                       void *d_workspace, SmallArgs *sm);
 int bank_path(const aof_ctx *ctx);            // (aof_batch.cpp) aof_set_bank_path's value
 void set_bank_path(aof_ctx *ctx, int path);
-// (aof_batch.cpp) aof_set_bank_streams' binding: the array (nullptr: none) and its stream count
-const aof_bank_stream *bank_streams(const aof_ctx *ctx, int32_t *n_streams);
-void set_bank_streams(aof_ctx *ctx, const aof_bank_stream *d_streams, int32_t n_streams);
-// (aof_batch.cpp) aof_set_bank_sensors' binding: the array (nullptr: none), its stream count and its camera_bytes
-const aof_bank_sensor *bank_sensors(const aof_ctx *ctx, int32_t *n_streams, uint64_t *camera_bytes);
-void set_bank_sensors(aof_ctx *ctx, const aof_bank_sensor *d_sensors, int32_t n_streams, uint64_t camera_bytes);
-// (aof_batch.cpp) aof_set_bank_pixel_formats' binding: the array (nullptr: none) and its stream count
-const uint8_t *bank_pixel_formats(const aof_ctx *ctx, int32_t *n_streams);
-void set_bank_pixel_formats(aof_ctx *ctx, const uint8_t *d_formats, int32_t n_streams);
-// (aof_batch.cpp) aof_set_bank_binning's binding: the array (nullptr: none) and its stream count
-const uint8_t *bank_binning(const aof_ctx *ctx, int32_t *n_streams);
-void set_bank_binning(aof_ctx *ctx, const uint8_t *d_bins, int32_t n_streams);
+struct BankTables;                            // (aof_bank_tables.hpp) what the four aof_set_bank_* calls have bound
+BankTables &bank_tables(aof_ctx *ctx);        // (aof_batch.cpp) the context's
 // (aof_capi.hip) sticky fault / wedged state and current-device check of a context, before anything is enqueued; and
 // aof_last_error's text for the callers outside aof_capi.hip
 int precheck(aof_ctx *ctx);

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "aof.h"
+#include "bank_table.hpp"
 #include "flow_bank.hpp"
 #include "opencv_params.hpp"
 #include "optical_flow_rad.hpp"
@@ -85,6 +86,24 @@ struct Staged {
 	}
 };
 
+// A per-stream table: a shadow array the setters write and its copy on the device, with the flags that decide when it
+// is copied and bound (bank_table.hpp).  The four of an object, in the order a tick copies and binds them.
+struct Table : Staged, BankTableFlags {};
+enum { kSensors, kFormats, kBins, kStreams, kTables };
+const char *const kTableCopyFailed[kTables] = {
+	"copy of the per-stream sensor records failed", "copy of the per-stream pixel formats failed",
+	"copy of the per-stream binning failed", "copy of the per-stream records failed"};
+// The one thing the tables differ in: the call of the C ABI that binds the device array (camera_bytes: of the sensor records).
+int bindTable(aof_ctx *ctx, int which, const uint8_t *d, int n_streams, size_t camera_bytes)
+{
+	switch (which) {
+	case kSensors: return aof_set_bank_sensors(ctx, reinterpret_cast<const aof_bank_sensor *>(d), n_streams, camera_bytes);
+	case kFormats: return aof_set_bank_pixel_formats(ctx, d, n_streams);
+	case kBins: return aof_set_bank_binning(ctx, d, n_streams);
+	default: return aof_set_bank_streams(ctx, reinterpret_cast<const aof_bank_stream *>(d), n_streams);
+	}
+}
+
 }  // namespace
 
 struct OpticalFlowBank::Impl {
@@ -124,28 +143,21 @@ struct OpticalFlowBank::Impl {
 	Staged bytes;            // u8 [n_streams][max_bytes], then their lengths u16 [n_streams]
 	size_t off_rx_len;
 	aof_mavlink_rx_state *d_rx_state;
-	// the per-stream form (setStream...()): the shadow records start from the constructor's values; nothing is copied or
-	// bound before the first setter
-	Staged streams;          // aof_bank_stream [n_streams]
-	bool streams_used, streams_dirty, streams_bound;
-	bool streams_copying;    // a copy of the shadow is enqueued: it is through once collect() has seen the tick's tag
-	// the per-sensor form (setStreamSensor()): allocated by enableCamera(), the shadow records start from what its sensor
-	// size means (aof_bank_sensor_from_camera); nothing is copied or bound before the first call
-	Staged sensors;          // aof_bank_sensor [n_streams]
-	bool sensors_used, sensors_dirty, sensors_bound, sensors_copying;
-	// the pixel formats beside them (enableCameraPacked(), setStreamPixelFormat()): u8 [n_streams], the same scheme; they
-	// travel with the sensor records (formats_used implies sensors_used)
-	Staged formats;
-	bool formats_used, formats_dirty, formats_bound, formats_copying;
-	// and the binning (setStreamBinning()): u8 [n_streams], ones until a call; the same scheme, beside the records
-	Staged bins;
-	bool bins_used, bins_dirty, bins_bound, bins_copying;
+	// the per-stream tables; nothing of one is copied or bound before its first setter
+	//   kStreams  (setStream...()): aof_bank_stream [n_streams], the shadow records start from the constructor's values
+	//   kSensors  (setStreamSensor()): aof_bank_sensor [n_streams], allocated by enableCamera() like the next two; the
+	//             shadow records start from what its sensor size means (aof_bank_sensor_from_camera)
+	//   kFormats  (enableCameraPacked(), setStreamPixelFormat()): u8 [n_streams]; they travel with the sensor records
+	//             (used implies that the records are)
+	//   kBins     (setStreamBinning()): u8 [n_streams], ones until a call; beside the records as well
+	Table table[kTables];
 
 	int fail(int code, const char *what) { return self->fail(code, what); }
 	int failed(int rc) { return rc ? fail(rc, aof_last_error(ctx)) : 0; }   // of a call of the C ABI
 	uint8_t *imuCounts() { return samples.h + off_imu_counts; }
 	uint16_t *rxLengths() { return reinterpret_cast<uint16_t *>(bytes.h + off_rx_len); }
-	aof_bank_stream *shadow() { return reinterpret_cast<aof_bank_stream *>(streams.h); }
+	aof_bank_stream *shadow() { return reinterpret_cast<aof_bank_stream *>(table[kStreams].h); }
+	aof_bank_sensor *sensorRecords() { return reinterpret_cast<aof_bank_sensor *>(table[kSensors].h); }
 	static aof_bank_stream *record(Impl *m, int s);
 	bool waitIdle();
 	int startOver(const uint8_t *mask, bool imu_too);
@@ -198,7 +210,7 @@ OpticalFlowBank::OpticalFlowBank(float f_length_x, float f_length_y, int output_
 		     m->mem.get((void **)&m->d_records, S * sizeof(aof_tick_record), Allocations::kDevice) &&
 		     m->mem.get((void **)&m->d_mavlink, S * AOF_SEQ_FRAME_BYTES, Allocations::kDevice) &&
 		     m->mem.get((void **)&m->d_lens, S, Allocations::kDevice) &&
-		     m->streams.alloc(m->mem, S * sizeof(aof_bank_stream)) &&
+		     m->table[kStreams].alloc(m->mem, S * sizeof(aof_bank_stream)) &&
 		     m->mem.get((void **)&m->outbox, m->outbox_bytes, Allocations::kOutbox);
 	}
 	_m = m;
@@ -287,17 +299,16 @@ void OpticalFlowBank::setTimestampOffset(uint64_t offset_usec)
 {
 	if (!_m) return;
 	_m->bp.offset_timestamp_usec = offset_usec;
-	if (!_m->streams.h) return;
+	if (!_m->shadow()) return;
 	for (int s = 0; s < n_streams; s++) _m->shadow()[s].offset_timestamp_usec = offset_usec;
-	_m->streams_dirty = true;
+	_m->table[kStreams].touchUnused();
 }
 
 // The shadow record of stream s for a setter, or NULL (no engine, no memory, bad index); the next push copies the array.
 aof_bank_stream *OpticalFlowBank::Impl::record(Impl *m, int s)
 {
-	if (!m || !m->streams.h || s < 0 || (size_t)s >= m->S) return NULL;
-	m->streams_used = true;
-	m->streams_dirty = true;
+	if (!m || !m->shadow() || s < 0 || (size_t)s >= m->S) return NULL;
+	m->table[kStreams].touch();
 	return &m->shadow()[s];
 }
 
@@ -342,7 +353,7 @@ int OpticalFlowBank::setStreamTimestampOffset(int s, uint64_t offset_usec)
 int OpticalFlowBank::setStreamSensor(int s, uint64_t offset, int pitch, int width, int height, int x0, int y0)
 {
 	Impl *m = _m;
-	if (!m || !m->camera || !m->sensors.h || s < 0 || s >= n_streams) return -EINVAL;
+	if (!m || !m->camera || !m->sensorRecords() || s < 0 || s >= n_streams) return -EINVAL;
 	aof_bank_sensor rec;
 	std::memset(&rec, 0, sizeof(rec));
 	rec.offset = offset;
@@ -353,44 +364,41 @@ int OpticalFlowBank::setStreamSensor(int s, uint64_t offset, int pitch, int widt
 	rec.y0 = y0;
 	// the kernels' own rule, against the staging buffer pushCamera() fills: here the host can see the record
 	// (with the stream's current pixel format and binning)
-	if (aof_bank_sensor_valid_binned(&rec, m->formats.h[s], m->bins.h[s], image_width, image_height, 0, m->sensor.bytes) != 1)
+	if (aof_bank_sensor_valid_binned(&rec, m->table[kFormats].h[s], m->table[kBins].h[s], image_width, image_height, 0, m->sensor.bytes) != 1)
 		return refuse(-EINVAL, "setStreamSensor(): the record does not describe memory inside the staging buffer");
-	reinterpret_cast<aof_bank_sensor *>(m->sensors.h)[s] = rec;
-	m->sensors_used = true;
-	m->sensors_dirty = true;
+	m->sensorRecords()[s] = rec;
+	m->table[kSensors].touch();
 	return 0;
 }
 
 int OpticalFlowBank::setStreamPixelFormat(int s, int format)
 {
 	Impl *m = _m;
-	if (!m || !m->camera || !m->sensors.h || !m->formats.h || s < 0 || s >= n_streams) return -EINVAL;
+	if (!m || !m->camera || !m->sensorRecords() || !m->table[kFormats].h || s < 0 || s >= n_streams) return -EINVAL;
 	if (format < AOF_PIXEL_GREY8 || format > AOF_PIXEL_LUMA16_HI)
 		return refuse(-EINVAL, "setStreamPixelFormat(): no such format");
 	// the stream's current record, by the kernels' own rule, with the new format
-	if (aof_bank_sensor_valid_binned(reinterpret_cast<aof_bank_sensor *>(m->sensors.h) + s, (uint8_t)format, m->bins.h[s], image_width,
+	if (aof_bank_sensor_valid_binned(m->sensorRecords() + s, (uint8_t)format, m->table[kBins].h[s], image_width,
 					 image_height, 0, m->sensor.bytes) != 1)
 		return refuse(-EINVAL, "setStreamPixelFormat(): the stream's record no longer lies inside the staging buffer");
-	m->formats.h[s] = (uint8_t)format;
-	m->formats_used = m->formats_dirty = true;
-	m->sensors_used = true;   // (formats are bound next to the records only)
-	if (!m->sensors_bound) m->sensors_dirty = true;
+	m->table[kFormats].h[s] = (uint8_t)format;
+	m->table[kFormats].touch();
+	m->table[kSensors].rideAlong();   // (formats are bound next to the records only)
 	return 0;
 }
 
 int OpticalFlowBank::setStreamBinning(int s, int bin)
 {
 	Impl *m = _m;
-	if (!m || !m->camera || !m->sensors.h || !m->formats.h || !m->bins.h || s < 0 || s >= n_streams) return -EINVAL;
+	if (!m || !m->camera || !m->sensorRecords() || !m->table[kFormats].h || !m->table[kBins].h || s < 0 || s >= n_streams) return -EINVAL;
 	if (bin != 1 && bin != 2 && bin != 4) return refuse(-EINVAL, "setStreamBinning(): the bin is 1, 2 or 4");
 	// the stream's current record and format, by the kernels' own rule, with the new footprint
-	if (aof_bank_sensor_valid_binned(reinterpret_cast<aof_bank_sensor *>(m->sensors.h) + s, m->formats.h[s], (uint8_t)bin, image_width,
+	if (aof_bank_sensor_valid_binned(m->sensorRecords() + s, m->table[kFormats].h[s], (uint8_t)bin, image_width,
 					 image_height, 0, m->sensor.bytes) != 1)
 		return refuse(-EINVAL, "setStreamBinning(): the binned crop no longer lies inside the stream's sensor frame");
-	m->bins.h[s] = (uint8_t)bin;
-	m->bins_used = m->bins_dirty = true;
-	m->sensors_used = true;   // (the binning is bound next to the records only)
-	if (!m->sensors_bound) m->sensors_dirty = true;
+	m->table[kBins].h[s] = (uint8_t)bin;
+	m->table[kBins].touch();
+	m->table[kSensors].rideAlong();   // (the binning is bound next to the records only)
 	return 0;
 }
 
@@ -480,50 +488,15 @@ int OpticalFlowBank::Impl::receive()
 						 reinterpret_cast<aof_imu_sample *>(samples.d), samples.d + off_imu_counts, stream));
 }
 
-// In front of a tick: the shadow records to the device if a setter changed them, and bound to the context the first
-// time.  Without a setter nothing happens: the tick runs on the scalars, as it always did.  The shadow counts as copied
-// only once collect() has waited for the tick: a setter behind a push that failed in between writes an array that is
-// still marked dirty, and the object has failed for good by then.
+// In front of a tick: every per-stream table a setter has touched goes to the device if it is dirty and is bound to the
+// context the first time (BankTableFlags::sync, bank_table.hpp) -- sensors, formats, binning, streams.
 int OpticalFlowBank::Impl::syncStreams()
 {
-	if (sensors_used) {   // (the same scheme for the sensor records of setStreamSensor())
-		if (sensors_dirty) {
-			if (!sensors.upload(stream, 0, sensors.bytes)) return fail(-EIO, "copy of the per-stream sensor records failed");
-			sensors_copying = true;
-		}
-		if (!sensors_bound) {
-			if (failed(aof_set_bank_sensors(ctx, reinterpret_cast<aof_bank_sensor *>(sensors.d), (int)S, sensor.bytes))) return -EIO;
-			sensors_bound = true;
-		}
-	}
-	if (formats_used) {
-		if (formats_dirty) {
-			if (!formats.upload(stream, 0, formats.bytes)) return fail(-EIO, "copy of the per-stream pixel formats failed");
-			formats_copying = true;
-		}
-		if (!formats_bound) {
-			if (failed(aof_set_bank_pixel_formats(ctx, formats.d, (int)S))) return -EIO;
-			formats_bound = true;
-		}
-	}
-	if (bins_used) {
-		if (bins_dirty) {
-			if (!bins.upload(stream, 0, bins.bytes)) return fail(-EIO, "copy of the per-stream binning failed");
-			bins_copying = true;
-		}
-		if (!bins_bound) {
-			if (failed(aof_set_bank_binning(ctx, bins.d, (int)S))) return -EIO;
-			bins_bound = true;
-		}
-	}
-	if (!streams_used) return 0;
-	if (streams_dirty) {
-		if (!streams.upload(stream, 0, streams.bytes)) return fail(-EIO, "copy of the per-stream records failed");
-		streams_copying = true;   // (still dirty: a push that fails behind this point copies again)
-	}
-	if (!streams_bound) {
-		if (failed(aof_set_bank_streams(ctx, reinterpret_cast<aof_bank_stream *>(streams.d), (int)S))) return -EIO;
-		streams_bound = true;
+	for (int t = 0; t < kTables; t++) {
+		const int rc = table[t].sync(
+			[&]() { return table[t].upload(stream, 0, table[t].bytes) ? 0 : fail(-EIO, kTableCopyFailed[t]); },
+			[&]() { return failed(bindTable(ctx, t, table[t].d, (int)S, sensor.bytes)) ? -EIO : 0; });
+		if (rc) return rc;
 	}
 	return 0;
 }
@@ -552,22 +525,7 @@ int OpticalFlowBank::Impl::collect()
 	while (__atomic_load_n(word, __ATOMIC_ACQUIRE) != want) {
 		if (secondsSince(t0) > kDeadlineS) return fail(-ETIMEDOUT, "the tick did not finish within the deadline");
 	}
-	if (streams_copying) {   // the copy of the per-stream records in front of the tick is through as well
-		streams_copying = false;
-		streams_dirty = false;
-	}
-	if (sensors_copying) {
-		sensors_copying = false;
-		sensors_dirty = false;
-	}
-	if (formats_copying) {
-		formats_copying = false;
-		formats_dirty = false;
-	}
-	if (bins_copying) {
-		bins_copying = false;
-		bins_dirty = false;
-	}
+	for (int t = 0; t < kTables; t++) table[t].tagSeen();   // the copies in front of the tick are through as well
 	if (imu) std::memset(imuCounts(), 0, S);                      // the tick took the queued samples
 	if (rx) std::memset(rxLengths(), 0, S * sizeof(uint16_t));    // and the queued bytes
 	return (int)reinterpret_cast<const aof_outbox_header *>(outbox)->n_messages;
@@ -624,9 +582,9 @@ int OpticalFlowBank::Impl::enableSensorFrames(int camera_width, int camera_heigh
 	void *bank = NULL;
 	if (!m->mem.get(&bank, L.total_bytes, Allocations::kDevice) ||
 	    !m->sensor.alloc(m->mem, S * (size_t)camera_width * (size_t)camera_height * bpp) ||
-	    !m->sensors.alloc(m->mem, S * sizeof(aof_bank_sensor)) ||
-	    !m->formats.alloc(m->mem, alignUp(S, 16)) ||
-	    !m->bins.alloc(m->mem, alignUp(S, 16)) ||
+	    !m->table[kSensors].alloc(m->mem, S * sizeof(aof_bank_sensor)) ||
+	    !m->table[kFormats].alloc(m->mem, alignUp(S, 16)) ||
+	    !m->table[kBins].alloc(m->mem, alignUp(S, 16)) ||
 	    !m->mem.get((void **)&m->d_exposure, S * sizeof(aof_exposure_record), Allocations::kDevice) ||
 	    !m->mem.get((void **)&m->d_exposure_state, S * sizeof(aof_exposure_state), Allocations::kDevice) ||
 	    !m->mem.get((void **)&m->commands, S * sizeof(aof_exposure_command), Allocations::kOutbox))
@@ -638,16 +596,16 @@ int OpticalFlowBank::Impl::enableSensorFrames(int camera_width, int camera_heigh
 	m->cam = cam;
 	for (size_t s = 0; s < S; s++) {
 		// the centred record; packed pixels: rows and frames of bpp bytes per pixel, and the stream's format beside it
-		aof_bank_sensor *rec = reinterpret_cast<aof_bank_sensor *>(m->sensors.h) + s;
+		aof_bank_sensor *rec = m->sensorRecords() + s;
 		aof_bank_sensor_from_camera(&p, &cam, (int32_t)s, rec);
 		rec->offset *= bpp;
 		rec->pitch *= (int32_t)bpp;
-		m->formats.h[s] = (uint8_t)format;
+		m->table[kFormats].h[s] = (uint8_t)format;
 	}
-	std::memset(m->bins.h, 1, m->bins.bytes);
+	std::memset(m->table[kBins].h, 1, m->table[kBins].bytes);
 	if (format != AOF_PIXEL_GREY8) {
-		m->sensors_used = m->sensors_dirty = true;
-		m->formats_used = m->formats_dirty = true;
+		m->table[kSensors].touch();
+		m->table[kFormats].touch();
 	}
 	aof_exposure_control_default(&m->ec);
 	std::memset(m->commands, 0, S * sizeof(aof_exposure_command));

@@ -9,7 +9,9 @@
 // cases of tests/small_plan_ref.py, likewise; the plan of the flat lane-per-block launches (aof_lane8_plan.hpp: lane8_flat_plan)
 // on the cases of tests/lane8_plan_ref.py, likewise, and xcd_remap (aof_xcd_remap.hpp, the text the kernels run) printed value by
 // value for the test to hold to the model's; and fastdiv_make against the division it replaces, with the kernels' fast_div restated in 32-bit
-// arithmetic.
+// arithmetic; the stream bank's bound per-stream tables (aof_bank_tables.hpp): binding, resolving for a push or an IMU call, the
+// sensor arguments of a round, case by case against literal values; and the flags of one per-stream table of OpticalFlowBank
+// (facade/src/bank_table.hpp) over runs of ticks.
 // Built with -fsanitize=address,undefined by tests/test_host_asan.py.
 #include <cmath>
 #include <cstdio>
@@ -17,6 +19,7 @@
 #include <cstring>
 
 #include "aof.h"
+#include "aof_bank_tables.hpp"
 #include "aof_coarse_plan.hpp"
 #include "aof_cols8_plan.hpp"
 #include "aof_exposure_step.hpp"
@@ -25,6 +28,7 @@
 #include "aof_mavlink.hpp"
 #include "aof_small_plan.hpp"
 #include "aof_xcd_remap.hpp"
+#include "bank_table.hpp"
 #include "optical_flow_rad.hpp"
 
 static unsigned rng_state = 777u;
@@ -356,6 +360,215 @@ static int check_fastdiv(int *divisors)
     return extra;
 }
 
+// The stream bank's bound per-stream tables (aof_bank_tables.hpp): what a binding call accepts and leaves behind, and
+// which tables a push or an IMU call uses or why it is refused, each case against the value written here.  The arrays
+// are places in `arena`; nothing reads them.  Returns the number of cases, or -1.
+alignas(16) static uint8_t arena[96];
+
+static bool same_text(const char *got, const char *want)
+{
+    return (!got && !want) || (got && want && std::strcmp(got, want) == 0);
+}
+
+static int check_bank_tables()
+{
+    using namespace aof;
+    const void *const A = arena + 16, *const ODD = arena + 40, *const OLD = arena + 64;   // 16-byte aligned, 8 off, the binding before
+    int cases = 0;
+    // ---- binding: every case starts from all four bound for 3 streams, camera_bytes 1000 ----
+    const struct {
+        BankTable which; const void *array; int32_t n; uint64_t camera_bytes;
+        const char *refusal;                                  // nullptr: accepted, and the table then holds
+        const void *array_after; int32_t n_after; uint64_t camera_bytes_after;
+    } binds[] = {
+        {kBankStreams, nullptr, 5, 0, nullptr, nullptr, 0, 1000},
+        {kBankStreams, A, 0, 0, "bank streams: an array needs n_streams >= 1", OLD, 3, 1000},
+        {kBankStreams, A, -1, 0, "bank streams: an array needs n_streams >= 1", OLD, 3, 1000},
+        {kBankStreams, ODD, 4, 0, "bank streams: the array must be 16-byte aligned", OLD, 3, 1000},
+        {kBankStreams, A, 4, 0, nullptr, A, 4, 1000},
+        {kBankSensors, nullptr, 5, 77, nullptr, nullptr, 0, 0},
+        {kBankSensors, A, 0, 77, "bank sensors: an array needs n_streams >= 1", OLD, 3, 1000},
+        {kBankSensors, A, -1, 77, "bank sensors: an array needs n_streams >= 1", OLD, 3, 1000},
+        {kBankSensors, ODD, 4, 77, "bank sensors: the array must be 16-byte aligned", OLD, 3, 1000},
+        {kBankSensors, A, 4, 0, "bank sensors: an array needs camera_bytes > 0", OLD, 3, 1000},
+        {kBankSensors, ODD, 0, 0, "bank sensors: an array needs n_streams >= 1", OLD, 3, 1000},   // (the first of three reasons)
+        {kBankSensors, A, 4, 77, nullptr, A, 4, 77},
+        {kBankFormats, nullptr, 5, 0, nullptr, nullptr, 0, 1000},
+        {kBankFormats, A, 0, 0, "bank pixel formats: an array needs n_streams >= 1", OLD, 3, 1000},
+        {kBankFormats, A, -1, 0, "bank pixel formats: an array needs n_streams >= 1", OLD, 3, 1000},
+        {kBankFormats, ODD, 4, 0, nullptr, ODD, 4, 1000},
+        {kBankFormats, (const uint8_t *)ODD + 1, 2, 0, nullptr, (const uint8_t *)ODD + 1, 2, 1000},
+        {kBankBins, nullptr, 5, 0, nullptr, nullptr, 0, 1000},
+        {kBankBins, A, 0, 0, "bank binning: an array needs n_streams >= 1", OLD, 3, 1000},
+        {kBankBins, A, -1, 0, "bank binning: an array needs n_streams >= 1", OLD, 3, 1000},
+        {kBankBins, ODD, 4, 0, nullptr, ODD, 4, 1000},
+        {kBankBins, (const uint8_t *)ODD + 3, 1, 0, nullptr, (const uint8_t *)ODD + 3, 1, 1000},
+    };
+    for (const auto &c : binds) {
+        BankTables before = {};
+        for (int t = 0; t < kBankTableCount; t++) before.table[t] = {OLD, 3};
+        before.camera_bytes = 1000;
+        BankTables b = before;
+        if (!same_text(bank_tables_bind(&b, c.which, c.array, c.n, c.camera_bytes), c.refusal)) return -1;
+        if (c.refusal && !(b == before)) return -1;
+        BankTables want = before;
+        want.table[c.which] = {c.array_after, c.n_after};
+        want.camera_bytes = c.camera_bytes_after;
+        if (!(b == want)) return -1;
+        cases++;
+    }
+    // ---- resolving, for a call of 3 streams: {streams, sensors, formats, bins} bound for that many streams (0: not bound) ----
+    const int64_t kBig = INT64_MAX / AOF_BANK_BURST_MAX + 1;
+    enum { kImu = 2 };
+    enum { S = 1, N = 2, F = 4, B = 8 };   // the arrays the call uses
+    const struct {
+        int32_t bound[kBankTableCount]; int form; int64_t round_stride;   // form: 0 pre-cropped frames, 1 sensor frames, kImu
+        const char *refusal; int uses; uint64_t camera_bytes;
+    } calls[] = {
+        {{0, 0, 0, 0}, 0, 0, nullptr, 0, 0},
+        {{0, 0, 0, 0}, 1, 0, nullptr, 0, 0},
+        {{3, 0, 0, 0}, 0, 0, nullptr, S, 0},
+        {{3, 0, 0, 0}, 1, 0, nullptr, S, 0},
+        {{0, 3, 0, 0}, 1, 0, nullptr, N, 1000},
+        {{0, 3, 3, 0}, 1, 0, nullptr, N | F, 1000},
+        {{0, 3, 0, 3}, 1, 0, nullptr, N | B, 1000},
+        {{3, 3, 3, 3}, 1, 640, nullptr, S | N | F | B, 1000},
+        {{4, 0, 0, 0}, 0, 0, "bank: n_streams differs from the array bound with aof_set_bank_streams", 0, 0},
+        {{4, 0, 0, 0}, 1, 0, "bank: n_streams differs from the array bound with aof_set_bank_streams", 0, 0},
+        {{0, 4, 0, 0}, 1, 0, "bank: n_streams differs from the array bound with aof_set_bank_sensors", 0, 0},
+        {{0, 3, 4, 0}, 1, 0, "bank: n_streams differs from the array bound with aof_set_bank_pixel_formats", 0, 0},
+        {{0, 3, 0, 4}, 1, 0, "bank: n_streams differs from the array bound with aof_set_bank_binning", 0, 0},
+        {{4, 4, 0, 0}, 1, 0, "bank: n_streams differs from the array bound with aof_set_bank_streams", 0, 0},
+        {{0, 0, 3, 0}, 1, 0, "bank: pixel formats are bound (aof_set_bank_pixel_formats) without sensor records", 0, 0},
+        {{0, 0, 4, 0}, 1, 0, "bank: pixel formats are bound (aof_set_bank_pixel_formats) without sensor records", 0, 0},
+        {{0, 0, 0, 3}, 1, 0, "bank: a binning is bound (aof_set_bank_binning) without sensor records", 0, 0},
+        {{0, 0, 3, 3}, 1, 0, "bank: pixel formats are bound (aof_set_bank_pixel_formats) without sensor records", 0, 0},
+        {{0, 3, 4, 4}, 1, 0, "bank: n_streams differs from the array bound with aof_set_bank_pixel_formats", 0, 0},
+        {{0, 3, 0, 0}, 1, kBig, "bank burst: round_stride too large for sensor records", 0, 0},
+        {{0, 3, 0, 0}, 1, kBig - 1, nullptr, N, 1000},
+        {{3, 0, 0, 0}, 1, kBig, nullptr, S, 0},
+        {{0, 4, 0, 0}, 1, kBig, "bank: n_streams differs from the array bound with aof_set_bank_sensors", 0, 0},
+        {{0, 3, 4, 0}, 1, kBig, "bank burst: round_stride too large for sensor records", 0, 0},
+        {{0, 4, 4, 4}, 0, 0, nullptr, 0, 0},
+        {{3, 4, 4, 4}, 0, kBig, nullptr, S, 0},
+        {{0, 0, 3, 3}, 0, 0, nullptr, 0, 0},
+        {{4, 0, 0, 0}, kImu, 0, "imu: n_streams differs from the array bound with aof_set_bank_streams", 0, 0},
+        {{3, 4, 4, 4}, kImu, 0, nullptr, S, 0},
+        {{0, 0, 3, 3}, kImu, 0, nullptr, 0, 0},
+    };
+    for (const auto &c : calls) {
+        BankTables b = {};
+        for (int t = 0; t < kBankTableCount; t++)
+            if (c.bound[t]) b.table[t] = {arena + 16 * (t + 1), c.bound[t]};
+        b.camera_bytes = c.bound[kBankSensors] ? 1000 : 0;
+        const BankTablesUsed untouched = {(const aof_bank_stream *)arena, (const aof_bank_sensor *)arena, 5, arena, arena};
+        BankTablesUsed u = untouched;
+        const char *got;
+        if (c.form == kImu) got = bank_tables_for_imu(b, 3, &u.streams);
+        else got = bank_tables_for_push(b, 3, c.form == 1, c.round_stride, &u);
+        if (!same_text(got, c.refusal)) return -1;
+        if (c.refusal) {   // a refused call hands nothing out
+            if (u.streams != untouched.streams || u.sensors != untouched.sensors || u.formats != untouched.formats || u.bins != untouched.bins) return -1;
+        } else {
+            if (u.streams != (c.uses & S ? (const void *)(arena + 16) : nullptr)) return -1;
+            if (c.form != kImu) {
+                if (u.sensors != (c.uses & N ? (const void *)(arena + 32) : nullptr) || u.camera_bytes != c.camera_bytes) return -1;
+                if (u.formats != (c.uses & F ? arena + 48 : nullptr) || u.bins != (c.uses & B ? arena + 64 : nullptr)) return -1;
+            }
+        }
+        cases++;
+    }
+    // ---- the kernels' sensor arguments of a round: every value in its own field ----
+    const BankTablesUsed u = {(const aof_bank_stream *)(arena + 16), (const aof_bank_sensor *)(arena + 32), 1000, arena + 48, arena + 64};
+    const BankSensors bs = bank_sensors_of_round(u, 640);
+    if ((const void *)bs.recs != arena + 32 || bs.camera_bytes != 1000 || bs.camera_base != 640 || bs.formats != arena + 48 || bs.bins != arena + 64) return -1;
+    const IngestSensors is = ingest_sensors_of_round(u, 640, arena + 80), plain = ingest_sensors_of_round(u, 0);
+    if ((const void *)is.recs != arena + 32 || is.base != 640 || is.camera_bytes != 1000 || is.ok != arena + 80 || is.formats != arena + 48 ||
+        is.bins != arena + 64 || plain.ok != nullptr || plain.base != 0)
+        return -1;
+    return cases + 2;
+}
+
+// The flags of one per-stream table of OpticalFlowBank (facade/src/bank_table.hpp) over a run of ticks, with counters in
+// place of the copy and the binding call: after every step the numbers written here.  Returns the number of steps, or -1.
+struct TableSim {
+    BankTableFlags f = {};
+    int uploads = 0, binds = 0;
+    int upload_rc = 0, bind_rc = 0;   // what the copy and the binding call answer
+    // one tick: the table in front of the push; `fails`: the push fails behind it, before the tag is seen
+    int tick(bool fails = false)
+    {
+        const int rc = f.sync([&]() { uploads++; return upload_rc; }, [&]() { binds++; return bind_rc; });
+        if (rc) return rc;
+        if (fails) return -1;
+        f.tagSeen();
+        return 0;
+    }
+    bool at(int want_uploads, int want_binds, bool want_dirty) const
+    {
+        return uploads == want_uploads && binds == want_binds && f.dirty == want_dirty && !(f.copying && !f.dirty);
+    }
+};
+
+static int check_facade_table()
+{
+    int steps = 0;
+#define STEP(cond) do { if (!(cond)) return -1; steps++; } while (0)
+    {   // no setter, three ticks: nothing is copied or bound
+        TableSim t;
+        for (int k = 0; k < 3; k++) STEP(t.tick() == 0 && t.at(0, 0, false) && !t.f.used && !t.f.bound);
+    }
+    {   // a setter before tick 0: one copy and the binding at tick 0, nothing at tick 1; a setter between ticks 1 and 2:
+        // one more copy, no second binding
+        TableSim t;
+        t.f.touch();
+        STEP(t.tick() == 0 && t.at(1, 1, false) && t.f.bound);
+        STEP(t.tick() == 0 && t.at(1, 1, false));
+        t.f.touch();
+        STEP(t.at(1, 1, true));
+        STEP(t.tick() == 0 && t.at(2, 1, false));
+        STEP(t.tick() == 0 && t.at(2, 1, false));
+    }
+    {   // the tick fails behind the enqueued copy, before its tag: still dirty, the next tick copies again
+        TableSim t;
+        t.f.touch();
+        STEP(t.tick(true) == -1 && t.at(1, 1, true) && t.f.copying && t.f.bound);
+        STEP(t.tick() == 0 && t.at(2, 1, false) && !t.f.copying);
+        STEP(t.tick() == 0 && t.at(2, 1, false));
+    }
+    {   // dirty without used (setTimestampOffset()): nothing until a setter marks the table used, then one copy carries both
+        TableSim t;
+        t.f.touchUnused();
+        STEP(t.tick() == 0 && t.at(0, 0, true) && !t.f.used);
+        STEP(t.tick() == 0 && t.at(0, 0, true));
+        t.f.touch();
+        STEP(t.tick() == 0 && t.at(1, 1, false));
+        t.f.touchUnused();   // and once the table is used, such a change is copied at the next tick
+        STEP(t.tick() == 0 && t.at(2, 1, false));
+    }
+    {   // needed beside another table (setStreamPixelFormat(), setStreamBinning()): copied and bound once, not copied again
+        TableSim t;
+        t.f.rideAlong();
+        STEP(t.f.used && t.f.dirty);
+        STEP(t.tick() == 0 && t.at(1, 1, false));
+        t.f.rideAlong();
+        STEP(t.tick() == 0 && t.at(1, 1, false));
+    }
+    {   // the copy fails: no binding call, nothing marked; the binding call fails: asked again at the next tick
+        TableSim t;
+        t.f.touch();
+        t.upload_rc = -5;
+        STEP(t.tick() == -5 && t.at(1, 0, true) && !t.f.copying && !t.f.bound);
+        t.upload_rc = 0;
+        t.bind_rc = -7;
+        STEP(t.tick() == -7 && t.at(2, 1, true) && t.f.copying && !t.f.bound);
+        t.bind_rc = 0;
+        STEP(t.tick() == 0 && t.at(3, 2, false) && t.f.bound);
+    }
+#undef STEP
+    return steps;
+}
+
 int main(int argc, char **argv)
 {
     int bad = 0, valid = 0;
@@ -413,6 +626,12 @@ int main(int argc, char **argv)
     if (numerators < 0) return 15;
     std::printf("host selftest: fast_div: %d divisors, all numerators below 65536 and up to %d around multiples up to 2^31 equal to n / d\n",
                 divisors, numerators);
+    const int tables = check_bank_tables();
+    if (tables < 0) return 20;
+    std::printf("host selftest: bank tables: %d cases\n", tables);
+    const int steps = check_facade_table();
+    if (steps < 0) return 21;
+    std::printf("host selftest: facade table: %d steps, copies and bindings as written\n", steps);
     if (argc > 1) {
         const int plans = print_cols_plans(argv[1]);
         if (plans < 0) return 16;

@@ -365,6 +365,37 @@ def test_the_facade_with_stream_sensors_equals_an_object_fed_uniform_frames(aof,
     a.close(), b.close()
 
 
+def test_the_facade_takes_a_sensor_record_set_between_ticks_from_that_tick(aof, synth, gpu_device):
+    """OpticalFlowBank, S = 2, 64 x 64, rate 0, four ticks: object A with enableCamera(80, 80) and no setter before the
+    first tick; setStreamSensor() before tick 2 -- the first copy of the shadow records and their binding, between two
+    ticks -- moves stream 1's crop from the centre to the corner.  Object B with enableCamera(64, 64) is fed the crops
+    the host cuts: entries and exposure commands by raw bytes at every tick."""
+    S, T, w, cw = 2, 4, 64, 80
+    seqs = [synth.make_sequence(cw, cw, T, 4, seed=181000 + s, max_step=3)[0] for s in range(S)]
+    a, b = (aof.OpticalFlowBank(FX, FY, 0, w, w, S) for _ in range(2))
+    for bank, size in ((a, cw), (b, w)):
+        assert bank.engineOk(), bank.lastError()
+        bank.setTimestampOffset(OFFSET)
+        assert bank.enableCamera(size, size, 100, 4, INTERVAL) == 0, bank.lastError()
+    centre = (cw - w) // 2
+    entries_seen = 0
+    for k in range(T):
+        if k == 2:
+            assert a.setStreamSensor(1, 1 * cw * cw, cw, cw, cw, 0, 0) == 0, a.lastError()
+        sensor = np.stack([q[k] for q in seqs])
+        origin = [centre, centre if k < 2 else 0]
+        crops = np.stack([sensor[s, o:o + w, o:o + w] for s, o in enumerate(origin)])
+        times = np.full(S, 12_000 * (k + 1), np.uint64)
+        na, ea = a.pushCamera(sensor, times)
+        nb, eb = b.pushCamera(crops, times)
+        assert na == nb >= 0, (k, a.lastError(), b.lastError())
+        assert ea.tobytes() == eb.tobytes(), ("entries", k)
+        assert a.exposureCommands().tobytes() == b.exposureCommands().tobytes(), ("exposure commands", k)
+        entries_seen += na
+    assert entries_seen >= 2 * (T - 1)
+    a.close(), b.close()
+
+
 # ---- bindings and refusals ----
 
 def test_bindings_and_refusals(aof, orc, synth, gpu_device):

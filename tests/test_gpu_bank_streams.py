@@ -451,6 +451,30 @@ def test_the_facade_with_setters_equals_one_opencv_object_per_camera(aof, synth,
     plain.close()
 
 
+def test_the_facade_takes_an_identity_set_between_ticks_from_that_tick(aof, synth, gpu_device):
+    """OpticalFlowBank, S = 2, 64 x 64, rate 0 (every frame publishes), six ticks with every stream active and no setter
+    before the first: setStreamIdentity(1, ...) before tick 2 is the first copy of the shadow records and their binding,
+    the one before tick 4 a second copy of an array that is already bound.  Each applies from its own tick, to stream 1
+    alone."""
+    S, T, w = 2, 6, 64
+    seqs = [synth.make_sequence(w, w, T, 4, seed=171000 + s, max_step=3)[0] for s in range(S)]
+    bank = aof.OpticalFlowBank(FX, FY, 0, w, w, S)
+    assert bank.engineOk(), bank.lastError()
+    bank.setTimestampOffset(5_000_000)
+    want = [(1, 100), (1, 100), (42, 43), (42, 43), (52, 53), (52, 53)]
+    for k in range(T):
+        if k == 2:
+            assert bank.setStreamIdentity(1, 42, 43, 7) == 0
+        if k == 4:
+            assert bank.setStreamIdentity(1, 52, 53, 9) == 0
+        n, entries = bank.push(np.stack([q[k] for q in seqs]), np.full(S, 12_000 * (k + 1), np.uint64))
+        assert n == len(entries) == 2, (k, n, bank.lastError())
+        assert list(entries["stream"]) == [0, 1], k
+        ids = [tuple(bytes(e["mavlink"][5:7])) for e in entries]
+        assert all(int(e["mavlink_len"]) > 0 for e in entries) and ids == [(1, 100), want[k]], (k, ids)
+    bank.close()
+
+
 def test_the_facade_with_imu_sends_with_each_stream_s_identity(aof, synth, gpu_device):
     """OpticalFlowBank with enableImu(), S = 3, 14 ticks: the IMU call packs the frames, with the identity and the
     sequence numbers setStreamIdentity() gave each stream; setStreamTimestampOffset() is ignored, as setTimestampOffset()

@@ -8,7 +8,10 @@ every case of tests/coarse_plan_ref.py and a list of extreme shapes, the same wa
 (csrc/aof_small_plan.hpp: small_plan_make, lane8_group_plan) on every case of tests/small_plan_ref.py and its list of
 extreme shapes, likewise; the plan of the flat lane-per-block launches (csrc/aof_lane8_plan.hpp: lane8_flat_plan) on every case of
 tests/lane8_plan_ref.py, likewise, with xcd_remap (csrc/aof_xcd_remap.hpp, the text the kernels run) a permutation for every
-total up to 4 096 and equal to the model's at every probe; fastdiv_make against the division it replaces."""
+total up to 4 096 and equal to the model's at every probe; fastdiv_make against the division it replaces; the stream bank's
+bound per-stream tables (csrc/aof_bank_tables.hpp: what a binding call accepts, which tables a push uses and the order of its
+refusals) and the flags of one per-stream table of OpticalFlowBank (facade/src/bank_table.hpp) over runs of ticks, both
+against values written out in the selftest."""
 import os
 import subprocess
 
@@ -25,7 +28,7 @@ def test_host_logic_is_clean_under_asan_ubsan(tmp_path):
     exe = tmp_path / "host_selftest"
     cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
            "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(pkg, "csrc"),
-           "-I" + os.path.join(pkg, "facade", "include"),
+           "-I" + os.path.join(pkg, "facade", "include"), "-I" + os.path.join(pkg, "facade", "src"),
            os.path.join(ROOT, "tests", "native", "host_selftest.cpp"), os.path.join(pkg, "csrc", "aof_params.cpp"),
            os.path.join(pkg, "facade", "src", "optical_flow_rad.cpp"), "-o", str(exe)]
     subprocess.run(cmd, check=True, timeout=300)
@@ -51,6 +54,10 @@ def test_host_logic_is_clean_under_asan_ubsan(tmp_path):
     assert "packer: 4012 frames equal to the facade's, lengths 52 and 56" in r.stdout
     assert "checksum: both steps and the facade's agree on 65536 x 256 inputs" in r.stdout
     assert "exposure: 256 bins and 2002 mean sample values equal to the public functions" in r.stdout
+    # the bank's bound tables and the facade's table flags: every case equal to the value written in the selftest
+    tables = [int(line.split()[4]) for line in r.stdout.splitlines() if line.startswith("host selftest: bank tables: ")]
+    assert len(tables) == 1 and tables[0] >= 25, r.stdout
+    assert "host selftest: facade table: 21 steps, copies and bindings as written" in r.stdout
     assert "fast_div: 20416 divisors, all numerators below 65536 and up to 196 around multiples up to 2^31 equal to n / d" in r.stdout
     # cols_plan_make == the model, on every case of every list
     assert f"cols plan: {len(cases)} cases" in r.stdout and len(cases) >= 60
