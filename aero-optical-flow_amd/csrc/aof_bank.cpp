@@ -23,7 +23,7 @@ size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // 1 536: 16.2 / 18.1, 2 048: 20.8 / 19.2, 4 096: 33.8 / 26.7; 128x128 on two levels 1 024: 39.9 / 48.3, 1 536: 50.1 /
 // 54.6, 2 048: 69.5 / 62.3, 4 096: 126.0 / 94.3.  A workgroup per stream wins until the grid is six rounds of the
 // device's 256 compute units; beyond that the grouped flow kernels make up for the commit kernel's second pass over
-// the new frames.  (Flow alone crosses at 128 pairs, kSmallMaxPairs of aof_batch.cpp: the tick's write-back and tail
+// the new frames.  (Flow alone crosses at 128 pairs, kSmallMaxPairs of aof_batch_plan.hpp: the tick's write-back and tail
 // ride along in the one launch and cost a launch and a pass of their own on the composed path.)
 constexpr int32_t kBankFusedMaxStreams = 1536;
 // The same for aof_bank_push_camera_device, whose composed path carries a third launch (the ingest kernel into the

@@ -119,11 +119,11 @@ int aof_create(const aof_params *p, int device, aof_ctx **out)
 
     aof_ctx *ctx = new (std::nothrow) aof_ctx();   // (zeroed)
     if (!ctx) return -ENOMEM;
-    ctx->params = *p;
+    ctx->cfg.params = *p;
     ctx->device = device;
-    ctx->cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    grid_for_level(*p, 0, &ctx->g0);
-    if (p->pyramid_levels == 2) grid_for_level(*p, 1, &ctx->g1);
+    ctx->cfg.cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    grid_for_level(*p, 0, &ctx->cfg.g0);
+    if (p->pyramid_levels == 2) grid_for_level(*p, 1, &ctx->cfg.g1);
     std::snprintf(ctx->err, sizeof(ctx->err), "ok");
     if (p->tile == 8 && p->search == 4) {   // the flat lane8 search can reduce in its own launch
         DeviceGuard guard(device);
@@ -152,7 +152,7 @@ int aof_create(const aof_params *p, int device, aof_ctx **out)
     ctx->votes.separate = true;   // the in-launch reduction is opt-in (aof_set_reduce_fusion)
     // exact pruning wherever it pays (include/aof.h): 16x16 tiles by a probe per pair, 8x8 tiles by what the
     // context's previous launches reported
-    ctx->search_mode = AOF_SEARCH_ADAPTIVE;
+    ctx->cfg.search_mode = AOF_SEARCH_ADAPTIVE;
     ctx->adapt.belief = -1;
     ctx->adapt.stats.belief = -1;
 
@@ -199,7 +199,7 @@ void aof_destroy(aof_ctx *ctx)
 
 const char *aof_last_error(const aof_ctx *ctx) { return ctx ? ctx->err : "null context"; }
 
-int aof_get_search_mode(const aof_ctx *ctx) { return ctx ? ctx->search_mode : -EINVAL; }
+int aof_get_search_mode(const aof_ctx *ctx) { return ctx ? ctx->cfg.search_mode : -EINVAL; }
 
 int aof_get_search_stats(const aof_ctx *ctx, aof_search_stats *out)
 {
@@ -221,31 +221,31 @@ int aof_set_search_belief(aof_ctx *ctx, int belief)
 int aof_get_params(const aof_ctx *ctx, aof_params *out)
 {
     if (!ctx || !out) return -EINVAL;
-    *out = ctx->params;
+    *out = ctx->cfg.params;
     return 0;
 }
 
 int aof_set_force_generic(aof_ctx *ctx, int on)
 {
     if (!ctx) return -EINVAL;
-    kernel_choice_changes(ctx, (on != 0) != ctx->force_generic);
-    ctx->force_generic = on != 0;
+    kernel_choice_changes(ctx, (on != 0) != ctx->cfg.force_generic);
+    ctx->cfg.force_generic = on != 0;
     return 0;
 }
 
 int aof_set_search_mode(aof_ctx *ctx, int mode)
 {
     if (!ctx || mode < AOF_SEARCH_EXHAUSTIVE || mode > AOF_SEARCH_ADAPTIVE) return -EINVAL;
-    kernel_choice_changes(ctx, mode != ctx->search_mode);
-    ctx->search_mode = mode;
+    kernel_choice_changes(ctx, mode != ctx->cfg.search_mode);
+    ctx->cfg.search_mode = mode;
     return 0;
 }
 
 int aof_set_split_coarse(aof_ctx *ctx, int on)
 {
     if (!ctx) return -EINVAL;
-    kernel_choice_changes(ctx, (on != 0) != ctx->split_coarse);
-    ctx->split_coarse = on != 0;
+    kernel_choice_changes(ctx, (on != 0) != ctx->cfg.split_coarse);
+    ctx->cfg.split_coarse = on != 0;
     return 0;
 }
 
@@ -276,7 +276,7 @@ int aof_debug_vote_deadline_ticks(aof_ctx *ctx, uint32_t ticks)
 int aof_debug_tile16_verdicts(aof_ctx *ctx, const uint8_t *verdicts, int count)
 {
     if (!ctx) return -EINVAL;
-    if (ctx->params.tile != 16) return fail(ctx, -EINVAL, "verdicts of the 16x16 search on a %dx%d context", ctx->params.tile, ctx->params.tile);
+    if (ctx->cfg.params.tile != 16) return fail(ctx, -EINVAL, "verdicts of the 16x16 search on a %dx%d context", ctx->cfg.params.tile, ctx->cfg.params.tile);
     if (count < 0 || count > kMaxForcedVerdicts) return fail(ctx, -EINVAL, "%d verdicts: 0 .. %d", count, kMaxForcedVerdicts);
     if (count > 0 && !verdicts) return fail(ctx, -EINVAL, "null verdicts");
     Tile16Verdicts f = {};

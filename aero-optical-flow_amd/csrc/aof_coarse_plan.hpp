@@ -109,6 +109,13 @@ inline CoarsePlan coarse_plan_make(int w, int h, int64_t pair_stride, uintptr_t 
     return p;
 }
 
+// The plan of a launch's arguments (first_generation: the CUs of the context's device).
+inline CoarsePlan coarse_plan_of(const CoarseArgs &a)
+{
+    return coarse_plan_make(a.w, a.h, a.pair_stride, reinterpret_cast<uintptr_t>(a.prev), reinterpret_cast<uintptr_t>(a.cur), a.grid,
+                            a.tail.range, a.tile, a.search, a.subpixel, a.n_pairs, a.first_generation);
+}
+
 constexpr int kPyramidThreads = 256;
 constexpr int kPyramidItemsPerBlock = 1024;    // 16-px x 2-row items per workgroup
 

@@ -4,8 +4,25 @@
 #include <cstdint>
 
 #include "aof_internal.hpp"
+#include "aof_small_plan.hpp"   // lane8_plan_supported
 
 namespace aof {
+
+// The pruned search on dense grids as a column walk (k_search_cols8.hip): a lane keeps the lower half of its window for
+// the block below.  Same modes (a.prune 1 / 2), same report as the chunk walk.
+inline bool lane8_cols_supported(const SearchArgs &a)
+{
+    // a dense grid whose next block row is the same window eight rows further down; one unit per column and segment
+    return lane8_plan_supported(a) && a.grid.step_y == 8 && a.grid.nx >= 16 && a.grid.ny >= 2 && a.grid.blocks() > 256;
+}
+
+// tail + votes: the reduction in the same launch (k_flow_lane8_cols), as launch_search_lane8 does for the exhaustive scan
+inline bool lane8_cols_votes_supported(const SearchArgs &a, const VoteMem &votes, int64_t capacity_pairs)
+{
+    const int n = 2 * (2 * a.hist_range + 1) + 1;
+    if (!lane8_cols_supported(a) || !votes.base || !votes.fault || n > 62 || votes.stride < (uint32_t)(2 + 2 * n)) return false;
+    return a.n_pairs <= capacity_pairs;   // (one launch: capacity is far below the 31-bit unit index)
+}
 
 // (outside the anonymous namespace: profilers print kernel names with their parameter types, and the tools cut the
 //  name at the first "(anonymous namespace)::")

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include "aof_bank_tables.hpp"
+#include "aof_batch_plan.hpp"   // BatchConfig, AdaptiveSearch
 #include "aof_internal.hpp"
 
 namespace aof {
@@ -64,17 +65,6 @@ struct InLaunchReduce {
     bool captured;              // a captured graph holds an in-launch reduction: eager launches keep to K3
 };
 
-// ADAPTIVE search of 8x8 contexts (choose_lane8): what the pruned kernel's last reporting launch said, in pinned host
-// words behind the fault word (same allocation), and what the context does with it.
-struct AdaptiveSearch {
-    uint32_t *slots;            // kPruneSlots words
-    uint32_t launch_no;         // number of the last reporting launch (its low 16 bits tag the words)
-    uint32_t expected;          // words that launch writes, 0 = none yet
-    int belief;                 // -1 nothing known yet, 0 pruning does not pay on this context's images, 1 it does
-    int since_probe;            // exhaustive launches since the last look
-    aof_search_stats stats;
-};
-
 struct Profiling {
     bool on;
     uint32_t mask;
@@ -119,14 +109,9 @@ void free_host_state(aof_ctx *ctx);
 }  // namespace aof
 
 struct aof_ctx {
-    aof_params params;
-    aof::Grid g0, g1;
+    aof::BatchConfig cfg;       // params, grids, CUs of `device`, search mode and the kernel-choice switches: what the batch plan reads
     int device;
-    int cus;                    // compute units of `device`
     char err[256];
-    int search_mode;
-    bool force_generic;
-    bool split_coarse;          // run K1 / level-1 search / level-1 reduce as separate kernels
     int bank_path;              // aof_set_bank_path: 0 the library chooses, 1 the one-launch tick kernel, 2 the composed path
     aof::BankTables bank;       // aof_set_bank_streams / _sensors / _pixel_formats / _binning: the caller's per-stream arrays (aof_bank_tables.hpp)
     bool graph_disabled;        // per-call graphs switched off, or a capture failed once: stay on the plain path

@@ -70,7 +70,7 @@ struct VoteMem {
     uint32_t deadline_ticks;   // finaliser waves give up after this many ticks of the 100 MHz counter
 };
 
-// What the pruned lane8 search tells the host about itself (the ADAPTIVE mode of 8x8 contexts, aof_batch.cpp):
+// What the pruned lane8 search tells the host about itself (the ADAPTIVE mode of 8x8 contexts, choose_lane8 in aof_batch_plan.hpp):
 // one workgroup in `stride` stores how many of its first wave's chunks left with "pruning pays" into a word of
 // pinned host memory: tag (low 16 bits of launch_no) << 16 | paying << 8 | chunks.  Plain stores, nobody waits
 // for them: the host reads whatever has arrived when it enqueues the next launch.  Speed only, never results.
@@ -164,7 +164,6 @@ struct PyramidArgs {
 // hipError_t of the launch as int (0 = ok).
 int launch_pyramid(const PyramidArgs &a, void *stream);   // zeroes a.sums first
 int launch_zero_words(uint32_t *words, int64_t count, void *stream);   // (a kernel: replays correctly from a hipGraph)
-bool coarse_fused_supported(const CoarseArgs &a);
 int launch_coarse_fused(const CoarseArgs &a, void *stream);
 int launch_search_generic(const SearchArgs &a, void *stream);
 // K2b: half-pixel refinement of records written by an integer search (tile 8 or 16; today only
@@ -172,21 +171,16 @@ int launch_search_generic(const SearchArgs &a, void *stream);
 int launch_refine(const SearchArgs &a, void *stream);
 // Lane-per-block kernel straight from global memory for B=8, S=4 on ANY grid / width /
 // predictor (sparse PX4Flow grid, rows that are no multiple of 16 bytes), half-pixel refinement
-// included.
-bool lane8_supported(const SearchArgs &a);
+// included (lane8_plan_supported, aof_small_plan.hpp).
 // tail + votes: the reduction runs inside the same launch (votes through agent-scope atomics into the
-// context's vote memory, the last wave of a pair writes its flow record); no K3 follows.
-bool lane8_votes_supported(const SearchArgs &a, const VoteMem &votes, int64_t capacity_pairs);
+// context's vote memory, the last wave of a pair writes its flow record); no K3 follows (lane8_votes_verdict,
+// aof_lane8_plan.hpp).
 int launch_search_lane8(const SearchArgs &a, void *stream, const FlowTail *tail = nullptr,
                         const VoteMem *votes = nullptr, PruneReport *report = nullptr);
 // The pruned kernels carry their hints from block to block of a wave and need a launch large enough for walks of three
 // blocks before that pays: at least kPruneMinChunks (below) 256-block chunks (lane8_flat_plan, aof_lane8_plan.hpp).
-bool lane8_prune_large(const SearchArgs &a);
-// The pruned search on dense grids as a column walk (k_search_cols8.hip): a lane keeps the lower half of its window for
-// the block below.  Same modes (a.prune 1 / 2), same report.
-bool lane8_cols_supported(const SearchArgs &a);
-// tail + votes: the reduction in the same launch (k_flow_lane8_cols), as launch_search_lane8 does for the exhaustive scan
-bool lane8_cols_votes_supported(const SearchArgs &a, const VoteMem &votes, int64_t capacity_pairs);
+// The pruned search on dense grids as a column walk (k_search_cols8.hip; lane8_cols_supported, aof_cols8_plan.hpp).  Same
+// modes (a.prune 1 / 2), same report.  tail + votes: the reduction in the same launch (lane8_cols_votes_supported).
 int launch_search_lane8_cols(const SearchArgs &a, void *stream, PruneReport *report = nullptr, const FlowTail *tail = nullptr,
                              const VoteMem *votes = nullptr);
 // Smallest launch (in 256-block chunks) the ADAPTIVE mode lets prune.  Round 5 sweep, bench.py --pairs N as it chooses
@@ -195,12 +189,10 @@ int launch_search_lane8_cols(const SearchArgs &a, void *stream, PruneReport *rep
 // 96: 22.2 / 20.4, 128: 23.0-24.5 / 26.0, 192: 26.6 / 38.0, 256: 33.8 / 49.7 -- a walk of two blocks pays for its vote
 // and its second round of row loads with too little; from three blocks on (112 VGA pairs) it wins.
 constexpr int64_t kPruneMinChunks = 2048;
-// Grids of 8..256 blocks: a workgroup owns whole pairs and also writes their flow records (no K3).
-int lane8_group(const SearchArgs &a);  // pairs per workgroup, 0 = not applicable
+// Grids of 8..256 blocks: a workgroup owns whole pairs and also writes their flow records (no K3; lane8_group_plan,
+// aof_small_plan.hpp).
 int launch_flow_lane8(const SearchArgs &a, const FlowTail &tail, void *stream);
-// LDS-tiled (block, dy)-per-lane kernel for B=16, S=8 on a dense grid (any predictor).
-bool tile16_supported(const SearchArgs &a);
-bool tile16_refines(const SearchArgs &a);   // the launch also writes the half-pixel directions (no K2b behind it)
+// LDS-tiled (block, dy)-per-lane kernel for B=16, S=8 on a dense grid (any predictor; tile16_plan, aof_tile16_plan.hpp).
 // Test hook of the adaptive 16x16 search (aof_debug_tile16_verdicts): pair i gets v[i % count] instead of the probe's
 // verdict; count 0 = the probe decides.  Only launches with prune == 2 read it.
 constexpr int kMaxForcedVerdicts = 8;
@@ -209,8 +201,8 @@ struct Tile16Verdicts {
     int32_t count;
 };
 int launch_search_tile16(const SearchArgs &a, void *stream, const Tile16Verdicts &forced);
-// Small pairs (frames fit LDS, grids <= 256 blocks), one or two levels, in one launch: one workgroup per pair.
-bool flow_small_supported(const SmallArgs &a);
+// Small pairs (frames fit LDS, grids <= 256 blocks), one or two levels, in one launch: one workgroup per pair
+// (small_plan_make, aof_small_plan.hpp).
 int launch_flow_small(const SmallArgs &a, void *stream);
 // One pair, the record published in pinned host memory by ONE tagged 16-byte store (top byte of `count` =
 // low byte of *tag, which the host wrote before the launch): the per-call path polls for it.
@@ -341,7 +333,7 @@ struct BankSensors {
     const uint8_t *bins;
 };
 // One launch per tick: a workgroup per stream computes the pair with flow_small_pair, runs the stream's tail and
-// stores the new frame (sm: the small-pair plan of (bank frames, tick frames), flow_small_supported).  With
+// stores the new frame (sm: the small-pair plan of (bank frames, tick frames), small_plan_make).  With
 // a.cam.camera the workgroup fetches the crop's rows from the stream's sensor frame itself (a.frames is not read).
 int launch_bank_tick(const SmallArgs &sm, const BankArgs &a, void *stream, const BankSensors &sen = BankSensors{nullptr, 0, 0, nullptr, nullptr});
 // Behind aof_flow_batch_device on (bank frames, tick frames): the tail of every stream and the masked copy of the

@@ -21,7 +21,7 @@ void forget_host_state(aof_ctx *ctx) { ctx->host = {}; }
 
 int alloc_host_state(aof_ctx *ctx)
 {
-    const aof_params &p = ctx->params;
+    const aof_params &p = ctx->cfg.params;
     HostState &h = ctx->host;
     const size_t frame = (size_t)p.width * p.height;
     aof_ws_layout L;
@@ -29,8 +29,8 @@ int alloc_host_state(aof_ctx *ctx)
     HIP_TRY(ctx, hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking));
     for (int i = 0; i < 2; i++) HIP_TRY(ctx, hipMalloc((void **)&h.d_frames[i], frame));
     for (int i = 0; i < 2; i++) HIP_TRY(ctx, hipMalloc((void **)&h.d_pair[i], frame));
-    HIP_TRY(ctx, hipMalloc((void **)&h.d_blocks, sizeof(aof_block) * (size_t)ctx->g0.blocks()));
-    HIP_TRY(ctx, hipMalloc((void **)&h.d_subdirs, (size_t)ctx->g0.blocks()));
+    HIP_TRY(ctx, hipMalloc((void **)&h.d_blocks, sizeof(aof_block) * (size_t)ctx->cfg.g0.blocks()));
+    HIP_TRY(ctx, hipMalloc((void **)&h.d_subdirs, (size_t)ctx->cfg.g0.blocks()));
     HIP_TRY(ctx, hipMalloc(&h.d_ws, L.total_bytes));
     h.ws_bytes = L.total_bytes;
     HIP_TRY(ctx, hipMalloc((void **)&h.d_flow, sizeof(aof_flow)));
@@ -93,7 +93,7 @@ inline void retag_stale_record(aof_flow *pinned, uint32_t tag)
 void build_push_graph(aof_ctx *ctx, int slot)
 {
     HostState &h = ctx->host;
-    const aof_params &p = ctx->params;
+    const aof_params &p = ctx->cfg.params;
     const size_t bytes = (size_t)p.width * p.height;
     hipGraph_t graph = nullptr;
     if (hipStreamBeginCapture(h.stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
@@ -135,11 +135,11 @@ void build_push_graph(aof_ctx *ctx, int slot)
 int run_one(aof_ctx *ctx, const uint8_t *d_prev, const uint8_t *d_cur, aof_block *blocks, uint8_t *subdirs, aof_flow *flow)
 {
     HostState &h = ctx->host;
-    const aof_params &p = ctx->params;
+    const aof_params &p = ctx->cfg.params;
     int rc = aof_flow_batch_device(ctx, d_prev, d_cur, (int64_t)p.width * p.height, 1, h.d_blocks, h.d_subdirs, h.d_flow,
                                    h.d_ws, h.ws_bytes, h.stream);
     if (rc) return rc;
-    const size_t nb = (size_t)ctx->g0.blocks();
+    const size_t nb = (size_t)ctx->cfg.g0.blocks();
     HIP_TRY(ctx, hipMemcpyAsync(flow, h.d_flow, sizeof(aof_flow), hipMemcpyDeviceToHost, h.stream));
     if (blocks)
         HIP_TRY(ctx, hipMemcpyAsync(blocks, h.d_blocks, nb * sizeof(aof_block), hipMemcpyDeviceToHost, h.stream));
@@ -158,7 +158,7 @@ int stream_push_graph(aof_ctx *ctx, const uint8_t *frame, aof_flow *flow, int sl
 {
     HostState &h = ctx->host;
     ctx->res.frame_req[slot] = 0;   // (written outside a resident request)
-    std::memcpy(h.zero_copy ? h.h_frames[slot] : h.h_frame, frame, (size_t)ctx->params.width * ctx->params.height);
+    std::memcpy(h.zero_copy ? h.h_frames[slot] : h.h_frame, frame, (size_t)ctx->cfg.params.width * ctx->cfg.params.height);
     const bool tagged = h.push_tagged[slot];
     uint32_t tag = 0;
     if (tagged) {
@@ -201,7 +201,7 @@ int stream_push_resident(aof_ctx *ctx, const uint8_t *frame, aof_flow *flow, int
 {
     HostState &h = ctx->host;
     Resident &r = ctx->res;
-    const size_t bytes = (size_t)ctx->params.width * ctx->params.height;
+    const size_t bytes = (size_t)ctx->cfg.params.width * ctx->cfg.params.height;
     *served = false;
     if (!r.k.box) {
         // The kernel's own stream at the HIGHEST priority: the runtime keeps a pool of hardware queues per priority,
@@ -387,7 +387,7 @@ int aof_flow_pair_host(aof_ctx *ctx, const uint8_t *prev, const uint8_t *cur, ao
     int rc = ensure_host_state(ctx);
     if (rc) return rc;
     HostState &h = ctx->host;
-    const size_t frame = (size_t)ctx->params.width * ctx->params.height;
+    const size_t frame = (size_t)ctx->cfg.params.width * ctx->cfg.params.height;
     // own scratch frames: the streaming state (aof_stream_push_host) is left untouched
     HIP_TRY(ctx, hipMemcpyAsync(h.d_pair[0], prev, frame, hipMemcpyHostToDevice, h.stream));
     HIP_TRY(ctx, hipMemcpyAsync(h.d_pair[1], cur, frame, hipMemcpyHostToDevice, h.stream));
@@ -403,7 +403,7 @@ int aof_stream_push_host(aof_ctx *ctx, const uint8_t *frame, aof_flow *flow)
     int rc = ensure_host_state(ctx);
     if (rc) return rc;
     HostState &h = ctx->host;   // (the same object after a rebuild: ensure_host_state refills it in place)
-    const size_t bytes = (size_t)ctx->params.width * ctx->params.height;
+    const size_t bytes = (size_t)ctx->cfg.params.width * ctx->cfg.params.height;
     int slot = h.have_prev ? 1 - h.cur_slot : 0;
     if (h.have_prev) ctx->stats.calls++;
     if (h.have_prev && ctx->res.on && h.zero_copy && !ctx->prof.on) {

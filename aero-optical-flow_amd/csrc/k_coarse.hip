@@ -330,27 +330,14 @@ __global__ __launch_bounds__(kThreads) void k_coarse(CoarseArgs a)
 
 }  // namespace
 
-namespace {
-
-CoarsePlan plan_of(const CoarseArgs &a)
-{
-    return coarse_plan_make(a.w, a.h, a.pair_stride, reinterpret_cast<uintptr_t>(a.prev), reinterpret_cast<uintptr_t>(a.cur), a.grid,
-                            a.tail.range, a.tile, a.search, a.subpixel, a.n_pairs, a.first_generation);
-}
-
-}  // namespace
 
 // The plan (rows per sweep, fast-div constants, LDS, stagger, workgroups) and the verdict: aof_coarse_plan.hpp.
-size_t coarse_lds_bytes(const CoarseArgs &a) { return coarse_plan_lds(a.w, a.h, a.grid); }
-
-bool coarse_fused_supported(const CoarseArgs &a) { return plan_of(a).verdict == COARSE_OK; }
-
 int launch_coarse_fused(const CoarseArgs &a, void *stream)
 {
     if (a.n_pairs == 0) return 0;
     // first_generation: the CU count of the context's device, set by the caller
     if (a.first_generation <= 0) return (int)hipErrorInvalidValue;
-    const CoarsePlan plan = plan_of(a);
+    const CoarsePlan plan = coarse_plan_of(a);
     if (plan.verdict != COARSE_OK) return (int)hipErrorInvalidValue;
     CoarseArgs k = a;
     k.div_nb = plan.div_nb;

@@ -131,9 +131,6 @@ __global__ __launch_bounds__(kThreads) void k_flow_resident(SmallArgs a, Residen
 
 }  // namespace
 
-// (the conditions, in order: small_plan_make, aof_small_plan.hpp)
-bool flow_small_supported(const SmallArgs &a) { return small_plan_make(a).verdict == SMALL_OK; }
-
 int launch_flow_resident(const SmallArgs &a, ResidentBox *box, aof_flow *host_record, const uint8_t *frame_a,
                          const uint8_t *frame_b, uint32_t served, uint32_t launch_no, uint64_t idle_ticks,
                          uint64_t life_ticks, bool deaf, void *stream)

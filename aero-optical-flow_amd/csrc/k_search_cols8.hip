@@ -8,19 +8,6 @@
 
 namespace aof {
 
-bool lane8_cols_supported(const SearchArgs &a)
-{
-    // a dense grid whose next block row is the same window eight rows further down; one unit per column and segment
-    return lane8_supported(a) && a.grid.step_y == 8 && a.grid.nx >= 16 && a.grid.ny >= 2 && a.grid.blocks() > 256;
-}
-
-bool lane8_cols_votes_supported(const SearchArgs &a, const VoteMem &votes, int64_t capacity_pairs)
-{
-    const int n = 2 * (2 * a.hist_range + 1) + 1;
-    if (!lane8_cols_supported(a) || !votes.base || !votes.fault || n > 62 || votes.stride < (uint32_t)(2 + 2 * n)) return false;
-    return a.n_pairs <= capacity_pairs;   // (one launch: capacity is far below the 31-bit unit index)
-}
-
 int launch_search_lane8_cols(const SearchArgs &a, void *stream, PruneReport *report, const FlowTail *tail, const VoteMem *votes)
 {
     if (report) report->expected = 0;

@@ -11,8 +11,6 @@
 
 namespace aof {
 
-bool lane8_supported(const SearchArgs &a) { return lane8_plan_supported(a); }   // (aof_small_plan.hpp)
-
 namespace {
 
 // The arguments of slice p (lane8_flat_plan: at most kMaxItems (pair, block) items each).
@@ -40,13 +38,6 @@ FlowTail slice_tail(const FlowTail &tail, const Lane8FlatPlan &p)
 }
 
 }  // namespace
-
-bool lane8_votes_supported(const SearchArgs &a, const VoteMem &votes, int64_t capacity_pairs)
-{
-    return lane8_votes_verdict(a, &votes, capacity_pairs) == VOTES_OK;
-}
-
-bool lane8_prune_large(const SearchArgs &a) { return lane8_flat_plan(a, false, nullptr, 0).prune_large != 0; }
 
 // The launcher only launches: every number below is lane8_flat_plan's.
 int launch_search_lane8(const SearchArgs &a, void *stream, const FlowTail *tail, const VoteMem *votes, PruneReport *report)
@@ -84,9 +75,6 @@ int launch_search_lane8(const SearchArgs &a, void *stream, const FlowTail *tail,
     }
     return 0;
 }
-
-// Pairs per workgroup of the grouped kernel; 0 = the grid does not qualify (lane8_group_plan, aof_small_plan.hpp).
-int lane8_group(const SearchArgs &a) { return lane8_group_plan(a).ppw; }
 
 int launch_flow_lane8(const SearchArgs &a, const FlowTail &tail, void *stream)
 {

@@ -18,22 +18,14 @@
 #include "aof_internal.hpp"
 #include "aof_refine.hpp"
 #include "aof_sad.hpp"
+#include "aof_tile16_plan.hpp"   // kTile16Threads, kSide, the probe's constants and probe_samples; the launch plan
 
 namespace aof {
 
-bool tile16_refines(const SearchArgs &a);
-
 namespace {
 
-constexpr int kThreads = 512;
-constexpr int kSide = 17;  // 2S+1
 constexpr int kBoundRows = 2;  // tile rows summed for the lower bound of the pruned search
 // ADAPTIVE mode (the default of 16x16 contexts): the probe kernel below decides per pair.
-constexpr int kProbeThreads = 1024;        // a pair's ~1 200 probe items in two rounds
-constexpr int kProbeStride = 8;            // every eighth block in x and in y is probed (VGA-like grids: ~1.6 % of the blocks)
-constexpr int kProbeMaxBlocks = 128;       // sample blocks per pair at the most (the strides grow beyond that)
-// Blocks stride/2, stride/2 + stride, ... of an axis of n blocks.
-__host__ __device__ constexpr int probe_samples(int n, int stride) { return (n + stride - 1 - stride / 2) / stride; }
 // (thresholds from a same-box sweep over sensor noise 0 .. 40 LSB, profiles/r04_c5_adaptive_thresholds.txt: with
 //  6 x / 35 % the mode follows the faster of the two fixed modes within 5 % at every noise level but one, 8 %)
 constexpr uint32_t kFullOverBound = 6;     // a row can survive when its two-row bound <= this x the block's smallest bound
@@ -158,13 +150,13 @@ __device__ __forceinline__ void quad_join(u64 (&acc)[4], uint32_t &acc16)
 template <int kStageUnroll, typename Map>
 __device__ __forceinline__ void stage_chunks(int total, int tid, int delta, Map &&map)
 {
-    for (int c0 = tid; c0 < total; c0 += kStageUnroll * kThreads) {
+    for (int c0 = tid; c0 < total; c0 += kStageUnroll * kTile16Threads) {
         uint4 v[kStageUnroll];
         uint8_t *to[kStageUnroll];       // (LDS: one register each; kept from the address pass, not computed twice)
         bool shift[kStageUnroll];
 #pragma unroll
         for (int u = 0; u < kStageUnroll; u++) {
-            const int c = min(c0 + u * kThreads, total - 1);
+            const int c = min(c0 + u * kTile16Threads, total - 1);
             const uint8_t *src;
             bool is_cur;
             map(c, src, to[u], is_cur);
@@ -173,7 +165,7 @@ __device__ __forceinline__ void stage_chunks(int total, int tid, int delta, Map 
         }
 #pragma unroll
         for (int u = 0; u < kStageUnroll; u++) {
-            if (c0 + u * kThreads < total) {
+            if (c0 + u * kTile16Threads < total) {
                 uint4 w = v[u];
                 if (shift[u]) w = sat_add_u8x16(w, delta);
                 *reinterpret_cast<uint4 *>(to[u]) = w;
@@ -202,7 +194,7 @@ __device__ __forceinline__ void wave_append(uint16_t *list, uint32_t *count, boo
 __device__ __forceinline__ void list_survivors(const uint32_t *s_best, const uint16_t *s_pmin, uint16_t *s_list, uint32_t *s_count,
                                                int nx, const SearchArgs &a, int items, int tid)
 {
-    for (int item0 = tid - (tid & 63); item0 < items; item0 += kThreads) {   // whole waves
+    for (int item0 = tid - (tid & 63); item0 < items; item0 += kTile16Threads) {   // whole waves
         const int item = item0 + (tid & 63);
         bool keep = false;
         if (item < items) {
@@ -219,7 +211,7 @@ __device__ __forceinline__ void list_survivors(const uint32_t *s_best, const uin
 // summed out of LDS behind the search -- four lanes per block, four tile rows each, joined by shuffles --
 // instead of by a second pass over global memory (K2b, bound by the L1 rate of its per-lane row loads).
 template <bool PRUNE, bool REFINE>
-__global__ __launch_bounds__(kThreads) void k_search_tile16(SearchArgs a, uint32_t total_wgs)
+__global__ __launch_bounds__(kTile16Threads) void k_search_tile16(SearchArgs a, uint32_t total_wgs)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     constexpr int kLead = REFINE ? 1 : 0;            // cur rows staged above row 0 (and below row 31)
@@ -295,12 +287,12 @@ __global__ __launch_bounds__(kThreads) void k_search_tile16(SearchArgs a, uint32
         if (PRUNE && pays) stage_chunks<8>(cur_chunks + prev_chunks, tid, delta, where);   // (uniform in the workgroup)
         else stage_chunks<1>(cur_chunks + prev_chunks, tid, delta, where);
     }
-    for (int b = tid; b < nx; b += kThreads) s_best[b] = 0xFFFFFFFFu;
+    for (int b = tid; b < nx; b += kTile16Threads) s_best[b] = 0xFFFFFFFFu;
     __syncthreads();
 
     const int items = rows_ok ? kSide * nx : 0;
     if constexpr (!PRUNE) {
-        for (int item = tid; item < items; item += kThreads) {
+        for (int item = tid; item < items; item += kTile16Threads) {
             const int dyi = (int)fast_div((uint32_t)item, a.div_nx), bx = item - dyi * nx;
             const int xf = 16 * bx + px;                  // moved-frame column of the window start
             if (xf < 0 || xf + 32 > Wb) continue;         // window leaves the frame: block skipped below
@@ -326,7 +318,7 @@ __global__ __launch_bounds__(kThreads) void k_search_tile16(SearchArgs a, uint32
         // 0 = its candidates look alike (sensor noise: nothing could be dropped and the pruned steps would
         // cost 1.5x the exhaustive scan), so the workgroup runs the exhaustive scan; the records are the same.
         if (!pays) {
-            for (int item = tid; item < items; item += kThreads) {
+            for (int item = tid; item < items; item += kTile16Threads) {
                 const int dyi = (int)fast_div((uint32_t)item, a.div_nx), bx = item - dyi * nx;
                 const int xf = 16 * bx + px;
                 if (xf < 0 || xf + 32 > Wb) continue;
@@ -336,7 +328,7 @@ __global__ __launch_bounds__(kThreads) void k_search_tile16(SearchArgs a, uint32
         const int items_all = items;
         const int items = pays ? items_all : 0;   // (the pruned steps below then have nothing to do)
         if (hint >= 3u) {   // (sensor noise: deeper bounds; the pair's verdict is uniform in the workgroup)
-            for (int item = tid; item < items; item += kThreads) {
+            for (int item = tid; item < items; item += kTile16Threads) {
                 const int dyi = (int)fast_div((uint32_t)item, a.div_nx), bx = item - dyi * nx;
                 const int xf = 16 * bx + px;
                 uint32_t bound = 0xFFFFu;
@@ -347,7 +339,7 @@ __global__ __launch_bounds__(kThreads) void k_search_tile16(SearchArgs a, uint32
             }
         } else {
         const bool one_row = hint == 2u;
-        for (int item = tid; item < items; item += kThreads) {
+        for (int item = tid; item < items; item += kTile16Threads) {
             const int dyi = (int)fast_div((uint32_t)item, a.div_nx), bx = item - dyi * nx;
             const int xf = 16 * bx + px;
             uint32_t bound = 0xFFFFu;
@@ -360,7 +352,7 @@ __global__ __launch_bounds__(kThreads) void k_search_tile16(SearchArgs a, uint32
         __syncthreads();
         // (four lanes per block, four interleaved tile rows each, sums joined across the quad: the
         //  step is one item's latency long whatever the lane count, so it is kept a quarter item)
-        for (int q = tid; q < (rows_ok && pays ? 4 * ((nx + 15) / 16 * 16) : 0); q += kThreads) {   // whole waves: shuffles
+        for (int q = tid; q < (rows_ok && pays ? 4 * ((nx + 15) / 16 * 16) : 0); q += kTile16Threads) {   // whole waves: shuffles
             const int bx = q >> 2, part = q & 3;
             const int xf = 16 * bx + px;
             const bool in = bx < nx && !(xf < 0 || xf + 32 > Wb);
@@ -405,7 +397,7 @@ __global__ __launch_bounds__(kThreads) void k_search_tile16(SearchArgs a, uint32
         // quarter of those items (noise-dominated frames), the rest of the list skips it and is
         // summed completely at once -- the row then costs the exhaustive scan plus the probes.
         bool bound_pays = true;
-        for (int k0 = tid - (tid & 63); k0 < listed; k0 += kThreads) {   // whole waves
+        for (int k0 = tid - (tid & 63); k0 < listed; k0 += kTile16Threads) {   // whole waves
             const int k = k0 + (tid & 63);
             bool keep = false;
             int item = 0;
@@ -419,14 +411,14 @@ __global__ __launch_bounds__(kThreads) void k_search_tile16(SearchArgs a, uint32
                 }
             }
             wave_append(s_list2, s_count, keep, item);
-            if (k0 < kThreads && listed > kThreads) {   // after the first round (uniform)
+            if (k0 < kTile16Threads && listed > kTile16Threads) {   // after the first round (uniform)
                 __syncthreads();
-                bound_pays = 4 * (int)*s_count <= 3 * kThreads;
+                bound_pays = 4 * (int)*s_count <= 3 * kTile16Threads;
             }
         }
         __syncthreads();
         const int listed2 = (int)*s_count;
-        for (int k = tid; k < listed2; k += kThreads) {
+        for (int k = tid; k < listed2; k += kTile16Threads) {
             const int item = s_list2[k];
             const int dyi = (int)fast_div((uint32_t)item, a.div_nx), bx = item - dyi * nx;
             atomicMin(&s_best[bx], eval_item<16, 1>(s_prev, s_cur, W, dyi, bx, 16 * bx + px - sh, 0));
@@ -435,7 +427,7 @@ __global__ __launch_bounds__(kThreads) void k_search_tile16(SearchArgs a, uint32
     __syncthreads();
 
     // one lane per block: 4x4 gradient gate (tile bytes 6..9, rows 6..9) and the record
-    for (int bx = tid; bx < nx; bx += kThreads) {
+    for (int bx = tid; bx < nx; bx += kTile16Threads) {
         uint32_t mid[4];
 #pragma unroll
         for (int r = 0; r < 4; r++) {
@@ -466,7 +458,7 @@ __global__ __launch_bounds__(kThreads) void k_search_tile16(SearchArgs a, uint32
         // the four slices add up across the quad (integer sums: any order).  Whole waves: shuffles.
         uint8_t *subdirs = a.subdirs + pair * (int64_t)(nx * ny) + (int64_t)by * nx;
         constexpr int kParts = kRefineParts, kRows = 16 / kParts;
-        for (int q = tid; q < (kParts * nx + 63) / 64 * 64; q += kThreads) {
+        for (int q = tid; q < (kParts * nx + 63) / 64 * 64; q += kTile16Threads) {
             const int bx = q / kParts, part = q % kParts;
             const uint32_t key = bx < nx ? s_best[bx] : 0xFFFFFFFFu;
             const bool live = key != 0xFFFFFFFFu;
@@ -659,76 +651,41 @@ __global__ __launch_bounds__(kProbeThreads) void k_tile16_probe(SearchArgs a, ui
 // where the probe puts its separation figure (the search kernel reads the low byte alone).  The verdicts travel as a kernel
 // argument: no host copy, so the launch can be captured into a graph.
 constexpr uint32_t kForcedVerdictPattern = 0x5A5A00u;
-constexpr int kFillThreads = 256;
 __global__ __launch_bounds__(kFillThreads) void k_tile16_fill_verdicts(uint32_t *hints, int64_t n_pairs, Tile16Verdicts f)
 {
     const int64_t i = (int64_t)blockIdx.x * kFillThreads + threadIdx.x;
     if (i < n_pairs) hints[i] = (uint32_t)f.v[i % f.count] | kForcedVerdictPattern;
 }
 
-size_t tile16_lds(const SearchArgs &a)
-{
-    size_t bytes = (size_t)48 * a.w + 4 * (size_t)a.grid.nx + 16;
-    if (tile16_refines(a)) bytes += 2 * (size_t)a.w + 16 + 16;   // cur rows -1 and 32, the pad in front, dword reads past the last ring
-    if (a.prune) bytes += 4 * (size_t)kSide * a.grid.nx + 16;   // lower bounds + item list + counter
-    return bytes;
-}
-
 }  // namespace
 
-// Half-pixel refinement runs inside the search launch (k_search_tile16<.., true>) whenever directions are wanted.
-bool tile16_refines(const SearchArgs &a) { return a.subpixel && a.subdirs; }
-
-bool tile16_supported(const SearchArgs &a)
-{
-    if (a.tile != 16 || a.search != 8) return false;
-    const int org = a.subpixel ? 1 : 0;  // origin S+1: K2b follows
-    if (a.grid.x0 != 8 + org || a.grid.y0 != 8 + org || a.grid.step_x != 16 || a.grid.step_y != 16) return false;
-    if (a.w % 16 || a.pair_stride % 16) return false;
-    if (reinterpret_cast<uintptr_t>(a.prev) % 16 || reinterpret_cast<uintptr_t>(a.cur) % 16) return false;
-    if ((int64_t)a.w * a.h > 0x7FFFFFFF) return false;
-    return tile16_lds(a) <= 156 * 1024;
-}
-
+// The launcher only launches: every number below is tile16_plan's.
 int launch_search_tile16(const SearchArgs &a, void *stream, const Tile16Verdicts &forced)
 {
     if (a.n_pairs == 0) return 0;
-    const int64_t total = a.n_pairs * a.grid.ny;
-    if (total > 0x7FFFFFFF) return (int)hipErrorInvalidValue;
-    if (a.prune == 2 && forced.count > 0) {   // (test hook: the verdicts are set, no probe runs)
-        if (!a.hints || forced.count > kMaxForcedVerdicts) return (int)hipErrorInvalidValue;
-        hipLaunchKernelGGL(k_tile16_fill_verdicts, dim3((uint32_t)((a.n_pairs + kFillThreads - 1) / kFillThreads)), dim3(kFillThreads), 0,
-                           static_cast<hipStream_t>(stream), a.hints, a.n_pairs, forced);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-    } else if (a.prune == 2) {   // ADAPTIVE: judge every pair first (hints in the workspace), then the search decides per pair
-        if (!a.hints) return (int)hipErrorInvalidValue;
-        // every kProbeStride-th block per axis; an axis with fewer blocks than that is sampled more densely (at least one
-        // block), and the strides grow -- the longer axis first -- until the sample fits the kernel's table
-        int stx = kProbeStride, sty = kProbeStride;
-        while (stx > 1 && probe_samples(a.grid.nx, stx) == 0) stx /= 2;
-        while (sty > 1 && probe_samples(a.grid.ny, sty) == 0) sty /= 2;
-        while (probe_samples(a.grid.nx, stx) * probe_samples(a.grid.ny, sty) > kProbeMaxBlocks) {
-            if (probe_samples(a.grid.nx, stx) >= probe_samples(a.grid.ny, sty)) stx *= 2; else sty *= 2;
-        }
-        hipLaunchKernelGGL(k_tile16_probe, dim3((uint32_t)a.n_pairs), dim3(kProbeThreads), 0, static_cast<hipStream_t>(stream), a,
-                           a.hints, stx, sty);
+    const Tile16Plan p = tile16_plan(a, forced.count);
+    if (p.refused) return (int)hipErrorInvalidValue;
+    if (p.front == TILE16_FRONT_FILL) {
+        hipLaunchKernelGGL(k_tile16_fill_verdicts, dim3((uint32_t)p.front_wgs), dim3(kFillThreads), 0, static_cast<hipStream_t>(stream), a.hints,
+                           a.n_pairs, forced);
+    } else if (p.front == TILE16_FRONT_PROBE) {
+        hipLaunchKernelGGL(k_tile16_probe, dim3((uint32_t)p.front_wgs), dim3(kProbeThreads), 0, static_cast<hipStream_t>(stream), a, a.hints,
+                           p.stx, p.sty);
+    }
+    if (p.front != TILE16_FRONT_NONE) {
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
     }
     SearchArgs k = a;
     k.div_nx = fastdiv_make((uint32_t)a.grid.nx);   // item -> (dy row, block): a run-time division costs ~20 VALU per lane and item
-    const size_t lds = tile16_lds(a);
     void (*fn)(SearchArgs, uint32_t) =
-        tile16_refines(a) ? (a.prune ? k_search_tile16<true, true> : k_search_tile16<false, true>)
-                          : (a.prune ? k_search_tile16<true, false> : k_search_tile16<false, false>);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        p.refine ? (p.prune ? k_search_tile16<true, true> : k_search_tile16<false, true>)
+                 : (p.prune ? k_search_tile16<true, false> : k_search_tile16<false, false>);
+    if (p.attr) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
         if (e != hipSuccess) return (int)e;
     }
-    hipLaunchKernelGGL(fn, dim3((uint32_t)total), dim3(kThreads), lds, static_cast<hipStream_t>(stream), k,
-                       (uint32_t)total);
+    hipLaunchKernelGGL(fn, dim3((uint32_t)p.total), dim3(kTile16Threads), p.lds, static_cast<hipStream_t>(stream), k, (uint32_t)p.total);
     return (int)hipGetLastError();
 }
 

@@ -1,6 +1,6 @@
 """The launch plans of a two-level pair's coarse passes in plain Python -- k_coarse's sweep plan and K1's strip plan
 (csrc/aof_coarse_plan.hpp: coarse_plan_make, pyramid_plan_make) --, what the kernels make of them lane by lane (k_coarse's
-phase 1, k_pyramid_vec, k_pyramid_scalar), which kernel a batch's coarse pass is made by (aof_batch.cpp: plan_batch), the
+phase 1, k_pyramid_vec, k_pyramid_scalar), which kernel a batch's coarse pass is made by (batch_plan_ref.py, the model of aof_batch_plan.hpp: plan_batch), the
 names of the paths a launch can take through all of it, and the case lists of tests/test_coarse_plan_ref.py,
 tests/test_host_asan.py (the same plans from the C++ functions) and tests/test_gpu_coarse_plan.py (every case of
 GPU_CASES on the device, against the oracle).
@@ -28,7 +28,6 @@ STAGGER_GROUPS, STAGGER_BYTES_PER_US = 3, 75000
 K1_THREADS, K1_ITEMS = 256, 1024
 # the verdict of coarse_fused_supported: the first condition that fails (enum CoarseVerdict, in this order)
 VERDICTS = ("ok", "tile", "search", "subpixel", "width", "height", "stride", "chunks", "prev", "cur", "grid", "bins", "pairs", "lds")
-SMALL_MAX_PAIRS, SMALL_THREADS, SMALL_PAD = 128, 256, 16   # aof_batch.cpp, aof_flow_small.hpp
 CENSUS_CUS = 256   # the CU-relative pair counts of the case lists are evaluated here on the host
 BASE = 0x7F0000000000   # a frame address for the plans: 16-byte aligned
 
@@ -278,31 +277,12 @@ def frame_layout(c):
     return frame + c["stride_extra"], BASE + c["prev_off"], BASE + (1 << 32) + c["cur_off"]
 
 
-def groups(nb, tile, search):
-    """A level's search is the grouped lane-per-block kernel (a workgroup owns whole pairs): grids of 8 .. 256 blocks."""
-    return tile == 8 and search == 4 and 8 <= nb <= 256
-
-
 def coarse_kind(c, cus=CENSUS_CUS):
     """'small' (k_flow_small does the whole batch), 'fused' (k_coarse), 'k1' (K1, then the level-1 search where there are
-    two levels), 'none' (one level without equalisation)."""
-    w, h, n = c["w"], c["h"], n_pairs_of(c, cus)
-    two = c["levels"] == 2
-    stride, prev, cur = frame_layout(c)
-    g0, g1 = (dense_grid(w, h, l, c["tile"], c["search"], c["subpixel"]) for l in (0, 1))
-    nb0, nb1 = g0[4] * g0[5], g1[4] * g1[5]
-    frame0, frame1 = w * h, (w // 2) * (h // 2)
-    lds = 2 * (frame0 + SMALL_PAD) + (2 * ((frame1 + SMALL_PAD + 15) // 16 * 16) if two else 0)
-    small_class = (not c["split"] and groups(nb0, c["tile"], c["search"]) and (not two or groups(nb1, c["tile"], c["search"]))
-                   and w % 16 == 0 and (n <= 1 or stride % 16 == 0) and prev % 16 == 0 and cur % 16 == 0 and (not two or h % 2 == 0)
-                   and lds + 4096 <= LDS_LIMIT)
-    if small_class and n <= SMALL_MAX_PAIRS:
-        return "small"
-    if not two and not c["mean_subtract"]:
-        return "none"
-    if two and not c["split"] and case_coarse_plan(c, cus)["supported"]:
-        return "fused"
-    return "k1"
+    two levels), 'none' (one level without equalisation): batch_plan_ref owns the rule."""
+    import batch_plan_ref as bp
+    pl = bp.plan(bp.of_coarse(c, cus))
+    return "small" if pl["small"] else pl["coarse"]
 
 
 def case_coarse_plan(c, cus=CENSUS_CUS):
@@ -318,16 +298,11 @@ def case_pyramid_plan(c, cus=CENSUS_CUS):
 
 
 def counters(c, cus=CENSUS_CUS):
-    """The launches of one call by profiling counter: K_PYRAMID, K_SEARCH_L1, K_REDUCE_L1 (None: not asserted)."""
-    kind = coarse_kind(c, cus)
-    if kind in ("small", "none"):
-        return dict(K_PYRAMID=0, K_SEARCH_L1=0, K_REDUCE_L1=0)
-    if kind == "fused":
-        return dict(K_PYRAMID=1, K_SEARCH_L1=0, K_REDUCE_L1=0)
-    if c["levels"] == 1:
-        return dict(K_PYRAMID=1, K_SEARCH_L1=0, K_REDUCE_L1=0)
-    g1 = dense_grid(c["w"], c["h"], 1, c["tile"], c["search"], c["subpixel"])
-    return dict(K_PYRAMID=1, K_SEARCH_L1=1, K_REDUCE_L1=0 if groups(g1[4] * g1[5], c["tile"], c["search"]) else 1)
+    """The launches of one call by profiling counter: K_PYRAMID, K_SEARCH_L1, K_REDUCE_L1 (a flat level-1 search: K3 behind
+    it, the in-launch reduction is the caller's switch)."""
+    import batch_plan_ref as bp
+    got = bp.plan(bp.of_coarse(c, cus))["counters"]
+    return {k: 1 if got[k] is None else got[k] for k in ("K_PYRAMID", "K_SEARCH_L1", "K_REDUCE_L1")}
 
 
 # ---- cases and what they reach -----------------------------------------------------------------------------------------------

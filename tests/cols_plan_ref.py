@@ -169,19 +169,23 @@ def case_plan(c):
     return plan(c["nx"], c["ny"], c["n_pairs"], c["w"], c["h"])
 
 
+def launch_of(c):
+    """choose_lane8 of the case's level-0 launch (batch_plan_ref owns the rule): a context in the case's mode, told what the
+    mode's name says -- 'adaptive0' at the launch that looks again --, the in-launch reduction switched as the case asks."""
+    import batch_plan_ref as bp
+    call = bp.of_cols(c)
+    st = bp.fresh_state({"pruned": -1, "adaptive1": 1, "adaptive0": 0}[c["mode"]], bp.PROBE_EVERY - 1 if c["mode"] == "adaptive0" else 0)
+    return bp.choose_lane8(call["mode"], st, bp.lane8_args(call), separate=not c["fused"])
+
+
 def votes(c):
     """The reduction runs in the launch (k_flow_lane8_cols): asked for, and the context's vote records hold the launch."""
-    hist_range = 3 * SEARCH + 1 if c["levels"] == 2 else SEARCH
-    return c["fused"] and c["n_pairs"] <= VOTE_PAIRS and 2 * (2 * hist_range + 1) + 1 <= 62
+    return launch_of(c)["fused"]
 
 
 def runs_the_walk(c):
     """lane8_cols_supported, and for the adaptive mode a launch large enough to prune (adaptive_lane8_prunes)."""
-    blocks = c["nx"] * c["ny"]
-    ok = c["nx"] >= 16 and c["ny"] >= 2 and blocks > 256
-    if c["mode"] != "pruned":
-        ok = ok and (c["n_pairs"] * blocks + 255) // 256 >= PRUNE_MIN_CHUNKS
-    return ok
+    return launch_of(c)["cols"]
 
 
 def misalignments(c, pl):

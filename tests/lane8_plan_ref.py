@@ -202,14 +202,10 @@ def hist_range(c):
     return 13 if c["levels"] == 2 else 4
 
 
-def prune_of(c, pl0=None):
-    """SearchArgs.prune of the level-0 launch as choose_lane8 resolves it: 0, 1 or 2."""
-    if c["mode"] == "exhaustive":
-        return 0
-    if c["mode"] == "pruned":
-        return 1
-    large = -(-c["n_pairs"] * c["nb"] // THREADS) >= PRUNE_MIN_CHUNKS
-    return 0 if not large else 1 if c["mode"] == "adaptive1" else 2
+def prune_of(c):
+    """SearchArgs.prune of the level-0 launch as choose_lane8 resolves it: 0, 1 or 2 (batch_plan_ref owns the rule)."""
+    import batch_plan_ref as bp
+    return bp.lane8_prune(bp.of_lane8(c), 1 if c["mode"] == "adaptive1" else -1)
 
 
 def case_plan(c, slice=0):

@@ -8,7 +8,9 @@
 // printed the same way; the plans of the small-pair kernels (aof_small_plan.hpp: small_plan_make, lane8_group_plan) on the
 // cases of tests/small_plan_ref.py, likewise; the plan of the flat lane-per-block launches (aof_lane8_plan.hpp: lane8_flat_plan)
 // on the cases of tests/lane8_plan_ref.py, likewise, and xcd_remap (aof_xcd_remap.hpp, the text the kernels run) printed value by
-// value for the test to hold to the model's; and fastdiv_make against the division it replaces, with the kernels' fast_div restated in 32-bit
+// value for the test to hold to the model's; the plan of a batch and the per-launch choice of a flat 8x8 launch (aof_batch_plan.hpp:
+// plan_batch, choose_lane8) and the launch plan of the 16x16 search (aof_tile16_plan.hpp: tile16_plan) on the cases of
+// tests/batch_plan_ref.py, likewise, with a table of choose_lane8 rows against values written here; and fastdiv_make against the division it replaces, with the kernels' fast_div restated in 32-bit
 // arithmetic; the stream bank's bound per-stream tables (aof_bank_tables.hpp): binding, resolving for a push or an IMU call, the
 // sensor arguments of a round, case by case against literal values; and the flags of one per-stream table of OpticalFlowBank
 // (facade/src/bank_table.hpp) over runs of ticks.
@@ -20,6 +22,7 @@
 
 #include "aof.h"
 #include "aof_bank_tables.hpp"
+#include "aof_batch_plan.hpp"
 #include "aof_coarse_plan.hpp"
 #include "aof_cols8_plan.hpp"
 #include "aof_exposure_step.hpp"
@@ -27,6 +30,7 @@
 #include "aof_lane8_plan.hpp"
 #include "aof_mavlink.hpp"
 #include "aof_small_plan.hpp"
+#include "aof_tile16_plan.hpp"
 #include "aof_xcd_remap.hpp"
 #include "bank_table.hpp"
 #include "optical_flow_rad.hpp"
@@ -285,6 +289,215 @@ static int print_lane8_plans(const char *path)
     }
     std::fclose(f);
     return cases;
+}
+
+// (d7) the plan of a batch (aof_batch_plan.hpp) and of the 16x16 search (aof_tile16_plan.hpp).  A call as
+// tests/batch_plan_ref.py writes it: w h tile search px4 num_blocks subpixel levels mean_subtract n_pairs pair_stride prev cur
+// mode force_generic split cus k1_ready.  Parameters aof_params_check refuses get an empty grid and an empty layout (no
+// context exists for them; the plan is then only the function's answer).  The workspace is a place, nothing reads it.
+struct PlannedCall {
+    aof::BatchConfig cfg;
+    aof::BatchView view;
+    int64_t n_pairs;
+    bool valid, k1_ready;
+};
+
+static bool read_call(std::FILE *f, PlannedCall *c)
+{
+    long long w, h, tile, search, px4, num_blocks, subpixel, levels, mean_subtract, n_pairs, stride, mode, force_generic, split, cus, k1_ready;
+    unsigned long long prev, cur;
+    if (std::fscanf(f, "%lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %llu %llu %lld %lld %lld %lld %lld", &w, &h, &tile, &search, &px4,
+                    &num_blocks, &subpixel, &levels, &mean_subtract, &n_pairs, &stride, &prev, &cur, &mode, &force_generic, &split, &cus,
+                    &k1_ready) != 18)
+        return false;
+    aof::BatchConfig &cfg = c->cfg;
+    cfg = {};
+    aof_params &p = cfg.params;
+    aof_params_default(&p, (int)w, (int)h);
+    p.tile = (int)tile; p.search = (int)search;
+    p.grid_mode = px4 ? AOF_GRID_PX4FLOW : AOF_GRID_DENSE;
+    p.num_blocks = (int)num_blocks;
+    p.subpixel = (int)subpixel; p.pyramid_levels = (int)levels; p.mean_subtract = (int)mean_subtract;
+    c->valid = aof_params_check(&p) == 0;
+    aof::Grid *g[2] = {&cfg.g0, &cfg.g1};
+    for (int l = 0; l < (int)levels && l < 2; l++)
+        if (aof::grid_for_level(p, l, g[l])) *g[l] = {};
+    cfg.cus = (int)cus; cfg.search_mode = (int)mode; cfg.force_generic = force_generic != 0; cfg.split_coarse = split != 0;
+    aof_ws_layout L = {};
+    if (c->valid && aof_workspace_layout(&p, (int64_t)n_pairs, &L)) return false;
+    c->n_pairs = (int64_t)n_pairs;
+    c->k1_ready = k1_ready != 0;
+    c->view = aof::batch_view(cfg, L, reinterpret_cast<const uint8_t *>((uintptr_t)prev), reinterpret_cast<const uint8_t *>((uintptr_t)cur),
+                              (int64_t)stride, nullptr, nullptr, reinterpret_cast<aof_flow *>((uintptr_t)0x7E0000000000ull),
+                              reinterpret_cast<void *>((uintptr_t)0x7D0000000000ull));
+    return true;
+}
+
+// One line of fields per call, in the order of batch_plan_ref.PLAN_FIELDS; kinds[]: how often each SearchKind was planned
+// (level 0, and level 1 where K1 is followed by a search), coarse[]: each CoarseKind.
+static int print_batch_plans(const char *path, int kinds[4], int coarse[3])
+{
+    std::FILE *f = std::fopen(path, "r");
+    if (!f) return -1;
+    int cases = 0;
+    PlannedCall c;
+    while (read_call(f, &c)) {
+        const aof::BatchPlan P = aof::plan_batch(c.cfg, c.view, c.n_pairs, c.k1_ready);
+        const bool level1 = !P.small && P.coarse == aof::COARSE_K1 && c.cfg.params.pyramid_levels == 2;
+        std::printf("batch plan: %d %d %d %d %d %d %d %d %d %d %d %d\n", c.valid ? 1 : 0, P.small ? 1 : 0, P.small_class ? 1 : 0, (int)P.coarse,
+                    P.k1_pass ? 1 : 0, P.sequence ? 1 : 0, (int)P.level[0].kind, P.level[0].refine ? 1 : 0, P.level[0].a.prune,
+                    level1 ? (int)P.level[1].kind : 0, level1 && P.level[1].refine ? 1 : 0, level1 ? P.level[1].a.prune : 0);
+        kinds[P.level[0].kind]++;
+        if (level1) kinds[P.level[1].kind]++;
+        coarse[P.coarse]++;
+        cases++;
+    }
+    std::fclose(f);
+    return cases;
+}
+
+// tile16_plan on a case file, one search per line: w h pair_stride prev cur tile search grid[6] subpixel subdirs prune hints
+// n_pairs forced.  One line of fields per case, in the order of batch_plan_ref.T16_FIELDS; verdicts[]: the census.
+static int print_tile16_plans(const char *path, int verdicts[9])
+{
+    std::FILE *f = std::fopen(path, "r");
+    if (!f) return -1;
+    int cases = 0;
+    long long w, h, stride, tile, search, g[6], subpixel, subdirs, prune, hints, n_pairs, forced;
+    unsigned long long prev, cur;
+    static uint8_t somewhere[4];   // (directions and hints: only looked at for being there)
+    while (std::fscanf(f, "%lld %lld %lld %llu %llu %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld", &w, &h, &stride, &prev,
+                       &cur, &tile, &search, &g[0], &g[1], &g[2], &g[3], &g[4], &g[5], &subpixel, &subdirs, &prune, &hints, &n_pairs,
+                       &forced) == 19) {
+        aof::SearchArgs a = {};
+        a.prev = reinterpret_cast<const uint8_t *>((uintptr_t)prev);
+        a.cur = reinterpret_cast<const uint8_t *>((uintptr_t)cur);
+        a.pair_stride = (int64_t)stride;
+        a.w = (int32_t)w; a.h = (int32_t)h;
+        a.tile = (int32_t)tile; a.search = (int32_t)search;
+        a.grid = {(int32_t)g[0], (int32_t)g[1], (int32_t)g[2], (int32_t)g[3], (int32_t)g[4], (int32_t)g[5]};
+        a.subpixel = (int32_t)subpixel;
+        a.subdirs = subdirs ? somewhere : nullptr;
+        a.prune = (int32_t)prune;
+        a.hints = hints ? reinterpret_cast<uint32_t *>(somewhere) : nullptr;
+        a.n_pairs = (int64_t)n_pairs;
+        const aof::Tile16Plan p = aof::tile16_plan(a, (int)forced);
+        if ((p.verdict == aof::TILE16_OK) != aof::tile16_supported(a) || (p.refines != 0) != aof::tile16_refines(a) || p.lds != aof::tile16_lds(a)) return -1;
+        std::printf("tile16 plan: %d %d %zu %d %d %d %lld %d %d %d %lld %d %d %d %d\n", p.verdict, p.refines, p.lds, p.attr, p.prune, p.refine,
+                    (long long)p.total, p.overflow, p.front, p.refused, (long long)p.front_wgs, p.stx, p.sty, p.sx, p.sy);
+        if (p.verdict >= 0 && p.verdict < 9) verdicts[p.verdict]++;
+        cases++;
+    }
+    std::fclose(f);
+    return cases;
+}
+
+// The report a pruned launch leaves in the context's pinned words: the first `arrived` of `expected` carry the launch's
+// tag with `paying` of `seen` chunks each, the rest a stale tag.
+static uint32_t report_words[aof::kPruneSlots];
+
+static aof::AdaptiveSearch adaptive_state(int belief, int since_probe, uint32_t launch_no, uint32_t expected, uint32_t arrived, uint32_t paying,
+                                          uint32_t seen)
+{
+    aof::AdaptiveSearch st = {};
+    st.slots = report_words;
+    st.launch_no = launch_no;
+    st.expected = expected;
+    st.belief = belief;
+    st.since_probe = since_probe;
+    st.stats.belief = belief;
+    const uint32_t tag = launch_no & 0xFFFFu;
+    for (uint32_t i = 0; i < (uint32_t)aof::kPruneSlots; i++)
+        report_words[i] = i < arrived ? (tag << 16 | paying << 8 | seen) : ((tag ^ 1u) << 16 | 0xFFFFu);
+    return st;
+}
+
+// choose_lane8 on a case file: a call's line (its level-0 search must be a flat 8x8 launch), then belief since_probe launch_no
+// expected arrived paying seen capture captured separate votes_memory votes_fault votes_stride.  One line per row: the
+// launch and the state after it, in the order of batch_plan_ref.CHOOSE_FIELDS.
+static int print_choose_lane8(const char *path)
+{
+    std::FILE *f = std::fopen(path, "r");
+    if (!f) return -1;
+    int rows = 0;
+    PlannedCall c;
+    static uint32_t somewhere[1];
+    while (read_call(f, &c)) {
+        long long belief, since, launch_no, expected, arrived, paying, seen, capture, captured, separate, mem, fault, vstride;
+        if (std::fscanf(f, "%lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld", &belief, &since, &launch_no, &expected, &arrived, &paying,
+                        &seen, &capture, &captured, &separate, &mem, &fault, &vstride) != 13)
+            return -1;
+        const aof::BatchPlan P = aof::plan_batch(c.cfg, c.view, c.n_pairs, c.k1_ready);
+        if (!c.valid || P.small || P.level[0].kind != aof::SK_LANE8) return -1;
+        aof::AdaptiveSearch st = adaptive_state((int)belief, (int)since, (uint32_t)launch_no, (uint32_t)expected, (uint32_t)arrived, (uint32_t)paying,
+                                                (uint32_t)seen);
+        const aof::VoteMem vm = {mem ? somewhere : nullptr, (uint32_t)vstride, fault ? somewhere : nullptr, 0};
+        const aof::Lane8Launch l = aof::choose_lane8(c.cfg, st, P.level[0].a, (aof::Capture)capture, vm, 2048 /* kVotePairs, aof_ctx.hpp */, separate != 0, captured != 0);
+        std::printf("choose lane8: %d %d %d %d %u %d %d %u %llu %llu %llu %d %d\n", l.prune, l.cols ? 1 : 0, l.fused ? 1 : 0, l.rep.slots ? 1 : 0,
+                    l.rep.launch_no, st.belief, st.since_probe, st.launch_no, (unsigned long long)st.stats.pruned_launches,
+                    (unsigned long long)st.stats.exhaustive_launches, (unsigned long long)st.stats.reports_read, st.stats.belief, st.stats.paying_pct);
+        rows++;
+    }
+    std::fclose(f);
+    return rows;
+}
+
+// choose_lane8, row by row against the values written here: 1 024 VGA pairs on the dense grid (4 661 blocks: a launch large
+// enough to prune, the column walk's grid), 19 vote bins, vote records for 2 048 pairs, the last reporting launch number 7.
+// Returns the number of rows, or -1.
+static int check_choose_lane8()
+{
+    using namespace aof;
+    enum { EX = AOF_SEARCH_EXHAUSTIVE, PR = AOF_SEARCH_PRUNED, AD = AOF_SEARCH_ADAPTIVE };
+    const struct {
+        int mode, belief, since; uint32_t launch_no, expected, arrived, paying; Capture cap; bool captured, separate;   // (every word: `paying` of 100 chunks)
+        int prune; bool cols, fused; int belief_after, since_after; uint32_t launch_after, tag; uint64_t pruned, exhaustive, read;
+    } rows[] = {
+        // the fixed modes read and change nothing
+        {EX, -1, 14, 7, 0, 0, 0, CAPTURE_NONE, false, false, 0, false, true, -1, 14, 7, 0, 0, 0, 0},
+        {PR, -1, 14, 7, 0, 0, 0, CAPTURE_NONE, false, false, 1, true, true, -1, 14, 7, 0, 0, 0, 0},
+        // nothing known: the first chunk of every wave judges; pruning pays: every wave prunes at once
+        {AD, -1, 14, 7, 0, 0, 0, CAPTURE_NONE, false, false, 2, true, true, -1, 14, 8, 8, 1, 0, 0},
+        {AD, 1, 14, 7, 0, 0, 0, CAPTURE_NONE, false, false, 1, true, true, 1, 14, 8, 8, 1, 0, 0},
+        // it does not pay: the exhaustive kernel, and the pruned one with the 16th launch
+        {AD, 0, 14, 7, 0, 0, 0, CAPTURE_NONE, false, false, 0, false, true, 0, 15, 7, 0, 0, 1, 0},
+        {AD, 0, 15, 7, 0, 0, 0, CAPTURE_NONE, false, false, 2, true, true, 0, 0, 8, 8, 1, 0, 0},
+        // a report counts once a quarter of its words have arrived, and says "pays" from 40 % on
+        {AD, 0, 14, 7, 8, 1, 100, CAPTURE_NONE, false, false, 0, false, true, 0, 15, 7, 0, 0, 1, 0},
+        {AD, 0, 14, 7, 8, 2, 39, CAPTURE_NONE, false, false, 0, false, true, 0, 15, 7, 0, 0, 1, 1},
+        {AD, 0, 14, 7, 8, 2, 40, CAPTURE_NONE, false, false, 1, true, true, 1, 14, 8, 8, 1, 0, 1},
+        {AD, 1, 14, 7, 8, 8, 39, CAPTURE_NONE, false, false, 0, false, true, 0, 15, 7, 0, 0, 1, 1},
+        {AD, -1, 15, 7, 8, 8, 40, CAPTURE_NONE, false, false, 1, true, true, 1, 15, 8, 8, 1, 0, 1},
+        // the reduction in the launch: inside a capture always, eagerly until a graph holds one, never where the capture
+        // state is unknown or the caller keeps K3
+        {AD, 1, 14, 7, 0, 0, 0, CAPTURE_ACTIVE, true, false, 1, true, true, 1, 14, 8, 8, 1, 0, 0},
+        {AD, 1, 14, 7, 0, 0, 0, CAPTURE_NONE, true, false, 1, true, false, 1, 14, 8, 8, 1, 0, 0},
+        {AD, 1, 14, 7, 0, 0, 0, CAPTURE_UNKNOWN, false, false, 1, true, false, 1, 14, 8, 8, 1, 0, 0},
+        {AD, 1, 14, 7, 0, 0, 0, CAPTURE_ACTIVE, false, true, 1, true, false, 1, 14, 8, 8, 1, 0, 0},
+        {EX, -1, 14, 7, 0, 0, 0, CAPTURE_NONE, false, true, 0, false, false, -1, 14, 7, 0, 0, 0, 0},
+        // the launch counter skips tag 0
+        {AD, 1, 14, 0xFFFFu, 0, 0, 0, CAPTURE_NONE, false, false, 1, true, true, 1, 14, 0x10001u, 1, 1, 0, 0},
+    };
+    aof_params p;
+    aof_params_default(&p, 640, 480);
+    BatchConfig cfg = {};
+    cfg.params = p;
+    if (grid_for_level(p, 0, &cfg.g0) || cfg.g0.blocks() != 4661) return -1;
+    cfg.cus = 256;
+    static uint32_t somewhere[1];
+    const VoteMem vm = {somewhere, 128, somewhere, 0};
+    int n = 0;
+    for (const auto &r : rows) {
+        cfg.search_mode = r.mode;
+        const SearchArgs a = search_args(cfg, 0, nullptr, nullptr, 640 * 480, nullptr, nullptr, nullptr, nullptr, 1024);
+        AdaptiveSearch st = adaptive_state(r.belief, r.since, r.launch_no, r.expected, r.arrived, r.paying, 100);
+        const Lane8Launch l = choose_lane8(cfg, st, a, r.cap, vm, 2048, r.separate, r.captured);
+        if (l.prune != r.prune || l.cols != r.cols || l.fused != r.fused || (l.rep.slots != nullptr) != (r.tag != 0) || (r.tag && l.rep.launch_no != r.tag)) return -1;
+        if (st.belief != r.belief_after || st.since_probe != r.since_after || st.launch_no != r.launch_after) return -1;
+        if (st.stats.pruned_launches != r.pruned || st.stats.exhaustive_launches != r.exhaustive || st.stats.reports_read != r.read) return -1;
+        n++;
+    }
+    return n;
 }
 
 // (d6) xcd_remap, the function the kernels run: a permutation of [0, total) for every total up to 4096 (every logical id hit
@@ -652,6 +865,17 @@ int main(int argc, char **argv)
         if (lane8 < 0 || totals < 0 || probes < 0) return 19;
         std::printf("host selftest: lane8 plan: %d cases\nhost selftest: xcd_remap: a permutation for every total up to %d, %d probes\n", lane8,
                     totals, probes);
+    }
+    if (argc > 9) {
+        int kinds[4] = {}, coarse[3] = {}, verdicts[9] = {};
+        const int batch = print_batch_plans(argv[7], kinds, coarse), tile16 = print_tile16_plans(argv[8], verdicts);
+        const int chosen = print_choose_lane8(argv[9]), written = check_choose_lane8();
+        if (batch < 0 || tile16 < 0 || chosen < 0 || written < 0) return 22;
+        std::printf("host selftest: batch plan: %d cases, kinds %d %d %d %d, coarse %d %d %d\n", batch, kinds[0], kinds[1], kinds[2], kinds[3],
+                    coarse[0], coarse[1], coarse[2]);
+        std::printf("host selftest: tile16 plan: %d cases, verdicts %d %d %d %d %d %d %d %d %d\n", tile16, verdicts[0], verdicts[1], verdicts[2],
+                    verdicts[3], verdicts[4], verdicts[5], verdicts[6], verdicts[7], verdicts[8]);
+        std::printf("host selftest: choose lane8: %d rows equal to the values written, %d rows printed\n", written, chosen);
     }
     std::printf("host selftest: %d valid parameter sets, %d rejected\n", valid, bad);
     return valid > 1000 ? 0 : 11;

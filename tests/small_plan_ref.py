@@ -1,7 +1,7 @@
 """The launch plans of the small-pair kernels in plain Python -- the one-workgroup class that runs flow_small_pair
 (csrc/aof_small_plan.hpp: small_plan_make) and the grouped lane-per-block search k_flow_lane8 (lane8_group_plan) --, what
 the kernels make of them lane by lane (passes A, B, C and D1 of csrc/aof_flow_small.hpp, the (workgroup, lane) -> (pair,
-block) map of k_flow_lane8), which kernels serve a batch (aof_batch.cpp: plan_batch), the names of the paths a launch
+block) map of k_flow_lane8), which kernels serve a batch (batch_plan_ref.py, the model of aof_batch_plan.hpp: plan_batch), the names of the paths a launch
 can take through all of it, and the case lists of tests/test_small_plan_ref.py, tests/test_host_asan.py (the same plans
 from the C++ functions) and tests/test_gpu_small_plan.py (every case of GPU_CASES on the device, against the oracle).
 
@@ -21,13 +21,11 @@ there for, and the height comes from the grid rule (grid_for_level).  Only the w
 extreme shapes of PLAN_ONLY are written out."""
 import numpy as np
 
-from coarse_plan_ref import coarse_verdict
 
 # csrc/aof_small_plan.hpp
 THREADS, MAX_BINS, LOADS, PAD = 256, 64, 8, 16
 STATIC_LDS, LDS_LIMIT, ATTR_ABOVE = 4096, 160 * 1024, 48 * 1024
 TRIP_A = LOADS * THREADS
-SMALL_MAX_PAIRS = 128   # aof_batch.cpp
 ZERO_COPY_MAX = 64 * 1024   # aof_percall.cpp: the per-call paths read frames up to here from pinned host memory (tagged, resident)
 # the verdict of flow_small_supported: the first condition that fails (enum SmallVerdict, in this order)
 VERDICTS = ("ok", "levels", "tile", "pairs", "grid0", "bins0", "width", "stride", "prev", "cur", "subdirs0", "height", "grid1", "bins1",
@@ -335,39 +333,30 @@ def case_group_plan(c, n_pairs, level=0):
 
 
 def kind(c, n_pairs=None, split=False):
-    """'small' (one launch of the one-workgroup kernel) or 'separate' (plan_batch keeps the separate kernels)."""
-    n = c["n_pairs"] if n_pairs is None else n_pairs
-    g0, g1 = grids(c)
-    two = c["levels"] == 2
-    groups = lambda g: 8 <= blocks(g) <= THREADS
-    small_class = not split and groups(g0) and (not two or groups(g1)) and case_plan(c, n)["verdict"] == "ok"
-    return "small" if small_class and n <= SMALL_MAX_PAIRS else "separate"
+    """'small' (one launch of the one-workgroup kernel) or 'separate' (plan_batch keeps the separate kernels):
+    batch_plan_ref owns the rule."""
+    import batch_plan_ref as bp
+    return "small" if bp.plan(bp.of_small(c, n_pairs, split))["small"] else "separate"
 
 
 def why_separate(c):
-    """What keeps a case of `separate` kind out of the one launch: 'grid0' / 'grid1' (a level's search is not the grouped
-    one: plan_batch), else the verdict of flow_small_supported."""
-    g0, g1 = grids(c)
-    if not 8 <= blocks(g0) <= THREADS:
+    """What keeps a case of `separate` kind out of the one launch: 'plan_grid0' / 'plan_grid1' (a level's search is not the
+    grouped one), else the verdict of small_plan_make."""
+    import batch_plan_ref as bp
+    pl = bp.plan(bp.of_small(c))
+    if pl["kind"][0] != "lane8_group":
         return "plan_grid0"
-    if c["levels"] == 2 and not 8 <= blocks(g1) <= THREADS:
+    if c["levels"] == 2 and pl["small_l1_kind"] != "lane8_group":
         return "plan_grid1"
-    return case_plan(c)["verdict"]
+    return pl["small_verdict"]
 
 
 def counters(c, n_pairs=None, split=False):
-    """The launches of one call by profiling counter [K_PYRAMID, K_SEARCH_L1, K_REDUCE_L1, K_SEARCH, K_REDUCE]."""
-    if kind(c, n_pairs, split) == "small":
-        return [0, 0, 0, 1, 0]
-    g0, g1 = grids(c)
-    two, eq = c["levels"] == 2, bool(c["mean_subtract"])
-    groups = lambda g: 8 <= blocks(g) <= THREADS
-    stride, prev, cur = frame_layout(c)
-    if two and not split and coarse_verdict(c["w"], c["h"], stride, prev, cur, g1, 4, 8, 4, c["subpixel"], n_pairs or c["n_pairs"]) == "ok":
-        return [1, 0, 0, 1, 0 if groups(g0) else 1]      # k_coarse makes level 1 (counted as K_PYRAMID)
-    # one level: K1 only for the sums; two levels: K1 and the level-1 search.  A grouped search writes its flow records
-    # itself, any other is followed by K3
-    return [1 if two or eq else 0, 1 if two else 0, 0 if not two or groups(g1) else 1, 1, 0 if groups(g0) else 1]
+    """The launches of one call by profiling counter [K_PYRAMID, K_SEARCH_L1, K_REDUCE_L1, K_SEARCH, K_REDUCE] (a flat
+    search: K3 behind it, the in-launch reduction is the caller's switch)."""
+    import batch_plan_ref as bp
+    got = bp.plan(bp.of_small(c, n_pairs, split))["counters"]
+    return [1 if got[k] is None else got[k] for k in bp.COUNTERS]
 
 
 def group_counts(c):

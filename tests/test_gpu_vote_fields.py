@@ -4,26 +4,17 @@ reduce_model as well.  Each case first asserts, on the ORACLE's records, that it
 there for (vote_field_ref.check_reaches), then runs the device, then asserts with the profiling counters which kernel
 finalised.  Large launches are replicas of the few distinct designed pairs.
 
-Which launch takes which path (aof_batch.cpp plan_batch / enqueue_level, k_reduce.hip launch_reduce, aof_params.cpp
-reduce_chunks, k_flow_small.hip flow_small_supported, k_coarse.hip coarse_fused_supported, as they read today):
+Which launch takes which search, coarse pass and in-launch reduction is the batch plan's rule: csrc/aof_batch_plan.hpp
+(plan_batch, choose_lane8) and its model tests/batch_plan_ref.py (DESIGN.md "Which kernel serves which configuration").
+Behind a search that does not reduce itself K3 chooses its own form (k_reduce.hip launch_reduce, aof_params.cpp
+reduce_chunks):
 
-  8x8 tiles, +-4, grids of 8..256 blocks   the grouped search finalises in its own tail, no K3 -- or, for up to 128
-                                           pairs of a frame whose width is a multiple of 16, k_flow_small; K3's
-                                           one-wave-per-pair form serves such grids behind the generic search
-                                           (force_generic) and behind the 16x16 search
-  more than 256 blocks                     flat search, then K3: 1 024 lanes per pair for up to 512 pairs of at least
-                                           2 048 blocks, 512 lanes for up to 1 024 such pairs, else 256 lanes
+  more than 256 blocks                     1 024 lanes per pair for up to 512 pairs of at least 2 048 blocks, 512 lanes
+                                           for up to 1 024 such pairs, else 256 lanes
   more than 8 192 blocks                   k_reduce_chunk over ceil(blocks / 4 096) chunks of ceil(blocks / chunks)
                                            records, then k_reduce on the parts
-  set_reduce_fusion(True), > 256 blocks    votes through the context's vote memory inside the search launch: the
-                                           exhaustive search by vote_and_arrive, the column walk (SEARCH_PRUNED, at
-                                           least 16 block columns) by WalkVotes -- by vote_and_arrive with half-pixel
-                                           refinement --, a finaliser wave per pair; no K3
-  two levels, 8x8 +-4, width % 16 == 0     k_coarse (pyramid, level-1 search, level-1 reduce, predictor: one launch
-                                           counted as K_PYRAMID) unless split; pairs that fit one workgroup take
-                                           k_flow_small for both levels (one launch counted as K_SEARCH)
-  two levels otherwise, or split           K1, level-1 search, level-1 reduce (K3 emitting the predictor, unless the
-                                           level-1 search is the grouped one), level 0
+  grids of 8..256 blocks                   K3's one-wave-per-pair form, behind the generic search (force_generic) and
+                                           behind the 16x16 search
   more than 64 bins (two levels, S >= 5)   K3 hands the bins to one thread: finalise_flow
 """
 import numpy as np

@@ -8,13 +8,16 @@ every case of tests/coarse_plan_ref.py and a list of extreme shapes, the same wa
 (csrc/aof_small_plan.hpp: small_plan_make, lane8_group_plan) on every case of tests/small_plan_ref.py and its list of
 extreme shapes, likewise; the plan of the flat lane-per-block launches (csrc/aof_lane8_plan.hpp: lane8_flat_plan) on every case of
 tests/lane8_plan_ref.py, likewise, with xcd_remap (csrc/aof_xcd_remap.hpp, the text the kernels run) a permutation for every
-total up to 4 096 and equal to the model's at every probe; fastdiv_make against the division it replaces; the stream bank's
+total up to 4 096 and equal to the model's at every probe; the plan of a batch, the per-launch choice of a flat 8x8 launch
+(csrc/aof_batch_plan.hpp: plan_batch, choose_lane8) and the launch plan of the 16x16 search (csrc/aof_tile16_plan.hpp: tile16_plan)
+on every case of tests/batch_plan_ref.py, likewise; fastdiv_make against the division it replaces; the stream bank's
 bound per-stream tables (csrc/aof_bank_tables.hpp: what a binding call accepts, which tables a push uses and the order of its
 refusals) and the flags of one per-stream table of OpticalFlowBank (facade/src/bank_table.hpp) over runs of ticks, both
 against values written out in the selftest."""
 import os
 import subprocess
 
+import batch_plan_ref as batch
 import coarse_plan_ref as coarse
 import cols_plan_ref as ref
 import lane8_plan_ref as lane8
@@ -47,8 +50,13 @@ def test_host_logic_is_clean_under_asan_ubsan(tmp_path):
     lane8_listing.write_text("".join(lane8.selftest_line(c) + "\n" for c in lane8.CASES))
     xcd_probes = lane8.xcd_probes()
     xcd_listing.write_text("".join(f"{total} {b}\n" for total, b in xcd_probes))
+    batch_cases, tile16_cases, choose_rows = batch.batch_cases(), batch.tile16_cases(), batch.choose_rows()
+    batch_listing, tile16_listing, choose_listing = tmp_path / "batch_plan_cases.txt", tmp_path / "tile16_plan_cases.txt", tmp_path / "choose_lane8_rows.txt"
+    batch_listing.write_text("".join(batch.selftest_line(c) + "\n" for c in batch_cases))
+    tile16_listing.write_text("".join(batch.tile16_line(c) + "\n" for c in tile16_cases))
+    choose_listing.write_text("".join(batch.choose_line(r) + "\n" for r in choose_rows))
     r = subprocess.run([str(exe), str(listing), str(coarse_listing), str(pyramid_listing), str(small_listing), str(lane8_listing),
-                        str(xcd_listing)], capture_output=True, text=True, timeout=300)
+                        str(xcd_listing), str(batch_listing), str(tile16_listing), str(choose_listing)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, f"rc={r.returncode}\n{r.stdout}{r.stderr}"
     assert "valid parameter sets" in r.stdout
     assert "packer: 4012 frames equal to the facade's, lengths 52 and 56" in r.stdout
@@ -107,3 +115,31 @@ def test_host_logic_is_clean_under_asan_ubsan(tmp_path):
     assert f"xcd_remap: a permutation for every total up to 4096, {len(xcd_probes)} probes" in r.stdout and len(xcd_probes) >= 1000
     remapped = [int(line.split()[2]) for line in r.stdout.splitlines() if line.startswith("xcd remap: ")]
     assert remapped == [int(lane8.xcd_remap(b, total)) for total, b in xcd_probes]
+    # plan_batch, tile16_plan and choose_lane8 == the model, on every case of every list; every kind and verdict occurs
+    assert f"batch plan: {len(batch_cases)} cases" in r.stdout and len(batch_cases) >= 250
+    assert f"tile16 plan: {len(tile16_cases)} cases" in r.stdout and len(tile16_cases) >= 30
+    assert f"{len(choose_rows)} rows printed" in r.stdout and len(choose_rows) >= 1000
+    for tag, cases, fields, names in (("batch plan: ", batch_cases, lambda c: batch.plan_fields(batch.plan(c)), batch.PLAN_FIELDS),
+                                      ("tile16 plan: ", tile16_cases, lambda c: batch.tile16_fields(batch.tile16_plan(c)), batch.T16_FIELDS),
+                                      ("choose lane8: ", choose_rows, batch.choose_row, batch.CHOOSE_FIELDS)):
+        plans = [line.split()[2:] for line in r.stdout.splitlines() if line.startswith(tag)]
+        assert len(plans) == len(cases)
+        for c, got in zip(cases, plans):
+            want = fields(c)
+            assert len(got) == len(want) == len(names)
+            diff = {name: (int(g), w) for name, g, w in zip(names, got, want) if int(g) != w}
+            assert not diff, (tag, c["id"], diff)
+    planned = [batch.plan(c) for c in batch_cases]
+    assert {k for pl in planned for k in pl["kind"] if k} == set(batch.SEARCH_KINDS)
+    assert {pl["coarse"] for pl in planned} == set(batch.COARSE_KINDS)
+    assert {pl["small"] for pl in planned} == {True, False} and {pl["valid"] for pl in planned} == {True, False}
+    assert any(pl["small_class"] and not pl["small"] for pl in planned) and any(pl["sequence"] and not pl["k1_pass"] for pl in planned)
+    assert any(pl["kind"][0] == "tile16" and pl["prune"][0] == 0 and c["mode"] != 0 for c, pl in zip(batch_cases, planned)), "search_kind clears prune"
+    assert {batch.tile16_plan(c)["verdict"] for c in tile16_cases} == set(batch.T16_VERDICTS)
+    assert {batch.tile16_plan(c)["front"] for c in tile16_cases} == set(batch.FRONTS)
+    assert {(pl["overflow"], pl["refused"]) for pl in map(batch.tile16_plan, tile16_cases)} == {(0, 0), (0, 1), (1, 1)}
+    chosen = [batch.choose_row(r) for r in choose_rows]
+    assert {(row[0], row[1], row[2]) for row in chosen} >= {(0, 0, 0), (0, 0, 1), (1, 1, 1), (2, 1, 0), (1, 0, 0), (2, 0, 0)}
+    census = [line for line in r.stdout.splitlines() if line.startswith("host selftest: batch plan:") or line.startswith("host selftest: tile16 plan:")]
+    assert len(census) == 2 and all(int(v) > 0 for line in census for v in line.replace(",", "").split()[6:] if v.isdigit()), census
+    assert "host selftest: choose lane8: 17 rows equal to the values written" in r.stdout

@@ -53,7 +53,7 @@ int main(int argc, char **argv)
     a.sums = d_sums; a.blocks = d_blocks; a.n_pairs = n;
     a.tail.nblocks = g1.blocks(); a.tail.range = 4; a.tail.hist_filter = 1; a.tail.min_valid = 10;
     a.tail.flows = d_flows; a.tail.pred = nullptr; a.tail.emit_predictor = 1;
-    if (!coarse_fused_supported(a)) { printf("not supported\n"); return 1; }
+    if (coarse_plan_of(a).verdict != COARSE_OK) { printf("not supported\n"); return 1; }
     a.first_generation = 256;
     a.stagger_groups = argc > 2 ? atoi(argv[2]) : 1;
     a.stagger_ticks = argc > 3 ? atoi(argv[3]) : 1200;
