@@ -132,6 +132,7 @@ BANK_BURST_MAX = 16
 TICK_HELD, TICK_IDLE = -1, -2
 BANK_BIN_MAX = 4   # AOF_BANK_BIN_MAX: a stream's binning is 1, 2 or 4 (aof_set_bank_binning)
 PIXEL_GREY8, PIXEL_LUMA16_LO, PIXEL_LUMA16_HI = 0, 1, 2   # AOF_PIXEL_*: a stream's pixel format (aof_set_bank_pixel_formats)
+PIXEL_Y10, PIXEL_Y12, PIXEL_Y14, PIXEL_Y10P, PIXEL_Y12P = 4, 5, 6, 7, 8   # raw mono pixels: 16-bit words, MIPI-packed groups (3: no format)
 TICK_BAD_SENSOR = -5   # the stream's sensor record (aof_bank_sensor) does not describe memory inside the camera buffer
 TICK_DTYPE = np.dtype([("quality", "<i4"), ("dt_us", "<i4"), ("flow_x", "<f4"), ("flow_y", "<f4"),
                        ("gyro_x", "<f4"), ("gyro_y", "<f4"), ("gyro_z", "<f4"), ("frame", "<u4"), ("pixel", FLOW_DTYPE)])
@@ -296,6 +297,7 @@ def _load():
         "aof_bank_sensor_centred_binned": (C.c_int, [P(Params), C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_uint8, C.c_uint8,
                                                      P(BankSensor)]),
         "aof_ingest_sensors_binned_device": (C.c_int, [C.c_int32, C.c_int32, VP, C.c_uint64, VP, VP, VP, I64, VP, I64, VP, VP, VP]),
+        "aof_bank_pixel_row_bytes": (C.c_int, [C.c_uint8, C.c_int32, P(C.c_int64)]),
         "aof_bank_camera_layout": (C.c_int, [P(Params), P(BankParams), P(BankCamera), P(BankLayout), P(C.c_size_t)]),
         "aof_bank_push_camera_device": (C.c_int, [VP, P(BankParams), P(BankCamera), VP, VP, VP, VP, VP, C.c_size_t, VP, VP, VP,
                                                   VP, VP, VP]),
@@ -508,6 +510,16 @@ def bank_sensor_centred(p: Params, offset, pitch, width, height, format=0, bin=1
     if rc:
         raise AofError(rc, lib.aof_strerror(rc).decode())
     return _sensor_record(rec)
+
+
+def bank_pixel_row_bytes(format, width) -> int:
+    """aof_bank_pixel_row_bytes: the bytes of a row of ``width`` pixels of ``format`` (PIXEL_*), (width / G) * Bg.  AofError
+    (-EINVAL) for a value that is no format, width < 1 or a width that is not whole groups."""
+    out = C.c_int64(0)
+    rc = lib.aof_bank_pixel_row_bytes(int(format) & 0xFF, int(width), C.byref(out))
+    if rc:
+        raise AofError(rc, lib.aof_strerror(rc).decode())
+    return int(out.value)
 
 
 def bank_sensor_valid(rec, crop_w, crop_h, camera_bytes, base=0, format=0, bin=1) -> bool:
@@ -1323,8 +1335,8 @@ class FlowEngine:
         self._bind_bank_table(lib.aof_set_bank_sensors, "_bank_sensors", sensors, n_streams, 32, int(camera_bytes))
 
     def set_bank_pixel_formats(self, formats=None, n_streams=None):
-        """aof_set_bank_pixel_formats: binds a uint8 CUDA tensor of S pixel formats (PIXEL_GREY8, PIXEL_LUMA16_LO,
-        PIXEL_LUMA16_HI; any alignment) to the context, or with None unbinds.  n_streams: S, where the tensor holds more.
+        """aof_set_bank_pixel_formats: binds a uint8 CUDA tensor of S pixel formats (PIXEL_GREY8 .. PIXEL_Y12P;
+        any alignment) to the context, or with None unbinds.  n_streams: S, where the tensor holds more.
         Used by the camera pushes next to bound sensor records (set_bank_sensors): stream s's crop then comes from pixels
         of one or two bytes.  The kernels read it when they run: keep it alive; it may be rewritten between ticks."""
         self._bind_bank_table(lib.aof_set_bank_pixel_formats, "_bank_formats", formats, n_streams, 1)
@@ -1660,16 +1672,17 @@ class OpticalFlowBank:
 
     def enableCameraPacked(self, camera_width, camera_height, format, exposure0=1, gain0=1, exposure_interval_us=200000):
         """enableCamera() for cameras that all deliver pixel format ``format`` (PIXEL_*): pushCamera() then takes
-        camera_width x camera_height pixels of one or two bytes per stream.  Returns 0 or a negative value."""
+        camera_height rows of bank_pixel_row_bytes(format, camera_width) bytes per stream.  Returns 0 or a negative value
+        (-EINVAL also for a value that is no format and a camera_width that is not whole groups of the format)."""
         rc = facade_lib().aof_facade_bank_enable_camera_packed(self._h, int(camera_width), int(camera_height), int(format),
                                                                int(exposure0), int(gain0), int(exposure_interval_us))
         if rc == 0:
-            self._sensor = int(camera_width) * int(camera_height) * (1 if int(format) == PIXEL_GREY8 else 2)
+            self._sensor = int(camera_height) * bank_pixel_row_bytes(format, camera_width)
         return rc
 
     def setStreamPixelFormat(self, s, format):
         """Stream s's own pixel format (PIXEL_*) inside the bytes pushCamera() takes, from the next pushCamera() on.  0, or
-        -EINVAL (bad index, a format above 2, before enableCamera(), a record that no longer fits those bytes)."""
+        -EINVAL (bad index, a value that is no format, before enableCamera(), a record that no longer fits those bytes)."""
         return facade_lib().aof_facade_bank_set_stream_pixel_format(self._h, int(s), int(format))
 
     def setStreamBinning(self, s, bin):
@@ -1678,8 +1691,8 @@ class OpticalFlowBank:
         return facade_lib().aof_facade_bank_set_stream_binning(self._h, int(s), int(bin))
 
     def pushCamera(self, sensor_frames, img_time_us, active=None, gyro=None):
-        """sensor_frames uint8 [S, camera_height, camera_width] (enableCameraPacked(): [S, camera_height, camera_width *
-        bpp]); the rest and the return value as push()."""
+        """sensor_frames uint8 [S, camera_height, camera_width] (enableCameraPacked(): [S, camera_height, row_bytes], see
+        bank_pixel_row_bytes()); the rest and the return value as push()."""
         assert getattr(self, "_sensor", None), "pushCamera() needs enableCamera()"
         return self._push(facade_lib().aof_facade_bank_push_camera, sensor_frames, self._sensor, img_time_us, active, gyro)
 

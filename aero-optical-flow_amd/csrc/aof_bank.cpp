@@ -381,9 +381,11 @@ int aof_bank_sensor_centred_binned(const aof_params *p, uint64_t offset, int32_t
     rec.pitch = pitch;
     rec.width = width; rec.height = height;
     rec.x0 = width / 2 - (int32_t)((int64_t)bin * p->width / 2); rec.y0 = height / 2 - (int32_t)((int64_t)bin * p->height / 2);
+    const BankPixelLayout l = bank_pixel_layout(format);
+    if (l.group_px > 1 && rec.x0 > 0) rec.x0 -= rec.x0 % l.group_px;   // (a packed form's crop starts on a group)
     // (the rule against a buffer that ends with the frame: everything but the place in a camera buffer)
     if (p->width < 1 || p->height < 1 || width < 1 || height < 1 ||
-        !bank_sensor_valid(0, pitch, width, height, rec.x0, rec.y0, p->width, p->height, 0, UINT64_MAX, bank_pixel_bpp(format), bin))
+        !bank_sensor_valid_format(0, pitch, width, height, rec.x0, rec.y0, p->width, p->height, 0, UINT64_MAX, format, bin))
         return -EINVAL;
     *out = rec;
     return 0;
@@ -414,8 +416,16 @@ int aof_bank_sensor_valid_binned(const aof_bank_sensor *rec, uint8_t format, uin
                                  uint64_t base, uint64_t camera_bytes)
 {
     if (!rec) return -EINVAL;
-    return bank_sensor_valid(rec->offset, rec->pitch, rec->width, rec->height, rec->x0, rec->y0, crop_width, crop_height, base,
-                             camera_bytes, bank_pixel_bpp(format), bin) ? 1 : 0;
+    return bank_sensor_valid_format(rec->offset, rec->pitch, rec->width, rec->height, rec->x0, rec->y0, crop_width, crop_height, base,
+                                    camera_bytes, format, bin) ? 1 : 0;
+}
+
+int aof_bank_pixel_row_bytes(uint8_t format, int32_t width, int64_t *out)
+{
+    const BankPixelLayout l = bank_pixel_layout(format);
+    if (!out || l.group_px == 0 || width < 1 || width % l.group_px != 0) return -EINVAL;
+    *out = (int64_t)(width / l.group_px) * l.group_bytes;
+    return 0;
 }
 
 int aof_bank_sensor_valid_format(const aof_bank_sensor *rec, uint8_t format, int32_t crop_width, int32_t crop_height, uint64_t base,

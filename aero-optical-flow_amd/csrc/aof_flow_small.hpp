@@ -46,8 +46,8 @@ struct LevelMeta { int px, py, delta; };
 
 // One 16-byte piece of a crop row out of a sensor frame (defined in aof_bank_stream.hpp, the one place a crop is
 // fetched; used below by the PITCHED instantiations only, which that header's kernels make).
-__device__ __forceinline__ void crop_piece16(uint4 &v, const uint8_t *src, int y, int pitch, int x, int bpp, int phase);
-__device__ __forceinline__ void crop_piece16_binned(uint4 &v, const uint8_t *src, int y, int pitch, int x, int bpp, int phase, int bin);
+__device__ __forceinline__ void crop_piece16(uint4 &v, const uint8_t *src, int y, int pitch, int x, int gb, int shift);
+__device__ __forceinline__ void crop_piece16_binned(uint4 &v, const uint8_t *src, int y, int pitch, int x, int gb, int shift, int bin);
 
 // One level of one pair out of LDS: search, records, refinement, votes, flow record.
 // `keys`: one packed key per block; `record_out`: LDS copy of the flow record (level 1: it carries the
@@ -190,16 +190,17 @@ __device__ __forceinline__ void run_level(const SearchArgs &a, const FlowTail &t
 // previous call in LDS and fetches only the new one.
 // PITCHED (the stream bank's camera forms): bit b of `pitched` says that src[b] is a window of a larger image -- its
 // rows lie `pitch` bytes apart and may start on any byte; every other source is a contiguous, 16-byte aligned frame.
-// The camera tick fetches its new frame into buffer 1 (the default); a burst alternates the buffers.  bpp, phase: the
+// The camera tick fetches its new frame into buffer 1 (the default); a burst alternates the buffers.  gb, shift: the
 // windows' pixel format (crop_piece16), looked at by the PACKED instantiations only (the kernels with a sensor argument):
-// 1, 0 is one grey byte per pixel, bpp 2 packed 16-bit pixels whose grey value is byte `phase`; bin 2 or 4: a pixel of
-// the window is the rounded mean of bin x bin sensor pixels (crop_piece16_binned).
+// 1, 0 is one grey byte per pixel, gb 2 16-bit pixels whose grey value is bits shift .. shift + 7, gb 5 and 3 the
+// MIPI-packed groups of Y10P and Y12P; bin 2 or 4: a pixel of the window is the rounded mean of bin x bin sensor pixels
+// (crop_piece16_binned).
 // `search` false: only the fetch (passes A and B) -- the buffers named by `load` then hold their frame, its level-1
 // image and its sums for a later call that names them as the older frame (a stream's first frame inside a burst).
 template <bool SUBPIXEL, bool PITCHED = false, bool PACKED = false>
 __device__ __forceinline__ void flow_small_pair(const SmallArgs &a, uint32_t pair, const uint8_t *src0, const uint8_t *src1,
                                                 int cur_buf, uint32_t load, aof_flow *final_copy = nullptr, int pitch = 0,
-                                                uint32_t pitched = 2u, bool search = true, int bpp = 1, int phase = 0, int bin = 1)
+                                                uint32_t pitched = 2u, bool search = true, int gb = 1, int shift = 0, int bin = 1)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_mem[];
     __shared__ uint32_t s_keys[kThreads];
@@ -224,8 +225,10 @@ __device__ __forceinline__ void flow_small_pair(const SmallArgs &a, uint32_t pai
         uint32_t sum[2] = {0, 0};
         uint32_t rest = load;   // the buffers the loop of 16-byte pieces below fetches: all, but for windows of packed pixels
         if constexpr (PITCHED && PACKED) {
-            if (bin != 1) {   // (uniform) binned windows come first as well: one piece per lane and trip -- a piece is bin
-                              // rows of up to eight loads, and its eight sums are all it keeps
+            if (bin != 1 || gb > 2) {   // (uniform) binned windows come first as well: one piece per lane and trip -- a piece
+                              // is bin rows of up to eight loads, and its eight sums are all it keeps.  MIPI-packed windows
+                              // (gb 5, 3) go the same way, binned or not: a loop of their own, pieces one behind the other
+
                 const int row_chunks = w / 16;
 #pragma unroll
                 for (int buf = 0; buf < 2; buf++) {
@@ -235,7 +238,8 @@ __device__ __forceinline__ void flow_small_pair(const SmallArgs &a, uint32_t pai
                     for (int c = tid; c < per_frame; c += kThreads) {
                         const int y = c / row_chunks, x = c - y * row_chunks;
                         uint4 v;
-                        crop_piece16_binned(v, src, y, pitch, x, bpp, phase, bin);
+                        if (bin != 1) crop_piece16_binned(v, src, y, pitch, x, gb, shift, bin);
+                        else crop_piece16(v, src, y, pitch, x, gb, shift);
                         uint32_t s = 0;
                         s = byte_sum(v.x, s); s = byte_sum(v.y, s);
                         s = byte_sum(v.z, s); s = byte_sum(v.w, s);
@@ -244,7 +248,7 @@ __device__ __forceinline__ void flow_small_pair(const SmallArgs &a, uint32_t pai
                     }
                 }
                 rest = load & ~pitched;
-            } else if (bpp != 1) {   // (uniform) two source bytes per pixel: the windows come first, in trips of half as many
+            } else if (gb != 1) {   // (uniform) two source bytes per pixel: the windows come first, in trips of half as many
                               // pieces -- as many 16-byte loads in flight as below, not twice the registers
                 constexpr int kHalf = kLoads / 2;
                 const int row_chunks = w / 16;
@@ -260,7 +264,7 @@ __device__ __forceinline__ void flow_small_pair(const SmallArgs &a, uint32_t pai
                             v[k] = make_uint4(0, 0, 0, 0);
                             if (c < per_frame) {
                                 const int y = c / row_chunks, x = c - y * row_chunks;
-                                crop_piece16(v[k], src, y, pitch, x, 2, phase);
+                                crop_piece16(v[k], src, y, pitch, x, 2, shift);
                             }
                         }
 #pragma unroll

@@ -108,7 +108,7 @@ __global__ __launch_bounds__(kThreads) void k_ingest(aof_ingest_params p, const 
     mx0 = max(mx0, 0); my0 = max(my0, 0); mx1 = min(mx1, p.crop_width); my1 = min(my1, p.crop_height);
 
     const uint8_t *src = camera + frame * camera_stride + (int64_t)y0 * p.camera_width + x0;
-    int pitch = p.camera_width, bpp = 1, phase = 0;   // (the pixel format: the record's, with a format array; else grey)
+    int pitch = p.camera_width, gb = 1, shift = 0;   // (the pixel format: the record's, with a format array; else grey)
     int bin = 1;                                      // (the binning: the record's, with a binning array)
     if constexpr (sizeof...(Sen) > 0) {   // (uniform, as is the record: one frame per workgroup)
         static_assert(!PYRAMID, "the sequence pipeline has no records");
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(kThreads) void k_ingest(aof_ingest_params p, const 
         if (!r.ok) return;
         src = camera + r.origin;
         pitch = r.pitch;
-        bpp = r.bpp; phase = r.phase;
+        gb = r.gb; shift = r.shift;
         bin = r.bin;
     }
     uint8_t *dst = cropped ? cropped + frame * cropped_stride : nullptr;
@@ -133,7 +133,8 @@ __global__ __launch_bounds__(kThreads) void k_ingest(aof_ingest_params p, const 
         int round = 0;
         for (int base = 0; base < items; base += kUnroll * kThreads) {  // uniform trip count
             if constexpr (sizeof...(Sen) > 0) {
-                if (bin != 1) {   // (uniform, decided per trip: binned pixels) the trip's pieces one behind the other, each used
+                if (bin != 1 || gb > 2) {   // (uniform, decided per trip: binned pixels, and the MIPI-packed forms binned or
+                                  // not) the trip's pieces one behind the other, each used
                                   // before the next is fetched: a piece is bin rows of loads and eight sums of its own, and with
                                   // four of them in flight the kernel took 112 registers and ran half its waves for EVERY frame,
                                   // binned or not (LAB_LOG.md, "Stream bank binned sensor pixels")
@@ -159,7 +160,8 @@ __global__ __launch_bounds__(kThreads) void k_ingest(aof_ingest_params p, const 
                         const bool active = it < items;
                         const int y = row_begin + (active ? it / pieces : 0), x = active ? (it % pieces) * 16 : 0;
                         uint4 val = make_uint4(0, 0, 0, 0);
-                        if (active) crop_piece16_binned(val, src, y, pitch, x / 16, bpp, phase, bin);
+                        if (active && bin != 1) crop_piece16_binned(val, src, y, pitch, x / 16, gb, shift, bin);
+                        else if (active) crop_piece16(val, src, y, pitch, x / 16, gb, shift);
                         consume(val, y, x, active);
                     }
                     continue;
@@ -181,13 +183,13 @@ __global__ __launch_bounds__(kThreads) void k_ingest(aof_ingest_params p, const 
                 ys[u] = row_begin + (act[u] ? it / pieces : 0);
                 xs[u] = act[u] ? (it % pieces) * 16 : 0;
                 v[u] = make_uint4(0, 0, 0, 0);
-                if (act[u] && bpp == 1) crop_piece16(v[u], src, ys[u], pitch, xs[u] / 16, 1, 0);  // window start may be unaligned
+                if (act[u] && gb == 1) crop_piece16(v[u], src, ys[u], pitch, xs[u] / 16, 1, 0);  // window start may be unaligned
             }
             if constexpr (sizeof...(Sen) > 0) {
-                if (bpp != 1) {   // (uniform, decided per trip: packed 16-bit pixels, eight loads in flight)
+                if (gb != 1) {   // (uniform, decided per trip: 16-bit pixels, eight loads in flight)
 #pragma unroll
                     for (int u = 0; u < kUnroll; u++)
-                        if (act[u]) crop_piece16(v[u], src, ys[u], pitch, xs[u] / 16, 2, phase);
+                        if (act[u]) crop_piece16(v[u], src, ys[u], pitch, xs[u] / 16, 2, shift);
                 }
             }
 #pragma unroll
@@ -254,14 +256,14 @@ __global__ __launch_bounds__(kThreads) void k_ingest(aof_ingest_params p, const 
         const int items = (row_end - row_begin) * p.crop_width;
         for (int it = tid; it < items; it += kThreads) {
             const int y = row_begin + it / p.crop_width, x = it % p.crop_width;
-            uint32_t v = src[(int64_t)y * bin * pitch + x * bin * bpp];   // (src: the grey byte of the crop's first pixel)
-            if constexpr (sizeof...(Sen) > 0) {
-                if (bin != 1) {   // (uniform) the pixel's bin x bin sensor pixels, rounded once
-                    v = 0;
-                    for (int j = 0; j < bin; j++)
-                        for (int i = 0; i < bin; i++) v += src[(int64_t)(y * bin + j) * pitch + (x * bin + i) * bpp];
-                    v = (v + bin * bin / 2) >> (bin == 2 ? 2 : 4);
-                }
+            uint32_t v;
+            if constexpr (sizeof...(Sen) > 0) {   // (src: the first group of the crop's first pixel; the form is the record's)
+                v = 0;                            // the pixel's bin x bin sensor pixels, rounded once (bin 1: the pixel)
+                for (int j = 0; j < bin; j++)
+                    for (int i = 0; i < bin; i++) v += crop_pixel(src + (int64_t)(y * bin + j) * pitch, (int64_t)x * bin + i, gb, shift);
+                if (bin != 1) v = (v + bin * bin / 2) >> (bin == 2 ? 2 : 4);
+            } else {
+                v = src[(int64_t)y * pitch + x];
             }
             if (dst) dst[(int64_t)y * p.crop_width + x] = (uint8_t)v;
             if (hist && y >= my0 && y < my1 && x >= mx0 && x < mx1) {

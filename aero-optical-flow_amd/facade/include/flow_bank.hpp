@@ -88,15 +88,18 @@ public:
 	int setStreamSensor(int stream, uint64_t offset, int pitch, int width, int height, int x0, int y0);
 	// Packed 16-bit sensor pixels (include/aof.h, "packed sensor pixels"; format: AOF_PIXEL_GREY8, _LUMA16_LO for YUYV /
 	// Y16_BE, _LUMA16_HI for UYVY / Y16): the buffer a V4L2 driver filled goes in as it is, the crop takes the grey byte of
-	// every pixel.  enableCameraPacked() is enableCamera() for cameras that all deliver `format`: it sizes for n_streams *
-	// camera_width * camera_height * bpp bytes (bpp 1 or 2), every stream starts from the centred record with pitch =
-	// camera_width * bpp and that format, and pushCamera() then takes that many bytes.  -EINVAL also for a format above 2.
+	// every pixel.  Raw mono pixels ("raw mono pixels" there; AOF_PIXEL_Y10, _Y12, _Y14, _Y10P, _Y12P) go in the same way:
+	// the grey value is the top eight bits of a sample.  enableCameraPacked() is enableCamera() for cameras that all
+	// deliver `format`: with row_bytes = aof_bank_pixel_row_bytes(format, camera_width) it sizes for n_streams *
+	// camera_height * row_bytes bytes, every stream starts from the centred record (x0 on a pixel group) with pitch =
+	// row_bytes and that format, and pushCamera() then takes that many bytes.  -EINVAL also for a value that is no format
+	// (3, above 8) and for a camera_width that is not whole pixel groups of the format.
 	int enableCameraPacked(int camera_width, int camera_height, int format, uint16_t exposure0, uint8_t gain0,
 			       uint32_t exposure_interval_us = 200000);
 	// One stream's own format, after either enable call, from the next pushCamera() on: its current record (setStreamSensor(),
 	// or the enable call's) is checked again, with the new format, against the bytes pushCamera() takes; setStreamSensor()
-	// checks with the stream's current format.  Returns 0, or -EINVAL, the object unchanged: a bad stream index, a format
-	// above 2, a record that no longer fits, a call before enabling.  An object on which neither call was made runs exactly
+	// checks with the stream's current format.  Returns 0, or -EINVAL, the object unchanged: a bad stream index, a value
+	// that is no format, a record that no longer fits, a call before enabling.  An object on which neither call was made runs exactly
 	// as before.
 	int setStreamPixelFormat(int stream, int format);
 	// One stream's binning (include/aof.h, "binned sensor pixels"; bin: 1, 2 or 4), after either enable call, from the next

@@ -375,7 +375,8 @@ int OpticalFlowBank::setStreamPixelFormat(int s, int format)
 {
 	Impl *m = _m;
 	if (!m || !m->camera || !m->sensorRecords() || !m->table[kFormats].h || s < 0 || s >= n_streams) return -EINVAL;
-	if (format < AOF_PIXEL_GREY8 || format > AOF_PIXEL_LUMA16_HI)
+	int64_t group_row = 0;   // (a row of four pixels is whole groups of every format: this asks for the format alone)
+	if (format < 0 || format > 255 || aof_bank_pixel_row_bytes((uint8_t)format, 4, &group_row))
 		return refuse(-EINVAL, "setStreamPixelFormat(): no such format");
 	// the stream's current record, by the kernels' own rule, with the new format
 	if (aof_bank_sensor_valid_binned(m->sensorRecords() + s, (uint8_t)format, m->table[kBins].h[s], image_width,
@@ -550,7 +551,9 @@ int OpticalFlowBank::enableCameraPacked(int camera_width, int camera_height, int
 					uint32_t exposure_interval_us)
 {
 	if (!engineOk()) return -1;
-	if (format < AOF_PIXEL_GREY8 || format > AOF_PIXEL_LUMA16_HI) return refuse(-EINVAL, "enableCameraPacked(): no such format");
+	int64_t group_row = 0;   // (as in setStreamPixelFormat(); the camera's own width is held to the format below)
+	if (format < 0 || format > 255 || aof_bank_pixel_row_bytes((uint8_t)format, 4, &group_row))
+		return refuse(-EINVAL, "enableCameraPacked(): no such format");
 	return _m->enableSensorFrames(camera_width, camera_height, format, exposure0, gain0, exposure_interval_us);
 }
 
@@ -561,7 +564,9 @@ int OpticalFlowBank::Impl::enableSensorFrames(int camera_width, int camera_heigh
 {
 	Impl *m = this;
 	const int image_width = self->image_width, image_height = self->image_height, n_streams = self->n_streams;
-	const size_t bpp = format == AOF_PIXEL_GREY8 ? 1 : 2;
+	int64_t row_bytes = 0;   // a sensor row: (camera_width / G) * Bg bytes of the format's groups
+	if (camera_width >= 1 && aof_bank_pixel_row_bytes((uint8_t)format, camera_width, &row_bytes))
+		return self->refuse(-EINVAL, "enableCameraPacked(): the camera width is not whole pixel groups of the format");
 	// a refused call leaves the object as it was: nothing of the object is written before the arguments are accepted
 	if (m->camera) return self->refuse(-EINVAL, "enableCamera() was already called");
 	if (!m->waitIdle()) return -ETIMEDOUT;
@@ -581,7 +586,7 @@ int OpticalFlowBank::Impl::enableSensorFrames(int camera_width, int camera_heigh
 	const size_t S = m->S;
 	void *bank = NULL;
 	if (!m->mem.get(&bank, L.total_bytes, Allocations::kDevice) ||
-	    !m->sensor.alloc(m->mem, S * (size_t)camera_width * (size_t)camera_height * bpp) ||
+	    !m->sensor.alloc(m->mem, S * (size_t)camera_height * (size_t)row_bytes) ||
 	    !m->table[kSensors].alloc(m->mem, S * sizeof(aof_bank_sensor)) ||
 	    !m->table[kFormats].alloc(m->mem, alignUp(S, 16)) ||
 	    !m->table[kBins].alloc(m->mem, alignUp(S, 16)) ||
@@ -595,11 +600,14 @@ int OpticalFlowBank::Impl::enableSensorFrames(int camera_width, int camera_heigh
 	m->bank_bytes = L.total_bytes;
 	m->cam = cam;
 	for (size_t s = 0; s < S; s++) {
-		// the centred record; packed pixels: rows and frames of bpp bytes per pixel, and the stream's format beside it
+		// the centred record; another format than grey bytes: rows of row_bytes, frames of camera_height such rows, the crop
+		// on a pixel group, and the stream's format beside it
 		aof_bank_sensor *rec = m->sensorRecords() + s;
-		aof_bank_sensor_from_camera(&p, &cam, (int32_t)s, rec);
-		rec->offset *= bpp;
-		rec->pitch *= (int32_t)bpp;
+		if (format == AOF_PIXEL_GREY8)
+			aof_bank_sensor_from_camera(&p, &cam, (int32_t)s, rec);
+		else
+			aof_bank_sensor_centred_binned(&p, (uint64_t)s * (uint64_t)camera_height * (uint64_t)row_bytes, (int32_t)row_bytes,
+						       camera_width, camera_height, (uint8_t)format, 1, rec);
 		m->table[kFormats].h[s] = (uint8_t)format;
 	}
 	std::memset(m->table[kBins].h, 1, m->table[kBins].bytes);

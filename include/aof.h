@@ -692,9 +692,10 @@ int aof_ingest_sensors_device(int32_t crop_width, int32_t crop_height, const uin
  *     d_camera + k*round_stride + offset + (y0 + y)*pitch + (x0 + x)*bpp + phase.
  * width, x0 and the crop size stay in pixels, offset and pitch in bytes.  From the cropped frame on nothing changes
  * (exposure mask, histogram, MSV, flow, limiter, wire frame, de-rotation).  The kernels fetch the 32 source bytes of a
- * 16-pixel piece and pack the even or the odd ones (v_perm_b32): no de-interleave pass, no second buffer.
+ * 16-pixel piece and pack every pixel's byte 0 or byte 1 (a uniform shift, then v_perm_b32): no de-interleave pass, no
+ * second buffer.
  * A record with its format is valid iff, in 64 bits so that nothing wraps,
- *     format <= 2;  width >= 1, height >= 1, pitch >= width*bpp;  the crop inside width x height;
+ *     format <= 2 (4 .. 8: "raw mono pixels" below);  width >= 1, height >= 1, pitch >= width*bpp;  the crop inside width x height;
  *     k*round_stride + offset + (height-1)*pitch + width*bpp <= camera_bytes.
  * An invalid record or format is treated as an invalid record is today: AOF_TICK_BAD_SENSOR for that round, not one byte
  * of the stream's frame read, its bank bytes untouched.
@@ -715,7 +716,7 @@ int aof_ingest_sensors_device(int32_t crop_width, int32_t crop_height, const uin
  * -EINVAL: NULL ctx, a non-NULL array with n_streams < 1 (the binding stays as it was). */
 int aof_set_bank_pixel_formats(aof_ctx *ctx, const uint8_t *d_formats, int32_t n_streams);
 /* Host only: aof_bank_sensor_valid for a record of pixel format `format` (the same function the kernels decide with,
- * compiled for the host): 1 valid, 0 not (a format above 2 included).  -EINVAL: NULL rec. */
+ * compiled for the host): 1 valid, 0 not (a value that is no format -- 3, 9..255 -- included).  -EINVAL: NULL rec. */
 int aof_bank_sensor_valid_format(const aof_bank_sensor *rec, uint8_t format, int32_t crop_width, int32_t crop_height,
                                  uint64_t base, uint64_t camera_bytes);
 /* aof_ingest_sensors_device with frame i's pixel format d_formats[i] (u8 [n_frames], device memory, any alignment);
@@ -763,8 +764,9 @@ int aof_set_bank_binning(aof_ctx *ctx, const uint8_t *d_bins, int32_t n_streams)
 int aof_bank_sensor_valid_binned(const aof_bank_sensor *rec, uint8_t format, uint8_t bin, int32_t crop_width, int32_t crop_height,
                                  uint64_t base, uint64_t camera_bytes);
 /* Host only: aof_bank_sensor_centred for a binned stream: x0 = width/2 - (bin*p->width)/2, y0 likewise.
- * -EINVAL: NULL p / out, and wherever the record would be invalid (a format above 2, a bin that is none of 1, 2, 4,
- * pitch < width*bpp, a footprint that is not inside width x height); *out is then not written. */
+ * For the MIPI-packed forms ("raw mono pixels" below) x0 is rounded down to a multiple of G.
+ * -EINVAL: NULL p / out, and wherever the record would be invalid (a value that is no format, a bin that is none of
+ * 1, 2, 4, pitch < row_bytes, a footprint that is not inside width x height); *out is then not written. */
 int aof_bank_sensor_centred_binned(const aof_params *p, uint64_t offset, int32_t pitch, int32_t width, int32_t height,
                                    uint8_t format, uint8_t bin, aof_bank_sensor *out);
 /* aof_ingest_sensor_formats_device with frame i binned d_bins[i] times (u8 [n_frames], device memory, any alignment);
@@ -774,6 +776,45 @@ int aof_ingest_sensors_binned_device(int32_t crop_width, int32_t crop_height, co
                                      const aof_bank_sensor *d_sensors, const uint8_t *d_formats, const uint8_t *d_bins,
                                      int64_t n_frames, uint8_t *d_cropped, int64_t cropped_stride, uint32_t *d_hist, uint8_t *d_ok,
                                      void *stream);
+
+/* ---- the stream bank with raw mono pixels: Y10, Y12, Y14, Y10P and Y12P buffers as the CSI receiver filled them ----
+ * Mono global-shutter flow sensors (OV7251, OV9281, MT9V034) are 10- or 12-bit parts, and without an ISP in front the
+ * V4L2 buffer holds their samples right-justified in 16-bit little-endian words (Y10, Y12, Y14) or MIPI-packed (Y10P:
+ * four pixels in five bytes, Y12P: two pixels in three).  Five more values of a stream's format byte describe them.  A
+ * row is groups of G pixels in Bg bytes; the grey value of sensor pixel X of a row is the top eight bits of its
+ * sample, truncated -- what the sensor's own 8-bit mode gives:
+ *     code  format          Bg / G   grey value of pixel X (row: the row's first byte)
+ *       3   (none)                   no format, as are 9..255
+ *       4   AOF_PIXEL_Y10   2 / 1    (v >> 2) & 0xFF, v the little-endian 16-bit word at row + 2*X
+ *       5   AOF_PIXEL_Y12   2 / 1    (v >> 4) & 0xFF
+ *       6   AOF_PIXEL_Y14   2 / 1    (v >> 6) & 0xFF
+ *       7   AOF_PIXEL_Y10P  5 / 4    the byte at row + (X/4)*5 + X%4 (MIPI RAW10: the four high bytes lead, the fifth
+ *                                    byte holds the low bits)
+ *       8   AOF_PIXEL_Y12P  3 / 2    the byte at row + (X/2)*3 + X%2
+ * with row = d_camera + k*round_stride + offset + Y*pitch.  Bits above the sample and the low-bit bytes of the packed
+ * forms are never looked at.  AOF_PIXEL_LUMA16_LO and _HI are the 16-bit form with shifts 0 and 8, AOF_PIXEL_GREY8 is
+ * 1 / 1.  Everything behind the crop is unchanged, and binning composes as written above: the once-rounded mean of
+ * bin x bin grey values g(X, Y).  The kernels fetch exactly the 32, 20 or 24 source bytes of a 16-pixel piece -- whole
+ * groups of the crop's own pixels -- and select bytes in registers: no unpack pass, no second buffer.
+ * With row_bytes = (width / G) * Bg, a record with one of these formats (and its bin) is valid iff, in 64 bits so that
+ * nothing wraps,
+ *     width % G == 0 and x0 % G == 0;  width >= 1, height >= 1, pitch >= row_bytes;
+ *     the crop's footprint (bin*crop_width x bin*crop_height at x0, y0) inside width x height;
+ *     k*round_stride + offset + (height-1)*pitch + row_bytes <= camera_bytes.
+ * (For G = 1 this is the rule above.)  An invalid record is treated as any invalid record is: AOF_TICK_BAD_SENSOR for
+ * that round, not one byte of the stream's frame read, its bank bytes untouched.  Binding and rewriting: as for every
+ * format byte.  Contract (a) holds for these forms as well: stream s's outputs and bank bytes equal those of the grey
+ * sensor path fed the plane of grey values defined by the table (a grey record of the same width, height, x0, y0 and
+ * the grey buffer's own pitch), byte for byte.
+ * Not served: big-endian samples, Y14P, Bayer mosaics, rounding, an x0 that is no multiple of G. */
+#define AOF_PIXEL_Y10  4   /* 16-bit little-endian word, sample in bits 9..0 */
+#define AOF_PIXEL_Y12  5   /* 16-bit little-endian word, sample in bits 11..0 */
+#define AOF_PIXEL_Y14  6   /* 16-bit little-endian word, sample in bits 13..0 */
+#define AOF_PIXEL_Y10P 7   /* MIPI RAW10: four pixels in five bytes */
+#define AOF_PIXEL_Y12P 8   /* MIPI RAW12: two pixels in three bytes */
+/* Host only: the bytes of a row of `width` pixels of `format`, (width / G) * Bg, into *out; 0.
+ * -EINVAL: a value that is no format, width < 1, width % G != 0, NULL out (*out is then not written). */
+int aof_bank_pixel_row_bytes(uint8_t format, int32_t width, int64_t *out);
 
 /* ---- the stream bank's outbox: the published messages of a push as one dense, ordered, host-pollable list ----
  * A push leaves [K][S] records of which most say "nothing to do": the limiter publishes at 15 Hz from 75 Hz cameras, the

@@ -67,6 +67,14 @@ pixel of the synthetic frame repeated bin x bin times, so every leg searches the
     Y4  AOF_PIXEL_LUMA16_LO sensors binned 4x;
     D2 / D4   what a caller does without the call: aof_ingest_sensors_binned_device of the B2 / B4 sensors into a dense
         grey buffer, then the camera tick on that buffer (sensors and formats bound, as G).
+With --raw-formats, the camera tick with raw mono pixels (AOF_PIXEL_Y10 .. AOF_PIXEL_Y12P), on both bank paths (leg names
+end in the path, 1 or 2).  Every stream's frame lies in a slot of 2 cam_w cam_h bytes, its rows row_bytes of its format apart:
+    G   sensors bound, no formats: grey frames (with AOF_LIB, on a build without the formats: the yardstick of G on this build);
+    R   all AOF_PIXEL_Y10: 16-bit little-endian words, the grey value in bits 2..9;
+    P   all AOF_PIXEL_Y10P: four pixels in five bytes;
+    M   formats mixed per stream (s % 8 over GREY8, LUMA16_LO, LUMA16_HI, Y10, Y12, Y14, Y10P, Y12P);
+    D   what a caller does without the formats: a device unpack of the whole Y10 buffer (a shift of the 16-bit words and a
+        narrowing copy, two launches, 2 + 2 + 2 + 1 bytes moved per sensor pixel) into a grey buffer, then leg G on that.
 K1 / K2 are the legs --camera runs under those names (leg_camera); --per-sensor --legs K1,K2 runs them alone, which is how
 two builds of the library are compared in turn in one session.
 Every leg settles for about 0.2 s of untimed ticks, then times at least --ticks ticks and at least --seconds seconds
@@ -81,7 +89,8 @@ between the repeats is the run-to-run spread a difference between legs has to be
     python tools/bench_bank.py --mavlink-rx > profiles/bank_mavlink_rx_sweep.txt
     python tools/bench_bank.py --per-stream --streams 64,1024 > profiles/bank_per_stream_ab.txt
     python tools/bench_bank.py --per-sensor --streams 64,1024 > profiles/bank_per_sensor_ab.txt
-    python tools/bench_bank.py --binning --repeats 3 > profiles/bank_binning_ab.txt"""
+    python tools/bench_bank.py --binning --repeats 3 > profiles/bank_binning_ab.txt
+    python tools/bench_bank.py --raw-formats --repeats 3 > profiles/bank_raw_formats_ab.txt"""
 import argparse
 import ctypes as C
 import importlib
@@ -340,6 +349,123 @@ def pixel_formats_sweep(a, dev):
                 if all(k + str(path) in m for k in ("G", "P0", "Y", "M", "D")):
                     g, q, y, mm, d = (m[k + str(path)] for k in ("G", "P0", "Y", "M", "D"))
                     line += f"  P0{path}/G{path} {q / g:5.3f}  Y{path}/D{path} {y / d:5.3f}  M{path}/D{path} {mm / d:5.3f}"
+            print(line)
+
+
+RAW_GROUPS = {0: (1, 1, None), 1: (1, 2, 0), 2: (1, 2, 8), 4: (1, 2, 2), 5: (1, 2, 4), 6: (1, 2, 6), 7: (4, 5, None), 8: (2, 3, None)}
+RAW_MIX = (0, 1, 2, 4, 5, 6, 7, 8)
+
+
+def leg_raw(p, S, path, inp, dev, a, cam_w, cam_h, leg):
+    """One of G / R / P / M / D of --raw-formats on `path`: the camera tick with sensor records bound.  inp.frames[k] sits at
+    the centre crop as the grey values of each stream's format (include/aof.h, "raw mono pixels"); every other bit is noise."""
+    eng = aof.FlowEngine(p, 0)
+    eng.set_bank_path(path)
+    bp = aof.bank_params(S, FX, FY, 15, 5_000_000, 1, 100, 0)
+    cam = aof.bank_camera_params(cam_w, cam_h, p.width, p.height, 0, 200_000, DEROTATE, FX, FY)
+    bank = eng.bank_create(bp, dev, camera=cam)
+    fmts = {"G": np.zeros(S, np.uint8), "R": np.full(S, 4, np.uint8), "P": np.full(S, 7, np.uint8),
+            "M": np.array(RAW_MIX, np.uint8)[np.arange(S) % len(RAW_MIX)], "D": np.full(S, 4, np.uint8)}[leg]
+    slot = cam_w * cam_h * (1 if leg == "G" else 2)
+    x0, y0 = cam_w // 2 - p.width // 2, cam_h // 2 - p.height // 2
+    assert cam_w % 4 == 0 and x0 % 4 == 0
+    rows = np.array([cam_w // RAW_GROUPS[int(f)][0] * RAW_GROUPS[int(f)][1] for f in fmts])
+    cams = []
+    for k in range(RING):
+        buf = torch.randint(0, 256, (S, slot), dtype=torch.uint8, device=dev)
+        for f in sorted(set(fmts.tolist())):
+            idx = torch.from_numpy(np.nonzero(fmts == f)[0]).to(dev)
+            G, Bg, shift = RAW_GROUPS[f]
+            frames = inp.frames[k][idx]
+            if shift is None:       # a group's leading bytes are its pixels' grey values
+                view = buf[:, :cam_h * (cam_w // G) * Bg].view(S, cam_h, cam_w // G, Bg)
+                sub = view[idx]
+                sub[:, y0:y0 + p.height, x0 // G:(x0 + p.width) // G, :G] = frames.view(len(idx), p.height, p.width // G, G)
+                view[idx] = sub
+            else:                   # bits shift .. shift + 7 of a little-endian word
+                view = buf[:, :cam_h * cam_w * 2].view(S, cam_h, cam_w, 2)
+                sub = view[idx]
+                old = sub[:, y0:y0 + p.height, x0:x0 + p.width].to(torch.int32)
+                word = (old[..., 0] | old[..., 1] << 8) & ~(0xFF << shift) | frames.to(torch.int32) << shift
+                sub[:, y0:y0 + p.height, x0:x0 + p.width, 0] = (word & 0xFF).to(torch.uint8)
+                sub[:, y0:y0 + p.height, x0:x0 + p.width, 1] = (word >> 8 & 0xFF).to(torch.uint8)
+                view[idx] = sub
+        cams.append(buf)
+    grey = torch.empty((S, cam_w * cam_h), dtype=torch.uint8, device=dev) if leg == "D" else None
+    words = torch.empty((S, cam_w * cam_h), dtype=torch.int16, device=dev) if leg == "D" else None
+    table = aof.bank_sensor_from_camera(p, cam, n=S)
+    if leg != "D":
+        table["offset"] = np.arange(S, dtype=np.uint64) * np.uint64(slot)
+        table["pitch"] = rows
+    d_table = torch.from_numpy(table.view(np.uint8).reshape(S, 32)).to(dev)
+    eng.set_bank_sensors(d_table, S, S * (cam_w * cam_h if leg == "D" else slot))
+    if leg not in ("G", "D"):
+        d_fmts = torch.from_numpy(fmts).to(dev)
+        eng.set_bank_pixel_formats(d_fmts, S)
+    recs = torch.empty((S, 48), dtype=torch.uint8, device=dev)
+    expo = torch.empty((S, 48), dtype=torch.uint8, device=dev)
+    derot = torch.empty((S, 2), dtype=torch.float32, device=dev)
+    wire = torch.empty((S, 56), dtype=torch.uint8, device=dev)
+    lens = torch.empty(S, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    fn, ctx, bpp_, cp = aof.lib.aof_bank_push_camera_device, eng._ctx, C.byref(bp), C.byref(cam)
+    times = torch.zeros(S, dtype=torch.int64, device=dev)
+    rest = (times.data_ptr(), None, inp.gyro.data_ptr(), bank.buffer.data_ptr(), bank.buffer.numel(), recs.data_ptr(), expo.data_ptr(),
+            derot.data_ptr(), wire.data_ptr(), lens.data_ptr(), stream)
+    ptrs = [c.data_ptr() for c in cams]
+    raw16 = [c.view(torch.int16) for c in cams] if leg == "D" else None
+
+    def step(i):
+        times.add_(13333)
+        if leg == "D":
+            torch.bitwise_right_shift(raw16[i % RING], 2, out=words)
+            grey.copy_(words)          # (narrowing: the low byte of each shifted word)
+            rc = fn(ctx, bpp_, cp, grey.data_ptr(), *rest)
+        else:
+            rc = fn(ctx, bpp_, cp, ptrs[i % RING], *rest)
+        if rc:
+            raise aof.AofError(rc, aof.lib.aof_last_error(ctx).decode())
+    out = timed(step, torch.cuda.synchronize, a.ticks, a.seconds, a.settle)
+    r = aof.ticks_view(recs)
+    assert (r["quality"] >= aof.TICK_HELD).all() and (r["frame"] > a.ticks).all(), "the timed ticks were real ticks"
+    eng.close()
+    return out
+
+
+def raw_formats_sweep(a, dev):
+    print("# legs (the digit: bank path 1 / 2): G sensors bound, grey frames; R all Y10; P all Y10P; M formats s % 8 over the eight; "
+          "D device unpack of the Y10 buffer, then G (exposure records, de-rotation, MAVLink frames on, all streams active)")
+    print("# us = microseconds per tick (host clock, ticks ending in a synchronise)")
+    bound = hasattr(aof.lib, "aof_bank_pixel_row_bytes")      # (AOF_LIB may name a build without the formats: G legs only)
+    kinds = ["G", "R", "P", "M", "D"] if bound else ["G"]
+    legs = [(k + str(path), k, path) for path in (1, 2) for k in kinds]
+    if a.legs is not None:
+        legs = [leg for leg in legs if leg[0] in a.legs.split(",")]
+    sizes = [int(s) for s in a.streams.split(",")]
+    results = {}
+    for rep in range(a.repeats):
+        for cfg in a.configs.split(","):
+            p = params_of(cfg)
+            cam_w, cam_h = SENSOR[cfg]
+            for S in sizes:
+                inp = Inputs(p, S, dev)
+                for name, kind, path in legs:
+                    sec, n = leg_raw(p, S, path, inp, dev, a, cam_w, cam_h, kind)
+                    results.setdefault((cfg, S, name), []).append(sec)
+                    print(f"rep {rep} {cfg:11s} S={S:6d} {name:3s} {sec * 1e6:10.2f} us  ({n} ticks)", flush=True)
+                    torch.cuda.empty_cache()
+                del inp
+    print("# ---- summary (median of the repeats; p10..p90 of the repeats in us) ----")
+    for cfg in a.configs.split(","):
+        for S in sizes:
+            m = {n: float(np.median(results[(cfg, S, n)])) for n, _, _ in legs}
+            line = f"{cfg:11s} S={S:6d}  " + "  ".join(
+                f"{n} {m[n] * 1e6:9.2f} us ({np.percentile(results[(cfg, S, n)], 10) * 1e6:.2f}..{np.percentile(results[(cfg, S, n)], 90) * 1e6:.2f})"
+                for n in m)
+            for path in (1, 2):
+                if all(k + str(path) in m for k in ("R", "P", "M", "D")):
+                    r, q, mm, d = (m[k + str(path)] for k in ("R", "P", "M", "D"))
+                    line += f"  R{path}/D{path} {r / d:5.3f}  P{path}/D{path} {q / d:5.3f}  M{path}/D{path} {mm / d:5.3f}"
             print(line)
 
 
@@ -1400,16 +1526,18 @@ def main():
                     "bank paths (G1, ..., D2; --legs G1,G2 runs the yardstick alone, for a build without the call through AOF_LIB)")
     ap.add_argument("--binning", action="store_true", help="the camera tick with binned sensor pixels: legs G, B0, B2, B4, Y4, D2, D4 on both "
                     "bank paths (G1, ..., D42; --legs G1,G2 runs the yardstick alone, for a build without the call through AOF_LIB)")
+    ap.add_argument("--raw-formats", action="store_true", help="the camera tick with raw mono pixels: legs G, R, P, M, D on both bank "
+                    "paths (G1, ..., D2; --legs G1,G2 runs the yardstick alone, for a build without the formats through AOF_LIB)")
     ap.add_argument("--forms", default="plain,camera", help="--burst: entry points to sweep")
     ap.add_argument("--input-bytes-max", type=float, default=24 * 2**30, help="--burst: sizes whose K rounds of input exceed this are skipped")
     a = ap.parse_args()
-    if a.legs is None and not a.per_sensor and not a.pixel_formats and not a.binning:
+    if a.legs is None and not a.per_sensor and not a.pixel_formats and not a.binning and not a.raw_formats:
         a.legs = "T0,T1,T2,C,B"
     if a.burst and a.ticks == ap.get_default("ticks"):
         a.ticks = 1000           # (frame rounds)
     if a.camera and a.streams == ap.get_default("streams"):
         a.streams = "1,64,1024,1536,2048,4096"
-    if (a.pixel_formats or a.binning) and a.streams == ap.get_default("streams"):
+    if (a.pixel_formats or a.binning or a.raw_formats) and a.streams == ap.get_default("streams"):
         a.streams = "64,256,1024,2048"
     if a.exposure_control and a.streams == ap.get_default("streams"):
         a.streams = "64,1024,4096"
@@ -1432,6 +1560,8 @@ def main():
         return pixel_formats_sweep(a, dev)
     if a.binning:
         return binning_sweep(a, dev)
+    if a.raw_formats:
+        return raw_formats_sweep(a, dev)
     if a.mavlink_rx:
         return mavlink_rx_sweep(a, dev)
     if a.imu:
