@@ -8,12 +8,6 @@
 
 namespace aof {
 
-// Bytes per pixel of the first three formats (AOF_PIXEL_GREY8, _LUMA16_LO, _LUMA16_HI): 1, 2, 2; 0 for every other value
-// (the forms of bank_pixel_layout below among them: what asks here knows whole bytes per pixel and one grey byte only).
-AOF_HD_INLINE int32_t bank_pixel_bpp(uint32_t format) { return format == 0 ? 1 : (format <= 2 ? 2 : 0); }
-// Which byte of a pixel holds its grey value: 0, or 1 for AOF_PIXEL_LUMA16_HI.
-AOF_HD_INLINE int32_t bank_pixel_phase(uint32_t format) { return format == 2 ? 1 : 0; }
-
 // How a format lays a row's pixels out ("raw mono pixels", include/aof.h): groups of `group_px` pixels in `group_bytes`
 // bytes -- 1 in 1 (grey), 1 in 2 (every 16-bit form), 4 in 5 (Y10P), 2 in 3 (Y12P); group_px 0 for a value that is no
 // format.  shift: a 16-bit form's grey value is bits shift .. shift + 7 of the pixel's little-endian word (0, 8 for the
@@ -56,14 +50,6 @@ AOF_HD_INLINE bool bank_sensor_valid_groups(uint64_t offset, int32_t pitch, int3
     if (base > camera_bytes || offset > camera_bytes - base) return false;
     const uint64_t extent = (uint64_t)(height - 1) * (uint64_t)pitch + (uint64_t)row_bytes;
     return extent <= camera_bytes - base - offset;
-}
-
-// The G = 1 case: `bpp` bytes per pixel, 1 or 2 (anything else: no).
-AOF_HD_INLINE bool bank_sensor_valid(uint64_t offset, int32_t pitch, int32_t width, int32_t height, int32_t x0, int32_t y0,
-                                     int32_t w, int32_t h, uint64_t base, uint64_t camera_bytes, int32_t bpp = 1, int32_t bin = 1)
-{
-    if (bpp < 1 || bpp > 2) return false;
-    return bank_sensor_valid_groups(offset, pitch, width, height, x0, y0, w, h, base, camera_bytes, 1, bpp, bin);
 }
 
 // The rule for a record whose pixels have the form `format` (AOF_PIXEL_*; a value that is no format: no).

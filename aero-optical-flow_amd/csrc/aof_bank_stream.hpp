@@ -89,9 +89,7 @@ __device__ __forceinline__ BankStream bank_stream(const BankArgs &a, uint32_t s)
 // footprint is bin * w x bin * h sensor pixels at (x0, y0); a value that is none of 1, 2, 4 makes the record invalid.
 struct BankSensor {
     int64_t origin;    // offset + y0 * pitch + x0 / G * gb: the first byte of the crop's first group (0 for an invalid record)
-    int32_t pitch;
-    int32_t gb, shift;    // bytes per group: 1 (grey), 2 (a 16-bit word), 5 (Y10P's four pixels), 3 (Y12P's two); a word's shift
-    int32_t bin;          // sensor pixels per crop pixel and axis (1, 2, 4)
+    CropSource crop;   // the record's pitch, its format's group bytes and shift, its bin (aof_crop.hpp)
     bool ok;
 };
 static_assert(sizeof(aof_bank_sensor) == 32 && offsetof(aof_bank_sensor, pitch) == 8 && offsetof(aof_bank_sensor, width) == 12 &&
@@ -110,11 +108,11 @@ __device__ __forceinline__ BankSensor bank_sensor(const aof_bank_sensor *sensors
     BankSensor v;
     BankPixelLayout l = {1, 1, 0};
     if (formats) l = bank_pixel_layout((uint32_t)__builtin_amdgcn_readfirstlane((int)formats[s]));
-    v.gb = l.group_bytes; v.shift = l.shift;
-    v.bin = 1;
-    if (bins) v.bin = __builtin_amdgcn_readfirstlane((int)bins[s]);
-    v.ok = bank_sensor_valid_groups(offset, pitch, width, height, x0, y0, w, h, base, camera_bytes, l.group_px, l.group_bytes, v.bin);
-    v.pitch = pitch;
+    v.crop.gb = l.group_bytes; v.crop.shift = l.shift;
+    v.crop.bin = 1;
+    if (bins) v.crop.bin = __builtin_amdgcn_readfirstlane((int)bins[s]);
+    v.ok = bank_sensor_valid_groups(offset, pitch, width, height, x0, y0, w, h, base, camera_bytes, l.group_px, l.group_bytes, v.crop.bin);
+    v.crop.pitch = pitch;
     v.origin = v.ok ? (int64_t)offset + (int64_t)y0 * pitch + (int64_t)(x0 >> (l.group_px >> 1)) * l.group_bytes : 0;   // (x0 is whole groups of 1, 2 or 4)
     return v;
 }
@@ -286,124 +284,15 @@ __device__ __forceinline__ void bank_histogram(const BankCamera &c, const uint8_
     __syncthreads();
 }
 
-// Source bytes of 16 pixels of a row: 16 pixels are 16, 8 or 4 whole groups of gb bytes (16, 32, 20, 24 bytes).
-__device__ __forceinline__ int piece_bytes(int gb) { return gb == 5 ? 20 : (gb == 3 ? 24 : 16 * gb); }
-
-// The grey value of pixel x of the row whose first group starts at `row` (the per-pixel path of k_ingest; the header's
-// table, include/aof.h "raw mono pixels"): a grey byte, bits shift .. shift + 7 of a little-endian word, or one of a
-// packed group's leading bytes.  Reads bytes of pixel x's own group only.
-__device__ __forceinline__ uint32_t crop_pixel(const uint8_t *row, int64_t x, int gb, int shift)
-{
-    if (gb == 1) return row[x];
-    if (gb == 2) return (((uint32_t)row[2 * x] | (uint32_t)row[2 * x + 1] << 8) >> shift) & 0xFFu;
-    if (gb == 5) return row[(x >> 2) * 5 + (x & 3)];
-    return row[(x >> 1) * 3 + (x & 1)];
-}
-
-// The ONE fetch of a crop: pixels 16 x .. 16 x + 15 of the crop row whose first group starts at `row`, as 16 grey bytes.
-// gb 1: one 16-byte load wherever the row starts.  gb 2 (16-bit pixels, the grey value in bits shift .. shift + 7 of
-// each little-endian word): the 32 source bytes in two 16-byte loads, every dword shifted right by the uniform `shift`
-// -- byte 0 of d >> shift is one pixel's grey value, byte 2 the next one's -- and v_perm_b32 takes bytes 0 and 2 of
-// each pair of dwords.  gb 5 (Y10P): exactly the piece's 20 bytes, 16 + 4; a group's four leading bytes are its grey
-// values, and the groups start at bytes 0, 5, 10, 15: dword 0, then v_alignbyte_b32 by 1, 2, 3 across the seams.  gb 3
-// (Y12P): exactly 24 bytes, 16 + 8; a group's two leading bytes, so a dword of four pixels is bytes 0, 1, 3, 4 of one
-// pair of dwords or bytes 2, 3, 5, 6 of the next.  The bytes read are pixels x0 + 16 x .. x0 + 16 x + 15 of the sensor
-// row, whole groups and nothing else: inside the row's row_bytes whenever the crop lies inside `width`, so
-// bank_sensor_valid_groups is the bounds proof for every form.  gb and shift are workgroup-uniform; as the constants
-// 1, 0 (every kernel without a sensor argument) the function is the single load it always was.
-__device__ __forceinline__ void crop_piece16(uint4 &v, const uint8_t *src, int y, int pitch, int x, int gb, int shift)
-{
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-    u32x4 r;
-    if (gb == 1) {
-        __builtin_memcpy(&r, src + (int64_t)y * pitch + x * 16, 16);
-    } else if (gb == 2) {
-        u32x4 a, b;
-        const uint8_t *p = src + (int64_t)y * pitch + x * 32;
-        __builtin_memcpy(&a, p, 16);
-        __builtin_memcpy(&b, p + 16, 16);
-        constexpr uint32_t sel = 0x06040200u;
-        r = u32x4{__builtin_amdgcn_perm(a.y >> shift, a.x >> shift, sel), __builtin_amdgcn_perm(a.w >> shift, a.z >> shift, sel),
-                  __builtin_amdgcn_perm(b.y >> shift, b.x >> shift, sel), __builtin_amdgcn_perm(b.w >> shift, b.z >> shift, sel)};
-    } else if (gb == 5) {
-        u32x4 a;
-        uint32_t b;
-        const uint8_t *p = src + (int64_t)y * pitch + x * 20;
-        __builtin_memcpy(&a, p, 16);
-        __builtin_memcpy(&b, p + 16, 4);
-        r = u32x4{a.x, __builtin_amdgcn_alignbyte(a.z, a.y, 1u), __builtin_amdgcn_alignbyte(a.w, a.z, 2u),
-                  __builtin_amdgcn_alignbyte(b, a.w, 3u)};
-    } else {
-        u32x4 a;
-        u32x2 b;
-        const uint8_t *p = src + (int64_t)y * pitch + x * 24;
-        __builtin_memcpy(&a, p, 16);
-        __builtin_memcpy(&b, p + 16, 8);
-        r = u32x4{__builtin_amdgcn_perm(a.y, a.x, 0x04030100u), __builtin_amdgcn_perm(a.z, a.y, 0x06050302u),
-                  __builtin_amdgcn_perm(b.x, a.w, 0x04030100u), __builtin_amdgcn_perm(b.y, b.x, 0x06050302u)};
-    }
-    __builtin_memcpy(&v, &r, 16);   // (one whole 16-byte value for every form)
-}
-
-// B rows of a binned piece: sensor rows B y .. B y + B - 1 of the 16 B pixels behind `row` (the first one's group),
-// added into eight registers of two 16-bit sums each -- crop pixel 2 i in the low half of acc[i], 2 i + 1 in the high
-// half.  A row is B grey pieces of crop_piece16 (B piece_bytes source bytes, the same unaligned loads and byte
-// selection).  B = 2: a grey dword gives two horizontal pair sums, the halves box2 adds; B = 4: a grey dword is one crop
-// pixel's four bytes of the row, v_sad_u8 against zero adds them to the low half, v_sad_hi_u8 to the high half.  The rows
-// go one behind the other (not unrolled): a row's loads are all that is in flight, eight at the most (gb 2, B = 4).
-template <int B>
-__device__ __forceinline__ void binned_rows(uint32_t (&acc)[8], const uint8_t *row, int pitch, int gb, int shift)
-{
-    constexpr uint32_t m = 0x00FF00FFu;
-#pragma unroll 1
-    for (int j = 0; j < B; j++, row += pitch) {
-#pragma unroll
-        for (int q = 0; q < B; q++) {
-            uint4 g;
-            crop_piece16(g, row, 0, 0, q, gb, shift);
-            if constexpr (B == 2) {
-                acc[4 * q + 0] += (g.x & m) + ((g.x >> 8) & m);
-                acc[4 * q + 1] += (g.y & m) + ((g.y >> 8) & m);
-                acc[4 * q + 2] += (g.z & m) + ((g.z >> 8) & m);
-                acc[4 * q + 3] += (g.w & m) + ((g.w >> 8) & m);
-            } else {
-                acc[2 * q] = __builtin_amdgcn_sad_hi_u8(g.y, 0u, byte_sum(g.x, acc[2 * q]));
-                acc[2 * q + 1] = __builtin_amdgcn_sad_hi_u8(g.w, 0u, byte_sum(g.z, acc[2 * q + 1]));
-            }
-        }
-    }
-}
-
-// crop_piece16 for a binned stream (bin 2 or 4, workgroup-uniform): pixels 16 x .. 16 x + 15 of row y of the BINNED crop,
-// each (the sum of its bin x bin sensor pixels + bin^2 / 2) >> (2 log2 bin) -- one rounding of the whole sum, box2's for
-// bin 2.  `src` is the first byte of sensor pixel (x0, y0)'s group.  The piece reads whole pixels x0 + 16 bin x .. x0 + 16 bin
-// (x + 1) - 1 of rows y0 + bin y .. y0 + bin y + bin - 1: inside width and height whenever the footprint is, so
-// bank_sensor_valid_groups (with its bin) is the bounds proof here too.
-__device__ __forceinline__ void crop_piece16_binned(uint4 &v, const uint8_t *src, int y, int pitch, int x, int gb, int shift, int bin)
-{
-    uint32_t acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const uint8_t *row = src + (int64_t)y * bin * pitch + (int64_t)x * (bin * piece_bytes(gb));
-    uint32_t half, mean;
-    if (bin == 2) { binned_rows<2>(acc, row, pitch, gb, shift); half = 0x00020002u; mean = 2; }
-    else { binned_rows<4>(acc, row, pitch, gb, shift); half = 0x00080008u; mean = 4; }
-#pragma unroll
-    for (int i = 0; i < 8; i++) acc[i] = (acc[i] + half) >> mean;   // (bytes 0 and 2 are the two pixels; bytes 1, 3 are not looked at)
-    v = make_uint4(__builtin_amdgcn_perm(acc[1], acc[0], 0x06040200u), __builtin_amdgcn_perm(acc[3], acc[2], 0x06040200u),
-                   __builtin_amdgcn_perm(acc[5], acc[4], 0x06040200u), __builtin_amdgcn_perm(acc[7], acc[6], 0x06040200u));
-}
-
 // CAMERA: the crop of a stream's first frame, sensor rows -> LDS -> slot (a first frame is always due: its histogram
 // comes from the LDS copy).  Ends in a barrier.
-__device__ __forceinline__ void crop_first_frame(const BankCamera &c, const uint8_t *src, int32_t pitch, uint8_t *lds, uint8_t *slot,
-                                                 int gb = 1, int shift = 0, int bin = 1)
+__device__ __forceinline__ void crop_first_frame(const BankCamera &c, const uint8_t *src, const CropSource &from, uint8_t *lds, uint8_t *slot)
 {
     const int row_chunks = c.crop_w / 16, chunks = row_chunks * c.crop_h;
     for (int i = threadIdx.x; i < chunks; i += kThreads) {
         const int y = i / row_chunks, x = i - y * row_chunks;
         uint4 v;
-        if (bin != 1) crop_piece16_binned(v, src, y, pitch, x, gb, shift, bin);   // (uniform)
-        else crop_piece16(v, src, y, pitch, x, gb, shift);
+        crop_piece(v, src, y, x, from);
         reinterpret_cast<uint4 *>(lds)[i] = v;
         reinterpret_cast<uint4 *>(slot)[i] = v;
     }
@@ -417,16 +306,14 @@ __device__ __forceinline__ void crop_first_frame(const BankCamera &c, const uint
 // by the call's scalars, and ok is the constant true -- everything that asks for it folds away.
 struct BankSource {
     const uint8_t *src;
-    int32_t pitch;
+    CropSource crop;   // grey, unbinned -- constants -- without a sensor argument
     bool ok;
-    int32_t gb, shift;    // the source's pixel format (crop_piece16); 1, 0 -- constants -- without a sensor argument
-    int32_t bin;          // sensor pixels per crop pixel and axis (crop_piece16_binned); the constant 1 without one
 };
 template <bool CAMERA>
 __device__ __forceinline__ BankSource bank_source(const BankArgs &a, uint32_t s, uint64_t base = 0)
 {
-    if constexpr (CAMERA) return BankSource{a.cam.camera + (int64_t)s * a.cam.camera_stride + a.cam.origin, a.cam.pitch, true, 1, 0, 1};
-    else return BankSource{a.frames + (int64_t)s * a.frame_stride, 0, true, 1, 0, 1};
+    if constexpr (CAMERA) return BankSource{a.cam.camera + (int64_t)s * a.cam.camera_stride + a.cam.origin, crop_grey(a.cam.pitch), true};
+    else return BankSource{a.frames + (int64_t)s * a.frame_stride, crop_grey(0), true};
 }
 template <bool CAMERA>
 __device__ __forceinline__ BankSource bank_source(const BankArgs &a, uint32_t s, uint64_t base, const BankSensors &sen)
@@ -434,7 +321,7 @@ __device__ __forceinline__ BankSource bank_source(const BankArgs &a, uint32_t s,
     static_assert(CAMERA, "sensor records belong to the camera forms");
     const BankSensor r = bank_sensor(sen.recs, s, a.cam.crop_w, a.cam.crop_h, sen.camera_base + base, sen.camera_bytes, sen.formats,
                                      sen.bins);
-    return BankSource{a.cam.camera + r.origin, r.pitch, r.ok, r.gb, r.shift, r.bin};
+    return BankSource{a.cam.camera + r.origin, r.crop, r.ok};
 }
 
 // The stream's newest frame out of LDS into its slot, by the whole workgroup.

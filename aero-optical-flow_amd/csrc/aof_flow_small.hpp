@@ -4,6 +4,7 @@
 // record of a pair cannot depend on the entry point that computed it.
 #pragma once
 
+#include "aof_crop.hpp"
 #include "aof_device.hpp"
 #include "aof_internal.hpp"
 #include "aof_reduce.hpp"
@@ -43,11 +44,6 @@ __device__ __forceinline__ void lds_bytes12(const uint8_t *frame, int off, uint3
 }
 
 struct LevelMeta { int px, py, delta; };
-
-// One 16-byte piece of a crop row out of a sensor frame (defined in aof_bank_stream.hpp, the one place a crop is
-// fetched; used below by the PITCHED instantiations only, which that header's kernels make).
-__device__ __forceinline__ void crop_piece16(uint4 &v, const uint8_t *src, int y, int pitch, int x, int gb, int shift);
-__device__ __forceinline__ void crop_piece16_binned(uint4 &v, const uint8_t *src, int y, int pitch, int x, int gb, int shift, int bin);
 
 // One level of one pair out of LDS: search, records, refinement, votes, flow record.
 // `keys`: one packed key per block; `record_out`: LDS copy of the flow record (level 1: it carries the
@@ -189,19 +185,18 @@ __device__ __forceinline__ void run_level(const SearchArgs &a, const FlowTail &t
 // b has to be fetched (and its level-1 image and sums made) -- the resident kernel keeps the frame of its
 // previous call in LDS and fetches only the new one.
 // PITCHED (the stream bank's camera forms): bit b of `pitched` says that src[b] is a window of a larger image -- its
-// rows lie `pitch` bytes apart and may start on any byte; every other source is a contiguous, 16-byte aligned frame.
-// The camera tick fetches its new frame into buffer 1 (the default); a burst alternates the buffers.  gb, shift: the
-// windows' pixel format (crop_piece16), looked at by the PACKED instantiations only (the kernels with a sensor argument):
-// 1, 0 is one grey byte per pixel, gb 2 16-bit pixels whose grey value is bits shift .. shift + 7, gb 5 and 3 the
-// MIPI-packed groups of Y10P and Y12P; bin 2 or 4: a pixel of the window is the rounded mean of bin x bin sensor pixels
-// (crop_piece16_binned).
+// rows lie crop.pitch bytes apart and may start on any byte; every other source is a contiguous, 16-byte aligned frame.
+// The camera tick fetches its new frame into buffer 1 (the default); a burst alternates the buffers.  `crop` (aof_crop.hpp)
+// is the windows' source; its pixel format and binning are looked at by the PACKED instantiations only (the kernels with
+// a sensor argument), every other one fetches grey, unbinned rows.
 // `search` false: only the fetch (passes A and B) -- the buffers named by `load` then hold their frame, its level-1
 // image and its sums for a later call that names them as the older frame (a stream's first frame inside a burst).
 template <bool SUBPIXEL, bool PITCHED = false, bool PACKED = false>
 __device__ __forceinline__ void flow_small_pair(const SmallArgs &a, uint32_t pair, const uint8_t *src0, const uint8_t *src1,
-                                                int cur_buf, uint32_t load, aof_flow *final_copy = nullptr, int pitch = 0,
-                                                uint32_t pitched = 2u, bool search = true, int gb = 1, int shift = 0, int bin = 1)
+                                                int cur_buf, uint32_t load, aof_flow *final_copy = nullptr,
+                                                const CropSource &crop = crop_grey(0), uint32_t pitched = 2u, bool search = true)
 {
+    const int pitch = crop.pitch, gb = crop.gb, shift = crop.shift, bin = crop.bin;
     extern __shared__ __attribute__((aligned(16))) uint8_t s_mem[];
     __shared__ uint32_t s_keys[kThreads];
     __shared__ uint32_t s_votes[2][kMaxBins];
@@ -225,6 +220,8 @@ __device__ __forceinline__ void flow_small_pair(const SmallArgs &a, uint32_t pai
         uint32_t sum[2] = {0, 0};
         uint32_t rest = load;   // the buffers the loop of 16-byte pieces below fetches: all, but for windows of packed pixels
         if constexpr (PITCHED && PACKED) {
+            // crop_fetch's three answers (aof_crop.hpp), spelled out: asked through the function, or through crop_piece in
+            // the loop below, the four sensor kernels of the tick and the burst come out as other code (LAB_LOG.md)
             if (bin != 1 || gb > 2) {   // (uniform) binned windows come first as well: one piece per lane and trip -- a piece
                               // is bin rows of up to eight loads, and its eight sums are all it keeps.  MIPI-packed windows
                               // (gb 5, 3) go the same way, binned or not: a loop of their own, pieces one behind the other

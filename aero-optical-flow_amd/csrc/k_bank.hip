@@ -56,12 +56,12 @@ __global__ __launch_bounds__(kThreads) void k_bank_tick(SmallArgs sm, BankArgs a
             }
         }
         if (gate & kGateFirst) {
-            crop_first_frame(a.cam, src, from.pitch, lds_new, slot, from.gb, from.shift, from.bin);
+            crop_first_frame(a.cam, src, from.crop, lds_new, slot);
             if (gate & kGateDue) bank_histogram(a.cam, lds_new, s_hist);
             if (threadIdx.x == 0) bank_tail<true>(a, s, aof_flow{}, true, s_payload, s_hist);
             return;
         }
-        flow_small_pair<SUBPIXEL, true, kSensors>(sm, s, slot, src, 1, 3u, &s_record, from.pitch, 2u, true, from.gb, from.shift, from.bin);
+        flow_small_pair<SUBPIXEL, true, kSensors>(sm, s, slot, src, 1, 3u, &s_record, from.crop);
         // (run_level's last barrier is behind every read of the frames; s_hist is nobody else's)
         if (gate & kGateDue) bank_histogram(a.cam, lds_new, s_hist);
         __syncthreads();

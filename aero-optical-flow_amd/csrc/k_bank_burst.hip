@@ -83,8 +83,8 @@ __device__ __forceinline__ void bank_burst_rounds(SmallArgs sm, BankArgs a, Bank
         const int cur = newest < 0 ? (first ? 0 : 1) : 1 - newest;
         const uint32_t load = first ? 1u : newest < 0 ? 3u : 1u << cur;
         const uint8_t *src = base + (int64_t)k * b.round_stride;
-        flow_small_pair<SUBPIXEL, CAMERA, (sizeof...(Sen) > 0)>(r, s, cur ? slot : src, cur ? src : slot, cur, load, &s_record, from.pitch,
-                                          kWindow << cur, !first, from.gb, from.shift, from.bin);
+        flow_small_pair<SUBPIXEL, CAMERA, (sizeof...(Sen) > 0)>(r, s, cur ? slot : src, cur ? src : slot, cur, load, &s_record, from.crop,
+                                          kWindow << cur, !first);
         // (run_level's last barrier is behind every read of the frames; s_hist is nobody else's)
         if constexpr (CAMERA) {
             if (gate & 2u) bank_histogram(a.cam, f0[cur], s_hist);

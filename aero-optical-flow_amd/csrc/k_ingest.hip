@@ -108,8 +108,7 @@ __global__ __launch_bounds__(kThreads) void k_ingest(aof_ingest_params p, const 
     mx0 = max(mx0, 0); my0 = max(my0, 0); mx1 = min(mx1, p.crop_width); my1 = min(my1, p.crop_height);
 
     const uint8_t *src = camera + frame * camera_stride + (int64_t)y0 * p.camera_width + x0;
-    int pitch = p.camera_width, gb = 1, shift = 0;   // (the pixel format: the record's, with a format array; else grey)
-    int bin = 1;                                      // (the binning: the record's, with a binning array)
+    CropSource from = crop_grey(p.camera_width);   // (grey, unbinned rows of the camera's width; with records, the record's)
     if constexpr (sizeof...(Sen) > 0) {   // (uniform, as is the record: one frame per workgroup)
         static_assert(!PYRAMID, "the sequence pipeline has no records");
         const IngestSensors &sen = (sensors, ...);
@@ -118,9 +117,7 @@ __global__ __launch_bounds__(kThreads) void k_ingest(aof_ingest_params p, const 
         if (sen.ok && strip == 0 && tid == 0) sen.ok[frame] = r.ok ? 1 : 0;
         if (!r.ok) return;
         src = camera + r.origin;
-        pitch = r.pitch;
-        gb = r.gb; shift = r.shift;
-        bin = r.bin;
+        from = r.crop;
     }
     uint8_t *dst = cropped ? cropped + frame * cropped_stride : nullptr;
     const int row_begin = strip * kRowsPerBlock, row_end = min(p.crop_height, row_begin + kRowsPerBlock);
@@ -133,7 +130,7 @@ __global__ __launch_bounds__(kThreads) void k_ingest(aof_ingest_params p, const 
         int round = 0;
         for (int base = 0; base < items; base += kUnroll * kThreads) {  // uniform trip count
             if constexpr (sizeof...(Sen) > 0) {
-                if (bin != 1 || gb > 2) {   // (uniform, decided per trip: binned pixels, and the MIPI-packed forms binned or
+                if (crop_fetch(from) == kFetchOnePiece) {   // (uniform, decided per trip: binned pixels, and the MIPI-packed forms binned or
                                   // not) the trip's pieces one behind the other, each used
                                   // before the next is fetched: a piece is bin rows of loads and eight sums of its own, and with
                                   // four of them in flight the kernel took 112 registers and ran half its waves for EVERY frame,
@@ -160,8 +157,7 @@ __global__ __launch_bounds__(kThreads) void k_ingest(aof_ingest_params p, const 
                         const bool active = it < items;
                         const int y = row_begin + (active ? it / pieces : 0), x = active ? (it % pieces) * 16 : 0;
                         uint4 val = make_uint4(0, 0, 0, 0);
-                        if (active && bin != 1) crop_piece16_binned(val, src, y, pitch, x / 16, gb, shift, bin);
-                        else if (active) crop_piece16(val, src, y, pitch, x / 16, gb, shift);
+                        if (active) crop_piece(val, src, y, x / 16, from);
                         consume(val, y, x, active);
                     }
                     continue;
@@ -183,13 +179,13 @@ __global__ __launch_bounds__(kThreads) void k_ingest(aof_ingest_params p, const 
                 ys[u] = row_begin + (act[u] ? it / pieces : 0);
                 xs[u] = act[u] ? (it % pieces) * 16 : 0;
                 v[u] = make_uint4(0, 0, 0, 0);
-                if (act[u] && gb == 1) crop_piece16(v[u], src, ys[u], pitch, xs[u] / 16, 1, 0);  // window start may be unaligned
+                if (act[u] && from.gb == 1) crop_piece16(v[u], src, ys[u], from.pitch, xs[u] / 16, 1, 0);  // window start may be unaligned
             }
             if constexpr (sizeof...(Sen) > 0) {
-                if (gb != 1) {   // (uniform, decided per trip: 16-bit pixels, eight loads in flight)
+                if (crop_fetch(from) == kFetchHalfTrip) {   // (uniform, decided per trip: 16-bit pixels, eight loads in flight)
 #pragma unroll
                     for (int u = 0; u < kUnroll; u++)
-                        if (act[u]) crop_piece16(v[u], src, ys[u], pitch, xs[u] / 16, 2, shift);
+                        if (act[u]) crop_piece16(v[u], src, ys[u], from.pitch, xs[u] / 16, 2, from.shift);
                 }
             }
 #pragma unroll
@@ -259,11 +255,12 @@ __global__ __launch_bounds__(kThreads) void k_ingest(aof_ingest_params p, const 
             uint32_t v;
             if constexpr (sizeof...(Sen) > 0) {   // (src: the first group of the crop's first pixel; the form is the record's)
                 v = 0;                            // the pixel's bin x bin sensor pixels, rounded once (bin 1: the pixel)
+                const int bin = from.bin;
                 for (int j = 0; j < bin; j++)
-                    for (int i = 0; i < bin; i++) v += crop_pixel(src + (int64_t)(y * bin + j) * pitch, (int64_t)x * bin + i, gb, shift);
+                    for (int i = 0; i < bin; i++) v += crop_pixel(src + (int64_t)(y * bin + j) * from.pitch, (int64_t)x * bin + i, from.gb, from.shift);
                 if (bin != 1) v = (v + bin * bin / 2) >> (bin == 2 ? 2 : 4);
             } else {
-                v = src[(int64_t)y * pitch + x];
+                v = src[(int64_t)y * from.pitch + x];
             }
             if (dst) dst[(int64_t)y * p.crop_width + x] = (uint8_t)v;
             if (hist && y >= my0 && y < my1 && x >= mx0 && x < mx1) {

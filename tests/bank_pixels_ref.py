@@ -1,11 +1,10 @@
 """Inputs and expected values of the packed-pixel tests (tests/test_bank_pixels_ref.py, tests/test_bank_pixels_abi.py,
-tests/test_gpu_bank_pixels.py): the pixel formats of include/aof.h (AOF_PIXEL_*, aof_set_bank_pixel_formats), the crop a
-record and its format mean, byte by byte, and the layout tables of bank_sensors_ref with a format column.  The validity
-rule, the layouts and the packer (whose other byte per packed pixel is seeded noise independent of the luma) are
-bank_sensors_ref's.  Nothing here touches the GPU or the library under test."""
-import numpy as np
-
+tests/test_gpu_bank_pixels.py): the three 8- and 16-bit pixel formats of include/aof.h (AOF_PIXEL_*,
+aof_set_bank_pixel_formats) and the layout tables of bank_sensors_ref with a format column.  The validity rule, the crop,
+the layouts and the packer (whose other byte per packed pixel is seeded noise independent of the luma) are
+crop_source_ref's.  Nothing here touches the GPU or the library under test."""
 import bank_sensors_ref as sref
+import crop_source_ref as csr
 
 GREY8, LUMA16_LO, LUMA16_HI = 0, 1, 2
 FORMATS = (GREY8, LUMA16_LO, LUMA16_HI)
@@ -24,33 +23,26 @@ TABLES = {cfg: ([(w, h, pitch, mod, origin, fmt) for (w, h, _, mod, origin), (pi
 
 
 def bpp_of(fmt):
-    return 1 if fmt == GREY8 else 2
+    """Bytes per pixel of one of FORMATS."""
+    return csr.GROUPS[fmt][1]
 
 
 def phase_of(fmt):
-    return 1 if fmt == LUMA16_HI else 0
+    """Which byte of a pixel of one of FORMATS holds its grey value."""
+    return (csr.GROUPS[fmt][2] or 0) // 8
 
 
-# The rule, the extent, the layouts and the packer are bank_sensors_ref's, which take the format as their last argument (the
-# layout: as the table's last column) and know grey as format 0.
-extent, layout, pack = sref.extent, sref.layout, sref.pack
+extent, layout, pack = csr.extent, sref.layout, csr.pack
 
 
 def valid(rec, fmt, w, h, camera_bytes, base=0):
-    """bank_sensors_ref.valid with the format where the packed tests write it: behind the record."""
-    return sref.valid(rec, w, h, camera_bytes, base, fmt)
+    """The rule (crop_source_ref.valid) as the packed tests write it: no bin."""
+    return csr.valid(rec, fmt, 1, w, h, camera_bytes, base)
 
 
 def crop(buffer, rec, fmt, w, h, base=0):
-    """The w x h crop the record and its format mean, out of the flat uint8 buffer: byte by byte, the header's formula."""
-    bpp, phase = bpp_of(fmt), phase_of(fmt)
-    start = base + int(rec["offset"])
-    pitch, x0, y0 = int(rec["pitch"]), int(rec["x0"]), int(rec["y0"])
-    out = np.empty((h, w), np.uint8)
-    for y in range(h):
-        for x in range(w):
-            out[y, x] = buffer[start + (y0 + y) * pitch + (x0 + x) * bpp + phase]
-    return out
+    """The w x h crop the record and its format mean, out of the flat uint8 buffer."""
+    return csr.crop(buffer, rec, fmt, 1, w, h, base)
 
 
 def retable(cfg, fmts):

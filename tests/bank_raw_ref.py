@@ -1,24 +1,18 @@
 """Inputs and expected values of the raw-mono-pixel tests (tests/test_bank_raw_ref.py, tests/test_bank_raw_abi.py,
 tests/test_gpu_bank_raw.py): the formats of include/aof.h "raw mono pixels" (AOF_PIXEL_Y10 .. AOF_PIXEL_Y12P) beside the
-three older ones as a table of pixel groups, the grey value of a sensor pixel byte by byte from the header's formulas, the
-validity rule in Python integers, a packer whose every bit that is not a grey value is seeded noise, and the layout tables
-of the two small configurations.  Plain numpy: nothing here touches the GPU or the library under test."""
+three older ones (crop_source_ref's table of pixel groups, its grey value byte by byte, rule and packer), the layout tables
+of the two small configurations and their fifteen-tick case.  Plain numpy: nothing here touches the GPU or the library
+under test."""
 import hashlib
 
 import numpy as np
 
-import bank_binning_ref as bref
-import bank_sensors_ref as sref
+import crop_source_ref as csr
+from crop_source_ref import GREY8, LUMA16_LO, LUMA16_HI, Y10, Y12, Y14, Y10P, Y12P
 
-GREY8, LUMA16_LO, LUMA16_HI, Y10, Y12, Y14, Y10P, Y12P = 0, 1, 2, 4, 5, 6, 7, 8
 NEW = (Y10, Y12, Y14, Y10P, Y12P)
 NAMES = {GREY8: "GREY8", LUMA16_LO: "LUMA16_LO", LUMA16_HI: "LUMA16_HI", Y10: "Y10", Y12: "Y12", Y14: "Y14", Y10P: "Y10P", Y12P: "Y12P"}
-# format: (G pixels per group, Bg bytes per group, the grey value's shift inside a 16-bit word or None)
-GROUPS = {GREY8: (1, 1, None), LUMA16_LO: (1, 2, 0), LUMA16_HI: (1, 2, 8), Y10: (1, 2, 2), Y12: (1, 2, 4), Y14: (1, 2, 6),
-          Y10P: (4, 5, None), Y12P: (2, 3, None)}
-NO_FORMATS = (3, 9, 255)
-BINS = bref.BINS
-SENSOR_DTYPE = sref.SENSOR_DTYPE
+GROUPS, NO_FORMATS, BINS, SENSOR_DTYPE = csr.GROUPS, csr.NO_FORMATS, csr.BINS, csr.SENSOR_DTYPE
 
 T = 15                      # ticks 0..9, two ticks nobody is given, and the burst of K = 3 on ticks 12..14
 TICKS, K, BURST = 10, 3, 4  # (burst BURST of K rounds: ticks BURST * K ..)
@@ -29,87 +23,22 @@ SEEDS = {"px4-64": 96, "opencv-128": 97}    # (test_bank_raw_ref.py: every strea
 SIZES = {"px4-64": (64, 64), "opencv-128": (128, 128)}
 
 
-def row_bytes(fmt, width):
-    """(width / G) * Bg, None where the header's function answers -EINVAL."""
-    if fmt not in GROUPS or width < 1 or width % GROUPS[fmt][0]:
-        return None
-    G, Bg, _ = GROUPS[fmt]
-    return width // G * Bg
+row_bytes, valid, extent, grey, put_grey, footprint, crop, record = (csr.row_bytes, csr.valid, csr.extent, csr.grey, csr.put_grey,
+                                                                     csr.footprint, csr.crop, csr.record)
 
 
-def valid(rec, fmt, b, w, h, camera_bytes, base=0):
-    """The rule of include/aof.h in Python integers (which do not wrap)."""
-    if fmt not in GROUPS or b not in BINS:
-        return False
-    G, Bg, _ = GROUPS[fmt]
-    off, pitch, width, height, x0, y0 = (int(rec[n]) for n in ("offset", "pitch", "width", "height", "x0", "y0"))
-    if width < 1 or height < 1 or width % G or x0 % G:
-        return False
-    rb = width // G * Bg
-    if pitch < rb:
-        return False
-    if x0 < 0 or y0 < 0 or x0 + b * w > width or y0 + b * h > height:
-        return False
-    return base + off + (height - 1) * pitch + rb <= camera_bytes
-
-
-def extent(rec, fmt):
-    """Bytes from the frame's first to behind its last."""
-    return (int(rec["height"]) - 1) * int(rec["pitch"]) + row_bytes(fmt, int(rec["width"]))
-
-
-def grey(buffer, row, fmt, X):
-    """The grey value of sensor pixel X of the row that starts at byte `row` of the flat buffer (arrays broadcast): the
-    header's table, byte by byte."""
-    G, Bg, shift = GROUPS[fmt]
-    buffer, row, X = np.asarray(buffer), np.asarray(row, np.int64), np.asarray(X, np.int64)
-    if shift is None:
-        return buffer[row + (X // G) * Bg + X % G]
-    v = buffer[row + 2 * X].astype(np.uint32) | buffer[row + 2 * X + 1].astype(np.uint32) << 8
-    return ((v >> shift) & 0xFF).astype(np.uint8)
-
-
-def put_grey(buffer, row, fmt, X, values):
-    """Writes grey values into the buffer and leaves every other bit of it as it is: the low bits of a sample, the bits
-    above it, the low-bits bytes of the packed groups."""
-    G, Bg, shift = GROUPS[fmt]
-    row, X = np.asarray(row, np.int64), np.asarray(X, np.int64)
-    values = np.asarray(values, np.uint8)
-    if shift is None:
-        buffer[row + (X // G) * Bg + X % G] = values
-        return
-    lo, hi = row + 2 * X, row + 2 * X + 1
-    word = buffer[lo].astype(np.uint32) | buffer[hi].astype(np.uint32) << 8
-    word = (word & ~np.uint32(0xFF << shift)) | values.astype(np.uint32) << shift
-    buffer[lo], buffer[hi] = (word & 0xFF).astype(np.uint8), (word >> 8).astype(np.uint8)
+def pack_buffer(recs, fmts, bins, frames, nbytes, seed):
+    """crop_source_ref.pack with formats and bins where the raw tests write them."""
+    return csr.pack(recs, frames, nbytes, seed, fmts, bins)
 
 
 def pack(grey_plane, fmt, pitch, seed):
-    """A sensor frame of `fmt` whose grey values are grey_plane [H, W]: (H - 1) * pitch + row_bytes bytes of seeded noise
-    -- the samples' low bits, the bits above the sample, the packed forms' low-bits bytes and the row padding keep it, and
-    it does not depend on the plane."""
+    """A sensor frame of `fmt` whose grey values are grey_plane [H, W]: (H - 1) * pitch + row_bytes bytes, crop_source_ref's
+    packer on the one record that is the whole frame."""
     H, W = grey_plane.shape
-    rb = row_bytes(fmt, W)
-    assert rb is not None and pitch >= rb
-    buf = np.random.default_rng(seed).integers(0, 256, (H - 1) * pitch + rb, dtype=np.uint8)
-    put_grey(buf, np.arange(H)[:, None] * pitch, fmt, np.arange(W)[None, :], grey_plane)
-    return buf
-
-
-def footprint(buffer, rec, fmt, b, w, h, base=0):
-    """The grey values of the footprint the record, its format and its bin mean: [b*h, b*w]."""
-    pitch, x0, y0 = int(rec["pitch"]), int(rec["x0"]), int(rec["y0"])
-    Y, X = np.arange(b * h, dtype=np.int64)[:, None], np.arange(b * w, dtype=np.int64)[None, :]
-    return grey(buffer, base + int(rec["offset"]) + (y0 + Y) * pitch, fmt, x0 + X)
-
-
-def crop(buffer, rec, fmt, b, w, h, base=0):
-    """The w x h crop: the once-rounded mean (bank_binning_ref.bin_plane) of bin x bin grey values."""
-    return bref.bin_plane(footprint(buffer, rec, fmt, b, w, h, base), b)
-
-
-def record(*a):
-    return sref.record(*a)
+    rec = csr.record(0, pitch, W, H, 0, 0)
+    assert row_bytes(fmt, W) is not None and pitch >= row_bytes(fmt, W)
+    return csr.pack([rec], grey_plane[None], extent(rec, fmt), seed, [fmt])
 
 
 # ---- the layout tables: rows as bank_pixels_ref.TABLES (width, height, pitch in bytes, offset mod 16, origin, format), the
@@ -141,32 +70,8 @@ S = 10
 
 
 def layout(rows, order, bins, w, h, start=0):
-    """The records [S], formats [S] and the bytes of the buffer: the frames one behind the other in `order`, each at the
-    next offset with its row's residue mod 16; the last frame's last byte is the buffer's last."""
-    recs, fmts = np.zeros(len(rows), SENSOR_DTYPE), np.zeros(len(rows), np.uint8)
-    cursor = start
-    for s in order:
-        width, height, pitch, mod, origin, fmt = rows[s]
-        b = int(bins[s])
-        off = cursor + (mod - cursor) % 16
-        x0, y0 = origin if origin is not None else (width // 2 - b * w // 2, height // 2 - b * h // 2)
-        recs[s], fmts[s] = sref.record(off, pitch, width, height, x0, y0), fmt
-        cursor = off + extent(recs[s], fmt)
-    return recs, fmts, cursor
-
-
-def pack_buffer(recs, fmts, bins, frames, nbytes, seed):
-    """A noise buffer of nbytes in which stream s's footprint, read in its format and binned by bins[s], gives frames[s]
-    ([S, h, w]); the footprint's sensor pixels are bank_binning_ref.spread's noise around each crop pixel."""
-    rng = np.random.default_rng(seed)
-    buf = rng.integers(0, 256, nbytes, dtype=np.uint8)
-    h, w = frames.shape[1:]
-    for s, rec in enumerate(recs):
-        fmt, b = int(fmts[s]), int(bins[s])
-        foot = bref.spread(frames[s], b, rng)
-        pitch, x0, y0 = int(rec["pitch"]), int(rec["x0"]), int(rec["y0"])
-        put_grey(buf, int(rec["offset"]) + (y0 + np.arange(b * h)[:, None]) * pitch, fmt, x0 + np.arange(b * w)[None, :], foot)
-    return buf
+    """crop_source_ref.layout with the bins where the raw tests write them."""
+    return csr.layout(rows, order, w, h, bins, start)
 
 
 def grey_table(w, h, n=S):

@@ -1,17 +1,13 @@
 """Inputs and expected values of the per-stream sensor tests (tests/test_bank_sensors_ref.py, tests/test_bank_sensors_abi.py,
-tests/test_gpu_bank_sensors.py): the sensor record of include/aof.h (aof_bank_sensor) and its validity rule restated in
-Python integers, the crop a record means by numpy slicing, the layout tables of the tests and a packer that lays S
-sensor frames of different sizes, pitches and alignments into one byte buffer.  Nothing here touches the GPU or the
-library under test."""
-import numpy as np
-
+tests/test_gpu_bank_sensors.py): the layout tables of grey sensors of different sizes, pitches and alignments and the
+48-tick case.  The record, the rule, the crop, the layout and the packer are crop_source_ref's, here in the grey tests'
+spelling.  Nothing here touches the GPU or the library under test."""
 import bank_cases
 import bank_rig
+import crop_source_ref as csr
 from bank_rig import GATED, LIMITED
 
-SENSOR_DTYPE = np.dtype([("offset", "<u8"), ("pitch", "<i4"), ("width", "<i4"), ("height", "<i4"), ("x0", "<i4"), ("y0", "<i4"),
-                         ("reserved", "<u4")])
-assert SENSOR_DTYPE.itemsize == 32
+SENSOR_DTYPE, record, extent, pack = csr.SENSOR_DTYPE, csr.record, csr.extent, csr.pack
 TICK_BAD_SENSOR = -5
 
 # (cfg, S, seed) of the two configurations; tests/test_bank_sensors_ref.py asserts the census on the oracle's records
@@ -36,75 +32,20 @@ UNIFORM = {"px4-64": (96, 80), "opencv-128": (160, 144)}      # rig B: every str
 SCALARS = {"px4-64": (72, 66), "opencv-128": (136, 130)}      # what aof_bank_camera holds while records are bound: no stream's
 
 
-def _format(fmt):
-    """(bytes per pixel, the luma's byte in the pixel) of a pixel format, None of a value that is none.  The formats are
-    bank_pixels_ref's, imported late: that module builds its tables on this one's."""
-    import bank_pixels_ref as pref
-    return (pref.bpp_of(fmt), pref.phase_of(fmt)) if fmt in pref.FORMATS else None
-
-
 def valid(rec, w, h, camera_bytes, base=0, fmt=0):
-    """The rule of include/aof.h in Python integers (which do not wrap); fmt: the stream's pixel format, 0 is grey."""
-    if _format(fmt) is None:
-        return False
-    bpp = _format(fmt)[0]
-    off, pitch, width, height, x0, y0 = (int(rec[n]) for n in ("offset", "pitch", "width", "height", "x0", "y0"))
-    if width < 1 or height < 1 or pitch < width * bpp:
-        return False
-    if x0 < 0 or y0 < 0 or x0 + w > width or y0 + h > height:
-        return False
-    return base + off + (height - 1) * pitch + width * bpp <= camera_bytes
-
-
-def extent(rec, fmt=0):
-    """Bytes from the frame's first to behind its last."""
-    return (int(rec["height"]) - 1) * int(rec["pitch"]) + int(rec["width"]) * _format(fmt)[0]
+    """The rule (crop_source_ref.valid) as the grey tests write it: no bin, the format last."""
+    return csr.valid(rec, fmt, 1, w, h, camera_bytes, base)
 
 
 def crop(buffer, rec, w, h, base=0):
-    """The w x h crop the record means, out of the flat uint8 buffer."""
-    start = base + int(rec["offset"])
-    pitch, x0, y0 = int(rec["pitch"]), int(rec["x0"]), int(rec["y0"])
-    rows = [buffer[start + (y0 + y) * pitch + x0:start + (y0 + y) * pitch + x0 + w] for y in range(h)]
-    return np.stack(rows)
-
-
-def record(offset, pitch, width, height, x0, y0):
-    r = np.zeros((), SENSOR_DTYPE)
-    r["offset"], r["pitch"], r["width"], r["height"], r["x0"], r["y0"] = offset, pitch, width, height, x0, y0
-    return r
+    """The w x h crop a grey record means, out of the flat uint8 buffer."""
+    return csr.crop(buffer, rec, csr.GREY8, 1, w, h, base)
 
 
 def layout(table, order, w, h, start=0):
-    """The records [S] of a table's sensors laid one behind the other in `order`, each at the next offset with the
-    table's residue mod 16, and the bytes the buffer needs: the last frame's last byte is the buffer's last.  A table with
-    a format as its rows' last column (bank_pixels_ref.TABLES, the pitch in bytes of that format) gives (records,
-    formats [S] uint8, bytes)."""
-    recs, fmts = np.zeros(len(table), SENSOR_DTYPE), np.zeros(len(table), np.uint8)
-    cursor = start
-    for s in order:
-        width, height, pitch, mod, origin = table[s][:5]
-        fmts[s] = table[s][5] if len(table[s]) > 5 else 0
-        off = cursor + (mod - cursor) % 16
-        x0, y0 = origin if origin is not None else (width // 2 - w // 2, height // 2 - h // 2)
-        recs[s] = record(off, pitch, width, height, x0, y0)
-        cursor = off + extent(recs[s], int(fmts[s]))
-    return (recs, fmts, cursor) if len(table[0]) > 5 else (recs, cursor)
-
-
-def pack(recs, frames, nbytes, seed, fmts=None):
-    """A noise buffer of nbytes in which every record's crop, read in its format (fmts None: all grey), holds frames[s]
-    ([S, h, w]).  Every other byte -- the chroma or low byte of each packed pixel included -- keeps the seeded noise, which
-    does not depend on the frames."""
-    buf = np.random.default_rng(seed).integers(0, 256, nbytes, dtype=np.uint8)
-    h, w = frames.shape[1:]
-    for s, rec in enumerate(recs):
-        bpp, phase = _format(0 if fmts is None else int(fmts[s]))
-        pitch = int(rec["pitch"])
-        start = int(rec["offset"]) + int(rec["y0"]) * pitch + int(rec["x0"]) * bpp + phase
-        for y in range(h):
-            buf[start + y * pitch:start + y * pitch + w * bpp:bpp] = frames[s, y]
-    return buf
+    """crop_source_ref.layout: (records, bytes) of a grey table, (records, formats, bytes) of one with a format column."""
+    recs, fmts, end = csr.layout(table, order, w, h, start=start)
+    return (recs, fmts, end) if len(table[0]) > 5 else (recs, end)
 
 
 _cases = {}

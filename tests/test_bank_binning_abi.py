@@ -2,12 +2,11 @@
 header, library and binding, the macro has the header's value, aof_bank_sensor_valid_binned decides as the rule in Python
 integers (tests/bank_binning_ref.py) at the edges it is held at, aof_bank_sensor_centred_binned centres the footprint, and the
 calls refuse what they can refuse without a device.  The rule itself runs under UBSan and ASan in a stand-alone program
-with its own main against a 128-bit restatement (tests/native/bank_binning_rule_selftest.cpp); nothing sanitised is loaded
-into Python.  (A binning bound without sensors and a count mismatch need a context: tests/test_gpu_bank_binning.py.)"""
+(tests/test_crop_rule_ubsan.py).  (A binning bound without sensors and a count mismatch need a context:
+tests/test_gpu_bank_binning.py.)"""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,7 +17,6 @@ import bank_sensors_ref as sref
 
 EINVAL = -22
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CXX = os.environ.get("CXX", "c++")
 NAMES = ("aof_set_bank_binning", "aof_bank_sensor_valid_binned", "aof_bank_sensor_centred_binned", "aof_ingest_sensors_binned_device")
 BIN_BYTES = (0, 1, 2, 3, 4, 8, 255)
 
@@ -125,15 +123,3 @@ def test_calls_refuse_what_they_can_without_a_device(aof):
     args[7] = 0
     assert ingest(*args) == 0, "no frames: nothing to do, nothing launched"
     assert (buf == 0xEE).all(), "a refused call writes nothing"
-
-
-def test_the_rule_with_a_bin_neither_wraps_nor_overflows(tmp_path):
-    csrc = os.path.join(ROOT, "aero-optical-flow_amd", "csrc")
-    exe = tmp_path / "bank_binning_rule_selftest"
-    cmd = [CXX, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           "-I" + os.path.join(ROOT, "include"), "-I" + csrc, os.path.join(ROOT, "tests", "native", "bank_binning_rule_selftest.cpp"),
-           "-o", str(exe)]
-    subprocess.run(cmd, check=True, timeout=300)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, f"rc={r.returncode}\n{r.stdout}{r.stderr}"
-    assert "agree" in r.stdout

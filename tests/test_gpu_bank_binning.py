@@ -3,7 +3,7 @@ sensor buffers hold noisy footprints, against a twin bank on grey sensors that h
 numpy model, and against the oracle chain -- by bytes, never by tolerance.  Bursts, invalid footprints and bins, bins
 rewritten between ticks (eagerly and through a replayed graph), the stateless ingest and the facade.  The model, the tables
 and the packer: tests/bank_binning_ref.py (checked on the CPU: tests/test_bank_binning_ref.py); the rigs:
-tests/bank_binning_rig.py on tests/bank_sensor_rig.py."""
+tests/bank_sensor_rig.py."""
 
 import numpy as np
 import pytest
@@ -13,10 +13,9 @@ import bank_camera_ref as cref
 import bank_pixels_ref as pref
 import bank_sensors_ref as sref
 import ingest_ref
-from bank_binning_rig import BinnedRig, TwinRig
 from bank_ref import FX, FY
 from bank_rig import EINVAL, OFFSET, Guarded, counts_of, put, same, same_exposure, same_records, untouched, up
-from bank_sensor_rig import SLACK, same_rigs, table_tensor
+from bank_sensor_rig import SLACK, BinnedRig, GreyTwin, same_rigs, table_tensor
 from bank_rig import time_limit   # (this module's fixture too: every test under a limit of its own)
 
 pytestmark = pytest.mark.gpu
@@ -42,7 +41,7 @@ def test_a_mixed_bank_leaves_the_bytes_of_a_grey_bank_on_the_host_binned_crops_a
     p, run, want, wire, due, after, derot = bref.case(aof, orc, synth, cfg)
     _, _, cam, bp, (ea, eb) = setup(aof, synth, orc, cfg, path)
     a = BinnedRig(aof, ea, run, bp, gpu_device, cam, p.width, p.height)
-    b = TwinRig(aof, eb, run, bp, gpu_device, cam, p.width, p.height, a)
+    b = GreyTwin(aof, eb, run, bp, gpu_device, cam, a)
     a.bind(), b.bind()
     assert sorted(zip(a.layout_formats[0].tolist(), a.host_bins.tolist())) == sorted(bref.COMBOS)
     uniform = cref.CameraRun(run, p.width + 32, p.height + 16, 9)     # (the oracle crops at the centre: the same crops)
@@ -180,7 +179,7 @@ def test_a_bin_rewritten_between_ticks_eager_and_through_a_replayed_graph(aof, o
     p, run, cam, bp, (ea, eb) = setup(aof, synth, orc, cfg, path)
     assert bref.COMBOS[s] == (pref.LUMA16_LO, 4)
     a = BinnedRig(aof, ea, run, bp, gpu_device, cam, 64, 64)
-    b = TwinRig(aof, eb, run, bp, gpu_device, cam, 64, 64, a)
+    b = GreyTwin(aof, eb, run, bp, gpu_device, cam, a)
     a.bind(), b.bind()
     mask = torch.zeros(S, dtype=torch.uint8, device=gpu_device)
     mask[s] = 1
@@ -332,7 +331,7 @@ def test_bindings_and_refusals(aof, orc, synth, gpu_device):
     cfg = "px4-64"
     p, run, cam, bp, (ea, eb) = setup(aof, synth, orc, cfg, 0)
     a = BinnedRig(aof, ea, run, bp, gpu_device, cam, 64, 64)
-    b = TwinRig(aof, eb, run, bp, gpu_device, cam, 64, 64, a)
+    b = GreyTwin(aof, eb, run, bp, gpu_device, cam, a)
     a.bind(), b.bind()
     setter = aof.lib.aof_set_bank_binning
     base = a.bins.data_ptr()

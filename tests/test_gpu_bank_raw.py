@@ -3,7 +3,7 @@ streams whose sensor buffers hold 16-bit words and MIPI-packed groups full of no
 bank on grey sensors that hold the planes the numpy model reads out of those buffers -- by bytes, never by tolerance.  Ticks
 and a burst, a mixed bank against banks of one, invalid records, a format rewritten between ticks, the stateless ingest on
 its vector and its per-pixel path, and the facade.  The model, the tables and the packer: tests/bank_raw_ref.py (checked
-on the CPU: tests/test_bank_raw_ref.py); the rigs: tests/bank_raw_rig.py on tests/bank_sensor_rig.py.  Every camera buffer
+on the CPU: tests/test_bank_raw_ref.py); the rigs: tests/bank_sensor_rig.py.  Every camera buffer
 is allocated with more than 64 bytes of slack behind camera_bytes."""
 
 import numpy as np
@@ -14,10 +14,9 @@ import bank_raw_ref as rref
 import bank_ref as ref
 import bank_sensors_ref as sref
 import ingest_ref
-from bank_raw_rig import GreyTwin, RawRig
 from bank_ref import FX, FY
 from bank_rig import EINVAL, OFFSET, Guarded, put, same, same_records, untouched, up
-from bank_sensor_rig import SLACK, same_rigs, table_tensor
+from bank_sensor_rig import SLACK, GreyTwin, RawRig, same_rigs, table_tensor
 from bank_rig import time_limit   # (this module's fixture too: every test under a limit of its own)
 
 pytestmark = pytest.mark.gpu
