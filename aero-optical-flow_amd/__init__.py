@@ -112,6 +112,18 @@ BANK_SENSOR_DTYPE = np.dtype([("offset", "<u8"), ("pitch", "<i4"), ("width", "<i
 assert BANK_SENSOR_DTYPE.itemsize == 32 and C.sizeof(BankSensor) == 32
 
 
+# a node of a warp mesh (aof_warp_point): the sensor-plane coordinate of a crop pixel's centre in 1/32 pixel
+WARP_POINT_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4")])
+WARP_CELL = 8
+WARP_FRAC_BITS = 5
+WARP_NONE = -2**31     # AOF_WARP_NONE in a mesh's first node's x: the stream is not warped
+
+
+class Lens(C.Structure):
+    """aof_lens: the sensor camera and its Brown-Conrady coefficients, and the virtual pinhole camera of the crop."""
+    _fields_ = [(n, C.c_double) for n in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "out_fx", "out_fy", "out_cx", "out_cy")]
+
+
 class BankLayout(C.Structure):
     """``struct aof_bank_layout`` (include/aof.h)."""
     _fields_ = [(n, C.c_size_t) for n in ("total_bytes", "frames", "state", "scratch")]
@@ -298,6 +310,12 @@ def _load():
                                                      P(BankSensor)]),
         "aof_ingest_sensors_binned_device": (C.c_int, [C.c_int32, C.c_int32, VP, C.c_uint64, VP, VP, VP, I64, VP, I64, VP, VP, VP]),
         "aof_bank_pixel_row_bytes": (C.c_int, [C.c_uint8, C.c_int32, P(C.c_int64)]),
+        "aof_warp_mesh_size": (C.c_int, [P(Params), P(C.c_int32), P(C.c_int32)]),
+        "aof_warp_mesh_identity": (C.c_int, [P(Params), C.c_int32, C.c_int32, VP]),
+        "aof_warp_mesh_from_lens": (C.c_int, [P(Params), P(Lens), VP]),
+        "aof_set_bank_warps": (C.c_int, [VP, VP, C.c_int32]),
+        "aof_ingest_warped_device": (C.c_int, [C.c_int32, C.c_int32, VP, C.c_uint64, VP, VP, VP, I64, VP, I64, VP, VP, VP]),
+        "aof_warp_host": (C.c_int, [C.c_int32, C.c_int32, VP, C.c_uint64, P(BankSensor), C.c_uint8, VP, VP, VP]),
         "aof_bank_camera_layout": (C.c_int, [P(Params), P(BankParams), P(BankCamera), P(BankLayout), P(C.c_size_t)]),
         "aof_bank_push_camera_device": (C.c_int, [VP, P(BankParams), P(BankCamera), VP, VP, VP, VP, VP, C.c_size_t, VP, VP, VP,
                                                   VP, VP, VP]),
@@ -568,6 +586,83 @@ def ingest_sensors(camera, sensors, crop_w, crop_h, camera_bytes=None, cropped=N
         rc = lib.aof_ingest_sensors_device(*head, *tail)
     else:
         rc = lib.aof_ingest_sensor_formats_device(*head, formats.data_ptr(), *tail)
+    if rc:
+        raise AofError(rc, lib.aof_strerror(rc).decode())
+    return cropped, hist, ok
+
+
+def warp_mesh_size(p: Params):
+    """aof_warp_mesh_size: (nx, ny), the nodes of the mesh of p.width x p.height -- one every WARP_CELL crop pixels."""
+    nx, ny = C.c_int32(0), C.c_int32(0)
+    rc = lib.aof_warp_mesh_size(C.byref(p), C.byref(nx), C.byref(ny))
+    if rc:
+        raise AofError(rc, lib.aof_strerror(rc).decode())
+    return int(nx.value), int(ny.value)
+
+
+def warp_mesh_identity(p: Params, x0, y0) -> np.ndarray:
+    """aof_warp_mesh_identity: the mesh [ny, nx] (WARP_POINT_DTYPE) that gives the plain crop at (x0, y0) byte for byte."""
+    nx, ny = warp_mesh_size(p)
+    out = np.zeros((ny, nx), WARP_POINT_DTYPE)
+    rc = lib.aof_warp_mesh_identity(C.byref(p), int(x0), int(y0), out.ctypes.data)
+    if rc:
+        raise AofError(rc, lib.aof_strerror(rc).decode())
+    return out
+
+
+def warp_mesh_from_lens(p: Params, fx, fy, cx, cy, k1=0.0, k2=0.0, p1=0.0, p2=0.0, k3=0.0, out_fx=None, out_fy=None, out_cx=None,
+                        out_cy=None) -> np.ndarray:
+    """aof_warp_mesh_from_lens: the mesh [ny, nx] of a Brown-Conrady lens (fx, fy, cx, cy in plane pixels) seen by the
+    virtual pinhole camera out_* of the crop (default: the same focal lengths, the principal point at the crop's
+    centre).  The caller binds out_fx, out_fy as the stream's focal lengths."""
+    lens = Lens(fx, fy, cx, cy, k1, k2, p1, p2, k3, fx if out_fx is None else out_fx, fy if out_fy is None else out_fy,
+                p.width / 2.0 if out_cx is None else out_cx, p.height / 2.0 if out_cy is None else out_cy)
+    nx, ny = warp_mesh_size(p)
+    out = np.zeros((ny, nx), WARP_POINT_DTYPE)
+    rc = lib.aof_warp_mesh_from_lens(C.byref(p), C.byref(lens), out.ctypes.data)
+    if rc:
+        raise AofError(rc, lib.aof_strerror(rc).decode())
+    return out
+
+
+def warp_host(camera, rec, crop_w, crop_h, mesh, format=0, camera_bytes=None):
+    """aof_warp_host: one frame in host memory through its mesh, by the header the kernel compiles.  camera: a flat uint8
+    array; rec: a BANK_SENSOR_DTYPE record; mesh: [ny, nx] of WARP_POINT_DTYPE.  Returns (crop [crop_h, crop_w] uint8,
+    hist [10] uint32), or None where the record is not valid."""
+    camera = np.ascontiguousarray(camera, np.uint8).reshape(-1)
+    mesh = np.ascontiguousarray(mesh, WARP_POINT_DTYPE)
+    r = BankSensor.from_buffer_copy(np.asarray(rec, dtype=BANK_SENSOR_DTYPE).tobytes())
+    crop, hist = np.zeros((int(crop_h), int(crop_w)), np.uint8), np.zeros(10, np.uint32)
+    rc = lib.aof_warp_host(int(crop_w), int(crop_h), camera.ctypes.data, camera.size if camera_bytes is None else int(camera_bytes),
+                           C.byref(r), int(format) & 0xFF, mesh.ctypes.data, crop.ctypes.data, hist.ctypes.data)
+    if rc < 0:
+        raise AofError(rc, lib.aof_strerror(rc).decode())
+    return (crop, hist) if rc else None
+
+
+def ingest_warped(camera, sensors, points, crop_w, crop_h, camera_bytes=None, cropped=None, hist=None, ok=None, want_cropped=True,
+                  want_hist=True, want_ok=True, formats=None):
+    """aof_ingest_warped_device: ingest_sensors with frame i resampled through mesh i.  points: uint8 CUDA tensor of
+    n * ny * nx * 8 bytes (WARP_POINT_DTYPE nodes, 16-byte aligned).  Returns (cropped, hist, ok) as ingest_sensors does."""
+    import torch
+    assert camera.dtype == torch.uint8 and sensors.dtype == torch.uint8 and sensors.is_contiguous() and sensors.numel() % 32 == 0
+    assert points.dtype == torch.uint8 and points.is_contiguous()
+    n = sensors.numel() // 32
+    assert formats is None or (formats.dtype == torch.uint8 and formats.is_contiguous() and formats.numel() == n)
+    nodes = ((int(crop_w) + 7) // 8 + 1) * ((int(crop_h) + 7) // 8 + 1)
+    assert points.numel() >= n * nodes * 8
+    dev = camera.device
+    if cropped is None and want_cropped:
+        cropped = torch.empty((n, crop_h, crop_w), dtype=torch.uint8, device=dev)
+    if hist is None and want_hist:
+        hist = torch.empty((n, 10), dtype=torch.int32, device=dev)
+    if ok is None and want_ok:
+        ok = torch.empty((n,), dtype=torch.uint8, device=dev)
+    opt = lambda t: t.data_ptr() if t is not None else None
+    rc = lib.aof_ingest_warped_device(int(crop_w), int(crop_h), camera.data_ptr(), camera.numel() if camera_bytes is None else int(camera_bytes),
+                                      sensors.data_ptr(), opt(formats), points.data_ptr(), n, opt(cropped),
+                                      cropped.stride(0) if cropped is not None and n else crop_w * crop_h, opt(hist), opt(ok),
+                                      torch.cuda.current_stream(dev).cuda_stream)
     if rc:
         raise AofError(rc, lib.aof_strerror(rc).decode())
     return cropped, hist, ok
@@ -1349,6 +1444,23 @@ class FlowEngine:
         it may be rewritten between ticks."""
         self._bind_bank_table(lib.aof_set_bank_binning, "_bank_bins", bins, n_streams, 1)
 
+    def set_bank_warps(self, points=None, n_streams=None):
+        """aof_set_bank_warps: binds a uint8 CUDA tensor of S meshes (S * ny * nx nodes of WARP_POINT_DTYPE, 16-byte
+        aligned; warp_mesh_size) to the context, or with None unbinds.  n_streams: S, where the tensor holds more.  While it
+        is bound every camera push of S streams resamples stream s's crop through mesh s (a first node with x == WARP_NONE:
+        the plain crop) and takes the composed path.  The kernels read it when they run: keep it alive; it may be rewritten
+        between ticks."""
+        nx, ny = warp_mesh_size(self.params)
+        self._bind_bank_table(lib.aof_set_bank_warps, "_bank_warps", points, n_streams, nx * ny * 8)
+
+    def ingest_warped(self, camera, sensors, points, **kw):
+        """ingest_warped for the context's crop size."""
+        return ingest_warped(camera, sensors, points, self.params.width, self.params.height, **kw)
+
+    def warp_host(self, camera, rec, mesh, format=0, camera_bytes=None):
+        """warp_host for the context's crop size."""
+        return warp_host(camera, rec, self.params.width, self.params.height, mesh, format, camera_bytes)
+
     def set_bank_path(self, path=0):
         """0: the library chooses between the one-launch tick kernel and the composed path, 1: the tick kernel where
         the configuration allows it, 2: always the composed path.  Same bytes either way."""
@@ -1476,6 +1588,8 @@ def facade_lib():
         f.aof_facade_bank_set_stream_sensor.argtypes = [C.c_void_p, C.c_int, C.c_uint64] + [C.c_int] * 5
         f.aof_facade_bank_set_stream_pixel_format.argtypes = [C.c_void_p, C.c_int, C.c_int]
         f.aof_facade_bank_set_stream_binning.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        f.aof_facade_bank_set_stream_warp.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        f.aof_facade_bank_set_stream_lens.argtypes = [C.c_void_p, C.c_int] + [C.c_double] * 9
         f.aof_facade_bank_enable_camera_packed.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32]
         f.aof_facade_bank_push.argtypes = [C.c_void_p] * 5
         f.aof_facade_bank_enable_camera.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32]
@@ -1689,6 +1803,21 @@ class OpticalFlowBank:
         """Stream s's binning (1, 2 or 4) inside the bytes pushCamera() takes, from the next pushCamera() on.  0, or -EINVAL
         (bad index, another bin, before enableCamera(), a footprint that no longer fits the stream's sensor frame)."""
         return facade_lib().aof_facade_bank_set_stream_binning(self._h, int(s), int(bin))
+
+    def setStreamWarp(self, s, mesh=None):
+        """Stream s's warp mesh ([ny, nx] of WARP_POINT_DTYPE for the image size: warp_mesh_size) from the next pushCamera()
+        on; None: the stream's plain crop again.  0, or -EINVAL (bad index, not enabled, an object that bins a stream)."""
+        if mesh is None:
+            return facade_lib().aof_facade_bank_set_stream_warp(self._h, int(s), None)
+        mesh = np.ascontiguousarray(mesh, WARP_POINT_DTYPE)
+        nx, ny = (self.width + 7) // 8 + 1, (self.height + 7) // 8 + 1
+        assert mesh.shape == (ny, nx), (mesh.shape, (ny, nx))
+        return facade_lib().aof_facade_bank_set_stream_warp(self._h, int(s), mesh.ctypes.data)
+
+    def setStreamLens(self, s, fx, fy, cx, cy, k1=0.0, k2=0.0, p1=0.0, p2=0.0, k3=0.0):
+        """Stream s's lens: the sensor camera (plane pixels) and its Brown-Conrady coefficients; the image is that of a
+        pinhole camera of the same focal lengths with the principal point at the image centre.  0, or -EINVAL as setStreamWarp."""
+        return facade_lib().aof_facade_bank_set_stream_lens(self._h, int(s), *(float(v) for v in (fx, fy, cx, cy, k1, k2, p1, p2, k3)))
 
     def pushCamera(self, sensor_frames, img_time_us, active=None, gyro=None):
         """sensor_frames uint8 [S, camera_height, camera_width] (enableCameraPacked(): [S, camera_height, row_bytes], see

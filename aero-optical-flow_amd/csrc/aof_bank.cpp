@@ -1,9 +1,9 @@
 // The stream bank (include/aof.h, "a bank of live streams"): S live streams per tick from one device launch.  Host
 // side only: the layout and ONE push path (bank_push) behind the four push entry points -- pre-cropped or sensor
 // frames, one tick or a burst of K rounds: the argument checks, the path choice and the launches of k_bank.hip /
-// k_bank_burst.hip -- the one-launch kernel, or per round (the ingest kernel,) aof_flow_batch_device's own plan on
-// (bank frames, new frames) and the commit kernel.  An entry point only packs its arguments.  Nothing here allocates
-// or synchronises.
+// k_bank_burst.hip -- the one-launch kernel, or per round (the ingest kernel, or with meshes bound the warp kernel of
+// k_bank_warp.hip,) aof_flow_batch_device's own plan on (bank frames, new frames) and the commit kernel.  An entry point
+// only packs its arguments.  Nothing here allocates or synchronises.
 #include <cerrno>
 #include <cstdint>
 #include <cstring>
@@ -261,6 +261,10 @@ int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank
     BankTablesUsed tables;
     if (const char *what = bank_tables_for_push(bank_tables(ctx), bp->n_streams, p.camera, round_stride, &tables))
         return ctx_fail(ctx, -EINVAL, what);
+    // the meshes, if the push is on sensor frames and some are bound (aof_set_bank_warps)
+    const aof_warp_point *warps = nullptr;
+    if (p.camera)
+        if (const char *what = bank_warps_for_push(bank_warps(ctx), bp->n_streams, tables, &warps)) return ctx_fail(ctx, -EINVAL, what);
     // before the first launch: a faulted or wedged context, or a thread on another device, must not touch the bank
     if ((rc = precheck(ctx))) return rc;
 
@@ -281,7 +285,8 @@ int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank
     // enough for a workgroup per stream to pay, or because the caller asked for it
     const int path = bank_path(ctx);
     SmallArgs sm;
-    const bool fused = path != 2 &&
+    // (with warps bound always the composed path: the one-launch kernels have no warp inside them)
+    const bool fused = path != 2 && !warps &&
                        plan_small_batch(ctx, a.bank_frames, cur, L.stride, bp->n_streams, flows, bank + L.pub.scratch, &sm) &&
                        (path == 1 || bp->n_streams <= kFusedMaxStreams[p.camera][p.burst]);
     if (fused) {
@@ -299,7 +304,18 @@ int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank
         if (p.burst) r = round_args(a, k, p.camera ? staging : src);
         if (p.camera) {
             r.cam.camera = src;
-            if (launch_ingest(p.cam->ingest, src, a.cam.camera_stride, bp->n_streams, staging, L.stride, p.exposure ? hist : nullptr, stream,
+            if (warps) {   // the warped crops (and the plain ones of unwarped streams) in place of the ingest kernel's
+                WarpArgs w = {};
+                w.crop_w = p.cam->ingest.crop_width; w.crop_h = p.cam->ingest.crop_height;
+                w.camera = src;
+                w.recs = tables.sensors; w.base = base; w.camera_bytes = tables.camera_bytes; w.formats = tables.formats;
+                w.camera_stride = a.cam.camera_stride;
+                w.plane_w = p.cam->ingest.camera_width; w.plane_h = p.cam->ingest.camera_height;
+                w.points = warps;
+                w.cropped = staging; w.cropped_stride = L.stride;
+                w.hist = p.exposure ? hist : nullptr;
+                if (launch_warp(w, bp->n_streams, stream)) return ctx_fail(ctx, -EIO, "bank camera warp launch failed");
+            } else if (launch_ingest(p.cam->ingest, src, a.cam.camera_stride, bp->n_streams, staging, L.stride, p.exposure ? hist : nullptr, stream,
                               ingest_sensors_of_round(tables, base)))
                 return ctx_fail(ctx, -EIO, "bank camera ingest launch failed");
         }

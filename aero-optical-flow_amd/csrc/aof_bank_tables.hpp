@@ -98,6 +98,36 @@ inline const char *bank_tables_for_imu(const BankTables &b, int32_t n_streams, c
     return nullptr;
 }
 
+// The warp meshes (aof_set_bank_warps): a record of its own beside the tables -- an array of meshes, [S][ny][nx] nodes
+// of the context's crop, is no per-stream table of fixed records, and a push with it bound takes another path
+// (launch_warp in place of launch_ingest, always composed) where a table only changes a kernel's argument.
+struct BankWarps {
+    const aof_warp_point *points;   // device memory of the caller's, or nullptr: nothing bound
+    int32_t n_streams;
+};
+
+// The binding call: nullptr, or why it is refused -- the binding is then as it was.  A null array unbinds.
+inline const char *bank_warps_bind(BankWarps *w, const aof_warp_point *points, int32_t n_streams)
+{
+    if (points && n_streams < 1) return "bank warps: an array needs n_streams >= 1";
+    if (!aligned(points, 16)) return "bank warps: the array must be 16-byte aligned";
+    w->points = points;
+    w->n_streams = points ? n_streams : 0;
+    return nullptr;
+}
+
+// A camera push of n_streams with the tables `u` it uses: nullptr and the meshes (or nullptr: nothing bound, the push
+// runs as it always did), or why it is refused.
+inline const char *bank_warps_for_push(const BankWarps &w, int32_t n_streams, const BankTablesUsed &u, const aof_warp_point **points)
+{
+    *points = nullptr;
+    if (!w.points) return nullptr;
+    if (w.n_streams != n_streams) return "bank: n_streams differs from the array bound with aof_set_bank_warps";
+    if (u.bins) return "bank: a binning (aof_set_bank_binning) and warps (aof_set_bank_warps) are bound at the same time";
+    *points = w.points;
+    return nullptr;
+}
+
 // The kernels' sensor arguments of one round (base: bytes between the caller's d_camera and the round's first frame;
 // sensors == nullptr: the kernels without the argument).
 inline BankSensors bank_sensors_of_round(const BankTablesUsed &u, uint64_t base)

@@ -164,6 +164,7 @@ bool plan_small_batch(const aof_ctx *ctx, const uint8_t *prev, const uint8_t *cu
 int bank_path(const aof_ctx *ctx) { return ctx->bank_path; }
 void set_bank_path(aof_ctx *ctx, int path) { ctx->bank_path = path; }
 BankTables &bank_tables(aof_ctx *ctx) { return ctx->bank; }
+BankWarps &bank_warps(aof_ctx *ctx) { return ctx->warps; }
 
 // Would a sequence-view call (frames viewed twice, n_pairs = frames - 1) run K1 as a pass of its own?  The sequence
 // pipeline asks, because its ingest kernel can leave K1's outputs (pixel sums at ws + L.sums, one level-1 frame per

@@ -114,6 +114,7 @@ struct aof_ctx {
     char err[256];
     int bank_path;              // aof_set_bank_path: 0 the library chooses, 1 the one-launch tick kernel, 2 the composed path
     aof::BankTables bank;       // aof_set_bank_streams / _sensors / _pixel_formats / _binning: the caller's per-stream arrays (aof_bank_tables.hpp)
+    aof::BankWarps warps;       // aof_set_bank_warps: the caller's meshes (beside the tables, aof_bank_tables.hpp)
     bool graph_disabled;        // per-call graphs switched off, or a capture failed once: stay on the plain path
     bool capturing;             // a per-call graph is being captured (no event timing)
     bool wedged;                // a bounded wait for the device ran out: every later call fails, destroy frees nothing

@@ -427,6 +427,8 @@ int bank_path(const aof_ctx *ctx);            // (aof_batch.cpp) aof_set_bank_pa
 void set_bank_path(aof_ctx *ctx, int path);
 struct BankTables;                            // (aof_bank_tables.hpp) what the four aof_set_bank_* calls have bound
 BankTables &bank_tables(aof_ctx *ctx);        // (aof_batch.cpp) the context's
+struct BankWarps;                             // (aof_bank_tables.hpp) what aof_set_bank_warps has bound
+BankWarps &bank_warps(aof_ctx *ctx);          // (aof_batch.cpp) the context's
 // (aof_capi.hip) sticky fault / wedged state and current-device check of a context, before anything is enqueued; and
 // aof_last_error's text for the callers outside aof_capi.hip
 int precheck(aof_ctx *ctx);
@@ -458,5 +460,26 @@ int launch_ingest(const aof_ingest_params &p, const uint8_t *camera, int64_t cam
 bool ingest_pyramid_supported(const aof_ingest_params &p, const uint8_t *cropped, int64_t cropped_stride);
 int launch_ingest_pyramid(const aof_ingest_params &p, const uint8_t *camera, int64_t camera_stride, int64_t n_frames,
                           uint8_t *cropped, int64_t cropped_stride, uint32_t *hist, uint8_t *l1, uint32_t *sums, void *stream);
+
+// The warp of n_frames crops through their meshes (k_bank_warp.hip; include/aof.h "the stream bank with a lens"): where
+// launch_ingest stands in a camera push with aof_set_bank_warps bound, and behind aof_ingest_warped_device.  Frame i's
+// plane is record i's (recs, formats, base, camera_bytes as IngestSensors), or with recs == nullptr the grey frame of
+// plane_w x plane_h at camera + i * camera_stride (then the crop of an unwarped frame is the centred one).
+struct WarpArgs {
+    int32_t crop_w, crop_h;
+    const uint8_t *camera;
+    const aof_bank_sensor *recs;
+    uint64_t base, camera_bytes;
+    const uint8_t *formats;
+    int64_t camera_stride;
+    int32_t plane_w, plane_h;
+    const aof_warp_point *points;  // [n_frames][ny][nx], 16-byte aligned
+    uint8_t *cropped;              // [n_frames] crops cropped_stride apart, or nullptr
+    int64_t cropped_stride;
+    uint32_t *hist;                // [n_frames][10] raw masked histograms, or nullptr
+    uint8_t *ok;                   // u8 [n_frames] or nullptr
+    int32_t nstrips, strip_rows, vec, nx, ny;   // filled by the launcher
+};
+int launch_warp(const WarpArgs &a, int64_t n_frames, void *stream);   // hipErrorInvalidValue: a crop too wide for a strip's nodes
 
 }  // namespace aof

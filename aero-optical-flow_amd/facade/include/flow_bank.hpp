@@ -18,6 +18,7 @@ struct aof_outbox_entry;   // include/aof.h: stream, MAVLink frame, tick record 
 struct aof_gyro;           // include/aof.h: gyro angles integrated over the interval that ends at a frame
 struct aof_exposure_command;   // include/aof.h: what the auto-exposure controller decided for a stream in a tick
 struct aof_bank_stream;        // include/aof.h: one stream's focal lengths, output rate, time offset and MAVLink identity
+struct aof_warp_point;         // include/aof.h: a node of a stream's warp mesh, a sensor-plane coordinate in 1/32 pixel
 
 class OpticalFlowBank {
 public:
@@ -111,6 +112,20 @@ public:
 	// bin that is none of 1, 2, 4, a footprint that no longer fits, a call before enabling.  An object on which it was never
 	// called binds nothing.
 	int setStreamBinning(int stream, int bin);
+	// One stream's lens (include/aof.h, "the stream bank with a lens"), after either enable call, from the next pushCamera()
+	// on: the stream's image is its sensor plane resampled through a mesh of one node every 8 image pixels -- mesh:
+	// aof_warp_point [ny][nx] of aof_warp_mesh_size() for the image size, sensor-plane coordinates in 1/32 pixel, copied
+	// before the call returns; NULL: the stream is not warped any more (its plain crop).  The plane is the stream's record's
+	// (setStreamSensor(), or the enable call's), which must stay valid as before: that rule alone refuses a frame.
+	// setStreamLens() builds the mesh from the sensor camera (fx, fy, cx, cy in plane pixels) and its Brown-Conrady
+	// coefficients (OpenCV's order), for a virtual pinhole camera of the same focal lengths whose principal point is the
+	// image centre: the image's focal lengths are then fx, fy (setStreamFocalLength() is the caller's, as with binning).
+	// A push with any stream warped takes the composed path of the bank (three launches per tick).  Returns 0, or -EINVAL,
+	// the object unchanged: a bad stream index, a call before enabling, focal lengths that are zero or not finite, an
+	// object that bins a stream (setStreamBinning() was called: the two do not compose; setStreamBinning() refuses the
+	// same way once a stream was warped).  An object on which neither was called binds nothing.
+	int setStreamWarp(int stream, const aof_warp_point *mesh);
+	int setStreamLens(int stream, double fx, double fy, double cx, double cy, double k1, double k2, double p1, double p2, double k3);
 	// The last pushCamera()'s aof_exposure_command [n_streams] in pinned memory (flags 0: the stream's frame
 	// was not due); valid until the next push.  NULL without enableCamera().
 	const aof_exposure_command *exposureCommands() const;

@@ -110,6 +110,15 @@ int aof_facade_bank_set_stream_binning(void *bank, int stream, int bin)
 {
 	return static_cast<OpticalFlowBank *>(bank)->setStreamBinning(stream, bin);
 }
+int aof_facade_bank_set_stream_warp(void *bank, int stream, const void *mesh)
+{
+	return static_cast<OpticalFlowBank *>(bank)->setStreamWarp(stream, static_cast<const aof_warp_point *>(mesh));
+}
+int aof_facade_bank_set_stream_lens(void *bank, int stream, double fx, double fy, double cx, double cy, double k1, double k2, double p1,
+				    double p2, double k3)
+{
+	return static_cast<OpticalFlowBank *>(bank)->setStreamLens(stream, fx, fy, cx, cy, k1, k2, p1, p2, k3);
+}
 int aof_facade_bank_enable_camera_packed(void *bank, int camera_width, int camera_height, int format, int exposure0, int gain0,
 					 uint32_t exposure_interval_us)
 {

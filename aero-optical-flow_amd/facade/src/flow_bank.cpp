@@ -32,7 +32,7 @@ double secondsSince(std::chrono::steady_clock::time_point t0)
 // Every allocation of one object, recorded where it is made: release() frees them all, the newest first.
 struct Allocations {
 	enum Kind { kDevice, kPinned, kOutbox };   // hipMalloc, hipHostMalloc, aof_outbox_alloc_host: each has its own free
-	struct { void *p; Kind kind; } list[28];   // (26 with every form on, 27 inside enableCamera())
+	struct { void *p; Kind kind; } list[30];   // (28 with every form on, 29 inside enableCamera())
 	int n;
 
 	bool get(void **p, size_t bytes, Kind kind)
@@ -89,10 +89,10 @@ struct Staged {
 // A per-stream table: a shadow array the setters write and its copy on the device, with the flags that decide when it
 // is copied and bound (bank_table.hpp).  The four of an object, in the order a tick copies and binds them.
 struct Table : Staged, BankTableFlags {};
-enum { kSensors, kFormats, kBins, kStreams, kTables };
+enum { kSensors, kFormats, kBins, kStreams, kWarps, kTables };
 const char *const kTableCopyFailed[kTables] = {
 	"copy of the per-stream sensor records failed", "copy of the per-stream pixel formats failed",
-	"copy of the per-stream binning failed", "copy of the per-stream records failed"};
+	"copy of the per-stream binning failed", "copy of the per-stream records failed", "copy of the per-stream warp meshes failed"};
 // The one thing the tables differ in: the call of the C ABI that binds the device array (camera_bytes: of the sensor records).
 int bindTable(aof_ctx *ctx, int which, const uint8_t *d, int n_streams, size_t camera_bytes)
 {
@@ -100,6 +100,7 @@ int bindTable(aof_ctx *ctx, int which, const uint8_t *d, int n_streams, size_t c
 	case kSensors: return aof_set_bank_sensors(ctx, reinterpret_cast<const aof_bank_sensor *>(d), n_streams, camera_bytes);
 	case kFormats: return aof_set_bank_pixel_formats(ctx, d, n_streams);
 	case kBins: return aof_set_bank_binning(ctx, d, n_streams);
+	case kWarps: return aof_set_bank_warps(ctx, reinterpret_cast<const aof_warp_point *>(d), n_streams);
 	default: return aof_set_bank_streams(ctx, reinterpret_cast<const aof_bank_stream *>(d), n_streams);
 	}
 }
@@ -150,7 +151,10 @@ struct OpticalFlowBank::Impl {
 	//   kFormats  (enableCameraPacked(), setStreamPixelFormat()): u8 [n_streams]; they travel with the sensor records
 	//             (used implies that the records are)
 	//   kBins     (setStreamBinning()): u8 [n_streams], ones until a call; beside the records as well
+	//   kWarps    (setStreamWarp(), setStreamLens()): aof_warp_point [n_streams][mesh_nodes], allocated by enableCamera();
+	//             every mesh starts unwarped (AOF_WARP_NONE in its first node); bound on its own, never beside kBins
 	Table table[kTables];
+	size_t mesh_nodes;       // nodes of one stream's mesh (aof_warp_mesh_size)
 
 	int fail(int code, const char *what) { return self->fail(code, what); }
 	int failed(int rc) { return rc ? fail(rc, aof_last_error(ctx)) : 0; }   // of a call of the C ABI
@@ -158,6 +162,8 @@ struct OpticalFlowBank::Impl {
 	uint16_t *rxLengths() { return reinterpret_cast<uint16_t *>(bytes.h + off_rx_len); }
 	aof_bank_stream *shadow() { return reinterpret_cast<aof_bank_stream *>(table[kStreams].h); }
 	aof_bank_sensor *sensorRecords() { return reinterpret_cast<aof_bank_sensor *>(table[kSensors].h); }
+	aof_warp_point *mesh(int s) { return reinterpret_cast<aof_warp_point *>(table[kWarps].h) + (size_t)s * mesh_nodes; }
+	static aof_warp_point *meshFor(OpticalFlowBank *self, int s);
 	static aof_bank_stream *record(Impl *m, int s);
 	bool waitIdle();
 	int startOver(const uint8_t *mask, bool imu_too);
@@ -393,6 +399,7 @@ int OpticalFlowBank::setStreamBinning(int s, int bin)
 	Impl *m = _m;
 	if (!m || !m->camera || !m->sensorRecords() || !m->table[kFormats].h || !m->table[kBins].h || s < 0 || s >= n_streams) return -EINVAL;
 	if (bin != 1 && bin != 2 && bin != 4) return refuse(-EINVAL, "setStreamBinning(): the bin is 1, 2 or 4");
+	if (m->table[kWarps].used) return refuse(-EINVAL, "setStreamBinning(): the object warps streams (setStreamWarp()): binning and warp do not compose");
 	// the stream's current record and format, by the kernels' own rule, with the new footprint
 	if (aof_bank_sensor_valid_binned(m->sensorRecords() + s, m->table[kFormats].h[s], (uint8_t)bin, image_width,
 					 image_height, 0, m->sensor.bytes) != 1)
@@ -401,6 +408,42 @@ int OpticalFlowBank::setStreamBinning(int s, int bin)
 	m->table[kBins].touch();
 	m->table[kSensors].rideAlong();   // (the binning is bound next to the records only)
 	return 0;
+}
+
+// Stream s's shadow mesh for a setter, or NULL (refused: not enabled, a bad index, a binning in use); the next
+// pushCamera() copies the array.
+aof_warp_point *OpticalFlowBank::Impl::meshFor(OpticalFlowBank *self, int s)
+{
+	Impl *m = self->_m;
+	if (!m || !m->camera || !m->table[kWarps].h || s < 0 || s >= self->n_streams) return NULL;
+	if (m->table[kBins].used) {
+		self->refuse(-EINVAL, "setStreamWarp(): the object bins streams (setStreamBinning()): binning and warp do not compose");
+		return NULL;
+	}
+	m->table[kWarps].touch();
+	return m->mesh(s);
+}
+
+int OpticalFlowBank::setStreamWarp(int s, const aof_warp_point *mesh)
+{
+	aof_warp_point *dst = Impl::meshFor(this, s);
+	if (!dst) return -EINVAL;
+	if (mesh) std::memcpy(dst, mesh, _m->mesh_nodes * sizeof(aof_warp_point));
+	else dst[0].x = AOF_WARP_NONE;
+	return 0;
+}
+
+int OpticalFlowBank::setStreamLens(int s, double fx, double fy, double cx, double cy, double k1, double k2, double p1, double p2, double k3)
+{
+	if (!_m || !_m->camera) return -EINVAL;
+	aof_params p;
+	if (aof_get_params(_m->ctx, &p)) return -EINVAL;
+	const aof_lens lens = {fx, fy, cx, cy, k1, k2, p1, p2, k3, fx, fy, image_width / 2.0, image_height / 2.0};
+	if (!(fx == fx) || !(fy == fy) || fx == 0.0 || fy == 0.0 || fx - fx != 0.0 || fy - fy != 0.0)
+		return refuse(-EINVAL, "setStreamLens(): the focal lengths must be finite and not zero");
+	aof_warp_point *dst = Impl::meshFor(this, s);
+	if (!dst) return -EINVAL;
+	return aof_warp_mesh_from_lens(&p, &lens, dst);
 }
 
 int OpticalFlowBank::getPyramidLevels() const
@@ -585,7 +628,11 @@ int OpticalFlowBank::Impl::enableSensorFrames(int camera_width, int camera_heigh
 		return self->refuse(-EINVAL, "enableCamera(): the sensor frame cannot hold the image size");
 	const size_t S = m->S;
 	void *bank = NULL;
+	int32_t mesh_nx = 0, mesh_ny = 0;
+	if (aof_warp_mesh_size(&p, &mesh_nx, &mesh_ny)) return fail(-EIO, "the image size has no warp mesh");
+	const size_t mesh_nodes = (size_t)mesh_nx * (size_t)mesh_ny;
 	if (!m->mem.get(&bank, L.total_bytes, Allocations::kDevice) ||
+	    !m->table[kWarps].alloc(m->mem, alignUp(S * mesh_nodes * sizeof(aof_warp_point), 16)) ||
 	    !m->sensor.alloc(m->mem, S * (size_t)camera_height * (size_t)row_bytes) ||
 	    !m->table[kSensors].alloc(m->mem, S * sizeof(aof_bank_sensor)) ||
 	    !m->table[kFormats].alloc(m->mem, alignUp(S, 16)) ||
@@ -611,6 +658,8 @@ int OpticalFlowBank::Impl::enableSensorFrames(int camera_width, int camera_heigh
 		m->table[kFormats].h[s] = (uint8_t)format;
 	}
 	std::memset(m->table[kBins].h, 1, m->table[kBins].bytes);
+	m->mesh_nodes = mesh_nodes;
+	for (size_t s = 0; s < S; s++) m->mesh((int)s)[0].x = AOF_WARP_NONE;   // (no stream is warped before its setter)
 	if (format != AOF_PIXEL_GREY8) {
 		m->table[kSensors].touch();
 		m->table[kFormats].touch();

@@ -816,6 +816,87 @@ int aof_ingest_sensors_binned_device(int32_t crop_width, int32_t crop_height, co
  * -EINVAL: a value that is no format, width < 1, width % G != 0, NULL out (*out is then not written). */
 int aof_bank_pixel_row_bytes(uint8_t format, int32_t width, int64_t *out);
 
+/* ---- the stream bank with a lens: per-stream undistortion (a warp mesh) in place of the plain crop ----
+ * The reference crops the centre "because optical flow assumes narrow field of view" (mainloop.cpp:294) and has nothing
+ * for the lens itself; upstream's OpticalFlowOpenCV takes a camera matrix and distortion coefficients.  Short, cheap
+ * lenses bend the crop's edge by several percent.  A caller may make resampling through a lens model a property of a
+ * stream: a MESH of one node every AOF_WARP_CELL = 8 crop pixels on both axes,
+ *     nx = (width + 7) / 8 + 1,  ny = (height + 7) / 8 + 1   nodes, row-major (aof_warp_mesh_size),
+ * for the context's width x height crop.  Node (cx, cy) is the sensor-plane coordinate of the CENTRE of crop pixel
+ * (8 cx, 8 cy), in 1/32 pixel (AOF_WARP_FRAC_BITS = 5), relative to pixel (0, 0) of the stream's grey plane: the plane of
+ * width x height pixels of the stream's sensor record (with nothing bound: cam->ingest's camera_width x camera_height
+ * frame of the stream).  With xmax = min(width - 1, 32767), ymax likewise, the grey value of crop pixel (x, y) is, all in
+ * 32-bit integers of which none can wrap:
+ *     every node coordinate is first clamped to [0, xmax*32] / [0, ymax*32] (never invalid: the border replicates);
+ *     cx = x >> 3, cy = y >> 3, i = x & 7, j = y & 7;  A, B, C, D the clamped nodes (cx, cy), (cx+1, cy), (cx, cy+1),
+ *     (cx+1, cy+1);  per axis  N = (8-i)(8-j) A + i (8-j) B + (8-i) j C + i j D,  X = (N + 32) >> 6;
+ *     xi = X >> 5, fx = X & 31, x1 = min(xi + 1, xmax); the same for y;
+ *     v = (p(xi,yi)(32-fx)(32-fy) + p(x1,yi) fx (32-fy) + p(xi,y1)(32-fx) fy + p(x1,y1) fx fy + 512) >> 10,
+ * with p the plane's grey value read through the stream's pixel format (the tables above, every AOF_PIXEL_*).  An
+ * identity mesh, node = ((x0 + 8 cx)*32, (y0 + 8 cy)*32), gives the plain crop byte for byte wherever its nodes lie inside
+ * the plane (x0 + 8 (nx - 1) <= width - 1, likewise y: a node beyond the last pixel is clamped, which compresses the last
+ * cell of a crop that ends on the plane's last column or row).  A stream whose FIRST node has x == AOF_WARP_NONE is not
+ * warped: it takes the plain crop of its record, wherever that lies.
+ * Approximation: the mesh is piecewise bilinear.  Between nodes a lens model's curve is replaced by its chord; the error
+ * per axis is at most (8^2 / 8) * |second derivative by the crop pixel|: for k1 = -0.3 at the edge of a 128-pixel crop
+ * of focal length 100 (xn = 0.64), fx * |k1| * 6 xn / out_fx^2 = 0.0115 per pixel^2, so 0.09 pixel, three units of the
+ * 1/32 grid, and a quarter of that at half the radius.  The mesh is exact at its nodes.
+ * A stream's sensor record must be valid by the rule above -- its x0, y0 and the crop size included, whatever the mesh
+ * says: that rule alone decides AOF_TICK_BAD_SENSOR, and of a stream so refused not one byte is read or written.
+ * Contract: with warps bound, every camera push (tick and burst) computes a warped stream's new frame by the rule above;
+ * the exposure histogram and MSV are those of the warped crop; records, wire frames, de-rotated pairs, stored frame and
+ * state equal byte for byte those of a grey stream whose sensor frame is the warped crop computed on the host
+ * (aof_warp_host).  The push then always takes the composed path, whatever aof_set_bank_path says: the warp launch into
+ * the staging region (with the raw histograms), aof_flow_batch_device, the commit kernel; per round of a burst.  With
+ * nothing bound not one launch changes.
+ * Binding: used by the two camera pushes.  A bound count that differs from bp->n_streams, or a binning bound at the same
+ * time (aof_set_bank_binning: the composition of binning and warp is not served; bin the mesh instead, nodes 2 or 4
+ * times as far apart), makes those pushes return -EINVAL before anything is enqueued.  The KERNELS read the array when
+ * they run: nodes may be rewritten between ticks, a captured graph replays against the current contents.
+ * The focal length is the caller's: a warped crop has the focal lengths of the virtual camera (aof_lens.out_fx, out_fy),
+ * which the caller binds through aof_bank_stream.  The library does not touch it. */
+#define AOF_WARP_CELL 8
+#define AOF_WARP_FRAC_BITS 5
+#define AOF_WARP_NONE INT32_MIN
+typedef struct aof_warp_point {      /* 8 bytes: a node, 1/32 sensor pixel */
+    int32_t x, y;
+} aof_warp_point;
+typedef struct aof_lens {            /* Brown-Conrady, OpenCV's order of coefficients */
+    double fx, fy, cx, cy;           /* the sensor camera, in plane pixels */
+    double k1, k2, p1, p2, k3;
+    double out_fx, out_fy, out_cx, out_cy;   /* the virtual pinhole camera of the crop, in crop pixels */
+} aof_lens;
+/* Host only: the mesh of p->width x p->height.  -EINVAL: NULL p / nx / ny, a size below 1. */
+int aof_warp_mesh_size(const aof_params *p, int32_t *nx, int32_t *ny);
+/* Host only: out[ny][nx] = the identity mesh of the crop at (x0, y0).  -EINVAL: NULL, or a coordinate that leaves int32. */
+int aof_warp_mesh_identity(const aof_params *p, int32_t x0, int32_t y0, aof_warp_point *out);
+/* Host only, all in double: for node (u, v) = (8 cx, 8 cy)
+ *     xn = (u - out_cx) / out_fx, yn = (v - out_cy) / out_fy, r2 = xn^2 + yn^2, rad = 1 + r2 (k1 + r2 (k2 + r2 k3)),
+ *     xd = xn rad + 2 p1 xn yn + p2 (r2 + 2 xn^2),  yd = yn rad + p1 (r2 + 2 yn^2) + 2 p2 xn yn,
+ *     x = floor((fx xd + cx) * 32 + 0.5),  y = floor((fy yd + cy) * 32 + 0.5),  saturated to int32 (a NaN: 0); a first
+ * node that would be AOF_WARP_NONE becomes AOF_WARP_NONE + 1.  -EINVAL: NULL, out_fx or out_fy zero or not finite. */
+int aof_warp_mesh_from_lens(const aof_params *p, const aof_lens *lens, aof_warp_point *out);
+/* Stores the pointer on the context, like aof_set_bank_sensors: enqueues nothing, allocates nothing, reads nothing.
+ * d_points: aof_warp_point [n_streams][ny][nx] in device memory owned by the caller, alive for as long as it is bound,
+ * 16-byte aligned.  NULL (with n_streams 0) unbinds.  -EINVAL: NULL ctx, a non-NULL array with n_streams < 1, a
+ * misaligned array (the binding stays as it was). */
+int aof_set_bank_warps(aof_ctx *ctx, const aof_warp_point *d_points, int32_t n_streams);
+/* aof_ingest_sensor_formats_device with frame i resampled through mesh d_points[i] (aof_warp_point [n_frames][ny][nx] of
+ * the crop size, 16-byte aligned): any crop size up to 16 384 pixels wide, 16-byte stores where crop_width % 16 == 0 and
+ * d_cropped, cropped_stride are multiples of 16.  d_ok[i] = 0: frame i's record is not valid; nothing of it is read and
+ * no byte of its crop written (its histogram: untouched, or ten zeros where the crop is higher than 128 rows and the
+ * strips of a frame add to words zeroed in front of them).  -EINVAL as there, and for NULL or misaligned d_points. */
+int aof_ingest_warped_device(int32_t crop_width, int32_t crop_height, const uint8_t *d_camera, uint64_t camera_bytes,
+                             const aof_bank_sensor *d_sensors, const uint8_t *d_formats, const aof_warp_point *d_points,
+                             int64_t n_frames, uint8_t *d_cropped, int64_t cropped_stride, uint32_t *d_hist, uint8_t *d_ok,
+                             void *stream);
+/* Host only, no device and no context: the same for ONE frame in host memory, by the header the kernel compiles.
+ * camera: camera_bytes readable bytes; sensor: the frame's record; points: [ny][nx]; cropped: crop_width * crop_height
+ * bytes or NULL; hist: 10 words or NULL (the masked histogram of the warped crop).  Returns 1, or 0 where the record is
+ * not valid (nothing read, nothing written), or -EINVAL: NULL camera / sensor / points, both outputs NULL, a size below 1. */
+int aof_warp_host(int32_t crop_width, int32_t crop_height, const uint8_t *camera, uint64_t camera_bytes,
+                  const aof_bank_sensor *sensor, uint8_t format, const aof_warp_point *points, uint8_t *cropped, uint32_t *hist);
+
 /* ---- the stream bank's outbox: the published messages of a push as one dense, ordered, host-pollable list ----
  * A push leaves [K][S] records of which most say "nothing to do": the limiter publishes at 15 Hz from 75 Hz cameras, the
  * exposure gate opens at 5 Hz, idle streams get AOF_TICK_IDLE.  aof_bank_collect_device, enqueued behind any of the four

@@ -75,6 +75,13 @@ end in the path, 1 or 2).  Every stream's frame lies in a slot of 2 cam_w cam_h 
     M   formats mixed per stream (s % 8 over GREY8, LUMA16_LO, LUMA16_HI, Y10, Y12, Y14, Y10P, Y12P);
     D   what a caller does without the formats: a device unpack of the whole Y10 buffer (a shift of the 16-bit words and a
         narrowing copy, two launches, 2 + 2 + 2 + 1 bytes moved per sensor pixel) into a grey buffer, then leg G on that.
+With --warp, the camera tick with warp meshes (aof_set_bank_warps) on 640 x 480 grey frames -- the synthetic frame at the
+centre crop and repeated around it, so that a mesh reaching outside the plain crop reads moving texture:
+    P   the composed camera tick (path 2), nothing bound (with AOF_LIB, on a build without the call: the yardstick of P);
+    I   the same with S identity meshes bound (a push with meshes bound always takes the composed path);
+    L   with the mesh of a barrel lens (k1 -0.28, k2 0.07, focal length 0.9 of the crop size);
+    F   the one-launch camera tick (path 1), nothing bound: what a warped bank gives up (also run under AOF_LIB);
+    U   what a caller does without the binding: aof_ingest_warped_device into a grey buffer, then the camera tick on it.
 K1 / K2 are the legs --camera runs under those names (leg_camera); --per-sensor --legs K1,K2 runs them alone, which is how
 two builds of the library are compared in turn in one session.
 Every leg settles for about 0.2 s of untimed ticks, then times at least --ticks ticks and at least --seconds seconds
@@ -90,7 +97,8 @@ between the repeats is the run-to-run spread a difference between legs has to be
     python tools/bench_bank.py --per-stream --streams 64,1024 > profiles/bank_per_stream_ab.txt
     python tools/bench_bank.py --per-sensor --streams 64,1024 > profiles/bank_per_sensor_ab.txt
     python tools/bench_bank.py --binning --repeats 3 > profiles/bank_binning_ab.txt
-    python tools/bench_bank.py --raw-formats --repeats 3 > profiles/bank_raw_formats_ab.txt"""
+    python tools/bench_bank.py --raw-formats --repeats 3 > profiles/bank_raw_formats_ab.txt
+    python tools/bench_bank.py --warp --repeats 3 > profiles/bank_warp_ab.txt"""
 import argparse
 import ctypes as C
 import importlib
@@ -577,6 +585,109 @@ def binning_sweep(a, dev):
                     g, b0, b2, b4, y4, d2, d4 = (m[k + str(path)] for k in ("G", "B0", "B2", "B4", "Y4", "D2", "D4"))
                     line += (f"  B0{path}/G{path} {b0 / g:5.3f}  B2{path}/G{path} {b2 / g:5.3f}  B4{path}/G{path} {b4 / g:5.3f}  Y4{path}/G{path} {y4 / g:5.3f}"
                              f"  B2{path}/D2{path} {b2 / d2:5.3f}  B4{path}/D4{path} {b4 / d4:5.3f}")
+            print(line)
+
+
+WARP_RING = 4          # ticks of 640 x 480 sensor frames resident per size (2 048 streams: 2.5 GB)
+WARP_SENSOR = (640, 480)
+
+
+def tiled_sensor_frames(p, S, inp, dev, cam_w, cam_h, ring):
+    """`ring` ticks of S sensor frames on the device: inp.frames[k] at the crop origin and repeated around it, so that a
+    mesh that reaches outside the plain crop still reads moving texture (noise there would time another search)."""
+    w, h = p.width, p.height
+    x0, y0 = cam_w // 2 - w // 2, cam_h // 2 - h // 2
+    ys = (torch.arange(cam_h, device=dev) - y0) % h
+    xs = (torch.arange(cam_w, device=dev) - x0) % w
+    return [inp.frames[k][:, ys][:, :, xs].contiguous() for k in range(ring)]
+
+
+def leg_warp(p, S, inp, cams, dev, a, leg):
+    """One of P / I / L / F / U of --warp (see warp_sweep's text): the camera tick on 640 x 480 grey frames."""
+    eng = aof.FlowEngine(p, 0)
+    w, h = p.width, p.height
+    cam_w, cam_h = WARP_SENSOR
+    eng.set_bank_path({"P": 2, "I": 2, "L": 2, "F": 1, "U": 0}[leg])
+    bp = aof.bank_params(S, FX, FY, 15, 5_000_000, 1, 100, 0)
+    two_calls = leg == "U"
+    cam = aof.bank_camera_params(w if two_calls else cam_w, h if two_calls else cam_h, w, h, 0, 200_000, DEROTATE, FX, FY)
+    bank = eng.bank_create(bp, dev, camera=cam)
+    x0, y0 = cam_w // 2 - w // 2, cam_h // 2 - h // 2
+    d_points = d_table = grey = None
+    if leg in ("I", "L", "U"):
+        # the lens of a short downward camera: 13 % barrel at the crop's corner, seen by a pinhole camera of the same focal length
+        f = 0.9 * max(w, h)
+        mesh = aof.warp_mesh_identity(p, x0, y0) if leg == "I" else aof.warp_mesh_from_lens(p, f, f, cam_w / 2.0, cam_h / 2.0, k1=-0.28, k2=0.07)
+        d_points = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(mesh, (S,) + mesh.shape)).view(np.uint8).reshape(S, -1)).to(dev)
+    if two_calls:
+        table = aof.bank_sensor_from_camera(p, aof.bank_camera_params(cam_w, cam_h, w, h, 0, 200_000, DEROTATE, FX, FY), n=S)
+        d_table = torch.from_numpy(table.view(np.uint8).reshape(S, 32)).to(dev)
+        grey = torch.empty((S, h, w), dtype=torch.uint8, device=dev)
+    elif d_points is not None:
+        eng.set_bank_warps(d_points, S)
+    recs = torch.empty((S, 48), dtype=torch.uint8, device=dev)
+    expo = torch.empty((S, 48), dtype=torch.uint8, device=dev)
+    derot = torch.empty((S, 2), dtype=torch.float32, device=dev)
+    wire = torch.empty((S, 56), dtype=torch.uint8, device=dev)
+    lens = torch.empty(S, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    fn, ctx, bpp, cp = aof.lib.aof_bank_push_camera_device, eng._ctx, C.byref(bp), C.byref(cam)
+    times = torch.zeros(S, dtype=torch.int64, device=dev)
+    rest = (times.data_ptr(), None, inp.gyro.data_ptr(), bank.buffer.data_ptr(), bank.buffer.numel(), recs.data_ptr(), expo.data_ptr(),
+            derot.data_ptr(), wire.data_ptr(), lens.data_ptr(), stream)
+    ptrs = [c.data_ptr() for c in cams]
+    unwarp = aof.lib.aof_ingest_warped_device if two_calls else None
+
+    def step(i):
+        times.add_(13333)
+        if two_calls:
+            rc = unwarp(w, h, ptrs[i % WARP_RING], S * cam_w * cam_h, d_table.data_ptr(), None, d_points.data_ptr(), S, grey.data_ptr(), w * h,
+                        None, None, stream)
+            rc = rc or fn(ctx, bpp, cp, grey.data_ptr(), *rest)
+        else:
+            rc = fn(ctx, bpp, cp, ptrs[i % WARP_RING], *rest)
+        if rc:
+            raise aof.AofError(rc, aof.lib.aof_last_error(ctx).decode())
+    out = timed(step, torch.cuda.synchronize, a.ticks, a.seconds, a.settle)
+    r = aof.ticks_view(recs)
+    assert (r["quality"] >= aof.TICK_HELD).all() and (r["frame"] > a.ticks).all(), "the timed ticks were real ticks"
+    eng.close()
+    return out
+
+
+def warp_sweep(a, dev):
+    print("# legs, all on 640 x 480 grey sensor frames: P the composed camera tick (path 2), nothing bound; I the same with identity meshes bound; "
+          "L with the mesh of a barrel lens (k1 -0.28, k2 0.07); F the one-launch camera tick (path 1), nothing bound: what a warped bank gives up; "
+          "U aof_ingest_warped_device into a grey buffer, then the camera tick on it (path 0): a separate unwarp launch "
+          "(exposure records, de-rotation, MAVLink frames on, all streams active)")
+    print("# us = microseconds per tick (host clock, ticks ending in a synchronise)")
+    bound = hasattr(aof.lib, "aof_set_bank_warps")      # (AOF_LIB may name a build without the call: P and F only)
+    legs = ["P", "I", "L", "F", "U"] if bound else ["P", "F"]
+    if a.legs is not None:
+        legs = [leg for leg in legs if leg in a.legs.split(",")]
+    sizes = [int(s) for s in a.streams.split(",")]
+    results = {}
+    for rep in range(a.repeats):
+        for cfg in a.configs.split(","):
+            p = params_of(cfg)
+            for S in sizes:
+                inp = Inputs(p, S, dev)
+                cams = tiled_sensor_frames(p, S, inp, dev, *WARP_SENSOR, WARP_RING)
+                for name in legs:
+                    sec, n = leg_warp(p, S, inp, cams, dev, a, name)
+                    results.setdefault((cfg, S, name), []).append(sec)
+                    print(f"rep {rep} {cfg:11s} S={S:6d} {name:2s} {sec * 1e6:10.2f} us  ({n} ticks)", flush=True)
+                del inp, cams
+                torch.cuda.empty_cache()
+    print("# ---- summary (median of the repeats; p10..p90 of the repeats in us) ----")
+    for cfg in a.configs.split(","):
+        for S in sizes:
+            m = {n: float(np.median(results[(cfg, S, n)])) for n in legs}
+            line = f"{cfg:11s} S={S:6d}  " + "  ".join(
+                f"{n} {m[n] * 1e6:9.2f} us ({np.percentile(results[(cfg, S, n)], 10) * 1e6:.2f}..{np.percentile(results[(cfg, S, n)], 90) * 1e6:.2f})"
+                for n in m)
+            if all(n in m for n in ("P", "I", "L", "F", "U")):
+                line += f"  I/P {m['I'] / m['P']:5.3f}  L/P {m['L'] / m['P']:5.3f}  L/F {m['L'] / m['F']:5.3f}  L/U {m['L'] / m['U']:5.3f}"
             print(line)
 
 
@@ -1528,16 +1639,20 @@ def main():
                     "bank paths (G1, ..., D42; --legs G1,G2 runs the yardstick alone, for a build without the call through AOF_LIB)")
     ap.add_argument("--raw-formats", action="store_true", help="the camera tick with raw mono pixels: legs G, R, P, M, D on both bank "
                     "paths (G1, ..., D2; --legs G1,G2 runs the yardstick alone, for a build without the formats through AOF_LIB)")
+    ap.add_argument("--warp", action="store_true", help="the camera tick with warp meshes bound: legs P, I, L, F, U on 640 x 480 frames (--legs P,F "
+                    "runs the legs that need no mesh alone, for a build without the call through AOF_LIB)")
     ap.add_argument("--forms", default="plain,camera", help="--burst: entry points to sweep")
     ap.add_argument("--input-bytes-max", type=float, default=24 * 2**30, help="--burst: sizes whose K rounds of input exceed this are skipped")
     a = ap.parse_args()
-    if a.legs is None and not a.per_sensor and not a.pixel_formats and not a.binning and not a.raw_formats:
+    if a.legs is None and not a.per_sensor and not a.pixel_formats and not a.binning and not a.raw_formats and not a.warp:
         a.legs = "T0,T1,T2,C,B"
     if a.burst and a.ticks == ap.get_default("ticks"):
         a.ticks = 1000           # (frame rounds)
     if a.camera and a.streams == ap.get_default("streams"):
         a.streams = "1,64,1024,1536,2048,4096"
     if (a.pixel_formats or a.binning or a.raw_formats) and a.streams == ap.get_default("streams"):
+        a.streams = "64,256,1024,2048"
+    if a.warp and a.streams == ap.get_default("streams"):
         a.streams = "64,256,1024,2048"
     if a.exposure_control and a.streams == ap.get_default("streams"):
         a.streams = "64,1024,4096"
@@ -1562,6 +1677,8 @@ def main():
         return binning_sweep(a, dev)
     if a.raw_formats:
         return raw_formats_sweep(a, dev)
+    if a.warp:
+        return warp_sweep(a, dev)
     if a.mavlink_rx:
         return mavlink_rx_sweep(a, dev)
     if a.imu:
