@@ -294,6 +294,7 @@ def _load():
         "aof_bank_reset_device": (C.c_int, [VP, P(BankParams), VP, VP, C.c_size_t, VP]),
         "aof_bank_push_device": (C.c_int, [VP, P(BankParams), VP, VP, VP, VP, VP, C.c_size_t, VP, VP, VP, VP]),
         "aof_set_bank_path": (C.c_int, [VP, C.c_int]),
+        "aof_bank_last_path": (C.c_int, [VP]),
         "aof_bank_stream_from_params": (C.c_int, [P(BankParams), P(BankStream)]),
         "aof_set_bank_streams": (C.c_int, [VP, VP, C.c_int32]),
         "aof_set_bank_sensors": (C.c_int, [VP, VP, C.c_int32, C.c_uint64]),
@@ -314,6 +315,8 @@ def _load():
         "aof_warp_mesh_identity": (C.c_int, [P(Params), C.c_int32, C.c_int32, VP]),
         "aof_warp_mesh_from_lens": (C.c_int, [P(Params), P(Lens), VP]),
         "aof_set_bank_warps": (C.c_int, [VP, VP, C.c_int32]),
+        "aof_bank_warp_one_launch": (C.c_int, [P(Params), P(C.c_int64)]),
+        "aof_bank_warp_crossover": (C.c_int, []),
         "aof_ingest_warped_device": (C.c_int, [C.c_int32, C.c_int32, VP, C.c_uint64, VP, VP, VP, I64, VP, I64, VP, VP, VP]),
         "aof_warp_host": (C.c_int, [C.c_int32, C.c_int32, VP, C.c_uint64, P(BankSensor), C.c_uint8, VP, VP, VP]),
         "aof_bank_camera_layout": (C.c_int, [P(Params), P(BankParams), P(BankCamera), P(BankLayout), P(C.c_size_t)]),
@@ -623,6 +626,22 @@ def warp_mesh_from_lens(p: Params, fx, fy, cx, cy, k1=0.0, k2=0.0, p1=0.0, p2=0.
     if rc:
         raise AofError(rc, lib.aof_strerror(rc).decode())
     return out
+
+
+def bank_warp_one_launch(p: Params):
+    """aof_bank_warp_one_launch: (ok, lds_bytes) -- can a camera push of configuration p with warps bound run as one launch
+    per round, and the dynamic LDS a workgroup of it would ask for (the one-workgroup plan's bytes plus 8 nx ny)."""
+    lds = C.c_int64(0)
+    rc = lib.aof_bank_warp_one_launch(C.byref(p), C.byref(lds))
+    if rc < 0:
+        raise AofError(rc, lib.aof_strerror(rc).decode())
+    return bool(rc), int(lds.value)
+
+
+def bank_warp_crossover() -> int:
+    """aof_bank_warp_crossover: the largest n_streams at which set_bank_path(0) takes the one-launch kernel with warps
+    bound (0: never; path 1 still does)."""
+    return int(lib.aof_bank_warp_crossover())
 
 
 def warp_host(camera, rec, crop_w, crop_h, mesh, format=0, camera_bytes=None):
@@ -1448,8 +1467,9 @@ class FlowEngine:
         """aof_set_bank_warps: binds a uint8 CUDA tensor of S meshes (S * ny * nx nodes of WARP_POINT_DTYPE, 16-byte
         aligned; warp_mesh_size) to the context, or with None unbinds.  n_streams: S, where the tensor holds more.  While it
         is bound every camera push of S streams resamples stream s's crop through mesh s (a first node with x == WARP_NONE:
-        the plain crop) and takes the composed path.  The kernels read it when they run: keep it alive; it may be rewritten
-        between ticks."""
+        the plain crop); set_bank_path applies as ever -- the one-launch form is the tick kernel with the warp inside it
+        (bank_warp_one_launch says whether the configuration has one; last_bank_path says what a push took).  The kernels
+        read it when they run: keep it alive; it may be rewritten between ticks."""
         nx, ny = warp_mesh_size(self.params)
         self._bind_bank_table(lib.aof_set_bank_warps, "_bank_warps", points, n_streams, nx * ny * 8)
 
@@ -1465,6 +1485,14 @@ class FlowEngine:
         """0: the library chooses between the one-launch tick kernel and the composed path, 1: the tick kernel where
         the configuration allows it, 2: always the composed path.  Same bytes either way."""
         self._check(lib.aof_set_bank_path(self._ctx, int(path)))
+
+    def last_bank_path(self) -> int:
+        """aof_bank_last_path: 0 no push yet, 1 the most recent accepted push ran one-launch kernel(s), 2 the composed
+        launches.  A refused push leaves it as it was."""
+        rc = lib.aof_bank_last_path(self._ctx)
+        if rc < 0:
+            raise AofError(rc, lib.aof_strerror(rc).decode())
+        return int(rc)
 
     # -- host buffers -----------------------------------------------------------
     def flow_pair_host(self, prev: np.ndarray, cur: np.ndarray):
@@ -1604,6 +1632,7 @@ def facade_lib():
         f.aof_facade_bank_published.argtypes = [C.c_void_p]
         f.aof_facade_bank_reset.argtypes = [C.c_void_p, C.c_void_p]
         f.aof_facade_bank_pyramid_levels.argtypes = [C.c_void_p]
+        f.aof_facade_bank_last_push_path.argtypes = [C.c_void_p]
         f.aof_facade_bank_ok.argtypes = [C.c_void_p]
         f.aof_facade_bank_last_error.restype = C.c_char_p
         f.aof_facade_bank_last_error.argtypes = [C.c_void_p]
@@ -1745,6 +1774,10 @@ class OpticalFlowBank:
 
     def getPyramidLevels(self):
         return facade_lib().aof_facade_bank_pyramid_levels(self._h)
+
+    def lastPushPath(self):
+        """How the engine ran the last accepted push: 0 none yet, 1 one launch per tick, 2 the composed launches."""
+        return facade_lib().aof_facade_bank_last_push_path(self._h)
 
     def engineOk(self):
         return bool(facade_lib().aof_facade_bank_ok(self._h))

@@ -1,9 +1,10 @@
 // The stream bank (include/aof.h, "a bank of live streams"): S live streams per tick from one device launch.  Host
 // side only: the layout and ONE push path (bank_push) behind the four push entry points -- pre-cropped or sensor
 // frames, one tick or a burst of K rounds: the argument checks, the path choice and the launches of k_bank.hip /
-// k_bank_burst.hip -- the one-launch kernel, or per round (the ingest kernel, or with meshes bound the warp kernel of
-// k_bank_warp.hip,) aof_flow_batch_device's own plan on (bank frames, new frames) and the commit kernel.  An entry point
-// only packs its arguments.  Nothing here allocates or synchronises.
+// k_bank_burst.hip -- the one-launch kernel (with meshes bound: the tick with the warp inside it, k_bank_tick_warp.hip,
+// once per round), or per round (the ingest kernel, or with meshes bound the warp kernel of k_bank_warp.hip,)
+// aof_flow_batch_device's own plan on (bank frames, new frames) and the commit kernel.  An entry point only packs its
+// arguments.  Nothing here allocates or synchronises.
 #include <cerrno>
 #include <cstdint>
 #include <cstring>
@@ -11,12 +12,21 @@
 #include "aof_bank_sensor_rule.hpp"
 #include "aof_bank_tables.hpp"
 #include "aof_internal.hpp"
+#include "aof_small_plan.hpp"
+#include "aof_warp_step.hpp"
 
 using namespace aof;
 
 namespace {
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// Can the tick with the warp inside it serve the plan `sm`: the plan's verdict, and frames + the mesh's nodes + the
+// kernels' static arrays inside kSmallLdsLimit (small_warp_plan_make, next to small_plan_make in aof_small_plan.hpp).
+SmallWarpPlan warp_one_launch_fits(const SmallArgs &sm)
+{
+    return small_warp_plan_make(sm, (int64_t)warp_nodes(sm.l0.w > 0 ? sm.l0.w : 1) * warp_nodes(sm.l0.h > 0 ? sm.l0.h : 1));
+}
 
 // Largest bank the one-launch tick kernel serves under aof_set_bank_path(ctx, 0).  Measured (tools/bench_bank.py,
 // profiles/bank_tick_sweep.txt; us per tick, one-launch kernel / composed path): PX4 64x64 1 024 streams 13.0 / 17.2,
@@ -51,6 +61,18 @@ constexpr int32_t kBankBurstFusedMaxStreams = 1024;
 // 503.6 / 471.5.)  The small frames cross between 1 536 and 2 048 streams at every K; the two-level configuration
 // gives up 9 % at 2 048 for it.
 constexpr int32_t kBankCameraBurstFusedMaxStreams = 1536;
+// The same for a camera push with meshes bound (aof_set_bank_warps), tick or burst: the one-launch form is the tick with
+// the warp inside it (k_bank_tick_warp.hip; a burst of K rounds is K launches of it on either path, so the tick's crossover
+// is the burst's), the composed form three launches per round.  Measured (tools/bench_bank.py --warp, 640x480 frames, a
+// barrel lens; profiles/bank_warp_one_launch_ab.txt; us per tick, leg W: this kernel / leg L of the build before it, the
+// composed path, loaded in the same session: median (p10)): PX4 64x64 64 streams 17.1 / 23.8 (23.7), 256: 17.3 / 30.4
+// (30.2), 1 024: 30.4 / 43.7 (43.7), 2 048: 56.2 / 60.0 (59.7), 4 096: 89.2 / 95.2 (95.1); 128x128 on two levels 64: 33.8 /
+// 46.2 (46.2), 256: 34.9 / 73.2 (73.0), 1 024: 81.0 / 96.6 (96.4), 2 048: 135.8 / 137.2 (137.1), 4 096: 262.6 / 236.9
+// (236.9).  2 048 is the largest swept size at which W is below the p10 of L in both configurations -- by 0.9 % on the
+// two-level one, where identity meshes (WI 147.0) already lose 7 %: the gather's cost follows the mesh a little, the
+// composed path's does not.  Bursts of K = 5 (WB1 / WB2 of this build) cross at the same place: 681.2 / 682.0 at 2 048,
+// 1 308.7 / 1 178.6 at 4 096.
+constexpr int32_t kBankWarpFusedMaxStreams = 2048;
 // The four by form: [sensor frames][burst].
 constexpr int32_t kFusedMaxStreams[2][2] = {{kBankFusedMaxStreams, kBankBurstFusedMaxStreams},
                                             {kBankCameraFusedMaxStreams, kBankCameraBurstFusedMaxStreams}};
@@ -282,16 +304,32 @@ int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank
     const BankBurst b = {p.burst ? p.rounds->n_rounds : 1, round_stride, p.burst ? p.select : nullptr};
 
     // which path: the one-launch kernel where the configuration (and these buffers) allow it and the bank is small
-    // enough for a workgroup per stream to pay, or because the caller asked for it
+    // enough for a workgroup per stream to pay, or because the caller asked for it.  With warps bound the one-launch
+    // kernel is the tick with the warp inside it, which also needs the mesh's nodes in LDS (warp_one_launch_fits)
     const int path = bank_path(ctx);
     SmallArgs sm;
-    // (with warps bound always the composed path: the one-launch kernels have no warp inside them)
-    const bool fused = path != 2 && !warps &&
+    const bool fused = path != 2 &&
                        plan_small_batch(ctx, a.bank_frames, cur, L.stride, bp->n_streams, flows, bank + L.pub.scratch, &sm) &&
-                       (path == 1 || bp->n_streams <= kFusedMaxStreams[p.camera][p.burst]);
+                       (!warps || warp_one_launch_fits(sm).ok) &&
+                       (path == 1 || bp->n_streams <= (warps ? kBankWarpFusedMaxStreams : kFusedMaxStreams[p.camera][p.burst]));
+    if (fused && warps) {
+        // a round is one launch; the staging region is neither read nor written
+        for (int k = 0; k < b.n_rounds; k++) {
+            const uint64_t base = (uint64_t)k * (uint64_t)round_stride;
+            BankArgs r = a;   // (a tick keeps its `active` mask: round_args drops it for the burst's `count`)
+            if (p.burst) r = round_args(a, k, staging);
+            r.cam.camera = p.src + (int64_t)k * round_stride;
+            if (launch_bank_tick_warped(sm, r, bank_sensors_of_round(tables, base), warps, p.cam->ingest.camera_height, stream, b.count,
+                                        b.count ? k : 0))
+                return ctx_fail(ctx, -EIO, "bank warped tick launch failed");
+        }
+        bank_last_path(ctx) = 1;
+        return 0;
+    }
     if (fused) {
         if (p.burst ? launch_bank_burst(sm, a, b, stream, sen) : launch_bank_tick(sm, a, stream, sen))
             return ctx_fail(ctx, -EIO, p.burst ? "bank burst launch failed" : "bank tick launch failed");
+        bank_last_path(ctx) = 1;
         return 0;
     }
     // composed, per round and in order on the one stream: (camera forms) the crops and raw histograms of all S sensor
@@ -324,6 +362,7 @@ int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank
         if (rc) return rc;
         if (launch_bank_commit(r, stream, b.count, b.count ? k : 0, bank_sensors_of_round(tables, base))) return ctx_fail(ctx, -EIO, "bank commit launch failed");
     }
+    bank_last_path(ctx) = 2;
     return 0;
 }
 
@@ -355,6 +394,24 @@ int aof_set_bank_path(aof_ctx *ctx, int path)
     set_bank_path(ctx, path);
     return 0;
 }
+
+int aof_bank_last_path(const aof_ctx *ctx)
+{
+    if (!ctx) return -EINVAL;
+    return bank_last_path(const_cast<aof_ctx *>(ctx));
+}
+
+int aof_bank_warp_one_launch(const aof_params *p, int64_t *lds_bytes)
+{
+    if (!p) return -EINVAL;
+    SmallArgs sm;
+    const bool small = plan_small_params(p, &sm);
+    const SmallWarpPlan plan = warp_one_launch_fits(sm);
+    if (lds_bytes) *lds_bytes = (int64_t)plan.lds;
+    return small && plan.ok ? 1 : 0;
+}
+
+int aof_bank_warp_crossover(void) { return kBankWarpFusedMaxStreams; }
 
 int aof_bank_stream_from_params(const aof_bank_params *bp, aof_bank_stream *out)
 {

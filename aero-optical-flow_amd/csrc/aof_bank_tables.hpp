@@ -100,7 +100,8 @@ inline const char *bank_tables_for_imu(const BankTables &b, int32_t n_streams, c
 
 // The warp meshes (aof_set_bank_warps): a record of its own beside the tables -- an array of meshes, [S][ny][nx] nodes
 // of the context's crop, is no per-stream table of fixed records, and a push with it bound takes another path
-// (launch_warp in place of launch_ingest, always composed) where a table only changes a kernel's argument.
+// (the tick with the warp inside it, or launch_warp in place of launch_ingest on the composed path) where a table only
+// changes a kernel's argument.
 struct BankWarps {
     const aof_warp_point *points;   // device memory of the caller's, or nullptr: nothing bound
     int32_t n_streams;

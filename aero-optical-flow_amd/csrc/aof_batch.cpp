@@ -161,7 +161,27 @@ bool plan_small_batch(const aof_ctx *ctx, const uint8_t *prev, const uint8_t *cu
     return P.small_class;
 }
 
+bool plan_small_params(const aof_params *p, SmallArgs *sm)
+{
+    aof_ws_layout L;
+    *sm = SmallArgs{};
+    if (aof_params_check(p) || aof_workspace_layout(p, 1, &L)) return false;
+    BatchConfig cfg = {};
+    cfg.params = *p;
+    cfg.cus = 256;
+    cfg.search_mode = AOF_SEARCH_ADAPTIVE;
+    grid_for_level(*p, 0, &cfg.g0);
+    if (p->pyramid_levels == 2) grid_for_level(*p, 1, &cfg.g1);
+    // (never dereferenced: the plan looks at alignments and at which outputs exist)
+    uint8_t *at = reinterpret_cast<uint8_t *>(uintptr_t(256));
+    const BatchView v = batch_view(cfg, L, at, at, (int64_t)p->width * p->height, nullptr, nullptr, reinterpret_cast<aof_flow *>(at), at);
+    const BatchPlan P = plan_batch(cfg, v, 1, false);
+    *sm = P.sm;
+    return P.small_class;
+}
+
 int bank_path(const aof_ctx *ctx) { return ctx->bank_path; }
+int &bank_last_path(aof_ctx *ctx) { return ctx->bank_last_path; }
 void set_bank_path(aof_ctx *ctx, int path) { ctx->bank_path = path; }
 BankTables &bank_tables(aof_ctx *ctx) { return ctx->bank; }
 BankWarps &bank_warps(aof_ctx *ctx) { return ctx->warps; }

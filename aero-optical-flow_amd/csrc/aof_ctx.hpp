@@ -113,6 +113,7 @@ struct aof_ctx {
     int device;
     char err[256];
     int bank_path;              // aof_set_bank_path: 0 the library chooses, 1 the one-launch tick kernel, 2 the composed path
+    int bank_last_path;         // aof_bank_last_path: 0 no push yet, 1 the last accepted push ran one-launch kernel(s), 2 the composed launches
     aof::BankTables bank;       // aof_set_bank_streams / _sensors / _pixel_formats / _binning: the caller's per-stream arrays (aof_bank_tables.hpp)
     aof::BankWarps warps;       // aof_set_bank_warps: the caller's meshes (beside the tables, aof_bank_tables.hpp)
     bool graph_disabled;        // per-call graphs switched off, or a capture failed once: stay on the plain path

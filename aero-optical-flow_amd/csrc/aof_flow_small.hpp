@@ -191,10 +191,16 @@ __device__ __forceinline__ void run_level(const SearchArgs &a, const FlowTail &t
 // a sensor argument), every other one fetches grey, unbinned rows.
 // `search` false: only the fetch (passes A and B) -- the buffers named by `load` then hold their frame, its level-1
 // image and its sums for a later call that names them as the older frame (a stream's first frame inside a burst).
-template <bool SUBPIXEL, bool PITCHED = false, bool PACKED = false>
+// FILLED (the tick with the warp inside it, k_bank_tick_warp.hip): bit b of `filled` (uniform) says that the caller has
+// written buffer b's level-0 frame into LDS itself, in front of this call -- pass A does not fetch it, and bit b of `load`
+// then means only "make its sums and its level-1 image"; `filled_sum` is the lane's share of the byte sum of what it wrote
+// (one filled buffer at most).  The first barrier below stands between the caller's stores and every read of them.
+// Without FILLED the two arguments are not looked at and the function is the one it was, instruction for instruction.
+template <bool SUBPIXEL, bool PITCHED = false, bool PACKED = false, bool FILLED = false>
 __device__ __forceinline__ void flow_small_pair(const SmallArgs &a, uint32_t pair, const uint8_t *src0, const uint8_t *src1,
                                                 int cur_buf, uint32_t load, aof_flow *final_copy = nullptr,
-                                                const CropSource &crop = crop_grey(0), uint32_t pitched = 2u, bool search = true)
+                                                const CropSource &crop = crop_grey(0), uint32_t pitched = 2u, bool search = true,
+                                                uint32_t filled = 0u, uint32_t filled_sum = 0u)
 {
     const int pitch = crop.pitch, gb = crop.gb, shift = crop.shift, bin = crop.bin;
     extern __shared__ __attribute__((aligned(16))) uint8_t s_mem[];
@@ -218,7 +224,13 @@ __device__ __forceinline__ void flow_small_pair(const SmallArgs &a, uint32_t pai
     {
         const int per_frame = frame0 / 16;
         uint32_t sum[2] = {0, 0};
-        uint32_t rest = load;   // the buffers the loop of 16-byte pieces below fetches: all, but for windows of packed pixels
+        uint32_t fetch = load;   // the buffers pass A fetches: all that are loaded, but for those the caller has filled
+        if constexpr (FILLED) {
+            fetch = load & ~filled;
+            sum[0] = (filled & 1u) ? filled_sum : 0u;
+            sum[1] = (filled & 2u) ? filled_sum : 0u;
+        }
+        uint32_t rest = fetch;   // the buffers the loop of 16-byte pieces below fetches: all, but for windows of packed pixels
         if constexpr (PITCHED && PACKED) {
             // crop_fetch's three answers (aof_crop.hpp), spelled out: asked through the function, or through crop_piece in
             // the loop below, the four sensor kernels of the tick and the burst come out as other code (LAB_LOG.md)
@@ -229,7 +241,7 @@ __device__ __forceinline__ void flow_small_pair(const SmallArgs &a, uint32_t pai
                 const int row_chunks = w / 16;
 #pragma unroll
                 for (int buf = 0; buf < 2; buf++) {
-                    if (!(((load & pitched) >> buf) & 1u)) continue;
+                    if (!(((fetch & pitched) >> buf) & 1u)) continue;
                     const uint8_t *src = buf ? src1 : src0;
 #pragma unroll 1
                     for (int c = tid; c < per_frame; c += kThreads) {
@@ -244,14 +256,14 @@ __device__ __forceinline__ void flow_small_pair(const SmallArgs &a, uint32_t pai
                         *reinterpret_cast<uint4 *>(f0[buf] + c * 16) = v;
                     }
                 }
-                rest = load & ~pitched;
+                rest = fetch & ~pitched;
             } else if (gb != 1) {   // (uniform) two source bytes per pixel: the windows come first, in trips of half as many
                               // pieces -- as many 16-byte loads in flight as below, not twice the registers
                 constexpr int kHalf = kLoads / 2;
                 const int row_chunks = w / 16;
 #pragma unroll
                 for (int buf = 0; buf < 2; buf++) {
-                    if (!(((load & pitched) >> buf) & 1u)) continue;
+                    if (!(((fetch & pitched) >> buf) & 1u)) continue;
                     const uint8_t *src = buf ? src1 : src0;
                     for (int base = 0; base < per_frame; base += kHalf * kThreads) {
                         uint4 v[kHalf];
@@ -276,7 +288,7 @@ __device__ __forceinline__ void flow_small_pair(const SmallArgs &a, uint32_t pai
                         }
                     }
                 }
-                rest = load & ~pitched;
+                rest = fetch & ~pitched;
             }
         }
         const int first_a = (rest & 1u) ? 0 : 1, count_a = (rest == 3u) ? 2 : (rest ? 1 : 0);   // (first, count of `rest`)

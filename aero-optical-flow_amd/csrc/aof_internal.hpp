@@ -423,7 +423,11 @@ int launch_bank_mavlink_rx_reset(aof_mavlink_rx_state *state, const uint8_t *mas
 // context's configuration and these buffers (flows: [n]; d_workspace: aof_workspace_layout(p, n))
 bool plan_small_batch(const aof_ctx *ctx, const uint8_t *prev, const uint8_t *cur, int64_t stride, int64_t n, aof_flow *flows,
                       void *d_workspace, SmallArgs *sm);
+// (aof_batch.cpp) the small-pair plan of a configuration alone (no context, no buffers: pointers that are only looked at
+// for their alignment): true where one workgroup per pair can serve `p`
+bool plan_small_params(const aof_params *p, SmallArgs *sm);
 int bank_path(const aof_ctx *ctx);            // (aof_batch.cpp) aof_set_bank_path's value
+int &bank_last_path(aof_ctx *ctx);            // (aof_batch.cpp) aof_bank_last_path's value: 0 no push yet, 1 one-launch kernel(s), 2 composed
 void set_bank_path(aof_ctx *ctx, int path);
 struct BankTables;                            // (aof_bank_tables.hpp) what the four aof_set_bank_* calls have bound
 BankTables &bank_tables(aof_ctx *ctx);        // (aof_batch.cpp) the context's
@@ -481,5 +485,11 @@ struct WarpArgs {
     int32_t nstrips, strip_rows, vec, nx, ny;   // filled by the launcher
 };
 int launch_warp(const WarpArgs &a, int64_t n_frames, void *stream);   // hipErrorInvalidValue: a crop too wide for a strip's nodes
+// The one-launch tick with the warp inside it (k_bank_tick_warp.hip): launch_bank_tick's camera form with stream s's mesh
+// (points: [S][ny][nx]) in front of the new frame; sen.recs may be nullptr (the plane is then the call's grey frame of
+// cam.pitch x plane_h), sen.bins must be.  (count, round): launch_bank_commit's -- a burst's round k is one launch with
+// round_args' pointers.  Needs small_warp_plan_make(sm, nodes).ok (aof_small_plan.hpp); the staging region is not touched.
+int launch_bank_tick_warped(const SmallArgs &sm, const BankArgs &a, const BankSensors &sen, const aof_warp_point *points, int32_t plane_h,
+                            void *stream, const uint8_t *count = nullptr, int32_t round = 0);
 
 }  // namespace aof

@@ -110,6 +110,29 @@ inline SmallPlan small_plan_make(const SmallArgs &a)
     return p;
 }
 
+// The tick with the warp inside it (k_bank_tick_warp.hip): the plan's workgroup plus the stream's clamped mesh, `nodes`
+// (warp_nodes of the width times warp_nodes of the height, aof_warp_step.hpp: the callers' header) nodes of 8 bytes behind
+// the plan's dynamic LDS (648 B at 64 x 64, 2 312 B at 128 x 128; the plan's bytes are a multiple of 16, so the nodes
+// start on one).  ok: the plan's verdict is SMALL_OK and frames + nodes + the kernels' static arrays fit LDS; the rest is
+// filled whatever it says.
+struct SmallWarpPlan {
+    bool ok;
+    size_t nodes_at;               // byte offset of the nodes in the dynamic LDS
+    size_t lds;                    // dynamic LDS bytes of a workgroup: the plan's and the nodes
+    int32_t attr;                  // the launcher raises the instantiation's dynamic-LDS limit first
+};
+
+inline SmallWarpPlan small_warp_plan_make(const SmallArgs &a, int64_t nodes)
+{
+    const SmallPlan p = small_plan_make(a);
+    SmallWarpPlan q = {};
+    q.nodes_at = p.lds;
+    q.lds = p.lds + (size_t)(nodes > 0 ? nodes : 0) * sizeof(aof_warp_point);
+    q.attr = q.lds > kSmallAttrAbove ? 1 : 0;
+    q.ok = p.verdict == SMALL_OK && q.lds + kSmallStaticLds <= kSmallLdsLimit;
+    return q;
+}
+
 // ---- the grouped lane-per-block search (k_flow_lane8): a workgroup owns ppw whole pairs ----
 
 // The lane-per-block kernels serve B = 8, S = 4 on any grid, within their 24-bit multiplies and 32-bit offsets.

@@ -9,12 +9,13 @@
 // per pixel -- and stores them as one 16-byte value; crops whose width is no multiple of 16 (or whose destination is
 // not aligned) take a lane per pixel.  A gather, not a copy: a pixel is four taps at a place only the mesh knows.  Grey
 // planes fetch a tap's horizontal pair as ONE 2-byte load (any alignment), every other format a byte at a time through
-// warp_pixel; what that costs, and what wider fetches were not tried, is in LAB_LOG.md ("Stream bank warp").
+// warp_pixel (sample, aof_warp_gather.hpp: shared with the one-launch tick that has the warp inside it); what that costs,
+// and what wider fetches were not tried, is in LAB_LOG.md ("Stream bank warp").
 // The histogram is exposure_bin's: a lane counts in 12-bit fields of two 64-bit registers (bank_histogram's layout), the
 // waves add theirs to the workgroup's ten words, and a workgroup that owns its frame stores them; several strips add
 // with integer atomics to words the launcher zeroed.
 #include "aof_bank_stream.hpp"   // (bank_sensor, kThreads)
-#include "aof_warp_step.hpp"
+#include "aof_warp_gather.hpp"   // (aof_warp_step.hpp; sample)
 
 namespace aof {
 
@@ -43,30 +44,6 @@ __device__ __forceinline__ void flush_bins(uint32_t *s_hist, LaneBins &n)
         if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_hist[b], c);
     }
     n.lo = n.hi = 0;
-}
-
-// warp_sample for a grey plane (gb 1): the same four taps, a row's two in one 2-byte load where they are two pixels
-// (xi < xmax; at xi == xmax the rule's second tap IS the first).
-__device__ __forceinline__ uint32_t sample_grey(const WarpPlane &pl, int32_t X, int32_t Y)
-{
-    const int32_t xi = X >> AOF_WARP_FRAC_BITS, fx = X & (kWarpOne - 1);
-    const int32_t yi = Y >> AOF_WARP_FRAC_BITS, fy = Y & (kWarpOne - 1), y1 = yi + 1 < pl.ymax ? yi + 1 : pl.ymax;
-    const uint8_t *r0 = pl.base + (int64_t)yi * pl.pitch + xi, *r1 = pl.base + (int64_t)y1 * pl.pitch + xi;
-    uint32_t a, b;
-    if (xi < pl.xmax) {
-        uint16_t t0, t1;
-        __builtin_memcpy(&t0, r0, 2);
-        __builtin_memcpy(&t1, r1, 2);
-        a = t0; b = t1;
-    } else {
-        a = r0[0] * 0x101u; b = r1[0] * 0x101u;
-    }
-    return warp_blend(a & 0xFFu, a >> 8, b & 0xFFu, b >> 8, fx, fy);
-}
-
-__device__ __forceinline__ uint32_t sample(const WarpPlane &pl, int32_t X, int32_t Y)
-{
-    return pl.gb == 1 ? sample_grey(pl, X, Y) : warp_sample(pl, X, Y);   // (gb is uniform)
 }
 
 __global__ __launch_bounds__(kThreads) void k_bank_warp(WarpArgs a)

@@ -120,7 +120,8 @@ public:
 	// setStreamLens() builds the mesh from the sensor camera (fx, fy, cx, cy in plane pixels) and its Brown-Conrady
 	// coefficients (OpenCV's order), for a virtual pinhole camera of the same focal lengths whose principal point is the
 	// image centre: the image's focal lengths are then fx, fy (setStreamFocalLength() is the caller's, as with binning).
-	// A push with any stream warped takes the composed path of the bank (three launches per tick).  Returns 0, or -EINVAL,
+	// A push with any stream warped still takes the one-launch tick where the library chooses it (the tick kernel with the
+	// warp inside it; lastPushPath() says what the last push took).  Returns 0, or -EINVAL,
 	// the object unchanged: a bad stream index, a call before enabling, focal lengths that are zero or not finite, an
 	// object that bins a stream (setStreamBinning() was called: the two do not compose; setStreamBinning() refuses the
 	// same way once a stream was warped).  An object on which neither was called binds nothing.
@@ -165,6 +166,9 @@ public:
 	inline int getImageWidth() const { return image_width; }
 	inline int getImageHeight() const { return image_height; }
 	int getPyramidLevels() const;
+	// How the engine ran the last accepted push()/pushCamera(): 0 none yet, 1 one launch per tick, 2 the composed
+	// launches (aof_bank_last_path, include/aof.h).
+	int lastPushPath() const;
 	bool engineOk() const;
 	const char *lastError() const;
 

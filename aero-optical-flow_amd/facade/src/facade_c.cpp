@@ -161,6 +161,7 @@ const void *aof_facade_bank_exposure_commands(void *bank) { return static_cast<O
 const void *aof_facade_bank_published(void *bank) { return static_cast<OpticalFlowBank *>(bank)->published(); }
 int aof_facade_bank_reset(void *bank, const uint8_t *mask) { return static_cast<OpticalFlowBank *>(bank)->reset(mask); }
 int aof_facade_bank_pyramid_levels(void *bank) { return static_cast<OpticalFlowBank *>(bank)->getPyramidLevels(); }
+int aof_facade_bank_last_push_path(void *bank) { return static_cast<OpticalFlowBank *>(bank)->lastPushPath(); }
 int aof_facade_bank_ok(void *bank) { return static_cast<OpticalFlowBank *>(bank)->engineOk() ? 1 : 0; }
 const char *aof_facade_bank_last_error(void *bank) { return static_cast<OpticalFlowBank *>(bank)->lastError(); }
 

@@ -453,6 +453,13 @@ int OpticalFlowBank::getPyramidLevels() const
 	return p.pyramid_levels;
 }
 
+int OpticalFlowBank::lastPushPath() const
+{
+	if (!_m || !_m->ctx) return 0;
+	const int path = aof_bank_last_path(_m->ctx);
+	return path < 0 ? 0 : path;
+}
+
 bool OpticalFlowBank::engineOk() const { return _m != NULL && !_failed; }
 
 const char *OpticalFlowBank::lastError() const { return _err; }

@@ -472,6 +472,10 @@ int aof_bank_push_device(aof_ctx *ctx, const aof_bank_params *bp, const uint8_t 
  * the composed path, not an error), 2 = always the composed path.  Identical bytes either way (tests compare them).
  * -EINVAL: NULL ctx, path outside 0..2. */
 int aof_set_bank_path(aof_ctx *ctx, int path);
+/* Host only: which path the most recent ACCEPTED push of this context took, whichever of the four push forms it was:
+ * 0 = no push yet, 1 = one-launch kernel(s), 2 = the composed launches.  A refused push leaves it as it was.
+ * -EINVAL: NULL ctx. */
+int aof_bank_last_path(const aof_ctx *ctx);
 
 /* ---- the stream bank with per-stream cameras: focal lengths, output rate, vehicle time and MAVLink identity ----
  * aof_bank_params carries ONE focal length pair, output rate, time offset and MAVLink identity for all S streams: S
@@ -846,9 +850,22 @@ int aof_bank_pixel_row_bytes(uint8_t format, int32_t width, int64_t *out);
  * Contract: with warps bound, every camera push (tick and burst) computes a warped stream's new frame by the rule above;
  * the exposure histogram and MSV are those of the warped crop; records, wire frames, de-rotated pairs, stored frame and
  * state equal byte for byte those of a grey stream whose sensor frame is the warped crop computed on the host
- * (aof_warp_host).  The push then always takes the composed path, whatever aof_set_bank_path says: the warp launch into
- * the staging region (with the raw histograms), aof_flow_batch_device, the commit kernel; per round of a burst.  With
+ * (aof_warp_host).  aof_set_bank_path applies as it does without a lens.  The one-launch form is the tick kernel with the
+ * warp inside it: one workgroup per stream clamps the stream's mesh into LDS, gathers the warped crop straight into the
+ * new frame's LDS buffer and goes on as the camera tick does; a burst of K rounds is K such launches, one per round.  It
+ * is taken iff the path is not 2, the configuration is of the one-workgroup class (as for every one-launch tick), the
+ * frames, the mesh's nx*ny*8 bytes of nodes and the kernels' static arrays fit LDS (aof_bank_warp_one_launch below says
+ * so for a configuration), and the path is 1 or n_streams is at most the warped form's crossover
+ * (aof_bank_warp_crossover).  The one-launch warped push NEITHER READS NOR WRITES the staging region of the bank.
+ * Otherwise the push takes the composed path: the warp launch into the staging region (with the raw histograms),
+ * aof_flow_batch_device, the commit kernel; per round of a burst.  Identical bytes either way (tests compare them).  With
  * nothing bound not one launch changes.
+ * Measured (profiles/bank_warp_one_launch_ab.txt; 640x480 grey frames, a barrel lens, us per tick, one-launch / composed as
+ * the build before the kernel ran it): 64x64 crops 17.1 / 23.8 at 64 streams, 30.4 / 43.7 at 1 024, 56.2 / 60.0 at 2 048,
+ * 89.2 / 95.2 at 4 096; two-level 128x128 33.8 / 46.2, 81.0 / 96.6, 135.8 / 137.2, 262.6 / 236.9: the crossover is 2 048
+ * streams.  A lens costs 1.35 to 2.17 times the one-launch tick without one.  Not measured: the gather alone (a kernel
+ * trace), the source footprint staged in LDS against taps from L2, formats other than grey, other meshes, bursts other than
+ * K = 5 (LAB_LOG.md, "Stream bank warp, one launch").
  * Binding: used by the two camera pushes.  A bound count that differs from bp->n_streams, or a binning bound at the same
  * time (aof_set_bank_binning: the composition of binning and warp is not served; bin the mesh instead, nodes 2 or 4
  * times as far apart), makes those pushes return -EINVAL before anything is enqueued.  The KERNELS read the array when
@@ -881,6 +898,13 @@ int aof_warp_mesh_from_lens(const aof_params *p, const aof_lens *lens, aof_warp_
  * 16-byte aligned.  NULL (with n_streams 0) unbinds.  -EINVAL: NULL ctx, a non-NULL array with n_streams < 1, a
  * misaligned array (the binding stays as it was). */
 int aof_set_bank_warps(aof_ctx *ctx, const aof_warp_point *d_points, int32_t n_streams);
+/* Host only: 1 if a camera push of configuration p with warps bound can run as one launch per round (the one-workgroup
+ * class's verdict, and frames + nodes + static arrays inside LDS), else 0 (an invalid p included).  *lds_bytes (may be
+ * NULL): the dynamic LDS a workgroup of it would ask for -- the one-workgroup plan's bytes plus 8 nx ny.  -EINVAL: NULL p. */
+int aof_bank_warp_one_launch(const aof_params *p, int64_t *lds_bytes);
+/* Host only: the largest n_streams at which the library's own choice (aof_set_bank_path 0) takes the one-launch kernel
+ * for a push with warps bound; 0: never (path 1 still does). */
+int aof_bank_warp_crossover(void);
 /* aof_ingest_sensor_formats_device with frame i resampled through mesh d_points[i] (aof_warp_point [n_frames][ny][nx] of
  * the crop size, 16-byte aligned): any crop size up to 16 384 pixels wide, 16-byte stores where crop_width % 16 == 0 and
  * d_cropped, cropped_stride are multiples of 16.  d_ok[i] = 0: frame i's record is not valid; nothing of it is read and

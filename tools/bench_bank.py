@@ -78,10 +78,16 @@ end in the path, 1 or 2).  Every stream's frame lies in a slot of 2 cam_w cam_h 
 With --warp, the camera tick with warp meshes (aof_set_bank_warps) on 640 x 480 grey frames -- the synthetic frame at the
 centre crop and repeated around it, so that a mesh reaching outside the plain crop reads moving texture:
     P   the composed camera tick (path 2), nothing bound (with AOF_LIB, on a build without the call: the yardstick of P);
-    I   the same with S identity meshes bound (a push with meshes bound always takes the composed path);
+    I   the same with S identity meshes bound (path 2: the composed path of a bank with meshes bound);
     L   with the mesh of a barrel lens (k1 -0.28, k2 0.07, focal length 0.9 of the crop size);
     F   the one-launch camera tick (path 1), nothing bound: what a warped bank gives up (also run under AOF_LIB);
-    U   what a caller does without the binding: aof_ingest_warped_device into a grey buffer, then the camera tick on it.
+    U   what a caller does without the binding: aof_ingest_warped_device into a grey buffer, then the camera tick on it;
+    W   the barrel lens on path 1: the one-launch tick with the warp inside it (k_bank_tick_warp.hip);
+    WI  identity meshes on path 1;
+    WB1 / WB2   a burst of K = 5 rounds with the lens on path 1 (five launches of that kernel) and on path 2 (fifteen
+        launches), us per burst; the sensor frames of the burst legs carry noise around the crop.
+    W, WI, WB1 and WB2 assert through aof_bank_last_path that they timed the path they name.  The yardstick of W is leg L
+    of the build before the kernel, loaded through AOF_LIB in the same session (--legs P,L,F).
 K1 / K2 are the legs --camera runs under those names (leg_camera); --per-sensor --legs K1,K2 runs them alone, which is how
 two builds of the library are compared in turn in one session.
 Every leg settles for about 0.2 s of untimed ticks, then times at least --ticks ticks and at least --seconds seconds
@@ -98,7 +104,8 @@ between the repeats is the run-to-run spread a difference between legs has to be
     python tools/bench_bank.py --per-sensor --streams 64,1024 > profiles/bank_per_sensor_ab.txt
     python tools/bench_bank.py --binning --repeats 3 > profiles/bank_binning_ab.txt
     python tools/bench_bank.py --raw-formats --repeats 3 > profiles/bank_raw_formats_ab.txt
-    python tools/bench_bank.py --warp --repeats 3 > profiles/bank_warp_ab.txt"""
+    python tools/bench_bank.py --warp --repeats 3 > profiles/bank_warp_ab.txt
+    python tools/bench_bank.py --warp --repeats 3 --streams 64,256,1024,2048,4096 > profiles/bank_warp_one_launch_ab.txt"""
 import argparse
 import ctypes as C
 import importlib
@@ -603,21 +610,22 @@ def tiled_sensor_frames(p, S, inp, dev, cam_w, cam_h, ring):
 
 
 def leg_warp(p, S, inp, cams, dev, a, leg):
-    """One of P / I / L / F / U of --warp (see warp_sweep's text): the camera tick on 640 x 480 grey frames."""
+    """One of P / I / L / F / U / W / WI of --warp (see warp_sweep's text): the camera tick on 640 x 480 grey frames."""
     eng = aof.FlowEngine(p, 0)
     w, h = p.width, p.height
     cam_w, cam_h = WARP_SENSOR
-    eng.set_bank_path({"P": 2, "I": 2, "L": 2, "F": 1, "U": 0}[leg])
+    path = {"P": 2, "I": 2, "L": 2, "F": 1, "U": 0, "W": 1, "WI": 1}[leg]
+    eng.set_bank_path(path)
     bp = aof.bank_params(S, FX, FY, 15, 5_000_000, 1, 100, 0)
     two_calls = leg == "U"
     cam = aof.bank_camera_params(w if two_calls else cam_w, h if two_calls else cam_h, w, h, 0, 200_000, DEROTATE, FX, FY)
     bank = eng.bank_create(bp, dev, camera=cam)
     x0, y0 = cam_w // 2 - w // 2, cam_h // 2 - h // 2
     d_points = d_table = grey = None
-    if leg in ("I", "L", "U"):
+    if leg in ("I", "L", "U", "W", "WI"):
         # the lens of a short downward camera: 13 % barrel at the crop's corner, seen by a pinhole camera of the same focal length
         f = 0.9 * max(w, h)
-        mesh = aof.warp_mesh_identity(p, x0, y0) if leg == "I" else aof.warp_mesh_from_lens(p, f, f, cam_w / 2.0, cam_h / 2.0, k1=-0.28, k2=0.07)
+        mesh = aof.warp_mesh_identity(p, x0, y0) if leg in ("I", "WI") else aof.warp_mesh_from_lens(p, f, f, cam_w / 2.0, cam_h / 2.0, k1=-0.28, k2=0.07)
         d_points = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(mesh, (S,) + mesh.shape)).view(np.uint8).reshape(S, -1)).to(dev)
     if two_calls:
         table = aof.bank_sensor_from_camera(p, aof.bank_camera_params(cam_w, cam_h, w, h, 0, 200_000, DEROTATE, FX, FY), n=S)
@@ -651,8 +659,24 @@ def leg_warp(p, S, inp, cams, dev, a, leg):
     out = timed(step, torch.cuda.synchronize, a.ticks, a.seconds, a.settle)
     r = aof.ticks_view(recs)
     assert (r["quality"] >= aof.TICK_HELD).all() and (r["frame"] > a.ticks).all(), "the timed ticks were real ticks"
+    if path and hasattr(aof.lib, "aof_bank_last_path"):
+        assert eng.last_bank_path() == path, (leg, "timed path", eng.last_bank_path(), "meant", path)
     eng.close()
     return out
+
+
+WARP_BURST_K = 5
+
+
+def leg_warp_burst(p, S, dev, a, path):
+    """WB1 / WB2 of --warp: one camera burst of K = 5 rounds per step with the barrel lens bound, on `path`."""
+    w, h = p.width, p.height
+    cam_w, cam_h = WARP_SENSOR
+    f = 0.9 * max(w, h)
+    mesh = aof.warp_mesh_from_lens(p, f, f, cam_w / 2.0, cam_h / 2.0, k1=-0.28, k2=0.07)
+    points = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(mesh, (S,) + mesh.shape)).view(np.uint8).reshape(S, -1)).to(dev)
+    inp = BurstInputs(p, S, WARP_BURST_K, dev, sensor=WARP_SENSOR)
+    return leg_burst(p, S, WARP_BURST_K, path, inp, dev, a, WARP_SENSOR, False, points=points)
 
 
 def warp_sweep(a, dev):
@@ -663,6 +687,10 @@ def warp_sweep(a, dev):
     print("# us = microseconds per tick (host clock, ticks ending in a synchronise)")
     bound = hasattr(aof.lib, "aof_set_bank_warps")      # (AOF_LIB may name a build without the call: P and F only)
     legs = ["P", "I", "L", "F", "U"] if bound else ["P", "F"]
+    if hasattr(aof.lib, "aof_bank_last_path"):          # (the build with the warp inside the one-launch tick)
+        print("# W the barrel lens on path 1 (the one-launch tick with the warp inside it); WI identity meshes on path 1; WB1 / WB2 a burst of "
+              f"K = {WARP_BURST_K} rounds with the lens on path 1 / path 2, us per burst (noise around the crop); each asserts aof_bank_last_path")
+        legs += ["W", "WI", "WB1", "WB2"]
     if a.legs is not None:
         legs = [leg for leg in legs if leg in a.legs.split(",")]
     sizes = [int(s) for s in a.streams.split(",")]
@@ -674,7 +702,7 @@ def warp_sweep(a, dev):
                 inp = Inputs(p, S, dev)
                 cams = tiled_sensor_frames(p, S, inp, dev, *WARP_SENSOR, WARP_RING)
                 for name in legs:
-                    sec, n = leg_warp(p, S, inp, cams, dev, a, name)
+                    sec, n = leg_warp_burst(p, S, dev, a, int(name[2])) if name.startswith("WB") else leg_warp(p, S, inp, cams, dev, a, name)
                     results.setdefault((cfg, S, name), []).append(sec)
                     print(f"rep {rep} {cfg:11s} S={S:6d} {name:2s} {sec * 1e6:10.2f} us  ({n} ticks)", flush=True)
                 del inp, cams
@@ -688,6 +716,10 @@ def warp_sweep(a, dev):
                 for n in m)
             if all(n in m for n in ("P", "I", "L", "F", "U")):
                 line += f"  I/P {m['I'] / m['P']:5.3f}  L/P {m['L'] / m['P']:5.3f}  L/F {m['L'] / m['F']:5.3f}  L/U {m['L'] / m['U']:5.3f}"
+            if all(n in m for n in ("L", "F", "W")):
+                line += f"  W/F {m['W'] / m['F']:5.3f}  W/L {m['W'] / m['L']:5.3f}"
+            if all(n in m for n in ("WB1", "WB2")):
+                line += f"  WB1/WB2 {m['WB1'] / m['WB2']:5.3f}"
             print(line)
 
 
@@ -826,10 +858,13 @@ class BurstInputs:
         self.gyro = torch.full((K, S, 4), 0.001, dtype=torch.float32, device=dev)
 
 
-def leg_burst(p, S, K, path, inp, dev, a, sensor, single_ticks):
-    """One burst of K rounds per step, or (single_ticks) K calls of the single tick on the same buffers, round by round."""
+def leg_burst(p, S, K, path, inp, dev, a, sensor, single_ticks, points=None):
+    """One burst of K rounds per step, or (single_ticks) K calls of the single tick on the same buffers, round by round.
+    points: S warp meshes to bind (--warp's burst legs, which assert the path they timed)."""
     eng = aof.FlowEngine(p, 0)
     eng.set_bank_path(path)
+    if points is not None:
+        eng.set_bank_warps(points, S)
     bp = aof.bank_params(S, FX, FY, 15, 5_000_000, 1, 100, 0)
     cam = aof.bank_camera_params(sensor[0], sensor[1], p.width, p.height, 0, 200_000, DEROTATE, FX, FY) if sensor else None
     bank = eng.bank_create(bp, dev, camera=cam)
@@ -869,6 +904,8 @@ def leg_burst(p, S, K, path, inp, dev, a, sensor, single_ticks):
     out = timed_bursts(step, torch.cuda.synchronize, K, a.ticks, a.seconds, a.settle)
     r = aof.ticks_view(recs[K - 1])
     assert (r["quality"] >= aof.TICK_HELD).all() and (r["frame"] > a.ticks).all(), "the timed rounds were real rounds"
+    if points is not None:
+        assert eng.last_bank_path() == path, ("timed path", eng.last_bank_path(), "meant", path)
     eng.close()
     return out
 
@@ -1639,7 +1676,7 @@ def main():
                     "bank paths (G1, ..., D42; --legs G1,G2 runs the yardstick alone, for a build without the call through AOF_LIB)")
     ap.add_argument("--raw-formats", action="store_true", help="the camera tick with raw mono pixels: legs G, R, P, M, D on both bank "
                     "paths (G1, ..., D2; --legs G1,G2 runs the yardstick alone, for a build without the formats through AOF_LIB)")
-    ap.add_argument("--warp", action="store_true", help="the camera tick with warp meshes bound: legs P, I, L, F, U on 640 x 480 frames (--legs P,F "
+    ap.add_argument("--warp", action="store_true", help="the camera tick with warp meshes bound: legs P, I, L, F, U, W, WI, WB1, WB2 on 640 x 480 frames (--legs P,F "
                     "runs the legs that need no mesh alone, for a build without the call through AOF_LIB)")
     ap.add_argument("--forms", default="plain,camera", help="--burst: entry points to sweep")
     ap.add_argument("--input-bytes-max", type=float, default=24 * 2**30, help="--burst: sizes whose K rounds of input exceed this are skipped")
