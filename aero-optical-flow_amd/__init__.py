@@ -195,6 +195,18 @@ MAVLINK_RX_STATE_DTYPE = np.dtype([("bytes", "<u8"), ("frames", "<u4"), ("imu_sa
 assert MAVLINK_RX_STATE_DTYPE.itemsize == 128
 
 
+class FieldParams(C.Structure):
+    """``aof_field_params`` (include/aof.h)."""
+    _fields_ = [("min_blocks", C.c_int32), ("passes", C.c_int32), ("exclude_reach", C.c_int32), ("gate_px", C.c_float)]
+
+
+FIELD_VALID, FIELD_REFIT = 1, 2
+FIELD_DTYPE = np.dtype([("det", "<i8"), ("num_zoom", "<i8"), ("num_rot", "<i8"), ("accepted", "<u4"), ("at_reach", "<u4"),
+                        ("fitted", "<u4"), ("used", "<u4"), ("zoom", "<f4"), ("rotation", "<f4"), ("centre_x", "<f4"),
+                        ("centre_y", "<f4"), ("flags", "<u4"), ("reserved", "<u4")])   # aof_field
+assert FIELD_DTYPE.itemsize == 64
+
+
 class OutboxLayout(C.Structure):
     """``struct aof_outbox_layout`` (include/aof.h)."""
     _fields_ = [(n, C.c_size_t) for n in ("total_bytes", "messages", "exposures")]
@@ -340,6 +352,10 @@ def _load():
         "aof_bank_mavlink_rx_reset_device": (C.c_int, [VP, C.c_int32, VP, VP, VP]),
         "aof_bank_mavlink_rx_device": (C.c_int, [VP, P(MavlinkRxParams), VP, VP, VP, VP, VP, VP]),
         "aof_bank_mavlink_rx_host": (C.c_int, [P(MavlinkRxParams), VP, VP, VP, VP, VP]),
+        "aof_field_params_default": (C.c_int, [P(FieldParams)]),
+        "aof_field_supported": (C.c_int, [P(Params)]),
+        "aof_field_batch_device": (C.c_int, [VP, P(FieldParams), VP, VP, VP, I64, VP, VP]),
+        "aof_field_host": (C.c_int, [P(Params), P(FieldParams), VP, VP, VP, I64, VP]),
         "aof_derotate_batch_device": (C.c_int, [P(DerotateParams), VP, VP, I64, VP, VP]),
         "aof_exposure_msv": (C.c_float, [VP]),
         "aof_exposure_bin": (C.c_int, [C.c_int]),
@@ -912,6 +928,50 @@ def mavlink_rx_states_view(t) -> np.ndarray:
     return np.ascontiguousarray(a).view(MAVLINK_RX_STATE_DTYPE).reshape(a.shape[:-1])
 
 
+def field_params(min_blocks=None, passes=None, exclude_reach=None, gate_px=None) -> FieldParams:
+    """``aof_field_params_default`` (8 blocks, two passes, blocks at reach left out, a gate of 1 px), with overrides."""
+    fp = FieldParams()
+    lib.aof_field_params_default(C.byref(fp))
+    for k, v in (("min_blocks", min_blocks), ("passes", passes), ("exclude_reach", exclude_reach)):
+        if v is not None:
+            setattr(fp, k, int(v))
+    if gate_px is not None:
+        fp.gate_px = float(gate_px)
+    return fp
+
+
+def field_supported(p: Params) -> bool:
+    """``aof_field_supported``: does the motion-field fit serve the level-0 grid of `p`?"""
+    return lib.aof_field_supported(C.byref(p)) == 0
+
+
+def field_host(p: Params, blocks, flows, subdirs=None, params: FieldParams = None) -> np.ndarray:
+    """``aof_field_host``: the motion-field fit on host memory, no device.  blocks: BLOCK_DTYPE (or uint32) [n, nb];
+    flows: FLOW_DTYPE [n]; subdirs: uint8 [n, nb] or None.  Returns FIELD_DTYPE [n]."""
+    blocks = np.ascontiguousarray(blocks)
+    assert blocks.dtype.itemsize == 4 and blocks.ndim == 2
+    n, nb = blocks.shape
+    flows = np.ascontiguousarray(flows, dtype=FLOW_DTYPE).reshape(n)
+    if subdirs is not None:
+        subdirs = np.ascontiguousarray(subdirs, dtype=np.uint8)
+        assert subdirs.shape == (n, nb)
+    g = grid(p, 0)
+    assert nb == g[4] * g[5], (nb, g)
+    out = np.zeros(n, FIELD_DTYPE)
+    fp = params if params is not None else field_params()
+    rc = lib.aof_field_host(C.byref(p), C.byref(fp), blocks.ctypes.data, subdirs.ctypes.data if subdirs is not None else None,
+                            flows.ctypes.data, n, out.ctypes.data)
+    if rc:
+        raise AofError(rc, lib.aof_strerror(rc).decode())
+    return out
+
+
+def fields_view(t) -> np.ndarray:
+    """uint8 tensor/array [n, 64] of ``aof_field`` -> structured numpy view [n]."""
+    a = t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+    return np.ascontiguousarray(a).view(FIELD_DTYPE).reshape(a.shape[:-1])
+
+
 def exposure_states_view(t) -> np.ndarray:
     """uint8 tensor/array [S, 16] of ``aof_exposure_state`` -> structured numpy view [S]."""
     a = t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
@@ -1093,6 +1153,25 @@ class FlowEngine:
             subdirs.data_ptr() if subdirs is not None else None, flows.data_ptr(),
             workspace.data_ptr(), workspace.numel(), stream))
         return blocks, flows, workspace
+
+    def field_batch(self, blocks, flows, subdirs=None, fields=None, params: FieldParams = None, stream=None):
+        """aof_field_batch_device behind flow_batch: blocks [n, nb] int32-viewed records, flows [n, 16] bytes, subdirs uint8
+        [n, nb] or None, all CUDA tensors as flow_batch returns them.  fields: a uint8 tensor [n, 64] to write or None (a new
+        one; read it with fields_view()).  Enqueued on torch's current stream, or on `stream` (a hipStream_t value)."""
+        import torch
+        n, nb = blocks.shape
+        assert blocks.dtype == torch.int32 and blocks.is_contiguous() and nb == self.nblocks(0)
+        assert flows.dtype == torch.uint8 and flows.is_contiguous() and flows.numel() == 16 * n
+        assert subdirs is None or (subdirs.dtype == torch.uint8 and subdirs.is_contiguous() and tuple(subdirs.shape) == (n, nb))
+        if fields is None:
+            fields = torch.empty((n, 64), dtype=torch.uint8, device=blocks.device)
+        assert fields.dtype == torch.uint8 and fields.is_contiguous() and fields.numel() == 64 * n
+        fp = params if params is not None else field_params()
+        if stream is None:
+            stream = torch.cuda.current_stream(blocks.device).cuda_stream
+        self._check(lib.aof_field_batch_device(self._ctx, C.byref(fp), blocks.data_ptr(), subdirs.data_ptr() if subdirs is not None else None,
+                                               flows.data_ptr(), n, fields.data_ptr(), stream))
+        return fields
 
     def bind_batch(self, prev, cur, blocks, flows, workspace, subdirs=None, stream=None):
         """flow_batch with every argument resolved once: returns a callable that enqueues the same

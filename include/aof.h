@@ -1212,6 +1212,59 @@ int aof_bank_mavlink_rx_device(aof_ctx *ctx, const aof_mavlink_rx_params *rp, co
 int aof_bank_mavlink_rx_host(const aof_mavlink_rx_params *rp, const uint8_t *bytes, const uint16_t *len,
                              aof_mavlink_rx_state *states, aof_imu_sample *samples, uint8_t *sample_count);
 
+/* ---- the motion FIELD of a batch: zoom, rotation and the flow at the frame centre, fitted to the block records ----
+ * aof_flow holds one translation, the histogram-filtered mean of the block shifts.  A downward camera also climbs,
+ * descends and yaws: the block field is then not constant, the votes spread over several bins and the peak window keeps
+ * an arbitrary part of them.  This call fits, per pair, the least-squares SIMILARITY to the same block records --
+ * nothing looks at the images again -- and gives the translation at the frame centre, the relative scale change and the
+ * rotation.  DESIGN.md ("The motion field") is the normative text; in short, with the level-0 grid of aof_grid,
+ * B = tile, S = search, W x H the frame and vthr = min(value_threshold, 0xFFFF), block k = by*nx + bx
+ *   is ACCEPTED iff sad != 0xFFFF && sad < vthr (Reduce's rule: accepted == aof_flow.count),
+ *   is AT REACH iff accepted and |dx - pred_x| == S or |dy - pred_y| == S (pred of the pair's aof_flow, whatever its flags say),
+ *   sits at X = 2*(x0 + bx*step_x) + B - W, Y = 2*(y0 + by*step_y) + B - H (half-pixels from the frame centre to the block centre)
+ *   and moved by U = 2*dx + hx, V = 2*dy + hy (half-pixels; (hx, hy) from the sub-direction as in Reduce, (0, 0) without subdirs).
+ * Over a set M of blocks the exact integer sums n, SX, SY, SU, SV, Q = sum(X*X + Y*Y), A = sum(X*U + Y*V),
+ * C = sum(X*V - Y*U) give D = n*Q - SX*SX - SY*SY, Na = n*A - SX*SU - SY*SV, Nb = n*C - SX*SV + SY*SU; M FITS iff
+ * n >= min_blocks and D > 0.  The model, in double, every operation rounded on its own (no fused multiply-add), integers
+ * converted to double first:  a = Na / D,  b = Nb / D,  tU = ((SU - a*SX) + b*SY) / n,  tV = ((SV - b*SX) - a*SY) / n;
+ * it says U ~ tU + a*X - b*Y and V ~ tV + b*X + a*Y.
+ * M1 = the accepted blocks, without those at reach when exclude_reach is set.  With passes == 2, M2 = the blocks of M1
+ * with fabs(U - ((tU + a*X) - b*Y)) <= g and fabs(V - ((tV + b*X) + a*Y)) <= g, g = 2.0 * (double)gate_px; if M2 fits,
+ * its model is published and AOF_FIELD_REFIT set, else M1's.  If M1 does not fit the record is all zero except
+ * `accepted` and `at_reach`.
+ * Not here: the per-call path (aof_flow_pair_host, aof_stream_push_host), the sequence pipeline, the stream bank and the
+ * facade classes publish no field. */
+typedef struct aof_field_params {
+    int32_t min_blocks;     /* >= 3, default 8 */
+    int32_t passes;         /* 1 | 2, default 2 */
+    int32_t exclude_reach;  /* 0 | 1, default 1 */
+    float gate_px;          /* > 0, finite, default 1.0 */
+} aof_field_params;
+#define AOF_FIELD_VALID 1u
+#define AOF_FIELD_REFIT 2u
+typedef struct aof_field {              /* 64 bytes, 8-byte aligned, one per pair */
+    int64_t det, num_zoom, num_rot;     /* D, Na, Nb of the published set */
+    uint32_t accepted, at_reach, fitted /* |M1| */, used /* |published set| */;
+    float zoom, rotation;               /* (float)a, (float)b: relative scale change, radians (small angle) */
+    float centre_x, centre_y;           /* (float)(tU*0.5), (float)(tV*0.5): level-0 pixels at the frame centre */
+    uint32_t flags, reserved;           /* AOF_FIELD_*; reserved = 0 */
+} aof_field;
+int aof_field_params_default(aof_field_params *fp);
+/* 0 where the fit serves the geometry of `p`; -EINVAL for parameters aof_params_check refuses and for a level-0 grid with
+ * nb*nb * (Xmax*Xmax + Ymax*Ymax) >= 2^62 (nb blocks, Xmax / Ymax the largest |X| / |Y| of the grid): below that bound every
+ * sum and product above fits int64 (the proof stands in csrc/aof_field.cpp).  Host only. */
+int aof_field_supported(const aof_params *p);
+/* d_blocks: [n_pairs][nb0] as aof_flow_batch_device wrote them; d_subdirs: [n_pairs][nb0] or NULL; d_flows: [n_pairs], the
+ * pairs' records (read for pred_x / pred_y); d_fields: [n_pairs], written.  Only enqueues on `stream`: no allocation, no
+ * host synchronisation, capturable; the inputs are only read.  -EINVAL with nothing enqueued: NULL ctx, fp, d_blocks,
+ * d_flows or d_fields, n_pairs < 0 or >= 2^31, parameters outside the ranges above, a geometry aof_field_supported refuses,
+ * d_blocks or d_flows not 4-byte aligned, d_fields not 8-byte aligned; -EIO: the context's sticky fault. */
+int aof_field_batch_device(aof_ctx *ctx, const aof_field_params *fp, const aof_block *d_blocks, const uint8_t *d_subdirs,
+                           const aof_flow *d_flows, int64_t n_pairs, aof_field *d_fields, void *stream);
+/* The same function on host memory, a plain loop: no device, no context.  -EINVAL as above (alignment aside). */
+int aof_field_host(const aof_params *p, const aof_field_params *fp, const aof_block *blocks, const uint8_t *subdirs,
+                   const aof_flow *flows, int64_t n_pairs, aof_field *out);
+
 /* ---- measurement ----
  * With profiling on, every launch is bracketed by HIP events on the stream it
  * is launched on; the last AOF_PROFILE_RING launches of each kernel are kept.
