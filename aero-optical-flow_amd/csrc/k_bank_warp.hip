@@ -5,7 +5,7 @@
 // Shaped like k_ingest: 256 lanes, a workgroup per (frame, strip of up to 128 rows); the frame's record comes through the
 // scalar path (bank_sensor, aof_bank_stream.hpp) and a workgroup whose record forbids the read leaves before its first
 // load.  The strip's nodes are clamped into LDS once (two node rows more than a strip has cells: 17 rows of nx for 128
-// rows).  A lane produces 16 consecutive pixels of a row -- two cells, along which a coordinate advances by one addition
+// rows; the strip, its halving for wide crops and the launch's LDS are warp_plan_make's, aof_warp_plan.hpp).  A lane produces 16 consecutive pixels of a row -- two cells, along which a coordinate advances by one addition
 // per pixel -- and stores them as one 16-byte value; crops whose width is no multiple of 16 (or whose destination is
 // not aligned) take a lane per pixel.  A gather, not a copy: a pixel is four taps at a place only the mesh knows.  Grey
 // planes fetch a tap's horizontal pair as ONE 2-byte load (any alignment), every other format a byte at a time through
@@ -16,15 +16,11 @@
 // with integer atomics to words the launcher zeroed.
 #include "aof_bank_stream.hpp"   // (bank_sensor, kThreads)
 #include "aof_warp_gather.hpp"   // (aof_warp_step.hpp; sample)
+#include "aof_warp_plan.hpp"     // (the launch plan and its constants: kLaneItems)
 
 namespace aof {
 
 namespace {
-
-constexpr int kStripRows = 128;          // (k_ingest's kRowsPerBlock; a multiple of the cell)
-constexpr int kNodeBytesWanted = 32768;  // a strip is halved until its nodes fit this ...
-constexpr int kNodeBytesMax = 61440;     // ... and a crop whose 8-row strip needs more than this is refused
-constexpr int kLaneItems = 255;          // 16-pixel items of a lane between two flushes: 255 * 16 < 4096 (12-bit fields)
 
 struct LaneBins { unsigned long long lo, hi; };   // bins 0..4, 5..9, 12 bits each
 
@@ -164,23 +160,22 @@ __global__ __launch_bounds__(kThreads) void k_bank_warp(WarpArgs a)
 int launch_warp(const WarpArgs &args, int64_t n_frames, void *stream)
 {
     if (n_frames == 0) return 0;
+    const WarpPlan plan = warp_plan_make(args.crop_w, args.crop_h, n_frames, reinterpret_cast<uintptr_t>(args.cropped), args.cropped_stride,
+                                         args.hist != nullptr);
+    if (plan.verdict != WARP_OK) return (int)hipErrorInvalidValue;
     WarpArgs a = args;
-    a.nx = warp_nodes(a.crop_w); a.ny = warp_nodes(a.crop_h);
-    // the strip: k_ingest's 128 rows, halved while its node rows would not fit
-    a.strip_rows = kStripRows;
-    auto node_bytes = [&](int rows) { return (int64_t)(rows / kWarpCell + 1) * a.nx * (int64_t)sizeof(int2); };
-    while (a.strip_rows > kWarpCell && node_bytes(a.strip_rows) > kNodeBytesWanted) a.strip_rows /= 2;
-    if (node_bytes(a.strip_rows) > kNodeBytesMax) return (int)hipErrorInvalidValue;
-    a.nstrips = (a.crop_h + a.strip_rows - 1) / a.strip_rows;
-    if (n_frames * a.nstrips > 0x7FFFFFFF) return (int)hipErrorInvalidValue;
-    if (a.hist && a.nstrips > 1) {   // several workgroups add to a frame's histogram
+    a.nx = plan.nx; a.ny = plan.ny;
+    a.strip_rows = plan.strip_rows; a.nstrips = plan.nstrips;
+    a.vec = plan.vec;
+    if (plan.zero_hist) {   // several workgroups add to a frame's histogram
         const int rc = launch_zero_words(a.hist, n_frames * AOF_EXPOSURE_BINS, stream);
         if (rc) return rc;
     }
-    a.vec = (a.crop_w % 16 == 0) && (!a.cropped || (reinterpret_cast<uintptr_t>(a.cropped) % 16 == 0 && a.cropped_stride % 16 == 0));
-    const int rows = a.crop_h < a.strip_rows ? a.crop_h : a.strip_rows;
-    const size_t lds = (size_t)node_bytes((rows + kWarpCell - 1) / kWarpCell * kWarpCell);
-    hipLaunchKernelGGL(k_bank_warp, dim3((uint32_t)(n_frames * a.nstrips)), dim3(kThreads), lds, static_cast<hipStream_t>(stream), a);
+    if (plan.attr) {   // (aof_small_plan.hpp: dynamic LDS beyond 48 KiB needs the function attribute)
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_bank_warp), hipFuncAttributeMaxDynamicSharedMemorySize, kNodeBytesMax);
+        if (e != hipSuccess) return e == hipErrorInvalidValue ? (int)hipErrorLaunchFailure : (int)e;   // (invalid value is the plan's refusal)
+    }
+    hipLaunchKernelGGL(k_bank_warp, dim3((uint32_t)plan.wgs), dim3(kThreads), plan.lds, static_cast<hipStream_t>(stream), a);
     return (int)hipGetLastError();
 }
 

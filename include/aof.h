@@ -908,8 +908,10 @@ int aof_bank_warp_crossover(void);
 /* aof_ingest_sensor_formats_device with frame i resampled through mesh d_points[i] (aof_warp_point [n_frames][ny][nx] of
  * the crop size, 16-byte aligned): any crop size up to 16 384 pixels wide, 16-byte stores where crop_width % 16 == 0 and
  * d_cropped, cropped_stride are multiples of 16.  d_ok[i] = 0: frame i's record is not valid; nothing of it is read and
- * no byte of its crop written (its histogram: untouched, or ten zeros where the crop is higher than 128 rows and the
- * strips of a frame add to words zeroed in front of them).  -EINVAL as there, and for NULL or misaligned d_points. */
+ * no byte of its crop written (its histogram: untouched, or ten zeros where a frame is made in several strips, which add
+ * to words zeroed in front of them: a crop higher than 128 rows, or higher than the 64 .. 8 rows a strip keeps from 1 920
+ * pixels of width on).  -EINVAL as there, for NULL or misaligned d_points, and for a crop wider than 30 712 pixels (the
+ * nodes of one cell row no longer fit a workgroup's 60 KiB: nothing is launched or written). */
 int aof_ingest_warped_device(int32_t crop_width, int32_t crop_height, const uint8_t *d_camera, uint64_t camera_bytes,
                              const aof_bank_sensor *d_sensors, const uint8_t *d_formats, const aof_warp_point *d_points,
                              int64_t n_frames, uint8_t *d_cropped, int64_t cropped_stride, uint32_t *d_hist, uint8_t *d_ok,

@@ -10,7 +10,8 @@
 // on the cases of tests/lane8_plan_ref.py, likewise, and xcd_remap (aof_xcd_remap.hpp, the text the kernels run) printed value by
 // value for the test to hold to the model's; the plan of a batch and the per-launch choice of a flat 8x8 launch (aof_batch_plan.hpp:
 // plan_batch, choose_lane8) and the launch plan of the 16x16 search (aof_tile16_plan.hpp: tile16_plan) on the cases of
-// tests/batch_plan_ref.py, likewise, with a table of choose_lane8 rows against values written here; and fastdiv_make against the division it replaces, with the kernels' fast_div restated in 32-bit
+// tests/batch_plan_ref.py, likewise, with a table of choose_lane8 rows against values written here; the launch plan of the warp
+// kernel (aof_warp_plan.hpp: warp_plan_make) on the cases of tests/warp_plan_ref.py, likewise; and fastdiv_make against the division it replaces, with the kernels' fast_div restated in 32-bit
 // arithmetic; the stream bank's bound per-stream tables (aof_bank_tables.hpp): binding, resolving for a push or an IMU call, the
 // sensor arguments of a round, case by case against literal values; and the flags of one per-stream table of OpticalFlowBank
 // (facade/src/bank_table.hpp) over runs of ticks.
@@ -31,6 +32,7 @@
 #include "aof_mavlink.hpp"
 #include "aof_small_plan.hpp"
 #include "aof_tile16_plan.hpp"
+#include "aof_warp_plan.hpp"
 #include "aof_xcd_remap.hpp"
 #include "bank_table.hpp"
 #include "optical_flow_rad.hpp"
@@ -386,6 +388,27 @@ static int print_tile16_plans(const char *path, int verdicts[9])
         std::printf("tile16 plan: %d %d %zu %d %d %d %lld %d %d %d %lld %d %d %d %d\n", p.verdict, p.refines, p.lds, p.attr, p.prune, p.refine,
                     (long long)p.total, p.overflow, p.front, p.refused, (long long)p.front_wgs, p.stx, p.sty, p.sx, p.sy);
         if (p.verdict >= 0 && p.verdict < 9) verdicts[p.verdict]++;
+        cases++;
+    }
+    std::fclose(f);
+    return cases;
+}
+
+// (d8) warp_plan_make on a case file, one call per line: w h n_frames cropped cropped_stride hist.  One line of fields per
+// case, in the order of warp_plan_ref.WARP_FIELDS; verdicts[]: the census.
+static int print_warp_plans(const char *path, int verdicts[3])
+{
+    std::FILE *f = std::fopen(path, "r");
+    if (!f) return -1;
+    int cases = 0;
+    long long w, h, n_frames, stride, hist;
+    unsigned long long cropped;
+    while (std::fscanf(f, "%lld %lld %lld %llu %lld %lld", &w, &h, &n_frames, &cropped, &stride, &hist) == 6) {
+        const aof::WarpPlan p = aof::warp_plan_make((int32_t)w, (int32_t)h, (int64_t)n_frames, (uintptr_t)cropped, (int64_t)stride, hist != 0);
+        std::printf("warp plan: %d %d %d %d %d %d %d %d %d %lld %lld %d %zu %d %d %lld %lld %d %d %lld\n", (int)p.verdict, p.nx, p.ny, p.strip_rows, p.nstrips,
+                    p.rows[0], p.rows[1], p.node_rows[0], p.node_rows[1], (long long)p.node_bytes[0], (long long)p.node_bytes[1], p.vec, p.lds, p.attr,
+                    p.zero_hist, (long long)p.items[0], (long long)p.items[1], p.trips[0], p.trips[1], (long long)p.wgs);
+        if (p.verdict >= 0 && p.verdict < 3) verdicts[p.verdict]++;
         cases++;
     }
     std::fclose(f);
@@ -876,6 +899,12 @@ int main(int argc, char **argv)
         std::printf("host selftest: tile16 plan: %d cases, verdicts %d %d %d %d %d %d %d %d %d\n", tile16, verdicts[0], verdicts[1], verdicts[2],
                     verdicts[3], verdicts[4], verdicts[5], verdicts[6], verdicts[7], verdicts[8]);
         std::printf("host selftest: choose lane8: %d rows equal to the values written, %d rows printed\n", written, chosen);
+    }
+    if (argc > 10) {
+        int verdicts[3] = {};
+        const int warp = print_warp_plans(argv[10], verdicts);
+        if (warp < 0) return 23;
+        std::printf("host selftest: warp plan: %d cases, verdicts %d %d %d\n", warp, verdicts[0], verdicts[1], verdicts[2]);
     }
     std::printf("host selftest: %d valid parameter sets, %d rejected\n", valid, bad);
     return valid > 1000 ? 0 : 11;

@@ -3,7 +3,8 @@ numpy model (tests/bank_warp_ref.py, held to aof_warp_host on the CPU by tests/t
 everything behind the warped crop against what exists already -- a twin bank with nothing bound, the CPU oracle's calcFlow
 chain fed the model's crops.  Sizes are the smallest that reach every path of the kernel: 64 x 64 out of 96 x 80 planes
 (16-byte stores), 20 x 12 (a lane per pixel; the width a multiple of neither 8 nor 16) and 16 x 136 (two strips: the
-histogram through atomics); S = 5.  Every camera buffer is allocated with slack behind camera_bytes."""
+histogram through atomics), and the edges of the launch plan as tests/warp_plan_ref.py lists them (WARP_CASES: second trips,
+node trips, a mask edge inside an item, a halved strip, the widest crops served and the first refused); S = 5.  Every camera buffer is allocated with slack behind camera_bytes."""
 import numpy as np
 import pytest
 
@@ -11,6 +12,7 @@ import bank_camera_ref as cref
 import bank_ref as ref
 import bank_warp_ref as wref
 import crop_source_ref as csr
+import warp_plan_ref as wplan
 from bank_ref import FX, FY
 from bank_rig import EINVAL, OFFSET, Guarded, put, same, untouched, up
 from bank_sensor_rig import SLACK, SensorRig, same_rigs, table_tensor
@@ -28,22 +30,29 @@ ORDER = [0, 1, 4, 3, 2]
 
 # ---- 1. the stateless form against the model ----
 
-SIZES = {"vector-64x64": (64, 64, 96, 80), "per-pixel-20x12": (20, 12, 44, 36), "two-strips-16x136": (16, 136, 40, 150)}
+CASES = {c["id"]: c for c in wplan.WARP_CASES}      # the edges of the launch plan (tests/warp_plan_ref.py names what each is there for)
+SIZES = {cid: (c["w"], c["h"], *c["plane"]) for cid, c in CASES.items()}
 FORMATS = (csr.GREY8, csr.LUMA16_LO, csr.Y10, csr.Y10P)
+WIDE_FORMATS = (csr.GREY8, csr.Y10P)
+RUNS = [(cid, fmt) for cid, c in CASES.items() for fmt in FORMATS if not c["wide"] or fmt in WIDE_FORMATS]
+FORMAT_IDS = {csr.GREY8: "grey8", csr.LUMA16_LO: "luma16-lo", csr.Y10: "y10", csr.Y10P: "y10p"}
 
 
-@pytest.mark.parametrize("fmt", FORMATS, ids=["grey8", "luma16-lo", "y10", "y10p"])
-@pytest.mark.parametrize("size", list(SIZES), ids=list(SIZES))
+@pytest.mark.parametrize("size,fmt", RUNS, ids=[f"{cid}-{FORMAT_IDS[fmt]}" for cid, fmt in RUNS])
 def test_ingest_warped_is_the_model_on_every_design(aof, gpu_device, size, fmt):
     """One frame per design (and one not warped, and one whose record is not valid) in one launch: planes of `fmt` at
     non-zero offsets with padded pitches in a noise buffer, into dirty guarded outputs; crops byte for byte, histograms as
-    exact integers, ok flags.  The refused frame: not read, its crop not written."""
+    exact integers, ok flags.  The refused frame: not read, its crop not written.  A case the plan refuses (a crop too
+    wide): EINVAL before any launch, no output byte and no ok flag touched."""
     import torch
+    case, plan = CASES[size], wplan.case_warp_plan(CASES[size])
     w, h, width, height = SIZES[size]
     rb = csr.row_bytes(fmt, width)
     x0, y0 = width // 2 - w // 2, height // 2 - h // 2
-    names = list(wref.designs(w, h, width, height, x0, y0)) + ["none", "refused"]
+    designs = wref.designs(w, h, width, height, x0, y0)
+    names = [k for k in designs if not case["wide"] or k in wplan.WIDE_DESIGNS] + ["none", "refused"]
     n = len(names)
+    assert n == wplan.case_frames(case)
     recs, cursor = np.zeros(n, csr.SENSOR_DTYPE), 0
     for i in range(n):
         off = cursor + 1 + i % 5
@@ -54,16 +63,25 @@ def test_ingest_warped_is_the_model_on_every_design(aof, gpu_device, size, fmt):
     assert [csr.valid(r, fmt, 1, w, h, nbytes) for r in recs] == [True] * (n - 1) + [False]
     buf = np.random.default_rng([n, w, fmt]).integers(0, 256, nbytes + SLACK, dtype=np.uint8)
     buf[::7] = 255                                                 # saturated bytes among the noise: counted in no bin
-    designs = wref.designs(w, h, width, height, x0, y0)
     none = designs["smooth-random"].copy()
     none[0, 0]["x"] = wref.NONE
     meshes = np.stack([designs[k] for k in names[:-2]] + [none, designs["barrel"]])
     points = up(gpu_device, meshes.view(np.uint8).reshape(-1))
     assert points.data_ptr() % 16 == 0
-    crops, hist, ok = Guarded(gpu_device, (n, h, w), skew=3 if w % 16 else 0), Guarded(gpu_device, (n, 40)), Guarded(gpu_device, (n,))
+    skew = case["skew"] or (3 if w % 16 else 0)
+    crops, hist, ok = Guarded(gpu_device, (n, h, w), skew=skew), Guarded(gpu_device, (n, 40)), Guarded(gpu_device, (n,))
+    assert crops.tensor.data_ptr() % 16 == skew and bool(plan["vec"]) == (w % 16 == 0 and skew == 0)
     formats = up(gpu_device, np.concatenate([[0xEE], np.full(n, fmt, np.uint8)]).astype(np.uint8))[1:]
-    aof.ingest_warped(up(gpu_device, buf), table_tensor(gpu_device, recs), points, w, h, camera_bytes=nbytes, cropped=crops.tensor,
-                      hist=hist.tensor.view(torch.int32), ok=ok.tensor, want_cropped=False, want_hist=False, formats=formats)
+    call = lambda: aof.ingest_warped(up(gpu_device, buf), table_tensor(gpu_device, recs), points, w, h, camera_bytes=nbytes, cropped=crops.tensor,
+                                     hist=hist.tensor.view(torch.int32), ok=ok.tensor, want_cropped=False, want_hist=False, formats=formats)
+    if plan["verdict"] != "ok":
+        with pytest.raises(aof.AofError) as e:
+            call()
+        torch.cuda.synchronize()
+        assert e.value.code == EINVAL, "a crop too wide"
+        assert untouched(crops.read()) and untouched(hist.read()) and untouched(ok.read()), "a refused call writes nothing"
+        return
+    call()
     torch.cuda.synchronize()
     assert ok.read().tolist() == [1] * (n - 1) + [0]
     got_c, got_h = crops.read(), hist.read().view("<u4")
@@ -71,10 +89,11 @@ def test_ingest_warped_is_the_model_on_every_design(aof, gpu_device, size, fmt):
         want = wref.warp(buf, recs[i], fmt, meshes[i], w, h)
         same(got_c[i], want, ("crop", name))
         same(got_h[i], wref.histogram(want), ("histogram", name))
+        assert name in ("identity", "none") or not np.array_equal(want, csr.crop(buf, recs[i], fmt, 1, w, h)), (name, "the mesh matters")
     assert np.array_equal(got_c[n - 2], csr.crop(buf, recs[n - 2], fmt, 1, w, h)), "not warped: the plain crop"
     assert untouched(got_c[n - 1]), "a refused frame: no byte of its crop is written"
     # its histogram: untouched where a workgroup owns a frame; zeros where several strips add to words zeroed in front of them
-    assert untouched(got_h[n - 1]) if h <= 128 else not got_h[n - 1].any()
+    assert not got_h[n - 1].any() if plan["zero_hist"] else untouched(got_h[n - 1])
 
 
 def test_ingest_warped_without_a_crop_or_without_a_histogram(aof, gpu_device):

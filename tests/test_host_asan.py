@@ -10,7 +10,8 @@ extreme shapes, likewise; the plan of the flat lane-per-block launches (csrc/aof
 tests/lane8_plan_ref.py, likewise, with xcd_remap (csrc/aof_xcd_remap.hpp, the text the kernels run) a permutation for every
 total up to 4 096 and equal to the model's at every probe; the plan of a batch, the per-launch choice of a flat 8x8 launch
 (csrc/aof_batch_plan.hpp: plan_batch, choose_lane8) and the launch plan of the 16x16 search (csrc/aof_tile16_plan.hpp: tile16_plan)
-on every case of tests/batch_plan_ref.py, likewise; fastdiv_make against the division it replaces; the stream bank's
+on every case of tests/batch_plan_ref.py, likewise; the launch plan of the warp kernel (csrc/aof_warp_plan.hpp: warp_plan_make) on
+every case of tests/warp_plan_ref.py and its list of extreme shapes, likewise; fastdiv_make against the division it replaces; the stream bank's
 bound per-stream tables (csrc/aof_bank_tables.hpp: what a binding call accepts, which tables a push uses and the order of its
 refusals) and the flags of one per-stream table of OpticalFlowBank (facade/src/bank_table.hpp) over runs of ticks, both
 against values written out in the selftest."""
@@ -22,6 +23,7 @@ import coarse_plan_ref as coarse
 import cols_plan_ref as ref
 import lane8_plan_ref as lane8
 import small_plan_ref as small
+import warp_plan_ref as warp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -55,8 +57,12 @@ def test_host_logic_is_clean_under_asan_ubsan(tmp_path):
     batch_listing.write_text("".join(batch.selftest_line(c) + "\n" for c in batch_cases))
     tile16_listing.write_text("".join(batch.tile16_line(c) + "\n" for c in tile16_cases))
     choose_listing.write_text("".join(batch.choose_line(r) + "\n" for r in choose_rows))
+    warp_cases = warp.WARP_CASES + warp.WARP_PLAN_ONLY
+    warp_listing = tmp_path / "warp_plan_cases.txt"
+    warp_listing.write_text("".join(warp.warp_selftest_line(c) + "\n" for c in warp_cases))
     r = subprocess.run([str(exe), str(listing), str(coarse_listing), str(pyramid_listing), str(small_listing), str(lane8_listing),
-                        str(xcd_listing), str(batch_listing), str(tile16_listing), str(choose_listing)], capture_output=True, text=True, timeout=300)
+                        str(xcd_listing), str(batch_listing), str(tile16_listing), str(choose_listing), str(warp_listing)], capture_output=True, text=True,
+                       timeout=300)
     assert r.returncode == 0, f"rc={r.returncode}\n{r.stdout}{r.stderr}"
     assert "valid parameter sets" in r.stdout
     assert "packer: 4012 frames equal to the facade's, lengths 52 and 56" in r.stdout
@@ -143,3 +149,15 @@ def test_host_logic_is_clean_under_asan_ubsan(tmp_path):
     census = [line for line in r.stdout.splitlines() if line.startswith("host selftest: batch plan:") or line.startswith("host selftest: tile16 plan:")]
     assert len(census) == 2 and all(int(v) > 0 for line in census for v in line.replace(",", "").split()[6:] if v.isdigit()), census
     assert "host selftest: choose lane8: 17 rows equal to the values written" in r.stdout
+    # warp_plan_make == the model, on every case of both lists; every verdict occurs
+    assert f"warp plan: {len(warp_cases)} cases" in r.stdout and len(warp_cases) >= 30 and len(warp.WARP_PLAN_ONLY) >= 20
+    plans = [line.split()[2:] for line in r.stdout.splitlines() if line.startswith("warp plan: ")]
+    assert len(plans) == len(warp_cases)
+    for c, got in zip(warp_cases, plans):
+        want = warp.warp_fields(warp.warp_plan(**warp.warp_plan_args(c)))
+        assert len(got) == len(want) == len(warp.WARP_FIELDS)
+        diff = {name: (int(g), w) for name, g, w in zip(warp.WARP_FIELDS, got, want) if int(g) != w}
+        assert not diff, (c["id"], diff)
+    assert {warp.warp_plan(**warp.warp_plan_args(c))["verdict"] for c in warp_cases} == set(warp.VERDICTS)
+    assert {(pl["vec"], pl["attr"], pl["zero_hist"]) for pl in (warp.warp_plan(**warp.warp_plan_args(c)) for c in warp_cases)} >= {
+        (1, 0, 0), (0, 0, 0), (1, 1, 0), (1, 0, 1), (0, 0, 1), (0, 1, 0)}
