@@ -77,14 +77,10 @@ constexpr int32_t kBankWarpFusedMaxStreams = 2048;
 constexpr int32_t kFusedMaxStreams[2][2] = {{kBankFusedMaxStreams, kBankBurstFusedMaxStreams},
                                             {kBankCameraFusedMaxStreams, kBankCameraBurstFusedMaxStreams}};
 
-struct Layout {
-    struct aof_bank_layout pub;
-    size_t flow_ws_bytes, flows;   // inside the bank: the engine's workspace is at pub.scratch, the pixel records at `flows`
-    int64_t stride, frame;
-    size_t staging, staging_hist;  // camera layout only: the tick's cropped frames and their raw histograms
-};
+}  // namespace
 
-int bank_layout(const aof_params *p, const aof_bank_params *bp, Layout *L)
+// (declared in aof_internal.hpp: the stream bank's motion field, aof_bank_field.cpp, finds the scratch region with it)
+int aof::bank_layout(const aof_params *p, const aof_bank_params *bp, BankLayout *L)
 {
     if (!p || !bp) return -EINVAL;
     const int rc = aof_params_check(p);
@@ -111,8 +107,10 @@ int bank_layout(const aof_params *p, const aof_bank_params *bp, Layout *L)
     return 0;
 }
 
+namespace {
+
 // The bank layout plus the staging region of the camera push; also everything about `cam` that needs no context.
-int camera_layout(const aof_params *p, const aof_bank_params *bp, const aof_bank_camera *cam, Layout *L)
+int camera_layout(const aof_params *p, const aof_bank_params *bp, const aof_bank_camera *cam, BankLayout *L)
 {
     if (!cam) return -EINVAL;
     const int rc = bank_layout(p, bp, L);
@@ -130,7 +128,7 @@ int camera_layout(const aof_params *p, const aof_bank_params *bp, const aof_bank
 }
 
 // Everything all entry points check about the bank itself (cam: the camera push, whose bank has a staging region).
-int check_bank(aof_ctx *ctx, const aof_bank_params *bp, const void *d_bank, size_t bank_bytes, Layout *L,
+int check_bank(aof_ctx *ctx, const aof_bank_params *bp, const void *d_bank, size_t bank_bytes, BankLayout *L,
                const aof_bank_camera *cam = nullptr, bool camera = false)
 {
     if (!ctx) return -EINVAL;
@@ -161,7 +159,7 @@ int check_tick(aof_ctx *ctx, const void *d_frames, const uint64_t *d_time_us, co
 }
 
 // The tick's arguments for the kernels of k_bank.hip (frames: the caller's tick buffer, or the staging region).
-BankArgs bank_args(const aof_bank_params *bp, const Layout &L, uint8_t *bank, const uint8_t *frames, const uint64_t *d_time_us,
+BankArgs bank_args(const aof_bank_params *bp, const BankLayout &L, uint8_t *bank, const uint8_t *frames, const uint64_t *d_time_us,
                    const uint8_t *d_active, const aof_gyro *d_gyro, aof_tick_record *d_records, uint8_t *d_mavlink,
                    uint8_t *d_mavlink_len, const aof_bank_stream *d_streams)
 {
@@ -263,7 +261,7 @@ struct Push {
 // `active` mask and has no `count`.
 int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank_bytes, const Push &p, void *stream)
 {
-    Layout L;
+    BankLayout L;
     int rc = check_bank(ctx, bp, d_bank, bank_bytes, &L, p.cam, p.camera);
     if (rc) return rc;
     int64_t round_stride = 0;
@@ -381,7 +379,7 @@ extern "C" {
 int aof_bank_layout(const aof_params *p, const aof_bank_params *bp, struct aof_bank_layout *out)
 {
     if (!out) return -EINVAL;
-    Layout L;
+    BankLayout L;
     const int rc = bank_layout(p, bp, &L);
     if (rc) return rc;
     *out = L.pub;
@@ -545,7 +543,7 @@ int aof_ingest_sensors_device(int32_t crop_width, int32_t crop_height, const uin
 int aof_bank_reset_device(aof_ctx *ctx, const aof_bank_params *bp, const uint8_t *d_mask, void *d_bank, size_t bank_bytes,
                           void *stream)
 {
-    Layout L;
+    BankLayout L;
     int rc = check_bank(ctx, bp, d_bank, bank_bytes, &L);
     if (rc) return rc;
     if ((rc = precheck(ctx))) return rc;
@@ -559,7 +557,7 @@ int aof_bank_camera_layout(const aof_params *p, const aof_bank_params *bp, const
                            struct aof_bank_layout *out, size_t *staging)
 {
     if (!out || !staging) return -EINVAL;
-    Layout L;
+    BankLayout L;
     const int rc = camera_layout(p, bp, cam, &L);
     if (rc) return rc;
     *out = L.pub;

@@ -13,9 +13,10 @@
 
 using namespace aof;
 
-namespace {
+// (the three below are declared in aof_internal.hpp: the stream bank's motion field, aof_bank_field.cpp, runs them too)
+namespace aof {
 
-bool bad_params(const aof_field_params *fp)
+bool field_bad_params(const aof_field_params *fp)
 {
     return !fp || fp->min_blocks < 3 || (fp->passes != 1 && fp->passes != 2) || (fp->exclude_reach != 0 && fp->exclude_reach != 1) ||
            !(fp->gate_px > 0.0f) || !std::isfinite(fp->gate_px);
@@ -87,7 +88,7 @@ void field_pair(const FieldGeom &g, const aof_block *blocks, const uint8_t *subd
     *out = field_publish(accepted, at_reach, (uint32_t)s1.n, &m1, (uint32_t)s1.n, false);
 }
 
-}  // namespace
+}  // namespace aof
 
 extern "C" {
 
@@ -108,7 +109,7 @@ int aof_field_batch_device(aof_ctx *ctx, const aof_field_params *fp, const aof_b
 {
     if (!ctx) return -EINVAL;
     if (!fp || !d_blocks || !d_flows || !d_fields) return ctx_fail(ctx, -EINVAL, "field: null params, block, flow or field pointer");
-    if (bad_params(fp)) return ctx_fail(ctx, -EINVAL, "field: min_blocks < 3, passes outside 1..2, exclude_reach outside 0..1 or a gate that is not > 0 and finite");
+    if (field_bad_params(fp)) return ctx_fail(ctx, -EINVAL, "field: min_blocks < 3, passes outside 1..2, exclude_reach outside 0..1 or a gate that is not > 0 and finite");
     if (n_pairs < 0 || n_pairs > 0x7FFFFFFF) return ctx_fail(ctx, -EINVAL, "field: n_pairs outside 0..2^31-1");
     if (!aligned(d_blocks, 4) || !aligned(d_flows, 4)) return ctx_fail(ctx, -EINVAL, "field: blocks and flows must be 4-byte aligned");
     if (!aligned(d_fields, 8)) return ctx_fail(ctx, -EINVAL, "field: the field records must be 8-byte aligned");
@@ -130,7 +131,7 @@ int aof_field_batch_device(aof_ctx *ctx, const aof_field_params *fp, const aof_b
 int aof_field_host(const aof_params *p, const aof_field_params *fp, const aof_block *blocks, const uint8_t *subdirs,
                    const aof_flow *flows, int64_t n_pairs, aof_field *out)
 {
-    if (!p || !blocks || !flows || !out || n_pairs < 0 || bad_params(fp)) return -EINVAL;
+    if (!p || !blocks || !flows || !out || n_pairs < 0 || field_bad_params(fp)) return -EINVAL;
     FieldGeom g;
     if (field_geom(p, fp, &g)) return -EINVAL;
     for (int64_t i = 0; i < n_pairs; i++)

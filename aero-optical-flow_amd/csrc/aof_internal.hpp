@@ -282,6 +282,15 @@ struct BankState {
                                // reset.  The plain push passes it through.
 };
 static_assert(sizeof(BankState) == 64, "one bank state record is 64 bytes");
+// The regions of a bank (aof_bank.cpp): aof_bank_layout's offsets and what the library keeps to itself.  -EINVAL for
+// parameters a push refuses (n_streams, frame_stride, focal lengths), or what aof_params_check / aof_workspace_layout say.
+struct BankLayout {
+    struct aof_bank_layout pub;
+    size_t flow_ws_bytes, flows;   // inside the bank: the engine's workspace is at pub.scratch, the pixel records at `flows`
+    int64_t stride, frame;
+    size_t staging, staging_hist;  // camera layout only: the tick's cropped frames and their raw histograms
+};
+int bank_layout(const aof_params *p, const aof_bank_params *bp, BankLayout *L);
 // What aof_bank_push_camera_device adds to a tick (include/aof.h, "sensor frames").  camera == nullptr: a plain tick.
 struct BankCamera {
     const uint8_t *camera;         // [S] sensor frames, stream s at + s * camera_stride; its crop starts `origin` bytes in
@@ -419,6 +428,13 @@ struct MavlinkRxArgs {
 };
 int launch_bank_mavlink_rx(const MavlinkRxArgs &a, void *stream);
 int launch_bank_mavlink_rx_reset(aof_mavlink_rx_state *state, const uint8_t *mask, uint32_t n_streams, void *stream);
+// The motion-field fit's host side (aof_field.cpp), for the stream bank's motion field (aof_bank_field.cpp): are the
+// parameters outside their ranges; the geometry of a configuration's level-0 grid, or -EINVAL where the fit does not serve
+// it; and the fit of one pair on host memory (flow: read for pred_x / pred_y).
+struct FieldGeom;                             // (aof_field_step.hpp)
+bool field_bad_params(const aof_field_params *fp);
+int field_geom(const aof_params *p, const aof_field_params *fp, FieldGeom *out);
+void field_pair(const FieldGeom &g, const aof_block *blocks, const uint8_t *subdirs, const aof_flow &flow, aof_field *out);
 // (aof_batch.cpp) the small-pair plan of n pairs, whatever n: true where one workgroup per pair can serve the
 // context's configuration and these buffers (flows: [n]; d_workspace: aof_workspace_layout(p, n))
 bool plan_small_batch(const aof_ctx *ctx, const uint8_t *prev, const uint8_t *cur, int64_t stride, int64_t n, aof_flow *flows,

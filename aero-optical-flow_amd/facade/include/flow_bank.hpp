@@ -19,6 +19,9 @@ struct aof_gyro;           // include/aof.h: gyro angles integrated over the int
 struct aof_exposure_command;   // include/aof.h: what the auto-exposure controller decided for a stream in a tick
 struct aof_bank_stream;        // include/aof.h: one stream's focal lengths, output rate, time offset and MAVLink identity
 struct aof_warp_point;         // include/aof.h: a node of a stream's warp mesh, a sensor-plane coordinate in 1/32 pixel
+struct aof_field_params;       // include/aof.h: the motion-field fit's parameters (blocks needed, passes, reach, gate)
+struct aof_field;              // include/aof.h: one pair's fit -- zoom, rotation, flow at the frame centre
+struct aof_bank_field_record;  // include/aof.h: a stream's motion field integrated over the rate limiter's window
 
 class OpticalFlowBank {
 public:
@@ -161,6 +164,23 @@ public:
 	// Returns 0; -ENOBUFS, the object unchanged, when the slot cannot hold n more bytes; -EINVAL for a bad stream
 	// index, a negative n, NULL bytes or without enableMavlinkRx().
 	int pushMavlink(int stream, const uint8_t *bytes, int n);
+
+	// The motion field (include/aof.h, "the stream bank's motion field"): zoom, rotation and the flow at the frame
+	// centre, fitted to every pair's block records and integrated per stream over the rate limiter's window -- one
+	// field per published message, for the camera that climbs or yaws.  enableField() allocates the per-stream state
+	// and the pinned result arrays and starts every stream's window over; fp: the fit's parameters, NULL =
+	// aof_field_params_default().  From then on push() and pushCamera() run aof_bank_field_device right behind the
+	// bank push (in front of the IMU call: it sees the limiter's own verdicts), and reset() starts the masked
+	// streams' windows over with the streams.  An object on which it was never called runs exactly as before.
+	// Returns 0, or a negative value: -EINVAL for a second call, for parameters outside their ranges or for an image
+	// size the fit does not serve (refused: the object is as it was), anything else as enableCamera().
+	int enableField(const aof_field_params *fp = 0);
+	// The last push's aof_bank_field_record [n_streams] (status >= 0: published with that many valid fits in the
+	// window; AOF_TICK_HELD, AOF_TICK_IDLE, AOF_TICK_BAD_SENSOR otherwise) and the last push's own per-pair fits,
+	// aof_field [n_streams] (all zero for a stream that ran no pair), in pinned memory; valid until the next push.
+	// NULL without enableField().
+	const aof_bank_field_record *fieldRecords() const;
+	const aof_field *fields() const;
 
 	inline int getStreams() const { return n_streams; }
 	inline int getImageWidth() const { return image_width; }

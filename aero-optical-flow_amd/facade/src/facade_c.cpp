@@ -157,6 +157,12 @@ int aof_facade_bank_push_mavlink(void *bank, int stream, const uint8_t *bytes, i
 {
 	return static_cast<OpticalFlowBank *>(bank)->pushMavlink(stream, bytes, n);
 }
+int aof_facade_bank_enable_field(void *bank, const void *field_params)
+{
+	return static_cast<OpticalFlowBank *>(bank)->enableField(static_cast<const aof_field_params *>(field_params));
+}
+const void *aof_facade_bank_field_records(void *bank) { return static_cast<OpticalFlowBank *>(bank)->fieldRecords(); }
+const void *aof_facade_bank_fields(void *bank) { return static_cast<OpticalFlowBank *>(bank)->fields(); }
 const void *aof_facade_bank_exposure_commands(void *bank) { return static_cast<OpticalFlowBank *>(bank)->exposureCommands(); }
 const void *aof_facade_bank_published(void *bank) { return static_cast<OpticalFlowBank *>(bank)->published(); }
 int aof_facade_bank_reset(void *bank, const uint8_t *mask) { return static_cast<OpticalFlowBank *>(bank)->reset(mask); }

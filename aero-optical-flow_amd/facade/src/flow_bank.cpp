@@ -32,7 +32,7 @@ double secondsSince(std::chrono::steady_clock::time_point t0)
 // Every allocation of one object, recorded where it is made: release() frees them all, the newest first.
 struct Allocations {
 	enum Kind { kDevice, kPinned, kOutbox };   // hipMalloc, hipHostMalloc, aof_outbox_alloc_host: each has its own free
-	struct { void *p; Kind kind; } list[30];   // (28 with every form on, 29 inside enableCamera())
+	struct { void *p; Kind kind; } list[34];   // (31 with every form on, 32 inside enableCamera())
 	int n;
 
 	bool get(void **p, size_t bytes, Kind kind)
@@ -144,6 +144,12 @@ struct OpticalFlowBank::Impl {
 	Staged bytes;            // u8 [n_streams][max_bytes], then their lengths u16 [n_streams]
 	size_t off_rx_len;
 	aof_mavlink_rx_state *d_rx_state;
+	// the motion field (enableField): the fit and its window behind every push
+	bool field;
+	aof_field_params field_params;
+	aof_bank_field_state *d_field_state;
+	aof_bank_field_record *field_records;   // pinned (aof_outbox_alloc_host): [n_streams]
+	aof_field *field_fits;                  // pinned (aof_outbox_alloc_host): [n_streams]
 	// the per-stream tables; nothing of one is copied or bound before its first setter
 	//   kStreams  (setStream...()): aof_bank_stream [n_streams], the shadow records start from the constructor's values
 	//   kSensors  (setStreamSensor()): aof_bank_sensor [n_streams], allocated by enableCamera() like the next two; the
@@ -279,7 +285,8 @@ bool OpticalFlowBank::Impl::waitIdle()
 }
 
 // Masked streams (mask[s] != 0; NULL: all) start over, enqueued on the object's stream: their part of the bank, their
-// IMU state if the form is on (imu_too: or is being turned on) and their receive state if that is on.  What the pinned
+// IMU state if the form is on (imu_too: or is being turned on), their receive state and the window of their motion field
+// if those are on.  What the pinned
 // queues hold for them belongs to their past and is dropped with it.  The caller waits (waitIdle()).
 int OpticalFlowBank::Impl::startOver(const uint8_t *mask, bool imu_too)
 {
@@ -292,6 +299,7 @@ int OpticalFlowBank::Impl::startOver(const uint8_t *mask, bool imu_too)
 	int rc = failed(aof_bank_reset_device(ctx, &bp, d_mask, d_bank, bank_bytes, stream));
 	if (!rc && imu_too) rc = failed(aof_bank_imu_reset_device(ctx, (int)S, d_mask, imu_offset0, d_imu_state, stream));
 	if (!rc && rx) rc = failed(aof_bank_mavlink_rx_reset_device(ctx, (int)S, d_mask, d_rx_state, stream));
+	if (!rc && field) rc = failed(aof_bank_field_reset_device(ctx, (int)S, d_mask, d_field_state, stream));
 	if (rc) return rc;
 	for (size_t s = 0; s < S; s++) {
 		if (mask && !mask[s]) continue;
@@ -520,6 +528,10 @@ int OpticalFlowBank::Impl::tick(bool sensor_frames, const uint64_t *img_time_us,
 			   : aof_bank_push_device(ctx, &push_bp, stage.d, d_times, d_active, d_gyro, d_bank, bank_bytes, d_records,
 						  push_mavlink, push_lens, stream);
 	if (failed(rc)) return rc;
+	// 4b. the motion field, on the limiter's own verdicts: its records land in pinned memory in front of the collect's tag
+	if (field && (rc = failed(aof_bank_field_device(ctx, &push_bp, &field_params, d_bank, bank_bytes, d_records, d_field_state,
+							  field_fits, field_records, stream))) != 0)
+		return rc;
 	// 5. the IMU call, in place on the push's records
 	if (imu && (rc = takeImu()) != 0) return rc;
 	// 6. the exposure control: its commands land in pinned memory in front of the collect's tag
@@ -707,6 +719,48 @@ int OpticalFlowBank::enableImu(int max_samples, uint64_t offset0)
 	m->imu = true;
 	return 0;
 }
+
+int OpticalFlowBank::enableField(const aof_field_params *fp)
+{
+	if (!engineOk()) return -1;
+	Impl *m = _m;
+	if (m->field) return refuse(-EINVAL, "enableField() was already called");
+	aof_field_params mine;
+	aof_field_params_default(&mine);
+	if (fp) mine = *fp;
+	// the fit's own checks, on host memory: one stream whose tick record says "no frame" reads nothing else
+	aof_params p;
+	if (aof_get_params(m->ctx, &p)) return fail(-EIO, aof_last_error(m->ctx));
+	aof_block no_block;
+	aof_tick_record no_frame;
+	aof_bank_field_state scratch_state;
+	aof_bank_field_record scratch_record;
+	aof_bank_params one = m->bp;
+	one.n_streams = 1;
+	std::memset(&no_block, 0, sizeof(no_block));
+	std::memset(&no_frame, 0, sizeof(no_frame));
+	std::memset(&scratch_state, 0, sizeof(scratch_state));
+	no_frame.quality = AOF_TICK_IDLE;
+	if (aof_bank_field_host(&p, &one, NULL, &mine, &no_block, NULL, &no_frame, &scratch_state, NULL, &scratch_record))
+		return refuse(-EINVAL, "enableField(): parameters outside their ranges, or an image size the fit does not serve");
+	if (!m->waitIdle()) return -ETIMEDOUT;
+	const size_t S = m->S;
+	if (!m->mem.get((void **)&m->d_field_state, S * sizeof(aof_bank_field_state), Allocations::kDevice) ||
+	    !m->mem.get((void **)&m->field_records, S * sizeof(aof_bank_field_record), Allocations::kOutbox) ||
+	    !m->mem.get((void **)&m->field_fits, S * sizeof(aof_field), Allocations::kOutbox))
+		return fail(-ENOMEM, "device or pinned memory for the motion field could not be allocated");
+	std::memset(m->field_records, 0, S * sizeof(aof_bank_field_record));
+	std::memset(m->field_fits, 0, S * sizeof(aof_field));
+	m->field_params = mine;
+	if (m->failed(aof_bank_field_reset_device(m->ctx, n_streams, NULL, m->d_field_state, m->stream))) return -EIO;
+	if (!m->waitIdle()) return -ETIMEDOUT;
+	m->field = true;
+	return 0;
+}
+
+const aof_bank_field_record *OpticalFlowBank::fieldRecords() const { return _m && _m->field ? _m->field_records : NULL; }
+
+const aof_field *OpticalFlowBank::fields() const { return _m && _m->field ? _m->field_fits : NULL; }
 
 int OpticalFlowBank::pushImu(int stream, uint64_t time_usec, float xgyro, float ygyro, float zgyro)
 {

@@ -1234,8 +1234,9 @@ int aof_bank_mavlink_rx_host(const aof_mavlink_rx_params *rp, const uint8_t *byt
  * with fabs(U - ((tU + a*X) - b*Y)) <= g and fabs(V - ((tV + b*X) + a*Y)) <= g, g = 2.0 * (double)gate_px; if M2 fits,
  * its model is published and AOF_FIELD_REFIT set, else M1's.  If M1 does not fit the record is all zero except
  * `accepted` and `at_reach`.
- * Not here: the per-call path (aof_flow_pair_host, aof_stream_push_host), the sequence pipeline, the stream bank and the
- * facade classes publish no field. */
+ * The stream bank publishes the same fit per stream and limiter window ("the stream bank's motion field", below;
+ * OpticalFlowBank::enableField).  Not here: the per-call path (aof_flow_pair_host, aof_stream_push_host), the sequence
+ * pipeline and the per-call facade classes publish no field. */
 typedef struct aof_field_params {
     int32_t min_blocks;     /* >= 3, default 8 */
     int32_t passes;         /* 1 | 2, default 2 */
@@ -1266,6 +1267,14 @@ int aof_field_batch_device(aof_ctx *ctx, const aof_field_params *fp, const aof_b
 /* The same function on host memory, a plain loop: no device, no context.  -EINVAL as above (alignment aside). */
 int aof_field_host(const aof_params *p, const aof_field_params *fp, const aof_block *blocks, const uint8_t *subdirs,
                    const aof_flow *flows, int64_t n_pairs, aof_field *out);
+
+/* ---- the stream bank's motion field: zoom, rotation and centre flow per stream, integrated over the limiter's window ----
+ * aof_bank_field_reset_device, aof_bank_field_device and aof_bank_field_host with their two records: declared, with the
+ * normative text of the rule, in aof_bank_field.h beside this file, which is part of this header and comes in with it.  It is
+ * a file of its own for as long as the Python package does not bind the three calls: the package's EXPORTS is the census of
+ * the functions THIS file declares (tests/test_abi.py), and tests/bank_field_rig.py carries their binding until the package
+ * takes it over with a re-recorded surface -- then the text moves here. */
+#include "aof_bank_field.h"
 
 /* ---- measurement ----
  * With profiling on, every launch is bracketed by HIP events on the stream it

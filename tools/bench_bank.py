@@ -88,6 +88,13 @@ centre crop and repeated around it, so that a mesh reaching outside the plain cr
         launches), us per burst; the sensor frames of the burst legs carry noise around the crop.
     W, WI, WB1 and WB2 assert through aof_bank_last_path that they timed the path they name.  The yardstick of W is leg L
     of the build before the kernel, loaded through AOF_LIB in the same session (--legs P,L,F).
+With --field, the stream bank's motion field behind the plain tick (aof_bank_field_device; the records and prototypes are
+tests/bank_field_rig.py's), on both bank paths (leg names end in the path, 1 or 2), S = 64 .. 4 096:
+    T   the tick alone, pipelined (with AOF_LIB, on a build without the call: the yardstick of T on this build);
+    F   tick + aof_bank_field_device, pipelined: F - T prices the fit and the window's step in a stream that runs on;
+    H   what a host does without the call: tick + asynchronous device-to-host copies of the block records, the
+        sub-directions and the tick records into pinned memory + stream synchronise + aof_bank_field_host: every step ends
+        with the host holding the records.
 K1 / K2 are the legs --camera runs under those names (leg_camera); --per-sensor --legs K1,K2 runs them alone, which is how
 two builds of the library are compared in turn in one session.
 Every leg settles for about 0.2 s of untimed ticks, then times at least --ticks ticks and at least --seconds seconds
@@ -105,7 +112,8 @@ between the repeats is the run-to-run spread a difference between legs has to be
     python tools/bench_bank.py --binning --repeats 3 > profiles/bank_binning_ab.txt
     python tools/bench_bank.py --raw-formats --repeats 3 > profiles/bank_raw_formats_ab.txt
     python tools/bench_bank.py --warp --repeats 3 > profiles/bank_warp_ab.txt
-    python tools/bench_bank.py --warp --repeats 3 --streams 64,256,1024,2048,4096 > profiles/bank_warp_one_launch_ab.txt"""
+    python tools/bench_bank.py --warp --repeats 3 --streams 64,256,1024,2048,4096 > profiles/bank_warp_one_launch_ab.txt
+    python tools/bench_bank.py --field --repeats 3 > profiles/bank_field_ab.txt"""
 import argparse
 import ctypes as C
 import importlib
@@ -1614,6 +1622,113 @@ def per_stream_sweep(a, dev):
             print(line)
 
 
+def leg_field(p, S, path, inp, dev, a, kind):
+    """One of T / F / H of --field on `path`: the plain tick, alone, with the field call behind it, or with the copies, the
+    synchronise and the host function behind it."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import bank_field_rig as rig
+    eng = aof.FlowEngine(p, 0)
+    eng.set_bank_path(path)
+    bp = aof.bank_params(S, FX, FY, 15, 5_000_000, 1, 100, 0)
+    bank = eng.bank_create(bp, dev)
+    recs = torch.empty((S, 48), dtype=torch.uint8, device=dev)
+    wire = torch.empty((S, 56), dtype=torch.uint8, device=dev)
+    lens = torch.empty(S, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    fn, ctx, bpp = aof.lib.aof_bank_push_device, eng._ctx, C.byref(bp)
+    calls = [(inp.frames[k].data_ptr(), inp.times[k].data_ptr()) for k in range(RING)]
+    rest = (None, inp.gyro.data_ptr(), bank.buffer.data_ptr(), bank.buffer.numel(), recs.data_ptr(), wire.data_ptr(), lens.data_ptr(), stream)
+    sync = torch.cuda.synchronize
+    after = None
+    if kind != "T":
+        lib = rig.bind(aof)
+        fp = aof.field_params()
+        fpp = C.byref(fp)
+        nb = eng.nblocks(0)
+        out = torch.empty((S, 48), dtype=torch.uint8, device=dev)
+        fields = torch.empty((S, 64), dtype=torch.uint8, device=dev)
+    if kind == "F":
+        state = torch.zeros((S, 64), dtype=torch.uint8, device=dev)
+        assert rig.reset(aof, eng, state) == 0
+        tail = (bank.buffer.data_ptr(), bank.buffer.numel(), recs.data_ptr(), state.data_ptr(), fields.data_ptr(), out.data_ptr(), stream)
+
+        def after():
+            return lib.aof_bank_field_device(ctx, bpp, fpp, *tail)
+    if kind == "H":
+        at_b, at_s = rig.scratch_offsets(aof, p, bank.layout, S)
+        d_blocks, d_sub = bank.buffer[at_b:at_b + 4 * S * nb], bank.buffer[at_s:at_s + S * nb]
+        h_blocks = torch.empty(4 * S * nb, dtype=torch.uint8).pin_memory()
+        h_sub = torch.empty(S * nb, dtype=torch.uint8).pin_memory()
+        h_recs = torch.empty((S, 48), dtype=torch.uint8).pin_memory()
+        h_state = np.zeros(S, rig.STATE_DTYPE)
+        h_out, h_fields = np.zeros(S, rig.RECORD_DTYPE), np.zeros(S, aof.FIELD_DTYPE)
+        pp = C.byref(p)
+        host = (h_blocks.data_ptr(), h_sub.data_ptr() if p.subpixel else None, h_recs.data_ptr(), h_state.ctypes.data, h_fields.ctypes.data,
+                h_out.ctypes.data)
+
+        def after():
+            h_blocks.copy_(d_blocks, non_blocking=True)
+            if p.subpixel:
+                h_sub.copy_(d_sub, non_blocking=True)
+            h_recs.copy_(recs, non_blocking=True)
+            sync()
+            return lib.aof_bank_field_host(pp, bpp, None, fpp, *host)
+
+    def step(i):
+        f, t = calls[i % RING]
+        rc = fn(ctx, bpp, f, t, *rest)
+        if not rc and after is not None:
+            rc = after()
+        if rc:
+            raise aof.AofError(rc, aof.lib.aof_last_error(ctx).decode())
+    res = timed(step, sync, a.ticks, a.seconds, a.settle)
+    r = aof.ticks_view(recs)
+    assert (r["quality"] >= aof.TICK_HELD).all() and (r["frame"] > a.ticks).all(), "the timed ticks were real ticks"
+    if kind == "F":
+        o = out.cpu().numpy().reshape(-1).view(rig.RECORD_DTYPE)
+        assert (o["frame"] == r["frame"]).all() and (np.frombuffer(state.cpu().numpy(), rig.STATE_DTYPE)["published"] > 0).all(), "the field call ran behind every tick"
+    if path and hasattr(aof.lib, "aof_bank_last_path"):
+        assert eng.last_bank_path() == path, (kind, "timed path", eng.last_bank_path(), "meant", path)
+    eng.close()
+    return res
+
+
+def field_sweep(a, dev):
+    print("# legs (the digit: bank path 1 / 2): T the plain tick alone; F tick + aof_bank_field_device, pipelined; H tick + copies of block "
+          "records, sub-directions and tick records to pinned memory + synchronise + aof_bank_field_host (MAVLink frames on, all streams active, gyro)")
+    print("# us = microseconds per tick (host clock; T and F: ticks ending in a synchronise every 256; H: every tick ends with the host holding the records)")
+    bound = hasattr(aof.lib, "aof_bank_field_device")      # (AOF_LIB may name a build without the call: T legs only)
+    kinds = ["T", "F", "H"] if bound else ["T"]
+    legs = [(k + str(path), k, path) for path in (1, 2) for k in kinds]
+    if a.legs is not None:
+        legs = [leg for leg in legs if leg[0] in a.legs.split(",")]
+    sizes = [int(s) for s in a.streams.split(",")]
+    results = {}
+    for rep in range(a.repeats):
+        for cfg in a.configs.split(","):
+            p = params_of(cfg)
+            for S in sizes:
+                inp = Inputs(p, S, dev)
+                for name, kind, path in legs:
+                    sec, n = leg_field(p, S, path, inp, dev, a, kind)
+                    results.setdefault((cfg, S, name), []).append(sec)
+                    print(f"rep {rep} {cfg:11s} S={S:6d} {name:3s} {sec * 1e6:10.2f} us  ({n} ticks)", flush=True)
+                del inp
+                torch.cuda.empty_cache()
+    print("# ---- summary (median of the repeats; p10..p90 of the repeats in us) ----")
+    for cfg in a.configs.split(","):
+        for S in sizes:
+            m = {n: float(np.median(results[(cfg, S, n)])) for n, _, _ in legs}
+            line = f"{cfg:11s} S={S:6d}  " + "  ".join(
+                f"{n} {m[n] * 1e6:9.2f} us ({np.percentile(results[(cfg, S, n)], 10) * 1e6:.2f}..{np.percentile(results[(cfg, S, n)], 90) * 1e6:.2f})"
+                for n in m)
+            for path in (1, 2):
+                if all(k + str(path) in m for k in ("T", "F", "H")):
+                    t, f, h = (m[k + str(path)] for k in ("T", "F", "H"))
+                    line += f"  F{path}-T{path} {(f - t) * 1e6:6.2f} us  F{path}/T{path} {f / t:5.3f}  F{path}/H{path} {f / h:5.3f}"
+            print(line)
+
+
 def per_sensor_sweep(a, dev):
     print("# legs: K1/K2 camera tick on the scalars of aof_bank_camera on path 1/2, S1/S2 the same tick with S aof_bank_sensor "
           "records equal to aof_bank_sensor_from_camera bound (exposure records, de-rotation, MAVLink frames on, all streams active)")
@@ -1678,10 +1793,12 @@ def main():
                     "paths (G1, ..., D2; --legs G1,G2 runs the yardstick alone, for a build without the formats through AOF_LIB)")
     ap.add_argument("--warp", action="store_true", help="the camera tick with warp meshes bound: legs P, I, L, F, U, W, WI, WB1, WB2 on 640 x 480 frames (--legs P,F "
                     "runs the legs that need no mesh alone, for a build without the call through AOF_LIB)")
+    ap.add_argument("--field", action="store_true", help="the motion field behind the plain tick: legs T, F, H on both bank paths (--legs T1,T2 "
+                    "runs the tick alone, for a build without the call through AOF_LIB)")
     ap.add_argument("--forms", default="plain,camera", help="--burst: entry points to sweep")
     ap.add_argument("--input-bytes-max", type=float, default=24 * 2**30, help="--burst: sizes whose K rounds of input exceed this are skipped")
     a = ap.parse_args()
-    if a.legs is None and not a.per_sensor and not a.pixel_formats and not a.binning and not a.raw_formats and not a.warp:
+    if a.legs is None and not a.per_sensor and not a.pixel_formats and not a.binning and not a.raw_formats and not a.warp and not a.field:
         a.legs = "T0,T1,T2,C,B"
     if a.burst and a.ticks == ap.get_default("ticks"):
         a.ticks = 1000           # (frame rounds)
@@ -1691,6 +1808,8 @@ def main():
         a.streams = "64,256,1024,2048"
     if a.warp and a.streams == ap.get_default("streams"):
         a.streams = "64,256,1024,2048"
+    if a.field and a.streams == ap.get_default("streams"):
+        a.streams = "64,256,1024,4096"
     if a.exposure_control and a.streams == ap.get_default("streams"):
         a.streams = "64,1024,4096"
     if (a.imu or a.mavlink_rx) and a.streams == ap.get_default("streams"):
@@ -1704,6 +1823,8 @@ def main():
     print(f"# device: {torch.cuda.get_device_name(0)}")
     if not a.no_marker:
         print(f"# class marker: exhaustive C2 K2 (1 024 VGA pairs) {class_marker(dev):.4f} ms")
+    if a.field:
+        return field_sweep(a, dev)
     if a.per_stream:
         return per_stream_sweep(a, dev)
     if a.per_sensor:
