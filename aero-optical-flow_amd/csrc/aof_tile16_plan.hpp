@@ -1,7 +1,9 @@
 // The launch plan of the 16x16 search (DESIGN.md "Kernels": K2 tile16): which configurations k_search_tile16 serves, its
 // dynamic LDS, the instantiation, the n_pairs * ny grid, and the kernel in front of an ADAPTIVE launch -- the probe with its
 // sample strides, or the forced-verdict fill.  Host only, no HIP: tests/native/host_selftest.cpp holds tile16_plan to the
-// model of tests/batch_plan_ref.py.  The kernels' own address arithmetic stays in the kernels (k_search_tile16.hip).
+// model of tests/batch_plan_ref.py.  The kernels' own address arithmetic stays in the kernels (k_search_tile16.hip); what a
+// workgroup stages, from which bytes into which, and its loops' trips are restated by tests/tile16_rows_ref.py, whose byte
+// extents are held inside the frame arrays and inside tile16_lds() for every width, origin and predictor.
 #pragma once
 
 #include <cstddef>

@@ -15,7 +15,8 @@ namespace aof {
 // [0, total) for every total from 1 to 4 096 and for the workgroup count of every flat 8x8 case, with the logical ids
 // of an XCD contiguous, and the sanitizer self-test holds THIS function to that restatement value by value for every
 // total up to 4 096 and at the ends of the large ones.  The 16x16 kernel's launches are covered by the same proof
-// (their total is a workgroup count like any other); its own plan is not.
+// (their total is a workgroup count like any other); its own block-row plan by tests/tile16_rows_ref.py, whose device
+// cases launch one and two block rows per pair at totals off the multiples of 8.
 AOF_HD_INLINE uint32_t xcd_remap(uint32_t b, uint32_t total)
 {
     const uint32_t q = total / 8, r = total % 8, xcd = b % 8, slot = b / 8;

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import tile16_probe_ref as probe_ref
-from tile16_rig import JUNK, PATTERN, assert_matches, oracle_refs, run
+from tile16_rig import JUNK, PATTERN, assert_matches, hard_batch, oracle_refs, run
 
 pytestmark = pytest.mark.gpu
 
@@ -23,41 +23,6 @@ OPTION_SETS = {
     "two_level_equalised": dict(pyramid_levels=2, mean_subtract=1),
     "two_level_half_pixel": dict(pyramid_levels=2, subpixel=1),
 }
-
-
-def hard_batch(synth, W, H, two_level):
-    """(prevs, curs, names): translations, sensor noise, unrelated / identical / flat / half-flat frames, ties on periodic
-    textures, a checkerboard against its inverse, a saturating brightness step; two-level batches add a horizontal-only
-    motion (the predictor's column shift and tail guard) and one near the +-17 reach (windows pushed out of the frame)."""
-    reach = 17 if two_level else 8
-    pairs = []
-    for k, noise in enumerate((0, 0, 3, 8, 16, 40)):
-        p, c, _ = synth.make_pair(W, H, reach, 4100 + k, noise=noise)
-        pairs.append((f"noise{noise}" if noise else f"clean{k}", p, c))
-    rng = np.random.default_rng(41)
-    tex = synth.make_pair(W, H, reach, 4110)[0]
-    pairs.append(("unrelated", tex, rng.integers(0, 256, (H, W), dtype=np.uint8)))
-    pairs.append(("identical", tex, tex.copy()))
-    flat = np.full((H, W), 90, np.uint8)
-    pairs.append(("flat", flat, flat.copy()))
-    half = rng.integers(0, 256, (H, W), dtype=np.uint8)
-    half[:, : W // 2] = 90
-    pairs.append(("half_flat", half, half.copy()))
-    px2 = np.zeros((H, W), np.uint8); px2[:, 0::2] = 200
-    py2 = np.zeros((H, W), np.uint8); py2[0::2, :] = 150
-    dots = np.zeros((H, W), np.uint8); dots[0::4, 0::4] = 255
-    pairs += [("period2_x", px2, px2.copy()), ("period2_y", py2, py2.copy()), ("dots", dots, dots.copy())]
-    yy, xx = np.mgrid[0:H, 0:W]
-    chk = (((xx // 16 + yy // 16) % 2) * 255).astype(np.uint8)
-    pairs.append(("checker_inverse", chk, 255 - chk))
-    p, c, _ = synth.make_pair(W, H, reach, 4120, shift=(3, -2), brightness=120)
-    pairs.append(("bright_step", p, c))
-    if two_level:
-        p, c, _ = synth.make_pair(W, H, reach, 4130, shift=(13, 0))
-        pairs.append(("horizontal", p, c))
-        p, c, _ = synth.make_pair(W, H, reach, 4140, shift=(-16, 17))
-        pairs.append(("reach", p, c))
-    return np.stack([q[1] for q in pairs]), np.stack([q[2] for q in pairs]), [q[0] for q in pairs]
 
 
 def forced_words(verdicts, n):
