@@ -9,9 +9,12 @@
 #include <cstdint>
 #include <cstring>
 
+#include "aof_bank_args.hpp"
 #include "aof_bank_sensor_rule.hpp"
 #include "aof_bank_tables.hpp"
-#include "aof_internal.hpp"
+#include "aof_engine_args.hpp"
+#include "aof_host.hpp"
+#include "aof_ingest_args.hpp"
 #include "aof_small_plan.hpp"
 #include "aof_warp_step.hpp"
 
@@ -79,7 +82,7 @@ constexpr int32_t kFusedMaxStreams[2][2] = {{kBankFusedMaxStreams, kBankBurstFus
 
 }  // namespace
 
-// (declared in aof_internal.hpp: the stream bank's motion field, aof_bank_field.cpp, finds the scratch region with it)
+// (declared in aof_bank_args.hpp: the stream bank's motion field, aof_bank_field.cpp, finds the scratch region with it)
 int aof::bank_layout(const aof_params *p, const aof_bank_params *bp, BankLayout *L)
 {
     if (!p || !bp) return -EINVAL;
@@ -278,13 +281,14 @@ int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank
             return ctx_fail(ctx, -EINVAL, "bank camera: exposure records and de-rotated pairs must be 4-byte aligned");
     }
     // the bound per-stream arrays this push uses (aof_bank_tables.hpp)
+    BankCtx &bc = bank_ctx(ctx);
     BankTablesUsed tables;
-    if (const char *what = bank_tables_for_push(bank_tables(ctx), bp->n_streams, p.camera, round_stride, &tables))
+    if (const char *what = bank_tables_for_push(bc.tables, bp->n_streams, p.camera, round_stride, &tables))
         return ctx_fail(ctx, -EINVAL, what);
     // the meshes, if the push is on sensor frames and some are bound (aof_set_bank_warps)
     const aof_warp_point *warps = nullptr;
     if (p.camera)
-        if (const char *what = bank_warps_for_push(bank_warps(ctx), bp->n_streams, tables, &warps)) return ctx_fail(ctx, -EINVAL, what);
+        if (const char *what = bank_warps_for_push(bc.warps, bp->n_streams, tables, &warps)) return ctx_fail(ctx, -EINVAL, what);
     // before the first launch: a faulted or wedged context, or a thread on another device, must not touch the bank
     if ((rc = precheck(ctx))) return rc;
 
@@ -304,7 +308,7 @@ int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank
     // which path: the one-launch kernel where the configuration (and these buffers) allow it and the bank is small
     // enough for a workgroup per stream to pay, or because the caller asked for it.  With warps bound the one-launch
     // kernel is the tick with the warp inside it, which also needs the mesh's nodes in LDS (warp_one_launch_fits)
-    const int path = bank_path(ctx);
+    const int path = bc.path;
     SmallArgs sm;
     const bool fused = path != 2 &&
                        plan_small_batch(ctx, a.bank_frames, cur, L.stride, bp->n_streams, flows, bank + L.pub.scratch, &sm) &&
@@ -321,13 +325,13 @@ int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank
                                         b.count ? k : 0))
                 return ctx_fail(ctx, -EIO, "bank warped tick launch failed");
         }
-        bank_last_path(ctx) = 1;
+        bc.last_path = 1;
         return 0;
     }
     if (fused) {
         if (p.burst ? launch_bank_burst(sm, a, b, stream, sen) : launch_bank_tick(sm, a, stream, sen))
             return ctx_fail(ctx, -EIO, p.burst ? "bank burst launch failed" : "bank tick launch failed");
-        bank_last_path(ctx) = 1;
+        bc.last_path = 1;
         return 0;
     }
     // composed, per round and in order on the one stream: (camera forms) the crops and raw histograms of all S sensor
@@ -360,7 +364,7 @@ int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank
         if (rc) return rc;
         if (launch_bank_commit(r, stream, b.count, b.count ? k : 0, bank_sensors_of_round(tables, base))) return ctx_fail(ctx, -EIO, "bank commit launch failed");
     }
-    bank_last_path(ctx) = 2;
+    bc.last_path = 2;
     return 0;
 }
 
@@ -368,7 +372,7 @@ int bank_push(aof_ctx *ctx, const aof_bank_params *bp, void *d_bank, size_t bank
 int bind_table(aof_ctx *ctx, BankTable which, const void *array, int32_t n_streams, uint64_t camera_bytes = 0)
 {
     if (!ctx) return -EINVAL;
-    if (const char *what = bank_tables_bind(&bank_tables(ctx), which, array, n_streams, camera_bytes)) return ctx_fail(ctx, -EINVAL, what);
+    if (const char *what = bank_tables_bind(&bank_ctx(ctx).tables, which, array, n_streams, camera_bytes)) return ctx_fail(ctx, -EINVAL, what);
     return 0;
 }
 
@@ -389,14 +393,14 @@ int aof_bank_layout(const aof_params *p, const aof_bank_params *bp, struct aof_b
 int aof_set_bank_path(aof_ctx *ctx, int path)
 {
     if (!ctx || path < 0 || path > 2) return -EINVAL;
-    set_bank_path(ctx, path);
+    bank_ctx(ctx).path = path;
     return 0;
 }
 
 int aof_bank_last_path(const aof_ctx *ctx)
 {
     if (!ctx) return -EINVAL;
-    return bank_last_path(const_cast<aof_ctx *>(ctx));
+    return bank_ctx(const_cast<aof_ctx *>(ctx)).last_path;
 }
 
 int aof_bank_warp_one_launch(const aof_params *p, int64_t *lds_bytes)

@@ -8,9 +8,11 @@
 #include <cerrno>
 #include <cstring>
 
+#include "aof_bank_args.hpp"
+#include "aof_bank_calls.hpp"
 #include "aof_bank_field_step.hpp"
 #include "aof_bank_tables.hpp"
-#include "aof_internal.hpp"
+#include "aof_host.hpp"
 
 using namespace aof;
 
@@ -64,7 +66,7 @@ int aof_bank_field_device(aof_ctx *ctx, const aof_bank_params *bp, const aof_fie
     if (!aligned(d_records, 4) || !aligned(d_out, 4)) return ctx_fail(ctx, -EINVAL, "bank field: tick and output records must be 4-byte aligned");
     if (!aligned(d_state, 8) || !aligned(d_fields, 8)) return ctx_fail(ctx, -EINVAL, "bank field: state and fields must be 8-byte aligned");
     // a bound per-stream array (aof_set_bank_streams) gives every stream its own focal lengths; it is for one stream count
-    const BankTables &tables = bank_tables(ctx);
+    const BankTables &tables = bank_ctx(ctx).tables;
     if (bank_table_differs(tables, kBankStreams, bp->n_streams))
         return ctx_fail(ctx, -EINVAL, "bank field: n_streams differs from the array bound with aof_set_bank_streams");
     if (bank_bytes < L.pub.total_bytes) return ctx_fail(ctx, -ENOSPC, "bank field: bank smaller than aof_bank_layout().total_bytes");

@@ -6,7 +6,9 @@
 // stream's state: every float operation is the host's, in the host's order.
 #pragma once
 
+#include "aof_bank_args.hpp"
 #include "aof_derotate.hpp"
+#include "aof_engine_args.hpp"
 #include "aof_exposure_step.hpp"
 #include "aof_flow_small.hpp"
 #include "aof_bank_sensor_rule.hpp"   // (behind the HIP runtime's qualifiers)

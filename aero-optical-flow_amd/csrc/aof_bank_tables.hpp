@@ -9,7 +9,10 @@
 
 #include <cstdint>
 
-#include "aof_internal.hpp"
+#include "aof.h"
+#include "aof_bank_args.hpp"     // BankSensors
+#include "aof_host.hpp"          // aligned
+#include "aof_ingest_args.hpp"   // IngestSensors
 
 namespace aof {
 
@@ -141,5 +144,15 @@ inline IngestSensors ingest_sensors_of_round(const BankTablesUsed &u, uint64_t b
 {
     return IngestSensors{u.sensors, base, u.camera_bytes, ok, u.formats, u.bins};
 }
+
+// The stream bank's section of the context (a member of aof_ctx), and the one way to it for the host files that are
+// built without the HIP runtime and so cannot see aof_ctx itself (defined beside the context's life, aof_capi.hip).
+struct BankCtx {
+    int path;                   // aof_set_bank_path: 0 the library chooses, 1 the one-launch tick kernel, 2 the composed path
+    int last_path;              // aof_bank_last_path: 0 no push yet, 1 the last accepted push ran one-launch kernel(s), 2 the composed launches
+    BankTables tables;          // aof_set_bank_streams / _sensors / _pixel_formats / _binning: the caller's per-stream arrays
+    BankWarps warps;            // aof_set_bank_warps: the caller's meshes (beside the tables)
+};
+BankCtx &bank_ctx(aof_ctx *ctx);
 
 }  // namespace aof

@@ -5,6 +5,8 @@
 
 #include "aof_batch_plan.hpp"
 #include "aof_ctx.hpp"
+#include "aof_engine_args.hpp"
+#include "aof_host.hpp"
 
 using namespace aof;
 
@@ -179,12 +181,6 @@ bool plan_small_params(const aof_params *p, SmallArgs *sm)
     *sm = P.sm;
     return P.small_class;
 }
-
-int bank_path(const aof_ctx *ctx) { return ctx->bank_path; }
-int &bank_last_path(aof_ctx *ctx) { return ctx->bank_last_path; }
-void set_bank_path(aof_ctx *ctx, int path) { ctx->bank_path = path; }
-BankTables &bank_tables(aof_ctx *ctx) { return ctx->bank; }
-BankWarps &bank_warps(aof_ctx *ctx) { return ctx->warps; }
 
 // Would a sequence-view call (frames viewed twice, n_pairs = frames - 1) run K1 as a pass of its own?  The sequence
 // pipeline asks, because its ingest kernel can leave K1's outputs (pixel sums at ws + L.sums, one level-1 frame per

@@ -8,7 +8,7 @@
 
 #include "aof_coarse_plan.hpp"
 #include "aof_cols8_plan.hpp"
-#include "aof_internal.hpp"
+#include "aof_engine_args.hpp"
 #include "aof_lane8_plan.hpp"
 #include "aof_small_plan.hpp"
 #include "aof_tile16_plan.hpp"

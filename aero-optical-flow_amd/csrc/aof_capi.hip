@@ -7,7 +7,12 @@
 #include <new>
 #include <thread>
 
+#include "aof_bank_calls.hpp"
+#include "aof_bank_tables.hpp"
 #include "aof_ctx.hpp"
+#include "aof_engine_args.hpp"
+#include "aof_host.hpp"
+#include "aof_ingest_args.hpp"
 
 using namespace aof;
 
@@ -88,6 +93,8 @@ int precheck(aof_ctx *ctx)
 }
 
 int ctx_fail(aof_ctx *ctx, int code, const char *what) { return fail(ctx, code, "%s", what); }
+
+BankCtx &bank_ctx(aof_ctx *ctx) { return ctx->bank; }
 
 }  // namespace aof
 

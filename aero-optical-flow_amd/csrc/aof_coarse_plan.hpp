@@ -7,7 +7,8 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "aof_internal.hpp"
+#include "aof_engine_args.hpp"
+#include "aof_fastdiv.hpp"
 
 namespace aof {
 

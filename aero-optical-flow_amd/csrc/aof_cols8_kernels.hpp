@@ -21,7 +21,7 @@
 
 #include "aof_cols8_plan.hpp"
 #include "aof_device.hpp"
-#include "aof_internal.hpp"
+#include "aof_engine_args.hpp"
 #include "aof_lane8.hpp"
 #include "aof_reduce.hpp"
 #include "aof_refine.hpp"
@@ -241,7 +241,7 @@ __device__ __forceinline__ void cols_walk(const SearchArgs &a, const ColsPlan &p
         for (int s = 0; s < 8; s++) win[s] = win[s + 8];
     }
     if constexpr (VOTE) pending.flush(*votes, a.hist_range, pair);
-    // one workgroup in report.stride tells the host how its first wave fared (aof_internal.hpp: PruneReport)
+    // one workgroup in report.stride tells the host how its first wave fared (aof_engine_args.hpp: PruneReport)
     if (report.slots && threadIdx.x == 0 && wg % report.stride == 0)
         __hip_atomic_store(report.slots + wg / report.stride, (report.launch_no << 16) | ((uint32_t)paying << 8) | (uint32_t)seen,
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

@@ -3,7 +3,8 @@
 
 #include <cstdint>
 
-#include "aof_internal.hpp"
+#include "aof_engine_args.hpp"
+#include "aof_fastdiv.hpp"
 #include "aof_small_plan.hpp"   // lane8_plan_supported
 
 namespace aof {

@@ -4,9 +4,11 @@
 
 #include <hip/hip_runtime.h>
 #include <chrono>
-#include "aof_bank_tables.hpp"
-#include "aof_batch_plan.hpp"   // BatchConfig, AdaptiveSearch
-#include "aof_internal.hpp"
+#include "aof_bank_calls.hpp"    // OutboxCounter
+#include "aof_bank_tables.hpp"   // BankCtx
+#include "aof_batch_plan.hpp"    // BatchConfig, AdaptiveSearch
+#include "aof_engine_args.hpp"   // SmallArgs, Tile16Verdicts
+#include "aof_resident.hpp"      // ResidentBox
 
 namespace aof {
 
@@ -112,10 +114,7 @@ struct aof_ctx {
     aof::BatchConfig cfg;       // params, grids, CUs of `device`, search mode and the kernel-choice switches: what the batch plan reads
     int device;
     char err[256];
-    int bank_path;              // aof_set_bank_path: 0 the library chooses, 1 the one-launch tick kernel, 2 the composed path
-    int bank_last_path;         // aof_bank_last_path: 0 no push yet, 1 the last accepted push ran one-launch kernel(s), 2 the composed launches
-    aof::BankTables bank;       // aof_set_bank_streams / _sensors / _pixel_formats / _binning: the caller's per-stream arrays (aof_bank_tables.hpp)
-    aof::BankWarps warps;       // aof_set_bank_warps: the caller's meshes (beside the tables, aof_bank_tables.hpp)
+    aof::BankCtx bank;          // the stream bank's section: the path switch and what the aof_set_bank_* calls have bound (bank_ctx, aof_bank_tables.hpp)
     bool graph_disabled;        // per-call graphs switched off, or a capture failed once: stay on the plain path
     bool capturing;             // a per-call graph is being captured (no event timing)
     bool wedged;                // a bounded wait for the device ran out: every later call fails, destroy frees nothing

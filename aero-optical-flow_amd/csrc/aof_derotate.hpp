@@ -6,8 +6,8 @@
 // translation unit's default contraction and fuse after inlining.)
 #pragma once
 
+#include "aof.h"
 #include "aof_device.hpp"
-#include "aof_internal.hpp"
 
 namespace aof {
 

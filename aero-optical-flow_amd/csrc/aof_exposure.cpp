@@ -7,8 +7,10 @@
 #include <cmath>
 #include <cstring>
 
+#include "aof_bank_calls.hpp"
 #include "aof_ctx.hpp"
 #include "aof_exposure_step.hpp"
+#include "aof_host.hpp"
 
 using namespace aof;
 

@@ -8,12 +8,13 @@
 #include <cmath>
 #include <cstring>
 
+#include "aof_engine_args.hpp"
 #include "aof_field_step.hpp"
-#include "aof_internal.hpp"
+#include "aof_host.hpp"
 
 using namespace aof;
 
-// (the three below are declared in aof_internal.hpp: the stream bank's motion field, aof_bank_field.cpp, runs them too)
+// (the three below are declared in aof_host.hpp: the stream bank's motion field, aof_bank_field.cpp, runs them too)
 namespace aof {
 
 bool field_bad_params(const aof_field_params *fp)

@@ -20,6 +20,7 @@
 #pragma once
 
 #include "aof_device.hpp"
+#include "aof_fastdiv.hpp"
 #include "aof_field_step.hpp"
 
 namespace aof {

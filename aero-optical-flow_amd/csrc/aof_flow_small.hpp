@@ -6,7 +6,7 @@
 
 #include "aof_crop.hpp"
 #include "aof_device.hpp"
-#include "aof_internal.hpp"
+#include "aof_engine_args.hpp"
 #include "aof_reduce.hpp"
 #include "aof_refine.hpp"
 #include "aof_sad.hpp"

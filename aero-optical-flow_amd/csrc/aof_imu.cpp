@@ -6,7 +6,10 @@
 #include <cerrno>
 #include <cstring>
 
+#include "aof_bank_calls.hpp"
+#include "aof_bank_tables.hpp"
 #include "aof_ctx.hpp"
+#include "aof_host.hpp"
 #include "aof_imu_step.hpp"
 #include "aof_mavlink.hpp"
 
@@ -56,7 +59,7 @@ int aof_bank_imu_device(aof_ctx *ctx, const aof_imu_params *ip, const aof_imu_sa
         return ctx_fail(ctx, -EINVAL, what);
     // a bound per-stream array (aof_set_bank_streams) gives every stream its own identity; it is for one stream count
     const aof_bank_stream *d_streams = nullptr;
-    if (const char *what = bank_tables_for_imu(ctx->bank, ip->n_streams, &d_streams)) return ctx_fail(ctx, -EINVAL, what);
+    if (const char *what = bank_tables_for_imu(bank_ctx(ctx).tables, ip->n_streams, &d_streams)) return ctx_fail(ctx, -EINVAL, what);
     if (const int rc = precheck(ctx)) return rc;
 
     ImuArgs a;

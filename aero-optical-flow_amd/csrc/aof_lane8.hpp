@@ -4,7 +4,7 @@
 #pragma once
 
 #include "aof_device.hpp"
-#include "aof_internal.hpp"
+#include "aof_engine_args.hpp"
 #include "aof_refine.hpp"
 #include "aof_sad.hpp"
 

@@ -34,7 +34,7 @@
 #pragma once
 
 #include "aof_device.hpp"
-#include "aof_internal.hpp"
+#include "aof_engine_args.hpp"
 #include "aof_lane8.hpp"
 #include "aof_reduce.hpp"
 #include "aof_refine.hpp"
@@ -108,7 +108,7 @@ __device__ __forceinline__ void search_chunks(const SearchArgs &a, uint32_t item
         }
     }
     if constexpr (PRUNE) {
-        // one workgroup in report->stride tells the host how its first wave fared (aof_internal.hpp: PruneReport)
+        // one workgroup in report->stride tells the host how its first wave fared (aof_engine_args.hpp: PruneReport)
         if (report->slots && threadIdx.x == 0 && wg % report->stride == 0)
             __hip_atomic_store(report->slots + wg / report->stride,
                                (report->launch_no << 16) | ((uint32_t)chunks_paying << 8) | (uint32_t)chunks_seen,

@@ -4,7 +4,7 @@
 
 #include <cstdint>
 
-#include "aof_internal.hpp"
+#include "aof_engine_args.hpp"
 
 namespace aof {
 

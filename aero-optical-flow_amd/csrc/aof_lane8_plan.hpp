@@ -7,7 +7,7 @@
 
 #include <cstdint>
 
-#include "aof_internal.hpp"
+#include "aof_engine_args.hpp"
 #include "aof_small_plan.hpp"   // kThreads: block size of the chunk walk and of large flat launches; lane8_plan_supported
 
 namespace aof {

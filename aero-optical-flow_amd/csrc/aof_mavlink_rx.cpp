@@ -5,7 +5,9 @@
 #include <cerrno>
 #include <cstring>
 
+#include "aof_bank_calls.hpp"
 #include "aof_ctx.hpp"
+#include "aof_host.hpp"
 #include "aof_mavlink_rx_step.hpp"
 
 using namespace aof;

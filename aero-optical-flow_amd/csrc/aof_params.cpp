@@ -5,7 +5,7 @@
 #include <cstring>
 
 #include "aof_exposure_step.hpp"
-#include "aof_internal.hpp"
+#include "aof_engine_args.hpp"
 
 namespace aof {
 

@@ -5,6 +5,8 @@
 #include <cstring>
 
 #include "aof_ctx.hpp"
+#include "aof_engine_args.hpp"
+#include "aof_resident.hpp"
 
 using namespace aof;
 

@@ -6,7 +6,10 @@
 #include <cerrno>
 #include <cstring>
 
-#include "aof_internal.hpp"
+#include "aof_engine_args.hpp"
+#include "aof_host.hpp"
+#include "aof_ingest_args.hpp"
+#include "aof_sequence_args.hpp"
 #include "aof_math.h"
 
 using namespace aof;

@@ -7,7 +7,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "aof_internal.hpp"
+#include "aof_engine_args.hpp"
 
 namespace aof {
 

@@ -10,7 +10,7 @@
 #include <cstdint>
 
 #include "aof_hd.hpp"
-#include "aof_internal.hpp"
+#include "aof_engine_args.hpp"
 
 namespace aof {
 

@@ -7,7 +7,8 @@
 #include <cstdint>
 
 #include "aof_bank_tables.hpp"
-#include "aof_internal.hpp"
+#include "aof_host.hpp"
+#include "aof_ingest_args.hpp"
 #include "aof_warp_step.hpp"
 
 using namespace aof;
@@ -80,7 +81,7 @@ int aof_warp_mesh_from_lens(const aof_params *p, const aof_lens *lens, aof_warp_
 int aof_set_bank_warps(aof_ctx *ctx, const aof_warp_point *d_points, int32_t n_streams)
 {
     if (!ctx) return -EINVAL;
-    if (const char *what = bank_warps_bind(&bank_warps(ctx), d_points, n_streams)) return ctx_fail(ctx, -EINVAL, what);
+    if (const char *what = bank_warps_bind(&bank_ctx(ctx).warps, d_points, n_streams)) return ctx_fail(ctx, -EINVAL, what);
     return 0;
 }
 

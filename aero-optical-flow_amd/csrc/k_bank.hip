@@ -22,7 +22,9 @@
 // as is the launchers' check of the plan against the bank (bank_plan_fits); the tick goes out through the one launcher
 // of the one-workgroup class (launch_small_class, aof_flow_small.hpp).  On the host all four push forms are one path
 // (bank_push, aof_bank.cpp).
+#include "aof_bank_args.hpp"
 #include "aof_bank_stream.hpp"
+#include "aof_engine_args.hpp"
 
 namespace aof {
 

@@ -12,7 +12,9 @@
 //                  frame load.
 // Every record comes from bank_tail_step, every idle record from bank_idle, the gate, the histogram and the MSV from
 // aof_bank_stream.hpp: the functions k_bank_tick runs.
+#include "aof_bank_args.hpp"
 #include "aof_bank_stream.hpp"
+#include "aof_engine_args.hpp"
 
 namespace aof {
 

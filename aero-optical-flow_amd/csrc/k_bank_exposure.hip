@@ -12,8 +12,8 @@
 // one access each; gfx950 takes wider accesses at any 4-byte address.
 #include <hip/hip_runtime.h>
 
+#include "aof_bank_calls.hpp"
 #include "aof_exposure_step.hpp"
-#include "aof_internal.hpp"
 
 namespace aof {
 

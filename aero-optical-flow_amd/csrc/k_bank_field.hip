@@ -16,6 +16,7 @@
 // kept in pinned host memory are there for a host that sees the tag of a collect call enqueued behind this launch.
 #include "aof_device.hpp"   // (the HIP runtime first: the rule headers' qualifiers are its)
 #include "aof_bank_field_step.hpp"
+#include "aof_fastdiv.hpp"
 #include "aof_field_fit.hpp"
 
 namespace aof {

@@ -19,6 +19,7 @@
 // entry point's alignment rules); gfx950 takes wider accesses at those addresses, so the compiler may join them.
 #include <hip/hip_runtime.h>
 
+#include "aof_bank_calls.hpp"
 #include "aof_device.hpp"
 #include "aof_imu_step.hpp"
 #include "aof_mavlink.hpp"

@@ -23,7 +23,7 @@
 //     stored behind the round, and the kernel ends with a system-scope release behind its stores.
 #include <hip/hip_runtime.h>
 
-#include "aof_internal.hpp"
+#include "aof_bank_calls.hpp"
 #include "aof_mavlink_rx_step.hpp"
 
 namespace aof {

@@ -17,7 +17,8 @@
 // Two instantiations: the sources 16- / 8-byte aligned (16-byte loads), or only as aligned as the push demands.
 #include <hip/hip_runtime.h>
 
-#include "aof_internal.hpp"
+#include "aof_bank_calls.hpp"
+#include "aof_host.hpp"
 
 namespace aof {
 

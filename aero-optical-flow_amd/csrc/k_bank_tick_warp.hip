@@ -22,7 +22,9 @@
 // (count, round) are k_bank_commit's: a stream is active iff round < count[s]; with a null count the `active` mask
 // decides.  A warped camera burst of K rounds on this path is K launches with round_args' pointers (aof_bank.cpp): one
 // launch per round, byte-identical to K ticks by construction.
+#include "aof_bank_args.hpp"
 #include "aof_bank_stream.hpp"
+#include "aof_engine_args.hpp"
 #include "aof_warp_gather.hpp"
 
 namespace aof {

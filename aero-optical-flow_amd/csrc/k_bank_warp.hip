@@ -15,6 +15,8 @@
 // waves add theirs to the workgroup's ten words, and a workgroup that owns its frame stores them; several strips add
 // with integer atomics to words the launcher zeroed.
 #include "aof_bank_stream.hpp"   // (bank_sensor, kThreads)
+#include "aof_engine_args.hpp"   // (launch_zero_words)
+#include "aof_ingest_args.hpp"   // (WarpArgs, launch_warp)
 #include "aof_warp_gather.hpp"   // (aof_warp_step.hpp; sample)
 #include "aof_warp_plan.hpp"     // (the launch plan and its constants: kLaneItems)
 

@@ -24,7 +24,7 @@
 
 #include "aof_coarse_plan.hpp"
 #include "aof_device.hpp"
-#include "aof_internal.hpp"
+#include "aof_engine_args.hpp"
 #include "aof_lab_hooks.hpp"
 #include "aof_reduce.hpp"
 #include "aof_sad.hpp"

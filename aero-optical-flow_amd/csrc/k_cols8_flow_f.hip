@@ -1,6 +1,7 @@
 // K2 k_flow_lane8_cols<false>: the column walk with the reduction in its launch (aof_set_reduce_fusion).
 // ONE kernel per translation unit: aof_lane8_kernels.hpp says why.
 #include "aof_cols8_kernels.hpp"
+#include "aof_engine_args.hpp"
 #include "aof_lane8_launch.hpp"
 
 namespace aof {

@@ -1,6 +1,7 @@
 // K2 k_search_lane8_cols<false>: the pruned 8x8 search as a column walk on dense grids -- the C2 / C3 headline kernel (K3 follows).
 // ONE kernel per translation unit: aof_lane8_kernels.hpp says why.
 #include "aof_cols8_kernels.hpp"
+#include "aof_engine_args.hpp"
 #include "aof_lane8_launch.hpp"
 
 namespace aof {

@@ -1,6 +1,7 @@
 // Gyro de-rotation of a batch of flow records (include/aof.h).  The arithmetic of one
 // record is derotate_flow (aof_derotate.hpp), which the stream bank's tail lane runs as well.
 #include "aof_derotate.hpp"
+#include "aof_engine_args.hpp"
 
 namespace aof {
 

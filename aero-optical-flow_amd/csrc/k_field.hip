@@ -7,6 +7,7 @@
 //   * k_field<64, 1>: a wave per pair, four pairs per workgroup, for grids of at most 256 blocks (one quad of records per
 //     lane); k_field<256, 5>: a workgroup per pair above that, looping over the pair's quads, whatever their number.
 // Inputs are only read; a pair's 64-byte record, stored by lane 0 of its group, is the only store.
+#include "aof_fastdiv.hpp"
 #include "aof_field_fit.hpp"
 
 namespace aof {

@@ -21,7 +21,9 @@
 // kernels bit for bit.
 // Every kernel of this class -- the three forms here, the stream bank's tick and burst -- goes out through the one
 // launcher launch_small_class (aof_flow_small.hpp): the support check, the dynamic-LDS attribute, the launch.
+#include "aof_engine_args.hpp"
 #include "aof_flow_small.hpp"
+#include "aof_resident.hpp"
 
 namespace aof {
 

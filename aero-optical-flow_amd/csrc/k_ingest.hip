@@ -22,6 +22,8 @@
 // window's place, row pitch and origin are the frame's own: bank_sensor (aof_bank_stream.hpp), the function the bank's
 // kernels decide with.  A workgroup whose frame's record forbids the read leaves before its first load.
 #include "aof_bank_stream.hpp"   // (kThreads = 256 is the one-workgroup class's: one table entry per lane below)
+#include "aof_engine_args.hpp"   // (launch_zero_words)
+#include "aof_ingest_args.hpp"
 
 namespace aof {
 

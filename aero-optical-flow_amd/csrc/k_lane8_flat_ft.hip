@@ -1,5 +1,6 @@
 // K2 k_flow_lane8_flat<false, true>: the same scan with the reduction in its launch (aof_set_reduce_fusion).
 // ONE kernel per translation unit: aof_lane8_kernels.hpp says why.
+#include "aof_engine_args.hpp"
 #include "aof_lane8_kernels.hpp"
 #include "aof_lane8_launch.hpp"
 

@@ -1,5 +1,6 @@
 // K2 k_flow_lane8<true>: grids of 8..256 blocks, a workgroup owns whole pairs and finalises their flow records.
 // ONE kernel per translation unit: aof_lane8_kernels.hpp says why.
+#include "aof_engine_args.hpp"
 #include "aof_lane8_kernels.hpp"
 #include "aof_lane8_launch.hpp"
 

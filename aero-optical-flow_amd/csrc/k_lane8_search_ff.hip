@@ -1,5 +1,6 @@
 // K2 k_search_lane8<false, false>: the C2 headline's exhaustive scan: no half-pixel step, no equalisation code.
 // ONE kernel per translation unit: aof_lane8_kernels.hpp says why.
+#include "aof_engine_args.hpp"
 #include "aof_lane8_kernels.hpp"
 #include "aof_lane8_launch.hpp"
 

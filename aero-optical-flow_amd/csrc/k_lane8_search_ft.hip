@@ -1,5 +1,6 @@
 // K2 k_search_lane8<false, true>: exhaustive scan with mean equalisation (C3 level 0 on images that do not prune, level-1 searches of the split coarse passes).
 // ONE kernel per translation unit: aof_lane8_kernels.hpp says why.
+#include "aof_engine_args.hpp"
 #include "aof_lane8_kernels.hpp"
 #include "aof_lane8_launch.hpp"
 

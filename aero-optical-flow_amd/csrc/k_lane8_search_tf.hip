@@ -1,5 +1,6 @@
 // K2 k_search_lane8<true, false>: exhaustive scan with the half-pixel refinement in the lane.
 // ONE kernel per translation unit: aof_lane8_kernels.hpp says why.
+#include "aof_engine_args.hpp"
 #include "aof_lane8_kernels.hpp"
 #include "aof_lane8_launch.hpp"
 

@@ -1,5 +1,6 @@
 // K2 k_search_lane8<true, true>: exhaustive scan with half-pixel refinement and mean equalisation.
 // ONE kernel per translation unit: aof_lane8_kernels.hpp says why.
+#include "aof_engine_args.hpp"
 #include "aof_lane8_kernels.hpp"
 #include "aof_lane8_launch.hpp"
 

@@ -8,7 +8,7 @@
 // HBM-bound: reads W*H, writes W*H/4 per frame.
 #include "aof_coarse_plan.hpp"
 #include "aof_device.hpp"
-#include "aof_internal.hpp"
+#include "aof_engine_args.hpp"
 
 namespace aof {
 

@@ -12,7 +12,7 @@
 // of exactly-representable integers and two correctly-rounded divisions
 // (__fdiv_rn), so it is bit-identical to the host arithmetic of the oracle.
 #include "aof_device.hpp"
-#include "aof_internal.hpp"
+#include "aof_engine_args.hpp"
 #include "aof_reduce.hpp"
 
 namespace aof {

@@ -8,7 +8,7 @@
 // loads, and feeds them to the shared v_lerp_u8 arithmetic of aof_refine.hpp.  Blocks the
 // search skipped or rejected get direction 8 (none).
 #include "aof_device.hpp"
-#include "aof_internal.hpp"
+#include "aof_engine_args.hpp"
 #include "aof_refine.hpp"
 
 namespace aof {

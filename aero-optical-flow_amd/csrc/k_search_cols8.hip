@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "aof_cols8_plan.hpp"
-#include "aof_internal.hpp"
+#include "aof_engine_args.hpp"
 #include "aof_lane8_launch.hpp"
 
 namespace aof {

@@ -13,7 +13,7 @@
 // This kernel favours generality; the 8x8/+-4 configurations the metric is quoted on
 // run k_search_lane8 instead, 16x16/+-8 runs k_search_tile16.
 #include "aof_device.hpp"
-#include "aof_internal.hpp"
+#include "aof_engine_args.hpp"
 
 namespace aof {
 

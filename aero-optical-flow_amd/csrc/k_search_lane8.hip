@@ -4,7 +4,8 @@
 // (k_lane8_*.hip) together with the launch function declared below.
 #include <hip/hip_runtime.h>
 
-#include "aof_internal.hpp"
+#include "aof_engine_args.hpp"
+#include "aof_fastdiv.hpp"
 #include "aof_lane8_launch.hpp"
 #include "aof_lane8_plan.hpp"    // the plan of the flat launches, the slices of every launch here
 #include "aof_small_plan.hpp"    // the grouped plan

@@ -15,7 +15,8 @@
 // Half-pixel configurations stage one more cur row either side and refine the accepted blocks
 // behind the search, out of the same tile (<.., REFINE>, below).
 #include "aof_device.hpp"
-#include "aof_internal.hpp"
+#include "aof_engine_args.hpp"
+#include "aof_fastdiv.hpp"
 #include "aof_refine.hpp"
 #include "aof_sad.hpp"
 #include "aof_tile16_plan.hpp"   // kTile16Threads, kSide, the probe's constants and probe_samples; the launch plan

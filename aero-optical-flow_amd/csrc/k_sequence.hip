@@ -18,8 +18,8 @@
 // associative: the host sums in that order), converts, fills and packs.  Every float operation is the host's,
 // in the host's order: the frames are byte-identical to driving the C++ facade frame by frame.
 #include "aof_device.hpp"
-#include "aof_internal.hpp"
 #include "aof_mavlink.hpp"
+#include "aof_sequence_args.hpp"
 #include "aof_math.h"
 
 namespace aof {

@@ -21,7 +21,7 @@ SEARCH_KINDS = ("tile16", "lane8_group", "lane8", "generic")    # enum SearchKin
 COARSE_KINDS = ("none", "fused", "k1")                          # enum CoarseKind
 EXHAUSTIVE, PRUNED, ADAPTIVE = 0, 1, 2                          # AOF_SEARCH_*
 CAPTURES = ("none", "active", "unknown")                        # enum Capture
-# csrc/aof_tile16_plan.hpp, csrc/aof_internal.hpp
+# csrc/aof_tile16_plan.hpp, csrc/aof_engine_args.hpp
 T16_THREADS, T16_LDS_LIMIT, T16_ATTR_ABOVE, FILL_THREADS, MAX_FORCED = 512, 156 * 1024, 64 * 1024, 256, 8
 T16_VERDICTS = ("ok", "tile", "grid", "width", "stride", "prev", "cur", "frame", "lds")   # enum Tile16Verdict, in the order tested
 FRONTS = ("none", "probe", "fill")                              # enum Tile16Front

@@ -7,7 +7,7 @@ A case is a frame size (through its dense grid), a pair count and the form of th
 takes, the census of tests/test_cols_plan_ref.py fails on a path no device case takes."""
 import numpy as np
 
-# csrc/aof_cols8_plan.hpp, csrc/aof_ctx.hpp, csrc/aof_internal.hpp
+# csrc/aof_cols8_plan.hpp, csrc/aof_ctx.hpp, csrc/aof_engine_args.hpp
 THREADS, MAX_ROWS, MIN_ROWS, WAVES_WANTED, WAVE_SLOTS, MAX_UNITS = 256, 8, 2, 3072, 4096, 0x7FFF0000
 VOTE_PAIRS, PRUNE_MIN_CHUNKS = 2048, 2048
 TILE, SEARCH = 8, 4
@@ -16,7 +16,7 @@ TILE, SEARCH = 8, 4
 # ---- the plan ----------------------------------------------------------------------------------------------------
 
 def fastdiv_make(d):
-    """(mul, shift) of aof_internal.hpp's fastdiv_make."""
+    """(mul, shift) of aof_fastdiv.hpp's fastdiv_make."""
     if d == 0:
         return 0, 0
     l = 0

@@ -24,7 +24,7 @@ import numpy as np
 
 from small_plan_ref import blocks, grid_for_level, lane8_supported, rounded_mean
 
-# csrc/aof_lane8_plan.hpp, csrc/aof_internal.hpp, csrc/aof_ctx.hpp
+# csrc/aof_lane8_plan.hpp, csrc/aof_engine_args.hpp, csrc/aof_ctx.hpp
 THREADS, SMALL_THREADS, MAX_ITEMS, LARGE_ITEMS = 256, 64, 0x7FFF0000, 6 * 256 * 1024
 WALK_WGS, WALK_MAX, PRUNE_SLOTS, PRUNE_MIN_CHUNKS = 1536, 8, 256, 2048
 VOTE_PAIRS, VOTE_STRIDE = 2048, 128

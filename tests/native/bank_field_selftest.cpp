@@ -10,9 +10,11 @@
 #include <cstring>
 #include <vector>
 
+#include "aof_bank_args.hpp"
+#include "aof_bank_calls.hpp"
 #include "aof_bank_field_step.hpp"
 #include "aof_bank_tables.hpp"
-#include "aof_internal.hpp"
+#include "aof_host.hpp"
 
 // what the device-side entry points of aof_field.cpp and aof_bank_field.cpp link against: not called here
 namespace aof {
@@ -22,8 +24,8 @@ int launch_field(const FieldArgs &, void *) { return 1; }
 int launch_bank_field(const BankFieldArgs &, void *) { return 1; }
 int launch_bank_imu_reset(aof_imu_state *, const uint8_t *, uint32_t, uint64_t, void *) { return 1; }
 int bank_layout(const aof_params *, const aof_bank_params *, BankLayout *) { return -EINVAL; }
-static BankTables no_tables;
-BankTables &bank_tables(aof_ctx *) { return no_tables; }
+static BankCtx no_bank;
+BankCtx &bank_ctx(aof_ctx *) { return no_bank; }
 }  // namespace aof
 extern "C" int aof_get_params(const aof_ctx *, aof_params *) { return -EINVAL; }
 

@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "aof_field_step.hpp"
-#include "aof_internal.hpp"
+#include "aof_host.hpp"
 
 // what aof_field.cpp's device-side entry point links against: not called here
 namespace aof {

@@ -22,12 +22,16 @@
 #include <cstring>
 
 #include "aof.h"
+#include "aof_bank_args.hpp"
 #include "aof_bank_tables.hpp"
 #include "aof_batch_plan.hpp"
 #include "aof_coarse_plan.hpp"
 #include "aof_cols8_plan.hpp"
+#include "aof_engine_args.hpp"
 #include "aof_exposure_step.hpp"
-#include "aof_internal.hpp"
+#include "aof_fastdiv.hpp"
+#include "aof_host.hpp"
+#include "aof_ingest_args.hpp"
 #include "aof_lane8_plan.hpp"
 #include "aof_mavlink.hpp"
 #include "aof_small_plan.hpp"

@@ -14,12 +14,14 @@
 #include <vector>
 
 #include "aof_bank_tables.hpp"
+#include "aof_host.hpp"
+#include "aof_ingest_args.hpp"
 #include "aof_warp_step.hpp"
 
 // what aof_warp.cpp's device-side entry points link against: not called here
 namespace aof {
-static BankWarps g_warps;
-BankWarps &bank_warps(aof_ctx *) { return g_warps; }
+static BankCtx g_bank;
+BankCtx &bank_ctx(aof_ctx *) { return g_bank; }
 int ctx_fail(aof_ctx *, int code, const char *) { return code; }
 int launch_warp(const WarpArgs &, int64_t, void *) { return 1; }
 }  // namespace aof
