@@ -12,6 +12,7 @@ tests/test_host_asan.py holds them to each other field by field.  The models of 
 """
 import coarse_plan_ref as coarse
 import lane8_plan_ref as lane8
+import selftest_rig as rig
 import small_plan_ref as small
 from tile16_probe_ref import K_SIDE, probe_samples, sample_strides
 
@@ -111,17 +112,16 @@ def tile16_plan(a, forced=None):
 T16_FIELDS = ("verdict", "refines", "lds", "attr", "prune", "refine", "total", "overflow", "front", "refused", "front_wgs", "stx", "sty", "sx", "sy")
 
 
-def tile16_fields(pl):
+def _tile16_fields(pl):
     """The plan as the flat list of numbers the host self-test prints (T16_FIELDS)."""
     return [T16_VERDICTS.index(pl[k]) if k == "verdict" else FRONTS.index(pl[k]) if k == "front" else pl[k] for k in T16_FIELDS]
 
 
-def tile16_line(a):
+def _tile16_line(a):
     """The case as tests/native/host_selftest.cpp reads it: w h pair_stride prev cur tile search grid[6] subpixel subdirs prune
     hints n_pairs forced"""
-    v = [a["w"], a["h"], a["stride"], a["prev"], a["cur"], a["tile"], a["search"], *a["grid"], a["subpixel"], a["subdirs"], a["prune"], a["hints"],
-         a["n_pairs"], a["forced"]]
-    return " ".join(str(x) for x in v)
+    return rig.joined([a["w"], a["h"], a["stride"], a["prev"], a["cur"], a["tile"], a["search"], *a["grid"], a["subpixel"], a["subdirs"], a["prune"],
+                       a["hints"], a["n_pairs"], a["forced"]])
 
 
 def tile16_edge_width(prune=0, subpixel=0):
@@ -208,7 +208,7 @@ def finish(c, pl):
 PLAN_FIELDS = ("valid", "small", "small_class", "coarse", "k1_pass", "sequence", "kind0", "refine0", "prune0", "kind1", "refine1", "prune1")
 
 
-def plan_fields(pl):
+def _plan_fields(pl):
     """The plan as the flat list of numbers the host self-test prints (PLAN_FIELDS); level 1's are 0 where no level-1 search
     is planned (BatchPlan is zero there: SK_TILE16 is 0)."""
     k1 = pl["kind"][1]
@@ -217,12 +217,11 @@ def plan_fields(pl):
             pl["prune"][1] if k1 else 0]
 
 
-def selftest_line(c):
-    """The case as tests/native/host_selftest.cpp reads it: w h tile search px4 num_blocks subpixel levels mean_subtract n_pairs
+def _call_line(c):
+    """The call as tests/native/host_selftest.cpp reads it: w h tile search px4 num_blocks subpixel levels mean_subtract n_pairs
     pair_stride prev cur mode force_generic split cus k1_ready"""
-    v = [c["w"], c["h"], c["tile"], c["search"], int(c["px4"]), c["num_blocks"], c["subpixel"], c["levels"], c["mean_subtract"], c["n_pairs"],
-         c["stride"], c["prev"], c["cur"], c["mode"], int(c["force_generic"]), int(c["split"]), c["cus"], int(c["k1_ready"])]
-    return " ".join(str(x) for x in v)
+    return rig.joined([c["w"], c["h"], c["tile"], c["search"], int(c["px4"]), c["num_blocks"], c["subpixel"], c["levels"], c["mean_subtract"], c["n_pairs"],
+                       c["stride"], c["prev"], c["cur"], c["mode"], int(c["force_generic"]), int(c["split"]), c["cus"], int(c["k1_ready"])])
 
 
 # ---- the cases of the family models as calls ----------------------------------------------------------------------------------
@@ -473,8 +472,15 @@ CHOOSE_FIELDS = ("prune", "cols", "fused", "reports", "tag", "belief", "since_pr
                  "reports_read", "stats.belief", "stats.paying_pct")
 
 
-def choose_line(r):
+def _choose_line(r):
     """The row as tests/native/host_selftest.cpp reads it: the call's line, then belief since_probe launch_no expected arrived
     paying seen capture captured separate votes_memory votes_fault votes_stride"""
     v = [r["belief"], r["since"], r["launch_no"], *r["report"], CAPTURES.index(r["capture"]), r["captured"], r["separate"], *r["votes"]]
-    return selftest_line(choose_call(r)) + " " + " ".join(str(x) for x in v)
+    return _call_line(choose_call(r)) + " " + rig.joined(v)
+
+
+def selftest_families():
+    """plan_batch == plan(), tile16_plan == tile16_plan() and choose_lane8 == choose_row(), on every case of every list."""
+    return [rig.family("batch-plan", "batch plan: ", batch_cases(), _call_line, lambda c: _plan_fields(plan(c)), PLAN_FIELDS),
+            rig.family("tile16-plan", "tile16 plan: ", tile16_cases(), _tile16_line, lambda c: _tile16_fields(tile16_plan(c)), T16_FIELDS),
+            rig.family("choose-lane8", "choose lane8: ", choose_rows(), _choose_line, choose_row, CHOOSE_FIELDS, summary="choose lane8: {} rows printed")]

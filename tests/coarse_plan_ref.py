@@ -20,6 +20,7 @@ Written from DESIGN.md ("Kernels": K1, K1C) and the kernels' comments:
 """
 import numpy as np
 
+import selftest_rig as rig
 from cols_plan_ref import fast_div, fastdiv_make
 
 # csrc/aof_coarse_plan.hpp
@@ -88,7 +89,7 @@ COARSE_FIELDS = ("verdict", "rows_per_sweep", "nkf", "nk", "nk_pad", "nb.mul", "
                  "chunks.shift", "lds", "stagger_groups", "stagger_ticks", "wgs")
 
 
-def coarse_fields(pl):
+def _coarse_fields(pl):
     """The plan as the flat list of numbers the host self-test prints for coarse_plan_make (COARSE_FIELDS)."""
     return [VERDICTS.index(pl["verdict"]), pl["rows_per_sweep"], pl["nkf"], pl["nk"], pl["nk_pad"], *pl["div_nb"], *pl["div_nx"],
             *pl["div_chunks"], pl["lds"], pl["stagger_groups"], pl["stagger_ticks"], pl["wgs"]]
@@ -112,10 +113,6 @@ def pyramid_plan(w, h, pair_stride, prev, cur, sequence, n_pairs, sums=True):
 
 
 PYRAMID_FIELDS = ("vec", "rows_per_strip", "nstrips", "units", "total", "zero_words")
-
-
-def pyramid_fields(pl):
-    return [pl[k] for k in PYRAMID_FIELDS]
 
 
 # ---- k_coarse, phase 1: lanes, sweeps, loads ---------------------------------------------------------------------------
@@ -584,15 +581,23 @@ def plans_of(c, cus=CENSUS_CUS):
             pyramid_plan(a["w"], a["h"], a["pair_stride"], a["prev"], a["cur"], a["sequence"], a["k1_n"], bool(a["sums"])))
 
 
-def selftest_lines(c, cus=CENSUS_CUS):
-    """The case as tests/native/host_selftest.cpp reads it, one line per plan:
+def selftest_families():
+    """coarse_plan_make == coarse_plan() and pyramid_plan_make == pyramid_plan(), on every case of every list.  The cases as
+    tests/native/host_selftest.cpp reads them:
     coarse: w h pair_stride prev cur x0 y0 step_x step_y nx ny range tile search subpixel n_pairs cus
     pyramid: w h pair_stride prev cur sequence n_pairs sums"""
-    a = plan_args(c, cus)
-    coarse = [a["w"], a["h"], a["pair_stride"], a["prev"], a["cur"], *a["grid"], a["rng"], a["tile"], a["search"], a["subpixel"], a["n_pairs"],
-              a["cus"]]
-    k1 = [a["w"], a["h"], a["pair_stride"], a["prev"], a["cur"], a["sequence"], a["k1_n"], a["sums"]]
-    return " ".join(str(v) for v in coarse), " ".join(str(v) for v in k1)
+    def coarse_line(c):
+        a = plan_args(c)
+        return rig.joined([a["w"], a["h"], a["pair_stride"], a["prev"], a["cur"], *a["grid"], a["rng"], a["tile"], a["search"], a["subpixel"],
+                           a["n_pairs"], a["cus"]])
+
+    def pyramid_line(c):
+        a = plan_args(c)
+        return rig.joined([a["w"], a["h"], a["pair_stride"], a["prev"], a["cur"], a["sequence"], a["k1_n"], a["sums"]])
+
+    cases = CPU_CASES + GPU_CASES + PLAN_ONLY
+    return [rig.family("coarse-plan", "coarse plan: ", cases, coarse_line, lambda c: _coarse_fields(plans_of(c)[0]), COARSE_FIELDS),
+            rig.family("pyramid-plan", "pyramid plan: ", cases, pyramid_line, lambda c: [plans_of(c)[1][k] for k in PYRAMID_FIELDS], PYRAMID_FIELDS)]
 
 
 # ---- the frames of a device case ---------------------------------------------------------------------------------------

@@ -7,6 +7,8 @@ A case is a frame size (through its dense grid), a pair count and the form of th
 takes, the census of tests/test_cols_plan_ref.py fails on a path no device case takes."""
 import numpy as np
 
+import selftest_rig as rig
+
 # csrc/aof_cols8_plan.hpp, csrc/aof_ctx.hpp, csrc/aof_engine_args.hpp
 THREADS, MAX_ROWS, MIN_ROWS, WAVES_WANTED, WAVE_SLOTS, MAX_UNITS = 256, 8, 2, 3072, 4096, 0x7FFF0000
 VOTE_PAIRS, PRUNE_MIN_CHUNKS = 2048, 2048
@@ -74,7 +76,7 @@ PLAN_FIELDS = ("head.len", "head.segs", "head.units_per_pair", "head.mul", "head
                "per", "pairs", "tail_pairs", "units", "wgs")
 
 
-def plan_fields(pl):
+def _plan_fields(pl):
     """The plan as the flat list of numbers the host self-test prints for cols_plan_make (PLAN_FIELDS)."""
     out = []
     for cls in ("head", "tail"):
@@ -362,14 +364,18 @@ def plan_of(c):
     return plan(c["nx"], c["ny"], c["n_pairs"], **c["kw"]) if "kw" in c else case_plan(c)
 
 
-def selftest_line(c):
+def _selftest_line(c):
     """The case as tests/native/host_selftest.cpp reads it: nx ny step_x w h pair_stride cur n_pairs done."""
     if "kw" in c:
         kw = c["kw"]
         w, h = kw.get("w", 8 * c["nx"] + 8), kw.get("h", 8 * c["ny"] + 8)
-        return " ".join(str(v) for v in (c["nx"], c["ny"], kw.get("step_x", 8), w, h, kw.get("pair_stride", w * h), kw.get("cur", 0),
-                                         c["n_pairs"], kw.get("done", 0)))
-    return " ".join(str(v) for v in (c["nx"], c["ny"], 8, c["w"], c["h"], c["w"] * c["h"], 0, c["n_pairs"], 0))
+        return rig.joined((c["nx"], c["ny"], kw.get("step_x", 8), w, h, kw.get("pair_stride", w * h), kw.get("cur", 0), c["n_pairs"], kw.get("done", 0)))
+    return rig.joined((c["nx"], c["ny"], 8, c["w"], c["h"], c["w"] * c["h"], 0, c["n_pairs"], 0))
+
+
+def selftest_families():
+    """cols_plan_make == plan(), on every case of every list."""
+    return [rig.family("cols-plan", "cols plan: ", CPU_CASES + GPU_CASES + PLAN_ONLY, _selftest_line, lambda c: _plan_fields(plan_of(c)), PLAN_FIELDS)]
 
 
 # ---- device cases ----------------------------------------------------------------------------------------------------

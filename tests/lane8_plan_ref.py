@@ -22,6 +22,7 @@ import hashlib
 
 import numpy as np
 
+import selftest_rig as rig
 from small_plan_ref import blocks, grid_for_level, lane8_supported, rounded_mean
 
 # csrc/aof_lane8_plan.hpp, csrc/aof_engine_args.hpp, csrc/aof_ctx.hpp
@@ -85,7 +86,7 @@ PLAN_FIELDS = ("supported", "votes", "prune_large", "chunks_all", "per", "slices
                "expected")
 
 
-def plan_fields(pl):
+def _plan_fields(pl):
     """The plan as the flat list of numbers the host self-test prints (PLAN_FIELDS)."""
     return [VOTES.index(pl[k]) if k == "votes" else KINDS.index(pl[k]) if k == "kind" else pl[k] for k in PLAN_FIELDS]
 
@@ -392,17 +393,24 @@ def plan_of(c):
 CASES = CPU_CASES + GPU_CASES + PLAN_ONLY
 
 
-def selftest_line(c):
+def _selftest_line(c):
     """The case as tests/native/host_selftest.cpp reads it: nb n_pairs pair_stride w h prune fused rng votes_memory votes_fault
     votes_stride (votes_memory -1: no VoteMem at all) capacity slice tile search"""
     a = plan_args(c)
     mem, fault, stride = a["votes"] if a["votes"] else (-1, 0, 0)
-    v = [a["nb"], a["n_pairs"], a["pair_stride"], a["w"], a["h"], a["prune"], int(a["fused"]), a["rng"], mem, fault, stride, a["capacity"], a["slice"],
-         a["tile"], a["search"]]
-    return " ".join(str(x) for x in v)
+    return rig.joined([a["nb"], a["n_pairs"], a["pair_stride"], a["w"], a["h"], a["prune"], int(a["fused"]), a["rng"], mem, fault, stride, a["capacity"],
+                       a["slice"], a["tile"], a["search"]])
 
 
-def xcd_probes():
+def selftest_families():
+    """lane8_flat_plan == flat_plan(), on every case of every list; the C++ xcd_remap (the text the kernels run) == xcd_remap()
+    at every probe, a probe a line: total b."""
+    return [rig.family("lane8-plan", "lane8 plan: ", CASES, _selftest_line, lambda c: _plan_fields(plan_of(c)), PLAN_FIELDS),
+            rig.family("xcd-probes", "xcd remap: ", [dict(id=f"{total}/{b}", total=total, b=b) for total, b in _xcd_probes()],
+                       lambda p: f"{p['total']} {p['b']}", lambda p: [int(xcd_remap(p["b"], p["total"]))], ("logical id",), summary="xcd_remap: {} probes")]
+
+
+def _xcd_probes():
     """(total, b) pairs at which the self-test prints the C++ xcd_remap: every b of small totals with each remainder mod 8, and
     for the workgroup count of every case the first and last sixteen hardware ids and the XCD borders."""
     probes = [(total, b) for total in list(range(1, 18)) + [63, 64, 65, 255, 257] for b in range(total)]

@@ -1,22 +1,14 @@
-// Sanitizer self-test of the product's HOST-ONLY logic (no HIP calls): parameter checks, grids,
-// strip plans, workspace layout (aof_params.cpp) and the OPTICAL_FLOW_RAD packer; and of the rules the host shares
-// with the kernels, compiled for the host: the kernels' own packer (aof_mavlink.hpp) against the facade's, the two
-// forms of the checksum step against each other, the exposure bin and mean sample value (aof_exposure_step.hpp)
-// against the public functions; the column walk's segment plan (aof_cols8_plan.hpp: cols_plan_make) on the cases of
-// tests/cols_plan_ref.py, printed field by field for tests/test_host_asan.py to hold to the Python model; the plans of the
-// two coarse passes (aof_coarse_plan.hpp: coarse_plan_make, pyramid_plan_make) on the cases of tests/coarse_plan_ref.py,
-// printed the same way; the plans of the small-pair kernels (aof_small_plan.hpp: small_plan_make, lane8_group_plan) on the
-// cases of tests/small_plan_ref.py, likewise; the plan of the flat lane-per-block launches (aof_lane8_plan.hpp: lane8_flat_plan)
-// on the cases of tests/lane8_plan_ref.py, likewise, and xcd_remap (aof_xcd_remap.hpp, the text the kernels run) printed value by
-// value for the test to hold to the model's; the plan of a batch and the per-launch choice of a flat 8x8 launch (aof_batch_plan.hpp:
-// plan_batch, choose_lane8) and the launch plan of the 16x16 search (aof_tile16_plan.hpp: tile16_plan) on the cases of
-// tests/batch_plan_ref.py, likewise, with a table of choose_lane8 rows against values written here; the launch plan of the warp
-// kernel (aof_warp_plan.hpp: warp_plan_make) on the cases of tests/warp_plan_ref.py, likewise; and fastdiv_make against the division it replaces, with the kernels' fast_div restated in 32-bit
-// arithmetic; the stream bank's bound per-stream tables (aof_bank_tables.hpp): binding, resolving for a push or an IMU call, the
-// sensor arguments of a round, case by case against literal values; and the flags of one per-stream table of OpticalFlowBank
-// (facade/src/bank_table.hpp) over runs of ticks.
-// Built with -fsanitize=address,undefined by tests/test_host_asan.py.
+// Sanitizer self-test of the product's HOST-ONLY logic (no HIP calls) and of the rules the host shares with the kernels,
+// compiled for the host.  Built with -fsanitize=address,undefined and run by tests/test_host_asan.py, one check a run:
+//
+//   host_selftest list                  the names of the checks, one per line
+//   host_selftest <check> [case-file]   runs that check (the table above main says which read a case file)
+//
+// A check that holds prints its "host selftest: ..." line and exits 0; a plan check first prints one line of fields per case
+// of its file, which the test holds to the Python model of that plan.  A check that fails says which condition failed on
+// stderr and exits 1.  An unknown name or a case file that cannot be read: a sentence on stderr, exit 2.
 #include <cmath>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -41,11 +33,69 @@
 #include "bank_table.hpp"
 #include "optical_flow_rad.hpp"
 
-static unsigned rng_state = 777u;
+// The random inputs: a check that draws any seeds the generator itself, so what it draws depends on no other check.
+static unsigned rng_state;
+static void rnd_seed() { rng_state = 777u; }
 static unsigned rnd() { rng_state = rng_state * 1664525u + 1013904223u; return rng_state >> 8; }
-
 static uint64_t rnd64() { return ((uint64_t)rnd() << 48) ^ ((uint64_t)rnd() << 24) ^ rnd(); }
 template <typename T, typename U> static T bits_as(U u) { T t; static_assert(sizeof(T) == sizeof(U), "same size"); std::memcpy(&t, &u, sizeof(T)); return t; }
+
+// ---- reporting and case files ---------------------------------------------------------------------------------------------
+
+static const char *check_name, *case_path;   // the running check; the case file it reads and the line of the current case
+static int case_line;
+
+// The report of a failed check: the sentence, the case it was found at where there is one, exit 1.  (Nothing a caller
+// allocated is live when it reports: a leak report would replace the exit status.)
+[[noreturn]] static void fail(const char *fmt, ...)
+{
+    std::fprintf(stderr, "%s: ", check_name);
+    va_list ap;
+    va_start(ap, fmt);
+    std::vfprintf(stderr, fmt, ap);
+    va_end(ap);
+    if (case_path) std::fprintf(stderr, " (line %d of %s)", case_line, case_path);
+    std::fputc('\n', stderr);
+    std::exit(1);
+}
+#define HOLD(cond, ...) do { if (!(cond)) fail(__VA_ARGS__); } while (0)
+
+// The n whitespace-separated integers of f's next line into v: signed 64-bit values, and unsigned ones (an address with
+// its top bit set) by their bits.  False at end of file; a line that is not n integers fails the check.
+static bool read_ints(std::FILE *f, int n, int64_t *v)
+{
+    char line[1024], *s = line, *end;
+    if (!std::fgets(line, sizeof line, f)) return false;
+    case_line++;
+    int got = 0;
+    for (;; got++, s = end) {
+        const int64_t x = (int64_t)std::strtoull(s, &end, 10);   // (takes a sign too, and negates: the signed value's bits)
+        if (end == s) break;
+        if (got < n) v[got] = x;
+    }
+    HOLD(got == n && s[std::strspn(s, " \t\r\n")] == 0, "a line of %d integers%s where a case is %d integers", got, got == n ? " and more" : "", n);
+    return true;
+}
+
+// fn(v) on the n integers of every line of the case file; returns the number of cases.
+template <typename Fn> static int for_each_case(const char *path, int n, Fn fn)
+{
+    std::FILE *f = std::fopen(path, "r");
+    if (!f) { std::fprintf(stderr, "host_selftest: cannot read the case file %s\n", path); std::exit(2); }
+    case_path = path;
+    int64_t v[32];   // (the longest case has 31)
+    int cases = 0;
+    while (read_ints(f, n, v)) { fn(v); cases++; }
+    std::fclose(f);
+    return cases;
+}
+
+static aof::Grid grid_of(const int64_t *g) { return {(int32_t)g[0], (int32_t)g[1], (int32_t)g[2], (int32_t)g[3], (int32_t)g[4], (int32_t)g[5]}; }
+template <typename T> static const T *place_at(int64_t address) { return reinterpret_cast<const T *>((uintptr_t)address); }
+static uint32_t somewhere[1];   // a place for what a plan only looks at for being there: directions, hints, vote memory, a fault word
+static uint8_t *const somewhere8 = reinterpret_cast<uint8_t *>(somewhere);
+
+// ---- the packer, the checksum step, the exposure rule ---------------------------------------------------------------------
 
 struct Fields {
     uint64_t time_usec;
@@ -72,17 +122,18 @@ static int packers_agree(const Fields &f)
     return same ? n : -1;
 }
 
-// (a) a few thousand random field sets and the fixed cases; both frame lengths must occur (quality 0 truncates the
-// payload to 40 bytes, anything else leaves 44).  Returns the number of frames compared, or -1.
-static int check_packer()
+// packer: the kernels' packer == the facade's on a few thousand random field sets and the fixed cases; both frame lengths
+// must occur (quality 0 truncates the payload to 40 bytes, anything else leaves 44).
+static void check_packer(const char *)
 {
+    rnd_seed();
     int frames = 0, n52 = 0, n56 = 0;
     auto one = [&](const Fields &f) {
-        const int n = packers_agree(f);
+        const int n = packers_agree(f), want = f.quality & 0xFF ? 56 : 52;
+        HOLD(n == want, "frame %d (quality %d): the kernels' packer and the facade's differ, or the frame is not %d bytes", frames, f.quality, want);
         if (n == 52) n52++;
         if (n == 56) n56++;
         frames++;
-        return n == (f.quality & 0xFF ? 56 : 52);
     };
     for (int it = 0; it < 4000; it++) {
         Fields f;
@@ -102,7 +153,7 @@ static int check_packer()
         }
         f.quality = it % 7 == 0 ? 0 : (int)(rnd() % 256);
         f.seq = (uint8_t)rnd(); f.system_id = (uint8_t)rnd(); f.component_id = (uint8_t)rnd();
-        if (!one(f)) return -1;
+        one(f);
     }
     const Fields base = {5000000123ull, 66667, 0.01f, -0.02f, 0.1, 0.2, 0.3, 200, 7, 1, 100};
     const int ends[2] = {0, 255};
@@ -110,144 +161,142 @@ static int check_packer()
         for (int seq : ends) {
             Fields f = base;
             f.quality = q; f.seq = (uint8_t)seq;
-            if (!one(f)) return -1;
+            one(f);
             f.gx = -0.0; f.gy = 0.0; f.gz = -1e-60;              // all three convert to float -0.0 (gy through its sign switch)
-            if ((float)f.gx != 0.0f || !std::signbit((float)f.gx) || !std::signbit((float)(-f.gy)) || !std::signbit((float)f.gz)) return -1;
-            if (!one(f)) return -1;
+            HOLD((float)f.gx == 0.0f && std::signbit((float)f.gx) && std::signbit((float)(-f.gy)) && std::signbit((float)f.gz), "a sum does not convert to float -0.0");
+            one(f);
             f.time_usec = 0xFF00000000000000ull | (uint64_t)seq; // the top byte set
-            if (!one(f)) return -1;
+            one(f);
         }
-    return n52 > 0 && n56 > 0 ? frames : -1;
+    HOLD(n52 > 0 && n56 > 0, "a frame length never occurred: %d frames of 52 bytes, %d of 56", n52, n56);
+    std::printf("host selftest: packer: %d frames equal to the facade's, lengths 52 and 56\n", frames);
 }
 
-// (b) the two forms of the checksum step (aof_mavlink.hpp) on every (checksum, byte), and the facade's with them
-static bool check_crc_steps()
+// packer-range: the facade's packer alone on random messages: a frame's length within its bounds, its magic and length
+// bytes; and the ends of the public exposure functions.
+static void check_packer_range(const char *)
+{
+    rnd_seed();
+    uint8_t wire[OPTICAL_FLOW_RAD_MAX_FRAME];
+    for (int it = 0; it < 2000; it++) {
+        OpticalFlowRad m;
+        fillOpticalFlowRad(m, rnd(), rnd(), (int)rnd(), 0.001f * (float)(rnd() % 100), -0.002f * (float)(rnd() % 100),
+                           0.1, 0.2, 0.3, (int)(rnd() % 256));
+        size_t n = packOpticalFlowRad(m, (uint8_t)it, 1, 100, wire);
+        HOLD(n >= 13 && n <= OPTICAL_FLOW_RAD_MAX_FRAME && wire[0] == 0xFD && wire[1] == n - 12,
+             "message %d: a frame of %zu bytes, first byte 0x%02X, length byte %d", it, n, wire[0], wire[1]);
+    }
+    uint32_t hist[AOF_EXPOSURE_BINS] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10};
+    HOLD(aof_exposure_msv(hist) > 0.0f, "the mean sample value of a filled histogram is not positive");
+    HOLD(aof_exposure_bin(255) == -1 && aof_exposure_bin(-3) == -1, "aof_exposure_bin gives 255 or -3 a bin");
+    std::printf("host selftest: packer range: 2000 frames within their bounds, the exposure functions' ends as documented\n");
+}
+
+// checksum: the two forms of the checksum step (aof_mavlink.hpp) on every (checksum, byte), and the facade's with them.
+static void check_crc_steps(const char *)
 {
     for (uint32_t crc = 0; crc < 65536u; crc++)
         for (uint32_t b = 0; b < 256u; b++) {
             const uint8_t byte = (uint8_t)b;
             const uint32_t narrow = aof::crc_accumulate(byte, (uint16_t)crc);
-            if (narrow != aof::rx_crc(b, crc) || narrow != mavlinkCrcAccumulate(&byte, 1, (uint16_t)crc)) return false;
+            HOLD(narrow == aof::rx_crc(b, crc) && narrow == mavlinkCrcAccumulate(&byte, 1, (uint16_t)crc),
+                 "checksum 0x%04X, byte 0x%02X: crc_accumulate gives 0x%04X, rx_crc or the facade's step another", crc, b, narrow);
         }
-    return true;
+    std::printf("host selftest: checksum: both steps and the facade's agree on 65536 x 256 inputs\n");
 }
 
-// (c) the shared bin and mean sample value against the public functions.  Returns the histograms compared, or -1.
-static int check_exposure()
+// exposure: the shared bin and mean sample value (aof_exposure_step.hpp) against the public functions.
+static void check_exposure(const char *)
 {
+    rnd_seed();
     for (int v = 0; v < 256; v++) {
         const int shared = aof::exposure_bin((uint32_t)v), pub = aof_exposure_bin(v);
-        if (shared < 0 || shared > AOF_EXPOSURE_BINS || (shared == AOF_EXPOSURE_BINS ? -1 : shared) != pub) return -1;
+        HOLD(shared >= 0 && shared <= AOF_EXPOSURE_BINS && (shared == AOF_EXPOSURE_BINS ? -1 : shared) == pub, "sample value %d: shared bin %d, public bin %d", v, shared, pub);
     }
-    if (aof::exposure_bin(255u) != AOF_EXPOSURE_BINS || aof_exposure_bin(254) != 9 || aof_exposure_bin(0) != 0) return -1;
+    HOLD(aof::exposure_bin(255u) == AOF_EXPOSURE_BINS && aof_exposure_bin(254) == 9 && aof_exposure_bin(0) == 0, "the bins of 255, 254 and 0 are not saturated, 9 and 0");
     int hists = 0;
     for (int it = 0; it < 2002; it++) {
         uint32_t hist[AOF_EXPOSURE_BINS];
         for (uint32_t &h : hist) h = it == 0 ? 0u : it == 1 ? 16384u : (it & 1) ? rnd() % 16385u : (uint32_t)rnd64();
         const float shared = aof::exposure_msv(hist), pub = aof_exposure_msv(hist);
-        if (std::memcmp(&shared, &pub, sizeof(float)) != 0) return -1;
-        if (it == 0 && shared != 0.0f) return -1;
-        if (it == 1 && shared != 55.0f) return -1;   // 1 + 2 + ... + 10, every term exact
+        HOLD(std::memcmp(&shared, &pub, sizeof(float)) == 0, "histogram %d: the shared mean sample value is %.9g, the public one %.9g", it, shared, pub);
+        HOLD(it != 0 || shared == 0.0f, "the empty histogram's mean sample value is %.9g", shared);
+        HOLD(it != 1 || shared == 55.0f, "the level histogram's mean sample value is %.9g, not 55", shared);   // 1 + 2 + ... + 10, every term exact
         hists++;
     }
-    return hists;
+    std::printf("host selftest: exposure: 256 bins and %d mean sample values equal to the public functions\n", hists);
 }
 
-// (d) cols_plan_make on the case file of tests/test_host_asan.py, one case per line: nx ny step_x w h pair_stride cur n_pairs
-// done.  One line of fields per case, in the order of cols_plan_ref.PLAN_FIELDS.  Returns the cases read, or -1.
-static int print_cols_plans(const char *path)
+// ---- the plan checks: one line of fields per case of the file, in the order of the Python model's field names ---------------
+
+// cols-plan: cols_plan_make (aof_cols8_plan.hpp), fields in the order of cols_plan_ref.PLAN_FIELDS.  A case: nx ny step_x w h
+// pair_stride cur n_pairs done.
+static void print_cols_plans(const char *path)
 {
-    std::FILE *f = std::fopen(path, "r");
-    if (!f) return -1;
-    int cases = 0;
-    long long nx, ny, step_x, w, h, stride, n_pairs, done;
-    unsigned long long cur;
-    while (std::fscanf(f, "%lld %lld %lld %lld %lld %lld %llu %lld %lld", &nx, &ny, &step_x, &w, &h, &stride, &cur, &n_pairs, &done) == 9) {
+    const int cases = for_each_case(path, 9, [](const int64_t *v) {
+        const int64_t nx = v[0], ny = v[1], step_x = v[2], w = v[3], h = v[4], stride = v[5], cur = v[6], n_pairs = v[7], done = v[8];
         aof::Grid g = {4, 4, (int32_t)step_x, 8, (int32_t)nx, (int32_t)ny};
-        const aof::ColsLaunch l = aof::cols_plan_make(g, (int)w, (int)h, (int64_t)stride, (uintptr_t)cur, (int64_t)n_pairs, (int64_t)done);
+        const aof::ColsLaunch l = aof::cols_plan_make(g, (int)w, (int)h, stride, (uintptr_t)cur, n_pairs, done);
         const aof::ColsSegments *cls[2] = {&l.plan.head, &l.plan.tail};
         std::printf("cols plan:");
         for (const aof::ColsSegments *s : cls) std::printf(" %d %d %u %u %u", s->len, s->segs, s->units_per_pair, s->div_units.mul, s->div_units.shift);
         std::printf(" %u %u %u %u %u %lld %lld %lld %lld %lld\n", l.plan.head_pairs, l.plan.head_units, l.plan.div_nx.mul, l.plan.div_nx.shift,
                     l.plan.aligned, (long long)l.per, (long long)l.pairs, (long long)l.tail_pairs, (long long)l.units, (long long)l.wgs);
-        cases++;
-    }
-    std::fclose(f);
-    return cases;
+    });
+    std::printf("host selftest: cols plan: %d cases\n", cases);
 }
 
-// (d2) coarse_plan_make on a case file, one case per line: w h pair_stride prev cur x0 y0 step_x step_y nx ny range tile
-// search subpixel n_pairs cus.  One line of fields per case, in the order of coarse_plan_ref.COARSE_FIELDS.
-static int print_coarse_plans(const char *path)
+// coarse-plan: coarse_plan_make (aof_coarse_plan.hpp), fields in the order of coarse_plan_ref.COARSE_FIELDS.  A case: w h
+// pair_stride prev cur x0 y0 step_x step_y nx ny range tile search subpixel n_pairs cus.
+static void print_coarse_plans(const char *path)
 {
-    std::FILE *f = std::fopen(path, "r");
-    if (!f) return -1;
-    int cases = 0;
-    long long w, h, stride, g[6], range, tile, search, subpixel, n_pairs, cus;
-    unsigned long long prev, cur;
-    while (std::fscanf(f, "%lld %lld %lld %llu %llu %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld", &w, &h, &stride, &prev, &cur,
-                       &g[0], &g[1], &g[2], &g[3], &g[4], &g[5], &range, &tile, &search, &subpixel, &n_pairs, &cus) == 17) {
-        const aof::Grid grid = {(int32_t)g[0], (int32_t)g[1], (int32_t)g[2], (int32_t)g[3], (int32_t)g[4], (int32_t)g[5]};
-        const aof::CoarsePlan p = aof::coarse_plan_make((int)w, (int)h, (int64_t)stride, (uintptr_t)prev, (uintptr_t)cur, grid, (int)range,
-                                                        (int)tile, (int)search, (int)subpixel, (int64_t)n_pairs, (int)cus);
+    const int cases = for_each_case(path, 17, [](const int64_t *v) {
+        const int64_t w = v[0], h = v[1], stride = v[2], prev = v[3], cur = v[4], range = v[11], tile = v[12], search = v[13], subpixel = v[14],
+                      n_pairs = v[15], cus = v[16];
+        const aof::CoarsePlan p = aof::coarse_plan_make((int)w, (int)h, stride, (uintptr_t)prev, (uintptr_t)cur, grid_of(v + 5), (int)range, (int)tile,
+                                                        (int)search, (int)subpixel, n_pairs, (int)cus);
         std::printf("coarse plan: %d %d %d %d %d %u %u %u %u %u %u %zu %d %d %lld\n", (int)p.verdict, p.rows_per_sweep, p.nkf, p.nk, p.nk_pad,
                     p.div_nb.mul, p.div_nb.shift, p.div_nx.mul, p.div_nx.shift, p.div_chunks.mul, p.div_chunks.shift, p.lds, p.stagger_groups,
                     p.stagger_ticks, (long long)p.wgs);
-        cases++;
-    }
-    std::fclose(f);
-    return cases;
+    });
+    std::printf("host selftest: coarse plan: %d cases\n", cases);
 }
 
-// (d3) pyramid_plan_make on a case file, one case per line: w h pair_stride prev cur sequence n_pairs sums.  One line of
-// fields per case, in the order of coarse_plan_ref.PYRAMID_FIELDS.
-static int print_pyramid_plans(const char *path)
+// pyramid-plan: pyramid_plan_make (aof_coarse_plan.hpp), fields in the order of coarse_plan_ref.PYRAMID_FIELDS.  A case: w h
+// pair_stride prev cur sequence n_pairs sums.
+static void print_pyramid_plans(const char *path)
 {
-    std::FILE *f = std::fopen(path, "r");
-    if (!f) return -1;
-    int cases = 0;
-    long long w, h, stride, sequence, n_pairs, sums;
-    unsigned long long prev, cur;
-    while (std::fscanf(f, "%lld %lld %lld %llu %llu %lld %lld %lld", &w, &h, &stride, &prev, &cur, &sequence, &n_pairs, &sums) == 8) {
-        const aof::PyramidPlan p = aof::pyramid_plan_make((int)w, (int)h, (int64_t)stride, (uintptr_t)prev, (uintptr_t)cur, (int)sequence,
-                                                          (int64_t)n_pairs, sums != 0);
+    const int cases = for_each_case(path, 8, [](const int64_t *v) {
+        const int64_t w = v[0], h = v[1], stride = v[2], prev = v[3], cur = v[4], sequence = v[5], n_pairs = v[6], sums = v[7];
+        const aof::PyramidPlan p = aof::pyramid_plan_make((int)w, (int)h, stride, (uintptr_t)prev, (uintptr_t)cur, (int)sequence, n_pairs, sums != 0);
         std::printf("pyramid plan: %d %d %d %lld %lld %lld\n", p.vec, p.rows_per_strip, p.nstrips, (long long)p.units, (long long)p.total,
                     (long long)p.zero_words);
-        cases++;
-    }
-    std::fclose(f);
-    return cases;
+    });
+    std::printf("host selftest: pyramid plan: %d cases\n", cases);
 }
 
-// (d4) small_plan_make and lane8_group_plan on a case file, one case per line: w h levels, the level-0 and the level-1 grid
-// (x0 y0 step_x step_y nx ny each), n_pairs pair_stride prev cur subpixel tile search, the histogram ranges of level 0 and 1,
-// whether levels 0 and 1 have a place for their half-pixel directions, and level 1's size as the caller states it.  Two
-// lines of fields per case, in the order of small_plan_ref.PLAN_FIELDS and GROUP_FIELDS.
-static int print_small_plans(const char *path)
+// small-plan: small_plan_make and lane8_group_plan (aof_small_plan.hpp), two lines a case, fields in the order of
+// small_plan_ref.PLAN_FIELDS and GROUP_FIELDS.  A case: w h levels, the level-0 and the level-1 grid (x0 y0 step_x step_y nx ny
+// each), n_pairs pair_stride prev cur subpixel tile search, the histogram ranges of level 0 and 1, whether levels 0 and 1
+// have a place for their half-pixel directions, and level 1's size as the caller states it.
+static void print_small_plans(const char *path)
 {
-    std::FILE *f = std::fopen(path, "r");
-    if (!f) return -1;
-    int cases = 0;
-    long long w, h, levels, g0[6], g1[6], n_pairs, stride, subpixel, tile, search, rng0, rng1, sub0, sub1, l1_w, l1_h;
-    unsigned long long prev, cur;
-    static uint8_t somewhere[1];   // (a place for directions: only looked at for being there)
-    while (std::fscanf(f, "%lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %llu %llu %lld %lld %lld %lld %lld %lld %lld %lld %lld",
-                       &w, &h, &levels, &g0[0], &g0[1], &g0[2], &g0[3], &g0[4], &g0[5], &g1[0], &g1[1], &g1[2], &g1[3], &g1[4], &g1[5], &n_pairs,
-                       &stride, &prev, &cur, &subpixel, &tile, &search, &rng0, &rng1, &sub0, &sub1, &l1_w, &l1_h) == 28) {
+    const int cases = for_each_case(path, 28, [](const int64_t *v) {
+        const int64_t w = v[0], h = v[1], levels = v[2], *g[2] = {v + 3, v + 9}, n_pairs = v[15], stride = v[16], prev = v[17], cur = v[18],
+                      subpixel = v[19], tile = v[20], search = v[21], rng0 = v[22], rng1 = v[23], sub0 = v[24], sub1 = v[25], l1_w = v[26], l1_h = v[27];
         aof::SmallArgs a = {};
         aof::SearchArgs *lv[2] = {&a.l0, &a.l1};
-        const long long *g[2] = {g0, g1};
         for (int l = 0; l < 2; l++) {
             aof::SearchArgs &s = *lv[l];
-            s.prev = reinterpret_cast<const uint8_t *>((uintptr_t)prev);
-            s.cur = reinterpret_cast<const uint8_t *>((uintptr_t)cur);
-            s.pair_stride = (int64_t)stride;
+            s.prev = place_at<uint8_t>(prev);
+            s.cur = place_at<uint8_t>(cur);
+            s.pair_stride = stride;
             s.w = (int32_t)(l ? l1_w : w); s.h = (int32_t)(l ? l1_h : h);
             s.tile = (int32_t)tile; s.search = (int32_t)search;
-            s.grid = {(int32_t)g[l][0], (int32_t)g[l][1], (int32_t)g[l][2], (int32_t)g[l][3], (int32_t)g[l][4], (int32_t)g[l][5]};
+            s.grid = grid_of(g[l]);
             s.subpixel = (int32_t)subpixel;
-            s.subdirs = (l ? sub1 : sub0) ? somewhere : nullptr;
-            s.n_pairs = (int64_t)n_pairs;
+            s.subdirs = (l ? sub1 : sub0) ? somewhere8 : nullptr;
+            s.n_pairs = n_pairs;
             s.hist_range = (int32_t)(l ? rng1 : rng0);
             s.level = l;
         }
@@ -258,96 +307,83 @@ static int print_small_plans(const char *path)
                     p.trips_a[0], p.trips_a[1], p.trips_a[2], p.trips_b[0], p.trips_b[1], p.trips_c[0], p.trips_c[1], p.trips_d1[0], p.trips_d1[1]);
         const aof::Lane8GroupPlan gp = aof::lane8_group_plan(a.l0);
         std::printf("group plan: %d %lld %d %zu\n", gp.ppw, (long long)gp.wgs, gp.last_live, gp.lds);
-        cases++;
-    }
-    std::fclose(f);
-    return cases;
+    });
+    std::printf("host selftest: small plan: %d cases\n", cases);
 }
 
-// (d5) lane8_flat_plan on a case file, one case per line: nb n_pairs pair_stride w h prune fused rng votes_memory votes_fault
-// votes_stride (votes_memory -1: no VoteMem at all) capacity slice tile search.  One line of fields per case, in the order of
-// lane8_plan_ref.PLAN_FIELDS.
-static int print_lane8_plans(const char *path)
+// lane8-plan: lane8_flat_plan (aof_lane8_plan.hpp), fields in the order of lane8_plan_ref.PLAN_FIELDS.  A case: nb n_pairs
+// pair_stride w h prune fused rng votes_memory votes_fault votes_stride (votes_memory -1: no VoteMem at all) capacity slice
+// tile search.
+static void print_lane8_plans(const char *path)
 {
-    std::FILE *f = std::fopen(path, "r");
-    if (!f) return -1;
-    int cases = 0;
-    long long nb, n_pairs, stride, w, h, prune, fused, rng, mem, fault, vstride, capacity, slice, tile, search;
-    static uint32_t somewhere[1];   // (vote memory and fault word: only looked at for being there)
-    while (std::fscanf(f, "%lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld", &nb, &n_pairs, &stride, &w, &h, &prune, &fused,
-                       &rng, &mem, &fault, &vstride, &capacity, &slice, &tile, &search) == 15) {
+    const int cases = for_each_case(path, 15, [](const int64_t *v) {
+        const int64_t nb = v[0], n_pairs = v[1], stride = v[2], w = v[3], h = v[4], prune = v[5], fused = v[6], rng = v[7], mem = v[8], fault = v[9],
+                      vstride = v[10], capacity = v[11], slice = v[12], tile = v[13], search = v[14];
         aof::SearchArgs a = {};
-        a.pair_stride = (int64_t)stride;
+        a.pair_stride = stride;
         a.w = (int32_t)w; a.h = (int32_t)h;
         a.tile = (int32_t)tile; a.search = (int32_t)search;
         a.grid = {4, 4, 8, 8, (int32_t)nb, nb > 0 ? 1 : 0};
-        a.n_pairs = (int64_t)n_pairs;
+        a.n_pairs = n_pairs;
         a.hist_range = (int32_t)rng;
         a.prune = (int32_t)prune;
         aof::VoteMem vm = {mem > 0 ? somewhere : nullptr, (uint32_t)vstride, fault > 0 ? somewhere : nullptr, 0};
-        const aof::Lane8FlatPlan p = aof::lane8_flat_plan(a, fused != 0, mem < 0 ? nullptr : &vm, (int64_t)capacity, (int64_t)slice);
+        const aof::Lane8FlatPlan p = aof::lane8_flat_plan(a, fused != 0, mem < 0 ? nullptr : &vm, capacity, slice);
         std::printf("lane8 plan: %d %d %d %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %d %d %lld %lld %lld %d %lld %d %d %u %u\n", p.supported, p.votes,
                     p.prune_large, (long long)p.chunks_all, (long long)p.per, (long long)p.slices, (long long)p.done, (long long)p.pairs,
                     (long long)p.frame_off, (long long)p.block_off, (long long)p.pred_off, (long long)p.sums_off, (long long)p.items, p.kind,
                     p.threads, (long long)p.wgs, (long long)p.finalisers, (long long)p.grid, p.last_live, (long long)p.chunks, p.spw, p.last_chunks,
                     p.stride, p.expected);
-        cases++;
-    }
-    std::fclose(f);
-    return cases;
+    });
+    std::printf("host selftest: lane8 plan: %d cases\n", cases);
 }
 
-// (d7) the plan of a batch (aof_batch_plan.hpp) and of the 16x16 search (aof_tile16_plan.hpp).  A call as
-// tests/batch_plan_ref.py writes it: w h tile search px4 num_blocks subpixel levels mean_subtract n_pairs pair_stride prev cur
-// mode force_generic split cus k1_ready.  Parameters aof_params_check refuses get an empty grid and an empty layout (no
-// context exists for them; the plan is then only the function's answer).  The workspace is a place, nothing reads it.
+// A call as tests/batch_plan_ref.py writes it: w h tile search px4 num_blocks subpixel levels mean_subtract n_pairs pair_stride
+// prev cur mode force_generic split cus k1_ready.  Parameters aof_params_check refuses get an empty grid and an empty layout
+// (no context exists for them; the plan is then only the function's answer).  The workspace is a place, nothing reads it.
 struct PlannedCall {
     aof::BatchConfig cfg;
     aof::BatchView view;
     int64_t n_pairs;
     bool valid, k1_ready;
 };
+enum { kCallInts = 18 };
 
-static bool read_call(std::FILE *f, PlannedCall *c)
+static PlannedCall planned_call(const int64_t *v)
 {
-    long long w, h, tile, search, px4, num_blocks, subpixel, levels, mean_subtract, n_pairs, stride, mode, force_generic, split, cus, k1_ready;
-    unsigned long long prev, cur;
-    if (std::fscanf(f, "%lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %llu %llu %lld %lld %lld %lld %lld", &w, &h, &tile, &search, &px4,
-                    &num_blocks, &subpixel, &levels, &mean_subtract, &n_pairs, &stride, &prev, &cur, &mode, &force_generic, &split, &cus,
-                    &k1_ready) != 18)
-        return false;
-    aof::BatchConfig &cfg = c->cfg;
-    cfg = {};
+    const int64_t w = v[0], h = v[1], tile = v[2], search = v[3], px4 = v[4], num_blocks = v[5], subpixel = v[6], levels = v[7], mean_subtract = v[8],
+                  n_pairs = v[9], stride = v[10], prev = v[11], cur = v[12], mode = v[13], force_generic = v[14], split = v[15], cus = v[16],
+                  k1_ready = v[17];
+    PlannedCall c = {};
+    aof::BatchConfig &cfg = c.cfg;
     aof_params &p = cfg.params;
     aof_params_default(&p, (int)w, (int)h);
     p.tile = (int)tile; p.search = (int)search;
     p.grid_mode = px4 ? AOF_GRID_PX4FLOW : AOF_GRID_DENSE;
     p.num_blocks = (int)num_blocks;
     p.subpixel = (int)subpixel; p.pyramid_levels = (int)levels; p.mean_subtract = (int)mean_subtract;
-    c->valid = aof_params_check(&p) == 0;
+    c.valid = aof_params_check(&p) == 0;
     aof::Grid *g[2] = {&cfg.g0, &cfg.g1};
     for (int l = 0; l < (int)levels && l < 2; l++)
         if (aof::grid_for_level(p, l, g[l])) *g[l] = {};
     cfg.cus = (int)cus; cfg.search_mode = (int)mode; cfg.force_generic = force_generic != 0; cfg.split_coarse = split != 0;
     aof_ws_layout L = {};
-    if (c->valid && aof_workspace_layout(&p, (int64_t)n_pairs, &L)) return false;
-    c->n_pairs = (int64_t)n_pairs;
-    c->k1_ready = k1_ready != 0;
-    c->view = aof::batch_view(cfg, L, reinterpret_cast<const uint8_t *>((uintptr_t)prev), reinterpret_cast<const uint8_t *>((uintptr_t)cur),
-                              (int64_t)stride, nullptr, nullptr, reinterpret_cast<aof_flow *>((uintptr_t)0x7E0000000000ull),
-                              reinterpret_cast<void *>((uintptr_t)0x7D0000000000ull));
-    return true;
+    HOLD(!c.valid || aof_workspace_layout(&p, (int64_t)n_pairs, &L) == 0, "valid parameters of a call have no workspace layout");
+    c.n_pairs = n_pairs;
+    c.k1_ready = k1_ready != 0;
+    c.view = aof::batch_view(cfg, L, place_at<uint8_t>(prev), place_at<uint8_t>(cur), (int64_t)stride, nullptr, nullptr,
+                             reinterpret_cast<aof_flow *>((uintptr_t)0x7E0000000000ull), reinterpret_cast<void *>((uintptr_t)0x7D0000000000ull));
+    return c;
 }
 
-// One line of fields per call, in the order of batch_plan_ref.PLAN_FIELDS; kinds[]: how often each SearchKind was planned
-// (level 0, and level 1 where K1 is followed by a search), coarse[]: each CoarseKind.
-static int print_batch_plans(const char *path, int kinds[4], int coarse[3])
+// batch-plan: plan_batch (aof_batch_plan.hpp) on a call per line, fields in the order of batch_plan_ref.PLAN_FIELDS.  The
+// summary counts how often each SearchKind was planned (level 0, and level 1 where K1 is followed by a search) and each
+// CoarseKind.
+static void print_batch_plans(const char *path)
 {
-    std::FILE *f = std::fopen(path, "r");
-    if (!f) return -1;
-    int cases = 0;
-    PlannedCall c;
-    while (read_call(f, &c)) {
+    int kinds[4] = {}, coarse[3] = {};
+    const int cases = for_each_case(path, kCallInts, [&](const int64_t *v) {
+        const PlannedCall c = planned_call(v);
         const aof::BatchPlan P = aof::plan_batch(c.cfg, c.view, c.n_pairs, c.k1_ready);
         const bool level1 = !P.small && P.coarse == aof::COARSE_K1 && c.cfg.params.pyramid_levels == 2;
         std::printf("batch plan: %d %d %d %d %d %d %d %d %d %d %d %d\n", c.valid ? 1 : 0, P.small ? 1 : 0, P.small_class ? 1 : 0, (int)P.coarse,
@@ -356,67 +392,57 @@ static int print_batch_plans(const char *path, int kinds[4], int coarse[3])
         kinds[P.level[0].kind]++;
         if (level1) kinds[P.level[1].kind]++;
         coarse[P.coarse]++;
-        cases++;
-    }
-    std::fclose(f);
-    return cases;
+    });
+    std::printf("host selftest: batch plan: %d cases, kinds %d %d %d %d, coarse %d %d %d\n", cases, kinds[0], kinds[1], kinds[2], kinds[3],
+                coarse[0], coarse[1], coarse[2]);
 }
 
-// tile16_plan on a case file, one search per line: w h pair_stride prev cur tile search grid[6] subpixel subdirs prune hints
-// n_pairs forced.  One line of fields per case, in the order of batch_plan_ref.T16_FIELDS; verdicts[]: the census.
-static int print_tile16_plans(const char *path, int verdicts[9])
+// tile16-plan: tile16_plan (aof_tile16_plan.hpp), fields in the order of batch_plan_ref.T16_FIELDS, and the three questions the
+// plan answers asked one by one; the summary counts the verdicts.  A case: w h pair_stride prev cur tile search grid[6] subpixel
+// subdirs prune hints n_pairs forced.
+static void print_tile16_plans(const char *path)
 {
-    std::FILE *f = std::fopen(path, "r");
-    if (!f) return -1;
-    int cases = 0;
-    long long w, h, stride, tile, search, g[6], subpixel, subdirs, prune, hints, n_pairs, forced;
-    unsigned long long prev, cur;
-    static uint8_t somewhere[4];   // (directions and hints: only looked at for being there)
-    while (std::fscanf(f, "%lld %lld %lld %llu %llu %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld", &w, &h, &stride, &prev,
-                       &cur, &tile, &search, &g[0], &g[1], &g[2], &g[3], &g[4], &g[5], &subpixel, &subdirs, &prune, &hints, &n_pairs,
-                       &forced) == 19) {
+    int verdicts[9] = {};
+    const int cases = for_each_case(path, 19, [&](const int64_t *v) {
+        const int64_t w = v[0], h = v[1], stride = v[2], prev = v[3], cur = v[4], tile = v[5], search = v[6], subpixel = v[13], subdirs = v[14],
+                      prune = v[15], hints = v[16], n_pairs = v[17], forced = v[18];
         aof::SearchArgs a = {};
-        a.prev = reinterpret_cast<const uint8_t *>((uintptr_t)prev);
-        a.cur = reinterpret_cast<const uint8_t *>((uintptr_t)cur);
-        a.pair_stride = (int64_t)stride;
+        a.prev = place_at<uint8_t>(prev);
+        a.cur = place_at<uint8_t>(cur);
+        a.pair_stride = stride;
         a.w = (int32_t)w; a.h = (int32_t)h;
         a.tile = (int32_t)tile; a.search = (int32_t)search;
-        a.grid = {(int32_t)g[0], (int32_t)g[1], (int32_t)g[2], (int32_t)g[3], (int32_t)g[4], (int32_t)g[5]};
+        a.grid = grid_of(v + 7);
         a.subpixel = (int32_t)subpixel;
-        a.subdirs = subdirs ? somewhere : nullptr;
+        a.subdirs = subdirs ? somewhere8 : nullptr;
         a.prune = (int32_t)prune;
-        a.hints = hints ? reinterpret_cast<uint32_t *>(somewhere) : nullptr;
-        a.n_pairs = (int64_t)n_pairs;
+        a.hints = hints ? somewhere : nullptr;
+        a.n_pairs = n_pairs;
         const aof::Tile16Plan p = aof::tile16_plan(a, (int)forced);
-        if ((p.verdict == aof::TILE16_OK) != aof::tile16_supported(a) || (p.refines != 0) != aof::tile16_refines(a) || p.lds != aof::tile16_lds(a)) return -1;
+        HOLD((p.verdict == aof::TILE16_OK) == aof::tile16_supported(a) && (p.refines != 0) == aof::tile16_refines(a) && p.lds == aof::tile16_lds(a),
+             "the plan (verdict %d, refines %d, lds %zu) is not what tile16_supported, tile16_refines and tile16_lds answer", p.verdict, p.refines, p.lds);
         std::printf("tile16 plan: %d %d %zu %d %d %d %lld %d %d %d %lld %d %d %d %d\n", p.verdict, p.refines, p.lds, p.attr, p.prune, p.refine,
                     (long long)p.total, p.overflow, p.front, p.refused, (long long)p.front_wgs, p.stx, p.sty, p.sx, p.sy);
         if (p.verdict >= 0 && p.verdict < 9) verdicts[p.verdict]++;
-        cases++;
-    }
-    std::fclose(f);
-    return cases;
+    });
+    std::printf("host selftest: tile16 plan: %d cases, verdicts %d %d %d %d %d %d %d %d %d\n", cases, verdicts[0], verdicts[1], verdicts[2],
+                verdicts[3], verdicts[4], verdicts[5], verdicts[6], verdicts[7], verdicts[8]);
 }
 
-// (d8) warp_plan_make on a case file, one call per line: w h n_frames cropped cropped_stride hist.  One line of fields per
-// case, in the order of warp_plan_ref.WARP_FIELDS; verdicts[]: the census.
-static int print_warp_plans(const char *path, int verdicts[3])
+// warp-plan: warp_plan_make (aof_warp_plan.hpp), fields in the order of warp_plan_ref.WARP_FIELDS; the summary counts the
+// verdicts.  A case: w h n_frames cropped cropped_stride hist.
+static void print_warp_plans(const char *path)
 {
-    std::FILE *f = std::fopen(path, "r");
-    if (!f) return -1;
-    int cases = 0;
-    long long w, h, n_frames, stride, hist;
-    unsigned long long cropped;
-    while (std::fscanf(f, "%lld %lld %lld %llu %lld %lld", &w, &h, &n_frames, &cropped, &stride, &hist) == 6) {
-        const aof::WarpPlan p = aof::warp_plan_make((int32_t)w, (int32_t)h, (int64_t)n_frames, (uintptr_t)cropped, (int64_t)stride, hist != 0);
+    int verdicts[3] = {};
+    const int cases = for_each_case(path, 6, [&](const int64_t *v) {
+        const int64_t w = v[0], h = v[1], n_frames = v[2], cropped = v[3], stride = v[4], hist = v[5];
+        const aof::WarpPlan p = aof::warp_plan_make((int32_t)w, (int32_t)h, n_frames, (uintptr_t)cropped, stride, hist != 0);
         std::printf("warp plan: %d %d %d %d %d %d %d %d %d %lld %lld %d %zu %d %d %lld %lld %d %d %lld\n", (int)p.verdict, p.nx, p.ny, p.strip_rows, p.nstrips,
                     p.rows[0], p.rows[1], p.node_rows[0], p.node_rows[1], (long long)p.node_bytes[0], (long long)p.node_bytes[1], p.vec, p.lds, p.attr,
                     p.zero_hist, (long long)p.items[0], (long long)p.items[1], p.trips[0], p.trips[1], (long long)p.wgs);
         if (p.verdict >= 0 && p.verdict < 3) verdicts[p.verdict]++;
-        cases++;
-    }
-    std::fclose(f);
-    return cases;
+    });
+    std::printf("host selftest: warp plan: %d cases, verdicts %d %d %d\n", cases, verdicts[0], verdicts[1], verdicts[2]);
 }
 
 // The report a pruned launch leaves in the context's pinned words: the first `arrived` of `expected` carry the launch's
@@ -439,23 +465,17 @@ static aof::AdaptiveSearch adaptive_state(int belief, int since_probe, uint32_t 
     return st;
 }
 
-// choose_lane8 on a case file: a call's line (its level-0 search must be a flat 8x8 launch), then belief since_probe launch_no
-// expected arrived paying seen capture captured separate votes_memory votes_fault votes_stride.  One line per row: the
-// launch and the state after it, in the order of batch_plan_ref.CHOOSE_FIELDS.
-static int print_choose_lane8(const char *path)
+// choose-lane8: choose_lane8 (aof_batch_plan.hpp) on a row per line: a call (its level-0 search must be a flat 8x8 launch),
+// then belief since_probe launch_no expected arrived paying seen capture captured separate votes_memory votes_fault
+// votes_stride.  One line per row: the launch and the state after it, in the order of batch_plan_ref.CHOOSE_FIELDS.
+static void print_choose_lane8(const char *path)
 {
-    std::FILE *f = std::fopen(path, "r");
-    if (!f) return -1;
-    int rows = 0;
-    PlannedCall c;
-    static uint32_t somewhere[1];
-    while (read_call(f, &c)) {
-        long long belief, since, launch_no, expected, arrived, paying, seen, capture, captured, separate, mem, fault, vstride;
-        if (std::fscanf(f, "%lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld", &belief, &since, &launch_no, &expected, &arrived, &paying,
-                        &seen, &capture, &captured, &separate, &mem, &fault, &vstride) != 13)
-            return -1;
+    const int rows = for_each_case(path, kCallInts + 13, [](const int64_t *v) {
+        const PlannedCall c = planned_call(v);
+        const int64_t *r = v + kCallInts, belief = r[0], since = r[1], launch_no = r[2], expected = r[3], arrived = r[4], paying = r[5], seen = r[6],
+                      capture = r[7], captured = r[8], separate = r[9], mem = r[10], fault = r[11], vstride = r[12];
         const aof::BatchPlan P = aof::plan_batch(c.cfg, c.view, c.n_pairs, c.k1_ready);
-        if (!c.valid || P.small || P.level[0].kind != aof::SK_LANE8) return -1;
+        HOLD(c.valid && !P.small && P.level[0].kind == aof::SK_LANE8, "the row's call is not a flat 8x8 launch at level 0");
         aof::AdaptiveSearch st = adaptive_state((int)belief, (int)since, (uint32_t)launch_no, (uint32_t)expected, (uint32_t)arrived, (uint32_t)paying,
                                                 (uint32_t)seen);
         const aof::VoteMem vm = {mem ? somewhere : nullptr, (uint32_t)vstride, fault ? somewhere : nullptr, 0};
@@ -463,16 +483,14 @@ static int print_choose_lane8(const char *path)
         std::printf("choose lane8: %d %d %d %d %u %d %d %u %llu %llu %llu %d %d\n", l.prune, l.cols ? 1 : 0, l.fused ? 1 : 0, l.rep.slots ? 1 : 0,
                     l.rep.launch_no, st.belief, st.since_probe, st.launch_no, (unsigned long long)st.stats.pruned_launches,
                     (unsigned long long)st.stats.exhaustive_launches, (unsigned long long)st.stats.reports_read, st.stats.belief, st.stats.paying_pct);
-        rows++;
-    }
-    std::fclose(f);
-    return rows;
+    });
+    std::printf("host selftest: choose lane8: %d rows printed\n", rows);
 }
 
-// choose_lane8, row by row against the values written here: 1 024 VGA pairs on the dense grid (4 661 blocks: a launch large
-// enough to prune, the column walk's grid), 19 vote bins, vote records for 2 048 pairs, the last reporting launch number 7.
-// Returns the number of rows, or -1.
-static int check_choose_lane8()
+// choose-lane8-written: choose_lane8, row by row against the values written here: 1 024 VGA pairs on the dense grid (4 661
+// blocks: a launch large enough to prune, the column walk's grid), 19 vote bins, vote records for 2 048 pairs, the last
+// reporting launch number 7.
+static void check_choose_lane8(const char *)
 {
     using namespace aof;
     enum { EX = AOF_SEARCH_EXHAUSTIVE, PR = AOF_SEARCH_PRUNED, AD = AOF_SEARCH_ADAPTIVE };
@@ -509,9 +527,8 @@ static int check_choose_lane8()
     aof_params_default(&p, 640, 480);
     BatchConfig cfg = {};
     cfg.params = p;
-    if (grid_for_level(p, 0, &cfg.g0) || cfg.g0.blocks() != 4661) return -1;
+    HOLD(grid_for_level(p, 0, &cfg.g0) == 0 && cfg.g0.blocks() == 4661, "the dense VGA grid does not have 4661 blocks");
     cfg.cus = 256;
-    static uint32_t somewhere[1];
     const VoteMem vm = {somewhere, 128, somewhere, 0};
     int n = 0;
     for (const auto &r : rows) {
@@ -519,62 +536,57 @@ static int check_choose_lane8()
         const SearchArgs a = search_args(cfg, 0, nullptr, nullptr, 640 * 480, nullptr, nullptr, nullptr, nullptr, 1024);
         AdaptiveSearch st = adaptive_state(r.belief, r.since, r.launch_no, r.expected, r.arrived, r.paying, 100);
         const Lane8Launch l = choose_lane8(cfg, st, a, r.cap, vm, 2048, r.separate, r.captured);
-        if (l.prune != r.prune || l.cols != r.cols || l.fused != r.fused || (l.rep.slots != nullptr) != (r.tag != 0) || (r.tag && l.rep.launch_no != r.tag)) return -1;
-        if (st.belief != r.belief_after || st.since_probe != r.since_after || st.launch_no != r.launch_after) return -1;
-        if (st.stats.pruned_launches != r.pruned || st.stats.exhaustive_launches != r.exhaustive || st.stats.reports_read != r.read) return -1;
+        HOLD(l.prune == r.prune && l.cols == r.cols && l.fused == r.fused && (l.rep.slots != nullptr) == (r.tag != 0) && (!r.tag || l.rep.launch_no == r.tag),
+             "row %d: the launch (prune %d, cols %d, fused %d) or its report tag is not the one written", n, l.prune, (int)l.cols, (int)l.fused);
+        HOLD(st.belief == r.belief_after && st.since_probe == r.since_after && st.launch_no == r.launch_after,
+             "row %d: the state after the launch (belief %d, since_probe %d, launch_no %u) is not the one written", n, st.belief, st.since_probe, st.launch_no);
+        HOLD(st.stats.pruned_launches == r.pruned && st.stats.exhaustive_launches == r.exhaustive && st.stats.reports_read == r.read,
+             "row %d: the counters after the launch are not the ones written", n);
         n++;
     }
-    return n;
+    std::printf("host selftest: choose lane8: %d rows equal to the values written\n", n);
 }
 
-// (d6) xcd_remap, the function the kernels run: a permutation of [0, total) for every total up to 4096 (every logical id hit
-// once), and printed at the probes of the case file's second kind of line for the test to hold to the model: "total b".
-static int check_xcd_remap()
+// xcd-permutation: xcd_remap (aof_xcd_remap.hpp, the text the kernels run) is a permutation of [0, total) for every total up
+// to 4096: every logical id hit once.
+static void check_xcd_remap(const char *)
 {
     static uint8_t hit[4096];
     for (uint32_t total = 1; total <= 4096u; total++) {
         std::memset(hit, 0, total);
         for (uint32_t b = 0; b < total; b++) {
             const uint32_t wg = aof::xcd_remap(b, total);
-            if (wg >= total || hit[wg]++) return -1;
-            if (b >= 8 && wg != aof::xcd_remap(b - 8, total) + 1) return -1;   // an XCD's logical ids are contiguous
+            HOLD(wg < total && !hit[wg]++, "total %u: hardware id %u maps to %u, beyond the total or taken", total, b, wg);
+            HOLD(b < 8 || wg == aof::xcd_remap(b - 8, total) + 1, "total %u: hardware ids %u and %u do not map to neighbours", total, b - 8, b);   // an XCD's logical ids are contiguous
         }
     }
-    return 4096;
+    std::printf("host selftest: xcd_remap: a permutation for every total up to 4096\n");
 }
 
-static int print_xcd_probes(const char *path)
+// xcd-probes: xcd_remap printed value by value for the test to hold to the model's.  A probe: total b.
+static void print_xcd_probes(const char *path)
 {
-    std::FILE *f = std::fopen(path, "r");
-    if (!f) return -1;
-    int probes = 0;
-    unsigned long long total, b;
-    while (std::fscanf(f, "%llu %llu", &total, &b) == 2) {
-        std::printf("xcd remap: %u\n", aof::xcd_remap((uint32_t)b, (uint32_t)total));
-        probes++;
-    }
-    std::fclose(f);
-    return probes;
+    const int probes = for_each_case(path, 2, [](const int64_t *v) { std::printf("xcd remap: %u\n", aof::xcd_remap((uint32_t)v[1], (uint32_t)v[0])); });
+    std::printf("host selftest: xcd_remap: %d probes\n", probes);
 }
 
-// (e) fastdiv_make: the kernels' fast_div (aof_device.hpp) restated -- the high half of the product, the sum and the shift
-// in 32 bits -- against n / d.  Divisors: every d up to 4096 (grid widths, blocks per pair) and every multiple of 64 up to
-// 2^20 (units per pair); numerators: all below 2^16, and around 65 multiples of d spread up to the top of the 31 bits
-// the launchers keep to.  Returns the numerators per divisor beyond the first 2^16, or -1.
+// fastdiv: fastdiv_make against the division it replaces, with the kernels' fast_div (aof_device.hpp) restated -- the high
+// half of the product, the sum and the shift in 32 bits.  Divisors: every d up to 4096 (grid widths, blocks per pair) and
+// every multiple of 64 up to 2^20 (units per pair); numerators: all below 2^16, and around 65 multiples of d spread up to the
+// top of the 31 bits the launchers keep to.
 static uint32_t fast_div_host(uint32_t n, aof::FastDiv d) { return ((uint32_t)(((uint64_t)n * d.mul) >> 32) + n) >> d.shift; }
 
-static int check_fastdiv(int *divisors)
+static void check_fastdiv(const char *)
 {
-    int extra = 0;
-    *divisors = 0;
+    int extra = 0, divisors = 0;   // extra: the numerators per divisor beyond the first 2^16
     for (uint32_t i = 1; i <= 4096u + (1u << 20) / 64u; i++) {
         const uint32_t d = i <= 4096u ? i : (i - 4096u) * 64u;
         if (i > 4096u && d <= 4096u) continue;   // (already seen)
         const aof::FastDiv fd = aof::fastdiv_make(d);
-        if (fd.shift > 31u) return -1;
+        HOLD(fd.shift <= 31u, "divisor %u: a shift of %u", d, fd.shift);
         uint32_t q = 0, r = 0;
         for (uint32_t n = 0; n < 65536u; n++) {
-            if (fast_div_host(n, fd) != q) return -1;
+            HOLD(fast_div_host(n, fd) == q, "%u / %u: fast_div gives %u", n, d, fast_div_host(n, fd));
             if (++r == d) { r = 0; q++; }
         }
         const uint32_t top = 0x7FFFFFFFu / d;
@@ -584,25 +596,26 @@ static int check_fastdiv(int *divisors)
             const uint64_t around[3] = {(uint64_t)k * d - 1u, (uint64_t)k * d, (uint64_t)k * d + 1u};
             for (uint64_t n : around) {
                 if (n > 0x7FFFFFFFull) continue;   // (k = 0: -1 wraps; the top multiple + 1 may pass 2^31)
-                if (fast_div_host((uint32_t)n, fd) != (uint32_t)(n / d)) return -1;
+                HOLD(fast_div_host((uint32_t)n, fd) == (uint32_t)(n / d), "%u / %u: fast_div gives %u", (uint32_t)n, d, fast_div_host((uint32_t)n, fd));
                 count++;
             }
         }
         const uint32_t ends[2] = {0x7FFEFFFFu, 0x7FFFFFFFu};
         for (uint32_t n : ends) {
-            if (fast_div_host(n, fd) != n / d) return -1;
+            HOLD(fast_div_host(n, fd) == n / d, "%u / %u: fast_div gives %u", n, d, fast_div_host(n, fd));
             count++;
         }
-        if (count < 190) return -1;
+        HOLD(count >= 190, "divisor %u: only %d numerators around its multiples", d, count);
         extra = count > extra ? count : extra;
-        (*divisors)++;
+        divisors++;
     }
-    return extra;
+    std::printf("host selftest: fast_div: %d divisors, all numerators below 65536 and up to %d around multiples up to 2^31 equal to n / d\n",
+                divisors, extra);
 }
 
-// The stream bank's bound per-stream tables (aof_bank_tables.hpp): what a binding call accepts and leaves behind, and
-// which tables a push or an IMU call uses or why it is refused, each case against the value written here.  The arrays
-// are places in `arena`; nothing reads them.  Returns the number of cases, or -1.
+// bank-tables: the stream bank's bound per-stream tables (aof_bank_tables.hpp): what a binding call accepts and leaves
+// behind, and which tables a push or an IMU call uses or why it is refused, each case against the value written here.  The
+// arrays are places in `arena`; nothing reads them.
 alignas(16) static uint8_t arena[96];
 
 static bool same_text(const char *got, const char *want)
@@ -610,7 +623,7 @@ static bool same_text(const char *got, const char *want)
     return (!got && !want) || (got && want && std::strcmp(got, want) == 0);
 }
 
-static int check_bank_tables()
+static void check_bank_tables(const char *)
 {
     using namespace aof;
     const void *const A = arena + 16, *const ODD = arena + 40, *const OLD = arena + 64;   // 16-byte aligned, 8 off, the binding before
@@ -649,12 +662,13 @@ static int check_bank_tables()
         for (int t = 0; t < kBankTableCount; t++) before.table[t] = {OLD, 3};
         before.camera_bytes = 1000;
         BankTables b = before;
-        if (!same_text(bank_tables_bind(&b, c.which, c.array, c.n, c.camera_bytes), c.refusal)) return -1;
-        if (c.refusal && !(b == before)) return -1;
+        const char *got = bank_tables_bind(&b, c.which, c.array, c.n, c.camera_bytes);
+        HOLD(same_text(got, c.refusal), "binding case %d: answered '%s', written '%s'", cases, got ? got : "(accepted)", c.refusal ? c.refusal : "(accepted)");
+        HOLD(!c.refusal || b == before, "binding case %d: a refused binding changed the tables", cases);
         BankTables want = before;
         want.table[c.which] = {c.array_after, c.n_after};
         want.camera_bytes = c.camera_bytes_after;
-        if (!(b == want)) return -1;
+        HOLD(b == want, "binding case %d: the tables after the call are not the ones written", cases);
         cases++;
     }
     // ---- resolving, for a call of 3 streams: {streams, sensors, formats, bins} bound for that many streams (0: not bound) ----
@@ -706,14 +720,14 @@ static int check_bank_tables()
         const char *got;
         if (c.form == kImu) got = bank_tables_for_imu(b, 3, &u.streams);
         else got = bank_tables_for_push(b, 3, c.form == 1, c.round_stride, &u);
-        if (!same_text(got, c.refusal)) return -1;
+        HOLD(same_text(got, c.refusal), "case %d (bindings and calls counted together): answered '%s', written '%s'", cases, got ? got : "(accepted)", c.refusal ? c.refusal : "(accepted)");
         if (c.refusal) {   // a refused call hands nothing out
-            if (u.streams != untouched.streams || u.sensors != untouched.sensors || u.formats != untouched.formats || u.bins != untouched.bins) return -1;
+            HOLD(u.streams == untouched.streams && u.sensors == untouched.sensors && u.formats == untouched.formats && u.bins == untouched.bins, "case %d: refused, yet a table handed out", cases);
         } else {
-            if (u.streams != (c.uses & S ? (const void *)(arena + 16) : nullptr)) return -1;
+            HOLD(u.streams == (c.uses & S ? (const void *)(arena + 16) : nullptr), "case %d: the stream table handed out is not the one written", cases);
             if (c.form != kImu) {
-                if (u.sensors != (c.uses & N ? (const void *)(arena + 32) : nullptr) || u.camera_bytes != c.camera_bytes) return -1;
-                if (u.formats != (c.uses & F ? arena + 48 : nullptr) || u.bins != (c.uses & B ? arena + 64 : nullptr)) return -1;
+                HOLD(u.sensors == (c.uses & N ? (const void *)(arena + 32) : nullptr) && u.camera_bytes == c.camera_bytes, "case %d: not the sensor table or camera_bytes written", cases);
+                HOLD(u.formats == (c.uses & F ? arena + 48 : nullptr) && u.bins == (c.uses & B ? arena + 64 : nullptr), "case %d: not the format or binning table written", cases);
             }
         }
         cases++;
@@ -721,16 +735,17 @@ static int check_bank_tables()
     // ---- the kernels' sensor arguments of a round: every value in its own field ----
     const BankTablesUsed u = {(const aof_bank_stream *)(arena + 16), (const aof_bank_sensor *)(arena + 32), 1000, arena + 48, arena + 64};
     const BankSensors bs = bank_sensors_of_round(u, 640);
-    if ((const void *)bs.recs != arena + 32 || bs.camera_bytes != 1000 || bs.camera_base != 640 || bs.formats != arena + 48 || bs.bins != arena + 64) return -1;
+    HOLD((const void *)bs.recs == arena + 32 && bs.camera_bytes == 1000 && bs.camera_base == 640 && bs.formats == arena + 48 && bs.bins == arena + 64,
+         "bank_sensors_of_round puts a value into another field");
     const IngestSensors is = ingest_sensors_of_round(u, 640, arena + 80), plain = ingest_sensors_of_round(u, 0);
-    if ((const void *)is.recs != arena + 32 || is.base != 640 || is.camera_bytes != 1000 || is.ok != arena + 80 || is.formats != arena + 48 ||
-        is.bins != arena + 64 || plain.ok != nullptr || plain.base != 0)
-        return -1;
-    return cases + 2;
+    HOLD((const void *)is.recs == arena + 32 && is.base == 640 && is.camera_bytes == 1000 && is.ok == arena + 80 && is.formats == arena + 48 &&
+             is.bins == arena + 64 && plain.ok == nullptr && plain.base == 0,
+         "ingest_sensors_of_round puts a value into another field");
+    std::printf("host selftest: bank tables: %d cases\n", cases + 2);
 }
 
-// The flags of one per-stream table of OpticalFlowBank (facade/src/bank_table.hpp) over a run of ticks, with counters in
-// place of the copy and the binding call: after every step the numbers written here.  Returns the number of steps, or -1.
+// facade-table: the flags of one per-stream table of OpticalFlowBank (facade/src/bank_table.hpp) over a run of ticks, with
+// counters in place of the copy and the binding call: after every step the numbers written here.
 struct TableSim {
     BankTableFlags f = {};
     int uploads = 0, binds = 0;
@@ -750,10 +765,10 @@ struct TableSim {
     }
 };
 
-static int check_facade_table()
+static void check_facade_table(const char *)
 {
     int steps = 0;
-#define STEP(cond) do { if (!(cond)) return -1; steps++; } while (0)
+#define STEP(cond) do { HOLD(cond, "step %d does not hold: %s", steps, #cond); steps++; } while (0)
     {   // no setter, three ticks: nothing is copied or bound
         TableSim t;
         for (int k = 0; k < 3; k++) STEP(t.tick() == 0 && t.at(0, 0, false) && !t.f.used && !t.f.bound);
@@ -806,11 +821,15 @@ static int check_facade_table()
         STEP(t.tick() == 0 && t.at(3, 2, false) && t.f.bound);
     }
 #undef STEP
-    return steps;
+    std::printf("host selftest: facade table: %d steps, copies and bindings as written\n", steps);
 }
 
-int main(int argc, char **argv)
+// params: 20 000 random parameter sets, invalid ones among them.  Every set aof_params_check takes has a grid at every level
+// whose tiles and search windows lie inside the level's frame, reduction chunks that cover the grid, histogram bytes as
+// the layout rule states them, and a workspace layout; more than 1 000 of the sets are valid.
+static void check_params(const char *)
 {
+    rnd_seed();
     int bad = 0, valid = 0;
     for (int it = 0; it < 20000; it++) {
         aof_params p;
@@ -826,90 +845,67 @@ int main(int argc, char **argv)
         if (aof_params_check(&p) != 0) { bad++; continue; }
         valid++;
         for (int l = 0; l < p.pyramid_levels; l++) {
+            char at[96];   // where a condition fails
+            std::snprintf(at, sizeof at, "at level %d of %dx%d tile %d search %d", l, p.width, p.height, p.tile, p.search);
             int32_t g[6];
-            if (aof_grid(&p, l, &g[0], &g[1], &g[2], &g[3], &g[4], &g[5])) return 1;
-            if (g[4] < 1 || g[5] < 1) return 2;
+            HOLD(aof_grid(&p, l, &g[0], &g[1], &g[2], &g[3], &g[4], &g[5]) == 0, "valid parameters have no grid %s", at);
+            HOLD(g[4] >= 1 && g[5] >= 1, "a grid of %d x %d blocks %s", g[4], g[5], at);
             // every tile of the grid, with its search window, lies inside the level's frame
             const int w = p.width >> l, h = p.height >> l, m = p.subpixel ? 1 : 0;
             const int lx = g[0] + (g[4] - 1) * g[2], ly = g[1] + (g[5] - 1) * g[3];
-            if (g[0] - p.search - m < 0 || lx + p.tile + p.search + m > w) return 3;
-            if (g[1] - p.search - m < 0 || ly + p.tile + p.search + m > h) return 4;
+            HOLD(g[0] - p.search - m >= 0 && lx + p.tile + p.search + m <= w, "tile window leaves the frame to the left or right %s", at);
+            HOLD(g[1] - p.search - m >= 0 && ly + p.tile + p.search + m <= h, "tile window leaves the frame at the top or bottom %s", at);
             // the two-step reduction of large grids covers every block with its chunks
             const int chunks = aof::reduce_chunks(g[4] * g[5]);
-            if (chunks < 0 || (chunks > 0 && (long long)chunks * 4096 < (long long)g[4] * g[5])) return 5;
-            if (aof::hist_bytes_per_pair(p, l) != (size_t)chunks * 2 * (2 * (2 * (size_t)aof::level_range(p, l) + 1) + 1) * 4) return 6;
+            HOLD(chunks >= 0 && (chunks == 0 || (long long)chunks * 4096 >= (long long)g[4] * g[5]), "%d reduction chunks do not cover %d blocks %s", chunks, g[4] * g[5], at);
+            HOLD(aof::hist_bytes_per_pair(p, l) == (size_t)chunks * 2 * (2 * (2 * (size_t)aof::level_range(p, l) + 1) + 1) * 4,
+                 "%zu histogram bytes a pair are not those of %d chunks %s", aof::hist_bytes_per_pair(p, l), chunks, at);
         }
         aof_ws_layout L;
-        if (aof_workspace_layout(&p, (int64_t)(rnd() % 5000), &L)) return 7;
-        if (L.total_bytes % 256 || L.l0_hist < L.l0_subdirs || L.total_bytes < L.l1_hist) return 8;
+        HOLD(aof_workspace_layout(&p, (int64_t)(rnd() % 5000), &L) == 0, "valid parameters (set %d, %dx%d) have no workspace layout", it, p.width, p.height);
+        HOLD(L.total_bytes % 256 == 0 && L.l0_hist >= L.l0_subdirs && L.total_bytes >= L.l1_hist,
+             "the workspace layout of set %d (%dx%d) is not a multiple of 256 bytes or its regions are out of order", it, p.width, p.height);
     }
-    uint8_t wire[OPTICAL_FLOW_RAD_MAX_FRAME];
-    for (int it = 0; it < 2000; it++) {
-        OpticalFlowRad m;
-        fillOpticalFlowRad(m, rnd(), rnd(), (int)rnd(), 0.001f * (float)(rnd() % 100), -0.002f * (float)(rnd() % 100),
-                           0.1, 0.2, 0.3, (int)(rnd() % 256));
-        size_t n = packOpticalFlowRad(m, (uint8_t)it, 1, 100, wire);
-        if (n < 13 || n > OPTICAL_FLOW_RAD_MAX_FRAME || wire[0] != 0xFD || wire[1] != n - 12) return 9;
-    }
-    uint32_t hist[AOF_EXPOSURE_BINS] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10};
-    if (aof_exposure_msv(hist) <= 0.0f || aof_exposure_bin(255) != -1 || aof_exposure_bin(-3) != -1) return 10;
-    const int frames = check_packer();
-    if (frames < 0) return 12;
-    std::printf("host selftest: packer: %d frames equal to the facade's, lengths 52 and 56\n", frames);
-    if (!check_crc_steps()) return 13;
-    std::printf("host selftest: checksum: both steps and the facade's agree on 65536 x 256 inputs\n");
-    const int hists = check_exposure();
-    if (hists < 0) return 14;
-    std::printf("host selftest: exposure: 256 bins and %d mean sample values equal to the public functions\n", hists);
-    int divisors = 0;
-    const int numerators = check_fastdiv(&divisors);
-    if (numerators < 0) return 15;
-    std::printf("host selftest: fast_div: %d divisors, all numerators below 65536 and up to %d around multiples up to 2^31 equal to n / d\n",
-                divisors, numerators);
-    const int tables = check_bank_tables();
-    if (tables < 0) return 20;
-    std::printf("host selftest: bank tables: %d cases\n", tables);
-    const int steps = check_facade_table();
-    if (steps < 0) return 21;
-    std::printf("host selftest: facade table: %d steps, copies and bindings as written\n", steps);
-    if (argc > 1) {
-        const int plans = print_cols_plans(argv[1]);
-        if (plans < 0) return 16;
-        std::printf("host selftest: cols plan: %d cases\n", plans);
-    }
-    if (argc > 3) {
-        const int coarse = print_coarse_plans(argv[2]), pyramid = print_pyramid_plans(argv[3]);
-        if (coarse < 0 || pyramid < 0) return 17;
-        std::printf("host selftest: coarse plan: %d cases\nhost selftest: pyramid plan: %d cases\n", coarse, pyramid);
-    }
-    if (argc > 4) {
-        const int small = print_small_plans(argv[4]);
-        if (small < 0) return 18;
-        std::printf("host selftest: small plan: %d cases\n", small);
-    }
-    if (argc > 6) {
-        const int lane8 = print_lane8_plans(argv[5]), totals = check_xcd_remap(), probes = print_xcd_probes(argv[6]);
-        if (lane8 < 0 || totals < 0 || probes < 0) return 19;
-        std::printf("host selftest: lane8 plan: %d cases\nhost selftest: xcd_remap: a permutation for every total up to %d, %d probes\n", lane8,
-                    totals, probes);
-    }
-    if (argc > 9) {
-        int kinds[4] = {}, coarse[3] = {}, verdicts[9] = {};
-        const int batch = print_batch_plans(argv[7], kinds, coarse), tile16 = print_tile16_plans(argv[8], verdicts);
-        const int chosen = print_choose_lane8(argv[9]), written = check_choose_lane8();
-        if (batch < 0 || tile16 < 0 || chosen < 0 || written < 0) return 22;
-        std::printf("host selftest: batch plan: %d cases, kinds %d %d %d %d, coarse %d %d %d\n", batch, kinds[0], kinds[1], kinds[2], kinds[3],
-                    coarse[0], coarse[1], coarse[2]);
-        std::printf("host selftest: tile16 plan: %d cases, verdicts %d %d %d %d %d %d %d %d %d\n", tile16, verdicts[0], verdicts[1], verdicts[2],
-                    verdicts[3], verdicts[4], verdicts[5], verdicts[6], verdicts[7], verdicts[8]);
-        std::printf("host selftest: choose lane8: %d rows equal to the values written, %d rows printed\n", written, chosen);
-    }
-    if (argc > 10) {
-        int verdicts[3] = {};
-        const int warp = print_warp_plans(argv[10], verdicts);
-        if (warp < 0) return 23;
-        std::printf("host selftest: warp plan: %d cases, verdicts %d %d %d\n", warp, verdicts[0], verdicts[1], verdicts[2]);
-    }
+    HOLD(valid > 1000, "only %d of 20000 random parameter sets are valid, no more than 1000", valid);
     std::printf("host selftest: %d valid parameter sets, %d rejected\n", valid, bad);
-    return valid > 1000 ? 0 : 11;
+}
+
+static const struct { const char *name; void (*run)(const char *case_file); bool takes_case_file; } checks[] = {
+    {"params", check_params, false},
+    {"packer-range", check_packer_range, false},
+    {"packer", check_packer, false},
+    {"checksum", check_crc_steps, false},
+    {"exposure", check_exposure, false},
+    {"fastdiv", check_fastdiv, false},
+    {"bank-tables", check_bank_tables, false},
+    {"facade-table", check_facade_table, false},
+    {"choose-lane8-written", check_choose_lane8, false},
+    {"xcd-permutation", check_xcd_remap, false},
+    {"cols-plan", print_cols_plans, true},
+    {"coarse-plan", print_coarse_plans, true},
+    {"pyramid-plan", print_pyramid_plans, true},
+    {"small-plan", print_small_plans, true},
+    {"lane8-plan", print_lane8_plans, true},
+    {"xcd-probes", print_xcd_probes, true},
+    {"batch-plan", print_batch_plans, true},
+    {"tile16-plan", print_tile16_plans, true},
+    {"choose-lane8", print_choose_lane8, true},
+    {"warp-plan", print_warp_plans, true},
+};
+
+int main(int argc, char **argv)
+{
+    if (argc == 2 && std::strcmp(argv[1], "list") == 0) {
+        for (const auto &c : checks) std::printf("%s\n", c.name);
+        return 0;
+    }
+    for (const auto &c : checks)
+        if (argc >= 2 && std::strcmp(argv[1], c.name) == 0) {
+            if (argc != (c.takes_case_file ? 3 : 2)) break;
+            check_name = c.name;
+            c.run(c.takes_case_file ? argv[2] : nullptr);
+            return 0;
+        }
+    std::fprintf(stderr, "host_selftest: '%s' is no check, or is given a case file too many or too few; `host_selftest list` prints the names\n", argc >= 2 ? argv[1] : "");
+    return 2;
 }

@@ -21,6 +21,7 @@ there for, and the height comes from the grid rule (grid_for_level).  Only the w
 extreme shapes of PLAN_ONLY are written out."""
 import numpy as np
 
+import selftest_rig as rig
 
 # csrc/aof_small_plan.hpp
 THREADS, MAX_BINS, LOADS, PAD = 256, 64, 8, 16
@@ -115,7 +116,7 @@ def small_plan(w, h, levels, g0, g1, n_pairs, pair_stride, prev, cur, subpixel=0
 PLAN_FIELDS = ("verdict", "lds", "f0[0]", "f0[1]", "f1[0]", "f1[1]", "attr", "a[1]", "a[2]", "a[3]", "b[1]", "b[2]", "c[0]", "c[1]", "d1[0]", "d1[1]")
 
 
-def plan_fields(pl):
+def _plan_fields(pl):
     """The plan as the flat list of numbers the host self-test prints for small_plan_make (PLAN_FIELDS)."""
     return [VERDICTS.index(pl["verdict"]), pl["lds"], *pl["f0"], *pl["f1"], pl["attr"], *pl["trips_a"], *pl["trips_b"], *pl["trips_c"],
             *pl["trips_d1"]]
@@ -145,10 +146,6 @@ def group_plan(w, h, g, n_pairs, pair_stride, rng, tile=8, search=4):
 
 
 GROUP_FIELDS = ("ppw", "wgs", "last_live", "lds")
-
-
-def group_fields(pl):
-    return [pl[k] for k in GROUP_FIELDS]
 
 
 # ---- the decodes ---------------------------------------------------------------------------------------------------------
@@ -603,13 +600,19 @@ def plans_of(c):
     return small, group
 
 
-def selftest_line(c):
-    """The case as tests/native/host_selftest.cpp reads it: w h levels g0[6] g1[6] n_pairs pair_stride prev cur subpixel tile
-    search rng0 rng1 subdirs0 subdirs1 l1_w l1_h"""
-    a = plan_args(c)
-    v = [a["w"], a["h"], a["levels"], *a["g0"], *a["g1"], a["n_pairs"], a["pair_stride"], a["prev"], a["cur"], a["subpixel"], a["tile"], a["search"],
-         a["rng0"], a["rng1"], a["subdirs0"], a["subdirs1"], a["l1_w"], a["l1_h"]]
-    return " ".join(str(x) for x in v)
+def selftest_families():
+    """small_plan_make == small_plan() and lane8_group_plan == group_plan(), on every case of every list: one listing, two
+    lines a case.  The case as tests/native/host_selftest.cpp reads it: w h levels g0[6] g1[6] n_pairs pair_stride prev cur
+    subpixel tile search rng0 rng1 subdirs0 subdirs1 l1_w l1_h"""
+    def line(c):
+        a = plan_args(c)
+        return rig.joined([a["w"], a["h"], a["levels"], *a["g0"], *a["g1"], a["n_pairs"], a["pair_stride"], a["prev"], a["cur"], a["subpixel"], a["tile"],
+                           a["search"], a["rng0"], a["rng1"], a["subdirs0"], a["subdirs1"], a["l1_w"], a["l1_h"]])
+
+    cases = CPU_CASES + GPU_CASES + PLAN_ONLY
+    return [rig.family("small-plan", "small plan: ", cases, line, lambda c: _plan_fields(plans_of(c)[0]), PLAN_FIELDS),
+            rig.family("small-plan", "group plan: ", cases, line, lambda c: [plans_of(c)[1][k] for k in GROUP_FIELDS], GROUP_FIELDS, name="group-plan",
+                       summary="small plan: {} cases")]
 
 
 # ---- the frames of a device case -----------------------------------------------------------------------------------------

@@ -3,20 +3,11 @@ bank_sensor_valid_groups and bank_sensor_valid_format, which the kernels and the
 _binned decide with), driven by a stand-alone program with its own main against one 128-bit restatement by pixel groups
 over every format byte, every bin byte that matters and edge values on every axis (tests/native/crop_rule_selftest.cpp).
 CPU only; nothing here is loaded into Python."""
-import os
-import subprocess
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CXX = os.environ.get("CXX", "c++")
+import selftest_rig as rig
 
 
 def test_the_rule_of_a_crop_source_neither_wraps_nor_overflows(tmp_path):
-    csrc = os.path.join(ROOT, "aero-optical-flow_amd", "csrc")
-    exe = tmp_path / "crop_rule_selftest"
-    cmd = [CXX, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           "-I" + os.path.join(ROOT, "include"), "-I" + csrc, os.path.join(ROOT, "tests", "native", "crop_rule_selftest.cpp"),
-           "-o", str(exe)]
-    subprocess.run(cmd, check=True, timeout=300)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    exe = rig.build(tmp_path, "crop_rule_selftest", ["tests/native/crop_rule_selftest.cpp"])
+    r = rig.run(exe)
     assert r.returncode == 0, f"rc={r.returncode}\n{r.stdout}{r.stderr}"
     assert "agree" in r.stdout

@@ -3,21 +3,12 @@ host side around it (csrc/aof_field.cpp: the geometry, its range check, the plai
 by a stand-alone program with its own main against one restatement in __int128: the largest grids the range check admits,
 shifts at the ends of int8, determinants beyond 2^53 that convert exactly and ones that have to be rounded, arrays allocated
 at their exact size (tests/native/field_selftest.cpp).  CPU only; nothing here is loaded into Python."""
-import os
-import subprocess
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CXX = os.environ.get("CXX", "c++")
+import selftest_rig as rig
 
 
 def test_the_field_rule_neither_wraps_nor_reads_outside_its_records(tmp_path):
-    csrc = os.path.join(ROOT, "aero-optical-flow_amd", "csrc")
-    exe = tmp_path / "field_selftest"
-    cmd = [CXX, "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fsanitize=float-cast-overflow",
-           "-fno-sanitize-recover=all", "-I" + os.path.join(ROOT, "include"), "-I" + csrc,
-           os.path.join(ROOT, "tests", "native", "field_selftest.cpp"), os.path.join(csrc, "aof_field.cpp"),
-           os.path.join(csrc, "aof_params.cpp"), "-o", str(exe)]
-    subprocess.run(cmd, check=True, timeout=300)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    exe = rig.build(tmp_path, "field_selftest", ["tests/native/field_selftest.cpp", rig.CSRC + "/aof_field.cpp", rig.CSRC + "/aof_params.cpp"],
+                    fp_contract_off=True, float_cast=True)
+    r = rig.run(exe)
     assert r.returncode == 0, f"rc={r.returncode}\n{r.stdout}{r.stderr}"
     assert "agree" in r.stdout

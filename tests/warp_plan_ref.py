@@ -20,6 +20,7 @@ Written from the header text and the kernels' comments:
 
 No size is asserted here as a literal beyond what the case tables state: a case names a shape and the properties it is
 there for, and reach() derives every property from the plan."""
+import selftest_rig as rig
 import small_plan_ref as small
 
 # csrc/aof_warp_plan.hpp, csrc/aof_warp_step.hpp
@@ -83,7 +84,7 @@ WARP_FIELDS = ("verdict", "nx", "ny", "strip_rows", "nstrips", "rows[0]", "rows[
                "node_bytes[1]", "vec", "lds", "attr", "zero_hist", "items[0]", "items[1]", "trips[0]", "trips[1]", "wgs")
 
 
-def warp_fields(pl):
+def _warp_fields(pl):
     """The plan as the flat list of numbers the host self-test prints for warp_plan_make (WARP_FIELDS)."""
     return [VERDICTS.index(pl["verdict"]), pl["nx"], pl["ny"], pl["strip_rows"], pl["nstrips"], *pl["rows"], *pl["node_rows"], *pl["node_bytes"],
             pl["vec"], pl["lds"], pl["attr"], pl["zero_hist"], *pl["items"], *pl["trips"], pl["wgs"]]
@@ -187,17 +188,26 @@ WARP_PLAN_ONLY = [
 ]
 
 
-def warp_plan_args(c):
+def _warp_plan_args(c):
     if "tags" in c:
         return dict(w=c["w"], h=c["h"], n_frames=case_frames(c), cropped=BASE + c["skew"], cropped_stride=c["w"] * c["h"], hist=1)
     return dict(w=c["w"], h=c["h"], n_frames=c.get("n_frames", 1), cropped=c.get("cropped", BASE), cropped_stride=c.get("cropped_stride", c["w"] * c["h"]),
                 hist=c.get("hist", 1))
 
 
-def warp_selftest_line(c):
-    """The case as tests/native/host_selftest.cpp reads it: w h n_frames cropped cropped_stride hist"""
-    a = warp_plan_args(c)
-    return " ".join(str(a[k]) for k in ("w", "h", "n_frames", "cropped", "cropped_stride", "hist"))
+def selftest_plan(c):
+    """The warp launch plan of a case of WARP_CASES or WARP_PLAN_ONLY."""
+    return warp_plan(**_warp_plan_args(c))
+
+
+def selftest_families():
+    """warp_plan_make == warp_plan(), on every case of both lists.  The case as tests/native/host_selftest.cpp reads it: w h
+    n_frames cropped cropped_stride hist"""
+    def line(c):
+        a = _warp_plan_args(c)
+        return rig.joined(a[k] for k in ("w", "h", "n_frames", "cropped", "cropped_stride", "hist"))
+
+    return [rig.family("warp-plan", "warp plan: ", WARP_CASES + WARP_PLAN_ONLY, line, lambda c: _warp_fields(selftest_plan(c)), WARP_FIELDS)]
 
 
 # ---- what the warp kernel's lanes do --------------------------------------------------------------------------------------
