@@ -1,5 +1,6 @@
 // The stream bank's IMU (include/aof.h, "the stream bank's IMU"; mainloop.cpp:333-357 and 383-405), the ONE place its
-// arithmetic and its gates are written: k_bank_imu.hip runs the two steps per lane, aof_bank_imu_host per element.
+// arithmetic and its gates are written: k_bank_imu.hip runs the two steps per lane, aof_bank_imu_host per element; the
+// sequence pipeline's IMU call (k_sequence_imu.hip, aof_sequence_imu_host) runs the same two over a recording.
 // IEEE double throughout, every operation rounded on its own: nothing is contracted into a multiply-add, on either
 // side, and the division by 1e6 is a division.
 #pragma once
@@ -36,7 +37,10 @@ struct ImuFrame {
 
 // The record of a frame with time `t` (what the push wrote, `rec`, completed in place).  Returns true where the record
 // is sent: `f` then says what its frame carries, and the caller packs it.  A record with quality < 0 is left as it is.
-AOF_HD_INLINE bool imu_take(aof_imu_state &st, aof_tick_record &rec, uint64_t t, uint8_t first_seq, ImuFrame &f)
+// Record: the bank's aof_tick_record or the sequence pipeline's aof_seq_record -- the gate reads and writes `quality` and
+// writes the three gyro floats, which both have.
+template <typename Record>
+AOF_HD_INLINE bool imu_take(aof_imu_state &st, Record &rec, uint64_t t, uint8_t first_seq, ImuFrame &f)
 {
     if (rec.quality < 0) return false;   // held or idle: nothing is taken
     f.gx = st.gyro_x; f.gy = st.gyro_y; f.gz = st.gyro_z;

@@ -1,6 +1,6 @@
 // OPTICAL_FLOW_RAD, the ONE place the library writes it: the field mapping of mainloop.cpp:359-371 and the MAVLink 2
-// frame of mavlink_tcp.cpp:142-162, for the kernels (one lane per message: the sequence pipeline, k_sequence.hip; the
-// stream bank, k_bank.hip, k_bank_burst.hip, k_bank_imu.hip) and for the host twin aof_bank_imu_host alike.  All of
+// frame of mavlink_tcp.cpp:142-162, for the kernels (one lane per message: the sequence pipeline, k_sequence.hip and
+// k_sequence_imu.hip; the stream bank, k_bank.hip, k_bank_burst.hip, k_bank_imu.hip) and for the host twins alike.  All of
 // them write the bytes fillOpticalFlowRad + packOpticalFlowRad do.  Those (facade/src/optical_flow_rad.cpp) stay a
 // second implementation on purpose: the facade is a library that sees only include/, and it is the independent packer
 // the tests hold this one against.

@@ -26,8 +26,9 @@ int scratch_layout(const aof_params *p, int64_t n_frames, Scratch *s)
 {
     const size_t nodes = (size_t)n_frames + 1;
     size_t off = 0;
-    for (int b = 0; b < 2; b++) { s->jump[b] = off; off = align_up(off + nodes * 4, 256); }
-    for (int b = 0; b < 2; b++) { s->hops[b] = off; off = align_up(off + nodes * 4, 256); }
+    const size_t slot = limiter_slot_bytes(n_frames);   // (== align_up(nodes * 4, 256))
+    for (int b = 0; b < 2; b++) { s->jump[b] = off; off += slot; }
+    for (int b = 0; b < 2; b++) { s->hops[b] = off; off += slot; }
     s->rank = off;    off = align_up(off + nodes * 4, 256);
     s->reached = off; off = align_up(off + nodes, 256);
     aof_ws_layout L;

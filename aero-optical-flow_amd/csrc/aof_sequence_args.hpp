@@ -1,6 +1,7 @@
 // The sequence pipeline's output kernel: its arguments and launcher (aof_sequence.cpp, k_sequence.hip).
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 
 #include "aof.h"
@@ -35,5 +36,10 @@ inline int sequence_rounds(int64_t n_frames)   // smallest R with 4^R > n_frames
     return r;
 }
 int launch_sequence_output(const SequenceArgs &a, void *stream);
+
+// Where the limiter's four buffers lie inside aof_seq_layout.scratch: jump[0], jump[1], hops[0], hops[1], each (n_frames + 1)
+// words in a slot of this many bytes, from offset 0.  (The sequence IMU call, aof_sequence_imu.cpp, keeps its scan there once
+// k_sequence_emit has run.)
+inline size_t limiter_slot_bytes(int64_t n_frames) { return (((size_t)n_frames + 1) * 4 + 255) / 256 * 256; }
 
 }  // namespace aof

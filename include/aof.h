@@ -1276,6 +1276,12 @@ int aof_field_host(const aof_params *p, const aof_field_params *fp, const aof_bl
  * takes it over with a re-recorded surface -- then the text moves here. */
 #include "aof_bank_field.h"
 
+/* ---- the sequence pipeline's IMU: raw HIGHRES_IMU samples in, gyro sums and the send gates for a whole recording ----
+ * The sequence form of the stream bank's IMU call, enqueued behind a records-only sequence call on the same workspace: two
+ * calls and one record, declared with their normative text in aof_sequence_imu.h beside this file, which is part of this
+ * header and comes in with it.  A file of its own for the reason above: tests/sequence_imu_rig.py carries the binding. */
+#include "aof_sequence_imu.h"
+
 /* ---- measurement ----
  * With profiling on, every launch is bracketed by HIP events on the stream it
  * is launched on; the last AOF_PROFILE_RING launches of each kernel are kept.
