@@ -24,13 +24,15 @@ struct Scratch {   // offsets inside aof_seq_layout.scratch
 
 int scratch_layout(const aof_params *p, int64_t n_frames, Scratch *s)
 {
-    const size_t nodes = (size_t)n_frames + 1;
     size_t off = 0;
-    const size_t slot = limiter_slot_bytes(n_frames);   // (== align_up(nodes * 4, 256))
+    const size_t slot = limiter_slot_bytes(n_frames);   // (== align_up(nodes * 4, 256), nodes = n_frames + 1)
     for (int b = 0; b < 2; b++) { s->jump[b] = off; off += slot; }
     for (int b = 0; b < 2; b++) { s->hops[b] = off; off += slot; }
-    s->rank = off;    off = align_up(off + nodes * 4, 256);
-    s->reached = off; off = align_up(off + nodes, 256);
+    // (rank: nodes words, reached: nodes bytes, each rounded up to 256; the offsets stand in aof_sequence_args.hpp, for the
+    // calls behind this one that read the flow engine's workspace)
+    s->rank = limiter_rank_offset(n_frames);
+    s->reached = limiter_reached_offset(n_frames);
+    off = sequence_flow_ws_offset(n_frames);
     aof_ws_layout L;
     const int rc = aof_workspace_layout(p, n_frames > 1 ? n_frames - 1 : 0, &L);
     if (rc) return rc;

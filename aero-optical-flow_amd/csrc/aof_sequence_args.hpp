@@ -41,5 +41,14 @@ int launch_sequence_output(const SequenceArgs &a, void *stream);
 // words in a slot of this many bytes, from offset 0.  (The sequence IMU call, aof_sequence_imu.cpp, keeps its scan there once
 // k_sequence_emit has run.)
 inline size_t limiter_slot_bytes(int64_t n_frames) { return (((size_t)n_frames + 1) * 4 + 255) / 256 * 256; }
+// Behind them the limiter's rank ((n_frames + 1) words) and reached ((n_frames + 1) bytes), each rounded up to 256 bytes, then
+// the flow engine's workspace for n_frames - 1 pairs (aof_workspace_layout), where a sequence call leaves every pair's level-0
+// block records.  (The sequence field call, aof_sequence_field.cpp, reads them there.)
+inline size_t limiter_rank_offset(int64_t n_frames) { return 4 * limiter_slot_bytes(n_frames); }
+inline size_t limiter_reached_offset(int64_t n_frames) { return limiter_rank_offset(n_frames) + limiter_slot_bytes(n_frames); }
+inline size_t sequence_flow_ws_offset(int64_t n_frames)
+{
+    return limiter_reached_offset(n_frames) + ((size_t)n_frames + 1 + 255) / 256 * 256;
+}
 
 }  // namespace aof

@@ -1235,8 +1235,9 @@ int aof_bank_mavlink_rx_host(const aof_mavlink_rx_params *rp, const uint8_t *byt
  * its model is published and AOF_FIELD_REFIT set, else M1's.  If M1 does not fit the record is all zero except
  * `accepted` and `at_reach`.
  * The stream bank publishes the same fit per stream and limiter window ("the stream bank's motion field", below;
- * OpticalFlowBank::enableField).  Not here: the per-call path (aof_flow_pair_host, aof_stream_push_host), the sequence
- * pipeline and the per-call facade classes publish no field. */
+ * OpticalFlowBank::enableField), and the sequence pipeline per record of a recording ("the sequence pipeline's motion
+ * field", below).  Not here: the per-call path (aof_flow_pair_host, aof_stream_push_host) and the per-call facade classes
+ * publish no field. */
 typedef struct aof_field_params {
     int32_t min_blocks;     /* >= 3, default 8 */
     int32_t passes;         /* 1 | 2, default 2 */
@@ -1281,6 +1282,12 @@ int aof_field_host(const aof_params *p, const aof_field_params *fp, const aof_bl
  * calls and one record, declared with their normative text in aof_sequence_imu.h beside this file, which is part of this
  * header and comes in with it.  A file of its own for the reason above: tests/sequence_imu_rig.py carries the binding. */
 #include "aof_sequence_imu.h"
+
+/* ---- the sequence pipeline's motion field: zoom, rotation and centre flow per published message of a recording ----
+ * The sequence form of the stream bank's motion field, enqueued behind a sequence call on the same workspace: two calls over
+ * the records above, declared with their normative text in aof_sequence_field.h beside this file, which is part of this
+ * header and comes in with it.  A file of its own for the reason above: tests/sequence_field_rig.py carries the binding. */
+#include "aof_sequence_field.h"
 
 /* ---- measurement ----
  * With profiling on, every launch is bracketed by HIP events on the stream it
