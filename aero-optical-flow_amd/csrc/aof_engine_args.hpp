@@ -139,8 +139,8 @@ int launch_pyramid(const PyramidArgs &a, void *stream);   // zeroes a.sums first
 int launch_zero_words(uint32_t *words, int64_t count, void *stream);   // (a kernel: replays correctly from a hipGraph)
 int launch_coarse_fused(const CoarseArgs &a, void *stream);
 int launch_search_generic(const SearchArgs &a, void *stream);
-// K2b: half-pixel refinement of records written by an integer search (tile 8 or 16; today only
-// the 16x16 kernel needs it); fills a.subdirs.
+// K2b: half-pixel refinement of records written by an integer search (tile 8 or 16; today no
+// plan asks for it: every search kernel refines itself, k_refine.hip); fills a.subdirs.
 int launch_refine(const SearchArgs &a, void *stream);
 // Lane-per-block kernel straight from global memory for B=8, S=4 on ANY grid / width /
 // predictor (sparse PX4Flow grid, rows that are no multiple of 16 bytes), half-pixel refinement

@@ -1,8 +1,10 @@
 // K2b -- half-pixel refinement as a separate pass (DESIGN.md "Spec": Half-pixel refinement).
 //
-// Behind the searches that do not refine themselves: the generic wave-per-block kernel, and the
-// 16x16 kernel where its LDS tile with the two extra rows does not fit (k_search_tile16 refines
-// out of LDS otherwise, the 8x8 kernels in the search lane).  One lane per block, consecutive
+// Behind a 16x16 search that was given no place for the directions (plan_level, aof_batch_plan.hpp).
+// Every search kernel refines itself today -- the generic wave-per-block kernel out of its staged
+// window, k_search_tile16 out of its LDS tile, the 8x8 kernels in the search lane -- and batch_view()
+// always supplies a direction array (the caller's or the workspace's), so no call plans this pass:
+// it is kept, unlaunched (tests/test_batch_plan_ref.py).  One lane per block, consecutive
 // lanes = consecutive (pair, block) items: the lane reads its reference tile and the (B+2)^2
 // neighbourhood of its best match straight from global memory, rows as unaligned 8/16-byte
 // loads, and feeds them to the shared v_lerp_u8 arithmetic of aof_refine.hpp.  Blocks the

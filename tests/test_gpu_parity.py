@@ -778,7 +778,7 @@ CANARY = [
     dict(width=640, height=480),                                           # flat lane8, K3 / in-launch reduction
     dict(width=640, height=480, subpixel=1),                               # flat lane8 + refinement in the lane
     dict(width=160, height=130, pyramid_levels=2, mean_subtract=1, subpixel=1),
-    dict(width=320, height=240, tile=16, search=8, value_threshold=12000, subpixel=1),  # tile16 + K2b
+    dict(width=320, height=240, tile=16, search=8, value_threshold=12000, subpixel=1),  # tile16, refining out of its tile
     dict(px4=1, width=64, height=64),                                      # grouped lane8
     dict(width=188, height=120, subpixel=1),                               # flat lane8
     dict(width=100, height=90, search=3, subpixel=1),                      # generic

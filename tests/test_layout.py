@@ -1,6 +1,6 @@
 """The one rule of how the tests are laid out: a test module is nobody's library.  What several files share lives in a
 module that holds no tests (tests/bank_rig.py, tests/bank_cases.py, tests/mavlink_model.py, tests/sequence_ref.py,
-tests/npref.py, the *_ref.py models)."""
+tests/npref.py, the *_ref.py models, tests/generic_edges_ref.py: designed inputs and their census)."""
 import ast
 import glob
 import os
