@@ -1289,6 +1289,13 @@ int aof_field_host(const aof_params *p, const aof_field_params *fp, const aof_bl
  * header and comes in with it.  A file of its own for the reason above: tests/sequence_field_rig.py carries the binding. */
 #include "aof_sequence_field.h"
 
+/* ---- the sequence pipeline's MAVLink receive: a recorded connection's bytes in, HIGHRES_IMU samples out ----
+ * The sequence form of the stream bank's MAVLink receive, enqueued in front of aof_sequence_imu_device: the recorded bytes
+ * and the byte count at every frame become that call's samples and sample_end on the device.  Three functions and one
+ * record, declared with their normative text in aof_sequence_mavlink_rx.h beside this file, which is part of this header
+ * and comes in with it.  A file of its own for the reason above: tests/sequence_rx_rig.py carries the binding. */
+#include "aof_sequence_mavlink_rx.h"
+
 /* ---- measurement ----
  * With profiling on, every launch is bracketed by HIP events on the stream it
  * is launched on; the last AOF_PROFILE_RING launches of each kernel are kept.
