@@ -56,14 +56,18 @@ def in_progress(p):
 
 def model(log, byte_end, max_samples):
     """The call on a log (bytes) -> dict: samples SAMPLE_DTYPE [written], total (imu_samples), delivered (the position behind
-    each sample's last byte, all of them), sample_end uint32 [n], state (128 bytes), parser."""
+    each sample's last byte, all of them), sample_start (where each of those frames began), sample_end uint32 [n], state (128
+    bytes), parser."""
     log = bytes(log)
-    p, out, delivered = rx.Parser(), [], []
+    p, out, delivered, started, start = rx.Parser(), [], [], [], 0
     for i in range(len(log)):
-        before = p.c["imu_samples"]
+        before, idle = p.c["imu_samples"], p.phase == "idle"
         p.feed(log[i:i + 1], max_samples, out)
+        if idle and p.phase != "idle":
+            start = i
         if p.c["imu_samples"] != before:
             delivered.append(i + 1)
+            started.append(start)
     samples = np.zeros(len(out), SAMPLE_DTYPE)
     for j, (t, x, y, z) in enumerate(out):
         samples[j]["time_usec"] = t
@@ -74,7 +78,7 @@ def model(log, byte_end, max_samples):
     state = np.zeros(1, STATE_DTYPE)
     for n in rx.COUNTERS:
         state[n] = p.c[n]
-    return dict(samples=samples, total=p.c["imu_samples"], delivered=d, sample_end=sample_end,
+    return dict(samples=samples, total=p.c["imu_samples"], delivered=d, sample_start=np.array(started, np.int64), sample_end=sample_end,
                 state=state.tobytes()[:32] + in_progress(p), parser=p)
 
 
@@ -111,12 +115,16 @@ def reached(log):
 def exit_table(log, c):
     """Chunk c's table: for entry offset o < TABLE the offset at which the chain enters chunk c + 1, or END."""
     N, base, table = len(log), c * C, []
+    stop, leaves = min(base + C, N), {}          # leaves: position of the chunk -> where the chain from it leaves the chunk, or END
     for o in range(TABLE):
-        p = base + o
-        while p < min(base + C, N):
+        p, path = base + o, []
+        while p != END and p < stop and p not in leaves:
+            path.append(p)
             p = successor(log, p)
-            if p == END:
-                break
+        if p != END and p < stop:
+            p = leaves[p]
+        for q in path:
+            leaves[q] = p
         table.append(END if p == END else min(max(p - base - C, 0), TABLE - 1))
     return table
 
@@ -424,4 +432,309 @@ def _content(log, frames_at):
                 got.add("other message len 0")
             if ln == 255:
                 got.add("other message len 255")
+    return got
+
+
+# ---- the deep family: more than one trip of a workgroup's lanes, full lists, more than one scan group ---------------------------
+FREE = 1 << 30            # a capacity no log of the family reaches
+GROUP = 256               # chunks per workgroup of a scan level (kSeqRxThreads)
+LIST = 512                # kSeqRxChunkSamples
+
+
+def capped(free, N, byte_end, M):
+    """The result at capacity M from the result of the same N bytes without a cap.  The header's rule is one cap for the log: sample j
+    is kept iff j < M, the others are counted in `overflowed`, sample_end is clipped to M, and nothing else depends on M."""
+    q = np.minimum(np.asarray(byte_end, np.int64), N)
+    sample_end = np.minimum(np.searchsorted(free["delivered"], q, side="right"), M).astype(np.uint32)
+    state = np.frombuffer(free["state"], STATE_DTYPE).copy()
+    state["overflowed"] = max(0, free["total"] - M)
+    return dict(free, samples=free["samples"][:M], sample_end=sample_end, state=state.tobytes())
+
+
+@functools.lru_cache(maxsize=None)
+def _free(log):
+    return model(log, [], FREE)
+
+
+def tiled_expectation(tile, N, byte_end, M):
+    """The TILE RULE: what model(log, byte_end, M) gives for log = the tile repeated and cut at N, without walking the log.  The tile
+    is whole frames, so the machine is idle at both of its ends (asserted) and every repeat is parsed as the first one was: with
+    m = the model of one tile, J = N // T whole tiles and the model of the cut one behind them, every counter is J times m's plus the
+    cut one's, the deliveries and the samples are m's at j * T for every j and then the cut one's, and the state in progress is the cut
+    one's.  tests/test_sequence_rx_ref.py holds the rule to the sequential model on a log of three tiles and a cut."""
+    tile = bytes(tile)
+    T = len(tile)
+    J, r = divmod(N, T)
+    m, t = _free(tile), _free(tile[:r])
+    assert m["parser"].phase == "idle", "a tile is whole frames"
+    at = np.arange(J, dtype=np.int64)[:, None] * T
+    every = lambda key: np.concatenate([(at + m[key][None, :]).reshape(-1), J * T + t[key]])
+    whole, state = np.frombuffer(m["state"], STATE_DTYPE), np.frombuffer(t["state"], STATE_DTYPE).copy()
+    for n in rx.COUNTERS:
+        state[n] = J * int(whole[n][0]) + int(state[n][0])
+    free = dict(samples=np.concatenate([np.tile(m["samples"], J), t["samples"]]), total=J * m["total"] + t["total"],
+                delivered=every("delivered"), sample_start=every("sample_start"), state=state.tobytes(), parser=t["parser"])
+    return capped(free, N, byte_end, M)
+
+
+def tiled_log(tile, N):
+    """The tile repeated and cut at N, as a uint8 array."""
+    t = np.frombuffer(bytes(tile), np.uint8)
+    return np.tile(t, N // len(t) + 1)[:N]
+
+
+def _odd(rng, tile):
+    """(an odd tile meets the chunk grid at another phase every time)"""
+    return tile if len(tile) % 2 else tile + rx.junk(rng, 1)
+
+
+def sparse_tile(rng, n_bytes):
+    """About n_bytes of whole frames: MAVLink 2 frames of other messages with 200 to 255 payload bytes, a HIGHRES_IMU frame about
+    every 2 KiB, one frame with a bad check, one start with an incompat flag the parser cannot size, a few junk bytes; odd."""
+    parts, size, due, k = [], 0, 0, 0
+    while size < n_bytes:
+        if k == 3:
+            f = rx.frame_v2(rx.HIGHRES_IMU, imu(5), seq=5, bad=True)
+        elif k == 7:
+            f = rx.frame_v2(rx.HIGHRES_IMU, imu(3), incompat=2) + rx.junk(rng, 5)
+        elif size >= due:
+            f = rx.frame_v2(rx.HIGHRES_IMU, imu(k), seq=k & 255)
+            due += 2048
+        else:
+            f = rx.frame_v2(int(rng.choice([0, 30, 33, 74])), rng.integers(0, 256, int(rng.integers(200, 256)), dtype=np.uint8).tobytes(),
+                            seq=k & 255, truncate=False)
+        parts.append(f)
+        size += len(f)
+        k += 1
+    return _odd(rng, b"".join(parts))
+
+
+@functools.lru_cache(maxsize=None)
+def _short(seq):
+    return rx.frame_v1(rx.HIGHRES_IMU, b"", seq=seq)
+
+
+def dense(first, n):
+    """n HIGHRES_IMU frames of len 0, 8 bytes each, back to back: each delivers a sample of zeros."""
+    return b"".join(_short(i & 255) for i in range(first, first + n))
+
+
+def _seam_frames():
+    rng = np.random.default_rng(99)
+    longest = rx.frame_v2(rx.HIGHRES_IMU, imu(9) + bytes(rng.integers(1, 256, 255 - 62, dtype=np.uint8)), truncate=False, signature=SIG)
+    assert len(longest) == FRAME_MAX
+    return (("v2 sample", rx.frame_v2(rx.HIGHRES_IMU, imu(7), seq=7)), ("longest frame", longest), ("v1 sample", rx.frame_v1(rx.HIGHRES_IMU, imu(0))))
+
+
+def _one_chunk_of(n):
+    def build(rng):
+        head = healthy(rng, C - 400)
+        assert len(head) <= C
+        return head + rx.junk(rng, C - len(head)) + dense(0, n) + rx.junk(rng, C - 8 * n) + healthy(rng, C, start=700)
+    return build
+
+
+def _chunks_of_healthy(chunks):
+    n = chunks * C - 11 * (chunks % 3)
+    if chunks * C <= 1 << 20 or chunks == 257:       # the sequential model is the expectation up to about 1 MiB
+        return lambda rng: healthy(rng, chunks * C)[:n]
+    return lambda rng: (_odd(rng, healthy(rng, 6 * C + 1000)), n)
+
+
+@functools.lru_cache(maxsize=None)
+def _deep_specs():
+    """name -> (claimed edges, build(rng) -> the log's bytes or (tile, N), capacity rule, byte_end rule); nothing is built here."""
+    out = {}
+
+    def add(name, edges, build, cap="total+1", ends="every"):
+        assert name not in out
+        out[name] = (set(edges), build, cap, ends)
+    every = "byte_end at every delivery"
+    add("512 per chunk, aligned", {"512 samples start in one chunk", "two full lists side by side", every, "byte_end in no order",
+                                   "byte_end = c*C with a delivery at c*C", "3 chunks"}, lambda rng: dense(0, 1027), ends="every, shuffled")
+    add("512 per chunk, last one crosses the seam",
+        {"full list and a delivery behind the seam", every, "byte_end between a seam and a delivery behind it of a frame that began in front of it"},
+        lambda rng: rx.junk(rng, 5) + dense(0, 1027))
+    add("256 in a chunk", {"samples of a chunk = one trip", every}, _one_chunk_of(256))
+    add("257 in a chunk", {"samples of a chunk = one trip + 1", every}, _one_chunk_of(257))
+    add("full chunk between empty ones", {"count 0 next to count 512", every}, lambda rng: bytes(C) + dense(0, LIST) + bytes(C) + dense(LIST, LIST))
+    for cap, edge in ((256, "capacity = one trip"), (257, "capacity ends inside the second trip"), (511, "capacity ends inside the second trip"),
+                      (512, "capacity = one full list"), (513, "capacity one past a full list"), (512 + 300, "capacity ends inside the second trip"),
+                      ("total-1", None)):
+        add(f"512 per chunk, max_samples {cap}", {every} | ({edge} if edge else set()), lambda rng: dense(0, 1027), cap=cap)
+    between = "byte_end between a seam and a delivery behind it of a frame that began in front of it"
+    behind = {0: {"a frame from in front of a seam delivered at it", "byte_end = c*C with a delivery at c*C"},
+              1: {"a frame from in front of a seam delivered one behind it", between}, 279: {"a delivery 279 behind a seam"}}
+    for what, frame in _seam_frames():
+        for seam in (1, 2):
+            for off in (0, 1, 279):
+                edges = behind[off] | {every} | ({"a frame from in front of a seam delivered 279 behind it", between} if len(frame) == FRAME_MAX and off == 279 else set())
+                add(f"{what} delivered at {seam if seam > 1 else ''}C+{off}", edges,
+                    lambda rng, frame=frame, at=seam * C + off - len(frame): placed(rng, frame, at))
+    add("N cuts a frame that began in the chunk in front", {"entry END for a chunk with bytes in front of N", "state in progress with pos >= 100", every},
+        lambda rng: placed(rng, _seam_frames()[1][1], C - 1)[:C + 100])
+    second, sums1 = "a chunk with samples in the second group", "sample_end read through sums[1]"
+    add("256 chunks", {"256 chunks"}, _chunks_of_healthy(256), ends="groups")
+    add("257 chunks", {"257 chunks", "two scan levels", second}, _chunks_of_healthy(257), ends="groups")
+    add("512 chunks", {"512 chunks", "two scan levels", second, sums1}, _chunks_of_healthy(512), ends="groups")
+    add("513 chunks", {"513 chunks", "two scan levels", second, sums1, "a chunk with samples in the third group"}, _chunks_of_healthy(513), ends="groups")
+    return out
+
+
+# the largest, on one buffer: three scan levels and 17 entry rounds; two levels with every group full and 16 rounds; and one chunk
+# more than the first, since the last pass reads the scan at the chunk IN FRONT of byte_end's: with 65 537 chunks (as with 257) only
+# the pack pass reads the second entry of the top level
+BIG = {"65537 chunks less 1234 bytes": (65537 * C - 1234, {"three scan levels", "a chunk with samples behind 65536 chunks", "17 entry rounds", "65537 chunks"}),
+       "65536 chunks": (65536 * C, {"two scan levels", "16 entry rounds, every group full", "65536 chunks"}),
+       "65538 chunks less 1234 bytes": (65538 * C - 1234, {"three scan levels", "sample_end read through sums[2]", "17 entry rounds", "65538 chunks"})}
+
+
+def deep_names():
+    return list(_deep_specs())
+
+
+@functools.lru_cache(maxsize=1)
+def big_log():
+    """(the tile, the tile repeated up to the larger of the two N)."""
+    tile = sparse_tile(np.random.default_rng(65537), 7 * C)
+    return tile, tiled_log(tile, max(n for n, _ in BIG.values()))
+
+
+def _deep_ends(rule, N, delivered, rng, span):
+    d = np.asarray(delivered, np.int64)
+    if rule.startswith("every"):           # every delivery, the position in front of it and the one behind it; the ends; every seam
+        vals = np.concatenate([d - 1, d, d + 1, [0, N, N + 5], np.arange(0, N + 1, C)])
+        vals = rng.permutation(vals) if rule.endswith("shuffled") else np.sort(vals)
+        return vals.astype(np.uint32)
+    # "groups": spread over the log; around every multiple of `span` bytes, a chunk behind it (from there on the last pass reads the
+    # scan of the chunk in front through the next group's entry), and around the first delivery behind each of those
+    marks = np.array([g * span + at + k for g in range(N // span + 1) for at in (0, C) for k in (-1, 0, 1)], np.int64)
+    marks = marks[marks >= 0]
+    i = np.searchsorted(d, marks, side="right")
+    nxt = d[i[i < len(d)]]
+    n_lin = 600 - 2 * len(marks) if span > GROUP * C else 300 - 2 * len(marks)
+    return np.concatenate([np.linspace(0, N + 3, n_lin).astype(np.int64), marks, nxt - 1, nxt, nxt + 1]).astype(np.uint32)
+
+
+@functools.lru_cache(maxsize=None)
+def deep_case(name):
+    """One case of the deep family, in the shape of cases()'s: name, log, byte_end, max_samples, claimed, want -- the sequential
+    model's result where the log is small, tiled_expectation's elsewhere (want["tiled"])."""
+    import zlib
+    rng = np.random.default_rng(zlib.crc32(name.encode()))
+    if name in BIG:
+        N, claimed = BIG[name]
+        tile, log = big_log()
+        built, log, cap, ends, span = (tile, N), log[:N], "total+1", "groups", GROUP * GROUP * C
+    else:
+        claimed, build, cap, ends = _deep_specs()[name]
+        built, span = build(rng), GROUP * C
+        log = tiled_log(*built) if isinstance(built, tuple) else np.frombuffer(built, np.uint8).copy()
+    tiled = isinstance(built, tuple)
+    free = tiled_expectation(built[0], built[1], [], FREE) if tiled else model(built, [], FREE)
+    total, N = free["total"], len(log)
+    M = max(1, {"total-1": total - 1, "total+1": total + 1}.get(cap, cap))
+    byte_end = _deep_ends(ends, N, free["delivered"], rng, span)
+    return dict(name=name, log=log, byte_end=byte_end, max_samples=M, claimed=claimed, want=capped(free, N, byte_end, M),
+                tile=built[0] if tiled else None)
+
+
+def deep_cases():
+    """The deep family up to 513 chunks (the two of BIG are built by name: deep_case(name))."""
+    return [deep_case(name) for name in deep_names()]
+
+
+DEEP_EDGES = (["512 samples start in one chunk", "two full lists side by side", "full list and a delivery behind the seam",
+               "samples of a chunk = one trip", "samples of a chunk = one trip + 1", "count 0 next to count 512", "capacity = one trip",
+               "capacity ends inside the second trip", "capacity = one full list", "capacity one past a full list", "byte_end at every delivery",
+               "byte_end between a seam and a delivery behind it of a frame that began in front of it", "byte_end = c*C with a delivery at c*C",
+               "byte_end in no order", "a frame from in front of a seam delivered at it", "a frame from in front of a seam delivered one behind it",
+               "a frame from in front of a seam delivered 279 behind it", "a delivery 279 behind a seam",
+               "entry END for a chunk with bytes in front of N", "state in progress with pos >= 100", "two scan levels",
+               "a chunk with samples in the second group", "a chunk with samples in the third group", "sample_end read through sums[1]",
+               "three scan levels", "a chunk with samples behind 65536 chunks", "sample_end read through sums[2]", "17 entry rounds",
+               "16 entry rounds, every group full"] + [f"{c} chunks" for c in (3, 256, 257, 512, 513, 65536, 65537, 65538)])
+
+
+def deep_census(case):
+    """The edges a deep case reaches, found on its expectation (where every sample's frame starts and is delivered, the state in
+    progress) and the plan, not taken from its name."""
+    N, want, M = len(case["log"]), case["want"], case["max_samples"]
+    P = plan(N)
+    chunks, levels = P["chunks"], len(P["scan_entries"])
+    d, s, total = want["delivered"], want["sample_start"], want["total"]
+    counts = np.bincount(s // C, minlength=chunks)          # samples whose frames start in chunk c: the kernels' count[c]
+    first = np.concatenate([[0], np.cumsum(counts)])        # and in front of chunk c: the scan
+    be = case["byte_end"].astype(np.int64)
+    got = {f"{chunks} chunks"}
+    full, none = counts == LIST, counts == 0
+    assert counts.max() <= LIST
+    if full.any():
+        got.add("512 samples start in one chunk")
+    if (full[:-1] & full[1:]).any():
+        got.add("two full lists side by side")
+    if (none[:-1] & full[1:]).any() and (full[:-1] & none[1:]).any():
+        got.add("count 0 next to count 512")
+    if (counts == GROUP).any():
+        got.add("samples of a chunk = one trip")
+    if (counts == GROUP + 1).any():
+        got.add("samples of a chunk = one trip + 1")
+    if any(d[first[c + 1] - 1] > (c + 1) * C for c in np.flatnonzero(full)):
+        got.add("full list and a delivery behind the seam")
+    if M < total:
+        c = int(np.searchsorted(first, M, side="right")) - 1       # the chunk of the first sample that is not kept
+        j = M - int(first[c])                                      # and its place in that chunk's list
+        if j > GROUP:
+            got.add("capacity ends inside the second trip")
+        if j == GROUP:
+            got.add("capacity = one trip")
+        if j == 0 and c > 0 and full[c - 1]:
+            got.add("capacity = one full list")
+        if j == 1 and c > 0 and full[c - 1]:
+            got.add("capacity one past a full list")
+    ends = set(be.tolist())
+    if len(d) and all(v in ends for v in np.concatenate([d - 1, d, d + 1]).tolist()):
+        got.add("byte_end at every delivery")
+    if len(be) > 2 and (np.diff(be) < 0).any():
+        got.add("byte_end in no order")
+    seam = (s // C + 1) * C                                  # the seam behind each sample's start
+    ordered = np.sort(be)
+    i = np.searchsorted(ordered, seam)                       # the first byte_end at or behind that seam: in front of the delivery?
+    if (ordered[np.minimum(i, len(ordered) - 1)] < d)[i < len(ordered)].any():
+        got.add("byte_end between a seam and a delivery behind it of a frame that began in front of it")
+    if any(int(v) in ends for v in d[d % C == 0]):
+        got.add("byte_end = c*C with a delivery at c*C")
+    for off, edge in ((0, "at it"), (1, "one behind it"), (279, "279 behind it")):
+        if (d - seam == off).any():
+            got.add("a frame from in front of a seam delivered " + edge)
+    if (d % C == 279).any():
+        got.add("a delivery 279 behind a seam")
+    rest = np.frombuffer(want["state"][32:], IN_PROGRESS)[0]
+    if rest["start"]:
+        cut = N - int(rest["pos"]) - 1                        # where the frame that N cuts began (pos: the bytes behind its start byte)
+        if cut // C < (N - 1) // C:
+            got.add("entry END for a chunk with bytes in front of N")
+        if rest["pos"] >= 100:
+            got.add("state in progress with pos >= 100")
+    got |= {2: {"two scan levels"}, 3: {"three scan levels"}}.get(levels, set())
+    if P["rounds"] == 17:
+        got.add("17 entry rounds")
+    if P["rounds"] == 16 and chunks == GROUP * GROUP:
+        got.add("16 entry rounds, every group full")
+    if levels > 1:
+        groups = np.add.reduceat(counts, np.arange(0, chunks, GROUP))
+        assert (groups[:chunks // GROUP] > 0).all(), "every full group holds samples: a dropped group term would go unseen otherwise"
+        q = np.minimum(be, N)
+        c0 = np.maximum(np.minimum(q // C, chunks - 1) - 1, 0)          # the first of the two chunks the last pass searches
+        unclipped = want["sample_end"] < M
+        if counts[GROUP:2 * GROUP].any():
+            got.add("a chunk with samples in the second group")
+        if counts[2 * GROUP:3 * GROUP].any():
+            got.add("a chunk with samples in the third group")
+        if ((c0 >= GROUP) & unclipped).any():
+            got.add("sample_end read through sums[1]")
+        if levels > 2 and counts[GROUP * GROUP:].any():
+            got.add("a chunk with samples behind 65536 chunks")
+        if levels > 2 and ((c0 >= GROUP * GROUP) & unclipped).any():
+            got.add("sample_end read through sums[2]")
     return got

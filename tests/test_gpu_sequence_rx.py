@@ -5,7 +5,10 @@ every size, seam, chain, chunk count, capacity, byte_end and frame count edge); 
 aof_sequence_device and aof_sequence_imu_device against the same chain fed the host function's arrays; from a captured graph
 replayed on other bytes; and the refusals.  A byte_end in no order, with values far above N, is one of the family's cases: the
 kernels clamp it (k_seq_rx_sample_end: q = min(byte_end, N), the chunk index below the chunk count, the list length to 512),
-and each k is compared with the host all the same.  No tolerance anywhere."""
+and each k is compared with the host all the same.  The DEEP family (sequence_rx_ref.deep_cases) holds the same call where a chunk
+fills its list of 512, a workgroup's lanes take a second trip, the scan has two levels and a graph nine entry rounds; three logs of
+268 MB on one upload hold three scan levels and 17 rounds, against the host function and against the tile rule.  No tolerance
+anywhere."""
 import ctypes as C
 
 import numpy as np
@@ -19,6 +22,7 @@ from bank_rig import FILL, GUARD, Guarded, time_limit   # noqa: F401  (time_limi
 pytestmark = pytest.mark.gpu
 
 CASES = ref.cases()
+DEEP = ref.deep_names()
 FX, FY = 216.6677, 216.2457
 
 
@@ -33,12 +37,14 @@ def small(aof, gpu_device):
 
 class Rx:
     """The device buffers of one call shape (N bytes, n frames, max_samples slots): the log with decoy start bytes behind N up
-    to the next multiple of 16, guarded outputs, and the scratch at its exact size between guard bytes."""
+    to the next multiple of 16, guarded outputs, and the scratch at its exact size between guard bytes.  log: the loaded log
+    buffer of another Rx whose first N bytes this one reads (arm() in place of load())."""
 
-    def __init__(self, aof, eng, gpu_device, N, n, max_samples):
+    def __init__(self, aof, eng, gpu_device, N, n, max_samples, log=None):
         import torch
         self.aof, self.eng, self.dev, self.torch, self.N, self.n, self.M = aof, eng, gpu_device, torch, N, n, max_samples
-        self.log = torch.full((max((N + 15) // 16 * 16, 16),), 0xFD, dtype=torch.uint8, device=gpu_device)
+        self.log = torch.full((max((N + 15) // 16 * 16, 16),), 0xFD, dtype=torch.uint8, device=gpu_device) if log is None else log
+        assert self.log.numel() >= N
         self.byte_end = torch.zeros(max(n, 1), dtype=torch.int32, device=gpu_device)
         self.samples = Guarded(gpu_device, (max_samples, 24))
         self.sample_end = Guarded(gpu_device, (max(n, 1), 4))
@@ -51,10 +57,16 @@ class Rx:
 
     def load(self, log, byte_end):
         torch = self.torch
-        assert len(log) == self.N and len(byte_end) == self.n
+        assert len(log) == self.N
         self.log.fill_(0xFD)
         if self.N:
             self.log[:self.N].copy_(rig.up(torch, log, self.dev))
+        self.arm(byte_end)
+
+    def arm(self, byte_end):
+        """byte_end up, every output refilled."""
+        torch = self.torch
+        assert len(byte_end) == self.n
         if self.n:
             self.byte_end.copy_(rig.up(torch, np.asarray(byte_end, np.uint32), self.dev).view(torch.int32))
         for g in (self.samples, self.sample_end, self.state):
@@ -93,6 +105,49 @@ def test_the_device_call_equals_the_host_function(aof, small, gpu_device, case):
     rx.same_as_host(case["log"], case["byte_end"], case["name"])
 
 
+@pytest.mark.parametrize("name", DEEP)
+def test_the_device_call_equals_the_host_function_on_the_deep_family(aof, small, gpu_device, name):
+    eng, _ = small
+    case = ref.deep_case(name)
+    rx = Rx(aof, eng, gpu_device, len(case["log"]), len(case["byte_end"]), case["max_samples"])
+    rx.load(case["log"], case["byte_end"])
+    assert rx.run() == 0
+    rx.same_as_host(case["log"], case["byte_end"], name)
+
+
+def same_as_expected(rx, want, what):
+    """The outputs of a call against an expectation of the reference module (the sentinels are same_as_host's business)."""
+    written = len(want["samples"])
+    assert written == min(want["total"], rx.M)
+    assert rx.samples.read(used=written * 24).tobytes() == want["samples"].tobytes(), (what, "samples")
+    assert rx.sample_end.read(used=rx.n * 4).tobytes() == want["sample_end"].tobytes(), (what, "sample_end")
+    assert rx.state.read().tobytes() == want["state"], (what, "state")
+
+
+def test_three_scan_levels_equal_the_host_function(aof, small, gpu_device):
+    """One upload of 268 MB; N = 65 537 C - 1 234 (three levels, 17 rounds, the last chunk alone in the top level's second entry),
+    N = 65 536 C (two levels, every group full, 16 rounds) and N = 65 538 C - 1 234 (the last pass reads the top level's second
+    entry) on its first bytes, each with outputs and a scratch of its own that no call wrote before.  Wall time: LAB_LOG.md."""
+    import torch
+    eng, _ = small
+    names = list(ref.BIG)
+    cases = [ref.deep_case(name) for name in names]
+    whole = max(cases, key=lambda c: len(c["log"]))
+    first = Rx(aof, eng, gpu_device, len(whole["log"]), len(whole["byte_end"]), whole["max_samples"])
+    first.load(whole["log"], whole["byte_end"])
+    for name, case in zip(names, cases):
+        rx = first if case is whole else Rx(aof, eng, gpu_device, len(case["log"]), len(case["byte_end"]), case["max_samples"], log=first.log)
+        rx.arm(case["byte_end"])
+        assert rx.run() == 0
+        rx.same_as_host(case["log"], case["byte_end"], name)
+        same_as_expected(rx, case["want"], name)
+        if rx is not first:
+            del rx
+            torch.cuda.empty_cache()
+    del first
+    torch.cuda.empty_cache()
+
+
 def test_without_a_state_only_samples_and_sample_end_are_written(aof, small, gpu_device):
     eng, _ = small
     case = next(c for c in CASES if c["name"] == "3 chunks")
@@ -110,6 +165,29 @@ def test_one_captured_graph_replayed_twice_on_other_bytes(aof, small, gpu_device
     logs = [ref.mixed(rng, N), ref.healthy(rng, N + 300)[:N]]
     ends = [np.sort(rng.integers(0, N + 50, 70)).astype(np.uint32), np.linspace(0, N, 70).astype(np.uint32)]
     rx = Rx(aof, eng, gpu_device, N, 70, 40)
+    rx.load(logs[0], ends[0])
+    assert rx.run() == 0                      # (eager once: everything the launches need exists before the capture)
+    rx.same_as_host(logs[0], ends[0], "eager")
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        assert rx.run() == 0
+    for i in (1, 0):
+        rx.load(logs[i], ends[i])
+        rx.scratch.fill_(FILL)
+        g.replay()
+        rx.same_as_host(logs[i], ends[i], ("replay", i))
+
+
+def test_one_captured_graph_of_nine_entry_rounds_and_two_scan_levels_replayed_on_other_bytes(aof, small, gpu_device):
+    import torch
+    eng, _ = small
+    case = ref.deep_case("257 chunks")
+    N, n, M = len(case["log"]), len(case["byte_end"]), case["max_samples"]
+    assert ref.plan(N)["rounds"] == 9 and len(ref.plan(N)["scan_entries"]) == 2
+    other = np.frombuffer(ref.healthy(np.random.default_rng(12), N + 300, start=3)[:N], np.uint8)
+    logs, ends = [case["log"], other], [case["byte_end"], case["byte_end"][::-1].copy()]
+    rx = Rx(aof, eng, gpu_device, N, n, M)
     rx.load(logs[0], ends[0])
     assert rx.run() == 0                      # (eager once: everything the launches need exists before the capture)
     rx.same_as_host(logs[0], ends[0], "eager")

@@ -1,7 +1,9 @@
 """aof_sequence_mavlink_rx_host (include/aof_sequence_mavlink_rx.h) against the sequential model of tests/sequence_rx_ref.py,
 byte for byte, on the family of designed logs; the closed form the kernels compute against the same model; the host function
 against aof_bank_mavlink_rx_host fed the log in rounds; the census of the family; the refusals; and the scratch size against
-the plan's model.  CPU only."""
+the plan's model; and the same on the DEEP family (sequence_rx_ref.deep_cases: full lists, a second trip of a workgroup's lanes, two
+and three scan levels, byte_end at every delivery), whose largest logs take their expectation from the tile rule, held to the
+sequential model here.  CPU only."""
 import ctypes as C
 
 import numpy as np
@@ -12,6 +14,7 @@ import sequence_rx_rig as rig
 
 CASES = ref.cases()
 IDS = [c["name"] for c in CASES]
+DEEP, BIG = ref.deep_names(), list(ref.BIG)
 BURST_MAX, SLOTS_MAX, ROUND_BYTES = 16, 16, 4096
 
 
@@ -136,3 +139,89 @@ def test_the_scratch_size_is_the_plans(aof):
     big = ref.plan((1 << 31) - 1)
     assert big["chunks"] == 1 << 19 and big["rounds"] == 19 and big["scan_entries"] == [1 << 19, 2048, 8]
     assert ref.plan(20_000_000)["total_bytes"] < 0.30 * 20_000_000, "two tables of 288 u16 per chunk: about 28 % of N"
+
+
+# ---- the deep family ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", DEEP)
+def test_the_closed_form_reaches_what_the_expectation_holds_on_the_deep_family(name):
+    case = ref.deep_case(name)
+    log, want = bytes(case["log"]), case["want"]
+    counters = np.frombuffer(want["state"], ref.STATE_DTYPE)[0]
+    starts, cut = ref.reached(log)
+    frames = [s for s in starts if log[s] in (0xFD, 0xFE)]
+    assert counters["bytes"] == len(log)
+    assert len(starts) - len(frames) == counters["skipped"]
+    assert len(frames) == counters["frames"] + counters["rejected_flags"] + (cut is not None)
+    assert (cut is not None) == (want["parser"].phase != "idle")
+    assert set(want["sample_start"].tolist()) <= set(frames), "every sample's frame starts at a reached position"
+    entry = ref.entry_chain(log)
+    assert entry == ref.entry_chain_serial(log)
+    assert all(e == ref.END or e < ref.FRAME_MAX for e in entry)
+    assert len(entry) == ref.plan(len(log))["chunks"]
+
+
+def host_equals(aof, case):
+    want, M = case["want"], case["max_samples"]
+    samples, sample_end, state = rig.run_host(aof, case["log"], case["byte_end"], M, ref.SENTINEL)
+    written = len(want["samples"])
+    assert written == min(want["total"], M)
+    assert samples[:written].tobytes() == want["samples"].tobytes()
+    assert (samples[written:] == ref.SENTINEL).all(), "slots behind the written samples are not written"
+    assert sample_end.tobytes() == want["sample_end"].tobytes()
+    assert state.tobytes() == want["state"]
+    overflowed = np.frombuffer(state.tobytes(), ref.STATE_DTYPE)["overflowed"][0]
+    assert overflowed == max(0, want["total"] - M)
+
+
+@pytest.mark.parametrize("name", DEEP)
+def test_the_host_function_equals_the_expectation_on_the_deep_family(aof, name):
+    host_equals(aof, ref.deep_case(name))
+
+
+@pytest.mark.parametrize("name", BIG)
+def test_the_host_function_equals_the_tile_rule_on_the_largest_logs(aof, name):
+    case = ref.deep_case(name)
+    assert case["tile"] is not None and len(case["tile"]) % 2 == 1 and 6 * ref.C <= len(case["tile"]) <= 8 * ref.C
+    assert case["want"]["total"] > 120_000 and 580 <= len(case["byte_end"]) <= 640
+    host_equals(aof, case)
+
+
+def test_the_tile_rule_equals_the_sequential_model():
+    """Three tiles and a cut, about 100 KB, at a capacity below the total, for both kinds of tile; with it capped() is held too."""
+    rng = np.random.default_rng(3)
+    for tile in (ref.big_log()[0], ref.deep_case("513 chunks")["tile"]):
+        T = len(tile)
+        assert T % 2 == 1
+        for N in (3 * T + 5000, 3 * T, 2 * T + 1, T - 1):
+            byte_end = np.concatenate([rng.integers(0, N + 9, 200), [0, N, T, 2 * T, 3 * T]]).astype(np.uint32)
+            want = ref.model(ref.tiled_log(tile, N).tobytes(), byte_end, 1 << 30)
+            for M in (want["total"] + 1, want["total"] - 3):
+                want = ref.model(ref.tiled_log(tile, N).tobytes(), byte_end, M) if M < want["total"] else want
+                got = ref.tiled_expectation(tile, N, byte_end, M)
+                for key in ("samples", "delivered", "sample_start", "sample_end"):
+                    assert got[key].tobytes() == want[key].tobytes() and got[key].dtype == want[key].dtype, (N, M, key)
+                assert got["total"] == want["total"] and got["state"] == want["state"], (N, M)
+
+
+def test_every_deep_edge_is_reached():
+    reached = set()
+    for name in DEEP + BIG:
+        case = ref.deep_case(name)
+        got = ref.deep_census(case)
+        assert case["claimed"] <= got, (name, sorted(case["claimed"] - got))
+        reached |= got
+    missing = [e for e in ref.DEEP_EDGES if e not in reached]
+    assert not missing, missing
+    assert [c["name"] for c in ref.deep_cases()] == DEEP and len(ref.cases()) == 58
+
+
+def test_the_scratch_size_is_the_plans_at_the_deep_chunk_counts(aof):
+    shapes = {"256 chunks": (8, [256]), "257 chunks": (9, [257, 2]), "512 chunks": (9, [512, 2]), "513 chunks": (10, [513, 3]),
+              "65536 chunks": (16, [65536, 256]), "65537 chunks less 1234 bytes": (17, [65537, 257, 2]),
+              "65538 chunks less 1234 bytes": (17, [65538, 257, 2])}
+    for name, (rounds, scan) in shapes.items():
+        n = ref.BIG[name][0] if name in ref.BIG else len(ref.deep_case(name)["log"])
+        P = ref.plan(n)
+        assert rig.scratch_bytes(aof, n) == P["total_bytes"], name
+        assert (P["rounds"], P["scan_entries"]) == (rounds, scan), name
+    assert ref.plan(ref.BIG["65537 chunks less 1234 bytes"][0])["total_bytes"] < 0.29 * 65537 * ref.C
